@@ -15,6 +15,12 @@ process, as the reference's caller is (one Julia process calling posterior(fx, y
 N GPUs by itself; under the launcher (torch.distributed.run, N ranks) rank 0 drives the N devices and the other ranks only
 take part in the barriers.  Same total work for every N ("strong" scaling).  Rank 0 prints ONE JSON line.  It exits non-zero
 if fewer than N GPUs are visible — never a silent 1-GPU run.
+
+A plain run sets up, warms up, times the K steps and prints the line (headline, phases, the §8(d) roofline fraction of the timed pair).
+`--full` adds everything measured or checked beside it, after the timed region: the instrumented per-kernel passes and the rest of the
+roofline object, the parity checks (committed oracle digest, normal equations), the next rows and the other BASELINE configs, the
+rocSOLVER comparator and the CPU baseline (`--no-*` switch single parts of it off).  `--dump-outputs DIR` writes what the last timed
+step returned (dump_outputs).
 """
 import argparse
 import json
@@ -133,7 +139,7 @@ def cpu_baseline(n_full: int, d: int, full: bool = True):
         t_full = time.perf_counter() - t0
         out.update({"value": n_full / t_full, "pair_s": t_full, "phases_s": {k: round(v, 3) for k, v in tm.items()},
                     "potrf_gflops": n_full**3 / 3 / tm["potrf_s"] / 1e9, "logpdf": float(lp), "_alpha": alpha,
-                    "sample": (f"full run: the oracle's in-place fused logpdf+posterior pair (one Gram + one dpotrf) at N={n_full}, the bench's own "
+                    "sample": (f"full run: the oracle's in-place fused logpdf+posterior pair (one Gram + one in-place Cholesky, blocked above 2^31 elements) at N={n_full}, the bench's own "
                                f"inputs, measured once on this box's host: {t_full:.1f} s (Gram {tm['gram_s']:.1f} / potrf {tm['potrf_s']:.1f} / "
                                f"solves {tm['solves_s']:.1f})")})
         t_twice = t_full + tm["gram_s"] + tm["potrf_s"]
@@ -281,6 +287,23 @@ def cached_cpu_baseline(n_full: int):
                                   f"profiles/{rnd}/fullsize_parity.jsonl; the live bounded sample is timed by the --gpus 1 run",
                         "two_factorisations": {"value": r["oracle_points_per_s_two_factorisations"], "unit": "points/s"}}
     return None
+
+
+def dump_outputs(out_dir: str, post) -> dict:
+    """--dump-outputs DIR: what the last timed step returned to its caller, float64 .npy files — logpdf.npy (logpdf(fx, y), shape (1,)),
+    alpha.npy (α, N values) and factor_probe.npy (C.Uᵀ Ξ for a fixed PCG64(20261016) Gaussian N×4 Ξ, through the library's own
+    factor product on the resident factor: the N×N factor stays on the device, and each of these columns depends on every entry of
+    it).  2.6 MB at N = 65 536.  Returns {name: shape} for the line."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    n = int(post.data.alpha.shape[0])
+    xi = np.random.default_rng(20261016).standard_normal((n, 4))
+    arrays = {"logpdf": np.array([float(post.logpdf_value)], dtype=np.float64),
+              "alpha": np.asarray(post.data.alpha, dtype=np.float64),
+              "factor_probe": np.asarray(post.data.C.Ut_mul(xi), dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 HBM_SPEC_TBPS = 8.0      # MI355X_MICROARCH.md: HBM3E spec
@@ -581,15 +604,22 @@ def main():
     ap.add_argument("--vranks", dest="virtual", type=int, default=0, help="V virtual ranks sharing GPU 0 (schedule test / 1-rank overhead measurement)")
     ap.add_argument("--selftest", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--comparator-child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline-sample-only", action="store_true", help="skip the full-size oracle run (≈ 2-3 minutes at C4); value is then the extrapolation")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the C2 / C3 / C5 lines (other_configs)")
-    ap.add_argument("--no-check", action="store_true", help="skip the post-run parity properties")
-    ap.add_argument("--no-comparator", action="store_true", help="skip the rocsolver_dpotrf comparator (run after the timed region; never on the product path)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the instrumented per-kernel passes, the parity checks, the next rows and other configs, "
+                         "the rocsolver comparator and the CPU baseline (a plain run does none of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step returned (logpdf, alpha, a seeded probe of the factor) as float64 DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--cpu-baseline-sample-only", action="store_true", help="(--full) skip the full-size oracle run (≈ 2-3 minutes at C4); value is then the extrapolation")
+    ap.add_argument("--no-other-configs", action="store_true", help="(--full) skip the C2 / C3 / C5 lines (other_configs)")
+    ap.add_argument("--no-check", action="store_true", help="(--full) skip the post-run parity properties")
+    ap.add_argument("--no-comparator", action="store_true", help="(--full) skip the rocsolver_dpotrf comparator (run after the timed region; never on the product path)")
     ap.add_argument("--dry-launcher", action="store_true",
                     help="launcher protocol only (gloo process group, barriers, max over ranks, rank 0 prints the line) with a stub step and no GPU: "
                          "what the world_size-2 CPU test runs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.selftest:
         sys.exit(selftest(args.gpus, args.virtual, args.grid))
@@ -691,82 +721,88 @@ def main():
         if driver:
             note(f"timed region done: {dt / args.steps * 1e3:.1f} ms per step")
             logpdf_val, alpha = float(post.logpdf_value), post.data.alpha
-            # ---- separate, untimed instrumented pass: every MFMA GEMM launch bracketed by HIP events on its own stream
-            post.data.C.free()
-            ctx.set_param("time_kernels", 1)
-            post = step()
-            tm = ctx.timings()
-            ctx.set_param("time_kernels", 0)
-            gemm_ms, gemm_flops, gemm_bytes, gemm_launches = tm["gemm_ms"], tm["gemm_flops"], tm.get("gemm_bytes", 0.0), tm["gemm_launches"]
-            kernel_tflops = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-            # the same launches with the look-ahead off: every GEMM then has the machine to itself, so its event-bracketed duration is the
-            # kernel's own (with the look-ahead the register-resident leaves of the panel stream share CUs with the update, which shortens the
-            # wall time and lengthens each launch as the events — and rocprofv3 — see it)
-            kernel_alone = None
-            note("instrumented pass done")
-            if not multi:
-                post.data.C.free()
-                la_prev = ctx.get_param("lookahead")
-                ctx.set_param("lookahead", 0)
-                ctx.set_param("time_kernels", 1)
-                post = step()
-                tm0 = ctx.timings()
-                ctx.set_param("time_kernels", 0)
-                ctx.set_param("lookahead", la_prev)
-                if tm0["gemm_ms"] > 0:
-                    kernel_alone = tm0["gemm_flops"] / (tm0["gemm_ms"] * 1e-3) / 1e12
-            note("look-ahead-off pass done")
-            mfma_ceiling = agp._lib.C.c_double()
-            agp._lib.check(ctx.lib.gp_bench_mfma_f64(ctx.handle, 20000, agp._lib.C.byref(mfma_ceiling)))
             pair_tf = f_pair(n) / (dt / args.steps) / 1e12
             peak = FP64_MFMA_PEAK_TFLOPS * (1 if args.virtual else ngpus)
-            # roofline: the SURVEY.md §8(d) number — F_pair / t_pair over the whole job — with the dominant kernel's own rate beside it
-            roofline = {"bound": "mfma", "achieved": pair_tf, "peak": peak, "unit": "TFLOP/s",
-                        "frac": pair_tf / peak,
-                        **(pmc_traffic(n) if not multi else {"traffic": None, "traffic_note": "HBM/fabric bytes come from separate rocprofv3 --pmc passes over the "
-                           "single-GPU command (profiles/r*/pmc_bench_summary.json: same kernel, per launch); PMC cannot be sampled inside a timed multi-GPU run"}),
-                        "definition": "achieved = (N^3/3 + 3N^2) / wall time of one pair (SURVEY.md 8(d)), peak = 78.6 TF/s x n_gpus; "
-                                      "kernel_* = the dominant kernel alone" + (" (rank 0's launches)" if multi else ""),
-                        "kernel": "gemm_nt_dma_kernel<double> (v_mfma_f64_16x16x4_f64 trailing update, LDS-DMA operands; launches of <= 4096 tiles run its "
-                                  "persistent stream-K variant gemm_nt_sk_kernel — kernel_* and the per-launch averages cover both)",
-                        "kernel_achieved": kernel_tflops, "kernel_frac": kernel_tflops / FP64_MFMA_PEAK_TFLOPS,
-                        "kernel_achieved_lookahead_off": kernel_alone, "kernel_frac_lookahead_off": None if kernel_alone is None else kernel_alone / FP64_MFMA_PEAK_TFLOPS,
-                        "kernel_timing": "separate untimed pass with time_kernels=1 (HIP events around each launch on its stream)",
-                        "algorithmic_bytes_per_launch_avg": gemm_bytes / max(gemm_launches, 1),
-                        "launches_per_step": gemm_launches,
-                        "avg_launch_ms": gemm_ms / max(gemm_launches, 1),
-                        "flops_per_launch_avg": gemm_flops / max(gemm_launches, 1),
-                        "measured_mfma_f64_ceiling_tflops": mfma_ceiling.value}
+            roofline = {"bound": "mfma", "achieved": pair_tf, "peak": peak, "unit": "TFLOP/s", "frac": pair_tf / peak,
+                        "definition": "achieved = (N^3/3 + 3N^2) / wall time of one pair (SURVEY.md 8(d)), peak = 78.6 TF/s x n_gpus"}
             extra["phases_ms"] = phases
-            if not multi and phases["assemble_ms"] > 0:  # the Gram phase is HBM-write bound: 8·N(N+1)/2 written once + 8·N·D read
-                kb = 8.0 * n * (n + 1) / 2 + 8.0 * n * d
-                gbps = kb / (phases["assemble_ms"] * 1e-3) / 1e9
-                roofline["kmat"] = {"kernel": "kmat_kernel<double>", "bound": "hbm", "algorithmic_bytes": kb, "ms": phases["assemble_ms"], "achieved": gbps,
-                                    "unit": "GB/s", "frac_of_8TBps_spec": gbps / (HBM_SPEC_TBPS * 1e3), "frac_of_6.29TBps_copy": gbps / (HBM_COPY_TBPS * 1e3)}
-            if not args.no_check and n == 65536:
-                extra.update(digest_check(n, logpdf_val, alpha))
-            if not args.no_check:  # size-independent parity properties at full size
-                r = np.asarray(post.data.delta, dtype=np.float64)
-                # (K + σ²I) α = δ  checked through a second, independent device path: posterior mean at the
-                # training inputs is K α = δ − σ² α
-                idx = np.linspace(0, n - 1, 512).astype(int)
-                m_tr = post.mean(agp.RowVecs(x[idx]))
-                extra["check_residual_max"] = float(np.max(np.abs(m_tr - (r[idx] - sigma2 * alpha[idx]))))
-            note("parity checks done")
-            if not multi and not args.no_other_configs and n == 65536:
-                nxt = next_rows(agp, ctx, post, x, y, n, sigma2)
-                note("next rows (predict / cov / sequential update) done")
+            if args.dump_outputs:
+                shapes = dump_outputs(args.dump_outputs, post)
+                note(f"outputs of the last timed step written to {args.dump_outputs}: {shapes}")
+            if args.full:  # everything below is measured or checked beside the headline, after the timed region
+                # ---- separate, untimed instrumented pass: every MFMA GEMM launch bracketed by HIP events on its own stream
                 post.data.C.free()
-                ctx.trim()
-                extra["other_configs"] = other_configs(agp, ctx)
-                note("other configs (C2 / C3 / C5) done")
-                nxt["value_and_gradient"] = grad_rows(agp, ctx)
-                note("value + gradient rows done")
-                extra["other_configs"]["next"] = nxt
-                ctx.trim()
-                if not args.no_comparator:
-                    extra["comparator_rocsolver_dpotrf"] = rocsolver_comparator()
-                    note("rocsolver comparator done")
+                ctx.set_param("time_kernels", 1)
+                post = step()
+                tm = ctx.timings()
+                ctx.set_param("time_kernels", 0)
+                gemm_ms, gemm_flops, gemm_bytes, gemm_launches = tm["gemm_ms"], tm["gemm_flops"], tm.get("gemm_bytes", 0.0), tm["gemm_launches"]
+                kernel_tflops = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+                # the same launches with the look-ahead off: every GEMM then has the machine to itself, so its event-bracketed duration is the
+                # kernel's own (with the look-ahead the register-resident leaves of the panel stream share CUs with the update, which shortens the
+                # wall time and lengthens each launch as the events — and rocprofv3 — see it)
+                kernel_alone = None
+                note("instrumented pass done")
+                if not multi:
+                    post.data.C.free()
+                    la_prev = ctx.get_param("lookahead")
+                    ctx.set_param("lookahead", 0)
+                    ctx.set_param("time_kernels", 1)
+                    post = step()
+                    tm0 = ctx.timings()
+                    ctx.set_param("time_kernels", 0)
+                    ctx.set_param("lookahead", la_prev)
+                    if tm0["gemm_ms"] > 0:
+                        kernel_alone = tm0["gemm_flops"] / (tm0["gemm_ms"] * 1e-3) / 1e12
+                note("look-ahead-off pass done")
+                mfma_ceiling = agp._lib.C.c_double()
+                agp._lib.check(ctx.lib.gp_bench_mfma_f64(ctx.handle, 20000, agp._lib.C.byref(mfma_ceiling)))
+                # roofline: the SURVEY.md §8(d) number — F_pair / t_pair over the whole job — with the dominant kernel's own rate beside it
+                roofline = {"bound": "mfma", "achieved": pair_tf, "peak": peak, "unit": "TFLOP/s",
+                            "frac": pair_tf / peak,
+                            **(pmc_traffic(n) if not multi else {"traffic": None, "traffic_note": "HBM/fabric bytes come from separate rocprofv3 --pmc passes over the "
+                               "single-GPU command (profiles/r*/pmc_bench_summary.json: same kernel, per launch); PMC cannot be sampled inside a timed multi-GPU run"}),
+                            "definition": "achieved = (N^3/3 + 3N^2) / wall time of one pair (SURVEY.md 8(d)), peak = 78.6 TF/s x n_gpus; "
+                                          "kernel_* = the dominant kernel alone" + (" (rank 0's launches)" if multi else ""),
+                            "kernel": "gemm_nt_dma_kernel<double> (v_mfma_f64_16x16x4_f64 trailing update, LDS-DMA operands; launches of <= 4096 tiles run its "
+                                      "persistent stream-K variant gemm_nt_sk_kernel — kernel_* and the per-launch averages cover both)",
+                            "kernel_achieved": kernel_tflops, "kernel_frac": kernel_tflops / FP64_MFMA_PEAK_TFLOPS,
+                            "kernel_achieved_lookahead_off": kernel_alone, "kernel_frac_lookahead_off": None if kernel_alone is None else kernel_alone / FP64_MFMA_PEAK_TFLOPS,
+                            "kernel_timing": "separate untimed pass with time_kernels=1 (HIP events around each launch on its stream)",
+                            "algorithmic_bytes_per_launch_avg": gemm_bytes / max(gemm_launches, 1),
+                            "launches_per_step": gemm_launches,
+                            "avg_launch_ms": gemm_ms / max(gemm_launches, 1),
+                            "flops_per_launch_avg": gemm_flops / max(gemm_launches, 1),
+                            "measured_mfma_f64_ceiling_tflops": mfma_ceiling.value}
+                if not multi and phases["assemble_ms"] > 0:  # the Gram phase is HBM-write bound: 8·N(N+1)/2 written once + 8·N·D read
+                    kb = 8.0 * n * (n + 1) / 2 + 8.0 * n * d
+                    gbps = kb / (phases["assemble_ms"] * 1e-3) / 1e9
+                    roofline["kmat"] = {"kernel": "kmat_kernel<double>", "bound": "hbm", "algorithmic_bytes": kb, "ms": phases["assemble_ms"], "achieved": gbps,
+                                        "unit": "GB/s", "frac_of_8TBps_spec": gbps / (HBM_SPEC_TBPS * 1e3), "frac_of_6.29TBps_copy": gbps / (HBM_COPY_TBPS * 1e3)}
+                if not args.no_check and n == 65536:
+                    extra.update(digest_check(n, logpdf_val, alpha))
+                if not args.no_check:  # size-independent parity properties at full size
+                    r = np.asarray(post.data.delta, dtype=np.float64)
+                    # (K + σ²I) α = δ  checked through a second, independent device path: posterior mean at the
+                    # training inputs is K α = δ − σ² α
+                    idx = np.linspace(0, n - 1, 512).astype(int)
+                    m_tr = post.mean(agp.RowVecs(x[idx]))
+                    extra["check_residual_max"] = float(np.max(np.abs(m_tr - (r[idx] - sigma2 * alpha[idx]))))
+                note("parity checks done")
+                if not multi and not args.no_other_configs and n == 65536:
+                    nxt = next_rows(agp, ctx, post, x, y, n, sigma2)
+                    note("next rows (predict / cov / sequential update) done")
+                    post.data.C.free()
+                    ctx.trim()
+                    extra["other_configs"] = other_configs(agp, ctx)
+                    note("other configs (C2 / C3 / C5) done")
+                    nxt["value_and_gradient"] = grad_rows(agp, ctx)
+                    note("value + gradient rows done")
+                    extra["other_configs"]["next"] = nxt
+                    ctx.trim()
+                    if not args.no_comparator:
+                        extra["comparator_rocsolver_dpotrf"] = rocsolver_comparator()
+                        note("rocsolver comparator done")
             if multi:
                 extra["multi_stats"] = ctx.multi_stats()  # fits / retries (repetitions after a failed self-check) / solves: a non-zero retry count is never silent
             if multi:
@@ -796,7 +832,7 @@ def main():
             "lib_sha16": lib_sha16(),
         }
         line.update(extra)
-        if not multi and not args.no_cpu_baseline:
+        if args.full and not multi and not args.no_cpu_baseline:
             cb = cpu_baseline(n, d, full=not args.cpu_baseline_sample_only)
             a_cpu = cb.pop("_alpha", None)
             if a_cpu is not None:  # the measured oracle run is also a live parity check of the timed result (1e-10 / 1e-8)
@@ -805,7 +841,7 @@ def main():
                 cb["engine_vs_this_run"]["pass"] = bool(cb["engine_vs_this_run"]["logpdf_rel"] <= 1e-10 and cb["engine_vs_this_run"]["alpha_rel"] <= 1e-8)
             line["cpu_baseline"] = cb
             note("cpu baseline done")
-        elif multi and not args.no_cpu_baseline:
+        elif args.full and multi and not args.no_cpu_baseline:
             line["cpu_baseline"] = cached_cpu_baseline(n) or cpu_baseline(n, d, full=False)
         print(json.dumps(line), flush=True)
     if have_pg:

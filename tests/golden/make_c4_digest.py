@@ -10,7 +10,7 @@ memory, minutes of host BLAS) and stores what a checker needs to pin a device re
   (PCG64 seed 20260926 + i) — a wrong α that keeps its norm, its sampled entries AND all eight projections would have to be
   wrong in a 65 536 − 1 033 dimensional subspace by design, not by accident.
 
-bench.py compares the timed engine's logpdf / α against this file on every run (`check_logpdf_rel_vs_digest`,
+bench.py --full compares the timed engine's logpdf / α against this file on every run (`check_logpdf_rel_vs_digest`,
 `check_alpha_rel_vs_digest`), tests/test_gpu_fullsize.py asserts it, and the GPU test-suite ALSO re-runs the oracle itself
 at this size (test_c4_full_size_values_vs_oracle).  Test infrastructure: the product never reads this file.
 """

@@ -43,6 +43,13 @@ def test_dry_launcher_single_process():
     assert json.loads(r.stdout.strip().splitlines()[-1])["world"] == 1
 
 
+def test_steps_must_be_positive():
+    """--steps sets the number of timed steps: zero steps would time nothing (and divide by zero), so the parser refuses it."""
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--dry-launcher", *bad], capture_output=True, text=True, timeout=120, cwd=str(ROOT))
+        assert r.returncode == 2 and "--steps must be >= 1" in r.stderr, (bad, r.stderr[-500:])
+
+
 def test_comparator_is_bounded_and_never_takes_the_line_down(monkeypatch):
     """The rocSOLVER yardstick runs in a child process with a hard time limit (one GPU box of round 4 needed more than five minutes to
     load librocsolver.so and the whole bench timed out in it).  Without a device the child answers with an error object; with a child that

@@ -2,7 +2,9 @@
 generator tests/golden/make_golden.jl and the shim abstractgps.jl_amd/julia/HipGPs.jl — so that the first maintainer run does not die on a typo:
 block / `end` balance and bracket balance (a lexer that knows strings, comments, `a[end]`, symbols and generator forms), every AbstractGPs name the
 generator calls against the reference's export list (src/AbstractGPs.jl:19-35; KernelFunctions is re-exported, :8), every `data.<field>` it reads
-against the NamedTuples the reference builds (src/exact_gpr_posterior.jl:34, src/sparse_approximations.jl:73)."""
+against the NamedTuples the reference builds (src/exact_gpr_posterior.jl:34, src/sparse_approximations.jl:73).  Those lists are checked against the
+names extracted from the reference (tests/golden/reference_api.json, tests/golden/make_reference_api.py)."""
+import json
 import re
 from pathlib import Path
 
@@ -11,7 +13,7 @@ import pytest
 ROOT = Path(__file__).resolve().parent.parent
 GEN = ROOT / "tests" / "golden" / "make_golden.jl"
 SHIM = ROOT / "abstractgps.jl_amd" / "julia" / "HipGPs.jl"
-REF = Path("/root/reference/src")
+REF_API = ROOT / "tests" / "golden" / "reference_api.json"
 
 # src/AbstractGPs.jl:19-35 (AbstractGPs 0.5.24)
 EXPORTS = {"GP", "LatentGP", "VFE", "DTC", "ZeroMean", "ConstMean", "CustomMean", "rand!", "mean", "cov", "var", "std", "mean_and_cov", "mean_and_var",
@@ -187,17 +189,11 @@ def test_generator_reads_only_fields_the_reference_cache_has():
     assert every == exact | sparse, "a `.data.<field>` read on a variable this test does not classify"
 
 
-@pytest.mark.skipif(not REF.exists(), reason="the reference tree is not on this machine (GPU box): the lists above are checked where it is")
 def test_the_lists_above_are_the_reference_s():
-    txt = (REF / "AbstractGPs.jl").read_text()
-    blocks = re.findall(r"^export (.*?)(?=^\S|\Z)", txt, flags=re.S | re.M)
-    names = set()
-    for b in blocks:
-        names |= {t.strip() for t in b.replace("\n", " ").split(",") if t.strip()}
+    ref = json.loads(REF_API.read_text())
+    assert ref["reference"] == "AbstractGPs.jl 0.5.24"
+    names = set(ref["exports"])
     assert names == EXPORTS, (sorted(names - EXPORTS), sorted(EXPORTS - names))
-    assert "@reexport using KernelFunctions" in txt
-    exact = re.search(r"PosteriorGP\(fx\.f, \((.*?)\)\)", (REF / "exact_gpr_posterior.jl").read_text())
-    assert exact and {kv.split("=")[0].strip() for kv in exact.group(1).split(",")} == EXACT_FIELDS
-    sp = (REF / "sparse_approximations.jl").read_text()
-    m = re.search(r"cache = \((.*?)\)\n", sp)
-    assert m and {kv.split("=")[0].strip() for kv in m.group(1).split(",")} == VFE_FIELDS
+    assert ref["reexports_kernelfunctions"] is True
+    assert set(ref["exact_posterior_data_fields"]) == EXACT_FIELDS
+    assert set(ref["vfe_cache_fields"]) == VFE_FIELDS

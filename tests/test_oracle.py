@@ -336,3 +336,26 @@ def test_elbo_grad_survives_an_ill_conditioned_kzz():
     an = float(np.sum(g["z"] * dZ))
     assert abs(fds[0] - fds[1]) <= 1e-3 * abs(fds[1])          # the difference quotient has converged
     assert an == pytest.approx(fds[1], rel=1e-3), (an, fds)
+
+
+@pytest.mark.parametrize("block", [256, 1000])
+def test_blocked_inplace_factor_matches_lapack(block):
+    """potrf_upper_inplace above its single-call limit (forced here at N = 3 001): the blocked factorisation of the upper triangle against one
+    dpotrf call, the strict lower triangle outside the diagonal blocks left as it was, and LAPACK's 1-based minor reported for a non-PD matrix."""
+    x, _ = o.synth_inputs(3001, 3, 4)
+    C = np.asfortranarray(o.kernelmatrix(o.Kernel(o.SE), x))
+    C[np.diag_indices_from(C)] += 0.01
+    U_ref = o.cholesky_upper(C.copy())
+    A = C.copy(order="F")
+    U = o.potrf_upper_inplace(A, block=block, max_single=0)
+    assert U is A
+    np.testing.assert_allclose(np.triu(U), U_ref, rtol=0, atol=1e-13)
+    below = np.tril(np.ones(C.shape, dtype=bool), -1)
+    for k in range(0, C.shape[0], block):
+        below[k:k + block, k:k + block] = False
+    assert np.array_equal(U[below], C[below])
+    B = C.copy(order="F")
+    B[1200, 1200] = -1.0
+    with pytest.raises(o.PosDefException) as e:
+        o.potrf_upper_inplace(B, block=block, max_single=0)
+    assert e.value.info == 1201

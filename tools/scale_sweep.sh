@@ -12,7 +12,7 @@ STEPS=${1:-3}; WARM=${2:-1}
 OUT=${OUT:-gpurun_out/scale_sweep.jsonl}
 mkdir -p "$(dirname "$OUT")"; : > "$OUT"
 NGPU=$(python -c 'import torch; print(torch.cuda.device_count())')
-COMMON="--steps $STEPS --warmup $WARM --no-cpu-baseline --no-other-configs --no-comparator"
+COMMON="--full --steps $STEPS --warmup $WARM --no-cpu-baseline --no-other-configs --no-comparator"
 run() {  # run <gpus> <extra bench args...>
   local n=$1; shift
   if [ -n "$VRANKS" ]; then
