@@ -18,6 +18,19 @@ class gp_kernel(C.Structure):
                 ("scale", C.POINTER(C.c_double))]
 
 
+class gp_kfactor(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("nscale", C.c_int32), ("scale", C.POINTER(C.c_double)), ("nparam", C.c_int32),
+                ("param", C.POINTER(C.c_double))]
+
+
+class gp_kterm(C.Structure):
+    _fields_ = [("variance", C.c_double), ("nfactors", C.c_int32), ("factors", C.POINTER(gp_kfactor))]
+
+
+class gp_ksum(C.Structure):
+    _fields_ = [("dtype", C.c_int32), ("nterms", C.c_int32), ("terms", C.POINTER(gp_kterm))]
+
+
 class gp_points(C.Structure):
     _fields_ = [("data", C.c_void_p), ("n", C.c_int64), ("d", C.c_int32), ("layout", C.c_int32)]
 
@@ -39,6 +52,7 @@ class gp_grid(C.Structure):
 
 vp, i32, i64, dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_double
 PK, PP, PN, PG = C.POINTER(gp_kernel), C.POINTER(gp_points), C.POINTER(gp_noise), C.POINTER(gp_grid)
+PS = C.POINTER(gp_ksum)
 
 # name -> (restype, argtypes); must cover every function declared in include/gpmi355.h
 PROTOTYPES = {
@@ -63,6 +77,10 @@ PROTOTYPES = {
     "gp_posterior_predict": (i32, [vp, PP, vp, i32, vp, vp, vp]),
     "gp_posterior_get_factor": (i32, [vp, vp]),
     "gp_logpdf_grad": (i32, [vp, PK, PP, PN, vp, vp, vp, C.POINTER(dbl), C.POINTER(dbl), vp, vp, vp]),
+    "gp_kernelmatrix_sum": (i32, [vp, PS, PP, PP, vp]),
+    "gp_logpdf_sum": (i32, [vp, PS, PP, PN, vp, vp, i64, i32, vp]),
+    "gp_posterior_fit_sum": (i32, [vp, PS, PP, PN, vp, vp, C.POINTER(vp), vp, vp]),
+    "gp_logpdf_grad_sum": (i32, [vp, PS, PP, PN, vp, vp, vp, C.POINTER(dbl), vp, vp]),
     "gp_posterior_update": (i32, [vp, PP, PN, vp, C.POINTER(vp), vp, vp]),
     "gp_posterior_factor_mul": (i32, [vp, vp, i32, vp]),
     "gp_posterior_solve": (i32, [vp, vp, i32, vp]),

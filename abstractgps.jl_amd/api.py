@@ -25,7 +25,7 @@ from typing import Callable, Optional, Union
 import numpy as np
 
 from . import _lib
-from ._lib import PosDefException, check, gp_kernel, gp_noise, gp_points, gp_timings
+from ._lib import PosDefException, check, gp_kernel, gp_kfactor, gp_ksum, gp_kterm, gp_noise, gp_points, gp_timings
 
 default_sigma2 = 1e-18  # src/finite_gp_projection.jl:17
 
@@ -46,23 +46,93 @@ class ARDTransform:
         object.__setattr__(self, "v", tuple(float(t) for t in np.asarray(v).ravel()))
 
 
+class _KernelOps:
+    """KernelFunctions' composition operators: k1 + k2 (KernelSum), k1 * k2 (KernelProduct), a * k (ScaledKernel)."""
+
+    def __add__(self, other):
+        if not isinstance(other, _KernelOps):
+            return NotImplemented
+        return KernelSum(_flat(self, KernelSum) + _flat(other, KernelSum))
+
+    def _times(self, other):  # a kernel times a kernel: KernelProduct
+        return KernelProduct(_flat(self, KernelProduct) + _flat(other, KernelProduct))
+
+
+def _flat(k, cls) -> tuple:
+    return k.kernels if isinstance(k, cls) else (k,)
+
+
 @dataclass(frozen=True)
-class Kernel:
+class Kernel(_KernelOps):
+    """variance · base(kind) ∘ transform.  kind 0..3 SqExponential / Matern12 / Matern32 / Matern52 (the single-kind path, gp_kernel);
+    4 Periodic (param = r), 5 RationalQuadratic (param = (α,)), 6 White (composite path, gp_ksum — include/gpmi355.h)."""
+
     kind: int
     variance: float = 1.0
     transform: Union[None, ScaleTransform, ARDTransform] = None
+    param: tuple = ()
 
     def __matmul__(self, t):  # k ∘ ScaleTransform(s)  /  k ∘ ARDTransform(v)
         if not isinstance(t, (ScaleTransform, ARDTransform)):
             raise TypeError("only ScaleTransform / ARDTransform are accelerated")
         if self.transform is not None:
             raise TypeError("nested transforms are not accelerated")
-        return Kernel(self.kind, self.variance, t)
+        if self.kind == 6:  # δ(x, x') does not change under a (nonzero) scale, and the transform's tangent is zero: dropped
+            return self
+        return Kernel(self.kind, self.variance, t, self.param)
 
     def __rmul__(self, a):  # α * k  (ScaledKernel)
-        return Kernel(self.kind, self.variance * float(a), self.transform)
+        return Kernel(self.kind, self.variance * float(a), self.transform, self.param)
 
-    __mul__ = __rmul__
+    def __mul__(self, a):  # k * k2 (KernelProduct) or k * α
+        if isinstance(a, _KernelOps):
+            return self._times(a)
+        return self.__rmul__(a)
+
+
+@dataclass(frozen=True)
+class KernelSum(_KernelOps):
+    kernels: tuple
+
+    def __matmul__(self, t):
+        raise TypeError("a transform around a sum of kernels is not accelerated: put it on each base kernel")
+
+    def __mul__(self, a):
+        return self._times(a) if isinstance(a, _KernelOps) else ScaledKernel(self, float(a))
+
+    def __rmul__(self, a):
+        return ScaledKernel(self, float(a))
+
+
+@dataclass(frozen=True)
+class KernelProduct(_KernelOps):
+    kernels: tuple
+
+    def __matmul__(self, t):
+        raise TypeError("a transform around a product of kernels is not accelerated: put it on each base kernel")
+
+    def __mul__(self, a):
+        return self._times(a) if isinstance(a, _KernelOps) else ScaledKernel(self, float(a))
+
+    def __rmul__(self, a):
+        return ScaledKernel(self, float(a))
+
+
+@dataclass(frozen=True)
+class ScaledKernel(_KernelOps):
+    """σ² · k for a composite k (a base kernel folds its ScaledKernel factor into Kernel.variance)."""
+
+    kernel: object
+    variance: float
+
+    def __matmul__(self, t):
+        raise TypeError("a transform around a scaled sum or product of kernels is not accelerated")
+
+    def __mul__(self, a):
+        return self._times(a) if isinstance(a, _KernelOps) else ScaledKernel(self.kernel, self.variance * float(a))
+
+    def __rmul__(self, a):
+        return ScaledKernel(self.kernel, self.variance * float(a))
 
 
 def SqExponentialKernel():
@@ -85,6 +155,153 @@ def Matern32Kernel():
 
 def Matern52Kernel():
     return Kernel(3)
+
+
+def PeriodicKernel(r=(1.0,)):
+    """PeriodicKernel(; r): exp(−½ Σ_p (sinpi(u_p) / r_p)²), one r_p > 0 per input dimension (KernelFunctions' default r = [1.0])."""
+    r = tuple(float(v) for v in np.asarray(r, dtype=np.float64).ravel())
+    if not r or not all(v > 0 for v in r):
+        raise ValueError("PeriodicKernel: every r must be > 0")
+    return Kernel(4, 1.0, None, r)
+
+
+def RationalQuadraticKernel(alpha=2.0):
+    """RationalQuadraticKernel(; α): (1 + d²/(2α))^(−α), α > 0 (KernelFunctions' default α = 2)."""
+    if not float(alpha) > 0:
+        raise ValueError("RationalQuadraticKernel: alpha must be > 0")
+    return Kernel(5, 1.0, None, (float(alpha),))
+
+
+def WhiteKernel():
+    """WhiteKernel(): 1 where x and x' are equal in every coordinate, else 0."""
+    return Kernel(6)
+
+
+# Limits of the composite path (include/gpmi355.h gp_ksum)
+KSUM_MAX_TERMS, KSUM_MAX_FACTORS_PER_TERM, KSUM_MAX_FACTORS, KSUM_MAX_THETA, KSUM_MAX_D = 8, 4, 16, 64, 16
+
+
+def _is_composite(k) -> bool:
+    """True for what goes through the *_sum entry points: a sum, a product, a scaled composite or a base kernel of kind 4..6."""
+    return not (isinstance(k, Kernel) and k.kind <= 3)
+
+
+class _NormalForm:
+    """Σ_t σ_t² Π_f κ_f of a kernel tree.  `params` holds the tree's own parameters depth-first, left to right — a node's before its children's;
+    a base kernel: its variance (the ScaledKernel factor), then Periodic r / RQ α, then its transform's s or v — and every term refers to them by
+    index, so that products distributed over sums share their parameters.  `theta` is the flat vector of the C ABI (term by term σ_t², then per
+    factor scale, then param); `chain` maps ∂/∂theta back to ∂/∂params."""
+
+    def __init__(self, k):
+        self.params = []
+        self.terms = self._walk(k)  # [(variance indices, [(kind, scale indices, param indices)])]
+
+    def _new(self, v) -> int:
+        self.params.append(float(v))
+        return len(self.params) - 1
+
+    def _walk(self, k):
+        if isinstance(k, Kernel):
+            vi = self._new(k.variance)
+            pi = [self._new(v) for v in k.param]
+            t = k.transform
+            si = [self._new(t.s)] if isinstance(t, ScaleTransform) else ([self._new(v) for v in t.v] if isinstance(t, ARDTransform) else [])
+            return [([vi], [(k.kind, si, pi)])]
+        if isinstance(k, ScaledKernel):
+            vi = self._new(k.variance)
+            return [([vi] + v, f) for v, f in self._walk(k.kernel)]
+        if isinstance(k, KernelSum):
+            return [t for c in k.kernels for t in self._walk(c)]
+        if isinstance(k, KernelProduct):
+            terms = [([], [])]
+            for c in k.kernels:
+                ct = self._walk(c)
+                terms = [(v1 + v2, f1 + f2) for v1, f1 in terms for v2, f2 in ct]
+            return terms
+        raise TypeError(f"not an accelerated kernel: {k!r}")
+
+    def check(self, d: int) -> None:
+        """The limits of include/gpmi355.h gp_ksum (TypeError) and the per-dimension parameter counts (ValueError, as ARDTransform's)."""
+        nt, nf = len(self.terms), sum(len(f) for _, f in self.terms)
+        if nt > KSUM_MAX_TERMS:
+            raise TypeError(f"composite kernel: {nt} terms in the normal form, at most {KSUM_MAX_TERMS} are accelerated")
+        if any(len(f) > KSUM_MAX_FACTORS_PER_TERM for _, f in self.terms):
+            raise TypeError(f"composite kernel: a term with more than {KSUM_MAX_FACTORS_PER_TERM} factors is not accelerated")
+        if nf > KSUM_MAX_FACTORS:
+            raise TypeError(f"composite kernel: {nf} factors in all, at most {KSUM_MAX_FACTORS} are accelerated")
+        if len(self.theta()) > KSUM_MAX_THETA:
+            raise TypeError(f"composite kernel: {len(self.theta())} entries in theta, at most {KSUM_MAX_THETA} are accelerated")
+        if d > KSUM_MAX_D:
+            raise TypeError(f"composite kernel: D = {d}, at most {KSUM_MAX_D} is accelerated")
+        for _, fs in self.terms:
+            for kind, si, pi in fs:
+                if len(si) > 1 and len(si) != d:
+                    raise ValueError(f"DimensionMismatch: ARDTransform has {len(si)} scales, inputs have D={d}")
+                if kind == 4 and len(pi) != d:
+                    raise ValueError(f"DimensionMismatch: PeriodicKernel has {len(pi)} entries in r, inputs have D={d}")
+
+    def theta(self) -> list:
+        p, th = self.params, []
+        for vi, fs in self.terms:
+            th.append(math.prod(p[i] for i in vi))
+            for _, si, pi in fs:
+                th += [p[i] for i in si] + [p[i] for i in pi]
+        return th
+
+    def chain(self, g_theta) -> np.ndarray:
+        """∂/∂params from ∂/∂theta: ∂σ_t²/∂v = Π of the term's other variances (no division), scales and parameters one to one; a parameter
+        in several terms sums its contributions."""
+        p, g, j = self.params, np.zeros(len(self.params)), 0
+        for vi, fs in self.terms:
+            for a in range(len(vi)):
+                g[vi[a]] += g_theta[j] * math.prod(p[vi[b]] for b in range(len(vi)) if b != a)
+            j += 1
+            for _, si, pi in fs:
+                for i in si + pi:
+                    g[i] += g_theta[j]
+                    j += 1
+        return g
+
+
+def params(k) -> np.ndarray:
+    """The kernel tree's own parameters in a fixed order — depth-first, left to right: ScaledKernel σ², and per base kernel its variance, Periodic r /
+    RationalQuadratic α, then ScaleTransform s / ARDTransform v — the order of logpdf_and_grad's g["kernel"]."""
+    return np.array(_NormalForm(k).params)
+
+
+def with_params(k, theta):
+    """The same tree with the parameters `theta` (the order of params(k))."""
+    it = iter(np.asarray(theta, dtype=np.float64).ravel().tolist())
+
+    def rebuild(k):
+        if isinstance(k, Kernel):
+            v = next(it)
+            par = tuple(next(it) for _ in k.param)
+            t = k.transform
+            if isinstance(t, ScaleTransform):
+                t = ScaleTransform(next(it))
+            elif isinstance(t, ARDTransform):
+                t = ARDTransform([next(it) for _ in t.v])
+            return Kernel(k.kind, v, t, par)
+        if isinstance(k, ScaledKernel):
+            v = next(it)
+            return ScaledKernel(rebuild(k.kernel), v)
+        if isinstance(k, (KernelSum, KernelProduct)):
+            return type(k)(tuple(rebuild(c) for c in k.kernels))
+        raise TypeError(f"not an accelerated kernel: {k!r}")
+
+    out = rebuild(k)
+    if next(it, None) is not None:
+        raise ValueError("with_params: more values than the kernel has parameters")
+    return out
+
+
+def _prior_variance(k) -> float:
+    """k(x, x) = Σ_t σ_t² (every base κ(x, x) = 1)."""
+    if isinstance(k, Kernel) and k.kind <= 3:
+        return k.variance
+    nf = _NormalForm(k)
+    return float(sum(math.prod(nf.params[i] for i in vi) for vi, _ in nf.terms))
 
 
 def compose(k: Kernel, t) -> Kernel:
@@ -180,6 +397,32 @@ class _Marshal:
                 raise ValueError(f"DimensionMismatch: ARDTransform has {s.shape[0]} scales, inputs have D={d}")
         self.keep.append(s)
         return gp_kernel(k.kind, dt, k.variance, s.shape[0], s.ctypes.data_as(C.POINTER(C.c_double)))
+
+    def ksum(self, k, d: int):
+        """gp_ksum of a composite kernel (normal form on the host) and its _NormalForm (for the chain rule of the gradient)."""
+        nf = _NormalForm(k)
+        nf.check(d)
+        dt = 0 if self.dtype == np.float64 else 1
+        p = nf.params
+        terms = (gp_kterm * len(nf.terms))()
+        for t, (vi, fs) in enumerate(nf.terms):
+            facs = (gp_kfactor * len(fs))()
+            for j, (kind, si, pi) in enumerate(fs):
+                sv = np.array([p[i] for i in si], dtype=np.float64)
+                pv = np.array([p[i] for i in pi], dtype=np.float64)
+                self.keep += [sv, pv]
+                dp = C.POINTER(C.c_double)
+                facs[j] = gp_kfactor(kind, len(si), sv.ctypes.data_as(dp) if len(si) else None, len(pi), pv.ctypes.data_as(dp) if len(pi) else None)
+            self.keep.append(facs)
+            terms[t] = gp_kterm(math.prod(p[i] for i in vi), len(fs), facs)
+        self.keep.append(terms)
+        return gp_ksum(dt, len(nf.terms), terms), nf
+
+    def any_kernel(self, k, d: int):
+        """(entry-point suffix, descriptor): "" and a gp_kernel for kinds 0..3, "_sum" and a gp_ksum for everything composite."""
+        if _is_composite(k):
+            return "_sum", self.ksum(k, d)[0]
+        return "", self.kernel(k, d)
 
     def noise(self, sigma2, n: int) -> gp_noise:
         s = np.asarray(sigma2)
@@ -320,7 +563,7 @@ class GP(AbstractGP):
             self.mean_fn, self.kernel = args  # GP(c::Real, k) / GP(f, k)  base_gp.jl:62-63
         else:
             raise TypeError("GP(kernel) or GP(mean, kernel)")
-        if not isinstance(self.kernel, Kernel):
+        if not isinstance(self.kernel, _KernelOps):
             raise TypeError("kernel must be one of the accelerated kernels")
         self.ctx = ctx
 
@@ -338,7 +581,7 @@ class GP(AbstractGP):
         return kernelmatrix(self.kernel, x, z, ctx=self.context())
 
     def var(self, x):
-        return np.full(_npoints(x), self.kernel.variance, dtype=_input_dtype(x))  # kernelmatrix_diag
+        return np.full(_npoints(x), _prior_variance(self.kernel), dtype=_input_dtype(x))  # kernelmatrix_diag
 
     def mean_and_var(self, x):
         return self.mean(x), self.var(x)
@@ -375,15 +618,16 @@ def kernelmatrix(k: Kernel, x, z=None, ctx: Optional[Context] = None) -> np.ndar
     dt = _input_dtype(x)
     m = _Marshal(dt)
     px = m.points(x)
-    kk = m.kernel(k, px.d)
+    sfx, kk = m.any_kernel(k, px.d)
+    fn = getattr(ctx.lib, "gp_kernelmatrix" + sfx)
     n = px.n
     if z is None:
         out = np.empty((n, n), dtype=dt, order="F")
-        check(ctx.lib.gp_kernelmatrix(ctx.handle, C.byref(kk), C.byref(px), None, out.ctypes.data))
+        check(fn(ctx.handle, C.byref(kk), C.byref(px), None, out.ctypes.data))
     else:
         pz = m.points(z)
         out = np.empty((n, pz.n), dtype=dt, order="F")
-        check(ctx.lib.gp_kernelmatrix(ctx.handle, C.byref(kk), C.byref(px), C.byref(pz), out.ctypes.data))
+        check(fn(ctx.handle, C.byref(kk), C.byref(px), C.byref(pz), out.ctypes.data))
     return out
 
 
@@ -410,14 +654,14 @@ def logpdf(fx: FiniteGP, y):
     dt = np.result_type(_input_dtype(fx.x), np.float32 if y.dtype == np.float32 else np.float64).type
     m = _Marshal(dt)
     px = m.points(fx.x)
-    kk = m.kernel(f.kernel, px.d)
+    sfx, kk = m.any_kernel(f.kernel, px.d)
     nz = m.noise(fx.sigma2, px.n)
     mean = _mean_vector(f.mean_fn, fx.x, dt)
     mean = None if mean is None else m.arr(mean)
     Y = m.arr(y if y.ndim == 2 else y[:, None], order="F")
     out = np.empty(Y.shape[1], dtype=dt)
-    check(ctx.lib.gp_logpdf(ctx.handle, C.byref(kk), C.byref(px), C.byref(nz), m.ptr(mean), Y.ctypes.data,
-                            Y.shape[0], Y.shape[1], out.ctypes.data))
+    check(getattr(ctx.lib, "gp_logpdf" + sfx)(ctx.handle, C.byref(kk), C.byref(px), C.byref(nz), m.ptr(mean), Y.ctypes.data,
+                                              Y.shape[0], Y.shape[1], out.ctypes.data))
     return out[0] if y.ndim == 1 else out
 
 
@@ -426,6 +670,9 @@ def _terms(fx: FiniteGP, y, want_logdet: bool, want_sqmahal: bool):
     f = fx.f
     if not isinstance(f, GP):
         raise TypeError("only GP priors are accelerated here (the shim falls back to the stock methods otherwise)")
+    if _is_composite(f.kernel):
+        raise NotImplementedError("logdet / sqmahal of a composite kernel are not accelerated (gp_logpdf_terms is single-kind; "
+                                  "the Julia shim falls back to stock AbstractGPs)")
     ctx = f.context()
     dt = _input_dtype(fx.x) if y is None else np.result_type(_input_dtype(fx.x), np.float32 if np.asarray(y).dtype == np.float32 else np.float64).type
     m = _Marshal(dt)
@@ -480,7 +727,9 @@ def logpdf_and_grad(fx: FiniteGP, y, wrt_x: bool = False) -> tuple:
     """Value and gradient of logpdf(fx, y) for the rrule of the accelerated path (the reference differentiates the same
     expression by AD — test/finite_gp_projection.jl:152-178).  Returns (logpdf, grads) with grads =
     {"variance": ∂/∂σ_k², "scale": ∂/∂s (ScaleTransform) or ∂/∂v (ARDTransform) or None, "noise": ∂/∂σ² (scalar Σy) or the
-    vector ∂/∂Σy_ii, "y": −α, "mean": +α} and, with wrt_x, "x": ∂/∂x in the shape of the input container's array."""
+    vector ∂/∂Σy_ii, "y": −α, "mean": +α} and, with wrt_x, "x": ∂/∂x in the shape of the input container's array.
+    A composite kernel (sums, products, Periodic / RationalQuadratic / White) returns "kernel": ∂/∂params(k) in the order of params(k), and "theta":
+    the gradient against the flat θ of include/gpmi355.h (gp_logpdf_grad_sum), in place of "variance" / "scale"; wrt_x is not offered for it."""
     y = _check_y(fx, y)
     if y.ndim != 1:
         raise TypeError("logpdf_and_grad expects a vector of observations")
@@ -491,12 +740,23 @@ def logpdf_and_grad(fx: FiniteGP, y, wrt_x: bool = False) -> tuple:
     dt = np.result_type(_input_dtype(fx.x), np.float32 if y.dtype == np.float32 else np.float64).type
     m = _Marshal(dt)
     px = m.points(fx.x)
-    kk = m.kernel(f.kernel, px.d)
+    kk = None if _is_composite(f.kernel) else m.kernel(f.kernel, px.d)
     nz = m.noise(fx.sigma2, px.n)
     mean = _mean_vector(f.mean_fn, fx.x, dt)
     mean = None if mean is None else m.arr(mean)
     yv = m.arr(y)
     lp = np.empty(1, dtype=dt)
+    if _is_composite(f.kernel):
+        if wrt_x:
+            raise NotImplementedError("∂/∂x of a composite kernel is not accelerated")
+        ks, nf = m.ksum(f.kernel, px.d)
+        dth = (C.c_double * max(len(nf.theta()), 1))()
+        dnoise = np.empty(1 if nz.kind == 0 else px.n, dtype=dt)
+        dy = np.empty(px.n, dtype=dt)
+        check(ctx.lib.gp_logpdf_grad_sum(ctx.handle, C.byref(ks), C.byref(px), C.byref(nz), m.ptr(mean), yv.ctypes.data, lp.ctypes.data, dth,
+                                         dnoise.ctypes.data, dy.ctypes.data))
+        gth = np.array(dth[:len(nf.theta())])
+        return lp[0], {"kernel": nf.chain(gth), "theta": gth, "noise": dnoise[0] if nz.kind == 0 else dnoise, "y": dy, "mean": -dy}
     dvar = C.c_double()
     dscale = (C.c_double * max(kk.nscale, 1))()
     dnoise = np.empty(1 if nz.kind == 0 else px.n, dtype=dt)
@@ -639,7 +899,7 @@ def _posterior_exact(fx: FiniteGP, y, zero_mean: bool = False) -> PosteriorGP:
     dt = np.result_type(_input_dtype(fx.x), np.float32 if y.dtype == np.float32 else np.float64).type
     m = _Marshal(dt)
     px = m.points(fx.x)
-    kk = m.kernel(f.kernel, px.d)
+    sfx, kk = m.any_kernel(f.kernel, px.d)
     nz = m.noise(fx.sigma2, px.n)
     mean = None if zero_mean else _mean_vector(f.mean_fn, fx.x, dt)
     yv = m.arr(y)
@@ -648,8 +908,8 @@ def _posterior_exact(fx: FiniteGP, y, zero_mean: bool = False) -> PosteriorGP:
     alpha = np.empty(px.n, dtype=dt)
     lp = np.empty(1, dtype=dt)
     h = C.c_void_p()
-    check(ctx.lib.gp_posterior_fit(ctx.handle, C.byref(kk), C.byref(px), C.byref(nz), m.ptr(mean), yv.ctypes.data,
-                                   C.byref(h), alpha.ctypes.data, lp.ctypes.data))
+    check(getattr(ctx.lib, "gp_posterior_fit" + sfx)(ctx.handle, C.byref(kk), C.byref(px), C.byref(nz), m.ptr(mean), yv.ctypes.data,
+                                                     C.byref(h), alpha.ctypes.data, lp.ctypes.data))
     return PosteriorGP(f, _PostData(alpha, _Factor(ctx, h, px.n, dt), fx.x, delta), lp[0])
 
 
@@ -826,6 +1086,9 @@ def _vfe_call(approx, fx: FiniteGP, y, want_post: bool):
         raise AssertionError("vfe.fz.f === fx.f")
     if not isinstance(f, GP):
         raise TypeError("VFE/DTC: unsupported prior type")
+    if _is_composite(f.kernel):
+        raise NotImplementedError("VFE / DTC with a composite kernel are not accelerated (the Julia shim falls back to stock AbstractGPs; "
+                                  "the exact path takes composite kernels)")
     ctx = f.context()
     dt = np.result_type(_input_dtype(fx.x), np.float32 if y.dtype == np.float32 else np.float64).type
     m = _Marshal(dt)

@@ -37,6 +37,21 @@ struct GridMap {
     int ktri_off;    // ktri == 1 with A pointing at row ktri_off of the triangular matrix: row tile m0 stops at ktri_off + m0 + 128
                      // ktri == 2: rows [0, ktri_off) of A are dense, the upper-triangular block starts at row ktri_off (row tile m0 > ktri_off starts at column m0 − ktri_off)
 };
+
+// Packed composite kernel Σ_t σ_t² Π_f κ_f (include/gpmi355.h gp_ksum), passed BY VALUE as a kernel argument (under 1 KB; uniform across the
+// wavefront, read with scalar loads).  Every parameter lives in th[] in θ order, so a θ index is also the slot of its gradient.
+struct KSum {
+    enum { MAXT = 8, MAXFT = 4, MAXF = 16, MAXTH = 64, MAXD = 16 };
+    int nterms, nth;
+    int t0[MAXT + 1];  // factors of term t: [t0[t], t0[t + 1])
+    int tv[MAXT];      // θ index of σ_t²
+    int kind[MAXF];    // 0..6 (include/gpmi355.h)
+    int ns[MAXF];      // 0 none, 1 ScaleTransform, D ARDTransform
+    int so[MAXF];      // θ index of scale[0]
+    int po[MAXF];      // θ index of param[0] (r_0 for kind 4, α for kind 5)
+    double th[MAXTH];
+};
+static_assert(sizeof(KSum) < 1024, "the composite kernel descriptor travels as a kernel argument");
 }  // namespace gpmi
 
 // ---- errors (thread-local text behind gp_last_error) ---------------------------------------------
@@ -263,6 +278,8 @@ struct gp_post {
     double logdet_half;  // Σ log L_ii
     DibCache dibc;            // −inv(L_bb) of the factor's diagonal blocks, built on the first forward solve against the resident factor ("dib_nb")
     gp_multi_post* pieces = nullptr;  // multi-device fit: the factor still lives as block-cyclic pieces (A == nullptr until gathered)
+    bool composite = false;   // fitted by gp_posterior_fit_sum: the kernel is `ks` (kind 0, nscale 0, variance Σ_t σ_t²), xs holds the RAW inputs
+    gpmi::KSum ks{};
 };
 
 // ---- engine entry points used by multi.hip (fp64; work is issued on stream s of ctx c and not synchronised) ----

@@ -924,12 +924,32 @@ static void scale_points_into(const gp_kernel* k, const gp_points* x, long ldx, 
 // posterior handle
 // ------------------------------------------------------------------------------------------------
 
-template <typename T> static int32_t assemble_sym(gp_ctx* c, const gp_kernel* k, const T* xs_dev, long ldx, int d,
+// The kernel a Gram / mean launch evaluates: one kind (variance · κ_kind on pre-scaled inputs, ks == nullptr) or a composite kernel (ks, raw
+// inputs).  Every place that evaluates a handle's kernel goes through gram() / kvec(); with a single kind they launch what they always launched.
+struct KDesc {
+    int kind;
+    double variance;
+    const KSum* ks;
+};
+static KDesc kdesc(const gp_kernel* k, const KSum* ks) { return KDesc{k->kind, k->variance, ks}; }
+static KDesc kdesc(const gp_post* p) { return KDesc{p->kind, p->variance, p->composite ? &p->ks : nullptr}; }
+template <typename T>
+static void gram(const KDesc& k, dim3 grid, hipStream_t s, T* out, long ld, const T* xr, long ldxr, const T* xc, long ldxc, int d, const T* noise,
+                 long nr_valid, long nc_valid, int sym, GridMap g) {
+    if (k.ks) launch_kmat_sum<T>(grid, s, out, ld, xr, ldxr, xc, ldxc, d, *k.ks, noise, nr_valid, nc_valid, sym, g);
+    else launch_kmat<T>(grid, s, out, ld, xr, ldxr, xc, ldxc, d, k.kind, (T)k.variance, noise, nr_valid, nc_valid, sym, g, (const T*)nullptr, (const T*)nullptr);
+}
+template <typename T>
+static void kvec(const KDesc& k, long ns, hipStream_t s, const T* xs, long ldxs, const T* x, long ldx, int d, long n, const T* alpha, T* out) {
+    if (k.ks) launch_kvec_sum<T>(ns, s, xs, ldxs, x, ldx, d, *k.ks, n, alpha, out);
+    else hipLaunchKernelGGL(kvec_kernel<T>, dim3((unsigned)ns), dim3(256), 0, s, xs, ldxs, x, ldx, d, k.kind, (T)k.variance, n, alpha, out);
+}
+
+template <typename T> static int32_t assemble_sym(gp_ctx* c, const KDesc& k, const T* xs_dev, long ldx, int d,
                                                   const T* noise_dev, long n, long np, T* A, long ld) {
     GridMap g = plain_map(1, 0, 0);
     dim3 grid((unsigned)(np / 128), (unsigned)(np / 128));
-    launch_kmat<T>(grid, c->sm, A, ld, xs_dev, ldx, xs_dev, ldx, d, k->kind,
-                       (T)k->variance, noise_dev, n, n, 1, g, (const T*)nullptr, (const T*)nullptr);
+    gram<T>(k, grid, c->sm, A, ld, xs_dev, ldx, xs_dev, ldx, d, noise_dev, n, n, 1, g);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -942,11 +962,12 @@ struct FitOut {
 };
 
 // Shared by gp_logpdf and gp_posterior_fit.  Y: n×ncols column-major host.  If post != NULL the factor
-// is kept and α is computed for column 0.
+// is kept and α is computed for column 0.  ks != NULL: a composite kernel (the *_sum calls) — k then scales nothing (nscale 0) and
+// carries Σ_t σ_t² as its variance, the prior variance the predictions use.
 template <typename T>
 static int32_t fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise,
                         const void* mean_or_null, const void* Yv, long ldy, int ncols, FitOut& out, gp_post* post,
-                        void* alpha_out) {
+                        void* alpha_out, const KSum* ks = nullptr) {
     const long n = x->n, np = round_up(n, 128);
     const int d = x->d;
     const long R = round_up(std::max(ncols, 1), 128);
@@ -992,7 +1013,7 @@ static int32_t fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const
         HIPCHK(hipMemsetAsync(A + np * ld, 0, sizeof(T) * (size_t)(R + 128) * ld, c->sm));
         HIPCHK(hipMemcpy2DAsync(A + np * ld, sizeof(T) * ld, rhs_h.data(), sizeof(T) * np, sizeof(T) * np, ncols,
                                 hipMemcpyHostToDevice, c->sm));
-        RC(assemble_sym<T>(c, k, (const T*)xs_v, np, d, (const T*)noise_v, n, np, A, ld));
+        RC(assemble_sym<T>(c, kdesc(k, ks), (const T*)xs_v, np, d, (const T*)noise_v, n, np, A, ld));
         HIPCHK(hipEventRecord(c->ev_phase[1], c->sm));
         RC(potrf_full<T>(c, A, ld, np, mtot, c->info_dev, n, c->scal_dev));
         HIPCHK(hipEventRecord(c->ev_phase[2], c->sm));
@@ -1064,6 +1085,8 @@ static int32_t fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const
     post->xs = xs_v; post->xs_bytes = xs_bytes;
     post->alpha = alpha_v; post->alpha_bytes = nz_bytes;
     post->logdet_half = logdet_half_out;
+    post->composite = ks != nullptr;
+    if (ks) post->ks = *ks;
     return 0;
 }
 
@@ -1094,9 +1117,7 @@ static int32_t predict_impl(gp_post* post, const gp_points* xs, const void* pm, 
         HIPCHK(hipMemcpyAsync(xs_v, xs_h.data(), xs_bytes, hipMemcpyHostToDevice, c->sm));
         if (what & 1) {
             RC(bufs.get(m_bytes, &m_v));
-            hipLaunchKernelGGL(kvec_kernel<T>, dim3((unsigned)ns), dim3(256), 0, c->sm, (const T*)xs_v, nsp,
-                               (const T*)post->xs, np, d, post->kind, (T)post->variance, n, (const T*)post->alpha,
-                               (T*)m_v);
+            kvec<T>(kdesc(post), ns, c->sm, (const T*)xs_v, nsp, (const T*)post->xs, np, d, n, (const T*)post->alpha, (T*)m_v);
             HIPCHK(hipGetLastError());
             std::vector<T> m_h(ns);
             HIPCHK(hipMemcpyAsync(m_h.data(), m_v, sizeof(T) * ns, hipMemcpyDeviceToHost, c->sm));
@@ -1120,9 +1141,7 @@ static int32_t predict_impl(gp_post* post, const gp_points* xs, const void* pm, 
                 const long rows = std::min(chunk, nsp - r0);
                 GridMap g = plain_map(0, r0, 0);
                 dim3 grid((unsigned)(np / 128), (unsigned)(rows / 128));
-                launch_kmat<T>(grid, c->sm, X, ldx, (const T*)xs_v, nsp,
-                                   (const T*)post->xs, np, d, post->kind, (T)post->variance, (const T*)nullptr, ns, n,
-                                   0, g, (const T*)nullptr, (const T*)nullptr);
+                gram<T>(kdesc(post), grid, c->sm, X, ldx, (const T*)xs_v, nsp, (const T*)post->xs, np, d, (const T*)nullptr, ns, n, 0, g);
                 HIPCHK(hipGetLastError());
                 RC(trsm_post<T>(post, c->sm, X, ldx, rows, bufs));
                 if (what & 2) {
@@ -1133,7 +1152,7 @@ static int32_t predict_impl(gp_post* post, const gp_points* xs, const void* pm, 
                                           c->sm));
                     HIPCHK(hipStreamSynchronize(c->sm));
                     for (long i = 0; i < rows && r0 + i < ns; ++i)
-                        vo[r0 + i] = (T)((double)post->variance - ss[i]);
+                        vo[r0 + i] = (T)((double)post->variance - ss[i]);  // k(x, x) = σ² (composite: Σ_t σ_t², every κ_f(x, x) = 1)
                 }
             }
             if (want_cov) {
@@ -1143,9 +1162,7 @@ static int32_t predict_impl(gp_post* post, const gp_points* xs, const void* pm, 
                 T* Cm = (T*)C_v;
                 GridMap g = plain_map(0, 0, 0);
                 dim3 grid((unsigned)(nsp / 128), (unsigned)(nsp / 128));
-                launch_kmat<T>(grid, c->sm, Cm, ldc, (const T*)xs_v, nsp,
-                                   (const T*)xs_v, nsp, d, post->kind, (T)post->variance, (const T*)nullptr, ns, ns,
-                                   0, g, (const T*)nullptr, (const T*)nullptr);
+                gram<T>(kdesc(post), grid, c->sm, Cm, ldc, (const T*)xs_v, nsp, (const T*)xs_v, nsp, d, (const T*)nullptr, ns, ns, 0, g);
                 HIPCHK(hipGetLastError());
                 RC(launch_gemm<T>(c, c->sm, Cm, ldc, X, ldx, X, ldx, nsp, nsp, np, plain_map(0, 0, 0)));
                 // symmetric: row-major == column-major
@@ -1160,17 +1177,18 @@ static int32_t predict_impl(gp_post* post, const gp_points* xs, const void* pm, 
     return rc;
 }
 
-// logpdf value + gradient (see include/gpmi355.h gp_logpdf_grad)
+// logpdf value + gradient (see include/gpmi355.h gp_logpdf_grad; ks != NULL: gp_logpdf_grad_sum, ∂/∂θ into dtheta, no dx)
 template <typename T>
 static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean,
-                         const void* y, void* logpdf_out, double* dvar, double* dscale, void* dnoise, void* dy, void* dx) {
+                         const void* y, void* logpdf_out, double* dvar, double* dscale, void* dnoise, void* dy, void* dx,
+                         const KSum* ks = nullptr, double* dtheta = nullptr) {
     const long n = x->n;
     const int d = x->d;
     gp_post post{};
     post.ctx = c;
     FitOut fo;
     std::vector<T> alpha_h((size_t)n);
-    RC(fit_impl<T>(c, k, x, noise, mean, y, n, 1, fo, &post, alpha_h.data()));
+    RC(fit_impl<T>(c, k, x, noise, mean, y, n, 1, fo, &post, alpha_h.data(), ks));
     SkScope sk(c);
     const long np = post.np, ld = post.ld;
     hipStream_t s = c->sm;
@@ -1178,13 +1196,14 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
     const size_t gx_b = sizeof(double) * (size_t)d * np;
     std::vector<double> gx_h(dx ? (size_t)d * np : 0);
     const int nsc = std::max(k->nscale, 1);
-    const size_t M_b = sizeof(T) * (size_t)(np + 128) * ld, g_b = sizeof(double) * (size_t)(2 + nsc), dn_b = sizeof(T) * (size_t)np;
+    const int ng = ks ? ks->nth : nsc;  // g[2 + p]: ∂/∂scale_p, or ∂/∂θ_p of a composite kernel
+    const size_t M_b = sizeof(T) * (size_t)(np + 128) * ld, g_b = sizeof(double) * (size_t)(2 + ng), dn_b = sizeof(T) * (size_t)np;
     const size_t sc_b = sizeof(double) * (size_t)nsc;
     DevBufs bufs(c);
     bufs.v.push_back(post.A);  // the temporary posterior's blocks go back to the cache with everything else
     bufs.v.push_back(post.xs);
     bufs.v.push_back(post.alpha);
-    std::vector<double> g_hv((size_t)(2 + nsc), 0.0);  // [0] ∂/∂variance, [1] Σ_i ∂/∂Σy_ii, [2 + p] ∂/∂scale_p
+    std::vector<double> g_hv((size_t)(2 + ng), 0.0);  // [0] ∂/∂variance, [1] Σ_i ∂/∂Σy_ii, [2 + p] ∂/∂scale_p (∂/∂θ_p)
     double* g_h = g_hv.data();
     std::vector<T> dn_h((size_t)n);
     std::vector<double> sc_h((size_t)nsc, 1.0);
@@ -1235,7 +1254,12 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
 #define GPMI_KGRAD_FAST(ND_)                                                                                                                  \
     hipLaunchKernelGGL((kgrad_fast_kernel<T, ND_>), grid, dim3(256), 0, s, (const T*)Ci, ld, (const T*)post.xs, np, d, post.kind, (T)post.variance, \
                        post.nscale, (const double*)sc_v, (const T*)post.alpha, n, (double*)g_v)
-        if (d <= 16 && (ld * (long)sizeof(T)) % 16 == 0) {  // the scratch-free form (16-byte loads of the weights)
+        if (ks) {  // composite kernel: one launch per chunk of 16 θ entries
+            for (int p0 = 0; p0 < ks->nth; p0 += 16) {
+                launch_kgrad_sum<T>(grid, s, (const T*)Ci, ld, (const T*)post.xs, np, d, *ks, (const T*)post.alpha, n, (double*)g_v, p0);
+                HIPCHK(hipGetLastError());
+            }
+        } else if (d <= 16 && (ld * (long)sizeof(T)) % 16 == 0) {  // the scratch-free form (16-byte loads of the weights)
             if (d <= 4) GPMI_KGRAD_FAST(4);
             else if (d <= 8) GPMI_KGRAD_FAST(8);
             else GPMI_KGRAD_FAST(16);
@@ -1274,6 +1298,8 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
     if (dvar) *dvar = g_h[0];
     if (dscale)
         for (int p = 0; p < k->nscale; ++p) dscale[p] = g_h[2 + p];
+    if (dtheta && ks)
+        for (int p = 0; p < ks->nth; ++p) dtheta[p] = g_h[2 + p];
     if (dnoise) {
         if (noise->kind == 0) *(T*)dnoise = (T)g_h[1];
         else memcpy(dnoise, dn_h.data(), sizeof(T) * (size_t)n);
@@ -1352,8 +1378,7 @@ static int32_t update_impl(gp_post* old, const gp_points* x2, const gp_noise* no
         {
             GridMap g = plain_map(0, 0, 0);
             dim3 grid((unsigned)(np1 / 128), (unsigned)(n2p / 128));
-            launch_kmat<T>(grid, s, X, ldx, (const T*)x2_v, n2p, (const T*)old->xs, np1, d,
-                               k.kind, (T)k.variance, (const T*)nullptr, n2, n1, 0, g, (const T*)nullptr, (const T*)nullptr);
+            gram<T>(kdesc(old), grid, s, X, ldx, (const T*)x2_v, n2p, (const T*)old->xs, np1, d, (const T*)nullptr, n2, n1, 0, g);
             HIPCHK(hipGetLastError());
         }
         RC(trsm_post<T>(old, s, X, ldx, n2p, bufs));
@@ -1361,8 +1386,7 @@ static int32_t update_impl(gp_post* old, const gp_points* x2, const gp_noise* no
         {
             GridMap g = plain_map(1, 0, 0);
             dim3 grid((unsigned)(n2p / 128), (unsigned)(n2p / 128));
-            launch_kmat<T>(grid, s, S, lds, (const T*)x2_v, n2p, (const T*)x2_v, n2p, d,
-                               k.kind, (T)k.variance, (const T*)nz_v, n2, n2, 1, g, (const T*)nullptr, (const T*)nullptr);
+            gram<T>(kdesc(old), grid, s, S, lds, (const T*)x2_v, n2p, (const T*)x2_v, n2p, d, (const T*)nz_v, n2, n2, 1, g);
             HIPCHK(hipGetLastError());
         }
         RC(launch_gemm<T>(c, s, S, lds, X, ldx, X, ldx, n2p, n2p, np1, plain_map(1, 0, 0)));
@@ -1402,6 +1426,8 @@ static int32_t update_impl(gp_post* old, const gp_points* x2, const gp_noise* no
     post->n = n; post->np = np; post->ld = ld; post->mtot = mtot; post->d = d;
     post->kind = old->kind; post->variance = old->variance; post->nscale = old->nscale;
     post->scale = old->scale;
+    post->composite = old->composite;
+    post->ks = old->ks;
     post->A = A_v; post->A_bytes = A_b;
     post->xs = xs_v; post->xs_bytes = xs_b;
     post->alpha = alpha_v; post->alpha_bytes = v_b;
@@ -1504,23 +1530,20 @@ static int32_t post_joint(gp_post* post, const gp_points* xs, const void* pm, co
     std::vector<T> m_h((size_t)ns);
     HIPCHK(hipMemcpyAsync(xs_v, xs_h.data(), sizeof(T) * (size_t)d * nsp, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(nz_v, nz_h.data(), sizeof(T) * (size_t)nsp, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(kvec_kernel<T>, dim3((unsigned)ns), dim3(256), 0, s, (const T*)xs_v, nsp, (const T*)post->xs, np, d,
-                       post->kind, (T)post->variance, n, (const T*)post->alpha, (T*)m_v);                       // K_*x α
+    kvec<T>(kdesc(post), ns, s, (const T*)xs_v, nsp, (const T*)post->xs, np, d, n, (const T*)post->alpha, (T*)m_v);  // K_*x α
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(m_h.data(), m_v, sizeof(T) * (size_t)ns, hipMemcpyDeviceToHost, s));
     {
         GridMap g = plain_map(0, 0, 0);
         dim3 grid((unsigned)(np / 128), (unsigned)(nsp / 128));
-        launch_kmat<T>(grid, s, X, ldx, (const T*)xs_v, nsp, (const T*)post->xs, np, d,
-                           post->kind, (T)post->variance, (const T*)nullptr, ns, n, 0, g, (const T*)nullptr, (const T*)nullptr);
+        gram<T>(kdesc(post), grid, s, X, ldx, (const T*)xs_v, nsp, (const T*)post->xs, np, d, (const T*)nullptr, ns, n, 0, g);
         HIPCHK(hipGetLastError());
     }
     RC(trsm_post<T>(post, s, X, ldx, nsp, bufs));                                                              // V ᵀ = K_*x L⁻ᵀ
     {
         GridMap g = plain_map(1, 0, 0);
         dim3 grid((unsigned)(nsp / 128), (unsigned)(nsp / 128));
-        launch_kmat<T>(grid, s, Cm, ldc, (const T*)xs_v, nsp, (const T*)xs_v, nsp, d,
-                           post->kind, (T)post->variance, (const T*)nz_v, ns, ns, 1, g, (const T*)nullptr, (const T*)nullptr);
+        gram<T>(kdesc(post), grid, s, Cm, ldc, (const T*)xs_v, nsp, (const T*)xs_v, nsp, d, (const T*)nz_v, ns, ns, 1, g);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemsetAsync(Cm + nsp * ldc, 0, sizeof(T) * (size_t)(R + 128) * ldc, s));
@@ -1827,15 +1850,8 @@ int32_t gp_get_timings(gp_ctx* c, gp_timings* out) {
     return 0;
 }
 
-int32_t gp_kernelmatrix(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_points* y, void* out) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
-    RC(check_points(x, 3));
-    RC(check_kernel(k, x->d, 2));
-    if (y) {
-        RC(check_points(y, 4));
-        if (y->d != x->d) return set_arg_err(4, "x and y have different D");
-    }
-    if (!out) return set_arg_err(5, "out is NULL");
+// gp_kernelmatrix / gp_kernelmatrix_sum after their argument checks (k: the input scaling and dtype; ks: composite kernel or NULL)
+static int32_t kernelmatrix_impl(gp_ctx* c, const gp_kernel* k, const KSum* ks, const gp_points* x, const gp_points* y, void* out) {
     std::lock_guard<std::mutex> l(c->mu);
     HIPCHK(hipSetDevice(c->device));
     auto run = [&](auto tag) -> int32_t {
@@ -1858,9 +1874,8 @@ int32_t gp_kernelmatrix(gp_ctx* c, const gp_kernel* k, const gp_points* x, const
             if (y) HIPCHK(hipMemcpyAsync(xr_v, xr_h.data(), xrb, hipMemcpyHostToDevice, c->sm));
             GridMap g = plain_map(0, 0, 0);
             dim3 grid((unsigned)(np / 128), (unsigned)(mp / 128));
-            launch_kmat<T>(grid, c->sm, (T*)K_v, ld, (const T*)(y ? xr_v : xc_v),
-                               y ? mp : np, (const T*)xc_v, np, x->d, k->kind, (T)k->variance, (const T*)nullptr, m, n,
-                               0, g, (const T*)nullptr, (const T*)nullptr);
+            gram<T>(kdesc(k, ks), grid, c->sm, (T*)K_v, ld, (const T*)(y ? xr_v : xc_v), y ? mp : np, (const T*)xc_v, np, x->d,
+                    (const T*)nullptr, m, n, 0, g);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpy2DAsync(out, sizeof(T) * n, K_v, sizeof(T) * ld, sizeof(T) * n, m, hipMemcpyDeviceToHost,
                                     c->sm));
@@ -1871,6 +1886,88 @@ int32_t gp_kernelmatrix(gp_ctx* c, const gp_kernel* k, const gp_points* x, const
         return rc;
     };
     return k->dtype == 0 ? run(double()) : run(float());
+}
+
+int32_t gp_kernelmatrix(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_points* y, void* out) {
+    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    RC(check_points(x, 3));
+    RC(check_kernel(k, x->d, 2));
+    if (y) {
+        RC(check_points(y, 4));
+        if (y->d != x->d) return set_arg_err(4, "x and y have different D");
+    }
+    if (!out) return set_arg_err(5, "out is NULL");
+    return kernelmatrix_impl(c, k, nullptr, x, y, out);
+}
+
+// Validates a gp_ksum (limits and malformed descriptors: −argi with the reason) and packs it for the device.  kid: the single-kind descriptor
+// the engine carries beside it — kind 0, no transform (the inputs stay raw), variance Σ_t σ_t² (the prior variance k(x, x)).
+static int32_t pack_ksum(const gp_ksum* k, int d, int argi, KSum& ks, gp_kernel& kid) {
+    if (!k) return set_arg_err(argi, "kernel is NULL");
+    if (k->dtype != 0 && k->dtype != 1) return set_arg_err(argi, "dtype must be 0 (f64) or 1 (f32)");
+    if (k->nterms < 1 || k->nterms > KSum::MAXT) return set_arg_err(argi, "composite kernel: 1..8 terms");
+    if (!k->terms) return set_arg_err(argi, "composite kernel: terms is NULL");
+    if (d > KSum::MAXD) return set_arg_err(argi, "composite kernel: D must be <= 16");
+    ks = KSum{};
+    int nf = 0, nth = 0;
+    double vsum = 0;
+    const char* too_many = "composite kernel: at most 64 entries in theta";
+    for (int t = 0; t < k->nterms; ++t) {
+        const gp_kterm& tm = k->terms[t];
+        if (!(tm.variance > 0)) return set_arg_err(argi, "composite kernel: term variance must be > 0");
+        if (tm.nfactors < 1 || tm.nfactors > KSum::MAXFT) return set_arg_err(argi, "composite kernel: 1..4 factors per term");
+        if (!tm.factors) return set_arg_err(argi, "composite kernel: factors is NULL");
+        if (nf + tm.nfactors > KSum::MAXF) return set_arg_err(argi, "composite kernel: at most 16 factors in all");
+        if (nth >= KSum::MAXTH) return set_arg_err(argi, too_many);
+        ks.t0[t] = nf;
+        ks.tv[t] = nth;
+        ks.th[nth++] = tm.variance;
+        vsum += tm.variance;
+        for (int j = 0; j < tm.nfactors; ++j, ++nf) {
+            const gp_kfactor& f = tm.factors[j];
+            if (f.kind < 0 || f.kind > 6) return set_arg_err(argi, "composite kernel: factor kind must be 0..6");
+            if (f.nscale != 0 && f.nscale != 1 && f.nscale != d) return set_arg_err(argi, "composite kernel: nscale must be 0, 1 or D");
+            if (f.nscale > 0 && !f.scale) return set_arg_err(argi, "composite kernel: scale is NULL");
+            if (f.kind == 6 && f.nscale != 0) return set_arg_err(argi, "composite kernel: WhiteKernel takes no transform");
+            const int want = f.kind == 4 ? d : (f.kind == 5 ? 1 : 0);
+            if (f.nparam != want)
+                return set_arg_err(argi, "composite kernel: param holds D entries (r) for kind 4, 1 (alpha) for kind 5, none otherwise");
+            if (want > 0 && !f.param) return set_arg_err(argi, "composite kernel: param is NULL");
+            for (int q = 0; q < want; ++q)
+                if (!(f.param[q] > 0)) return set_arg_err(argi, "composite kernel: Periodic r and RationalQuadratic alpha must be > 0");
+            if (nth + f.nscale + want > KSum::MAXTH) return set_arg_err(argi, too_many);
+            ks.kind[nf] = f.kind;
+            ks.ns[nf] = f.nscale;
+            ks.so[nf] = nth;
+            for (int q = 0; q < f.nscale; ++q) ks.th[nth++] = f.scale[q];
+            ks.po[nf] = nth;
+            for (int q = 0; q < want; ++q) ks.th[nth++] = f.param[q];
+        }
+    }
+    ks.t0[k->nterms] = nf;
+    ks.nterms = k->nterms;
+    ks.nth = nth;
+    kid = gp_kernel{};
+    kid.kind = 0;
+    kid.dtype = k->dtype;
+    kid.variance = vsum;
+    kid.nscale = 0;
+    kid.scale = nullptr;
+    return 0;
+}
+
+int32_t gp_kernelmatrix_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_points* y, void* out) {
+    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    RC(check_points(x, 3));
+    KSum ks;
+    gp_kernel kid;
+    RC(pack_ksum(k, x->d, 2, ks, kid));
+    if (y) {
+        RC(check_points(y, 4));
+        if (y->d != x->d) return set_arg_err(4, "x and y have different D");
+    }
+    if (!out) return set_arg_err(5, "out is NULL");
+    return kernelmatrix_impl(c, &kid, &ks, x, y, out);
 }
 
 static int32_t check_fit_args(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise) {
@@ -2054,6 +2151,81 @@ int32_t gp_logpdf_grad(gp_ctx* c, const gp_kernel* k, const gp_points* x, const 
     HIPCHK(hipSetDevice(c->device));
     return k->dtype == 0 ? grad_impl<double>(c, k, x, noise, mean, y, logpdf_out, dvar, dscale, dnoise, dy, dx)
                          : grad_impl<float>(c, k, x, noise, mean, y, logpdf_out, dvar, dscale, dnoise, dy, dx);
+}
+
+// ---- composite kernels (gp_ksum): the single-device engine — on a multi-device ctx that of its first device, as fit_any does for fp32 fits
+static int32_t check_fit_args_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, KSum& ks, gp_kernel& kid) {
+    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    RC(check_points(x, 3));
+    RC(pack_ksum(k, x->d, 2, ks, kid));
+    if (!noise) return set_arg_err(4, "noise is NULL");
+    if (noise->kind != 0 && noise->kind != 1) return set_arg_err(4, "noise kind must be 0 or 1");
+    if (noise->kind == 1 && !noise->diag) return set_arg_err(4, "noise diag is NULL");
+    return 0;
+}
+
+int32_t gp_logpdf_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y, int64_t ldy,
+                      int32_t ncols, void* out) {
+    KSum ks;
+    gp_kernel kid;
+    RC(check_fit_args_sum(c, k, x, noise, ks, kid));
+    if (!Y) return set_arg_err(6, "Y is NULL");
+    if (ldy < x->n) return set_arg_err(7, "ldy < n");
+    if (ncols < 1) return set_arg_err(8, "ncols must be >= 1");
+    if (!out) return set_arg_err(9, "out is NULL");
+    std::lock_guard<std::mutex> l(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    FitOut fo;
+    const int32_t rc = kid.dtype == 0 ? fit_impl<double>(c, &kid, x, noise, mean, Y, ldy, ncols, fo, nullptr, nullptr, &ks)
+                                      : fit_impl<float>(c, &kid, x, noise, mean, Y, ldy, ncols, fo, nullptr, nullptr, &ks);
+    if (rc != 0) return rc;
+    for (int s = 0; s < ncols; ++s) {
+        if (kid.dtype == 0) ((double*)out)[s] = fo.logpdf[s];
+        else ((float*)out)[s] = (float)fo.logpdf[s];
+    }
+    return 0;
+}
+
+int32_t gp_posterior_fit_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, gp_post** out,
+                             void* alpha_out, void* logpdf_out) {
+    KSum ks;
+    gp_kernel kid;
+    RC(check_fit_args_sum(c, k, x, noise, ks, kid));
+    if (!y) return set_arg_err(6, "y is NULL");
+    if (!out) return set_arg_err(7, "out is NULL");
+    *out = nullptr;
+    std::lock_guard<std::mutex> l(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    gp_post* p = new gp_post();
+    p->ctx = c;
+    FitOut fo;
+    const int32_t rc = kid.dtype == 0 ? fit_impl<double>(c, &kid, x, noise, mean, y, x->n, 1, fo, p, alpha_out, &ks)
+                                      : fit_impl<float>(c, &kid, x, noise, mean, y, x->n, 1, fo, p, alpha_out, &ks);
+    if (rc != 0) {
+        delete p;
+        return rc;
+    }
+    if (logpdf_out) {
+        if (kid.dtype == 0) *(double*)logpdf_out = fo.logpdf[0];
+        else *(float*)logpdf_out = (float)fo.logpdf[0];
+    }
+    c->refs++;
+    reg_add(p);
+    *out = p;
+    return 0;
+}
+
+int32_t gp_logpdf_grad_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y,
+                           void* logpdf_out, double* dtheta, void* dnoise, void* dy) {
+    KSum ks;
+    gp_kernel kid;
+    RC(check_fit_args_sum(c, k, x, noise, ks, kid));
+    if (!y) return set_arg_err(6, "y is NULL");
+    if (!logpdf_out) return set_arg_err(7, "logpdf_out is NULL");
+    std::lock_guard<std::mutex> l(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    return kid.dtype == 0 ? grad_impl<double>(c, &kid, x, noise, mean, y, logpdf_out, nullptr, nullptr, dnoise, dy, nullptr, &ks, dtheta)
+                          : grad_impl<float>(c, &kid, x, noise, mean, y, logpdf_out, nullptr, nullptr, dnoise, dy, nullptr, &ks, dtheta);
 }
 
 int32_t gp_posterior_update(gp_post* old, const gp_points* x2, const gp_noise* noise2, const void* delta_all, gp_post** out,

@@ -2331,6 +2331,332 @@ __global__ __launch_bounds__(256) void kvec_kernel(const T* __restrict__ xs, lon
     if (threadIdx.x == 0) out[s] = (T)(red[0] + red[1] + red[2] + red[3]);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Composite kernels Σ_t σ_t² Π_f κ_f (KSum, engine.hpp; closed forms and θ order in include/gpmi355.h gp_ksum).
+//   The inputs are RAW (unscaled, dimension-major): every factor applies its own transform to the differences t_p = x_p − x'_p
+//   (u_p = s·t_p or v_p·t_p; a ScaleTransform factor reuses the raw squared distance times s²).  DR = 1 / 4 / 16 bounds D; the
+//   difference arrays hold DR entries, zero beyond D (the staged inputs are zero there), so that every loop over them unrolls
+//   into registers.  The descriptor is a by-value kernel argument: its fields are wave-uniform and read with scalar loads.
+//   kmat_sum_kernel / kvec_sum_kernel are the composite counterparts of kmat_kernel / kvec_kernel (same tile contract, same grids,
+//   no atomics); kgrad_sum_kernel is that of kgrad_fast_kernel (same weights, fp64 atomics after a workgroup reduction).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double sinpi_t(double x) { return sinpi(x); }  // exact argument reduction, as Julia's sinpi
+__device__ __forceinline__ float sinpi_t(float x) { return sinpif(x); }
+__device__ __forceinline__ double log1p_t(double x) { return log1p(x); }
+__device__ __forceinline__ float log1p_t(float x) { return log1pf(x); }
+
+// d² of a non-periodic factor f: the raw r² (no transform), s²·r² (ScaleTransform), Σ_p (v_p t_p)² (ARDTransform)
+template <typename T, int DR>
+__device__ __forceinline__ T ksum_d2(const KSum& k, int f, const T (&t)[DR], T r2, int d) {
+    const int ns = k.ns[f];
+    if (ns == 0) return r2;
+    if (ns == 1) {
+        const T s = (T)k.th[k.so[f]];
+        return s * s * r2;
+    }
+    T d2 = T(0);
+#pragma unroll
+    for (int p = 0; p < DR; ++p)
+        if (p < d) {
+            const T u = (T)k.th[k.so[f] + p] * t[p];
+            d2 = fma(u, u, d2);
+        }
+    return d2;
+}
+
+// κ_f at the differences t (r2 = Σ t_p², eq: every t_p == 0)
+template <typename T, int DR>
+__device__ __forceinline__ T ksum_factor(const KSum& k, int f, const T (&t)[DR], T r2, bool eq, int d) {
+    const int kind = k.kind[f];
+    if (kind == 6) return eq ? T(1) : T(0);
+    if (kind == 4) {
+        const int ns = k.ns[f];
+        T acc = T(0);
+#pragma unroll
+        for (int p = 0; p < DR; ++p)
+            if (p < d) {
+                const T sc = ns == 0 ? T(1) : (T)k.th[k.so[f] + (ns == 1 ? 0 : p)];
+                const T v = sinpi_t(sc * t[p]) / (T)k.th[k.po[f] + p];
+                acc = fma(v, v, acc);
+            }
+        return exp_nonpos<T>(T(-0.5) * acc);
+    }
+    const T d2 = ksum_d2<T, DR>(k, f, t, r2, d);
+    if (kind == 5) {
+        const T a = (T)k.th[k.po[f]];
+        return exp_nonpos<T>(-a * log1p_t(d2 / (T(2) * a)));
+    }
+    return kappa<T>(kind, d2);
+}
+
+template <typename T, int DR>
+__device__ __forceinline__ void ksum_r2(const T (&t)[DR], T& r2, bool& eq) {
+    r2 = T(0);
+    eq = true;
+#pragma unroll
+    for (int p = 0; p < DR; ++p) {
+        r2 = fma(t[p], t[p], r2);
+        eq = eq && t[p] == T(0);
+    }
+}
+
+template <typename T, int DR>
+__device__ __forceinline__ T ksum_eval(const KSum& k, const T (&t)[DR], int d) {
+    T r2;
+    bool eq;
+    ksum_r2<T, DR>(t, r2, eq);
+    T sum = T(0);
+    for (int tt = 0; tt < k.nterms; ++tt) {
+        T prod = (T)k.th[k.tv[tt]];
+        for (int f = k.t0[tt]; f < k.t0[tt + 1]; ++f) prod *= ksum_factor<T, DR>(k, f, t, r2, eq, d);
+        sum += prod;
+    }
+    return sum;
+}
+
+// out[r][c] = Σ_t σ_t² Π_f κ_f(xr_r − xc_c) (+ noise_r on the global diagonal when sym): the tile contract of kmat_kernel (128×128 tiles, 256
+// threads, GridMap lower-tile skipping, identity padding when sym, zeros outside the valid rows / columns otherwise).
+template <typename T, int DR>
+__global__ __launch_bounds__(256) void kmat_sum_kernel(T* __restrict__ out, long ld, const T* __restrict__ xr, long ldxr,
+                                                        const T* __restrict__ xc, long ldxc, int d, const KSum k,
+                                                        const T* __restrict__ noise, long nr_valid, long nc_valid, int sym, GridMap g) {
+    using pair_t = typename Tr<T>::pair_t;
+    const int m0 = blockIdx.y * 128, n0 = blockIdx.x * 128;
+    const long gr0 = glob_idx(g.row0 + m0, g.nb, g.P, g.p);
+    const long gc0 = glob_idx(g.col0 + n0, g.nb, g.Q, g.q);
+    if (g.lower && gc0 > gr0 + 127) return;
+    __shared__ T xi[DR][128];
+    __shared__ __attribute__((aligned(16))) T xj[DR][128];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int e = tid; e < DR * 128; e += 256) {
+        const int dd = e / 128, i = e % 128;
+        xi[dd][i] = dd < d ? xr[(long)dd * ldxr + gr0 + i] : T(0);
+        xj[dd][i] = dd < d ? xc[(long)dd * ldxc + gc0 + i] : T(0);
+    }
+    __syncthreads();
+    const long gj0 = gc0 + 2 * lane, gj1 = gj0 + 1;
+    T y0[DR], y1[DR];
+#pragma unroll
+    for (int p = 0; p < DR; ++p) {
+        y0[p] = xj[p][2 * lane];
+        y1[p] = xj[p][2 * lane + 1];
+    }
+    for (int rr = 0; rr < 32; ++rr) {
+        const int row = w + 4 * rr;
+        const long gi = gr0 + row;
+        T v0, v1;
+        if (gi >= nr_valid) {  // wave-uniform
+            v0 = (sym && gi == gj0) ? T(1) : T(0);
+            v1 = (sym && gi == gj1) ? T(1) : T(0);
+        } else {
+            T t0[DR], t1[DR];
+#pragma unroll
+            for (int p = 0; p < DR; ++p) {
+                const T xv = xi[p][row];
+                t0[p] = xv - y0[p];
+                t1[p] = xv - y1[p];
+            }
+            v0 = gj0 < nc_valid ? ksum_eval<T, DR>(k, t0, d) : T(0);
+            v1 = gj1 < nc_valid ? ksum_eval<T, DR>(k, t1, d) : T(0);
+            if (sym && noise != nullptr) {
+                if (gi == gj0) v0 += noise[gi];
+                if (gi == gj1) v1 += noise[gi];
+            }
+        }
+        pair_t o;
+        o.x = v0;
+        o.y = v1;
+        *reinterpret_cast<pair_t*>(out + (long)(m0 + row) * ld + n0 + 2 * lane) = o;
+    }
+}
+
+// out[s] = Σ_i k(xs_s, x_i) α_i for the composite kernel (K_*x α without K_*x; one block per s, as kvec_kernel)
+template <typename T, int DR>
+__global__ __launch_bounds__(256) void kvec_sum_kernel(const T* __restrict__ xs, long ldxs, const T* __restrict__ x, long ldx, int d,
+                                                        const KSum k, long n, const T* __restrict__ alpha, T* __restrict__ out) {
+    __shared__ double red[4];
+    const long s = blockIdx.x;
+    T xv[DR];
+#pragma unroll
+    for (int p = 0; p < DR; ++p) xv[p] = p < d ? xs[(long)p * ldxs + s] : T(0);
+    double acc = 0;
+    for (long i = threadIdx.x; i < n; i += 256) {
+        T t[DR];
+#pragma unroll
+        for (int p = 0; p < DR; ++p) t[p] = p < d ? xv[p] - x[(long)p * ldx + i] : T(0);
+        acc += (double)(ksum_eval<T, DR>(k, t, d) * alpha[i]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) out[s] = (T)(red[0] + red[1] + red[2] + red[3]);
+}
+
+// c·∂κ_f/∂θ_q for every parameter q of factor f (scale entries, then r / α), handed to add(θ index, value); kap = κ_f.
+//   kinds 0..3: ∂κ/∂d² as kappa_and_dr2;  RQ (q = d²/(2α)): ∂κ/∂d² = −κ/(2(1+q)), ∂κ/∂α = κ (q/(1+q) − log1p q);
+//   Periodic: ∂κ/∂r_p = κ sinpi(u_p)²/r_p³, ∂κ/∂u_p = −κ (π/2) sinpi(2u_p)/r_p²;  ∂d²/∂s = 2 s r², ∂d²/∂v_p = 2 v_p t_p², ∂u_p/∂s = t_p.
+template <typename T, int DR, class Add>
+__device__ __forceinline__ void ksum_factor_grad(const KSum& k, int f, const T (&t)[DR], T r2, T kap, int d, double c, Add& add) {
+    const int kind = k.kind[f], ns = k.ns[f];
+    if (kind == 6) return;
+    const double kp = (double)kap;
+    if (kind == 4) {
+        double dsum = 0.0;  // ScaleTransform: Σ_p ∂κ/∂u_p · t_p
+#pragma unroll
+        for (int p = 0; p < DR; ++p)
+            if (p < d) {
+                const T sc = ns == 0 ? T(1) : (T)k.th[k.so[f] + (ns == 1 ? 0 : p)];
+                const T u = sc * t[p];
+                const double r = k.th[k.po[f] + p], sp = (double)sinpi_t(u);
+                add(k.po[f] + p, c * kp * sp * sp / (r * r * r));
+                if (ns != 0) {
+                    const double du = -kp * 1.5707963267948966192 * (double)sinpi_t(T(2) * u) / (r * r);
+                    if (ns == 1) dsum += du * (double)t[p];
+                    else add(k.so[f] + p, c * du * (double)t[p]);
+                }
+            }
+        if (ns == 1) add(k.so[f], c * dsum);
+        return;
+    }
+    const T d2 = ksum_d2<T, DR>(k, f, t, r2, d);
+    double dk;
+    if (kind == 5) {
+        const double a = k.th[k.po[f]], q = (double)d2 / (2.0 * a);
+        dk = -kp / (2.0 * (1.0 + q));
+        add(k.po[f], c * kp * (q / (1.0 + q) - log1p(q)));
+    } else {
+        T kk, dkt;
+        kappa_and_dr2<T>(kind, d2, kk, dkt);
+        dk = (double)dkt;
+    }
+    if (ns == 1) {
+        add(k.so[f], c * dk * 2.0 * k.th[k.so[f]] * (double)r2);
+    } else if (ns > 1) {
+#pragma unroll
+        for (int p = 0; p < DR; ++p)
+            if (p < d) add(k.so[f] + p, c * dk * 2.0 * k.th[k.so[f] + p] * (double)t[p] * (double)t[p]);
+    }
+}
+
+// ∂C_ij/∂θ of one element, times the weight w, handed to add(θ index, value): σ_t² gets Π_f κ_f, a factor's parameters get σ_t² Π_{g≠f} κ_g ∂κ_f/∂θ —
+// the product over the other factors as a running prefix times a suffix product (dividing by κ_f would fail where it underflows to 0).  The κ_f of
+// the term wait in this thread's LDS slots kf[j][tid]: the factor loop stays a loop (unrolled over 4 factors, the element body of D = 16 grew
+// beyond what the compiler inlines and went to a call frame in scratch).
+template <typename T, int DR, class Add>
+__device__ __forceinline__ void ksum_grad(const KSum& k, const T (&t)[DR], int d, double w, Add& add, double (*kf)[256], int tid) {
+    T r2;
+    bool eq;
+    ksum_r2<T, DR>(t, r2, eq);
+    for (int tt = 0; tt < k.nterms; ++tt) {
+        const int f0 = k.t0[tt], nf = k.t0[tt + 1] - f0;
+        double prod = 1.0;
+        for (int j = 0; j < nf; ++j) {
+            const double v = (double)ksum_factor<T, DR>(k, f0 + j, t, r2, eq, d);
+            kf[j][tid] = v;
+            prod *= v;
+        }
+        add(k.tv[tt], w * prod);
+        const double wv = w * k.th[k.tv[tt]];
+        double pre = 1.0;
+        for (int j = 0; j < nf; ++j) {
+            double suf = 1.0;
+            for (int i = j + 1; i < nf; ++i) suf *= kf[i][tid];
+            const double kj = kf[j][tid];
+            ksum_factor_grad<T, DR>(k, f0 + j, t, r2, (T)kj, d, wv * pre * suf, add);
+            pre *= kj;
+        }
+    }
+}
+
+// g[2 + p] += ∂logpdf/∂θ_p for p in [p0, p0 + 16) (g[0], g[1] as kgrad_kernel: unused / the noise sum of noise_grad_kernel).  One pass over the
+// lower triangle of the −C⁻¹ grad_impl forms, weights α_i α_j + (−C⁻¹)_ij halved on the diagonal, as kgrad_fast_kernel: column inputs and α_j in
+// registers, row inputs as LDS broadcasts.  The θ index of a contribution is only known at run time, so the per-thread sums live in LDS slots of
+// their own (acc[p][tid]: no atomics, no register arrays indexed at run time — those would go to scratch), reduced across the workgroup at the end.
+template <typename T, int DR>
+__global__ __launch_bounds__(256) void kgrad_sum_kernel(const T* __restrict__ Cinv, long ld, const T* __restrict__ x, long ldx, int d,
+                                                         const KSum k, const T* __restrict__ alpha, long n, double* __restrict__ g, int p0) {
+    constexpr int NP = 16;
+    const int m0 = blockIdx.y * 128, n0 = blockIdx.x * 128;
+    if (n0 > m0) return;
+    __shared__ T xi[DR][128];
+    __shared__ double acc[NP][256];
+    __shared__ double kf[KSum::MAXFT][256];
+    __shared__ double red[4][NP];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int e = tid; e < DR * 128; e += 256) {
+        const int dd = e / 128, i = e % 128;
+        xi[dd][i] = dd < d ? x[(long)dd * ldx + m0 + i] : T(0);
+    }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) acc[p][tid] = 0.0;
+    const long gj0 = n0 + 2 * lane, gj1 = gj0 + 1;
+    T xj0[DR], xj1[DR];  // the two columns by name: an array indexed by the column loop was not unrolled and went to scratch
+#pragma unroll
+    for (int p = 0; p < DR; ++p) {
+        xj0[p] = p < d ? x[(long)p * ldx + gj0] : T(0);
+        xj1[p] = p < d ? x[(long)p * ldx + gj1] : T(0);
+    }
+    const double aj0 = gj0 < n ? (double)alpha[gj0] : 0.0, aj1 = gj1 < n ? (double)alpha[gj1] : 0.0;
+    auto add = [&](int idx, double v) {
+        const unsigned q = (unsigned)(idx - p0);
+        if (q < (unsigned)NP) acc[q][tid] += v;
+    };
+    __syncthreads();
+    for (int rr = 0; rr < 32; ++rr) {
+        const int row = w + 4 * rr;
+        const long gi = m0 + row;
+        if (gi >= n) continue;  // wave-uniform
+        const double ai = (double)alpha[gi];
+        T xrow[DR];
+#pragma unroll
+        for (int p = 0; p < DR; ++p) xrow[p] = xi[p][row];
+#pragma unroll 1
+        for (int cc = 0; cc < 2; ++cc) {  // ONE call site of the (large) element body; the column is selected, not indexed
+            const long gj = gj0 + cc;
+            if (gj > gi) continue;  // gj <= gi < n
+            T t[DR];
+#pragma unroll
+            for (int p = 0; p < DR; ++p) t[p] = xrow[p] - (cc ? xj1[p] : xj0[p]);
+            const double wgt = (ai * (cc ? aj1 : aj0) + (double)Cinv[gi * ld + gj]) * (gi == gj ? 0.5 : 1.0);  // Cinv holds −C⁻¹
+            ksum_grad<T, DR>(k, t, d, wgt, add, kf, tid);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        double v = acc[p][tid];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == 0) red[w][p] = v;
+    }
+    __syncthreads();
+    if (tid < NP && p0 + tid < k.nth) atomicAdd(g + 2 + p0 + tid, red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid]);
+}
+
+// D -> instance (1 / 4 / 16); the host refuses D > 16 for composite kernels
+template <typename T>
+static inline void launch_kmat_sum(dim3 grid, hipStream_t s, T* out, long ld, const T* xr, long ldxr, const T* xc, long ldxc, int d, const KSum& k,
+                                   const T* noise, long nr_valid, long nc_valid, int sym, GridMap g) {
+    if (d <= 1) hipLaunchKernelGGL((kmat_sum_kernel<T, 1>), grid, dim3(256), 0, s, out, ld, xr, ldxr, xc, ldxc, d, k, noise, nr_valid, nc_valid, sym, g);
+    else if (d <= 4) hipLaunchKernelGGL((kmat_sum_kernel<T, 4>), grid, dim3(256), 0, s, out, ld, xr, ldxr, xc, ldxc, d, k, noise, nr_valid, nc_valid, sym, g);
+    else hipLaunchKernelGGL((kmat_sum_kernel<T, 16>), grid, dim3(256), 0, s, out, ld, xr, ldxr, xc, ldxc, d, k, noise, nr_valid, nc_valid, sym, g);
+}
+template <typename T>
+static inline void launch_kvec_sum(long ns, hipStream_t s, const T* xs, long ldxs, const T* x, long ldx, int d, const KSum& k, long n, const T* alpha, T* out) {
+    const dim3 grid((unsigned)ns);
+    if (d <= 1) hipLaunchKernelGGL((kvec_sum_kernel<T, 1>), grid, dim3(256), 0, s, xs, ldxs, x, ldx, d, k, n, alpha, out);
+    else if (d <= 4) hipLaunchKernelGGL((kvec_sum_kernel<T, 4>), grid, dim3(256), 0, s, xs, ldxs, x, ldx, d, k, n, alpha, out);
+    else hipLaunchKernelGGL((kvec_sum_kernel<T, 16>), grid, dim3(256), 0, s, xs, ldxs, x, ldx, d, k, n, alpha, out);
+}
+template <typename T>
+static inline void launch_kgrad_sum(dim3 grid, hipStream_t s, const T* Cinv, long ld, const T* x, long ldx, int d, const KSum& k, const T* alpha, long n,
+                                    double* g, int p0) {
+    if (d <= 1) hipLaunchKernelGGL((kgrad_sum_kernel<T, 1>), grid, dim3(256), 0, s, Cinv, ld, x, ldx, d, k, alpha, n, g, p0);
+    else if (d <= 4) hipLaunchKernelGGL((kgrad_sum_kernel<T, 4>), grid, dim3(256), 0, s, Cinv, ld, x, ldx, d, k, alpha, n, g, p0);
+    else hipLaunchKernelGGL((kgrad_sum_kernel<T, 16>), grid, dim3(256), 0, s, Cinv, ld, x, ldx, d, k, alpha, n, g, p0);
+}
+
 // ---- small M×M helpers of the VFE path ------------------------------------------------------------
 // dst[i][j] = -(double) src[max(i,j)][min(i,j)]   (the SYRK accumulator holds -G in its lower triangle)
 template <typename T>

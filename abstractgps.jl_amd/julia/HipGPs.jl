@@ -39,6 +39,23 @@ struct CKernel          # gp_kernel
     nscale::Int32
     scale::Ptr{Float64}
 end
+struct CKFactor         # gp_kfactor
+    kind::Int32
+    nscale::Int32
+    scale::Ptr{Float64}
+    nparam::Int32
+    param::Ptr{Float64}
+end
+struct CKTerm           # gp_kterm
+    variance::Float64
+    nfactors::Int32
+    factors::Ptr{CKFactor}
+end
+struct CKSum            # gp_ksum
+    dtype::Int32
+    nterms::Int32
+    terms::Ptr{CKTerm}
+end
 struct CPoints          # gp_points
     data::Ptr{Cvoid}
     n::Int64
@@ -113,7 +130,7 @@ end
 HipGP(gp::GP) = HipGP(gp, default_context())
 
 # internal AbstractGP API delegates to the wrapped GP (src/base_gp.jl:68-74) so that everything that is not
-# accelerated (dense Σy, composite kernels, exotic input containers) keeps working through the stock methods.
+# accelerated (dense Σy, kernels outside the composite limits, exotic input containers) keeps working through the stock methods.
 Statistics.mean(f::HipGP, x::AbstractVector) = mean(f.gp, x)
 Statistics.cov(f::HipGP, x::AbstractVector) = cov(f.gp, x)
 Statistics.var(f::HipGP, x::AbstractVector) = var(f.gp, x)
@@ -141,6 +158,88 @@ function descriptor(k::TransformedKernel{<:Any,<:ARDTransform})
     d = descriptor(k.kernel)
     (d === nothing || !isempty(d[3])) && return nothing
     return (d[1], d[2], Vector{Float64}(k.transform.v))
+end
+
+# ---- composite kernels -> normal form Σ_t σ_t² Π_f κ_f (include/gpmi355.h gp_ksum) ------------------------------------
+# sum_walk pushes the tree's own parameters into P, depth-first and left to right (ScaledKernel σ², Periodic r, RationalQuadratic α, then the
+# transform's s / v), and returns the terms as (variance slots, [(kind, scale slots, param slots)]) — products distributed over sums share
+# their slots — or `nothing` for anything the device does not evaluate (the caller then takes the stock path).
+kind_of_sum(k) = kind_of(k)
+kind_of_sum(::PeriodicKernel) = Int32(4)
+kind_of_sum(::RationalQuadraticKernel) = Int32(5)
+kind_of_sum(::WhiteKernel) = Int32(6)
+base_params(k) = Float64[]
+base_params(k::PeriodicKernel) = Vector{Float64}(k.r)
+base_params(k::RationalQuadraticKernel) = Float64[only(k.α)]
+function sum_walk(k, P)
+    kd = kind_of_sum(k)
+    kd === nothing && return nothing
+    pi = [(push!(P, v); length(P)) for v in base_params(k)]
+    return [(Int[], [(kd, Int[], pi)])]
+end
+function sum_walk(k::ScaledKernel, P)
+    push!(P, only(k.σ²)); vi = length(P)
+    t = sum_walk(k.kernel, P)
+    return t === nothing ? nothing : [([vi; v], f) for (v, f) in t]
+end
+function sum_walk(k::TransformedKernel{<:Any,<:Union{ScaleTransform,ARDTransform}}, P)
+    k.kernel isa WhiteKernel && return sum_walk(k.kernel, P)  # δ(x, x') is unchanged by a nonzero scale: the transform is dropped
+    kd = kind_of_sum(k.kernel)
+    kd === nothing && return nothing                          # a transform around a sum or product is not accelerated
+    pi = [(push!(P, v); length(P)) for v in base_params(k.kernel)]
+    sv = k.transform isa ScaleTransform ? Float64[only(k.transform.s)] : Vector{Float64}(k.transform.v)
+    si = [(push!(P, v); length(P)) for v in sv]
+    return [(Int[], [(kd, si, pi)])]
+end
+function sum_walk(k::KernelSum, P)
+    out = []
+    for c in k.kernels
+        t = sum_walk(c, P)
+        t === nothing && return nothing
+        append!(out, t)
+    end
+    return out
+end
+function sum_walk(k::KernelProduct, P)
+    out = [(Int[], [])]
+    for c in k.kernels
+        t = sum_walk(c, P)
+        t === nothing && return nothing
+        out = [([v1; v2], [f1; f2]) for (v1, f1) in out for (v2, f2) in t]
+    end
+    return out
+end
+# (P, terms) or nothing (beyond the limits of gp_ksum: the stock path); single-kind kernels keep `descriptor`, which marshal asks first
+function sum_descriptor(k)
+    P = Float64[]
+    t = sum_walk(k, P)
+    t === nothing && return nothing
+    (length(t) > 8 || any(((_, f),) -> length(f) > 4, t) || sum(((_, f),) -> length(f), t) > 16) && return nothing
+    return (P, t)
+end
+# θ of the C ABI (term by term σ_t², then per factor scale, then param) and the chain rule ∂/∂θ -> ∂/∂P
+function sum_theta(P, terms)
+    θ = Float64[]
+    for (v, f) in terms
+        push!(θ, prod(P[v]; init=1.0))
+        for (_, s, q) in f
+            append!(θ, P[s]); append!(θ, P[q])
+        end
+    end
+    return θ
+end
+function sum_chain(P, terms, gθ)
+    g = zeros(length(P)); j = 1
+    for (v, f) in terms
+        for a in eachindex(v)
+            g[v[a]] += gθ[j] * prod((P[v[b]] for b in eachindex(v) if b != a); init=1.0)
+        end
+        j += 1
+        for (_, s, q) in f, i in [s; q]
+            g[i] += gθ[j]; j += 1
+        end
+    end
+    return g
 end
 
 # ---- input / noise marshalling ---------------------------------------------------------------------
@@ -179,7 +278,7 @@ prior_mean(f::GP, x, ::Type{T}) where {T} = Vector{T}(mean_vector(f.mean, x))
 # promotion (src/finite_gp_projection.jl:309): T = promote_type(eltype(x), eltype(Y)), restricted to Float32 / Float64.
 function marshal(fx::FiniteGP{<:HipGP}, Ty::Type=input_eltype(fx.x))
     desc = descriptor(fx.f.gp.kernel)
-    desc === nothing && return nothing
+    desc === nothing && return marshal_sum(fx, Ty)
     T = hip_eltype(input_eltype(fx.x), Ty)
     px = points(fx.x, T)
     px === nothing && return nothing
@@ -191,6 +290,35 @@ function marshal(fx::FiniteGP{<:HipGP}, Ty::Type=input_eltype(fx.x))
         throw(DimensionMismatch("ARDTransform has $(length(scales)) scales, inputs have D=$(cx.d)"))
     ck = CKernel(kind, T === Float64 ? 0 : 1, variance, length(scales), isempty(scales) ? C_NULL : pointer(scales))
     return (; T, xbuf, cx, scales, ck, nbuf=nz[1], cn=nz[2], m=prior_mean(fx.f.gp, fx.x, T))
+end
+# the same for a composite kernel: `ks` (a CKSum) in place of `ck`, the descriptor's buffers kept alive in `kbuf`
+function marshal_sum(fx::FiniteGP{<:HipGP}, Ty::Type)
+    sd = sum_descriptor(fx.f.gp.kernel)
+    sd === nothing && return nothing
+    T = hip_eltype(input_eltype(fx.x), Ty)
+    px = points(fx.x, T)
+    px === nothing && return nothing
+    xbuf, cx = px
+    nz = noise(fx.Σy, T)
+    nz === nothing && return nothing
+    P, terms = sd
+    (cx.d > 16 || length(sum_theta(P, terms)) > 64) && return nothing
+    kbuf = Any[]
+    cterms = CKTerm[]
+    for (v, f) in terms
+        facs = CKFactor[]
+        for (kind, s, q) in f
+            sv, qv = P[s], P[q]
+            (length(sv) > 1 && length(sv) != cx.d) && throw(DimensionMismatch("ARDTransform has $(length(sv)) scales, inputs have D=$(cx.d)"))
+            push!(kbuf, sv, qv)
+            push!(facs, CKFactor(kind, length(sv), isempty(sv) ? C_NULL : pointer(sv), length(qv), isempty(qv) ? C_NULL : pointer(qv)))
+        end
+        push!(kbuf, facs)
+        push!(cterms, CKTerm(prod(P[v]; init=1.0), length(facs), pointer(facs)))
+    end
+    push!(kbuf, cterms)
+    ks = CKSum(T === Float64 ? 0 : 1, length(cterms), pointer(cterms))
+    return (; T, xbuf, cx, ks, kbuf, P, terms, nbuf=nz[1], cn=nz[2], m=prior_mean(fx.f.gp, fx.x, T))
 end
 stock(fx::FiniteGP{<:HipGP}) = FiniteGP(fx.f.gp, fx.x, fx.Σy)
 
@@ -204,9 +332,15 @@ function Distributions.logpdf(fx::FiniteGP{<:HipGP}, Y::AbstractVecOrMat{<:Real}
     out = Vector{T}(undef, size(Yd, 2))
     mptr = a.m === nothing ? C_NULL : pointer(a.m)
     GC.@preserve a Yd out begin
-        check(ccall((:gp_logpdf, libgpmi355), Int32,
-            (Ptr{Cvoid}, Ref{CKernel}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}),
-            fx.f.ctx.handle, a.ck, a.cx, a.cn, mptr, Yd, size(Yd, 1), size(Yd, 2), out))
+        if haskey(a, :ks)
+            check(ccall((:gp_logpdf_sum, libgpmi355), Int32,
+                (Ptr{Cvoid}, Ref{CKSum}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}),
+                fx.f.ctx.handle, a.ks, a.cx, a.cn, mptr, Yd, size(Yd, 1), size(Yd, 2), out))
+        else
+            check(ccall((:gp_logpdf, libgpmi355), Int32,
+                (Ptr{Cvoid}, Ref{CKernel}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}),
+                fx.f.ctx.handle, a.ck, a.cx, a.cn, mptr, Yd, size(Yd, 1), size(Yd, 2), out))
+        end
     end
     return Y isa AbstractVector ? out[1] : out
 end
@@ -214,7 +348,7 @@ end
 # ---- the two terms of logpdf on their own (src/finite_gp_projection.jl:313-337): sqmahal, logdetcov, gradlogpdf ----------------
 function logpdf_terms(fx::FiniteGP{<:HipGP}, Y::Union{Nothing,AbstractVecOrMat{<:Real}}; logdet::Bool, sq::Bool)
     a = marshal(fx, Y === nothing ? input_eltype(fx.x) : eltype(Y))
-    a === nothing && return nothing
+    (a === nothing || haskey(a, :ks)) && return nothing   # gp_logpdf_terms is single-kind: composite kernels take the stock path
     T = a.T
     Yd = Y === nothing ? nothing : Matrix{T}(reshape(Y, size(Y, 1), :))
     Yd === nothing || size(Yd, 1) == length(fx) || throw(DimensionMismatch("length(fx) = $(length(fx)) but Y has $(size(Yd, 1)) rows"))
@@ -264,6 +398,7 @@ end
 function logpdf_and_grad(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}; wrt_x::Bool=true)
     a = marshal(fx, eltype(y))
     a === nothing && throw(ArgumentError("kernel / noise form is not accelerated"))
+    haskey(a, :ks) && return logpdf_and_grad_sum(fx, y, a)
     T = a.T
     yv = Vector{T}(y)
     lp = Ref{T}(zero(T)); dvar = Ref{Float64}(0.0)
@@ -280,6 +415,23 @@ function logpdf_and_grad(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}; wrt_x
     end
     return lp[], (variance=dvar[], scale=dscale[1:length(a.scales)], noise=a.cn.kind == 0 ? dnoise[1] : dnoise, y=dy, mean=-dy,
         x=wrt_x ? dx : nothing)
+end
+
+# composite kernel (gp_logpdf_grad_sum): `theta` = ∂/∂θ of the C ABI, `kernel` = ∂/∂(the tree's own parameters) in sum_walk's order; no ∂/∂x
+function logpdf_and_grad_sum(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}, a)
+    T = a.T
+    yv = Vector{T}(y)
+    lp = Ref{T}(zero(T))
+    dθ = zeros(Float64, length(sum_theta(a.P, a.terms)))
+    dnoise = Vector{T}(undef, a.cn.kind == 0 ? 1 : length(yv))
+    dy = Vector{T}(undef, length(yv))
+    mptr = a.m === nothing ? C_NULL : pointer(a.m)
+    GC.@preserve a yv dθ dnoise dy begin
+        check(ccall((:gp_logpdf_grad_sum, libgpmi355), Int32,
+            (Ptr{Cvoid}, Ref{CKSum}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{T}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}),
+            fx.f.ctx.handle, a.ks, a.cx, a.cn, mptr, yv, lp, dθ, dnoise, dy))
+    end
+    return lp[], (theta=dθ, kernel=sum_chain(a.P, a.terms, dθ), noise=a.cn.kind == 0 ? dnoise[1] : dnoise, y=dy, mean=-dy, x=nothing)
 end
 
 # ---- reverse-mode rule: Zygote / any ChainRules-based AD differentiates THROUGH the ccall -----------------------------------
@@ -303,6 +455,32 @@ function kernel_tangent(k::TransformedKernel{<:Any,<:ARDTransform}, dvar, varian
     return Tangent{typeof(k)}(; kernel=kernel_tangent(k.kernel, dvar, variance, dscale),
         transform=Tangent{typeof(k.transform)}(; v=collect(dscale)))
 end
+# composite kernels: ∂/∂(the tree's own parameters) handed out node by node, in sum_walk's order (KernelSum / KernelProduct: a tuple of tangents)
+sum_tangent(k, g, pos) = NoTangent()
+function sum_tangent(k::ScaledKernel, g, pos)
+    d = g[pos[]]; pos[] += 1
+    return Tangent{typeof(k)}(; kernel=sum_tangent(k.kernel, g, pos), σ²=[d])
+end
+function sum_tangent(k::PeriodicKernel, g, pos)
+    n = length(k.r); d = g[pos[]:pos[]+n-1]; pos[] += n
+    return Tangent{typeof(k)}(; r=d)
+end
+function sum_tangent(k::RationalQuadraticKernel, g, pos)
+    d = g[pos[]]; pos[] += 1
+    return Tangent{typeof(k)}(; α=[d])
+end
+sum_tangent(k::WhiteKernel, g, pos) = NoTangent()
+function sum_tangent(k::TransformedKernel{<:Any,<:Union{ScaleTransform,ARDTransform}}, g, pos)
+    k.kernel isa WhiteKernel && return NoTangent()
+    dk = sum_tangent(k.kernel, g, pos)
+    if k.transform isa ScaleTransform
+        dt = Tangent{typeof(k.transform)}(; s=[g[pos[]]]); pos[] += 1
+    else
+        n = length(k.transform.v); dt = Tangent{typeof(k.transform)}(; v=g[pos[]:pos[]+n-1]); pos[] += n
+    end
+    return Tangent{typeof(k)}(; kernel=dk, transform=dt)
+end
+sum_tangent(k::Union{KernelSum,KernelProduct}, g, pos) = Tangent{typeof(k)}(; kernels=Tuple(sum_tangent(c, g, pos) for c in k.kernels))
 mean_tangent(::ZeroMean, dm) = NoTangent()
 mean_tangent(m::ConstMean, dm) = Tangent{typeof(m)}(; c=sum(dm))
 mean_tangent(m, dm) = ChainRulesCore.@not_implemented("HipGPs: gradients w.r.t. CustomMean parameters go through the stock path")
@@ -315,7 +493,7 @@ noise_tangent(Σ::Diagonal, dn) = Tangent{typeof(Σ)}(; diag=dn)
 function ChainRulesCore.rrule(config::RuleConfig{>:HasReverseMode}, ::typeof(Distributions.logpdf), fx::FiniteGP{<:HipGP},
     y::AbstractVector{<:Real})
     desc = descriptor(fx.f.gp.kernel)
-    if desc === nothing || marshal(fx, eltype(y)) === nothing   # not accelerated: the stock path keeps its own AD
+    if marshal(fx, eltype(y)) === nothing   # not accelerated: the stock path keeps its own AD (composite kernels: sum_tangent below)
         lp0, back = rrule_via_ad(config, (g_, x_, Σ_, y_) -> logpdf(FiniteGP(g_, x_, Σ_), y_), fx.f.gp, fx.x, fx.Σy, y)
         return lp0, function (Δ)
             _, dg, dx, dΣ, dy = back(Δ)
@@ -326,10 +504,12 @@ function ChainRulesCore.rrule(config::RuleConfig{>:HasReverseMode}, ::typeof(Dis
     function logpdf_hip_pullback(Δ)
         Δr = unthunk(Δ)
         gp = fx.f.gp
-        dk = kernel_tangent(gp.kernel, Δr * g.variance, desc[2], Δr .* g.scale)
+        dk = desc === nothing ? sum_tangent(gp.kernel, Δr .* g.kernel, Ref(1)) : kernel_tangent(gp.kernel, Δr * g.variance, desc[2], Δr .* g.scale)
         dgp = Tangent{typeof(gp)}(; mean=mean_tangent(gp.mean, Δr .* g.mean), kernel=dk)
         df = Tangent{typeof(fx.f)}(; gp=dgp, ctx=NoTangent())
-        dfx = Tangent{typeof(fx)}(; f=df, x=input_tangent(fx.x, g.x, Δr), Σy=noise_tangent(fx.Σy, Δr .* g.noise))
+        # composite kernels: ∂/∂x is not computed on the device — refused loudly (a NoTangent would claim x is not differentiable)
+        dx = g.x === nothing ? ChainRulesCore.@not_implemented("HipGPs: ∂/∂x of a composite kernel is not accelerated") : input_tangent(fx.x, g.x, Δr)
+        dfx = Tangent{typeof(fx)}(; f=df, x=dx, Σy=noise_tangent(fx.Σy, Δr .* g.noise))
         return NoTangent(), dfx, Δr .* g.y
     end
     return lp, logpdf_hip_pullback
@@ -389,9 +569,15 @@ function AbstractGPs.posterior(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real})
     h = Ref{Ptr{Cvoid}}(C_NULL)
     mptr = a.m === nothing ? C_NULL : pointer(a.m)
     GC.@preserve a yv α begin
-        check(ccall((:gp_posterior_fit, libgpmi355), Int32,
-            (Ptr{Cvoid}, Ref{CKernel}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Ref{T}),
-            fx.f.ctx.handle, a.ck, a.cx, a.cn, mptr, yv, h, α, lp))
+        if haskey(a, :ks)   # a composite kernel: the handle keeps it, every posterior method below works on it unchanged
+            check(ccall((:gp_posterior_fit_sum, libgpmi355), Int32,
+                (Ptr{Cvoid}, Ref{CKSum}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Ref{T}),
+                fx.f.ctx.handle, a.ks, a.cx, a.cn, mptr, yv, h, α, lp))
+        else
+            check(ccall((:gp_posterior_fit, libgpmi355), Int32,
+                (Ptr{Cvoid}, Ref{CKernel}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Ref{T}),
+                fx.f.ctx.handle, a.ck, a.cx, a.cn, mptr, yv, h, α, lp))
+        end
     end
     return HipPosteriorGP(fx.f, (α=α, C=device_cholesky(h[], length(yv), T), x=fx.x, δ=δ), Float64(lp[]))
 end
@@ -583,7 +769,7 @@ function vfe_call(approx::Union{VFE,DTC}, fx::FiniteGP{<:HipGP}, y::AbstractVect
     @assert approx.fz.f === fx.f                                                       # :59, :249, :283
     length(fx) == length(y) || throw(DimensionMismatch("length(fx) != length(y)"))    # :290-294
     a = marshal(fx, eltype(y))
-    a === nothing && return nothing
+    (a === nothing || haskey(a, :ks)) && return nothing   # VFE / DTC are single-kind: composite kernels take the stock path
     T = a.T
     pz = points(approx.fz.x, T)
     pz === nothing && return nothing

@@ -54,6 +54,39 @@ typedef struct {
     const double* scale;
 } gp_kernel;
 
+/* Composite kernel: Σ_t σ_t² · Π_f κ_f — the normal form of any KernelSum / KernelProduct / ScaledKernel tree (products
+ * distributed over sums, the ScaledKernel factors on a path multiplied into σ_t²).  A FACTOR is a base kernel behind its own
+ * transform T_f (nscale / scale as in gp_kernel: none, ScaleTransform(s), ARDTransform(v)); u = T_f(x) − T_f(x'), d² = ‖u‖²:
+ *   kind 0..3  as gp_kernel (SqExponential, Matern12, Matern32, Matern52)                            nparam 0
+ *   kind 4     PeriodicKernel(; r), metric Sinus(r):  exp(−½ Σ_p (sinpi(u_p) / r_p)²),  r_p > 0        nparam D (param = r)
+ *              (with_lengthscale(Per, p) = ScaleTransform(1/p) gives period p)
+ *   kind 5     RationalQuadraticKernel(; α):  (1 + d²/(2α))^(−α) = exp(−α·log1p(d²/(2α))),  α > 0  nparam 1 (param = α)
+ *   kind 6     WhiteKernel():  1 if x and x' are equal in every coordinate, else 0; takes no transform  nparam 0
+ * Every κ_f(x, x) = 1, so the prior variance is Σ_t σ_t²; White adds to a cross-covariance wherever a test point equals a training
+ * point exactly (as KernelFunctions does).
+ * Limits: 1..8 terms, 1..4 factors per term, at most 16 factors in all, D <= 16, at most 64 entries in θ.  Outside them, or with a
+ * malformed descriptor (variance <= 0, a param count or value that breaks the table, a transform on White), the *_sum calls return
+ * −2 (the descriptor argument) with the reason in gp_last_error().
+ * θ (the flat parameter vector of gp_logpdf_grad_sum): term by term σ_t², then for each of its factors scale[0..nscale) and then
+ * param[0..nparam). */
+typedef struct {
+    int32_t kind;
+    int32_t nscale;
+    const double* scale;
+    int32_t nparam;
+    const double* param;
+} gp_kfactor;
+typedef struct {
+    double variance;
+    int32_t nfactors;
+    const gp_kfactor* factors;
+} gp_kterm;
+typedef struct {
+    int32_t dtype;
+    int32_t nterms;
+    const gp_kterm* terms;
+} gp_ksum;
+
 /* Inputs (host).  layout: 0 = Vector{T} (d must be 1); 1 = ColVecs(X), X is d×n column-major
  * (point-contiguous); 2 = RowVecs(X), X is n×d column-major (dimension-contiguous).
  * src/finite_gp_projection.jl:32-37. */
@@ -292,6 +325,24 @@ int32_t gp_posterior_rand(gp_post* post, const gp_points* xs, const void* prior_
 int32_t gp_logpdf_grad(gp_ctx* ctx, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null,
                        const void* y, void* logpdf_out, double* dvariance_out, double* dscale_out, void* dnoise_out,
                        void* dy_out, void* dx_out);
+
+/* ---- exact GP with a composite kernel (gp_ksum above) ------------------------------------------------------------------ */
+/* The same contracts as gp_kernelmatrix / gp_logpdf / gp_posterior_fit / gp_logpdf_grad with a gp_ksum in place of the gp_kernel.
+ * Assembly, the predictive mean and the gradient pass evaluate the composite kernel on the device (kmat_sum_kernel, kvec_sum_kernel,
+ * kgrad_sum_kernel); everything after the Gram matrix is the single-kind path.  A handle from gp_posterior_fit_sum keeps its composite
+ * kernel: every gp_posterior_* entry point works on it unchanged.  The assembly and mean kernels use no floating-point atomics, so
+ * "deterministic" = 1 covers composite fits as well.  On a multi-device ctx these calls run on the single-device engine of the ctx's
+ * first device (the 2-D block-cyclic driver is single-kind).
+ * gp_logpdf_grad_sum: dtheta_out (fp64, one entry per θ entry in the order documented at gp_ksum) = ∂logpdf/∂θ; dnoise_out and dy_out
+ * as in gp_logpdf_grad.  ∂/∂x is not offered for composite kernels, nor is gp_logpdf_terms; VFE / DTC stay single-kind. */
+int32_t gp_kernelmatrix_sum(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, const gp_points* y_or_null, void* out);
+int32_t gp_logpdf_sum(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null,
+                      const void* Y, int64_t ldy, int32_t ncols, void* out);
+int32_t gp_posterior_fit_sum(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null,
+                             const void* y, gp_post** out, void* alpha_out_or_null, void* logpdf_out_or_null);
+int32_t gp_logpdf_grad_sum(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null,
+                           const void* y, void* logpdf_out, double* dtheta_out_or_null, void* dnoise_out_or_null,
+                           void* dy_out_or_null);
 
 /* Sequential conditioning, posterior(fx::FiniteGP{<:PosteriorGP}, y) (src/exact_gpr_posterior.jl:46-56): the resident
  * factor of `old` is extended by the bordered-Cholesky step update_chol (src/util/common_covmat_ops.jl:38-42):
