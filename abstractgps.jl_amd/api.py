@@ -433,7 +433,20 @@ class _Marshal:
                 raise ValueError("DimensionMismatch: noise vector length != number of points")
             v = self.arr(s)
             return gp_noise(1, 0.0, v.ctypes.data)
-        raise NotImplementedError("dense Σy is outside the accelerated path (falls back to stock AbstractGPs in the Julia shim)")
+        # dense Σy: the engine reads ONE triangle of an n×n column-major array (include/gpmi355.h gp_noise: kind 2 upper, kind 3 lower).  The mirror always
+        # means the UPPER triangle of the array the user passed, as Symmetric(Σy) does (src/util/common_covmat_ops.jl:5): a C-ordered array is the column-major
+        # array of its transpose — its upper triangle is that one's lower (kind 3, zero-copy); a Fortran-ordered array is column-major as it lies (kind 2,
+        # zero-copy); anything else (strided, another dtype) is copied once into C order.
+        if s.ndim != 2 or s.shape != (n, n):
+            raise ValueError(f"DimensionMismatch: noise covariance has shape {s.shape}, expected ({n},) or ({n}, {n})")
+        if s.dtype == self.dtype and s.flags.c_contiguous:
+            self.keep.append(s)
+            return gp_noise(3, 0.0, s.ctypes.data)
+        if s.dtype == self.dtype and s.flags.f_contiguous:
+            self.keep.append(s)
+            return gp_noise(2, 0.0, s.ctypes.data)
+        v = self.arr(s)
+        return gp_noise(3, 0.0, v.ctypes.data)
 
 
 def _input_dim(x) -> int:
@@ -599,8 +612,19 @@ class FiniteGP:
         return _npoints(self.x)
 
     def noise_vector(self):
+        """diag(Σy): what var / mean_and_var / marginals add (src/finite_gp_projection.jl:115-116, 156-157)."""
         s = np.asarray(self.sigma2)
+        if s.ndim == 2:
+            return np.diagonal(s).copy()
         return np.full(len(self), float(s)) if s.ndim == 0 else s
+
+    def noise_matrix_or_none(self):
+        """Symmetric(Σy) for a dense Σy (the upper triangle of the array, mirrored), None for a scalar / vector one."""
+        s = np.asarray(self.sigma2)
+        if s.ndim != 2:
+            return None
+        u = np.triu(s)
+        return u + np.triu(s, 1).T
 
     def _prior_factor(self):
         """Device-resident factor of cov(fx) = K + Σy for a GP prior, computed once per FiniteGP object and reused by
@@ -723,11 +747,17 @@ def gradlogpdf(fx: FiniteGP, y):
         post.data.C.free()
 
 
+def _dnoise_shape(nz: gp_noise, n: int):
+    """dnoise_out of gp_logpdf_grad: 1 entry (scalar Σy), n (Diagonal), n×n (dense: symmetric, so column-major == row-major)."""
+    return 1 if nz.kind == 0 else (n if nz.kind == 1 else (n, n))
+
+
 def logpdf_and_grad(fx: FiniteGP, y, wrt_x: bool = False) -> tuple:
     """Value and gradient of logpdf(fx, y) for the rrule of the accelerated path (the reference differentiates the same
     expression by AD — test/finite_gp_projection.jl:152-178).  Returns (logpdf, grads) with grads =
-    {"variance": ∂/∂σ_k², "scale": ∂/∂s (ScaleTransform) or ∂/∂v (ARDTransform) or None, "noise": ∂/∂σ² (scalar Σy) or the
-    vector ∂/∂Σy_ii, "y": −α, "mean": +α} and, with wrt_x, "x": ∂/∂x in the shape of the input container's array.
+    {"variance": ∂/∂σ_k², "scale": ∂/∂s (ScaleTransform) or ∂/∂v (ARDTransform) or None, "noise": ∂/∂σ² (scalar Σy), the
+    vector ∂/∂Σy_ii, or for a dense Σy the (n, n) symmetric matrix G = ½(ααᵀ − C⁻¹) with d logpdf = ⟨G, dΣy⟩ for symmetric dΣy (a parametric Σy(φ) chains
+    as ⟨G, ∂Σy/∂φ⟩), "y": −α, "mean": +α} and, with wrt_x, "x": ∂/∂x in the shape of the input container's array.
     A composite kernel (sums, products, Periodic / RationalQuadratic / White) returns "kernel": ∂/∂params(k) in the order of params(k), and "theta":
     the gradient against the flat θ of include/gpmi355.h (gp_logpdf_grad_sum), in place of "variance" / "scale"; wrt_x is not offered for it."""
     y = _check_y(fx, y)
@@ -751,7 +781,7 @@ def logpdf_and_grad(fx: FiniteGP, y, wrt_x: bool = False) -> tuple:
             raise NotImplementedError("∂/∂x of a composite kernel is not accelerated")
         ks, nf = m.ksum(f.kernel, px.d)
         dth = (C.c_double * max(len(nf.theta()), 1))()
-        dnoise = np.empty(1 if nz.kind == 0 else px.n, dtype=dt)
+        dnoise = np.empty(_dnoise_shape(nz, px.n), dtype=dt)
         dy = np.empty(px.n, dtype=dt)
         check(ctx.lib.gp_logpdf_grad_sum(ctx.handle, C.byref(ks), C.byref(px), C.byref(nz), m.ptr(mean), yv.ctypes.data, lp.ctypes.data, dth,
                                          dnoise.ctypes.data, dy.ctypes.data))
@@ -759,7 +789,7 @@ def logpdf_and_grad(fx: FiniteGP, y, wrt_x: bool = False) -> tuple:
         return lp[0], {"kernel": nf.chain(gth), "theta": gth, "noise": dnoise[0] if nz.kind == 0 else dnoise, "y": dy, "mean": -dy}
     dvar = C.c_double()
     dscale = (C.c_double * max(kk.nscale, 1))()
-    dnoise = np.empty(1 if nz.kind == 0 else px.n, dtype=dt)
+    dnoise = np.empty(_dnoise_shape(nz, px.n), dtype=dt)
     dy = np.empty(px.n, dtype=dt)
     # ∂/∂x comes back in the ABI layout of the inputs: (n,) vector; ColVecs (N, D) C-order = D×N column-major; RowVecs (D, N)
     dxb = None
@@ -1026,6 +1056,9 @@ def cov(fx_or_f, x=None, z=None):
             assert fx.f is x.f
             return fx.f.cov(fx.x, x.x)
         Cm = np.array(fx.f.cov(fx.x))
+        S = fx.noise_matrix_or_none()
+        if S is not None:  # cov(f, x) + Σy with a dense Σy  :96, :135
+            return Cm + S.astype(Cm.dtype, copy=False)
         Cm[np.diag_indices_from(Cm)] += fx.noise_vector()
         return Cm
     return fx_or_f.cov(x, z)
@@ -1077,6 +1110,12 @@ class _VfeState:
         self._fin = weakref.finalize(self, ctx.lib.gp_vfe_free, handle)
 
 
+def _refuse_dense_vfe(fx: FiniteGP):
+    if np.ndim(fx.sigma2) == 2:
+        raise NotImplementedError("VFE / DTC with a dense Σy are not accelerated: the reference factors Σy there (an N×N Cholesky that defeats the sparse cost, "
+                                  "src/sparse_approximations.jl:61, :97) and its elbo has no method for a dense Σy (:307-313); the exact path takes a dense Σy")
+
+
 def _vfe_call(approx, fx: FiniteGP, y, want_post: bool):
     y = _check_y(fx, y)
     if y.ndim != 1:
@@ -1089,6 +1128,7 @@ def _vfe_call(approx, fx: FiniteGP, y, want_post: bool):
     if _is_composite(f.kernel):
         raise NotImplementedError("VFE / DTC with a composite kernel are not accelerated (the Julia shim falls back to stock AbstractGPs; "
                                   "the exact path takes composite kernels)")
+    _refuse_dense_vfe(fx)
     ctx = f.context()
     dt = np.result_type(_input_dtype(fx.x), np.float32 if y.dtype == np.float32 else np.float64).type
     m = _Marshal(dt)
@@ -1276,6 +1316,7 @@ def update_posterior(f_post_approx: ApproxPosteriorGP, fx: FiniteGP, y=None):
         approx = type(f_post_approx.approx)(f_post_approx.prior(z_all, f_post_approx.approx.fz.sigma2))  # _update_approx (:178-179)
         return ApproxPosteriorGP(approx, f_post_approx.prior, _VfeState(st.ctx, h), dt, f_post_approx._m + pz.n, obj[0])
     y = _check_y(fx, y)
+    _refuse_dense_vfe(fx)
     px = mm.points(fx.x)
     nz = mm.noise(fx.sigma2, px.n)
     mean = _mean_vector(f_post_approx.prior.mean_fn, fx.x, dt)

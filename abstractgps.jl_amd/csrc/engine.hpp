@@ -134,6 +134,8 @@ struct gp_ctx {
     int xcd_swizzle = 0;   // XCD-aware super-tile order of the MFMA gemm workgroups
     long xcd_min_tiles = 256;
     long ldpad = 32;       // elements of padding per row: de-aliases power-of-two strides across HBM channels
+    long dense_stage_mb = 64;  // dense Σy (noise kind 2 / 3): MiB per staging buffer of the streamed upload / gradient download (two page-locked + two device buffers;
+                               // a piece is never shorter than 128 rows or columns)
     gp_timings tm{};
     std::vector<FreeBlock> pool;               // cached free device blocks (true sizes)
     std::unordered_map<void*, size_t> blk;     // true size of every block handed out by ctx_alloc

@@ -18,6 +18,7 @@
 #include <set>
 #include <memory>
 #include <string>
+#include <thread>
 #include <type_traits>
 #include <unordered_map>
 #include <vector>
@@ -954,6 +955,125 @@ template <typename T> static int32_t assemble_sym(gp_ctx* c, const KDesc& k, con
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Dense Σy (gp_noise kind 2 / 3, include/gpmi355.h): the named triangle of the caller's n×n column-major host array is streamed onto the n×n block at A
+// (row-major, lower tiles) in pieces of at most "dense_stage_mb" MiB: host array -> page-locked half (host threads) -> device half (panel stream) -> add
+// kernel (main stream).  Two halves of each, so the three stages of neighbouring pieces overlap; no second N×N buffer exists anywhere.  kind 2: a piece is a
+// block of device rows (= host columns, rows 0..i), kind 3 a block of device columns (= host columns, rows j..n−1).  Returns with the last adds queued on
+// the main stream; every byte of the host array has been read by then.  TA: matrix type, TS: type of the host array.
+// ------------------------------------------------------------------------------------------------
+static inline bool noise_dense(const gp_noise* nz) { return nz && (nz->kind == 2 || nz->kind == 3); }
+// the diagonal of kinds 0 / 1 as the Gram kernels take it; a dense Σy is added afterwards (dense_add), its vector is zero
+template <typename TC, typename TIO> static inline TC noise_entry(const gp_noise* nz, long i) {
+    return nz->kind == 0 ? (TC)nz->s : (nz->kind == 1 ? (TC)((const TIO*)nz->diag)[i] : TC(0));
+}
+static int dense_host_threads() {  // host threads that fill one page-locked piece (environment GPMI_DENSE_THREADS, 1..16; measured: profiles/r8/dense_threads_ab.json)
+    static const int nt = []() {
+        const char* e = getenv("GPMI_DENSE_THREADS");
+        const int v = e ? atoi(e) : 4;
+        return v < 1 ? 1 : (v > 16 ? 16 : v);
+    }();
+    return nt;
+}
+template <typename F> static void dense_host_runs(long cnt, size_t bytes, F&& f) {  // f(lo, hi) over the runs [0, cnt) of one piece
+    const int nt = (bytes >= ((size_t)8 << 20) && cnt >= 16) ? dense_host_threads() : 1;
+    if (nt == 1) {
+        f(0L, cnt);
+        return;
+    }
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; ++t) th.emplace_back([&, t]() { f(cnt * t / nt, cnt * (t + 1) / nt); });
+    f(0L, cnt / nt);
+    for (auto& x : th) x.join();
+}
+static long dense_piece(gp_ctx* c, long n, size_t elt) {  // rows / columns per piece: a multiple of 128 within the staging budget, at least 128
+    const long budget = (long)(((size_t)c->dense_stage_mb << 20) / elt);
+    return std::max(128L, budget / round_up(n, 4) / 128 * 128);
+}
+template <typename TA, typename TS>
+static int32_t dense_add(gp_ctx* c, DevBufs& bufs, TA* A, long ld, const gp_noise* nz, long n) {
+    const TS* H = (const TS*)nz->diag;
+    const bool by_rows = nz->kind == 2;
+    const long pr = dense_piece(c, n, sizeof(TS));
+    const size_t buf_b = (size_t)round_up((long)sizeof(TS) * std::min(pr, n) * round_up(n, 4), 256);
+    void* dev_v = nullptr;
+    RC(bufs.get(2 * buf_b, &dev_v));
+    char* pin = (char*)ctx_pinned(c, 2 * buf_b);
+    if (!pin) return set_err_text(-1000 - (int)hipErrorOutOfMemory, "dense noise: no page-locked staging (lower \"dense_stage_mb\")");
+    hipEvent_t copied[2], added[2];
+    for (int b = 0; b < 2; ++b) {
+        RC(ctx_event(c, &copied[b], false));
+        RC(ctx_event(c, &added[b], false));
+    }
+    constexpr int E = 16 / sizeof(TS);
+    long p = 0;
+    for (long p0 = 0; p0 < n; p0 += pr, ++p) {
+        const int b = (int)(p & 1);
+        const long cnt = std::min(pr, n - p0);
+        TS* hp = (TS*)(pin + b * buf_b);
+        TS* dp = (TS*)((char*)dev_v + b * buf_b);
+        const long w = by_rows ? round_up(p0 + cnt, 4) : round_up(n - p0, 4);
+        if (p >= 2) HIPCHK(hipEventSynchronize(copied[b]));  // the upload out of this page-locked half is done
+        if (by_rows)
+            dense_host_runs(cnt, sizeof(TS) * (size_t)cnt * w, [&](long lo, long hi) {
+                for (long r = lo; r < hi; ++r) memcpy(hp + r * w, H + (size_t)(p0 + r) * n, sizeof(TS) * (size_t)(p0 + r + 1));
+            });
+        else
+            dense_host_runs(cnt, sizeof(TS) * (size_t)cnt * w, [&](long lo, long hi) {
+                for (long r = lo; r < hi; ++r) memcpy(hp + r * w + r, H + (size_t)(p0 + r) * n + (p0 + r), sizeof(TS) * (size_t)(n - p0 - r));
+            });
+        if (p >= 2) HIPCHK(hipStreamWaitEvent(c->sp, added[b], 0));  // the add that read this device half is done
+        HIPCHK(hipMemcpyAsync(dp, hp, sizeof(TS) * (size_t)cnt * w, hipMemcpyHostToDevice, c->sp));
+        HIPCHK(hipEventRecord(copied[b], c->sp));
+        HIPCHK(hipStreamWaitEvent(c->sm, copied[b], 0));
+        if (by_rows) {
+            const long ncol = std::min(n, round_up(p0 + cnt, 128));
+            hipLaunchKernelGGL((dense_add_rows_kernel<TA, TS>), dim3((unsigned)((ncol + 256 * E - 1) / (256 * E)), (unsigned)std::min(cnt, 65535L)), dim3(256), 0,
+                               c->sm, A, ld, (const TS*)dp, w, p0, cnt, n);
+        } else {
+            hipLaunchKernelGGL((dense_add_cols_kernel<TA, TS>), dim3((unsigned)((cnt + 63) / 64), (unsigned)((n - p0 + 63) / 64)), dim3(256), 0, c->sm, A, ld,
+                               (const TS*)dp, w, p0, n);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(added[b], c->sm));
+    }
+    return 0;
+}
+// G = ½(α αᵀ − C⁻¹) (n×n, symmetric: column-major == row-major) to the caller's host array in row blocks: kernel -> device half -> page-locked half on the
+// stream, the copy into the pageable array on the host while the next block is on its way.  Cinv: −C⁻¹, lower, row-major.
+template <typename T>
+static int32_t dense_grad_out(gp_ctx* c, hipStream_t s, DevBufs& bufs, const T* Cinv, long ld, const T* alpha, long n, T* out) {
+    const long budget = (long)(((size_t)c->dense_stage_mb << 20) / sizeof(T));
+    const long pr = std::max(64L, budget / n / 64 * 64);
+    const size_t buf_b = (size_t)round_up((long)sizeof(T) * std::min(pr, round_up(n, 64)) * n, 256);
+    void* dev_v = nullptr;
+    RC(bufs.get(2 * buf_b, &dev_v));
+    char* pin = (char*)ctx_pinned(c, 2 * buf_b);
+    if (!pin) return set_err_text(-1000 - (int)hipErrorOutOfMemory, "dense noise gradient: no page-locked staging (lower \"dense_stage_mb\")");
+    hipEvent_t done[2];
+    for (int b = 0; b < 2; ++b) RC(ctx_event(c, &done[b], false));
+    const long np_ = (n + pr - 1) / pr;
+    auto drain = [&](long q) -> int32_t {  // piece q: wait for its download, copy it to the caller
+        const int b = (int)(q & 1);
+        HIPCHK(hipEventSynchronize(done[b]));
+        const long r0 = q * pr, cnt = std::min(pr, n - r0);
+        memcpy(out + (size_t)r0 * n, pin + b * buf_b, sizeof(T) * (size_t)cnt * n);
+        return 0;
+    };
+    for (long q = 0; q < np_; ++q) {
+        const int b = (int)(q & 1);
+        if (q >= 2) RC(drain(q - 2));
+        const long r0 = q * pr, cnt = std::min(pr, n - r0);
+        T* dp = (T*)((char*)dev_v + b * buf_b);
+        hipLaunchKernelGGL(dense_grad_rows_kernel<T>, dim3((unsigned)((n + 63) / 64), (unsigned)((cnt + 63) / 64)), dim3(256), 0, s, Cinv, ld, alpha, n, r0, cnt, dp);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(pin + b * buf_b, dp, sizeof(T) * (size_t)cnt * n, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipEventRecord(done[b], s));
+    }
+    for (long q = std::max(0L, np_ - 2); q < np_; ++q) RC(drain(q));
+    return 0;
+}
+
 struct FitOut {
     std::vector<double> logpdf;  // per RHS column
     double logdet = 0;           // logdet(K + Σy)            (src/finite_gp_projection.jl:310)
@@ -987,7 +1107,7 @@ static int32_t fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const
     std::vector<T> xs_h;
     scale_points<T>(k, x, np, xs_h);
     std::vector<T> noise_h((size_t)np, T(0));
-    for (long i = 0; i < n; ++i) noise_h[i] = noise->kind == 0 ? (T)noise->s : ((const T*)noise->diag)[i];
+    for (long i = 0; i < n; ++i) noise_h[i] = noise_entry<T, T>(noise, i);
     std::vector<T> rhs_h((size_t)ncols * np, T(0));  // rows: δ_sᵀ = (Y[:,s] - m)ᵀ, zero padded
     for (int s = 0; s < ncols; ++s)
         for (long i = 0; i < n; ++i) rhs_h[(size_t)s * np + i] = Y[(size_t)s * ldy + i] - (mean ? mean[i] : T(0));
@@ -1014,6 +1134,7 @@ static int32_t fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const
         HIPCHK(hipMemcpy2DAsync(A + np * ld, sizeof(T) * ld, rhs_h.data(), sizeof(T) * np, sizeof(T) * np, ncols,
                                 hipMemcpyHostToDevice, c->sm));
         RC(assemble_sym<T>(c, kdesc(k, ks), (const T*)xs_v, np, d, (const T*)noise_v, n, np, A, ld));
+        if (noise_dense(noise)) RC((dense_add<T, T>(c, bufs, A, ld, noise, n)));  // all of Σy before the factorisation (counts into assemble_ms)
         HIPCHK(hipEventRecord(c->ev_phase[1], c->sm));
         RC(potrf_full<T>(c, A, ld, np, mtot, c->info_dev, n, c->scal_dev));
         HIPCHK(hipEventRecord(c->ev_phase[2], c->sm));
@@ -1275,6 +1396,7 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
         hipLaunchKernelGGL(noise_grad_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const T*)Ci, ld,
                            (const T*)post.alpha, n, (T*)dn_v, (double*)g_v + 1);
         HIPCHK(hipGetLastError());
+        if (dnoise && noise_dense(noise)) RC(dense_grad_out<T>(c, s, bufs, (const T*)Ci, ld, (const T*)post.alpha, n, (T*)dnoise));  // G = ½(ααᵀ − C⁻¹), n×n
         if (dx) {  // ∂/∂x: full-square pass (the mirrored C⁻¹ entry serves the tiles above the diagonal), 16 dimensions per launch
             HIPCHK(hipMemsetAsync(gx_v, 0, gx_b, s));
             for (int p0 = 0; p0 < d; p0 += 16) {
@@ -1302,7 +1424,7 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
         for (int p = 0; p < ks->nth; ++p) dtheta[p] = g_h[2 + p];
     if (dnoise) {
         if (noise->kind == 0) *(T*)dnoise = (T)g_h[1];
-        else memcpy(dnoise, dn_h.data(), sizeof(T) * (size_t)n);
+        else if (noise->kind == 1) memcpy(dnoise, dn_h.data(), sizeof(T) * (size_t)n);  // (dense: written above)
     }
     if (dy)
         for (long i = 0; i < n; ++i) ((T*)dy)[i] = -alpha_h[i];
@@ -1342,7 +1464,7 @@ static int32_t update_impl(gp_post* old, const gp_points* x2, const gp_noise* no
     std::vector<T> x2s_h;
     scale_points<T>(&k, x2, n2p, x2s_h);  // [d][n2p]
     std::vector<T> noise_h((size_t)n2p, T(0));
-    for (long i = 0; i < n2; ++i) noise_h[i] = noise2->kind == 0 ? (T)noise2->s : ((const T*)noise2->diag)[i];
+    for (long i = 0; i < n2; ++i) noise_h[i] = noise_entry<T, T>(noise2, i);
     std::vector<T> delta_h((size_t)np, T(0));
     memcpy(delta_h.data(), delta_all, sizeof(T) * (size_t)n);
 
@@ -1390,6 +1512,7 @@ static int32_t update_impl(gp_post* old, const gp_points* x2, const gp_noise* no
             HIPCHK(hipGetLastError());
         }
         RC(launch_gemm<T>(c, s, S, lds, X, ldx, X, ldx, n2p, n2p, np1, plain_map(1, 0, 0)));
+        if (noise_dense(noise2)) RC((dense_add<T, T>(c, bufs, S, lds, noise2, n2)));                         // C22 = cov(prior, x2) + Σy2      :50
         RC(potrf_full<T>(c, S, lds, n2p, n2p, c->info_dev, n2, c->scal_dev));
         // new factor [L11 0; U12ᵀ U22ᵀ], identity padding, δ as the right-hand side                          :41
         HIPCHK(hipMemsetAsync(A + np * ld, 0, sizeof(T) * (size_t)(128 + 128) * ld, s));
@@ -1497,7 +1620,7 @@ template <typename TC, typename TIO>
 static void noise_to(const gp_noise* noise, long ns, long nsp, std::vector<TC>& out) {
     out.assign((size_t)nsp, TC(0));
     if (!noise) return;
-    for (long i = 0; i < ns; ++i) out[i] = noise->kind == 0 ? (TC)noise->s : (TC)((const TIO*)noise->diag)[i];
+    for (long i = 0; i < ns; ++i) out[i] = noise_entry<TC, TIO>(noise, i);
 }
 
 template <typename T>
@@ -1548,6 +1671,7 @@ static int32_t post_joint(gp_post* post, const gp_points* xs, const void* pm, co
     }
     HIPCHK(hipMemsetAsync(Cm + nsp * ldc, 0, sizeof(T) * (size_t)(R + 128) * ldc, s));
     RC(launch_gemm<T>(c, s, Cm, ldc, X, ldx, X, ldx, nsp, nsp, np, plain_map(1, 0, 0)));                       // K** + Σy* − VᵀV
+    if (noise_dense(noise)) RC((dense_add<T, T>(c, bufs, Cm, ldc, noise, ns)));                                // a dense Σy*
     HIPCHK(hipStreamSynchronize(s));
     const T* prior_mean = (const T*)pm;
     J.mean.resize((size_t)ns);
@@ -1597,6 +1721,7 @@ static int32_t post_joint_dist(gp_post* post, const gp_points* xs, const void* p
     }
     HIPCHK(hipMemsetAsync(Cm + nsp * ldc, 0, sizeof(double) * (size_t)(R + 128) * ldc, s));
     RC(gpmi::eng_add_vec(c, s, Cm, (const double*)W_v, nsp * ldc));                                           // K** + Σy* − VᵀV
+    if (noise_dense(noise)) RC((dense_add<double, double>(c, bufs, Cm, ldc, noise, ns)));                     // a dense Σy*
     HIPCHK(hipStreamSynchronize(s));
     J.mean.assign(m_h.begin(), m_h.end());
     return 0;
@@ -1794,6 +1919,7 @@ int32_t gp_ctx_set_param(gp_ctx* c, const char* name, int64_t v) {
     else if (!strcmp(name, "leaf_group")) c->leaf_group = v < 128 ? 64 : (v >= 512 ? 512 : (v >= 256 ? 256 : 128));
     else if (!strcmp(name, "xcd_min_tiles")) c->xcd_min_tiles = v;
     else if (!strcmp(name, "ldpad")) c->ldpad = round_up(std::max<int64_t>(0, v), 16);
+    else if (!strcmp(name, "dense_stage_mb")) c->dense_stage_mb = std::min<int64_t>(std::max<int64_t>(1, v), 256);
     else if (!strcmp(name, "vfe_ks")) c->vfe_ks = std::max<int64_t>(512, round_up(v, 512));
     else if (!strcmp(name, "vfe_sk")) c->vfe_sk = v != 0;
     else if (!strcmp(name, "vfe_dual")) c->vfe_dual = v != 0;
@@ -1820,7 +1946,7 @@ int32_t gp_ctx_get_param(gp_ctx* c, const char* name, int64_t* out) {
         {"gemm_pad_lds", c->gemm_pad_user ? c->gemm_pad_lds : 0}, {"trsv_nb", c->trsv_nb},  {"deterministic", c->deterministic},
         {"leaf_v2", c->leaf_v2}, {"leaf_xr", c->leaf_xr}, {"leaf_cols", c->leaf_cols}, {"updk_max_k", c->updk_max_k}, {"updk_rt", c->updk_rt},
         {"updk_tall_k", c->updk_tall_k}, {"updk_tall_m", c->updk_tall_m}, {"upd128", c->upd128}, {"leaf_group", c->leaf_group},
-        {"ldpad", c->ldpad}, {"vfe_ks", c->vfe_ks}, {"vfe_sk", c->vfe_sk}, {"vfe_dual", c->vfe_dual}, {"vfe_inv_nb", c->vfe_inv_nb}, {"vfe_overlap", c->vfe_overlap}, {"vfe_chunk", c->vfe_chunk},
+        {"ldpad", c->ldpad}, {"dense_stage_mb", c->dense_stage_mb}, {"vfe_ks", c->vfe_ks}, {"vfe_sk", c->vfe_sk}, {"vfe_dual", c->vfe_dual}, {"vfe_inv_nb", c->vfe_inv_nb}, {"vfe_overlap", c->vfe_overlap}, {"vfe_chunk", c->vfe_chunk},
         {"kmat_rows", g_kmat_rows.load()}, {"dib_nb", c->dib_nb}, {"pool_cap_mb", (int64_t)(c->pool_cap >> 20)},
         {"pool_cached_mb", (int64_t)(c->pool_bytes >> 20)}, {"pool_blocks", (int64_t)c->pool.size()}};  // the last two are read-only
     for (const auto& e : tab)
@@ -1970,21 +2096,31 @@ int32_t gp_kernelmatrix_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, con
     return kernelmatrix_impl(c, &kid, &ks, x, y, out);
 }
 
-static int32_t check_fit_args(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise) {
+// noise kinds (include/gpmi355.h): 0 σ²·I, 1 Diagonal, 2 / 3 dense (upper / lower triangle of a column-major n×n host array).  dense_ok = false: the sparse
+// fits, where the reference needs cholesky(Σy) — an N×N factorisation that defeats the sparse cost (src/sparse_approximations.jl:61, :97) — and whose elbo
+// has no trace term for a dense Σy at all (:307-313).
+static int32_t check_noise(const gp_noise* noise, int argi, bool dense_ok) {
+    if (!noise) return set_arg_err(argi, "noise is NULL");
+    if (noise->kind < 0 || noise->kind > 3) return set_arg_err(argi, "noise kind must be 0 (scalar), 1 (diagonal), 2 or 3 (dense, upper / lower triangle)");
+    if (noise->kind >= 2 && !dense_ok)
+        return set_arg_err(argi, "dense noise (kind 2 / 3) is not offered for VFE / DTC fits: the reference factors Σy there (an N×N Cholesky that defeats the sparse "
+                                 "cost) and its elbo has no method for a dense Σy");
+    if (noise->kind != 0 && !noise->diag) return set_arg_err(argi, noise->kind == 1 ? "noise diag is NULL" : "noise diag (the dense matrix) is NULL");
+    return 0;
+}
+static int32_t check_fit_args(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, bool dense_ok = true) {
     if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
     RC(check_points(x, 3));
     RC(check_kernel(k, x->d, 2));
-    if (!noise) return set_arg_err(4, "noise is NULL");
-    if (noise->kind != 0 && noise->kind != 1) return set_arg_err(4, "noise kind must be 0 or 1");
-    if (noise->kind == 1 && !noise->diag) return set_arg_err(4, "noise diag is NULL");
-    return 0;
+    return check_noise(noise, 4, dense_ok);
 }
 
 // One (logpdf, posterior) pair on whatever the ctx drives: the 2D block-cyclic driver (multi.hip) for fp64 fits with at most
-// 128 right-hand sides on a multi-device ctx, the single-device engine (devices[0] of a multi-device ctx) for everything else.
+// 128 right-hand sides on a multi-device ctx, the single-device engine (devices[0] of a multi-device ctx) for everything else — fits with a dense Σy
+// (noise kind 2 / 3) among them: the block-cyclic driver takes a scalar or a vector noise only.
 static int32_t fit_any(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y,
                        long ldy, int ncols, FitOut& fo, gp_post* p, void* alpha_out) {
-    if (c->multi && k->dtype == 0 && ncols <= 128) {
+    if (c->multi && k->dtype == 0 && ncols <= 128 && !noise_dense(noise)) {
         fo.logpdf.assign((size_t)ncols, 0.0);
         std::vector<double> terms((size_t)ncols + 1, 0.0);
         RC(multi_fit(c, k, x, noise, mean, Y, ldy, ncols, fo.logpdf.data(), terms.data(), p, alpha_out));
@@ -2158,10 +2294,7 @@ static int32_t check_fit_args_sum(gp_ctx* c, const gp_ksum* k, const gp_points* 
     if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
     RC(check_points(x, 3));
     RC(pack_ksum(k, x->d, 2, ks, kid));
-    if (!noise) return set_arg_err(4, "noise is NULL");
-    if (noise->kind != 0 && noise->kind != 1) return set_arg_err(4, "noise kind must be 0 or 1");
-    if (noise->kind == 1 && !noise->diag) return set_arg_err(4, "noise diag is NULL");
-    return 0;
+    return check_noise(noise, 4, true);
 }
 
 int32_t gp_logpdf_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y, int64_t ldy,
@@ -2234,14 +2367,13 @@ int32_t gp_posterior_update(gp_post* old, const gp_points* x2, const gp_noise* n
     if (!gd.ok) return set_arg_err(1, "not a live gp_post");
     RC(check_points(x2, 2));
     if (x2->d != old->d) return set_arg_err(2, "x2 has a different D than the training inputs");
-    if (!noise2 || (noise2->kind != 0 && noise2->kind != 1) || (noise2->kind == 1 && !noise2->diag))
-        return set_arg_err(3, "bad noise");
+    RC(check_noise(noise2, 3, true));
     if (!delta_all) return set_arg_err(4, "delta_all is NULL");
     if (!out) return set_arg_err(5, "out is NULL");
     *out = nullptr;
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
-    if (old->dtype == 0 && multi_can_solve(old) && x2->n <= 4096) {
+    if (old->dtype == 0 && multi_can_solve(old) && x2->n <= 4096 && !noise_dense(noise2)) {  // (a dense Σy2: gathered path, single-device engine)
         // multi-device posterior whose factor still lives as block-cyclic pieces: the factor is extended where it lives (multi.hip:
         // multi_update) — no gather; a failed forward / backward consistency check (-1991) falls back to the gathered path below
         gp_post* p = new gp_post();
@@ -2348,7 +2480,7 @@ int32_t gp_posterior_free(gp_post* post) {
 // ---- VFE / DTC ---------------------------------------------------------------------------------------
 int32_t gp_vfe_fit(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_points* z, const gp_noise* noise,
                    double jitter, const void* mean, const void* y, int32_t approx, gp_vfe** out, void* objective_out) {
-    RC(check_fit_args(c, k, x, noise));
+    RC(check_fit_args(c, k, x, noise, false));
     RC(check_points(z, 4));
     if (z->d != x->d) return set_arg_err(4, "z has a different D than x");
     if (!(jitter >= 0)) return set_arg_err(6, "jitter must be >= 0");
@@ -2384,8 +2516,7 @@ int32_t gp_vfe_update(gp_vfe* old, const gp_points* x2, const gp_noise* noise2, 
     if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
     RC(check_points(x2, 2));
     if (x2->d != old->d) return set_arg_err(2, "x2 has a different D than the training inputs");
-    if (!noise2 || (noise2->kind != 0 && noise2->kind != 1) || (noise2->kind == 1 && !noise2->diag))
-        return set_arg_err(3, "bad noise");
+    RC(check_noise(noise2, 3, false));
     if (!y2) return set_arg_err(5, "y2 is NULL");
     if (!out) return set_arg_err(6, "out is NULL");
     *out = nullptr;
@@ -2465,8 +2596,7 @@ int32_t gp_vfe_predict(gp_vfe* p, const gp_points* xs, const void* pm, int32_t w
 static int32_t check_joint_args(const gp_points* xs, int d, const gp_noise* noise) {
     RC(check_points(xs, 2));
     if (xs->d != d) return set_arg_err(2, "xs has a different D than the training inputs");
-    if (!noise || (noise->kind != 0 && noise->kind != 1) || (noise->kind == 1 && !noise->diag)) return set_arg_err(4, "bad noise");
-    return 0;
+    return check_noise(noise, 4, true);
 }
 
 int32_t gp_vfe_logpdf(gp_vfe* p, const gp_points* xs, const void* pm, const gp_noise* noise, const void* Y, int64_t ldy,

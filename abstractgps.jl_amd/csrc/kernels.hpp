@@ -2954,4 +2954,133 @@ template <int VAR> __global__ __launch_bounds__(1024) void mfma_rate_f32_kernel(
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Dense observation-noise covariance Σy (gp_noise kind 2 / 3): the named triangle of the caller's column-major host array arrives in pieces in a
+// staging buffer (gpmi355.hip dense_add) and is added onto the row-major lower matrix K.  Both kernels touch lower 128×128 tiles only, keep a diagonal
+// tile whole and symmetric (as kmat_kernel leaves it: the entries above the diagonal inside it get the mirrored value), never touch a row or column
+// >= n (identity padding, right-hand-side rows), use 64-bit element offsets and no atomics.  TA: matrix type, TS: staging (host array) type.
+// Pieces start at a multiple of 128 and are a multiple of 128 long unless they end at n, so a diagonal tile's mirror entries lie in the same piece.
+// ------------------------------------------------------------------------------------------------
+template <typename T, int E> struct alignas(sizeof(T) * E) DVec {
+    T v[E];
+};
+// kind 2 (upper triangle of the column-major array): host column i, rows 0..i, IS device row i, columns 0..i — contiguous on both sides.
+// Piece = device rows [r0, r0 + rows):  S[(i − r0)·w + j] = Σy(j, i) for j <= i (w multiple of 4).  One thread per 16 bytes of staging;
+// grid (ceil(columns / (256·E)), min(rows, 65 535)), rows grid-strided: no dimension can wrap.
+template <typename TA, typename TS>
+__global__ __launch_bounds__(256) void dense_add_rows_kernel(TA* __restrict__ A, long ld, const TS* __restrict__ S, long w, long r0, long rows, long n) {
+    constexpr int E = 16 / sizeof(TS);
+    const long j0 = ((long)blockIdx.x * 256 + threadIdx.x) * E;
+    for (long r = blockIdx.y; r < rows; r += gridDim.y) {
+        const long i = r0 + r;
+        const long tile_end = (i / 128 + 1) * 128;
+        const long lim = tile_end < n ? tile_end : n;  // end of row i's diagonal tile, real columns only
+        if (j0 >= lim) continue;
+        TA* a = A + i * ld + j0;
+        if (j0 + E <= i + 1) {  // all on or below the diagonal
+            const DVec<TS, E> s = *reinterpret_cast<const DVec<TS, E>*>(S + r * w + j0);
+            DVec<TA, E> v = *reinterpret_cast<const DVec<TA, E>*>(a);
+#pragma unroll
+            for (int e = 0; e < E; ++e) v.v[e] += (TA)s.v[e];
+            *reinterpret_cast<DVec<TA, E>*>(a) = v;
+        } else {  // crosses the diagonal: above it the mirrored entry Σy(i, j) = host column j, row i
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const long j = j0 + e;
+                if (j < lim) a[e] += (TA)(j <= i ? S[r * w + j] : S[(j - r0) * w + i]);
+            }
+        }
+    }
+}
+// kind 3 (lower triangle of the column-major array — the upper triangle of a C-ordered NumPy matrix as it lies): host column j, rows j..n−1, is device
+// COLUMN j: a transposing add.  Piece = device columns [c0, c0 + cols):  S[(j − c0)·w + (i − c0)] = Σy(i, j) for i >= j.
+// One workgroup per 64×64 block (grid: column blocks of the piece × row blocks from c0 down, at most n/64 each): 16-byte loads along the staging
+// rows into LDS, 16-byte read-modify-writes along the matrix rows out of it.  tile[64][65]: in the transposed read a lane's two values sit 65 elements
+// apart and the 16 lanes of a row segment 130 — 16 distinct 4-bank groups, the other half of a 32-lane group one row (2 banks) further: conflict-free for
+// fp64; the row-wise fill is conflict-free by construction.  Blocks above the diagonal exist only inside a diagonal 128×128 tile (mirror, straight add).
+template <typename TA, typename TS>
+__global__ __launch_bounds__(256) void dense_add_cols_kernel(TA* __restrict__ A, long ld, const TS* __restrict__ S, long w, long c0, long n) {
+    constexpr int E = 16 / sizeof(TS);
+    constexpr int VR = 64 / E;  // 16-byte vectors per 64-element run
+    __shared__ TS tile[64][65];
+    const long jb = c0 + (long)blockIdx.x * 64, ib = c0 + (long)blockIdx.y * 64;
+    if (jb >= n || ib >= n) return;
+    const int t = threadIdx.x;
+    if (jb > ib) {
+        if (jb / 128 != ib / 128) return;
+        // upper 64×64 block of a diagonal tile: A[i][j] += Σy(j, i) = S[(i − c0)·w + (j − c0)], row-contiguous on both sides
+        for (int lin = t; lin < 64 * VR; lin += 256) {
+            const long i = ib + lin / VR, j = jb + (lin % VR) * E;
+            if (i >= n || j >= n) continue;
+            TA* a = A + i * ld + j;
+            const TS* s = S + (i - c0) * w + (j - c0);
+            if (j + E <= n) {
+                const DVec<TS, E> sv = *reinterpret_cast<const DVec<TS, E>*>(s);
+                DVec<TA, E> v = *reinterpret_cast<const DVec<TA, E>*>(a);
+#pragma unroll
+                for (int e = 0; e < E; ++e) v.v[e] += (TA)sv.v[e];
+                *reinterpret_cast<DVec<TA, E>*>(a) = v;
+            } else {
+                for (int e = 0; e < E && j + e < n; ++e) a[e] += (TA)s[e];
+            }
+        }
+        return;
+    }
+    // fill: tile[jj][ii] = Σy(ib + ii, jb + jj) (entries with i < j are staging bytes nobody wrote: loaded, never used)
+    for (int lin = t; lin < 64 * VR; lin += 256) {
+        const int jj = lin / VR, iv = (lin % VR) * E;
+        const long j = jb + jj, i = ib + iv;
+        if (j >= n || i >= n) continue;
+        const TS* s = S + (j - c0) * w + (i - c0);
+        if (i + E <= n) {
+            const DVec<TS, E> sv = *reinterpret_cast<const DVec<TS, E>*>(s);
+#pragma unroll
+            for (int e = 0; e < E; ++e) tile[jj][iv + e] = sv.v[e];
+        } else {
+            for (int e = 0; e < E && i + e < n; ++e) tile[jj][iv + e] = s[e];
+        }
+    }
+    __syncthreads();
+    const bool diag = jb == ib;
+    for (int lin = t; lin < 64 * VR; lin += 256) {
+        // 16 lanes along a matrix row (16 vectors = 256 bytes), the next 16 lanes on the next row
+        const int q = lin % 16, rest = lin / 32;
+        const int ii = (rest / (VR / 16)) * 2 + (lin / 16) % 2, jv = ((rest % (VR / 16)) * 16 + q) * E;
+        const long i = ib + ii, j = jb + jv;
+        if (i >= n || j >= n) continue;
+        TA* a = A + i * ld + j;
+        TS sv[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) sv[e] = (!diag || jv + e <= ii) ? tile[jv + e][ii] : tile[ii][jv + e];
+        if (j + E <= n) {
+            DVec<TA, E> v = *reinterpret_cast<const DVec<TA, E>*>(a);
+#pragma unroll
+            for (int e = 0; e < E; ++e) v.v[e] += (TA)sv[e];
+            *reinterpret_cast<DVec<TA, E>*>(a) = v;
+        } else {
+            for (int e = 0; e < E && j + e < n; ++e) a[e] += (TA)sv[e];
+        }
+    }
+}
+// Rows [r0, r0 + rows) of G = ½(α αᵀ − C⁻¹), the gradient of logpdf with respect to a dense Σy (d logpdf = ⟨G, dΣy⟩ for symmetric dΣy), into a staging
+// buffer of row length n: out[(i − r0)·n + j].  Cinv holds −C⁻¹ in its lower triangle (row-major); the entries right of the diagonal come from the mirrored
+// 64×64 block through LDS, so both triangles are read row-contiguously and G is symmetric to the bit (α_i·α_j commutes).  grid (ceil(n/64), ceil(rows/64)).
+template <typename T>
+__global__ __launch_bounds__(256) void dense_grad_rows_kernel(const T* __restrict__ Cinv, long ld, const T* __restrict__ alpha, long n, long r0, long rows,
+                                                               T* __restrict__ out) {
+    __shared__ T tile[64][65];
+    const long ib = r0 + (long)blockIdx.y * 64, jb = (long)blockIdx.x * 64;  // r0 is a multiple of 64
+    const bool upper = jb > ib;
+    const long sr = upper ? jb : ib, sc = upper ? ib : jb;  // the resident block: rows sr.., columns sc.. (sr >= sc)
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    for (int r = ty; r < 64; r += 4) tile[r][tx] = (sr + r < n && sc + tx < n && sc + tx <= sr + r) ? Cinv[(sr + r) * ld + sc + tx] : T(0);
+    __syncthreads();
+    for (int r = ty; r < 64; r += 4) {
+        const long i = ib + r, j = jb + tx;
+        if (i >= r0 + rows || i >= n || j >= n) continue;
+        const T ci = upper ? tile[tx][r] : (j <= i ? tile[r][tx] : tile[tx][r]);  // the last case: a diagonal block (sr == sc)
+        out[(i - r0) * n + j] = (T)(0.5 * ((double)alpha[i] * (double)alpha[j] + (double)ci));
+    }
+}
+
 }  // namespace gpmi

@@ -664,6 +664,7 @@ static int32_t vfe_joint(gp_vfe* p, const gp_points* xs, const void* pm, const g
     HIPCHK(hipMemsetAsync(Cm + nsp * ldc, 0, sizeof(double) * (size_t)(R + 128) * ldc, s));
     RC(launch_gemm<double>(c, s, Cm, ldc, X1, ld, X1, ld, nsp, nsp, mp, plain_map(1, 0, 0)));                     // − AᵀA
     RC(launch_gemm<double>(c, s, Cm, ldc, (const double*)X2n_v, ld, X2, ld, nsp, nsp, mp, plain_map(1, 0, 0)));  // + (Λ_ε.U⁻ᵀA)ᵀ(·)
+    if (noise_dense(noise)) RC((dense_add<double, T>(c, bufs, Cm, ldc, noise, ns)));                              // a dense Σy* (host array in T)
     HIPCHK(hipStreamSynchronize(s));
     const T* prior = (const T*)pm;
     J.mean.resize((size_t)ns);

@@ -269,7 +269,24 @@ function noise(Σ::Diagonal, ::Type{T}) where {T}
     v = Vector{T}(Σ.diag)
     return (v, CNoise(1, 0.0, pointer(v)))
 end
-noise(::Any, ::Type) = nothing   # dense Σy: not accelerated
+# dense Σy (gp_noise kind 2 / 3: ONE triangle of an n×n column-major array is read — include/gpmi355.h): a Matrix{T} goes out as it lies with kind 2
+# (its upper triangle, what _symmetric reads, src/util/common_covmat_ops.jl:5); anything else is converted once; the buffer is kept alive across the ccall
+# by the callers' GC.@preserve of `nbuf`.  Symmetric(A, uplo): its parent with the triangle it names.
+dense_buffer(Σ::Matrix{T}, ::Type{T}) where {T} = Σ
+dense_buffer(Σ::AbstractMatrix, ::Type{T}) where {T} = Matrix{T}(Σ)
+function noise(Σ::AbstractMatrix{<:Real}, ::Type{T}) where {T}
+    size(Σ, 1) == size(Σ, 2) || throw(DimensionMismatch("Σy is $(size(Σ, 1))×$(size(Σ, 2))"))
+    b = dense_buffer(Σ, T)
+    return (b, CNoise(2, 0.0, pointer(b)))
+end
+function noise(Σ::Symmetric{<:Real}, ::Type{T}) where {T}
+    b = dense_buffer(parent(Σ), T)
+    return (b, CNoise(Σ.uplo == 'U' ? 2 : 3, 0.0, pointer(b)))
+end
+noise(::Any, ::Type) = nothing
+is_dense(cn::CNoise) = cn.kind >= 2
+# dnoise_out of gp_logpdf_grad / _sum: 1 entry (Fill), n (Diagonal), n×n (dense: G = ½(ααᵀ − C⁻¹), symmetric)
+dnoise_buffer(cn::CNoise, ::Type{T}, n) where {T} = cn.kind == 0 ? Vector{T}(undef, 1) : (cn.kind == 1 ? Vector{T}(undef, n) : Matrix{T}(undef, n, n))
 
 prior_mean(f::GP{<:ZeroMean}, x, ::Type{T}) where {T} = nothing
 prior_mean(f::GP, x, ::Type{T}) where {T} = Vector{T}(mean_vector(f.mean, x))
@@ -403,7 +420,7 @@ function logpdf_and_grad(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}; wrt_x
     yv = Vector{T}(y)
     lp = Ref{T}(zero(T)); dvar = Ref{Float64}(0.0)
     dscale = zeros(Float64, max(length(a.scales), 1))
-    dnoise = Vector{T}(undef, a.cn.kind == 0 ? 1 : length(yv))
+    dnoise = dnoise_buffer(a.cn, T, length(yv))
     dy = Vector{T}(undef, length(yv))
     dx = wrt_x ? similar(a.xbuf) : T[]                  # same container layout as the inputs (Vector / D×N / N×D)
     mptr = a.m === nothing ? C_NULL : pointer(a.m)
@@ -423,7 +440,7 @@ function logpdf_and_grad_sum(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}, a
     yv = Vector{T}(y)
     lp = Ref{T}(zero(T))
     dθ = zeros(Float64, length(sum_theta(a.P, a.terms)))
-    dnoise = Vector{T}(undef, a.cn.kind == 0 ? 1 : length(yv))
+    dnoise = dnoise_buffer(a.cn, T, length(yv))
     dy = Vector{T}(undef, length(yv))
     mptr = a.m === nothing ? C_NULL : pointer(a.m)
     GC.@preserve a yv dθ dnoise dy begin
@@ -489,6 +506,10 @@ input_tangent(x::ColVecs, dx, Δ) = Tangent{typeof(x)}(; X=Δ .* dx)
 input_tangent(x::RowVecs, dx, Δ) = Tangent{typeof(x)}(; X=Δ .* dx)
 noise_tangent(Σ::Diagonal{<:Any,<:Fill}, dn) = Tangent{typeof(Σ)}(; diag=Tangent{typeof(Σ.diag)}(; value=dn))
 noise_tangent(Σ::Diagonal, dn) = Tangent{typeof(Σ)}(; diag=dn)
+# dense Σy: the library returns G = ½(ααᵀ − C⁻¹) with d logpdf = ⟨G, dΣy⟩ for symmetric dΣy — the natural tangent of a matrix that is read through Symmetric
+noise_tangent(Σ::Matrix, dn) = dn
+noise_tangent(Σ::Symmetric, dn) = Tangent{typeof(Σ)}(; data=dn)
+noise_tangent(Σ::AbstractMatrix, dn) = dn
 
 function ChainRulesCore.rrule(config::RuleConfig{>:HasReverseMode}, ::typeof(Distributions.logpdf), fx::FiniteGP{<:HipGP},
     y::AbstractVector{<:Real})
@@ -587,7 +608,7 @@ function joint_args(fx::FiniteGP, gp::GP, ::Type{T}) where {T}
     px = points(fx.x, T)
     px === nothing && throw(ArgumentError("unsupported input container for the accelerated posterior (use a Vector, ColVecs or RowVecs)"))
     nz = noise(fx.Σy, T)
-    nz === nothing && throw(ArgumentError("dense Σy is not accelerated"))
+    nz === nothing && throw(ArgumentError("this form of Σy is not accelerated"))
     return px[1], px[2], nz[1], nz[2], prior_mean(gp, fx.x, T)
 end
 
@@ -770,6 +791,7 @@ function vfe_call(approx::Union{VFE,DTC}, fx::FiniteGP{<:HipGP}, y::AbstractVect
     length(fx) == length(y) || throw(DimensionMismatch("length(fx) != length(y)"))    # :290-294
     a = marshal(fx, eltype(y))
     (a === nothing || haskey(a, :ks)) && return nothing   # VFE / DTC are single-kind: composite kernels take the stock path
+    is_dense(a.cn) && return nothing                      # dense Σy: the sparse fits need cholesky(Σy) (src/sparse_approximations.jl:61) — stock path
     T = a.T
     pz = points(approx.fz.x, T)
     pz === nothing && return nothing
@@ -898,6 +920,7 @@ function AbstractGPs.update_posterior(f::HipApproxPosteriorGP, fx::FiniteGP{<:Hi
     @assert f.prior === fx.f
     T = getfield(f, :T)
     xbuf, cx, nbuf, cn, m2 = joint_args(fx, f.prior.gp, T)
+    is_dense(cn) && throw(ArgumentError("update_posterior of a VFE / DTC posterior with a dense Σy is not accelerated (the reference factors Σy there)"))
     yv = Vector{T}(y)
     obj = Ref{T}(zero(T))
     h = Ref{Ptr{Cvoid}}(C_NULL)

@@ -98,7 +98,24 @@ typedef struct {
 } gp_points;
 
 /* Observation noise Σy.  kind 0: σ²·I (Fill, src/finite_gp_projection.jl:19-21); kind 1: Diagonal(diag)
- * (length n, host, kernel dtype) (:13-15).  Dense Σy is not accelerated (shim falls back). */
+ * (length n, host, kernel dtype) (:13-15).
+ * Dense Σy (any matrix, :2-11; cov(fx) = cov(f, x) + Σy, factored as cholesky(_symmetric(K + Σy)), :96, :308): `diag` points to an n×n COLUMN-MAJOR
+ * contiguous host array (leading dimension n) of the kernel's dtype, n = the number of points of the call the noise belongs to (x->n, x2->n, xs->n); `s` is
+ * ignored.
+ *   kind 2: only the UPPER triangle (row <= column) is read — Symmetric(Σy) = :U, what _symmetric does (src/util/common_covmat_ops.jl:5);
+ *   kind 3: only the LOWER triangle (row >= column) is read.  A C-ordered (row-major) array handed over as it lies is the column-major array of its
+ *           transpose, so kind 3 is the zero-copy form of "the upper triangle of a row-major matrix".
+ * Nothing outside the named triangle is read (it may hold anything).  The triangle is streamed host -> page-locked staging -> device staging -> the resident
+ * K in pieces of at most "dense_stage_mb" MiB and added before the factorisation: no second N×N buffer on either side, 8·N(N+1)/2 bytes (fp64) over the bus
+ * up to piece padding; the upload and the adds count into gp_timings.assemble_ms.  No atomics: "deterministic" = 1 covers dense fits.  The copy into the
+ * page-locked buffer is the slowest stage (it runs on GPMI_DENSE_THREADS host threads, environment, 1..16, default 4): an upload costs 1.1-1.6 times a
+ * plain hipMemcpy of the triangle (profiles/r8/).
+ * Accepted by every exact-path call that takes a gp_noise (gp_logpdf, gp_logpdf_terms, gp_posterior_fit, gp_logpdf_grad, their *_sum forms,
+ * gp_posterior_update, gp_posterior_logpdf, gp_posterior_rand) and by gp_vfe_logpdf / gp_vfe_rand (Σy* of the ns×ns joint).  gp_vfe_fit / gp_vfe_update
+ * refuse kinds 2 / 3 (argument error, reason in gp_last_error()): the reference needs cholesky(Σy) there — an N×N factorisation that defeats the sparse
+ * cost (src/sparse_approximations.jl:61, :97) — and its elbo has no method for a dense Σy (:307-313).
+ * On a multi-device ctx a fit with a dense Σy runs on the single-device engine of the ctx's first device (like composite and fp32 fits): the 2-D
+ * block-cyclic driver takes kinds 0 / 1 only; a sequential update with a dense Σy2 gathers the factor first. */
 typedef struct {
     int32_t kind;
     double s;
@@ -133,7 +150,7 @@ int32_t gp_ctx_create(gp_ctx** out, int32_t device, void* stream_or_null);
  * times ("virtual ranks": the full schedule on one GPU with same-device copies — how CI exercises it).  Every other entry
  * point works unchanged on such a ctx: fp64 fits are distributed, everything else (and everything downstream of a fit:
  * predictions, updates, sampling — the factor is gathered onto devices[0] on first need) runs on devices[0].
- * fp32 fits and fits with more than 128 right-hand-side columns also run on devices[0] (single-device engine).
+ * fp32 fits, fits with more than 128 right-hand-side columns and fits with a dense Σy (gp_noise kind 2 / 3) also run on devices[0] (single-device engine).
  * Extra parameters: "lookahead_depth" (1..3, default 2), "dist_nb", "multi_gemm_streamk" (stream-K cuts inside the rank
  * contexts, default 0), "multi_timeout_s" (a rank that waits longer for a peer or for its own streams fails the fit instead
  * of hanging, default 600), "multi_check" (diagnostics: 1 marker/checker kernels around every event record / wait, 2 operand
@@ -216,6 +233,8 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
  *                    carries an error of order cond(L_bb)·ε where substitution is backward stable: a handle whose factor has max |L_ii| / min |L_ii|
  *                    above 1e5 (cond(K + Σy) >= 1e10) keeps the substitution leaves                   default 2048
  *   "ldpad"          row padding in elements (multiple of 16)                             default 32
+ *   "dense_stage_mb" dense Σy (gp_noise kind 2 / 3): MiB per staging buffer of the streamed upload and of the gradient's download (two page-locked and two
+ *                    device buffers of this size; 1..256; a piece is never shorter than 128 rows / columns of the matrix)   default 64
  *   "vfe_chunk"      data points per streamed VFE chunk (multiple of vfe_ks); 0 = automatic: 16 384 for M > 2 048 pseudo-points (measured best at C5),
  *                    × 2 … 16 for fewer (chunk × M kept at C5's footprint), at most the batch; a handle keeps the chunk of its first fit        default 0
  *   "vfe_ks"         fp32 VFE: data points per fp32 partial product of the chunk SYRK      default 2048
@@ -256,7 +275,7 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
     "nb=-1,nb_small=4096,nb_large=2048,lookahead=1,lookahead_min_n=24576,time_kernels=0,xcd_swizzle=0,xcd_min_tiles=256,gemm_streamk=1,sk_max_tiles=4096," \
     "sk_min_k=0,gemm_pipe=1,gemm_pad_f32=0,gemm_pad_lds=0,trsv_nb=256,deterministic=0,leaf_v2=1,leaf_xr=0,leaf_cols=128,"    \
     "updk_max_k=512,updk_rt=0,updk_tall_k=256,updk_tall_m=8192,upd128=1,leaf_group=128,ldpad=32,vfe_ks=2048,vfe_sk=0,"          \
-    "vfe_overlap=1,vfe_dual=0,vfe_inv_nb=512,vfe_chunk=0,kmat_rows=1,dib_nb=2048,pool_cap_mb=98304"
+    "vfe_overlap=1,vfe_dual=0,vfe_inv_nb=512,vfe_chunk=0,kmat_rows=1,dib_nb=2048,pool_cap_mb=98304,dense_stage_mb=64"
 int32_t gp_ctx_set_param(gp_ctx* ctx, const char* name, int64_t value);
 /* Read a parameter back (same names; "gemm_pad_lds" reads 0 until it has been set explicitly).  Used by the test-suite to assert that
  * every GPU test starts from the documented defaults. */
@@ -319,6 +338,10 @@ int32_t gp_posterior_rand(gp_post* post, const gp_points* xs, const void* prior_
  *   dvariance_out  double[1]        ∂/∂(kernel variance)
  *   dscale_out     double[nscale]   ∂/∂scale (ScaleTransform s, or ARDTransform v_p; any D: 16 dimensions per pass)
  *   dnoise_out     noise.kind 0: 1 entry ∂/∂σ² = ½(αᵀα − tr C⁻¹);  kind 1: n entries ½(α_i² − C⁻¹_ii)
+ *                  kind 2 / 3 (dense Σy): n×n entries, column-major, the FULL symmetric matrix G = ½(α αᵀ − C⁻¹) — the gradient in the sense
+ *                  d logpdf = ⟨G, dΣy⟩ = Σ_ij G_ij dΣy_ij for SYMMETRIC dΣy, so a parametric Σy(φ) chains as ∂logpdf/∂φ = ⟨G, ∂Σy/∂φ⟩.  It is NOT what AD
+ *                  through Symmetric(Σy, :U) returns entry by entry (that puts 2·G_ij on the named off-diagonal entries and 0 on the others).  Streamed to
+ *                  the host in row blocks ("dense_stage_mb"); skipped when dnoise_out is NULL.
  *   dy_out         n entries ∂/∂y = −α   (∂/∂m = +α for a mean vector m)
  *   dx_out         n×d entries ∂/∂x in the container layout of x (what a deep-kernel model back-propagates into its feature
  *                  map, examples/2-deep-kernel-learning/script.jl); the prior mean is taken as constant in x */
