@@ -81,6 +81,8 @@ PROTOTYPES = {
     "gp_logpdf_sum": (i32, [vp, PS, PP, PN, vp, vp, i64, i32, vp]),
     "gp_posterior_fit_sum": (i32, [vp, PS, PP, PN, vp, vp, C.POINTER(vp), vp, vp]),
     "gp_logpdf_grad_sum": (i32, [vp, PS, PP, PN, vp, vp, vp, C.POINTER(dbl), vp, vp]),
+    "gp_logpdf_batch": (i32, [vp, i32, PK, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp)]),
+    "gp_logpdf_batch_sum": (i32, [vp, i32, PS, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp)]),
     "gp_posterior_update": (i32, [vp, PP, PN, vp, C.POINTER(vp), vp, vp]),
     "gp_posterior_factor_mul": (i32, [vp, vp, i32, vp]),
     "gp_posterior_solve": (i32, [vp, vp, i32, vp]),
@@ -127,6 +129,11 @@ def header_functions() -> list[str]:
     return sorted(set(re.findall(r"\b(gpd?_[a-z0-9_]+)\s*\(", txt)))
 
 
+def batch_max_n() -> int:
+    """GPMI355_BATCH_MAX_N of include/gpmi355.h: the largest problem gp_logpdf_batch hands to its batch kernel."""
+    return int(re.search(r"#define GPMI355_BATCH_MAX_N (\d+)", HEADER.read_text()).group(1))
+
+
 _lib = None
 
 
@@ -152,9 +159,10 @@ def load() -> C.CDLL:
 class PosDefException(Exception):
     """Mirror of LinearAlgebra.PosDefException(info) (reference src/finite_gp_projection.jl:308)."""
 
-    def __init__(self, info: int):
-        super().__init__(f"matrix is not positive definite; leading minor of order {info}")
+    def __init__(self, info: int, index=None):
+        super().__init__(f"matrix is not positive definite; leading minor of order {info}" + ("" if index is None else f" (problem {index} of the batch)"))
         self.info = info
+        self.index = index  # logpdf_batch: position of the failing problem in the caller's sequence
 
 
 class GpmiError(RuntimeError):

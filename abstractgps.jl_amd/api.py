@@ -689,6 +689,128 @@ def logpdf(fx: FiniteGP, y):
     return out[0] if y.ndim == 1 else out
 
 
+# --------------------------------------------------------------------------------------------
+# many small problems in one call: gp_logpdf_batch / gp_logpdf_batch_sum
+# --------------------------------------------------------------------------------------------
+@dataclass(eq=False)
+class _BatchGroup:
+    """The problems of a logpdf_batch call that travel in ONE ABI call: one ctx, one dtype, single-kind or composite descriptors."""
+
+    ctx: Optional[Context]  # None: the default context
+    dtype: type
+    composite: bool
+    index: list             # positions in the caller's sequence, ascending
+    fxs: list
+    ys: list
+    nx: int = 0             # 1: every problem holds the SAME x object (sent once), else len(index)
+    ny: int = 0
+
+
+def _batch_groups(fxs, ys) -> list:
+    """Grouping of a logpdf_batch call — needs no context and no device.  ys: a sequence of vectors, or ONE vector shared by all."""
+    fxs = list(fxs)
+    if isinstance(ys, np.ndarray) and ys.ndim == 1 or (len(ys) > 0 and np.ndim(ys[0]) == 0):
+        ys = [ys] * len(fxs)  # one vector for every problem: the same object in every entry
+    ys = list(ys)
+    if len(ys) != len(fxs):
+        raise ValueError(f"DimensionMismatch: {len(fxs)} problems but {len(ys)} observation vectors")
+    groups = {}
+    for i, (fx, y) in enumerate(zip(fxs, ys)):
+        if not isinstance(fx, FiniteGP) or not isinstance(fx.f, GP):
+            raise TypeError("logpdf_batch: every entry must be a FiniteGP over a GP prior")
+        yv = y if isinstance(y, np.ndarray) else np.asarray(y)
+        if yv.ndim != 1 or yv.shape[0] != len(fx):
+            raise ValueError(f"DimensionMismatch: problem {i}: length(fx) = {len(fx)} but y has shape {yv.shape}")
+        dt = np.result_type(_input_dtype(fx.x), np.float32 if yv.dtype == np.float32 else np.float64).type
+        key = (id(fx.f.ctx) if fx.f.ctx is not None else None, dt, _is_composite(fx.f.kernel))
+        g = groups.get(key)
+        if g is None:
+            g = groups[key] = _BatchGroup(fx.f.ctx, dt, key[2], [], [], [])
+        g.index.append(i)
+        g.fxs.append(fx)
+        g.ys.append(y)
+    out = list(groups.values())
+    for g in out:
+        g.nx = 1 if all(fx.x is g.fxs[0].x for fx in g.fxs) else len(g.index)
+        g.ny = 1 if all(y is g.ys[0] for y in g.ys) else len(g.index)
+    return out
+
+
+@dataclass(eq=False)
+class _BatchCall:
+    """The marshalled arguments of one gp_logpdf_batch[_sum] call (everything after the ctx) and the buffers behind them."""
+
+    entry: str
+    nb: int
+    nx: int
+    ny: int
+    args: tuple
+    out: np.ndarray
+    info: np.ndarray
+    alphas: Optional[list]
+    keep: object
+
+
+def _batch_marshal(g: _BatchGroup, return_alpha: bool) -> _BatchCall:
+    """ctypes arguments of one group — needs no context."""
+    m = _Marshal(g.dtype)
+    nb = len(g.index)
+    pts = (gp_points * g.nx)(*[m.points(fx.x) for fx in g.fxs[:g.nx]])
+    dims = [pts[0 if g.nx == 1 else b].d for b in range(nb)]
+    kerns = [m.ksum(fx.f.kernel, d)[0] if g.composite else m.kernel(fx.f.kernel, d) for fx, d in zip(g.fxs, dims)]
+    karr = ((gp_ksum if g.composite else gp_kernel) * nb)(*kerns)
+    narr = (gp_noise * nb)(*[m.noise(fx.sigma2, len(fx)) for fx in g.fxs])
+    means = [_mean_vector(fx.f.mean_fn, fx.x, g.dtype) for fx in g.fxs]
+    means = [None if v is None else m.arr(v) for v in means]
+    marr = None if all(v is None for v in means) else (C.c_void_p * nb)(*[None if v is None else v.ctypes.data for v in means])
+    yarr = (C.c_void_p * g.ny)(*[m.arr(y).ctypes.data for y in g.ys[:g.ny]])
+    out = np.empty(nb, dtype=g.dtype)
+    info = np.zeros(nb, dtype=np.int32)
+    alphas = [np.empty(len(fx), dtype=g.dtype) for fx in g.fxs] if return_alpha else None
+    aarr = (C.c_void_p * nb)(*[a.ctypes.data for a in alphas]) if return_alpha else None
+    m.keep += [pts, karr, narr, marr, yarr, aarr]
+    args = (nb, karr, g.nx, pts, narr, marr, g.ny, yarr, out.ctypes.data, info.ctypes.data_as(C.POINTER(C.c_int32)), aarr)
+    return _BatchCall("gp_logpdf_batch" + ("_sum" if g.composite else ""), nb, g.nx, g.ny, args, out, info, alphas, m)
+
+
+def _batch_merge(n: int, parts: list, return_alpha: bool, on_error: str):
+    """Results of the groups back in the caller's order.  parts: (index, logpdf, info, alphas or None) per group."""
+    dt = np.float64 if any(p[1].dtype == np.float64 for p in parts) else np.float32
+    lp = np.empty(n, dtype=dt)
+    info = np.zeros(n, dtype=np.int32)
+    alphas = [None] * n
+    for index, out, inf, al in parts:
+        lp[index] = out
+        info[index] = inf
+        if al is not None:
+            for i, a in zip(index, al):
+                alphas[i] = a
+    bad = np.flatnonzero(info)
+    if on_error == "raise" and bad.size:
+        raise PosDefException(int(info[bad[0]]), index=int(bad[0]))
+    return (lp, alphas) if return_alpha else lp
+
+
+def logpdf_batch(fxs, ys, *, return_alpha: bool = False, on_error: str = "raise"):
+    """logpdf(fx_b, y_b) of many independent exact GPs in one library call per (ctx, dtype, single-kind / composite) group
+    (src/finite_gp_projection.jl:306-311 once per problem; with return_alpha also α_b = C_b \\ (y_b − m_b), src/exact_gpr_posterior.jl:29-35).
+    fxs: FiniteGPs over GP priors — any mix of kernels, sizes, containers, means and noise forms; ys: a sequence of vectors, or ONE vector shared by
+    all.  The same x object / y object in every entry is sent once.  on_error = "raise": the PosDefException of the first failing problem (.info,
+    .index); "nan": NaN in its place.  Returns an array of the promoted dtype (and the list of α vectors)."""
+    if on_error not in ("raise", "nan"):
+        raise ValueError('on_error must be "raise" or "nan"')
+    fxs = list(fxs)
+    if not fxs:
+        return (np.empty(0), []) if return_alpha else np.empty(0)
+    parts = []
+    for g in _batch_groups(fxs, ys):
+        call = _batch_marshal(g, return_alpha)
+        ctx = g.ctx or default_context()
+        check(getattr(ctx.lib, call.entry)(ctx.handle, *call.args))
+        parts.append((g.index, call.out, call.info, call.alphas))
+    return _batch_merge(len(fxs), parts, return_alpha, on_error)
+
+
 def _terms(fx: FiniteGP, y, want_logdet: bool, want_sqmahal: bool):
     """gp_logpdf_terms: logdet(cov(fx)) and / or sqmahal(fx, y) from ONE factorisation on the device."""
     f = fx.f

@@ -1,6 +1,7 @@
 // engine.hpp — internal interface shared by the translation units of libgpmi355.so:
 //   gpmi355.hip  kernels (kernels.hpp), the single-device engine and the C ABI
 //   multi.hip    the multi-device 2D block-cyclic driver (host code only: RCCL / peer copies + calls into the engine)
+//   batch.hip    many small problems in one call: the batch kernel (kfun.hpp) and gp_logpdf_batch / gp_logpdf_batch_sum
 // Nothing here is part of the public ABI (include/gpmi355.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -314,6 +315,13 @@ int32_t launch_panel_updk(hipStream_t s, double* C, long ldc, const double* P, l
 // 2-D block copy by a kernel (16-B aligned rows, even cols): source may live on a peer device with peer access enabled
 int32_t eng_copy2d(gp_ctx* c, hipStream_t s, double* dst, long dld, const double* src, long sld, long rows, long cols);
 }  // namespace gpmi
+
+// ---- argument checks of the C ABI (gpmi355.hip), shared with the batch entry points (batch.hip): −argi with the reason, or 0
+// (check_noise and pack_ksum are defined inside the ABI's extern "C" block: `extern "C++"` there keeps them C++ functions) ----
+int32_t check_kernel(const gp_kernel* k, int d, int argi);
+int32_t check_points(const gp_points* x, int argi);
+int32_t check_noise(const gp_noise* noise, int argi, bool dense_ok);
+int32_t pack_ksum(const gp_ksum* k, int d, int argi, gpmi::KSum& ks, gp_kernel& kid);  // validates and packs a composite kernel for the device
 
 // ---- multi-device contexts (multi.hip) --------------------------------------------------------------
 void multi_destroy(gp_multi* m);

@@ -876,7 +876,7 @@ template <typename T> static T pt_get(const gp_points* x, long i, int dd) {
     if (x->layout == 1) return p[(long)dd + i * x->d];
     return p[i + (long)dd * x->n];
 }
-static int32_t check_kernel(const gp_kernel* k, int d, int argi) {
+int32_t check_kernel(const gp_kernel* k, int d, int argi) {
     if (!k) return set_arg_err(argi, "kernel is NULL");
     if (k->kind < 0 || k->kind > 3) return set_arg_err(argi, "kernel kind must be 0..3");
     if (k->dtype != 0 && k->dtype != 1) return set_arg_err(argi, "dtype must be 0 (f64) or 1 (f32)");
@@ -885,7 +885,7 @@ static int32_t check_kernel(const gp_kernel* k, int d, int argi) {
     if (k->nscale != 0 && !k->scale) return set_arg_err(argi, "scale is NULL");
     return 0;
 }
-static int32_t check_points(const gp_points* x, int argi) {
+int32_t check_points(const gp_points* x, int argi) {
     if (!x || !x->data) return set_arg_err(argi, "points NULL");
     if (x->n <= 0) return set_arg_err(argi, "n must be > 0");
     if (x->d <= 0) return set_arg_err(argi, "d must be > 0");
@@ -2028,7 +2028,7 @@ int32_t gp_kernelmatrix(gp_ctx* c, const gp_kernel* k, const gp_points* x, const
 
 // Validates a gp_ksum (limits and malformed descriptors: −argi with the reason) and packs it for the device.  kid: the single-kind descriptor
 // the engine carries beside it — kind 0, no transform (the inputs stay raw), variance Σ_t σ_t² (the prior variance k(x, x)).
-static int32_t pack_ksum(const gp_ksum* k, int d, int argi, KSum& ks, gp_kernel& kid) {
+extern "C++" int32_t pack_ksum(const gp_ksum* k, int d, int argi, KSum& ks, gp_kernel& kid) {
     if (!k) return set_arg_err(argi, "kernel is NULL");
     if (k->dtype != 0 && k->dtype != 1) return set_arg_err(argi, "dtype must be 0 (f64) or 1 (f32)");
     if (k->nterms < 1 || k->nterms > KSum::MAXT) return set_arg_err(argi, "composite kernel: 1..8 terms");
@@ -2099,7 +2099,7 @@ int32_t gp_kernelmatrix_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, con
 // noise kinds (include/gpmi355.h): 0 σ²·I, 1 Diagonal, 2 / 3 dense (upper / lower triangle of a column-major n×n host array).  dense_ok = false: the sparse
 // fits, where the reference needs cholesky(Σy) — an N×N factorisation that defeats the sparse cost (src/sparse_approximations.jl:61, :97) — and whose elbo
 // has no trace term for a dense Σy at all (:307-313).
-static int32_t check_noise(const gp_noise* noise, int argi, bool dense_ok) {
+extern "C++" int32_t check_noise(const gp_noise* noise, int argi, bool dense_ok) {
     if (!noise) return set_arg_err(argi, "noise is NULL");
     if (noise->kind < 0 || noise->kind > 3) return set_arg_err(argi, "noise kind must be 0 (scalar), 1 (diagonal), 2 or 3 (dense, upper / lower triangle)");
     if (noise->kind >= 2 && !dense_ok)

@@ -27,7 +27,7 @@ using KernelFunctions: SqExponentialKernel, Matern12Kernel, ExponentialKernel, M
 using LinearAlgebra, FillArrays, Statistics, StatsBase, Distributions, Random
 using ChainRulesCore
 
-export HipGP, HipPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, elbo_and_grad
+export HipGP, HipPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, elbo_and_grad, logpdf_batch, BatchPosDefException
 
 const libgpmi355 = get(ENV, "GPMI355_LIB", joinpath(@__DIR__, "..", "csrc", "libgpmi355.so"))
 
@@ -363,6 +363,84 @@ function Distributions.logpdf(fx::FiniteGP{<:HipGP}, Y::AbstractVecOrMat{<:Real}
 end
 
 # ---- the two terms of logpdf on their own (src/finite_gp_projection.jl:313-337): sqmahal, logdetcov, gradlogpdf ----------------
+# ---- many small problems in one call: gp_logpdf_batch / gp_logpdf_batch_sum ---------------------------------------------------
+# logpdf_batch(fxs, ys): logpdf(fxs[b], ys[b]) (src/finite_gp_projection.jl:306-311, once per problem) of independent exact GPs — the chains of a
+# sampler over hyper-parameters, the starts of a multi-start optimiser, cross-validation folds — in ONE library call per (context, eltype,
+# single-kind / composite) group; `ys` is a vector of vectors, or ONE vector shared by all.  The same `x` / `y` object in every entry is sent
+# once (nx / ny = 1).  return_alpha = true also returns α_b = C_b \ (y_b − m_b) (src/exact_gpr_posterior.jl:29-35).  on_error = :raise throws the
+# PosDefException of the first failing problem (BatchPosDefException carries its index as well); :nan leaves NaN in its place.  A problem the
+# ABI has no layout for takes the stock path.
+struct BatchPosDefException <: Exception
+    info::Int
+    index::Int
+end
+Base.showerror(io::IO, e::BatchPosDefException) =
+    print(io, "PosDefException: problem ", e.index, " of the batch is not positive definite; leading minor of order ", e.info)
+
+function logpdf_batch(fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys; return_alpha::Bool=false, on_error::Symbol=:raise)
+    on_error in (:raise, :nan) || throw(ArgumentError("on_error must be :raise or :nan"))
+    nb = length(fxs)
+    yv = (ys isa AbstractVector{<:Real}) ? fill(ys, nb) : collect(ys)
+    length(yv) == nb || throw(DimensionMismatch("$(nb) problems but $(length(yv)) observation vectors"))
+    args = [marshal(fxs[b], eltype(yv[b])) for b in 1:nb]
+    T = (nb > 0 && all(a -> a !== nothing && a.T === Float32, args)) ? Float32 : Float64
+    lp = Vector{T}(undef, nb)
+    info = zeros(Int32, nb)
+    alphas = Vector{Any}(nothing, nb)
+    groups = Dict{Any,Vector{Int}}()
+    for b in 1:nb
+        length(yv[b]) == length(fxs[b]) || throw(DimensionMismatch("problem $(b): length(fx) = $(length(fxs[b])) but y has $(length(yv[b])) entries"))
+        a = args[b]
+        if a === nothing  # stock path, one problem at a time
+            try
+                lp[b] = logpdf(stock(fxs[b]), yv[b])
+                return_alpha && (alphas[b] = cholesky(Symmetric(cov(stock(fxs[b])))) \ (yv[b] .- mean(stock(fxs[b]))))
+            catch e
+                e isa PosDefException || rethrow()
+                lp[b] = NaN
+                info[b] = e.info
+            end
+        else
+            push!(get!(groups, (fxs[b].f.ctx, a.T, haskey(a, :ks)), Int[]), b)
+        end
+    end
+    for ((ctx, Tg, composite), idx) in groups
+        g = length(idx)
+        nx = all(b -> fxs[b].x === fxs[idx[1]].x, idx) ? 1 : g
+        ny = all(b -> yv[b] === yv[idx[1]], idx) ? 1 : g
+        cxs = [args[b].cx for b in idx[1:nx]]
+        cns = [args[b].cn for b in idx]
+        ybufs = [Vector{Tg}(yv[b]) for b in idx[1:ny]]
+        yptrs = Ptr{Cvoid}[pointer(v) for v in ybufs]
+        mptrs = Ptr{Cvoid}[args[b].m === nothing ? C_NULL : pointer(args[b].m) for b in idx]
+        out = Vector{Tg}(undef, g)
+        inf = zeros(Int32, g)
+        abufs = return_alpha ? [Vector{Tg}(undef, length(fxs[b])) for b in idx] : Vector{Tg}[]
+        aptrs = Ptr{Cvoid}[pointer(v) for v in abufs]
+        GC.@preserve args ybufs abufs cxs cns yptrs mptrs out inf aptrs begin
+            if composite
+                ks = [args[b].ks for b in idx]
+                GC.@preserve ks check(ccall((:gp_logpdf_batch_sum, libgpmi355), Int32,
+                    (Ptr{Cvoid}, Int32, Ptr{CKSum}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Ptr{Cvoid}}),
+                    ctx.handle, g, ks, nx, cxs, cns, mptrs, ny, yptrs, out, inf, return_alpha ? pointer(aptrs) : C_NULL))
+            else
+                cks = [args[b].ck for b in idx]
+                GC.@preserve cks check(ccall((:gp_logpdf_batch, libgpmi355), Int32,
+                    (Ptr{Cvoid}, Int32, Ptr{CKernel}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Ptr{Cvoid}}),
+                    ctx.handle, g, cks, nx, cxs, cns, mptrs, ny, yptrs, out, inf, return_alpha ? pointer(aptrs) : C_NULL))
+            end
+        end
+        for (j, b) in enumerate(idx)
+            lp[b] = out[j]
+            info[b] = inf[j]
+            return_alpha && (alphas[b] = abufs[j])
+        end
+    end
+    bad = findfirst(!=(0), info)
+    (on_error === :raise && bad !== nothing) && throw(BatchPosDefException(Int(info[bad]), bad))
+    return return_alpha ? (lp, alphas) : lp
+end
+
 function logpdf_terms(fx::FiniteGP{<:HipGP}, Y::Union{Nothing,AbstractVecOrMat{<:Real}}; logdet::Bool, sq::Bool)
     a = marshal(fx, Y === nothing ? input_eltype(fx.x) : eltype(Y))
     (a === nothing || haskey(a, :ks)) && return nothing   # gp_logpdf_terms is single-kind: composite kernels take the stock path

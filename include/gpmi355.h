@@ -367,6 +367,36 @@ int32_t gp_logpdf_grad_sum(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, co
                            const void* y, void* logpdf_out, double* dtheta_out_or_null, void* dnoise_out_or_null,
                            void* dy_out_or_null);
 
+/* ---- many small exact GPs in one call ------------------------------------------------------------------------------------------ */
+/* nb independent problems (k_b, x_b, Σy_b, m_b, y_b), each with its own size n_b: logpdf_out[b] = logpdf(f_b(x_b, Σy_b), y_b)
+ * (src/finite_gp_projection.jl:306-311, once per problem — what a sampler over hyper-parameters, a multi-start optimiser, a grid search or a
+ * set of cross-validation folds evaluates again and again) and, where alpha_out_or_null[b] is not NULL, α_b = C_b \ (y_b − m_b)
+ * (src/exact_gpr_posterior.jl:29-35; n_b entries).  Value and weights only: no gradient, no posterior handle.
+ *   k, noise, logpdf_out, info_out: arrays of nb;  x: nx entries, y: ny pointers (n_b entries each), nx, ny ∈ {1, nb} — 1 = every problem shares
+ *   that x (resp. y; the problems then have one size), which is uploaded once;  mean_or_null, alpha_out_or_null: NULL, or nb pointers each of
+ *   which may be NULL (ZeroMean / α not wanted).  One dtype per call (that of k[0]; a descriptor that differs is an argument error).
+ * A failing problem is data, not a status: info_out[b] = 0, or the order of the first leading minor that is not positive definite (what
+ * gp_logpdf returns for the same problem) with logpdf_out[b] = NaN and α_b filled with NaN — the other problems are not affected.  The return
+ * value reports argument errors only (−i, reason in gp_last_error(); nb = 0 returns 0 and touches nothing).
+ * fp64 problems with noise kind 0 / 1, n_b <= GPMI355_BATCH_MAX_N and D <= 16 are served by the batch kernel (csrc/batch.hip): one workgroup
+ * per problem, inputs of a launch in ONE packed host -> device copy, results in one copy back, a bounded workspace from the ctx's block cache
+ * (a larger batch runs in waves).  No floating-point atomics and a fixed schedule per problem: its result is the same bits whatever batch it
+ * rides in.  Every other problem (fp32, a dense Σy, a larger n_b or D) is answered inside the same call by the single path; which path serves a
+ * problem depends on that problem alone.  On a multi-device ctx the batch kernel runs on the first device.
+ * GPMI355_BATCH_MAX_N: the largest multiple of 128 of the measured sweep (tools/batch_profile.py, profiles/r9/batch_profile.json: n = 64 … 2 048 ×
+ * nb = 1, 8, 64, 512) for which one batch call beat the loop of gp_logpdf calls in every cell with nb >= 8.  The nb = 8 cells decide it: 768 points
+ * 3.06 ms against 3.64 ms, 896 points 4.39 ms against 3.68 ms — one workgroup per problem stops paying where eight of them leave most of the chip idle
+ * for longer than eight whole-chip fits take.  (The environment variable GPMI_BATCH_MAX_N, 0 … 2 048 = what the kernel admits, read per call, overrides
+ * it for measurements.) */
+#define GPMI355_BATCH_MAX_N 768
+int32_t gp_logpdf_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                        const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
+                        void* const* alpha_out_or_null);
+/* The same with one composite kernel (gp_ksum) per problem. */
+int32_t gp_logpdf_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                            const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
+                            void* const* alpha_out_or_null);
+
 /* Sequential conditioning, posterior(fx::FiniteGP{<:PosteriorGP}, y) (src/exact_gpr_posterior.jl:46-56): the resident
  * factor of `old` is extended by the bordered-Cholesky step update_chol (src/util/common_covmat_ops.jl:38-42):
  *   U12 = U11'\C12  (here: rows K(x2,x1)·L11⁻ᵀ by the blocked MFMA TRSM),  U22 = chol(C22 − U12'U12).
