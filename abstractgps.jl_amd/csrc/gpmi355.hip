@@ -62,6 +62,13 @@ static void pool_drop(gp_ctx* c, size_t i) {
     (void)hipFree(c->pool[i].p);
     c->pool.erase(c->pool.begin() + i);
 }
+// "alloc_poison": all-ones bytes (NaN as fp64 / fp32, −1 as int32) over a block before anyone sees it.  The blocks are used on the panel and third
+// streams too, hence the wait (a diagnostic: nothing in the production path sets it).
+static int32_t ctx_poison(gp_ctx* c, void* p, size_t bytes) {
+    HIPCHK(hipMemsetAsync(p, 0xFF, bytes, c->sm));
+    HIPCHK(hipStreamSynchronize(c->sm));
+    return 0;
+}
 int32_t ctx_alloc(gp_ctx* c, size_t bytes, void** out) {
     size_t best = (size_t)-1;
     int bi = -1;
@@ -75,6 +82,7 @@ int32_t ctx_alloc(gp_ctx* c, size_t bytes, void** out) {
         c->blk[*out] = c->pool[bi].bytes;  // the block keeps its true size
         c->pool_bytes -= c->pool[bi].bytes;
         c->pool.erase(c->pool.begin() + bi);
+        if (c->alloc_poison) RC(ctx_poison(c, *out, c->blk[*out]));  // the block's true size
         return 0;
     }
     hipError_t e = hipMalloc(out, bytes);
@@ -85,6 +93,7 @@ int32_t ctx_alloc(gp_ctx* c, size_t bytes, void** out) {
     }
     if (e != hipSuccess) return set_hip_err(e, "hipMalloc", __LINE__);
     c->blk[*out] = bytes;
+    if (c->alloc_poison) RC(ctx_poison(c, *out, bytes));
     return 0;
 }
 void ctx_release(gp_ctx* c, void* p, size_t /*requested*/) {
@@ -178,6 +187,7 @@ int32_t ctx_scal(gp_ctx* c, long n) {
     if (c->scal_dev) (void)hipFree(c->scal_dev);
     c->scal_cap = round_up(n, 1024);
     HIPCHK(hipMalloc((void**)&c->scal_dev, sizeof(double) * c->scal_cap));
+    if (c->alloc_poison) RC(ctx_poison(c, c->scal_dev, sizeof(double) * c->scal_cap));
     return 0;
 }
 
@@ -203,6 +213,7 @@ int32_t ctx_prime(gp_ctx* c, long nb_hint) {
         c->w_ws_bytes = 0;
         HIPCHK(hipMalloc(&c->w_ws, need));
         HIPCHK(hipMemset(c->w_ws, 0, need));
+        if (c->alloc_poison) RC(ctx_poison(c, c->w_ws, need));
         c->w_ws_bytes = need;
     }
     hipLaunchKernelGGL(prime_kernel, dim3(1), dim3(64), 0, c->sm, c->info_dev);
@@ -427,6 +438,10 @@ template <typename T> static int32_t trtri_tiles(gp_ctx* c, hipStream_t s, const
         c->w_ws_bytes = 0;
         HIPCHK(hipMalloc(&c->w_ws, need));
         HIPCHK(hipMemsetAsync(c->w_ws, 0, need, s));  // same stream as the trtri launch that follows
+        if (c->alloc_poison) {
+            HIPCHK(hipStreamSynchronize(s));
+            RC(ctx_poison(c, c->w_ws, need));
+        }
         c->w_ws_bytes = need;
     }
     hipLaunchKernelGGL(trtri_64_kernel<T>, dim3((unsigned)(n / 64)), dim3(64), 0, s, L, ldl, (T*)c->w_ws);
@@ -1927,6 +1942,7 @@ int32_t gp_ctx_set_param(gp_ctx* c, const char* name, int64_t v) {
     else if (!strcmp(name, "vfe_overlap")) c->vfe_overlap = v != 0;
     else if (!strcmp(name, "vfe_chunk")) c->vfe_chunk = v <= 0 ? 0 : std::max<int64_t>(2048, round_up(v, 2048));
     else if (!strcmp(name, "pool_cap_mb")) c->pool_cap = (size_t)std::max<int64_t>(0, v) << 20;
+    else if (!strcmp(name, "alloc_poison")) c->alloc_poison = v != 0;
     else if (!strcmp(name, "lookahead_depth") || !strcmp(name, "dist_nb") || !strcmp(name, "copy_kernel") || !strcmp(name, "multi_debug_sync") ||
              !strcmp(name, "multi_check") || !strcmp(name, "multi_verify") || !strcmp(name, "multi_inject_fault") || !strcmp(name, "multi_dist_predict") || !strcmp(name, "multi_window") || !strcmp(name, "multi_timeout_s") || !strcmp(name, "multi_gemm_streamk") || !strcmp(name, "multi_leaf_cols")) return c->multi ? 0 : set_arg_err(2, "multi-device parameter on a single-device ctx");
     else return set_arg_err(2, "unknown parameter");
@@ -1947,7 +1963,7 @@ int32_t gp_ctx_get_param(gp_ctx* c, const char* name, int64_t* out) {
         {"leaf_v2", c->leaf_v2}, {"leaf_xr", c->leaf_xr}, {"leaf_cols", c->leaf_cols}, {"updk_max_k", c->updk_max_k}, {"updk_rt", c->updk_rt},
         {"updk_tall_k", c->updk_tall_k}, {"updk_tall_m", c->updk_tall_m}, {"upd128", c->upd128}, {"leaf_group", c->leaf_group},
         {"ldpad", c->ldpad}, {"dense_stage_mb", c->dense_stage_mb}, {"vfe_ks", c->vfe_ks}, {"vfe_sk", c->vfe_sk}, {"vfe_dual", c->vfe_dual}, {"vfe_inv_nb", c->vfe_inv_nb}, {"vfe_overlap", c->vfe_overlap}, {"vfe_chunk", c->vfe_chunk},
-        {"kmat_rows", g_kmat_rows.load()}, {"dib_nb", c->dib_nb}, {"pool_cap_mb", (int64_t)(c->pool_cap >> 20)},
+        {"kmat_rows", g_kmat_rows.load()}, {"dib_nb", c->dib_nb}, {"pool_cap_mb", (int64_t)(c->pool_cap >> 20)}, {"alloc_poison", c->alloc_poison},
         {"pool_cached_mb", (int64_t)(c->pool_bytes >> 20)}, {"pool_blocks", (int64_t)c->pool.size()}};  // the last two are read-only
     for (const auto& e : tab)
         if (!strcmp(name, e.n)) {

@@ -267,6 +267,10 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
  *                    of N = 131 072: 17.2 s per pair when it is returned to the driver and allocated again every fit, 11.0 s cached) — it takes the
  *                    place of everything else in the cache and is the last block to go; 0 caches nothing; gp_ctx_trim empties the cache; an
  *                    allocation that fails drops the cache and retries.   default 98304
+ *   "alloc_poison"   diagnostic: 1 = every device block the ctx hands out (recycled or fresh, over its true size) and the ctx's scalar / inverse-tile
+ *                    workspaces when they are created or grown are filled with 0xFF bytes first — NaN read as fp64 or fp32, −1 as int32 — by a memset
+ *                    on the main stream that is waited for.  No entry point may return anything that depends on what a block held before it wrote it
+ *                    (tests/test_gpu_poisoned_blocks.py); forwarded to the rank contexts of a multi-device ctx; one not-taken branch per allocation when 0.   default 0
  *   "pool_cached_mb", "pool_blocks"   read-only (gp_ctx_get_param): MiB and number of blocks in the cache now */
 /* The defaults above, machine-readable (single-device parameters; gp_ctx_get_param reads the same names): the test-suite asserts before
  * every GPU test that the shared default context still has exactly these values, so that no test can leave a non-production setting
@@ -275,7 +279,7 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
     "nb=-1,nb_small=4096,nb_large=2048,lookahead=1,lookahead_min_n=24576,time_kernels=0,xcd_swizzle=0,xcd_min_tiles=256,gemm_streamk=1,sk_max_tiles=4096," \
     "sk_min_k=0,gemm_pipe=1,gemm_pad_f32=0,gemm_pad_lds=0,trsv_nb=256,deterministic=0,leaf_v2=1,leaf_xr=0,leaf_cols=128,"    \
     "updk_max_k=512,updk_rt=0,updk_tall_k=256,updk_tall_m=8192,upd128=1,leaf_group=128,ldpad=32,vfe_ks=2048,vfe_sk=0,"          \
-    "vfe_overlap=1,vfe_dual=0,vfe_inv_nb=512,vfe_chunk=0,kmat_rows=1,dib_nb=2048,pool_cap_mb=98304,dense_stage_mb=64"
+    "vfe_overlap=1,vfe_dual=0,vfe_inv_nb=512,vfe_chunk=0,kmat_rows=1,dib_nb=2048,pool_cap_mb=98304,dense_stage_mb=64,alloc_poison=0"
 int32_t gp_ctx_set_param(gp_ctx* ctx, const char* name, int64_t value);
 /* Read a parameter back (same names; "gemm_pad_lds" reads 0 until it has been set explicitly).  Used by the test-suite to assert that
  * every GPU test starts from the documented defaults. */

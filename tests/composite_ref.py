@@ -116,3 +116,20 @@ def ref_from_theta(nf, th, X):
             prod = prod * factor(kind, sc, par, T)[0]
         K = K + var * prod
     return K
+
+
+def ml_kernel():
+    """The Mauna Loa form with amplitudes of order 1: the example's own amplitudes (50² for the trend) over dense inputs give K + Σy a condition
+    number near 1e9, where the 1e-13·Σσ² the assembly may differ by (raw differences, then scaled) moves logpdf by more than 1e-10."""
+    SE = agp.SqExponentialKernel
+    return (agp.with_lengthscale(SE(), 50.0) + 0.5 * (agp.with_lengthscale(agp.PeriodicKernel(r=[1.0]), 1.0) * agp.with_lengthscale(SE(), 100.0))
+            + 0.1 * agp.with_lengthscale(agp.RationalQuadraticKernel(alpha=1.5), 1.2)
+            + (0.05 * agp.with_lengthscale(SE(), 0.1) + 0.01 * agp.WhiteKernel()))
+
+
+def dense_data(n, seed=0):
+    """n points over 65 years (years since 1958), standardised trend + seasonal + noise."""
+    rng = np.random.default_rng(seed)
+    x = np.linspace(0.0, 65.0, n)
+    y = 0.02 * x**2 + 1.3 * x + 3.0 * np.sin(2 * np.pi * x) + 0.3 * rng.standard_normal(n)
+    return x, (y - y.mean()) / y.std()
