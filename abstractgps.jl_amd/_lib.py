@@ -113,10 +113,18 @@ PROTOTYPES = {
     "gpd_trsv": (i32, [vp, vp, i64, i64, vp, i64, i32, i32]),
     "gpd_gemv_t": (i32, [vp, vp, i64, i64, i64, vp, vp]),
     "gpd_rowsumsq": (i32, [vp, vp, i64, i64, i64, vp]),
+    "gpd_assemble_f32": (i32, [vp, PK, vp, i64, i64, i32, vp, PG, vp, i64, i64, i64]),
+    "gpd_potrf_f32": (i32, [vp, vp, i64, i64, i64, vp, i32, i64, vp]),
+    "gpd_trsm_f32": (i32, [vp, vp, i64, i64, vp, i64, i64]),
+    "gpd_gemm_nt_f32": (i32, [vp, vp, i64, vp, i64, vp, i64, i64, i64, i64, PG, i64, i64]),
+    "gpd_trsv_f32": (i32, [vp, vp, i64, i64, vp, i64, i32, i32]),
+    "gpd_gemv_t_f32": (i32, [vp, vp, i64, i64, i64, vp, vp]),
+    "gpd_rowsumsq_f32": (i32, [vp, vp, i64, i64, i64, vp]),
     "gpd_sync": (i32, [vp]),
     "gpd_gemm_time": (i32, [vp, C.POINTER(dbl), C.POINTER(i64)]),
     "gp_rccl_selftest": (i32, [i32, i64, C.POINTER(dbl)]),
     "gp_probe_mfma_f64": (i32, [vp, vp, vp, vp]),
+    "gp_probe_mfma_f32": (i32, [vp, vp, vp, vp]),
     "gp_bench_mfma_f64": (i32, [vp, i32, C.POINTER(dbl)]),
     "gp_bench_mfma_f32": (i32, [vp, i32, i32, C.POINTER(dbl)]),
 }

@@ -2828,6 +2828,22 @@ int32_t gp_probe_mfma_f64(gp_ctx* c, const double* A_host, const double* B_host,
     HIPCHK(hipFree(buf));
     return 0;
 }
+// the fp32 twin: D(16×16) = A(16×4)·B(4×16) through Tr<float> — the MFMA and the C/D row map every fp32 kernel uses
+int32_t gp_probe_mfma_f32(gp_ctx* c, const float* A_host, const float* B_host, float* D_host) {
+    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    std::lock_guard<std::mutex> l(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    float* buf;
+    HIPCHK(hipMalloc((void**)&buf, sizeof(float) * (64 + 64 + 256)));
+    HIPCHK(hipMemcpy(buf, A_host, sizeof(float) * 64, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(buf + 64, B_host, sizeof(float) * 64, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(mfma_probe_f32_kernel, dim3(1), dim3(64), 0, c->sm, buf, buf + 64, buf + 128);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->sm));
+    HIPCHK(hipMemcpy(D_host, buf + 128, sizeof(float) * 256, hipMemcpyDeviceToHost));
+    HIPCHK(hipFree(buf));
+    return 0;
+}
 // returns measured TFLOP/s of back-to-back v_mfma_f64_16x16x4_f64 (all CUs, 2 blocks per CU)
 int32_t gp_bench_mfma_f64(gp_ctx* c, int32_t iters, double* tflops_out) {
     if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
@@ -2903,42 +2919,139 @@ static GridMap to_map(const gp_grid* g, long row0, long col0) {
     return m;
 }
 
-int32_t gpd_assemble(gp_ctx* c, const gp_kernel* k, const double* x_dev, int64_t n_valid, int64_t n_pad, int32_t d,
-                     const double* noise_dev, const gp_grid* g, double* a_loc, int64_t lda, int64_t m_loc,
-                     int64_t n_loc) {
+extern "C++" {
+// Each building block with matrix / vector data of either dtype is ONE template (dev_*<T>) behind two extern "C" wrappers (gpd_X: fp64, gpd_X_f32).  The
+// fp32 kernels move rows as 16-byte pieces = 4 floats where the fp64 ones move 2 doubles and step k by 32 instead of 16 (kernels.hpp BK): what the fp32
+// instantiations need of their arguments is checked here (aligned4), what the fp64 entry points have always refused is unchanged.
+template <typename T> static inline bool aligned4(const T* p, int64_t ld) { return ((uintptr_t)p & 15) == 0 && ld % 4 == 0; }
+
+template <typename T>
+static int32_t dev_assemble(gp_ctx* c, const gp_kernel* k, const T* x_dev, int64_t n_valid, int64_t n_pad, int32_t d, const T* noise_dev, const gp_grid* g,
+                            T* a_loc, int64_t lda, int64_t m_loc, int64_t n_loc) {
     if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
     RC(check_kernel(k, d, 2));
     if (m_loc % 128 || n_loc % 128) return set_arg_err(11, "m_loc, n_loc must be multiples of 128");
+    if constexpr (sizeof(T) == 4) {  // the Gram kernel stores two columns (8 bytes) per lane
+        if (((uintptr_t)a_loc & 7) != 0) return set_arg_err(9, "a_loc must be 8-byte aligned");
+        if (lda % 2 != 0 || lda < n_loc) return set_arg_err(10, "lda must be even and >= n_loc");
+    }
     std::lock_guard<std::mutex> l(c->mu);
     HIPCHK(hipSetDevice(c->device));
     GridMap m = to_map(g, 0, 0);
     dim3 grid((unsigned)(n_loc / 128), (unsigned)(m_loc / 128));
     if (grid.x == 0 || grid.y == 0) return 0;
-    launch_kmat<double>(grid, c->sm, a_loc, lda, x_dev, n_pad, x_dev, n_pad, d,
-                       k->kind, k->variance, noise_dev, n_valid, n_valid, 1, m, (const double*)nullptr, (const double*)nullptr);
+    launch_kmat<T>(grid, c->sm, a_loc, lda, x_dev, n_pad, x_dev, n_pad, d, k->kind, (T)k->variance, noise_dev, n_valid, n_valid, 1, m, (const T*)nullptr,
+                   (const T*)nullptr);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-int32_t gpd_potrf(gp_ctx* c, double* a, int64_t lda, int64_t m, int64_t n, int32_t* info_dev, int32_t col0,
-                  int64_t n_valid, double* logdet_dev) {
+template <typename T>
+static int32_t dev_potrf(gp_ctx* c, T* a, int64_t lda, int64_t m, int64_t n, int32_t* info_dev, int32_t col0, int64_t n_valid, double* logdet_dev) {
     if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
     if (n % 64 || m % 64 || m < n) return set_arg_err(4, "m, n must be multiples of 64 with m >= n");
-    // the register-resident leaf and the in-panel update kernel move rows as 16-byte pieces (leaf.hpp ld4 / st4)
+    // the leaf kernels (and, in fp64, the in-panel update kernel) move rows as 16-byte pieces (leaf.hpp ld4 / st4; kernels.hpp panel64 chunk_t)
     if (((uintptr_t)a & 15) != 0) return set_arg_err(2, "a must be 16-byte aligned");
-    if (lda % 2 != 0 || lda < n) return set_arg_err(3, "lda must be even and >= n");
+    if constexpr (sizeof(T) == 8) {
+        if (lda % 2 != 0 || lda < n) return set_arg_err(3, "lda must be even and >= n");
+    } else {
+        if (lda % 4 != 0 || lda < n) return set_arg_err(3, "lda must be a multiple of 4 and >= n");
+    }
     std::lock_guard<std::mutex> l(c->mu);
     HIPCHK(hipSetDevice(c->device));
-    return potrf_rec<double>(c, c->sm, a, lda, 0, n, m, info_dev, col0, n_valid, logdet_dev);
+    return potrf_rec<T>(c, c->sm, a, lda, 0, n, m, info_dev, col0, n_valid, logdet_dev);
 }
 
-int32_t gpd_trsm(gp_ctx* c, double* x, int64_t ldx, int64_t m, const double* lmat, int64_t ldl, int64_t n) {
+template <typename T>
+static int32_t dev_trsm(gp_ctx* c, T* x, int64_t ldx, int64_t m, const T* lmat, int64_t ldl, int64_t n) {
     if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
     if (n % 64 || m % 64) return set_arg_err(4, "m, n must be multiples of 64");
+    if constexpr (sizeof(T) == 4) {
+        if (!aligned4(x, ldx)) return set_arg_err(2, "x must be 16-byte aligned and ldx a multiple of 4");
+        if (!aligned4(lmat, ldl)) return set_arg_err(5, "l must be 16-byte aligned and ldl a multiple of 4");
+    }
     if (m == 0) return 0;
     std::lock_guard<std::mutex> l(c->mu);
     HIPCHK(hipSetDevice(c->device));
-    return trsm_rec<double>(c, c->sm, x, ldx, m, lmat, ldl, n);
+    return trsm_rec<T>(c, c->sm, x, ldx, m, lmat, ldl, n);
+}
+
+template <typename T>
+static int32_t dev_gemm_nt(gp_ctx* c, T* cm, int64_t ldc, const T* a, int64_t lda, const T* b, int64_t ldb, int64_t m, int64_t n, int64_t k, const gp_grid* g,
+                           int64_t row0, int64_t col0) {
+    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    if constexpr (sizeof(T) == 8) {
+        if (m % 64 || n % 64 || k % 16) return set_arg_err(8, "m, n multiples of 64 and k multiple of 16 required");
+    } else {
+        if (m % 64 || n % 64 || k % 32) return set_arg_err(8, "m, n multiples of 64 and k multiple of 32 required");
+        // operand rows travel to LDS as 16-byte pieces (global_load_lds_dwordx4); C is read and written element by element
+        if (!aligned4(a, lda)) return set_arg_err(4, "a must be 16-byte aligned and lda a multiple of 4");
+        if (!aligned4(b, ldb)) return set_arg_err(6, "b must be 16-byte aligned and ldb a multiple of 4");
+    }
+    std::lock_guard<std::mutex> l(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    return launch_gemm<T>(c, c->sm, cm, ldc, a, lda, b, ldb, m, n, k, to_map(g, row0, col0));
+}
+
+template <typename T>
+static int32_t dev_trsv(gp_ctx* c, const T* lmat, int64_t ldl, int64_t np, T* r, int64_t ldr, int32_t nrhs, int32_t forward) {
+    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    if (np % 128) return set_arg_err(4, "np must be a multiple of 128");
+    if constexpr (sizeof(T) == 4) {  // the diagonal tiles are inverted from 16-byte row pieces (trtri_64)
+        if (!aligned4(lmat, ldl)) return set_arg_err(2, "l must be 16-byte aligned and ldl a multiple of 4");
+    }
+    std::lock_guard<std::mutex> l(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    return trsv<T>(c, c->sm, lmat, ldl, np, r, ldr, nrhs, forward != 0);
+}
+
+template <typename T>
+static int32_t dev_gemv_t(gp_ctx* c, const T* lmat, int64_t ldl, int64_t nrows, int64_t ncols, const T* a, T* r) {
+    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    if (nrows <= 0 || ncols <= 0) return 0;
+    std::lock_guard<std::mutex> l(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    hipLaunchKernelGGL(gemv_t_kernel<T>, dim3((unsigned)((ncols + 255) / 256), (unsigned)((nrows + 63) / 64)), dim3(256),
+                       0, c->sm, lmat, ldl, nrows, ncols, a, r);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+template <typename T>
+static int32_t dev_rowsumsq(gp_ctx* c, const T* x, int64_t ldx, int64_t nrows, int64_t ncols, double* out_dev) {
+    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    if (nrows <= 0) return 0;
+    std::lock_guard<std::mutex> l(c->mu);
+    HIPCHK(hipSetDevice(c->device));
+    hipLaunchKernelGGL(rowsumsq_kernel<T>, dim3((unsigned)nrows), dim3(256), 0, c->sm, x, ldx, ncols, out_dev);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+}  // extern "C++"
+
+int32_t gpd_assemble(gp_ctx* c, const gp_kernel* k, const double* x_dev, int64_t n_valid, int64_t n_pad, int32_t d,
+                     const double* noise_dev, const gp_grid* g, double* a_loc, int64_t lda, int64_t m_loc,
+                     int64_t n_loc) {
+    return dev_assemble<double>(c, k, x_dev, n_valid, n_pad, d, noise_dev, g, a_loc, lda, m_loc, n_loc);
+}
+int32_t gpd_assemble_f32(gp_ctx* c, const gp_kernel* k, const float* x_dev, int64_t n_valid, int64_t n_pad, int32_t d, const float* noise_dev,
+                         const gp_grid* g, float* a_loc, int64_t lda, int64_t m_loc, int64_t n_loc) {
+    return dev_assemble<float>(c, k, x_dev, n_valid, n_pad, d, noise_dev, g, a_loc, lda, m_loc, n_loc);
+}
+
+int32_t gpd_potrf(gp_ctx* c, double* a, int64_t lda, int64_t m, int64_t n, int32_t* info_dev, int32_t col0,
+                  int64_t n_valid, double* logdet_dev) {
+    return dev_potrf<double>(c, a, lda, m, n, info_dev, col0, n_valid, logdet_dev);
+}
+int32_t gpd_potrf_f32(gp_ctx* c, float* a, int64_t lda, int64_t m, int64_t n, int32_t* info_dev, int32_t col0, int64_t n_valid, double* logdet_dev) {
+    return dev_potrf<float>(c, a, lda, m, n, info_dev, col0, n_valid, logdet_dev);
+}
+
+int32_t gpd_trsm(gp_ctx* c, double* x, int64_t ldx, int64_t m, const double* lmat, int64_t ldl, int64_t n) {
+    return dev_trsm<double>(c, x, ldx, m, lmat, ldl, n);
+}
+int32_t gpd_trsm_f32(gp_ctx* c, float* x, int64_t ldx, int64_t m, const float* lmat, int64_t ldl, int64_t n) {
+    return dev_trsm<float>(c, x, ldx, m, lmat, ldl, n);
 }
 
 int32_t gpd_inv_lower(gp_ctx* c, const double* lmat, int64_t ldl, int64_t nb, double* w, int64_t ldw, double* scratch1, double* scratch2) {
@@ -2960,41 +3073,33 @@ int32_t gpd_trsm_inv(gp_ctx* c, double* x, int64_t ldx, int64_t m, const double*
 
 int32_t gpd_gemm_nt(gp_ctx* c, double* cm, int64_t ldc, const double* a, int64_t lda, const double* b, int64_t ldb,
                     int64_t m, int64_t n, int64_t k, const gp_grid* g, int64_t row0, int64_t col0) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
-    if (m % 64 || n % 64 || k % 16) return set_arg_err(8, "m, n multiples of 64 and k multiple of 16 required");
-    std::lock_guard<std::mutex> l(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    return launch_gemm<double>(c, c->sm, cm, ldc, a, lda, b, ldb, m, n, k, to_map(g, row0, col0));
+    return dev_gemm_nt<double>(c, cm, ldc, a, lda, b, ldb, m, n, k, g, row0, col0);
+}
+int32_t gpd_gemm_nt_f32(gp_ctx* c, float* cm, int64_t ldc, const float* a, int64_t lda, const float* b, int64_t ldb, int64_t m, int64_t n, int64_t k,
+                        const gp_grid* g, int64_t row0, int64_t col0) {
+    return dev_gemm_nt<float>(c, cm, ldc, a, lda, b, ldb, m, n, k, g, row0, col0);
 }
 
 int32_t gpd_trsv(gp_ctx* c, const double* lmat, int64_t ldl, int64_t np, double* r, int64_t ldr, int32_t nrhs,
                  int32_t forward) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
-    if (np % 128) return set_arg_err(4, "np must be a multiple of 128");
-    std::lock_guard<std::mutex> l(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    return trsv<double>(c, c->sm, lmat, ldl, np, r, ldr, nrhs, forward != 0);
+    return dev_trsv<double>(c, lmat, ldl, np, r, ldr, nrhs, forward);
+}
+int32_t gpd_trsv_f32(gp_ctx* c, const float* lmat, int64_t ldl, int64_t np, float* r, int64_t ldr, int32_t nrhs, int32_t forward) {
+    return dev_trsv<float>(c, lmat, ldl, np, r, ldr, nrhs, forward);
 }
 
 int32_t gpd_gemv_t(gp_ctx* c, const double* lmat, int64_t ldl, int64_t nrows, int64_t ncols, const double* a, double* r) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
-    if (nrows <= 0 || ncols <= 0) return 0;
-    std::lock_guard<std::mutex> l(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipLaunchKernelGGL(gemv_t_kernel<double>, dim3((unsigned)((ncols + 255) / 256), (unsigned)((nrows + 63) / 64)), dim3(256),
-                       0, c->sm, lmat, ldl, nrows, ncols, a, r);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return dev_gemv_t<double>(c, lmat, ldl, nrows, ncols, a, r);
+}
+int32_t gpd_gemv_t_f32(gp_ctx* c, const float* lmat, int64_t ldl, int64_t nrows, int64_t ncols, const float* a, float* r) {
+    return dev_gemv_t<float>(c, lmat, ldl, nrows, ncols, a, r);
 }
 
 int32_t gpd_rowsumsq(gp_ctx* c, const double* x, int64_t ldx, int64_t nrows, int64_t ncols, double* out_dev) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
-    if (nrows <= 0) return 0;
-    std::lock_guard<std::mutex> l(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    hipLaunchKernelGGL(rowsumsq_kernel<double>, dim3((unsigned)nrows), dim3(256), 0, c->sm, x, ldx, ncols, out_dev);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return dev_rowsumsq<double>(c, x, ldx, nrows, ncols, out_dev);
+}
+int32_t gpd_rowsumsq_f32(gp_ctx* c, const float* x, int64_t ldx, int64_t nrows, int64_t ncols, double* out_dev) {
+    return dev_rowsumsq<float>(c, x, ldx, nrows, ncols, out_dev);
 }
 
 int32_t gpd_gemm_time(gp_ctx* c, double* ms_out, int64_t* launches_out) {

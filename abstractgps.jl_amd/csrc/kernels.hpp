@@ -2795,6 +2795,13 @@ __global__ void mfma_probe_f64_kernel(const double* A, const double* B, double* 
     c = __builtin_amdgcn_mfma_f64_16x16x4f64(A[(l & 15) * 4 + (l >> 4)], B[(l >> 4) * 16 + (l & 15)], c, 0, 0, 0);
     for (int r = 0; r < 4; ++r) D[((l >> 4) + 4 * r) * 16 + (l & 15)] = c[r];
 }
+// the same through the fp32 traits (kcommon.hpp Tr<float>): the MFMA and the C/D row map of every fp32 kernel
+__global__ void mfma_probe_f32_kernel(const float* A, const float* B, float* D) {
+    const int l = threadIdx.x;
+    f4_t c = (f4_t)(0.0f);
+    c = Tr<float>::mfma(A[(l & 15) * 4 + (l >> 4)], B[(l >> 4) * 16 + (l & 15)], c);
+    for (int r = 0; r < 4; ++r) D[Tr<float>::crow(l, r) * 16 + (l & 15)] = c[r];
+}
 // Peak-rate microbenchmark: one 1024-thread block per CU (a large dynamic-LDS request pins residency to
 // 1 block/CU), i.e. 4 waves per SIMD, 4 independent accumulators per wave, iters back-to-back MFMAs.
 __global__ __launch_bounds__(1024) void mfma_rate_f64_kernel(double* out, int iters) {

@@ -482,10 +482,13 @@ int32_t gp_vfe_free(gp_vfe* post);
 /* ---- device-level building blocks ------------------------------------------------------------ */
 /* The operations the in-library multi-device driver composes (csrc/multi.hip calls the same engine functions), exposed on DEVICE
  * memory so that they can be unit-tested one by one (tests/test_gpu_units.py) and driven by a caller that keeps its own
- * device-resident data.  All pointers below are DEVICE pointers (fp64), row-major with the given leading dimension, i.e.
+ * device-resident data.  All pointers below are DEVICE pointers (double* in the entry points declared first, float* in their
+ * _f32 twins), row-major with the given leading dimension, i.e.
  * a row-major lower factor L — memory-identical to Julia's column-major C.U.  Work is issued on the
  * ctx main stream and NOT synchronised (gpd_sync, or order it against your own stream work).
- * m, n multiples of 64 (gpd_trsv: np multiple of 128); k multiple of 16 (gemm). */
+ * m, n multiples of 64 (gpd_trsv: np multiple of 128); k multiple of 16 (gemm; 32 in gpd_gemm_nt_f32).
+ * Every entry point with matrix / vector data has an fp32 twin gpd_X_f32 (declared below, after the fp64 ones): the same arguments with float* data, the same kernels
+ * instantiated for float — what every fp32 fit runs (tests/test_gpu_units_f32.py).  info_dev stays int32*, logdet_dev and the row sums stay double*. */
 
 /* Fill local tiles of K + Σy.  rows: global indices row0 + i (i < m) mapped through the block-cyclic
  * map (global tile-row of local 128-tile t is ((t / tb) * P + p) * tb + t % tb); same for columns with
@@ -531,6 +534,30 @@ int32_t gpd_gemv_t(gp_ctx* ctx, const double* l, int64_t ldl, int64_t nrows, int
 /* out_dev[i] = Σ_{c<ncols} x[i*ldx + c]² for i < nrows. */
 int32_t gpd_rowsumsq(gp_ctx* ctx, const double* x, int64_t ldx, int64_t nrows, int64_t ncols, double* out_dev);
 int32_t gpd_sync(gp_ctx* ctx);
+/* The fp32 twins.  Contracts, read off the float instantiations (rows move as 16-byte pieces = 4 floats; the GEMM's k step is 32); anything else is refused with a
+ * status and a reason (gp_last_error), never run:
+ *   gpd_assemble_f32 : m_loc, n_loc multiples of 128 (−11); a_loc 8-byte aligned (−9), lda even and >= n_loc (−10): two columns per store.
+ *   gpd_potrf_f32    : m, n multiples of 64, m >= n (−4); a 16-byte aligned (−2); lda a multiple of 4 and >= n (−3).  Every leaf is panel64_kernel<float>
+ *                      ("leaf_v2" is fp64-only); (m + 128) rows allocated (the trailing GEMM's operand over-read).
+ *   gpd_trsm_f32     : m, n multiples of 64 (−4); x and l 16-byte aligned, ldx and ldl multiples of 4 (−2 / −5).
+ *   gpd_gemm_nt_f32  : m, n multiples of 64, k a multiple of 32 (−8); a and b 16-byte aligned, lda and ldb multiples of 4 (−4 / −6); c: any float alignment.
+ *                      As in fp64 both operands are over-read up to the next multiple of 128 rows: allocate them.
+ *   gpd_trsv_f32     : np a multiple of 128 (−4); l 16-byte aligned, ldl a multiple of 4 (−2); r: any float alignment.
+ *   gpd_gemv_t_f32, gpd_rowsumsq_f32 : element-wise access, no alignment contract (gpd_rowsumsq_f32 sums in fp64 and returns doubles). */
+int32_t gpd_assemble_f32(gp_ctx* ctx, const gp_kernel* k, const float* x_dev, int64_t n_valid, int64_t n_pad,
+                         int32_t d, const float* noise_dev, const gp_grid* g, float* a_loc, int64_t lda,
+                         int64_t m_loc, int64_t n_loc);
+int32_t gpd_potrf_f32(gp_ctx* ctx, float* a, int64_t lda, int64_t m, int64_t n, int32_t* info_dev, int32_t col0,
+                      int64_t n_valid, double* logdet_dev);
+int32_t gpd_trsm_f32(gp_ctx* ctx, float* x, int64_t ldx, int64_t m, const float* l, int64_t ldl, int64_t n);
+int32_t gpd_gemm_nt_f32(gp_ctx* ctx, float* c, int64_t ldc, const float* a, int64_t lda, const float* b,
+                        int64_t ldb, int64_t m, int64_t n, int64_t k, const gp_grid* g_or_null, int64_t row0,
+                        int64_t col0);
+int32_t gpd_trsv_f32(gp_ctx* ctx, const float* l, int64_t ldl, int64_t np, float* r, int64_t ldr, int32_t nrhs,
+                     int32_t forward);
+int32_t gpd_gemv_t_f32(gp_ctx* ctx, const float* l, int64_t ldl, int64_t nrows, int64_t ncols, const float* a,
+                       float* r);
+int32_t gpd_rowsumsq_f32(gp_ctx* ctx, const float* x, int64_t ldx, int64_t nrows, int64_t ncols, double* out_dev);
 /* With parameter "time_kernels" = 1 every gpd_gemm_nt launch is bracketed by HIP events on the ctx
  * stream.  This synchronises the stream, returns the summed launch durations (ms) and the launch count since the
  * previous call, and clears the records (the caller knows the algorithmic flops of its own launches). */
@@ -545,6 +572,8 @@ int32_t gp_rccl_selftest(int32_t device, int64_t count, double* max_abs_err_out_
 /* ---- probes used by tools/gpu_diag.py and bench.py ------------------------------------------ */
 /* D(16×16) = A(16×4)·B(4×16), all row-major host arrays: checks the f64 MFMA lane maps. */
 int32_t gp_probe_mfma_f64(gp_ctx* ctx, const double* a_host, const double* b_host, double* d_host);
+/* the same for fp32, through the traits every fp32 kernel uses (csrc/kcommon.hpp Tr<float>: v_mfma_f32_16x16x4_f32, row = 4·(lane>>4) + r). */
+int32_t gp_probe_mfma_f32(gp_ctx* ctx, const float* a_host, const float* b_host, float* d_host);
 /* measured TFLOP/s of back-to-back v_mfma_f64_16x16x4_f64 on all CUs (the roofline's measured ceiling). */
 int32_t gp_bench_mfma_f64(gp_ctx* ctx, int32_t iters, double* tflops_out);
 /* the same for fp32: variant 0 = v_mfma_f32_16x16x4_f32, 1 = v_mfma_f32_32x32x2_f32 (the C5 roofline's measured ceiling). */

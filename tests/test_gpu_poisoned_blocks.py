@@ -492,7 +492,9 @@ class Fp32DtcVarianceOff(AssertionError):
 FP32_DTC_FINDING = ("gp_vfe_grad on an fp32 DTC handle with M = 40: d/dvariance is 6.3e-3 from the fp64 oracle (bound 2e-3·max(|ref|, 1), reference 0.86) on a clean "
                     "and on a poisoned context alike.  Not a stale-block dependence: the fp32 chunk SYRK of csrc/vfe.hpp (launch_gemm<float>, gemm_nt_dma, into the fp32 "
                     "scratch that add_lower_batched_kernel sums into D_acc) rounds the M×M accumulator D_acc = B Bᵀ, whose entries are of size tr(B Bᵀ) ≈ 2e4, and "
-                    "the backward pass forms tr(C⁻¹ Q_ff) <= M from it by the Woodbury identity; the ELBO's trace term (−3 336) hides the same error for VFE")
+                    "the backward pass forms tr(C⁻¹ Q_ff) <= M from it by the Woodbury identity; the ELBO's trace term (−3 336) hides the same error for VFE.  "
+                    "The fp32 GEMM / SYRK kernels themselves are inside their rounding bounds (tests/test_gpu_units_f32.py: exact on integer operands, at most 0.01 of "
+                    "γ_{k+2·CUs}(|C₀| + |A||B|ᵀ) up to k = 20 000), so the miss is rounding amplified by the cancellation, not a kernel fault")
 
 
 def _sparse_case(m, approx, dtype, variance_against):

@@ -9,6 +9,9 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 
+from tests import unit_helpers as uh  # noqa: E402  (after the importorskip: it imports torch)
+
+
 def P(t):
     return C.c_void_p(t.data_ptr())
 
@@ -21,6 +24,19 @@ def lib(agp):
 @pytest.fixture(scope="module")
 def h(ctx):
     return ctx.handle
+
+
+@pytest.fixture(scope="module")
+def pad_h(agp):
+    with uh.padded_context(agp) as hh:
+        yield hh
+
+
+@pytest.fixture(params=list(uh.GEMM_CONFIGS))
+def gemm_h(request, lib, h, pad_h):
+    """the handle to launch on, under one of the GEMM launch variants (unit_helpers.GEMM_CONFIGS)"""
+    with uh.gemm_variant(lib, h, pad_h, request.param) as hh:
+        yield hh
 
 
 def _sync(lib, h):
@@ -90,8 +106,22 @@ def test_gemm_nt_lower_skips_upper(lib, h, m, n, off, coff):
         assert got[skipped].abs().max().item() == 0.0
 
 
-@pytest.mark.parametrize("n,extra", [(64, 0), (64, 192), (128, 64), (192, 128), (256, 0), (1024, 256),
-                                      (64, 128 * 700), (128, 128 * 300 + 64)])  # > 256 workgroups: late starters
+@pytest.mark.parametrize("m,n", uh.GEMM_RECT)
+def test_gemm_nt_exact_rect(lib, gemm_h, m, n):
+    """integer operands: the result equals the reference exactly, whatever the summation order (sharper than 1e-11·√k, and free)"""
+    uh.gemm_exact(lib, gemm_h, torch.float64, m, n)
+
+
+@pytest.mark.parametrize("m,n,off,coff", uh.GEMM_LOWER)
+def test_gemm_nt_exact_lower(lib, gemm_h, m, n, off, coff):
+    uh.gemm_exact(lib, gemm_h, torch.float64, m, n, lower=(off, coff))
+
+
+POTRF_SHAPES = [(64, 0), (64, 192), (128, 64), (192, 128), (256, 0), (1024, 256),
+                (64, 128 * 700), (128, 128 * 300 + 64)]  # > 256 workgroups: late starters
+
+
+@pytest.mark.parametrize("n,extra", POTRF_SHAPES)
 def test_potrf_and_trsm(lib, h, n, extra):
     from abstractgps_jl_amd._lib import check
 
@@ -182,6 +212,14 @@ def test_rowsumsq(lib, h):
     np.testing.assert_allclose(out.cpu().numpy(), (X[:, :777] ** 2).sum(1).cpu().numpy(), rtol=1e-13)
 
 
+def test_gemv_t_exact(lib, h):
+    uh.gemv_t_exact(lib, h, torch.float64)
+
+
+def test_rowsumsq_exact(lib, h):
+    uh.rowsumsq_exact(lib, h, torch.float64)
+
+
 @pytest.mark.parametrize("group", [64, 128, 256, 512])
 def test_potrf_leaf_groups(lib, h, group):
     """left-looking leaf groups: a leaf applies the kpre = 0..group/64−1 tiles to its left itself before factoring (64 = every
@@ -196,6 +234,25 @@ def test_potrf_leaf_groups(lib, h, group):
         test_potrf_reports_first_bad_pivot(lib, h)
     finally:
         check(lib.gp_ctx_set_param(h, b"leaf_group", 128))
+
+
+@pytest.mark.parametrize("group", [64, 128, 256, 512])
+def test_potrf_panel64_leaf(lib, h, group):
+    """leaf_v2 = 0: every leaf is panel64_kernel<double> — the template whose float instantiation is the ONLY fp32 leaf — with its kpre = 0..group/64−1 left tiles,
+    at the fp64 tolerances of test_potrf_and_trsm (the register-resident leaf.hip kernels that are the fp64 default hide it from every other fp64 test)"""
+    with uh.params(lib, h, leaf_v2=0, leaf_group=group):
+        for n, extra in POTRF_SHAPES + [(512, 0), (576, 200 * 128 + 64), (1024, 320)]:
+            test_potrf_and_trsm(lib, h, n, extra)
+        test_potrf_reports_first_bad_pivot(lib, h)
+
+
+@pytest.mark.parametrize("xr", [64, 128])
+def test_potrf_leaf_row_tiles(lib, h, xr):
+    """leaf_xr = 64 / 128: the rows of X per workgroup of the register-resident leaf forced (0, the default, lets the launch pick)"""
+    with uh.params(lib, h, leaf_xr=xr):
+        for n, extra in POTRF_SHAPES + [(576, 200 * 128 + 64)]:
+            test_potrf_and_trsm(lib, h, n, extra)
+        test_potrf_reports_first_bad_pivot(lib, h)
 
 
 @pytest.mark.parametrize("rt,maxk", [(1, 512), (2, 512), (4, 512), (0, 1024), (0, 0)])
