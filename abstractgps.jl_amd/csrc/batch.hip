@@ -321,8 +321,7 @@ void pack_points(const gp_points& x, double* out) {
 }
 
 void put_result(const BatchArgs& a, int b, double lp, int32_t info) {
-    if (a.dtype == 0) ((double*)a.logpdf_out)[b] = lp;
-    else ((float*)a.logpdf_out)[b] = (float)lp;
+    put(a.logpdf_out, a.dtype, b, lp);
     a.info_out[b] = info;
 }
 
@@ -416,7 +415,7 @@ int32_t run_wave(gp_ctx* c, const BatchArgs& a, const std::vector<KSum>& packed,
     RC(bufs.get(in_bytes, &in_d));
     RC(bufs.get(sizeof(double) * (size_t)ws, &ws_d));
     RC(bufs.get(out_bytes, &res_d));
-    const int32_t rc = [&]() -> int32_t {
+    RC(run_drained(c, [&]() -> int32_t {
         HIPCHK(hipMemcpyAsync(in_d, hin, in_bytes, hipMemcpyHostToDevice, c->sm));
         if (a.ks) hipLaunchKernelGGL(batch_logpdf_kernel<true>, dim3((unsigned)nw), dim3(NT), 0, c->sm, (const double*)in_d, (double*)ws_d, (double*)res_d, nw);
         else hipLaunchKernelGGL(batch_logpdf_kernel<false>, dim3((unsigned)nw), dim3(NT), 0, c->sm, (const double*)in_d, (double*)ws_d, (double*)res_d, nw);
@@ -424,11 +423,7 @@ int32_t run_wave(gp_ctx* c, const BatchArgs& a, const std::vector<KSum>& packed,
         HIPCHK(hipMemcpyAsync(hout, res_d, out_bytes, hipMemcpyDeviceToHost, c->sm));
         HIPCHK(hipStreamSynchronize(c->sm));
         return 0;
-    }();
-    if (rc != 0) {
-        (void)hipStreamSynchronize(c->sm);
-        return rc;
-    }
+    }));
     for (int t = 0; t < nw; ++t) {
         const int b = idx[t];
         put_result(a, b, hout[t], (int32_t)hout[nw + t]);
@@ -438,7 +433,8 @@ int32_t run_wave(gp_ctx* c, const BatchArgs& a, const std::vector<KSum>& packed,
 }
 
 int32_t batch_impl(gp_ctx* c, BatchArgs& a) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     if (a.nb < 0) return set_arg_err(2, "nb must be >= 0");
     if (a.nb == 0) return 0;
     if (!a.k && !a.ks) return set_arg_err(3, "kernel array is NULL");
@@ -475,7 +471,6 @@ int32_t batch_impl(gp_ctx* c, BatchArgs& a) {
         (take ? mine : routed).push_back(b);
     }
     if (!mine.empty()) {
-        std::lock_guard<std::mutex> l(c->mu);
         HIPCHK(hipSetDevice(c->device));
         size_t i = 0;
         while (i < mine.size()) {  // waves bounded by the workspace budget and by the launch size
@@ -490,13 +485,14 @@ int32_t batch_impl(gp_ctx* c, BatchArgs& a) {
             i = j;
         }
     }
-    // everything else: the single path, one problem at a time (each call takes the ctx lock itself)
+    // everything else: the single path, one problem at a time.  Each of those calls takes the ctx lock itself (std::mutex is not recursive): it is released
+    // here; the ctx stays pinned by the Guard, and every call validates it again.
+    gd.lk.unlock();
     const size_t es = a.dtype == 0 ? 8 : 4;
     for (int b : routed) {
         const gp_points& x = a.xb(b);
         int32_t rc;
-        if (a.dtype == 0) ((double*)a.logpdf_out)[b] = 0;
-        else ((float*)a.logpdf_out)[b] = 0;
+        put(a.logpdf_out, a.dtype, b, 0);
         void* lp = (char*)a.logpdf_out + es * (size_t)b;
         if (a.ab(b)) {
             gp_post* post = nullptr;

@@ -9,6 +9,7 @@
 
 #include <array>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <string>
@@ -72,6 +73,15 @@ int32_t set_err_text(int32_t status, const std::string& msg);  // returns status
 
 static inline long round_up(long v, long m) { return (v + m - 1) / m * m; }
 static const double LOG2PI = 1.8378770664093454835606594728112;
+
+// ---- dtype plumbing of the C ABI (dtype 0 = f64, 1 = f32: include/gpmi355.h) -------------------------
+// f(double()) or f(float()): one generic lambda in place of a ternary that spells its argument list twice
+template <class F> static inline auto by_dtype(int dtype, F&& f) { return dtype == 0 ? f(double()) : f(float()); }
+// out[i] = v in the call's dtype (results are computed in double and handed back in the caller's type)
+static inline void put(void* out, int dtype, size_t i, double v) {
+    if (dtype == 0) ((double*)out)[i] = v;
+    else ((float*)out)[i] = (float)v;
+}
 
 // ------------------------------------------------------------------------------------------------
 // handles
@@ -187,28 +197,51 @@ int32_t ctx_prime(gp_ctx* c, long nb_hint);          // lazy workspaces + the ha
 int32_t ctx_prime_stream(gp_ctx* c, hipStream_t s);  // one empty kernel on s (creates its hardware queue), drained
 // Validates a handle (gp_ctx / gp_post / gp_vfe) and locks its ctx without racing a concurrent *_free / gp_ctx_destroy from
 // another thread: the ctx is pinned under the registry mutex, locked, and the handle is checked again under the ctx lock
-// (every *_free removes its handle from the registry BEFORE it takes the ctx lock to release the buffers).
+// (every *_free and gp_ctx_destroy remove their handle from the registry BEFORE they take the ctx lock to release the buffers).
+// Every entry point that takes a handle starts with it, the ones that take a gp_ctx included; the argument checks that follow run
+// under the lock (they touch neither the device nor another lock; std::mutex is not recursive: nothing below an entry point locks again).
 struct Guard {
     gp_ctx* c = nullptr;
     std::unique_lock<std::mutex> lk;
     bool ok = false;
     static gp_ctx* ctx_of(gp_ctx* h) { return h; }
     template <class H> static gp_ctx* ctx_of(H* h) { return h->ctx; }
-    template <class H> explicit Guard(H* h) {
+    // lock = false (gpd_sync): the live handle's ctx is pinned for the Guard's lifetime — it cannot be freed under the caller — and nothing is locked
+    template <class H> explicit Guard(H* h, bool lock = true) {
         {
             std::lock_guard<std::mutex> l(g_reg_mu);
             if (!h || !g_live.count((void*)h)) return;
             c = ctx_of(h);
             c->refs++;
         }
-        lk = std::unique_lock<std::mutex>(c->mu);
-        ok = reg_has((void*)h) && !c->dead;
+        if (lock) lk = std::unique_lock<std::mutex>(c->mu);
+        ok = !lock || (reg_has((void*)h) && !c->dead);
     }
     ~Guard() {
         if (lk.owns_lock()) lk.unlock();
         if (c) ctx_unref(c);
     }
 };
+
+// The device work of one call (a lambda that HIPCHK / RC leave early): when it fails, both ctx streams are drained before the call's blocks go back to
+// the cache (an idle stream costs nothing on an error path).
+static inline void ctx_drain(gp_ctx* c) {
+    (void)hipStreamSynchronize(c->sm);
+    (void)hipStreamSynchronize(c->sp);
+}
+template <class F> static inline int32_t run_drained(gp_ctx* c, F&& f) {
+    const int32_t rc = f();
+    if (rc != 0) ctx_drain(c);
+    return rc;
+}
+
+// Hands a filled handle (gp_post / gp_vfe) of ctx c to the caller: from here on it holds a reference on c and is live.  Until then the unique_ptr owns
+// it, so every error path of the entry point drops it.  Caller holds the ctx lock.
+template <class H> static inline void publish(gp_ctx* c, std::unique_ptr<H>& h, H** out) {
+    c->refs++;
+    reg_add(h.get());
+    *out = h.release();
+}
 
 // RAII owner of the device blocks of one call: everything still owned when it goes out of scope returns to the ctx cache
 // (every early-return / error path included); keep() hands a block over to a handle.
@@ -261,6 +294,31 @@ struct DibCache {
     long nbi = 0, ldw = 0;  // nbi = −1: this factor keeps the substitution leaves (conditioning guard)
 };
 
+// ---- the kernel of a handle -----------------------------------------------------------------------
+// What a Gram / mean launch evaluates: one kind (variance · κ_kind on pre-scaled inputs, ks == nullptr) or a composite kernel (ks, raw inputs).
+struct KDesc {
+    int kind;
+    double variance;
+    const gpmi::KSum* ks;
+};
+// The kernel a handle was fitted with, as every later call on the handle needs it: a single kind behind scale.size() input scales (0 none, 1 ScaleTransform,
+// D ARDTransform), or a composite kernel — then kind 0, no scales (xs holds the RAW inputs) and variance Σ_t σ_t², the prior variance the predictions use.
+struct KernelRec {
+    int kind = 0;
+    double variance = 1;
+    std::vector<double> scale;
+    bool composite = false;
+    gpmi::KSum ks{};
+    KernelRec() = default;
+    KernelRec(const gp_kernel* k, const gpmi::KSum* s) : kind(k->kind), variance(k->variance), composite(s != nullptr) {
+        if (k->scale && k->nscale > 0) scale.assign(k->scale, k->scale + k->nscale);
+        if (s) ks = *s;
+    }
+    int nscale() const { return (int)scale.size(); }
+    gp_kernel view(int dtype) const { return gp_kernel{kind, dtype, variance, nscale(), scale.empty() ? nullptr : scale.data()}; }  // borrows scale
+    KDesc desc() const { return KDesc{kind, variance, composite ? &ks : nullptr}; }
+};
+
 // ---- posterior handle -----------------------------------------------------------------------------
 struct gp_multi;
 struct gp_multi_post;  // multi.hip: block-cyclic pieces of a factor that has not been gathered yet
@@ -269,10 +327,7 @@ struct gp_post {
     int dtype;
     long n, np, ld, mtot;
     int d;
-    int kind;
-    double variance;
-    int nscale;
-    std::vector<double> scale;
+    KernelRec kern;  // (a handle from gp_posterior_fit_sum keeps its composite kernel)
     void* A;
     size_t A_bytes;  // factor (+ RHS rows)
     void* xs;
@@ -282,8 +337,6 @@ struct gp_post {
     double logdet_half;  // Σ log L_ii
     DibCache dibc;            // −inv(L_bb) of the factor's diagonal blocks, built on the first forward solve against the resident factor ("dib_nb")
     gp_multi_post* pieces = nullptr;  // multi-device fit: the factor still lives as block-cyclic pieces (A == nullptr until gathered)
-    bool composite = false;   // fitted by gp_posterior_fit_sum: the kernel is `ks` (kind 0, nscale 0, variance Σ_t σ_t²), xs holds the RAW inputs
-    gpmi::KSum ks{};
 };
 
 // ---- engine entry points used by multi.hip (fp64; work is issued on stream s of ctx c and not synchronised) ----

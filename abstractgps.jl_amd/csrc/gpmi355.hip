@@ -940,15 +940,7 @@ static void scale_points_into(const gp_kernel* k, const gp_points* x, long ldx, 
 // posterior handle
 // ------------------------------------------------------------------------------------------------
 
-// The kernel a Gram / mean launch evaluates: one kind (variance · κ_kind on pre-scaled inputs, ks == nullptr) or a composite kernel (ks, raw
-// inputs).  Every place that evaluates a handle's kernel goes through gram() / kvec(); with a single kind they launch what they always launched.
-struct KDesc {
-    int kind;
-    double variance;
-    const KSum* ks;
-};
-static KDesc kdesc(const gp_kernel* k, const KSum* ks) { return KDesc{k->kind, k->variance, ks}; }
-static KDesc kdesc(const gp_post* p) { return KDesc{p->kind, p->variance, p->composite ? &p->ks : nullptr}; }
+// Every place that evaluates a kernel (KDesc, engine.hpp) goes through gram() / kvec(); with a single kind they launch what they always launched.
 template <typename T>
 static void gram(const KDesc& k, dim3 grid, hipStream_t s, T* out, long ld, const T* xr, long ldxr, const T* xc, long ldxc, int d, const T* noise,
                  long nr_valid, long nc_valid, int sym, GridMap g) {
@@ -1096,6 +1088,32 @@ struct FitOut {
     int32_t info = 0;
 };
 
+// gp_timings of a finished fit (the stream has been synchronised): the phases between the four ev_phase records and the event-bracketed GEMM launches
+static int32_t fit_timings(gp_ctx* c) {
+    float ms;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[0], c->ev_phase[1]));
+    c->tm.assemble_ms = ms;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[1], c->ev_phase[2]));
+    c->tm.potrf_ms = ms;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[2], c->ev_phase[3]));
+    c->tm.solve_ms = ms;
+    HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[0], c->ev_phase[3]));
+    c->tm.total_ms = ms;
+    c->tm.gemm_ms = 0;
+    c->tm.gemm_flops = 0;
+    c->tm.gemm_bytes = 0;
+    c->tm.gemm_launches = (int64_t)c->gemm_recs.size();
+    for (auto& r : c->gemm_recs) {
+        HIPCHK(hipEventElapsedTime(&ms, r.a, r.b));
+        c->tm.gemm_ms += ms;
+        c->tm.gemm_flops += r.flops;
+        c->tm.gemm_bytes += r.bytes;
+        if (getenv("GPMI_DUMP_GEMM"))
+            fprintf(stderr, "GEMM s%d M=%ld N=%ld K=%ld ms=%.4f tflops=%.2f\n", r.stream, r.M, r.N, r.K, ms, r.flops / ms / 1e9);
+    }
+    return 0;
+}
+
 // Shared by gp_logpdf and gp_posterior_fit.  Y: n×ncols column-major host.  If post != NULL the factor
 // is kept and α is computed for column 0.  ks != NULL: a composite kernel (the *_sum calls) — k then scales nothing (nscale 0) and
 // carries Σ_t σ_t² as its variance, the prior variance the predictions use.
@@ -1138,7 +1156,7 @@ static int32_t fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const
     RC(bufs.get(nz_bytes, &alpha_v));
     T* A = (T*)A_v;
     double logdet_half_out = 0;
-    int32_t rc = [&]() -> int32_t {
+    const int32_t rc = run_drained(c, [&]() -> int32_t {
         HIPCHK(hipEventRecord(c->ev_phase[0], c->sm));
         HIPCHK(hipMemcpyAsync(xs_v, xs_h.data(), xs_bytes, hipMemcpyHostToDevice, c->sm));
         HIPCHK(hipMemcpyAsync(noise_v, noise_h.data(), nz_bytes, hipMemcpyHostToDevice, c->sm));
@@ -1148,7 +1166,7 @@ static int32_t fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const
         HIPCHK(hipMemsetAsync(A + np * ld, 0, sizeof(T) * (size_t)(R + 128) * ld, c->sm));
         HIPCHK(hipMemcpy2DAsync(A + np * ld, sizeof(T) * ld, rhs_h.data(), sizeof(T) * np, sizeof(T) * np, ncols,
                                 hipMemcpyHostToDevice, c->sm));
-        RC(assemble_sym<T>(c, kdesc(k, ks), (const T*)xs_v, np, d, (const T*)noise_v, n, np, A, ld));
+        RC(assemble_sym<T>(c, KDesc{k->kind, k->variance, ks}, (const T*)xs_v, np, d, (const T*)noise_v, n, np, A, ld));
         if (noise_dense(noise)) RC((dense_add<T, T>(c, bufs, A, ld, noise, n)));  // all of Σy before the factorisation (counts into assemble_ms)
         HIPCHK(hipEventRecord(c->ev_phase[1], c->sm));
         RC(potrf_full<T>(c, A, ld, np, mtot, c->info_dev, n, c->scal_dev));
@@ -1179,50 +1197,20 @@ static int32_t fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const
             out.sqmahal[s] = scal_h[8 + s];
             out.logpdf[s] = -0.5 * ((double)n * LOG2PI + logdet + scal_h[8 + s]);
         }
-        // timings
-        float ms;
-        HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[0], c->ev_phase[1]));
-        c->tm.assemble_ms = ms;
-        HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[1], c->ev_phase[2]));
-        c->tm.potrf_ms = ms;
-        HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[2], c->ev_phase[3]));
-        c->tm.solve_ms = ms;
-        HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[0], c->ev_phase[3]));
-        c->tm.total_ms = ms;
-        c->tm.gemm_ms = 0;
-        c->tm.gemm_flops = 0;
-        c->tm.gemm_bytes = 0;
-        c->tm.gemm_launches = (int64_t)c->gemm_recs.size();
-        for (auto& r : c->gemm_recs) {
-            HIPCHK(hipEventElapsedTime(&ms, r.a, r.b));
-            c->tm.gemm_ms += ms;
-            c->tm.gemm_flops += r.flops;
-            c->tm.gemm_bytes += r.bytes;
-            if (getenv("GPMI_DUMP_GEMM"))
-                fprintf(stderr, "GEMM s%d M=%ld N=%ld K=%ld ms=%.4f tflops=%.2f\n", r.stream, r.M, r.N, r.K, ms, r.flops / ms / 1e9);
-        }
-        return 0;
-    }();
-    if (rc != 0) {
-        (void)hipStreamSynchronize(c->sm);
-        (void)hipStreamSynchronize(c->sp);
-        return rc;
-    }
+        return fit_timings(c);
+    });
+    if (rc != 0) return rc;
     if (out.info != 0 || !post) return out.info;
     bufs.keep(A_v);
     bufs.keep(xs_v);
     bufs.keep(alpha_v);
     post->dtype = k->dtype;
     post->n = n; post->np = np; post->ld = ld; post->mtot = mtot; post->d = d;
-    post->kind = k->kind; post->variance = k->variance; post->nscale = k->nscale;
-    post->scale.clear();
-    if (k->scale && k->nscale > 0) post->scale.assign(k->scale, k->scale + k->nscale);
+    post->kern = KernelRec(k, ks);
     post->A = A_v; post->A_bytes = A_bytes;
     post->xs = xs_v; post->xs_bytes = xs_bytes;
     post->alpha = alpha_v; post->alpha_bytes = nz_bytes;
     post->logdet_half = logdet_half_out;
-    post->composite = ks != nullptr;
-    if (ks) post->ks = *ks;
     return 0;
 }
 
@@ -1234,9 +1222,7 @@ static int32_t predict_impl(gp_post* post, const gp_points* xs, const void* pm, 
     const long n = post->n, np = post->np, ld = post->ld;
     const long ns = xs->n, nsp = round_up(ns, 128);
     const int d = post->d;
-    gp_kernel k{};
-    k.kind = post->kind; k.dtype = post->dtype; k.variance = post->variance; k.nscale = post->nscale;
-    k.scale = post->scale.empty() ? nullptr : post->scale.data();
+    const gp_kernel k = post->kern.view(post->dtype);
     std::vector<T> xs_h;
     scale_points<T>(&k, xs, nsp, xs_h);
     void* xs_v = nullptr;
@@ -1249,11 +1235,11 @@ static int32_t predict_impl(gp_post* post, const gp_points* xs, const void* pm, 
     const T* A = (const T*)post->A;
     c->ev_used = 0;
     c->gemm_recs.clear();
-    int32_t rc = [&]() -> int32_t {
+    return run_drained(c, [&]() -> int32_t {
         HIPCHK(hipMemcpyAsync(xs_v, xs_h.data(), xs_bytes, hipMemcpyHostToDevice, c->sm));
         if (what & 1) {
             RC(bufs.get(m_bytes, &m_v));
-            kvec<T>(kdesc(post), ns, c->sm, (const T*)xs_v, nsp, (const T*)post->xs, np, d, n, (const T*)post->alpha, (T*)m_v);
+            kvec<T>(post->kern.desc(), ns, c->sm, (const T*)xs_v, nsp, (const T*)post->xs, np, d, n, (const T*)post->alpha, (T*)m_v);
             HIPCHK(hipGetLastError());
             std::vector<T> m_h(ns);
             HIPCHK(hipMemcpyAsync(m_h.data(), m_v, sizeof(T) * ns, hipMemcpyDeviceToHost, c->sm));
@@ -1277,7 +1263,7 @@ static int32_t predict_impl(gp_post* post, const gp_points* xs, const void* pm, 
                 const long rows = std::min(chunk, nsp - r0);
                 GridMap g = plain_map(0, r0, 0);
                 dim3 grid((unsigned)(np / 128), (unsigned)(rows / 128));
-                gram<T>(kdesc(post), grid, c->sm, X, ldx, (const T*)xs_v, nsp, (const T*)post->xs, np, d, (const T*)nullptr, ns, n, 0, g);
+                gram<T>(post->kern.desc(), grid, c->sm, X, ldx, (const T*)xs_v, nsp, (const T*)post->xs, np, d, (const T*)nullptr, ns, n, 0, g);
                 HIPCHK(hipGetLastError());
                 RC(trsm_post<T>(post, c->sm, X, ldx, rows, bufs));
                 if (what & 2) {
@@ -1288,7 +1274,7 @@ static int32_t predict_impl(gp_post* post, const gp_points* xs, const void* pm, 
                                           c->sm));
                     HIPCHK(hipStreamSynchronize(c->sm));
                     for (long i = 0; i < rows && r0 + i < ns; ++i)
-                        vo[r0 + i] = (T)((double)post->variance - ss[i]);  // k(x, x) = σ² (composite: Σ_t σ_t², every κ_f(x, x) = 1)
+                        vo[r0 + i] = (T)(post->kern.variance - ss[i]);  // k(x, x) = σ² (composite: Σ_t σ_t², every κ_f(x, x) = 1)
                 }
             }
             if (want_cov) {
@@ -1298,7 +1284,7 @@ static int32_t predict_impl(gp_post* post, const gp_points* xs, const void* pm, 
                 T* Cm = (T*)C_v;
                 GridMap g = plain_map(0, 0, 0);
                 dim3 grid((unsigned)(nsp / 128), (unsigned)(nsp / 128));
-                gram<T>(kdesc(post), grid, c->sm, Cm, ldc, (const T*)xs_v, nsp, (const T*)xs_v, nsp, d, (const T*)nullptr, ns, ns, 0, g);
+                gram<T>(post->kern.desc(), grid, c->sm, Cm, ldc, (const T*)xs_v, nsp, (const T*)xs_v, nsp, d, (const T*)nullptr, ns, ns, 0, g);
                 HIPCHK(hipGetLastError());
                 RC(launch_gemm<T>(c, c->sm, Cm, ldc, X, ldx, X, ldx, nsp, nsp, np, plain_map(0, 0, 0)));
                 // symmetric: row-major == column-major
@@ -1308,9 +1294,7 @@ static int32_t predict_impl(gp_post* post, const gp_points* xs, const void* pm, 
             }
         }
         return 0;
-    }();
-    if (rc != 0) (void)hipStreamSynchronize(c->sm);
-    return rc;
+    });
 }
 
 // logpdf value + gradient (see include/gpmi355.h gp_logpdf_grad; ks != NULL: gp_logpdf_grad_sum, ∂/∂θ into dtheta, no dx)
@@ -1344,7 +1328,7 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
     std::vector<T> dn_h((size_t)n);
     std::vector<double> sc_h((size_t)nsc, 1.0);
     for (int p = 0; p < k->nscale; ++p) sc_h[p] = k->scale[p];
-    int32_t rc = [&]() -> int32_t {
+    const int32_t rc = run_drained(c, [&]() -> int32_t {
         RC(bufs.get(M_b, &W_v));
         RC(bufs.get(M_b, &Ci_v));
         RC(bufs.get(g_b, &g_v));
@@ -1388,8 +1372,8 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
         dim3 grid((unsigned)(np / 128), (unsigned)(np / 128));
         // one launch per chunk of 16 ARD scales (a single launch for scalar / no transform, whatever D is)
 #define GPMI_KGRAD_FAST(ND_)                                                                                                                  \
-    hipLaunchKernelGGL((kgrad_fast_kernel<T, ND_>), grid, dim3(256), 0, s, (const T*)Ci, ld, (const T*)post.xs, np, d, post.kind, (T)post.variance, \
-                       post.nscale, (const double*)sc_v, (const T*)post.alpha, n, (double*)g_v)
+    hipLaunchKernelGGL((kgrad_fast_kernel<T, ND_>), grid, dim3(256), 0, s, (const T*)Ci, ld, (const T*)post.xs, np, d, post.kern.kind, (T)post.kern.variance, \
+                       post.kern.nscale(), (const double*)sc_v, (const T*)post.alpha, n, (double*)g_v)
         if (ks) {  // composite kernel: one launch per chunk of 16 θ entries
             for (int p0 = 0; p0 < ks->nth; p0 += 16) {
                 launch_kgrad_sum<T>(grid, s, (const T*)Ci, ld, (const T*)post.xs, np, d, *ks, (const T*)post.alpha, n, (double*)g_v, p0);
@@ -1401,9 +1385,9 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
             else GPMI_KGRAD_FAST(16);
             HIPCHK(hipGetLastError());
         } else {
-            for (int p0 = 0; p0 < (post.nscale > 1 ? post.nscale : 1); p0 += 16) {
-                hipLaunchKernelGGL(kgrad_kernel<T>, grid, dim3(256), 0, s, (const T*)Ci, ld, (const T*)post.xs, np, d, post.kind,
-                                   (T)post.variance, post.nscale, (const double*)sc_v, (const T*)post.alpha, n, (double*)g_v, p0);
+            for (int p0 = 0; p0 < (post.kern.nscale() > 1 ? post.kern.nscale() : 1); p0 += 16) {
+                hipLaunchKernelGGL(kgrad_kernel<T>, grid, dim3(256), 0, s, (const T*)Ci, ld, (const T*)post.xs, np, d, post.kern.kind,
+                                   (T)post.kern.variance, post.kern.nscale(), (const double*)sc_v, (const T*)post.alpha, n, (double*)g_v, p0);
                 HIPCHK(hipGetLastError());
             }
         }
@@ -1415,8 +1399,8 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
         if (dx) {  // ∂/∂x: full-square pass (the mirrored C⁻¹ entry serves the tiles above the diagonal), 16 dimensions per launch
             HIPCHK(hipMemsetAsync(gx_v, 0, gx_b, s));
             for (int p0 = 0; p0 < d; p0 += 16) {
-                hipLaunchKernelGGL(kgradx_kernel<T>, grid, dim3(256), 0, s, (const T*)Ci, ld, (const T*)post.xs, np, d, post.kind,
-                                   (T)post.variance, post.nscale, (const double*)sc_v, (const T*)post.alpha, n, (double*)gx_v, np, p0);
+                hipLaunchKernelGGL(kgradx_kernel<T>, grid, dim3(256), 0, s, (const T*)Ci, ld, (const T*)post.xs, np, d, post.kern.kind,
+                                   (T)post.kern.variance, post.kern.nscale(), (const double*)sc_v, (const T*)post.alpha, n, (double*)gx_v, np, p0);
                 HIPCHK(hipGetLastError());
             }
             HIPCHK(hipMemcpyAsync(gx_h.data(), gx_v, gx_b, hipMemcpyDeviceToHost, s));
@@ -1425,11 +1409,7 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
         HIPCHK(hipMemcpyAsync(dn_h.data(), dn_v, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return 0;
-    }();
-    if (rc != 0) {
-        (void)hipStreamSynchronize(c->sm);
-        (void)hipStreamSynchronize(c->sp);
-    }
+    });
     if (rc != 0) return rc;
     *(T*)logpdf_out = (T)fo.logpdf[0];
     if (dvar) *dvar = g_h[0];
@@ -1466,9 +1446,7 @@ static int32_t update_impl(gp_post* old, const gp_points* x2, const gp_noise* no
     const long n2 = x2->n, n2p = round_up(n2, 128);
     const long n = n1 + n2, np = round_up(n, 128), ld = np + c->ldpad, mtot = np + 128;
     const int d = old->d;
-    gp_kernel k{};
-    k.kind = old->kind; k.dtype = old->dtype; k.variance = old->variance; k.nscale = old->nscale;
-    k.scale = old->scale.empty() ? nullptr : old->scale.data();
+    const gp_kernel k = old->kern.view(old->dtype);
     SkScope sk(c);
     hipStream_t s = c->sm;
     c->ev_used = 0;
@@ -1502,7 +1480,7 @@ static int32_t update_impl(gp_post* old, const gp_points* x2, const gp_noise* no
     const T* A1 = (const T*)old->A;
     int info_h = 0;
     double scal_h[16] = {0};
-    int32_t rc = [&]() -> int32_t {
+    int32_t rc = run_drained(c, [&]() -> int32_t {
         HIPCHK(hipMemcpyAsync(x2_v, x2s_h.data(), x2_b, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(nz_v, noise_h.data(), nz_b, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemsetAsync(c->info_dev, 0, sizeof(int), s));
@@ -1515,7 +1493,7 @@ static int32_t update_impl(gp_post* old, const gp_points* x2, const gp_noise* no
         {
             GridMap g = plain_map(0, 0, 0);
             dim3 grid((unsigned)(np1 / 128), (unsigned)(n2p / 128));
-            gram<T>(kdesc(old), grid, s, X, ldx, (const T*)x2_v, n2p, (const T*)old->xs, np1, d, (const T*)nullptr, n2, n1, 0, g);
+            gram<T>(old->kern.desc(), grid, s, X, ldx, (const T*)x2_v, n2p, (const T*)old->xs, np1, d, (const T*)nullptr, n2, n1, 0, g);
             HIPCHK(hipGetLastError());
         }
         RC(trsm_post<T>(old, s, X, ldx, n2p, bufs));
@@ -1523,7 +1501,7 @@ static int32_t update_impl(gp_post* old, const gp_points* x2, const gp_noise* no
         {
             GridMap g = plain_map(1, 0, 0);
             dim3 grid((unsigned)(n2p / 128), (unsigned)(n2p / 128));
-            gram<T>(kdesc(old), grid, s, S, lds, (const T*)x2_v, n2p, (const T*)x2_v, n2p, d, (const T*)nz_v, n2, n2, 1, g);
+            gram<T>(old->kern.desc(), grid, s, S, lds, (const T*)x2_v, n2p, (const T*)x2_v, n2p, d, (const T*)nz_v, n2, n2, 1, g);
             HIPCHK(hipGetLastError());
         }
         RC(launch_gemm<T>(c, s, S, lds, X, ldx, X, ldx, n2p, n2p, np1, plain_map(1, 0, 0)));
@@ -1549,11 +1527,7 @@ static int32_t update_impl(gp_post* old, const gp_points* x2, const gp_noise* no
         if (alpha_out) HIPCHK(hipMemcpyAsync(alpha_out, alpha_v, sizeof(T) * n, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return 0;
-    }();
-    if (rc != 0) {
-        (void)hipStreamSynchronize(c->sm);
-        (void)hipStreamSynchronize(c->sp);
-    }
+    });
     if (rc == 0 && info_h != 0) rc = (int32_t)n1 + info_h;  // order of the failing leading minor of the bordered matrix
     if (rc != 0) return rc;
     bufs.keep(A_v);
@@ -1562,10 +1536,7 @@ static int32_t update_impl(gp_post* old, const gp_points* x2, const gp_noise* no
     post->ctx = c;
     post->dtype = old->dtype;
     post->n = n; post->np = np; post->ld = ld; post->mtot = mtot; post->d = d;
-    post->kind = old->kind; post->variance = old->variance; post->nscale = old->nscale;
-    post->scale = old->scale;
-    post->composite = old->composite;
-    post->ks = old->ks;
+    post->kern = old->kern;
     post->A = A_v; post->A_bytes = A_b;
     post->xs = xs_v; post->xs_bytes = xs_b;
     post->alpha = alpha_v; post->alpha_bytes = v_b;
@@ -1583,7 +1554,7 @@ template <typename T> static int32_t factor_mul_impl(gp_post* post, const void* 
     RC(bufs.get(b, &in_v));
     RC(bufs.get(b, &out_v));
     hipStream_t s = c->sm;
-    int32_t rc = [&]() -> int32_t {
+    return run_drained(c, [&]() -> int32_t {
         HIPCHK(hipMemsetAsync(in_v, 0, b, s));
         HIPCHK(hipMemcpy2DAsync(in_v, sizeof(T) * np, xi, sizeof(T) * n, sizeof(T) * n, ncols, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(trmv_lower_kernel<T>, dim3((unsigned)n), dim3(256), 0, s, (const T*)post->A, post->ld, (const T*)in_v, np,
@@ -1592,9 +1563,7 @@ template <typename T> static int32_t factor_mul_impl(gp_post* post, const void* 
         HIPCHK(hipMemcpy2DAsync(out, sizeof(T) * n, out_v, sizeof(T) * np, sizeof(T) * n, ncols, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return 0;
-    }();
-    if (rc != 0) (void)hipStreamSynchronize(s);
-    return rc;
+    });
 }
 
 // out[:, s] = C \ B[:, s] with the resident factor (forward + backward vector sweeps, all columns per sweep)
@@ -1606,7 +1575,7 @@ template <typename T> static int32_t solve_impl(gp_post* post, const void* B, in
     DevBufs bufs(c);
     RC(bufs.get(b, &r_v));
     hipStream_t s = c->sm;
-    int32_t rc = [&]() -> int32_t {
+    return run_drained(c, [&]() -> int32_t {
         HIPCHK(hipMemsetAsync(r_v, 0, b, s));
         HIPCHK(hipMemcpy2DAsync(r_v, sizeof(T) * np, B, sizeof(T) * n, sizeof(T) * n, ncols, hipMemcpyHostToDevice, s));
         RC(trsv<T>(c, s, (const T*)post->A, post->ld, np, (T*)r_v, np, ncols, true));
@@ -1614,9 +1583,7 @@ template <typename T> static int32_t solve_impl(gp_post* post, const void* B, in
         HIPCHK(hipMemcpy2DAsync(out, sizeof(T) * n, r_v, sizeof(T) * np, sizeof(T) * n, ncols, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return 0;
-    }();
-    if (rc != 0) (void)hipStreamSynchronize(s);
-    return rc;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1646,9 +1613,7 @@ static int32_t post_joint(gp_post* post, const gp_points* xs, const void* pm, co
     const long n = post->n, np = post->np, ld = post->ld;
     const long ns = xs->n, nsp = round_up(ns, 128);
     const int d = post->d;
-    gp_kernel k{};
-    k.kind = post->kind; k.dtype = post->dtype; k.variance = post->variance; k.nscale = post->nscale;
-    k.scale = post->scale.empty() ? nullptr : post->scale.data();
+    const gp_kernel k = post->kern.view(post->dtype);
     std::vector<T> xs_h, nz_h;
     scale_points<T>(&k, xs, nsp, xs_h);
     noise_to<T, T>(noise, ns, nsp, nz_h);
@@ -1668,20 +1633,20 @@ static int32_t post_joint(gp_post* post, const gp_points* xs, const void* pm, co
     std::vector<T> m_h((size_t)ns);
     HIPCHK(hipMemcpyAsync(xs_v, xs_h.data(), sizeof(T) * (size_t)d * nsp, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(nz_v, nz_h.data(), sizeof(T) * (size_t)nsp, hipMemcpyHostToDevice, s));
-    kvec<T>(kdesc(post), ns, s, (const T*)xs_v, nsp, (const T*)post->xs, np, d, n, (const T*)post->alpha, (T*)m_v);  // K_*x α
+    kvec<T>(post->kern.desc(), ns, s, (const T*)xs_v, nsp, (const T*)post->xs, np, d, n, (const T*)post->alpha, (T*)m_v);  // K_*x α
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(m_h.data(), m_v, sizeof(T) * (size_t)ns, hipMemcpyDeviceToHost, s));
     {
         GridMap g = plain_map(0, 0, 0);
         dim3 grid((unsigned)(np / 128), (unsigned)(nsp / 128));
-        gram<T>(kdesc(post), grid, s, X, ldx, (const T*)xs_v, nsp, (const T*)post->xs, np, d, (const T*)nullptr, ns, n, 0, g);
+        gram<T>(post->kern.desc(), grid, s, X, ldx, (const T*)xs_v, nsp, (const T*)post->xs, np, d, (const T*)nullptr, ns, n, 0, g);
         HIPCHK(hipGetLastError());
     }
     RC(trsm_post<T>(post, s, X, ldx, nsp, bufs));                                                              // V ᵀ = K_*x L⁻ᵀ
     {
         GridMap g = plain_map(1, 0, 0);
         dim3 grid((unsigned)(nsp / 128), (unsigned)(nsp / 128));
-        gram<T>(kdesc(post), grid, s, Cm, ldc, (const T*)xs_v, nsp, (const T*)xs_v, nsp, d, (const T*)nz_v, ns, ns, 1, g);
+        gram<T>(post->kern.desc(), grid, s, Cm, ldc, (const T*)xs_v, nsp, (const T*)xs_v, nsp, d, (const T*)nz_v, ns, ns, 1, g);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemsetAsync(Cm + nsp * ldc, 0, sizeof(T) * (size_t)(R + 128) * ldc, s));
@@ -1701,9 +1666,7 @@ static int32_t post_joint_dist(gp_post* post, const gp_points* xs, const void* p
     gp_ctx* c = post->ctx;
     const long ns = xs->n, nsp = round_up(ns, 128);
     const int d = post->d;
-    gp_kernel k{};
-    k.kind = post->kind; k.dtype = 0; k.variance = post->variance; k.nscale = post->nscale;
-    k.scale = post->scale.empty() ? nullptr : post->scale.data();
+    const gp_kernel k = post->kern.view(0);
     std::vector<double> m_h((size_t)ns), xs_n, xs_p, nz_h;
     RC(predict_impl<double>(post, xs, pm, 1, m_h.data(), nullptr, nullptr));   // m(x*) + K_*x α (no factor involved)
     scale_points<double>(&k, xs, ns, xs_n);
@@ -1730,8 +1693,8 @@ static int32_t post_joint_dist(gp_post* post, const gp_points* xs, const void* p
     {
         GridMap g = plain_map(1, 0, 0);
         dim3 grid((unsigned)(nsp / 128), (unsigned)(nsp / 128));
-        launch_kmat<double>(grid, s, Cm, ldc, (const double*)xs_v, nsp, (const double*)xs_v, nsp, d, post->kind,
-                           post->variance, (const double*)nz_v, ns, ns, 1, g, (const double*)nullptr, (const double*)nullptr);
+        launch_kmat<double>(grid, s, Cm, ldc, (const double*)xs_v, nsp, (const double*)xs_v, nsp, d, post->kern.kind,
+                           post->kern.variance, (const double*)nz_v, ns, ns, 1, g, (const double*)nullptr, (const double*)nullptr);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemsetAsync(Cm + nsp * ldc, 0, sizeof(double) * (size_t)(R + 128) * ldc, s));
@@ -1756,7 +1719,7 @@ static int32_t joint_logpdf(gp_ctx* c, Joint<TC>& J, const void* Yv, long ldy, i
         for (long i = 0; i < ns; ++i) rhs[(size_t)q * nsp + i] = (TC)((double)Y[(size_t)q * ldy + i] - J.mean[i]);
     int info_h = 0;
     std::vector<double> scal_h(8 + ncols);
-    int32_t rc = [&]() -> int32_t {
+    const int32_t rc = run_drained(c, [&]() -> int32_t {
         HIPCHK(hipMemsetAsync(c->info_dev, 0, sizeof(int), s));
         HIPCHK(hipMemsetAsync(c->scal_dev, 0, sizeof(double) * (8 + J.R), s));
         HIPCHK(hipMemcpy2DAsync(Cm + nsp * ld, sizeof(TC) * ld, rhs.data(), sizeof(TC) * nsp, sizeof(TC) * nsp, ncols,
@@ -1768,12 +1731,8 @@ static int32_t joint_logpdf(gp_ctx* c, Joint<TC>& J, const void* Yv, long ldy, i
         HIPCHK(hipMemcpyAsync(scal_h.data(), c->scal_dev, sizeof(double) * (8 + ncols), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return 0;
-    }();
-    if (rc != 0) {
-        (void)hipStreamSynchronize(c->sm);
-        (void)hipStreamSynchronize(c->sp);
-        return rc;
-    }
+    });
+    if (rc != 0) return rc;
     if (info_h != 0) return info_h;
     for (int q = 0; q < ncols; ++q)
         ((TIO*)outv)[q] = (TIO)(-0.5 * ((double)ns * LOG2PI + 2.0 * scal_h[0] + scal_h[8 + q]));
@@ -1797,7 +1756,7 @@ static int32_t joint_rand(gp_ctx* c, Joint<TC>& J, DevBufs& bufs, const void* xi
     RC(bufs.get(b, &in_v));
     RC(bufs.get(b, &out_v));
     int info_h = 0;
-    int32_t rc = [&]() -> int32_t {
+    const int32_t rc = run_drained(c, [&]() -> int32_t {
         HIPCHK(hipMemsetAsync(c->info_dev, 0, sizeof(int), s));
         HIPCHK(hipMemsetAsync(c->scal_dev, 0, sizeof(double) * 16, s));
         HIPCHK(hipMemcpyAsync(in_v, in_h.data(), b, hipMemcpyHostToDevice, s));
@@ -1809,12 +1768,8 @@ static int32_t joint_rand(gp_ctx* c, Joint<TC>& J, DevBufs& bufs, const void* xi
         HIPCHK(hipMemcpyAsync(out_h.data(), out_v, b, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return 0;
-    }();
-    if (rc != 0) {
-        (void)hipStreamSynchronize(c->sm);
-        (void)hipStreamSynchronize(c->sp);
-        return rc;
-    }
+    });
+    if (rc != 0) return rc;
     if (info_h != 0) return info_h;
     for (int q = 0; q < ncols; ++q)
         for (long i = 0; i < ns; ++i) ((TIO*)outv)[(size_t)q * ns + i] = (TIO)(J.mean[i] + (double)out_h[(size_t)q * nsp + i]);
@@ -1899,9 +1854,9 @@ int32_t gp_ctx_destroy(gp_ctx* c) {
 }
 
 int32_t gp_ctx_set_param(gp_ctx* c, const char* name, int64_t v) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     if (!name) return set_arg_err(2, "name is NULL");
-    std::lock_guard<std::mutex> l(c->mu);
     if (c->multi && multi_set_param(c, name, v) == 0) return 0;  // (generic names are forwarded to the rank contexts too)
     if (!strcmp(name, "nb")) c->nb = v < 0 ? -1 : (v == 0 ? 0 : round_up(v, 128));
     else if (!strcmp(name, "nb_small")) c->nb_small = (v <= 0) ? 0 : round_up(v, 128);
@@ -1950,10 +1905,10 @@ int32_t gp_ctx_set_param(gp_ctx* c, const char* name, int64_t v) {
 }
 
 int32_t gp_ctx_get_param(gp_ctx* c, const char* name, int64_t* out) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     if (!name) return set_arg_err(2, "name is NULL");
     if (!out) return set_arg_err(3, "out is NULL");
-    std::lock_guard<std::mutex> l(c->mu);
     if (c->multi && multi_get_param(c, name, out) == 0) return 0;
     const struct { const char* n; int64_t v; } tab[] = {
         {"nb", c->nb}, {"nb_small", c->nb_small}, {"nb_large", c->nb_large}, {"lookahead", c->lookahead}, {"lookahead_min_n", c->lookahead_min_n}, {"time_kernels", c->time_kernels},
@@ -1985,61 +1940,11 @@ int32_t gp_ctx_trim(gp_ctx* c) {
 }
 
 int32_t gp_get_timings(gp_ctx* c, gp_timings* out) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     if (!out) return set_arg_err(2, "out is NULL");
-    std::lock_guard<std::mutex> l(c->mu);
     *out = c->tm;
     return 0;
-}
-
-// gp_kernelmatrix / gp_kernelmatrix_sum after their argument checks (k: the input scaling and dtype; ks: composite kernel or NULL)
-static int32_t kernelmatrix_impl(gp_ctx* c, const gp_kernel* k, const KSum* ks, const gp_points* x, const gp_points* y, void* out) {
-    std::lock_guard<std::mutex> l(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    auto run = [&](auto tag) -> int32_t {
-        using T = decltype(tag);
-        // device rows = y points (or x), device cols = x points: row-major (m×n) == column-major (n×m)
-        const gp_points* rp = y ? y : x;
-        const long n = x->n, m = rp->n, np = round_up(n, 128), mp = round_up(m, 128);
-        const long ld = np + c->ldpad;
-        std::vector<T> xc_h, xr_h;
-        scale_points<T>(k, x, np, xc_h);
-        if (y) scale_points<T>(k, y, mp, xr_h);
-        void *xc_v = nullptr, *xr_v = nullptr, *K_v = nullptr;
-        const size_t xcb = sizeof(T) * xc_h.size(), xrb = sizeof(T) * xr_h.size(), Kb = sizeof(T) * (size_t)mp * ld;
-        DevBufs bufs(c);
-        RC(bufs.get(xcb, &xc_v));
-        if (y) RC(bufs.get(xrb, &xr_v));
-        RC(bufs.get(Kb, &K_v));
-        int32_t rc = [&]() -> int32_t {
-            HIPCHK(hipMemcpyAsync(xc_v, xc_h.data(), xcb, hipMemcpyHostToDevice, c->sm));
-            if (y) HIPCHK(hipMemcpyAsync(xr_v, xr_h.data(), xrb, hipMemcpyHostToDevice, c->sm));
-            GridMap g = plain_map(0, 0, 0);
-            dim3 grid((unsigned)(np / 128), (unsigned)(mp / 128));
-            gram<T>(kdesc(k, ks), grid, c->sm, (T*)K_v, ld, (const T*)(y ? xr_v : xc_v), y ? mp : np, (const T*)xc_v, np, x->d,
-                    (const T*)nullptr, m, n, 0, g);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpy2DAsync(out, sizeof(T) * n, K_v, sizeof(T) * ld, sizeof(T) * n, m, hipMemcpyDeviceToHost,
-                                    c->sm));
-            HIPCHK(hipStreamSynchronize(c->sm));
-            return 0;
-        }();
-        if (rc != 0) (void)hipStreamSynchronize(c->sm);
-        return rc;
-    };
-    return k->dtype == 0 ? run(double()) : run(float());
-}
-
-int32_t gp_kernelmatrix(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_points* y, void* out) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
-    RC(check_points(x, 3));
-    RC(check_kernel(k, x->d, 2));
-    if (y) {
-        RC(check_points(y, 4));
-        if (y->d != x->d) return set_arg_err(4, "x and y have different D");
-    }
-    if (!out) return set_arg_err(5, "out is NULL");
-    return kernelmatrix_impl(c, k, nullptr, x, y, out);
 }
 
 // Validates a gp_ksum (limits and malformed descriptors: −argi with the reason) and packs it for the device.  kid: the single-kind descriptor
@@ -2098,20 +2003,6 @@ extern "C++" int32_t pack_ksum(const gp_ksum* k, int d, int argi, KSum& ks, gp_k
     return 0;
 }
 
-int32_t gp_kernelmatrix_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_points* y, void* out) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
-    RC(check_points(x, 3));
-    KSum ks;
-    gp_kernel kid;
-    RC(pack_ksum(k, x->d, 2, ks, kid));
-    if (y) {
-        RC(check_points(y, 4));
-        if (y->d != x->d) return set_arg_err(4, "x and y have different D");
-    }
-    if (!out) return set_arg_err(5, "out is NULL");
-    return kernelmatrix_impl(c, &kid, &ks, x, y, out);
-}
-
 // noise kinds (include/gpmi355.h): 0 σ²·I, 1 Diagonal, 2 / 3 dense (upper / lower triangle of a column-major n×n host array).  dense_ok = false: the sparse
 // fits, where the reference needs cholesky(Σy) — an N×N factorisation that defeats the sparse cost (src/sparse_approximations.jl:61, :97) — and whose elbo
 // has no trace term for a dense Σy at all (:307-313).
@@ -2124,19 +2015,32 @@ extern "C++" int32_t check_noise(const gp_noise* noise, int argi, bool dense_ok)
     if (noise->kind != 0 && !noise->diag) return set_arg_err(argi, noise->kind == 1 ? "noise diag is NULL" : "noise diag (the dense matrix) is NULL");
     return 0;
 }
-static int32_t check_fit_args(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, bool dense_ok = true) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
-    RC(check_points(x, 3));
-    RC(check_kernel(k, x->d, 2));
-    return check_noise(noise, 4, dense_ok);
+
+// The kernel of one call as the engine carries it.  Single kind: the caller's gp_kernel.  Composite (the *_sum calls): the packed terms `ks` beside the
+// kind-0 descriptor without a transform (the inputs stay raw) whose variance is Σ_t σ_t² — what pack_ksum returns.
+struct ResolvedKernel {
+    gp_kernel k{};
+    KSum ks;  // filled when composite
+    bool composite = false;
+    const KSum* sum() const { return composite ? &ks : nullptr; }
+};
+static int32_t resolve_kernel(const gp_kernel* k, int d, int argi, ResolvedKernel& rk) {
+    RC(check_kernel(k, d, argi));
+    rk.k = *k;
+    return 0;
+}
+static int32_t resolve_kernel(const gp_ksum* k, int d, int argi, ResolvedKernel& rk) {
+    rk.composite = true;
+    return pack_ksum(k, d, argi, rk.ks, rk.k);
 }
 
-// One (logpdf, posterior) pair on whatever the ctx drives: the 2D block-cyclic driver (multi.hip) for fp64 fits with at most
-// 128 right-hand sides on a multi-device ctx, the single-device engine (devices[0] of a multi-device ctx) for everything else — fits with a dense Σy
-// (noise kind 2 / 3) among them: the block-cyclic driver takes a scalar or a vector noise only.
-static int32_t fit_any(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y,
+// One (logpdf, posterior) pair on whatever the ctx drives: the 2D block-cyclic driver (multi.hip) for fp64 single-kind fits with at most
+// 128 right-hand sides on a multi-device ctx, the single-device engine (devices[0] of a multi-device ctx) for everything else — composite kernels and fits
+// with a dense Σy (noise kind 2 / 3) among them: the block-cyclic driver is single-kind and takes a scalar or a vector noise only.
+static int32_t fit_any(gp_ctx* c, const ResolvedKernel& rk, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y,
                        long ldy, int ncols, FitOut& fo, gp_post* p, void* alpha_out) {
-    if (c->multi && k->dtype == 0 && ncols <= 128 && !noise_dense(noise)) {
+    const gp_kernel* k = &rk.k;
+    if (c->multi && !rk.composite && k->dtype == 0 && ncols <= 128 && !noise_dense(noise)) {
         fo.logpdf.assign((size_t)ncols, 0.0);
         std::vector<double> terms((size_t)ncols + 1, 0.0);
         RC(multi_fit(c, k, x, noise, mean, Y, ldy, ncols, fo.logpdf.data(), terms.data(), p, alpha_out));
@@ -2144,27 +2048,144 @@ static int32_t fit_any(gp_ctx* c, const gp_kernel* k, const gp_points* x, const 
         fo.sqmahal.assign(terms.begin() + 1, terms.end());
         return 0;
     }
-    return k->dtype == 0 ? fit_impl<double>(c, k, x, noise, mean, Y, ldy, ncols, fo, p, alpha_out)
-                         : fit_impl<float>(c, k, x, noise, mean, Y, ldy, ncols, fo, p, alpha_out);
+    return by_dtype(k->dtype, [&](auto t) { return fit_impl<decltype(t)>(c, k, x, noise, mean, Y, ldy, ncols, fo, p, alpha_out, rk.sum()); });
 }
 
-int32_t gp_logpdf(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean,
-                  const void* Y, int64_t ldy, int32_t ncols, void* out) {
-    RC(check_fit_args(c, k, x, noise));
+// ---- the bodies gp_X and gp_X_sum share (K: gp_kernel or gp_ksum; everything after the kernel argument's check is one path) ----
+extern "C++" {
+template <class K>
+static int32_t check_fit_args(const K* k, const gp_points* x, const gp_noise* noise, ResolvedKernel& rk, bool dense_ok = true) {
+    RC(check_points(x, 3));
+    RC(resolve_kernel(k, x->d, 2, rk));
+    return check_noise(noise, 4, dense_ok);
+}
+
+template <class K> static int32_t kernelmatrix_any(gp_ctx* c, const K* k, const gp_points* x, const gp_points* y, void* out) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    RC(check_points(x, 3));
+    ResolvedKernel rk;
+    RC(resolve_kernel(k, x->d, 2, rk));
+    if (y) {
+        RC(check_points(y, 4));
+        if (y->d != x->d) return set_arg_err(4, "x and y have different D");
+    }
+    if (!out) return set_arg_err(5, "out is NULL");
+    HIPCHK(hipSetDevice(c->device));
+    return by_dtype(rk.k.dtype, [&](auto tag) -> int32_t {
+        using T = decltype(tag);
+        // device rows = y points (or x), device cols = x points: row-major (m×n) == column-major (n×m)
+        const gp_points* rp = y ? y : x;
+        const long n = x->n, m = rp->n, np = round_up(n, 128), mp = round_up(m, 128);
+        const long ld = np + c->ldpad;
+        std::vector<T> xc_h, xr_h;
+        scale_points<T>(&rk.k, x, np, xc_h);
+        if (y) scale_points<T>(&rk.k, y, mp, xr_h);
+        void *xc_v = nullptr, *xr_v = nullptr, *K_v = nullptr;
+        const size_t xcb = sizeof(T) * xc_h.size(), xrb = sizeof(T) * xr_h.size(), Kb = sizeof(T) * (size_t)mp * ld;
+        DevBufs bufs(c);
+        RC(bufs.get(xcb, &xc_v));
+        if (y) RC(bufs.get(xrb, &xr_v));
+        RC(bufs.get(Kb, &K_v));
+        return run_drained(c, [&]() -> int32_t {
+            HIPCHK(hipMemcpyAsync(xc_v, xc_h.data(), xcb, hipMemcpyHostToDevice, c->sm));
+            if (y) HIPCHK(hipMemcpyAsync(xr_v, xr_h.data(), xrb, hipMemcpyHostToDevice, c->sm));
+            GridMap g = plain_map(0, 0, 0);
+            dim3 grid((unsigned)(np / 128), (unsigned)(mp / 128));
+            gram<T>(KDesc{rk.k.kind, rk.k.variance, rk.sum()}, grid, c->sm, (T*)K_v, ld, (const T*)(y ? xr_v : xc_v), y ? mp : np, (const T*)xc_v, np,
+                    x->d, (const T*)nullptr, m, n, 0, g);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpy2DAsync(out, sizeof(T) * n, K_v, sizeof(T) * ld, sizeof(T) * n, m, hipMemcpyDeviceToHost,
+                                    c->sm));
+            HIPCHK(hipStreamSynchronize(c->sm));
+            return 0;
+        });
+    });
+}
+
+template <class K>
+static int32_t logpdf_any(gp_ctx* c, const K* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y, int64_t ldy,
+                          int32_t ncols, void* out) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    ResolvedKernel rk;
+    RC(check_fit_args(k, x, noise, rk));
     if (!Y) return set_arg_err(6, "Y is NULL");
     if (ncols < 1) return set_arg_err(8, "ncols must be >= 1");
     if (ldy < x->n) return set_arg_err(7, "ldy < n");
     if (!out) return set_arg_err(9, "out is NULL");
-    std::lock_guard<std::mutex> l(c->mu);
     HIPCHK(hipSetDevice(c->device));
     FitOut fo;
-    const int32_t rc = fit_any(c, k, x, noise, mean, Y, ldy, ncols, fo, nullptr, nullptr);
-    if (rc != 0) return rc;
-    for (int s = 0; s < ncols; ++s) {
-        if (k->dtype == 0) ((double*)out)[s] = fo.logpdf[s];
-        else ((float*)out)[s] = (float)fo.logpdf[s];
-    }
+    RC(fit_any(c, rk, x, noise, mean, Y, ldy, ncols, fo, nullptr, nullptr));
+    for (int s = 0; s < ncols; ++s) put(out, rk.k.dtype, s, fo.logpdf[s]);
     return 0;
+}
+
+template <class K>
+static int32_t posterior_fit_any(gp_ctx* c, const K* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, gp_post** out,
+                                 void* alpha_out, void* logpdf_out) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    ResolvedKernel rk;
+    RC(check_fit_args(k, x, noise, rk));
+    if (!y) return set_arg_err(6, "y is NULL");
+    if (!out) return set_arg_err(7, "out is NULL");
+    *out = nullptr;
+    HIPCHK(hipSetDevice(c->device));
+    auto p = std::make_unique<gp_post>();
+    p->ctx = c;
+    FitOut fo;
+    RC(fit_any(c, rk, x, noise, mean, y, x->n, 1, fo, p.get(), alpha_out));
+    if (logpdf_out) put(logpdf_out, rk.k.dtype, 0, fo.logpdf[0]);
+    publish(c, p, out);
+    return 0;
+}
+
+// single kind: dvar / dscale / dx, dtheta NULL; composite: dtheta (one entry per θ entry), the other three NULL
+template <class K>
+static int32_t logpdf_grad_any(gp_ctx* c, const K* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, void* logpdf_out,
+                               double* dvar, double* dscale, void* dnoise, void* dy, void* dx, double* dtheta) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    ResolvedKernel rk;
+    RC(check_fit_args(k, x, noise, rk));
+    if (!y) return set_arg_err(6, "y is NULL");
+    if (!logpdf_out) return set_arg_err(7, "logpdf_out is NULL");
+    HIPCHK(hipSetDevice(c->device));
+    return by_dtype(rk.k.dtype, [&](auto t) {
+        return grad_impl<decltype(t)>(c, &rk.k, x, noise, mean, y, logpdf_out, dvar, dscale, dnoise, dy, dx, rk.sum(), dtheta);
+    });
+}
+}  // extern "C++"
+
+int32_t gp_kernelmatrix(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_points* y, void* out) { return kernelmatrix_any(c, k, x, y, out); }
+int32_t gp_kernelmatrix_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_points* y, void* out) { return kernelmatrix_any(c, k, x, y, out); }
+
+int32_t gp_logpdf(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean,
+                  const void* Y, int64_t ldy, int32_t ncols, void* out) {
+    return logpdf_any(c, k, x, noise, mean, Y, ldy, ncols, out);
+}
+int32_t gp_logpdf_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y, int64_t ldy,
+                      int32_t ncols, void* out) {
+    return logpdf_any(c, k, x, noise, mean, Y, ldy, ncols, out);
+}
+
+int32_t gp_posterior_fit(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean,
+                         const void* y, gp_post** out, void* alpha_out, void* logpdf_out) {
+    return posterior_fit_any(c, k, x, noise, mean, y, out, alpha_out, logpdf_out);
+}
+int32_t gp_posterior_fit_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, gp_post** out,
+                             void* alpha_out, void* logpdf_out) {
+    return posterior_fit_any(c, k, x, noise, mean, y, out, alpha_out, logpdf_out);
+}
+
+int32_t gp_logpdf_grad(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y,
+                       void* logpdf_out, double* dvar, double* dscale, void* dnoise, void* dy, void* dx) {
+    return logpdf_grad_any(c, k, x, noise, mean, y, logpdf_out, dvar, dscale, dnoise, dy, dx, nullptr);
+}
+int32_t gp_logpdf_grad_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y,
+                           void* logpdf_out, double* dtheta, void* dnoise, void* dy) {
+    return logpdf_grad_any(c, k, x, noise, mean, y, logpdf_out, nullptr, nullptr, dnoise, dy, nullptr, dtheta);
 }
 
 // logdet(cov(fx)) and sqmahal(fx, Y) — the two terms logpdf adds up (src/finite_gp_projection.jl:306-311): `logdetcov` is not in
@@ -2172,14 +2193,16 @@ int32_t gp_logpdf(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_no
 // the posterior fit.  Y may be NULL (ncols ignored): logdet only.  Outputs in the kernel's dtype; either may be NULL.
 int32_t gp_logpdf_terms(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean,
                         const void* Y, int64_t ldy, int32_t ncols, void* logdet_out, void* sqmahal_out) {
-    RC(check_fit_args(c, k, x, noise));
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    ResolvedKernel rk;
+    RC(check_fit_args(k, x, noise, rk));
     if (Y) {
         if (ncols < 1) return set_arg_err(8, "ncols must be >= 1");
         if (ldy < x->n) return set_arg_err(7, "ldy < n");
     } else if (sqmahal_out) {
         return set_arg_err(6, "sqmahal needs Y");
     }
-    std::lock_guard<std::mutex> l(c->mu);
     HIPCHK(hipSetDevice(c->device));
     FitOut fo;
     std::vector<char> zero;
@@ -2188,25 +2211,46 @@ int32_t gp_logpdf_terms(gp_ctx* c, const gp_kernel* k, const gp_points* x, const
         // side that rides along ((K + Σy) α = δ on every row) — an all-zero δ would make that check vacuous (α = 0 whatever the
         // factor holds).  A fixed pseudo-random probe in [−½, ½) rides instead; its sqmahal is discarded.
         zero.assign((size_t)x->n * (k->dtype == 0 ? 8 : 4), 0);
-        for (int64_t i = 0; i < x->n; ++i) {
-            const double v = (double)(((uint32_t)i * 2654435761u >> 8) & 0xffffu) / 65536.0 - 0.5 + 1.0 / 131072.0;
-            if (k->dtype == 0) ((double*)zero.data())[i] = v;
-            else ((float*)zero.data())[i] = (float)v;
-        }
+        for (int64_t i = 0; i < x->n; ++i)
+            put(zero.data(), k->dtype, (size_t)i, (double)(((uint32_t)i * 2654435761u >> 8) & 0xffffu) / 65536.0 - 0.5 + 1.0 / 131072.0);
         ncols = 1;
         ldy = x->n;
     }
-    const int32_t rc = fit_any(c, k, x, noise, Y ? mean : nullptr, Y ? Y : (const void*)zero.data(), ldy, ncols, fo, nullptr, nullptr);
-    if (rc != 0) return rc;
-    if (logdet_out) {
-        if (k->dtype == 0) *(double*)logdet_out = fo.logdet;
-        else *(float*)logdet_out = (float)fo.logdet;
-    }
+    RC(fit_any(c, rk, x, noise, Y ? mean : nullptr, Y ? Y : (const void*)zero.data(), ldy, ncols, fo, nullptr, nullptr));
+    if (logdet_out) put(logdet_out, k->dtype, 0, fo.logdet);
     if (sqmahal_out)
-        for (int s = 0; s < ncols; ++s) {
-            if (k->dtype == 0) ((double*)sqmahal_out)[s] = fo.sqmahal[s];
-            else ((float*)sqmahal_out)[s] = (float)fo.sqmahal[s];
-        }
+        for (int s = 0; s < ncols; ++s) put(sqmahal_out, k->dtype, s, fo.sqmahal[s]);
+    return 0;
+}
+
+// ---- argument checks the exact and the sparse posterior share (argi: position of the first argument checked; the others follow it) ----
+static int32_t check_test_points(const gp_points* xs, int d) {
+    RC(check_points(xs, 2));
+    if (xs->d != d) return set_arg_err(2, "xs has a different D than the training inputs");
+    return 0;
+}
+static int32_t check_predict_out(int what, const void* mean_out, const void* var_out, const void* cov_out, int argi) {
+    if (what <= 0 || what > 7) return set_arg_err(argi, "what must be a combination of 1|2|4");
+    if ((what & 1) && !mean_out) return set_arg_err(argi + 1, "mean_out is NULL");
+    if ((what & 2) && !var_out) return set_arg_err(argi + 2, "var_out is NULL");
+    if ((what & 4) && !cov_out) return set_arg_err(argi + 3, "cov_out is NULL");
+    return 0;
+}
+static int32_t check_joint_args(const gp_points* xs, int d, const gp_noise* noise) {
+    RC(check_test_points(xs, d));
+    return check_noise(noise, 4, true);
+}
+static int32_t check_heldout(const void* Y, int64_t ldy, int32_t ncols, const void* out, int64_t n, int argi) {
+    if (!Y) return set_arg_err(argi, "Y is NULL");
+    if (ldy < n) return set_arg_err(argi + 1, "ldy < n");
+    if (ncols < 1) return set_arg_err(argi + 2, "ncols must be >= 1");
+    if (!out) return set_arg_err(argi + 3, "out is NULL");
+    return 0;
+}
+static int32_t check_draws(const void* xi, int32_t ncols, const void* out, int argi) {
+    if (!xi) return set_arg_err(argi, "xi is NULL");
+    if (ncols < 1) return set_arg_err(argi + 1, "ncols must be >= 1");
+    if (!out) return set_arg_err(argi + 2, "out is NULL");
     return 0;
 }
 
@@ -2219,58 +2263,26 @@ int32_t gp_posterior_logdet(gp_post* post, double* out) {
     return 0;
 }
 
-int32_t gp_posterior_fit(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean,
-                         const void* y, gp_post** out, void* alpha_out, void* logpdf_out) {
-    RC(check_fit_args(c, k, x, noise));
-    if (!y) return set_arg_err(6, "y is NULL");
-    if (!out) return set_arg_err(7, "out is NULL");
-    *out = nullptr;
-    std::lock_guard<std::mutex> l(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    gp_post* p = new gp_post();
-    p->ctx = c;
-    FitOut fo;
-    const int32_t rc = fit_any(c, k, x, noise, mean, y, x->n, 1, fo, p, alpha_out);
-    if (rc != 0) {
-        delete p;
-        return rc;
-    }
-    if (logpdf_out) {
-        if (k->dtype == 0) *(double*)logpdf_out = fo.logpdf[0];
-        else *(float*)logpdf_out = (float)fo.logpdf[0];
-    }
-    c->refs++;
-    reg_add(p);
-    *out = p;
-    return 0;
-}
-
 int32_t gp_posterior_predict(gp_post* post, const gp_points* xs, const void* pm, int32_t what, void* mean_out,
                              void* var_out, void* cov_out) {
     Guard gd(post);
     if (!gd.ok) return set_arg_err(1, "not a live gp_post");
-    RC(check_points(xs, 2));
-    if (xs->d != post->d) return set_arg_err(2, "xs has a different D than the training inputs");
-    if (what <= 0 || what > 7) return set_arg_err(4, "what must be a combination of 1|2|4");
-    if ((what & 1) && !mean_out) return set_arg_err(5, "mean_out is NULL");
-    if ((what & 2) && !var_out) return set_arg_err(6, "var_out is NULL");
-    if ((what & 4) && !cov_out) return set_arg_err(7, "cov_out is NULL");
+    RC(check_test_points(xs, post->d));
+    RC(check_predict_out(what, mean_out, var_out, cov_out, 4));
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
     if ((what & 6) && multi_can_solve(post) && (!(what & 4) || xs->n <= 4096)) {
         // multi-device fit whose factor still lives as block-cyclic pieces: variances and (up to 4 096 test points) the full
         // covariance come from a forward solve ON the pieces (multi.hip: multi_predict_var) — no gather; the mean needs α only
         if (what & 1) RC(predict_impl<double>(post, xs, pm, 1, mean_out, nullptr, nullptr));
-        gp_kernel k{};
-        k.kind = post->kind; k.dtype = 0; k.variance = post->variance; k.nscale = post->nscale;
-        k.scale = post->scale.empty() ? nullptr : post->scale.data();
+        const gp_kernel k = post->kern.view(0);
         const long ns = xs->n;
         std::vector<double> xs_h;
         scale_points<double>(&k, xs, ns, xs_h);
         std::vector<double> sub((size_t)ns, 0.0), csub((what & 4) ? (size_t)ns * ns : 0, 0.0);
         RC(multi_predict_var(post, xs_h.data(), ns, ns, sub.data(), (what & 4) ? csub.data() : nullptr));
         if (what & 2)
-            for (long i = 0; i < ns; ++i) ((double*)var_out)[i] = post->variance - sub[i];  // k** = σ² for the stationary kernels of the path
+            for (long i = 0; i < ns; ++i) ((double*)var_out)[i] = post->kern.variance - sub[i];  // k** = σ² for the stationary kernels of the path
         if (what & 4) {  // K** on the device (the ctx's own stream), minus X Xᵀ
             const long nsp = round_up(ns, 128), ldc = nsp + c->ldpad;
             std::vector<double> xsp((size_t)post->d * nsp, 0.0);
@@ -2280,7 +2292,7 @@ int32_t gp_posterior_predict(gp_post* post, const gp_points* xs, const void* pm,
             RC(bufs.get(sizeof(double) * xsp.size(), &x_v));
             RC(bufs.get(sizeof(double) * (size_t)nsp * ldc, &C_v));
             HIPCHK(hipMemcpyAsync(x_v, xsp.data(), sizeof(double) * xsp.size(), hipMemcpyHostToDevice, c->sm));
-            RC(gpmi::eng_kcross(c, c->sm, post->kind, post->variance, (const double*)x_v, nsp, ns, nsp, (const double*)x_v, nsp, ns, nsp, post->d,
+            RC(gpmi::eng_kcross(c, c->sm, post->kern.kind, post->kern.variance, (const double*)x_v, nsp, ns, nsp, (const double*)x_v, nsp, ns, nsp, post->d,
                                 (double*)C_v, ldc));
             double* co = (double*)cov_out;
             HIPCHK(hipMemcpy2DAsync(co, sizeof(double) * ns, C_v, sizeof(double) * ldc, sizeof(double) * ns, ns, hipMemcpyDeviceToHost, c->sm));
@@ -2290,91 +2302,7 @@ int32_t gp_posterior_predict(gp_post* post, const gp_points* xs, const void* pm,
         return 0;
     }
     if (what & 6) RC(multi_gather(post));  // multi-device fit: the factor is assembled on this device on first need
-    return post->dtype == 0 ? predict_impl<double>(post, xs, pm, what, mean_out, var_out, cov_out)
-                            : predict_impl<float>(post, xs, pm, what, mean_out, var_out, cov_out);
-}
-
-int32_t gp_logpdf_grad(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y,
-                       void* logpdf_out, double* dvar, double* dscale, void* dnoise, void* dy, void* dx) {
-    RC(check_fit_args(c, k, x, noise));
-    if (!y) return set_arg_err(6, "y is NULL");
-    if (!logpdf_out) return set_arg_err(7, "logpdf_out is NULL");
-    std::lock_guard<std::mutex> l(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    return k->dtype == 0 ? grad_impl<double>(c, k, x, noise, mean, y, logpdf_out, dvar, dscale, dnoise, dy, dx)
-                         : grad_impl<float>(c, k, x, noise, mean, y, logpdf_out, dvar, dscale, dnoise, dy, dx);
-}
-
-// ---- composite kernels (gp_ksum): the single-device engine — on a multi-device ctx that of its first device, as fit_any does for fp32 fits
-static int32_t check_fit_args_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, KSum& ks, gp_kernel& kid) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
-    RC(check_points(x, 3));
-    RC(pack_ksum(k, x->d, 2, ks, kid));
-    return check_noise(noise, 4, true);
-}
-
-int32_t gp_logpdf_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y, int64_t ldy,
-                      int32_t ncols, void* out) {
-    KSum ks;
-    gp_kernel kid;
-    RC(check_fit_args_sum(c, k, x, noise, ks, kid));
-    if (!Y) return set_arg_err(6, "Y is NULL");
-    if (ldy < x->n) return set_arg_err(7, "ldy < n");
-    if (ncols < 1) return set_arg_err(8, "ncols must be >= 1");
-    if (!out) return set_arg_err(9, "out is NULL");
-    std::lock_guard<std::mutex> l(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    FitOut fo;
-    const int32_t rc = kid.dtype == 0 ? fit_impl<double>(c, &kid, x, noise, mean, Y, ldy, ncols, fo, nullptr, nullptr, &ks)
-                                      : fit_impl<float>(c, &kid, x, noise, mean, Y, ldy, ncols, fo, nullptr, nullptr, &ks);
-    if (rc != 0) return rc;
-    for (int s = 0; s < ncols; ++s) {
-        if (kid.dtype == 0) ((double*)out)[s] = fo.logpdf[s];
-        else ((float*)out)[s] = (float)fo.logpdf[s];
-    }
-    return 0;
-}
-
-int32_t gp_posterior_fit_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, gp_post** out,
-                             void* alpha_out, void* logpdf_out) {
-    KSum ks;
-    gp_kernel kid;
-    RC(check_fit_args_sum(c, k, x, noise, ks, kid));
-    if (!y) return set_arg_err(6, "y is NULL");
-    if (!out) return set_arg_err(7, "out is NULL");
-    *out = nullptr;
-    std::lock_guard<std::mutex> l(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    gp_post* p = new gp_post();
-    p->ctx = c;
-    FitOut fo;
-    const int32_t rc = kid.dtype == 0 ? fit_impl<double>(c, &kid, x, noise, mean, y, x->n, 1, fo, p, alpha_out, &ks)
-                                      : fit_impl<float>(c, &kid, x, noise, mean, y, x->n, 1, fo, p, alpha_out, &ks);
-    if (rc != 0) {
-        delete p;
-        return rc;
-    }
-    if (logpdf_out) {
-        if (kid.dtype == 0) *(double*)logpdf_out = fo.logpdf[0];
-        else *(float*)logpdf_out = (float)fo.logpdf[0];
-    }
-    c->refs++;
-    reg_add(p);
-    *out = p;
-    return 0;
-}
-
-int32_t gp_logpdf_grad_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y,
-                           void* logpdf_out, double* dtheta, void* dnoise, void* dy) {
-    KSum ks;
-    gp_kernel kid;
-    RC(check_fit_args_sum(c, k, x, noise, ks, kid));
-    if (!y) return set_arg_err(6, "y is NULL");
-    if (!logpdf_out) return set_arg_err(7, "logpdf_out is NULL");
-    std::lock_guard<std::mutex> l(c->mu);
-    HIPCHK(hipSetDevice(c->device));
-    return kid.dtype == 0 ? grad_impl<double>(c, &kid, x, noise, mean, y, logpdf_out, nullptr, nullptr, dnoise, dy, nullptr, &ks, dtheta)
-                          : grad_impl<float>(c, &kid, x, noise, mean, y, logpdf_out, nullptr, nullptr, dnoise, dy, nullptr, &ks, dtheta);
+    return by_dtype(post->dtype, [&](auto t) { return predict_impl<decltype(t)>(post, xs, pm, what, mean_out, var_out, cov_out); });
 }
 
 int32_t gp_posterior_update(gp_post* old, const gp_points* x2, const gp_noise* noise2, const void* delta_all, gp_post** out,
@@ -2392,36 +2320,23 @@ int32_t gp_posterior_update(gp_post* old, const gp_points* x2, const gp_noise* n
     if (old->dtype == 0 && multi_can_solve(old) && x2->n <= 4096 && !noise_dense(noise2)) {  // (a dense Σy2: gathered path, single-device engine)
         // multi-device posterior whose factor still lives as block-cyclic pieces: the factor is extended where it lives (multi.hip:
         // multi_update) — no gather; a failed forward / backward consistency check (-1991) falls back to the gathered path below
-        gp_post* p = new gp_post();
+        auto p = std::make_unique<gp_post>();
         double lp = 0;
-        const int32_t rc = multi_update(old, x2, noise2, delta_all, p, alpha_out, &lp);
+        const int32_t rc = multi_update(old, x2, noise2, delta_all, p.get(), alpha_out, &lp);
         if (rc == 0) {
             if (logpdf_out) *(double*)logpdf_out = lp;
-            c->refs++;
-            reg_add(p);
-            *out = p;
+            publish(c, p, out);
             return 0;
         }
-        delete p;
         (void)hipSetDevice(c->device);
         if (rc != -1991) return rc;
     }
     RC(multi_gather(old));
-    gp_post* p = new gp_post();
+    auto p = std::make_unique<gp_post>();
     double lp = 0;
-    int32_t rc = old->dtype == 0 ? update_impl<double>(old, x2, noise2, delta_all, p, alpha_out, &lp)
-                                 : update_impl<float>(old, x2, noise2, delta_all, p, alpha_out, &lp);
-    if (rc != 0) {
-        delete p;
-        return rc;
-    }
-    if (logpdf_out) {
-        if (old->dtype == 0) *(double*)logpdf_out = lp;
-        else *(float*)logpdf_out = (float)lp;
-    }
-    c->refs++;
-    reg_add(p);
-    *out = p;
+    RC(by_dtype(old->dtype, [&](auto t) { return update_impl<decltype(t)>(old, x2, noise2, delta_all, p.get(), alpha_out, &lp); }));
+    if (logpdf_out) put(logpdf_out, old->dtype, 0, lp);
+    publish(c, p, out);
     return 0;
 }
 
@@ -2435,7 +2350,7 @@ int32_t gp_posterior_factor_mul(gp_post* post, const void* xi, int32_t ncols, vo
     HIPCHK(hipSetDevice(c->device));
     if (post->dtype == 0 && multi_can_solve(post) && ncols <= 1024) return multi_factor_mul(post, (const double*)xi, ncols, (double*)out);  // on the pieces
     RC(multi_gather(post));
-    return post->dtype == 0 ? factor_mul_impl<double>(post, xi, ncols, out) : factor_mul_impl<float>(post, xi, ncols, out);
+    return by_dtype(post->dtype, [&](auto t) { return factor_mul_impl<decltype(t)>(post, xi, ncols, out); });
 }
 
 int32_t gp_posterior_solve(gp_post* post, const void* B, int32_t ncols, void* out) {
@@ -2448,7 +2363,7 @@ int32_t gp_posterior_solve(gp_post* post, const void* B, int32_t ncols, void* ou
     HIPCHK(hipSetDevice(c->device));
     if (post->dtype == 0 && multi_can_solve(post) && ncols <= 128) return multi_solve(post, (const double*)B, ncols, (double*)out);  // on the pieces
     RC(multi_gather(post));
-    return post->dtype == 0 ? solve_impl<double>(post, B, ncols, out) : solve_impl<float>(post, B, ncols, out);
+    return by_dtype(post->dtype, [&](auto t) { return solve_impl<decltype(t)>(post, B, ncols, out); });
 }
 
 int64_t gp_posterior_n(gp_post* post) {
@@ -2496,33 +2411,23 @@ int32_t gp_posterior_free(gp_post* post) {
 // ---- VFE / DTC ---------------------------------------------------------------------------------------
 int32_t gp_vfe_fit(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_points* z, const gp_noise* noise,
                    double jitter, const void* mean, const void* y, int32_t approx, gp_vfe** out, void* objective_out) {
-    RC(check_fit_args(c, k, x, noise, false));
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    ResolvedKernel rk;
+    RC(check_fit_args(k, x, noise, rk, false));
     RC(check_points(z, 4));
     if (z->d != x->d) return set_arg_err(4, "z has a different D than x");
     if (!(jitter >= 0)) return set_arg_err(6, "jitter must be >= 0");
     if (!y) return set_arg_err(8, "y is NULL");
     if (approx != 0 && approx != 1) return set_arg_err(9, "approx must be 0 (VFE) or 1 (DTC)");
     if (out) *out = nullptr;
-    std::lock_guard<std::mutex> l(c->mu);
     HIPCHK(hipSetDevice(c->device));
-    gp_vfe* p = out ? new gp_vfe() : nullptr;
+    std::unique_ptr<gp_vfe> p(out ? new gp_vfe() : nullptr);  // out == NULL: the objective only, no handle
     if (p) p->ctx = c;
     double obj = 0;
-    int32_t rc = k->dtype == 0 ? vfe_fit_impl<double>(c, k, x, z, noise, jitter, mean, y, approx, p, &obj)
-                               : vfe_fit_impl<float>(c, k, x, z, noise, jitter, mean, y, approx, p, &obj);
-    if (rc != 0) {
-        delete p;
-        return rc;
-    }
-    if (objective_out) {
-        if (k->dtype == 0) *(double*)objective_out = obj;
-        else *(float*)objective_out = (float)obj;
-    }
-    if (p) {
-        c->refs++;
-        reg_add(p);
-        *out = p;
-    }
+    RC(by_dtype(k->dtype, [&](auto t) { return vfe_fit_impl<decltype(t)>(c, k, x, z, noise, jitter, mean, y, approx, p.get(), &obj); }));
+    if (objective_out) put(objective_out, k->dtype, 0, obj);
+    if (p) publish(c, p, out);
     return 0;
 }
 
@@ -2538,26 +2443,15 @@ int32_t gp_vfe_update(gp_vfe* old, const gp_points* x2, const gp_noise* noise2, 
     *out = nullptr;
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
-    gp_kernel k{};
-    k.kind = old->kind; k.dtype = old->dtype; k.variance = old->variance; k.nscale = old->nscale;
-    k.scale = old->scale.empty() ? nullptr : old->scale.data();
-    gp_vfe* p = new gp_vfe();
+    const gp_kernel k = old->kern.view(old->dtype);
+    auto p = std::make_unique<gp_vfe>();
     p->ctx = c;
     double obj = 0;
-    int32_t rc = old->dtype == 0
-                     ? vfe_fit_impl<double>(c, &k, x2, nullptr, noise2, 0.0, mean2, y2, old->approx, p, &obj, old, VFE_UPDATE)
-                     : vfe_fit_impl<float>(c, &k, x2, nullptr, noise2, 0.0, mean2, y2, old->approx, p, &obj, old, VFE_UPDATE);
-    if (rc != 0) {
-        delete p;
-        return rc;
-    }
-    if (objective_out) {
-        if (old->dtype == 0) *(double*)objective_out = obj;
-        else *(float*)objective_out = (float)obj;
-    }
-    c->refs++;
-    reg_add(p);
-    *out = p;
+    RC(by_dtype(old->dtype, [&](auto t) {
+        return vfe_fit_impl<decltype(t)>(c, &k, x2, nullptr, noise2, 0.0, mean2, y2, old->approx, p.get(), &obj, old, VFE_UPDATE);
+    }));
+    if (objective_out) put(objective_out, old->dtype, 0, obj);
+    publish(c, p, out);
     return 0;
 }
 
@@ -2571,48 +2465,26 @@ int32_t gp_vfe_append(gp_vfe* old, const gp_points* z2, gp_vfe** out, void* obje
     if (old->segs.empty()) return set_arg_err(1, "gp_vfe holds no observations");
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
-    gp_kernel k{};
-    k.kind = old->kind; k.dtype = old->dtype; k.variance = old->variance; k.nscale = old->nscale;
-    k.scale = old->scale.empty() ? nullptr : old->scale.data();
-    gp_vfe* p = new gp_vfe();
+    const gp_kernel k = old->kern.view(old->dtype);
+    auto p = std::make_unique<gp_vfe>();
     p->ctx = c;
     double obj = 0;
-    int32_t rc = old->dtype == 0
-                     ? vfe_fit_impl<double>(c, &k, nullptr, z2, nullptr, 0.0, nullptr, nullptr, old->approx, p, &obj, old, VFE_APPEND)
-                     : vfe_fit_impl<float>(c, &k, nullptr, z2, nullptr, 0.0, nullptr, nullptr, old->approx, p, &obj, old, VFE_APPEND);
-    if (rc != 0) {
-        delete p;
-        return rc;
-    }
-    if (objective_out) {
-        if (old->dtype == 0) *(double*)objective_out = obj;
-        else *(float*)objective_out = (float)obj;
-    }
-    c->refs++;
-    reg_add(p);
-    *out = p;
+    RC(by_dtype(old->dtype, [&](auto t) {
+        return vfe_fit_impl<decltype(t)>(c, &k, nullptr, z2, nullptr, 0.0, nullptr, nullptr, old->approx, p.get(), &obj, old, VFE_APPEND);
+    }));
+    if (objective_out) put(objective_out, old->dtype, 0, obj);
+    publish(c, p, out);
     return 0;
 }
 
 int32_t gp_vfe_predict(gp_vfe* p, const gp_points* xs, const void* pm, int32_t what, void* mean_out, void* var_out, void* cov_out) {
     Guard gd(p);
     if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
-    RC(check_points(xs, 2));
-    if (xs->d != p->d) return set_arg_err(2, "xs has a different D than the training inputs");
-    if (what <= 0 || what > 7) return set_arg_err(4, "what must be a combination of 1|2|4");
-    if ((what & 1) && !mean_out) return set_arg_err(5, "mean_out is NULL");
-    if ((what & 2) && !var_out) return set_arg_err(6, "var_out is NULL");
-    if ((what & 4) && !cov_out) return set_arg_err(7, "cov_out is NULL");
+    RC(check_test_points(xs, p->d));
+    RC(check_predict_out(what, mean_out, var_out, cov_out, 4));
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
-    return p->dtype == 0 ? vfe_predict_impl<double>(p, xs, pm, what, mean_out, var_out, cov_out)
-                         : vfe_predict_impl<float>(p, xs, pm, what, mean_out, var_out, cov_out);
-}
-
-static int32_t check_joint_args(const gp_points* xs, int d, const gp_noise* noise) {
-    RC(check_points(xs, 2));
-    if (xs->d != d) return set_arg_err(2, "xs has a different D than the training inputs");
-    return check_noise(noise, 4, true);
+    return by_dtype(p->dtype, [&](auto t) { return vfe_predict_impl<decltype(t)>(p, xs, pm, what, mean_out, var_out, cov_out); });
 }
 
 int32_t gp_vfe_logpdf(gp_vfe* p, const gp_points* xs, const void* pm, const gp_noise* noise, const void* Y, int64_t ldy,
@@ -2620,19 +2492,17 @@ int32_t gp_vfe_logpdf(gp_vfe* p, const gp_points* xs, const void* pm, const gp_n
     Guard gd(p);
     if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
     RC(check_joint_args(xs, p->d, noise));
-    if (!Y) return set_arg_err(5, "Y is NULL");
-    if (ldy < xs->n) return set_arg_err(6, "ldy < n");
-    if (ncols < 1) return set_arg_err(7, "ncols must be >= 1");
-    if (!out) return set_arg_err(8, "out is NULL");
+    RC(check_heldout(Y, ldy, ncols, out, xs->n, 5));
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
     DevBufs bufs(c);
     Joint<double> J;
     const long R = round_up(ncols, 128);
-    int32_t rc = p->dtype == 0 ? vfe_joint<double>(p, xs, pm, noise, R, bufs, J) : vfe_joint<float>(p, xs, pm, noise, R, bufs, J);
-    if (rc == 0)
-        rc = p->dtype == 0 ? joint_logpdf<double, double>(c, J, Y, ldy, ncols, out) : joint_logpdf<double, float>(c, J, Y, ldy, ncols, out);
-    if (rc < 0) (void)hipStreamSynchronize(c->sm);
+    const int32_t rc = by_dtype(p->dtype, [&](auto t) -> int32_t {  // the M×M side and the joint are fp64 whatever the handle's dtype
+        RC(vfe_joint<decltype(t)>(p, xs, pm, noise, R, bufs, J));
+        return joint_logpdf<double, decltype(t)>(c, J, Y, ldy, ncols, out);
+    });
+    if (rc < 0) ctx_drain(c);  // (a positive status is a failed minor of the joint covariance, not an error)
     return rc;
 }
 
@@ -2640,17 +2510,16 @@ int32_t gp_vfe_rand(gp_vfe* p, const gp_points* xs, const void* pm, const gp_noi
     Guard gd(p);
     if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
     RC(check_joint_args(xs, p->d, noise));
-    if (!xi) return set_arg_err(5, "xi is NULL");
-    if (ncols < 1) return set_arg_err(6, "ncols must be >= 1");
-    if (!out) return set_arg_err(7, "out is NULL");
+    RC(check_draws(xi, ncols, out, 5));
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
     DevBufs bufs(c);
     Joint<double> J;
-    int32_t rc = p->dtype == 0 ? vfe_joint<double>(p, xs, pm, noise, 0, bufs, J) : vfe_joint<float>(p, xs, pm, noise, 0, bufs, J);
-    if (rc == 0)
-        rc = p->dtype == 0 ? joint_rand<double, double>(c, J, bufs, xi, ncols, out) : joint_rand<double, float>(c, J, bufs, xi, ncols, out);
-    if (rc < 0) (void)hipStreamSynchronize(c->sm);
+    const int32_t rc = by_dtype(p->dtype, [&](auto t) -> int32_t {
+        RC(vfe_joint<decltype(t)>(p, xs, pm, noise, 0, bufs, J));
+        return joint_rand<double, decltype(t)>(c, J, bufs, xi, ncols, out);
+    });
+    if (rc < 0) ctx_drain(c);
     return rc;
 }
 
@@ -2662,14 +2531,8 @@ int32_t gp_vfe_get(gp_vfe* p, void* alpha_out, void* meps_out) {
     std::vector<double> h((size_t)p->mp * 3);
     HIPCHK(hipMemcpy(h.data(), p->vec, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
     for (long i = 0; i < p->m; ++i) {
-        if (alpha_out) {
-            if (p->dtype == 0) ((double*)alpha_out)[i] = h[2 * p->mp + i];
-            else ((float*)alpha_out)[i] = (float)h[2 * p->mp + i];
-        }
-        if (meps_out) {
-            if (p->dtype == 0) ((double*)meps_out)[i] = h[p->mp + i];
-            else ((float*)meps_out)[i] = (float)h[p->mp + i];
-        }
+        if (alpha_out) put(alpha_out, p->dtype, i, h[2 * p->mp + i]);
+        if (meps_out) put(meps_out, p->dtype, i, h[p->mp + i]);
     }
     return 0;
 }
@@ -2692,11 +2555,7 @@ int32_t gp_vfe_get_factors(gp_vfe* p, void* U_out, void* LamU_out) {
                                 hipMemcpyDeviceToHost, c->sm));
         HIPCHK(hipStreamSynchronize(c->sm));
         for (long j = 0; j < m; ++j)
-            for (long i = 0; i < m; ++i) {
-                const double v = i <= j ? h[(size_t)j * m + i] : 0.0;
-                if (p->dtype == 0) ((double*)dsts[which])[(size_t)j * m + i] = v;
-                else ((float*)dsts[which])[(size_t)j * m + i] = (float)v;
-            }
+            for (long i = 0; i < m; ++i) put(dsts[which], p->dtype, (size_t)j * m + i, i <= j ? h[(size_t)j * m + i] : 0.0);
     }
     return 0;
 }
@@ -2732,8 +2591,7 @@ int32_t gp_vfe_grad(gp_vfe* p, double* dvariance, double* dscale, double* dnoise
     if (dx && (x_layout < 0 || x_layout > 2 || (x_layout == 0 && p->d != 1))) return set_arg_err(10, "x_layout must be 0 (vector, D = 1), 1 (ColVecs) or 2 (RowVecs)");
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
-    return p->dtype == 0 ? vfe_grad_impl<double>(p, dvariance, dscale, dnoise_sum, dnoise_diag, dy, dz, z_layout, dx, x_layout)
-                         : vfe_grad_impl<float>(p, dvariance, dscale, dnoise_sum, dnoise_diag, dy, dz, z_layout, dx, x_layout);
+    return by_dtype(p->dtype, [&](auto t) { return vfe_grad_impl<decltype(t)>(p, dvariance, dscale, dnoise_sum, dnoise_diag, dy, dz, z_layout, dx, x_layout); });
 }
 
 int64_t gp_vfe_m(gp_vfe* p) {
@@ -2761,10 +2619,7 @@ int32_t gp_posterior_logpdf(gp_post* post, const gp_points* xs, const void* pm, 
     Guard gd(post);
     if (!gd.ok) return set_arg_err(1, "not a live gp_post");
     RC(check_joint_args(xs, post->d, noise));
-    if (!Y) return set_arg_err(5, "Y is NULL");
-    if (ldy < xs->n) return set_arg_err(6, "ldy < n");
-    if (ncols < 1) return set_arg_err(7, "ncols must be >= 1");
-    if (!out) return set_arg_err(8, "out is NULL");
+    RC(check_heldout(Y, ldy, ncols, out, xs->n, 5));
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
     const bool dist = multi_can_solve(post) && xs->n <= 4096;  // held-out logpdf on the block-cyclic pieces: no gather
@@ -2781,7 +2636,7 @@ int32_t gp_posterior_logpdf(gp_post* post, const gp_points* xs, const void* pm, 
         rc = post_joint<float>(post, xs, pm, noise, R, bufs, J);
         if (rc == 0) rc = joint_logpdf<float, float>(c, J, Y, ldy, ncols, out);
     }
-    if (rc < 0) (void)hipStreamSynchronize(c->sm);
+    if (rc < 0) ctx_drain(c);
     return rc;
 }
 
@@ -2790,9 +2645,7 @@ int32_t gp_posterior_rand(gp_post* post, const gp_points* xs, const void* pm, co
     Guard gd(post);
     if (!gd.ok) return set_arg_err(1, "not a live gp_post");
     RC(check_joint_args(xs, post->d, noise));
-    if (!xi) return set_arg_err(5, "xi is NULL");
-    if (ncols < 1) return set_arg_err(6, "ncols must be >= 1");
-    if (!out) return set_arg_err(7, "out is NULL");
+    RC(check_draws(xi, ncols, out, 5));
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
     const bool dist = multi_can_solve(post) && xs->n <= 4096;  // posterior sampling on the block-cyclic pieces: no gather
@@ -2808,14 +2661,14 @@ int32_t gp_posterior_rand(gp_post* post, const gp_points* xs, const void* pm, co
         rc = post_joint<float>(post, xs, pm, noise, 0, bufs, J);
         if (rc == 0) rc = joint_rand<float, float>(c, J, bufs, xi, ncols, out);
     }
-    if (rc < 0) (void)hipStreamSynchronize(c->sm);
+    if (rc < 0) ctx_drain(c);
     return rc;
 }
 
 // ---- microbenchmarks / probes (tools/gpu_diag.py) ------------------------------------------------
 int32_t gp_probe_mfma_f64(gp_ctx* c, const double* A_host, const double* B_host, double* D_host) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
-    std::lock_guard<std::mutex> l(c->mu);
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     HIPCHK(hipSetDevice(c->device));
     double* buf;
     HIPCHK(hipMalloc((void**)&buf, sizeof(double) * (64 + 64 + 256)));
@@ -2830,8 +2683,8 @@ int32_t gp_probe_mfma_f64(gp_ctx* c, const double* A_host, const double* B_host,
 }
 // the fp32 twin: D(16×16) = A(16×4)·B(4×16) through Tr<float> — the MFMA and the C/D row map every fp32 kernel uses
 int32_t gp_probe_mfma_f32(gp_ctx* c, const float* A_host, const float* B_host, float* D_host) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
-    std::lock_guard<std::mutex> l(c->mu);
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     HIPCHK(hipSetDevice(c->device));
     float* buf;
     HIPCHK(hipMalloc((void**)&buf, sizeof(float) * (64 + 64 + 256)));
@@ -2846,8 +2699,8 @@ int32_t gp_probe_mfma_f32(gp_ctx* c, const float* A_host, const float* B_host, f
 }
 // returns measured TFLOP/s of back-to-back v_mfma_f64_16x16x4_f64 (all CUs, 2 blocks per CU)
 int32_t gp_bench_mfma_f64(gp_ctx* c, int32_t iters, double* tflops_out) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
-    std::lock_guard<std::mutex> l(c->mu);
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     HIPCHK(hipSetDevice(c->device));
     double* buf;
     HIPCHK(hipMalloc((void**)&buf, 64));
@@ -2876,8 +2729,8 @@ int32_t gp_bench_mfma_f64(gp_ctx* c, int32_t iters, double* tflops_out) {
 
 // measured TFLOP/s of back-to-back fp32 MFMAs: variant 0 = v_mfma_f32_16x16x4_f32 (what the GEMM kernels issue), 1 = 32x32x2
 int32_t gp_bench_mfma_f32(gp_ctx* c, int32_t variant, int32_t iters, double* tflops_out) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
-    std::lock_guard<std::mutex> l(c->mu);
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     HIPCHK(hipSetDevice(c->device));
     float* buf;
     HIPCHK(hipMalloc((void**)&buf, 64));
@@ -2928,14 +2781,14 @@ template <typename T> static inline bool aligned4(const T* p, int64_t ld) { retu
 template <typename T>
 static int32_t dev_assemble(gp_ctx* c, const gp_kernel* k, const T* x_dev, int64_t n_valid, int64_t n_pad, int32_t d, const T* noise_dev, const gp_grid* g,
                             T* a_loc, int64_t lda, int64_t m_loc, int64_t n_loc) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     RC(check_kernel(k, d, 2));
     if (m_loc % 128 || n_loc % 128) return set_arg_err(11, "m_loc, n_loc must be multiples of 128");
     if constexpr (sizeof(T) == 4) {  // the Gram kernel stores two columns (8 bytes) per lane
         if (((uintptr_t)a_loc & 7) != 0) return set_arg_err(9, "a_loc must be 8-byte aligned");
         if (lda % 2 != 0 || lda < n_loc) return set_arg_err(10, "lda must be even and >= n_loc");
     }
-    std::lock_guard<std::mutex> l(c->mu);
     HIPCHK(hipSetDevice(c->device));
     GridMap m = to_map(g, 0, 0);
     dim3 grid((unsigned)(n_loc / 128), (unsigned)(m_loc / 128));
@@ -2948,7 +2801,8 @@ static int32_t dev_assemble(gp_ctx* c, const gp_kernel* k, const T* x_dev, int64
 
 template <typename T>
 static int32_t dev_potrf(gp_ctx* c, T* a, int64_t lda, int64_t m, int64_t n, int32_t* info_dev, int32_t col0, int64_t n_valid, double* logdet_dev) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     if (n % 64 || m % 64 || m < n) return set_arg_err(4, "m, n must be multiples of 64 with m >= n");
     // the leaf kernels (and, in fp64, the in-panel update kernel) move rows as 16-byte pieces (leaf.hpp ld4 / st4; kernels.hpp panel64 chunk_t)
     if (((uintptr_t)a & 15) != 0) return set_arg_err(2, "a must be 16-byte aligned");
@@ -2957,21 +2811,20 @@ static int32_t dev_potrf(gp_ctx* c, T* a, int64_t lda, int64_t m, int64_t n, int
     } else {
         if (lda % 4 != 0 || lda < n) return set_arg_err(3, "lda must be a multiple of 4 and >= n");
     }
-    std::lock_guard<std::mutex> l(c->mu);
     HIPCHK(hipSetDevice(c->device));
     return potrf_rec<T>(c, c->sm, a, lda, 0, n, m, info_dev, col0, n_valid, logdet_dev);
 }
 
 template <typename T>
 static int32_t dev_trsm(gp_ctx* c, T* x, int64_t ldx, int64_t m, const T* lmat, int64_t ldl, int64_t n) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     if (n % 64 || m % 64) return set_arg_err(4, "m, n must be multiples of 64");
     if constexpr (sizeof(T) == 4) {
         if (!aligned4(x, ldx)) return set_arg_err(2, "x must be 16-byte aligned and ldx a multiple of 4");
         if (!aligned4(lmat, ldl)) return set_arg_err(5, "l must be 16-byte aligned and ldl a multiple of 4");
     }
     if (m == 0) return 0;
-    std::lock_guard<std::mutex> l(c->mu);
     HIPCHK(hipSetDevice(c->device));
     return trsm_rec<T>(c, c->sm, x, ldx, m, lmat, ldl, n);
 }
@@ -2979,7 +2832,8 @@ static int32_t dev_trsm(gp_ctx* c, T* x, int64_t ldx, int64_t m, const T* lmat, 
 template <typename T>
 static int32_t dev_gemm_nt(gp_ctx* c, T* cm, int64_t ldc, const T* a, int64_t lda, const T* b, int64_t ldb, int64_t m, int64_t n, int64_t k, const gp_grid* g,
                            int64_t row0, int64_t col0) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     if constexpr (sizeof(T) == 8) {
         if (m % 64 || n % 64 || k % 16) return set_arg_err(8, "m, n multiples of 64 and k multiple of 16 required");
     } else {
@@ -2988,28 +2842,27 @@ static int32_t dev_gemm_nt(gp_ctx* c, T* cm, int64_t ldc, const T* a, int64_t ld
         if (!aligned4(a, lda)) return set_arg_err(4, "a must be 16-byte aligned and lda a multiple of 4");
         if (!aligned4(b, ldb)) return set_arg_err(6, "b must be 16-byte aligned and ldb a multiple of 4");
     }
-    std::lock_guard<std::mutex> l(c->mu);
     HIPCHK(hipSetDevice(c->device));
     return launch_gemm<T>(c, c->sm, cm, ldc, a, lda, b, ldb, m, n, k, to_map(g, row0, col0));
 }
 
 template <typename T>
 static int32_t dev_trsv(gp_ctx* c, const T* lmat, int64_t ldl, int64_t np, T* r, int64_t ldr, int32_t nrhs, int32_t forward) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     if (np % 128) return set_arg_err(4, "np must be a multiple of 128");
     if constexpr (sizeof(T) == 4) {  // the diagonal tiles are inverted from 16-byte row pieces (trtri_64)
         if (!aligned4(lmat, ldl)) return set_arg_err(2, "l must be 16-byte aligned and ldl a multiple of 4");
     }
-    std::lock_guard<std::mutex> l(c->mu);
     HIPCHK(hipSetDevice(c->device));
     return trsv<T>(c, c->sm, lmat, ldl, np, r, ldr, nrhs, forward != 0);
 }
 
 template <typename T>
 static int32_t dev_gemv_t(gp_ctx* c, const T* lmat, int64_t ldl, int64_t nrows, int64_t ncols, const T* a, T* r) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     if (nrows <= 0 || ncols <= 0) return 0;
-    std::lock_guard<std::mutex> l(c->mu);
     HIPCHK(hipSetDevice(c->device));
     hipLaunchKernelGGL(gemv_t_kernel<T>, dim3((unsigned)((ncols + 255) / 256), (unsigned)((nrows + 63) / 64)), dim3(256),
                        0, c->sm, lmat, ldl, nrows, ncols, a, r);
@@ -3019,9 +2872,9 @@ static int32_t dev_gemv_t(gp_ctx* c, const T* lmat, int64_t ldl, int64_t nrows, 
 
 template <typename T>
 static int32_t dev_rowsumsq(gp_ctx* c, const T* x, int64_t ldx, int64_t nrows, int64_t ncols, double* out_dev) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     if (nrows <= 0) return 0;
-    std::lock_guard<std::mutex> l(c->mu);
     HIPCHK(hipSetDevice(c->device));
     hipLaunchKernelGGL(rowsumsq_kernel<T>, dim3((unsigned)nrows), dim3(256), 0, c->sm, x, ldx, ncols, out_dev);
     HIPCHK(hipGetLastError());
@@ -3055,18 +2908,18 @@ int32_t gpd_trsm_f32(gp_ctx* c, float* x, int64_t ldx, int64_t m, const float* l
 }
 
 int32_t gpd_inv_lower(gp_ctx* c, const double* lmat, int64_t ldl, int64_t nb, double* w, int64_t ldw, double* scratch1, double* scratch2) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     if (nb < 64 || nb % 64) return set_arg_err(4, "nb must be a multiple of 64");
     if (!lmat || !w || !scratch1) return set_arg_err(2, "l / w / scratch1 is NULL");
-    std::lock_guard<std::mutex> l(c->mu);
     HIPCHK(hipSetDevice(c->device));
     return gpmi::eng_inv_lower(c, c->sm, lmat, ldl, nb, w, ldw, scratch1, scratch2);
 }
 int32_t gpd_trsm_inv(gp_ctx* c, double* x, int64_t ldx, int64_t m, const double* w, int64_t ldw, int64_t nb, double* scratch, int64_t lds) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     if (nb % 64 || m % 64) return set_arg_err(3, "m, nb must be multiples of 64");
     if (m == 0) return 0;
-    std::lock_guard<std::mutex> l(c->mu);
     HIPCHK(hipSetDevice(c->device));
     return gpmi::eng_trsm_inv(c, c->sm, x, ldx, m, w, ldw, nb, scratch, lds);
 }
@@ -3103,8 +2956,8 @@ int32_t gpd_rowsumsq_f32(gp_ctx* c, const float* x, int64_t ldx, int64_t nrows, 
 }
 
 int32_t gpd_gemm_time(gp_ctx* c, double* ms_out, int64_t* launches_out) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
-    std::lock_guard<std::mutex> l(c->mu);
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->sm));
     double tot = 0;
@@ -3121,7 +2974,8 @@ int32_t gpd_gemm_time(gp_ctx* c, double* ms_out, int64_t* launches_out) {
 }
 
 int32_t gpd_sync(gp_ctx* c) {
-    if (!c || !reg_has(c)) return set_arg_err(1, "not a live gp_ctx");
+    Guard gd(c, false);  // no lock, as ever: the wait must not queue behind another thread's call on the ctx
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->sm));
     HIPCHK(hipStreamSynchronize(c->sp));

@@ -2112,9 +2112,7 @@ int32_t multi_fit(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_no
         post->ctx = c;
         post->dtype = 0;
         post->n = n; post->np = np; post->ld = np + c->ldpad; post->mtot = np + 128; post->d = d;
-        post->kind = k->kind; post->variance = k->variance; post->nscale = k->nscale;
-        post->scale.clear();
-        if (k->scale && k->nscale > 0) post->scale.assign(k->scale, k->scale + k->nscale);
+        post->kern = KernelRec(k, nullptr);
         post->A = nullptr; post->A_bytes = 0;
         post->xs = mb.keep(xs_v); post->xs_bytes = sizeof(double) * (size_t)d * np;
         post->alpha = mb.keep(al_v); post->alpha_bytes = sizeof(double) * (size_t)np;
@@ -2299,7 +2297,7 @@ int32_t multi_predict_var(gp_post* post, const double* xs_scaled, long ns_ld, lo
         SolveDims sd{mp->n, mp->npad, mp->nblk, mp->nb, nsc, nsp, d};
         sd.valid = mp->valid.data();
         std::vector<std::vector<double>> part, cpart;
-        RC(run_solve(c, sd, mp->pieces, post->kind, post->variance, x_h.data(), xs_h.data(), nullptr, cov_sub != nullptr, nullptr, part, cpart));
+        RC(run_solve(c, sd, mp->pieces, post->kern.kind, post->kern.variance, x_h.data(), xs_h.data(), nullptr, cov_sub != nullptr, nullptr, part, cpart));
         for (long i = 0; i < nsc; ++i) {
             double acc = 0;
             for (int r = 0; r < R; ++r) acc += part[r][i];
@@ -2329,7 +2327,7 @@ int32_t multi_solve(gp_post* post, const double* B, int ncols, double* out) {
     sd.rhs = true;
     sd.nbwd = ncols;
     std::vector<std::vector<double>> part, cpart;
-    RC(run_solve(c, sd, mp->pieces, post->kind, post->variance, nullptr, nullptr, rhs_h.data(), false, z_h.data(), part, cpart));
+    RC(run_solve(c, sd, mp->pieces, post->kern.kind, post->kern.variance, nullptr, nullptr, rhs_h.data(), false, z_h.data(), part, cpart));
     to_compact(z_h.data(), npad, ncols, mp->valid, mp->nb, out, n);
     return 0;
 }
@@ -2424,7 +2422,7 @@ int32_t multi_update(gp_post* old, const gp_points* x2, const gp_noise* noise2, 
     {
         const double* pd = (const double*)x2->data;
         for (int dd = 0; dd < d; ++dd) {
-            const double sc = old->nscale == 1 ? old->scale[0] : (old->nscale > 1 ? old->scale[dd] : 1.0);
+            const double sc = old->kern.nscale() == 1 ? old->kern.scale[0] : (old->kern.nscale() > 1 ? old->kern.scale[dd] : 1.0);
             for (long i = 0; i < n2; ++i) {
                 const double v = sc * (x2->layout == 0 ? pd[i] : (x2->layout == 1 ? pd[(long)dd + i * x2->d] : pd[i + (long)dd * x2->n]));
                 xs2_h[(size_t)dd * nsp + i] = v;
@@ -2475,7 +2473,7 @@ int32_t multi_update(gp_post* old, const gp_points* x2, const gp_noise* noise2, 
         SolveDims sd{n0, npad0, nblk0, NB, n2, nsp, d};
         sd.valid = mp0->valid.data();
         sd.sink_nb2 = nb2;
-        rc = run_solve(c, sd, mp0->pieces, old->kind, old->variance, x0_h.data(), xs2_h.data(), nullptr, true, nullptr, part, cpart);
+        rc = run_solve(c, sd, mp0->pieces, old->kern.kind, old->kern.variance, x0_h.data(), xs2_h.data(), nullptr, true, nullptr, part, cpart);
     }
     // ---- U22ᵀ = chol(K(x2, x2) + Σy2 − X Xᵀ) on the first device (identity padding up to the block boundary), blocks to their owners
     double logdet2_half = 0;
@@ -2506,7 +2504,7 @@ int32_t multi_update(gp_post* old, const gp_points* x2, const gp_noise* noise2, 
             MCHK(hipMemsetAsync(c->info_dev, 0, sizeof(int), sm));
             MCHK(hipMemsetAsync(c->scal_dev, 0, sizeof(double) * 16, sm));
             MCHK(hipMemsetAsync(S_v, 0, sizeof(double) * (size_t)(Sp + 128) * lds, sm));
-            RC(eng_assemble(c, sm, old->kind, old->variance, (const double*)x2_v, n2, Sp, d, (const double*)nz_v, plain_map(1, 0, 0), (double*)S_v, lds, Sp, Sp));
+            RC(eng_assemble(c, sm, old->kern.kind, old->kern.variance, (const double*)x2_v, n2, Sp, d, (const double*)nz_v, plain_map(1, 0, 0), (double*)S_v, lds, Sp, Sp));
             hipLaunchKernelGGL(mk_addmat_kernel, dim3((unsigned)std::min<long>(1024, (nsp * nsp + 255) / 256)), dim3(256), 0, sm, (double*)S_v, lds, (const double*)T_v,
                                nsp, nsp, nsp);
             MCHK(hipGetLastError());
@@ -2540,7 +2538,7 @@ int32_t multi_update(gp_post* old, const gp_points* x2, const gp_noise* noise2, 
         sd.valid = valid1.data();
         sd.rhs = true;
         sd.nbwd = 1;
-        rc = run_solve(c, sd, pieces1, old->kind, old->variance, nullptr, nullptr, rhs_h.data(), false, z_h.data(), part, cpart);
+        rc = run_solve(c, sd, pieces1, old->kern.kind, old->kern.variance, nullptr, nullptr, rhs_h.data(), false, z_h.data(), part, cpart);
         if (rc == 0) {
             for (int r = 0; r < R; ++r) sqm += part[r][0];
             to_compact(z_h.data(), npad1, 1, valid1, NB, al.data(), n1);
@@ -2577,7 +2575,7 @@ int32_t multi_update(gp_post* old, const gp_points* x2, const gp_noise* noise2, 
             // with K·α evaluated from the inputs (kvec kernel, no factor).  A mismatch returns −1991: the caller gathers instead.
             void* kv_v = nullptr;
             RC(mb.get(sizeof(double) * (size_t)nsp, &kv_v));
-            RC(eng_kvec(c, c->sm, (const double*)xs_v + n0, np1, (const double*)xs_v, np1, d, old->kind, old->variance, n1, (const double*)al_v,
+            RC(eng_kvec(c, c->sm, (const double*)xs_v + n0, np1, (const double*)xs_v, np1, d, old->kern.kind, old->kern.variance, n1, (const double*)al_v,
                         (double*)kv_v, n2));
             std::vector<double> kv((size_t)n2);
             MCHK(hipMemcpyAsync(kv.data(), kv_v, sizeof(double) * (size_t)n2, hipMemcpyDeviceToHost, c->sm));
@@ -2591,7 +2589,7 @@ int32_t multi_update(gp_post* old, const gp_points* x2, const gp_noise* noise2, 
                 const double a2 = al[(size_t)(n0 + i)], lhs = kv[(size_t)i] + nz_h[(size_t)i] * a2;
                 res = std::max(res, std::fabs(lhs - dl[n0 + i]));
             }
-            const double scale = (double)n1 * old->variance * amax + dmax;  // the bound multi_fit's every-row check uses
+            const double scale = (double)n1 * old->kern.variance * amax + dmax;  // the bound multi_fit's every-row check uses
             if (!(res <= 1e-9 * scale)) {
                 char b[220];
                 snprintf(b, sizeof b, "sequential update on the pieces: rows of the new observations miss (K + Sigma) alpha = delta by %.3g (scale %.3g)", res, scale);
@@ -2614,8 +2612,7 @@ int32_t multi_update(gp_post* old, const gp_points* x2, const gp_noise* noise2, 
     post->ctx = c;
     post->dtype = 0;
     post->n = n1; post->np = np1; post->ld = np1 + c->ldpad; post->mtot = np1 + 128; post->d = d;
-    post->kind = old->kind; post->variance = old->variance; post->nscale = old->nscale;
-    post->scale = old->scale;
+    post->kern = old->kern;
     post->A = nullptr; post->A_bytes = 0;
     post->xs = mb.keep(xs_v); post->xs_bytes = sizeof(double) * (size_t)d * np1;
     post->alpha = mb.keep(al_v); post->alpha_bytes = sizeof(double) * (size_t)np1;

@@ -41,10 +41,9 @@ struct gp_vfe {
     gp_ctx* ctx = nullptr;
     int dtype = 0;
     long m = 0, mp = 0, ld = 0;
-    int d = 0, kind = 0;
-    double variance = 1, jitter = 0;
-    int nscale = 0;
-    std::vector<double> scale;
+    int d = 0;
+    KernelRec kern;  // single-kind: VFE / DTC take no composite kernel
+    double jitter = 0;
     void *Lz = nullptr, *Ld = nullptr;  // (mp + 256) × ld doubles: chol(K_zz + jitter I), Λ_ε factor
     void* zs = nullptr;                 // scaled inducing inputs, double [d][mp]
     void* vec = nullptr;                // double [4][mp]: rows c, m_ε, α, spare
@@ -387,7 +386,7 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
         return 0;
     };
 
-    int32_t rc = [&]() -> int32_t {
+    const int32_t rc = run_drained(c, [&]() -> int32_t {
         HIPCHK(hipEventRecord(c->ev_phase[0], s));
         HIPCHK(hipMemcpyAsync(jit_v, jit_h.data(), jit_b, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemsetAsync(c->info_dev, 0, sizeof(int), s));
@@ -553,12 +552,8 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
             c->tm.gemm_bytes += r.bytes;
         }
         return 0;
-    }();
-    if (rc != 0) {
-        (void)hipStreamSynchronize(c->sm);
-        (void)hipStreamSynchronize(c->sp);
-        return rc;
-    }
+    });
+    if (rc != 0) return rc;
     // a failing factorisation: K_zz (+ the bordered block of an append) or Λ_ε — reported like the reference's cholesky calls
     if (info_h != 0) return (mode == VFE_APPEND && info_h <= m2) ? (int32_t)(m_old + info_h) : info_h;
     // objective: dtc = -½ (N log2π + logdet Σy + logdet Λ_ε + ‖δ_s‖² − ‖Λ_ε.U⁻ᵀ A δ_s‖²)          :302-303
@@ -572,10 +567,8 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
     if (out) {
         out->ctx = c;
         out->dtype = k->dtype;
-        out->m = m; out->mp = mp; out->ld = ld; out->d = d; out->kind = k->kind;
-        out->variance = k->variance; out->nscale = k->nscale; out->jitter = jitter;
-        out->scale.clear();
-        if (k->scale && k->nscale > 0) out->scale.assign(k->scale, k->scale + k->nscale);
+        out->m = m; out->mp = mp; out->ld = ld; out->d = d; out->jitter = jitter;
+        out->kern = KernelRec(k, nullptr);
         out->Lz = bufs.keep(Lz_v);
         out->Ld = bufs.keep(Ld_v);
         out->zs = bufs.keep(zsD_v);
@@ -606,9 +599,7 @@ static int32_t vfe_joint(gp_vfe* p, const gp_points* xs, const void* pm, const g
     const long m = p->m, mp = p->mp, ld = p->ld;
     const long ns = xs->n, nsp = round_up(ns, 128);
     const int d = p->d;
-    gp_kernel k{};
-    k.kind = p->kind; k.dtype = 0; k.variance = p->variance; k.nscale = p->nscale;
-    k.scale = p->scale.empty() ? nullptr : p->scale.data();
+    const gp_kernel k = p->kern.view(0);
     std::vector<T> xsT;
     scale_points<T>(&k, xs, nsp, xsT);  // inputs arrive in T; scale in T (as the fit did), then widen
     std::vector<double> xs_h(xsT.begin(), xsT.end()), nz_h;
@@ -635,14 +626,14 @@ static int32_t vfe_joint(gp_vfe* p, const gp_points* xs, const void* pm, const g
     HIPCHK(hipMemcpyAsync(xs_v, xs_h.data(), sizeof(double) * xs_h.size(), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(nz_v, nz_h.data(), sizeof(double) * (size_t)nsp, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(kvec_kernel<double>, dim3((unsigned)ns), dim3(256), 0, s, (const double*)xs_v, nsp, (const double*)p->zs, mp, d,
-                       p->kind, p->variance, m, vec + 2 * mp, (double*)m_v);                                     // K_*z α
+                       p->kern.kind, p->kern.variance, m, vec + 2 * mp, (double*)m_v);                                     // K_*z α
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(m_h.data(), m_v, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, s));
     {
         GridMap g = plain_map(0, 0, 0);
         dim3 grid((unsigned)(mp / 128), (unsigned)(nsp / 128));
         launch_kmat<double>(grid, s, X1, ld, (const double*)xs_v, nsp, (const double*)p->zs, mp, d,
-                           p->kind, p->variance, (const double*)nullptr, ns, m, 0, g, (const double*)nullptr, (const double*)nullptr);
+                           p->kern.kind, p->kern.variance, (const double*)nullptr, ns, m, 0, g, (const double*)nullptr, (const double*)nullptr);
         HIPCHK(hipGetLastError());
     }
     RC(trsm_cached<double>(c, s, X1, ld, nsp, (const double*)p->Lz, ld, mp, p->m, p->dib_z, bufs));
@@ -658,7 +649,7 @@ static int32_t vfe_joint(gp_vfe* p, const gp_points* xs, const void* pm, const g
         GridMap g = plain_map(1, 0, 0);
         dim3 grid((unsigned)(nsp / 128), (unsigned)(nsp / 128));
         launch_kmat<double>(grid, s, Cm, ldc, (const double*)xs_v, nsp, (const double*)xs_v, nsp, d,
-                           p->kind, p->variance, (const double*)nz_v, ns, ns, 1, g, (const double*)nullptr, (const double*)nullptr);
+                           p->kern.kind, p->kern.variance, (const double*)nz_v, ns, ns, 1, g, (const double*)nullptr, (const double*)nullptr);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemsetAsync(Cm + nsp * ldc, 0, sizeof(double) * (size_t)(R + 128) * ldc, s));
@@ -679,9 +670,9 @@ static int32_t vfe_predict_impl(gp_vfe* p, const gp_points* xs, const void* pm, 
     if (what & 4) {  // full covariance (+ mean): the joint, copied out and mirrored on the host                :187-190, :205-210
         DevBufs bufs(c);
         Joint<double> J;
-        int32_t rc = vfe_joint<T>(p, xs, pm, nullptr, 0, bufs, J);
+        const int32_t rc = vfe_joint<T>(p, xs, pm, nullptr, 0, bufs, J);
         if (rc != 0) {
-            (void)hipStreamSynchronize(c->sm);
+            ctx_drain(c);
             return rc;
         }
         const long ns = J.ns;
@@ -701,9 +692,7 @@ static int32_t vfe_predict_impl(gp_vfe* p, const gp_points* xs, const void* pm, 
     const long m = p->m, mp = p->mp, ld = p->ld;
     const long ns = xs->n, nsp = round_up(ns, 128);
     const int d = p->d;
-    gp_kernel k{};
-    k.kind = p->kind; k.dtype = 0; k.variance = p->variance; k.nscale = p->nscale;
-    k.scale = p->scale.empty() ? nullptr : p->scale.data();
+    const gp_kernel k = p->kern.view(0);
     // inputs arrive in T; scale in T (as the fit did), then widen
     std::vector<T> xsT;
     scale_points<T>(&k, xs, nsp, xsT);
@@ -722,18 +711,18 @@ static int32_t vfe_predict_impl(gp_vfe* p, const gp_points* xs, const void* pm, 
     c->ev_used = 0;
     c->gemm_recs.clear();
     std::vector<double> oh((size_t)nsp * 3, 0.0);
-    int32_t rc = [&]() -> int32_t {
+    const int32_t rc = run_drained(c, [&]() -> int32_t {
         HIPCHK(hipMemcpyAsync(xs_v, xs_h.data(), xs_b, hipMemcpyHostToDevice, s));
         if (what & 1) {  // mean = m(x*) + K_*z α                                                  :183-185
             hipLaunchKernelGGL(kvec_kernel<double>, dim3((unsigned)ns), dim3(256), 0, s, (const double*)xs_v, nsp,
-                               (const double*)p->zs, mp, d, p->kind, p->variance, m, vec + 2 * mp, o);
+                               (const double*)p->zs, mp, d, p->kern.kind, p->kern.variance, m, vec + 2 * mp, o);
             HIPCHK(hipGetLastError());
         }
         if (what & 2) {  // var = k** − ‖A‖²_col + ‖Λ_ε.U⁻ᵀ A‖²_col, Aᵀ = K_*z L_z⁻ᵀ                 :192-195
             GridMap g = plain_map(0, 0, 0);
             dim3 grid((unsigned)(mp / 128), (unsigned)(nsp / 128));
             launch_kmat<double>(grid, s, X, ld, (const double*)xs_v, nsp,
-                               (const double*)p->zs, mp, d, p->kind, p->variance, (const double*)nullptr, ns, m, 0, g,
+                               (const double*)p->zs, mp, d, p->kern.kind, p->kern.variance, (const double*)nullptr, ns, m, 0, g,
                                (const double*)nullptr, (const double*)nullptr);
             HIPCHK(hipGetLastError());
             RC(trsm_cached<double>(c, s, X, ld, nsp, (const double*)p->Lz, ld, mp, p->m, p->dib_z, bufs));
@@ -746,16 +735,13 @@ static int32_t vfe_predict_impl(gp_vfe* p, const gp_points* xs, const void* pm, 
         HIPCHK(hipMemcpyAsync(oh.data(), o, o_b, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return 0;
-    }();
-    if (rc != 0) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
+    });
+    if (rc != 0) return rc;
     const T* prior = (const T*)pm;
     if (what & 1)
         for (long i = 0; i < ns; ++i) ((T*)mean_out)[i] = (T)((prior ? (double)prior[i] : 0.0) + oh[i]);
     if (what & 2)
-        for (long i = 0; i < ns; ++i) ((T*)var_out)[i] = (T)(p->variance - oh[nsp + i] + oh[2 * nsp + i]);
+        for (long i = 0; i < ns; ++i) ((T*)var_out)[i] = (T)(p->kern.variance - oh[nsp + i] + oh[2 * nsp + i]);
     return 0;
 }
 
@@ -813,7 +799,7 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
     c->gemm_recs.clear();
     for (auto& e : c->ev_phase)
         if (!e) HIPCHK(hipEventCreate(&e));
-    const int nsc = std::max(p->nscale, 1);
+    const int nsc = std::max(p->kern.nscale(), 1);
     const size_t L_b = sizeof(double) * (size_t)(mp + 128 + 128) * ld;
     const size_t X_b = sizeof(double) * (size_t)(CH + 128) * ld, g_b = sizeof(double) * (size_t)(2 + nsc + 2), gz_b = sizeof(double) * (size_t)d * mp;
     void *W_v = 0, *V_v = 0, *H_v = 0, *R_v = 0, *E_v = 0, *Gp_v = 0, *Gz_v = 0, *X_v = 0, *X2_v = 0, *C2_v = 0, *xc_v = 0, *rc_v = 0, *bc_v = 0, *C_v = 0, *g_v = 0, *gz_v = 0, *sc_v = 0;
@@ -842,7 +828,7 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
     const double* Ld = (const double*)p->Ld;
     const double* alpha = (const double*)p->vec + 2 * mp;
     std::vector<double> sc_h((size_t)nsc, 1.0);
-    for (int q = 0; q < p->nscale; ++q) sc_h[q] = p->scale[q];
+    for (int q = 0; q < p->kern.nscale(); ++q) sc_h[q] = p->kern.scale[q];
     std::vector<double> g_h((size_t)(2 + nsc + 2), 0.0), gz_h((size_t)d * mp, 0.0);   // [0] ∂/∂variance, [2 + p] ∂/∂scale_p, [2 + nsc] Σ ∂/∂σ_i², [3 + nsc] Σ σ_i⁻²
     // per observation (concatenated over the segments, arrival order): what the host needs to finish ∂/∂σ_i², ∂/∂y_i, ∂/∂x_i
     long n_all = 0;
@@ -861,7 +847,7 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
         HIPCHK(hipGetLastError());
         return 0;
     };
-    int32_t rc = [&]() -> int32_t {
+    const int32_t rc = run_drained(c, [&]() -> int32_t {
         HIPCHK(hipEventRecord(c->ev_phase[0], s));
         HIPCHK(hipMemcpyAsync(sc_v, sc_h.data(), sizeof(double) * (size_t)nsc, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemsetAsync(g_v, 0, g_b, s));
@@ -959,7 +945,7 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
             }
             GridMap g = plain_map(0, 0, 0);
             dim3 grid((unsigned)(mp / 128), (unsigned)(CH / 128));
-            launch_kmat<double>(grid, sa, (double*)Xb[bb], ld, I.xr, I.ldxr, (const double*)p->zs, mp, d, p->kind, p->variance, (const double*)nullptr, I.nr, m, 0, g,
+            launch_kmat<double>(grid, sa, (double*)Xb[bb], ld, I.xr, I.ldxr, (const double*)p->zs, mp, d, p->kern.kind, p->kern.variance, (const double*)nullptr, I.nr, m, 0, g,
                                 (const double*)nullptr, I.rs);
             HIPCHK(hipGetLastError());
             if (ovl) {
@@ -989,11 +975,11 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
             if (ovl) HIPCHK(hipStreamWaitEvent(sa, evG[bb], 0));
             dim3 grid((unsigned)(mp / 128), (unsigned)((I.nr + 127) / 128));
             if (dx)
-                RC((launch_vgrad<double, true>(sa, grid, (const double*)Cb[bb], ld, 0, I.xr, I.ldxr, (const double*)p->zs, mp, d, p->kind, p->variance, p->nscale,
+                RC((launch_vgrad<double, true>(sa, grid, (const double*)Cb[bb], ld, 0, I.xr, I.ldxr, (const double*)p->zs, mp, d, p->kern.kind, p->kern.variance, p->kern.nscale(),
                                                (const double*)sc_v, I.rs, I.b, alpha, I.nr, m, (double*)g_v, (double*)gz_v, mp, 1.0, cks[ci].rq, cks[ci].rp,
                                                cks[ci].gx, cks[ci].sg->npad)));
             else
-                RC((launch_vgrad<double, false>(sa, grid, (const double*)Cb[bb], ld, 0, I.xr, I.ldxr, (const double*)p->zs, mp, d, p->kind, p->variance, p->nscale,
+                RC((launch_vgrad<double, false>(sa, grid, (const double*)Cb[bb], ld, 0, I.xr, I.ldxr, (const double*)p->zs, mp, d, p->kern.kind, p->kern.variance, p->kern.nscale(),
                                                 (const double*)sc_v, I.rs, I.b, alpha, I.nr, m, (double*)g_v, (double*)gz_v, mp, 1.0, cks[ci].rq, cks[ci].rp,
                                                 (double*)nullptr, 0L)));
             if (ovl) {
@@ -1011,7 +997,7 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
             RC(bufs.get(sizeof(T) * (size_t)sg.n, &dn_v));
             RC(bufs.get(sizeof(T) * (size_t)sg.n, &dy_v));
             hipLaunchKernelGGL(vgrad_finish_kernel<T>, dim3((unsigned)std::min<long>((sg.n + 255) / 256, 2048)), dim3(256), 0, s, (const T*)sg.rs, (const T*)sg.b,
-                               (const double*)segb[si][0], (const double*)segb[si][1], sg.n, p->variance, vfe ? 1 : 0, (T*)dn_v, (T*)dy_v, (double*)g_v + 2 + nsc);
+                               (const double*)segb[si][0], (const double*)segb[si][1], sg.n, p->kern.variance, vfe ? 1 : 0, (T*)dn_v, (T*)dy_v, (double*)g_v + 2 + nsc);
             HIPCHK(hipGetLastError());
             if (dnoise) HIPCHK(hipMemcpyAsync((T*)dnoise + off, dn_v, sizeof(T) * (size_t)sg.n, hipMemcpyDeviceToHost, s));
             if (dy) HIPCHK(hipMemcpyAsync((T*)dy + off, dy_v, sizeof(T) * (size_t)sg.n, hipMemcpyDeviceToHost, s));
@@ -1028,7 +1014,7 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
         // ---- K_zz: explicit weights G_zz over the full square; z_j enters through both arguments (factor 2 on the column role)
         {
             dim3 grid((unsigned)(mp / 128), (unsigned)((m + 127) / 128));
-            RC((launch_vgrad<double, false>(s, grid, (const double*)Gz, ld, 1, (const double*)p->zs, mp, (const double*)p->zs, mp, d, p->kind, p->variance, p->nscale,
+            RC((launch_vgrad<double, false>(s, grid, (const double*)Gz, ld, 1, (const double*)p->zs, mp, (const double*)p->zs, mp, d, p->kern.kind, p->kern.variance, p->kern.nscale(),
                                             (const double*)sc_v, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, m, m, (double*)g_v,
                                             (double*)gz_v, mp, 2.0, (double*)nullptr, (double*)nullptr, (double*)nullptr, 0L)));
         }
@@ -1046,14 +1032,11 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
         HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[0], c->ev_phase[3]));
         c->tm.total_ms = ms;
         return 0;
-    }();
-    if (rc != 0) {
-        (void)hipStreamSynchronize(c->sm);
-        return rc;
-    }
+    });
+    if (rc != 0) return rc;
     if (dvar) *dvar = g_h[0] - (vfe ? 0.5 * g_h[3 + nsc] : 0.0);   // − ½ Σ_i ∂k_ii/∂σ_k² / σ_i²: the trace term
     if (dscale)
-        for (int q = 0; q < p->nscale; ++q) dscale[q] = g_h[2 + q];
+        for (int q = 0; q < p->kern.nscale(); ++q) dscale[q] = g_h[2 + q];
     if (dnoise_sum) *dnoise_sum = g_h[2 + nsc];
     if (dz)  // the container layout of the pseudo-inputs (src/finite_gp_projection.jl:32-37): 0 vector, 1 ColVecs (D×M column-major), 2 RowVecs (M×D column-major)
         for (int q = 0; q < d; ++q)
