@@ -38,6 +38,9 @@ struct GridMap {
     long astride, bstride;  // != 0 with nbatch > 1: independent products instead — A + b·astride, B + b·bstride, the full k range each
     int ktri_off;    // ktri == 1 with A pointing at row ktri_off of the triangular matrix: row tile m0 stops at ktri_off + m0 + 128
                      // ktri == 2: rows [0, ktri_off) of A are dense, the upper-triangular block starts at row ktri_off (row tile m0 > ktri_off starts at column m0 − ktri_off)
+    long c2off;      // beta0 with s1 != 0 (fp64 tile kernel; the Strassen products): the tile is accumulated from zero, then C[idx] −= s1·acc and,
+    int s1, s2;      // with c2off != 0, C[c2off + idx] −= s2·acc (s1, s2 = ±1) — plain loads and stores, the launches of one decomposition are ordered on one stream
+    long c2stride;   // nbatch > 1: product b's second target lies at c2off + b·c2stride from ITS first target (C + b·cstride); the targets of one launch are disjoint
 };
 
 // Packed composite kernel Σ_t σ_t² Π_f κ_f (include/gpmi355.h gp_ksum), passed BY VALUE as a kernel argument (under 1 KB; uniform across the
@@ -142,6 +145,8 @@ struct gp_ctx {
                            // on the main stream, so that each launch's last partial round of workgroups is filled by the other — C5 +0.4…0.7 ms with the priority,
                            // −0.45 ms with both at equal priority (profiles/r6/c5_ab*.jsonl): the single-stream pass has no idle tail to fill
     long vfe_inv_nb = 512; // VFE prelude: inv(L_z) with the inverse diagonal blocks of this width built in one batched launch sequence (0: 64-wide leaves)
+    long strassen_min_rows = 16384;  // fp64 fits: smallest side of an off-diagonal block of the bulk trailing update (and of gpd_gemm_nt) that runs as seven
+                                 // half-size products (one level of Strassen: gpmi355.hip gemm_nt_strassen / syrk_lower_split); 0 = never
     int xcd_swizzle = 0;   // XCD-aware super-tile order of the MFMA gemm workgroups
     long xcd_min_tiles = 256;
     long ldpad = 32;       // elements of padding per row: de-aliases power-of-two strides across HBM channels

@@ -259,7 +259,7 @@ static int32_t launch_gemm(gp_ctx* c, hipStream_t s, CT* C, long ldc, const T* A
                                 : (g.ktri == 2 ? (g.ktri_off > 0 ? 2.0 * (double)g.ktri_off * (double)N * (double)K + (double)N * (double)K * (double)K
                                                                  : (double)M * (double)M * (double)M / 3.0)
                                                : (g.ktri == 3 ? (double)M * (double)N * (double)(N + 128) : 2.0 * (double)K * elems));
-        rec.bytes = 2.0 * sizeof(CT) * elems + sizeof(T) * (double)K * (double)(M + N);
+        rec.bytes = 2.0 * sizeof(CT) * elems * (g.c2off ? 2 : 1) + sizeof(T) * (double)K * (double)(M + N);
         rec.M = M; rec.N = N; rec.K = K;
         rec.stream = (s == c->sp);
         HIPCHK(hipEventRecord(rec.a, s));
@@ -349,7 +349,92 @@ GridMap gpmi::plain_map(int lower, long row0, long col0) {
     g.astride = 0;
     g.bstride = 0;
     g.ktri_off = 0;
+    g.c2off = 0;
+    g.c2stride = 0;
+    g.s1 = 0;
+    g.s2 = 0;
     return g;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Strassen form of the large off-diagonal products of the trailing update (fp64; ctx parameter "strassen_min_rows").
+//   C(M×N) −= A·Bᵀ with every operand cut into 2×2 quadrants (rows, k) is seven products of (M/2)×(N/2)×(K/2) instead of eight: two launches of
+//   strassen_sums_kernel write the ten operand sums into the workspace, then ordered launches of the tile GEMM accumulate each product from zero
+//   and subtract it from its one or two target quadrants (GridMap c2off / s1 / s2), products with disjoint targets two to a launch: four launches.
+//   No atomics, one stream: bitwise repeatable.
+// ------------------------------------------------------------------------------------------------
+struct StrassenWs {  // the ten sum panels, rows of K/2 + ldpad elements (the pad keeps the row stride off a power of two like every other operand's)
+    double* p = nullptr;
+    size_t elems = 0;
+};
+static size_t strassen_ws_elems(const gp_ctx* c, long M, long N, long K) { return (size_t)5 * (size_t)(M / 2 + N / 2) * (size_t)(K / 2 + c->ldpad); }
+// shapes the Strassen form takes: quadrants of whole 128×128 tiles, whole k steps per half, operand rows movable as 16-byte pieces
+static bool strassen_shape(const gp_ctx* c, long M, long N, long K) {
+    return c->strassen_min_rows > 0 && std::min(M, N) >= std::max(256L, c->strassen_min_rows) && M % 256 == 0 && N % 256 == 0 && K % 32 == 0;
+}
+// side of the off-diagonal block the lower SYRK of side m is split at (multiple of 256); 0: no split
+static long strassen_split(const gp_ctx* c, long m, long K) {
+    const long h = (m / 2) / 256 * 256;
+    return strassen_shape(c, h, h, K) ? h : 0;
+}
+
+static int32_t gemm_nt_strassen(gp_ctx* c, hipStream_t s, const StrassenWs& ws, double* C, long ldc, const double* A, long lda, const double* B, long ldb,
+                                long M, long N, long K) {
+    if (!strassen_shape(c, M, N, K) || !ws.p || ws.elems < strassen_ws_elems(c, M, N, K) || lda % 2 || ldb % 2 || (((uintptr_t)A | (uintptr_t)B) & 15))
+        return launch_gemm<double>(c, s, C, ldc, A, lda, B, ldb, M, N, K, plain_map(0, 0, 0));
+    const long mh = M / 2, nh = N / 2, kh = K / 2, lds = kh + c->ldpad;
+    const long pa = mh * lds, pb = nh * lds;
+    double* const SA = ws.p;            // A11+A22, A21+A22, A11+A12, A21−A11, A12−A22
+    double* const SB = ws.p + 5 * pa;   // B11+B22, B21−B22, B12−B11, B11+B21, B12+B22
+    hipLaunchKernelGGL(strassen_sums_kernel<double>, dim3((unsigned)((mh * (kh / 2) + 255) / 256)), dim3(256), 0, s, A, lda, (int)mh, (int)kh, (int)lds, 0, SA, pa);
+    hipLaunchKernelGGL(strassen_sums_kernel<double>, dim3((unsigned)((nh * (kh / 2) + 255) / 256)), dim3(256), 0, s, B, ldb, (int)nh, (int)kh, (int)lds, 1, SB, pb);
+    HIPCHK(hipGetLastError());
+    // one launch: `nb` products with disjoint targets (product b: operands a + b·as, b + b·bs, first target c1 + b·cs, second target c2off + b·c2s from it)
+    auto prod = [&](int nb, double* c1, long cs, long c2off, long c2s, int s1, int s2, const double* a, long la, long as, const double* b, long lb, long bs) -> int32_t {
+        GridMap g = plain_map(0, 0, 0);
+        g.beta0 = 1;
+        g.c2off = c2off;
+        g.c2stride = c2s;
+        g.s1 = s1;
+        g.s2 = s2;
+        g.nbatch = nb;
+        g.cstride = cs;
+        g.astride = as;
+        g.bstride = bs;
+        return launch_gemm<double>(c, s, c1, ldc, a, la, b, lb, mh, nh, kh, g);
+    };
+    const long dn = nh, dm = mh * ldc;  // C11 = C, C12 = C + dn, C21 = C + dm, C22 = C + dm + dn
+    // Products whose targets do not meet share a launch (a launch ends with a partly filled round of workgroups: four of them instead of seven); every quadrant
+    // still receives its products in one fixed order.
+    //   M1 = (A11+A22)(B11+B22)ᵀ -> C11, C22
+    RC(prod(1, C, 0, dm + dn, 0, 1, 1, SA, lds, 0, SB, lds, 0));
+    //   M2 = (A21+A22) B11ᵀ -> C21, −C22   |   M5 = (A11+A12) B22ᵀ -> C12, −C11
+    RC(prod(2, C + dm, dn - dm, dn, -2 * dn, 1, -1, SA + pa, lds, pa, B, ldb, nh * ldb + kh));
+    //   M3 = A11 (B21−B22)ᵀ -> C12, C22    |   M4 = A22 (B12−B11)ᵀ -> C11, C21
+    RC(prod(2, C + dn, -dn, dm, 0, 1, 1, A, lda, mh * lda + kh, SB + pb, lds, pb));
+    //   M6 = (A21−A11)(B11+B21)ᵀ -> C22    |   M7 = (A12−A22)(B12+B22)ᵀ -> C11
+    RC(prod(2, C + dm + dn, -(dm + dn), 0, 0, 1, 0, SA + 3 * pa, lds, pa, SB + 3 * pb, lds, pb));
+    return 0;
+}
+
+// Lower SYRK C(m×m) −= P·Pᵀ (P = mrows × K; rows [m, mrows) of C are the carried rows below the square, updated over all m columns; row0: the
+// square's offset on the global diagonal).  Split by rows at h: two half-size SYRKs on the diagonal (recursively) and the block between them,
+// which carries half the flops, in the Strassen form.  Below the threshold: the one launch this always was.
+static int32_t syrk_lower_split(gp_ctx* c, hipStream_t s, const StrassenWs& ws, double* C, long ldc, const double* P, long ldp, long mrows, long m, long K,
+                                long row0) {
+    const long h = ws.p ? strassen_split(c, m, K) : 0;
+    if (h == 0) return launch_gemm<double>(c, s, C, ldc, P, ldp, P, ldp, mrows, m, K, plain_map(1, row0, row0));
+    const long b = m - h, bs = b / 256 * 256;  // rows below the split; the Strassen block takes whole 256-row pieces of them
+    RC(syrk_lower_split(c, s, ws, C, ldc, P, ldp, h, h, K, row0));
+    RC(gemm_nt_strassen(c, s, ws, C + h * ldc, ldc, P + h * ldp, ldp, P, ldp, bs, h, K));
+    if (b > bs) RC(launch_gemm<double>(c, s, C + (h + bs) * ldc, ldc, P + (h + bs) * ldp, ldp, P, ldp, b - bs, h, K, plain_map(0, 0, 0)));
+    RC(syrk_lower_split(c, s, ws, C + h * ldc + h, ldc, P + h * ldp, ldp, b, b, K, row0 + h));
+    if (mrows > m) RC(launch_gemm<double>(c, s, C + m * ldc, ldc, P + m * ldp, ldp, P, ldp, mrows - m, m, K, plain_map(0, 0, 0)));
+    return 0;
+}
+// workspace of the above for a SYRK of side m (its largest Strassen block has at most m/2 + 255 rows and m/2 columns); 0 bytes: nothing is split
+static size_t syrk_split_ws_elems(const gp_ctx* c, long m, long K) {
+    return strassen_split(c, m, K) ? strassen_ws_elems(c, m / 2 + 256, m / 2 + 256, K) : 0;
 }
 
 static long split_half(long n) {  // largest multiple of 64 that is <= n/2 (>= 64)
@@ -663,13 +748,14 @@ static int32_t trsm_post(gp_post* post, hipStream_t s, T* X, long ldx, long M, D
 // Full factorisation of the np×np matrix (rows [np, mtot) are carried RHS rows): right-looking over panels of width nb with a
 // one-panel look-ahead (potrf_full_la below); nb = 0: the plain recursion on one stream.
 template <typename T>
-static int32_t potrf_full_la(gp_ctx* c, T* A, long lda, long np, long mtot, int* info_dev, long n_valid, double* logdet_dev);
+static int32_t potrf_full_la(gp_ctx* c, T* A, long lda, long np, long mtot, int* info_dev, long n_valid, double* logdet_dev, DevBufs* bufs);
 
+// bufs (the exact fit passes its own): owner of the Strassen workspace of the bulk trailing updates; without it they stay single launches
 template <typename T>
 static int32_t potrf_full(gp_ctx* c, T* A, long lda, long np, long mtot, int* info_dev, long n_valid,
-                          double* logdet_dev) {
+                          double* logdet_dev, DevBufs* bufs = nullptr) {
     if (c->nb == 0) return potrf_rec<T>(c, c->sm, A, lda, 0, np, mtot, info_dev, 0, n_valid, logdet_dev);
-    return potrf_full_la<T>(c, A, lda, np, mtot, info_dev, n_valid, logdet_dev);
+    return potrf_full_la<T>(c, A, lda, np, mtot, info_dev, n_valid, logdet_dev, bufs);
 }
 
 // sched 0: right-looking over panels of width nb with a one-panel look-ahead: the whole next panel (recursive
@@ -679,7 +765,7 @@ static int32_t potrf_full(gp_ctx* c, T* A, long lda, long np, long mtot, int* in
 // in the history at f1ed70e.)
 template <typename T>
 static int32_t potrf_full_la(gp_ctx* c, T* A, long lda, long np, long mtot, int* info_dev, long n_valid,
-                             double* logdet_dev) {
+                             double* logdet_dev, DevBufs* bufs) {
     long nb = c->nb;
     // below the look-ahead threshold the schedule is one stream anyway: panels of "nb_small" (4 096) columns halve the passes over the trailing matrix
     // (K = 4 096 updates) — C2 29.8-30.1 -> 29.0-29.2 ms on two boxes, N = 8 192 6.51 -> 6.43 (profiles/r5/nb_sweep.txt); from the threshold on the
@@ -690,6 +776,17 @@ static int32_t potrf_full_la(gp_ctx* c, T* A, long lda, long np, long mtot, int*
     const bool la = c->lookahead != 0 && np >= c->lookahead_min_n;
     hipStream_t sM = c->sm, sP = la ? c->sp : c->sm;
     hipEvent_t ev_u1 = nullptr, ev_panel = nullptr;
+    StrassenWs ws;  // one set of sum panels per fit, sized for the first (largest) bulk update; every launch that touches it is ordered on the main stream
+    if constexpr (std::is_same<T, double>::value) {
+        const long m2 = np - 2 * nb;
+        const size_t el = (bufs && m2 > 0) ? syrk_split_ws_elems(c, m2, nb) : 0;
+        if (el) {
+            void* p = nullptr;
+            RC(bufs->get(sizeof(double) * el, &p));
+            ws.p = (double*)p;
+            ws.elems = el;
+        }
+    }
     if (la) {  // the panel stream starts after everything queued so far on the main stream (assembly)
         RC(ctx_event(c, &ev_u1, false));
         HIPCHK(hipEventRecord(ev_u1, c->sm));
@@ -715,9 +812,13 @@ static int32_t potrf_full_la(gp_ctx* c, T* A, long lda, long np, long mtot, int*
         }
         // U2: the rest of the trailing matrix
         const long k2 = k1 + nb1;
-        if (k2 < np)
-            RC(launch_gemm<T>(c, sM, A + k2 * lda + k2, lda, A + k2 * lda + k, lda, A + k2 * lda + k, lda,
-                              mtot - k2, np - k2, nbk, plain_map(1, k2, k2)));
+        if (k2 < np) {
+            if constexpr (std::is_same<T, double>::value)
+                RC(syrk_lower_split(c, sM, ws, A + k2 * lda + k2, lda, A + k2 * lda + k, lda, mtot - k2, np - k2, nbk, k2));
+            else
+                RC(launch_gemm<T>(c, sM, A + k2 * lda + k2, lda, A + k2 * lda + k, lda, A + k2 * lda + k, lda,
+                                  mtot - k2, np - k2, nbk, plain_map(1, k2, k2)));
+        }
     }
     return 0;
 }
@@ -1169,7 +1270,7 @@ static int32_t fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const
         RC(assemble_sym<T>(c, KDesc{k->kind, k->variance, ks}, (const T*)xs_v, np, d, (const T*)noise_v, n, np, A, ld));
         if (noise_dense(noise)) RC((dense_add<T, T>(c, bufs, A, ld, noise, n)));  // all of Σy before the factorisation (counts into assemble_ms)
         HIPCHK(hipEventRecord(c->ev_phase[1], c->sm));
-        RC(potrf_full<T>(c, A, ld, np, mtot, c->info_dev, n, c->scal_dev));
+        RC(potrf_full<T>(c, A, ld, np, mtot, c->info_dev, n, c->scal_dev, &bufs));
         HIPCHK(hipEventRecord(c->ev_phase[2], c->sm));
         // sqmahal per RHS row: ‖z_s‖², z_sᵀ = δ_sᵀ L⁻ᵀ sits in row np+s
         hipLaunchKernelGGL(rowsumsq_kernel<T>, dim3((unsigned)ncols), dim3(256), 0, c->sm, A + np * ld, ld, np,
@@ -1865,6 +1966,7 @@ int32_t gp_ctx_set_param(gp_ctx* c, const char* name, int64_t v) {
     else if (!strcmp(name, "lookahead_min_n")) c->lookahead_min_n = std::max<int64_t>(0, v);
     else if (!strcmp(name, "time_kernels")) c->time_kernels = v != 0;
     else if (!strcmp(name, "xcd_swizzle")) c->xcd_swizzle = v != 0;
+    else if (!strcmp(name, "strassen_min_rows")) c->strassen_min_rows = v <= 0 ? 0 : round_up(v, 256);
     else if (!strcmp(name, "gemm_streamk")) c->gemm_streamk = v != 0;
     else if (!strcmp(name, "sk_max_tiles")) c->sk_max_tiles = v;
     else if (!strcmp(name, "sk_min_k")) c->sk_min_k = v;
@@ -1912,7 +2014,7 @@ int32_t gp_ctx_get_param(gp_ctx* c, const char* name, int64_t* out) {
     if (c->multi && multi_get_param(c, name, out) == 0) return 0;
     const struct { const char* n; int64_t v; } tab[] = {
         {"nb", c->nb}, {"nb_small", c->nb_small}, {"nb_large", c->nb_large}, {"lookahead", c->lookahead}, {"lookahead_min_n", c->lookahead_min_n}, {"time_kernels", c->time_kernels},
-        {"xcd_swizzle", c->xcd_swizzle}, {"xcd_min_tiles", c->xcd_min_tiles}, {"gemm_streamk", c->gemm_streamk},
+        {"xcd_swizzle", c->xcd_swizzle}, {"strassen_min_rows", c->strassen_min_rows}, {"xcd_min_tiles", c->xcd_min_tiles}, {"gemm_streamk", c->gemm_streamk},
         {"sk_max_tiles", c->sk_max_tiles}, {"sk_min_k", c->sk_min_k}, {"gemm_pipe", c->gemm_pipe}, {"gemm_pad_f32", c->gemm_pad_f32},
         {"gemm_pad_lds", c->gemm_pad_user ? c->gemm_pad_lds : 0}, {"trsv_nb", c->trsv_nb},  {"deterministic", c->deterministic},
         {"leaf_v2", c->leaf_v2}, {"leaf_xr", c->leaf_xr}, {"leaf_cols", c->leaf_cols}, {"updk_max_k", c->updk_max_k}, {"updk_rt", c->updk_rt},
@@ -2843,6 +2945,19 @@ static int32_t dev_gemm_nt(gp_ctx* c, T* cm, int64_t ldc, const T* a, int64_t ld
         if (!aligned4(b, ldb)) return set_arg_err(6, "b must be 16-byte aligned and ldb a multiple of 4");
     }
     HIPCHK(hipSetDevice(c->device));
+    if constexpr (sizeof(T) == 8) {  // "strassen_min_rows": the same decomposition the factorisation's bulk update uses
+        const bool syrk = g && g->lower && g->P == 1 && g->Q == 1 && a == b && lda == ldb && row0 == col0 && m >= n;
+        const size_t el = !g ? (strassen_shape(c, m, n, k) ? strassen_ws_elems(c, m, n, k) : 0) : (syrk ? syrk_split_ws_elems(c, n, k) : 0);
+        if (el) {
+            DevBufs bufs(c);
+            void* p = nullptr;
+            RC(bufs.get(sizeof(double) * el, &p));
+            const StrassenWs ws{(double*)p, el};
+            const int32_t rc = syrk ? syrk_lower_split(c, c->sm, ws, cm, ldc, a, lda, m, n, k, row0) : gemm_nt_strassen(c, c->sm, ws, cm, ldc, a, lda, b, ldb, m, n, k);
+            HIPCHK(hipStreamSynchronize(c->sm));  // the sum panels go back to the cache when this returns: nothing may still read them
+            return rc;
+        }
+    }
     return launch_gemm<T>(c, c->sm, cm, ldc, a, lda, b, ldb, m, n, k, to_map(g, row0, col0));
 }
 

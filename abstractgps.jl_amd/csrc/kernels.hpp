@@ -8,6 +8,7 @@
 // Kernels (reference call site each one replaces):
 //   kmat_kernel        KernelFunctions.kernelmatrix (+ Σy on the diagonal)   src/base_gp.jl:70,74; src/finite_gp_projection.jl:133-136
 //   gemm_nt_dma_kernel / gemm_nt_sk_kernel  the SYRK/GEMM trailing update inside LAPACK dpotrf/dtrsm (MFMA)  src/finite_gp_projection.jl:308
+//   strassen_sums_kernel  the operand sums of the one-level Strassen form of the large off-diagonal GEMMs (ten panels, two launches)   :308
 //   panel64_kernel     dpotf2 of a 64×64 diagonal tile + Σ log L_ii + X ← X L⁻ᵀ of the rows below it   :308, :310
 //   trsm64_mfma_kernel X ← X L⁻ᵀ against a 64×64 tile (dtrsm)               src/util/common_covmat_ops.jl:54-60
 //   trsv_*             forward / backward substitutions for vectors (dtrtrs/dpotrs)   src/exact_gpr_posterior.jl:33
@@ -325,6 +326,33 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_dma_kernel(CT* C, long ldc, co
         return;
     }
 #endif
+    if constexpr (sizeof(T) == 8) {
+        if (g.beta0 && g.s1 != 0) {  // dual-target epilogue (block-uniform): the product, accumulated from zero, is subtracted from one or two targets with a sign each
+            if (active) {
+                const bool two = g.c2off != 0;
+                const long c2off = g.c2off + (g.nbatch > 1 ? (long)blockIdx.z * g.c2stride : 0L);
+                const CT f1 = (CT)g.s1, f2 = (CT)g.s2;
+#pragma unroll
+                for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                    for (int nt = 0; nt < 4; ++nt) {  // fragment by fragment: four loads, four stores per target
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            CT* const p = Cw + (long)(mt * 16 + TR::crow(lane, r)) * ldc + nt * 16;
+                            *p = *p - f1 * acc[mt][nt][r];
+                        }
+                        if (two) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                CT* const p = Cw + c2off + (long)(mt * 16 + TR::crow(lane, r)) * ldc + nt * 16;
+                                *p = *p - f2 * acc[mt][nt][r];
+                            }
+                        }
+                    }
+            }
+            return;
+        }
+    }
     if (active) {
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
@@ -333,6 +361,47 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_dma_kernel(CT* C, long ldc, co
 #pragma unroll
                 for (int r = 0; r < 4; ++r) Cw[(long)(mt * 16 + TR::crow(lane, r)) * ldc + nt * 16] = -acc[mt][nt][r];
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// strassen_sums: the five operand sums one side of a one-level Strassen product needs, from ONE pass over the operand block.
+//   X is rows × 2·kh (row-major, ld ldx; 16-byte aligned rows), split into the quadrants X11 X12 / X21 X22 of (rows/2) × kh; the outputs are
+//   five (rows/2) × kh panels S + i·pstride with row stride lds.  side 0 (A):  X11+X22, X21+X22, X11+X12, X21−X11, X12−X22
+//                                                         side 1 (B):  X11+X22, X21−X22, X12−X11, X11+X21, X12+X22
+//   One lane moves one 16-byte piece of each quadrant: 4 loads, 5 stores.
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void strassen_sums_kernel(const T* __restrict__ X, long ldx, int rh, int kh, int lds, int side, T* __restrict__ S, long pstride) {
+    constexpr int E = 16 / (int)sizeof(T);
+    struct alignas(16) V {
+        T v[E];
+    };
+    const int cpr = kh / E;  // 16-byte pieces per quadrant row
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)rh * cpr) return;
+    const int r = (int)(idx / cpr), cc = (int)(idx - (long)r * cpr) * E;
+    const T* const x1 = X + (long)r * ldx + cc;
+    const T* const x2 = X + (long)(r + rh) * ldx + cc;
+    const V a = *(const V*)x1, b = *(const V*)(x1 + kh), c = *(const V*)x2, d = *(const V*)(x2 + kh);  // X11 X12 X21 X22
+    V o[5];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        o[0].v[e] = a.v[e] + d.v[e];
+        if (side == 0) {
+            o[1].v[e] = c.v[e] + d.v[e];
+            o[2].v[e] = a.v[e] + b.v[e];
+            o[3].v[e] = c.v[e] - a.v[e];
+            o[4].v[e] = b.v[e] - d.v[e];
+        } else {
+            o[1].v[e] = c.v[e] - d.v[e];
+            o[2].v[e] = b.v[e] - a.v[e];
+            o[3].v[e] = a.v[e] + c.v[e];
+            o[4].v[e] = b.v[e] + d.v[e];
+        }
+    }
+    T* const s = S + (long)r * lds + cc;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) *(V*)(s + i * pstride) = o[i];
 }
 
 // (Two measured-slower variants of this kernel were removed in round 3 — a three-stage operand ring with one workgroup per CU,
