@@ -81,6 +81,8 @@ PROTOTYPES = {
     "gp_logpdf_sum": (i32, [vp, PS, PP, PN, vp, vp, i64, i32, vp]),
     "gp_posterior_fit_sum": (i32, [vp, PS, PP, PN, vp, vp, C.POINTER(vp), vp, vp]),
     "gp_logpdf_grad_sum": (i32, [vp, PS, PP, PN, vp, vp, vp, C.POINTER(dbl), vp, vp]),
+    "gp_logpdf_grad_sum_x": (i32, [vp, PS, PP, PN, vp, vp, vp, C.POINTER(dbl), vp, vp, vp]),
+    "gp_logpdf_terms_sum": (i32, [vp, PS, PP, PN, vp, vp, i64, i32, vp, vp]),
     "gp_logpdf_batch": (i32, [vp, i32, PK, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp)]),
     "gp_logpdf_batch_sum": (i32, [vp, i32, PS, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp)]),
     "gp_posterior_update": (i32, [vp, PP, PN, vp, C.POINTER(vp), vp, vp]),

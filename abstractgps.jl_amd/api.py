@@ -812,27 +812,25 @@ def logpdf_batch(fxs, ys, *, return_alpha: bool = False, on_error: str = "raise"
 
 
 def _terms(fx: FiniteGP, y, want_logdet: bool, want_sqmahal: bool):
-    """gp_logpdf_terms: logdet(cov(fx)) and / or sqmahal(fx, y) from ONE factorisation on the device."""
+    """gp_logpdf_terms (gp_logpdf_terms_sum for a composite kernel): logdet(cov(fx)) and / or sqmahal(fx, y) from ONE factorisation on the device."""
     f = fx.f
     if not isinstance(f, GP):
         raise TypeError("only GP priors are accelerated here (the shim falls back to the stock methods otherwise)")
-    if _is_composite(f.kernel):
-        raise NotImplementedError("logdet / sqmahal of a composite kernel are not accelerated (gp_logpdf_terms is single-kind; "
-                                  "the Julia shim falls back to stock AbstractGPs)")
     ctx = f.context()
     dt = _input_dtype(fx.x) if y is None else np.result_type(_input_dtype(fx.x), np.float32 if np.asarray(y).dtype == np.float32 else np.float64).type
     m = _Marshal(dt)
     px = m.points(fx.x)
-    kk = m.kernel(f.kernel, px.d)
+    composite = _is_composite(f.kernel)
+    kk = m.ksum(f.kernel, px.d)[0] if composite else m.kernel(f.kernel, px.d)
     nz = m.noise(fx.sigma2, px.n)
     mean = _mean_vector(f.mean_fn, fx.x, dt)
     mean = None if mean is None else m.arr(mean)
     Y = None if y is None else m.arr(y if y.ndim == 2 else y[:, None], order="F")
     ld = np.empty(1, dtype=dt)
     sq = np.empty(1 if Y is None else Y.shape[1], dtype=dt)
-    check(ctx.lib.gp_logpdf_terms(ctx.handle, C.byref(kk), C.byref(px), C.byref(nz), m.ptr(mean), m.ptr(Y), px.n,
-                                  0 if Y is None else Y.shape[1], ld.ctypes.data if want_logdet else None,
-                                  sq.ctypes.data if want_sqmahal else None))
+    terms = ctx.lib.gp_logpdf_terms_sum if composite else ctx.lib.gp_logpdf_terms
+    check(terms(ctx.handle, C.byref(kk), C.byref(px), C.byref(nz), m.ptr(mean), m.ptr(Y), px.n, 0 if Y is None else Y.shape[1],
+                ld.ctypes.data if want_logdet else None, sq.ctypes.data if want_sqmahal else None))
     return ld[0], sq
 
 
@@ -874,6 +872,19 @@ def _dnoise_shape(nz: gp_noise, n: int):
     return 1 if nz.kind == 0 else (n if nz.kind == 1 else (n, n))
 
 
+def _dx_buffer(px: gp_points, dt) -> np.ndarray:
+    """dx_out of gp_logpdf_grad / gp_logpdf_grad_sum_x, in the ABI layout of the inputs: (n,) vector; ColVecs (N, D) C-order = D×N column-major; RowVecs (D, N)."""
+    return np.empty((px.n,) if px.layout == 0 else ((px.n, px.d) if px.layout == 1 else (px.d, px.n)), dtype=dt)
+
+
+def _dx_shaped(dxb: np.ndarray, px: gp_points, x) -> np.ndarray:
+    """The buffer comes back in the ABI layout the inputs were passed in: (n, d) for layout 1, (d, n) for layout 2; the result has the shape of x.X."""
+    if px.layout == 0:
+        return dxb
+    nd = dxb if px.layout == 1 else dxb.T                       # (N, D) view
+    return np.ascontiguousarray(nd.T if isinstance(_as_input(x), ColVecs) else nd)
+
+
 def logpdf_and_grad(fx: FiniteGP, y, wrt_x: bool = False) -> tuple:
     """Value and gradient of logpdf(fx, y) for the rrule of the accelerated path (the reference differentiates the same
     expression by AD — test/finite_gp_projection.jl:152-178).  Returns (logpdf, grads) with grads =
@@ -881,7 +892,7 @@ def logpdf_and_grad(fx: FiniteGP, y, wrt_x: bool = False) -> tuple:
     vector ∂/∂Σy_ii, or for a dense Σy the (n, n) symmetric matrix G = ½(ααᵀ − C⁻¹) with d logpdf = ⟨G, dΣy⟩ for symmetric dΣy (a parametric Σy(φ) chains
     as ⟨G, ∂Σy/∂φ⟩), "y": −α, "mean": +α} and, with wrt_x, "x": ∂/∂x in the shape of the input container's array.
     A composite kernel (sums, products, Periodic / RationalQuadratic / White) returns "kernel": ∂/∂params(k) in the order of params(k), and "theta":
-    the gradient against the flat θ of include/gpmi355.h (gp_logpdf_grad_sum), in place of "variance" / "scale"; wrt_x is not offered for it."""
+    the gradient against the flat θ of include/gpmi355.h (gp_logpdf_grad_sum; gp_logpdf_grad_sum_x with wrt_x), in place of "variance" / "scale"."""
     y = _check_y(fx, y)
     if y.ndim != 1:
         raise TypeError("logpdf_and_grad expects a vector of observations")
@@ -899,24 +910,26 @@ def logpdf_and_grad(fx: FiniteGP, y, wrt_x: bool = False) -> tuple:
     yv = m.arr(y)
     lp = np.empty(1, dtype=dt)
     if _is_composite(f.kernel):
-        if wrt_x:
-            raise NotImplementedError("∂/∂x of a composite kernel is not accelerated")
         ks, nf = m.ksum(f.kernel, px.d)
         dth = (C.c_double * max(len(nf.theta()), 1))()
         dnoise = np.empty(_dnoise_shape(nz, px.n), dtype=dt)
         dy = np.empty(px.n, dtype=dt)
-        check(ctx.lib.gp_logpdf_grad_sum(ctx.handle, C.byref(ks), C.byref(px), C.byref(nz), m.ptr(mean), yv.ctypes.data, lp.ctypes.data, dth,
-                                         dnoise.ctypes.data, dy.ctypes.data))
+        head = (ctx.handle, C.byref(ks), C.byref(px), C.byref(nz), m.ptr(mean), yv.ctypes.data, lp.ctypes.data, dth, dnoise.ctypes.data, dy.ctypes.data)
+        if wrt_x:
+            dxb = _dx_buffer(px, dt)
+            check(ctx.lib.gp_logpdf_grad_sum_x(*head, m.ptr(dxb)))
+        else:
+            check(ctx.lib.gp_logpdf_grad_sum(*head))
         gth = np.array(dth[:len(nf.theta())])
-        return lp[0], {"kernel": nf.chain(gth), "theta": gth, "noise": dnoise[0] if nz.kind == 0 else dnoise, "y": dy, "mean": -dy}
+        g = {"kernel": nf.chain(gth), "theta": gth, "noise": dnoise[0] if nz.kind == 0 else dnoise, "y": dy, "mean": -dy}
+        if wrt_x:
+            g["x"] = _dx_shaped(dxb, px, fx.x)
+        return lp[0], g
     dvar = C.c_double()
     dscale = (C.c_double * max(kk.nscale, 1))()
     dnoise = np.empty(_dnoise_shape(nz, px.n), dtype=dt)
     dy = np.empty(px.n, dtype=dt)
-    # ∂/∂x comes back in the ABI layout of the inputs: (n,) vector; ColVecs (N, D) C-order = D×N column-major; RowVecs (D, N)
-    dxb = None
-    if wrt_x:
-        dxb = np.empty((px.n,) if px.layout == 0 else ((px.n, px.d) if px.layout == 1 else (px.d, px.n)), dtype=dt)
+    dxb = _dx_buffer(px, dt) if wrt_x else None
     check(ctx.lib.gp_logpdf_grad(ctx.handle, C.byref(kk), C.byref(px), C.byref(nz), m.ptr(mean), yv.ctypes.data,
                                  lp.ctypes.data, C.byref(dvar), dscale, dnoise.ctypes.data, dy.ctypes.data, m.ptr(dxb)))
     sc = None
@@ -925,12 +938,8 @@ def logpdf_and_grad(fx: FiniteGP, y, wrt_x: bool = False) -> tuple:
     elif kk.nscale > 1:
         sc = np.array([dscale[i] for i in range(kk.nscale)])
     g = {"variance": dvar.value, "scale": sc, "noise": dnoise[0] if nz.kind == 0 else dnoise, "y": dy, "mean": -dy}
-    if wrt_x:  # the buffer comes back in the ABI layout the inputs were passed in: (n, d) for layout 1, (d, n) for layout 2; the result has the shape of x.X
-        if px.layout == 0:
-            g["x"] = dxb
-        else:
-            nd = dxb if px.layout == 1 else dxb.T                       # (N, D) view
-            g["x"] = np.ascontiguousarray(nd.T if isinstance(_as_input(fx.x), ColVecs) else nd)
+    if wrt_x:
+        g["x"] = _dx_shaped(dxb, px, fx.x)
     return lp[0], g
 
 

@@ -1398,7 +1398,7 @@ static int32_t predict_impl(gp_post* post, const gp_points* xs, const void* pm, 
     });
 }
 
-// logpdf value + gradient (see include/gpmi355.h gp_logpdf_grad; ks != NULL: gp_logpdf_grad_sum, ∂/∂θ into dtheta, no dx)
+// logpdf value + gradient (see include/gpmi355.h gp_logpdf_grad; ks != NULL: gp_logpdf_grad_sum / gp_logpdf_grad_sum_x, ∂/∂θ into dtheta)
 template <typename T>
 static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean,
                          const void* y, void* logpdf_out, double* dvar, double* dscale, void* dnoise, void* dy, void* dx,
@@ -1499,10 +1499,15 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
         if (dnoise && noise_dense(noise)) RC(dense_grad_out<T>(c, s, bufs, (const T*)Ci, ld, (const T*)post.alpha, n, (T*)dnoise));  // G = ½(ααᵀ − C⁻¹), n×n
         if (dx) {  // ∂/∂x: full-square pass (the mirrored C⁻¹ entry serves the tiles above the diagonal), 16 dimensions per launch
             HIPCHK(hipMemsetAsync(gx_v, 0, gx_b, s));
-            for (int p0 = 0; p0 < d; p0 += 16) {
-                hipLaunchKernelGGL(kgradx_kernel<T>, grid, dim3(256), 0, s, (const T*)Ci, ld, (const T*)post.xs, np, d, post.kern.kind,
-                                   (T)post.kern.variance, post.kern.nscale(), (const double*)sc_v, (const T*)post.alpha, n, (double*)gx_v, np, p0);
+            if (ks) {  // composite kernel: post.xs holds the raw inputs, D <= 16 (pack_ksum), one launch
+                launch_kgradx_sum<T>(grid, s, (const T*)Ci, ld, (const T*)post.xs, np, d, *ks, (const T*)post.alpha, n, (double*)gx_v, np);
                 HIPCHK(hipGetLastError());
+            } else {
+                for (int p0 = 0; p0 < d; p0 += 16) {
+                    hipLaunchKernelGGL(kgradx_kernel<T>, grid, dim3(256), 0, s, (const T*)Ci, ld, (const T*)post.xs, np, d, post.kern.kind,
+                                       (T)post.kern.variance, post.kern.nscale(), (const double*)sc_v, (const T*)post.alpha, n, (double*)gx_v, np, p0);
+                    HIPCHK(hipGetLastError());
+                }
             }
             HIPCHK(hipMemcpyAsync(gx_h.data(), gx_v, gx_b, hipMemcpyDeviceToHost, s));
         }
@@ -2243,7 +2248,7 @@ static int32_t posterior_fit_any(gp_ctx* c, const K* k, const gp_points* x, cons
     return 0;
 }
 
-// single kind: dvar / dscale / dx, dtheta NULL; composite: dtheta (one entry per θ entry), the other three NULL
+// single kind: dvar / dscale / dx, dtheta NULL; composite: dtheta (one entry per θ entry) and dx, dvar / dscale NULL
 template <class K>
 static int32_t logpdf_grad_any(gp_ctx* c, const K* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, void* logpdf_out,
                                double* dvar, double* dscale, void* dnoise, void* dy, void* dx, double* dtheta) {
@@ -2257,6 +2262,42 @@ static int32_t logpdf_grad_any(gp_ctx* c, const K* k, const gp_points* x, const 
     return by_dtype(rk.k.dtype, [&](auto t) {
         return grad_impl<decltype(t)>(c, &rk.k, x, noise, mean, y, logpdf_out, dvar, dscale, dnoise, dy, dx, rk.sum(), dtheta);
     });
+}
+
+// logdet(cov(fx)) and sqmahal(fx, Y) — the two terms logpdf adds up (src/finite_gp_projection.jl:306-311): `logdetcov` is not in
+// the reference's API by that name but `sqmahal` is (src/finite_gp_projection.jl:313-326), and `gradlogpdf` (:328-337) is −α of
+// the posterior fit.  Y may be NULL (ncols ignored): logdet only.  Outputs in the kernel's dtype; either may be NULL.
+template <class K>
+static int32_t logpdf_terms_any(gp_ctx* c, const K* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y, int64_t ldy,
+                                int32_t ncols, void* logdet_out, void* sqmahal_out) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    ResolvedKernel rk;
+    RC(check_fit_args(k, x, noise, rk));
+    if (Y) {
+        if (ncols < 1) return set_arg_err(8, "ncols must be >= 1");
+        if (ldy < x->n) return set_arg_err(7, "ldy < n");
+    } else if (sqmahal_out) {
+        return set_arg_err(6, "sqmahal needs Y");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    FitOut fo;
+    std::vector<char> zero;
+    if (!Y) {
+        // logdet only: the factorisation is all that is needed, but a multi-device fit verifies its result through the right-hand
+        // side that rides along ((K + Σy) α = δ on every row) — an all-zero δ would make that check vacuous (α = 0 whatever the
+        // factor holds).  A fixed pseudo-random probe in [−½, ½) rides instead; its sqmahal is discarded.
+        zero.assign((size_t)x->n * (rk.k.dtype == 0 ? 8 : 4), 0);
+        for (int64_t i = 0; i < x->n; ++i)
+            put(zero.data(), rk.k.dtype, (size_t)i, (double)(((uint32_t)i * 2654435761u >> 8) & 0xffffu) / 65536.0 - 0.5 + 1.0 / 131072.0);
+        ncols = 1;
+        ldy = x->n;
+    }
+    RC(fit_any(c, rk, x, noise, Y ? mean : nullptr, Y ? Y : (const void*)zero.data(), ldy, ncols, fo, nullptr, nullptr));
+    if (logdet_out) put(logdet_out, rk.k.dtype, 0, fo.logdet);
+    if (sqmahal_out)
+        for (int s = 0; s < ncols; ++s) put(sqmahal_out, rk.k.dtype, s, fo.sqmahal[s]);
+    return 0;
 }
 }  // extern "C++"
 
@@ -2290,39 +2331,18 @@ int32_t gp_logpdf_grad_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, cons
     return logpdf_grad_any(c, k, x, noise, mean, y, logpdf_out, nullptr, nullptr, dnoise, dy, nullptr, dtheta);
 }
 
-// logdet(cov(fx)) and sqmahal(fx, Y) — the two terms logpdf adds up (src/finite_gp_projection.jl:306-311): `logdetcov` is not in
-// the reference's API by that name but `sqmahal` is (src/finite_gp_projection.jl:313-326), and `gradlogpdf` (:328-337) is −α of
-// the posterior fit.  Y may be NULL (ncols ignored): logdet only.  Outputs in the kernel's dtype; either may be NULL.
+int32_t gp_logpdf_grad_sum_x(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y,
+                             void* logpdf_out, double* dtheta, void* dnoise, void* dy, void* dx) {
+    return logpdf_grad_any(c, k, x, noise, mean, y, logpdf_out, nullptr, nullptr, dnoise, dy, dx, dtheta);
+}
+
 int32_t gp_logpdf_terms(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean,
                         const void* Y, int64_t ldy, int32_t ncols, void* logdet_out, void* sqmahal_out) {
-    Guard gd(c);
-    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
-    ResolvedKernel rk;
-    RC(check_fit_args(k, x, noise, rk));
-    if (Y) {
-        if (ncols < 1) return set_arg_err(8, "ncols must be >= 1");
-        if (ldy < x->n) return set_arg_err(7, "ldy < n");
-    } else if (sqmahal_out) {
-        return set_arg_err(6, "sqmahal needs Y");
-    }
-    HIPCHK(hipSetDevice(c->device));
-    FitOut fo;
-    std::vector<char> zero;
-    if (!Y) {
-        // logdet only: the factorisation is all that is needed, but a multi-device fit verifies its result through the right-hand
-        // side that rides along ((K + Σy) α = δ on every row) — an all-zero δ would make that check vacuous (α = 0 whatever the
-        // factor holds).  A fixed pseudo-random probe in [−½, ½) rides instead; its sqmahal is discarded.
-        zero.assign((size_t)x->n * (k->dtype == 0 ? 8 : 4), 0);
-        for (int64_t i = 0; i < x->n; ++i)
-            put(zero.data(), k->dtype, (size_t)i, (double)(((uint32_t)i * 2654435761u >> 8) & 0xffffu) / 65536.0 - 0.5 + 1.0 / 131072.0);
-        ncols = 1;
-        ldy = x->n;
-    }
-    RC(fit_any(c, rk, x, noise, Y ? mean : nullptr, Y ? Y : (const void*)zero.data(), ldy, ncols, fo, nullptr, nullptr));
-    if (logdet_out) put(logdet_out, k->dtype, 0, fo.logdet);
-    if (sqmahal_out)
-        for (int s = 0; s < ncols; ++s) put(sqmahal_out, k->dtype, s, fo.sqmahal[s]);
-    return 0;
+    return logpdf_terms_any(c, k, x, noise, mean, Y, ldy, ncols, logdet_out, sqmahal_out);
+}
+int32_t gp_logpdf_terms_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y, int64_t ldy,
+                            int32_t ncols, void* logdet_out, void* sqmahal_out) {
+    return logpdf_terms_any(c, k, x, noise, mean, Y, ldy, ncols, logdet_out, sqmahal_out);
 }
 
 // ---- argument checks the exact and the sparse posterior share (argi: position of the first argument checked; the others follow it) ----

@@ -2593,7 +2593,131 @@ __global__ __launch_bounds__(256) void kgrad_sum_kernel(const T* __restrict__ Ci
     if (tid < NP && p0 + tid < k.nth) atomicAdd(g + 2 + p0 + tid, red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid]);
 }
 
+// acc[p] += w · ∂k/∂t_p at the differences t, k = Σ_t σ_t² Π_f κ_f:  ∂k/∂t_p = Σ_t σ_t² Σ_f (Π_{g≠f} κ_g) ∂κ_f/∂t_p, the product over the other factors as
+// prefix × suffix with the κ_f in this thread's LDS slots, as ksum_grad.  With c_p the factor's transform (1, s or v_p):
+//   kinds 0..3 and RQ: ∂κ_f/∂t_p = ∂κ/∂d² · 2 c_p² t_p (∂κ/∂d² as ksum_factor_grad; Matern12 at d = 0 taken as 0);  White: 0;
+//   Periodic (u_p = c_p t_p): ∂κ_f/∂t_p = −κ (π/2) sinpi(2u_p)/r_p² · c_p.
+// Factors without a transform or with a ScaleTransform share the direction t: their coefficients add up in one scalar, applied once at the end.
+template <typename T, int DR>
+__device__ __forceinline__ void ksum_gradx(const KSum& k, const T (&t)[DR], int d, double w, double (&acc)[DR], double (*kf)[256], int tid) {
+    T r2;
+    bool eq;
+    ksum_r2<T, DR>(t, r2, eq);
+    double iso = 0.0;
+    for (int tt = 0; tt < k.nterms; ++tt) {
+        const int f0 = k.t0[tt], nf = k.t0[tt + 1] - f0;
+        for (int j = 0; j < nf; ++j) kf[j][tid] = (double)ksum_factor<T, DR>(k, f0 + j, t, r2, eq, d);
+        const double wv = w * k.th[k.tv[tt]];
+        double pre = 1.0;
+        for (int j = 0; j < nf; ++j) {
+            double suf = 1.0;
+            for (int i = j + 1; i < nf; ++i) suf *= kf[i][tid];
+            const double kj = kf[j][tid], c = wv * pre * suf;
+            pre *= kj;
+            const int f = f0 + j, kind = k.kind[f], ns = k.ns[f];
+            if (kind == 6) continue;
+            if (kind == 4) {
+                const double ck = -c * kj * 1.5707963267948966192;
+#pragma unroll
+                for (int p = 0; p < DR; ++p)
+                    if (p < d) {
+                        const T sc = ns == 0 ? T(1) : (T)k.th[k.so[f] + (ns == 1 ? 0 : p)];
+                        const double r = k.th[k.po[f] + p];
+                        acc[p] += ck * (double)sinpi_t(T(2) * sc * t[p]) * (double)sc / (r * r);
+                    }
+                continue;
+            }
+            const T d2 = ksum_d2<T, DR>(k, f, t, r2, d);
+            double dk;
+            if (kind == 5) {
+                dk = -kj / (2.0 * (1.0 + (double)d2 / (2.0 * k.th[k.po[f]])));
+            } else {
+                T kk, dkt;
+                kappa_and_dr2<T>(kind, d2, kk, dkt);
+                dk = (double)dkt;
+            }
+            const double c2 = 2.0 * c * dk;
+            if (ns == 0) {
+                iso += c2;
+            } else if (ns == 1) {
+                const double s = k.th[k.so[f]];
+                iso += c2 * s * s;
+            } else {
+#pragma unroll
+                for (int p = 0; p < DR; ++p)
+                    if (p < d) {
+                        const double v = k.th[k.so[f] + p];
+                        acc[p] += c2 * v * v * (double)t[p];
+                    }
+            }
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < DR; ++p) acc[p] += iso * (double)t[p];
+}
+
+// gx[p][j] += ∂logpdf/∂x_jp = Σ_i W_ij ∂k/∂t_p(x_j − x_i), W = α αᵀ − C⁻¹ — the composite counterpart of kgradx_kernel (RAW inputs, dimension-major, like
+// the other *_sum kernels; gx: double [d][ldg]).  One 128×128 tile of the FULL square per workgroup, the mirrored entry of the lower −C⁻¹ for the tiles above
+// the diagonal.  W is symmetric and ∂k/∂t is odd in t, so a thread sums DOWN its column over the differences t = x_i − x_j and flips the sign once at the end:
+// one column and 64 of the tile's rows per thread (the row inputs and α_i are LDS broadcasts, the sums acc[DR] stay in registers under static indices, the
+// element body has one call site), the two row halves meet in LDS, one fp64 atomicAdd per (column, p) and tile.  No per-row wave reductions.
+template <typename T, int DR>
+__global__ __launch_bounds__(256) void kgradx_sum_kernel(const T* __restrict__ Cinv, long ld, const T* __restrict__ x, long ldx, int d, const KSum k,
+                                                          const T* __restrict__ alpha, long n, double* __restrict__ gx, long ldg) {
+    const int m0 = blockIdx.y * 128, n0 = blockIdx.x * 128;
+    __shared__ T xi[DR][128];
+    __shared__ double ai[128];
+    __shared__ double kf[KSum::MAXFT][256];
+    __shared__ double red[DR][128];
+    const int tid = threadIdx.x, col = tid & 127, half = tid >> 7;
+    for (int e = tid; e < DR * 128; e += 256) {
+        const int dd = e / 128, i = e % 128;
+        xi[dd][i] = dd < d ? x[(long)dd * ldx + m0 + i] : T(0);
+    }
+    if (tid < 128) ai[tid] = m0 + tid < n ? (double)alpha[m0 + tid] : 0.0;
+    const long gj = n0 + col;
+    T xj[DR];
+    double acc[DR];
+#pragma unroll
+    for (int p = 0; p < DR; ++p) {
+        xj[p] = p < d ? x[(long)p * ldx + gj] : T(0);
+        acc[p] = 0.0;
+    }
+    const double aj = gj < n ? (double)alpha[gj] : 0.0;
+    __syncthreads();
+    if (gj < n) {
+        for (int rr = 0; rr < 64; ++rr) {
+            const int row = half * 64 + rr;
+            const long gi = m0 + row;
+            if (gi >= n) break;  // wave-uniform
+            if (gi == gj) continue;
+            T t[DR];
+#pragma unroll
+            for (int p = 0; p < DR; ++p) t[p] = xi[p][row] - xj[p];
+            const double wgt = ai[row] * aj + (double)(gi > gj ? Cinv[gi * ld + gj] : Cinv[gj * ld + gi]);  // Cinv holds −C⁻¹
+            ksum_gradx<T, DR>(k, t, d, wgt, acc, kf, tid);
+        }
+    }
+    if (half == 1) {
+#pragma unroll
+        for (int p = 0; p < DR; ++p) red[p][col] = acc[p];
+    }
+    __syncthreads();
+    if (half == 0 && gj < n) {
+#pragma unroll
+        for (int p = 0; p < DR; ++p)
+            if (p < d) atomicAdd(gx + (long)p * ldg + gj, -(acc[p] + red[p][col]));
+    }
+}
+
 // D -> instance (1 / 4 / 16); the host refuses D > 16 for composite kernels
+template <typename T>
+static inline void launch_kgradx_sum(dim3 grid, hipStream_t s, const T* Cinv, long ld, const T* x, long ldx, int d, const KSum& k, const T* alpha, long n,
+                                     double* gx, long ldg) {
+    if (d <= 1) hipLaunchKernelGGL((kgradx_sum_kernel<T, 1>), grid, dim3(256), 0, s, Cinv, ld, x, ldx, d, k, alpha, n, gx, ldg);
+    else if (d <= 4) hipLaunchKernelGGL((kgradx_sum_kernel<T, 4>), grid, dim3(256), 0, s, Cinv, ld, x, ldx, d, k, alpha, n, gx, ldg);
+    else hipLaunchKernelGGL((kgradx_sum_kernel<T, 16>), grid, dim3(256), 0, s, Cinv, ld, x, ldx, d, k, alpha, n, gx, ldg);
+}
 template <typename T>
 static inline void launch_kmat_sum(dim3 grid, hipStream_t s, T* out, long ld, const T* xr, long ldxr, const T* xc, long ldxc, int d, const KSum& k,
                                    const T* noise, long nr_valid, long nc_valid, int sym, GridMap g) {

@@ -443,7 +443,7 @@ end
 
 function logpdf_terms(fx::FiniteGP{<:HipGP}, Y::Union{Nothing,AbstractVecOrMat{<:Real}}; logdet::Bool, sq::Bool)
     a = marshal(fx, Y === nothing ? input_eltype(fx.x) : eltype(Y))
-    (a === nothing || haskey(a, :ks)) && return nothing   # gp_logpdf_terms is single-kind: composite kernels take the stock path
+    a === nothing && return nothing
     T = a.T
     Yd = Y === nothing ? nothing : Matrix{T}(reshape(Y, size(Y, 1), :))
     Yd === nothing || size(Yd, 1) == length(fx) || throw(DimensionMismatch("length(fx) = $(length(fx)) but Y has $(size(Yd, 1)) rows"))
@@ -451,10 +451,17 @@ function logpdf_terms(fx::FiniteGP{<:HipGP}, Y::Union{Nothing,AbstractVecOrMat{<
     out = Vector{T}(undef, Yd === nothing ? 1 : size(Yd, 2))
     mptr = a.m === nothing ? C_NULL : pointer(a.m)
     GC.@preserve a Yd out begin
-        check(ccall((:gp_logpdf_terms, libgpmi355), Int32,
-            (Ptr{Cvoid}, Ref{CKernel}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}),
-            fx.f.ctx.handle, a.ck, a.cx, a.cn, mptr, Yd === nothing ? C_NULL : pointer(Yd), length(fx),
-            Yd === nothing ? 0 : size(Yd, 2), logdet ? Base.unsafe_convert(Ptr{Cvoid}, ld) : C_NULL, sq ? pointer(out) : C_NULL))
+        if haskey(a, :ks)   # composite kernel
+            check(ccall((:gp_logpdf_terms_sum, libgpmi355), Int32,
+                (Ptr{Cvoid}, Ref{CKSum}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}),
+                fx.f.ctx.handle, a.ks, a.cx, a.cn, mptr, Yd === nothing ? C_NULL : pointer(Yd), length(fx),
+                Yd === nothing ? 0 : size(Yd, 2), logdet ? Base.unsafe_convert(Ptr{Cvoid}, ld) : C_NULL, sq ? pointer(out) : C_NULL))
+        else
+            check(ccall((:gp_logpdf_terms, libgpmi355), Int32,
+                (Ptr{Cvoid}, Ref{CKernel}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}),
+                fx.f.ctx.handle, a.ck, a.cx, a.cn, mptr, Yd === nothing ? C_NULL : pointer(Yd), length(fx),
+                Yd === nothing ? 0 : size(Yd, 2), logdet ? Base.unsafe_convert(Ptr{Cvoid}, ld) : C_NULL, sq ? pointer(out) : C_NULL))
+        end
     end
     return (ld[], out)
 end
@@ -493,7 +500,7 @@ end
 function logpdf_and_grad(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}; wrt_x::Bool=true)
     a = marshal(fx, eltype(y))
     a === nothing && throw(ArgumentError("kernel / noise form is not accelerated"))
-    haskey(a, :ks) && return logpdf_and_grad_sum(fx, y, a)
+    haskey(a, :ks) && return logpdf_and_grad_sum(fx, y, a; wrt_x=wrt_x)
     T = a.T
     yv = Vector{T}(y)
     lp = Ref{T}(zero(T)); dvar = Ref{Float64}(0.0)
@@ -512,27 +519,35 @@ function logpdf_and_grad(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}; wrt_x
         x=wrt_x ? dx : nothing)
 end
 
-# composite kernel (gp_logpdf_grad_sum): `theta` = ∂/∂θ of the C ABI, `kernel` = ∂/∂(the tree's own parameters) in sum_walk's order; no ∂/∂x
-function logpdf_and_grad_sum(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}, a)
+# composite kernel: `theta` = ∂/∂θ of the C ABI, `kernel` = ∂/∂(the tree's own parameters) in sum_walk's order; with wrt_x the call is
+# gp_logpdf_grad_sum_x and `x` = ∂/∂x in the container layout of the inputs, otherwise gp_logpdf_grad_sum
+function logpdf_and_grad_sum(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}, a; wrt_x::Bool=true)
     T = a.T
     yv = Vector{T}(y)
     lp = Ref{T}(zero(T))
     dθ = zeros(Float64, length(sum_theta(a.P, a.terms)))
     dnoise = dnoise_buffer(a.cn, T, length(yv))
     dy = Vector{T}(undef, length(yv))
+    dx = wrt_x ? similar(a.xbuf) : T[]
     mptr = a.m === nothing ? C_NULL : pointer(a.m)
-    GC.@preserve a yv dθ dnoise dy begin
-        check(ccall((:gp_logpdf_grad_sum, libgpmi355), Int32,
-            (Ptr{Cvoid}, Ref{CKSum}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{T}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}),
-            fx.f.ctx.handle, a.ks, a.cx, a.cn, mptr, yv, lp, dθ, dnoise, dy))
+    GC.@preserve a yv dθ dnoise dy dx begin
+        if wrt_x
+            check(ccall((:gp_logpdf_grad_sum_x, libgpmi355), Int32,
+                (Ptr{Cvoid}, Ref{CKSum}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{T}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                fx.f.ctx.handle, a.ks, a.cx, a.cn, mptr, yv, lp, dθ, dnoise, dy, pointer(dx)))
+        else
+            check(ccall((:gp_logpdf_grad_sum, libgpmi355), Int32,
+                (Ptr{Cvoid}, Ref{CKSum}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{T}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}),
+                fx.f.ctx.handle, a.ks, a.cx, a.cn, mptr, yv, lp, dθ, dnoise, dy))
+        end
     end
-    return lp[], (theta=dθ, kernel=sum_chain(a.P, a.terms, dθ), noise=a.cn.kind == 0 ? dnoise[1] : dnoise, y=dy, mean=-dy, x=nothing)
+    return lp[], (theta=dθ, kernel=sum_chain(a.P, a.terms, dθ), noise=a.cn.kind == 0 ? dnoise[1] : dnoise, y=dy, mean=-dy, x=wrt_x ? dx : nothing)
 end
 
 # ---- reverse-mode rule: Zygote / any ChainRules-based AD differentiates THROUGH the ccall -----------------------------------
 # The reference's users differentiate logpdf by AD (test/finite_gp_projection.jl:152-178, test/mean_function.jl:38-56,
 # examples/1-mauna-loa/script.jl:201-240); a ccall is opaque to AD, so the accelerated logpdf carries its own pullback built
-# from gp_logpdf_grad.  Tangents are structural, mirroring how `descriptor` walks the kernel:
+# from gp_logpdf_grad (gp_logpdf_grad_sum_x for a composite kernel).  Tangents are structural, mirroring how `descriptor` walks the kernel:
 #   ScaledKernel.σ²  (1-vector)  <- ∂/∂variance · (total variance / σ²)      TransformedKernel.transform.s / .v  <- ∂/∂scale
 #   ConstMean.c <- Σ_i α_i        FiniteGP.Σy (Diagonal{Fill} value / Diagonal diag) <- ∂/∂σ² / ½(α_i² − C⁻¹_ii)        y <- −α
 #   x (Vector / ColVecs.X / RowVecs.X) <- ∂/∂x, the input gradient a deep-kernel model back-propagates into its feature map
@@ -606,9 +621,7 @@ function ChainRulesCore.rrule(config::RuleConfig{>:HasReverseMode}, ::typeof(Dis
         dk = desc === nothing ? sum_tangent(gp.kernel, Δr .* g.kernel, Ref(1)) : kernel_tangent(gp.kernel, Δr * g.variance, desc[2], Δr .* g.scale)
         dgp = Tangent{typeof(gp)}(; mean=mean_tangent(gp.mean, Δr .* g.mean), kernel=dk)
         df = Tangent{typeof(fx.f)}(; gp=dgp, ctx=NoTangent())
-        # composite kernels: ∂/∂x is not computed on the device — refused loudly (a NoTangent would claim x is not differentiable)
-        dx = g.x === nothing ? ChainRulesCore.@not_implemented("HipGPs: ∂/∂x of a composite kernel is not accelerated") : input_tangent(fx.x, g.x, Δr)
-        dfx = Tangent{typeof(fx)}(; f=df, x=dx, Σy=noise_tangent(fx.Σy, Δr .* g.noise))
+        dfx = Tangent{typeof(fx)}(; f=df, x=input_tangent(fx.x, g.x, Δr), Σy=noise_tangent(fx.Σy, Δr .* g.noise))
         return NoTangent(), dfx, Δr .* g.y
     end
     return lp, logpdf_hip_pullback

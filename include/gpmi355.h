@@ -363,7 +363,10 @@ int32_t gp_logpdf_grad(gp_ctx* ctx, const gp_kernel* k, const gp_points* x, cons
  * "deterministic" = 1 covers composite fits as well.  On a multi-device ctx these calls run on the single-device engine of the ctx's
  * first device (the 2-D block-cyclic driver is single-kind).
  * gp_logpdf_grad_sum: dtheta_out (fp64, one entry per θ entry in the order documented at gp_ksum) = ∂logpdf/∂θ; dnoise_out and dy_out
- * as in gp_logpdf_grad.  ∂/∂x is not offered for composite kernels, nor is gp_logpdf_terms; VFE / DTC stay single-kind. */
+ * as in gp_logpdf_grad.  gp_logpdf_grad_sum_x is the same call with gp_logpdf_grad's dx_out behind it (n×d entries ∂/∂x in the container
+ * layout of x, kernel dtype, the prior mean taken as constant in x; kgradx_sum_kernel: one more pass over the full square of C⁻¹); with
+ * dx_out NULL it does exactly what gp_logpdf_grad_sum does.  A Matern12 factor's derivative at coincident inputs is taken as 0.
+ * gp_logpdf_terms_sum: the contract of gp_logpdf_terms for a composite kernel.  VFE / DTC stay single-kind. */
 int32_t gp_kernelmatrix_sum(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, const gp_points* y_or_null, void* out);
 int32_t gp_logpdf_sum(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null,
                       const void* Y, int64_t ldy, int32_t ncols, void* out);
@@ -372,6 +375,11 @@ int32_t gp_posterior_fit_sum(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, 
 int32_t gp_logpdf_grad_sum(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null,
                            const void* y, void* logpdf_out, double* dtheta_out_or_null, void* dnoise_out_or_null,
                            void* dy_out_or_null);
+int32_t gp_logpdf_grad_sum_x(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null,
+                             const void* y, void* logpdf_out, double* dtheta_out_or_null, void* dnoise_out_or_null,
+                             void* dy_out_or_null, void* dx_out_or_null);
+int32_t gp_logpdf_terms_sum(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null,
+                            const void* Y_or_null, int64_t ldy, int32_t ncols, void* logdet_out_or_null, void* sqmahal_out_or_null);
 
 /* ---- many small exact GPs in one call ------------------------------------------------------------------------------------------ */
 /* nb independent problems (k_b, x_b, Σy_b, m_b, y_b), each with its own size n_b: logpdf_out[b] = logpdf(f_b(x_b, Σy_b), y_b)
