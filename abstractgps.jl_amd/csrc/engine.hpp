@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/gpmi355.h"
+#include "bulk_plan.hpp"  // host-only plan of a grouped bulk update + the device table entry GrpProb
 
 namespace gpmi {
 // 2D block-cyclic bookkeeping shared by kmat and gemm: local absolute index -> global index.
@@ -145,8 +146,16 @@ struct gp_ctx {
                            // on the main stream, so that each launch's last partial round of workgroups is filled by the other — C5 +0.4…0.7 ms with the priority,
                            // −0.45 ms with both at equal priority (profiles/r6/c5_ab*.jsonl): the single-stream pass has no idle tail to fill
     long vfe_inv_nb = 512; // VFE prelude: inv(L_z) with the inverse diagonal blocks of this width built in one batched launch sequence (0: 64-wide leaves)
-    long strassen_min_rows = 16384;  // fp64 fits: smallest side of an off-diagonal block of the bulk trailing update (and of gpd_gemm_nt) that runs as seven
+    long strassen_min_rows = 8192;   // fp64 fits: smallest side of an off-diagonal block of the bulk trailing update (and of gpd_gemm_nt) that runs as seven
                                  // half-size products (one level of Strassen: gpmi355.hip gemm_nt_strassen / syrk_lower_split); 0 = never
+    int strassen_group = 1;          // 1: a bulk update that is split at all (and gpd_gemm_nt's lower SYRK) runs as FOUR grouped launches over the tiles of all its pieces
+                                     // (bulk_plan.hpp, kernels.hpp gemm_nt_grp_kernel) instead of four launches per Strassen block and one per classical piece.
+    long strassen_group_min_rows = 8192;  // The grouped form is taken when the side m of the update is at least this; below it, with strassen_group = 0 and with
+                                          // "xcd_swizzle" set (the grouped kernel has no super-tile order) the per-block launch sequence runs unchanged.
+    void* plan_pin = nullptr;        // page-locked staging of the problem tables of one call (uploaded by ONE async copy; reused once plan_ev has passed)
+    size_t plan_pin_bytes = 0;
+    hipEvent_t plan_ev = nullptr;
+    bool grp_pad_set = false;
     int xcd_swizzle = 0;   // XCD-aware super-tile order of the MFMA gemm workgroups
     long xcd_min_tiles = 256;
     long ldpad = 32;       // elements of padding per row: de-aliases power-of-two strides across HBM channels
@@ -165,6 +174,7 @@ struct gp_ctx {
         hipEvent_t a, b;
         double flops, bytes;
         long M, N, K;
+        long nprob, ntiles;  // a grouped launch (gemm_nt_grp_kernel): its problems and tiles, M = N = 0 and K = that of its longest problems; 0, 0: a single-problem launch
         int stream;  // 0 main, 1 panel
     };
     std::vector<GemmRec> gemm_recs;

@@ -136,6 +136,8 @@ void ctx_unref(gp_ctx* c) {
         if (e) (void)hipEventDestroy(e);
     if (c->info_dev) (void)hipFree(c->info_dev);
     if (c->pin) (void)hipHostFree(c->pin);
+    if (c->plan_pin) (void)hipHostFree(c->plan_pin);
+    if (c->plan_ev) (void)hipEventDestroy(c->plan_ev);
     if (c->ticket_dev) (void)hipFree(c->ticket_dev);
     if (c->w_ws) (void)hipFree(c->w_ws);
     if (c->scal_dev) (void)hipFree(c->scal_dev);
@@ -234,14 +236,7 @@ int32_t ctx_prime_stream(gp_ctx* c, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------
 // launches
 // ------------------------------------------------------------------------------------------------
-static double lower_count(long M, long N, long row0, long col0) {
-    // number of (r, c) in [row0,row0+M) × [col0,col0+N) with c <= r  (closed form)
-    const long a = row0 - col0 + 1;  // count in the first row before clamping to [0, N]
-    const long i1 = std::min(std::max(1 - a, 0L), M);           // rows contributing 0
-    const long i2 = std::max(i1, std::min(std::max(N - a, 0L), M));  // rows from i2 on contribute N
-    const double mid = (double)(i2 - i1) * (double)a + 0.5 * (double)(i1 + i2 - 1) * (double)(i2 - i1);
-    return mid + (double)(M - i2) * (double)N;
-}
+// (lower_count: bulk_plan.hpp)
 
 template <typename T, typename CT = T>
 static int32_t launch_gemm(gp_ctx* c, hipStream_t s, CT* C, long ldc, const T* A, long lda, const T* B, long ldb,
@@ -367,16 +362,12 @@ struct StrassenWs {  // the ten sum panels, rows of K/2 + ldpad elements (the pa
     double* p = nullptr;
     size_t elems = 0;
 };
-static size_t strassen_ws_elems(const gp_ctx* c, long M, long N, long K) { return (size_t)5 * (size_t)(M / 2 + N / 2) * (size_t)(K / 2 + c->ldpad); }
+// (the shape rules live in bulk_plan.hpp: the plan of a grouped update and the launch sequence below split at the same points)
+static size_t strassen_ws_elems(const gp_ctx* c, long M, long N, long K) { return strassen_ws_rule(c->ldpad, M, N, K); }
 // shapes the Strassen form takes: quadrants of whole 128×128 tiles, whole k steps per half, operand rows movable as 16-byte pieces
-static bool strassen_shape(const gp_ctx* c, long M, long N, long K) {
-    return c->strassen_min_rows > 0 && std::min(M, N) >= std::max(256L, c->strassen_min_rows) && M % 256 == 0 && N % 256 == 0 && K % 32 == 0;
-}
+static bool strassen_shape(const gp_ctx* c, long M, long N, long K) { return strassen_shape_rule(c->strassen_min_rows, M, N, K); }
 // side of the off-diagonal block the lower SYRK of side m is split at (multiple of 256); 0: no split
-static long strassen_split(const gp_ctx* c, long m, long K) {
-    const long h = (m / 2) / 256 * 256;
-    return strassen_shape(c, h, h, K) ? h : 0;
-}
+static long strassen_split(const gp_ctx* c, long m, long K) { return strassen_split_rule(c->strassen_min_rows, m, K); }
 
 static int32_t gemm_nt_strassen(gp_ctx* c, hipStream_t s, const StrassenWs& ws, double* C, long ldc, const double* A, long lda, const double* B, long ldb,
                                 long M, long N, long K) {
@@ -435,6 +426,104 @@ static int32_t syrk_lower_split(gp_ctx* c, hipStream_t s, const StrassenWs& ws, 
 // workspace of the above for a SYRK of side m (its largest Strassen block has at most m/2 + 255 rows and m/2 columns); 0 bytes: nothing is split
 static size_t syrk_split_ws_elems(const gp_ctx* c, long m, long K) {
     return strassen_split(c, m, K) ? strassen_ws_elems(c, m / 2 + 256, m / 2 + 256, K) : 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Grouped form of a bulk update ("strassen_group", "strassen_group_min_rows"; bulk_plan.hpp): the sums of every Strassen block, then FOUR launches of
+// gemm_nt_grp_kernel over the tiles of all pieces of the update.  The tables of all grouped updates of a call are built before its first launch and
+// travel in one async copy from page-locked memory.  In steady state no host wait lands between the Gram assembly and the first panel or inside the panel loop;
+// the FIRST call on a ctx (and a later call with larger tables) allocates the page-locked staging buffer at that point, once.  "xcd_swizzle" keeps the per-block
+// sequence: the grouped kernel enumerates row-major / compact_tile only.
+// ------------------------------------------------------------------------------------------------
+static bool group_applies(const gp_ctx* c, long m, long K, long ldp, const double* P) {
+    return c->strassen_group && !c->xcd_swizzle && m >= c->strassen_group_min_rows && strassen_split(c, m, K) != 0 && ldp % 2 == 0 && ((uintptr_t)P & 15) == 0;
+}
+struct GroupedUpdate {
+    BulkPlan plan;
+    const double* P = nullptr;
+    size_t tab0[4] = {0, 0, 0, 0};  // first entry of launch l in the call's table
+};
+struct PlanTables {
+    std::vector<GroupedUpdate> upd;
+    std::vector<GrpProb> host;
+    size_t ws_elems = 0;  // the updates of a call are ordered on one stream and share the workspace: the largest plan's
+    GrpProb* dev = nullptr;
+    void add(const gp_ctx* c, long mrows, long m, long K, long row0, long ldc, const double* P, long ldp) {
+        GroupedUpdate u;
+        u.plan = bulk_plan_build(mrows, m, K, row0, ldc, ldp, c->strassen_min_rows, c->ldpad);
+        u.P = P;
+        ws_elems = std::max(ws_elems, u.plan.ws_elems);
+        upd.push_back(std::move(u));
+    }
+    // the table entries (absolute pointers) and their upload on stream s, in front of everything that reads them
+    int32_t upload(gp_ctx* c, hipStream_t s, DevBufs& bufs, const std::vector<double*>& Cs, const double* ws) {
+        for (size_t i = 0; i < upd.size(); ++i)
+            for (int l = 0; l < 4; ++l) {
+                upd[i].tab0[l] = host.size();
+                for (const PlanProb& e : upd[i].plan.list[l]) host.push_back(plan_entry(upd[i].plan, e, Cs[i], upd[i].P, ws));
+            }
+        if (host.empty()) return 0;
+        const size_t bytes = host.size() * sizeof(GrpProb);
+        void* p = nullptr;
+        RC(bufs.get(bytes, &p));
+        dev = (GrpProb*)p;
+        if (!c->plan_ev) HIPCHK(hipEventCreateWithFlags(&c->plan_ev, hipEventDisableTiming));
+        HIPCHK(hipEventSynchronize(c->plan_ev));  // the previous call's copy out of the staging buffer (long done: its call has returned its results)
+        if (c->plan_pin_bytes < bytes) {
+            if (c->plan_pin) (void)hipHostFree(c->plan_pin);
+            c->plan_pin = nullptr;
+            c->plan_pin_bytes = 0;
+            HIPCHK(hipHostMalloc(&c->plan_pin, bytes + bytes / 4 + 4096, hipHostMallocDefault));
+            c->plan_pin_bytes = bytes + bytes / 4 + 4096;
+        }
+        memcpy(c->plan_pin, host.data(), bytes);
+        HIPCHK(hipMemcpyAsync(dev, c->plan_pin, bytes, hipMemcpyHostToDevice, s));
+        HIPCHK(hipEventRecord(c->plan_ev, s));
+        return 0;
+    }
+};
+
+// one grouped launch: the tiles [0, ntiles) of table entries [tab, tab + nprob)
+static int32_t launch_gemm_grp(gp_ctx* c, hipStream_t s, const GrpProb* tab, long nprob, long ntiles, double flops, double bytes, long K) {
+    if (nprob <= 0 || ntiles <= 0) return 0;
+    gp_ctx::GemmRec rec{};
+    const bool timed = c->time_kernels != 0;
+    if (timed) {
+        RC(ctx_event(c, &rec.a, true));
+        RC(ctx_event(c, &rec.b, true));
+        rec.flops = flops;
+        rec.bytes = bytes;
+        rec.M = 0; rec.N = 0; rec.K = K;  // no single shape: the problems and tiles are recorded instead (GPMI_DUMP_GEMM prints them)
+        rec.nprob = nprob; rec.ntiles = ntiles;
+        rec.stream = (s == c->sp);
+        HIPCHK(hipEventRecord(rec.a, s));
+    }
+    const long pad = c->gemm_pad_user ? c->gemm_pad_lds : 0;  // "gemm_pad_lds" applies as in launch_gemm
+    if (pad > 0 && !c->grp_pad_set) {
+        HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_grp_kernel<double, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 32768));
+        HIPCHK(hipFuncSetAttribute((const void*)gemm_nt_grp_kernel<double, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 32768));
+        c->grp_pad_set = true;
+    }
+    if (c->gemm_pipe) hipLaunchKernelGGL((gemm_nt_grp_kernel<double, 1>), dim3((unsigned)ntiles), dim3(256), (size_t)pad, s, tab, (int)nprob);
+    else hipLaunchKernelGGL((gemm_nt_grp_kernel<double, 0>), dim3((unsigned)ntiles), dim3(256), (size_t)pad, s, tab, (int)nprob);
+    HIPCHK(hipGetLastError());
+    if (timed) {
+        HIPCHK(hipEventRecord(rec.b, s));
+        c->gemm_recs.push_back(rec);
+    }
+    return 0;
+}
+
+static int32_t run_grouped(gp_ctx* c, hipStream_t s, const PlanTables& T, size_t i, double* ws) {
+    const GroupedUpdate& u = T.upd[i];
+    const BulkPlan& p = u.plan;
+    for (const PlanSums& j : p.sums)  // P is not written by the update: every block's sums go first, each into its own slice
+        hipLaunchKernelGGL(strassen_sums_kernel<double>, dim3((unsigned)((j.rh * (j.kh / 2) + 255) / 256)), dim3(256), 0, s, u.P + j.x_off, p.ldp, (int)j.rh, (int)j.kh,
+                           (int)p.lds, j.side, ws + j.s_off, j.pstride);
+    HIPCHK(hipGetLastError());
+    for (int l = 0; l < 4; ++l)
+        RC(launch_gemm_grp(c, s, T.dev + u.tab0[l], (long)p.list[l].size(), p.ntiles[l], p.flops[l], p.bytes[l], p.list[l].empty() ? 0 : p.list[l].front().K));
+    return 0;
 }
 
 static long split_half(long n) {  // largest multiple of 64 that is <= n/2 (>= 64)
@@ -776,15 +865,37 @@ static int32_t potrf_full_la(gp_ctx* c, T* A, long lda, long np, long mtot, int*
     const bool la = c->lookahead != 0 && np >= c->lookahead_min_n;
     hipStream_t sM = c->sm, sP = la ? c->sp : c->sm;
     hipEvent_t ev_u1 = nullptr, ev_panel = nullptr;
-    StrassenWs ws;  // one set of sum panels per fit, sized for the first (largest) bulk update; every launch that touches it is ordered on the main stream
+    StrassenWs ws;  // one workspace of sum panels per fit, sized for the update that needs most; every launch that touches it is ordered on the main stream
+    PlanTables tabs;          // the grouped bulk updates of the fit, planned and uploaded before the first panel
+    std::vector<long> gidx;   // per panel step: index into tabs.upd, −1: the per-block launch sequence
     if constexpr (std::is_same<T, double>::value) {
-        const long m2 = np - 2 * nb;
-        const size_t el = (bufs && m2 > 0) ? syrk_split_ws_elems(c, m2, nb) : 0;
-        if (el) {
-            void* p = nullptr;
-            RC(bufs->get(sizeof(double) * el, &p));
-            ws.p = (double*)p;
-            ws.elems = el;
+        if (bufs) {
+            size_t el = 0;
+            std::vector<double*> Cs;
+            for (long k = 0; k < np; k += nb) {
+                const long nbk = std::min(nb, np - k), k1 = k + nbk;
+                if (k1 >= np) break;
+                const long k2 = k1 + std::min(nb, np - k1);
+                long gi = -1;
+                if (k2 < np) {
+                    const double* P = A + k2 * lda + k;
+                    if (group_applies(c, np - k2, nbk, lda, P)) {
+                        gi = (long)tabs.upd.size();
+                        tabs.add(c, mtot - k2, np - k2, nbk, k2, lda, P, lda);
+                        Cs.push_back(A + k2 * lda + k2);
+                    } else
+                        el = std::max(el, syrk_split_ws_elems(c, np - k2, nbk));
+                }
+                gidx.push_back(gi);
+            }
+            el = std::max(el, tabs.ws_elems);
+            if (el) {
+                void* p = nullptr;
+                RC(bufs->get(sizeof(double) * el, &p));
+                ws.p = (double*)p;
+                ws.elems = el;
+            }
+            RC(tabs.upload(c, c->sm, *bufs, Cs, ws.p));
         }
     }
     if (la) {  // the panel stream starts after everything queued so far on the main stream (assembly)
@@ -813,9 +924,11 @@ static int32_t potrf_full_la(gp_ctx* c, T* A, long lda, long np, long mtot, int*
         // U2: the rest of the trailing matrix
         const long k2 = k1 + nb1;
         if (k2 < np) {
-            if constexpr (std::is_same<T, double>::value)
-                RC(syrk_lower_split(c, sM, ws, A + k2 * lda + k2, lda, A + k2 * lda + k, lda, mtot - k2, np - k2, nbk, k2));
-            else
+            if constexpr (std::is_same<T, double>::value) {
+                const size_t step = (size_t)(k / nb);
+                if (step < gidx.size() && gidx[step] >= 0) RC(run_grouped(c, sM, tabs, (size_t)gidx[step], ws.p));
+                else RC(syrk_lower_split(c, sM, ws, A + k2 * lda + k2, lda, A + k2 * lda + k, lda, mtot - k2, np - k2, nbk, k2));
+            } else
                 RC(launch_gemm<T>(c, sM, A + k2 * lda + k2, lda, A + k2 * lda + k, lda, A + k2 * lda + k, lda,
                                   mtot - k2, np - k2, nbk, plain_map(1, k2, k2)));
         }
@@ -1209,8 +1322,10 @@ static int32_t fit_timings(gp_ctx* c) {
         c->tm.gemm_ms += ms;
         c->tm.gemm_flops += r.flops;
         c->tm.gemm_bytes += r.bytes;
-        if (getenv("GPMI_DUMP_GEMM"))
-            fprintf(stderr, "GEMM s%d M=%ld N=%ld K=%ld ms=%.4f tflops=%.2f\n", r.stream, r.M, r.N, r.K, ms, r.flops / ms / 1e9);
+        if (getenv("GPMI_DUMP_GEMM")) {
+            if (r.nprob) fprintf(stderr, "GEMM s%d grouped problems=%ld tiles=%ld Kmax=%ld ms=%.4f tflops=%.2f\n", r.stream, r.nprob, r.ntiles, r.K, ms, r.flops / ms / 1e9);
+            else fprintf(stderr, "GEMM s%d M=%ld N=%ld K=%ld ms=%.4f tflops=%.2f\n", r.stream, r.M, r.N, r.K, ms, r.flops / ms / 1e9);
+        }
     }
     return 0;
 }
@@ -1972,6 +2087,8 @@ int32_t gp_ctx_set_param(gp_ctx* c, const char* name, int64_t v) {
     else if (!strcmp(name, "time_kernels")) c->time_kernels = v != 0;
     else if (!strcmp(name, "xcd_swizzle")) c->xcd_swizzle = v != 0;
     else if (!strcmp(name, "strassen_min_rows")) c->strassen_min_rows = v <= 0 ? 0 : round_up(v, 256);
+    else if (!strcmp(name, "strassen_group")) c->strassen_group = v != 0;
+    else if (!strcmp(name, "strassen_group_min_rows")) c->strassen_group_min_rows = std::max<int64_t>(256, round_up(v, 256));
     else if (!strcmp(name, "gemm_streamk")) c->gemm_streamk = v != 0;
     else if (!strcmp(name, "sk_max_tiles")) c->sk_max_tiles = v;
     else if (!strcmp(name, "sk_min_k")) c->sk_min_k = v;
@@ -2019,7 +2136,7 @@ int32_t gp_ctx_get_param(gp_ctx* c, const char* name, int64_t* out) {
     if (c->multi && multi_get_param(c, name, out) == 0) return 0;
     const struct { const char* n; int64_t v; } tab[] = {
         {"nb", c->nb}, {"nb_small", c->nb_small}, {"nb_large", c->nb_large}, {"lookahead", c->lookahead}, {"lookahead_min_n", c->lookahead_min_n}, {"time_kernels", c->time_kernels},
-        {"xcd_swizzle", c->xcd_swizzle}, {"strassen_min_rows", c->strassen_min_rows}, {"xcd_min_tiles", c->xcd_min_tiles}, {"gemm_streamk", c->gemm_streamk},
+        {"xcd_swizzle", c->xcd_swizzle}, {"strassen_min_rows", c->strassen_min_rows}, {"strassen_group", c->strassen_group}, {"strassen_group_min_rows", c->strassen_group_min_rows}, {"xcd_min_tiles", c->xcd_min_tiles}, {"gemm_streamk", c->gemm_streamk},
         {"sk_max_tiles", c->sk_max_tiles}, {"sk_min_k", c->sk_min_k}, {"gemm_pipe", c->gemm_pipe}, {"gemm_pad_f32", c->gemm_pad_f32},
         {"gemm_pad_lds", c->gemm_pad_user ? c->gemm_pad_lds : 0}, {"trsv_nb", c->trsv_nb},  {"deterministic", c->deterministic},
         {"leaf_v2", c->leaf_v2}, {"leaf_xr", c->leaf_xr}, {"leaf_cols", c->leaf_cols}, {"updk_max_k", c->updk_max_k}, {"updk_rt", c->updk_rt},
@@ -2967,13 +3084,20 @@ static int32_t dev_gemm_nt(gp_ctx* c, T* cm, int64_t ldc, const T* a, int64_t ld
     HIPCHK(hipSetDevice(c->device));
     if constexpr (sizeof(T) == 8) {  // "strassen_min_rows": the same decomposition the factorisation's bulk update uses
         const bool syrk = g && g->lower && g->P == 1 && g->Q == 1 && a == b && lda == ldb && row0 == col0 && m >= n;
-        const size_t el = !g ? (strassen_shape(c, m, n, k) ? strassen_ws_elems(c, m, n, k) : 0) : (syrk ? syrk_split_ws_elems(c, n, k) : 0);
+        PlanTables tabs;  // the lower SYRK in the grouped form: one update, planned here
+        if (syrk && group_applies(c, n, k, lda, a)) tabs.add(c, m, n, k, row0, ldc, a, lda);
+        const size_t el = !tabs.upd.empty() ? tabs.ws_elems : (!g ? (strassen_shape(c, m, n, k) ? strassen_ws_elems(c, m, n, k) : 0) : (syrk ? syrk_split_ws_elems(c, n, k) : 0));
         if (el) {
             DevBufs bufs(c);
             void* p = nullptr;
             RC(bufs.get(sizeof(double) * el, &p));
             const StrassenWs ws{(double*)p, el};
-            const int32_t rc = syrk ? syrk_lower_split(c, c->sm, ws, cm, ldc, a, lda, m, n, k, row0) : gemm_nt_strassen(c, c->sm, ws, cm, ldc, a, lda, b, ldb, m, n, k);
+            int32_t rc = 0;
+            if (!tabs.upd.empty()) {
+                rc = tabs.upload(c, c->sm, bufs, {cm}, ws.p);
+                if (rc == 0) rc = run_grouped(c, c->sm, tabs, 0, ws.p);
+            } else
+                rc = syrk ? syrk_lower_split(c, c->sm, ws, cm, ldc, a, lda, m, n, k, row0) : gemm_nt_strassen(c, c->sm, ws, cm, ldc, a, lda, b, ldb, m, n, k);
             HIPCHK(hipStreamSynchronize(c->sm));  // the sum panels go back to the cache when this returns: nothing may still read them
             return rc;
         }

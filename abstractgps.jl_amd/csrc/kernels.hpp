@@ -160,31 +160,21 @@ __device__ __forceinline__ void gemm_kloop_pipe(typename Tr<T>::acc_t (&acc)[4][
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA may still be writing this workgroup's LDS when it is handed on
 }
 
-template <typename T, typename CT = T, int PIPE = 1>
-__global__ __launch_bounds__(256, 2) void gemm_nt_dma_kernel(CT* C, long ldc, const T* A, long lda, const T* B, long ldb, int M,
-                                                              int N, int K, GridMap g) {
+// One 128×128 tile (bi, bj) of C −= A·Bᵀ, product bz of a batched launch: the whole per-tile body — prologue, k loop, plain and dual-target epilogue — shared by
+// gemm_nt_dma_kernel (one problem per launch) and gemm_nt_grp_kernel (a table of problems per launch).
+template <typename T, typename CT, int PIPE>
+__device__ __forceinline__ void gemm_nt_tile(CT* C, long ldc, const T* A, long lda, const T* B, long ldb, int M, int N, int K, const GridMap& g, int bi, int bj,
+                                             int bz) {
     using TR = Tr<T>;
     using chunk_t = typename TR::chunk_t;
     using acc_t = typename TR::acc_t;
     constexpr int VEC = TR::VEC;
     constexpr int BK = 8 * VEC;
 
-    int bi = blockIdx.y, bj = blockIdx.x;
-    if (g.compact == 1) compact_tile(g, (int)blockIdx.x, bi, bj);
-    else if (g.compact >= 2) {
-        if (!xcd_tile(g, (int)blockIdx.x, bi, bj)) return;
-    } else if (g.ktri == 1) {
-        bi = (int)gridDim.y - 1 - bi;  // triangular k range: the long row tiles are dispatched first
-    } else if (g.ktri == 3) {
-        // B lower triangular: the k range grows with the COLUMN tile.  Workgroup b runs on XCD b % 8 and blockIdx.x is the fastest index, so
-        // without the rotation XCD x would only ever see column tiles x, x + 8, ... (XCD 7: the longest k ranges of every row) — the
-        // imbalance measured in round 4 (34 -> 57 TF/s on the explicit-inverse panel product); rotating by the row tile deals them evenly.
-        bj = (bj + bi) % (int)gridDim.x;
-    }
     if (g.nbatch > 1) {
-        C += (long)blockIdx.z * g.cstride;
-        A += (long)blockIdx.z * (g.astride ? g.astride : (long)K);  // astride / bstride = 0: split-K (the k range [z·K, (z+1)·K) of both operands)
-        B += (long)blockIdx.z * (g.bstride ? g.bstride : (long)K);
+        C += (long)bz * g.cstride;
+        A += (long)bz * (g.astride ? g.astride : (long)K);  // astride / bstride = 0: split-K (the k range [z·K, (z+1)·K) of both operands)
+        B += (long)bz * (g.bstride ? g.bstride : (long)K);
     }
     const int m0 = bi * 128, n0 = bj * 128;
     long gr0 = 0, gc0 = 0;
@@ -330,7 +320,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_dma_kernel(CT* C, long ldc, co
         if (g.beta0 && g.s1 != 0) {  // dual-target epilogue (block-uniform): the product, accumulated from zero, is subtracted from one or two targets with a sign each
             if (active) {
                 const bool two = g.c2off != 0;
-                const long c2off = g.c2off + (g.nbatch > 1 ? (long)blockIdx.z * g.c2stride : 0L);
+                const long c2off = g.c2off + (g.nbatch > 1 ? (long)bz * g.c2stride : 0L);
                 const CT f1 = (CT)g.s1, f2 = (CT)g.s2;
 #pragma unroll
                 for (int mt = 0; mt < 4; ++mt)
@@ -361,6 +351,69 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_dma_kernel(CT* C, long ldc, co
 #pragma unroll
                 for (int r = 0; r < 4; ++r) Cw[(long)(mt * 16 + TR::crow(lane, r)) * ldc + nt * 16] = -acc[mt][nt][r];
     }
+}
+
+template <typename T, typename CT = T, int PIPE = 1>
+__global__ __launch_bounds__(256, 2) void gemm_nt_dma_kernel(CT* C, long ldc, const T* A, long lda, const T* B, long ldb, int M,
+                                                              int N, int K, GridMap g) {
+    int bi = blockIdx.y, bj = blockIdx.x;
+    if (g.compact == 1) compact_tile(g, (int)blockIdx.x, bi, bj);
+    else if (g.compact >= 2) {
+        if (!xcd_tile(g, (int)blockIdx.x, bi, bj)) return;
+    } else if (g.ktri == 1) {
+        bi = (int)gridDim.y - 1 - bi;  // triangular k range: the long row tiles are dispatched first
+    } else if (g.ktri == 3) {
+        // B lower triangular: the k range grows with the COLUMN tile.  Workgroup b runs on XCD b % 8 and blockIdx.x is the fastest index, so
+        // without the rotation XCD x would only ever see column tiles x, x + 8, ... (XCD 7: the longest k ranges of every row) — the
+        // imbalance measured in round 4 (34 -> 57 TF/s on the explicit-inverse panel product); rotating by the row tile deals them evenly.
+        bj = (bj + bi) % (int)gridDim.x;
+    }
+    gemm_nt_tile<T, CT, PIPE>(C, ldc, A, lda, B, ldb, M, N, K, g, bi, bj, (int)blockIdx.z);
+}
+
+// ------------------------------------------------------------------------------------------------
+// gemm_nt_grp: ONE launch over the tiles of MANY problems C_p −= A_p·B_pᵀ of different shapes (fp64; the four launches of a grouped bulk update:
+//   bulk_plan.hpp).  1-D grid over all tiles of the list; workgroup b finds its problem — the last table entry whose first tile index is <= b, a
+//   block-uniform binary search over scalar loads — and enumerates its tile as the problem's own launch would: row-major for a rectangle, compact_tile for
+//   a lower problem.  The tile body is gemm_nt_dma_kernel's; the problems of one launch write disjoint parts of C: no atomics, no waits between workgroups.
+// ------------------------------------------------------------------------------------------------
+template <typename T, int PIPE = 1>
+__global__ __launch_bounds__(256, 2) void gemm_nt_grp_kernel(const GrpProb* __restrict__ tab, int nprob) {
+    const int b = (int)blockIdx.x;
+    int lo = 0, hi = nprob - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab[mid].tile0 <= b) lo = mid;
+        else hi = mid - 1;
+    }
+    const GrpProb* const e = tab + lo;
+    GridMap g;
+    g.lower = e->lower;
+    g.P = 1; g.p = 0; g.Q = 1; g.q = 0;
+    g.nb = 128;
+    g.row0 = e->row0;
+    g.col0 = e->col0;
+    g.compact = 0;
+    g.tn = e->tn;
+    g.dt = 0;
+    g.tm = 0;
+    g.beta0 = e->beta0;
+    g.ktri = 0;
+    g.nbatch = 1;
+    g.cstride = 0; g.astride = 0; g.bstride = 0;
+    g.ktri_off = 0;
+    g.c2off = e->c2off;
+    g.c2stride = 0;
+    g.s1 = e->s1;
+    g.s2 = e->s2;
+    const int t = b - e->tile0;
+    int bi, bj;
+    if (g.lower) compact_tile(g, t, bi, bj);
+    else {
+        bi = t / g.tn;
+        bj = t - bi * g.tn;
+    }
+    gemm_nt_tile<T, T, PIPE>((T*)e->C, e->ldc, (const T*)e->A, e->lda, (const T*)e->B, e->ldb, e->M, e->N, e->K, g, bi, bj, 0);
 }
 
 // ------------------------------------------------------------------------------------------------

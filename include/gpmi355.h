@@ -199,7 +199,12 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
  *   "time_kernels"   bracket every MFMA GEMM launch with HIP events (gp_get_timings)      default 0
  *   "xcd_swizzle", "xcd_min_tiles"  XCD-aware super-tile workgroup order for large GEMM grids   default 0, 256
  *   "strassen_min_rows"  fp64 exact fits (and gpd_gemm_nt): smallest side of an off-diagonal block of the bulk trailing update that runs as seven
- *                    half-size products (one level of Strassen, ordered launches, no atomics: DESIGN.md §4); rounded up to 256; 0 = never   default 16384
+ *                    half-size products (one level of Strassen, ordered launches, no atomics: DESIGN.md §4); rounded up to 256; 0 = never   default 8192
+ *   "strassen_group", "strassen_group_min_rows"  a bulk update (or gpd_gemm_nt lower SYRK) of side >= strassen_group_min_rows that is split at all runs as
+ *                    FOUR grouped launches over the tiles of all its pieces — launch i of every Strassen block and the classical pieces write disjoint
+ *                    parts of C — instead of four launches per block and one per piece (csrc/bulk_plan.hpp, gemm_nt_grp_kernel: a device table of
+ *                    problems per launch, no atomics, bitwise equal to the per-block sequence under "deterministic"); every block then has its own
+ *                    sum panels.  0 / below the floor / with "xcd_swizzle": the per-block sequence.  The floor is rounded up to 256 and is at least 256   default 1, 8192
  *   "gemm_streamk"   persistent-grid GEMM with a stream-K tail on launches of <= sk_max_tiles tiles   default 1
  *                    (0 in the rank contexts of a multi-device ctx: "multi_gemm_streamk").  The tail adds its k-slices into C with
  *                    hardware floating-point atomics, so the order of summation depends on scheduling: results agree with the
@@ -281,7 +286,7 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
     "nb=-1,nb_small=4096,nb_large=2048,lookahead=1,lookahead_min_n=24576,time_kernels=0,xcd_swizzle=0,xcd_min_tiles=256,gemm_streamk=1,sk_max_tiles=4096," \
     "sk_min_k=0,gemm_pipe=1,gemm_pad_f32=0,gemm_pad_lds=0,trsv_nb=256,deterministic=0,leaf_v2=1,leaf_xr=0,leaf_cols=128,"    \
     "updk_max_k=512,updk_rt=0,updk_tall_k=256,updk_tall_m=8192,upd128=1,leaf_group=128,ldpad=32,vfe_ks=2048,vfe_sk=0,"          \
-    "vfe_overlap=1,vfe_dual=0,vfe_inv_nb=512,vfe_chunk=0,kmat_rows=1,dib_nb=2048,pool_cap_mb=98304,dense_stage_mb=64,alloc_poison=0,strassen_min_rows=16384"
+    "vfe_overlap=1,vfe_dual=0,vfe_inv_nb=512,vfe_chunk=0,kmat_rows=1,dib_nb=2048,pool_cap_mb=98304,dense_stage_mb=64,alloc_poison=0,strassen_min_rows=8192,strassen_group=1,strassen_group_min_rows=8192"
 int32_t gp_ctx_set_param(gp_ctx* ctx, const char* name, int64_t value);
 /* Read a parameter back (same names; "gemm_pad_lds" reads 0 until it has been set explicitly).  Used by the test-suite to assert that
  * every GPU test starts from the documented defaults. */
