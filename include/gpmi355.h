@@ -214,7 +214,10 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
  *   "deterministic"  1: the exact path (gp_logpdf, gp_logpdf_terms, gp_posterior_fit and every method of its posterior) uses no
  *                    floating-point atomics — no stream-K tails whatever "gemm_streamk" says, one thread per column in the backward
  *                    sweep — so two calls with the same inputs on the same ctx return the same BITS (tests/test_gpu_api.py; the leaf's one
- *                    Σ log L_ii add per launch is issued by a single thread and the leaves of a fit are totally ordered, so its order is fixed).  The VFE
+ *                    Σ log L_ii add per launch is issued by a single thread and the leaves of a fit are totally ordered, so its order is fixed).  The bits
+ *                    do not depend on the schedule either: the same fit on one stream and with the two-stream look-ahead, and with grouped and with
+ *                    per-block Strassen updates, returns the same logpdf, α and factor (tests/test_gpu_schedule_matrix.py); another panel width or
+ *                    another "strassen_min_rows" is another order of operations.  The VFE
  *                    path, the gradient kernels and the multi-device backward sweep keep their atomics.  1-5 % slower at N <= 32 768.   default 0
  *   "leaf_v2", "leaf_xr"  fp64 leaves by the register-resident panel64v2_kernel (csrc/leaf.hpp) / rows of X per leaf workgroup (0 auto)   default 1, 0
  *   "leaf_cols"      columns per register-resident leaf launch (64 or 128; 128 = one workgroup chain per 128 columns)   default 128

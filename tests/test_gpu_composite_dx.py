@@ -66,10 +66,25 @@ def test_six_term_kernel_every_container_and_the_other_gradients_unchanged(n, ve
     _assert_gx(gc["x"].T, g_ref, f"six-term n={n} ColVecs")
     lp0, g0 = agp.logpdf_and_grad(f(agp.RowVecs(X), noise), y)
     assert "x" not in g0 and set(g) == set(g0) | {"x"}
-    assert lp == lp0 and np.array_equal(g["y"], g0["y"]) and np.array_equal(g["mean"], g0["mean"])
+    # two calls on the default context: the stream-K tails of the factorisation and the backward sweep behind α add with fp64 atomics, so lp, dy and dmean
+    # of two calls agree to rounding, not to the bit (profiles/README.md r15: 3 of 60 repeats differed in dy)
+    assert lp == pytest.approx(lp0, rel=1e-12) and _rel(g["y"], g0["y"]) <= 1e-12 and _rel(g["mean"], g0["mean"]) <= 1e-12
     assert _rel(g["kernel"], g0["kernel"]) <= 1e-12 and _rel(g["theta"], g0["theta"]) <= 1e-12  # sums by fp64 atomics: not bitwise
     assert _rel(g["noise"], g0["noise"]) <= 1e-12
-    assert lp == pytest.approx(host_fit(k, X, y, noise, mean)[0], rel=1e-10)
+    lp_h = host_fit(k, X, y, noise, mean)[0]
+    assert lp == pytest.approx(lp_h, rel=1e-10)
+    # "deterministic" = 1 promises the bits of the fit (include/gpmi355.h): with and without wrt_x, lp, dy and dmean are the same numbers
+    ctx = agp.Context(0)
+    try:
+        ctx.set_param("deterministic", 1)
+        fd = agp.GP(mean, k, ctx=ctx) if mean else agp.GP(k, ctx=ctx)
+        lpd, gd = agp.logpdf_and_grad(fd(agp.RowVecs(X), noise), y, wrt_x=True)
+        lpd0, gd0 = agp.logpdf_and_grad(fd(agp.RowVecs(X), noise), y)
+    finally:
+        ctx.close()
+    assert lpd == lpd0 and np.array_equal(gd["y"], gd0["y"]) and np.array_equal(gd["mean"], gd0["mean"])
+    assert lpd == pytest.approx(lp_h, rel=1e-10)
+    _assert_gx(gd["x"], g_ref, f"six-term n={n} RowVecs deterministic")
 
 
 def test_six_term_kernel_in_fp32():
