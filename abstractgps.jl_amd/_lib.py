@@ -75,6 +75,7 @@ PROTOTYPES = {
     "gp_posterior_logdet": (i32, [vp, C.POINTER(dbl)]),
     "gp_posterior_fit": (i32, [vp, PK, PP, PN, vp, vp, C.POINTER(vp), vp, vp]),
     "gp_posterior_predict": (i32, [vp, PP, vp, i32, vp, vp, vp]),
+    "gp_posterior_predict_grad": (i32, [vp, PP, vp, i32, vp, vp, vp, vp]),
     "gp_posterior_get_factor": (i32, [vp, vp]),
     "gp_logpdf_grad": (i32, [vp, PK, PP, PN, vp, vp, vp, C.POINTER(dbl), C.POINTER(dbl), vp, vp, vp]),
     "gp_kernelmatrix_sum": (i32, [vp, PS, PP, PP, vp]),
@@ -93,6 +94,7 @@ PROTOTYPES = {
     "gp_vfe_fit": (i32, [vp, PK, PP, PP, PN, dbl, vp, vp, i32, C.POINTER(vp), vp]),
     "gp_vfe_update": (i32, [vp, PP, PN, vp, vp, C.POINTER(vp), vp]),
     "gp_vfe_predict": (i32, [vp, PP, vp, i32, vp, vp, vp]),
+    "gp_vfe_predict_grad": (i32, [vp, PP, vp, i32, vp, vp, vp, vp]),
     "gp_vfe_append": (i32, [vp, PP, C.POINTER(vp), vp]),
     "gp_vfe_logpdf": (i32, [vp, PP, vp, PN, vp, i64, i32, vp]),
     "gp_vfe_rand": (i32, [vp, PP, vp, PN, vp, i32, vp]),

@@ -990,6 +990,31 @@ class _PostData:
     delta: np.ndarray  # δ
 
 
+def _predict_grad(fn, handle, dt, mean_fn, x, what: int, mean_grad=None) -> tuple:
+    """gp_posterior_predict_grad / gp_vfe_predict_grad: (mean, var, dmean, dvar) of the sides in `what` (bit 0 mean, bit 1 variance; the others None),
+    values and gradients from one call.  The gradients have the shape of x's array: (n,) for a vector, the ColVecs / RowVecs array shape otherwise.
+    The device treats the prior mean as constant in x — exact for ZeroMean / ConstMean; a CustomMean needs `mean_grad`, a callable x -> the (ns × d)
+    derivative of the mean function, which is added to dmean (TypeError without it: never a silently incomplete gradient)."""
+    custom = callable(mean_fn) and (what & 1)
+    if custom and mean_grad is None:
+        raise TypeError("the prior mean is a CustomMean: pass mean_grad=callable returning its (ns × d) derivative at x")
+    m = _Marshal(dt)
+    px = m.points(x)
+    pm = _mean_vector(mean_fn, x, dt)
+    pm = None if pm is None else m.arr(pm)
+    mean = np.empty(px.n, dtype=dt) if what & 1 else None
+    var = np.empty(px.n, dtype=dt) if what & 2 else None
+    dmean = _dx_buffer(px, dt) if what & 1 else None
+    dvar = _dx_buffer(px, dt) if what & 2 else None
+    check(fn(handle, C.byref(px), m.ptr(pm), what, m.ptr(mean), m.ptr(var), m.ptr(dmean), m.ptr(dvar)))
+    dmean = None if dmean is None else _dx_shaped(dmean, px, x)
+    dvar = None if dvar is None else _dx_shaped(dvar, px, x)
+    if custom:
+        g = np.asarray(mean_grad(x), dtype=dt).reshape(px.n, px.d)  # (ns × d)
+        dmean = dmean + (g[:, 0] if px.layout == 0 else (g.T if isinstance(_as_input(x), ColVecs) else g))
+    return mean, var, dmean, dvar
+
+
 class PosteriorGP(AbstractGP):
     """src/exact_gpr_posterior.jl:1-4, with data = (α, C, x, δ) (:34); C lives on the device."""
 
@@ -1034,6 +1059,20 @@ class PosteriorGP(AbstractGP):
     def mean_and_cov(self, x):  # :78-83
         m, _, c = self._predict(x, 5)
         return m, c
+
+    def mean_and_var_grad(self, x, mean_grad=None):
+        """(mean, var, ∂mean/∂x, ∂var/∂x) at x in one device call (_predict_grad): what AD through mean_and_var(f_post, x) yields in the reference."""
+        return _predict_grad(self.data.C.ctx.lib.gp_posterior_predict_grad, self.data.C.handle, self.data.C.dtype, self.prior.mean_fn, x, 3, mean_grad)
+
+    def mean_grad(self, x, mean_grad=None):
+        """(mean, ∂mean/∂x): the α-weighted kernel only, no solve."""
+        r = _predict_grad(self.data.C.ctx.lib.gp_posterior_predict_grad, self.data.C.handle, self.data.C.dtype, self.prior.mean_fn, x, 1, mean_grad)
+        return r[0], r[2]
+
+    def var_grad(self, x):
+        """(var, ∂var/∂x)."""
+        r = _predict_grad(self.data.C.ctx.lib.gp_posterior_predict_grad, self.data.C.handle, self.data.C.dtype, self.prior.mean_fn, x, 2)
+        return r[1], r[3]
 
 
 def _stack_inputs(x, z):
@@ -1371,6 +1410,21 @@ class ApproxPosteriorGP(AbstractGP):
     def mean_and_cov(self, x):  # :205-210
         m, _, c = self._predict(x, 5)
         return m, c
+
+    def mean_and_var_grad(self, x, mean_grad=None):
+        """(mean, var, ∂mean/∂x, ∂var/∂x) at x in one device call (_predict_grad)."""
+        st = self._state
+        return _predict_grad(st.ctx.lib.gp_vfe_predict_grad, st.handle, self._dtype, self.prior.mean_fn, x, 3, mean_grad)
+
+    def mean_grad(self, x, mean_grad=None):
+        st = self._state
+        r = _predict_grad(st.ctx.lib.gp_vfe_predict_grad, st.handle, self._dtype, self.prior.mean_fn, x, 1, mean_grad)
+        return r[0], r[2]
+
+    def var_grad(self, x):
+        st = self._state
+        r = _predict_grad(st.ctx.lib.gp_vfe_predict_grad, st.handle, self._dtype, self.prior.mean_fn, x, 2)
+        return r[1], r[3]
 
 
     def objective_grad(self, wrt_x: bool = False) -> dict:

@@ -834,6 +834,62 @@ static int32_t trsm_post(gp_post* post, hipStream_t s, T* X, long ldx, long M, D
     return trsm_cached<T>(post->ctx, s, X, ldx, M, (const T*)post->A, post->ld, post->np, post->n, post->dibc, bufs);
 }
 
+// The backward solve X (M × np, + 128 slack rows; Mvalid real rows) ← X L⁻¹ against the same resident factor, the counterpart of trsm_cached (with it a row of
+// X becomes (C⁻¹k)ᵀ: the weights of the predictive variance's gradient).  It runs AFTER a forward solve on the handle and uses the inverse diagonal blocks that
+// solve left in `cache`, walking the blocks of dib_ranges from the last to the first:
+//   diagonal step      X_b ← X_b L_bb⁻¹ = −X_b W_b: ONE NT GEMM against the TRANSPOSED cached block (full k range: the transposed block is upper triangular, a
+//                      shape no triangular-k map covers) into the forward solve's scratch panel, copied back;
+//   off-diagonal step  X[:, 0:j0] −= X_b · L[b, 0:j0]: ONE NT GEMM whose B operand is the block row of L transposed into scratch.
+// Both transposes (transpose_rect_kernel) go through ONE scratch of (np + 128) × ldw elements — the size of the cache, no second N×N buffer — that `ws`
+// keeps for the chunks of a call (zeroed once: the GEMM over-reads B up to the next multiple of 128 rows).  No host synchronisation.
+// Without blocks ("dib_nb" = 0, np < "dib_nb", or the conditioning guard nbi = −1) the rows go through the vector solve trsv(fwd = false) — they already are in
+// its right-hand-side layout.  That path is SERIAL in the number of rows (one pass of the block sweep per row inside every launch), and it is also what a
+// call falls back to when the transpose scratch or the S panel cannot be allocated.  The ratios measured against the forward solve (predict_grad_impl) are
+// those of the BLOCKED path; the substitution path's cost grows with rows × np / 256 diagonal solves of ≈ 10 µs each (measured: include/gpmi355.h).
+struct BackWs {
+    void* bt = nullptr;
+};
+template <typename T>
+static int32_t trsv(gp_ctx* c, hipStream_t s, const T* L, long ldl, long np, T* R, long ldr, int nrhs, bool fwd);
+template <typename T>
+static int32_t trsm_back_cached(gp_ctx* c, hipStream_t s, T* X, long ldx, long M, long Mvalid, const T* A, long ld, long np, const DibCache& cache,
+                                DevBufs& bufs, BackWs& ws) {
+    if (M <= 0 || Mvalid <= 0) return 0;
+    if (!cache.w || cache.nbi < 128 || c->dib_nb < 128) return trsv<T>(c, s, A, ld, np, X, ldx, (int)Mvalid, false);
+    const long nbi = cache.nbi, ldw = cache.ldw;
+    if (!ws.bt) {
+        const size_t wb = sizeof(T) * (size_t)(np + 128) * ldw;
+        void* S_probe = nullptr;
+        if (bufs.get(wb, &ws.bt) != 0 || bufs.scratch(sizeof(T) * (size_t)(M + 128) * ldw, &S_probe) != 0) {
+            ws.bt = nullptr;
+            return trsv<T>(c, s, A, ld, np, X, ldx, (int)Mvalid, false);
+        }
+        HIPCHK(hipMemsetAsync(ws.bt, 0, wb, s));
+    }
+    void* S_v = nullptr;
+    RC(bufs.scratch(sizeof(T) * (size_t)(M + 128) * ldw, &S_v));
+    T* Bt = (T*)ws.bt;
+    T* S = (T*)S_v;
+    const T* W = (const T*)cache.w;
+    std::vector<std::pair<long, long>> blocks;
+    dib_ranges(0, np, nbi, blocks);
+    for (long bi = (long)blocks.size() - 1; bi >= 0; --bi) {
+        const long j0 = blocks[bi].first, n = blocks[bi].second;
+        hipLaunchKernelGGL(transpose_rect_kernel<T>, dim3((unsigned)((n + 31) / 32), (unsigned)((n + 31) / 32)), dim3(256), 0, s, W + j0 * ldw, ldw, Bt, ldw, n, n, 1);
+        HIPCHK(hipGetLastError());
+        GridMap g = plain_map(0, 0, 0);
+        g.beta0 = 1;
+        RC(launch_gemm<T>(c, s, S, ldw, X + j0, ldx, Bt, ldw, M, n, n, g));
+        HIPCHK(hipMemcpy2DAsync(X + j0, sizeof(T) * ldx, S, sizeof(T) * ldw, sizeof(T) * n, M, hipMemcpyDeviceToDevice, s));
+        if (j0 > 0) {
+            hipLaunchKernelGGL(transpose_rect_kernel<T>, dim3((unsigned)((j0 + 31) / 32), (unsigned)((n + 31) / 32)), dim3(256), 0, s, A + j0 * ld, ld, Bt, ldw, n, j0, 0);
+            HIPCHK(hipGetLastError());
+            RC(launch_gemm<T>(c, s, X, ldx, X + j0, ldx, Bt, ldw, M, j0, n, plain_map(0, 0, 0)));
+        }
+    }
+    return 0;
+}
+
 // Full factorisation of the np×np matrix (rows [np, mtot) are carried RHS rows): right-looking over panels of width nb with a
 // one-panel look-ahead (potrf_full_la below); nb = 0: the plain recursion on one stream.
 template <typename T>
@@ -1511,6 +1567,133 @@ static int32_t predict_impl(gp_post* post, const gp_points* xs, const void* pm, 
         }
         return 0;
     });
+}
+
+// gm / gv for `cnt` test points from j0 on (kernels.hpp kpgrad_kernel / kpgrad_sum_kernel): a composite kernel in one launch (D <= 16), a single kind once per
+// chunk of 16 dimensions.  sc: the kind's input scales on the device (double [max(nscale, 1)]).
+template <typename T>
+static int32_t launch_kpgrad(const KDesc& k, int nscale, const double* sc, long cnt, hipStream_t s, const T* xs, long ldxs, const T* x, long ldx, int d, long n,
+                             const T* alpha, const T* W, long ldw, double* gm, double* gv, long ldg, long j0) {
+    if (cnt <= 0) return 0;
+    if (k.ks) {
+        launch_kpgrad_sum<T>(cnt, s, xs, ldxs, x, ldx, d, *k.ks, n, alpha, W, ldw, gm, gv, ldg, j0);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    for (int p0 = 0; p0 < d; p0 += 16) {
+        hipLaunchKernelGGL(kpgrad_kernel<T>, dim3((unsigned)cnt), dim3(256), 0, s, xs, ldxs, x, ldx, d, k.kind, (T)k.variance, nscale, sc, n, alpha, W, ldw, gm, gv,
+                           ldg, j0, p0);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+// g (double [d][ldg], dimension-major) -> out in the container layout of xs, in T
+template <typename T>
+static void grad_to_layout(const gp_points* xs, const double* g, long ldg, void* out) {
+    T* o = (T*)out;
+    const long ns = xs->n;
+    const int d = xs->d;
+    for (int dd = 0; dd < d; ++dd)
+        for (long i = 0; i < ns; ++i) {
+            const T v = (T)g[(size_t)dd * ldg + i];
+            if (xs->layout == 0) o[i] = v;
+            else if (xs->layout == 1) o[(long)dd + i * d] = v;
+            else o[i + (long)dd * ns] = v;
+        }
+}
+
+// Predictive mean / variance AND their gradients w.r.t. the test inputs (include/gpmi355.h gp_posterior_predict_grad), next to predict_impl and in its
+// chunks.  Mean side: the α-weighted kernels only (no Gram matrix, no solve).  Variance side, per chunk of 4 096 test points: Gram → forward solve
+// (trsm_post; the variance falls out of rowsumsq as in predict_impl) → backward solve in place (trsm_back_cached: the rows become C⁻¹k_j) → kpgrad.
+// Measured against gp_posterior_predict(what = 3) on the same handle and 4 096 test points (profiles/r17/predict_grad_profile.json), BLOCKED path: 2.07 at
+// N = 16 384, 2.06 at N = 65 536 (the design predicts a ratio near 2: a second solve of the same flops — GEMM event times 17.3 ms forward, 17.6 ms backward at
+// N = 16 384; kpgrad 0.69 ms and the 15 transposes 0.44 ms).  Back-substitution path (no inverse blocks): N = 1 920, 1.3 -> 282 ms, a ratio of 212.
+template <typename T>
+static int32_t predict_grad_impl(gp_post* post, const gp_points* xs, const void* pm, int what, void* mean_out, void* var_out, void* dmean_out,
+                                 void* dvar_out) {
+    gp_ctx* c = post->ctx;
+    SkScope sk(c);
+    const long n = post->n, np = post->np;
+    const long ns = xs->n, nsp = round_up(ns, 128);
+    const int d = post->d;
+    const gp_kernel k = post->kern.view(post->dtype);
+    const KDesc kd = post->kern.desc();
+    std::vector<T> xs_h;
+    scale_points<T>(&k, xs, nsp, xs_h);
+    const bool want_gm = (what & 1) && dmean_out, want_gv = (what & 2) && dvar_out, side_v = (what & 2) != 0;
+    const int nsc = std::max(k.nscale, 1);
+    std::vector<double> sc_h((size_t)nsc, 1.0);
+    for (int p = 0; p < k.nscale; ++p) sc_h[p] = k.scale[p];
+    void *xs_v = nullptr, *m_v = nullptr, *X_v = nullptr, *g_v = nullptr, *sc_v = nullptr;
+    const size_t xs_bytes = sizeof(T) * (size_t)d * nsp, g_bytes = sizeof(double) * (size_t)2 * d * nsp, sc_bytes = sizeof(double) * (size_t)nsc;
+    DevBufs bufs(c);
+    RC(bufs.get(xs_bytes, &xs_v));
+    RC(bufs.get(g_bytes, &g_v));
+    RC(bufs.get(sc_bytes, &sc_v));
+    std::vector<double> g_h((want_gm || want_gv) ? (size_t)2 * d * nsp : 0);
+    const T* prior_mean = (const T*)pm;
+    c->ev_used = 0;
+    c->gemm_recs.clear();
+    const int32_t rc = run_drained(c, [&]() -> int32_t {
+        double* gm = want_gm ? (double*)g_v : nullptr;
+        double* gv = want_gv ? (double*)g_v + (size_t)d * nsp : nullptr;
+        HIPCHK(hipMemcpyAsync(xs_v, xs_h.data(), xs_bytes, hipMemcpyHostToDevice, c->sm));
+        HIPCHK(hipMemcpyAsync(sc_v, sc_h.data(), sc_bytes, hipMemcpyHostToDevice, c->sm));
+        if ((what & 1) && mean_out) {
+            RC(bufs.get(sizeof(T) * (size_t)nsp, &m_v));
+            kvec<T>(kd, ns, c->sm, (const T*)xs_v, nsp, (const T*)post->xs, np, d, n, (const T*)post->alpha, (T*)m_v);
+            HIPCHK(hipGetLastError());
+            std::vector<T> m_h(ns);
+            HIPCHK(hipMemcpyAsync(m_h.data(), m_v, sizeof(T) * ns, hipMemcpyDeviceToHost, c->sm));
+            HIPCHK(hipStreamSynchronize(c->sm));
+            T* mo = (T*)mean_out;
+            for (long i = 0; i < ns; ++i) mo[i] = (prior_mean ? prior_mean[i] : T(0)) + m_h[i];
+        }
+        if (want_gm && !want_gv)  // the mean side alone: one launch over every test point
+            RC(launch_kpgrad<T>(kd, k.nscale, (const double*)sc_v, ns, c->sm, (const T*)xs_v, nsp, (const T*)post->xs, np, d, n, (const T*)post->alpha,
+                                (const T*)nullptr, 0, gm, (double*)nullptr, nsp, 0));
+        if (side_v) {
+            const long chunk = std::min<long>(nsp, 4096);
+            const long ldx = np + c->ldpad;
+            RC(bufs.get(sizeof(T) * (size_t)(chunk + 128) * ldx, &X_v));
+            RC(ctx_scal(c, 8 + chunk));
+            T* X = (T*)X_v;
+            // the 128 slack rows below a chunk are operand over-read of the solves' GEMMs: finite, whatever the recycled block held
+            HIPCHK(hipMemsetAsync(X + (size_t)chunk * ldx, 0, sizeof(T) * (size_t)128 * ldx, c->sm));
+            std::vector<double> ss(chunk);
+            T* vo = (T*)var_out;
+            BackWs ws;
+            for (long r0 = 0; r0 < nsp; r0 += chunk) {
+                const long rows = std::min(chunk, nsp - r0), valid = std::min(rows, ns - r0);
+                GridMap g = plain_map(0, r0, 0);
+                dim3 grid((unsigned)(np / 128), (unsigned)(rows / 128));
+                gram<T>(kd, grid, c->sm, X, ldx, (const T*)xs_v, nsp, (const T*)post->xs, np, d, (const T*)nullptr, ns, n, 0, g);
+                HIPCHK(hipGetLastError());
+                RC(trsm_post<T>(post, c->sm, X, ldx, rows, bufs));
+                if (vo) {
+                    hipLaunchKernelGGL(rowsumsq_kernel<T>, dim3((unsigned)rows), dim3(256), 0, c->sm, X, ldx, np, c->scal_dev + 8);
+                    HIPCHK(hipGetLastError());
+                    HIPCHK(hipMemcpyAsync(ss.data(), c->scal_dev + 8, sizeof(double) * rows, hipMemcpyDeviceToHost, c->sm));
+                    HIPCHK(hipStreamSynchronize(c->sm));
+                    for (long i = 0; i < valid; ++i) vo[r0 + i] = (T)(post->kern.variance - ss[i]);  // k(x, x) = σ² (composite: Σ_t σ_t²)
+                }
+                if (want_gv) {
+                    RC(trsm_back_cached<T>(c, c->sm, X, ldx, rows, valid, (const T*)post->A, post->ld, np, post->dibc, bufs, ws));
+                    RC(launch_kpgrad<T>(kd, k.nscale, (const double*)sc_v, valid, c->sm, (const T*)xs_v, nsp, (const T*)post->xs, np, d, n,
+                                        (const T*)post->alpha, (const T*)X, ldx, gm, gv, nsp, r0));
+                }
+            }
+        }
+        if (want_gm || want_gv) {
+            HIPCHK(hipMemcpyAsync(g_h.data(), g_v, g_bytes, hipMemcpyDeviceToHost, c->sm));
+            HIPCHK(hipStreamSynchronize(c->sm));
+        }
+        return 0;
+    });
+    if (rc != 0) return rc;
+    if (want_gm) grad_to_layout<T>(xs, g_h.data(), nsp, dmean_out);
+    if (want_gv) grad_to_layout<T>(xs, g_h.data() + (size_t)d * nsp, nsp, dvar_out);
+    return 0;
 }
 
 // logpdf value + gradient (see include/gpmi355.h gp_logpdf_grad; ks != NULL: gp_logpdf_grad_sum / gp_logpdf_grad_sum_x, ∂/∂θ into dtheta)
@@ -2544,6 +2727,26 @@ int32_t gp_posterior_predict(gp_post* post, const gp_points* xs, const void* pm,
     return by_dtype(post->dtype, [&](auto t) { return predict_impl<decltype(t)>(post, xs, pm, what, mean_out, var_out, cov_out); });
 }
 
+// what: 1 mean side, 2 variance side; a side that is asked for needs its value or its gradient pointer (argi: position of `what`)
+static int32_t check_predict_grad_out(int what, const void* mean_out, const void* var_out, const void* dmean_out, const void* dvar_out, int argi) {
+    if (what <= 0 || what > 3) return set_arg_err(argi, "what must be a combination of 1|2");
+    if ((what & 1) && !mean_out && !dmean_out) return set_arg_err(argi + 1, "mean_out and dmean_out are both NULL");
+    if ((what & 2) && !var_out && !dvar_out) return set_arg_err(argi + 2, "var_out and dvar_out are both NULL");
+    return 0;
+}
+
+int32_t gp_posterior_predict_grad(gp_post* post, const gp_points* xs, const void* pm, int32_t what, void* mean_out, void* var_out, void* dmean_out,
+                                  void* dvar_out) {
+    Guard gd(post);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_post");
+    RC(check_test_points(xs, post->d));
+    RC(check_predict_grad_out(what, mean_out, var_out, dmean_out, dvar_out, 4));
+    gp_ctx* c = gd.c;
+    HIPCHK(hipSetDevice(c->device));
+    if (what & 2) RC(multi_gather(post));  // multi-device fit: the factor is assembled on this device (both solves run on the single-device path)
+    return by_dtype(post->dtype, [&](auto t) { return predict_grad_impl<decltype(t)>(post, xs, pm, what, mean_out, var_out, dmean_out, dvar_out); });
+}
+
 int32_t gp_posterior_update(gp_post* old, const gp_points* x2, const gp_noise* noise2, const void* delta_all, gp_post** out,
                             void* alpha_out, void* logpdf_out) {
     Guard gd(old);
@@ -2724,6 +2927,16 @@ int32_t gp_vfe_predict(gp_vfe* p, const gp_points* xs, const void* pm, int32_t w
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
     return by_dtype(p->dtype, [&](auto t) { return vfe_predict_impl<decltype(t)>(p, xs, pm, what, mean_out, var_out, cov_out); });
+}
+
+int32_t gp_vfe_predict_grad(gp_vfe* p, const gp_points* xs, const void* pm, int32_t what, void* mean_out, void* var_out, void* dmean_out, void* dvar_out) {
+    Guard gd(p);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
+    RC(check_test_points(xs, p->d));
+    RC(check_predict_grad_out(what, mean_out, var_out, dmean_out, dvar_out, 4));
+    gp_ctx* c = gd.c;
+    HIPCHK(hipSetDevice(c->device));
+    return by_dtype(p->dtype, [&](auto t) { return vfe_predict_grad_impl<decltype(t)>(p, xs, pm, what, mean_out, var_out, dmean_out, dvar_out); });
 }
 
 int32_t gp_vfe_logpdf(gp_vfe* p, const gp_points* xs, const void* pm, const gp_noise* noise, const void* Y, int64_t ldy,

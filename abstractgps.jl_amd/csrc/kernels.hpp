@@ -2793,6 +2793,152 @@ static inline void launch_kgrad_sum(dim3 grid, hipStream_t s, const T* Cinv, lon
     else hipLaunchKernelGGL((kgrad_sum_kernel<T, 16>), grid, dim3(256), 0, s, Cinv, ld, x, ldx, d, k, alpha, n, g, p0);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Gradients of the predictive mean and variance w.r.t. the test inputs (gp_posterior_predict_grad / gp_vfe_predict_grad, include/gpmi355.h):
+//     gm[p][j] =      Σ_i α_i  ∂k(x*_j, x_i)/∂x*_jp          (α read only when gm != nullptr)
+//     gv[p][j] = −2 · Σ_i w_ji ∂k(x*_j, x_i)/∂x*_jp          (row j of W = the weights C⁻¹k_j; read only when gv != nullptr)
+//   One workgroup per test point (the shape of kvec_kernel): the threads stride over i (coalesced loads of x, α and the weight row, ONE pass over the
+//   weights), every sum in fp64, wave shuffles, then the four waves meet in LDS and ONE thread per (p, j) writes — no atomics, bitwise reproducible.
+//   gm / gv: double [d][ldg], dimension-major like the inputs; test point j = j0 + blockIdx.x, its weight row blockIdx.x.
+// ------------------------------------------------------------------------------------------------
+template <int NP>
+__device__ __forceinline__ void kpgrad_reduce(const double (&am)[NP], const double (&av)[NP], int np_, double (*red)[2 * NP], double sm, double sv,
+                                              double* __restrict__ gm, double* __restrict__ gv, long ldg, long j, int p0,
+                                              const double* __restrict__ scale, int nscale) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        double a = am[p], b = av[p];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            a += __shfl_xor(a, o, 64);
+            b += __shfl_xor(b, o, 64);
+        }
+        if (lane == 0) {
+            red[w][p] = a;
+            red[w][NP + p] = b;
+        }
+    }
+    __syncthreads();
+    if (tid < 2 * NP) {
+        const int p = tid < NP ? tid : tid - NP;
+        if (p < np_) {
+            const double v = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+            const double sp = nscale == 0 ? 1.0 : (nscale == 1 ? scale[0] : scale[p0 + p]);
+            if (tid < NP) {
+                if (gm) gm[(long)(p0 + p) * ldg + j] = sm * sp * v;
+            } else if (gv) {
+                gv[(long)(p0 + p) * ldg + j] = sv * sp * v;
+            }
+        }
+    }
+}
+// single kind, pre-scaled inputs u = s∘x: ∂k/∂x*_p = 2 s_p σ² κ'(d²)(u*_p − u_p) (kappa_and_dr2; Matern12 at d = 0 taken as 0).  Any D: d² runs over every
+// dimension, the sums over the 16 of the launch's chunk [p0, p0 + 16) — the host launches once per chunk, as for kgradx_kernel.
+template <typename T>
+__global__ __launch_bounds__(256) void kpgrad_kernel(const T* __restrict__ xs, long ldxs, const T* __restrict__ x, long ldx, int d, int kind, T variance,
+                                                      int nscale, const double* __restrict__ scale, long n, const T* __restrict__ alpha,
+                                                      const T* __restrict__ W, long ldw, double* __restrict__ gm, double* __restrict__ gv, long ldg,
+                                                      long j0, int p0) {
+    constexpr int DC = 16;
+    __shared__ double red[4][2 * DC];
+    const long j = j0 + blockIdx.x;
+    const T* wrow = W + (long)blockIdx.x * ldw;
+    const int np_ = min(DC, d - p0);
+    T xp[DC];
+#pragma unroll
+    for (int p = 0; p < DC; ++p) xp[p] = p < np_ ? xs[(long)(p0 + p) * ldxs + j] : T(0);
+    double am[DC], av[DC];
+#pragma unroll
+    for (int p = 0; p < DC; ++p) am[p] = av[p] = 0.0;
+    for (long i = threadIdx.x; i < n; i += 256) {
+        T d2 = 0;
+        for (int dd = 0; dd < d; ++dd) {
+            const T t = xs[(long)dd * ldxs + j] - x[(long)dd * ldx + i];
+            d2 = fma(t, t, d2);
+        }
+        T kap, dk;
+        kappa_and_dr2<T>(kind, d2, kap, dk);
+        const double cm = gm ? (double)alpha[i] * (double)dk : 0.0;
+        const double cv = gv ? (double)wrow[i] * (double)dk : 0.0;
+#pragma unroll
+        for (int p = 0; p < DC; ++p)
+            if (p < np_) {
+                const double t = (double)(xp[p] - x[(long)(p0 + p) * ldx + i]);
+                am[p] += cm * t;
+                av[p] += cv * t;
+            }
+    }
+    kpgrad_reduce<DC>(am, av, np_, red, 2.0 * (double)variance, -4.0 * (double)variance, gm, gv, ldg, j, p0, scale, nscale);
+}
+// composite kernel, RAW inputs, D <= DR (1 / 4 / 16): ∂k/∂t at t = x*_j − x_i by ksum_gradx, evaluated ONCE per pair with unit weight and then
+// weighted by α_i and w_ji.
+template <typename T, int DR>
+__global__ __launch_bounds__(256) void kpgrad_sum_kernel(const T* __restrict__ xs, long ldxs, const T* __restrict__ x, long ldx, int d, const KSum k, long n,
+                                                          const T* __restrict__ alpha, const T* __restrict__ W, long ldw, double* __restrict__ gm,
+                                                          double* __restrict__ gv, long ldg, long j0) {
+    __shared__ double red[4][2 * DR];
+    __shared__ double kf[KSum::MAXFT][256];
+    const long j = j0 + blockIdx.x;
+    const T* wrow = W + (long)blockIdx.x * ldw;
+    const int tid = threadIdx.x;
+    T xv[DR];
+#pragma unroll
+    for (int p = 0; p < DR; ++p) xv[p] = p < d ? xs[(long)p * ldxs + j] : T(0);
+    double am[DR], av[DR];
+#pragma unroll
+    for (int p = 0; p < DR; ++p) am[p] = av[p] = 0.0;
+    for (long i = tid; i < n; i += 256) {
+        T t[DR];
+        double g[DR];
+#pragma unroll
+        for (int p = 0; p < DR; ++p) {
+            t[p] = p < d ? xv[p] - x[(long)p * ldx + i] : T(0);
+            g[p] = 0.0;
+        }
+        ksum_gradx<T, DR>(k, t, d, 1.0, g, kf, tid);
+        const double cm = gm ? (double)alpha[i] : 0.0;
+        const double cv = gv ? (double)wrow[i] : 0.0;
+#pragma unroll
+        for (int p = 0; p < DR; ++p) {
+            am[p] += cm * g[p];
+            av[p] += cv * g[p];
+        }
+    }
+    kpgrad_reduce<DR>(am, av, min(DR, d), red, 1.0, -2.0, gm, gv, ldg, j, 0, (const double*)nullptr, 0);
+}
+template <typename T>
+static inline void launch_kpgrad_sum(long ns, hipStream_t s, const T* xs, long ldxs, const T* x, long ldx, int d, const KSum& k, long n, const T* alpha,
+                                     const T* W, long ldw, double* gm, double* gv, long ldg, long j0) {
+    const dim3 grid((unsigned)ns);
+    if (d <= 1) hipLaunchKernelGGL((kpgrad_sum_kernel<T, 1>), grid, dim3(256), 0, s, xs, ldxs, x, ldx, d, k, n, alpha, W, ldw, gm, gv, ldg, j0);
+    else if (d <= 4) hipLaunchKernelGGL((kpgrad_sum_kernel<T, 4>), grid, dim3(256), 0, s, xs, ldxs, x, ldx, d, k, n, alpha, W, ldw, gm, gv, ldg, j0);
+    else hipLaunchKernelGGL((kpgrad_sum_kernel<T, 16>), grid, dim3(256), 0, s, xs, ldxs, x, ldx, d, k, n, alpha, W, ldw, gm, gv, ldg, j0);
+}
+// dst[c][r] = src[r][c] for a rows × cols block (any shape; 32×32 tiles through LDS): the B operands of the backward solve X ← X L⁻¹ (a block row of L, and —
+// lower = 1, entries above the source's diagonal written as zero — an inverse diagonal block).  grid (ceil(cols/32), ceil(rows/32)).
+template <typename T>
+__global__ __launch_bounds__(256) void transpose_rect_kernel(const T* __restrict__ src, long lds_, T* __restrict__ dst, long ldd, long rows, long cols, int lower) {
+    __shared__ T tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const long i0 = (long)blockIdx.y * 32, c0 = (long)blockIdx.x * 32;
+#pragma unroll
+    for (int r = ty; r < 32; r += 8) {
+        const long i = i0 + r, cc = c0 + tx;
+        tile[r][tx] = (i < rows && cc < cols && !(lower && cc > i)) ? src[i * lds_ + cc] : T(0);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = ty; r < 32; r += 8)
+        if (c0 + r < cols && i0 + tx < rows) dst[(c0 + r) * ldd + i0 + tx] = tile[tx][r];
+}
+// b[r][c] = a[r][c] − b[r][c]   (cols columns, both with leading dimension ld; one block per row)
+__global__ __launch_bounds__(256) void rsub_kernel(const double* __restrict__ a, double* __restrict__ b, long ld, long cols) {
+    const double* ar = a + (long)blockIdx.x * ld;
+    double* br = b + (long)blockIdx.x * ld;
+    for (long cc = threadIdx.x; cc < cols; cc += 256) br[cc] = ar[cc] - br[cc];
+}
+
 // ---- small M×M helpers of the VFE path ------------------------------------------------------------
 // dst[i][j] = -(double) src[max(i,j)][min(i,j)]   (the SYRK accumulator holds -G in its lower triangle)
 template <typename T>

@@ -745,6 +745,101 @@ static int32_t vfe_predict_impl(gp_vfe* p, const gp_points* xs, const void* pm, 
     return 0;
 }
 
+// Predictive mean / variance of a sparse posterior AND their gradients w.r.t. the test inputs (include/gpmi355.h gp_vfe_predict_grad), next to
+// vfe_predict_impl and with its buffers (fp64 whatever the handle's dtype; results rounded to T).  With A_j = L_z⁻¹ K(z, x*_j) a row of X1 = K_*z L_z⁻ᵀ:
+//   ∂mean_j = Σ_m α_m ∂k(x*_j, z_m),   ∂var_j = −2 Σ_m u_jm ∂k(x*_j, z_m),   u_j = L_z⁻ᵀ (A_j − Λ_ε⁻¹ A_j)
+// Both forward solves as in vfe_predict_impl (X2 = X1 L_d⁻ᵀ), then X2 ← X2 L_d⁻¹ (= (Λ_ε⁻¹A)ᵀ), X2 ← X1 − X2, X2 ← X2 L_z⁻¹ (all M-wide, trsm_back_cached) and
+// kpgrad_kernel over the pseudo-points.
+template <typename T>
+static int32_t vfe_predict_grad_impl(gp_vfe* p, const gp_points* xs, const void* pm, int what, void* mean_out, void* var_out, void* dmean_out,
+                                     void* dvar_out) {
+    gp_ctx* c = p->ctx;
+    const long m = p->m, mp = p->mp, ld = p->ld;
+    const long ns = xs->n, nsp = round_up(ns, 128);
+    const int d = p->d;
+    const gp_kernel k = p->kern.view(0);
+    const KDesc kd = p->kern.desc();
+    std::vector<T> xsT;
+    scale_points<T>(&k, xs, nsp, xsT);
+    std::vector<double> xs_h(xsT.begin(), xsT.end());
+    const double* vec = (const double*)p->vec;
+    const bool want_gm = (what & 1) && dmean_out, want_gv = (what & 2) && dvar_out, side_v = (what & 2) != 0;
+    const int nsc = std::max(k.nscale, 1);
+    std::vector<double> sc_h((size_t)nsc, 1.0);
+    for (int q = 0; q < k.nscale; ++q) sc_h[q] = k.scale[q];
+    const size_t xs_b = sizeof(double) * xs_h.size(), X_b = sizeof(double) * (size_t)(nsp + 128) * ld, o_b = sizeof(double) * (size_t)nsp * 3,
+                 g_b = sizeof(double) * (size_t)2 * d * nsp, sc_b = sizeof(double) * (size_t)nsc;
+    void *xs_v = 0, *X1_v = 0, *X2_v = 0, *o_v = 0, *g_v = 0, *sc_v = 0;
+    DevBufs bufs(c);
+    RC(bufs.get(xs_b, &xs_v));
+    RC(bufs.get(o_b, &o_v));
+    RC(bufs.get(g_b, &g_v));
+    RC(bufs.get(sc_b, &sc_v));
+    if (side_v) RC(bufs.get(X_b, &X1_v));
+    if (want_gv) RC(bufs.get(X_b, &X2_v));
+    double* X1 = (double*)X1_v;
+    double* X2 = want_gv ? (double*)X2_v : X1;
+    double* o = (double*)o_v;
+    hipStream_t s = c->sm;
+    c->ev_used = 0;
+    c->gemm_recs.clear();
+    std::vector<double> oh((size_t)nsp * 3, 0.0), g_h((want_gm || want_gv) ? (size_t)2 * d * nsp : 0);
+    const int32_t rc = run_drained(c, [&]() -> int32_t {
+        double* gm = want_gm ? (double*)g_v : nullptr;
+        double* gv = want_gv ? (double*)g_v + (size_t)d * nsp : nullptr;
+        HIPCHK(hipMemcpyAsync(xs_v, xs_h.data(), xs_b, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(sc_v, sc_h.data(), sc_b, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemsetAsync(o, 0, o_b, s));
+        // the 128 slack rows below the test points are operand over-read of the solves' GEMMs: finite, whatever the recycled block held
+        if (side_v) HIPCHK(hipMemsetAsync(X1 + (size_t)nsp * ld, 0, sizeof(double) * (size_t)128 * ld, s));
+        if (want_gv) HIPCHK(hipMemsetAsync(X2 + (size_t)nsp * ld, 0, sizeof(double) * (size_t)128 * ld, s));
+        if ((what & 1) && mean_out) {
+            hipLaunchKernelGGL(kvec_kernel<double>, dim3((unsigned)ns), dim3(256), 0, s, (const double*)xs_v, nsp, (const double*)p->zs, mp, d, p->kern.kind,
+                               p->kern.variance, m, vec + 2 * mp, o);
+            HIPCHK(hipGetLastError());
+        }
+        if (want_gm && !want_gv)
+            RC(launch_kpgrad<double>(kd, k.nscale, (const double*)sc_v, ns, s, (const double*)xs_v, nsp, (const double*)p->zs, mp, d, m, vec + 2 * mp,
+                                     (const double*)nullptr, 0, gm, (double*)nullptr, nsp, 0));
+        if (side_v) {
+            GridMap g = plain_map(0, 0, 0);
+            dim3 grid((unsigned)(mp / 128), (unsigned)(nsp / 128));
+            launch_kmat<double>(grid, s, X1, ld, (const double*)xs_v, nsp, (const double*)p->zs, mp, d, p->kern.kind, p->kern.variance, (const double*)nullptr, ns,
+                                m, 0, g, (const double*)nullptr, (const double*)nullptr);
+            HIPCHK(hipGetLastError());
+            RC(trsm_cached<double>(c, s, X1, ld, nsp, (const double*)p->Lz, ld, mp, p->m, p->dib_z, bufs));
+            hipLaunchKernelGGL(rowsumsq_kernel<double>, dim3((unsigned)nsp), dim3(256), 0, s, X1, ld, mp, o + nsp);
+            HIPCHK(hipGetLastError());
+            if (want_gv) HIPCHK(hipMemcpyAsync(X2, X1, sizeof(double) * (size_t)nsp * ld, hipMemcpyDeviceToDevice, s));
+            RC(trsm_cached<double>(c, s, X2, ld, nsp, (const double*)p->Ld, ld, mp, p->m, p->dib_d, bufs));
+            hipLaunchKernelGGL(rowsumsq_kernel<double>, dim3((unsigned)nsp), dim3(256), 0, s, X2, ld, mp, o + 2 * nsp);
+            HIPCHK(hipGetLastError());
+            if (want_gv) {
+                BackWs wb;  // one transpose scratch for both sweeps (same M, same block width)
+                RC(trsm_back_cached<double>(c, s, X2, ld, nsp, ns, (const double*)p->Ld, ld, mp, p->dib_d, bufs, wb));
+                hipLaunchKernelGGL(rsub_kernel, dim3((unsigned)ns), dim3(256), 0, s, (const double*)X1, X2, ld, mp);
+                HIPCHK(hipGetLastError());
+                RC(trsm_back_cached<double>(c, s, X2, ld, nsp, ns, (const double*)p->Lz, ld, mp, p->dib_z, bufs, wb));
+                RC(launch_kpgrad<double>(kd, k.nscale, (const double*)sc_v, ns, s, (const double*)xs_v, nsp, (const double*)p->zs, mp, d, m, vec + 2 * mp,
+                                         (const double*)X2, ld, gm, gv, nsp, 0));
+            }
+        }
+        HIPCHK(hipMemcpyAsync(oh.data(), o, o_b, hipMemcpyDeviceToHost, s));
+        if (want_gm || want_gv) HIPCHK(hipMemcpyAsync(g_h.data(), g_v, g_b, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    });
+    if (rc != 0) return rc;
+    const T* prior = (const T*)pm;
+    if ((what & 1) && mean_out)
+        for (long i = 0; i < ns; ++i) ((T*)mean_out)[i] = (T)((prior ? (double)prior[i] : 0.0) + oh[i]);
+    if (side_v && var_out)
+        for (long i = 0; i < ns; ++i) ((T*)var_out)[i] = (T)(p->kern.variance - oh[nsp + i] + oh[2 * nsp + i]);
+    if (want_gm) grad_to_layout<T>(xs, g_h.data(), nsp, dmean_out);
+    if (want_gv) grad_to_layout<T>(xs, g_h.data() + (size_t)d * nsp, nsp, dvar_out);
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Gradient of the sparse objective of a fitted handle (gp_vfe_grad): elbo (VFE, src/sparse_approximations.jl:248-254) or approx_log_evidence (DTC, :282-286)
 // against the kernel variance, the Scale / ARD parameters, the noise variances, y, the pseudo-inputs z and (optionally) the inputs x — what an AD backend

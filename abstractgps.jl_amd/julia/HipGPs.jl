@@ -13,6 +13,7 @@
 #   Zygote.gradient(θ -> logpdf(build(θ)(x, σ²), y), θ)   # -> rrule below -> gp_logpdf_grad
 #   p   = posterior(fx, y)                          # -> gp_posterior_fit           src/exact_gpr_posterior.jl:29-35
 #   mean_and_var(p(xs)); cov(p(xs))                 # -> gp_posterior_predict       src/exact_gpr_posterior.jl:60-90
+#   Zygote.gradient(x -> sum(mean(p, x) .+ 2 .* sqrt.(var(p, x))), xs)   # -> rrules -> gp_posterior_predict_grad / gp_vfe_predict_grad
 #   logpdf(p(xs, σ²), ys); rand(rng, p(xs, σ²), 3)  # -> gp_posterior_logpdf / gp_posterior_rand   (device, no refit)
 #   posterior(VFE(f(z, 1e-6)), fx, y); elbo(...)    # -> gp_vfe_fit / gp_vfe_predict src/sparse_approximations.jl:58-75,248-254
 #   Zygote.gradient(θ -> elbo(VFE(build(θ)(z(θ), 1e-6)), build(θ)(x, σ²), y), θ)   # -> rrule -> gp_vfe_fit + gp_vfe_grad
@@ -1005,6 +1006,76 @@ function StatsBase.mean_and_cov(f::HipApproxPosteriorGP, x::AbstractVector)     
 end
 StatsBase.mean_and_var(f::HipApproxPosteriorGP, x::AbstractVector) = vfe_predict(f, x, 3)[1:2] # :212-217
 AbstractGPs.inducing_points(f::HipApproxPosteriorGP) = f.approx.fz.x                            # :219
+
+# ---- gradients of the predictive mean / variance w.r.t. the test inputs ---------------------------------
+# What an AD backend computes when it differentiates mean(f_post, x) / var(f_post, x) / mean_and_var(f_post, x) of the stock posteriors
+# (src/exact_gpr_posterior.jl:60-90, src/sparse_approximations.jl:183-217): acquisition functions over x*, the test-time half of a deep kernel.
+# gp_posterior_predict_grad / gp_vfe_predict_grad return values and gradients from ONE call; dm / dv lie in the container layout of x
+# (Vector / D×N of ColVecs / N×D of RowVecs).  The device takes the prior mean as constant in x — exact for ZeroMean / ConstMean; the mean side of a
+# CustomMean prior is refused here (never a silently incomplete gradient: such a model differentiates the stock path).
+grad_entry(::HipPosteriorGP) = :exact
+grad_entry(::HipApproxPosteriorGP) = :sparse
+grad_eltype(f::HipPosteriorGP) = getfield(f.data.C, :T)
+grad_eltype(f::HipApproxPosteriorGP) = getfield(f, :T)
+grad_handle(f::HipPosteriorGP) = getfield(f.data.C, :handle)
+grad_handle(f::HipApproxPosteriorGP) = getfield(f, :handle)[]
+function predict_grad(f::Union{HipPosteriorGP,HipApproxPosteriorGP}, x::AbstractVector, what::Integer)
+    T = grad_eltype(f)
+    px = points(x, T)
+    px === nothing && throw(ArgumentError("unsupported input container for the accelerated posterior (use a Vector, ColVecs or RowVecs)"))
+    (what & 1) != 0 && f.prior.gp.mean isa CustomMean &&
+        throw(ArgumentError("HipGPs: the gradient of the predictive mean under a CustomMean needs the mean function's own derivative; differentiate the stock path"))
+    xbuf, cx = px
+    ns = length(x)
+    pm = prior_mean(f.prior.gp, x, T)
+    m = (what & 1) != 0 ? Vector{T}(undef, ns) : T[]
+    v = (what & 2) != 0 ? Vector{T}(undef, ns) : T[]
+    dm = (what & 1) != 0 ? similar(xbuf) : T[]
+    dv = (what & 2) != 0 ? similar(xbuf) : T[]
+    h = grad_handle(f)
+    GC.@preserve f xbuf pm m v dm dv begin
+        if grad_entry(f) === :exact
+            check(ccall((:gp_posterior_predict_grad, libgpmi355), Int32,
+                (Ptr{Cvoid}, Ref{CPoints}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                h, cx, pm === nothing ? C_NULL : pointer(pm), what, m, v, dm, dv))
+        else
+            check(ccall((:gp_vfe_predict_grad, libgpmi355), Int32,
+                (Ptr{Cvoid}, Ref{CPoints}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                h, cx, pm === nothing ? C_NULL : pointer(pm), what, m, v, dm, dv))
+        end
+    end
+    return m, v, dm, dv
+end
+# Δ_j · g[j, :] in the layout of the container, and the tangent of the container around it
+rows_times(x::AbstractVector{<:Real}, g, Δ) = Δ .* g
+rows_times(x::ColVecs, g, Δ) = g .* reshape(Δ, 1, :)
+rows_times(x::RowVecs, g, Δ) = g .* reshape(Δ, :, 1)
+# a zero cotangent of one side (m, v = mean_and_var(p, x); sum(m) delivers (Δm, ZeroTangent)): one method per container, so that none is ambiguous with the three above
+rows_times(x::AbstractVector{<:Real}, g, ::ChainRulesCore.AbstractZero) = zero(g)
+rows_times(x::ColVecs, g, ::ChainRulesCore.AbstractZero) = zero(g)
+rows_times(x::RowVecs, g, ::ChainRulesCore.AbstractZero) = zero(g)
+points_tangent(x::AbstractVector{<:Real}, G) = G
+points_tangent(x::Union{ColVecs,RowVecs}, G) = Tangent{typeof(x)}(; X=G)
+posterior_tangent() = ChainRulesCore.@not_implemented("HipGPs: the device posterior is a constant of mean / var (gradients w.r.t. the fit go through logpdf / elbo)")
+
+function ChainRulesCore.rrule(::typeof(Statistics.mean), f::Union{HipPosteriorGP,HipApproxPosteriorGP}, x::AbstractVector)
+    m, _, dm, _ = predict_grad(f, x, 1)
+    predictive_mean_pullback(Δ) = (NoTangent(), posterior_tangent(), points_tangent(x, rows_times(x, dm, unthunk(Δ))))
+    return m, predictive_mean_pullback
+end
+function ChainRulesCore.rrule(::typeof(Statistics.var), f::Union{HipPosteriorGP,HipApproxPosteriorGP}, x::AbstractVector)
+    _, v, _, dv = predict_grad(f, x, 2)
+    predictive_var_pullback(Δ) = (NoTangent(), posterior_tangent(), points_tangent(x, rows_times(x, dv, unthunk(Δ))))
+    return v, predictive_var_pullback
+end
+function ChainRulesCore.rrule(::typeof(StatsBase.mean_and_var), f::Union{HipPosteriorGP,HipApproxPosteriorGP}, x::AbstractVector)
+    m, v, dm, dv = predict_grad(f, x, 3)
+    function predictive_mean_and_var_pullback(Δ)
+        Δm, Δv = unthunk(Δ)
+        return NoTangent(), posterior_tangent(), points_tangent(x, rows_times(x, dm, unthunk(Δm)) .+ rows_times(x, dv, unthunk(Δv)))
+    end
+    return (m, v), predictive_mean_and_var_pullback
+end
 
 # update_posterior with new observations, same pseudo-points (src/sparse_approximations.jl:87-121)
 function AbstractGPs.update_posterior(f::HipApproxPosteriorGP, fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real})

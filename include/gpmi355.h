@@ -175,8 +175,8 @@ int32_t gp_ctx_multi_stats(gp_ctx* ctx, int64_t* fits, int64_t* retries, int64_t
  *                       posterior (each batch of observations ends in its own padded blocks).
  *   gp_posterior_factor_mul (<= 1 024 columns): every rank multiplies the blocks it holds with its share of ξ, the process rows'
  *                       partial products are summed on the host — no exchange between the ranks.
- * C.U (gp_posterior_get_factor) and covariances of more than 4 096 test points gather the factor onto devices[0] (real points only: the
- * padding inside the blocks is dropped).
+ * C.U (gp_posterior_get_factor), covariances of more than 4 096 test points and the variance side of gp_posterior_predict_grad gather the
+ * factor onto devices[0] (real points only: the padding inside the blocks is dropped).
  * gp_multi_solve_trace / _ex write the schedule of such a pass for a P×Q grid (dry run of the real rank threads, like
  * gp_multi_schedule_trace); flags: 1 = given right-hand sides, 2 = rows kept for an extended factor (sequential update),
  * 4 = followed by two backward sweeps. */
@@ -333,6 +333,30 @@ int32_t gp_posterior_fit(gp_ctx* ctx, const gp_kernel* k, const gp_points* x, co
  * mean = m(x*) + K_*x α;  var = k** - colsumsq(U⁻ᵀ K_x*);  cov = K** - VᵀV. */
 int32_t gp_posterior_predict(gp_post* post, const gp_points* xs, const void* prior_mean_xs_or_null,
                              int32_t what, void* mean_out, void* var_out, void* cov_out);
+/* Predictive mean / variance AND their gradients w.r.t. the test inputs: what an AD backend computes when a caller differentiates
+ * mean(f_post, x*) / var(f_post, x*) (src/exact_gpr_posterior.jl:60-90) — acquisition functions, the test-time half of a deep kernel, input
+ * uncertainty.  For every test point j independently, with k_j = K(X, x*_j), alpha and the factor L of C resident:
+ *     dmean[j, p] =      sum_i alpha_i dk(x*_j, x_i)/dx*_jp
+ *     dvar[j, p]  = -2 * sum_i w_ji    dk(x*_j, x_i)/dx*_jp,     w_j = C^-1 k_j = L^-T (L^-1 k_j)
+ * k(x*, x*) is constant (every kappa(x, x) = 1), and the prior mean counts as constant in x* (as dx_out of gp_logpdf_grad does): a caller whose mean
+ * function depends on x adds its derivative to dmean.  Matern12 at distance 0 contributes 0; a White factor contributes 0.
+ * what: bit 0 the mean side, bit 1 the variance side (0 or any other bit: argument error).  A side that is asked for writes its value (mean_out / var_out,
+ * ns entries) and / or its gradient (dmean_out / dvar_out: ns * d entries in the container layout of xs, in the handle's dtype) — each pointer may be
+ * NULL, not both of a side.  Values and gradients come from ONE pass: mean side alone needs no Gram matrix and no solve; the variance side runs, per
+ * 4 096 test points, Gram -> forward solve (the variance, as gp_posterior_predict) -> backward solve X <- X L^-1 in place -> one fused kernel that
+ * contracts the weights with dk/dx* (fp64 sums, one writer per output, no atomics: the gradient kernel is bitwise reproducible at any setting).
+ * The backward solve uses the inverse diagonal blocks of the forward solve ("dib_nb").  A handle without them ("dib_nb" = 0, fewer than "dib_nb" padded
+ * points, or a factor whose diagonal ratio trips the conditioning guard) takes the vector back-substitution once per test point: SERIAL in the number
+ * of test points.
+ * Multi-device ctx: the variance side gathers the factor onto devices[0] and runs the single-device path (like covariances of more than 4 096 points).
+ * Cost against gp_posterior_predict(what = 3) on the same handle: a second triangular solve of the same flops plus bandwidth passes, a ratio near 2 by
+ * design ON THE BLOCKED PATH.  Measured (tools/predict_grad_profile.py, 4 096 test points, profiles/r17/predict_grad_profile.json): 2.07 at N = 16 384
+ * (17.9 -> 37.0 ms; GEMM event times 17.3 ms forward, 17.6 ms backward), 2.06 at N = 65 536 (256 -> 528 ms); gp_vfe_predict_grad 2.10 at M = 4 096
+ * (3.2 -> 6.6 ms).  These figures do NOT hold for the back-substitution path — which every handle below "dib_nb" (2 048) padded points takes on a default
+ * ctx, and any call whose scratch cannot be allocated: measured at N = 1 920, 4 096 test points 1.3 -> 282 ms (a ratio of 212, 69 us per test point);
+ * a caller with many test points on a small handle lowers "dib_nb" (128 at least) on its ctx to get the blocked path. */
+int32_t gp_posterior_predict_grad(gp_post* post, const gp_points* xs, const void* prior_mean_xs_or_null, int32_t what,
+                                  void* mean_out_or_null, void* var_out_or_null, void* dmean_out_or_null, void* dvar_out_or_null);
 /* logpdf(post(x*, Σy*), Y*) on the device: the FiniteGP-over-PosteriorGP path of the reference — mean_and_cov
  * (src/exact_gpr_posterior.jl:78-83) + Σy* (src/finite_gp_projection.jl:133-136), cholesky (:308), logdet + _sqmahal
  * (:310, :325-326).  Y: ns × ncols column-major, leading dimension ldy; out: ncols entries.  The N*×N* predictive
@@ -466,6 +490,14 @@ int32_t gp_vfe_append(gp_vfe* old, const gp_points* z2, gp_vfe** out, void* obje
  * bit2 full cov (ns×ns column-major) = K** − AᵀA + (Λ_ε.U⁻ᵀA)ᵀ(Λ_ε.U⁻ᵀA). */
 int32_t gp_vfe_predict(gp_vfe* post, const gp_points* xs, const void* prior_mean_xs_or_null, int32_t what,
                        void* mean_out, void* var_out, void* cov_out);
+/* The sparse counterpart of gp_posterior_predict_grad (same `what`, outputs, conventions; src/sparse_approximations.jl:183-217).  With
+ * A_j = L_z^-1 K(z, x*_j), Lambda_eps = L_d L_d^T and alpha over the M pseudo-points:
+ *     dmean[j, p] =      sum_m alpha_m dk(x*_j, z_m)/dx*_jp
+ *     dvar[j, p]  = -2 * sum_m u_jm    dk(x*_j, z_m)/dx*_jp,     u_j = L_z^-T (A_j - Lambda_eps^-1 A_j)
+ * Both forward solves of gp_vfe_predict, then the Lambda_eps backward solve, the subtraction and the L_z backward solve (all M wide), then the same
+ * kernel over z.  fp64 on the device whatever the handle's dtype, like gp_vfe_predict. */
+int32_t gp_vfe_predict_grad(gp_vfe* post, const gp_points* xs, const void* prior_mean_xs_or_null, int32_t what,
+                            void* mean_out_or_null, void* var_out_or_null, void* dmean_out_or_null, void* dvar_out_or_null);
 /* logpdf(f_post_approx(x*, Σy*), Y*) and rand(...) — same contracts as gp_posterior_logpdf / gp_posterior_rand. */
 int32_t gp_vfe_logpdf(gp_vfe* post, const gp_points* xs, const void* prior_mean_xs_or_null, const gp_noise* noise,
                       const void* Y, int64_t ldy, int32_t ncols, void* out);
