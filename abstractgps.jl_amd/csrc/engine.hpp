@@ -148,6 +148,10 @@ struct gp_ctx {
     long vfe_inv_nb = 512; // VFE prelude: inv(L_z) with the inverse diagonal blocks of this width built in one batched launch sequence (0: 64-wide leaves)
     long strassen_min_rows = 8192;   // fp64 fits: smallest side of an off-diagonal block of the bulk trailing update (and of gpd_gemm_nt) that runs as seven
                                  // half-size products (one level of Strassen: gpmi355.hip gemm_nt_strassen / syrk_lower_split); 0 = never
+    long strassen_min_rows_large = 4096;  // the same threshold for fits of padded order >= lookahead_min_n, used as long as the caller has not set "strassen_min_rows" (an explicit
+                                          // value applies at every size).  Since the batched dual-target epilogue 4 096 wins C4 and C3's size; it loses C2's (profiles/r18/strassen_sweep.txt)
+    bool strassen_min_rows_set = false;   // "strassen_min_rows" was set by the caller
+    long strassen_v = 8192;               // the threshold of the call in progress (potrf_full_la, gpd_gemm_nt): what the shape rules below read
     int strassen_group = 1;          // 1: a bulk update that is split at all (and gpd_gemm_nt's lower SYRK) runs as FOUR grouped launches over the tiles of all its pieces
                                      // (bulk_plan.hpp, kernels.hpp gemm_nt_grp_kernel) instead of four launches per Strassen block and one per classical piece.
     long strassen_group_min_rows = 8192;  // The grouped form is taken when the side m of the update is at least this; below it, with strassen_group = 0 and with

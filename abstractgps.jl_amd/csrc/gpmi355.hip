@@ -365,9 +365,9 @@ struct StrassenWs {  // the ten sum panels, rows of K/2 + ldpad elements (the pa
 // (the shape rules live in bulk_plan.hpp: the plan of a grouped update and the launch sequence below split at the same points)
 static size_t strassen_ws_elems(const gp_ctx* c, long M, long N, long K) { return strassen_ws_rule(c->ldpad, M, N, K); }
 // shapes the Strassen form takes: quadrants of whole 128×128 tiles, whole k steps per half, operand rows movable as 16-byte pieces
-static bool strassen_shape(const gp_ctx* c, long M, long N, long K) { return strassen_shape_rule(c->strassen_min_rows, M, N, K); }
+static bool strassen_shape(const gp_ctx* c, long M, long N, long K) { return strassen_shape_rule(c->strassen_v, M, N, K); }
 // side of the off-diagonal block the lower SYRK of side m is split at (multiple of 256); 0: no split
-static long strassen_split(const gp_ctx* c, long m, long K) { return strassen_split_rule(c->strassen_min_rows, m, K); }
+static long strassen_split(const gp_ctx* c, long m, long K) { return strassen_split_rule(c->strassen_v, m, K); }
 
 static int32_t gemm_nt_strassen(gp_ctx* c, hipStream_t s, const StrassenWs& ws, double* C, long ldc, const double* A, long lda, const double* B, long ldb,
                                 long M, long N, long K) {
@@ -450,7 +450,7 @@ struct PlanTables {
     GrpProb* dev = nullptr;
     void add(const gp_ctx* c, long mrows, long m, long K, long row0, long ldc, const double* P, long ldp) {
         GroupedUpdate u;
-        u.plan = bulk_plan_build(mrows, m, K, row0, ldc, ldp, c->strassen_min_rows, c->ldpad);
+        u.plan = bulk_plan_build(mrows, m, K, row0, ldc, ldp, c->strassen_v, c->ldpad);
         u.P = P;
         ws_elems = std::max(ws_elems, u.plan.ws_elems);
         upd.push_back(std::move(u));
@@ -912,6 +912,8 @@ template <typename T>
 static int32_t potrf_full_la(gp_ctx* c, T* A, long lda, long np, long mtot, int* info_dev, long n_valid,
                              double* logdet_dev, DevBufs* bufs) {
     long nb = c->nb;
+    // "strassen_min_rows_large": the Strassen threshold of the large fits — the ones that take the look-ahead schedule — unless the caller chose one
+    c->strassen_v = (!c->strassen_min_rows_set && np >= c->lookahead_min_n) ? c->strassen_min_rows_large : c->strassen_min_rows;
     // below the look-ahead threshold the schedule is one stream anyway: panels of "nb_small" (4 096) columns halve the passes over the trailing matrix
     // (K = 4 096 updates) — C2 29.8-30.1 -> 29.0-29.2 ms on two boxes, N = 8 192 6.51 -> 6.43 (profiles/r5/nb_sweep.txt); from the threshold on the
     // widths measure within ± 0.5 % of each other ("nb_large" = 2 048).  An explicit "nb" >= 0 applies to every size.
@@ -2269,7 +2271,10 @@ int32_t gp_ctx_set_param(gp_ctx* c, const char* name, int64_t v) {
     else if (!strcmp(name, "lookahead_min_n")) c->lookahead_min_n = std::max<int64_t>(0, v);
     else if (!strcmp(name, "time_kernels")) c->time_kernels = v != 0;
     else if (!strcmp(name, "xcd_swizzle")) c->xcd_swizzle = v != 0;
-    else if (!strcmp(name, "strassen_min_rows")) c->strassen_min_rows = v <= 0 ? 0 : round_up(v, 256);
+    else if (!strcmp(name, "strassen_min_rows")) {
+        c->strassen_min_rows = v <= 0 ? 0 : round_up(v, 256);
+        c->strassen_min_rows_set = true;  // from here on it applies at every size ("strassen_min_rows_large" no longer does)
+    } else if (!strcmp(name, "strassen_min_rows_large")) c->strassen_min_rows_large = v <= 0 ? 0 : round_up(v, 256);
     else if (!strcmp(name, "strassen_group")) c->strassen_group = v != 0;
     else if (!strcmp(name, "strassen_group_min_rows")) c->strassen_group_min_rows = std::max<int64_t>(256, round_up(v, 256));
     else if (!strcmp(name, "gemm_streamk")) c->gemm_streamk = v != 0;
@@ -2319,7 +2324,7 @@ int32_t gp_ctx_get_param(gp_ctx* c, const char* name, int64_t* out) {
     if (c->multi && multi_get_param(c, name, out) == 0) return 0;
     const struct { const char* n; int64_t v; } tab[] = {
         {"nb", c->nb}, {"nb_small", c->nb_small}, {"nb_large", c->nb_large}, {"lookahead", c->lookahead}, {"lookahead_min_n", c->lookahead_min_n}, {"time_kernels", c->time_kernels},
-        {"xcd_swizzle", c->xcd_swizzle}, {"strassen_min_rows", c->strassen_min_rows}, {"strassen_group", c->strassen_group}, {"strassen_group_min_rows", c->strassen_group_min_rows}, {"xcd_min_tiles", c->xcd_min_tiles}, {"gemm_streamk", c->gemm_streamk},
+        {"xcd_swizzle", c->xcd_swizzle}, {"strassen_min_rows", c->strassen_min_rows}, {"strassen_min_rows_large", c->strassen_min_rows_large}, {"strassen_group", c->strassen_group}, {"strassen_group_min_rows", c->strassen_group_min_rows}, {"xcd_min_tiles", c->xcd_min_tiles}, {"gemm_streamk", c->gemm_streamk},
         {"sk_max_tiles", c->sk_max_tiles}, {"sk_min_k", c->sk_min_k}, {"gemm_pipe", c->gemm_pipe}, {"gemm_pad_f32", c->gemm_pad_f32},
         {"gemm_pad_lds", c->gemm_pad_user ? c->gemm_pad_lds : 0}, {"trsv_nb", c->trsv_nb},  {"deterministic", c->deterministic},
         {"leaf_v2", c->leaf_v2}, {"leaf_xr", c->leaf_xr}, {"leaf_cols", c->leaf_cols}, {"updk_max_k", c->updk_max_k}, {"updk_rt", c->updk_rt},
@@ -3296,6 +3301,7 @@ static int32_t dev_gemm_nt(gp_ctx* c, T* cm, int64_t ldc, const T* a, int64_t ld
     }
     HIPCHK(hipSetDevice(c->device));
     if constexpr (sizeof(T) == 8) {  // "strassen_min_rows": the same decomposition the factorisation's bulk update uses
+        c->strassen_v = c->strassen_min_rows;
         const bool syrk = g && g->lower && g->P == 1 && g->Q == 1 && a == b && lda == ldb && row0 == col0 && m >= n;
         PlanTables tabs;  // the lower SYRK in the grouped form: one update, planned here
         if (syrk && group_applies(c, n, k, lda, a)) tabs.add(c, m, n, k, row0, ldc, a, lda);

@@ -163,13 +163,20 @@ __device__ __forceinline__ void gemm_kloop_pipe(typename Tr<T>::acc_t (&acc)[4][
 // One 128×128 tile (bi, bj) of C −= A·Bᵀ, product bz of a batched launch: the whole per-tile body — prologue, k loop, plain and dual-target epilogue — shared by
 // gemm_nt_dma_kernel (one problem per launch) and gemm_nt_grp_kernel (a table of problems per launch).
 template <typename T, typename CT, int PIPE>
-__device__ __forceinline__ void gemm_nt_tile(CT* C, long ldc, const T* A, long lda, const T* B, long ldb, int M, int N, int K, const GridMap& g, int bi, int bj,
+__device__ __forceinline__ void gemm_nt_tile(CT* Cp, long ldc, const T* Ap, long lda, const T* Bp, long ldb, int M, int N, int K, const GridMap& g, int bi, int bj,
                                              int bz) {
     using TR = Tr<T>;
     using chunk_t = typename TR::chunk_t;
     using acc_t = typename TR::acc_t;
     constexpr int VEC = TR::VEC;
     constexpr int BK = 8 * VEC;
+    // C, A and B are device-memory pointers.  gemm_nt_grp_kernel reads them from its table, where the compiler can only take them for generic pointers: every access
+    // of C would be a flat_* instruction, which counts on lgkmcnt as well as vmcnt.  As global-address-space pointers they are global_* in both callers.
+    typedef __attribute__((address_space(1))) CT gct_t;
+    typedef __attribute__((address_space(1))) const T gt_t;
+    gct_t* C = (gct_t*)Cp;
+    gt_t* A = (gt_t*)Ap;
+    gt_t* B = (gt_t*)Bp;
 
     if (g.nbatch > 1) {
         C += (long)bz * g.cstride;
@@ -194,8 +201,8 @@ __device__ __forceinline__ void gemm_nt_tile(CT* C, long ldc, const T* A, long l
 
     // DMA map: instruction i of wave w covers rows 8·(4i+w) .. +8; lane -> row 8·(4i+w) + (lane>>3), slot lane&7
     const int drow = lane >> 3;
-    const T* Ag[4];
-    const T* Bg[4];
+    gt_t* Ag[4];
+    gt_t* Bg[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int r = 8 * (4 * i + w) + drow;
@@ -208,7 +215,7 @@ __device__ __forceinline__ void gemm_nt_tile(CT* C, long ldc, const T* A, long l
     // explicit vmcnt(0) in front of the step's barrier below.
     const unsigned ldsA = (unsigned)(unsigned long)(__attribute__((address_space(3))) char*)&As[0][0];
     const unsigned ldsB = (unsigned)(unsigned long)(__attribute__((address_space(3))) char*)&Bs[0][0];
-    auto dma1 = [&](const T* src, unsigned dst) {
+    auto dma1 = [&](gt_t* src, unsigned dst) {
         unsigned keep;
         const unsigned d = __builtin_amdgcn_readfirstlane(dst);
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
@@ -231,8 +238,8 @@ __device__ __forceinline__ void gemm_nt_tile(CT* C, long ldc, const T* A, long l
 
     const int li = lane & 15, lg = lane >> 4;
     acc_t acc[4][4];
-    CT* const Cw = C + (long)(m0 + wr * 64) * ldc + n0 + wc * 64 + li;
-    const CT* const Cr = active ? Cw : C + li;
+    gct_t* const Cw = C + (long)(m0 + wr * 64) * ldc + n0 + wc * 64 + li;
+    const gct_t* const Cr = active ? Cw : C + li;
     const int kt0 = (g.ktri == 2 && m0 > g.ktri_off) ? (m0 - g.ktri_off) / BK : 0;  // upper-triangular A (from row ktri_off on): leading zeros skipped
     dma(0, kt0);
     if (g.beta0) {
@@ -318,27 +325,49 @@ __device__ __forceinline__ void gemm_nt_tile(CT* C, long ldc, const T* A, long l
 #endif
     if constexpr (sizeof(T) == 8) {
         if (g.beta0 && g.s1 != 0) {  // dual-target epilogue (block-uniform): the product, accumulated from zero, is subtracted from one or two targets with a sign each
+            // A tile writes every target element exactly once and its two targets never overlap, so the read-modify-writes need no order among themselves.  They go
+            // in batches of one 16-row group (mt): the 16 loads of each target are issued back to back — 32 eight-byte values in flight per lane with two targets,
+            // in the registers the operand fragments left — then the FMAs, then the stores, and the next batch's loads are not held back by these stores.  Element
+            // by element (load, wait, FMA, store: the form of rounds 13-17) every one of a lane's 64 or 128 loads waited out a whole memory round trip.
+            // The expression per element is unchanged (one fused multiply-add): the bits are those of the serial form.
             if (active) {
-                const bool two = g.c2off != 0;
                 const long c2off = g.c2off + (g.nbatch > 1 ? (long)bz * g.c2stride : 0L);
                 const CT f1 = (CT)g.s1, f2 = (CT)g.s2;
+                auto rmw = [&](auto two_c) {
+                    constexpr bool two = decltype(two_c)::value;
 #pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
+                    for (int mt = 0; mt < 4; ++mt) {
+                        CT v1[4][4], v2[4][4];
 #pragma unroll
-                    for (int nt = 0; nt < 4; ++nt) {  // fragment by fragment: four loads, four stores per target
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            CT* const p = Cw + (long)(mt * 16 + TR::crow(lane, r)) * ldc + nt * 16;
-                            *p = *p - f1 * acc[mt][nt][r];
-                        }
-                        if (two) {
+                        for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
-                                CT* const p = Cw + c2off + (long)(mt * 16 + TR::crow(lane, r)) * ldc + nt * 16;
-                                *p = *p - f2 * acc[mt][nt][r];
+                                gct_t* const p = Cw + (long)(mt * 16 + TR::crow(lane, r)) * ldc + nt * 16;
+                                v1[nt][r] = *p;
+                                if constexpr (two) v2[nt][r] = p[c2off];
                             }
-                        }
+                        __builtin_amdgcn_sched_barrier(0);  // all loads of the batch in front of its first FMA
+#pragma unroll
+                        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                v1[nt][r] = v1[nt][r] - f1 * acc[mt][nt][r];
+                                if constexpr (two) v2[nt][r] = v2[nt][r] - f2 * acc[mt][nt][r];
+                            }
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                gct_t* const p = Cw + (long)(mt * 16 + TR::crow(lane, r)) * ldc + nt * 16;
+                                *p = v1[nt][r];
+                                if constexpr (two) p[c2off] = v2[nt][r];
+                            }
+                        __builtin_amdgcn_sched_barrier(0);
                     }
+                };
+                if (g.c2off != 0) rmw(std::true_type{});
+                else rmw(std::false_type{});
             }
             return;
         }

@@ -200,6 +200,9 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
  *   "xcd_swizzle", "xcd_min_tiles"  XCD-aware super-tile workgroup order for large GEMM grids   default 0, 256
  *   "strassen_min_rows"  fp64 exact fits (and gpd_gemm_nt): smallest side of an off-diagonal block of the bulk trailing update that runs as seven
  *                    half-size products (one level of Strassen, ordered launches, no atomics: DESIGN.md §4); rounded up to 256; 0 = never   default 8192
+ *   "strassen_min_rows_large"  the same threshold for fits whose padded order is at least "lookahead_min_n" (the two-stream schedule), used as long as
+ *                    "strassen_min_rows" has not been set on the ctx: once the caller sets that one — to any value, its default included — it applies at
+ *                    every size.  4 096 measures faster than 8 192 at N = 65 536 and 32 768 and slower at 16 384 (profiles/r18/strassen_sweep.txt)   default 4096
  *   "strassen_group", "strassen_group_min_rows"  a bulk update (or gpd_gemm_nt lower SYRK) of side >= strassen_group_min_rows that is split at all runs as
  *                    FOUR grouped launches over the tiles of all its pieces — launch i of every Strassen block and the classical pieces write disjoint
  *                    parts of C — instead of four launches per block and one per piece (csrc/bulk_plan.hpp, gemm_nt_grp_kernel: a device table of
@@ -289,7 +292,7 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
     "nb=-1,nb_small=4096,nb_large=2048,lookahead=1,lookahead_min_n=24576,time_kernels=0,xcd_swizzle=0,xcd_min_tiles=256,gemm_streamk=1,sk_max_tiles=4096," \
     "sk_min_k=0,gemm_pipe=1,gemm_pad_f32=0,gemm_pad_lds=0,trsv_nb=256,deterministic=0,leaf_v2=1,leaf_xr=0,leaf_cols=128,"    \
     "updk_max_k=512,updk_rt=0,updk_tall_k=256,updk_tall_m=8192,upd128=1,leaf_group=128,ldpad=32,vfe_ks=2048,vfe_sk=0,"          \
-    "vfe_overlap=1,vfe_dual=0,vfe_inv_nb=512,vfe_chunk=0,kmat_rows=1,dib_nb=2048,pool_cap_mb=98304,dense_stage_mb=64,alloc_poison=0,strassen_min_rows=8192,strassen_group=1,strassen_group_min_rows=8192"
+    "vfe_overlap=1,vfe_dual=0,vfe_inv_nb=512,vfe_chunk=0,kmat_rows=1,dib_nb=2048,pool_cap_mb=98304,dense_stage_mb=64,alloc_poison=0,strassen_min_rows=8192,strassen_min_rows_large=4096,strassen_group=1,strassen_group_min_rows=8192"
 int32_t gp_ctx_set_param(gp_ctx* ctx, const char* name, int64_t value);
 /* Read a parameter back (same names; "gemm_pad_lds" reads 0 until it has been set explicitly).  Used by the test-suite to assert that
  * every GPU test starts from the documented defaults. */
