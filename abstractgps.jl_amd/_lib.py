@@ -86,6 +86,10 @@ PROTOTYPES = {
     "gp_logpdf_terms_sum": (i32, [vp, PS, PP, PN, vp, vp, i64, i32, vp, vp]),
     "gp_logpdf_batch": (i32, [vp, i32, PK, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp)]),
     "gp_logpdf_batch_sum": (i32, [vp, i32, PS, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp)]),
+    "gp_predict_batch": (i32, [vp, i32, PK, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), i32, PP, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp), vp,
+                               C.POINTER(i32)]),
+    "gp_predict_batch_sum": (i32, [vp, i32, PS, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), i32, PP, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp), vp,
+                                   C.POINTER(i32)]),
     "gp_posterior_update": (i32, [vp, PP, PN, vp, C.POINTER(vp), vp, vp]),
     "gp_posterior_factor_mul": (i32, [vp, vp, i32, vp]),
     "gp_posterior_solve": (i32, [vp, vp, i32, vp]),

@@ -704,6 +704,8 @@ class _BatchGroup:
     ys: list
     nx: int = 0             # 1: every problem holds the SAME x object (sent once), else len(index)
     ny: int = 0
+    xss: Optional[list] = None  # mean_and_var_batch: the test points of every problem
+    nxs: int = 0
 
 
 def _batch_groups(fxs, ys) -> list:
@@ -809,6 +811,91 @@ def logpdf_batch(fxs, ys, *, return_alpha: bool = False, on_error: str = "raise"
         check(getattr(ctx.lib, call.entry)(ctx.handle, *call.args))
         parts.append((g.index, call.out, call.info, call.alphas))
     return _batch_merge(len(fxs), parts, return_alpha, on_error)
+
+
+# --------------------------------------------------------------------------------------------
+# the predictive half: gp_predict_batch / gp_predict_batch_sum
+# --------------------------------------------------------------------------------------------
+def _predict_groups(fxs, ys, xs) -> list:
+    """Grouping of a mean_and_var_batch call — needs no context and no device.  The groups are those of _batch_groups (ctx, dtype, single-kind or
+    composite); each also carries its problems' test points (`xss`) and nxs = 1 when every problem holds the SAME xs object.  xs: a sequence of input
+    containers, one per problem, or ONE container (an array, ColVecs, RowVecs) shared by all."""
+    fxs = list(fxs)
+    if isinstance(xs, (np.ndarray, ColVecs, RowVecs)):
+        xs = [xs] * len(fxs)  # one set of test points for every problem: the same object in every entry
+    xs = list(xs)
+    if len(xs) != len(fxs):
+        raise ValueError(f"DimensionMismatch: {len(fxs)} problems but {len(xs)} sets of test points")
+    groups = _batch_groups(fxs, ys)
+    for g in groups:
+        g.xss = [xs[i] for i in g.index]
+        g.nxs = 1 if all(v is g.xss[0] for v in g.xss) else len(g.index)
+    return groups
+
+
+@dataclass(eq=False)
+class _PredictCall:
+    """The marshalled arguments of one gp_predict_batch[_sum] call (everything after the ctx) and the buffers behind them."""
+
+    entry: str
+    nb: int
+    nx: int
+    ny: int
+    nxs: int
+    args: tuple
+    out: np.ndarray
+    info: np.ndarray
+    means: Optional[list]
+    vars: Optional[list]
+    keep: object
+
+
+def _predict_marshal(g: _BatchGroup, what: int) -> _PredictCall:
+    """ctypes arguments of one group — needs no context.  The leading arguments are those of _batch_marshal."""
+    fit = _batch_marshal(g, False)
+    m = fit.keep
+    nb = fit.nb
+    nbk, karr, nx, pts, narr, marr, ny, yarr, out, info, _ = fit.args
+    xpts = (gp_points * g.nxs)(*[m.points(v) for v in g.xss[:g.nxs]])
+    ns = [int(xpts[0 if g.nxs == 1 else b].n) for b in range(nb)]
+    pms = [_mean_vector(fx.f.mean_fn, v, g.dtype) for fx, v in zip(g.fxs, g.xss)]  # m(x*) on the host; None = ZeroMean
+    pms = [None if v is None else m.arr(v) for v in pms]
+    pmarr = None if all(v is None for v in pms) else (C.c_void_p * nb)(*[None if v is None else v.ctypes.data for v in pms])
+    means = [np.empty(k, dtype=g.dtype) for k in ns] if what & 1 else None
+    vars_ = [np.empty(k, dtype=g.dtype) for k in ns] if what & 2 else None
+    moarr = (C.c_void_p * nb)(*[a.ctypes.data for a in means]) if means is not None else None
+    voarr = (C.c_void_p * nb)(*[a.ctypes.data for a in vars_]) if vars_ is not None else None
+    m.keep += [xpts, pmarr, moarr, voarr]
+    args = (nbk, karr, nx, pts, narr, marr, ny, yarr, g.nxs, xpts, pmarr, what, moarr, voarr, out, info)
+    return _PredictCall("gp_predict_batch" + ("_sum" if g.composite else ""), nb, g.nx, g.ny, g.nxs, args, fit.out, fit.info, means, vars_, m)
+
+
+def mean_and_var_batch(fxs, ys, xs, *, what: int = 3, return_logpdf: bool = False, on_error: str = "raise"):
+    """mean_and_var(posterior(fx_b, y_b), xs_b) of many independent exact GPs (src/exact_gpr_posterior.jl:29-35, 60-70, once per problem) in one library
+    call per (ctx, dtype, single-kind / composite) group: what cross-validation folds, grids, multi-start optimisers and independent outputs sharing one
+    x ask after logpdf_batch.  fxs, ys as in logpdf_batch; xs: a sequence of input containers, one per problem (each with its own number of test points,
+    0 included), or ONE container shared by all.  The same x / y / xs object in every entry is sent once.  what: 1 the mean, 2 the variance, 3 both.
+    Returns the list of (mean, var) pairs in the caller's order, None in place of a side that was not asked for (with return_logpdf: that list and the
+    array of logpdf(fx_b, y_b)).  on_error = "raise": the PosDefException of the first failing problem (.info, .index); "nan": NaN in its outputs."""
+    if on_error not in ("raise", "nan"):
+        raise ValueError('on_error must be "raise" or "nan"')
+    if what not in (1, 2, 3):
+        raise ValueError("what must be 1 (mean), 2 (var) or 3 (both)")
+    fxs = list(fxs)
+    if not fxs:
+        return ([], np.empty(0)) if return_logpdf else []
+    n = len(fxs)
+    pairs = [None] * n
+    parts = []
+    for g in _predict_groups(fxs, ys, xs):
+        call = _predict_marshal(g, what)
+        ctx = g.ctx or default_context()
+        check(getattr(ctx.lib, call.entry)(ctx.handle, *call.args))
+        parts.append((g.index, call.out, call.info, None))
+        for j, i in enumerate(g.index):
+            pairs[i] = (call.means[j] if call.means is not None else None, call.vars[j] if call.vars is not None else None)
+    lp = _batch_merge(n, parts, False, on_error)
+    return (pairs, lp) if return_logpdf else pairs
 
 
 def _terms(fx: FiniteGP, y, want_logdet: bool, want_sqmahal: bool):

@@ -28,7 +28,7 @@ using KernelFunctions: SqExponentialKernel, Matern12Kernel, ExponentialKernel, M
 using LinearAlgebra, FillArrays, Statistics, StatsBase, Distributions, Random
 using ChainRulesCore
 
-export HipGP, HipPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, elbo_and_grad, logpdf_batch, BatchPosDefException
+export HipGP, HipPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, elbo_and_grad, logpdf_batch, mean_and_var_batch, BatchPosDefException
 
 const libgpmi355 = get(ENV, "GPMI355_LIB", joinpath(@__DIR__, "..", "csrc", "libgpmi355.so"))
 
@@ -440,6 +440,97 @@ function logpdf_batch(fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys; return_alpha
     bad = findfirst(!=(0), info)
     (on_error === :raise && bad !== nothing) && throw(BatchPosDefException(Int(info[bad]), bad))
     return return_alpha ? (lp, alphas) : lp
+end
+
+# ---- the predictive half: gp_predict_batch / gp_predict_batch_sum ------------------------------------------------------------------
+# mean_and_var_batch(fxs, ys, xs): mean_and_var(posterior(fxs[b], ys[b]), xs[b]) (src/exact_gpr_posterior.jl:29-35, 85-90, once per problem) in ONE
+# library call per (context, eltype, single-kind / composite) group.  `xs` is a vector of input containers, one per problem (each with its own
+# number of test points, none included), or ONE container shared by all; the same `x` / `y` / `xs` object in every entry is sent once.  what: 1 the
+# mean, 2 the variance, 3 both.  Returns the vector of (mean, var) tuples in the caller's order, `nothing` in place of a side that was not asked
+# for (with return_logpdf = true: that vector and the logpdfs).  on_error as in logpdf_batch.  A problem the ABI has no layout for takes the stock path.
+function mean_and_var_batch(fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys, xs; what::Integer=3, return_logpdf::Bool=false, on_error::Symbol=:raise)
+    on_error in (:raise, :nan) || throw(ArgumentError("on_error must be :raise or :nan"))
+    what in (1, 2, 3) || throw(ArgumentError("what must be 1 (mean), 2 (var) or 3 (both)"))
+    nb = length(fxs)
+    yv = (ys isa AbstractVector{<:Real}) ? fill(ys, nb) : collect(ys)
+    xv = (xs isa ColVecs || xs isa RowVecs || xs isa AbstractVector{<:Real}) ? fill(xs, nb) : collect(xs)
+    length(yv) == nb || throw(DimensionMismatch("$(nb) problems but $(length(yv)) observation vectors"))
+    length(xv) == nb || throw(DimensionMismatch("$(nb) problems but $(length(xv)) sets of test points"))
+    args = [marshal(fxs[b], eltype(yv[b])) for b in 1:nb]
+    T = (nb > 0 && all(a -> a !== nothing && a.T === Float32, args)) ? Float32 : Float64
+    lp = Vector{T}(undef, nb)
+    info = zeros(Int32, nb)
+    means = Vector{Any}(nothing, nb)
+    vars = Vector{Any}(nothing, nb)
+    groups = Dict{Any,Vector{Int}}()
+    for b in 1:nb
+        length(yv[b]) == length(fxs[b]) || throw(DimensionMismatch("problem $(b): length(fx) = $(length(fxs[b])) but y has $(length(yv[b])) entries"))
+        a = args[b]
+        if a === nothing || points(xv[b], a.T) === nothing  # stock path, one problem at a time
+            try
+                lp[b] = logpdf(stock(fxs[b]), yv[b])
+                m, v = mean_and_var(posterior(stock(fxs[b]), yv[b]), xv[b])
+                (what & 1) != 0 && (means[b] = m)
+                (what & 2) != 0 && (vars[b] = v)
+            catch e
+                e isa PosDefException || rethrow()
+                lp[b] = NaN
+                info[b] = e.info
+                (what & 1) != 0 && (means[b] = fill(NaN, length(xv[b])))
+                (what & 2) != 0 && (vars[b] = fill(NaN, length(xv[b])))
+            end
+        else
+            push!(get!(groups, (fxs[b].f.ctx, a.T, haskey(a, :ks)), Int[]), b)
+        end
+    end
+    for ((ctx, Tg, composite), idx) in groups
+        g = length(idx)
+        nx = all(b -> fxs[b].x === fxs[idx[1]].x, idx) ? 1 : g
+        ny = all(b -> yv[b] === yv[idx[1]], idx) ? 1 : g
+        nxs = all(b -> xv[b] === xv[idx[1]], idx) ? 1 : g
+        cxs = [args[b].cx for b in idx[1:nx]]
+        cns = [args[b].cn for b in idx]
+        ybufs = [Vector{Tg}(yv[b]) for b in idx[1:ny]]
+        yptrs = Ptr{Cvoid}[pointer(v) for v in ybufs]
+        mptrs = Ptr{Cvoid}[args[b].m === nothing ? C_NULL : pointer(args[b].m) for b in idx]
+        xsp = [points(xv[b], Tg) for b in idx[1:nxs]]  # (buffer, CPoints)
+        cxss = [p[2] for p in xsp]
+        pms = [prior_mean(fxs[b].f.gp, xv[b], Tg) for b in idx]  # m(x*) on the host; nothing = ZeroMean
+        pmptrs = Ptr{Cvoid}[m === nothing ? C_NULL : pointer(m) for m in pms]
+        mbufs = [Vector{Tg}(undef, (what & 1) != 0 ? length(xv[b]) : 0) for b in idx]
+        vbufs = [Vector{Tg}(undef, (what & 2) != 0 ? length(xv[b]) : 0) for b in idx]
+        moptrs = Ptr{Cvoid}[pointer(v) for v in mbufs]
+        voptrs = Ptr{Cvoid}[pointer(v) for v in vbufs]
+        out = Vector{Tg}(undef, g)
+        inf = zeros(Int32, g)
+        GC.@preserve args ybufs cxs cns yptrs mptrs xsp cxss pms pmptrs mbufs vbufs moptrs voptrs out inf begin
+            if composite
+                ks = [args[b].ks for b in idx]
+                GC.@preserve ks check(ccall((:gp_predict_batch_sum, libgpmi355), Int32,
+                    (Ptr{Cvoid}, Int32, Ptr{CKSum}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Int32, Ptr{CPoints},
+                     Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32}),
+                    ctx.handle, g, ks, nx, cxs, cns, mptrs, ny, yptrs, nxs, cxss, pmptrs, what, (what & 1) != 0 ? pointer(moptrs) : C_NULL,
+                    (what & 2) != 0 ? pointer(voptrs) : C_NULL, out, inf))
+            else
+                cks = [args[b].ck for b in idx]
+                GC.@preserve cks check(ccall((:gp_predict_batch, libgpmi355), Int32,
+                    (Ptr{Cvoid}, Int32, Ptr{CKernel}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Int32, Ptr{CPoints},
+                     Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32}),
+                    ctx.handle, g, cks, nx, cxs, cns, mptrs, ny, yptrs, nxs, cxss, pmptrs, what, (what & 1) != 0 ? pointer(moptrs) : C_NULL,
+                    (what & 2) != 0 ? pointer(voptrs) : C_NULL, out, inf))
+            end
+        end
+        for (j, b) in enumerate(idx)
+            lp[b] = out[j]
+            info[b] = inf[j]
+            (what & 1) != 0 && (means[b] = mbufs[j])
+            (what & 2) != 0 && (vars[b] = vbufs[j])
+        end
+    end
+    bad = findfirst(!=(0), info)
+    (on_error === :raise && bad !== nothing) && throw(BatchPosDefException(Int(info[bad]), bad))
+    pairs = [(means[b], vars[b]) for b in 1:nb]
+    return return_logpdf ? (pairs, lp) : pairs
 end
 
 function logpdf_terms(fx::FiniteGP{<:HipGP}, Y::Union{Nothing,AbstractVecOrMat{<:Real}}; logdet::Bool, sq::Bool)

@@ -446,6 +446,37 @@ int32_t gp_logpdf_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t n
                             const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
                             void* const* alpha_out_or_null);
 
+/* The predictive half of the batch call: the same nb problems, each with its own test points, answered by ONE call — what a set of cross-validation
+ * folds, a grid, a multi-start optimiser or independent outputs sharing one x want next (gp_posterior_fit + gp_posterior_predict + gp_posterior_free
+ * per problem otherwise).  Per problem the semantics are those of gp_posterior_fit followed by gp_posterior_predict (src/exact_gpr_posterior.jl:29-35,
+ * 60-70):  mean = m(x*) + K_*x α;  var = k(x*, x*) − colsumsq(L⁻¹ K_x*), not clamped.
+ *   The arguments up to y are those of gp_logpdf_batch.  xs: nxs entries, nxs ∈ {1, nb} — 1 = ONE set of test points shared by every problem (uploaded
+ *   once); problem b has ns_b = xs_b.n >= 0 test points of the D of its x (ns_b = 0 is legal: nothing of that problem's xs or outputs is touched).
+ *   prior_mean_xs_or_null: NULL, or nb pointers each NULL or m(x*_b) evaluated on the host (ns_b entries).  what: bit 0 the mean, bit 1 the variance, as
+ *   in gp_posterior_predict (0 or any other bit: argument error).  mean_out / var_out: nb pointers to ns_b entries each, in the call's dtype; the array
+ *   of a side that is asked for must not be NULL (nor its entries where ns_b > 0), the other one is not read.  logpdf_out_or_null: nb entries
+ *   (logpdf(f_b(x_b, Σy_b), y_b), from the same factorisation) or NULL;  info_out: nb entries.
+ * Failure is data, as in gp_logpdf_batch: info_out[b] is the order of the first leading minor that is not positive, that problem's logpdf, mean and var
+ * are NaN, the other problems are not affected.  The return value reports argument errors only (−i, reason in gp_last_error(); nb = 0 returns 0 and
+ * touches nothing).
+ * Problems the batch kernel takes (fp64, noise kind 0 / 1, n_b <= GPMI355_BATCH_MAX_N, D <= 16 — the routing of gp_logpdf_batch, decided by the problem
+ * alone) run as two kernels per wave: batch_logpdf_kernel, then batch_predict_kernel on the slices it left (csrc/batch.hip) — one workgroup per tile of
+ * 128 test points of one problem (cross-Gram rows and the mean in one pass, a left-looking forward solve against the read-only factor, the variance), so
+ * a problem with many test points spreads over many workgroups.  One packed copy in, one copy back; the workspace (slices plus one strip per predict
+ * workgroup) stays within the budget of a wave, and a wave with more tiles than one launch takes runs several predict launches against the same slices.
+ * No floating-point atomics, no waits between workgroups; every test point's arithmetic touches no other row, so its mean and variance are the same bits
+ * alone, among other test points, and in any batch.  Every other problem is answered inside the same call by gp_posterior_fit(_sum) +
+ * gp_posterior_predict + gp_posterior_free.  Measured against that loop: tools/batch_predict_profile.py, DESIGN.md §4. */
+int32_t gp_predict_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                         const void* const* mean_or_null, int32_t ny, const void* const* y, int32_t nxs, const gp_points* xs,
+                         const void* const* prior_mean_xs_or_null, int32_t what, void* const* mean_out, void* const* var_out,
+                         void* logpdf_out_or_null, int32_t* info_out);
+/* The same with one composite kernel (gp_ksum) per problem: k** = Σ_t σ_t². */
+int32_t gp_predict_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                             const void* const* mean_or_null, int32_t ny, const void* const* y, int32_t nxs, const gp_points* xs,
+                             const void* const* prior_mean_xs_or_null, int32_t what, void* const* mean_out, void* const* var_out,
+                             void* logpdf_out_or_null, int32_t* info_out);
+
 /* Sequential conditioning, posterior(fx::FiniteGP{<:PosteriorGP}, y) (src/exact_gpr_posterior.jl:46-56): the resident
  * factor of `old` is extended by the bordered-Cholesky step update_chol (src/util/common_covmat_ops.jl:38-42):
  *   U12 = U11'\C12  (here: rows K(x2,x1)·L11⁻ᵀ by the blocked MFMA TRSM),  U22 = chol(C22 − U12'U12).
