@@ -1030,6 +1030,88 @@ def logpdf_and_grad(fx: FiniteGP, y, wrt_x: bool = False) -> tuple:
     return lp[0], g
 
 
+# --------------------------------------------------------------------------------------------
+# the training half of the batch calls: gp_logpdf_grad_batch / gp_logpdf_grad_batch_sum
+# --------------------------------------------------------------------------------------------
+@dataclass(eq=False)
+class _GradBatchCall:
+    """The marshalled arguments of one gp_logpdf_grad_batch[_sum] call (everything after the ctx) and the buffers behind them."""
+
+    entry: str
+    nb: int
+    nx: int
+    ny: int
+    args: tuple
+    out: np.ndarray
+    info: np.ndarray
+    dvar: Optional[np.ndarray]   # single-kind: nb entries
+    dscale: Optional[list]       # single-kind: per problem an array of nscale entries, None where the kernel has no transform
+    dtheta: Optional[list]       # composite: per problem an array over θ
+    nfs: Optional[list]          # composite: the _NormalForm of every problem (the chain rule back to params(k))
+    dnoise: list                 # per problem: 1 entry, n entries or (n, n)
+    dy: list
+    noise_kind: list
+    keep: object
+
+
+def _grad_batch_marshal(g: _BatchGroup) -> _GradBatchCall:
+    """ctypes arguments of one group — needs no context.  The leading arguments are those of _batch_marshal."""
+    fit = _batch_marshal(g, False)
+    m = fit.keep
+    nb = fit.nb
+    nbk, karr, nx, pts, narr, marr, ny, yarr, out, info, _ = fit.args
+    ns = [len(fx) for fx in g.fxs]
+    kinds = [int(narr[b].kind) for b in range(nb)]
+    dnoise = [np.empty(_dnoise_shape(narr[b], ns[b]), dtype=g.dtype) for b in range(nb)]
+    dy = [np.empty(n, dtype=g.dtype) for n in ns]
+    dnarr = (C.c_void_p * nb)(*[a.ctypes.data for a in dnoise])
+    dyarr = (C.c_void_p * nb)(*[a.ctypes.data for a in dy])
+    m.keep += [dnarr, dyarr]
+    if g.composite:
+        nfs = [_NormalForm(fx.f.kernel) for fx in g.fxs]
+        dtheta = [np.empty(len(nf.theta()), dtype=np.float64) for nf in nfs]
+        dtarr = (C.c_void_p * nb)(*[a.ctypes.data for a in dtheta])
+        m.keep.append(dtarr)
+        args = (nbk, karr, nx, pts, narr, marr, ny, yarr, out, info, dtarr, dnarr, dyarr)
+        return _GradBatchCall("gp_logpdf_grad_batch_sum", nb, g.nx, g.ny, args, fit.out, fit.info, None, None, dtheta, nfs, dnoise, dy, kinds, m)
+    dvar = np.empty(nb, dtype=np.float64)
+    dscale = [np.empty(karr[b].nscale, dtype=np.float64) if karr[b].nscale > 0 else None for b in range(nb)]
+    dsarr = (C.c_void_p * nb)(*[None if a is None else a.ctypes.data for a in dscale])  # NULL where nscale = 0
+    m.keep.append(dsarr)
+    args = (nbk, karr, nx, pts, narr, marr, ny, yarr, out, info, dvar.ctypes.data_as(C.POINTER(C.c_double)), dsarr, dnarr, dyarr)
+    return _GradBatchCall("gp_logpdf_grad_batch", nb, g.nx, g.ny, args, fit.out, fit.info, dvar, dscale, None, None, dnoise, dy, kinds, m)
+
+
+def logpdf_and_grad_batch(fxs, ys, *, on_error: str = "raise"):
+    """Value and gradient of logpdf(fx_b, y_b) of many independent exact GPs in one library call per (ctx, dtype, single-kind / composite) group —
+    what multi-start hyper-parameter optimisation, gradient-based samplers over hyper-parameters and per-fold training evaluate at every step.  fxs, ys
+    as in logpdf_batch (the same x / y object in every entry is sent once).  Returns (array of logpdf, list of dicts in the caller's order); each dict
+    is that of logpdf_and_grad without "x": {"variance", "scale", "noise", "y", "mean"} for a single-kind kernel, {"kernel", "theta", "noise", "y",
+    "mean"} for a composite one.  on_error = "raise": the PosDefException of the first failing problem (.info, .index); "nan": NaN in its logpdf and in
+    every entry of its gradient."""
+    if on_error not in ("raise", "nan"):
+        raise ValueError('on_error must be "raise" or "nan"')
+    fxs = list(fxs)
+    if not fxs:
+        return np.empty(0), []
+    grads = [None] * len(fxs)
+    parts = []
+    for g in _batch_groups(fxs, ys):
+        call = _grad_batch_marshal(g)
+        ctx = g.ctx or default_context()
+        check(getattr(ctx.lib, call.entry)(ctx.handle, *call.args))
+        parts.append((g.index, call.out, call.info, None))
+        for j, i in enumerate(g.index):
+            dn = call.dnoise[j][0] if call.noise_kind[j] == 0 else call.dnoise[j]
+            tail = {"noise": dn, "y": call.dy[j], "mean": -call.dy[j]}
+            if g.composite:
+                grads[i] = {"kernel": call.nfs[j].chain(call.dtheta[j]), "theta": call.dtheta[j], **tail}
+            else:
+                sc = call.dscale[j]
+                grads[i] = {"variance": float(call.dvar[j]), "scale": None if sc is None else (float(sc[0]) if sc.shape[0] == 1 else sc), **tail}
+    return _batch_merge(len(fxs), parts, False, on_error), grads
+
+
 def loglikelihood(fx: FiniteGP, Y):  # src/finite_gp_projection.jl:304
     return np.sum(logpdf(fx, Y))
 

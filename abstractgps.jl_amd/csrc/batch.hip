@@ -1,6 +1,7 @@
-// batch.hip — many small exact GPs in one call: gp_logpdf_batch / gp_logpdf_batch_sum, gp_predict_batch / gp_predict_batch_sum (include/gpmi355.h) and the
-// two kernels behind them: the fit (batch_logpdf_kernel, below) and the predictions at each problem's test points from the slices it leaves
-// (batch_predict_kernel, further down).
+// batch.hip — many small exact GPs in one call: gp_logpdf_batch / gp_logpdf_batch_sum, gp_predict_batch / gp_predict_batch_sum, gp_logpdf_grad_batch /
+// gp_logpdf_grad_batch_sum (include/gpmi355.h) and the kernels behind them: the fit (batch_logpdf_kernel, below), the predictions at each problem's test
+// points from the slices it leaves (batch_predict_kernel, further down) and the gradient from the same slices (batch_inv_kernel, batch_grad_kernel,
+// batch_gsum_kernel, behind it).
 //
 // ONE workgroup owns ONE problem from its inputs to its scalar: it assembles the lower triangle of K + Σy into the problem's slice of a
 // workspace (δ = y − m riding along as row np, as in the single path), factors it by a blocked right-looking Cholesky (64-column blocks:
@@ -464,6 +465,336 @@ __global__ __launch_bounds__(NT) void batch_predict_kernel(const double* __restr
         }
         var_o[tid] = kss - ss;
     }
+}
+
+// ---- the gradient of logpdf: batch_inv_kernel, batch_grad_kernel, batch_gsum_kernel -----------------------------------------------------------------
+// Launched behind batch_logpdf_kernel on the same stream, on the slices it left (L in the lower triangle of rows [0, np), α in the result buffer):
+//   ∂logpdf/∂θ = ½ Σ_ij (α_i α_j − C⁻¹_ij) ∂C_ij/∂θ,   C⁻¹ = S Sᵀ with S = L⁻ᵀ (upper triangular).
+// A problem spreads over many workgroups and launch boundaries are the only synchronisation: no flags, no tickets, no floating-point atomics; every sum
+// runs in an order that the problem's size alone fixes, so a problem's gradient is the same bits alone, anywhere in any batch, and on repetition.
+enum {
+    GNT = 256,     // threads per workgroup of batch_grad_kernel: four waves, one 32×32 MFMA tile of the 64×64 tile each; the thread count ksum_grad's slots are sized for
+    GRAD_NP = 16,  // θ entries of a composite kernel per pass over the tile (their per-thread sums live in LDS slots)
+    GRAD_MAXG = 1 + KSum::MAXTH  // sums per problem at most: the noise sum, then the kernel's parameters
+};
+
+// What the gradient kernels know of a problem beyond its BatchProb; same position in its table as the descriptor in the packed input.  Offsets count doubles:
+// s_off (the S strip, np rows of ld) and part_off (ntiles × ng per-tile sums) into the workspace, g_off (ng sums) and dn_off (n entries ½(α_i² − C⁻¹_ii) of a
+// diagonal Σy; −1: scalar noise) into the result buffer.  The sums: [0] noise, then single-kind [1] variance, [2 + p] scale_p; composite [1 + q] θ_q.
+struct GradProb {
+    long s_off, part_off, g_off, dn_off;
+    int ng, ntiles;
+};
+static_assert(sizeof(GradProb) % 8 == 0, "the tables are packed behind double data");
+// One workgroup's work: tile ti of 128 rows of S (batch_inv_kernel), or the 64×64 tile (ti >= tj) of the lower triangle (batch_grad_kernel; idx = its place
+// among the problem's tiles, ti (ti + 1) / 2 + tj)
+struct GradTile {
+    int prob, ti, tj, idx;
+};
+static_assert(sizeof(GradTile) % 8 == 0, "the tables are packed behind double data");
+
+// Rows [r0, r0 + 128) of S = L⁻ᵀ into the problem's strip: batch_predict_kernel's step 2 (V ← V L⁻ᵀ, left-looking by 64-column blocks, 32×32 MFMA wave tiles,
+// the diagonal block by substitution from LDS with one row per thread in registers) with V = the identity rows of the tile.  S is upper triangular: the
+// columns left of r0 are zero, never written and never read (the k loops start at r0; batch_grad_kernel reads row i from column 64·⌊i / 64⌋ ≥ r0 on).
+// A failed problem's tiles return at once: nothing of it is read or written here.
+__global__ __launch_bounds__(NT) void batch_inv_kernel(const double* __restrict__ in, double* __restrict__ ws, const double* __restrict__ res, int nw,
+                                                       const GradProb* __restrict__ gps, const GradTile* __restrict__ tiles) {
+    __shared__ double sh[BT * BTS + BT];  // L_bb [BT][BTS] and 1 / L_jj behind it
+    const GradTile& T = tiles[blockIdx.x];
+    const BatchProb& P = reinterpret_cast<const BatchProb*>(in)[T.prob];
+    const GradProb& G = gps[T.prob];
+    if (res[nw + P.slot] != 0.0) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int np = P.np, r0 = T.ti * TP;
+    const long ld = P.ld;
+    const int nt = np / BT, rows = np - r0 < TP ? np - r0 : TP;  // 64 or 128
+    const double* __restrict__ A = ws + P.a_off;
+    double* __restrict__ V = ws + G.s_off + (long)r0 * ld;
+    {
+        const int wc = np - r0;
+        for (int e = tid; e < rows * wc; e += NT) {
+            const int i = e / wc, cc = e - i * wc;
+            V[(long)i * ld + r0 + cc] = i == cc ? 1.0 : 0.0;
+        }
+    }
+    __syncthreads();
+    double (*Ls)[BTS] = reinterpret_cast<double (*)[BTS]>(sh);
+    double* dinv = sh + BT * BTS;
+    const int r = lane & 15, g = lane >> 4;
+    for (int kb = r0 / BT; kb < nt; ++kb) {
+        const int j0 = kb * BT;
+        // Lane l = (r = l & 15, g = l >> 4) holds 16 consecutive k of rows r and 16 + r of both operands; MFMA step s multiplies the k-quadruple {16 g + s}.
+        for (int tile = w; tile < (rows / 32) * 2 && j0 > r0; tile += 8) {
+            const int i0 = 32 * (tile >> 1), c0 = j0 + 32 * (tile & 1);
+            d4_t acc[2][2];
+#pragma unroll
+            for (int hi = 0; hi < 2; ++hi)
+#pragma unroll
+                for (int hj = 0; hj < 2; ++hj)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) acc[hi][hj][q] = V[(long)(i0 + 16 * hi + Tr<double>::crow(lane, q)) * ld + c0 + 16 * hj + r];
+            for (int k0 = r0; k0 < j0; k0 += BT) {
+                double a[2][16], b[2][16];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const d2_t* pa = reinterpret_cast<const d2_t*>(V + (long)(i0 + 16 * h + r) * ld + k0 + 16 * g);
+                    const d2_t* pb = reinterpret_cast<const d2_t*>(A + (long)(c0 + 16 * h + r) * ld + k0 + 16 * g);
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        const d2_t ta = pa[q], tb = pb[q];
+                        a[h][2 * q] = -ta.x;
+                        a[h][2 * q + 1] = -ta.y;
+                        b[h][2 * q] = tb.x;
+                        b[h][2 * q + 1] = tb.y;
+                    }
+                }
+#pragma unroll
+                for (int s = 0; s < 16; ++s)
+#pragma unroll
+                    for (int hi = 0; hi < 2; ++hi)
+#pragma unroll
+                        for (int hj = 0; hj < 2; ++hj) acc[hi][hj] = Tr<double>::mfma(a[hi][s], b[hj][s], acc[hi][hj]);
+            }
+#pragma unroll
+            for (int hi = 0; hi < 2; ++hi)
+#pragma unroll
+                for (int hj = 0; hj < 2; ++hj)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) V[(long)(i0 + 16 * hi + Tr<double>::crow(lane, q)) * ld + c0 + 16 * hj + r] = acc[hi][hj][q];
+        }
+        // the diagonal block: its lower triangle in LDS (the rest of the tile is not the factor's)
+        for (int e = tid; e < BT * BT; e += NT) {
+            const int rr = e >> 6, cc = e & 63;
+            Ls[rr][cc] = cc <= rr ? A[(long)(j0 + rr) * ld + j0 + cc] : 0.0;
+        }
+        __syncthreads();
+        if (tid < BT) dinv[tid] = 1.0 / Ls[tid][tid];
+        __syncthreads();
+        if (tid < rows) {  // X ← X L_bb⁻ᵀ, one row of S per thread in registers
+            d2_t* row = reinterpret_cast<d2_t*>(V + (long)tid * ld + j0);
+            double xv[BT];
+#pragma unroll
+            for (int q = 0; q < BT / 2; ++q) {
+                const d2_t t = row[q];
+                xv[2 * q] = t.x;
+                xv[2 * q + 1] = t.y;
+            }
+#pragma unroll
+            for (int j = 0; j < BT; ++j) {
+                xv[j] *= dinv[j];
+#pragma unroll
+                for (int k2 = j + 1; k2 < BT; ++k2) {
+                    xv[k2] = fma(-xv[j], Ls[k2][j], xv[k2]);
+                    if ((k2 & 15) == 15) __builtin_amdgcn_sched_barrier(0);  // as in the fit kernel: hoisted LDS reads spill
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < BT / 2; ++q) {
+                d2_t t;
+                t.x = xv[2 * q];
+                t.y = xv[2 * q + 1];
+                row[q] = t;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// The 64×64 tile (ti >= tj) of the lower triangle of one problem:
+//   1. C⁻¹_tile = Σ_{k ≥ 64 ti} S[i, k] S[j, k] by v_mfma_f64_16x16x4_f64, one 32×32 wave tile per wave, in the NT operand form of the fit kernel's trailing
+//      update (16 consecutive k per lane straight from the strip); the weights W_ij = (α_i α_j − C⁻¹_ij)·(i = j ? ½ : 1) of the pairs j ≤ i < n into LDS;
+//   2. Σ W_ij ∂C_ij/∂θ with ∂C_ij/∂θ re-evaluated from the packed inputs: thread = (column j = lane, rows w, w + 4, …), the column's inputs in registers, the
+//      row's by scalar loads.  Single-kind: variance and scales in registers (the sums of kgrad_kernel, the 1 / scale factor of ∂r² at the end); composite:
+//      ksum_grad, GRAD_NP θ entries per pass in per-thread LDS slots.  The diagonal adds W_ii to the noise sum; a diagonal Σy's entries are stored directly.
+//   3. the per-thread sums by a butterfly per wave, the four waves added in order, stored as this tile's ng sums (batch_gsum_kernel adds the tiles).
+// A failed problem's tiles return at once (batch_gsum_kernel writes its NaN): neither slice nor strip is read.
+template <bool SUM>
+__global__ __launch_bounds__(GNT) void batch_grad_kernel(const double* __restrict__ in, double* __restrict__ ws, double* __restrict__ res, int nw,
+                                                        const GradProb* __restrict__ gps, const GradTile* __restrict__ tiles) {
+    __shared__ double Wt[BT][BT];
+    __shared__ double acc[SUM ? GRAD_NP : 1][GNT];
+    __shared__ double kf[SUM ? KSum::MAXFT : 1][GNT];
+    __shared__ double red[4][2 + BATCH_MAXD];
+    const GradTile& T = tiles[blockIdx.x];
+    const BatchProb& P = reinterpret_cast<const BatchProb*>(in)[T.prob];
+    const GradProb& G = gps[T.prob];
+    if (res[nw + P.slot] != 0.0) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = P.n, np = P.np, d = P.d;
+    const long ld = P.ld;
+    const int it0 = T.ti * BT, jt0 = T.tj * BT;
+    const double* __restrict__ S = ws + G.s_off;
+    const double* __restrict__ alpha = res + P.alpha_off;
+    const double* __restrict__ x = in + P.x_off;
+    double* __restrict__ part = ws + G.part_off + (long)T.idx * G.ng;
+
+    // ---- 1. the weights of the tile
+    {
+        const int wi = w >> 1, wj = w & 1;
+        if (!(T.ti == T.tj && wj > wi)) {  // the wave tile strictly above the diagonal holds no pair j <= i
+            const int r = lane & 15, g = lane >> 4;
+            const int i0 = it0 + 32 * wi, c0 = jt0 + 32 * wj;
+            d4_t c4[2][2];
+#pragma unroll
+            for (int hi = 0; hi < 2; ++hi)
+#pragma unroll
+                for (int hj = 0; hj < 2; ++hj)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) c4[hi][hj][q] = 0.0;
+            for (int k0 = it0; k0 < np; k0 += BT) {
+                double a[2][16], b[2][16];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const d2_t* pa = reinterpret_cast<const d2_t*>(S + (long)(i0 + 16 * h + r) * ld + k0 + 16 * g);
+                    const d2_t* pb = reinterpret_cast<const d2_t*>(S + (long)(c0 + 16 * h + r) * ld + k0 + 16 * g);
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        const d2_t ta = pa[q], tb = pb[q];
+                        a[h][2 * q] = ta.x;
+                        a[h][2 * q + 1] = ta.y;
+                        b[h][2 * q] = tb.x;
+                        b[h][2 * q + 1] = tb.y;
+                    }
+                }
+#pragma unroll
+                for (int s = 0; s < 16; ++s)
+#pragma unroll
+                    for (int hi = 0; hi < 2; ++hi)
+#pragma unroll
+                        for (int hj = 0; hj < 2; ++hj) c4[hi][hj] = Tr<double>::mfma(a[hi][s], b[hj][s], c4[hi][hj]);
+            }
+#pragma unroll
+            for (int hi = 0; hi < 2; ++hi)
+#pragma unroll
+                for (int hj = 0; hj < 2; ++hj) {
+                    const int gj = c0 + 16 * hj + r;
+                    const double aj = gj < n ? alpha[gj] : 0.0;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int gi = i0 + 16 * hi + Tr<double>::crow(lane, q);
+                        double wv = 0.0;
+                        if (gi < n && gj <= gi) wv = (alpha[gi] * aj - c4[hi][hj][q]) * (gi == gj ? 0.5 : 1.0);
+                        Wt[gi - it0][gj - jt0] = wv;
+                    }
+                }
+        }
+    }
+    __syncthreads();
+
+    // ---- 2. the contraction
+    const int gj = jt0 + lane;
+    double xj[BATCH_MAXD];
+#pragma unroll
+    for (int p = 0; p < BATCH_MAXD; ++p) xj[p] = (p < d && gj < n) ? x[(long)p * n + gj] : 0.0;
+    double gn = 0.0;  // Σ W_ii
+    if (T.ti == T.tj) {
+        const int gi = it0 + tid;
+        if (tid < BT && gi < n) {
+            gn = Wt[tid][tid];
+            if (G.dn_off >= 0) res[G.dn_off + gi] = gn;
+        }
+    }
+    if (!SUM) {
+        double gv = 0.0, gs[BATCH_MAXD];
+#pragma unroll
+        for (int p = 0; p < BATCH_MAXD; ++p) gs[p] = 0.0;
+        const int nscale = P.nscale;
+        for (int rr = 0; rr < BT / 4; ++rr) {
+            const int li = w + 4 * rr, gi = it0 + li;  // wave-uniform
+            if (gi >= n) continue;
+            if (gj > gi) continue;  // gj <= gi < n
+            const double wgt = Wt[li][lane];
+            double u2[BATCH_MAXD], d2 = 0.0;
+#pragma unroll
+            for (int p = 0; p < BATCH_MAXD; ++p) {
+                const double t = p < d ? x[(long)p * n + gi] - xj[p] : 0.0;
+                const double u = (nscale == 0 ? 1.0 : P.scale[nscale == 1 ? 0 : p]) * t;
+                u2[p] = u * u;
+                d2 = fma(u, u, d2);
+            }
+            double kap, dk;
+            kappa_and_dr2<double>(P.kind, d2, kap, dk);
+            gv = fma(wgt, kap, gv);
+            const double wk = wgt * P.variance * dk * 2.0;
+            if (nscale == 1) {
+                gs[0] = fma(wk, d2, gs[0]);
+            } else if (nscale > 1) {
+#pragma unroll
+                for (int p = 0; p < BATCH_MAXD; ++p) gs[p] = fma(wk, u2[p], gs[p]);
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < 2 + BATCH_MAXD; ++p) {
+            double v = p == 0 ? gn : (p == 1 ? gv : gs[p >= 2 ? p - 2 : 0]);
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+            if (lane == 0) red[w][p] = v;
+        }
+        __syncthreads();
+        if (tid < G.ng) {
+            double v = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+            if (tid >= 2) v /= P.scale[tid - 2];  // the 1 / s (1 / v_p) factor of ∂r²
+            part[tid] = v;
+        }
+    } else {
+        const KSum& ks = *reinterpret_cast<const KSum*>(in + P.ks_off);
+        const int nth = ks.nth;
+        for (int p0 = 0; p0 < nth; p0 += GRAD_NP) {
+#pragma unroll
+            for (int p = 0; p < GRAD_NP; ++p) acc[p][tid] = 0.0;
+            auto add = [&](int idx, double v) {
+                const unsigned q = (unsigned)(idx - p0);
+                if (q < (unsigned)GRAD_NP) acc[q][tid] += v;
+            };
+#pragma unroll 1
+            for (int rr = 0; rr < BT / 4; ++rr) {
+                const int li = w + 4 * rr, gi = it0 + li;  // wave-uniform
+                if (gi >= n) continue;
+                if (gj > gi) continue;  // gj <= gi < n
+                double t[BATCH_MAXD];
+#pragma unroll
+                for (int p = 0; p < BATCH_MAXD; ++p) t[p] = p < d ? x[(long)p * n + gi] - xj[p] : 0.0;
+                ksum_grad<double, BATCH_MAXD>(ks, t, d, Wt[li][lane], add, kf, tid);
+            }
+            if (p0 == 0) {
+                double v = gn;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+                if (lane == 0) red[w][GRAD_NP] = v;
+            }
+#pragma unroll
+            for (int p = 0; p < GRAD_NP; ++p) {
+                double v = acc[p][tid];
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+                if (lane == 0) red[w][p] = v;
+            }
+            __syncthreads();
+            if (tid < GRAD_NP && p0 + tid < nth) part[1 + p0 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+            if (tid == GRAD_NP && p0 == 0) part[0] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+            __syncthreads();
+        }
+    }
+}
+
+// The ng sums of every problem of a wave: one workgroup per problem adds its tiles in index order (thread = entry).  A failed problem gets NaN in every sum
+// and in the entries of a diagonal Σy's gradient; nothing of its workspace is read.
+__global__ __launch_bounds__(128) void batch_gsum_kernel(const double* __restrict__ in, const double* __restrict__ ws, double* __restrict__ res, int nw,
+                                                        const GradProb* __restrict__ gps) {
+    const BatchProb& P = reinterpret_cast<const BatchProb*>(in)[blockIdx.x];
+    const GradProb& G = gps[blockIdx.x];
+    const int tid = threadIdx.x;
+    if (res[nw + P.slot] != 0.0) {
+        if (tid < G.ng) res[G.g_off + tid] = __builtin_nan("");
+        if (G.dn_off >= 0)
+            for (int i = tid; i < P.n; i += 128) res[G.dn_off + i] = __builtin_nan("");
+        return;
+    }
+    if (tid >= G.ng) return;
+    const double* __restrict__ part = ws + G.part_off;
+    double s = 0.0;
+    for (int t = 0; t < G.ntiles; ++t) s += part[(long)t * G.ng + tid];
+    res[G.g_off + tid] = s;
 }
 
 }  // namespace gpmi
@@ -944,6 +1275,195 @@ int32_t predict_batch_impl(gp_ctx* c, PredictArgs& a) {
     return 0;
 }
 
+// ---- gp_logpdf_grad_batch / gp_logpdf_grad_batch_sum ---------------------------------------------------------------------------------------------------
+struct GradArgs : BatchArgs {
+    double* dvar;             // single-kind: nb entries, or NULL
+    double* const* dscale;    // single-kind: nb pointers, or NULL
+    double* const* dtheta;    // composite: nb pointers, or NULL
+    void* const* dnoise;
+    void* const* dy;
+    int arg0;                 // position of the first gradient argument (the reasons of the checks name the argument)
+    void* dnb(int b) const { return dnoise ? dnoise[b] : nullptr; }
+    void* dyb(int b) const { return dy ? dy[b] : nullptr; }
+};
+
+long batch_grad_max_n() {  // GPMI355_BATCH_GRAD_MAX_N; the environment variable GPMI_BATCH_GRAD_MAX_N (0 … what the kernels admit) overrides it for measurements
+    long v = GPMI355_BATCH_GRAD_MAX_N;
+    if (const char* e = getenv("GPMI_BATCH_GRAD_MAX_N")) v = atol(e);
+    return std::max(0L, std::min<long>(v, BATCH_KERNEL_MAX_N));
+}
+
+// the kernel parameters of problem b: variance + scales, or the θ entries of its composite kernel
+int grad_nkp(const GradArgs& a, const std::vector<KSum>& packed, int b) { return a.ks ? packed[b].nth : 1 + a.k[b].nscale; }
+long grad_ntiles(long n) { return batch_np(n) / BT * (batch_np(n) / BT + 1) / 2; }
+// workspace of a problem in a gradient wave: its slice, the S strip beside it and the per-tile sums
+long grad_ws(const GradArgs& a, const std::vector<KSum>& packed, int b) {
+    const long n = a.xb(b).n, np = batch_np(n);
+    return batch_slice(n) + np * batch_ld(np) + ((grad_ntiles(n) * (1 + grad_nkp(a, packed, b)) + 1) & ~1L);
+}
+
+// NaN in every gradient output of problem b (nkp kernel parameters)
+void grad_fill_nan(const GradArgs& a, int b, int nkp) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    const long n = a.xb(b).n;
+    if (a.dvar) a.dvar[b] = nan;
+    if (a.dscale && a.dscale[b]) std::fill_n(a.dscale[b], nkp - 1, nan);
+    if (a.dtheta) std::fill_n(a.dtheta[b], nkp, nan);
+    const int nk = a.noise[b].kind;
+    fill_nan(a.dnb(b), a.dtype, nk == 0 ? 1 : (nk == 1 ? n : n * n));
+    fill_nan(a.dyb(b), a.dtype, n);
+}
+
+// one wave: the fit launch of the problems idx[0..nw) with α for every one of them, then S = L⁻ᵀ, the tile sums and their totals.  Caller holds the ctx lock.
+int32_t run_grad_wave(gp_ctx* c, const GradArgs& a, const std::vector<KSum>& packed, const int* idx, int nw) {
+    WaveLayout L;
+    wave_layout(a, idx, nw, [](int) { return true; }, L);
+    // behind the fit's input: the GradProb table (in the order of the descriptors), the tiles of S and the tiles of the triangle, the widest problems first
+    std::vector<GradProb> gp((size_t)nw);
+    std::vector<GradTile> itiles, gtiles;
+    for (int s = 0; s < nw; ++s) {
+        const int t = L.order[s], b = idx[t];
+        const BatchProb& p = L.pr[t];
+        GradProb& g = gp[s];
+        const int nt = p.np / BT;
+        g.ng = 1 + grad_nkp(a, packed, b);
+        g.ntiles = nt * (nt + 1) / 2;
+        g.s_off = L.ws;
+        L.ws += (long)p.np * p.ld;
+        g.part_off = L.ws;
+        L.ws += ((long)g.ntiles * g.ng + 1) & ~1L;  // the next strip stays 16-byte aligned
+        g.g_off = L.roff;
+        L.roff += g.ng;
+        g.dn_off = -1;
+        if (a.noise[b].kind == 1) {
+            g.dn_off = L.roff;
+            L.roff += p.n;
+        }
+        for (int r0 = 0; r0 < p.np; r0 += TP) itiles.push_back(GradTile{s, r0 / TP, 0, 0});
+        for (int ti = 0; ti < nt; ++ti)
+            for (int tj = 0; tj <= ti; ++tj) gtiles.push_back(GradTile{s, ti, tj, ti * (ti + 1) / 2 + tj});
+    }
+    const long gp_off = L.off;
+    L.off += (long)(gp.size() * sizeof(GradProb) / 8);
+    const long it_off = L.off;
+    L.off += (long)(itiles.size() * sizeof(GradTile) / 8);
+    const long gt_off = L.off;
+    L.off += (long)(gtiles.size() * sizeof(GradTile) / 8);
+
+    const size_t in_bytes = sizeof(double) * (size_t)L.off, out_bytes = sizeof(double) * (size_t)L.roff;
+    std::vector<double> pageable;
+    double* hin = wave_staging(c, (size_t)(L.off + L.roff), pageable);
+    double* hout = hin + L.off;
+    wave_fill(a, packed, idx, nw, L, hin);
+    std::memcpy(hin + gp_off, gp.data(), gp.size() * sizeof(GradProb));
+    std::memcpy(hin + it_off, itiles.data(), itiles.size() * sizeof(GradTile));
+    std::memcpy(hin + gt_off, gtiles.data(), gtiles.size() * sizeof(GradTile));
+    DevBufs bufs(c);
+    void *in_d = nullptr, *ws_d = nullptr, *res_d = nullptr;
+    RC(bufs.get(in_bytes, &in_d));
+    RC(bufs.get(sizeof(double) * (size_t)L.ws, &ws_d));
+    RC(bufs.get(out_bytes, &res_d));
+    RC(run_drained(c, [&]() -> int32_t {
+        const double* in = (const double*)in_d;
+        const GradProb* gps = reinterpret_cast<const GradProb*>(in + gp_off);
+        const GradTile* its = reinterpret_cast<const GradTile*>(in + it_off);
+        const GradTile* gts = reinterpret_cast<const GradTile*>(in + gt_off);
+        HIPCHK(hipMemcpyAsync(in_d, hin, in_bytes, hipMemcpyHostToDevice, c->sm));
+        if (a.ks) hipLaunchKernelGGL(batch_logpdf_kernel<true>, dim3((unsigned)nw), dim3(NT), 0, c->sm, in, (double*)ws_d, (double*)res_d, nw);
+        else hipLaunchKernelGGL(batch_logpdf_kernel<false>, dim3((unsigned)nw), dim3(NT), 0, c->sm, in, (double*)ws_d, (double*)res_d, nw);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(batch_inv_kernel, dim3((unsigned)itiles.size()), dim3(NT), 0, c->sm, in, (double*)ws_d, (const double*)res_d, nw, gps, its);
+        HIPCHK(hipGetLastError());
+        if (a.ks) hipLaunchKernelGGL(batch_grad_kernel<true>, dim3((unsigned)gtiles.size()), dim3(GNT), 0, c->sm, in, (double*)ws_d, (double*)res_d, nw, gps, gts);
+        else hipLaunchKernelGGL(batch_grad_kernel<false>, dim3((unsigned)gtiles.size()), dim3(GNT), 0, c->sm, in, (double*)ws_d, (double*)res_d, nw, gps, gts);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(batch_gsum_kernel, dim3((unsigned)nw), dim3(128), 0, c->sm, in, (const double*)ws_d, (double*)res_d, nw, gps);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(hout, res_d, out_bytes, hipMemcpyDeviceToHost, c->sm));
+        HIPCHK(hipStreamSynchronize(c->sm));
+        return 0;
+    }));
+    c->batch_grad_problems += nw;
+    std::vector<int> pos((size_t)nw);
+    for (int s = 0; s < nw; ++s) pos[L.order[s]] = s;
+    for (int t = 0; t < nw; ++t) {
+        const int b = idx[t];
+        const GradProb& g = gp[pos[t]];
+        const long n = L.pr[t].n;
+        put_result(a, b, hout[t], (int32_t)hout[nw + t]);
+        const double* G = hout + g.g_off;  // [0] noise, then the kernel's parameters
+        if (a.dvar) a.dvar[b] = G[1];
+        if (a.dscale && a.dscale[b]) std::memcpy(a.dscale[b], G + 2, sizeof(double) * (size_t)(g.ng - 2));
+        if (a.dtheta) std::memcpy(a.dtheta[b], G + 1, sizeof(double) * (size_t)(g.ng - 1));
+        if (double* dn = (double*)a.dnb(b)) {
+            if (g.dn_off >= 0) std::memcpy(dn, hout + g.dn_off, sizeof(double) * (size_t)n);
+            else dn[0] = G[0];
+        }
+        if (double* dy = (double*)a.dyb(b)) {
+            const double* al = hout + L.pr[t].alpha_off;
+            for (long j = 0; j < n; ++j) dy[j] = -al[j];
+        }
+    }
+    return 0;
+}
+
+int32_t grad_batch_impl(gp_ctx* c, GradArgs& a) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    if (a.nb < 0) return set_arg_err(2, "nb must be >= 0");
+    if (a.nb == 0) return 0;
+    RC(check_batch_head(a));
+    if (!a.logpdf_out) return set_arg_err(10, "logpdf_out is NULL");
+    if (!a.info_out) return set_arg_err(11, "info_out is NULL");
+    std::vector<KSum> packed;
+    RC(check_batch_problems(a, packed));
+    // a gradient array that is given holds a pointer for every problem (dscale: wherever the problem has scales)
+    const int a_dn = a.ks ? a.arg0 + 1 : a.arg0 + 2, a_dy = a_dn + 1;
+    for (int b = 0; b < a.nb; ++b) {
+        if (a.dscale && a.k[b].nscale > 0 && !a.dscale[b]) return set_arg_err(a.arg0 + 1, "a dscale_out pointer is NULL where the kernel has scales");
+        if (a.dtheta && !a.dtheta[b]) return set_arg_err(a.arg0, "a dtheta_out pointer is NULL");
+        if (a.dnoise && !a.dnoise[b]) return set_arg_err(a_dn, "a dnoise_out pointer is NULL");
+        if (a.dy && !a.dy[b]) return set_arg_err(a_dy, "a dy_out pointer is NULL");
+    }
+    // the path of a problem depends on that problem alone
+    const long max_n = batch_grad_max_n();
+    std::vector<int> mine, routed;
+    for (int b = 0; b < a.nb; ++b) (batch_takes(a, b, max_n) ? mine : routed).push_back(b);
+    if (!mine.empty()) {
+        HIPCHK(hipSetDevice(c->device));
+        size_t i = 0;
+        while (i < mine.size()) {  // waves bounded by the launch size and by the workspace budget: slices, strips and tile sums count
+            size_t j = i, bytes = 0;
+            while (j < mine.size() && j - i < BATCH_WAVE_PROBLEMS) {
+                const size_t s = sizeof(double) * (size_t)grad_ws(a, packed, mine[j]);
+                if (j > i && bytes + s > BATCH_WS_BYTES) break;
+                bytes += s;
+                ++j;
+            }
+            RC(run_grad_wave(c, a, packed, mine.data() + i, (int)(j - i)));
+            i = j;
+        }
+    }
+    // everything else: gp_logpdf_grad / gp_logpdf_grad_sum, one problem at a time, after the lock is released (as batch_impl does)
+    gd.lk.unlock();
+    const size_t es = a.dtype == 0 ? 8 : 4;
+    for (int b : routed) {
+        const gp_points& x = a.xb(b);
+        put(a.logpdf_out, a.dtype, b, 0);
+        void* lp = (char*)a.logpdf_out + es * (size_t)b;
+        const int32_t rc = a.ks ? gp_logpdf_grad_sum(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), lp, a.dtheta ? a.dtheta[b] : nullptr, a.dnb(b), a.dyb(b))
+                                : gp_logpdf_grad(c, &a.k[b], &x, &a.noise[b], a.mb(b), a.yb(b), lp, a.dvar ? &a.dvar[b] : nullptr,
+                                                 a.dscale ? a.dscale[b] : nullptr, a.dnb(b), a.dyb(b), nullptr);
+        if (rc < 0) return rc;
+        a.info_out[b] = rc;
+        if (rc > 0) {
+            put_result(a, b, std::numeric_limits<double>::quiet_NaN(), rc);
+            grad_fill_nan(a, b, grad_nkp(a, packed, b));
+        }
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -980,5 +1500,22 @@ int32_t gp_predict_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t 
     PredictArgs a{{nb, nullptr, k, nx, x, noise, mean_or_null, ny, y, logpdf_out_or_null, info_out, nullptr, 0}, nxs, xs, prior_mean_xs_or_null, what, mean_out, var_out};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return predict_batch_impl(ctx, a);
+}
+
+int32_t gp_logpdf_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                             const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
+                             double* dvariance_out_or_null, double* const* dscale_out_or_null, void* const* dnoise_out_or_null,
+                             void* const* dy_out_or_null) {
+    GradArgs a{{nb, k, nullptr, nx, x, noise, mean_or_null, ny, y, logpdf_out, info_out, nullptr, 0}, dvariance_out_or_null, dscale_out_or_null, nullptr, dnoise_out_or_null, dy_out_or_null, 12};
+    if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
+    return grad_batch_impl(ctx, a);
+}
+
+int32_t gp_logpdf_grad_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                                 const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
+                                 double* const* dtheta_out_or_null, void* const* dnoise_out_or_null, void* const* dy_out_or_null) {
+    GradArgs a{{nb, nullptr, k, nx, x, noise, mean_or_null, ny, y, logpdf_out, info_out, nullptr, 0}, nullptr, nullptr, dtheta_out_or_null, dnoise_out_or_null, dy_out_or_null, 12};
+    if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
+    return grad_batch_impl(ctx, a);
 }
 }

@@ -1,7 +1,7 @@
 // engine.hpp — internal interface shared by the translation units of libgpmi355.so:
 //   gpmi355.hip  kernels (kernels.hpp), the single-device engine and the C ABI
 //   multi.hip    the multi-device 2D block-cyclic driver (host code only: RCCL / peer copies + calls into the engine)
-//   batch.hip    many small problems in one call: the batch kernel (kfun.hpp) and gp_logpdf_batch / gp_logpdf_batch_sum
+//   batch.hip    many small problems in one call: the batch kernels (kfun.hpp) and gp_logpdf_batch, gp_predict_batch, gp_logpdf_grad_batch and their *_sum forms
 // Nothing here is part of the public ABI (include/gpmi355.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -171,6 +171,7 @@ struct gp_ctx {
     size_t pool_bytes = 0;
     size_t pool_cap = (size_t)96 << 30;        // bytes kept in the cache at most ("pool_cap_mb"; gp_ctx_trim drops it all)
     int alloc_poison = 0;                      // diagnostic: 1 = ctx_alloc (and the scal_dev / w_ws workspaces when created or grown) fills every block with 0xFF bytes before use
+    int64_t batch_grad_problems = 0;           // problems served by the gradient kernels of gp_logpdf_grad_batch / _sum (batch.hip): read-only "batch_grad_kernel_problems"
     long vfe_chunk = 0;                        // data points per streamed VFE chunk (multiple of vfe_ks); 0: automatic — 16 384 (measured best at C5) × a power of two for fewer pseudo-points (vfe.hpp)
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;

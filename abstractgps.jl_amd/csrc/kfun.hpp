@@ -1,5 +1,5 @@
 // kfun.hpp — the covariance functions as __device__ code, shared by every translation unit that evaluates a kernel on the device
-// (kernels.hpp: kmat / kvec / kgrad and their composite forms; batch.hip: the batched small-problem kernel).
+// (kernels.hpp: kmat / kvec / kgrad and their composite forms; batch.hip: the batched small-problem kernels), and the derivatives the gradient kernels of both share.
 #pragma once
 #include "engine.hpp"
 #include "kcommon.hpp"
@@ -120,6 +120,107 @@ __device__ __forceinline__ T ksum_eval(const KSum& k, const T (&t)[DR], int d) {
         sum += prod;
     }
     return sum;
+}
+
+// ---- derivatives: κ with dκ/dr² of the four radial kinds, and ∂C_ij/∂θ of a composite kernel (kgrad_* in kernels.hpp, batch_grad_kernel in batch.hip)
+//   dκ/dr²: SE −κ/2 · Matern12 −κ/(2r), 0 at r = 0 · Matern32 −(3/2)e^{−√3 r} · Matern52 −(5/6)(1+√5 r)e^{−√5 r}
+template <typename T> __device__ __forceinline__ void kappa_and_dr2(int kind, T d2, T& kap, T& dk) {
+    if (kind == 0) {
+        kap = exp_nonpos<T>(T(-0.5) * d2);
+        dk = T(-0.5) * kap;
+        return;
+    }
+    const T d = sqrt(d2);
+    if (kind == 1) {
+        kap = exp_nonpos<T>(-d);
+        dk = d > T(0) ? -kap / (T(2) * d) : T(0);
+        return;
+    }
+    if (kind == 2) {
+        const T a = T(1.7320508075688772935) * d, e = exp_nonpos<T>(-a);
+        kap = (T(1) + a) * e;
+        dk = T(-1.5) * e;
+        return;
+    }
+    const T a = T(2.2360679774997896964) * d, e = exp_nonpos<T>(-a);
+    kap = (T(1) + a + T(5.0 / 3.0) * d2) * e;
+    dk = T(-5.0 / 6.0) * (T(1) + a) * e;
+}
+
+// c·∂κ_f/∂θ_q for every parameter q of factor f (scale entries, then r / α), handed to add(θ index, value); kap = κ_f.
+//   kinds 0..3: ∂κ/∂d² as kappa_and_dr2;  RQ (q = d²/(2α)): ∂κ/∂d² = −κ/(2(1+q)), ∂κ/∂α = κ (q/(1+q) − log1p q);
+//   Periodic: ∂κ/∂r_p = κ sinpi(u_p)²/r_p³, ∂κ/∂u_p = −κ (π/2) sinpi(2u_p)/r_p²;  ∂d²/∂s = 2 s r², ∂d²/∂v_p = 2 v_p t_p², ∂u_p/∂s = t_p.
+template <typename T, int DR, class Add>
+__device__ __forceinline__ void ksum_factor_grad(const KSum& k, int f, const T (&t)[DR], T r2, T kap, int d, double c, Add& add) {
+    const int kind = k.kind[f], ns = k.ns[f];
+    if (kind == 6) return;
+    const double kp = (double)kap;
+    if (kind == 4) {
+        double dsum = 0.0;  // ScaleTransform: Σ_p ∂κ/∂u_p · t_p
+#pragma unroll
+        for (int p = 0; p < DR; ++p)
+            if (p < d) {
+                const T sc = ns == 0 ? T(1) : (T)k.th[k.so[f] + (ns == 1 ? 0 : p)];
+                const T u = sc * t[p];
+                const double r = k.th[k.po[f] + p], sp = (double)sinpi_t(u);
+                add(k.po[f] + p, c * kp * sp * sp / (r * r * r));
+                if (ns != 0) {
+                    const double du = -kp * 1.5707963267948966192 * (double)sinpi_t(T(2) * u) / (r * r);
+                    if (ns == 1) dsum += du * (double)t[p];
+                    else add(k.so[f] + p, c * du * (double)t[p]);
+                }
+            }
+        if (ns == 1) add(k.so[f], c * dsum);
+        return;
+    }
+    const T d2 = ksum_d2<T, DR>(k, f, t, r2, d);
+    double dk;
+    if (kind == 5) {
+        const double a = k.th[k.po[f]], q = (double)d2 / (2.0 * a);
+        dk = -kp / (2.0 * (1.0 + q));
+        add(k.po[f], c * kp * (q / (1.0 + q) - log1p(q)));
+    } else {
+        T kk, dkt;
+        kappa_and_dr2<T>(kind, d2, kk, dkt);
+        dk = (double)dkt;
+    }
+    if (ns == 1) {
+        add(k.so[f], c * dk * 2.0 * k.th[k.so[f]] * (double)r2);
+    } else if (ns > 1) {
+#pragma unroll
+        for (int p = 0; p < DR; ++p)
+            if (p < d) add(k.so[f] + p, c * dk * 2.0 * k.th[k.so[f] + p] * (double)t[p] * (double)t[p]);
+    }
+}
+
+// ∂C_ij/∂θ of one element, times the weight w, handed to add(θ index, value): σ_t² gets Π_f κ_f, a factor's parameters get σ_t² Π_{g≠f} κ_g ∂κ_f/∂θ —
+// the product over the other factors as a running prefix times a suffix product (dividing by κ_f would fail where it underflows to 0).  The κ_f of
+// the term wait in this thread's LDS slots kf[j][tid] (NTH = the threads of the workgroup, the stride of the slots: 256 in kernels.hpp, batch.hip's own): the factor loop stays a loop (unrolled over 4 factors, the element body of D = 16 grew
+// beyond what the compiler inlines and went to a call frame in scratch).
+template <typename T, int DR, class Add, int NTH>
+__device__ __forceinline__ void ksum_grad(const KSum& k, const T (&t)[DR], int d, double w, Add& add, double (*kf)[NTH], int tid) {
+    T r2;
+    bool eq;
+    ksum_r2<T, DR>(t, r2, eq);
+    for (int tt = 0; tt < k.nterms; ++tt) {
+        const int f0 = k.t0[tt], nf = k.t0[tt + 1] - f0;
+        double prod = 1.0;
+        for (int j = 0; j < nf; ++j) {
+            const double v = (double)ksum_factor<T, DR>(k, f0 + j, t, r2, eq, d);
+            kf[j][tid] = v;
+            prod *= v;
+        }
+        add(k.tv[tt], w * prod);
+        const double wv = w * k.th[k.tv[tt]];
+        double pre = 1.0;
+        for (int j = 0; j < nf; ++j) {
+            double suf = 1.0;
+            for (int i = j + 1; i < nf; ++i) suf *= kf[i][tid];
+            const double kj = kf[j][tid];
+            ksum_factor_grad<T, DR>(k, f0 + j, t, r2, (T)kj, d, wv * pre * suf, add);
+            pre *= kj;
+        }
+    }
 }
 
 }  // namespace gpmi

@@ -28,7 +28,7 @@ using KernelFunctions: SqExponentialKernel, Matern12Kernel, ExponentialKernel, M
 using LinearAlgebra, FillArrays, Statistics, StatsBase, Distributions, Random
 using ChainRulesCore
 
-export HipGP, HipPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, elbo_and_grad, logpdf_batch, mean_and_var_batch, BatchPosDefException
+export HipGP, HipPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, elbo_and_grad, logpdf_batch, mean_and_var_batch, logpdf_and_grad_batch, BatchPosDefException
 
 const libgpmi355 = get(ENV, "GPMI355_LIB", joinpath(@__DIR__, "..", "csrc", "libgpmi355.so"))
 
@@ -531,6 +531,80 @@ function mean_and_var_batch(fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys, xs; wh
     (on_error === :raise && bad !== nothing) && throw(BatchPosDefException(Int(info[bad]), bad))
     pairs = [(means[b], vars[b]) for b in 1:nb]
     return return_logpdf ? (pairs, lp) : pairs
+end
+
+# ---- the training half: gp_logpdf_grad_batch / gp_logpdf_grad_batch_sum ------------------------------------------------------------
+# logpdf_and_grad_batch(fxs, ys): value and gradient of logpdf(fxs[b], ys[b]) of independent exact GPs — the starts of a multi-start optimiser, the
+# chains of a gradient-based sampler over hyper-parameters, per-fold training — in ONE library call per (context, eltype, single-kind / composite)
+# group.  Returns (logpdfs, gradients in the caller's order); a gradient is the named tuple of logpdf_and_grad without `x`: (variance, scale, noise,
+# y, mean) for a single-kind kernel, (theta, kernel, noise, y, mean) for a composite one.  on_error as in logpdf_batch; :nan leaves NaN in the logpdf
+# and in every gradient entry of a failing problem.  Every problem must be one the ABI has a layout for (as logpdf_and_grad demands).
+function logpdf_and_grad_batch(fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys; on_error::Symbol=:raise)
+    on_error in (:raise, :nan) || throw(ArgumentError("on_error must be :raise or :nan"))
+    nb = length(fxs)
+    yv = (ys isa AbstractVector{<:Real}) ? fill(ys, nb) : collect(ys)
+    length(yv) == nb || throw(DimensionMismatch("$(nb) problems but $(length(yv)) observation vectors"))
+    args = [marshal(fxs[b], eltype(yv[b])) for b in 1:nb]
+    any(a -> a === nothing, args) && throw(ArgumentError("kernel / noise form is not accelerated"))
+    T = (nb > 0 && all(a -> a.T === Float32, args)) ? Float32 : Float64
+    lp = Vector{T}(undef, nb)
+    info = zeros(Int32, nb)
+    grads = Vector{Any}(nothing, nb)
+    groups = Dict{Any,Vector{Int}}()
+    for b in 1:nb
+        length(yv[b]) == length(fxs[b]) || throw(DimensionMismatch("problem $(b): length(fx) = $(length(fxs[b])) but y has $(length(yv[b])) entries"))
+        push!(get!(groups, (fxs[b].f.ctx, args[b].T, haskey(args[b], :ks)), Int[]), b)
+    end
+    for ((ctx, Tg, composite), idx) in groups
+        g = length(idx)
+        nx = all(b -> fxs[b].x === fxs[idx[1]].x, idx) ? 1 : g
+        ny = all(b -> yv[b] === yv[idx[1]], idx) ? 1 : g
+        cxs = [args[b].cx for b in idx[1:nx]]
+        cns = [args[b].cn for b in idx]
+        ybufs = [Vector{Tg}(yv[b]) for b in idx[1:ny]]
+        yptrs = Ptr{Cvoid}[pointer(v) for v in ybufs]
+        mptrs = Ptr{Cvoid}[args[b].m === nothing ? C_NULL : pointer(args[b].m) for b in idx]
+        out = Vector{Tg}(undef, g)
+        inf = zeros(Int32, g)
+        dnbufs = [dnoise_buffer(args[b].cn, Tg, length(fxs[b])) for b in idx]
+        dybufs = [Vector{Tg}(undef, length(fxs[b])) for b in idx]
+        dnptrs = Ptr{Cvoid}[pointer(v) for v in dnbufs]
+        dyptrs = Ptr{Cvoid}[pointer(v) for v in dybufs]
+        GC.@preserve args ybufs cxs cns yptrs mptrs out inf dnbufs dybufs dnptrs dyptrs begin
+            if composite
+                ks = [args[b].ks for b in idx]
+                dθs = [zeros(Float64, length(sum_theta(args[b].P, args[b].terms))) for b in idx]
+                dθptrs = Ptr{Float64}[pointer(v) for v in dθs]
+                GC.@preserve ks dθs dθptrs check(ccall((:gp_logpdf_grad_batch_sum, libgpmi355), Int32,
+                    (Ptr{Cvoid}, Int32, Ptr{CKSum}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32},
+                     Ptr{Ptr{Float64}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}),
+                    ctx.handle, g, ks, nx, cxs, cns, mptrs, ny, yptrs, out, inf, dθptrs, dnptrs, dyptrs))
+                for (j, b) in enumerate(idx)
+                    grads[b] = (theta=dθs[j], kernel=sum_chain(args[b].P, args[b].terms, dθs[j]), noise=cns[j].kind == 0 ? dnbufs[j][1] : dnbufs[j],
+                        y=dybufs[j], mean=-dybufs[j])
+                end
+            else
+                cks = [args[b].ck for b in idx]
+                dvars = zeros(Float64, g)
+                dss = [zeros(Float64, length(args[b].scales)) for b in idx]
+                dsptrs = Ptr{Float64}[isempty(v) ? Ptr{Float64}(C_NULL) : pointer(v) for v in dss]  # NULL where the kernel has no transform
+                GC.@preserve cks dvars dss dsptrs check(ccall((:gp_logpdf_grad_batch, libgpmi355), Int32,
+                    (Ptr{Cvoid}, Int32, Ptr{CKernel}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32},
+                     Ptr{Float64}, Ptr{Ptr{Float64}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}),
+                    ctx.handle, g, cks, nx, cxs, cns, mptrs, ny, yptrs, out, inf, dvars, dsptrs, dnptrs, dyptrs))
+                for (j, b) in enumerate(idx)
+                    grads[b] = (variance=dvars[j], scale=dss[j], noise=cns[j].kind == 0 ? dnbufs[j][1] : dnbufs[j], y=dybufs[j], mean=-dybufs[j])
+                end
+            end
+        end
+        for (j, b) in enumerate(idx)
+            lp[b] = out[j]
+            info[b] = inf[j]
+        end
+    end
+    bad = findfirst(!=(0), info)
+    (on_error === :raise && bad !== nothing) && throw(BatchPosDefException(Int(info[bad]), bad))
+    return lp, grads
 end
 
 function logpdf_terms(fx::FiniteGP{<:HipGP}, Y::Union{Nothing,AbstractVecOrMat{<:Real}}; logdet::Bool, sq::Bool)

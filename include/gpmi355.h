@@ -284,7 +284,9 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
  *                    workspaces when they are created or grown are filled with 0xFF bytes first — NaN read as fp64 or fp32, −1 as int32 — by a memset
  *                    on the main stream that is waited for.  No entry point may return anything that depends on what a block held before it wrote it
  *                    (tests/test_gpu_poisoned_blocks.py); forwarded to the rank contexts of a multi-device ctx; one not-taken branch per allocation when 0.   default 0
- *   "pool_cached_mb", "pool_blocks"   read-only (gp_ctx_get_param): MiB and number of blocks in the cache now */
+ *   "pool_cached_mb", "pool_blocks"   read-only (gp_ctx_get_param): MiB and number of blocks in the cache now
+ *   "batch_grad_kernel_problems"      read-only (gp_ctx_get_param): the problems the gradient kernels of gp_logpdf_grad_batch / _sum have served on this ctx
+ *                    since it was created (the problems routed to the single path do not count): which path ran, for tests and measurements */
 /* The defaults above, machine-readable (single-device parameters; gp_ctx_get_param reads the same names): the test-suite asserts before
  * every GPU test that the shared default context still has exactly these values, so that no test can leave a non-production setting
  * behind for the tests that follow it (tests/conftest.py). */
@@ -476,6 +478,48 @@ int32_t gp_predict_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t 
                              const void* const* mean_or_null, int32_t ny, const void* const* y, int32_t nxs, const gp_points* xs,
                              const void* const* prior_mean_xs_or_null, int32_t what, void* const* mean_out, void* const* var_out,
                              void* logpdf_out_or_null, int32_t* info_out);
+
+/* The training half of the batch calls: value AND gradient of logpdf for the same nb problems in ONE call — what multi-start hyper-parameter
+ * optimisation, gradient-based samplers over hyper-parameters, per-fold training and independent outputs sharing one x evaluate at every step (one
+ * gp_logpdf_grad call per problem otherwise).  Per problem the semantics are those of gp_logpdf_grad / gp_logpdf_grad_sum:
+ *   ∂/∂θ = ½ Σ_ij (α_i α_j − C⁻¹_ij) ∂C_ij/∂θ.
+ *   The arguments up to y are those of gp_logpdf_batch (same sharing through nx, ny ∈ {1, nb}, same checks); logpdf_out and info_out: nb entries.
+ *   Every gradient output is optional: a NULL array means that side is not wanted; an array that is given holds a pointer for every problem (a NULL
+ *   entry is an argument error, except in dscale_out where nscale_b = 0):
+ *     dvariance_out_or_null   double[nb]                          ∂/∂(kernel variance) of problem b
+ *     dscale_out_or_null      nb pointers, double[nscale_b] each   ∂/∂scale (may be NULL where nscale_b = 0)
+ *     dtheta_out_or_null      (gp_logpdf_grad_batch_sum) nb pointers, one double per θ entry of k_b in the order documented at gp_ksum
+ *     dnoise_out_or_null      nb pointers, call dtype: 1 entry (noise kind 0) ½(αᵀα − tr C⁻¹), n_b entries (kind 1) ½(α_i² − C⁻¹_ii), n_b × n_b entries
+ *                             (kind 2 / 3, as gp_logpdf_grad; such a problem runs on the single path)
+ *     dy_out_or_null          nb pointers, call dtype, n_b entries: ∂/∂y = −α_b
+ *   There is no ∂/∂x here: gp_logpdf_grad (dx_out) and gp_logpdf_grad_sum_x have it, one problem per call.
+ * Failure is data, as in the other batch calls: info_out[b] is the order of the first leading minor that is not positive, that problem's logpdf and every
+ * one of its gradient outputs are NaN, the other problems are not affected.  The return value reports argument errors only (−i, reason in
+ * gp_last_error(); nb = 0 returns 0 and touches nothing).
+ * fp64 problems with noise kind 0 / 1, D <= 16 and n_b <= GPMI355_BATCH_GRAD_MAX_N run as four kernels per wave (csrc/batch.hip): batch_logpdf_kernel (the
+ * fit, α always), then on the slices it left batch_inv_kernel — one workgroup per tile of 128 rows of S = L⁻ᵀ, the left-looking solve of the predict
+ * kernel on identity rows, into a strip beside the slice — batch_grad_kernel — one workgroup per 64×64 tile of the lower triangle: C⁻¹_tile = S_i S_jᵀ by
+ * fp64 MFMA, the weights ½(α_i α_j − C⁻¹_ij) (off-diagonal pairs doubled) contracted with ∂C_ij/∂θ re-evaluated from the packed inputs, partial sums per
+ * tile reduced in a fixed order — and batch_gsum_kernel, which adds a problem's tiles in index order.  A problem spreads over many workgroups, launch
+ * boundaries are the only synchronisation; no floating-point atomics, no waits between workgroups: a problem's gradient is the same bits alone, at any
+ * position of any batch, and on repetition.  The workspace of a wave (slices, S strips, per-tile sums) stays within the budget of the other batch calls.
+ * Every other problem (fp32, a dense Σy, a larger n_b or D) is answered inside the same call by gp_logpdf_grad / gp_logpdf_grad_sum; which path serves a
+ * problem depends on that problem alone.  The read-only ctx parameter "batch_grad_kernel_problems" counts the problems the kernels served.
+ * GPMI355_BATCH_GRAD_MAX_N: chosen by the rule that fixed GPMI355_BATCH_MAX_N — the largest multiple of 128 of the measured sweep
+ * (tools/batch_grad_profile.py, profiles/r20/batch_grad_profile.json: n = 64 … 2 048 × nb = 1, 8, 64, 512, SE, D = 3, scalar noise) for which ONE
+ * gp_logpdf_grad_batch call beat the loop of gp_logpdf_grad calls in every cell with nb >= 8.  The nb = 8 cells decide it: 1 024 points 8.13 ms against
+ * 9.74 ms, 2 048 points 44.0 ms against 18.5 ms (no size between the two was measured); at nb = 64 and 512 the batch call wins every size of the sweep (2 048
+ * points: 121.6 against 148.2 ms, 680 against 1 186 ms), a single problem loses from 256 points on (0.65 against 0.43 ms), as it does in the other batch calls.  (The environment variable
+ * GPMI_BATCH_GRAD_MAX_N, 0 … 2 048 = what the kernels admit, read per call, overrides it for measurements.) */
+#define GPMI355_BATCH_GRAD_MAX_N 1024
+int32_t gp_logpdf_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                             const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
+                             double* dvariance_out_or_null, double* const* dscale_out_or_null, void* const* dnoise_out_or_null,
+                             void* const* dy_out_or_null);
+/* The same with one composite kernel (gp_ksum) per problem. */
+int32_t gp_logpdf_grad_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                                 const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
+                                 double* const* dtheta_out_or_null, void* const* dnoise_out_or_null, void* const* dy_out_or_null);
 
 /* Sequential conditioning, posterior(fx::FiniteGP{<:PosteriorGP}, y) (src/exact_gpr_posterior.jl:46-56): the resident
  * factor of `old` is extended by the bordered-Cholesky step update_chol (src/util/common_covmat_ops.jl:38-42):
