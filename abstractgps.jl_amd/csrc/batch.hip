@@ -5,8 +5,9 @@
 //
 // ONE workgroup owns ONE problem from its inputs to its scalar: it assembles the lower triangle of K + Σy into the problem's slice of a
 // workspace (δ = y − m riding along as row np, as in the single path), factors it by a blocked right-looking Cholesky (64-column blocks:
-// diagonal block in LDS, rows below by substitution in registers, trailing update by v_mfma_f64_16x16x4_f64 on 32×32 wave tiles with
-// register-resident operands), reads ‖L⁻¹δ‖² off the carried row and, when α is wanted, runs the backward sweep on the same slice.
+// diagonal block in LDS, rows below by substitution in registers: rows_solve_b64; trailing update by v_mfma_f64_16x16x4_f64 on 32×32 wave tiles with
+// register-resident operands: mfma_tile_k64), reads ‖L⁻¹δ‖² off the carried row and, when α is wanted, runs the backward sweep on the same slice.
+// The tile operations the kernels share are defined once in front of the first kernel, the steps the host drivers share in front of the first driver.
 // Workgroups never wait for one another (no flags, no tickets: blockIdx.x is the problem), every loop is bounded by the problem's size, no
 // floating-point atomics are used and the schedule of a problem depends on that problem alone — its result is the same bits whatever
 // batch it rides in.  The slice of a problem (its factor and the solved row) stays intact until the call ends.
@@ -21,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <utility>
 #include <vector>
 
 namespace gpmi {
@@ -52,6 +54,148 @@ __host__ __device__ static inline long batch_np(long n) { return (n + BT - 1) / 
 __host__ __device__ static inline long batch_ld(long np) { return np + 16; }  // keeps power-of-two orders off one HBM channel
 static inline long batch_slice(long n) { return (batch_np(n) + 32) * batch_ld(batch_np(n)); }
 
+// ---- the tile operations the kernels below are made of: one definition each, inlined into every kernel that uses it ----------------------------------
+// the inputs of point j of x (dimension-major [d][n]) in registers: zeros beyond d and beyond n
+__device__ __forceinline__ void batch_load_point(const double* x, int n, int d, int j, double (&xj)[BATCH_MAXD]) {
+#pragma unroll
+    for (int p = 0; p < BATCH_MAXD; ++p) xj[p] = (p < d && j < n) ? x[(long)p * n + j] : 0.0;
+}
+// t = x_i − xj (point i of x, i < n; by scalar loads where i is wave-uniform)
+__device__ __forceinline__ void batch_diff(const double* x, int n, int d, int i, const double (&xj)[BATCH_MAXD], double (&t)[BATCH_MAXD]) {
+#pragma unroll
+    for (int p = 0; p < BATCH_MAXD; ++p) t[p] = p < d ? x[(long)p * n + i] - xj[p] : 0.0;
+}
+// the kernel value of problem P at the difference vector t: the composite kernel behind the descriptor, or variance · κ(Σ_p (scale_p t_p)²)
+template <bool SUM>
+__device__ __forceinline__ double batch_kval(const double* in, const BatchProb* P, const double (&t)[BATCH_MAXD], int d) {
+    if (SUM) return ksum_eval<double, BATCH_MAXD>(*reinterpret_cast<const KSum*>(in + P->ks_off), t, d);
+    double d2 = 0.0;
+#pragma unroll
+    for (int p = 0; p < BATCH_MAXD; ++p) {
+        const double u = (P->nscale == 0 ? 1.0 : P->scale[P->nscale == 1 ? 0 : p]) * t[p];
+        d2 = fma(u, u, d2);
+    }
+    return P->variance * kappa<double>(P->kind, d2);
+}
+
+// The 2×2×4 fp64 accumulators of a 32×32 wave tile (v_mfma_f64_16x16x4_f64), from and to the tile of C whose corner is (i0, c0).
+__device__ __forceinline__ void acc_zero(d4_t (&acc)[2][2]) {
+#pragma unroll
+    for (int h = 0; h < 4; ++h) acc[h >> 1][h & 1] = 0.0;
+}
+__device__ __forceinline__ void acc_load(d4_t (&acc)[2][2], const double* C, int i0, int c0, long ld, int lane) {
+#pragma unroll
+    for (int h = 0; h < 4; ++h)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[h >> 1][h & 1][q] = C[(long)(i0 + 16 * (h >> 1) + Tr<double>::crow(lane, q)) * ld + c0 + 16 * (h & 1) + (lane & 15)];
+}
+__device__ __forceinline__ void acc_store(const d4_t (&acc)[2][2], double* C, int i0, int c0, long ld, int lane) {
+#pragma unroll
+    for (int h = 0; h < 4; ++h)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) C[(long)(i0 + 16 * (h >> 1) + Tr<double>::crow(lane, q)) * ld + c0 + 16 * (h & 1) + (lane & 15)] = acc[h >> 1][h & 1][q];
+}
+// The register-resident operands of one 64-wide k block of a wave tile: rows i0 … i0 + 31 of A and c0 … c0 + 31 of B, columns k0 … k0 + 63.  Lane l = (r = l & 15,
+// g = l >> 4) holds 16 consecutive k of rows r and 16 + r of both operands (eight d2_t per half-row); MFMA step s multiplies the k-quadruple {16 g + s}: the sum
+// over the block is complete after 16 steps, in a fixed order.  Row indices stay ints up to the product with ld, as the kernels always had them.
+template <bool NEG_A>
+__device__ __forceinline__ void tile_operands_k64(double (&a)[2][16], double (&b)[2][16], const double* A, int i0, const double* B, int c0, int k0, long ld, int lane) {
+    const int r = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const d2_t* pa = reinterpret_cast<const d2_t*>(A + (long)(i0 + 16 * h + r) * ld + k0 + 16 * g);
+        const d2_t* pb = reinterpret_cast<const d2_t*>(B + (long)(c0 + 16 * h + r) * ld + k0 + 16 * g);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const d2_t ta = pa[q], tb = pb[q];
+            a[h][2 * q] = NEG_A ? -ta.x : ta.x;
+            a[h][2 * q + 1] = NEG_A ? -ta.y : ta.y;
+            b[h][2 * q] = tb.x;
+            b[h][2 * q + 1] = tb.y;
+        }
+    }
+}
+__device__ __forceinline__ void tile_mfma_k64(d4_t (&acc)[2][2], const double (&a)[2][16], const double (&b)[2][16]) {
+#pragma unroll
+    for (int s = 0; s < 16; ++s)
+#pragma unroll
+        for (int hi = 0; hi < 2; ++hi)
+#pragma unroll
+            for (int hj = 0; hj < 2; ++hj) acc[hi][hj] = Tr<double>::mfma(a[hi][s], b[hj][s], acc[hi][hj]);
+}
+// acc ±= A Bᵀ over one 64-wide k block: the operands, then the 16 steps
+template <bool NEG_A>
+__device__ __forceinline__ void mfma_tile_k64(d4_t (&acc)[2][2], const double* A, int i0, const double* B, int c0, int k0, long ld, int lane) {
+    double a[2][16], b[2][16];
+    tile_operands_k64<NEG_A>(a, b, A, i0, B, c0, k0, ld, lane);
+    tile_mfma_k64(acc, a, b);
+}
+
+// X ← X L_bb⁻ᵀ for the rows row0 + tid, row0 + tid + NT, … < row0 + nrows of X, columns col0 … col0 + 63, one row per thread: its 64 entries in registers, the
+// lower triangle of L_bb and 1 / L_jj in LDS.  Returns ss + Σ of the squares of the solved entries, in column order (unused, the chain is dropped).  The row
+// loop is part of the helper: a helper for ONE row, the loop at the call sites, compiled to 256 VGPRs and 12.9 KB of scratch per lane (this form: none).
+__device__ __forceinline__ double rows_solve_b64(double* X, long ld, int row0, int col0, int nrows, int tid, const double (*Ls)[BTS], const double* dinv, double ss) {
+    for (int rr = tid; rr < nrows; rr += NT) {
+        d2_t* row = reinterpret_cast<d2_t*>(X + (long)(row0 + rr) * ld + col0);
+        double xv[BT];
+#pragma unroll
+        for (int q = 0; q < BT / 2; ++q) {
+            const d2_t t = row[q];
+            xv[2 * q] = t.x;
+            xv[2 * q + 1] = t.y;
+        }
+#pragma unroll
+        for (int j = 0; j < BT; ++j) {
+            xv[j] *= dinv[j];
+#pragma unroll
+            for (int k2 = j + 1; k2 < BT; ++k2) {
+                xv[k2] = fma(-xv[j], Ls[k2][j], xv[k2]);
+                if ((k2 & 15) == 15) __builtin_amdgcn_sched_barrier(0);  // keeps the LDS reads of a step next to their fma: hoisted, they spill
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < BT / 2; ++q) {
+            d2_t t;
+            t.x = xv[2 * q];
+            t.y = xv[2 * q + 1];
+            row[q] = t;
+            ss = fma(t.x, t.x, ss);
+            ss = fma(t.y, t.y, ss);
+        }
+    }
+    return ss;
+}
+
+// V ← V L⁻ᵀ for a strip V of `rows` rows (at most NT; columns left of k_lo zero and never touched), left-looking by 64-column blocks:
+// V[:, j0:j0+64] −= V[:, k_lo:j0] L[j0:j0+64, k_lo:j0]ᵀ on 32×32 wave tiles (the rows rounded up to 32), the k loop running inside the accumulators, then the
+// diagonal block by rows_solve_b64, one row per thread.  sh holds L_bb [BT][BTS] and 1 / L_jj behind it.  Returns Σ_k V_{tid,k}² of the solved row tid.
+__device__ __forceinline__ double strip_solve(double* V, const double* A, long ld, int k_lo, int nt, int rows, double* sh, int tid, int lane, int w) {
+    double (*Ls)[BTS] = reinterpret_cast<double (*)[BTS]>(sh);
+    double* dinv = sh + BT * BTS;
+    double ss = 0.0;
+    for (int kb = k_lo / BT; kb < nt; ++kb) {
+        const int j0 = kb * BT;
+        for (int tile = w; tile < (rows + 31) / 32 * 2 && j0 > k_lo; tile += 8) {
+            const int i0 = 32 * (tile >> 1), c0 = j0 + 32 * (tile & 1);
+            d4_t acc[2][2];
+            acc_load(acc, V, i0, c0, ld, lane);
+            for (int k0 = k_lo; k0 < j0; k0 += BT) mfma_tile_k64<true>(acc, V, i0, A, c0, k0, ld, lane);
+            acc_store(acc, V, i0, c0, ld, lane);
+        }
+        // the diagonal block: its lower triangle in LDS (the rest of the tile is not the factor's)
+        for (int e = tid; e < BT * BT; e += NT) {
+            const int rr = e >> 6, cc = e & 63;
+            Ls[rr][cc] = cc <= rr ? A[(long)(j0 + rr) * ld + j0 + cc] : 0.0;
+        }
+        __syncthreads();
+        if (tid < BT) dinv[tid] = 1.0 / Ls[tid][tid];
+        __syncthreads();
+        ss = rows_solve_b64(V, ld, 0, j0, rows, tid, Ls, dinv, ss);
+        __syncthreads();
+    }
+    return ss;
+}
+
 template <bool SUM>
 __global__ __launch_bounds__(NT) void batch_logpdf_kernel(const double* __restrict__ in, double* __restrict__ ws, double* __restrict__ res, int nw) {
     __shared__ double Ls[BT][BTS];
@@ -71,8 +215,7 @@ __global__ __launch_bounds__(NT) void batch_logpdf_kernel(const double* __restri
         for (int tj = 0; tj <= ti; ++tj) {
             const int j = tj * BT + lane;
             double xj[BATCH_MAXD];
-#pragma unroll
-            for (int p = 0; p < BATCH_MAXD; ++p) xj[p] = (p < d && j < n) ? x[(long)p * n + j] : 0.0;
+            batch_load_point(x, n, d, j, xj);
             for (int rr = 0; rr < BT / 8; ++rr) {
                 const int i = ti * BT + w + 8 * rr;  // wave-uniform
                 double v;
@@ -80,19 +223,8 @@ __global__ __launch_bounds__(NT) void batch_logpdf_kernel(const double* __restri
                     v = (i == j) ? 1.0 : 0.0;
                 } else {
                     double t[BATCH_MAXD];
-#pragma unroll
-                    for (int p = 0; p < BATCH_MAXD; ++p) t[p] = p < d ? x[(long)p * n + i] - xj[p] : 0.0;
-                    if (SUM) {
-                        v = ksum_eval<double, BATCH_MAXD>(*reinterpret_cast<const KSum*>(in + P.ks_off), t, d);
-                    } else {
-                        double d2 = 0.0;
-#pragma unroll
-                        for (int p = 0; p < BATCH_MAXD; ++p) {
-                            const double u = (P.nscale == 0 ? 1.0 : P.scale[P.nscale == 1 ? 0 : p]) * t[p];
-                            d2 = fma(u, u, d2);
-                        }
-                        v = P.variance * kappa<double>(P.kind, d2);
-                    }
+                    batch_diff(x, n, d, i, xj, t);
+                    v = batch_kval<SUM>(in, &P, t, d);
                     if (i == j) v += P.nz_off >= 0 ? in[P.nz_off + i] : P.noise_s;
                 }
                 A[(long)i * ld + j] = v;
@@ -147,78 +279,22 @@ __global__ __launch_bounds__(NT) void batch_logpdf_kernel(const double* __restri
 
         // rows below the block (the δ row np included): X ← X L⁻ᵀ, one row per thread in registers
         const int r_lo = j0 + BT;
-        for (int rr = tid; rr < np + 1 - r_lo; rr += NT) {
-            d2_t* row = reinterpret_cast<d2_t*>(A + (long)(r_lo + rr) * ld + j0);
-            double xv[BT];
-#pragma unroll
-            for (int q = 0; q < BT / 2; ++q) {
-                const d2_t t = row[q];
-                xv[2 * q] = t.x;
-                xv[2 * q + 1] = t.y;
-            }
-#pragma unroll
-            for (int j = 0; j < BT; ++j) {
-                xv[j] *= dinv[j];
-#pragma unroll
-                for (int k2 = j + 1; k2 < BT; ++k2) {
-                    xv[k2] = fma(-xv[j], Ls[k2][j], xv[k2]);
-                    if ((k2 & 15) == 15) __builtin_amdgcn_sched_barrier(0);  // keeps the LDS reads of a step next to their fma: hoisted, they spill
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < BT / 2; ++q) {
-                d2_t t;
-                t.x = xv[2 * q];
-                t.y = xv[2 * q + 1];
-                row[q] = t;
-            }
-        }
+        (void)rows_solve_b64(A, ld, r_lo, j0, np + 1 - r_lo, tid, Ls, dinv, 0.0);
         __syncthreads();
 
-        // trailing update C −= P Pᵀ on 32×32 wave tiles.  Lane l = (r = l & 15, g = l >> 4) holds 16 consecutive k of rows r and 16 + r of
-        // both operands; MFMA step s multiplies the k-quadruple {16 g + s}: the sum over k is complete after 16 steps, in a fixed order.
+        // trailing update C −= P Pᵀ on 32×32 wave tiles (the lower triangle and the δ row's tiles), dealt round-robin to the eight waves
         const int ntr = (np + 32 - r_lo) / 32, ntc = (np - r_lo) / 32;
-        const int r = lane & 15, g = lane >> 4;
         int cnt = 0;
         for (int ti = 0; ti < ntr; ++ti)
             for (int tj = 0; tj <= ti && tj < ntc; ++tj) {
                 if ((cnt++ & 7) != w) continue;
                 const int i0 = r_lo + 32 * ti, c0 = r_lo + 32 * tj;
                 double a[2][16], b[2][16];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const d2_t* pa = reinterpret_cast<const d2_t*>(A + (long)(i0 + 16 * h + r) * ld + j0 + 16 * g);
-                    const d2_t* pb = reinterpret_cast<const d2_t*>(A + (long)(c0 + 16 * h + r) * ld + j0 + 16 * g);
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const d2_t ta = pa[q], tb = pb[q];
-                        a[h][2 * q] = -ta.x;
-                        a[h][2 * q + 1] = -ta.y;
-                        b[h][2 * q] = tb.x;
-                        b[h][2 * q + 1] = tb.y;
-                    }
-                }
                 d4_t acc[2][2];
-#pragma unroll
-                for (int hi = 0; hi < 2; ++hi)
-#pragma unroll
-                    for (int hj = 0; hj < 2; ++hj)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            acc[hi][hj][q] = A[(long)(i0 + 16 * hi + Tr<double>::crow(lane, q)) * ld + c0 + 16 * hj + r];
-#pragma unroll
-                for (int s = 0; s < 16; ++s)
-#pragma unroll
-                    for (int hi = 0; hi < 2; ++hi)
-#pragma unroll
-                        for (int hj = 0; hj < 2; ++hj) acc[hi][hj] = Tr<double>::mfma(a[hi][s], b[hj][s], acc[hi][hj]);
-#pragma unroll
-                for (int hi = 0; hi < 2; ++hi)
-#pragma unroll
-                    for (int hj = 0; hj < 2; ++hj)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            A[(long)(i0 + 16 * hi + Tr<double>::crow(lane, q)) * ld + c0 + 16 * hj + r] = acc[hi][hj][q];
+                tile_operands_k64<true>(a, b, A, i0, A, c0, j0, ld, lane);
+                acc_load(acc, A, i0, c0, ld, lane);
+                tile_mfma_k64(acc, a, b);
+                acc_store(acc, A, i0, c0, ld, lane);
             }
         __syncthreads();
     }
@@ -295,9 +371,7 @@ static_assert(sizeof(BatchTile) % 8 == 0, "the tile table is packed behind doubl
 // over many workgroups and none of them waits for another.
 //   1. cross-Gram rows K(x*_tile, x) into the workgroup's own strip (TP × ld, zeros in the padded columns and in the rows beyond the tile), the mean
 //      Σ_i K*_ji α_i in the same pass: lane = training point, per-lane partial sums over the 64-column tiles in LDS, then a tree;
-//   2. V ← V L⁻ᵀ left-looking by 64-column blocks: V[:, j0:j0+64] −= V[:, 0:j0] L[j0:j0+64, 0:j0]ᵀ by v_mfma_f64_16x16x4_f64 on 32×32 wave tiles (the operand
-//      form of the fit kernel's trailing update, the k loop running over [0, j0) inside the accumulators), then the diagonal block by substitution: L_bb in
-//      LDS, one test point per thread in registers;
+//   2. V ← V L⁻ᵀ by strip_solve from column 0: one test point per thread in the substitution;
 //   3. var_j = k** − Σ_i V_ji², summed by the thread that owns the row, block after block.
 // Every row's arithmetic touches no other row: a test point's results are the same bits wherever it sits.  A failed problem's tiles write NaN and never
 // read the slice.  Only what this call wrote is read: the lower triangle of the slice rows [0, np), and of the strip the rows of the tile rounded up to 32.
@@ -332,27 +406,15 @@ __global__ __launch_bounds__(NT) void batch_predict_kernel(const double* __restr
     for (int tj = 0; tj < nt; ++tj) {
         const int j = tj * BT + lane;
         double xj[BATCH_MAXD];
-#pragma unroll
-        for (int p = 0; p < BATCH_MAXD; ++p) xj[p] = (p < d && j < n) ? x[(long)p * n + j] : 0.0;
+        batch_load_point(x, n, d, j, xj);
         const double aj = (alpha && j < n) ? alpha[j] : 0.0;
         for (int rr = 0; rr < rp / 8; ++rr) {
             const int i = w + 8 * rr;  // wave-uniform
             double v = 0.0;
             if (i < rows && j < n) {
                 double t[BATCH_MAXD];
-#pragma unroll
-                for (int p = 0; p < BATCH_MAXD; ++p) t[p] = p < d ? xs[(long)p * ns + i] - xj[p] : 0.0;
-                if (SUM) {
-                    v = ksum_eval<double, BATCH_MAXD>(*reinterpret_cast<const KSum*>(in + P.ks_off), t, d);
-                } else {
-                    double d2 = 0.0;
-#pragma unroll
-                    for (int p = 0; p < BATCH_MAXD; ++p) {
-                        const double u = (P.nscale == 0 ? 1.0 : P.scale[P.nscale == 1 ? 0 : p]) * t[p];
-                        d2 = fma(u, u, d2);
-                    }
-                    v = P.variance * kappa<double>(P.kind, d2);
-                }
+                batch_diff(xs, ns, d, i, xj, t);
+                v = batch_kval<SUM>(in, &P, t, d);
             }
             if (var_o) V[(long)i * ld + j] = v;
             if (alpha) sh[i * 64 + lane] = fma(v, aj, sh[i * 64 + lane]);
@@ -372,90 +434,8 @@ __global__ __launch_bounds__(NT) void batch_predict_kernel(const double* __restr
     }
     if (!var_o) return;
 
-    // ---- 2. V ← V L⁻ᵀ, left-looking; 3. Σ_i V_ji² by the thread that owns row j
-    double (*Ls)[BTS] = reinterpret_cast<double (*)[BTS]>(sh);
-    double* dinv = sh + BT * BTS;
-    const int r = lane & 15, g = lane >> 4;
-    double ss = 0.0;
-    for (int kb = 0; kb < nt; ++kb) {
-        const int j0 = kb * BT;
-        // Lane l = (r = l & 15, g = l >> 4) holds 16 consecutive k of rows r and 16 + r of both operands; MFMA step s multiplies the k-quadruple {16 g + s}.
-        for (int tile = w; tile < (rp / 32) * 2 && kb > 0; tile += 8) {
-            const int i0 = 32 * (tile >> 1), c0 = j0 + 32 * (tile & 1);
-            d4_t acc[2][2];
-#pragma unroll
-            for (int hi = 0; hi < 2; ++hi)
-#pragma unroll
-                for (int hj = 0; hj < 2; ++hj)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) acc[hi][hj][q] = V[(long)(i0 + 16 * hi + Tr<double>::crow(lane, q)) * ld + c0 + 16 * hj + r];
-            for (int k0 = 0; k0 < j0; k0 += BT) {
-                double a[2][16], b[2][16];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const d2_t* pa = reinterpret_cast<const d2_t*>(V + (long)(i0 + 16 * h + r) * ld + k0 + 16 * g);
-                    const d2_t* pb = reinterpret_cast<const d2_t*>(A + (long)(c0 + 16 * h + r) * ld + k0 + 16 * g);
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const d2_t ta = pa[q], tb = pb[q];
-                        a[h][2 * q] = -ta.x;
-                        a[h][2 * q + 1] = -ta.y;
-                        b[h][2 * q] = tb.x;
-                        b[h][2 * q + 1] = tb.y;
-                    }
-                }
-#pragma unroll
-                for (int s = 0; s < 16; ++s)
-#pragma unroll
-                    for (int hi = 0; hi < 2; ++hi)
-#pragma unroll
-                        for (int hj = 0; hj < 2; ++hj) acc[hi][hj] = Tr<double>::mfma(a[hi][s], b[hj][s], acc[hi][hj]);
-            }
-#pragma unroll
-            for (int hi = 0; hi < 2; ++hi)
-#pragma unroll
-                for (int hj = 0; hj < 2; ++hj)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) V[(long)(i0 + 16 * hi + Tr<double>::crow(lane, q)) * ld + c0 + 16 * hj + r] = acc[hi][hj][q];
-        }
-        // the diagonal block: its lower triangle in LDS (the rest of the tile is not the factor's)
-        for (int e = tid; e < BT * BT; e += NT) {
-            const int rr = e >> 6, cc = e & 63;
-            Ls[rr][cc] = cc <= rr ? A[(long)(j0 + rr) * ld + j0 + cc] : 0.0;
-        }
-        __syncthreads();
-        if (tid < BT) dinv[tid] = 1.0 / Ls[tid][tid];
-        __syncthreads();
-        if (tid < rows) {  // X ← X L_bb⁻ᵀ, one test point per thread in registers
-            d2_t* row = reinterpret_cast<d2_t*>(V + (long)tid * ld + j0);
-            double xv[BT];
-#pragma unroll
-            for (int q = 0; q < BT / 2; ++q) {
-                const d2_t t = row[q];
-                xv[2 * q] = t.x;
-                xv[2 * q + 1] = t.y;
-            }
-#pragma unroll
-            for (int j = 0; j < BT; ++j) {
-                xv[j] *= dinv[j];
-#pragma unroll
-                for (int k2 = j + 1; k2 < BT; ++k2) {
-                    xv[k2] = fma(-xv[j], Ls[k2][j], xv[k2]);
-                    if ((k2 & 15) == 15) __builtin_amdgcn_sched_barrier(0);  // as in the fit kernel: hoisted LDS reads spill
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < BT / 2; ++q) {
-                d2_t t;
-                t.x = xv[2 * q];
-                t.y = xv[2 * q + 1];
-                row[q] = t;
-                ss = fma(t.x, t.x, ss);
-                ss = fma(t.y, t.y, ss);
-            }
-        }
-        __syncthreads();
-    }
+    // ---- 2. V ← V L⁻ᵀ; 3. Σ_i V_ji² by the thread that owns row j, block after block
+    const double ss = strip_solve(V, A, ld, 0, nt, rows, sh, tid, lane, w);
     if (tid < rows) {
         double kss = P.variance;  // every κ(x, x) = 1: k** is the variance, Σ_t σ_t² for a composite kernel
         if (SUM) {
@@ -493,8 +473,7 @@ struct GradTile {
 };
 static_assert(sizeof(GradTile) % 8 == 0, "the tables are packed behind double data");
 
-// Rows [r0, r0 + 128) of S = L⁻ᵀ into the problem's strip: batch_predict_kernel's step 2 (V ← V L⁻ᵀ, left-looking by 64-column blocks, 32×32 MFMA wave tiles,
-// the diagonal block by substitution from LDS with one row per thread in registers) with V = the identity rows of the tile.  S is upper triangular: the
+// Rows [r0, r0 + 128) of S = L⁻ᵀ into the problem's strip: strip_solve from column r0 with V = the identity rows of the tile.  S is upper triangular: the
 // columns left of r0 are zero, never written and never read (the k loops start at r0; batch_grad_kernel reads row i from column 64·⌊i / 64⌋ ≥ r0 on).
 // A failed problem's tiles return at once: nothing of it is read or written here.
 __global__ __launch_bounds__(NT) void batch_inv_kernel(const double* __restrict__ in, double* __restrict__ ws, const double* __restrict__ res, int nw,
@@ -518,91 +497,12 @@ __global__ __launch_bounds__(NT) void batch_inv_kernel(const double* __restrict_
         }
     }
     __syncthreads();
-    double (*Ls)[BTS] = reinterpret_cast<double (*)[BTS]>(sh);
-    double* dinv = sh + BT * BTS;
-    const int r = lane & 15, g = lane >> 4;
-    for (int kb = r0 / BT; kb < nt; ++kb) {
-        const int j0 = kb * BT;
-        // Lane l = (r = l & 15, g = l >> 4) holds 16 consecutive k of rows r and 16 + r of both operands; MFMA step s multiplies the k-quadruple {16 g + s}.
-        for (int tile = w; tile < (rows / 32) * 2 && j0 > r0; tile += 8) {
-            const int i0 = 32 * (tile >> 1), c0 = j0 + 32 * (tile & 1);
-            d4_t acc[2][2];
-#pragma unroll
-            for (int hi = 0; hi < 2; ++hi)
-#pragma unroll
-                for (int hj = 0; hj < 2; ++hj)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) acc[hi][hj][q] = V[(long)(i0 + 16 * hi + Tr<double>::crow(lane, q)) * ld + c0 + 16 * hj + r];
-            for (int k0 = r0; k0 < j0; k0 += BT) {
-                double a[2][16], b[2][16];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const d2_t* pa = reinterpret_cast<const d2_t*>(V + (long)(i0 + 16 * h + r) * ld + k0 + 16 * g);
-                    const d2_t* pb = reinterpret_cast<const d2_t*>(A + (long)(c0 + 16 * h + r) * ld + k0 + 16 * g);
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const d2_t ta = pa[q], tb = pb[q];
-                        a[h][2 * q] = -ta.x;
-                        a[h][2 * q + 1] = -ta.y;
-                        b[h][2 * q] = tb.x;
-                        b[h][2 * q + 1] = tb.y;
-                    }
-                }
-#pragma unroll
-                for (int s = 0; s < 16; ++s)
-#pragma unroll
-                    for (int hi = 0; hi < 2; ++hi)
-#pragma unroll
-                        for (int hj = 0; hj < 2; ++hj) acc[hi][hj] = Tr<double>::mfma(a[hi][s], b[hj][s], acc[hi][hj]);
-            }
-#pragma unroll
-            for (int hi = 0; hi < 2; ++hi)
-#pragma unroll
-                for (int hj = 0; hj < 2; ++hj)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) V[(long)(i0 + 16 * hi + Tr<double>::crow(lane, q)) * ld + c0 + 16 * hj + r] = acc[hi][hj][q];
-        }
-        // the diagonal block: its lower triangle in LDS (the rest of the tile is not the factor's)
-        for (int e = tid; e < BT * BT; e += NT) {
-            const int rr = e >> 6, cc = e & 63;
-            Ls[rr][cc] = cc <= rr ? A[(long)(j0 + rr) * ld + j0 + cc] : 0.0;
-        }
-        __syncthreads();
-        if (tid < BT) dinv[tid] = 1.0 / Ls[tid][tid];
-        __syncthreads();
-        if (tid < rows) {  // X ← X L_bb⁻ᵀ, one row of S per thread in registers
-            d2_t* row = reinterpret_cast<d2_t*>(V + (long)tid * ld + j0);
-            double xv[BT];
-#pragma unroll
-            for (int q = 0; q < BT / 2; ++q) {
-                const d2_t t = row[q];
-                xv[2 * q] = t.x;
-                xv[2 * q + 1] = t.y;
-            }
-#pragma unroll
-            for (int j = 0; j < BT; ++j) {
-                xv[j] *= dinv[j];
-#pragma unroll
-                for (int k2 = j + 1; k2 < BT; ++k2) {
-                    xv[k2] = fma(-xv[j], Ls[k2][j], xv[k2]);
-                    if ((k2 & 15) == 15) __builtin_amdgcn_sched_barrier(0);  // as in the fit kernel: hoisted LDS reads spill
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < BT / 2; ++q) {
-                d2_t t;
-                t.x = xv[2 * q];
-                t.y = xv[2 * q + 1];
-                row[q] = t;
-            }
-        }
-        __syncthreads();
-    }
+    (void)strip_solve(V, A, ld, r0, nt, rows, sh, tid, lane, w);
 }
 
 // The 64×64 tile (ti >= tj) of the lower triangle of one problem:
-//   1. C⁻¹_tile = Σ_{k ≥ 64 ti} S[i, k] S[j, k] by v_mfma_f64_16x16x4_f64, one 32×32 wave tile per wave, in the NT operand form of the fit kernel's trailing
-//      update (16 consecutive k per lane straight from the strip); the weights W_ij = (α_i α_j − C⁻¹_ij)·(i = j ? ½ : 1) of the pairs j ≤ i < n into LDS;
+//   1. C⁻¹_tile = Σ_{k ≥ 64 ti} S[i, k] S[j, k] by mfma_tile_k64 straight from the strip, one 32×32 wave tile per wave; the weights
+//      W_ij = (α_i α_j − C⁻¹_ij)·(i = j ? ½ : 1) of the pairs j ≤ i < n into LDS;
 //   2. Σ W_ij ∂C_ij/∂θ with ∂C_ij/∂θ re-evaluated from the packed inputs: thread = (column j = lane, rows w, w + 4, …), the column's inputs in registers, the
 //      row's by scalar loads.  Single-kind: variance and scales in registers (the sums of kgrad_kernel, the 1 / scale factor of ∂r² at the end); composite:
 //      ksum_grad, GRAD_NP θ entries per pass in per-thread LDS slots.  The diagonal adds W_ii to the noise sum; a diagonal Σy's entries are stored directly.
@@ -632,37 +532,11 @@ __global__ __launch_bounds__(GNT) void batch_grad_kernel(const double* __restric
     {
         const int wi = w >> 1, wj = w & 1;
         if (!(T.ti == T.tj && wj > wi)) {  // the wave tile strictly above the diagonal holds no pair j <= i
-            const int r = lane & 15, g = lane >> 4;
+            const int r = lane & 15;
             const int i0 = it0 + 32 * wi, c0 = jt0 + 32 * wj;
             d4_t c4[2][2];
-#pragma unroll
-            for (int hi = 0; hi < 2; ++hi)
-#pragma unroll
-                for (int hj = 0; hj < 2; ++hj)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) c4[hi][hj][q] = 0.0;
-            for (int k0 = it0; k0 < np; k0 += BT) {
-                double a[2][16], b[2][16];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const d2_t* pa = reinterpret_cast<const d2_t*>(S + (long)(i0 + 16 * h + r) * ld + k0 + 16 * g);
-                    const d2_t* pb = reinterpret_cast<const d2_t*>(S + (long)(c0 + 16 * h + r) * ld + k0 + 16 * g);
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const d2_t ta = pa[q], tb = pb[q];
-                        a[h][2 * q] = ta.x;
-                        a[h][2 * q + 1] = ta.y;
-                        b[h][2 * q] = tb.x;
-                        b[h][2 * q + 1] = tb.y;
-                    }
-                }
-#pragma unroll
-                for (int s = 0; s < 16; ++s)
-#pragma unroll
-                    for (int hi = 0; hi < 2; ++hi)
-#pragma unroll
-                        for (int hj = 0; hj < 2; ++hj) c4[hi][hj] = Tr<double>::mfma(a[hi][s], b[hj][s], c4[hi][hj]);
-            }
+            acc_zero(c4);
+            for (int k0 = it0; k0 < np; k0 += BT) mfma_tile_k64<false>(c4, S, i0, S, c0, k0, ld, lane);
 #pragma unroll
             for (int hi = 0; hi < 2; ++hi)
 #pragma unroll
@@ -684,8 +558,7 @@ __global__ __launch_bounds__(GNT) void batch_grad_kernel(const double* __restric
     // ---- 2. the contraction
     const int gj = jt0 + lane;
     double xj[BATCH_MAXD];
-#pragma unroll
-    for (int p = 0; p < BATCH_MAXD; ++p) xj[p] = (p < d && gj < n) ? x[(long)p * n + gj] : 0.0;
+    batch_load_point(x, n, d, gj, xj);
     double gn = 0.0;  // Σ W_ii
     if (T.ti == T.tj) {
         const int gi = it0 + tid;
@@ -752,8 +625,7 @@ __global__ __launch_bounds__(GNT) void batch_grad_kernel(const double* __restric
                 if (gi >= n) continue;
                 if (gj > gi) continue;  // gj <= gi < n
                 double t[BATCH_MAXD];
-#pragma unroll
-                for (int p = 0; p < BATCH_MAXD; ++p) t[p] = p < d ? x[(long)p * n + gi] - xj[p] : 0.0;
+                batch_diff(x, n, d, gi, xj, t);
                 ksum_grad<double, BATCH_MAXD>(ks, t, d, Wt[li][lane], add, kf, tid);
             }
             if (p0 == 0) {
@@ -823,10 +695,12 @@ struct BatchArgs {
     void* ab(int b) const { return alpha_out ? alpha_out[b] : nullptr; }
 };
 
-long batch_max_n() {  // GPMI355_BATCH_MAX_N; the environment variable GPMI_BATCH_MAX_N (0 … what the kernel admits) overrides it for measurements
-    long v = GPMI355_BATCH_MAX_N;
-    if (const char* e = getenv("GPMI_BATCH_MAX_N")) v = atol(e);
-    return std::max(0L, std::min<long>(v, BATCH_KERNEL_MAX_N));
+// a size limit of the header; the environment variable read at the call site overrides it for measurements (0 … what the kernels admit)
+long env_capped(const char* env, long deflt) { return std::max(0L, std::min<long>(env ? atol(env) : deflt, BATCH_KERNEL_MAX_N)); }
+void fill_nan(void* out, int dtype, long n) {
+    if (!out) return;
+    if (dtype == 0) std::fill_n((double*)out, n, std::numeric_limits<double>::quiet_NaN());
+    else std::fill_n((float*)out, n, std::numeric_limits<float>::quiet_NaN());
 }
 
 // x of one problem, dimension-major [d][n], raw (the kernel applies the transform to the differences)
@@ -847,11 +721,30 @@ void put_result(const BatchArgs& a, int b, double lp, int32_t info) {
     a.info_out[b] = info;
 }
 
+// the logpdf entry of problem b for the single path, zeroed (NULL where gp_predict_batch was given no logpdf_out)
+void* logpdf_slot(const BatchArgs& a, int b) {
+    if (!a.logpdf_out) return nullptr;
+    put(a.logpdf_out, a.dtype, b, 0);
+    return (char*)a.logpdf_out + (a.dtype == 0 ? 8 : 4) * (size_t)b;
+}
+
+// `len` doubles of a packed buffer whose next free offset is `top`: where they start
+long take(long& top, long len) { return std::exchange(top, top + len); }
+
+// An array that every problem brings, or that all of them share (count == 1): the shared one is laid out, and filled, once.
+struct SharedOnce {
+    bool shared, seen = false;
+    long off = -1;
+    bool claim() { return !(shared && std::exchange(seen, true)); }  // true for the problem that is to lay out / write the array: every one, or the first
+    long place(long& top, long len) { return claim() ? off = take(top, len) : off; }  // layout: the problem's offset, `len` doubles taken at `top` by the claimant
+};
+
 // The packed input of one wave (doubles): descriptors | composite kernels | x | y | means | noise vectors, then whatever the caller appends at `off`;
 // `ws` counts the slices, `roff` the result buffer (logpdf and failure column of every problem, then the α vectors).
 struct WaveLayout {
     std::vector<BatchProb> pr;  // in the order of idx
     std::vector<int> order;     // the descriptors as they lie on the device: the widest problems first (the last workgroups to start are the shortest)
+    std::vector<int> pos;       // the inverse of order: where the descriptor of problem t lies
     long off = 0, ws = 0, roff = 0;
 };
 
@@ -859,9 +752,10 @@ struct WaveLayout {
 template <class F> void wave_layout(const BatchArgs& a, const int* idx, int nw, F&& want_alpha, WaveLayout& L) {
     std::vector<BatchProb>& pr = L.pr;
     pr.assign((size_t)nw, BatchProb{});
-    long off = (long)((size_t)nw * sizeof(BatchProb) / 8), ws = 0, roff = 2L * nw;
+    long &off = L.off, &ws = L.ws, &roff = L.roff;
+    off = (long)((size_t)nw * sizeof(BatchProb) / 8), ws = 0, roff = 2L * nw;
     const long ksd = (long)((sizeof(KSum) + 7) / 8);
-    long x_shared = -1, y_shared = -1;
+    SharedOnce xo{a.nx == 1}, yo{a.ny == 1};
     for (int t = 0; t < nw; ++t) {
         const int b = idx[t];
         const gp_points& x = a.xb(b);
@@ -871,112 +765,115 @@ template <class F> void wave_layout(const BatchArgs& a, const int* idx, int nw, 
         p.ld = (int)batch_ld(p.np);
         p.d = x.d;
         p.slot = t;
-        p.a_off = ws;
-        ws += batch_slice(x.n);
-        p.ks_off = -1;
-        if (a.ks) {
-            p.ks_off = off;
-            off += ksd;
-        } else {
+        p.a_off = take(ws, batch_slice(x.n));
+        p.ks_off = a.ks ? take(off, ksd) : -1;
+        if (!a.ks) {
             const gp_kernel& k = a.k[b];
             p.kind = k.kind;
             p.nscale = k.nscale;
             p.variance = k.variance;
             for (int q = 0; q < k.nscale; ++q) p.scale[q] = k.scale[q];
         }
-        if (a.nx == 1 && x_shared >= 0) {
-            p.x_off = x_shared;
-        } else {
-            p.x_off = x_shared = off;
-            off += (long)x.d * x.n;
-        }
-        if (a.ny == 1 && y_shared >= 0) {
-            p.y_off = y_shared;
-        } else {
-            p.y_off = y_shared = off;
-            off += x.n;
-        }
-        p.m_off = -1;
-        if (a.mb(b)) {
-            p.m_off = off;
-            off += x.n;
-        }
-        p.nz_off = -1;
+        p.x_off = xo.place(off, (long)x.d * x.n);
+        p.y_off = yo.place(off, x.n);
+        p.m_off = a.mb(b) ? take(off, x.n) : -1;
         p.noise_s = a.noise[b].s;
-        if (a.noise[b].kind == 1) {
-            p.nz_off = off;
-            off += x.n;
-        }
-        p.alpha_off = -1;
-        if (want_alpha(b)) {
-            p.alpha_off = roff;
-            roff += x.n;
-        }
+        p.nz_off = a.noise[b].kind == 1 ? take(off, x.n) : -1;
+        p.alpha_off = want_alpha(b) ? take(roff, x.n) : -1;
     }
     L.order.resize((size_t)nw);
     for (int t = 0; t < nw; ++t) L.order[t] = t;
     std::stable_sort(L.order.begin(), L.order.end(), [&](int u, int v) { return pr[u].n > pr[v].n; });
-    L.off = off;
-    L.ws = ws;
-    L.roff = roff;
+    L.pos.resize((size_t)nw);
+    for (int s = 0; s < nw; ++s) L.pos[L.order[s]] = s;
 }
 
 // fills the packed input of a laid-out wave: the descriptors in L.order, then every problem's data
 void wave_fill(const BatchArgs& a, const std::vector<KSum>& packed, const int* idx, int nw, const WaveLayout& L, double* hin) {
     for (int t = 0; t < nw; ++t) std::memcpy((char*)hin + (size_t)t * sizeof(BatchProb), &L.pr[L.order[t]], sizeof(BatchProb));
-    bool x_done = false, y_done = false;
+    SharedOnce xo{a.nx == 1}, yo{a.ny == 1};
     for (int t = 0; t < nw; ++t) {
         const int b = idx[t];
         const gp_points& x = a.xb(b);
         const BatchProb& p = L.pr[t];
         if (a.ks) std::memcpy(hin + p.ks_off, &packed[b], sizeof(KSum));
-        if (!(a.nx == 1 && x_done)) pack_points(x, hin + p.x_off);
-        if (!(a.ny == 1 && y_done)) std::memcpy(hin + p.y_off, a.yb(b), sizeof(double) * x.n);
-        x_done = y_done = true;
+        if (xo.claim()) pack_points(x, hin + p.x_off);
+        if (yo.claim()) std::memcpy(hin + p.y_off, a.yb(b), sizeof(double) * x.n);
         if (p.m_off >= 0) std::memcpy(hin + p.m_off, a.mb(b), sizeof(double) * x.n);
         if (p.nz_off >= 0) std::memcpy(hin + p.nz_off, a.noise[b].diag, sizeof(double) * x.n);
     }
 }
 
-// page-locked staging of one wave for both directions (pageable above the staging limit)
-double* wave_staging(gp_ctx* c, size_t doubles, std::vector<double>& pageable) {
-    double* h = (double*)ctx_pinned(c, sizeof(double) * doubles);
-    if (!h) {
-        pageable.resize(doubles);
-        h = pageable.data();
+// Host and device memory of one wave: page-locked staging for both directions (pageable above the staging limit; packed input, then results) and the three
+// device blocks, which return to the ctx cache with the wave.
+struct WaveMem {
+    gp_ctx* c;
+    DevBufs bufs;
+    std::vector<double> pageable;
+    double *hin = nullptr, *hout = nullptr, *ws = nullptr, *res = nullptr;
+    const double* in = nullptr;
+    size_t in_bytes = 0, out_bytes = 0;
+    explicit WaveMem(gp_ctx* c_) : c(c_), bufs(c_) {}
+    int32_t alloc(long in_doubles, long ws_doubles, long out_doubles) {
+        in_bytes = sizeof(double) * (size_t)in_doubles;
+        out_bytes = sizeof(double) * (size_t)out_doubles;
+        hin = (double*)ctx_pinned(c, in_bytes + out_bytes);
+        if (!hin) {
+            pageable.resize((size_t)(in_doubles + out_doubles));
+            hin = pageable.data();
+        }
+        hout = hin + in_doubles;
+        void *i = nullptr, *w = nullptr, *r = nullptr;
+        RC(bufs.get(in_bytes, &i));
+        RC(bufs.get(sizeof(double) * (size_t)ws_doubles, &w));
+        RC(bufs.get(out_bytes, &r));
+        in = (const double*)i, ws = (double*)w, res = (double*)r;
+        return 0;
     }
-    return h;
+    int32_t upload() {
+        HIPCHK(hipMemcpyAsync((void*)in, hin, in_bytes, hipMemcpyHostToDevice, c->sm));
+        return 0;
+    }
+    int32_t download_and_sync() {
+        HIPCHK(hipMemcpyAsync(hout, res, out_bytes, hipMemcpyDeviceToHost, c->sm));
+        HIPCHK(hipStreamSynchronize(c->sm));
+        return 0;
+    }
+};
+
+// The launches of a wave on the ctx's main stream, the <SUM> dispatch of each kernel in one place (ks: the call brought composite kernels).
+int32_t launch_fit(const WaveMem& m, bool ks, int nw) {
+    hipLaunchKernelGGL(ks ? batch_logpdf_kernel<true> : batch_logpdf_kernel<false>, dim3((unsigned)nw), dim3(NT), 0, m.c->sm, m.in, m.ws, m.res, nw);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int32_t launch_predict(const WaveMem& m, bool ks, int nw, const BatchTile* tiles, size_t ntiles) {
+    hipLaunchKernelGGL(ks ? batch_predict_kernel<true> : batch_predict_kernel<false>, dim3((unsigned)ntiles), dim3(NT), 0, m.c->sm, m.in, m.ws, m.res, nw, tiles);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int32_t launch_grad(const WaveMem& m, bool ks, int nw, const GradProb* gps, const GradTile* tiles, size_t ntiles) {
+    hipLaunchKernelGGL(ks ? batch_grad_kernel<true> : batch_grad_kernel<false>, dim3((unsigned)ntiles), dim3(GNT), 0, m.c->sm, m.in, m.ws, m.res, nw, gps, tiles);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 // one launch: the problems idx[0..nw) of the call, all taken by the kernel.  Caller holds the ctx lock.
 int32_t run_wave(gp_ctx* c, const BatchArgs& a, const std::vector<KSum>& packed, const int* idx, int nw) {
     WaveLayout L;
     wave_layout(a, idx, nw, [&](int b) { return a.ab(b) != nullptr; }, L);
-    const std::vector<BatchProb>& pr = L.pr;
-    const long off = L.off, ws = L.ws, roff = L.roff;
-    const size_t in_bytes = sizeof(double) * (size_t)off, out_bytes = sizeof(double) * (size_t)roff;
-    std::vector<double> pageable;
-    double* hin = wave_staging(c, (size_t)(off + roff), pageable);
-    double* hout = hin + off;
-    wave_fill(a, packed, idx, nw, L, hin);
-    DevBufs bufs(c);
-    void *in_d = nullptr, *ws_d = nullptr, *res_d = nullptr;
-    RC(bufs.get(in_bytes, &in_d));
-    RC(bufs.get(sizeof(double) * (size_t)ws, &ws_d));
-    RC(bufs.get(out_bytes, &res_d));
+    WaveMem m(c);
+    RC(m.alloc(L.off, L.ws, L.roff));
+    wave_fill(a, packed, idx, nw, L, m.hin);
     RC(run_drained(c, [&]() -> int32_t {
-        HIPCHK(hipMemcpyAsync(in_d, hin, in_bytes, hipMemcpyHostToDevice, c->sm));
-        if (a.ks) hipLaunchKernelGGL(batch_logpdf_kernel<true>, dim3((unsigned)nw), dim3(NT), 0, c->sm, (const double*)in_d, (double*)ws_d, (double*)res_d, nw);
-        else hipLaunchKernelGGL(batch_logpdf_kernel<false>, dim3((unsigned)nw), dim3(NT), 0, c->sm, (const double*)in_d, (double*)ws_d, (double*)res_d, nw);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(hout, res_d, out_bytes, hipMemcpyDeviceToHost, c->sm));
-        HIPCHK(hipStreamSynchronize(c->sm));
-        return 0;
+        RC(m.upload());
+        RC(launch_fit(m, a.ks != nullptr, nw));
+        return m.download_and_sync();
     }));
     for (int t = 0; t < nw; ++t) {
         const int b = idx[t];
-        put_result(a, b, hout[t], (int32_t)hout[nw + t]);
-        if (pr[t].alpha_off >= 0) std::memcpy(a.ab(b), hout + pr[t].alpha_off, sizeof(double) * pr[t].n);
+        put_result(a, b, m.hout[t], (int32_t)m.hout[nw + t]);
+        if (L.pr[t].alpha_off >= 0) std::memcpy(a.ab(b), m.hout + L.pr[t].alpha_off, sizeof(double) * L.pr[t].n);
     }
     return 0;
 }
@@ -1020,6 +917,30 @@ bool batch_takes(const BatchArgs& a, int b, long max_n) {
     return a.dtype == 0 && a.noise[b].kind <= 1 && x.n <= max_n && x.d <= BATCH_MAXD;
 }
 
+// the path of a problem depends on that problem alone: the kernels' (mine) or the single path's (routed)
+void split_by_path(const BatchArgs& a, long max_n, std::vector<int>& mine, std::vector<int>& routed) {
+    for (int b = 0; b < a.nb; ++b) (batch_takes(a, b, max_n) ? mine : routed).push_back(b);
+}
+
+// workspace bytes of one problem: `own` adds up over a wave, `shared` is needed once per wave, as wide as the widest problem asks for
+struct WaveCost { size_t own, shared; };
+// The kernel's problems in waves bounded by the launch size and by the workspace budget (a wave holds at least one problem); run(idx, nw) serves one wave.
+template <class Cost, class Run> int32_t for_each_wave(gp_ctx* c, const std::vector<int>& mine, Cost&& cost, Run&& run) {
+    if (mine.empty()) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    for (size_t i = 0, j; i < mine.size(); i = j) {
+        size_t own = 0, shared = 0;
+        for (j = i; j < mine.size() && j - i < BATCH_WAVE_PROBLEMS; ++j) {
+            const WaveCost w = cost(mine[j]);
+            if (j > i && own + w.own + std::max(shared, w.shared) > BATCH_WS_BYTES) break;
+            own += w.own;
+            shared = std::max(shared, w.shared);
+        }
+        RC(run(mine.data() + i, (int)(j - i)));
+    }
+    return 0;
+}
+
 int32_t batch_impl(gp_ctx* c, BatchArgs& a) {
     Guard gd(c);
     if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
@@ -1030,36 +951,17 @@ int32_t batch_impl(gp_ctx* c, BatchArgs& a) {
     if (!a.info_out) return set_arg_err(11, "info_out is NULL");
     std::vector<KSum> packed;
     RC(check_batch_problems(a, packed));
-    // the path of a problem depends on that problem alone
-    const long max_n = batch_max_n();
     std::vector<int> mine, routed;
-    for (int b = 0; b < a.nb; ++b) {
-        (batch_takes(a, b, max_n) ? mine : routed).push_back(b);
-    }
-    if (!mine.empty()) {
-        HIPCHK(hipSetDevice(c->device));
-        size_t i = 0;
-        while (i < mine.size()) {  // waves bounded by the workspace budget and by the launch size
-            size_t j = i, bytes = 0;
-            while (j < mine.size() && j - i < BATCH_WAVE_PROBLEMS) {
-                const size_t s = sizeof(double) * (size_t)batch_slice(a.xb(mine[j]).n);
-                if (j > i && bytes + s > BATCH_WS_BYTES) break;
-                bytes += s;
-                ++j;
-            }
-            RC(run_wave(c, a, packed, mine.data() + i, (int)(j - i)));
-            i = j;
-        }
-    }
+    split_by_path(a, env_capped(getenv("GPMI_BATCH_MAX_N"), GPMI355_BATCH_MAX_N), mine, routed);
+    RC(for_each_wave(c, mine, [&](int b) { return WaveCost{sizeof(double) * (size_t)batch_slice(a.xb(b).n), 0}; },
+                     [&](const int* idx, int nw) { return run_wave(c, a, packed, idx, nw); }));
     // everything else: the single path, one problem at a time.  Each of those calls takes the ctx lock itself (std::mutex is not recursive): it is released
     // here; the ctx stays pinned by the Guard, and every call validates it again.
     gd.lk.unlock();
-    const size_t es = a.dtype == 0 ? 8 : 4;
     for (int b : routed) {
         const gp_points& x = a.xb(b);
         int32_t rc;
-        put(a.logpdf_out, a.dtype, b, 0);
-        void* lp = (char*)a.logpdf_out + es * (size_t)b;
+        void* lp = logpdf_slot(a, b);
         if (a.ab(b)) {
             gp_post* post = nullptr;
             rc = a.ks ? gp_posterior_fit_sum(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), &post, a.ab(b), lp)
@@ -1073,10 +975,7 @@ int32_t batch_impl(gp_ctx* c, BatchArgs& a) {
         a.info_out[b] = rc;
         if (rc > 0) {
             put_result(a, b, std::numeric_limits<double>::quiet_NaN(), rc);
-            if (a.ab(b)) {
-                if (a.dtype == 0) std::fill_n((double*)a.ab(b), x.n, std::numeric_limits<double>::quiet_NaN());
-                else std::fill_n((float*)a.ab(b), x.n, std::numeric_limits<float>::quiet_NaN());
-            }
+            fill_nan(a.ab(b), a.dtype, x.n);
         }
     }
     return 0;
@@ -1096,40 +995,21 @@ struct PredictArgs : BatchArgs {
 
 long predict_strip(const PredictArgs& a, long n) { return (a.what & 2) ? (long)TP * batch_ld(batch_np(n)) : 0; }  // the mean alone needs no strip
 
-void fill_nan(void* out, int dtype, long n) {
-    if (!out) return;
-    if (dtype == 0) std::fill_n((double*)out, n, std::numeric_limits<double>::quiet_NaN());
-    else std::fill_n((float*)out, n, std::numeric_limits<float>::quiet_NaN());
-}
-
 // one wave: the fit launch of the problems idx[0..nw), then the predict launches against the slices it leaves.  Caller holds the ctx lock.
 int32_t run_predict_wave(gp_ctx* c, const PredictArgs& a, const std::vector<KSum>& packed, const int* idx, int nw) {
     WaveLayout L;
     wave_layout(a, idx, nw, [&](int b) { return (a.what & 1) && a.xsb(b).n > 0; }, L);
     // behind the fit's input: the test points (dimension-major, a shared set once), then the tile table; behind its results: mean and var of every problem
     std::vector<long> xs_off((size_t)nw, -1), mean_off((size_t)nw, -1), var_off((size_t)nw, -1);
-    long xs_shared = -1;
+    SharedOnce xso{a.nxs == 1}, xsf{a.nxs == 1};  // layout, filling
     for (int t = 0; t < nw; ++t) {
         const gp_points& xs = a.xsb(idx[t]);
         if (xs.n == 0) continue;
-        if (a.nxs == 1 && xs_shared >= 0) {
-            xs_off[t] = xs_shared;
-        } else {
-            xs_off[t] = xs_shared = L.off;
-            L.off += (long)xs.d * xs.n;
-        }
-        if (a.what & 1) {
-            mean_off[t] = L.roff;
-            L.roff += xs.n;
-        }
-        if (a.what & 2) {
-            var_off[t] = L.roff;
-            L.roff += xs.n;
-        }
+        xs_off[t] = xso.place(L.off, (long)xs.d * xs.n);
+        if (a.what & 1) mean_off[t] = take(L.roff, xs.n);
+        if (a.what & 2) var_off[t] = take(L.roff, xs.n);
     }
     // tiles of TP test points, the widest problems first; a launch closes at BATCH_PRED_TILES tiles or when its strips would pass the workspace budget
-    std::vector<int> pos((size_t)nw);
-    for (int s = 0; s < nw; ++s) pos[L.order[s]] = s;
     std::vector<BatchTile> tiles;
     std::vector<size_t> launch_end;
     long cur = L.ws, ws_top = L.ws;
@@ -1144,51 +1024,34 @@ int32_t run_predict_wave(gp_ctx* c, const PredictArgs& a, const std::vector<KSum
                 launch_begin = tiles.size();
                 cur = L.ws;  // the launches of a wave run one after the other on one stream: they share the strips
             }
-            BatchTile tl{xs_off[t], cur, mean_off[t], var_off[t], pos[t], (int)ns, (int)row0, (int)std::min<long>(TP, ns - row0)};
+            BatchTile tl{xs_off[t], cur, mean_off[t], var_off[t], L.pos[t], (int)ns, (int)row0, (int)std::min<long>(TP, ns - row0)};
             tiles.push_back(tl);
             cur += strip;
             ws_top = std::max(ws_top, cur);
         }
     }
     if (tiles.size() > launch_begin) launch_end.push_back(tiles.size());
-    const long tile_off = L.off;
-    L.off += (long)(tiles.size() * sizeof(BatchTile) / 8);
+    const long tile_off = take(L.off, (long)(tiles.size() * sizeof(BatchTile) / 8));
 
-    const size_t in_bytes = sizeof(double) * (size_t)L.off, out_bytes = sizeof(double) * (size_t)L.roff;
-    std::vector<double> pageable;
-    double* hin = wave_staging(c, (size_t)(L.off + L.roff), pageable);
-    double* hout = hin + L.off;
-    wave_fill(a, packed, idx, nw, L, hin);
-    bool xs_done = false;
+    WaveMem m(c);
+    RC(m.alloc(L.off, ws_top, L.roff));
+    wave_fill(a, packed, idx, nw, L, m.hin);
     for (int t = 0; t < nw; ++t) {
         const gp_points& xs = a.xsb(idx[t]);
-        if (xs.n == 0 || (a.nxs == 1 && xs_done)) continue;
-        pack_points(xs, hin + xs_off[t]);
-        xs_done = true;
+        if (xs.n > 0 && xsf.claim()) pack_points(xs, m.hin + xs_off[t]);
     }
-    if (!tiles.empty()) std::memcpy(hin + tile_off, tiles.data(), tiles.size() * sizeof(BatchTile));
-    DevBufs bufs(c);
-    void *in_d = nullptr, *ws_d = nullptr, *res_d = nullptr;
-    RC(bufs.get(in_bytes, &in_d));
-    RC(bufs.get(sizeof(double) * (size_t)ws_top, &ws_d));
-    RC(bufs.get(out_bytes, &res_d));
+    if (!tiles.empty()) std::memcpy(m.hin + tile_off, tiles.data(), tiles.size() * sizeof(BatchTile));
     RC(run_drained(c, [&]() -> int32_t {
-        HIPCHK(hipMemcpyAsync(in_d, hin, in_bytes, hipMemcpyHostToDevice, c->sm));
-        if (a.ks) hipLaunchKernelGGL(batch_logpdf_kernel<true>, dim3((unsigned)nw), dim3(NT), 0, c->sm, (const double*)in_d, (double*)ws_d, (double*)res_d, nw);
-        else hipLaunchKernelGGL(batch_logpdf_kernel<false>, dim3((unsigned)nw), dim3(NT), 0, c->sm, (const double*)in_d, (double*)ws_d, (double*)res_d, nw);
-        HIPCHK(hipGetLastError());
+        RC(m.upload());
+        RC(launch_fit(m, a.ks != nullptr, nw));
         size_t t0 = 0;
         for (size_t t1 : launch_end) {
-            const BatchTile* tl = reinterpret_cast<const BatchTile*>((const double*)in_d + tile_off) + t0;
-            if (a.ks) hipLaunchKernelGGL(batch_predict_kernel<true>, dim3((unsigned)(t1 - t0)), dim3(NT), 0, c->sm, (const double*)in_d, (double*)ws_d, (double*)res_d, nw, tl);
-            else hipLaunchKernelGGL(batch_predict_kernel<false>, dim3((unsigned)(t1 - t0)), dim3(NT), 0, c->sm, (const double*)in_d, (double*)ws_d, (double*)res_d, nw, tl);
-            HIPCHK(hipGetLastError());
+            RC(launch_predict(m, a.ks != nullptr, nw, reinterpret_cast<const BatchTile*>(m.in + tile_off) + t0, t1 - t0));
             t0 = t1;
         }
-        HIPCHK(hipMemcpyAsync(hout, res_d, out_bytes, hipMemcpyDeviceToHost, c->sm));
-        HIPCHK(hipStreamSynchronize(c->sm));
-        return 0;
+        return m.download_and_sync();
     }));
+    const double* hout = m.hout;
     for (int t = 0; t < nw; ++t) {
         const int b = idx[t];
         put_result(a, b, hout[t], (int32_t)hout[nw + t]);
@@ -1227,36 +1090,21 @@ int32_t predict_batch_impl(gp_ctx* c, PredictArgs& a) {
         if ((a.what & 1) && !a.mean_out[b]) return set_arg_err(14, "a mean_out pointer is NULL");
         if ((a.what & 2) && !a.var_out[b]) return set_arg_err(15, "a var_out pointer is NULL");
     }
-    const long max_n = batch_max_n();
     std::vector<int> mine, routed;
-    for (int b = 0; b < a.nb; ++b) (batch_takes(a, b, max_n) ? mine : routed).push_back(b);
-    if (!mine.empty()) {
-        HIPCHK(hipSetDevice(c->device));
-        size_t i = 0;
-        while (i < mine.size()) {  // waves bounded by the launch size and by the workspace budget: the slices and the widest strip of the wave fit in it
-            size_t j = i, bytes = 0, strip = 0;
-            while (j < mine.size() && j - i < BATCH_WAVE_PROBLEMS) {
-                const long n = a.xb(mine[j]).n;
-                const size_t s = sizeof(double) * (size_t)batch_slice(n);
-                const size_t st = std::max(strip, a.xsb(mine[j]).n > 0 ? sizeof(double) * (size_t)predict_strip(a, n) : 0);
-                if (j > i && bytes + s + st > BATCH_WS_BYTES) break;
-                bytes += s;
-                strip = st;
-                ++j;
-            }
-            RC(run_predict_wave(c, a, packed, mine.data() + i, (int)(j - i)));
-            i = j;
-        }
-    }
+    split_by_path(a, env_capped(getenv("GPMI_BATCH_MAX_N"), GPMI355_BATCH_MAX_N), mine, routed);
+    // the slices of a wave and its widest strip fit in the budget: the predict launches of a wave run one after the other and share the strips
+    auto cost = [&](int b) {
+        const long n = a.xb(b).n;
+        return WaveCost{sizeof(double) * (size_t)batch_slice(n), a.xsb(b).n > 0 ? sizeof(double) * (size_t)predict_strip(a, n) : 0};
+    };
+    RC(for_each_wave(c, mine, cost, [&](const int* idx, int nw) { return run_predict_wave(c, a, packed, idx, nw); }));
     // everything else: fit, predict and free on the single path, one problem at a time, after the lock is released (as batch_impl does)
     gd.lk.unlock();
-    const size_t es = a.dtype == 0 ? 8 : 4;
     for (int b : routed) {
         const gp_points& x = a.xb(b);
         const gp_points& xs = a.xsb(b);
         gp_post* post = nullptr;
-        void* lp = a.logpdf_out ? (char*)a.logpdf_out + es * (size_t)b : nullptr;
-        if (lp) put(a.logpdf_out, a.dtype, b, 0);
+        void* lp = logpdf_slot(a, b);
         int32_t rc = a.ks ? gp_posterior_fit_sum(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), &post, nullptr, lp)
                           : gp_posterior_fit(c, &a.k[b], &x, &a.noise[b], a.mb(b), a.yb(b), &post, nullptr, lp);
         if (rc == 0 && xs.n > 0)
@@ -1286,12 +1134,6 @@ struct GradArgs : BatchArgs {
     void* dnb(int b) const { return dnoise ? dnoise[b] : nullptr; }
     void* dyb(int b) const { return dy ? dy[b] : nullptr; }
 };
-
-long batch_grad_max_n() {  // GPMI355_BATCH_GRAD_MAX_N; the environment variable GPMI_BATCH_GRAD_MAX_N (0 … what the kernels admit) overrides it for measurements
-    long v = GPMI355_BATCH_GRAD_MAX_N;
-    if (const char* e = getenv("GPMI_BATCH_GRAD_MAX_N")) v = atol(e);
-    return std::max(0L, std::min<long>(v, BATCH_KERNEL_MAX_N));
-}
 
 // the kernel parameters of problem b: variance + scales, or the θ entries of its composite kernel
 int grad_nkp(const GradArgs& a, const std::vector<KSum>& packed, int b) { return a.ks ? packed[b].nth : 1 + a.k[b].nscale; }
@@ -1328,67 +1170,42 @@ int32_t run_grad_wave(gp_ctx* c, const GradArgs& a, const std::vector<KSum>& pac
         const int nt = p.np / BT;
         g.ng = 1 + grad_nkp(a, packed, b);
         g.ntiles = nt * (nt + 1) / 2;
-        g.s_off = L.ws;
-        L.ws += (long)p.np * p.ld;
-        g.part_off = L.ws;
-        L.ws += ((long)g.ntiles * g.ng + 1) & ~1L;  // the next strip stays 16-byte aligned
-        g.g_off = L.roff;
-        L.roff += g.ng;
-        g.dn_off = -1;
-        if (a.noise[b].kind == 1) {
-            g.dn_off = L.roff;
-            L.roff += p.n;
-        }
+        g.s_off = take(L.ws, (long)p.np * p.ld);
+        g.part_off = take(L.ws, ((long)g.ntiles * g.ng + 1) & ~1L);  // the next strip stays 16-byte aligned
+        g.g_off = take(L.roff, g.ng);
+        g.dn_off = a.noise[b].kind == 1 ? take(L.roff, p.n) : -1;
         for (int r0 = 0; r0 < p.np; r0 += TP) itiles.push_back(GradTile{s, r0 / TP, 0, 0});
         for (int ti = 0; ti < nt; ++ti)
             for (int tj = 0; tj <= ti; ++tj) gtiles.push_back(GradTile{s, ti, tj, ti * (ti + 1) / 2 + tj});
     }
-    const long gp_off = L.off;
-    L.off += (long)(gp.size() * sizeof(GradProb) / 8);
-    const long it_off = L.off;
-    L.off += (long)(itiles.size() * sizeof(GradTile) / 8);
-    const long gt_off = L.off;
-    L.off += (long)(gtiles.size() * sizeof(GradTile) / 8);
+    const long gp_off = take(L.off, (long)(gp.size() * sizeof(GradProb) / 8));
+    const long it_off = take(L.off, (long)(itiles.size() * sizeof(GradTile) / 8));
+    const long gt_off = take(L.off, (long)(gtiles.size() * sizeof(GradTile) / 8));
 
-    const size_t in_bytes = sizeof(double) * (size_t)L.off, out_bytes = sizeof(double) * (size_t)L.roff;
-    std::vector<double> pageable;
-    double* hin = wave_staging(c, (size_t)(L.off + L.roff), pageable);
-    double* hout = hin + L.off;
-    wave_fill(a, packed, idx, nw, L, hin);
-    std::memcpy(hin + gp_off, gp.data(), gp.size() * sizeof(GradProb));
-    std::memcpy(hin + it_off, itiles.data(), itiles.size() * sizeof(GradTile));
-    std::memcpy(hin + gt_off, gtiles.data(), gtiles.size() * sizeof(GradTile));
-    DevBufs bufs(c);
-    void *in_d = nullptr, *ws_d = nullptr, *res_d = nullptr;
-    RC(bufs.get(in_bytes, &in_d));
-    RC(bufs.get(sizeof(double) * (size_t)L.ws, &ws_d));
-    RC(bufs.get(out_bytes, &res_d));
+    WaveMem m(c);
+    RC(m.alloc(L.off, L.ws, L.roff));
+    wave_fill(a, packed, idx, nw, L, m.hin);
+    std::memcpy(m.hin + gp_off, gp.data(), gp.size() * sizeof(GradProb));
+    std::memcpy(m.hin + it_off, itiles.data(), itiles.size() * sizeof(GradTile));
+    std::memcpy(m.hin + gt_off, gtiles.data(), gtiles.size() * sizeof(GradTile));
     RC(run_drained(c, [&]() -> int32_t {
-        const double* in = (const double*)in_d;
-        const GradProb* gps = reinterpret_cast<const GradProb*>(in + gp_off);
-        const GradTile* its = reinterpret_cast<const GradTile*>(in + it_off);
-        const GradTile* gts = reinterpret_cast<const GradTile*>(in + gt_off);
-        HIPCHK(hipMemcpyAsync(in_d, hin, in_bytes, hipMemcpyHostToDevice, c->sm));
-        if (a.ks) hipLaunchKernelGGL(batch_logpdf_kernel<true>, dim3((unsigned)nw), dim3(NT), 0, c->sm, in, (double*)ws_d, (double*)res_d, nw);
-        else hipLaunchKernelGGL(batch_logpdf_kernel<false>, dim3((unsigned)nw), dim3(NT), 0, c->sm, in, (double*)ws_d, (double*)res_d, nw);
+        const GradProb* gps = reinterpret_cast<const GradProb*>(m.in + gp_off);
+        const GradTile* its = reinterpret_cast<const GradTile*>(m.in + it_off);
+        const GradTile* gts = reinterpret_cast<const GradTile*>(m.in + gt_off);
+        RC(m.upload());
+        RC(launch_fit(m, a.ks != nullptr, nw));
+        hipLaunchKernelGGL(batch_inv_kernel, dim3((unsigned)itiles.size()), dim3(NT), 0, c->sm, m.in, m.ws, (const double*)m.res, nw, gps, its);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(batch_inv_kernel, dim3((unsigned)itiles.size()), dim3(NT), 0, c->sm, in, (double*)ws_d, (const double*)res_d, nw, gps, its);
+        RC(launch_grad(m, a.ks != nullptr, nw, gps, gts, gtiles.size()));
+        hipLaunchKernelGGL(batch_gsum_kernel, dim3((unsigned)nw), dim3(128), 0, c->sm, m.in, (const double*)m.ws, m.res, nw, gps);
         HIPCHK(hipGetLastError());
-        if (a.ks) hipLaunchKernelGGL(batch_grad_kernel<true>, dim3((unsigned)gtiles.size()), dim3(GNT), 0, c->sm, in, (double*)ws_d, (double*)res_d, nw, gps, gts);
-        else hipLaunchKernelGGL(batch_grad_kernel<false>, dim3((unsigned)gtiles.size()), dim3(GNT), 0, c->sm, in, (double*)ws_d, (double*)res_d, nw, gps, gts);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(batch_gsum_kernel, dim3((unsigned)nw), dim3(128), 0, c->sm, in, (const double*)ws_d, (double*)res_d, nw, gps);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(hout, res_d, out_bytes, hipMemcpyDeviceToHost, c->sm));
-        HIPCHK(hipStreamSynchronize(c->sm));
-        return 0;
+        return m.download_and_sync();
     }));
+    const double* hout = m.hout;
     c->batch_grad_problems += nw;
-    std::vector<int> pos((size_t)nw);
-    for (int s = 0; s < nw; ++s) pos[L.order[s]] = s;
     for (int t = 0; t < nw; ++t) {
         const int b = idx[t];
-        const GradProb& g = gp[pos[t]];
+        const GradProb& g = gp[L.pos[t]];
         const long n = L.pr[t].n;
         put_result(a, b, hout[t], (int32_t)hout[nw + t]);
         const double* G = hout + g.g_off;  // [0] noise, then the kernel's parameters
@@ -1425,32 +1242,15 @@ int32_t grad_batch_impl(gp_ctx* c, GradArgs& a) {
         if (a.dnoise && !a.dnoise[b]) return set_arg_err(a_dn, "a dnoise_out pointer is NULL");
         if (a.dy && !a.dy[b]) return set_arg_err(a_dy, "a dy_out pointer is NULL");
     }
-    // the path of a problem depends on that problem alone
-    const long max_n = batch_grad_max_n();
     std::vector<int> mine, routed;
-    for (int b = 0; b < a.nb; ++b) (batch_takes(a, b, max_n) ? mine : routed).push_back(b);
-    if (!mine.empty()) {
-        HIPCHK(hipSetDevice(c->device));
-        size_t i = 0;
-        while (i < mine.size()) {  // waves bounded by the launch size and by the workspace budget: slices, strips and tile sums count
-            size_t j = i, bytes = 0;
-            while (j < mine.size() && j - i < BATCH_WAVE_PROBLEMS) {
-                const size_t s = sizeof(double) * (size_t)grad_ws(a, packed, mine[j]);
-                if (j > i && bytes + s > BATCH_WS_BYTES) break;
-                bytes += s;
-                ++j;
-            }
-            RC(run_grad_wave(c, a, packed, mine.data() + i, (int)(j - i)));
-            i = j;
-        }
-    }
+    split_by_path(a, env_capped(getenv("GPMI_BATCH_GRAD_MAX_N"), GPMI355_BATCH_GRAD_MAX_N), mine, routed);
+    RC(for_each_wave(c, mine, [&](int b) { return WaveCost{sizeof(double) * (size_t)grad_ws(a, packed, b), 0}; },  // slices, strips and tile sums count
+                     [&](const int* idx, int nw) { return run_grad_wave(c, a, packed, idx, nw); }));
     // everything else: gp_logpdf_grad / gp_logpdf_grad_sum, one problem at a time, after the lock is released (as batch_impl does)
     gd.lk.unlock();
-    const size_t es = a.dtype == 0 ? 8 : 4;
     for (int b : routed) {
         const gp_points& x = a.xb(b);
-        put(a.logpdf_out, a.dtype, b, 0);
-        void* lp = (char*)a.logpdf_out + es * (size_t)b;
+        void* lp = logpdf_slot(a, b);
         const int32_t rc = a.ks ? gp_logpdf_grad_sum(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), lp, a.dtheta ? a.dtheta[b] : nullptr, a.dnb(b), a.dyb(b))
                                 : gp_logpdf_grad(c, &a.k[b], &x, &a.noise[b], a.mb(b), a.yb(b), lp, a.dvar ? &a.dvar[b] : nullptr,
                                                  a.dscale ? a.dscale[b] : nullptr, a.dnb(b), a.dyb(b), nullptr);

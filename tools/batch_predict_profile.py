@@ -6,12 +6,14 @@ with the arguments marshalled beforehand:
   t_loop   B times gp_posterior_fit + gp_posterior_predict(what = 3) + gp_posterior_free on the same library — the single path.
 Both end in a stream synchronise inside the library, so the host clock around them is the whole cost.  Per cell: one same-shape warm-up of each, then
 `samples` (>= 5) samples, each the mean of enough repetitions to fill `min_s` (0.2 s); reported: the median with min-max.  The two results of a cell
-are compared before they are timed (mean 1e-8, var 1e-9 absolute, logpdf 1e-10 relative).  One JSON object to stdout and to --out.
+are compared before they are timed (mean 1e-8, var 1e-9 absolute, logpdf 1e-10 relative).  GPMI_BATCH_MAX_N is set to the kernel's own limit (KERNEL_MAX_N)
+for the run, as tools/batch_profile.py does, so that every size up to it is served by the batch kernels.  One JSON object to stdout and to --out.
 
     python tools/batch_predict_profile.py [--sizes 64,256,545,768] [--batches 1,8,64,512] [--points 64,1024] [--out profiles/r19/batch_predict_profile.json]"""
 import argparse
 import ctypes as C
 import json
+import os
 import socket
 import sys
 from pathlib import Path
@@ -22,6 +24,8 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
 from tools.batch_profile import _sample, _stats  # noqa: E402  (the same sampling method)
+
+KERNEL_MAX_N = 2048  # BATCH_KERNEL_MAX_N of csrc/batch.hip: what the kernels admit, whatever GPMI355_BATCH_MAX_N routes to them
 
 
 def main():
@@ -34,13 +38,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--batch-only", action="store_true", help="time the batch call alone (a kernel trace of it: two kernels and one copy each way per call)")
     a = ap.parse_args()
+    os.environ["GPMI_BATCH_MAX_N"] = str(KERNEL_MAX_N)
     import abstractgps_jl_amd as agp
 
     ctx = agp.default_context(0)
     lib = ctx.lib
     cells = []
     for n in [int(v) for v in a.sizes.split(",")]:
-        assert n <= agp._lib.batch_max_n(), "the sweep covers what the batch kernel is routed"
+        assert n <= KERNEL_MAX_N, "the sweep covers what the batch kernel is routed"
         for B in [int(v) for v in a.batches.split(",")]:
             for ns in [int(v) for v in a.points.split(",")]:
                 rng = np.random.default_rng(n * 1000 + B + 7 * ns)
