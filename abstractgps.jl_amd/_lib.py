@@ -90,6 +90,10 @@ PROTOTYPES = {
                                C.POINTER(i32)]),
     "gp_predict_batch_sum": (i32, [vp, i32, PS, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), i32, PP, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp), vp,
                                    C.POINTER(i32)]),
+    "gp_predict_grad_batch": (i32, [vp, i32, PK, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), i32, PP, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp),
+                                    C.POINTER(vp), C.POINTER(vp), vp, C.POINTER(i32)]),
+    "gp_predict_grad_batch_sum": (i32, [vp, i32, PS, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), i32, PP, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp),
+                                        C.POINTER(vp), C.POINTER(vp), vp, C.POINTER(i32)]),
     "gp_logpdf_grad_batch": (i32, [vp, i32, PK, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(vp), C.POINTER(vp),
                                    C.POINTER(vp)]),
     "gp_logpdf_grad_batch_sum": (i32, [vp, i32, PS, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp), C.POINTER(vp),
@@ -157,6 +161,11 @@ def batch_max_n() -> int:
 def batch_grad_max_n() -> int:
     """GPMI355_BATCH_GRAD_MAX_N of include/gpmi355.h: the largest problem gp_logpdf_grad_batch hands to its gradient kernels."""
     return int(re.search(r"#define GPMI355_BATCH_GRAD_MAX_N (\d+)", HEADER.read_text()).group(1))
+
+
+def batch_pgrad_max_n() -> int:
+    """GPMI355_BATCH_PGRAD_MAX_N of include/gpmi355.h: the largest problem gp_predict_grad_batch hands to its kernels."""
+    return int(re.search(r"#define GPMI355_BATCH_PGRAD_MAX_N (\d+)", HEADER.read_text()).group(1))
 
 
 _lib = None

@@ -898,6 +898,83 @@ def mean_and_var_batch(fxs, ys, xs, *, what: int = 3, return_logpdf: bool = Fals
     return (pairs, lp) if return_logpdf else pairs
 
 
+# --------------------------------------------------------------------------------------------
+# gradients of the batched predictions w.r.t. the test inputs: gp_predict_grad_batch / gp_predict_grad_batch_sum
+# --------------------------------------------------------------------------------------------
+@dataclass(eq=False)
+class _PredictGradCall:
+    """The marshalled arguments of one gp_predict_grad_batch[_sum] call (everything after the ctx) and the buffers behind them."""
+
+    entry: str
+    nb: int
+    args: tuple
+    out: np.ndarray
+    info: np.ndarray
+    means: Optional[list]
+    vars: Optional[list]
+    dmeans: Optional[list]   # in the ABI layout of each xs_b (_dx_buffer)
+    dvars: Optional[list]
+    xpts: object             # the gp_points of the test points (nxs entries)
+    keep: object
+
+
+def _predict_grad_marshal(g: _BatchGroup, what: int) -> _PredictGradCall:
+    """ctypes arguments of one group — needs no context.  The arguments up to `what` are those of _predict_marshal; all four outputs of the sides in `what`."""
+    pc = _predict_marshal(g, what)
+    m = pc.keep
+    nbk, karr, nx, pts, narr, marr, ny, yarr, nxs, xpts, pmarr, _, moarr, voarr, out, info = pc.args
+    pxs = [xpts[0 if g.nxs == 1 else b] for b in range(pc.nb)]
+    dmeans = [_dx_buffer(px, g.dtype) for px in pxs] if what & 1 else None
+    dvars = [_dx_buffer(px, g.dtype) for px in pxs] if what & 2 else None
+    dmarr = (C.c_void_p * pc.nb)(*[a.ctypes.data for a in dmeans]) if dmeans is not None else None
+    dvarr = (C.c_void_p * pc.nb)(*[a.ctypes.data for a in dvars]) if dvars is not None else None
+    m.keep += [dmarr, dvarr]
+    args = (nbk, karr, nx, pts, narr, marr, ny, yarr, nxs, xpts, pmarr, what, moarr, voarr, dmarr, dvarr, out, info)
+    return _PredictGradCall("gp_predict_grad_batch" + ("_sum" if g.composite else ""), pc.nb, args, pc.out, pc.info, pc.means, pc.vars, dmeans, dvars, pxs, m)
+
+
+def mean_and_var_grad_batch(fxs, ys, xs, *, what: int = 3, mean_grads=None, return_logpdf: bool = False, on_error: str = "raise"):
+    """mean_and_var_grad(posterior(fx_b, y_b), xs_b) of many independent exact GPs in one library call per (ctx, dtype, single-kind / composite) group:
+    the predictions of mean_and_var_batch AND their gradients w.r.t. the test inputs — what a gradient-based acquisition step over many surrogates
+    (multi-start UCB / EI, one local GP per trust region, independent outputs sharing one x) evaluates.  fxs, ys, xs, what, on_error as in
+    mean_and_var_batch.  Returns the list of (mean, var, dmean, dvar) in the caller's order, None for whatever was not asked for; the gradients have the
+    shape of each xs_b's array, as mean_and_var_grad shapes them (with return_logpdf: that list and the array of logpdf(fx_b, y_b)).
+    The device treats the prior mean as constant in x*: a problem with a CustomMean and the mean side needs its entry of `mean_grads` (a sequence with one
+    entry per problem, None where not needed): a callable x -> the (ns × d) derivative of the mean function, which is added to dmean (TypeError without it)."""
+    if on_error not in ("raise", "nan"):
+        raise ValueError('on_error must be "raise" or "nan"')
+    if what not in (1, 2, 3):
+        raise ValueError("what must be 1 (mean), 2 (var) or 3 (both)")
+    fxs = list(fxs)
+    if not fxs:
+        return ([], np.empty(0)) if return_logpdf else []
+    n = len(fxs)
+    mean_grads = [None] * n if mean_grads is None else list(mean_grads)
+    if len(mean_grads) != n:
+        raise ValueError(f"DimensionMismatch: {n} problems but {len(mean_grads)} entries of mean_grads")
+    groups = _predict_groups(fxs, ys, xs)
+    for i, fx in enumerate(fxs):
+        if callable(fx.f.mean_fn) and (what & 1) and mean_grads[i] is None:
+            raise TypeError(f"problem {i}: the prior mean is a CustomMean: pass mean_grads[{i}] = callable returning its (ns × d) derivative at xs")
+    quads = [None] * n
+    parts = []
+    for g in groups:
+        call = _predict_grad_marshal(g, what)
+        ctx = g.ctx or default_context()
+        check(getattr(ctx.lib, call.entry)(ctx.handle, *call.args))
+        parts.append((g.index, call.out, call.info, None))
+        for j, i in enumerate(g.index):
+            px, x = call.xpts[j], g.xss[j]
+            dmean = _dx_shaped(call.dmeans[j], px, x) if call.dmeans is not None else None
+            dvar = _dx_shaped(call.dvars[j], px, x) if call.dvars is not None else None
+            if dmean is not None and callable(g.fxs[j].f.mean_fn):
+                gm = np.asarray(mean_grads[i](x), dtype=g.dtype).reshape(px.n, px.d)  # (ns × d)
+                dmean = dmean + (gm[:, 0] if px.layout == 0 else (gm.T if isinstance(_as_input(x), ColVecs) else gm))
+            quads[i] = (call.means[j] if call.means is not None else None, call.vars[j] if call.vars is not None else None, dmean, dvar)
+    lp = _batch_merge(n, parts, False, on_error)
+    return (quads, lp) if return_logpdf else quads
+
+
 def _terms(fx: FiniteGP, y, want_logdet: bool, want_sqmahal: bool):
     """gp_logpdf_terms (gp_logpdf_terms_sum for a composite kernel): logdet(cov(fx)) and / or sqmahal(fx, y) from ONE factorisation on the device."""
     f = fx.f

@@ -1,7 +1,8 @@
 // batch.hip — many small exact GPs in one call: gp_logpdf_batch / gp_logpdf_batch_sum, gp_predict_batch / gp_predict_batch_sum, gp_logpdf_grad_batch /
-// gp_logpdf_grad_batch_sum (include/gpmi355.h) and the kernels behind them: the fit (batch_logpdf_kernel, below), the predictions at each problem's test
-// points from the slices it leaves (batch_predict_kernel, further down) and the gradient from the same slices (batch_inv_kernel, batch_grad_kernel,
-// batch_gsum_kernel, behind it).
+// gp_logpdf_grad_batch_sum, gp_predict_grad_batch / gp_predict_grad_batch_sum (include/gpmi355.h) and the kernels behind them: the fit (batch_logpdf_kernel,
+// below), the predictions at each problem's test points from the slices it leaves (batch_predict_kernel, further down), the gradient of logpdf from the same
+// slices (batch_inv_kernel, batch_grad_kernel, batch_gsum_kernel, behind it) and the gradients of the predictions w.r.t. the test inputs from the strips the
+// predict kernel leaves and the S of batch_inv_kernel (batch_pgrad_kernel, last).
 //
 // ONE workgroup owns ONE problem from its inputs to its scalar: it assembles the lower triangle of K + Σy into the problem's slice of a
 // workspace (δ = y − m riding along as row np, as in the single path), factors it by a blocked right-looking Cholesky (64-column blocks:
@@ -13,7 +14,7 @@
 // batch it rides in.  The slice of a problem (its factor and the solved row) stays intact until the call ends.
 //
 // Problems the kernel does not take (fp32, a dense Σy, n > GPMI355_BATCH_MAX_N, D > 16) are answered inside the same call by the
-// single path (gp_logpdf / gp_posterior_fit and their *_sum forms; for predictions gp_posterior_fit + gp_posterior_predict + gp_posterior_free); which
+// single path (gp_logpdf / gp_posterior_fit and their *_sum forms; for predictions gp_posterior_fit + gp_posterior_predict[_grad] + gp_posterior_free); which
 // path serves a problem depends on that problem alone.
 #include "kfun.hpp"
 
@@ -669,6 +670,139 @@ __global__ __launch_bounds__(128) void batch_gsum_kernel(const double* __restric
     res[G.g_off + tid] = s;
 }
 
+// ---- the gradients of the predictions w.r.t. the test inputs: batch_pgrad_kernel --------------------------------------------------------------------
+// What batch_pgrad_kernel knows of a tile beyond its BatchTile; same position in its table as the tile in the tile table.  Offsets count doubles: s_off
+// (the S strip of the problem, as GradProb's) into the workspace, dmean_off / dvar_off into the result buffer (the problem's gradients, dimension-major
+// [d][ns]; −1: that side's gradient is not wanted).
+struct PGradTile {
+    long s_off, dmean_off, dvar_off;
+};
+static_assert(sizeof(PGradTile) % 8 == 0, "the tables are packed behind double data");
+
+// Launched directly behind the batch_predict_kernel launch of the same tiles (the strips of a wave are shared by its launch groups), ONE workgroup per tile:
+//   dmean[j, p] = Σ_i α_i ∂k(x*_j, x_i)/∂x*_p,   dvar[j, p] = −2 Σ_i W[j, i] ∂k(x*_j, x_i)/∂x*_p,   W = V Sᵀ  (w_j = C⁻¹ k_j = L⁻ᵀ (L⁻¹ k_j)).
+//   1. (variance side) W[i, c] = Σ_{k ≥ c} V[i, k] S[c, k] IN PLACE on the strip the predict kernel left (V = K* L⁻ᵀ, rows of the tile rounded up to 32), by
+//      64-column blocks j0 ascending, one 32×32 wave tile per wave, k0 = j0 … np − 64: S's row c is written from column 128⌊c / 128⌋ <= j0 on and zero left
+//      of c, so only what batch_inv_kernel wrote is read.  The two column tiles of a block read each other's columns of V: every wave finishes its
+//      accumulators, barrier, store, barrier; later blocks read only k >= their own j0.  Padded columns give W = 0 and the contraction runs over i < n.
+//   2. the contraction, ∂k re-evaluated from the packed inputs: one wave per test point (w, w + waves, …), lanes striding over the training points, fp64 sums per
+//      lane and dimension, a butterfly per wave, lane 0 writes.  Single kind: 2 s_p² σ² κ'(r²)(x*_p − x_p) (kappa_and_dr2); composite: ksum_gradx.
+// No atomics, no waits between workgroups, every sum in an order the problem's size fixes: a test point's gradient is the same bits alone, among other test
+// points, in any batch and on repetition.  Mean side alone: no strip, no S, no product.  A failed problem's tiles write NaN and read neither slice nor strip.
+// Threads: NT (eight waves, one wave tile each) for a single kind; PGNT_SUM (four waves, two wave tiles each) for a composite kernel, whose element body
+// with both sides' sums over 16 dimensions does not fit the 256 registers a lane of an eight-wave workgroup has (it spilled to scratch).  Each wave tile and
+// each test point is summed by one wave in the same order either way.
+enum { PGNT_SUM = 256 };
+template <bool SUM>
+__global__ __launch_bounds__(SUM ? PGNT_SUM : NT) void batch_pgrad_kernel(const double* __restrict__ in, double* __restrict__ ws, double* __restrict__ res,
+                                                                         int nw, const BatchTile* __restrict__ tiles,
+                                                                         const PGradTile* __restrict__ ptiles) {
+    constexpr int NTH = SUM ? PGNT_SUM : NT, NWV = NTH / 64, TPW = 8 / NWV;  // threads, waves, wave tiles per wave and 64-column block
+    __shared__ double kf[SUM ? KSum::MAXFT : 1][NTH];
+    const BatchTile& T = tiles[blockIdx.x];
+    const PGradTile& G = ptiles[blockIdx.x];
+    const BatchProb& P = reinterpret_cast<const BatchProb*>(in)[T.prob];
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = P.n, np = P.np, d = P.d, ns = T.ns, rows = T.rows;
+    const long ld = P.ld;
+    double* dmean_o = G.dmean_off >= 0 ? res + G.dmean_off + T.row0 : nullptr;
+    double* dvar_o = G.dvar_off >= 0 ? res + G.dvar_off + T.row0 : nullptr;
+    if (res[nw + P.slot] != 0.0) {  // the fit failed: NaN, and neither slice nor strip is read
+        for (int e = tid; e < rows * d; e += NTH) {
+            const int p = e / rows, i = e - p * rows;
+            if (dmean_o) dmean_o[(long)p * ns + i] = __builtin_nan("");
+            if (dvar_o) dvar_o[(long)p * ns + i] = __builtin_nan("");
+        }
+        return;
+    }
+    double* __restrict__ V = ws + T.strip_off;
+    const double* __restrict__ x = in + P.x_off;
+    const double* __restrict__ xs = in + T.xs_off + T.row0;
+    const double* __restrict__ alpha = dmean_o ? res + P.alpha_off : nullptr;
+
+    // ---- 1. W = V Sᵀ in place
+    if (dvar_o) {
+        const double* __restrict__ S = ws + G.s_off;
+        const int ntile = (rows + 31) / 32 * 2;  // wave tiles per 64-column block: at most eight
+        for (int j0 = 0; j0 < np; j0 += BT) {
+            d4_t acc[TPW][2][2];
+#pragma unroll
+            for (int q = 0; q < TPW; ++q) {
+                const int tile = w + NWV * q;  // wave-uniform
+                acc_zero(acc[q]);
+                if (tile < ntile)
+                    for (int k0 = j0; k0 < np; k0 += BT) mfma_tile_k64<false>(acc[q], V, 32 * (tile >> 1), S, j0 + 32 * (tile & 1), k0, ld, lane);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < TPW; ++q) {
+                const int tile = w + NWV * q;
+                if (tile < ntile) acc_store(acc[q], V, 32 * (tile >> 1), j0 + 32 * (tile & 1), ld, lane);
+            }
+            __syncthreads();
+        }
+    }
+
+    // ---- 2. the contraction
+    for (int i = w; i < rows; i += NWV) {  // wave-uniform
+        double xv[BATCH_MAXD], am[BATCH_MAXD], av[BATCH_MAXD];
+#pragma unroll
+        for (int p = 0; p < BATCH_MAXD; ++p) {
+            xv[p] = p < d ? xs[(long)p * ns + i] : 0.0;
+            am[p] = av[p] = 0.0;
+        }
+        const double* __restrict__ wrow = V + (long)i * ld;
+        for (int j = lane; j < n; j += 64) {
+            const double cm = alpha ? alpha[j] : 0.0;
+            const double cv = dvar_o ? wrow[j] : 0.0;
+            double t[BATCH_MAXD];
+#pragma unroll
+            for (int p = 0; p < BATCH_MAXD; ++p) t[p] = p < d ? xv[p] - x[(long)p * n + j] : 0.0;
+            if (SUM) {
+                double g[BATCH_MAXD];
+#pragma unroll
+                for (int p = 0; p < BATCH_MAXD; ++p) g[p] = 0.0;
+                ksum_gradx<double, BATCH_MAXD>(*reinterpret_cast<const KSum*>(in + P.ks_off), t, d, 1.0, g, kf, tid);
+#pragma unroll
+                for (int p = 0; p < BATCH_MAXD; ++p) {
+                    am[p] = fma(cm, g[p], am[p]);
+                    av[p] = fma(cv, g[p], av[p]);
+                }
+            } else {
+                double u[BATCH_MAXD], d2 = 0.0;
+#pragma unroll
+                for (int p = 0; p < BATCH_MAXD; ++p) {
+                    u[p] = (P.nscale == 0 ? 1.0 : P.scale[P.nscale == 1 ? 0 : p]) * t[p];
+                    d2 = fma(u[p], u[p], d2);
+                }
+                double kap, dk;
+                kappa_and_dr2<double>(P.kind, d2, kap, dk);
+                const double gm = cm * dk, gv = cv * dk;
+#pragma unroll
+                for (int p = 0; p < BATCH_MAXD; ++p) {
+                    am[p] = fma(gm, u[p], am[p]);
+                    av[p] = fma(gv, u[p], av[p]);
+                }
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < BATCH_MAXD; ++p) {
+            double a = am[p], b = av[p];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                a += __shfl_xor(a, o, 64);
+                b += __shfl_xor(b, o, 64);
+            }
+            if (lane == 0 && p < d) {
+                // single kind: the sums ran over κ'(r²) u_p with u = s ∘ t; ∂k/∂x*_p = 2 σ² s_p κ' u_p
+                const double sp = SUM ? 1.0 : 2.0 * P.variance * (P.nscale == 0 ? 1.0 : P.scale[P.nscale == 1 ? 0 : p]);
+                if (dmean_o) dmean_o[(long)p * ns + i] = sp * a;
+                if (dvar_o) dvar_o[(long)p * ns + i] = -2.0 * sp * b;
+            }
+        }
+    }
+}
+
 }  // namespace gpmi
 
 using namespace gpmi;
@@ -852,6 +986,11 @@ int32_t launch_predict(const WaveMem& m, bool ks, int nw, const BatchTile* tiles
     HIPCHK(hipGetLastError());
     return 0;
 }
+int32_t launch_pgrad(const WaveMem& m, bool ks, int nw, const BatchTile* tiles, const PGradTile* ptiles, size_t ntiles) {
+    hipLaunchKernelGGL(ks ? batch_pgrad_kernel<true> : batch_pgrad_kernel<false>, dim3((unsigned)ntiles), dim3(ks ? PGNT_SUM : NT), 0, m.c->sm, m.in, m.ws, m.res, nw, tiles, ptiles);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 int32_t launch_grad(const WaveMem& m, bool ks, int nw, const GradProb* gps, const GradTile* tiles, size_t ntiles) {
     hipLaunchKernelGGL(ks ? batch_grad_kernel<true> : batch_grad_kernel<false>, dim3((unsigned)ntiles), dim3(GNT), 0, m.c->sm, m.in, m.ws, m.res, nw, gps, tiles);
     HIPCHK(hipGetLastError());
@@ -989,18 +1128,42 @@ struct PredictArgs : BatchArgs {
     int32_t what;           // 1 mean | 2 var
     void* const* mean_out;
     void* const* var_out;
+    // gp_predict_grad_batch / _sum only (grad): the gradient arrays; there each of the four arrays may be NULL, not both of a side that is asked for
+    bool grad = false;
+    void* const* dmean_out = nullptr;
+    void* const* dvar_out = nullptr;
     const gp_points& xsb(int b) const { return xs[nxs == 1 ? 0 : b]; }
     const void* pmb(int b) const { return pm ? pm[b] : nullptr; }
+    void* out_b(void* const* arr, int side, int b) const { return (arr && (what & side)) ? arr[b] : nullptr; }
+    bool want_dmean() const { return grad && (what & 1) && dmean_out; }
+    bool want_dvar() const { return grad && (what & 2) && dvar_out; }
 };
 
 long predict_strip(const PredictArgs& a, long n) { return (a.what & 2) ? (long)TP * batch_ld(batch_np(n)) : 0; }  // the mean alone needs no strip
 
-// one wave: the fit launch of the problems idx[0..nw), then the predict launches against the slices it leaves.  Caller holds the ctx lock.
+// the S strip of a problem that has a variance-side gradient and test points (beside its slice, as in a gradient wave)
+long pgrad_s(const PredictArgs& a, int b) {
+    const long np = batch_np(a.xb(b).n);
+    return (a.want_dvar() && a.xsb(b).n > 0) ? np * batch_ld(np) : 0;
+}
+// a gradient of the result buffer, dimension-major [d][ns], into the container layout of xs
+void unpack_grad(const gp_points& xs, const double* g, double* out) {
+    const long ns = xs.n;
+    if (xs.layout != 1) {
+        std::memcpy(out, g, sizeof(double) * (size_t)(ns * xs.d));
+        return;
+    }
+    for (int dd = 0; dd < xs.d; ++dd)
+        for (long i = 0; i < ns; ++i) out[(long)dd + i * xs.d] = g[(long)dd * ns + i];
+}
+
+// one wave: the fit launch of the problems idx[0..nw), then the predict launches against the slices it leaves — for a gradient call (a.grad) S = L⁻ᵀ of the
+// problems that need it in front of them, and batch_pgrad_kernel directly behind each predict launch, over the same tiles.  Caller holds the ctx lock.
 int32_t run_predict_wave(gp_ctx* c, const PredictArgs& a, const std::vector<KSum>& packed, const int* idx, int nw) {
     WaveLayout L;
     wave_layout(a, idx, nw, [&](int b) { return (a.what & 1) && a.xsb(b).n > 0; }, L);
     // behind the fit's input: the test points (dimension-major, a shared set once), then the tile table; behind its results: mean and var of every problem
-    std::vector<long> xs_off((size_t)nw, -1), mean_off((size_t)nw, -1), var_off((size_t)nw, -1);
+    std::vector<long> xs_off((size_t)nw, -1), mean_off((size_t)nw, -1), var_off((size_t)nw, -1), dmean_off((size_t)nw, -1), dvar_off((size_t)nw, -1);
     SharedOnce xso{a.nxs == 1}, xsf{a.nxs == 1};  // layout, filling
     for (int t = 0; t < nw; ++t) {
         const gp_points& xs = a.xsb(idx[t]);
@@ -1008,9 +1171,22 @@ int32_t run_predict_wave(gp_ctx* c, const PredictArgs& a, const std::vector<KSum
         xs_off[t] = xso.place(L.off, (long)xs.d * xs.n);
         if (a.what & 1) mean_off[t] = take(L.roff, xs.n);
         if (a.what & 2) var_off[t] = take(L.roff, xs.n);
+        if (a.want_dmean()) dmean_off[t] = take(L.roff, (long)xs.d * xs.n);
+        if (a.want_dvar()) dvar_off[t] = take(L.roff, (long)xs.d * xs.n);
+    }
+    // a gradient call: the S strips beside the slices, their tiles of 128 rows and the table batch_inv_kernel reads (built as run_grad_wave builds them)
+    std::vector<GradProb> gp(a.grad ? (size_t)nw : 0, GradProb{-1, -1, -1, -1, 0, 0});
+    std::vector<GradTile> itiles;
+    for (int s = 0; s < nw && a.grad; ++s) {
+        const int t = L.order[s];
+        const BatchProb& p = L.pr[t];
+        if (pgrad_s(a, idx[t]) == 0) continue;
+        gp[s].s_off = take(L.ws, (long)p.np * p.ld);
+        for (int r0 = 0; r0 < p.np; r0 += TP) itiles.push_back(GradTile{s, r0 / TP, 0, 0});
     }
     // tiles of TP test points, the widest problems first; a launch closes at BATCH_PRED_TILES tiles or when its strips would pass the workspace budget
     std::vector<BatchTile> tiles;
+    std::vector<PGradTile> ptiles;
     std::vector<size_t> launch_end;
     long cur = L.ws, ws_top = L.ws;
     size_t launch_begin = 0;
@@ -1026,12 +1202,16 @@ int32_t run_predict_wave(gp_ctx* c, const PredictArgs& a, const std::vector<KSum
             }
             BatchTile tl{xs_off[t], cur, mean_off[t], var_off[t], L.pos[t], (int)ns, (int)row0, (int)std::min<long>(TP, ns - row0)};
             tiles.push_back(tl);
+            if (a.grad) ptiles.push_back(PGradTile{gp[s].s_off, dmean_off[t], dvar_off[t]});
             cur += strip;
             ws_top = std::max(ws_top, cur);
         }
     }
     if (tiles.size() > launch_begin) launch_end.push_back(tiles.size());
     const long tile_off = take(L.off, (long)(tiles.size() * sizeof(BatchTile) / 8));
+    const long pt_off = take(L.off, (long)(ptiles.size() * sizeof(PGradTile) / 8));
+    const long gp_off = take(L.off, (long)(gp.size() * sizeof(GradProb) / 8));
+    const long it_off = take(L.off, (long)(itiles.size() * sizeof(GradTile) / 8));
 
     WaveMem m(c);
     RC(m.alloc(L.off, ws_top, L.roff));
@@ -1041,28 +1221,41 @@ int32_t run_predict_wave(gp_ctx* c, const PredictArgs& a, const std::vector<KSum
         if (xs.n > 0 && xsf.claim()) pack_points(xs, m.hin + xs_off[t]);
     }
     if (!tiles.empty()) std::memcpy(m.hin + tile_off, tiles.data(), tiles.size() * sizeof(BatchTile));
+    if (!ptiles.empty()) std::memcpy(m.hin + pt_off, ptiles.data(), ptiles.size() * sizeof(PGradTile));
+    if (!gp.empty()) std::memcpy(m.hin + gp_off, gp.data(), gp.size() * sizeof(GradProb));
+    if (!itiles.empty()) std::memcpy(m.hin + it_off, itiles.data(), itiles.size() * sizeof(GradTile));
     RC(run_drained(c, [&]() -> int32_t {
         RC(m.upload());
         RC(launch_fit(m, a.ks != nullptr, nw));
+        if (!itiles.empty()) {
+            hipLaunchKernelGGL(batch_inv_kernel, dim3((unsigned)itiles.size()), dim3(NT), 0, c->sm, m.in, m.ws, (const double*)m.res, nw,
+                               reinterpret_cast<const GradProb*>(m.in + gp_off), reinterpret_cast<const GradTile*>(m.in + it_off));
+            HIPCHK(hipGetLastError());
+        }
         size_t t0 = 0;
         for (size_t t1 : launch_end) {
-            RC(launch_predict(m, a.ks != nullptr, nw, reinterpret_cast<const BatchTile*>(m.in + tile_off) + t0, t1 - t0));
+            const BatchTile* tl = reinterpret_cast<const BatchTile*>(m.in + tile_off) + t0;
+            RC(launch_predict(m, a.ks != nullptr, nw, tl, t1 - t0));
+            // the strips are shared by the launch groups: the gradients of a group follow its own predict launch and precede the next one
+            if (a.want_dmean() || a.want_dvar()) RC(launch_pgrad(m, a.ks != nullptr, nw, tl, reinterpret_cast<const PGradTile*>(m.in + pt_off) + t0, t1 - t0));
             t0 = t1;
         }
         return m.download_and_sync();
     }));
     const double* hout = m.hout;
+    if (a.grad) c->batch_pgrad_problems += nw;
     for (int t = 0; t < nw; ++t) {
         const int b = idx[t];
         put_result(a, b, hout[t], (int32_t)hout[nw + t]);
         const long ns = a.xsb(b).n;
         if (ns == 0) continue;
-        if (a.what & 1) {
-            double* mo = (double*)a.mean_out[b];
+        if (double* mo = (double*)a.out_b(a.mean_out, 1, b)) {
             const double* pm = (const double*)a.pmb(b);
             for (long j = 0; j < ns; ++j) mo[j] = pm ? pm[j] + hout[mean_off[t] + j] : hout[mean_off[t] + j];
         }
-        if (a.what & 2) std::memcpy(a.var_out[b], hout + var_off[t], sizeof(double) * (size_t)ns);
+        if (void* vo = a.out_b(a.var_out, 2, b)) std::memcpy(vo, hout + var_off[t], sizeof(double) * (size_t)ns);
+        if (dmean_off[t] >= 0) unpack_grad(a.xsb(b), hout + dmean_off[t], (double*)a.dmean_out[b]);
+        if (dvar_off[t] >= 0) unpack_grad(a.xsb(b), hout + dvar_off[t], (double*)a.dvar_out[b]);
     }
     return 0;
 }
@@ -1118,6 +1311,77 @@ int32_t predict_batch_impl(gp_ctx* c, PredictArgs& a) {
                 if (a.what & 1) fill_nan(a.mean_out[b], a.dtype, xs.n);
                 if (a.what & 2) fill_nan(a.var_out[b], a.dtype, xs.n);
             }
+        }
+    }
+    return 0;
+}
+
+// ---- gp_predict_grad_batch / gp_predict_grad_batch_sum ---------------------------------------------------------------------------------------------------
+enum { PGRAD_GROUP_TILES = 256 };  // strips a wave of gp_predict_grad_batch keeps room for: one tile per CU in a launch group at least
+// NaN in every output of problem b that the call was given
+void pgrad_fill_nan(const PredictArgs& a, int b) {
+    const gp_points& xs = a.xsb(b);
+    if (xs.n <= 0) return;
+    fill_nan(a.out_b(a.mean_out, 1, b), a.dtype, xs.n);
+    fill_nan(a.out_b(a.var_out, 2, b), a.dtype, xs.n);
+    fill_nan(a.out_b(a.dmean_out, 1, b), a.dtype, xs.n * xs.d);
+    fill_nan(a.out_b(a.dvar_out, 2, b), a.dtype, xs.n * xs.d);
+}
+
+int32_t predict_grad_batch_impl(gp_ctx* c, PredictArgs& a) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    if (a.nb < 0) return set_arg_err(2, "nb must be >= 0");
+    if (a.nb == 0) return 0;
+    RC(check_batch_head(a));
+    if (a.nxs != 1 && a.nxs != a.nb) return set_arg_err(10, "nxs must be 1 (one xs shared by every problem) or nb");
+    if (!a.xs) return set_arg_err(11, "test points array is NULL");
+    if (a.what <= 0 || a.what > 3) return set_arg_err(13, "what must be a combination of 1|2");
+    if ((a.what & 1) && !a.mean_out && !a.dmean_out) return set_arg_err(14, "mean_out and dmean_out are both NULL");
+    if ((a.what & 2) && !a.var_out && !a.dvar_out) return set_arg_err(15, "var_out and dvar_out are both NULL");
+    if (!a.info_out) return set_arg_err(19, "info_out is NULL");
+    std::vector<KSum> packed;
+    RC(check_batch_problems(a, packed));
+    for (int b = 0; b < a.nb; ++b) {
+        const gp_points& xs = a.xsb(b);
+        if (xs.n < 0) return set_arg_err(11, "xs: n must be >= 0");
+        if (xs.n == 0) continue;  // no test points: nothing of this problem's xs or outputs is touched
+        RC(check_points(&xs, 11));
+        if (xs.d != a.xb(b).d) return set_arg_err(11, "xs has a different D than the training inputs");
+        if ((a.what & 1) && a.mean_out && !a.mean_out[b]) return set_arg_err(14, "a mean_out pointer is NULL");
+        if ((a.what & 2) && a.var_out && !a.var_out[b]) return set_arg_err(15, "a var_out pointer is NULL");
+        if ((a.what & 1) && a.dmean_out && !a.dmean_out[b]) return set_arg_err(16, "a dmean_out pointer is NULL");
+        if ((a.what & 2) && a.dvar_out && !a.dvar_out[b]) return set_arg_err(17, "a dvar_out pointer is NULL");
+    }
+    std::vector<int> mine, routed;
+    split_by_path(a, env_capped(getenv("GPMI_BATCH_PGRAD_MAX_N"), GPMI355_BATCH_PGRAD_MAX_N), mine, routed);
+    // The slices and S strips of a wave fit in the budget beside PGRAD_GROUP_TILES predict strips of its widest problem (W overwrites V in the strip: no second
+    // one).  Room for ONE strip, as gp_predict_batch leaves it, lets a wave that fills the budget run one tile per launch group — measured here at B = 512,
+    // ns = 1 024: 6.1 s at n = 1 024 against 2.4 s at n = 1 536; a group of a tile per CU keeps the chip busy.
+    auto cost = [&](int b) {
+        const long n = a.xb(b).n;
+        return WaveCost{sizeof(double) * (size_t)(batch_slice(n) + pgrad_s(a, b)),
+                        a.xsb(b).n > 0 ? sizeof(double) * (size_t)(PGRAD_GROUP_TILES * predict_strip(a, n)) : 0};
+    };
+    RC(for_each_wave(c, mine, cost, [&](const int* idx, int nw) { return run_predict_wave(c, a, packed, idx, nw); }));
+    // everything else: fit, predict_grad and free on the single path, one problem at a time, after the lock is released (as batch_impl does)
+    gd.lk.unlock();
+    for (int b : routed) {
+        const gp_points& x = a.xb(b);
+        const gp_points& xs = a.xsb(b);
+        gp_post* post = nullptr;
+        void* lp = logpdf_slot(a, b);
+        int32_t rc = a.ks ? gp_posterior_fit_sum(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), &post, nullptr, lp)
+                          : gp_posterior_fit(c, &a.k[b], &x, &a.noise[b], a.mb(b), a.yb(b), &post, nullptr, lp);
+        if (rc == 0 && xs.n > 0)
+            rc = gp_posterior_predict_grad(post, &xs, a.pmb(b), a.what, a.out_b(a.mean_out, 1, b), a.out_b(a.var_out, 2, b), a.out_b(a.dmean_out, 1, b),
+                                           a.out_b(a.dvar_out, 2, b));
+        if (post) (void)gp_posterior_free(post);
+        if (rc < 0) return rc;
+        a.info_out[b] = rc;
+        if (rc > 0) {
+            put_result(a, b, std::numeric_limits<double>::quiet_NaN(), rc);
+            pgrad_fill_nan(a, b);
         }
     }
     return 0;
@@ -1300,6 +1564,26 @@ int32_t gp_predict_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t 
     PredictArgs a{{nb, nullptr, k, nx, x, noise, mean_or_null, ny, y, logpdf_out_or_null, info_out, nullptr, 0}, nxs, xs, prior_mean_xs_or_null, what, mean_out, var_out};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return predict_batch_impl(ctx, a);
+}
+
+int32_t gp_predict_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                              const void* const* mean_or_null, int32_t ny, const void* const* y, int32_t nxs, const gp_points* xs,
+                              const void* const* prior_mean_xs_or_null, int32_t what, void* const* mean_out_or_null, void* const* var_out_or_null,
+                              void* const* dmean_out_or_null, void* const* dvar_out_or_null, void* logpdf_out_or_null, int32_t* info_out) {
+    PredictArgs a{{nb, k, nullptr, nx, x, noise, mean_or_null, ny, y, logpdf_out_or_null, info_out, nullptr, 0}, nxs, xs, prior_mean_xs_or_null, what,
+                  mean_out_or_null, var_out_or_null, true, dmean_out_or_null, dvar_out_or_null};
+    if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
+    return predict_grad_batch_impl(ctx, a);
+}
+
+int32_t gp_predict_grad_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                                  const void* const* mean_or_null, int32_t ny, const void* const* y, int32_t nxs, const gp_points* xs,
+                                  const void* const* prior_mean_xs_or_null, int32_t what, void* const* mean_out_or_null, void* const* var_out_or_null,
+                                  void* const* dmean_out_or_null, void* const* dvar_out_or_null, void* logpdf_out_or_null, int32_t* info_out) {
+    PredictArgs a{{nb, nullptr, k, nx, x, noise, mean_or_null, ny, y, logpdf_out_or_null, info_out, nullptr, 0}, nxs, xs, prior_mean_xs_or_null, what,
+                  mean_out_or_null, var_out_or_null, true, dmean_out_or_null, dvar_out_or_null};
+    if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
+    return predict_grad_batch_impl(ctx, a);
 }
 
 int32_t gp_logpdf_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, const gp_noise* noise,

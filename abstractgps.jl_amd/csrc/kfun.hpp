@@ -122,7 +122,8 @@ __device__ __forceinline__ T ksum_eval(const KSum& k, const T (&t)[DR], int d) {
     return sum;
 }
 
-// ---- derivatives: κ with dκ/dr² of the four radial kinds, and ∂C_ij/∂θ of a composite kernel (kgrad_* in kernels.hpp, batch_grad_kernel in batch.hip)
+// ---- derivatives: κ with dκ/dr² of the four radial kinds, ∂C_ij/∂θ of a composite kernel (kgrad_* in kernels.hpp, batch_grad_kernel in batch.hip) and, last,
+// its ∂k/∂t (ksum_gradx: kgradx_sum_kernel / kpgrad_sum_kernel in kernels.hpp, batch_pgrad_kernel in batch.hip)
 //   dκ/dr²: SE −κ/2 · Matern12 −κ/(2r), 0 at r = 0 · Matern32 −(3/2)e^{−√3 r} · Matern52 −(5/6)(1+√5 r)e^{−√5 r}
 template <typename T> __device__ __forceinline__ void kappa_and_dr2(int kind, T d2, T& kap, T& dk) {
     if (kind == 0) {
@@ -221,6 +222,69 @@ __device__ __forceinline__ void ksum_grad(const KSum& k, const T (&t)[DR], int d
             pre *= kj;
         }
     }
+}
+
+// acc[p] += w · ∂k/∂t_p at the differences t, k = Σ_t σ_t² Π_f κ_f:  ∂k/∂t_p = Σ_t σ_t² Σ_f (Π_{g≠f} κ_g) ∂κ_f/∂t_p, the product over the other factors as
+// prefix × suffix with the κ_f in this thread's LDS slots (stride NTH, deduced from the array), as ksum_grad.  With c_p the factor's transform (1, s or v_p):
+//   kinds 0..3 and RQ: ∂κ_f/∂t_p = ∂κ/∂d² · 2 c_p² t_p (∂κ/∂d² as ksum_factor_grad; Matern12 at d = 0 taken as 0);  White: 0;
+//   Periodic (u_p = c_p t_p): ∂κ_f/∂t_p = −κ (π/2) sinpi(2u_p)/r_p² · c_p.
+// Factors without a transform or with a ScaleTransform share the direction t: their coefficients add up in one scalar, applied once at the end.
+template <typename T, int DR, int NTH>
+__device__ __forceinline__ void ksum_gradx(const KSum& k, const T (&t)[DR], int d, double w, double (&acc)[DR], double (*kf)[NTH], int tid) {
+    T r2;
+    bool eq;
+    ksum_r2<T, DR>(t, r2, eq);
+    double iso = 0.0;
+    for (int tt = 0; tt < k.nterms; ++tt) {
+        const int f0 = k.t0[tt], nf = k.t0[tt + 1] - f0;
+        for (int j = 0; j < nf; ++j) kf[j][tid] = (double)ksum_factor<T, DR>(k, f0 + j, t, r2, eq, d);
+        const double wv = w * k.th[k.tv[tt]];
+        double pre = 1.0;
+        for (int j = 0; j < nf; ++j) {
+            double suf = 1.0;
+            for (int i = j + 1; i < nf; ++i) suf *= kf[i][tid];
+            const double kj = kf[j][tid], c = wv * pre * suf;
+            pre *= kj;
+            const int f = f0 + j, kind = k.kind[f], ns = k.ns[f];
+            if (kind == 6) continue;
+            if (kind == 4) {
+                const double ck = -c * kj * 1.5707963267948966192;
+#pragma unroll
+                for (int p = 0; p < DR; ++p)
+                    if (p < d) {
+                        const T sc = ns == 0 ? T(1) : (T)k.th[k.so[f] + (ns == 1 ? 0 : p)];
+                        const double r = k.th[k.po[f] + p];
+                        acc[p] += ck * (double)sinpi_t(T(2) * sc * t[p]) * (double)sc / (r * r);
+                    }
+                continue;
+            }
+            const T d2 = ksum_d2<T, DR>(k, f, t, r2, d);
+            double dk;
+            if (kind == 5) {
+                dk = -kj / (2.0 * (1.0 + (double)d2 / (2.0 * k.th[k.po[f]])));
+            } else {
+                T kk, dkt;
+                kappa_and_dr2<T>(kind, d2, kk, dkt);
+                dk = (double)dkt;
+            }
+            const double c2 = 2.0 * c * dk;
+            if (ns == 0) {
+                iso += c2;
+            } else if (ns == 1) {
+                const double s = k.th[k.so[f]];
+                iso += c2 * s * s;
+            } else {
+#pragma unroll
+                for (int p = 0; p < DR; ++p)
+                    if (p < d) {
+                        const double v = k.th[k.so[f] + p];
+                        acc[p] += c2 * v * v * (double)t[p];
+                    }
+            }
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < DR; ++p) acc[p] += iso * (double)t[p];
 }
 
 }  // namespace gpmi

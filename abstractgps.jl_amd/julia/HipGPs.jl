@@ -28,7 +28,7 @@ using KernelFunctions: SqExponentialKernel, Matern12Kernel, ExponentialKernel, M
 using LinearAlgebra, FillArrays, Statistics, StatsBase, Distributions, Random
 using ChainRulesCore
 
-export HipGP, HipPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, elbo_and_grad, logpdf_batch, mean_and_var_batch, logpdf_and_grad_batch, BatchPosDefException
+export HipGP, HipPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, elbo_and_grad, logpdf_batch, mean_and_var_batch, mean_and_var_grad_batch, logpdf_and_grad_batch, BatchPosDefException
 
 const libgpmi355 = get(ENV, "GPMI355_LIB", joinpath(@__DIR__, "..", "csrc", "libgpmi355.so"))
 
@@ -531,6 +531,98 @@ function mean_and_var_batch(fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys, xs; wh
     (on_error === :raise && bad !== nothing) && throw(BatchPosDefException(Int(info[bad]), bad))
     pairs = [(means[b], vars[b]) for b in 1:nb]
     return return_logpdf ? (pairs, lp) : pairs
+end
+
+# ---- gradients of the batched predictions w.r.t. the test inputs: gp_predict_grad_batch / gp_predict_grad_batch_sum ----------------
+# mean_and_var_grad_batch(fxs, ys, xs): what mean_and_var_batch returns AND the gradients of both sides w.r.t. the test inputs — a gradient-based
+# acquisition step over many independent surrogates — in ONE library call per (context, eltype, single-kind / composite) group.  Arguments as in
+# mean_and_var_batch.  Returns the vector of (mean, var, dmean, dvar) tuples in the caller's order, `nothing` for whatever was not asked for; a gradient
+# lies in the container layout of its xs (Vector / D×N of ColVecs / N×D of RowVecs), as predict_grad returns it.  The device takes the prior mean as
+# constant in x*: the mean side of a CustomMean prior needs its entry of `mean_grads` (a vector with one entry per problem, `nothing` where not needed):
+# a function x -> the ns × d derivative of the mean function, which is added to dmean (ArgumentError without it).  Every problem must be one the ABI has
+# a layout for (as logpdf_and_grad_batch demands).
+grad_plus(x::AbstractVector{<:Real}, dm, g) = dm .+ vec(g)
+grad_plus(x::ColVecs, dm, g) = dm .+ permutedims(g)
+grad_plus(x::RowVecs, dm, g) = dm .+ g
+function mean_and_var_grad_batch(fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys, xs; what::Integer=3, mean_grads=nothing, return_logpdf::Bool=false,
+                                 on_error::Symbol=:raise)
+    on_error in (:raise, :nan) || throw(ArgumentError("on_error must be :raise or :nan"))
+    what in (1, 2, 3) || throw(ArgumentError("what must be 1 (mean), 2 (var) or 3 (both)"))
+    nb = length(fxs)
+    yv = (ys isa AbstractVector{<:Real}) ? fill(ys, nb) : collect(ys)
+    xv = (xs isa ColVecs || xs isa RowVecs || xs isa AbstractVector{<:Real}) ? fill(xs, nb) : collect(xs)
+    mg = mean_grads === nothing ? fill(nothing, nb) : collect(Any, mean_grads)
+    length(yv) == nb || throw(DimensionMismatch("$(nb) problems but $(length(yv)) observation vectors"))
+    length(xv) == nb || throw(DimensionMismatch("$(nb) problems but $(length(xv)) sets of test points"))
+    length(mg) == nb || throw(DimensionMismatch("$(nb) problems but $(length(mg)) entries of mean_grads"))
+    args = [marshal(fxs[b], eltype(yv[b])) for b in 1:nb]
+    any(a -> a === nothing, args) && throw(ArgumentError("kernel / noise form is not accelerated"))
+    T = (nb > 0 && all(a -> a.T === Float32, args)) ? Float32 : Float64
+    lp = Vector{T}(undef, nb)
+    info = zeros(Int32, nb)
+    quads = Vector{Any}(nothing, nb)
+    groups = Dict{Any,Vector{Int}}()
+    for b in 1:nb
+        length(yv[b]) == length(fxs[b]) || throw(DimensionMismatch("problem $(b): length(fx) = $(length(fxs[b])) but y has $(length(yv[b])) entries"))
+        points(xv[b], args[b].T) === nothing && throw(ArgumentError("unsupported input container for the test points of problem $(b) (use a Vector, ColVecs or RowVecs)"))
+        ((what & 1) != 0 && fxs[b].f.gp.mean isa CustomMean && mg[b] === nothing) &&
+            throw(ArgumentError("problem $(b): the prior mean is a CustomMean: pass mean_grads[$(b)] = function returning its ns × d derivative at xs"))
+        push!(get!(groups, (fxs[b].f.ctx, args[b].T, haskey(args[b], :ks)), Int[]), b)
+    end
+    for ((ctx, Tg, composite), idx) in groups
+        g = length(idx)
+        nx = all(b -> fxs[b].x === fxs[idx[1]].x, idx) ? 1 : g
+        ny = all(b -> yv[b] === yv[idx[1]], idx) ? 1 : g
+        nxs = all(b -> xv[b] === xv[idx[1]], idx) ? 1 : g
+        cxs = [args[b].cx for b in idx[1:nx]]
+        cns = [args[b].cn for b in idx]
+        ybufs = [Vector{Tg}(yv[b]) for b in idx[1:ny]]
+        yptrs = Ptr{Cvoid}[pointer(v) for v in ybufs]
+        mptrs = Ptr{Cvoid}[args[b].m === nothing ? C_NULL : pointer(args[b].m) for b in idx]
+        xsp = [points(xv[b], Tg) for b in idx[1:nxs]]  # (buffer, CPoints)
+        cxss = [p[2] for p in xsp]
+        pms = [prior_mean(fxs[b].f.gp, xv[b], Tg) for b in idx]  # m(x*) on the host; nothing = ZeroMean
+        pmptrs = Ptr{Cvoid}[m === nothing ? C_NULL : pointer(m) for m in pms]
+        mbufs = [Vector{Tg}(undef, (what & 1) != 0 ? length(xv[b]) : 0) for b in idx]
+        vbufs = [Vector{Tg}(undef, (what & 2) != 0 ? length(xv[b]) : 0) for b in idx]
+        dmbufs = [(what & 1) != 0 ? similar(xsp[nxs == 1 ? 1 : j][1]) : Tg[] for j in 1:g]  # in the container layout of xs
+        dvbufs = [(what & 2) != 0 ? similar(xsp[nxs == 1 ? 1 : j][1]) : Tg[] for j in 1:g]
+        moptrs = Ptr{Cvoid}[pointer(v) for v in mbufs]
+        voptrs = Ptr{Cvoid}[pointer(v) for v in vbufs]
+        dmptrs = Ptr{Cvoid}[pointer(v) for v in dmbufs]
+        dvptrs = Ptr{Cvoid}[pointer(v) for v in dvbufs]
+        out = Vector{Tg}(undef, g)
+        inf = zeros(Int32, g)
+        GC.@preserve args ybufs cxs cns yptrs mptrs xsp cxss pms pmptrs mbufs vbufs dmbufs dvbufs moptrs voptrs dmptrs dvptrs out inf begin
+            if composite
+                ks = [args[b].ks for b in idx]
+                GC.@preserve ks check(ccall((:gp_predict_grad_batch_sum, libgpmi355), Int32,
+                    (Ptr{Cvoid}, Int32, Ptr{CKSum}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Int32, Ptr{CPoints},
+                     Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32}),
+                    ctx.handle, g, ks, nx, cxs, cns, mptrs, ny, yptrs, nxs, cxss, pmptrs, what, (what & 1) != 0 ? pointer(moptrs) : C_NULL,
+                    (what & 2) != 0 ? pointer(voptrs) : C_NULL, (what & 1) != 0 ? pointer(dmptrs) : C_NULL, (what & 2) != 0 ? pointer(dvptrs) : C_NULL,
+                    out, inf))
+            else
+                cks = [args[b].ck for b in idx]
+                GC.@preserve cks check(ccall((:gp_predict_grad_batch, libgpmi355), Int32,
+                    (Ptr{Cvoid}, Int32, Ptr{CKernel}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Int32, Ptr{CPoints},
+                     Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32}),
+                    ctx.handle, g, cks, nx, cxs, cns, mptrs, ny, yptrs, nxs, cxss, pmptrs, what, (what & 1) != 0 ? pointer(moptrs) : C_NULL,
+                    (what & 2) != 0 ? pointer(voptrs) : C_NULL, (what & 1) != 0 ? pointer(dmptrs) : C_NULL, (what & 2) != 0 ? pointer(dvptrs) : C_NULL,
+                    out, inf))
+            end
+        end
+        for (j, b) in enumerate(idx)
+            lp[b] = out[j]
+            info[b] = inf[j]
+            dm = (what & 1) != 0 ? dmbufs[j] : nothing
+            (dm !== nothing && fxs[b].f.gp.mean isa CustomMean) && (dm = grad_plus(xv[b], dm, Tg.(mg[b](xv[b]))))
+            quads[b] = ((what & 1) != 0 ? mbufs[j] : nothing, (what & 2) != 0 ? vbufs[j] : nothing, dm, (what & 2) != 0 ? dvbufs[j] : nothing)
+        end
+    end
+    bad = findfirst(!=(0), info)
+    (on_error === :raise && bad !== nothing) && throw(BatchPosDefException(Int(info[bad]), bad))
+    return return_logpdf ? (quads, lp) : quads
 end
 
 # ---- the training half: gp_logpdf_grad_batch / gp_logpdf_grad_batch_sum ------------------------------------------------------------

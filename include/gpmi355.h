@@ -479,6 +479,46 @@ int32_t gp_predict_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t 
                              const void* const* prior_mean_xs_or_null, int32_t what, void* const* mean_out, void* const* var_out,
                              void* logpdf_out_or_null, int32_t* info_out);
 
+/* gp_predict_batch with the gradients of its outputs w.r.t. the test inputs: what every gradient-based acquisition step over many independent
+ * surrogates asks for (multi-start UCB / EI, one local GP per trust region, independent outputs sharing one x, per-fold sensitivity) — per problem
+ * gp_posterior_fit + gp_posterior_predict_grad + gp_posterior_free otherwise.
+ *   Everything up to `what` means what it means in gp_predict_batch (nxs ∈ {1, nb}, ns_b = 0 legal, what bit 0 the mean side, bit 1 the variance side).
+ *   Per side the conventions are those of gp_posterior_predict_grad: a side that is asked for writes its values (mean_out / var_out: nb pointers to ns_b
+ *   entries) and / or its gradient (dmean_out / dvar_out: nb pointers to ns_b * d entries in the container layout of xs_b, in the call's dtype).  Each of
+ *   the four arrays may be NULL, not both of a side that is asked for; an array that is given holds a non-NULL pointer wherever ns_b > 0.
+ *     dmean[j, p] = sum_i alpha_i dk(x*_j, x_i)/dx*_jp,     dvar[j, p] = -2 sum_i w_ji dk(x*_j, x_i)/dx*_jp,     w_j = C^-1 k_j.
+ *   The prior mean counts as constant in x*, k(x*, x*) is constant, Matern12 at distance 0 contributes 0, a White factor contributes 0.
+ * Failure is data: info_out[b] > 0 means NaN in every output of that problem (logpdf included), the other problems are not affected.  The return value
+ * reports argument errors only (−i, reason in gp_last_error(); nb = 0 returns 0 and touches nothing).
+ * fp64 problems with noise kind 0 / 1, D <= 16 and n_b <= GPMI355_BATCH_PGRAD_MAX_N run on the batch kernels (csrc/batch.hip), per wave: batch_logpdf_kernel,
+ * batch_inv_kernel (S = L⁻ᵀ beside the slice, only for problems with a variance-side gradient and ns_b > 0), then per predict launch group
+ * batch_predict_kernel (mean, variance, V = K* L⁻ᵀ left in the tile's strip) and directly behind it batch_pgrad_kernel over the same tiles: the weights
+ * W = V Sᵀ by fp64 MFMA IN PLACE on the strip (64-column blocks ascending; accumulate, barrier, store, barrier), then the contraction with dk/dx*
+ * re-evaluated from the packed inputs — one wave per test point, lanes striding over the training points, fp64 sums, a butterfly, one writer per (j, p).
+ * No atomics, no waits between workgroups: a test point's gradient is the same bits alone, among other test points, in any batch and on repetition;
+ * mean, var and logpdf are the bits of gp_predict_batch (the same kernels).  The mean side alone needs no strip, no S and no product.  Every other problem
+ * is answered inside the same call by gp_posterior_fit(_sum) + gp_posterior_predict_grad + gp_posterior_free.  The read-only ctx parameter
+ * "batch_pgrad_kernel_problems" counts the problems the kernels served.
+ * GPMI355_BATCH_PGRAD_MAX_N: chosen by the rule that fixed the other two — the largest multiple of 128 of the measured sweep (tools/batch_predict_grad_profile.py,
+ * profiles/r22/batch_predict_grad_profile.json: n = 64 … 2 048 × nb = 1, 8, 64, 512 × ns = 1, 64, 1 024, SE, D = 3, scalar noise, what = 3 with all four outputs) at which ONE
+ * gp_predict_grad_batch call beat the loop of gp_posterior_fit + gp_posterior_predict_grad + gp_posterior_free in every cell with nb >= 8, the loop run twice — on a default ctx and
+ * on a ctx with "dib_nb" = 128 (the blocked single path) — and the faster of the two taken.  The nb = 8, ns = 1 cells decide it (the default-ctx loop is the opponent there):
+ * 1 152 points 11.43 ms (11.42 – 11.44) against 11.46 ms (11.45 – 11.47) — a win by 0.3 %, the ranges disjoint — 1 280 points 14.63 ms against 12.85 ms; 1 024 points is the last
+ * size won by more than 5 % in every such cell (8.83 against 9.50 ms).  At nb = 64 the batch call wins every size but 2 048 points with 1 024 test points (291 against 177 ms), at
+ * nb = 512 every size of the sweep (1 152 points, ns = 1 024: 198 against 1 088 ms); a single problem loses from 128 points on (ns = 64: 0.42 against 0.41 ms), as in the other
+ * batch calls.
+ * (The environment variable GPMI_BATCH_PGRAD_MAX_N, 0 … 2 048 = what the kernels admit, read per call, overrides it for measurements.) */
+#define GPMI355_BATCH_PGRAD_MAX_N 1152
+int32_t gp_predict_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                              const void* const* mean_or_null, int32_t ny, const void* const* y, int32_t nxs, const gp_points* xs,
+                              const void* const* prior_mean_xs_or_null, int32_t what, void* const* mean_out_or_null, void* const* var_out_or_null,
+                              void* const* dmean_out_or_null, void* const* dvar_out_or_null, void* logpdf_out_or_null, int32_t* info_out);
+/* The same with one composite kernel (gp_ksum) per problem. */
+int32_t gp_predict_grad_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                                  const void* const* mean_or_null, int32_t ny, const void* const* y, int32_t nxs, const gp_points* xs,
+                                  const void* const* prior_mean_xs_or_null, int32_t what, void* const* mean_out_or_null, void* const* var_out_or_null,
+                                  void* const* dmean_out_or_null, void* const* dvar_out_or_null, void* logpdf_out_or_null, int32_t* info_out);
+
 /* The training half of the batch calls: value AND gradient of logpdf for the same nb problems in ONE call — what multi-start hyper-parameter
  * optimisation, gradient-based samplers over hyper-parameters, per-fold training and independent outputs sharing one x evaluate at every step (one
  * gp_logpdf_grad call per problem otherwise).  Per problem the semantics are those of gp_logpdf_grad / gp_logpdf_grad_sum:
