@@ -245,6 +245,14 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
  *                    N = 65 536) on its first forward solve; 0 = the recursion down to 64-column TRSM leaves.  A product with an explicit inverse
  *                    carries an error of order cond(L_bb)·ε where substitution is backward stable: a handle whose factor has max |L_ii| / min |L_ii|
  *                    above 1e5 (cond(K + Σy) >= 1e10) keeps the substitution leaves                   default 2048
+ *                    What is NOT behind that guard (tests/test_gpu_backward_error.py measures both against componentwise rounding bounds): every Cholesky / TRSM leaf
+ *                    multiplies the rows below a 16×16 diagonal block T by inv(T), so the factor satisfies |A − LLᵀ| <= γ_{n+1} |L||L|ᵀ + 2γ_16 |L_iJ Tᵀ||T⁻ᵀ||Tᵀ| and
+ *                    not the first term alone — 68 times the first term when the factor's diagonal falls by 1e5 inside ONE 64-column tile (64 points of a smooth kernel at
+ *                    σ² = 1e-10), 1.4 at N = 320, below it from N ≈ 1 000; and the vector solves multiply by inv of every 64×64 diagonal tile, which is backward stable in
+ *                    the forward direction only: the backward sweep (α, gp_posterior_solve) carries γ_64·cond(T) of such a tile — 29 times substitution's bound at
+ *                    128 points under the same conditions, 0.04 at 1 024.  α's residual |Cα − δ| reached 2.9 times Theorem 10.4's bound at 130 such points and stayed
+ *                    below 0.02 of it in every other measured case.
+ *                    (tests/test_illcond_cpu.py reproduces both excesses with a NumPy emulation of the two designs.)
  *   "ldpad"          row padding in elements (multiple of 16)                             default 32
  *   "dense_stage_mb" dense Σy (gp_noise kind 2 / 3): MiB per staging buffer of the streamed upload and of the gradient's download (two page-locked and two
  *                    device buffers of this size; 1..256; a piece is never shorter than 128 rows / columns of the matrix)   default 64
