@@ -98,6 +98,10 @@ PROTOTYPES = {
                                    C.POINTER(vp)]),
     "gp_logpdf_grad_batch_sum": (i32, [vp, i32, PS, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp), C.POINTER(vp),
                                        C.POINTER(vp)]),
+    "gp_logpdf_grad_batch_x": (i32, [vp, i32, PK, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(vp), C.POINTER(vp),
+                                     C.POINTER(vp), C.POINTER(vp)]),
+    "gp_logpdf_grad_batch_sum_x": (i32, [vp, i32, PS, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp), C.POINTER(vp),
+                                         C.POINTER(vp), C.POINTER(vp)]),
     "gp_posterior_update": (i32, [vp, PP, PN, vp, C.POINTER(vp), vp, vp]),
     "gp_posterior_factor_mul": (i32, [vp, vp, i32, vp]),
     "gp_posterior_solve": (i32, [vp, vp, i32, vp]),
@@ -161,6 +165,11 @@ def batch_max_n() -> int:
 def batch_grad_max_n() -> int:
     """GPMI355_BATCH_GRAD_MAX_N of include/gpmi355.h: the largest problem gp_logpdf_grad_batch hands to its gradient kernels."""
     return int(re.search(r"#define GPMI355_BATCH_GRAD_MAX_N (\d+)", HEADER.read_text()).group(1))
+
+
+def batch_gradx_max_n() -> int:
+    """GPMI355_BATCH_GRADX_MAX_N of include/gpmi355.h: the largest problem gp_logpdf_grad_batch_x hands to its kernels when dx is asked for."""
+    return int(re.search(r"#define GPMI355_BATCH_GRADX_MAX_N (\d+)", HEADER.read_text()).group(1))
 
 
 def batch_pgrad_max_n() -> int:

@@ -1129,10 +1129,27 @@ class _GradBatchCall:
     dy: list
     noise_kind: list
     keep: object
+    dx: Optional[list] = None    # wrt_x: per problem the buffer in the ABI layout of its inputs (_dx_buffer)
+    pts: object = None           # the gp_points array of the call (nx entries)
 
 
-def _grad_batch_marshal(g: _BatchGroup) -> _GradBatchCall:
-    """ctypes arguments of one group — needs no context.  The leading arguments are those of _batch_marshal."""
+def _grad_batch_marshal(g: _BatchGroup, wrt_x: bool = False) -> _GradBatchCall:
+    """ctypes arguments of one group — needs no context.  The leading arguments are those of _batch_marshal; with wrt_x the entry point is the one with
+    `_x` behind its name and the dx array behind the others (every problem its own buffer, also where all share one x)."""
+    call = _grad_batch_marshal_plain(g)
+    if not wrt_x:
+        return call
+    pts = call.args[3]
+    call.pts = pts
+    call.dx = [_dx_buffer(pts[0 if g.nx == 1 else b], g.dtype) for b in range(call.nb)]
+    dxarr = (C.c_void_p * call.nb)(*[a.ctypes.data for a in call.dx])
+    call.keep.keep.append(dxarr)
+    call.entry += "_x"
+    call.args = call.args + (dxarr,)
+    return call
+
+
+def _grad_batch_marshal_plain(g: _BatchGroup) -> _GradBatchCall:
     fit = _batch_marshal(g, False)
     m = fit.keep
     nb = fit.nb
@@ -1159,22 +1176,26 @@ def _grad_batch_marshal(g: _BatchGroup) -> _GradBatchCall:
     return _GradBatchCall("gp_logpdf_grad_batch", nb, g.nx, g.ny, args, fit.out, fit.info, dvar, dscale, None, None, dnoise, dy, kinds, m)
 
 
-def logpdf_and_grad_batch(fxs, ys, *, on_error: str = "raise"):
+def logpdf_and_grad_batch(fxs, ys, *, wrt_x: bool = False, on_error: str = "raise"):
     """Value and gradient of logpdf(fx_b, y_b) of many independent exact GPs in one library call per (ctx, dtype, single-kind / composite) group —
     what multi-start hyper-parameter optimisation, gradient-based samplers over hyper-parameters and per-fold training evaluate at every step.  fxs, ys
     as in logpdf_batch (the same x / y object in every entry is sent once).  Returns (array of logpdf, list of dicts in the caller's order); each dict
-    is that of logpdf_and_grad without "x": {"variance", "scale", "noise", "y", "mean"} for a single-kind kernel, {"kernel", "theta", "noise", "y",
-    "mean"} for a composite one.  on_error = "raise": the PosDefException of the first failing problem (.info, .index); "nan": NaN in its logpdf and in
-    every entry of its gradient."""
+    is that of logpdf_and_grad: {"variance", "scale", "noise", "y", "mean"} for a single-kind kernel, {"kernel", "theta", "noise", "y", "mean"} for a
+    composite one and, with wrt_x (gp_logpdf_grad_batch_x / _sum_x), "x": ∂/∂x in the shape and dtype of that problem's input array, as
+    logpdf_and_grad(wrt_x=True) returns it — what a deep-kernel model behind many small GPs back-propagates into its feature map; problems that share one x
+    object each get their own gradient w.r.t. it.  on_error = "raise": the PosDefException of the first failing problem (.info, .index); "nan": NaN in its
+    logpdf and in every entry of its gradient."""
     if on_error not in ("raise", "nan"):
         raise ValueError('on_error must be "raise" or "nan"')
+    if not isinstance(wrt_x, (bool, np.bool_)):
+        raise TypeError("wrt_x must be a bool")
     fxs = list(fxs)
     if not fxs:
         return np.empty(0), []
     grads = [None] * len(fxs)
     parts = []
     for g in _batch_groups(fxs, ys):
-        call = _grad_batch_marshal(g)
+        call = _grad_batch_marshal(g, bool(wrt_x))
         ctx = g.ctx or default_context()
         check(getattr(ctx.lib, call.entry)(ctx.handle, *call.args))
         parts.append((g.index, call.out, call.info, None))
@@ -1186,6 +1207,8 @@ def logpdf_and_grad_batch(fxs, ys, *, on_error: str = "raise"):
             else:
                 sc = call.dscale[j]
                 grads[i] = {"variance": float(call.dvar[j]), "scale": None if sc is None else (float(sc[0]) if sc.shape[0] == 1 else sc), **tail}
+            if wrt_x:
+                grads[i]["x"] = _dx_shaped(call.dx[j], call.pts[0 if g.nx == 1 else j], g.fxs[j].x)
     return _batch_merge(len(fxs), parts, False, on_error), grads
 
 

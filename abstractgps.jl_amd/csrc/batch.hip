@@ -1,8 +1,9 @@
 // batch.hip — many small exact GPs in one call: gp_logpdf_batch / gp_logpdf_batch_sum, gp_predict_batch / gp_predict_batch_sum, gp_logpdf_grad_batch /
 // gp_logpdf_grad_batch_sum, gp_predict_grad_batch / gp_predict_grad_batch_sum (include/gpmi355.h) and the kernels behind them: the fit (batch_logpdf_kernel,
 // below), the predictions at each problem's test points from the slices it leaves (batch_predict_kernel, further down), the gradient of logpdf from the same
-// slices (batch_inv_kernel, batch_grad_kernel, batch_gsum_kernel, behind it) and the gradients of the predictions w.r.t. the test inputs from the strips the
-// predict kernel leaves and the S of batch_inv_kernel (batch_pgrad_kernel, last).
+// slices (batch_inv_kernel, batch_grad_kernel, batch_gsum_kernel, behind it; with the input gradient of gp_logpdf_grad_batch_x / gp_logpdf_grad_batch_sum_x:
+// batch_gradx_kernel, batch_gxsum_kernel) and the gradients of the predictions w.r.t. the test inputs from the strips the predict kernel leaves and the S of
+// batch_inv_kernel (batch_pgrad_kernel, last).
 //
 // ONE workgroup owns ONE problem from its inputs to its scalar: it assembles the lower triangle of K + Σy into the problem's slice of a
 // workspace (δ = y − m riding along as row np, as in the single path), factors it by a blocked right-looking Cholesky (64-column blocks:
@@ -670,6 +671,131 @@ __global__ __launch_bounds__(128) void batch_gsum_kernel(const double* __restric
     res[G.g_off + tid] = s;
 }
 
+// ---- the gradient of logpdf w.r.t. the inputs: batch_gradx_kernel, batch_gxsum_kernel ---------------------------------------------------------------------
+// Launched behind batch_grad_kernel, for the problems of a gradient wave whose dx is wanted, on the S strips and the α the wave already holds:
+//   ∂logpdf/∂x_ip = Σ_{j ≠ i} (α_i α_j − C⁻¹_ij) ∂k/∂t_p (t = x_i − x_j)    (both orders of the symmetric pair folded in; the diagonal contributes nothing).
+// What the two kernels know of a problem beyond its BatchProb and GradProb; same position in its table as the descriptor.  Offsets count doubles: xpart_off
+// (nt² tables of [d][64] row sums, tile (ti, tj) at ti · nt + tj) into the workspace, dx_off (the gradient, dimension-major [d][n]) into the result buffer.
+struct GradXProb {
+    long xpart_off, dx_off;
+};
+static_assert(sizeof(GradXProb) % 8 == 0, "the tables are packed behind double data");
+
+// The 64×64 tile (ti, tj) of the FULL square of one problem (idx = ti · nt + tj), as kgradx_kernel of the single path walks it:
+//   1. C⁻¹_tile = Σ_{k ≥ 64 max(ti, tj)} S[i, k] S[j, k] by mfma_tile_k64 straight from the strip, one 32×32 wave tile per wave (row i of the strip is valid from
+//      column 64·⌊i / 64⌋ on, S is upper triangular: nothing left of max(ti, tj) contributes); the weights α_i α_j − C⁻¹_ij into LDS, zero where i >= n, j >= n or i = j;
+//   2. the contraction: lane = column j with its inputs in registers, the rows w, w + 4, … of the tile with the row's inputs by scalar loads; every (row, p) is
+//      summed over the 64 columns by a butterfly.  Single kind: the sums run over W κ'(r²) u_p with u = s ∘ t, ∂k/∂t_p = 2 σ² s_p κ' u_p applied at the end
+//      (kappa_and_dr2: Matern12 at distance 0 is 0); composite: ksum_gradx with its per-thread LDS slots.
+//   3. lane 0 of the row's wave stores the d sums of the row into this tile's table: one writer per entry, rows beyond n store 0.
+// A failed problem's tiles return at once (batch_gxsum_kernel writes its NaN): neither strip nor α is read.
+template <bool SUM>
+__global__ __launch_bounds__(GNT) void batch_gradx_kernel(const double* __restrict__ in, double* __restrict__ ws, const double* __restrict__ res, int nw,
+                                                         const GradProb* __restrict__ gps, const GradXProb* __restrict__ gxs,
+                                                         const GradTile* __restrict__ tiles) {
+    __shared__ double Wt[BT][BT];
+    __shared__ double kf[SUM ? KSum::MAXFT : 1][GNT];
+    const GradTile& T = tiles[blockIdx.x];
+    const BatchProb& P = reinterpret_cast<const BatchProb*>(in)[T.prob];
+    if (res[nw + P.slot] != 0.0) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = P.n, np = P.np, d = P.d;
+    const long ld = P.ld;
+    const int it0 = T.ti * BT, jt0 = T.tj * BT;
+    const double* __restrict__ S = ws + gps[T.prob].s_off;
+    const double* __restrict__ alpha = res + P.alpha_off;
+    const double* __restrict__ x = in + P.x_off;
+    double* __restrict__ part = ws + gxs[T.prob].xpart_off + (long)T.idx * (BT * d);
+
+    // ---- 1. the weights of the tile
+    {
+        const int r = lane & 15;
+        const int i0 = it0 + 32 * (w >> 1), c0 = jt0 + 32 * (w & 1);
+        d4_t c4[2][2];
+        acc_zero(c4);
+        for (int k0 = T.ti > T.tj ? it0 : jt0; k0 < np; k0 += BT) mfma_tile_k64<false>(c4, S, i0, S, c0, k0, ld, lane);
+#pragma unroll
+        for (int hi = 0; hi < 2; ++hi)
+#pragma unroll
+            for (int hj = 0; hj < 2; ++hj) {
+                const int gj = c0 + 16 * hj + r;
+                const double aj = gj < n ? alpha[gj] : 0.0;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int gi = i0 + 16 * hi + Tr<double>::crow(lane, q);
+                    double wv = 0.0;
+                    if (gi < n && gj < n && gi != gj) wv = alpha[gi] * aj - c4[hi][hj][q];
+                    Wt[gi - it0][gj - jt0] = wv;
+                }
+            }
+    }
+    __syncthreads();
+
+    // ---- 2. the contraction, 3. the row sums
+    double xj[BATCH_MAXD];
+    batch_load_point(x, n, d, jt0 + lane, xj);
+#pragma unroll 1
+    for (int rr = 0; rr < BT / 4; ++rr) {
+        const int li = w + 4 * rr, gi = it0 + li;  // wave-uniform
+        double g[BATCH_MAXD];
+#pragma unroll
+        for (int p = 0; p < BATCH_MAXD; ++p) g[p] = 0.0;
+        if (gi < n) {
+            const double wgt = Wt[li][lane];
+            double t[BATCH_MAXD];
+            batch_diff(x, n, d, gi, xj, t);
+            if (SUM) {
+                ksum_gradx<double, BATCH_MAXD>(*reinterpret_cast<const KSum*>(in + P.ks_off), t, d, wgt, g, kf, tid);
+            } else {
+                double d2 = 0.0;
+#pragma unroll
+                for (int p = 0; p < BATCH_MAXD; ++p) {
+                    t[p] *= P.nscale == 0 ? 1.0 : P.scale[P.nscale == 1 ? 0 : p];  // u = s ∘ t
+                    d2 = fma(t[p], t[p], d2);
+                }
+                double kap, dk;
+                kappa_and_dr2<double>(P.kind, d2, kap, dk);
+                const double wk = wgt * dk;
+#pragma unroll
+                for (int p = 0; p < BATCH_MAXD; ++p) g[p] = wk * t[p];
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < BATCH_MAXD; ++p) {
+            if (p >= d) break;  // d is the problem's: the same in every lane
+            double v = g[p];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+            if (lane == 0) {
+                const double sp = SUM ? 1.0 : 2.0 * P.variance * (P.nscale == 0 ? 1.0 : P.scale[P.nscale == 1 ? 0 : p]);
+                part[p * BT + li] = sp * v;
+            }
+        }
+    }
+}
+
+// One 64-row block of the input gradient of one problem: the nt tables of tile row ti added in tj order (thread = row, the dimensions one after the other),
+// written dimension-major [d][n] into the result buffer.  A failed problem gets NaN; nothing of its workspace is read.
+__global__ __launch_bounds__(BT) void batch_gxsum_kernel(const double* __restrict__ in, const double* __restrict__ ws, double* __restrict__ res, int nw,
+                                                        const GradXProb* __restrict__ gxs, const GradTile* __restrict__ tiles) {
+    const GradTile& T = tiles[blockIdx.x];
+    const BatchProb& P = reinterpret_cast<const BatchProb*>(in)[T.prob];
+    const GradXProb& X = gxs[T.prob];
+    const int n = P.n, d = P.d, nt = P.np / BT, gi = T.ti * BT + (int)threadIdx.x;
+    if (gi >= n) return;
+    double* __restrict__ out = res + X.dx_off;
+    if (res[nw + P.slot] != 0.0) {
+        for (int p = 0; p < d; ++p) out[(long)p * n + gi] = __builtin_nan("");
+        return;
+    }
+    const double* __restrict__ part = ws + X.xpart_off + (long)T.ti * nt * (BT * d) + threadIdx.x;
+    for (int p = 0; p < d; ++p) {
+        double s = 0.0;
+        for (int tj = 0; tj < nt; ++tj) s += part[(long)tj * (BT * d) + p * BT];
+        out[(long)p * n + gi] = s;
+    }
+}
+
 // ---- the gradients of the predictions w.r.t. the test inputs: batch_pgrad_kernel --------------------------------------------------------------------
 // What batch_pgrad_kernel knows of a tile beyond its BatchTile; same position in its table as the tile in the tile table.  Offsets count doubles: s_off
 // (the S strip of the problem, as GradProb's) into the workspace, dmean_off / dvar_off into the result buffer (the problem's gradients, dimension-major
@@ -993,6 +1119,11 @@ int32_t launch_pgrad(const WaveMem& m, bool ks, int nw, const BatchTile* tiles, 
 }
 int32_t launch_grad(const WaveMem& m, bool ks, int nw, const GradProb* gps, const GradTile* tiles, size_t ntiles) {
     hipLaunchKernelGGL(ks ? batch_grad_kernel<true> : batch_grad_kernel<false>, dim3((unsigned)ntiles), dim3(GNT), 0, m.c->sm, m.in, m.ws, m.res, nw, gps, tiles);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int32_t launch_gradx(const WaveMem& m, bool ks, int nw, const GradProb* gps, const GradXProb* gxs, const GradTile* tiles, size_t ntiles) {
+    hipLaunchKernelGGL(ks ? batch_gradx_kernel<true> : batch_gradx_kernel<false>, dim3((unsigned)ntiles), dim3(GNT), 0, m.c->sm, m.in, m.ws, (const double*)m.res, nw, gps, gxs, tiles);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1395,17 +1526,24 @@ struct GradArgs : BatchArgs {
     void* const* dnoise;
     void* const* dy;
     int arg0;                 // position of the first gradient argument (the reasons of the checks name the argument)
+    void* const* dx = nullptr;  // gp_logpdf_grad_batch_x / _sum_x: nb pointers to n_b × d_b entries in the container layout of x_b, or NULL
     void* dnb(int b) const { return dnoise ? dnoise[b] : nullptr; }
     void* dyb(int b) const { return dy ? dy[b] : nullptr; }
+    void* dxb(int b) const { return dx ? dx[b] : nullptr; }
 };
 
 // the kernel parameters of problem b: variance + scales, or the θ entries of its composite kernel
 int grad_nkp(const GradArgs& a, const std::vector<KSum>& packed, int b) { return a.ks ? packed[b].nth : 1 + a.k[b].nscale; }
 long grad_ntiles(long n) { return batch_np(n) / BT * (batch_np(n) / BT + 1) / 2; }
+// the per-tile row sums of the input gradient: one [d][64] table per tile of the full square (an even count: what follows stays 16-byte aligned); 0 without dx
+long gradx_part(const GradArgs& a, int b) {
+    const long nt = batch_np(a.xb(b).n) / BT;
+    return a.dxb(b) ? nt * nt * BT * a.xb(b).d : 0;
+}
 // workspace of a problem in a gradient wave: its slice, the S strip beside it and the per-tile sums
 long grad_ws(const GradArgs& a, const std::vector<KSum>& packed, int b) {
     const long n = a.xb(b).n, np = batch_np(n);
-    return batch_slice(n) + np * batch_ld(np) + ((grad_ntiles(n) * (1 + grad_nkp(a, packed, b)) + 1) & ~1L);
+    return batch_slice(n) + np * batch_ld(np) + ((grad_ntiles(n) * (1 + grad_nkp(a, packed, b)) + 1) & ~1L) + gradx_part(a, b);
 }
 
 // NaN in every gradient output of problem b (nkp kernel parameters)
@@ -1418,6 +1556,7 @@ void grad_fill_nan(const GradArgs& a, int b, int nkp) {
     const int nk = a.noise[b].kind;
     fill_nan(a.dnb(b), a.dtype, nk == 0 ? 1 : (nk == 1 ? n : n * n));
     fill_nan(a.dyb(b), a.dtype, n);
+    fill_nan(a.dxb(b), a.dtype, n * a.xb(b).d);
 }
 
 // one wave: the fit launch of the problems idx[0..nw) with α for every one of them, then S = L⁻ᵀ, the tile sums and their totals.  Caller holds the ctx lock.
@@ -1442,9 +1581,31 @@ int32_t run_grad_wave(gp_ctx* c, const GradArgs& a, const std::vector<KSum>& pac
         for (int ti = 0; ti < nt; ++ti)
             for (int tj = 0; tj <= ti; ++tj) gtiles.push_back(GradTile{s, ti, tj, ti * (ti + 1) / 2 + tj});
     }
+    // the problems whose dx is wanted: their tables of row sums behind everything else in the workspace, the gradient [d][n] behind the other results, the
+    // tiles of the full square and the 64-row blocks batch_gxsum_kernel adds them up in.  Without any, the wave is laid out and launched as it always was.
+    std::vector<GradXProb> gx;
+    std::vector<GradTile> xtiles, xrows;
+    int nwx = 0;
+    for (int s = 0; s < nw; ++s) {
+        const int t = L.order[s], b = idx[t];
+        if (!a.dxb(b)) continue;
+        if (gx.empty()) gx.assign((size_t)nw, GradXProb{-1, -1});
+        const BatchProb& p = L.pr[t];
+        const int nt = p.np / BT;
+        gx[s].xpart_off = take(L.ws, gradx_part(a, b));
+        gx[s].dx_off = take(L.roff, (long)p.n * p.d);
+        for (int ti = 0; ti < nt; ++ti) {
+            for (int tj = 0; tj < nt; ++tj) xtiles.push_back(GradTile{s, ti, tj, ti * nt + tj});
+            xrows.push_back(GradTile{s, ti, 0, 0});
+        }
+        ++nwx;
+    }
     const long gp_off = take(L.off, (long)(gp.size() * sizeof(GradProb) / 8));
     const long it_off = take(L.off, (long)(itiles.size() * sizeof(GradTile) / 8));
     const long gt_off = take(L.off, (long)(gtiles.size() * sizeof(GradTile) / 8));
+    const long gx_off = take(L.off, (long)(gx.size() * sizeof(GradXProb) / 8));
+    const long xt_off = take(L.off, (long)(xtiles.size() * sizeof(GradTile) / 8));
+    const long xr_off = take(L.off, (long)(xrows.size() * sizeof(GradTile) / 8));
 
     WaveMem m(c);
     RC(m.alloc(L.off, L.ws, L.roff));
@@ -1452,6 +1613,11 @@ int32_t run_grad_wave(gp_ctx* c, const GradArgs& a, const std::vector<KSum>& pac
     std::memcpy(m.hin + gp_off, gp.data(), gp.size() * sizeof(GradProb));
     std::memcpy(m.hin + it_off, itiles.data(), itiles.size() * sizeof(GradTile));
     std::memcpy(m.hin + gt_off, gtiles.data(), gtiles.size() * sizeof(GradTile));
+    if (nwx) {
+        std::memcpy(m.hin + gx_off, gx.data(), gx.size() * sizeof(GradXProb));
+        std::memcpy(m.hin + xt_off, xtiles.data(), xtiles.size() * sizeof(GradTile));
+        std::memcpy(m.hin + xr_off, xrows.data(), xrows.size() * sizeof(GradTile));
+    }
     RC(run_drained(c, [&]() -> int32_t {
         const GradProb* gps = reinterpret_cast<const GradProb*>(m.in + gp_off);
         const GradTile* its = reinterpret_cast<const GradTile*>(m.in + it_off);
@@ -1463,10 +1629,18 @@ int32_t run_grad_wave(gp_ctx* c, const GradArgs& a, const std::vector<KSum>& pac
         RC(launch_grad(m, a.ks != nullptr, nw, gps, gts, gtiles.size()));
         hipLaunchKernelGGL(batch_gsum_kernel, dim3((unsigned)nw), dim3(128), 0, c->sm, m.in, (const double*)m.ws, m.res, nw, gps);
         HIPCHK(hipGetLastError());
+        if (nwx) {
+            const GradXProb* gxs = reinterpret_cast<const GradXProb*>(m.in + gx_off);
+            RC(launch_gradx(m, a.ks != nullptr, nw, gps, gxs, reinterpret_cast<const GradTile*>(m.in + xt_off), xtiles.size()));
+            hipLaunchKernelGGL(batch_gxsum_kernel, dim3((unsigned)xrows.size()), dim3(BT), 0, c->sm, m.in, (const double*)m.ws, m.res, nw, gxs,
+                               reinterpret_cast<const GradTile*>(m.in + xr_off));
+            HIPCHK(hipGetLastError());
+        }
         return m.download_and_sync();
     }));
     const double* hout = m.hout;
     c->batch_grad_problems += nw;
+    c->batch_gradx_problems += nwx;
     for (int t = 0; t < nw; ++t) {
         const int b = idx[t];
         const GradProb& g = gp[L.pos[t]];
@@ -1484,6 +1658,7 @@ int32_t run_grad_wave(gp_ctx* c, const GradArgs& a, const std::vector<KSum>& pac
             const double* al = hout + L.pr[t].alpha_off;
             for (long j = 0; j < n; ++j) dy[j] = -al[j];
         }
+        if (void* dx = a.dxb(b)) unpack_grad(a.xb(b), hout + gx[L.pos[t]].dx_off, (double*)dx);
     }
     return 0;
 }
@@ -1505,19 +1680,25 @@ int32_t grad_batch_impl(gp_ctx* c, GradArgs& a) {
         if (a.dtheta && !a.dtheta[b]) return set_arg_err(a.arg0, "a dtheta_out pointer is NULL");
         if (a.dnoise && !a.dnoise[b]) return set_arg_err(a_dn, "a dnoise_out pointer is NULL");
         if (a.dy && !a.dy[b]) return set_arg_err(a_dy, "a dy_out pointer is NULL");
+        if (a.dx && !a.dx[b]) return set_arg_err(a_dy + 1, "a dx_out pointer is NULL");
     }
+    // which path serves a problem depends on that problem alone and on whether the call asks for dx: the input-gradient kernels have a limit of their own
     std::vector<int> mine, routed;
-    split_by_path(a, env_capped(getenv("GPMI_BATCH_GRAD_MAX_N"), GPMI355_BATCH_GRAD_MAX_N), mine, routed);
+    split_by_path(a, a.dx ? env_capped(getenv("GPMI_BATCH_GRADX_MAX_N"), GPMI355_BATCH_GRADX_MAX_N)
+                          : env_capped(getenv("GPMI_BATCH_GRAD_MAX_N"), GPMI355_BATCH_GRAD_MAX_N), mine, routed);
     RC(for_each_wave(c, mine, [&](int b) { return WaveCost{sizeof(double) * (size_t)grad_ws(a, packed, b), 0}; },  // slices, strips and tile sums count
                      [&](const int* idx, int nw) { return run_grad_wave(c, a, packed, idx, nw); }));
-    // everything else: gp_logpdf_grad / gp_logpdf_grad_sum, one problem at a time, after the lock is released (as batch_impl does)
+    // everything else: gp_logpdf_grad / gp_logpdf_grad_sum (gp_logpdf_grad_sum_x where dx is wanted), one problem at a time, after the lock is released (as
+    // batch_impl does)
     gd.lk.unlock();
     for (int b : routed) {
         const gp_points& x = a.xb(b);
         void* lp = logpdf_slot(a, b);
-        const int32_t rc = a.ks ? gp_logpdf_grad_sum(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), lp, a.dtheta ? a.dtheta[b] : nullptr, a.dnb(b), a.dyb(b))
-                                : gp_logpdf_grad(c, &a.k[b], &x, &a.noise[b], a.mb(b), a.yb(b), lp, a.dvar ? &a.dvar[b] : nullptr,
-                                                 a.dscale ? a.dscale[b] : nullptr, a.dnb(b), a.dyb(b), nullptr);
+        double* dth = a.dtheta ? a.dtheta[b] : nullptr;
+        const int32_t rc = !a.ks       ? gp_logpdf_grad(c, &a.k[b], &x, &a.noise[b], a.mb(b), a.yb(b), lp, a.dvar ? &a.dvar[b] : nullptr,
+                                                        a.dscale ? a.dscale[b] : nullptr, a.dnb(b), a.dyb(b), a.dxb(b))
+                           : a.dxb(b) ? gp_logpdf_grad_sum_x(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), lp, dth, a.dnb(b), a.dyb(b), a.dxb(b))
+                                      : gp_logpdf_grad_sum(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), lp, dth, a.dnb(b), a.dyb(b));
         if (rc < 0) return rc;
         a.info_out[b] = rc;
         if (rc > 0) {
@@ -1526,6 +1707,15 @@ int32_t grad_batch_impl(gp_ctx* c, GradArgs& a) {
         }
     }
     return 0;
+}
+
+// gp_logpdf_grad_batch_x / _sum_x: the body of gp_logpdf_grad_batch / _sum with a.dx set.  The entry points' own guard: the ctx is pinned for the whole call
+// and the lock handed on, as it is to the single-path calls above (grad_batch_impl validates the ctx again and takes the lock itself).
+int32_t gradx_batch_impl(gp_ctx* c, GradArgs& a) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    gd.lk.unlock();
+    return grad_batch_impl(c, a);
 }
 
 }  // namespace
@@ -1601,5 +1791,23 @@ int32_t gp_logpdf_grad_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int3
     GradArgs a{{nb, nullptr, k, nx, x, noise, mean_or_null, ny, y, logpdf_out, info_out, nullptr, 0}, nullptr, nullptr, dtheta_out_or_null, dnoise_out_or_null, dy_out_or_null, 12};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return grad_batch_impl(ctx, a);
+}
+
+int32_t gp_logpdf_grad_batch_x(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                               const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
+                               double* dvariance_out_or_null, double* const* dscale_out_or_null, void* const* dnoise_out_or_null,
+                               void* const* dy_out_or_null, void* const* dx_out_or_null) {
+    GradArgs a{{nb, k, nullptr, nx, x, noise, mean_or_null, ny, y, logpdf_out, info_out, nullptr, 0}, dvariance_out_or_null, dscale_out_or_null, nullptr, dnoise_out_or_null, dy_out_or_null, 12, dx_out_or_null};
+    if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
+    return gradx_batch_impl(ctx, a);
+}
+
+int32_t gp_logpdf_grad_batch_sum_x(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                                   const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
+                                   double* const* dtheta_out_or_null, void* const* dnoise_out_or_null, void* const* dy_out_or_null,
+                                   void* const* dx_out_or_null) {
+    GradArgs a{{nb, nullptr, k, nx, x, noise, mean_or_null, ny, y, logpdf_out, info_out, nullptr, 0}, nullptr, nullptr, dtheta_out_or_null, dnoise_out_or_null, dy_out_or_null, 12, dx_out_or_null};
+    if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
+    return gradx_batch_impl(ctx, a);
 }
 }

@@ -631,7 +631,9 @@ end
 # group.  Returns (logpdfs, gradients in the caller's order); a gradient is the named tuple of logpdf_and_grad without `x`: (variance, scale, noise,
 # y, mean) for a single-kind kernel, (theta, kernel, noise, y, mean) for a composite one.  on_error as in logpdf_batch; :nan leaves NaN in the logpdf
 # and in every gradient entry of a failing problem.  Every problem must be one the ABI has a layout for (as logpdf_and_grad demands).
-function logpdf_and_grad_batch(fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys; on_error::Symbol=:raise)
+# wrt_x = true (gp_logpdf_grad_batch_x / gp_logpdf_grad_batch_sum_x): every gradient also carries `x`, ∂/∂x in the container layout of that problem's inputs
+# as logpdf_and_grad returns it — what a deep-kernel model behind many small GPs back-propagates; problems sharing one x each get their own gradient.
+function logpdf_and_grad_batch(fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys; wrt_x::Bool=false, on_error::Symbol=:raise)
     on_error in (:raise, :nan) || throw(ArgumentError("on_error must be :raise or :nan"))
     nb = length(fxs)
     yv = (ys isa AbstractVector{<:Real}) ? fill(ys, nb) : collect(ys)
@@ -662,15 +664,24 @@ function logpdf_and_grad_batch(fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys; on_
         dybufs = [Vector{Tg}(undef, length(fxs[b])) for b in idx]
         dnptrs = Ptr{Cvoid}[pointer(v) for v in dnbufs]
         dyptrs = Ptr{Cvoid}[pointer(v) for v in dybufs]
-        GC.@preserve args ybufs cxs cns yptrs mptrs out inf dnbufs dybufs dnptrs dyptrs begin
+        dxbufs = wrt_x ? [similar(args[b].xbuf) for b in idx] : []   # same container layout as the inputs (Vector / D×N / N×D), one per problem
+        dxptrs = Ptr{Cvoid}[pointer(v) for v in dxbufs]
+        GC.@preserve args ybufs cxs cns yptrs mptrs out inf dnbufs dybufs dnptrs dyptrs dxbufs dxptrs begin
             if composite
                 ks = [args[b].ks for b in idx]
                 dθs = [zeros(Float64, length(sum_theta(args[b].P, args[b].terms))) for b in idx]
                 dθptrs = Ptr{Float64}[pointer(v) for v in dθs]
-                GC.@preserve ks dθs dθptrs check(ccall((:gp_logpdf_grad_batch_sum, libgpmi355), Int32,
-                    (Ptr{Cvoid}, Int32, Ptr{CKSum}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32},
-                     Ptr{Ptr{Float64}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}),
-                    ctx.handle, g, ks, nx, cxs, cns, mptrs, ny, yptrs, out, inf, dθptrs, dnptrs, dyptrs))
+                if wrt_x
+                    GC.@preserve ks dθs dθptrs check(ccall((:gp_logpdf_grad_batch_sum_x, libgpmi355), Int32,
+                        (Ptr{Cvoid}, Int32, Ptr{CKSum}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32},
+                         Ptr{Ptr{Float64}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}),
+                        ctx.handle, g, ks, nx, cxs, cns, mptrs, ny, yptrs, out, inf, dθptrs, dnptrs, dyptrs, dxptrs))
+                else
+                    GC.@preserve ks dθs dθptrs check(ccall((:gp_logpdf_grad_batch_sum, libgpmi355), Int32,
+                        (Ptr{Cvoid}, Int32, Ptr{CKSum}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32},
+                         Ptr{Ptr{Float64}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}),
+                        ctx.handle, g, ks, nx, cxs, cns, mptrs, ny, yptrs, out, inf, dθptrs, dnptrs, dyptrs))
+                end
                 for (j, b) in enumerate(idx)
                     grads[b] = (theta=dθs[j], kernel=sum_chain(args[b].P, args[b].terms, dθs[j]), noise=cns[j].kind == 0 ? dnbufs[j][1] : dnbufs[j],
                         y=dybufs[j], mean=-dybufs[j])
@@ -680,12 +691,24 @@ function logpdf_and_grad_batch(fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys; on_
                 dvars = zeros(Float64, g)
                 dss = [zeros(Float64, length(args[b].scales)) for b in idx]
                 dsptrs = Ptr{Float64}[isempty(v) ? Ptr{Float64}(C_NULL) : pointer(v) for v in dss]  # NULL where the kernel has no transform
-                GC.@preserve cks dvars dss dsptrs check(ccall((:gp_logpdf_grad_batch, libgpmi355), Int32,
-                    (Ptr{Cvoid}, Int32, Ptr{CKernel}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32},
-                     Ptr{Float64}, Ptr{Ptr{Float64}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}),
-                    ctx.handle, g, cks, nx, cxs, cns, mptrs, ny, yptrs, out, inf, dvars, dsptrs, dnptrs, dyptrs))
+                if wrt_x
+                    GC.@preserve cks dvars dss dsptrs check(ccall((:gp_logpdf_grad_batch_x, libgpmi355), Int32,
+                        (Ptr{Cvoid}, Int32, Ptr{CKernel}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32},
+                         Ptr{Float64}, Ptr{Ptr{Float64}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}),
+                        ctx.handle, g, cks, nx, cxs, cns, mptrs, ny, yptrs, out, inf, dvars, dsptrs, dnptrs, dyptrs, dxptrs))
+                else
+                    GC.@preserve cks dvars dss dsptrs check(ccall((:gp_logpdf_grad_batch, libgpmi355), Int32,
+                        (Ptr{Cvoid}, Int32, Ptr{CKernel}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32},
+                         Ptr{Float64}, Ptr{Ptr{Float64}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}),
+                        ctx.handle, g, cks, nx, cxs, cns, mptrs, ny, yptrs, out, inf, dvars, dsptrs, dnptrs, dyptrs))
+                end
                 for (j, b) in enumerate(idx)
                     grads[b] = (variance=dvars[j], scale=dss[j], noise=cns[j].kind == 0 ? dnbufs[j][1] : dnbufs[j], y=dybufs[j], mean=-dybufs[j])
+                end
+            end
+            if wrt_x
+                for (j, b) in enumerate(idx)
+                    grads[b] = merge(grads[b], (x=dxbufs[j],))
                 end
             end
         end

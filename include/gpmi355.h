@@ -294,7 +294,8 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
  *                    (tests/test_gpu_poisoned_blocks.py); forwarded to the rank contexts of a multi-device ctx; one not-taken branch per allocation when 0.   default 0
  *   "pool_cached_mb", "pool_blocks"   read-only (gp_ctx_get_param): MiB and number of blocks in the cache now
  *   "batch_grad_kernel_problems"      read-only (gp_ctx_get_param): the problems the gradient kernels of gp_logpdf_grad_batch / _sum have served on this ctx
- *                    since it was created (the problems routed to the single path do not count): which path ran, for tests and measurements */
+ *                    since it was created (the problems routed to the single path do not count): which path ran, for tests and measurements
+ *   "batch_gradx_kernel_problems"     read-only: the same for the input-gradient kernels of gp_logpdf_grad_batch_x / _sum_x (problems whose dx they computed) */
 /* The defaults above, machine-readable (single-device parameters; gp_ctx_get_param reads the same names): the test-suite asserts before
  * every GPU test that the shared default context still has exactly these values, so that no test can leave a non-production setting
  * behind for the tests that follow it (tests/conftest.py). */
@@ -540,7 +541,7 @@ int32_t gp_predict_grad_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int
  *     dnoise_out_or_null      nb pointers, call dtype: 1 entry (noise kind 0) ½(αᵀα − tr C⁻¹), n_b entries (kind 1) ½(α_i² − C⁻¹_ii), n_b × n_b entries
  *                             (kind 2 / 3, as gp_logpdf_grad; such a problem runs on the single path)
  *     dy_out_or_null          nb pointers, call dtype, n_b entries: ∂/∂y = −α_b
- *   There is no ∂/∂x here: gp_logpdf_grad (dx_out) and gp_logpdf_grad_sum_x have it, one problem per call.
+ *   ∂/∂x: gp_logpdf_grad_batch_x / gp_logpdf_grad_batch_sum_x below are the same calls with one more array, dx_out_or_null, behind dy_out_or_null.
  * Failure is data, as in the other batch calls: info_out[b] is the order of the first leading minor that is not positive, that problem's logpdf and every
  * one of its gradient outputs are NaN, the other problems are not affected.  The return value reports argument errors only (−i, reason in
  * gp_last_error(); nb = 0 returns 0 and touches nothing).
@@ -568,6 +569,48 @@ int32_t gp_logpdf_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_
 int32_t gp_logpdf_grad_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx, const gp_points* x, const gp_noise* noise,
                                  const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
                                  double* const* dtheta_out_or_null, void* const* dnoise_out_or_null, void* const* dy_out_or_null);
+
+/* gp_logpdf_grad_batch / gp_logpdf_grad_batch_sum with the gradient w.r.t. the inputs — what a deep-kernel model back-propagates into its feature map
+ * (examples/2-deep-kernel-learning/script.jl) when one GP per output, task, fold or start sits behind it, and what a caller who optimises input or latent
+ * locations needs; one gp_logpdf_grad (dx_out) / gp_logpdf_grad_sum_x call per problem otherwise.  Per problem the semantics are theirs:
+ *     ∂logpdf/∂x_ip = Σ_{j ≠ i} (α_i α_j − C⁻¹_ij) ∂k/∂t_p (t = x_i − x_j)
+ *   — both orders of the symmetric pair folded in, the prior mean taken as constant in x, noise independent of x; the diagonal contributes nothing, Matern12
+ *   at distance 0 is taken as 0 (for coincident distinct points too), a White factor contributes 0.
+ *   dx_out_or_null: NULL, or nb pointers; entry b receives n_b × d_b values in the container layout of x_b (as dx_out of gp_logpdf_grad), in the call's
+ *   dtype.  With the array NULL the call does exactly what the entry point without _x does (kernel-served problems: the same bits in every output).  An
+ *   array that is given with a NULL entry is an argument error at that argument's position.  With a shared x (nx = 1) every problem still gets its own
+ *   n × d gradient w.r.t. the shared inputs; summing them is the caller's business.  Failure is data: info_out[b] > 0 means NaN in every entry of dx_out[b]
+ *   as in that problem's other outputs, the neighbours are not affected.
+ * With dx, fp64 problems with noise kind 0 / 1, D <= 16 and n_b <= GPMI355_BATCH_GRADX_MAX_N run on the kernels of gp_logpdf_grad_batch and, behind them on
+ * the S strips and α they leave, two more (csrc/batch.hip): batch_gradx_kernel — one workgroup per 64×64 tile of the FULL square of a problem: C⁻¹_tile =
+ * S_i S_jᵀ by fp64 MFMA over k >= 64·max(ti, tj), the weights α_i α_j − C⁻¹_ij (zero on the diagonal and in the padding) contracted with ∂k/∂t re-evaluated
+ * from the packed inputs, lane = column, every (row, p) summed over the tile's 64 columns by a butterfly and stored in the tile's own table, one writer per
+ * entry — and batch_gxsum_kernel — one workgroup per 64-row block, which adds the block's tables in column-tile order.  No floating-point atomics, no waits
+ * between workgroups, every sum in an order the problem's size alone fixes: a problem's dx is the same bits alone, at any position of any batch, and on
+ * repetition; its other outputs are the bits of the call without dx (the same kernels, launched the same way).  The tables (n_b²/64 × d_b doubles) count
+ * towards the workspace budget of a wave.  Every other problem is answered inside the same call by gp_logpdf_grad (dx_out) / gp_logpdf_grad_sum_x; which
+ * path serves a problem depends on that problem alone and on whether dx is asked for.  The read-only ctx parameter "batch_gradx_kernel_problems" counts the
+ * problems the two kernels served.
+ * GPMI355_BATCH_GRADX_MAX_N: chosen by the rule that fixed the other three — the largest multiple of 128 of the measured sweep (tools/batch_gradx_profile.py,
+ * profiles/r24/batch_gradx_profile.json: n = 64 … 2 048 × nb = 1, 8, 64, 512, SE, D = 3, scalar noise, all outputs) at which ONE gp_logpdf_grad_batch_x call
+ * beat the loop of gp_logpdf_grad calls with dx_out in every cell with nb >= 8.  The nb = 8 cells decide it: 1 152 points 11.20 ms (11.19 – 11.25) against
+ * 13.03 ms (12.86 – 13.04), 1 280 points 14.57 ms (14.56 – 14.57) against 14.22 ms (14.19 – 14.49), 1 536 points 22.8 against 16.9 ms.  The limit lies above
+ * GPMI355_BATCH_GRAD_MAX_N because the opponent pays more for dx than the batch call does: the loop's 1 024-point call costs 1.38 ms with dx (1.22 ms
+ * without, r20), the batch call 7 % more than without dx at nb = 8.  At nb = 64 and 512 the batch call wins every size of the sweep (2 048 points: 142.6
+ * against 160.8 ms, 854 against 1 263 ms); a single problem loses from 256 points on (0.71 against 0.57 ms), as in the other batch calls.  The batch call
+ * with dx against the batch call without it, same cells: 1.06 – 1.11 at nb = 8 from 256 points on (1.34 at 64 points), 1.18 – 1.35 at nb = 64, 1.26 – 1.57
+ * at nb = 512 (the full square of a problem is twice the tiles of batch_grad_kernel's triangle, each with its own S product).
+ * (The environment variable GPMI_BATCH_GRADX_MAX_N, 0 … 2 048 = what the kernels admit, read per call, overrides it for measurements.) */
+#define GPMI355_BATCH_GRADX_MAX_N 1152
+int32_t gp_logpdf_grad_batch_x(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                               const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
+                               double* dvariance_out_or_null, double* const* dscale_out_or_null, void* const* dnoise_out_or_null,
+                               void* const* dy_out_or_null, void* const* dx_out_or_null);
+/* The same with one composite kernel (gp_ksum) per problem. */
+int32_t gp_logpdf_grad_batch_sum_x(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                                   const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
+                                   double* const* dtheta_out_or_null, void* const* dnoise_out_or_null, void* const* dy_out_or_null,
+                                   void* const* dx_out_or_null);
 
 /* Sequential conditioning, posterior(fx::FiniteGP{<:PosteriorGP}, y) (src/exact_gpr_posterior.jl:46-56): the resident
  * factor of `old` is extended by the bordered-Cholesky step update_chol (src/util/common_covmat_ops.jl:38-42):
