@@ -94,6 +94,10 @@ PROTOTYPES = {
                                     C.POINTER(vp), C.POINTER(vp), vp, C.POINTER(i32)]),
     "gp_predict_grad_batch_sum": (i32, [vp, i32, PS, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), i32, PP, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp),
                                         C.POINTER(vp), C.POINTER(vp), vp, C.POINTER(i32)]),
+    "gp_joint_batch": (i32, [vp, i32, PK, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), i32, PP, C.POINTER(vp), PN, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                             vp, i32, C.POINTER(vp), C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(i32)]),
+    "gp_joint_batch_sum": (i32, [vp, i32, PS, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), i32, PP, C.POINTER(vp), PN, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                 vp, i32, C.POINTER(vp), C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(i32)]),
     "gp_logpdf_grad_batch": (i32, [vp, i32, PK, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(vp), C.POINTER(vp),
                                    C.POINTER(vp)]),
     "gp_logpdf_grad_batch_sum": (i32, [vp, i32, PS, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp), C.POINTER(vp),
@@ -175,6 +179,12 @@ def batch_gradx_max_n() -> int:
 def batch_pgrad_max_n() -> int:
     """GPMI355_BATCH_PGRAD_MAX_N of include/gpmi355.h: the largest problem gp_predict_grad_batch hands to its kernels."""
     return int(re.search(r"#define GPMI355_BATCH_PGRAD_MAX_N (\d+)", HEADER.read_text()).group(1))
+
+
+def batch_joint_max() -> tuple:
+    """(GPMI355_BATCH_JOINT_MAX_N, GPMI355_BATCH_JOINT_MAX_NS) of include/gpmi355.h: the largest problem and the most test points gp_joint_batch hands to its kernels."""
+    txt = HEADER.read_text()
+    return tuple(int(re.search(rf"#define GPMI355_BATCH_JOINT_MAX_{k} (\d+)", txt).group(1)) for k in ("N", "NS"))
 
 
 _lib = None

@@ -975,6 +975,154 @@ def mean_and_var_grad_batch(fxs, ys, xs, *, what: int = 3, mean_grads=None, retu
     return (quads, lp) if return_logpdf else quads
 
 
+# --------------------------------------------------------------------------------------------
+# the joint predictive distribution of many small problems: gp_joint_batch / gp_joint_batch_sum
+# --------------------------------------------------------------------------------------------
+JOINT_MEAN, JOINT_COV, JOINT_LOGPDF, JOINT_RAND = 1, 4, 8, 16  # the bits of gp_joint_batch's `what`
+
+
+@dataclass(eq=False)
+class _JointCall:
+    """The marshalled arguments of one gp_joint_batch[_sum] call (everything after the ctx) and the buffers behind them."""
+
+    entry: str
+    nb: int
+    nx: int
+    ny: int
+    nxs: int
+    args: tuple
+    out: np.ndarray                # logpdf(fx_b, y_b)
+    info: np.ndarray
+    info_joint: np.ndarray
+    means: Optional[list]
+    covs: Optional[list]           # ns_b × ns_b, Fortran order
+    heldout: Optional[np.ndarray]
+    samples: Optional[list]        # ns_b × nsamp, Fortran order
+    keep: object
+
+
+def _joint_marshal(g: _BatchGroup, what: int, noises, ys_heldout, xis) -> _JointCall:
+    """ctypes arguments of one group — needs no context.  The leading arguments are those of _predict_marshal; noises / ys_heldout / xis: one entry per
+    problem of the group (Σy*_b or None = zero; y*_b; the standard normals of problem b, ns_b × nsamp), or None."""
+    pc = _predict_marshal(g, what & 1)
+    m, nb = pc.keep, pc.nb
+    nbk, karr, nx, pts, narr, marr, ny, yarr, nxs, xpts, pmarr, _, moarr, _, out, info = pc.args
+    ns = [int(xpts[0 if g.nxs == 1 else b].n) for b in range(nb)]
+    nzarr = None
+    if noises is not None and any(v is not None for v in noises):
+        nzarr = (gp_noise * nb)(*[m.noise(0.0 if v is None else v, k) for v, k in zip(noises, ns)])
+    covs = [np.empty((k, k), dtype=g.dtype, order="F") for k in ns] if what & JOINT_COV else None
+    coarr = (C.c_void_p * nb)(*[a.ctypes.data for a in covs]) if covs is not None else None
+    ysarr = heldout = None
+    if what & JOINT_LOGPDF:
+        ysv = []
+        for b, (v, k) in enumerate(zip(ys_heldout, ns)):
+            v = m.arr(np.asarray(v))
+            if v.shape != (k,):
+                raise ValueError(f"DimensionMismatch: problem {g.index[b]}: {k} test points but ys_heldout has shape {v.shape}")
+            ysv.append(v)
+        ysarr = (C.c_void_p * nb)(*[v.ctypes.data for v in ysv])
+        heldout = np.zeros(nb, dtype=g.dtype)  # logpdf of no observations: 0
+    nsamp, xiarr, samples, soarr = 0, None, None, None
+    if what & JOINT_RAND:
+        xiv = []
+        for b, (v, k) in enumerate(zip(xis, ns)):
+            v = np.asarray(v, dtype=g.dtype)
+            v = v.reshape(k, -1) if v.ndim != 2 else v
+            if v.shape[0] != k or (xiv and v.shape[1] != xiv[0].shape[1]):
+                raise ValueError(f"DimensionMismatch: problem {g.index[b]}: xi must be ({k}, nsamp) with one nsamp per call, got {v.shape}")
+            xiv.append(m.arr(v, order="F"))
+        nsamp = xiv[0].shape[1]
+        xiarr = (C.c_void_p * nb)(*[v.ctypes.data for v in xiv])
+        samples = [np.empty((k, nsamp), dtype=g.dtype, order="F") for k in ns]
+        soarr = (C.c_void_p * nb)(*[a.ctypes.data for a in samples])
+    info_joint = np.zeros(nb, dtype=np.int32)
+    m.keep += [nzarr, coarr, ysarr, xiarr, soarr]
+    args = (nbk, karr, nx, pts, narr, marr, ny, yarr, nxs, xpts, pmarr, nzarr, what, moarr, coarr, ysarr, None if heldout is None else heldout.ctypes.data, nsamp,
+            xiarr, soarr, out, info, info_joint.ctypes.data_as(C.POINTER(C.c_int32)))
+    return _JointCall("gp_joint_batch" + ("_sum" if g.composite else ""), nb, g.nx, g.ny, g.nxs, args, pc.out, pc.info, info_joint, pc.means, covs, heldout, samples, m)
+
+
+def _per_problem(v, n: int, name: str):
+    """None, or one entry per problem: a sequence of n entries, or ONE entry (a scalar) for all of them"""
+    if v is None:
+        return None
+    if not isinstance(v, (list, tuple)) and np.ndim(v) == 0:
+        return [v] * n
+    v = list(v)
+    if len(v) != n:
+        raise ValueError(f"DimensionMismatch: {n} problems but {len(v)} entries of {name}")
+    return v
+
+
+def joint_batch(fxs, ys, xs, *, noise=None, ys_heldout=None, xi=None, what: Optional[int] = None, return_logpdf: bool = False, on_error: str = "raise"):
+    """The joint predictive distribution of many independent exact GPs at their test points, in one library call per (ctx, dtype, single-kind / composite)
+    group — per problem what posterior(fx_b, y_b)(xs_b, noise_b) answers (src/exact_gpr_posterior.jl:78-83, src/finite_gp_projection.jl:133-136, 233-237,
+    306-311): mean and latent covariance (no Σy* added, as mean_and_cov(post, xs_b)), the held-out logpdf(post_b(xs_b, noise_b), ys_heldout_b) and joint samples
+    mean + chol(cov + noise_b).L @ xi_b.  fxs, ys, xs as in mean_and_var_batch.  noise: None (zero), one scalar for all, or one entry per problem (None, a
+    scalar, a vector or a dense matrix over the ns_b test points).  ys_heldout: one vector per problem; xi: one (ns_b × nsamp) array of standard normals per
+    problem, one nsamp per call.  what: bits 1 mean | 4 covariance | 8 held-out logpdf | 16 samples; default: mean and covariance, plus whatever ys_heldout /
+    xi ask for.  Returns the list of (mean, cov, heldout_logpdf, samples) in the caller's order, None for what was not asked for (with return_logpdf: that
+    list and the array of logpdf(fx_b, y_b)).  on_error = "raise": the PosDefException of the first failing problem — its fit, or its joint covariance (.info,
+    .index); "nan": NaN in the outputs the failure reaches (a joint covariance that is not positive definite leaves mean and cov valid)."""
+    if on_error not in ("raise", "nan"):
+        raise ValueError('on_error must be "raise" or "nan"')
+    if what is None:
+        what = JOINT_MEAN | JOINT_COV | (JOINT_LOGPDF if ys_heldout is not None else 0) | (JOINT_RAND if xi is not None else 0)
+    if what <= 0 or what & ~(JOINT_MEAN | JOINT_COV | JOINT_LOGPDF | JOINT_RAND):
+        raise ValueError("what must be a combination of 1 (mean), 4 (cov), 8 (held-out logpdf) and 16 (samples)")
+    if what & JOINT_LOGPDF and ys_heldout is None:
+        raise ValueError("the held-out logpdf needs ys_heldout")
+    if what & JOINT_RAND and xi is None:
+        raise ValueError("samples need xi, the standard normals of every problem")
+    fxs = list(fxs)
+    if not fxs:
+        return ([], np.empty(0)) if return_logpdf else []
+    n = len(fxs)
+    noise, ys_heldout, xi = _per_problem(noise, n, "noise"), _per_problem(ys_heldout, n, "ys_heldout"), _per_problem(xi, n, "xi")
+    quads = [None] * n
+    parts, joint_bad = [], []
+    for g in _predict_groups(fxs, ys, xs):
+        pick = lambda v: None if v is None else [v[i] for i in g.index]
+        call = _joint_marshal(g, what, pick(noise), pick(ys_heldout), pick(xi))
+        ctx = g.ctx or default_context()
+        check(getattr(ctx.lib, call.entry)(ctx.handle, *call.args))
+        parts.append((g.index, call.out, call.info, None))
+        for j, i in enumerate(g.index):
+            quads[i] = (call.means[j] if call.means is not None else None, call.covs[j] if call.covs is not None else None,
+                        call.heldout[j] if call.heldout is not None else None, call.samples[j] if call.samples is not None else None)
+            if call.info_joint[j]:
+                joint_bad.append((i, int(call.info_joint[j])))
+    lp = _batch_merge(n, parts, False, on_error)
+    if on_error == "raise" and joint_bad:
+        i, info = min(joint_bad)
+        raise PosDefException(info, index=i)
+    return (quads, lp) if return_logpdf else quads
+
+
+def mean_and_cov_batch(fxs, ys, xs, **kw):
+    """mean_and_cov(posterior(fx_b, y_b), xs_b) of every problem: the (mean, cov) pairs of joint_batch(what = 1 | 4)."""
+    res = joint_batch(fxs, ys, xs, what=JOINT_MEAN | JOINT_COV, **kw)
+    pairs = [(q[0], q[1]) for q in (res[0] if kw.get("return_logpdf") else res)]
+    return (pairs, res[1]) if kw.get("return_logpdf") else pairs
+
+
+def logpdf_heldout_batch(fxs, ys, xs, ys_heldout, *, noise=None, **kw):
+    """logpdf(posterior(fx_b, y_b)(xs_b, noise_b), ys_heldout_b) of every problem — the score of a cross-validation fold: joint_batch(what = 8) as one array."""
+    res = joint_batch(fxs, ys, xs, noise=noise, ys_heldout=ys_heldout, what=JOINT_LOGPDF, **kw)
+    quads = res[0] if kw.get("return_logpdf") else res
+    hl = np.array([q[2] for q in quads], dtype=np.result_type(*[np.asarray(q[2]).dtype for q in quads]) if quads else np.float64)
+    return (hl, res[1]) if kw.get("return_logpdf") else hl
+
+
+def rand_batch(fxs, ys, xs, xi, *, noise=None, **kw):
+    """rand(posterior(fx_b, y_b)(xs_b, noise_b), nsamp) of every problem with the caller's standard normals xi_b (ns_b × nsamp): joint_batch(what = 16), the list of
+    (ns_b × nsamp) arrays."""
+    res = joint_batch(fxs, ys, xs, noise=noise, xi=xi, what=JOINT_RAND, **kw)
+    draws = [q[3] for q in (res[0] if kw.get("return_logpdf") else res)]
+    return (draws, res[1]) if kw.get("return_logpdf") else draws
+
+
 def _terms(fx: FiniteGP, y, want_logdet: bool, want_sqmahal: bool):
     """gp_logpdf_terms (gp_logpdf_terms_sum for a composite kernel): logdet(cov(fx)) and / or sqmahal(fx, y) from ONE factorisation on the device."""
     f = fx.f

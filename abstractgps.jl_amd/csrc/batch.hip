@@ -1,9 +1,9 @@
 // batch.hip — many small exact GPs in one call: gp_logpdf_batch / gp_logpdf_batch_sum, gp_predict_batch / gp_predict_batch_sum, gp_logpdf_grad_batch /
-// gp_logpdf_grad_batch_sum, gp_predict_grad_batch / gp_predict_grad_batch_sum (include/gpmi355.h) and the kernels behind them: the fit (batch_logpdf_kernel,
+// gp_logpdf_grad_batch_sum, gp_predict_grad_batch / gp_predict_grad_batch_sum, gp_joint_batch / gp_joint_batch_sum (include/gpmi355.h) and the kernels behind them: the fit (batch_logpdf_kernel,
 // below), the predictions at each problem's test points from the slices it leaves (batch_predict_kernel, further down), the gradient of logpdf from the same
 // slices (batch_inv_kernel, batch_grad_kernel, batch_gsum_kernel, behind it; with the input gradient of gp_logpdf_grad_batch_x / gp_logpdf_grad_batch_sum_x:
 // batch_gradx_kernel, batch_gxsum_kernel) and the gradients of the predictions w.r.t. the test inputs from the strips the predict kernel leaves and the S of
-// batch_inv_kernel (batch_pgrad_kernel, last).
+// batch_inv_kernel (batch_pgrad_kernel), last the joint predictive distribution from the same strips (batch_jcov_kernel, batch_jfact_kernel).
 //
 // ONE workgroup owns ONE problem from its inputs to its scalar: it assembles the lower triangle of K + Σy into the problem's slice of a
 // workspace (δ = y − m riding along as row np, as in the single path), factors it by a blocked right-looking Cholesky (64-column blocks:
@@ -15,7 +15,8 @@
 // batch it rides in.  The slice of a problem (its factor and the solved row) stays intact until the call ends.
 //
 // Problems the kernel does not take (fp32, a dense Σy, n > GPMI355_BATCH_MAX_N, D > 16) are answered inside the same call by the
-// single path (gp_logpdf / gp_posterior_fit and their *_sum forms; for predictions gp_posterior_fit + gp_posterior_predict[_grad] + gp_posterior_free); which
+// single path (gp_logpdf / gp_posterior_fit and their *_sum forms; for predictions gp_posterior_fit + gp_posterior_predict[_grad] + gp_posterior_free, for the
+// joint with gp_posterior_logpdf / gp_posterior_rand in between); which
 // path serves a problem depends on that problem alone.
 #include "kfun.hpp"
 
@@ -40,6 +41,7 @@ enum {
     BATCH_PRED_TILES = 1024      // predict workgroups per launch at most: a wave with more tiles of test points runs several predict launches
 };
 static const size_t BATCH_WS_BYTES = (size_t)4 << 30;  // workspace per launch at most: a larger batch runs in waves
+static const size_t JOINT_PIN_BYTES = (size_t)1 << 30;  // what the page-locked staging of a ctx takes (ctx_pinned): a wave of gp_joint_batch stays below it
 
 // One problem of a wave, first thing in the packed input.  Offsets count doubles: *_off into the packed input (−1: absent), a_off into the
 // workspace, alpha_off into the result buffer (−1: α not wanted).
@@ -198,51 +200,13 @@ __device__ __forceinline__ double strip_solve(double* V, const double* A, long l
     return ss;
 }
 
-template <bool SUM>
-__global__ __launch_bounds__(NT) void batch_logpdf_kernel(const double* __restrict__ in, double* __restrict__ ws, double* __restrict__ res, int nw) {
-    __shared__ double Ls[BT][BTS];
-    __shared__ double dinv[BT];
-    __shared__ double red[NT];
-    __shared__ double zs[BATCH_KERNEL_MAX_N];
-    const BatchProb& P = reinterpret_cast<const BatchProb*>(in)[blockIdx.x];
-    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);  // w in a scalar register: row inputs by scalar loads
-    const int n = P.n, np = P.np, d = P.d;
-    const long ld = P.ld;
+// The blocked right-looking Cholesky of a slice in the batch_slice layout, by one workgroup of NT threads: 64-column blocks, the diagonal block in LDS, the rows
+// below it (the carried row np included) by rows_solve_b64, the trailing update on 32×32 wave tiles dealt round-robin to the eight waves.  Ls, dinv and red
+// are the workgroup's LDS ([BT][BTS], [BT], at least BT entries); logdet_half gains Σ log L_ii of the rows below n (thread 0 holds the sum).  Returns 0, or the
+// order of the first leading minor that is not positive (the same value in every thread; the slice is then left half factored).
+__device__ __forceinline__ int batch_chol(double* __restrict__ A, long ld, int n, int np, int tid, int lane, int w, double (*Ls)[BTS], double* dinv, double* red,
+                                          double& logdet_half) {
     const int nt = np / BT;
-    double* __restrict__ A = ws + P.a_off;
-    const double* __restrict__ x = in + P.x_off;
-
-    // ---- 1. lower triangle of K + Σy, 64×64 tiles (lane = column, the eight waves interleave the rows); identity padding
-    for (int ti = 0; ti < nt; ++ti)
-        for (int tj = 0; tj <= ti; ++tj) {
-            const int j = tj * BT + lane;
-            double xj[BATCH_MAXD];
-            batch_load_point(x, n, d, j, xj);
-            for (int rr = 0; rr < BT / 8; ++rr) {
-                const int i = ti * BT + w + 8 * rr;  // wave-uniform
-                double v;
-                if (i >= n || j >= n) {
-                    v = (i == j) ? 1.0 : 0.0;
-                } else {
-                    double t[BATCH_MAXD];
-                    batch_diff(x, n, d, i, xj, t);
-                    v = batch_kval<SUM>(in, &P, t, d);
-                    if (i == j) v += P.nz_off >= 0 ? in[P.nz_off + i] : P.noise_s;
-                }
-                A[(long)i * ld + j] = v;
-            }
-        }
-    {
-        const double* y = in + P.y_off;
-        for (int j = tid; j < np; j += NT) {
-            A[(long)np * ld + j] = j < n ? y[j] - (P.m_off >= 0 ? in[P.m_off + j] : 0.0) : 0.0;
-            for (int r = 1; r < 32; ++r) A[(long)(np + r) * ld + j] = 0.0;
-        }
-    }
-    __syncthreads();
-
-    // ---- 2. blocked right-looking Cholesky
-    double logdet_half = 0.0;  // Σ log L_ii (thread 0)
     int failcol = 0;
     for (int kb = 0; kb < nt; ++kb) {
         const int j0 = kb * BT;
@@ -300,6 +264,55 @@ __global__ __launch_bounds__(NT) void batch_logpdf_kernel(const double* __restri
             }
         __syncthreads();
     }
+    return failcol;
+}
+
+template <bool SUM>
+__global__ __launch_bounds__(NT) void batch_logpdf_kernel(const double* __restrict__ in, double* __restrict__ ws, double* __restrict__ res, int nw) {
+    __shared__ double Ls[BT][BTS];
+    __shared__ double dinv[BT];
+    __shared__ double red[NT];
+    __shared__ double zs[BATCH_KERNEL_MAX_N];
+    const BatchProb& P = reinterpret_cast<const BatchProb*>(in)[blockIdx.x];
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);  // w in a scalar register: row inputs by scalar loads
+    const int n = P.n, np = P.np, d = P.d;
+    const long ld = P.ld;
+    const int nt = np / BT;
+    double* __restrict__ A = ws + P.a_off;
+    const double* __restrict__ x = in + P.x_off;
+
+    // ---- 1. lower triangle of K + Σy, 64×64 tiles (lane = column, the eight waves interleave the rows); identity padding
+    for (int ti = 0; ti < nt; ++ti)
+        for (int tj = 0; tj <= ti; ++tj) {
+            const int j = tj * BT + lane;
+            double xj[BATCH_MAXD];
+            batch_load_point(x, n, d, j, xj);
+            for (int rr = 0; rr < BT / 8; ++rr) {
+                const int i = ti * BT + w + 8 * rr;  // wave-uniform
+                double v;
+                if (i >= n || j >= n) {
+                    v = (i == j) ? 1.0 : 0.0;
+                } else {
+                    double t[BATCH_MAXD];
+                    batch_diff(x, n, d, i, xj, t);
+                    v = batch_kval<SUM>(in, &P, t, d);
+                    if (i == j) v += P.nz_off >= 0 ? in[P.nz_off + i] : P.noise_s;
+                }
+                A[(long)i * ld + j] = v;
+            }
+        }
+    {
+        const double* y = in + P.y_off;
+        for (int j = tid; j < np; j += NT) {
+            A[(long)np * ld + j] = j < n ? y[j] - (P.m_off >= 0 ? in[P.m_off + j] : 0.0) : 0.0;
+            for (int r = 1; r < 32; ++r) A[(long)(np + r) * ld + j] = 0.0;
+        }
+    }
+    __syncthreads();
+
+    // ---- 2. blocked right-looking Cholesky
+    double logdet_half = 0.0;  // Σ log L_ii (thread 0)
+    const int failcol = batch_chol(A, ld, n, np, tid, lane, w, Ls, dinv, red, logdet_half);
 
     double* alpha = P.alpha_off >= 0 ? res + P.alpha_off : nullptr;
     if (failcol) {  // per-problem failure is data: NaN and the first non-positive minor
@@ -929,6 +942,168 @@ __global__ __launch_bounds__(SUM ? PGNT_SUM : NT) void batch_pgrad_kernel(const 
     }
 }
 
+// ---- the joint predictive distribution at the test points: batch_jcov_kernel, batch_jfact_kernel ------------------------------------------------------
+// Launched behind batch_predict_kernel, whose strips of one problem lie one after the other and stay alive: together they are the matrix V = K* L⁻ᵀ of the
+// problem, (128 · tiles) × ld with row = test point.  Launch boundaries are the only synchronisation; every sum runs in an order the problem's sizes fix.
+// What the two kernels know of a problem with test points; `prob` is the position of its BatchProb.  Offsets count doubles: v_off (the strips) and js_off (the
+// joint slice in the batch_slice(ns) layout; −1: no factorisation wanted) into the workspace; cov_off (ns × ns, column-major; −1: not wanted), mean_off (the
+// mean batch_predict_kernel wrote, without the prior mean; −1 without a joint slice), samp_off (ns × nsamp; −1) and jr_off (held-out logpdf, then the failed minor
+// of the joint; −1) into the result buffer; xs_off, ysd_off (y* − m(x*); −1: zeros), nzs_off (a diagonal Σy*; −1: noise_s) and xi_off (ns × nsamp) into the input.
+struct JointProb {
+    long v_off, js_off, cov_off, mean_off, samp_off, jr_off, xs_off, ysd_off, nzs_off, xi_off;
+    int prob, ns, nsp, nsamp;
+    double noise_s;
+};
+static_assert(sizeof(JointProb) % 8 == 0, "the tables are packed behind double data");
+
+// The 64×64 tile (ti >= tj) of the ns × ns matrix of one problem (GradTile: prob = its JointProb), four waves with one 32×32 wave tile each:
+//   acc = K(x*_I, x*_J) evaluated from the packed test points through LDS (identity where a point lies beyond ns), then acc −= V_I V_Jᵀ over the np / 64 blocks of the
+//   strips by mfma_tile_k64 — the latent covariance K** − V Vᵀ of gp_posterior_predict's bit 2.
+// It is stored twice: into the covariance output, the tile and its mirror image (a diagonal tile computes the pairs j <= i only: both triangles hold the same
+// bits by construction), and with Σy* on the diagonal into the lower triangle of the joint slice.  The workgroups of the tiles (ti, 0) also write their 64
+// entries of the carried row δ* = y* − m(x*) − mean (row nsp) and of the 31 zero rows behind it.
+// Only what this call wrote is read: batch_predict_kernel writes the rows of a strip rounded up to 32, so a wave tile that lies wholly beyond ns touches
+// neither the strips nor the covariance.  A failed fit: NaN in the covariance; the joint slice is not written (batch_jfact_kernel does not read it then).
+template <bool SUM>
+__global__ __launch_bounds__(GNT) void batch_jcov_kernel(const double* __restrict__ in, double* __restrict__ ws, double* __restrict__ res, int nw,
+                                                        const JointProb* __restrict__ jps, const GradTile* __restrict__ tiles) {
+    __shared__ double Kt[BT * BTS];
+    const GradTile& T = tiles[blockIdx.x];
+    const JointProb& J = jps[T.prob];
+    const BatchProb& P = reinterpret_cast<const BatchProb*>(in)[J.prob];
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ns = J.ns, nsp = J.nsp, d = P.d;
+    const long lds = batch_ld(nsp);
+    const bool diag = T.ti == T.tj;
+    double* __restrict__ cov = J.cov_off >= 0 ? res + J.cov_off : nullptr;
+    double* __restrict__ S = J.js_off >= 0 ? ws + J.js_off : nullptr;
+    if (res[nw + P.slot] != 0.0) {
+        for (int e = tid; e < BT * BT && cov; e += GNT) {
+            const int gi = T.ti * BT + (e >> 6), gj = T.tj * BT + (e & 63);
+            if (gi < ns && gj < ns) cov[gj + (long)gi * ns] = cov[gi + (long)gj * ns] = __builtin_nan("");
+        }
+        return;
+    }
+    if (S && T.tj == 0) {  // the carried row and the zero rows of the trailing update's 32-row tiles
+        const double* mean = res + J.mean_off;
+        for (int e = tid; e < BT * 32; e += GNT) {
+            const int r = e >> 6, j = T.ti * BT + (e & 63);
+            S[(long)(nsp + r) * lds + j] = (r == 0 && j < ns && J.ysd_off >= 0) ? in[J.ysd_off + j] - mean[j] : 0.0;
+        }
+    }
+    {  // K(x*_I, x*_J) into LDS: lane = column with its inputs in registers, the four waves interleave the rows (wave-uniform: the row's inputs by scalar loads)
+        const double* __restrict__ xs = in + J.xs_off;
+        const int gj = T.tj * BT + lane;
+        double xj[BATCH_MAXD];
+        batch_load_point(xs, ns, d, gj, xj);
+        for (int rr = 0; rr < BT / 4; ++rr) {
+            const int li = w + 4 * rr, gi = T.ti * BT + li;
+            double v;
+            if (gi >= ns || gj >= ns) {
+                v = (gi == gj) ? 1.0 : 0.0;
+            } else {
+                double t[BATCH_MAXD];
+                batch_diff(xs, ns, d, gi, xj, t);
+                v = batch_kval<SUM>(in, &P, t, d);
+            }
+            Kt[li * BTS + lane] = v;
+        }
+    }
+    __syncthreads();
+    const int wi = w >> 1, wj = w & 1;
+    if (diag && wj > wi) return;  // the wave tile strictly above the diagonal: its mirror image computes it
+    const int i0 = T.ti * BT + 32 * wi, c0 = T.tj * BT + 32 * wj, r = lane & 15;  // c0 <= i0
+    d4_t acc[2][2];
+    acc_load(acc, Kt, 32 * wi, 32 * wj, BTS, lane);
+    if (i0 < ns) {  // rows i0 … i0 + 31 and c0 … c0 + 31 of the strips lie below ns rounded up to 32: written by this call
+        const double* __restrict__ V = ws + J.v_off;
+        for (int k0 = 0; k0 < P.np; k0 += BT) mfma_tile_k64<true>(acc, V, i0, V, c0, k0, P.ld, lane);
+    }
+    const bool lower_only = diag && wi == wj;  // the wave tile on the diagonal: the pairs j <= i, mirrored
+#pragma unroll
+    for (int hi = 0; hi < 2; ++hi)
+#pragma unroll
+        for (int hj = 0; hj < 2; ++hj) {
+            const int gj = c0 + 16 * hj + r;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int gi = i0 + 16 * hi + Tr<double>::crow(lane, q);
+                if (lower_only && gj > gi) continue;
+                const double v = acc[hi][hj][q];
+                if (cov && gi < ns && gj < ns) {
+                    cov[gj + (long)gi * ns] = v;
+                    if (gi != gj) cov[gi + (long)gj * ns] = v;
+                }
+                if (S) {
+                    const double nz = (gi == gj && gi < ns) ? (J.nzs_off >= 0 ? in[J.nzs_off + gi] : J.noise_s) : 0.0;
+                    S[(long)gi * lds + gj] = v + nz;
+                    if (diag && gi != gj) S[(long)gj * lds + gi] = v;  // the whole diagonal block is loaded into LDS by the factorisation
+                }
+            }
+        }
+}
+
+// The joint slice of one problem per workgroup: batch_chol on C* + Σy* with δ* riding along as row nsp, then
+//   hlogpdf = −½ (ns log 2π + 2 Σ log L*_ii + ‖L*⁻¹ δ*‖²)    off the carried row (strided partial sums, then a tree), and the samples
+//   out[i, s] = mean_i + Σ_{j <= i} L*_ij ξ_js                  one wave per row i, the lanes striding over j, a butterfly, lane 0 the only writer.
+// A non-positive pivot stores its order behind the logpdf, NaN in the logpdf and in the samples; so does a failed fit, with order 0.
+__global__ __launch_bounds__(NT) void batch_jfact_kernel(const double* __restrict__ in, double* __restrict__ ws, double* __restrict__ res, int nw,
+                                                        const JointProb* __restrict__ jps) {
+    __shared__ double Ls[BT][BTS];
+    __shared__ double dinv[BT];
+    __shared__ double red[NT];
+    const JointProb& J = jps[blockIdx.x];
+    const BatchProb& P = reinterpret_cast<const BatchProb*>(in)[J.prob];
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ns = J.ns, nsp = J.nsp, nsamp = J.nsamp;
+    const long lds = batch_ld(nsp);
+    double* __restrict__ A = ws + J.js_off;
+    double* __restrict__ out = J.samp_off >= 0 ? res + J.samp_off : nullptr;
+    double* __restrict__ jr = res + J.jr_off;
+    const bool fit_failed = res[nw + P.slot] != 0.0;  // the same value in every thread
+    double logdet_half = 0.0;
+    const int failcol = fit_failed ? 0 : batch_chol(A, lds, ns, nsp, tid, lane, w, Ls, dinv, red, logdet_half);
+    if (fit_failed || failcol) {
+        if (tid == 0) {
+            jr[0] = __builtin_nan("");
+            jr[1] = (double)failcol;
+        }
+        for (long e = tid; e < (long)ns * nsamp && out; e += NT) out[e] = __builtin_nan("");
+        return;
+    }
+    {
+        double s = 0.0;
+        for (int j = tid; j < nsp; j += NT) {
+            const double z = A[(long)nsp * lds + j];
+            s = fma(z, z, s);
+        }
+        red[tid] = s;
+        __syncthreads();
+        for (int h = NT / 2; h > 0; h >>= 1) {
+            if (tid < h) red[tid] += red[tid + h];
+            __syncthreads();
+        }
+        if (tid == 0) {
+            jr[0] = -0.5 * ((double)ns * 1.8378770664093454835606594728112 + 2.0 * logdet_half + red[0]);
+            jr[1] = 0.0;
+        }
+    }
+    if (!out) return;
+    const double* __restrict__ xi = in + J.xi_off;
+    const double* __restrict__ mean = res + J.mean_off;
+    for (int i = w; i < ns; i += 8) {  // wave-uniform
+        const double* row = A + (long)i * lds;
+        for (int s = 0; s < nsamp; ++s) {
+            const double* z = xi + (long)s * ns;
+            double v = 0.0;
+            for (int j = lane; j <= i; j += 64) v = fma(row[j], z[j], v);
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+            if (lane == 0) out[(long)s * ns + i] = mean[i] + v;
+        }
+    }
+}
+
 }  // namespace gpmi
 
 using namespace gpmi;
@@ -1518,6 +1693,250 @@ int32_t predict_grad_batch_impl(gp_ctx* c, PredictArgs& a) {
     return 0;
 }
 
+// ---- gp_joint_batch / gp_joint_batch_sum ------------------------------------------------------------------------------------------------------------------
+struct JointArgs : PredictArgs {  // what: 1 mean | 4 latent covariance | 8 held-out logpdf | 16 samples; var_out is not used
+    const gp_noise* noise_xs;
+    void* const* cov_out;
+    const void* const* ys;
+    void* hlogpdf_out;
+    int32_t nsamp;
+    const void* const* xi;
+    void* const* samples_out;
+    int32_t* info_joint;
+    bool want_fact() const { return (what & 24) != 0; }
+    bool want_mean() const { return (what & 25) != 0; }  // the held-out logpdf and the samples are built on it
+    long draws(int b) const { return (what & 16) ? xsb(b).n * (long)nsamp : 0; }
+    void* out_ptr(void* const* arr, int bit, int b) const { return (arr && (what & bit)) ? arr[b] : nullptr; }
+    size_t esize() const { return dtype == 0 ? 8 : 4; }
+};
+
+// NaN in the held-out logpdf and the samples of problem b (a joint covariance that is not positive definite, or a failed fit)
+void joint_fill_nan(const JointArgs& a, int b) {
+    if (a.what & 8) put(a.hlogpdf_out, a.dtype, b, std::numeric_limits<double>::quiet_NaN());
+    fill_nan(a.out_ptr(a.samples_out, 16, b), a.dtype, a.draws(b));
+}
+
+// workspace doubles of problem b beyond its slice: every predict strip (they stay alive for batch_jcov_kernel) and the joint slice
+long joint_ws(const JointArgs& a, int b) {
+    const long ns = a.xsb(b).n;
+    if (ns == 0 || a.what == 1) return 0;
+    return (ns + TP - 1) / TP * TP * batch_ld(batch_np(a.xb(b).n)) + (a.want_fact() ? batch_slice(ns) : 0);
+}
+
+// one wave: the fit, the predict launches with a strip per tile (none shared), batch_jcov_kernel over the 64×64 tiles of every problem's ns × ns matrix and
+// batch_jfact_kernel on the joint slices.  Caller holds the ctx lock.
+int32_t run_joint_wave(gp_ctx* c, const JointArgs& a, const std::vector<KSum>& packed, const int* idx, int nw) {
+    const bool need_v = a.what != 1;
+    WaveLayout L;
+    wave_layout(a, idx, nw, [&](int b) { return a.want_mean() && a.xsb(b).n > 0; }, L);
+    std::vector<long> xs_off((size_t)nw, -1), mean_off((size_t)nw, -1), var_off((size_t)nw, -1);
+    std::vector<int> jp_of((size_t)nw, -1);
+    std::vector<JointProb> jp;
+    SharedOnce xso{a.nxs == 1}, xsf{a.nxs == 1};  // layout, filling
+    for (int t = 0; t < nw; ++t) {
+        const int b = idx[t];
+        const gp_points& xs = a.xsb(b);
+        const long ns = xs.n;
+        if (ns == 0) continue;
+        xs_off[t] = xso.place(L.off, (long)xs.d * ns);
+        if (a.want_mean()) mean_off[t] = take(L.roff, ns);
+        if (!need_v) continue;
+        var_off[t] = take(L.roff, ns);  // the variance the predict kernel computes on its way to V: scratch
+        JointProb j{};
+        j.prob = L.pos[t], j.ns = (int)ns, j.nsp = (int)batch_np(ns), j.nsamp = a.nsamp;
+        j.v_off = j.js_off = -1;
+        j.xs_off = xs_off[t], j.mean_off = mean_off[t];
+        j.cov_off = (a.what & 4) ? take(L.roff, ns * ns) : -1;
+        j.jr_off = a.want_fact() ? take(L.roff, 2) : -1;
+        j.samp_off = (a.what & 16) ? take(L.roff, a.draws(b)) : -1;
+        j.ysd_off = (a.what & 8) ? take(L.off, ns) : -1;
+        j.xi_off = (a.what & 16) ? take(L.off, a.draws(b)) : -1;
+        const gp_noise* nz = a.noise_xs ? &a.noise_xs[b] : nullptr;
+        j.noise_s = nz ? nz->s : 0.0;
+        j.nzs_off = (nz && nz->kind == 1) ? take(L.off, ns) : -1;
+        jp_of[t] = (int)jp.size();
+        jp.push_back(j);
+    }
+    // a problem's tiles of TP test points lie one after the other, and so do their strips; a predict launch closes at BATCH_PRED_TILES tiles
+    std::vector<BatchTile> tiles;
+    std::vector<GradTile> jtiles;
+    std::vector<size_t> launch_end;
+    for (int s = 0; s < nw; ++s) {
+        const int t = L.order[s];
+        const long ns = a.xsb(idx[t]).n, strip = need_v ? (long)TP * L.pr[t].ld : 0;
+        if (ns == 0) continue;
+        if (jp_of[t] >= 0) jp[(size_t)jp_of[t]].v_off = L.ws;
+        for (long row0 = 0; row0 < ns; row0 += TP) {
+            if (!tiles.empty() && (tiles.size() - (launch_end.empty() ? 0 : launch_end.back())) == BATCH_PRED_TILES) launch_end.push_back(tiles.size());
+            tiles.push_back(BatchTile{xs_off[t], take(L.ws, strip), mean_off[t], var_off[t], L.pos[t], (int)ns, (int)row0, (int)std::min<long>(TP, ns - row0)});
+        }
+        if (jp_of[t] < 0) continue;
+        JointProb& j = jp[(size_t)jp_of[t]];
+        if (a.want_fact()) j.js_off = take(L.ws, batch_slice(ns));
+        for (int ti = 0; ti < j.nsp / BT; ++ti)
+            for (int tj = 0; tj <= ti; ++tj) jtiles.push_back(GradTile{jp_of[t], ti, tj, 0});
+    }
+    if (!tiles.empty()) launch_end.push_back(tiles.size());
+    const long tile_off = take(L.off, (long)(tiles.size() * sizeof(BatchTile) / 8));
+    const long jp_off = take(L.off, (long)(jp.size() * sizeof(JointProb) / 8));
+    const long jt_off = take(L.off, (long)(jtiles.size() * sizeof(GradTile) / 8));
+
+    WaveMem m(c);
+    RC(m.alloc(L.off, L.ws, L.roff));
+    wave_fill(a, packed, idx, nw, L, m.hin);
+    for (int t = 0; t < nw; ++t) {
+        const int b = idx[t];
+        const gp_points& xs = a.xsb(b);
+        if (xs.n == 0) continue;
+        if (xsf.claim()) pack_points(xs, m.hin + xs_off[t]);
+        if (jp_of[t] < 0) continue;
+        const JointProb& j = jp[(size_t)jp_of[t]];
+        if (j.ysd_off >= 0) {
+            const double *ys = (const double*)a.ys[b], *pm = (const double*)a.pmb(b);
+            for (long i = 0; i < xs.n; ++i) m.hin[j.ysd_off + i] = pm ? ys[i] - pm[i] : ys[i];
+        }
+        if (j.xi_off >= 0 && a.draws(b) > 0) std::memcpy(m.hin + j.xi_off, a.xi[b], sizeof(double) * (size_t)a.draws(b));
+        if (j.nzs_off >= 0) std::memcpy(m.hin + j.nzs_off, a.noise_xs[b].diag, sizeof(double) * (size_t)xs.n);
+    }
+    if (!tiles.empty()) std::memcpy(m.hin + tile_off, tiles.data(), tiles.size() * sizeof(BatchTile));
+    if (!jp.empty()) std::memcpy(m.hin + jp_off, jp.data(), jp.size() * sizeof(JointProb));
+    if (!jtiles.empty()) std::memcpy(m.hin + jt_off, jtiles.data(), jtiles.size() * sizeof(GradTile));
+    const bool ks = a.ks != nullptr;
+    RC(run_drained(c, [&]() -> int32_t {
+        RC(m.upload());
+        RC(launch_fit(m, ks, nw));
+        size_t t0 = 0;
+        for (size_t t1 : launch_end) {
+            RC(launch_predict(m, ks, nw, reinterpret_cast<const BatchTile*>(m.in + tile_off) + t0, t1 - t0));
+            t0 = t1;
+        }
+        const JointProb* djp = reinterpret_cast<const JointProb*>(m.in + jp_off);
+        if (!jtiles.empty()) {
+            hipLaunchKernelGGL(ks ? batch_jcov_kernel<true> : batch_jcov_kernel<false>, dim3((unsigned)jtiles.size()), dim3(GNT), 0, c->sm, m.in, m.ws, m.res, nw, djp,
+                               reinterpret_cast<const GradTile*>(m.in + jt_off));
+            HIPCHK(hipGetLastError());
+        }
+        if (a.want_fact() && !jp.empty()) {
+            hipLaunchKernelGGL(batch_jfact_kernel, dim3((unsigned)jp.size()), dim3(NT), 0, c->sm, m.in, m.ws, m.res, nw, djp);
+            HIPCHK(hipGetLastError());
+        }
+        return m.download_and_sync();
+    }));
+    const double* hout = m.hout;
+    c->batch_joint_problems += nw;
+    for (int t = 0; t < nw; ++t) {
+        const int b = idx[t];
+        put_result(a, b, hout[t], (int32_t)hout[nw + t]);
+        if (a.info_joint) a.info_joint[b] = 0;
+        const long ns = a.xsb(b).n;
+        if (ns == 0) continue;
+        const double* pm = (const double*)a.pmb(b);
+        if (double* mo = (double*)a.out_ptr(a.mean_out, 1, b))
+            for (long j = 0; j < ns; ++j) mo[j] = pm ? pm[j] + hout[mean_off[t] + j] : hout[mean_off[t] + j];
+        if (jp_of[t] < 0) continue;
+        const JointProb& j = jp[(size_t)jp_of[t]];
+        if (void* co = a.out_ptr(a.cov_out, 4, b)) std::memcpy(co, hout + j.cov_off, sizeof(double) * (size_t)(ns * ns));
+        if (j.jr_off >= 0) {
+            if (a.what & 8) ((double*)a.hlogpdf_out)[b] = hout[j.jr_off];
+            if (a.info_joint) a.info_joint[b] = (int32_t)hout[j.jr_off + 1];
+        }
+        if (double* so = (double*)a.out_ptr(a.samples_out, 16, b))
+            for (long e = 0; e < a.draws(b); ++e) so[e] = pm ? pm[e % ns] + hout[j.samp_off + e] : hout[j.samp_off + e];
+    }
+    return 0;
+}
+
+int32_t joint_batch_impl(gp_ctx* c, JointArgs& a) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    if (a.nb < 0) return set_arg_err(2, "nb must be >= 0");
+    if (a.nb == 0) return 0;
+    RC(check_batch_head(a));
+    if (a.nxs != 1 && a.nxs != a.nb) return set_arg_err(10, "nxs must be 1 (one xs shared by every problem) or nb");
+    if (!a.xs) return set_arg_err(11, "test points array is NULL");
+    if (a.what <= 0 || (a.what & ~29)) return set_arg_err(14, "what must be a combination of 1|4|8|16 (marginal variances: gp_predict_batch)");
+    if ((a.what & 1) && !a.mean_out) return set_arg_err(15, "mean_out is NULL");
+    if ((a.what & 4) && !a.cov_out) return set_arg_err(16, "cov_out is NULL");
+    if ((a.what & 8) && !a.ys) return set_arg_err(17, "ys array is NULL");
+    if ((a.what & 8) && !a.hlogpdf_out) return set_arg_err(18, "hlogpdf_out is NULL");
+    if (a.nsamp < 0) return set_arg_err(19, "nsamp must be >= 0");
+    if ((a.what & 16) && a.nsamp > 0 && !a.xi) return set_arg_err(20, "xi array is NULL");
+    if ((a.what & 16) && a.nsamp > 0 && !a.samples_out) return set_arg_err(21, "samples_out is NULL");
+    if (!a.info_out) return set_arg_err(23, "info_out is NULL");
+    std::vector<KSum> packed;
+    RC(check_batch_problems(a, packed));
+    for (int b = 0; b < a.nb; ++b) {
+        const gp_points& xs = a.xsb(b);
+        if (xs.n < 0) return set_arg_err(11, "xs: n must be >= 0");
+        if (xs.n == 0) continue;  // no test points: nothing of this problem's xs or outputs is touched
+        RC(check_points(&xs, 11));
+        if (xs.d != a.xb(b).d) return set_arg_err(11, "xs has a different D than the training inputs");
+        if (a.noise_xs) RC(check_noise(&a.noise_xs[b], 13, true));
+        if ((a.what & 1) && !a.mean_out[b]) return set_arg_err(15, "a mean_out pointer is NULL");
+        if ((a.what & 4) && !a.cov_out[b]) return set_arg_err(16, "a cov_out pointer is NULL");
+        if ((a.what & 8) && !a.ys[b]) return set_arg_err(17, "a ys pointer is NULL");
+        if ((a.what & 16) && a.nsamp > 0 && !a.xi[b]) return set_arg_err(20, "a xi pointer is NULL");
+        if ((a.what & 16) && a.nsamp > 0 && !a.samples_out[b]) return set_arg_err(21, "a samples_out pointer is NULL");
+    }
+    // which path serves a problem depends on that problem alone: gp_logpdf_batch's routing under the joint limits, and a Σy* the kernels take
+    const long max_n = env_capped(getenv("GPMI_BATCH_JOINT_MAX_N"), GPMI355_BATCH_JOINT_MAX_N);
+    const long max_ns = env_capped(getenv("GPMI_BATCH_JOINT_MAX_NS"), GPMI355_BATCH_JOINT_MAX_NS);
+    std::vector<int> mine, routed;
+    for (int b = 0; b < a.nb; ++b) {
+        const bool nz_ok = !a.noise_xs || a.xsb(b).n == 0 || a.noise_xs[b].kind <= 1;
+        (batch_takes(a, b, max_n) && a.xsb(b).n <= max_ns && nz_ok ? mine : routed).push_back(b);
+    }
+    // slice + strips + joint slice per problem.  The covariances and the draws of a wave travel through the page-locked staging of the ctx, which takes
+    // JOINT_PIN_BYTES: a wave that needs more is staged in pageable memory and copies at a quarter of the rate (measured: 512 problems of 64 points with 1 024 test points
+    // each in waves of 222, 1 252 ms; in waves that fit, 267 ms).  Charging four times the staged bytes against the workspace budget (four times that limit) bounds both.
+    static_assert(BATCH_WS_BYTES == 4 * JOINT_PIN_BYTES, "the factor below");
+    auto cost = [&](int b) {
+        const gp_points &x = a.xb(b), &xs = a.xsb(b);
+        const long n = x.n, ns = xs.n, nts = batch_np(ns) / BT;
+        const size_t ws = sizeof(double) * (size_t)(batch_slice(n) + joint_ws(a, b));
+        const size_t staged = sizeof(double) * (size_t)(((a.what & 4) ? ns * ns : 0) + 2 * a.draws(b) + (ns + n) * (x.d + 4) + 8) + sizeof(BatchProb) + sizeof(KSum) +
+                              sizeof(JointProb) + (size_t)((ns + TP - 1) / TP) * sizeof(BatchTile) + (size_t)(nts * (nts + 1) / 2) * sizeof(GradTile);
+        return WaveCost{std::max(ws, 4 * staged), 0};
+    };
+    RC(for_each_wave(c, mine, cost, [&](const int* idx, int nw) { return run_joint_wave(c, a, packed, idx, nw); }));
+    // everything else: gp_posterior_fit, _predict (bits 0 and 2), _logpdf, _rand and _free on the single path, after the lock is released (as batch_impl does)
+    gd.lk.unlock();
+    const gp_noise zero_noise{0, 0.0, nullptr};
+    for (int b : routed) {
+        const gp_points& x = a.xb(b);
+        const gp_points& xs = a.xsb(b);
+        const gp_noise* nz = a.noise_xs ? &a.noise_xs[b] : &zero_noise;
+        gp_post* post = nullptr;
+        void* lp = logpdf_slot(a, b);
+        int32_t rj = 0;
+        int32_t rc = a.ks ? gp_posterior_fit_sum(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), &post, nullptr, lp)
+                          : gp_posterior_fit(c, &a.k[b], &x, &a.noise[b], a.mb(b), a.yb(b), &post, nullptr, lp);
+        if (rc == 0 && xs.n > 0 && (a.what & 5))
+            rc = gp_posterior_predict(post, &xs, a.pmb(b), a.what & 5, a.out_ptr(a.mean_out, 1, b), nullptr, a.out_ptr(a.cov_out, 4, b));
+        if (rc == 0 && xs.n > 0 && (a.what & 8)) {
+            rj = gp_posterior_logpdf(post, &xs, a.pmb(b), nz, a.ys[b], xs.n, 1, (char*)a.hlogpdf_out + a.esize() * (size_t)b);
+            if (rj < 0) rc = rj;
+        }
+        if (rc == 0 && rj == 0 && xs.n > 0 && a.draws(b) > 0) {
+            rj = gp_posterior_rand(post, &xs, a.pmb(b), nz, a.xi[b], a.nsamp, a.samples_out[b]);
+            if (rj < 0) rc = rj;
+        }
+        if (post) (void)gp_posterior_free(post);
+        if (rc < 0) return rc;
+        a.info_out[b] = rc;
+        if (a.info_joint) a.info_joint[b] = rc == 0 ? rj : 0;
+        if (rc > 0) {
+            put_result(a, b, std::numeric_limits<double>::quiet_NaN(), rc);
+            if (xs.n > 0) {
+                fill_nan(a.out_ptr(a.mean_out, 1, b), a.dtype, xs.n);
+                fill_nan(a.out_ptr(a.cov_out, 4, b), a.dtype, xs.n * xs.n);
+            }
+        }
+        if ((rc > 0 || rj > 0) && xs.n > 0) joint_fill_nan(a, b);
+    }
+    return 0;
+}
+
 // ---- gp_logpdf_grad_batch / gp_logpdf_grad_batch_sum ---------------------------------------------------------------------------------------------------
 struct GradArgs : BatchArgs {
     double* dvar;             // single-kind: nb entries, or NULL
@@ -1774,6 +2193,31 @@ int32_t gp_predict_grad_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int
                   mean_out_or_null, var_out_or_null, true, dmean_out_or_null, dvar_out_or_null};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return predict_grad_batch_impl(ctx, a);
+}
+
+int32_t gp_joint_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                       const void* const* mean_or_null, int32_t ny, const void* const* y, int32_t nxs, const gp_points* xs,
+                       const void* const* prior_mean_xs_or_null, const gp_noise* noise_xs_or_null, int32_t what, void* const* mean_out_or_null,
+                       void* const* cov_out_or_null, const void* const* ys_or_null, void* hlogpdf_out_or_null, int32_t nsamp, const void* const* xi_or_null,
+                       void* const* samples_out_or_null, void* logpdf_out_or_null, int32_t* info_out, int32_t* info_joint_out_or_null) {
+    JointArgs a{{{nb, k, nullptr, nx, x, noise, mean_or_null, ny, y, logpdf_out_or_null, info_out, nullptr, 0}, nxs, xs, prior_mean_xs_or_null, what,
+                 mean_out_or_null, nullptr},
+                noise_xs_or_null, cov_out_or_null, ys_or_null, hlogpdf_out_or_null, nsamp, xi_or_null, samples_out_or_null, info_joint_out_or_null};
+    if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
+    return joint_batch_impl(ctx, a);
+}
+
+int32_t gp_joint_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                           const void* const* mean_or_null, int32_t ny, const void* const* y, int32_t nxs, const gp_points* xs,
+                           const void* const* prior_mean_xs_or_null, const gp_noise* noise_xs_or_null, int32_t what, void* const* mean_out_or_null,
+                           void* const* cov_out_or_null, const void* const* ys_or_null, void* hlogpdf_out_or_null, int32_t nsamp,
+                           const void* const* xi_or_null, void* const* samples_out_or_null, void* logpdf_out_or_null, int32_t* info_out,
+                           int32_t* info_joint_out_or_null) {
+    JointArgs a{{{nb, nullptr, k, nx, x, noise, mean_or_null, ny, y, logpdf_out_or_null, info_out, nullptr, 0}, nxs, xs, prior_mean_xs_or_null, what,
+                 mean_out_or_null, nullptr},
+                noise_xs_or_null, cov_out_or_null, ys_or_null, hlogpdf_out_or_null, nsamp, xi_or_null, samples_out_or_null, info_joint_out_or_null};
+    if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
+    return joint_batch_impl(ctx, a);
 }
 
 int32_t gp_logpdf_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, const gp_noise* noise,

@@ -2334,6 +2334,10 @@ int32_t gp_ctx_get_param(gp_ctx* c, const char* name, int64_t* out) {
         *out = c->batch_gradx_problems;
         return 0;
     }
+    if (!strcmp(name, "batch_joint_kernel_problems")) {  // the same for the kernels of gp_joint_batch / _sum (batch_jcov_kernel, batch_jfact_kernel)
+        *out = c->batch_joint_problems;
+        return 0;
+    }
     const struct { const char* n; int64_t v; } tab[] = {
         {"nb", c->nb}, {"nb_small", c->nb_small}, {"nb_large", c->nb_large}, {"lookahead", c->lookahead}, {"lookahead_min_n", c->lookahead_min_n}, {"time_kernels", c->time_kernels},
         {"xcd_swizzle", c->xcd_swizzle}, {"strassen_min_rows", c->strassen_min_rows}, {"strassen_min_rows_large", c->strassen_min_rows_large}, {"strassen_group", c->strassen_group}, {"strassen_group_min_rows", c->strassen_group_min_rows}, {"xcd_min_tiles", c->xcd_min_tiles}, {"gemm_streamk", c->gemm_streamk},

@@ -28,7 +28,7 @@ using KernelFunctions: SqExponentialKernel, Matern12Kernel, ExponentialKernel, M
 using LinearAlgebra, FillArrays, Statistics, StatsBase, Distributions, Random
 using ChainRulesCore
 
-export HipGP, HipPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, elbo_and_grad, logpdf_batch, mean_and_var_batch, mean_and_var_grad_batch, logpdf_and_grad_batch, BatchPosDefException
+export HipGP, HipPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, elbo_and_grad, logpdf_batch, mean_and_var_batch, mean_and_var_grad_batch, joint_batch, mean_and_cov_batch, logpdf_heldout_batch, rand_batch, logpdf_and_grad_batch, BatchPosDefException
 
 const libgpmi355 = get(ENV, "GPMI355_LIB", joinpath(@__DIR__, "..", "csrc", "libgpmi355.so"))
 
@@ -532,6 +532,153 @@ function mean_and_var_batch(fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys, xs; wh
     pairs = [(means[b], vars[b]) for b in 1:nb]
     return return_logpdf ? (pairs, lp) : pairs
 end
+
+# ---- the joint predictive distribution: gp_joint_batch / gp_joint_batch_sum --------------------------------------------------------
+# joint_batch(fxs, ys, xs; noise, ys_heldout, xi, what): per problem what posterior(fxs[b], ys[b])(xs[b], noise[b]) answers (src/exact_gpr_posterior.jl:78-83,
+# src/finite_gp_projection.jl:133-136, 233-237, 306-311) in ONE library call per (context, eltype, single-kind / composite) group: what bit 1 the mean,
+# 4 the latent covariance (mean_and_cov(post, xs[b]): no Σy* added), 8 logpdf(post(xs[b], noise[b]), ys_heldout[b]), 16 the samples
+# mean .+ cholesky(cov + noise[b]).L * xi[b] with the caller's standard normals (ns_b × nsamp, one nsamp per call).  noise: nothing (zero), one Real for all,
+# or one entry per problem (nothing, a Real, or a covariance matrix over the test points as a FiniteGP holds it).  Returns the vector of
+# (mean, cov, heldout_logpdf, samples) tuples in the caller's order, `nothing` for what was not asked for (with return_logpdf = true: that vector and the
+# logpdfs).  on_error as in logpdf_batch; a joint covariance that is not positive definite counts as that problem's failure, with mean and cov left valid.
+# A problem the ABI has no layout for takes the stock path.
+joint_noise(::Nothing, n, ::Type{T}) where {T} = (nothing, CNoise(0, 0.0, C_NULL))
+joint_noise(s::Real, n, ::Type{T}) where {T} = (nothing, CNoise(0, Float64(s), C_NULL))
+joint_noise(Σ::AbstractMatrix, n, ::Type{T}) where {T} = noise(Σ, T)
+stock_noise(::Nothing) = 0.0
+stock_noise(s) = s
+function joint_batch(fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys, xs; noise=nothing, ys_heldout=nothing, xi=nothing,
+                     what::Integer=1 | 4 | (ys_heldout === nothing ? 0 : 8) | (xi === nothing ? 0 : 16), return_logpdf::Bool=false, on_error::Symbol=:raise)
+    on_error in (:raise, :nan) || throw(ArgumentError("on_error must be :raise or :nan"))
+    (what > 0 && (what & ~29) == 0) || throw(ArgumentError("what must be a combination of 1 (mean), 4 (cov), 8 (held-out logpdf) and 16 (samples)"))
+    ((what & 8) == 0 || ys_heldout !== nothing) || throw(ArgumentError("the held-out logpdf needs ys_heldout"))
+    ((what & 16) == 0 || xi !== nothing) || throw(ArgumentError("samples need xi, the standard normals of every problem"))
+    nb = length(fxs)
+    yv = (ys isa AbstractVector{<:Real}) ? fill(ys, nb) : collect(ys)
+    xv = (xs isa ColVecs || xs isa RowVecs || xs isa AbstractVector{<:Real}) ? fill(xs, nb) : collect(xs)
+    nzv = (noise === nothing || noise isa Real) ? fill(noise, nb) : collect(noise)
+    length(yv) == nb || throw(DimensionMismatch("$(nb) problems but $(length(yv)) observation vectors"))
+    length(xv) == nb || throw(DimensionMismatch("$(nb) problems but $(length(xv)) sets of test points"))
+    length(nzv) == nb || throw(DimensionMismatch("$(nb) problems but $(length(nzv)) entries of noise"))
+    nsamp = (what & 16) != 0 && nb > 0 ? size(xi[1], 2) : 0
+    args = [marshal(fxs[b], eltype(yv[b])) for b in 1:nb]
+    T = (nb > 0 && all(a -> a !== nothing && a.T === Float32, args)) ? Float32 : Float64
+    lp = Vector{T}(undef, nb)
+    info = zeros(Int32, nb)
+    infoj = zeros(Int32, nb)
+    means = Vector{Any}(nothing, nb)
+    covs = Vector{Any}(nothing, nb)
+    hls = Vector{Any}(nothing, nb)
+    draws = Vector{Any}(nothing, nb)
+    groups = Dict{Any,Vector{Int}}()
+    for b in 1:nb
+        length(yv[b]) == length(fxs[b]) || throw(DimensionMismatch("problem $(b): length(fx) = $(length(fxs[b])) but y has $(length(yv[b])) entries"))
+        a = args[b]
+        ns = length(xv[b])
+        if a === nothing || points(xv[b], a.T) === nothing || joint_noise(nzv[b], ns, a.T) === nothing  # stock path, one problem at a time
+            try
+                lp[b] = logpdf(stock(fxs[b]), yv[b])
+                post = posterior(stock(fxs[b]), yv[b])
+                m, Cs = mean_and_cov(post, xv[b])
+                (what & 1) != 0 && (means[b] = m)
+                (what & 4) != 0 && (covs[b] = Cs)
+                try
+                    fs = post(xv[b], stock_noise(nzv[b]))
+                    (what & 8) != 0 && (hls[b] = logpdf(fs, ys_heldout[b]))
+                    (what & 16) != 0 && (draws[b] = mean(fs) .+ cholesky(Symmetric(cov(fs))).L * xi[b])
+                catch e
+                    e isa PosDefException || rethrow()
+                    infoj[b] = e.info
+                    (what & 8) != 0 && (hls[b] = NaN)
+                    (what & 16) != 0 && (draws[b] = fill(NaN, ns, nsamp))
+                end
+            catch e
+                e isa PosDefException || rethrow()
+                lp[b] = NaN
+                info[b] = e.info
+                (what & 1) != 0 && (means[b] = fill(NaN, ns))
+                (what & 4) != 0 && (covs[b] = fill(NaN, ns, ns))
+                (what & 8) != 0 && (hls[b] = NaN)
+                (what & 16) != 0 && (draws[b] = fill(NaN, ns, nsamp))
+            end
+        else
+            push!(get!(groups, (fxs[b].f.ctx, a.T, haskey(a, :ks)), Int[]), b)
+        end
+    end
+    for ((ctx, Tg, composite), idx) in groups
+        g = length(idx)
+        nx = all(b -> fxs[b].x === fxs[idx[1]].x, idx) ? 1 : g
+        ny = all(b -> yv[b] === yv[idx[1]], idx) ? 1 : g
+        nxs = all(b -> xv[b] === xv[idx[1]], idx) ? 1 : g
+        cxs = [args[b].cx for b in idx[1:nx]]
+        cns = [args[b].cn for b in idx]
+        ybufs = [Vector{Tg}(yv[b]) for b in idx[1:ny]]
+        yptrs = Ptr{Cvoid}[pointer(v) for v in ybufs]
+        mptrs = Ptr{Cvoid}[args[b].m === nothing ? C_NULL : pointer(args[b].m) for b in idx]
+        xsp = [points(xv[b], Tg) for b in idx[1:nxs]]  # (buffer, CPoints)
+        cxss = [p[2] for p in xsp]
+        pms = [prior_mean(fxs[b].f.gp, xv[b], Tg) for b in idx]  # m(x*) on the host; nothing = ZeroMean
+        pmptrs = Ptr{Cvoid}[m === nothing ? C_NULL : pointer(m) for m in pms]
+        nzs = [joint_noise(nzv[b], length(xv[b]), Tg) for b in idx]  # (buffer, CNoise)
+        cnzs = [p[2] for p in nzs]
+        mbufs = [Vector{Tg}(undef, (what & 1) != 0 ? length(xv[b]) : 0) for b in idx]
+        cbufs = [Matrix{Tg}(undef, ((what & 4) != 0 ? (length(xv[b]), length(xv[b])) : (0, 0))...) for b in idx]
+        ysbufs = [(what & 8) != 0 ? Vector{Tg}(ys_heldout[b]) : Tg[] for b in idx]
+        xibufs = [(what & 16) != 0 ? Matrix{Tg}(reshape(xi[b], length(xv[b]), nsamp)) : Matrix{Tg}(undef, 0, 0) for b in idx]
+        sbufs = [Matrix{Tg}(undef, ((what & 16) != 0 ? (length(xv[b]), nsamp) : (0, 0))...) for b in idx]
+        for (j, b) in enumerate(idx)
+            ((what & 8) == 0 || length(ysbufs[j]) == length(xv[b])) || throw(DimensionMismatch("problem $(b): $(length(xv[b])) test points but ys_heldout has $(length(ysbufs[j])) entries"))
+        end
+        moptrs = Ptr{Cvoid}[pointer(v) for v in mbufs]
+        coptrs = Ptr{Cvoid}[pointer(v) for v in cbufs]
+        ysptrs = Ptr{Cvoid}[pointer(v) for v in ysbufs]
+        xiptrs = Ptr{Cvoid}[pointer(v) for v in xibufs]
+        soptrs = Ptr{Cvoid}[pointer(v) for v in sbufs]
+        hl = zeros(Tg, g)
+        out = Vector{Tg}(undef, g)
+        inf = zeros(Int32, g)
+        infj = zeros(Int32, g)
+        GC.@preserve args ybufs cxs cns yptrs mptrs xsp cxss pms pmptrs nzs cnzs mbufs cbufs ysbufs xibufs sbufs moptrs coptrs ysptrs xiptrs soptrs hl out inf infj begin
+            if composite
+                ks = [args[b].ks for b in idx]
+                GC.@preserve ks check(ccall((:gp_joint_batch_sum, libgpmi355), Int32,
+                    (Ptr{Cvoid}, Int32, Ptr{CKSum}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Int32, Ptr{CPoints},
+                     Ptr{Ptr{Cvoid}}, Ptr{CNoise}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}},
+                     Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}),
+                    ctx.handle, g, ks, nx, cxs, cns, mptrs, ny, yptrs, nxs, cxss, pmptrs, cnzs, what, (what & 1) != 0 ? pointer(moptrs) : C_NULL,
+                    (what & 4) != 0 ? pointer(coptrs) : C_NULL, (what & 8) != 0 ? pointer(ysptrs) : C_NULL, (what & 8) != 0 ? pointer(hl) : C_NULL, nsamp,
+                    (what & 16) != 0 ? pointer(xiptrs) : C_NULL, (what & 16) != 0 ? pointer(soptrs) : C_NULL, out, inf, infj))
+            else
+                cks = [args[b].ck for b in idx]
+                GC.@preserve cks check(ccall((:gp_joint_batch, libgpmi355), Int32,
+                    (Ptr{Cvoid}, Int32, Ptr{CKernel}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Int32, Ptr{CPoints},
+                     Ptr{Ptr{Cvoid}}, Ptr{CNoise}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}},
+                     Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}),
+                    ctx.handle, g, cks, nx, cxs, cns, mptrs, ny, yptrs, nxs, cxss, pmptrs, cnzs, what, (what & 1) != 0 ? pointer(moptrs) : C_NULL,
+                    (what & 4) != 0 ? pointer(coptrs) : C_NULL, (what & 8) != 0 ? pointer(ysptrs) : C_NULL, (what & 8) != 0 ? pointer(hl) : C_NULL, nsamp,
+                    (what & 16) != 0 ? pointer(xiptrs) : C_NULL, (what & 16) != 0 ? pointer(soptrs) : C_NULL, out, inf, infj))
+            end
+        end
+        for (j, b) in enumerate(idx)
+            lp[b] = out[j]
+            info[b] = inf[j]
+            infoj[b] = infj[j]
+            (what & 1) != 0 && (means[b] = mbufs[j])
+            (what & 4) != 0 && (covs[b] = cbufs[j])
+            (what & 8) != 0 && (hls[b] = hl[j])
+            (what & 16) != 0 && (draws[b] = sbufs[j])
+        end
+    end
+    bad = findfirst(!=(0), info)
+    (on_error === :raise && bad !== nothing) && throw(BatchPosDefException(Int(info[bad]), bad))
+    badj = findfirst(!=(0), infoj)
+    (on_error === :raise && badj !== nothing) && throw(BatchPosDefException(Int(infoj[badj]), badj))
+    quads = [(means[b], covs[b], hls[b], draws[b]) for b in 1:nb]
+    return return_logpdf ? (quads, lp) : quads
+end
+mean_and_cov_batch(fxs, ys, xs; kw...) = (r = joint_batch(fxs, ys, xs; what=5, kw...); q = r isa Tuple ? r[1] : r; p = [(t[1], t[2]) for t in q]; r isa Tuple ? (p, r[2]) : p)
+logpdf_heldout_batch(fxs, ys, xs, ys_heldout; kw...) = (r = joint_batch(fxs, ys, xs; ys_heldout=ys_heldout, what=8, kw...); q = r isa Tuple ? r[1] : r; p = [t[3] for t in q]; r isa Tuple ? (p, r[2]) : p)
+rand_batch(fxs, ys, xs, xi; kw...) = (r = joint_batch(fxs, ys, xs; xi=xi, what=16, kw...); q = r isa Tuple ? r[1] : r; p = [t[4] for t in q]; r isa Tuple ? (p, r[2]) : p)
 
 # ---- gradients of the batched predictions w.r.t. the test inputs: gp_predict_grad_batch / gp_predict_grad_batch_sum ----------------
 # mean_and_var_grad_batch(fxs, ys, xs): what mean_and_var_batch returns AND the gradients of both sides w.r.t. the test inputs — a gradient-based

@@ -295,7 +295,8 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
  *   "pool_cached_mb", "pool_blocks"   read-only (gp_ctx_get_param): MiB and number of blocks in the cache now
  *   "batch_grad_kernel_problems"      read-only (gp_ctx_get_param): the problems the gradient kernels of gp_logpdf_grad_batch / _sum have served on this ctx
  *                    since it was created (the problems routed to the single path do not count): which path ran, for tests and measurements
- *   "batch_gradx_kernel_problems"     read-only: the same for the input-gradient kernels of gp_logpdf_grad_batch_x / _sum_x (problems whose dx they computed) */
+ *   "batch_gradx_kernel_problems"     read-only: the same for the input-gradient kernels of gp_logpdf_grad_batch_x / _sum_x (problems whose dx they computed)
+ *   "batch_joint_kernel_problems"     read-only: the same for the kernels of gp_joint_batch / _sum */
 /* The defaults above, machine-readable (single-device parameters; gp_ctx_get_param reads the same names): the test-suite asserts before
  * every GPU test that the shared default context still has exactly these values, so that no test can leave a non-production setting
  * behind for the tests that follow it (tests/conftest.py). */
@@ -527,6 +528,61 @@ int32_t gp_predict_grad_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int
                                   const void* const* mean_or_null, int32_t ny, const void* const* y, int32_t nxs, const gp_points* xs,
                                   const void* const* prior_mean_xs_or_null, int32_t what, void* const* mean_out_or_null, void* const* var_out_or_null,
                                   void* const* dmean_out_or_null, void* const* dvar_out_or_null, void* logpdf_out_or_null, int32_t* info_out);
+
+/* The JOINT predictive distribution of the same nb problems at their test points, in ONE call: the latent covariance, the held-out log density
+ * logpdf(post_b(x*_b, Σy*_b), y*_b) — the score of a cross-validation fold, the scoring rule of a grid search — and joint samples rand(post_b(x*_b, Σy*_b)) for
+ * Thompson sampling and q-acquisitions over many surrogates (gp_posterior_fit + gp_posterior_predict(what = 5) / gp_posterior_logpdf / gp_posterior_rand +
+ * gp_posterior_free per problem otherwise).  Per problem the semantics are those of that sequence (src/exact_gpr_posterior.jl:29-35, 78-83;
+ * src/finite_gp_projection.jl:133-136, 233-237, 306-311, 325-326).
+ *   The arguments up to prior_mean_xs_or_null are those of gp_predict_batch (nx, ny, nxs ∈ {1, nb}; ns_b = 0 is legal and touches nothing of that problem but
+ *   its logpdf and info entries).  noise_xs_or_null: nb entries Σy*_b for the ns_b test points of each problem, NULL = zero.
+ *   what: bit 0 the mean; bit 2 the latent covariance K** − VᵀV with no Σy* added, as in gp_posterior_predict; bit 3 the held-out logpdf; bit 4 samples.  Bit 1
+ *   and every other bit are an argument error (marginal variances: gp_predict_batch), and so is 0.
+ *   mean_out_or_null: nb pointers to ns_b entries.  cov_out_or_null: nb pointers to ns_b × ns_b entries, column-major with leading dimension ns_b, both
+ *   triangles written and exactly symmetric.  ys_or_null: nb pointers to the ns_b held-out observations; hlogpdf_out_or_null: nb entries.  xi_or_null /
+ *   samples_out_or_null: nb pointers to ns_b × nsamp entries each, column-major with leading dimension ns_b — the caller's standard normals and the draws, as
+ *   in gp_posterior_rand: out[:, s] = mean + L* xi[:, s] with L* L*ᵀ = C* + Σy* (nsamp >= 0; 0 draws nothing).  The arrays of a bit that is asked for must not be
+ *   NULL (nor their entries where ns_b > 0).  logpdf_out_or_null: the training logpdf, as in gp_predict_batch.  info_out: nb entries, the training
+ *   factorisation; info_joint_out_or_null: nb entries, the order of the first leading minor of C*_b + Σy*_b that is not positive, or 0.
+ * Failure is data: a failed training fit gives NaN in every output of that problem; a failed joint factorisation gives NaN in that problem's held-out logpdf and
+ * samples only — its mean and covariance stay valid.  Other problems are never affected.  The return value reports argument errors only (−i, reason in
+ * gp_last_error(); nb = 0 returns 0 and touches nothing).
+ * fp64 problems with noise kind 0 / 1, D <= 16, n_b <= GPMI355_BATCH_JOINT_MAX_N, ns_b <= GPMI355_BATCH_JOINT_MAX_NS and a Σy*_b that is absent or of kind 0 / 1
+ * run on the batch kernels (csrc/batch.hip), per wave: batch_logpdf_kernel; batch_predict_kernel with one strip per tile of 128 test points, a problem's strips
+ * one behind the other — together V_b = K* L⁻ᵀ; batch_jcov_kernel, one workgroup per 64×64 tile (ti >= tj) of a problem's ns_b × ns_b matrix: K(x*_I, x*_J) from
+ * the packed test points, minus V_I V_Jᵀ by fp64 MFMA, stored into the covariance (tile and mirror image) and, with Σy* on the diagonal, into a joint slice;
+ * batch_jfact_kernel, one workgroup per problem: the blocked Cholesky of batch_logpdf_kernel on the joint slice with δ* = y* − mean riding along, the logpdf off
+ * the carried row, the samples one wave per row.  No atomics, no waits between workgroups: every output is the same bits alone, anywhere in any batch and on
+ * repetition; mean and training logpdf are the bits of gp_predict_batch.  Every other problem is answered inside the same call by the single-path sequence
+ * above; which path serves a problem depends on that problem alone.  The read-only ctx parameter "batch_joint_kernel_problems" counts the problems the kernels
+ * served.
+ * GPMI355_BATCH_JOINT_MAX_N / GPMI355_BATCH_JOINT_MAX_NS: chosen by the rule that fixed the other three — each the largest multiple of 128 of the measured sweep
+ * (tools/batch_joint_profile.py, profiles/r25/batch_joint_profile.json: n = 64 … 2 048 × nb = 1, 8, 64, 512 × ns = 64, 256, 1 024, SE, D = 3, scalar noise, scalar Σy*, what = 29
+ * with 4 samples) at which ONE gp_joint_batch call beat the loop of gp_posterior_fit + gp_posterior_predict(what = 5) + gp_posterior_logpdf + gp_posterior_rand +
+ * gp_posterior_free in every cell with nb >= 8, the loop run twice — on a default ctx and on a ctx with "dib_nb" = 128 — and the faster of the two taken.  The nb = 8 cells
+ * decide MAX_N (the default-ctx loop is the opponent there): 1 536 points win at every ns — 19.84 ms (19.84 – 19.86) against 29.60 ms (29.55 – 29.80) at ns = 64, 31.01 ms
+ * (30.94 – 31.20) against 37.04 ms (36.98 – 37.13) at ns = 1 024 — and 2 048 points lose at every ns: 40.54 ms (40.43 – 40.56) against 27.13 ms (27.07 – 27.21) at ns = 64,
+ * 53.25 against 34.80 ms at ns = 1 024 — eight workgroups factor for longer than eight whole-chip fits take, as in gp_logpdf_batch.  (1 536 is the largest size of the sweep below
+ * 2 048; nothing between them was measured.)  MAX_NS is the top of the sweep: 1 024 test points win every cell with nb >= 8 up to 1 536 points, the closest ones at nb = 8 (1 536 points
+ * as above, a factor 1.19; 128 points 9.71 ms (9.59 – 9.73) against 12.08 ms (12.06 – 12.60), 1.24); more test points were not measured, and the joint slice of a problem is factored by
+ * ONE workgroup, so ns_b is held to what was.  At nb = 64 the call wins every cell by 1.8 (2 048 points, ns = 1 024: 152 against 276 ms) to 118 (64 points, ns = 64), at nb = 512 by
+ * 2.9 to 198 (1 536 points, ns = 1 024: 481 against 2 625 ms); a single problem wins only up to 256 points with 64 test points and up to 128 points with 256, and loses everywhere else
+ * (ns = 1 024: 6.5 against 1.5 ms at 64 points), as in the other batch calls.
+ * (The environment variables GPMI_BATCH_JOINT_MAX_N / GPMI_BATCH_JOINT_MAX_NS, 0 … 2 048 = what the kernels admit, read per call, override them for measurements.) */
+#define GPMI355_BATCH_JOINT_MAX_N 1536
+#define GPMI355_BATCH_JOINT_MAX_NS 1024
+int32_t gp_joint_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                       const void* const* mean_or_null, int32_t ny, const void* const* y, int32_t nxs, const gp_points* xs,
+                       const void* const* prior_mean_xs_or_null, const gp_noise* noise_xs_or_null, int32_t what, void* const* mean_out_or_null,
+                       void* const* cov_out_or_null, const void* const* ys_or_null, void* hlogpdf_out_or_null, int32_t nsamp, const void* const* xi_or_null,
+                       void* const* samples_out_or_null, void* logpdf_out_or_null, int32_t* info_out, int32_t* info_joint_out_or_null);
+/* The same with one composite kernel (gp_ksum) per problem. */
+int32_t gp_joint_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                           const void* const* mean_or_null, int32_t ny, const void* const* y, int32_t nxs, const gp_points* xs,
+                           const void* const* prior_mean_xs_or_null, const gp_noise* noise_xs_or_null, int32_t what, void* const* mean_out_or_null,
+                           void* const* cov_out_or_null, const void* const* ys_or_null, void* hlogpdf_out_or_null, int32_t nsamp,
+                           const void* const* xi_or_null, void* const* samples_out_or_null, void* logpdf_out_or_null, int32_t* info_out,
+                           int32_t* info_joint_out_or_null);
 
 /* The training half of the batch calls: value AND gradient of logpdf for the same nb problems in ONE call — what multi-start hyper-parameter
  * optimisation, gradient-based samplers over hyper-parameters, per-fold training and independent outputs sharing one x evaluate at every step (one
