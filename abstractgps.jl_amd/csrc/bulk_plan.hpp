@@ -11,6 +11,10 @@
 //   instead of four launches per block: four partly filled last rounds of workgroups per update, however deep the split.  Every quadrant still
 //   receives its products in the fixed order; no tile's arithmetic changes.  All blocks of an update are live at once, so each has its own slice
 //   of sum panels.
+//
+//   U1, the update of the next panel's columns, is the same kind of update with a square that is never split and a tall rectangle below it: u1_plan_build
+//   puts the rectangle's whole quadrants through the same Builder::strassen and the rest through the same classical pieces and the same four lists
+//   (tests/u1_plan_check.cpp).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -134,20 +138,21 @@ struct Builder {
         p.ungrouped.push_back(PlanLaunch{0, mh, nh, kh, 1, 0});
         for (int i = 0; i < 3; ++i) p.ungrouped.push_back(PlanLaunch{0, mh, nh, kh, 2, 0});
     }
+    // one classical lower piece: the square of side m at offset roff on the update's diagonal with the mrows − m rows below it
+    void leaf(long roff, long mrows, long m) {
+        PlanProb e{};
+        e.c_off = roff * p.ldc + roff; e.a_off = roff * p.ldp; e.b_off = roff * p.ldp;
+        e.M = mrows; e.N = m; e.K = p.K;
+        e.lower = 1; e.roff = roff;
+        e.block = -1;
+        classical.push_back(e);
+        p.ungrouped.push_back(PlanLaunch{0, mrows, m, p.K, 1, 1});
+    }
     // the square of side m at offset roff on the update's diagonal, mrows >= m rows in all (syrk_lower_split)
     void syrk(long roff, long mrows, long m) {
         const long K = p.K, ldc = p.ldc, ldp = p.ldp;
         const long h = strassen_split_rule(min_rows, m, K);
-        if (h == 0) {
-            PlanProb e{};
-            e.c_off = roff * ldc + roff; e.a_off = roff * ldp; e.b_off = roff * ldp;
-            e.M = mrows; e.N = m; e.K = K;
-            e.lower = 1; e.roff = roff;
-            e.block = -1;
-            classical.push_back(e);
-            p.ungrouped.push_back(PlanLaunch{0, mrows, m, K, 1, 1});
-            return;
-        }
+        if (h == 0) return leaf(roff, mrows, m);
         const long b = m - h, bs = b / 256 * 256;  // rows below the split; the Strassen block takes whole 256-row pieces of them
         syrk(roff, h, h);
         strassen((roff + h) * ldc + roff, (roff + h) * ldp, roff * ldp, bs, h);
@@ -156,15 +161,8 @@ struct Builder {
         if (mrows > m) rect((roff + m) * ldc + roff, (roff + m) * ldp, roff * ldp, mrows - m, m);
     }
 };
-}  // namespace plan_detail
-
-// The plan of C(mrows × m; the m×m square lower, at row0 on the global diagonal) −= P·P[0:m]ᵀ, P = mrows × K.  min_rows: "strassen_min_rows".
-static inline BulkPlan bulk_plan_build(long mrows, long m, long K, long row0, long ldc, long ldp, long min_rows, long ldpad) {
-    BulkPlan p;
-    p.mrows = mrows; p.m = m; p.K = K; p.row0 = row0; p.ldc = ldc; p.ldp = ldp;
-    p.lds = K / 2 + ldpad;
-    plan_detail::Builder bd{p, min_rows, ldpad, {}};
-    bd.syrk(0, mrows, m);
+// The four lists of a plan from the builder's products and classical pieces: balance, order, tile prefix sums, flops and bytes per launch.
+static inline void finish(BulkPlan& p, Builder& bd, long row0) {
     // The classical pieces write parts of C nothing else of the update touches: each goes to the launch with the least work so far (tiles × k steps),
     // largest first.  Launch 1 holds one product per block against two in the others, so it takes most of them.
     double work[4];
@@ -199,6 +197,43 @@ static inline BulkPlan bulk_plan_build(long mrows, long m, long K, long row0, lo
         }
         p.ntiles[l] = t;
     }
+}
+}  // namespace plan_detail
+
+// The plan of C(mrows × m; the m×m square lower, at row0 on the global diagonal) −= P·P[0:m]ᵀ, P = mrows × K.  min_rows: "strassen_min_rows".
+static inline BulkPlan bulk_plan_build(long mrows, long m, long K, long row0, long ldc, long ldp, long min_rows, long ldpad) {
+    BulkPlan p;
+    p.mrows = mrows; p.m = m; p.K = K; p.row0 = row0; p.ldc = ldc; p.ldp = ldp;
+    p.lds = K / 2 + ldpad;
+    plan_detail::Builder bd{p, min_rows, ldpad, {}};
+    bd.syrk(0, mrows, m);
+    plan_detail::finish(p, bd, row0);
+    return p;
+}
+
+// U1, the update of the next panel's columns: C(mrows × nb1; the nb1×nb1 square lower, at row0 on the global diagonal) −= P·P[0:nb1]ᵀ, P = mrows × K.
+// Below the square lie the mrect rows of the matrix under the next panel and then the carried right-hand-side rows.  The whole 256-row quadrants of
+// the rectangle (rows [nb1, nb1 + bs), bs = mrect rounded down to 256) are ONE Strassen block — A = P from row nb1 on, B = P[0:nb1] — when that
+// block has at least u1_min_rows rows ("strassen_u1_min_rows"; 0: never), the panel at least u1_min_k columns ("strassen_u1_min_k": what a half-size
+// product costs beyond its flops does not shrink with K/2) and the block the Strassen shape.
+static inline long u1_block_rows(long u1_min_rows, long u1_min_k, long mrect, long nb1, long K) {
+    const long bs = mrect / 256 * 256;
+    return u1_min_rows > 0 && bs >= u1_min_rows && K >= u1_min_k && strassen_shape_rule(256, bs, nb1, K) ? bs : 0;
+}
+// The plan of U1 in that form: the square stays one classical lower piece, the block goes through Builder::strassen (the sums, products, signs, targets
+// and launch order of every other block), the remainder strip and the carried rows are classical rectangles; finish() balances them over the same four
+// lists.  Call it only where u1_block_rows() > 0.
+static inline BulkPlan u1_plan_build(long mrows, long mrect, long nb1, long K, long row0, long ldc, long ldp, long ldpad) {
+    BulkPlan p;
+    p.mrows = mrows; p.m = nb1; p.K = K; p.row0 = row0; p.ldc = ldc; p.ldp = ldp;
+    p.lds = K / 2 + ldpad;
+    plan_detail::Builder bd{p, 256, ldpad, {}};
+    const long bs = mrect / 256 * 256, carried = mrows - nb1 - mrect;
+    bd.leaf(0, nb1, nb1);
+    bd.strassen(nb1 * ldc, nb1 * ldp, 0, bs, nb1);
+    bd.rect((nb1 + bs) * ldc, (nb1 + bs) * ldp, 0, mrect - bs, nb1);
+    bd.rect((nb1 + mrect) * ldc, (nb1 + mrect) * ldp, 0, carried, nb1);
+    plan_detail::finish(p, bd, row0);
     return p;
 }
 

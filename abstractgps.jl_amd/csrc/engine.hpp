@@ -107,6 +107,8 @@ struct gp_ctx {
     long nb = -1;          // outer panel width: −1 automatic (nb_small below lookahead_min_n — one-stream schedule, wider panels halve the passes over the
                            // trailing matrix — nb_large from there on), 0 purely recursive, > 0 that width at every size
     long nb_small = 4096, nb_large = 2048;
+    long nb_huge = 4096, nb_huge_min_n = 49152;  // third automatic tier: nb_huge from padded order nb_huge_min_n on (0: no such tier) — the bulk update's Strassen products then
+                                             // run at K/2 = 2 048, where their K-independent overhead weighs half as much (profiles/r26/nb_sweep.txt)
     int lookahead = 1;
     long lookahead_min_n = 24576;  // the look-ahead pays from here on (N <= 16 384: 0.5-3 % slower with it since the register-resident leaf; measured round 4)
     int time_kernels = 0;
@@ -156,6 +158,9 @@ struct gp_ctx {
                                      // (bulk_plan.hpp, kernels.hpp gemm_nt_grp_kernel) instead of four launches per Strassen block and one per classical piece.
     long strassen_group_min_rows = 8192;  // The grouped form is taken when the side m of the update is at least this; below it, with strassen_group = 0 and with
                                           // "xcd_swizzle" set (the grouped kernel has no super-tile order) the per-block launch sequence runs unchanged.
+    long strassen_u1_min_rows = 16384;  // U1 (the update of the next panel's columns) with its rectangle below the panel's square as ONE Strassen block in four grouped
+                                        // launches (bulk_plan.hpp u1_plan_build) when the block has at least this many rows (0: the single launch U1 always was) ...
+    long strassen_u1_min_k = 4096;      // ... and the panel (the K of U1) at least this many columns: at K = 2 048 the form loses (C3's size 180.5 -> 182.1 ms, profiles/r26/bench_c2_c3_ab.txt)
     void* plan_pin = nullptr;        // page-locked staging of the problem tables of one call (uploaded by ONE async copy; reused once plan_ev has passed)
     size_t plan_pin_bytes = 0;
     hipEvent_t plan_ev = nullptr;

@@ -455,6 +455,14 @@ struct PlanTables {
         ws_elems = std::max(ws_elems, u.plan.ws_elems);
         upd.push_back(std::move(u));
     }
+    // U1 of a panel step in the Strassen form (bulk_plan.hpp u1_plan_build): an update like the others — same tables, same upload, same run_grouped
+    void add_u1(const gp_ctx* c, long mrows, long mrect, long nb1, long K, long row0, long ldc, const double* P, long ldp) {
+        GroupedUpdate u;
+        u.plan = u1_plan_build(mrows, mrect, nb1, K, row0, ldc, ldp, c->ldpad);
+        u.P = P;
+        ws_elems = std::max(ws_elems, u.plan.ws_elems);
+        upd.push_back(std::move(u));
+    }
     // the table entries (absolute pointers) and their upload on stream s, in front of everything that reads them
     int32_t upload(gp_ctx* c, hipStream_t s, DevBufs& bufs, const std::vector<double*>& Cs, const double* ws) {
         for (size_t i = 0; i < upd.size(); ++i)
@@ -915,9 +923,11 @@ static int32_t potrf_full_la(gp_ctx* c, T* A, long lda, long np, long mtot, int*
     // "strassen_min_rows_large": the Strassen threshold of the large fits — the ones that take the look-ahead schedule — unless the caller chose one
     c->strassen_v = (!c->strassen_min_rows_set && np >= c->lookahead_min_n) ? c->strassen_min_rows_large : c->strassen_min_rows;
     // below the look-ahead threshold the schedule is one stream anyway: panels of "nb_small" (4 096) columns halve the passes over the trailing matrix
-    // (K = 4 096 updates) — C2 29.8-30.1 -> 29.0-29.2 ms on two boxes, N = 8 192 6.51 -> 6.43 (profiles/r5/nb_sweep.txt); from the threshold on the
-    // widths measure within ± 0.5 % of each other ("nb_large" = 2 048).  An explicit "nb" >= 0 applies to every size.
-    if (nb < 0) nb = np < c->lookahead_min_n ? c->nb_small : c->nb_large;  // "nb" = −1: automatic
+    // (K = 4 096 updates) — C2 29.8-30.1 -> 29.0-29.2 ms on two boxes, N = 8 192 6.51 -> 6.43 (profiles/r5/nb_sweep.txt); from the threshold on
+    // "nb_large" = 2 048 (C3's size: 2 048 and 4 096 measure the same, 3 072 and 6 144 slower).  An explicit "nb" >= 0 applies to every size.
+    // From "nb_huge_min_n" on (0: no such tier) "nb_huge": the Strassen products of the bulk update then run at K/2 = nb_huge/2, and what a product costs
+    // beyond its flops — the dual-target epilogue, the partly filled last round of a launch — does not grow with K (profiles/r26/nb_sweep.txt).
+    if (nb < 0) nb = (c->nb_huge_min_n > 0 && np >= c->nb_huge_min_n) ? c->nb_huge : np < c->lookahead_min_n ? c->nb_small : c->nb_large;  // "nb" = −1: automatic
     if (nb <= 0 || nb >= np) return potrf_rec<T>(c, c->sm, A, lda, 0, np, mtot, info_dev, 0, n_valid, logdet_dev);
     nb = round_up(nb, 128);
     const bool la = c->lookahead != 0 && np >= c->lookahead_min_n;
@@ -926,6 +936,7 @@ static int32_t potrf_full_la(gp_ctx* c, T* A, long lda, long np, long mtot, int*
     StrassenWs ws;  // one workspace of sum panels per fit, sized for the update that needs most; every launch that touches it is ordered on the main stream
     PlanTables tabs;          // the grouped bulk updates of the fit, planned and uploaded before the first panel
     std::vector<long> gidx;   // per panel step: index into tabs.upd, −1: the per-block launch sequence
+    std::vector<long> uidx;   // per panel step: index into tabs.upd of U1 in the Strassen form ("strassen_u1_min_rows"), −1: the single launch
     if constexpr (std::is_same<T, double>::value) {
         if (bufs) {
             size_t el = 0;
@@ -934,8 +945,17 @@ static int32_t potrf_full_la(gp_ctx* c, T* A, long lda, long np, long mtot, int*
                 const long nbk = std::min(nb, np - k), k1 = k + nbk;
                 if (k1 >= np) break;
                 const long k2 = k1 + std::min(nb, np - k1);
-                long gi = -1;
+                long gi = -1, ui = -1;
                 if (k2 < np) {
+                    // U1's rectangle below the next panel's square as one Strassen block.  Its sum panels share the fit's workspace with the bulk update of
+                    // the same step: U1's sums and four launches, then the bulk update's, all on the main stream, in order.
+                    const double* P1 = A + k1 * lda + k;
+                    if (c->strassen_v > 0 && !c->xcd_swizzle && lda % 2 == 0 && ((uintptr_t)P1 & 15) == 0 &&
+                        u1_block_rows(c->strassen_u1_min_rows, c->strassen_u1_min_k, np - k2, k2 - k1, nbk) > 0) {
+                        ui = (long)tabs.upd.size();
+                        tabs.add_u1(c, mtot - k1, np - k2, k2 - k1, nbk, k1, lda, P1, lda);
+                        Cs.push_back(A + k1 * lda + k1);
+                    }
                     const double* P = A + k2 * lda + k;
                     if (group_applies(c, np - k2, nbk, lda, P)) {
                         gi = (long)tabs.upd.size();
@@ -945,6 +965,7 @@ static int32_t potrf_full_la(gp_ctx* c, T* A, long lda, long np, long mtot, int*
                         el = std::max(el, syrk_split_ws_elems(c, np - k2, nbk));
                 }
                 gidx.push_back(gi);
+                uidx.push_back(ui);
             }
             el = std::max(el, tabs.ws_elems);
             if (el) {
@@ -973,8 +994,17 @@ static int32_t potrf_full_la(gp_ctx* c, T* A, long lda, long np, long mtot, int*
         if (k1 >= np) break;  // RHS rows were already solved inside potrf_rec
         const long nb1 = std::min(nb, np - k1);
         // U1: next panel's columns, all rows below
-        RC(launch_gemm<T>(c, sM, A + k1 * lda + k1, lda, A + k1 * lda + k, lda, A + k1 * lda + k, lda, mtot - k1, nb1, nbk, plain_map(1, k1, k1)));
-        if (la) {
+        bool u1_grouped = false;
+        if constexpr (std::is_same<T, double>::value) {
+            const size_t step = (size_t)(k / nb);
+            if (step < uidx.size() && uidx[step] >= 0) {
+                RC(run_grouped(c, sM, tabs, (size_t)uidx[step], ws.p));
+                u1_grouped = true;
+            }
+        }
+        if (!u1_grouped)
+            RC(launch_gemm<T>(c, sM, A + k1 * lda + k1, lda, A + k1 * lda + k, lda, A + k1 * lda + k, lda, mtot - k1, nb1, nbk, plain_map(1, k1, k1)));
+        if (la) {  // the panel stream goes on after U1's last launch
             RC(ctx_event(c, &ev_u1, false));
             HIPCHK(hipEventRecord(ev_u1, sM));
             HIPCHK(hipStreamWaitEvent(sP, ev_u1, 0));
@@ -2267,6 +2297,8 @@ int32_t gp_ctx_set_param(gp_ctx* c, const char* name, int64_t v) {
     if (!strcmp(name, "nb")) c->nb = v < 0 ? -1 : (v == 0 ? 0 : round_up(v, 128));
     else if (!strcmp(name, "nb_small")) c->nb_small = (v <= 0) ? 0 : round_up(v, 128);
     else if (!strcmp(name, "nb_large")) c->nb_large = (v <= 0) ? 0 : round_up(v, 128);
+    else if (!strcmp(name, "nb_huge")) c->nb_huge = (v <= 0) ? 0 : round_up(v, 128);
+    else if (!strcmp(name, "nb_huge_min_n")) c->nb_huge_min_n = std::max<int64_t>(0, v);
     else if (!strcmp(name, "lookahead")) c->lookahead = v != 0;
     else if (!strcmp(name, "lookahead_min_n")) c->lookahead_min_n = std::max<int64_t>(0, v);
     else if (!strcmp(name, "time_kernels")) c->time_kernels = v != 0;
@@ -2275,6 +2307,8 @@ int32_t gp_ctx_set_param(gp_ctx* c, const char* name, int64_t v) {
         c->strassen_min_rows = v <= 0 ? 0 : round_up(v, 256);
         c->strassen_min_rows_set = true;  // from here on it applies at every size ("strassen_min_rows_large" no longer does)
     } else if (!strcmp(name, "strassen_min_rows_large")) c->strassen_min_rows_large = v <= 0 ? 0 : round_up(v, 256);
+    else if (!strcmp(name, "strassen_u1_min_rows")) c->strassen_u1_min_rows = v <= 0 ? 0 : round_up(v, 256);
+    else if (!strcmp(name, "strassen_u1_min_k")) c->strassen_u1_min_k = std::max<int64_t>(0, v);
     else if (!strcmp(name, "strassen_group")) c->strassen_group = v != 0;
     else if (!strcmp(name, "strassen_group_min_rows")) c->strassen_group_min_rows = std::max<int64_t>(256, round_up(v, 256));
     else if (!strcmp(name, "gemm_streamk")) c->gemm_streamk = v != 0;
@@ -2339,7 +2373,7 @@ int32_t gp_ctx_get_param(gp_ctx* c, const char* name, int64_t* out) {
         return 0;
     }
     const struct { const char* n; int64_t v; } tab[] = {
-        {"nb", c->nb}, {"nb_small", c->nb_small}, {"nb_large", c->nb_large}, {"lookahead", c->lookahead}, {"lookahead_min_n", c->lookahead_min_n}, {"time_kernels", c->time_kernels},
+        {"nb", c->nb}, {"nb_small", c->nb_small}, {"nb_large", c->nb_large}, {"nb_huge", c->nb_huge}, {"nb_huge_min_n", c->nb_huge_min_n}, {"strassen_u1_min_rows", c->strassen_u1_min_rows}, {"strassen_u1_min_k", c->strassen_u1_min_k}, {"lookahead", c->lookahead}, {"lookahead_min_n", c->lookahead_min_n}, {"time_kernels", c->time_kernels},
         {"xcd_swizzle", c->xcd_swizzle}, {"strassen_min_rows", c->strassen_min_rows}, {"strassen_min_rows_large", c->strassen_min_rows_large}, {"strassen_group", c->strassen_group}, {"strassen_group_min_rows", c->strassen_group_min_rows}, {"xcd_min_tiles", c->xcd_min_tiles}, {"gemm_streamk", c->gemm_streamk},
         {"sk_max_tiles", c->sk_max_tiles}, {"sk_min_k", c->sk_min_k}, {"gemm_pipe", c->gemm_pipe}, {"gemm_pad_f32", c->gemm_pad_f32},
         {"gemm_pad_lds", c->gemm_pad_user ? c->gemm_pad_lds : 0}, {"trsv_nb", c->trsv_nb},  {"deterministic", c->deterministic},

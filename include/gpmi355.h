@@ -190,10 +190,14 @@ int32_t gp_multi_schedule_trace(int32_t P, int32_t Q, int32_t nblk, int32_t dept
 int32_t gp_ctx_destroy(gp_ctx* ctx);
 /* Tuning / diagnostic parameters (all optional; the GPMI_PARAMS="name=value,..." environment variable applies the same
  * names at gp_ctx_create):
- *   "nb"             outer panel width: −1 = automatic ("nb_small" for matrices below "lookahead_min_n", "nb_large" from there on), 0 = purely
+ *   "nb"             outer panel width: −1 = automatic ("nb_small" for matrices below "lookahead_min_n", "nb_large" from there on, "nb_huge" from "nb_huge_min_n" on), 0 = purely
  *                    recursive, > 0 = that width (multiple of 128) at every size                default −1
  *   "nb_small", "nb_large"  the automatic widths: below the look-ahead threshold the schedule is one stream and 4 096-column panels halve the
  *                    passes over the trailing matrix (C2 −2.5 %); above it 2 048 / 4 096 / 8 192 measure within ± 0.5 %   default 4096, 2048
+ *   "nb_huge", "nb_huge_min_n"  third automatic tier: fits of padded order >= nb_huge_min_n take panels of nb_huge columns whatever the two widths above say.
+ *                    The Strassen products of the bulk update then run at K/2 = nb_huge/2, and what a product costs beyond its flops does not grow with K: at
+ *                    N = 65 536 4 096 measures 1.8 % faster than 2 048, 3 072 and 6 144 in between; at N = 32 768 4 096 and 2 048 measure the same and the other
+ *                    two slower (profiles/r26/nb_sweep.txt), hence the floor between the two sizes; nb_huge_min_n = 0: no such tier   default 4096, 49152
  *   "lookahead"      next panel on a second, high-priority stream (0/1)                   default 1
  *   "lookahead_min_n" ... for matrices of at least this (padded) order                    default 24576
  *   "time_kernels"   bracket every MFMA GEMM launch with HIP events (gp_get_timings)      default 0
@@ -208,6 +212,13 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
  *                    parts of C — instead of four launches per block and one per piece (csrc/bulk_plan.hpp, gemm_nt_grp_kernel: a device table of
  *                    problems per launch, no atomics, bitwise equal to the per-block sequence under "deterministic"); every block then has its own
  *                    sum panels.  0 / below the floor / with "xcd_swizzle": the per-block sequence.  The floor is rounded up to 256 and is at least 256   default 1, 8192
+ *   "strassen_u1_min_rows", "strassen_u1_min_k"  fp64 exact fits: U1, the update of the next panel's columns, is one launch over a lower trapezoid.  With this set, the whole 256-row
+ *                    quadrants of its rectangle below the panel's square run as ONE Strassen block when they are at least strassen_u1_min_rows rows (rounded up to 256), the
+ *                    panel — the K of this update — has at least strassen_u1_min_k columns and
+ *                    "strassen_min_rows" of the fit is not 0: the square, the remainder strip and the carried rows stay classical, and all of it runs as four
+ *                    grouped launches after two sums launches (csrc/bulk_plan.hpp u1_plan_build); 0 = the single launch.  At N = 65 536 with 4 096-column
+ *                    panels floors of 8 192 and 16 384 measure the same, 0.9 % faster than the single launch, 32 768 half of that (profiles/r26/u1_floor_sweep.txt); with 2 048-column panels the form is 0.9 % SLOWER at
+ *                    N = 32 768 (profiles/r26/bench_c2_c3_ab.txt: halves of K/2 = 1 024), hence the floor on K   default 16384, 4096
  *   "gemm_streamk"   persistent-grid GEMM with a stream-K tail on launches of <= sk_max_tiles tiles   default 1
  *                    (0 in the rank contexts of a multi-device ctx: "multi_gemm_streamk").  The tail adds its k-slices into C with
  *                    hardware floating-point atomics, so the order of summation depends on scheduling: results agree with the
@@ -301,7 +312,7 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
  * every GPU test that the shared default context still has exactly these values, so that no test can leave a non-production setting
  * behind for the tests that follow it (tests/conftest.py). */
 #define GPMI355_PARAM_DEFAULTS                                                                                                   \
-    "nb=-1,nb_small=4096,nb_large=2048,lookahead=1,lookahead_min_n=24576,time_kernels=0,xcd_swizzle=0,xcd_min_tiles=256,gemm_streamk=1,sk_max_tiles=4096," \
+    "nb=-1,nb_small=4096,nb_large=2048,nb_huge=4096,nb_huge_min_n=49152,strassen_u1_min_rows=16384,strassen_u1_min_k=4096,lookahead=1,lookahead_min_n=24576,time_kernels=0,xcd_swizzle=0,xcd_min_tiles=256,gemm_streamk=1,sk_max_tiles=4096," \
     "sk_min_k=0,gemm_pipe=1,gemm_pad_f32=0,gemm_pad_lds=0,trsv_nb=256,deterministic=0,leaf_v2=1,leaf_xr=0,leaf_cols=128,"    \
     "updk_max_k=512,updk_rt=0,updk_tall_k=256,updk_tall_m=8192,upd128=1,leaf_group=128,ldpad=32,vfe_ks=2048,vfe_sk=0,"          \
     "vfe_overlap=1,vfe_dual=0,vfe_inv_nb=512,vfe_chunk=0,kmat_rows=1,dib_nb=2048,pool_cap_mb=98304,dense_stage_mb=64,alloc_poison=0,strassen_min_rows=8192,strassen_min_rows_large=4096,strassen_group=1,strassen_group_min_rows=8192"
