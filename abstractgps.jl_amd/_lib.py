@@ -84,6 +84,12 @@ PROTOTYPES = {
     "gp_logpdf_grad_sum": (i32, [vp, PS, PP, PN, vp, vp, vp, C.POINTER(dbl), vp, vp]),
     "gp_logpdf_grad_sum_x": (i32, [vp, PS, PP, PN, vp, vp, vp, C.POINTER(dbl), vp, vp, vp]),
     "gp_logpdf_terms_sum": (i32, [vp, PS, PP, PN, vp, vp, i64, i32, vp, vp]),
+    "gp_posterior_fit_cols": (i32, [vp, PK, PP, PN, vp, vp, i64, i32, C.POINTER(vp), vp, vp]),
+    "gp_posterior_fit_cols_sum": (i32, [vp, PS, PP, PN, vp, vp, i64, i32, C.POINTER(vp), vp, vp]),
+    "gp_posterior_ncols": (i32, [vp, C.POINTER(i32)]),
+    "gp_posterior_predict_cols": (i32, [vp, PP, vp, i32, vp, vp, vp]),
+    "gp_logpdf_grad_cols": (i32, [vp, PK, PP, PN, vp, vp, i64, i32, vp, C.POINTER(dbl), C.POINTER(dbl), vp, vp, vp]),
+    "gp_logpdf_grad_cols_sum": (i32, [vp, PS, PP, PN, vp, vp, i64, i32, vp, C.POINTER(dbl), vp, vp, vp]),
     "gp_logpdf_batch": (i32, [vp, i32, PK, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp)]),
     "gp_logpdf_batch_sum": (i32, [vp, i32, PS, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp)]),
     "gp_predict_batch": (i32, [vp, i32, PK, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), i32, PP, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp), vp,
@@ -164,6 +170,11 @@ def header_functions() -> list[str]:
 def batch_max_n() -> int:
     """GPMI355_BATCH_MAX_N of include/gpmi355.h: the largest problem gp_logpdf_batch hands to its batch kernel."""
     return int(re.search(r"#define GPMI355_BATCH_MAX_N (\d+)", HEADER.read_text()).group(1))
+
+
+def cols_max() -> int:
+    """GPMI355_COLS_MAX of include/gpmi355.h: the most columns of Y one gp_posterior_fit_cols / gp_logpdf_grad_cols call takes."""
+    return int(re.search(r"#define GPMI355_COLS_MAX (\d+)", HEADER.read_text()).group(1))
 
 
 def batch_grad_max_n() -> int:

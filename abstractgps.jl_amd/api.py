@@ -1530,6 +1530,169 @@ def _posterior_exact(fx: FiniteGP, y, zero_mean: bool = False) -> PosteriorGP:
     return PosteriorGP(f, _PostData(alpha, _Factor(ctx, h, px.n, dt), fx.x, delta), lp[0])
 
 
+# --------------------------------------------------------------------------------------------
+# one factorisation for a matrix of observations: gp_posterior_fit_cols / gp_posterior_predict_cols / gp_logpdf_grad_cols
+# --------------------------------------------------------------------------------------------
+@dataclass(eq=False)
+class _ColsCall:
+    """The arguments of a *_cols call, built without a context (tests/test_cols_cpu.py reads them)."""
+    dt: type
+    m: _Marshal
+    px: gp_points
+    sfx: str            # "" or "_sum"
+    kk: object          # gp_kernel or gp_ksum
+    nf: object          # _NormalForm of a composite kernel, else None
+    nz: gp_noise
+    mean: Optional[np.ndarray]  # the ONE prior-mean vector every column shares
+    Y: np.ndarray       # (n, S), column-major
+    ldy: int
+    ncols: int
+
+
+def _cols_marshal(fx: FiniteGP, Y, name: str) -> _ColsCall:
+    Y = _check_y(fx, Y)
+    if Y.ndim != 2:
+        raise TypeError(f"{name} expects an (n, S) matrix of observations, one GP per column; a vector goes to its single-column counterpart")
+    f = fx.f
+    if not isinstance(f, GP):
+        raise TypeError(f"{name}: the prior must be a GP (sequential conditioning of column posteriors is not offered)")
+    if not 1 <= Y.shape[1] <= _lib.cols_max():
+        raise ValueError(f"{name}: {Y.shape[1]} columns, 1..{_lib.cols_max()} (GPMI355_COLS_MAX) fit one call: split them into groups")
+    dt = np.result_type(_input_dtype(fx.x), np.float32 if Y.dtype == np.float32 else np.float64).type
+    m = _Marshal(dt)
+    px = m.points(fx.x)
+    nf = None
+    if _is_composite(f.kernel):
+        sfx = "_sum"
+        kk, nf = m.ksum(f.kernel, px.d)
+    else:
+        sfx, kk = "", m.kernel(f.kernel, px.d)
+    nz = m.noise(fx.sigma2, px.n)
+    mean = _mean_vector(f.mean_fn, fx.x, dt)
+    mean = None if mean is None else m.arr(mean)
+    # a column-major array of the right dtype goes as it lies — the leading rows of a taller column-major array included (ldy = its column stride)
+    it = Y.itemsize
+    if Y.dtype == dt and Y.strides[0] == it and Y.strides[1] % it == 0 and Y.strides[1] // it >= max(Y.shape[0], 1) and Y.shape[1] > 1:
+        Yf, ldy = Y, Y.strides[1] // it
+    else:
+        Yf = m.arr(Y, order="F")
+        ldy = Yf.shape[0]
+    m.keep.append(Yf)
+    return _ColsCall(dt, m, px, sfx, kk, nf, nz, mean, Yf, ldy, Yf.shape[1])
+
+
+@dataclass
+class _ColsData:
+    alpha: np.ndarray  # (n, S): α_s = C \ (Y[:, s] − m)
+    C: _Factor
+    x: object
+    delta: np.ndarray  # (n, S)
+
+
+class ColumnsPosteriorGP(AbstractGP):
+    """S posteriors that share x, kernel, Σy and the prior mean and differ in y (the columns of Y): ONE device-resident factor, α for every column.
+    mean(x) is (ns, S); var / cov do not depend on y and are those of every column."""
+
+    def __init__(self, prior: GP, data: _ColsData, logpdf_values):
+        self.prior, self.data, self.logpdf_values = prior, data, logpdf_values
+
+    @property
+    def ncols(self) -> int:
+        out = C.c_int32()
+        check(self.data.C.ctx.lib.gp_posterior_ncols(self.data.C.handle, C.byref(out)))
+        return out.value
+
+    def _predict(self, x, what):
+        ctx, dt = self.data.C.ctx, self.data.C.dtype
+        m = _Marshal(dt)
+        px = m.points(x)
+        ns, S = px.n, self.data.alpha.shape[1]
+        pm = _mean_vector(self.prior.mean_fn, x, dt)
+        pm = None if pm is None else m.arr(pm)
+        mean = np.empty((ns, S), dtype=dt, order="F") if what & 1 else None
+        var = np.empty(ns, dtype=dt) if what & 2 else None
+        cov = np.empty((ns, ns), dtype=dt, order="F") if what & 4 else None
+        check(ctx.lib.gp_posterior_predict_cols(self.data.C.handle, C.byref(px), m.ptr(pm), what, m.ptr(mean), m.ptr(var), m.ptr(cov)))
+        return mean, var, cov
+
+    def mean(self, x=None):
+        if x is None:
+            return super().mean()
+        return self._predict(x, 1)[0]
+
+    def var(self, x):
+        return self._predict(x, 2)[1]
+
+    def cov(self, x, z=None):
+        if z is not None:
+            raise TypeError("cov(f, x, z) is not offered for a column posterior: take the block of cov(f, [x; z])")
+        return self._predict(x, 4)[2]
+
+    def mean_and_var(self, x):
+        m, v, _ = self._predict(x, 3)
+        return m, v
+
+    def mean_and_cov(self, x):
+        m, _, c = self._predict(x, 5)
+        return m, c
+
+    def _one_column_only(self, *a, **k):
+        raise TypeError("a column posterior holds one mean per column: this method needs a single-column posterior (posterior(fx, Y[:, s]))")
+
+    mean_and_var_grad = mean_grad = _one_column_only
+
+    def var_grad(self, x):
+        """(var, ∂var/∂x): the variance side uses no α."""
+        r = _predict_grad(self.data.C.ctx.lib.gp_posterior_predict_grad, self.data.C.handle, self.data.C.dtype, self.prior.mean_fn, x, 2)
+        return r[1], r[3]
+
+    def __call__(self, x, sigma2=default_sigma2):
+        raise TypeError("a FiniteGP over a column posterior (held-out logpdf, samples, sequential conditioning) is not offered: use posterior(fx, Y[:, s])")
+
+
+def posterior_columns(fx: FiniteGP, Y) -> ColumnsPosteriorGP:
+    """posterior(fx, Y[:, s]) for every column s of the (n, S) matrix Y from ONE Gram assembly and ONE factorisation (gp_posterior_fit_cols; S <= 128).
+    .data.alpha is (n, S), .logpdf_values (S,) = logpdf(fx, Y)."""
+    a = _cols_marshal(fx, Y, "posterior_columns")
+    f = fx.f
+    ctx = f.context()
+    delta = np.asfortranarray(a.Y - a.mean[:, None] if a.mean is not None else a.Y.copy(order="F"))
+    alpha = np.empty((a.px.n, a.ncols), dtype=a.dt, order="F")
+    lp = np.empty(a.ncols, dtype=a.dt)
+    h = C.c_void_p()
+    check(getattr(ctx.lib, "gp_posterior_fit_cols" + a.sfx)(ctx.handle, C.byref(a.kk), C.byref(a.px), C.byref(a.nz), a.m.ptr(a.mean), a.Y.ctypes.data, a.ldy,
+                                                            a.ncols, C.byref(h), alpha.ctypes.data, lp.ctypes.data))
+    return ColumnsPosteriorGP(f, _ColsData(alpha, _Factor(ctx, h, a.px.n, a.dt), fx.x, delta), lp)
+
+
+def logpdf_and_grad_columns(fx: FiniteGP, Y, wrt_x: bool = False) -> tuple:
+    """(logpdf(fx, Y[:, s]) for every s, gradient of their SUM) from one factorisation and one C⁻¹ (gp_logpdf_grad_cols / _sum; S <= 128).  The keys of
+    the gradient are those of logpdf_and_grad; "y" and "mean" are (n, S) — column s is −α_s / +α_s; sum "mean" over the columns for the shared mean vector."""
+    a = _cols_marshal(fx, Y, "logpdf_and_grad_columns")
+    ctx = fx.f.context()
+    n, S, dt, m = a.px.n, a.ncols, a.dt, a.m
+    lp = np.empty(S, dtype=dt)
+    dnoise = np.empty(_dnoise_shape(a.nz, n), dtype=dt)
+    dY = np.empty((n, S), dtype=dt, order="F")
+    dxb = _dx_buffer(a.px, dt) if wrt_x else None
+    head = (ctx.handle, C.byref(a.kk), C.byref(a.px), C.byref(a.nz), m.ptr(a.mean), a.Y.ctypes.data, a.ldy, S, lp.ctypes.data)
+    if a.nf is not None:
+        dth = (C.c_double * max(len(a.nf.theta()), 1))()
+        check(ctx.lib.gp_logpdf_grad_cols_sum(*head, dth, dnoise.ctypes.data, dY.ctypes.data, m.ptr(dxb)))
+        gth = np.array(dth[:len(a.nf.theta())])
+        g = {"kernel": a.nf.chain(gth), "theta": gth}
+    else:
+        dvar = C.c_double()
+        dscale = (C.c_double * max(a.kk.nscale, 1))()
+        check(ctx.lib.gp_logpdf_grad_cols(*head, C.byref(dvar), dscale, dnoise.ctypes.data, dY.ctypes.data, m.ptr(dxb)))
+        sc = None if a.kk.nscale == 0 else (float(dscale[0]) if a.kk.nscale == 1 else np.array(dscale[:a.kk.nscale]))
+        g = {"variance": dvar.value, "scale": sc}
+    g.update({"noise": dnoise[0] if a.nz.kind == 0 else dnoise, "y": dY, "mean": -dY})
+    if wrt_x:
+        g["x"] = _dx_shaped(dxb, a.px, fx.x)
+    return lp, g
+
+
 def _posterior_sequential(fx: FiniteGP, y) -> PosteriorGP:
     """posterior(fx::FiniteGP{<:PosteriorGP}, y) — src/exact_gpr_posterior.jl:46-56: the device-resident factor is
     extended by update_chol (src/util/common_covmat_ops.jl:38-42) instead of being recomputed."""

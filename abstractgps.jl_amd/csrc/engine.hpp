@@ -180,6 +180,8 @@ struct gp_ctx {
     int64_t batch_pgrad_problems = 0;          // problems served by batch_pgrad_kernel of gp_predict_grad_batch / _sum (batch.hip): read-only "batch_pgrad_kernel_problems"
     int64_t batch_gradx_problems = 0;          // problems served by batch_gradx_kernel of gp_logpdf_grad_batch_x / _sum_x (batch.hip): read-only "batch_gradx_kernel_problems"
     int64_t batch_joint_problems = 0;          // problems served by the kernels of gp_joint_batch / _sum (batch.hip): read-only "batch_joint_kernel_problems"
+    int64_t cols_kernel_calls = 0;             // kmul launches served (gp_posterior_predict_cols; the kvec loop of single-kind D > 16 does not count): read-only "cols_kernel_calls"
+    int64_t cols_kernel_splits = 0;            // workgroups along the training range of the last kmul launch (1 = no partial sums): read-only "cols_kernel_splits"
     long vfe_chunk = 0;                        // data points per streamed VFE chunk (multiple of vfe_ks); 0: automatic — 16 384 (measured best at C5) × a power of two for fewer pseudo-points (vfe.hpp)
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
@@ -361,7 +363,8 @@ struct gp_post {
     void* xs;
     size_t xs_bytes;  // scaled train inputs [d][np]
     void* alpha;
-    size_t alpha_bytes;  // [np]
+    size_t alpha_bytes;  // [ncols][np]
+    int ncols = 1;       // columns of Y the handle was fitted with (gp_posterior_fit_cols; 1 for every other fit)
     double logdet_half;  // Σ log L_ii
     DibCache dibc;            // −inv(L_bb) of the factor's diagonal blocks, built on the first forward solve against the resident factor ("dib_nb")
     gp_multi_post* pieces = nullptr;  // multi-device fit: the factor still lives as block-cyclic pieces (A == nullptr until gathered)

@@ -1254,6 +1254,45 @@ static void kvec(const KDesc& k, long ns, hipStream_t s, const T* xs, long ldxs,
     if (k.ks) launch_kvec_sum<T>(ns, s, xs, ldxs, x, ldx, d, *k.ks, n, alpha, out);
     else hipLaunchKernelGGL(kvec_kernel<T>, dim3((unsigned)ns), dim3(256), 0, s, xs, ldxs, x, ldx, d, k.kind, (T)k.variance, n, alpha, out);
 }
+// How many workgroups share the training range of a kmul launch (kernels.hpp): with few tiles of 64 test points the strips of 32 training points are dealt
+// out until about 512 workgroups exist, never fewer than 4 strips (128 training points) per workgroup.  The rule reads n and ns only, so the order of
+// summation — and with it every bit of a column's result — is the same whatever S is.  Smallest case that splits: n = 225 (8 strips) with ns <= 32 704 (511 tiles).
+static inline void kmul_split(long n, long ns, long& nsplit, long& sps) {
+    const long tiles = (ns + KMUL_TM - 1) / KMUL_TM, nstrips = (n + KMUL_KS - 1) / KMUL_KS;
+    nsplit = std::min((512 + tiles - 1) / tiles, std::max(1L, nstrips / 4));
+    sps = (nstrips + nsplit - 1) / nsplit;
+    nsplit = (nstrips + sps - 1) / sps;
+}
+// out[c][·] = K(xs, x) alpha[c][·] for c < S columns (alpha: [S][lda], out: [S][ldo]; xs padded to a multiple of 128 points): one kmul launch (+ the ordered
+// sum of the partial slices when the training range is split).  Single kind with D > 16: S kvec launches (kmul holds the inputs of a point in registers, 16
+// dimensions at most; such inputs are rare and kvec has no limit), not counted in "cols_kernel_calls".
+template <typename T>
+static int32_t kmul(gp_ctx* c, DevBufs& bufs, const KDesc& k, long ns, hipStream_t s, const T* xs, long ldxs, const T* x, long ldx, int d, long n,
+                    const T* alpha, long lda, int S, T* out, long ldo) {
+    if (!k.ks && d > 16) {
+        for (int col = 0; col < S; ++col) kvec<T>(k, ns, s, xs, ldxs, x, ldx, d, n, alpha + (long)col * lda, out + (long)col * ldo);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    long nsplit, sps;
+    kmul_split(n, ns, nsplit, sps);
+    const long slice = (long)S * ldo;
+    T* part = out;
+    if (nsplit > 1) {
+        void* p_v = nullptr;
+        RC(bufs.get(sizeof(T) * (size_t)nsplit * slice, &p_v));
+        part = (T*)p_v;
+    }
+    launch_kmul<T>(dim3((unsigned)((ns + KMUL_TM - 1) / KMUL_TM), (unsigned)nsplit), s, xs, ldxs, ns, x, ldx, d, k, n, alpha, lda, S, sps, part, ldo, slice);
+    HIPCHK(hipGetLastError());
+    if (nsplit > 1) {
+        hipLaunchKernelGGL(kmul_reduce_kernel<T>, dim3((unsigned)((ns + 255) / 256), (unsigned)S), dim3(256), 0, s, (const T*)part, slice, (int)nsplit, ns, ldo, out);
+        HIPCHK(hipGetLastError());
+    }
+    c->cols_kernel_calls++;
+    c->cols_kernel_splits = nsplit;
+    return 0;
+}
 
 template <typename T> static int32_t assemble_sym(gp_ctx* c, const KDesc& k, const T* xs_dev, long ldx, int d,
                                                   const T* noise_dev, long n, long np, T* A, long ld) {
@@ -1419,7 +1458,7 @@ static int32_t fit_timings(gp_ctx* c) {
 }
 
 // Shared by gp_logpdf and gp_posterior_fit.  Y: n×ncols column-major host.  If post != NULL the factor
-// is kept and α is computed for column 0.  ks != NULL: a composite kernel (the *_sum calls) — k then scales nothing (nscale 0) and
+// is kept and α is computed for every column (post->alpha: [ncols][np]; alpha_out: n×ncols column-major, leading dimension n).  ks != NULL: a composite kernel (the *_sum calls) — k then scales nothing (nscale 0) and
 // carries Σ_t σ_t² as its variance, the prior variance the predictions use.
 template <typename T>
 static int32_t fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise,
@@ -1457,7 +1496,8 @@ static int32_t fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const
     RC(bufs.get(A_bytes, &A_v));
     RC(bufs.get(xs_bytes, &xs_v));
     RC(bufs.get(nz_bytes, &noise_v));
-    RC(bufs.get(nz_bytes, &alpha_v));
+    const size_t alpha_bytes = post ? nz_bytes * (size_t)ncols : nz_bytes;
+    RC(bufs.get(alpha_bytes, &alpha_v));
     T* A = (T*)A_v;
     double logdet_half_out = 0;
     const int32_t rc = run_drained(c, [&]() -> int32_t {
@@ -1479,17 +1519,22 @@ static int32_t fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const
         hipLaunchKernelGGL(rowsumsq_kernel<T>, dim3((unsigned)ncols), dim3(256), 0, c->sm, A + np * ld, ld, np,
                            c->scal_dev + 8);
         HIPCHK(hipGetLastError());
-        if (post) {  // α = L⁻ᵀ z for column 0
+        if (post && ncols == 1) {  // α = L⁻ᵀ z
             HIPCHK(hipMemcpyAsync(alpha_v, A + np * ld, sizeof(T) * np, hipMemcpyDeviceToDevice, c->sm));
             RC(trsv<T>(c, c->sm, A, ld, np, (T*)alpha_v, np, 1, false));
+        } else if (post) {  // gp_posterior_fit_cols: every row z_sᵀ, one backward sweep for all of them (as solve_impl)
+            HIPCHK(hipMemcpy2DAsync(alpha_v, sizeof(T) * np, A + np * ld, sizeof(T) * ld, sizeof(T) * np, ncols, hipMemcpyDeviceToDevice, c->sm));
+            RC(trsv<T>(c, c->sm, A, ld, np, (T*)alpha_v, np, ncols, false));
         }
         HIPCHK(hipEventRecord(c->ev_phase[3], c->sm));
         int info_h = 0;
         std::vector<double> scal_h(8 + ncols);
         HIPCHK(hipMemcpyAsync(&info_h, c->info_dev, sizeof(int), hipMemcpyDeviceToHost, c->sm));
         HIPCHK(hipMemcpyAsync(scal_h.data(), c->scal_dev, sizeof(double) * (8 + ncols), hipMemcpyDeviceToHost, c->sm));
-        if (post && alpha_out)
+        if (post && alpha_out && ncols == 1)
             HIPCHK(hipMemcpyAsync(alpha_out, alpha_v, sizeof(T) * n, hipMemcpyDeviceToHost, c->sm));
+        else if (post && alpha_out)
+            HIPCHK(hipMemcpy2DAsync(alpha_out, sizeof(T) * n, alpha_v, sizeof(T) * np, sizeof(T) * n, ncols, hipMemcpyDeviceToHost, c->sm));
         HIPCHK(hipStreamSynchronize(c->sm));
         out.info = info_h;
         out.logpdf.resize(ncols);
@@ -1513,14 +1558,16 @@ static int32_t fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const
     post->kern = KernelRec(k, ks);
     post->A = A_v; post->A_bytes = A_bytes;
     post->xs = xs_v; post->xs_bytes = xs_bytes;
-    post->alpha = alpha_v; post->alpha_bytes = nz_bytes;
+    post->alpha = alpha_v; post->alpha_bytes = alpha_bytes;
+    post->ncols = ncols;
     post->logdet_half = logdet_half_out;
     return 0;
 }
 
+// cols: gp_posterior_predict_cols — the mean of every column of the handle (mean_out: ns×ncols column-major) by ONE kmul launch instead of kvec
 template <typename T>
 static int32_t predict_impl(gp_post* post, const gp_points* xs, const void* pm, int what, void* mean_out,
-                            void* var_out, void* cov_out) {
+                            void* var_out, void* cov_out, bool cols = false) {
     gp_ctx* c = post->ctx;
     SkScope sk(c);
     const long n = post->n, np = post->np, ld = post->ld;
@@ -1541,7 +1588,17 @@ static int32_t predict_impl(gp_post* post, const gp_points* xs, const void* pm, 
     c->gemm_recs.clear();
     return run_drained(c, [&]() -> int32_t {
         HIPCHK(hipMemcpyAsync(xs_v, xs_h.data(), xs_bytes, hipMemcpyHostToDevice, c->sm));
-        if (what & 1) {
+        if ((what & 1) && cols) {
+            const int S = post->ncols;
+            RC(bufs.get(m_bytes * (size_t)S, &m_v));
+            RC(kmul<T>(c, bufs, post->kern.desc(), ns, c->sm, (const T*)xs_v, nsp, (const T*)post->xs, np, d, n, (const T*)post->alpha, np, S, (T*)m_v, nsp));
+            T* mo = (T*)mean_out;
+            HIPCHK(hipMemcpy2DAsync(mo, sizeof(T) * ns, m_v, sizeof(T) * nsp, sizeof(T) * ns, S, hipMemcpyDeviceToHost, c->sm));
+            HIPCHK(hipStreamSynchronize(c->sm));
+            if (prior_mean)
+                for (int col = 0; col < S; ++col)
+                    for (long i = 0; i < ns; ++i) mo[(size_t)col * ns + i] += prior_mean[i];
+        } else if (what & 1) {
             RC(bufs.get(m_bytes, &m_v));
             kvec<T>(post->kern.desc(), ns, c->sm, (const T*)xs_v, nsp, (const T*)post->xs, np, d, n, (const T*)post->alpha, (T*)m_v);
             HIPCHK(hipGetLastError());
@@ -1732,18 +1789,21 @@ static int32_t predict_grad_impl(gp_post* post, const gp_points* xs, const void*
 template <typename T>
 static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean,
                          const void* y, void* logpdf_out, double* dvar, double* dscale, void* dnoise, void* dy, void* dx,
-                         const KSum* ks = nullptr, double* dtheta = nullptr) {
+                         const KSum* ks = nullptr, double* dtheta = nullptr, long ldy = 0, int ncols = 1) {
+    // ncols > 1 (gp_logpdf_grad_cols): y is n×ncols with leading dimension ldy, the gradients are those of Σ_s logpdf(fx, y[:, s]); logpdf_out: ncols
+    // entries, dy: n×ncols.  cols_weight_kernel folds Σ_s α_s α_sᵀ into Ci and the gradient kernels below run with a zeroed α vector (kernels.hpp).
     const long n = x->n;
     const int d = x->d;
     gp_post post{};
     post.ctx = c;
     FitOut fo;
-    std::vector<T> alpha_h((size_t)n);
-    RC(fit_impl<T>(c, k, x, noise, mean, y, n, 1, fo, &post, alpha_h.data(), ks));
+    std::vector<T> alpha_h((size_t)n * ncols);
+    RC(fit_impl<T>(c, k, x, noise, mean, y, ncols > 1 ? ldy : n, ncols, fo, &post, alpha_h.data(), ks));
     SkScope sk(c);
     const long np = post.np, ld = post.ld;
     hipStream_t s = c->sm;
-    void *W_v = 0, *Ci_v = 0, *g_v = 0, *dn_v = 0, *sc_v = 0, *gx_v = 0;
+    void *W_v = 0, *Ci_v = 0, *g_v = 0, *dn_v = 0, *sc_v = 0, *gx_v = 0, *a0_v = 0;
+    const T* alpha_g = (const T*)post.alpha;  // the α vector of the gradient kernels' weights α_i α_j + Ci_ij
     const size_t gx_b = sizeof(double) * (size_t)d * np;
     std::vector<double> gx_h(dx ? (size_t)d * np : 0);
     const int nsc = std::max(k->nscale, 1);
@@ -1801,13 +1861,20 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
         }
         // (no sign fold: the kernels below add the −C⁻¹ the product left — kernels.hpp)
         dim3 grid((unsigned)(np / 128), (unsigned)(np / 128));
+        if (ncols > 1) {
+            hipLaunchKernelGGL(cols_weight_kernel<T>, grid, dim3(256), 0, s, Ci, ld, (const T*)post.alpha, np, ncols);
+            HIPCHK(hipGetLastError());
+            RC(bufs.get(dn_b, &a0_v));
+            HIPCHK(hipMemsetAsync(a0_v, 0, dn_b, s));
+            alpha_g = (const T*)a0_v;
+        }
         // one launch per chunk of 16 ARD scales (a single launch for scalar / no transform, whatever D is)
 #define GPMI_KGRAD_FAST(ND_)                                                                                                                  \
     hipLaunchKernelGGL((kgrad_fast_kernel<T, ND_>), grid, dim3(256), 0, s, (const T*)Ci, ld, (const T*)post.xs, np, d, post.kern.kind, (T)post.kern.variance, \
-                       post.kern.nscale(), (const double*)sc_v, (const T*)post.alpha, n, (double*)g_v)
+                       post.kern.nscale(), (const double*)sc_v, alpha_g, n, (double*)g_v)
         if (ks) {  // composite kernel: one launch per chunk of 16 θ entries
             for (int p0 = 0; p0 < ks->nth; p0 += 16) {
-                launch_kgrad_sum<T>(grid, s, (const T*)Ci, ld, (const T*)post.xs, np, d, *ks, (const T*)post.alpha, n, (double*)g_v, p0);
+                launch_kgrad_sum<T>(grid, s, (const T*)Ci, ld, (const T*)post.xs, np, d, *ks, alpha_g, n, (double*)g_v, p0);
                 HIPCHK(hipGetLastError());
             }
         } else if (d <= 16 && (ld * (long)sizeof(T)) % 16 == 0) {  // the scratch-free form (16-byte loads of the weights)
@@ -1818,24 +1885,24 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
         } else {
             for (int p0 = 0; p0 < (post.kern.nscale() > 1 ? post.kern.nscale() : 1); p0 += 16) {
                 hipLaunchKernelGGL(kgrad_kernel<T>, grid, dim3(256), 0, s, (const T*)Ci, ld, (const T*)post.xs, np, d, post.kern.kind,
-                                   (T)post.kern.variance, post.kern.nscale(), (const double*)sc_v, (const T*)post.alpha, n, (double*)g_v, p0);
+                                   (T)post.kern.variance, post.kern.nscale(), (const double*)sc_v, alpha_g, n, (double*)g_v, p0);
                 HIPCHK(hipGetLastError());
             }
         }
 #undef GPMI_KGRAD_FAST
         hipLaunchKernelGGL(noise_grad_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const T*)Ci, ld,
-                           (const T*)post.alpha, n, (T*)dn_v, (double*)g_v + 1);
+                           alpha_g, n, (T*)dn_v, (double*)g_v + 1);
         HIPCHK(hipGetLastError());
-        if (dnoise && noise_dense(noise)) RC(dense_grad_out<T>(c, s, bufs, (const T*)Ci, ld, (const T*)post.alpha, n, (T*)dnoise));  // G = ½(ααᵀ − C⁻¹), n×n
+        if (dnoise && noise_dense(noise)) RC(dense_grad_out<T>(c, s, bufs, (const T*)Ci, ld, alpha_g, n, (T*)dnoise));  // G = ½(ααᵀ − C⁻¹), n×n
         if (dx) {  // ∂/∂x: full-square pass (the mirrored C⁻¹ entry serves the tiles above the diagonal), 16 dimensions per launch
             HIPCHK(hipMemsetAsync(gx_v, 0, gx_b, s));
             if (ks) {  // composite kernel: post.xs holds the raw inputs, D <= 16 (pack_ksum), one launch
-                launch_kgradx_sum<T>(grid, s, (const T*)Ci, ld, (const T*)post.xs, np, d, *ks, (const T*)post.alpha, n, (double*)gx_v, np);
+                launch_kgradx_sum<T>(grid, s, (const T*)Ci, ld, (const T*)post.xs, np, d, *ks, alpha_g, n, (double*)gx_v, np);
                 HIPCHK(hipGetLastError());
             } else {
                 for (int p0 = 0; p0 < d; p0 += 16) {
                     hipLaunchKernelGGL(kgradx_kernel<T>, grid, dim3(256), 0, s, (const T*)Ci, ld, (const T*)post.xs, np, d, post.kern.kind,
-                                       (T)post.kern.variance, post.kern.nscale(), (const double*)sc_v, (const T*)post.alpha, n, (double*)gx_v, np, p0);
+                                       (T)post.kern.variance, post.kern.nscale(), (const double*)sc_v, alpha_g, n, (double*)gx_v, np, p0);
                     HIPCHK(hipGetLastError());
                 }
             }
@@ -1847,7 +1914,7 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
         return 0;
     });
     if (rc != 0) return rc;
-    *(T*)logpdf_out = (T)fo.logpdf[0];
+    for (int col = 0; col < ncols; ++col) ((T*)logpdf_out)[col] = (T)fo.logpdf[col];
     if (dvar) *dvar = g_h[0];
     if (dscale)
         for (int p = 0; p < k->nscale; ++p) dscale[p] = g_h[2 + p];
@@ -1858,7 +1925,7 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
         else if (noise->kind == 1) memcpy(dnoise, dn_h.data(), sizeof(T) * (size_t)n);  // (dense: written above)
     }
     if (dy)
-        for (long i = 0; i < n; ++i) ((T*)dy)[i] = -alpha_h[i];
+        for (size_t i = 0; i < alpha_h.size(); ++i) ((T*)dy)[i] = -alpha_h[i];
     if (dx) {  // same container layout as the inputs (src/finite_gp_projection.jl:32-37)
         T* o = (T*)dx;
         for (int dd = 0; dd < d; ++dd)
@@ -2368,6 +2435,14 @@ int32_t gp_ctx_get_param(gp_ctx* c, const char* name, int64_t* out) {
         *out = c->batch_gradx_problems;
         return 0;
     }
+    if (!strcmp(name, "cols_kernel_calls")) {  // kmul launches served by gp_posterior_predict_cols since the ctx was created
+        *out = c->cols_kernel_calls;
+        return 0;
+    }
+    if (!strcmp(name, "cols_kernel_splits")) {  // workgroups along the training range of the last kmul launch (1: no partial sums; 0: none yet)
+        *out = c->cols_kernel_splits;
+        return 0;
+    }
     if (!strcmp(name, "batch_joint_kernel_problems")) {  // the same for the kernels of gp_joint_batch / _sum (batch_jcov_kernel, batch_jfact_kernel)
         *out = c->batch_joint_problems;
         return 0;
@@ -2502,7 +2577,7 @@ static int32_t resolve_kernel(const gp_ksum* k, int d, int argi, ResolvedKernel&
 static int32_t fit_any(gp_ctx* c, const ResolvedKernel& rk, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y,
                        long ldy, int ncols, FitOut& fo, gp_post* p, void* alpha_out) {
     const gp_kernel* k = &rk.k;
-    if (c->multi && !rk.composite && k->dtype == 0 && ncols <= 128 && !noise_dense(noise)) {
+    if (c->multi && !rk.composite && k->dtype == 0 && ncols <= 128 && !noise_dense(noise) && !(p && ncols > 1)) {  // (a column posterior: single-device engine)
         fo.logpdf.assign((size_t)ncols, 0.0);
         std::vector<double> terms((size_t)ncols + 1, 0.0);
         RC(multi_fit(c, k, x, noise, mean, Y, ldy, ncols, fo.logpdf.data(), terms.data(), p, alpha_out));
@@ -2603,6 +2678,48 @@ static int32_t posterior_fit_any(gp_ctx* c, const K* k, const gp_points* x, cons
     return 0;
 }
 
+// gp_posterior_fit_cols / _sum: posterior_fit_any for Y of ncols <= GPMI355_COLS_MAX columns; the handle keeps α for every column
+template <class K>
+static int32_t posterior_fit_cols_any(gp_ctx* c, const K* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y, int64_t ldy,
+                                      int32_t ncols, gp_post** out, void* alpha_out, void* logpdf_out) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    ResolvedKernel rk;
+    RC(check_fit_args(k, x, noise, rk));
+    if (!Y) return set_arg_err(6, "Y is NULL");
+    if (ldy < x->n) return set_arg_err(7, "ldy < n");
+    if (ncols < 1 || ncols > GPMI355_COLS_MAX) return set_arg_err(8, "ncols must be 1..GPMI355_COLS_MAX (128): split more columns into groups");
+    if (!out) return set_arg_err(9, "out is NULL");
+    *out = nullptr;
+    HIPCHK(hipSetDevice(c->device));
+    auto p = std::make_unique<gp_post>();
+    p->ctx = c;
+    FitOut fo;
+    RC(fit_any(c, rk, x, noise, mean, Y, ldy, ncols, fo, p.get(), alpha_out));
+    if (logpdf_out)
+        for (int s = 0; s < ncols; ++s) put(logpdf_out, rk.k.dtype, s, fo.logpdf[s]);
+    publish(c, p, out);
+    return 0;
+}
+
+// gp_logpdf_grad_cols / _sum: logpdf_grad_any for the sum over the columns of Y
+template <class K>
+static int32_t logpdf_grad_cols_any(gp_ctx* c, const K* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y, int64_t ldy,
+                                    int32_t ncols, void* logpdf_out, double* dvar, double* dscale, void* dnoise, void* dY, void* dx, double* dtheta) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    ResolvedKernel rk;
+    RC(check_fit_args(k, x, noise, rk));
+    if (!Y) return set_arg_err(6, "Y is NULL");
+    if (ldy < x->n) return set_arg_err(7, "ldy < n");
+    if (ncols < 1 || ncols > GPMI355_COLS_MAX) return set_arg_err(8, "ncols must be 1..GPMI355_COLS_MAX (128): split more columns into groups");
+    if (!logpdf_out) return set_arg_err(9, "logpdf_out is NULL");
+    HIPCHK(hipSetDevice(c->device));
+    return by_dtype(rk.k.dtype, [&](auto t) {
+        return grad_impl<decltype(t)>(c, &rk.k, x, noise, mean, Y, logpdf_out, dvar, dscale, dnoise, dY, dx, rk.sum(), dtheta, (long)ldy, ncols);
+    });
+}
+
 // single kind: dvar / dscale / dx, dtheta NULL; composite: dtheta (one entry per θ entry) and dx, dvar / dscale NULL
 template <class K>
 static int32_t logpdf_grad_any(gp_ctx* c, const K* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, void* logpdf_out,
@@ -2677,6 +2794,23 @@ int32_t gp_posterior_fit_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, co
     return posterior_fit_any(c, k, x, noise, mean, y, out, alpha_out, logpdf_out);
 }
 
+int32_t gp_posterior_fit_cols(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y, int64_t ldy,
+                              int32_t ncols, gp_post** out, void* alpha_out, void* logpdf_out) {
+    return posterior_fit_cols_any(c, k, x, noise, mean, Y, ldy, ncols, out, alpha_out, logpdf_out);
+}
+int32_t gp_posterior_fit_cols_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y, int64_t ldy,
+                                  int32_t ncols, gp_post** out, void* alpha_out, void* logpdf_out) {
+    return posterior_fit_cols_any(c, k, x, noise, mean, Y, ldy, ncols, out, alpha_out, logpdf_out);
+}
+int32_t gp_logpdf_grad_cols(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y, int64_t ldy,
+                            int32_t ncols, void* logpdf_out, double* dvar, double* dscale, void* dnoise, void* dY, void* dx) {
+    return logpdf_grad_cols_any(c, k, x, noise, mean, Y, ldy, ncols, logpdf_out, dvar, dscale, dnoise, dY, dx, nullptr);
+}
+int32_t gp_logpdf_grad_cols_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y, int64_t ldy,
+                                int32_t ncols, void* logpdf_out, double* dtheta, void* dnoise, void* dY, void* dx) {
+    return logpdf_grad_cols_any(c, k, x, noise, mean, Y, ldy, ncols, logpdf_out, nullptr, nullptr, dnoise, dY, dx, dtheta);
+}
+
 int32_t gp_logpdf_grad(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y,
                        void* logpdf_out, double* dvar, double* dscale, void* dnoise, void* dy, void* dx) {
     return logpdf_grad_any(c, k, x, noise, mean, y, logpdf_out, dvar, dscale, dnoise, dy, dx, nullptr);
@@ -2731,6 +2865,12 @@ static int32_t check_draws(const void* xi, int32_t ncols, const void* out, int a
     return 0;
 }
 
+// What a handle of gp_posterior_fit_cols with more than one column cannot answer (one mean, one y): argument error on the handle, nothing written.
+static int32_t cols_refused(const char* what) {
+    return set_arg_err(1, (std::string(what) + ": the handle holds more than one column of observations (gp_posterior_fit_cols); its means come from "
+                                               "gp_posterior_predict_cols").c_str());
+}
+
 // logdet(C) of a posterior's factor (C = cholesky(K + Σy), `post.data.C`): 2 Σ log L_ii kept from the fit.
 int32_t gp_posterior_logdet(gp_post* post, double* out) {
     Guard gd(post);
@@ -2746,6 +2886,7 @@ int32_t gp_posterior_predict(gp_post* post, const gp_points* xs, const void* pm,
     if (!gd.ok) return set_arg_err(1, "not a live gp_post");
     RC(check_test_points(xs, post->d));
     RC(check_predict_out(what, mean_out, var_out, cov_out, 4));
+    if ((what & 1) && post->ncols > 1) return cols_refused("gp_posterior_predict (mean)");
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
     if ((what & 6) && multi_can_solve(post) && (!(what & 4) || xs->n <= 4096)) {
@@ -2782,6 +2923,25 @@ int32_t gp_posterior_predict(gp_post* post, const gp_points* xs, const void* pm,
     return by_dtype(post->dtype, [&](auto t) { return predict_impl<decltype(t)>(post, xs, pm, what, mean_out, var_out, cov_out); });
 }
 
+int32_t gp_posterior_ncols(gp_post* post, int32_t* out) {
+    Guard gd(post);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_post");
+    if (!out) return set_arg_err(2, "out is NULL");
+    *out = post->ncols;
+    return 0;
+}
+
+int32_t gp_posterior_predict_cols(gp_post* post, const gp_points* xs, const void* pm, int32_t what, void* mean_out, void* var_out, void* cov_out) {
+    Guard gd(post);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_post");
+    RC(check_test_points(xs, post->d));
+    RC(check_predict_out(what, mean_out, var_out, cov_out, 4));
+    gp_ctx* c = gd.c;
+    HIPCHK(hipSetDevice(c->device));
+    if (what & 6) RC(multi_gather(post));  // (a one-column handle of a multi-device fit: the factor is assembled on this device on first need)
+    return by_dtype(post->dtype, [&](auto t) { return predict_impl<decltype(t)>(post, xs, pm, what, mean_out, var_out, cov_out, true); });
+}
+
 // what: 1 mean side, 2 variance side; a side that is asked for needs its value or its gradient pointer (argi: position of `what`)
 static int32_t check_predict_grad_out(int what, const void* mean_out, const void* var_out, const void* dmean_out, const void* dvar_out, int argi) {
     if (what <= 0 || what > 3) return set_arg_err(argi, "what must be a combination of 1|2");
@@ -2796,6 +2956,7 @@ int32_t gp_posterior_predict_grad(gp_post* post, const gp_points* xs, const void
     if (!gd.ok) return set_arg_err(1, "not a live gp_post");
     RC(check_test_points(xs, post->d));
     RC(check_predict_grad_out(what, mean_out, var_out, dmean_out, dvar_out, 4));
+    if ((what & 1) && post->ncols > 1) return cols_refused("gp_posterior_predict_grad (mean side)");
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
     if (what & 2) RC(multi_gather(post));  // multi-device fit: the factor is assembled on this device (both solves run on the single-device path)
@@ -2811,6 +2972,7 @@ int32_t gp_posterior_update(gp_post* old, const gp_points* x2, const gp_noise* n
     RC(check_noise(noise2, 3, true));
     if (!delta_all) return set_arg_err(4, "delta_all is NULL");
     if (!out) return set_arg_err(5, "out is NULL");
+    if (old->ncols > 1) return cols_refused("gp_posterior_update");
     *out = nullptr;
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
@@ -3127,6 +3289,7 @@ int32_t gp_posterior_logpdf(gp_post* post, const gp_points* xs, const void* pm, 
     if (!gd.ok) return set_arg_err(1, "not a live gp_post");
     RC(check_joint_args(xs, post->d, noise));
     RC(check_heldout(Y, ldy, ncols, out, xs->n, 5));
+    if (post->ncols > 1) return cols_refused("gp_posterior_logpdf");
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
     const bool dist = multi_can_solve(post) && xs->n <= 4096;  // held-out logpdf on the block-cyclic pieces: no gather
@@ -3153,6 +3316,7 @@ int32_t gp_posterior_rand(gp_post* post, const gp_points* xs, const void* pm, co
     if (!gd.ok) return set_arg_err(1, "not a live gp_post");
     RC(check_joint_args(xs, post->d, noise));
     RC(check_draws(xi, ncols, out, 5));
+    if (post->ncols > 1) return cols_refused("gp_posterior_rand");
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
     const bool dist = multi_can_solve(post) && xs->n <= 4096;  // posterior sampling on the block-cyclic pieces: no gather

@@ -2667,6 +2667,177 @@ static inline void launch_kgrad_sum(dim3 grid, hipStream_t s, const T* Cinv, lon
 }
 
 // ------------------------------------------------------------------------------------------------
+// Column posteriors (gp_posterior_predict_cols, include/gpmi355.h): M[ns × S] = K(xs, x) · A for the S <= 128 weight vectors of one factorisation,
+// K_*x evaluated once for all columns and never stored.
+//   out[c][j] = Σ_i k(xs_j, x_i) · alpha[c][i]        alpha: [S][lda] (a column's weights contiguous in the training index), out: [S][ldo]
+//   A workgroup (4 waves) owns KMUL_TM = 64 test points — 16 per wave — and all round_up(S, 16) columns, and walks its share of the training points in
+//   strips of KMUL_KS = 32.  Per strip the training inputs and the strip of every α row go to LDS once (As: row stride 34 elements ≡ 2 mod 32, so the 16
+//   columns × 2 k-values a half-wave reads per fragment fall into distinct banks).  A lane then evaluates κ for ITS test point (inputs in registers) against
+//   training points q, q + 4, … (q = lane / 16; LDS broadcasts): exactly the A fragments of the 16×16×4 MFMA, so the κ tile goes from the VALU into the
+//   MFMA without passing through LDS and every κ is evaluated once per workgroup.  The B fragments are α[k][column]; up to 8 column blocks accumulate in
+//   8 × 4 registers per lane (fp64: v_mfma_f64_16x16x4_f64, fp32: v_mfma_f32_16x16x4_f32 through Tr<T>).
+//   Training indices >= n contribute exactly 0: both their α entries and their κ are replaced by 0 (nothing is read from a padding that might be poisoned);
+//   test rows >= ns and columns >= S are not written.  A column's sum never mixes with another column's, and the order of summation depends on
+//   (n, ns) only: no atomics, bitwise repeatable, a column's bits independent of the other columns.
+//   gridDim.y > 1 splits the strips over workgroups (few test points): workgroup y writes its partial sums to slice y of `out` (slice elements apart),
+//   kmul_reduce_kernel adds the slices in the order 0, 1, 2, ….
+// ------------------------------------------------------------------------------------------------
+constexpr int KMUL_TM = 64, KMUL_KS = 32, KMUL_LDA = KMUL_KS + 2;
+
+// UNR: unroll count of the 8 evaluations of a strip — all of them for a single kind (independent exp chains), one at a time for a composite kernel, whose
+// evaluation at D = 16 is large enough that eight copies of it spilled 856 bytes per lane to scratch
+template <typename T, int DR, int UNR, class KF>
+__device__ __forceinline__ void kmul_body(const T* __restrict__ xs, long ldxs, long ns, const T* __restrict__ x, long ldx, int d, long n,
+                                          const T* __restrict__ alpha, long lda, int S, long strips_per_split, T* __restrict__ out, long ldo, long slice,
+                                          const KF& kf) {
+    using acc_t = typename Tr<T>::acc_t;
+    __shared__ T As[128][KMUL_LDA];
+    __shared__ T xj[DR][KMUL_KS];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, q = lane >> 4, c16 = lane & 15;
+    const int SB = (S + 15) >> 4;
+    const long m0 = (long)blockIdx.x * KMUL_TM + w * 16;
+    T xv[DR];
+#pragma unroll
+    for (int p = 0; p < DR; ++p) xv[p] = p < d ? xs[(long)p * ldxs + m0 + c16] : T(0);  // (xs is padded to a multiple of 128 points)
+    acc_t acc[8];
+#pragma unroll
+    for (int cb = 0; cb < 8; ++cb) acc[cb] = (acc_t)(T(0));
+    const long nstrips = (n + KMUL_KS - 1) / KMUL_KS;
+    const long st0 = (long)blockIdx.y * strips_per_split, st1 = st0 + strips_per_split < nstrips ? st0 + strips_per_split : nstrips;
+    for (long st = st0; st < st1; ++st) {
+        const long i0 = st * KMUL_KS;
+        __syncthreads();  // the fragments of the previous strip have been read
+        for (int e = tid; e < DR * KMUL_KS; e += 256) {
+            const int dd = e / KMUL_KS, k = e % KMUL_KS;
+            xj[dd][k] = (dd < d && i0 + k < n) ? x[(long)dd * ldx + i0 + k] : T(0);
+        }
+        for (int e = tid; e < SB * 16 * KMUL_KS; e += 256) {
+            const int c = e / KMUL_KS, k = e % KMUL_KS;
+            As[c][k] = (c < S && i0 + k < n) ? alpha[(long)c * lda + i0 + k] : T(0);
+        }
+        __syncthreads();
+#pragma unroll(UNR)
+        for (int j = 0; j < KMUL_KS / 4; ++j) {  // κ of this lane's test point at training point q + 4j: the A fragment of MFMA step j
+            const int k = q + 4 * j;
+            T t[DR];
+#pragma unroll
+            for (int p = 0; p < DR; ++p) t[p] = xv[p] - xj[p][k];
+            const T v = kf(t);
+            const T kap = i0 + k < n ? v : T(0);
+#pragma unroll
+            for (int cb = 0; cb < 8; ++cb)
+                if (cb < SB) acc[cb] = Tr<T>::mfma(kap, As[cb * 16 + c16][k], acc[cb]);
+        }
+    }
+    T* o = out + (long)blockIdx.y * slice;
+#pragma unroll
+    for (int cb = 0; cb < 8; ++cb)
+        if (cb < SB) {
+            const int col = cb * 16 + c16;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long mi = m0 + Tr<T>::crow(lane, r);
+                if (mi < ns && col < S) o[(long)col * ldo + mi] = acc[cb][r];
+            }
+        }
+}
+
+// single kind: variance · κ_kind on pre-scaled inputs, D <= DR (the host takes S kvec launches for D > 16)
+template <typename T, int DR>
+__global__ __launch_bounds__(256) void kmul_kernel(const T* __restrict__ xs, long ldxs, long ns, const T* __restrict__ x, long ldx, int d, int kind,
+                                                    T variance, long n, const T* __restrict__ alpha, long lda, int S, long strips_per_split,
+                                                    T* __restrict__ out, long ldo, long slice) {
+    kmul_body<T, DR, KMUL_KS / 4>(xs, ldxs, ns, x, ldx, d, n, alpha, lda, S, strips_per_split, out, ldo, slice, [&](const T(&t)[DR]) {
+        T d2 = T(0);
+#pragma unroll
+        for (int p = 0; p < DR; ++p) d2 = fma(t[p], t[p], d2);
+        return variance * kappa<T>(kind, d2);
+    });
+}
+// composite kernel on raw inputs (ksum_eval, kfun.hpp)
+template <typename T, int DR>
+__global__ __launch_bounds__(256) void kmul_sum_kernel(const T* __restrict__ xs, long ldxs, long ns, const T* __restrict__ x, long ldx, int d, const KSum k,
+                                                        long n, const T* __restrict__ alpha, long lda, int S, long strips_per_split, T* __restrict__ out,
+                                                        long ldo, long slice) {
+    kmul_body<T, DR, 1>(xs, ldxs, ns, x, ldx, d, n, alpha, lda, S, strips_per_split, out, ldo, slice,
+                        [&](const T(&t)[DR]) { return ksum_eval<T, DR>(k, t, d); });
+}
+// out[c][j] = part[0][c][j] + part[1][c][j] + … in that order, for j < ns, c < S (the only entries the split workgroups wrote)
+template <typename T>
+__global__ __launch_bounds__(256) void kmul_reduce_kernel(const T* __restrict__ part, long slice, int nsplit, long ns, long ldo, T* __restrict__ out) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
+    if (j >= ns) return;
+    T v = part[c * ldo + j];
+    for (int z = 1; z < nsplit; ++z) v += part[(long)z * slice + c * ldo + j];
+    out[c * ldo + j] = v;
+}
+// D -> instance (4 / 16 single kind, 1 / 4 / 16 composite)
+template <typename T>
+static inline void launch_kmul(dim3 grid, hipStream_t s, const T* xs, long ldxs, long ns, const T* x, long ldx, int d, const KDesc& k, long n, const T* alpha,
+                               long lda, int S, long sps, T* out, long ldo, long slice) {
+    if (k.ks) {
+        if (d <= 1) hipLaunchKernelGGL((kmul_sum_kernel<T, 1>), grid, dim3(256), 0, s, xs, ldxs, ns, x, ldx, d, *k.ks, n, alpha, lda, S, sps, out, ldo, slice);
+        else if (d <= 4) hipLaunchKernelGGL((kmul_sum_kernel<T, 4>), grid, dim3(256), 0, s, xs, ldxs, ns, x, ldx, d, *k.ks, n, alpha, lda, S, sps, out, ldo, slice);
+        else hipLaunchKernelGGL((kmul_sum_kernel<T, 16>), grid, dim3(256), 0, s, xs, ldxs, ns, x, ldx, d, *k.ks, n, alpha, lda, S, sps, out, ldo, slice);
+    } else if (d <= 4) {
+        hipLaunchKernelGGL((kmul_kernel<T, 4>), grid, dim3(256), 0, s, xs, ldxs, ns, x, ldx, d, k.kind, (T)k.variance, n, alpha, lda, S, sps, out, ldo, slice);
+    } else {
+        hipLaunchKernelGGL((kmul_kernel<T, 16>), grid, dim3(256), 0, s, xs, ldxs, ns, x, ldx, d, k.kind, (T)k.variance, n, alpha, lda, S, sps, out, ldo, slice);
+    }
+}
+
+// Gradient of Σ_s logpdf(fx, Y[:, s]) (gp_logpdf_grad_cols): Ci_ij ← S·Ci_ij + Σ_s α_is α_js on the lower 128×128 tiles of the Ci = −C⁻¹ grad_impl forms
+// (whole tiles, the diagonal ones included).  The gradient kernels then run with a zeroed α vector: their weight α_i α_j + Ci_ij is
+// Σ_s α_is α_js − S·C⁻¹_ij.  alpha: [S][lda].  Thread = 32 rows × 2 adjacent columns as in the other tile kernels; 16 columns of α per LDS pass, fp64
+// sums in a fixed order.
+template <typename T>
+__global__ __launch_bounds__(256) void cols_weight_kernel(T* __restrict__ Ci, long ld, const T* __restrict__ alpha, long lda, int S) {
+    using pair_t = typename Tr<T>::pair_t;
+    if (blockIdx.x > blockIdx.y) return;
+    __shared__ double ai[16][128];
+    __shared__ __attribute__((aligned(16))) double aj[16][128];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const long r0 = (long)blockIdx.y * 128, c0 = (long)blockIdx.x * 128;
+    double a0[32], a1[32];
+#pragma unroll
+    for (int rr = 0; rr < 32; ++rr) a0[rr] = a1[rr] = 0.0;
+    for (int s0 = 0; s0 < S; s0 += 16) {
+        __syncthreads();
+        for (int e = tid; e < 16 * 128; e += 256) {
+            const int s = e / 128, i = e % 128;
+            const bool in = s0 + s < S;
+            ai[s][i] = in ? (double)alpha[(long)(s0 + s) * lda + r0 + i] : 0.0;
+            aj[s][i] = in ? (double)alpha[(long)(s0 + s) * lda + c0 + i] : 0.0;
+        }
+        __syncthreads();
+        double b0[16], b1[16];
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            b0[s] = aj[s][2 * lane];
+            b1[s] = aj[s][2 * lane + 1];
+        }
+#pragma unroll
+        for (int rr = 0; rr < 32; ++rr) {
+#pragma unroll
+            for (int s = 0; s < 16; ++s) {
+                const double a = ai[s][w + 4 * rr];
+                a0[rr] = fma(a, b0[s], a0[rr]);
+                a1[rr] = fma(a, b1[s], a1[rr]);
+            }
+        }
+    }
+    const double Sd = (double)S;
+#pragma unroll
+    for (int rr = 0; rr < 32; ++rr) {
+        pair_t* p = reinterpret_cast<pair_t*>(Ci + (r0 + w + 4 * rr) * ld + c0 + 2 * lane);
+        pair_t v = *p;
+        v.x = (T)fma(Sd, (double)v.x, a0[rr]);
+        v.y = (T)fma(Sd, (double)v.y, a1[rr]);
+        *p = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Gradients of the predictive mean and variance w.r.t. the test inputs (gp_posterior_predict_grad / gp_vfe_predict_grad, include/gpmi355.h):
 //     gm[p][j] =      Σ_i α_i  ∂k(x*_j, x_i)/∂x*_jp          (α read only when gm != nullptr)
 //     gv[p][j] = −2 · Σ_i w_ji ∂k(x*_j, x_i)/∂x*_jp          (row j of W = the weights C⁻¹k_j; read only when gv != nullptr)

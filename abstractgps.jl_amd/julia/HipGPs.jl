@@ -28,7 +28,7 @@ using KernelFunctions: SqExponentialKernel, Matern12Kernel, ExponentialKernel, M
 using LinearAlgebra, FillArrays, Statistics, StatsBase, Distributions, Random
 using ChainRulesCore
 
-export HipGP, HipPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, elbo_and_grad, logpdf_batch, mean_and_var_batch, mean_and_var_grad_batch, joint_batch, mean_and_cov_batch, logpdf_heldout_batch, rand_batch, logpdf_and_grad_batch, BatchPosDefException
+export HipGP, HipPosteriorGP, HipColumnsPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, posterior_columns, logpdf_and_grad_columns, elbo_and_grad, logpdf_batch, mean_and_var_batch, mean_and_var_grad_batch, joint_batch, mean_and_cov_batch, logpdf_heldout_batch, rand_batch, logpdf_and_grad_batch, BatchPosDefException
 
 const libgpmi355 = get(ENV, "GPMI355_LIB", joinpath(@__DIR__, "..", "csrc", "libgpmi355.so"))
 
@@ -1233,6 +1233,112 @@ end
 function Statistics.cov(f::HipPosteriorGP, x::AbstractVector, z::AbstractVector)       # :72-76
     c = predict(f, vcat(x, z), 4)[3]
     return c[1:length(x), (length(x) + 1):end]
+end
+
+# ---- one factorisation for a matrix of observations (include/gpmi355.h "columns") ------------------
+# S = size(Y, 2) <= 128 GPs that share x, kernel, Σy and the prior mean and differ in y: posterior_columns(fx, Y) fits them with ONE Gram assembly and ONE
+# factorisation (gp_posterior_fit_cols), mean(f, x) is length(x)×S from ONE kernel launch (gp_posterior_predict_cols: K_*x evaluated once for all columns),
+# var / cov do not depend on y.  logpdf_and_grad_columns(fx, Y) returns logpdf(fx, Y) (length S) and the gradient of its SUM (gp_logpdf_grad_cols).
+const COLS_MAX = 128                   # GPMI355_COLS_MAX
+struct HipColumnsPosteriorGP{Tprior<:HipGP,Tdata} <: AbstractGP
+    prior::Tprior
+    data::Tdata                        # (α (n×S), C::DeviceCholesky, x, δ (n×S))
+    logpdf_values::Vector{Float64}     # logpdf(fx, Y) from the same factorisation
+end
+
+function columns_args(fx::FiniteGP{<:HipGP}, Y::AbstractMatrix{<:Real})
+    a = marshal(fx, eltype(Y))
+    a === nothing && throw(ArgumentError("kernel / noise form is not accelerated"))
+    size(Y, 1) == length(fx) || throw(DimensionMismatch("length(fx) = $(length(fx)) but Y has $(size(Y, 1)) rows"))
+    1 <= size(Y, 2) <= COLS_MAX || throw(ArgumentError("$(size(Y, 2)) columns: 1..$COLS_MAX fit one call, split them into groups"))
+    return a, Matrix{a.T}(Y)
+end
+
+function posterior_columns(fx::FiniteGP{<:HipGP}, Y::AbstractMatrix{<:Real})
+    a, Yv = columns_args(fx, Y)
+    T = a.T
+    n, S = size(Yv)
+    δ = a.m === nothing ? copy(Yv) : Yv .- a.m
+    α = Matrix{T}(undef, n, S)
+    lp = Vector{T}(undef, S)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    mptr = a.m === nothing ? C_NULL : pointer(a.m)
+    GC.@preserve a Yv α lp begin
+        if haskey(a, :ks)
+            check(ccall((:gp_posterior_fit_cols_sum, libgpmi355), Int32,
+                (Ptr{Cvoid}, Ref{CKSum}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Cvoid}),
+                fx.f.ctx.handle, a.ks, a.cx, a.cn, mptr, Yv, n, S, h, α, lp))
+        else
+            check(ccall((:gp_posterior_fit_cols, libgpmi355), Int32,
+                (Ptr{Cvoid}, Ref{CKernel}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Cvoid}),
+                fx.f.ctx.handle, a.ck, a.cx, a.cn, mptr, Yv, n, S, h, α, lp))
+        end
+    end
+    return HipColumnsPosteriorGP(fx.f, (α=α, C=device_cholesky(h[], n, T), x=fx.x, δ=δ), Vector{Float64}(lp))
+end
+
+function ncolumns(f::HipColumnsPosteriorGP)
+    out = Ref{Int32}(0)
+    check(ccall((:gp_posterior_ncols, libgpmi355), Int32, (Ptr{Cvoid}, Ref{Int32}), getfield(f.data.C, :handle), out))
+    return Int(out[])
+end
+
+function predict(f::HipColumnsPosteriorGP, x::AbstractVector, what::Integer)
+    T = getfield(f.data.C, :T)
+    px = points(x, T)
+    px === nothing && throw(ArgumentError("unsupported input container for the accelerated posterior (use a Vector, ColVecs or RowVecs)"))
+    xbuf, cx = px
+    ns = length(x)
+    pm = prior_mean(f.prior.gp, x, T)
+    m = (what & 1) != 0 ? Matrix{T}(undef, ns, size(f.data.α, 2)) : Matrix{T}(undef, 0, 0)
+    v = (what & 2) != 0 ? Vector{T}(undef, ns) : T[]
+    c = (what & 4) != 0 ? Matrix{T}(undef, ns, ns) : Matrix{T}(undef, 0, 0)
+    GC.@preserve xbuf pm m v c begin
+        check(ccall((:gp_posterior_predict_cols, libgpmi355), Int32,
+            (Ptr{Cvoid}, Ref{CPoints}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+            getfield(f.data.C, :handle), cx, pm === nothing ? C_NULL : pointer(pm), what, m, v, c))
+    end
+    return m, v, c
+end
+Statistics.mean(f::HipColumnsPosteriorGP, x::AbstractVector) = predict(f, x, 1)[1]            # length(x)×S
+Statistics.var(f::HipColumnsPosteriorGP, x::AbstractVector) = predict(f, x, 2)[2]
+Statistics.cov(f::HipColumnsPosteriorGP, x::AbstractVector) = predict(f, x, 4)[3]
+StatsBase.mean_and_var(f::HipColumnsPosteriorGP, x::AbstractVector) = predict(f, x, 3)[1:2]
+function StatsBase.mean_and_cov(f::HipColumnsPosteriorGP, x::AbstractVector)
+    m, _, c = predict(f, x, 5)
+    return m, c
+end
+# one mean per column: a FiniteGP over a column posterior (held-out logpdf, samples, sequential conditioning) is not offered
+(f::HipColumnsPosteriorGP)(x...) = throw(ArgumentError("a FiniteGP over a column posterior is not offered: use posterior(fx, Y[:, s])"))
+
+function logpdf_and_grad_columns(fx::FiniteGP{<:HipGP}, Y::AbstractMatrix{<:Real}; wrt_x::Bool=false)
+    a, Yv = columns_args(fx, Y)
+    T = a.T
+    n, S = size(Yv)
+    lp = Vector{T}(undef, S)
+    dnoise = dnoise_buffer(a.cn, T, n)
+    dY = Matrix{T}(undef, n, S)
+    dx = wrt_x ? similar(a.xbuf) : T[]
+    mptr = a.m === nothing ? C_NULL : pointer(a.m)
+    if haskey(a, :ks)
+        dθ = zeros(Float64, length(sum_theta(a.P, a.terms)))
+        GC.@preserve a Yv lp dθ dnoise dY dx begin
+            check(ccall((:gp_logpdf_grad_cols_sum, libgpmi355), Int32,
+                (Ptr{Cvoid}, Ref{CKSum}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid},
+                    Ptr{Cvoid}),
+                fx.f.ctx.handle, a.ks, a.cx, a.cn, mptr, Yv, n, S, lp, dθ, dnoise, dY, wrt_x ? pointer(dx) : C_NULL))
+        end
+        return lp, (theta=dθ, kernel=sum_chain(a.P, a.terms, dθ), noise=a.cn.kind == 0 ? dnoise[1] : dnoise, y=dY, mean=-dY, x=wrt_x ? dx : nothing)
+    end
+    dvar = Ref{Float64}(0.0)
+    dscale = zeros(Float64, max(length(a.scales), 1))
+    GC.@preserve a Yv lp dscale dnoise dY dx begin
+        check(ccall((:gp_logpdf_grad_cols, libgpmi355), Int32,
+            (Ptr{Cvoid}, Ref{CKernel}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Cvoid}, Ref{Float64}, Ptr{Float64}, Ptr{Cvoid},
+                Ptr{Cvoid}, Ptr{Cvoid}),
+            fx.f.ctx.handle, a.ck, a.cx, a.cn, mptr, Yv, n, S, lp, dvar, dscale, dnoise, dY, wrt_x ? pointer(dx) : C_NULL))
+    end
+    return lp, (variance=dvar[], scale=dscale[1:length(a.scales)], noise=a.cn.kind == 0 ? dnoise[1] : dnoise, y=dY, mean=-dY, x=wrt_x ? dx : nothing)
 end
 
 # ---- VFE / DTC (src/sparse_approximations.jl:58-75, 183-217, 248-254, 282-286) ---------------------

@@ -307,7 +307,9 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
  *   "batch_grad_kernel_problems"      read-only (gp_ctx_get_param): the problems the gradient kernels of gp_logpdf_grad_batch / _sum have served on this ctx
  *                    since it was created (the problems routed to the single path do not count): which path ran, for tests and measurements
  *   "batch_gradx_kernel_problems"     read-only: the same for the input-gradient kernels of gp_logpdf_grad_batch_x / _sum_x (problems whose dx they computed)
- *   "batch_joint_kernel_problems"     read-only: the same for the kernels of gp_joint_batch / _sum */
+ *   "batch_joint_kernel_problems"     read-only: the same for the kernels of gp_joint_batch / _sum
+ *   "cols_kernel_calls", "cols_kernel_splits"   read-only: kmul launches gp_posterior_predict_cols has served on this ctx since it was created, and the workgroups
+ *                    along the training range of the last of them (1 = unsplit, 0 = none yet): which path ran, for tests and measurements */
 /* The defaults above, machine-readable (single-device parameters; gp_ctx_get_param reads the same names): the test-suite asserts before
  * every GPU test that the shared default context still has exactly these values, so that no test can leave a non-production setting
  * behind for the tests that follow it (tests/conftest.py). */
@@ -438,6 +440,50 @@ int32_t gp_logpdf_grad_sum_x(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, 
                              void* dy_out_or_null, void* dx_out_or_null);
 int32_t gp_logpdf_terms_sum(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null,
                             const void* Y_or_null, int64_t ldy, int32_t ncols, void* logdet_out_or_null, void* sqmahal_out_or_null);
+
+/* ---- one factorisation for a matrix of observations ("columns") ------------------------------------------------------------------ */
+/* S = ncols independent GPs that share x, kernel, Σy and the prior-mean vector and differ in y — the columns of Y (n×ncols column-major, leading
+ * dimension ldy), as logpdf(fx, Y::AbstractMatrix) takes them (src/finite_gp_projection.jl:313-326): emulators with many PCA outputs, multi-objective
+ * surrogates, many series on one grid.  ONE Gram assembly and ONE factorisation serve all columns: the right-hand sides ride below the factor as
+ * gp_logpdf's do, at no extra cost up to GPMI355_COLS_MAX = 128 columns (one block of right-hand-side rows); more columns are an argument error
+ * (argument 8) — the caller groups them.
+ * gp_posterior_fit_cols / _sum: posterior(fx, Y[:, s]) for every s (src/exact_gpr_posterior.jl:29-35).  alpha_out_or_null: n×ncols column-major, leading
+ *   dimension n (α_s = C \ (Y[:, s] − m));  logpdf_out_or_null: ncols entries.  A failed factorisation returns the LAPACK info and no handle.
+ *   Column 0 goes through the code of gp_posterior_fit; with ncols = 1 the call IS gp_posterior_fit.
+ *   On a multi-device ctx a fit with ncols > 1 runs on the single-device engine of the ctx's first device (like composite fits).
+ * gp_posterior_ncols: the columns of a handle — 1 for every handle made by the other calls.
+ * gp_posterior_predict_cols: gp_posterior_predict for every column (src/exact_gpr_posterior.jl:60-90).  mean_out: ns×ncols column-major, column s =
+ *   m(x*) + K_*x α_s, prior_mean_xs_or_null (ns entries) shared by the columns; var_out (ns) and cov_out (ns×ns) do not depend on y and are what
+ *   gp_posterior_predict returns.  The means come from ONE launch of kmul_kernel / kmul_sum_kernel (csrc/kernels.hpp): K_*x is evaluated once for all
+ *   columns and never stored, the products run on the 16×16×4 MFMA (fp64 and fp32 alike), the training range is split over workgroups when the test
+ *   points are few and the partial sums are added in a fixed order: no floating-point atomics, bitwise repeatable, a column's bits independent of what
+ *   the other columns hold, at any "deterministic" setting.  Single-kind kernels with D > 16 take one kvec launch per column instead.  On a one-column
+ *   handle the call works and equals gp_posterior_predict.
+ *   Read-only ctx parameters (gp_ctx_get_param): "cols_kernel_calls" = kmul launches served since the ctx was created (the per-column kvec launches of
+ *   D > 16 do not count), "cols_kernel_splits" = workgroups along the training range of the last such launch (1 = unsplit; the rule: about 512
+ *   workgroups, at least 128 training points each — the smallest n that splits is 225).
+ * A handle with ncols > 1 serves unchanged everything that does not use α: gp_posterior_predict with what ⊆ {var, cov}, the variance side of
+ *   gp_posterior_predict_grad, gp_posterior_solve, gp_posterior_factor_mul, gp_posterior_get_factor, gp_posterior_logdet, gp_posterior_n, gp_posterior_free.
+ *   The mean bit of gp_posterior_predict, the mean side of gp_posterior_predict_grad, gp_posterior_logpdf, gp_posterior_rand and gp_posterior_update
+ *   return −1 (the handle argument) with the reason in gp_last_error() and write nothing.
+ * gp_logpdf_grad_cols / _sum: logpdf_out[s] = logpdf(fx, Y[:, s]) (ncols entries) and the gradient of Σ_s logpdf(fx, Y[:, s]), outputs as gp_logpdf_grad /
+ *   gp_logpdf_grad_sum / gp_logpdf_grad_sum_x (every noise kind; dx_out may be NULL) except dY_out: n×ncols column-major, column s = −α_s.  One
+ *   factorisation and one C⁻¹: ∂/∂θ = ½ Σ_ij (Σ_s α_is α_js − S·C⁻¹_ij) ∂C_ij/∂θ — cols_weight_kernel folds the sum over the columns into the −C⁻¹
+ *   buffer, then the gradient kernels of gp_logpdf_grad run once.  With ncols = 1 the call IS gp_logpdf_grad. */
+#define GPMI355_COLS_MAX 128
+int32_t gp_posterior_fit_cols(gp_ctx* ctx, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null, const void* Y,
+                              int64_t ldy, int32_t ncols, gp_post** out, void* alpha_out_or_null, void* logpdf_out_or_null);
+int32_t gp_posterior_fit_cols_sum(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null, const void* Y,
+                                  int64_t ldy, int32_t ncols, gp_post** out, void* alpha_out_or_null, void* logpdf_out_or_null);
+int32_t gp_posterior_ncols(gp_post* post, int32_t* out);
+int32_t gp_posterior_predict_cols(gp_post* post, const gp_points* xs, const void* prior_mean_xs_or_null, int32_t what, void* mean_out, void* var_out,
+                                  void* cov_out);
+int32_t gp_logpdf_grad_cols(gp_ctx* ctx, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null, const void* Y,
+                            int64_t ldy, int32_t ncols, void* logpdf_out, double* dvariance_out, double* dscale_out, void* dnoise_out, void* dY_out,
+                            void* dx_out);
+int32_t gp_logpdf_grad_cols_sum(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null, const void* Y,
+                                int64_t ldy, int32_t ncols, void* logpdf_out, double* dtheta_out_or_null, void* dnoise_out_or_null, void* dY_out_or_null,
+                                void* dx_out_or_null);
 
 /* ---- many small exact GPs in one call ------------------------------------------------------------------------------------------ */
 /* nb independent problems (k_b, x_b, Σy_b, m_b, y_b), each with its own size n_b: logpdf_out[b] = logpdf(f_b(x_b, Σy_b), y_b)
