@@ -90,6 +90,10 @@ PROTOTYPES = {
     "gp_posterior_predict_cols": (i32, [vp, PP, vp, i32, vp, vp, vp]),
     "gp_logpdf_grad_cols": (i32, [vp, PK, PP, PN, vp, vp, i64, i32, vp, C.POINTER(dbl), C.POINTER(dbl), vp, vp, vp]),
     "gp_logpdf_grad_cols_sum": (i32, [vp, PS, PP, PN, vp, vp, i64, i32, vp, C.POINTER(dbl), vp, vp, vp]),
+    "gp_loo": (i32, [vp, PK, PP, PN, vp, vp, vp, vp, vp, vp]),
+    "gp_loo_sum": (i32, [vp, PS, PP, PN, vp, vp, vp, vp, vp, vp]),
+    "gp_loo_grad": (i32, [vp, PK, PP, PN, vp, vp, vp, C.POINTER(dbl), C.POINTER(dbl), vp, vp, vp]),
+    "gp_loo_grad_sum": (i32, [vp, PS, PP, PN, vp, vp, vp, C.POINTER(dbl), vp, vp, vp]),
     "gp_logpdf_batch": (i32, [vp, i32, PK, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp)]),
     "gp_logpdf_batch_sum": (i32, [vp, i32, PS, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp)]),
     "gp_predict_batch": (i32, [vp, i32, PK, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), i32, PP, C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp), vp,

@@ -1205,12 +1205,18 @@ def logpdf_and_grad(fx: FiniteGP, y, wrt_x: bool = False) -> tuple:
     as ⟨G, ∂Σy/∂φ⟩), "y": −α, "mean": +α} and, with wrt_x, "x": ∂/∂x in the shape of the input container's array.
     A composite kernel (sums, products, Periodic / RationalQuadratic / White) returns "kernel": ∂/∂params(k) in the order of params(k), and "theta":
     the gradient against the flat θ of include/gpmi355.h (gp_logpdf_grad_sum; gp_logpdf_grad_sum_x with wrt_x), in place of "variance" / "scale"."""
+    return _objective_and_grad(fx, y, wrt_x, "logpdf_and_grad", "gp_logpdf_grad")
+
+
+def _objective_and_grad(fx: FiniteGP, y, wrt_x: bool, who: str, call: str) -> tuple:
+    """The body logpdf_and_grad (call = "gp_logpdf_grad") and loo_logpdf_and_grad ("gp_loo_grad") share: the two families take the same arguments and
+    return the same outputs, except that gp_logpdf_grad_sum has no dx_out (gp_logpdf_grad_sum_x has it) where gp_loo_grad_sum always has one."""
     y = _check_y(fx, y)
     if y.ndim != 1:
-        raise TypeError("logpdf_and_grad expects a vector of observations")
+        raise TypeError(f"{who} expects a vector of observations")
     f = fx.f
     if not isinstance(f, GP):
-        raise TypeError("logpdf_and_grad: unsupported GP type")
+        raise TypeError(f"{who}: unsupported GP type")
     ctx = f.context()
     dt = np.result_type(_input_dtype(fx.x), np.float32 if y.dtype == np.float32 else np.float64).type
     m = _Marshal(dt)
@@ -1227,9 +1233,9 @@ def logpdf_and_grad(fx: FiniteGP, y, wrt_x: bool = False) -> tuple:
         dnoise = np.empty(_dnoise_shape(nz, px.n), dtype=dt)
         dy = np.empty(px.n, dtype=dt)
         head = (ctx.handle, C.byref(ks), C.byref(px), C.byref(nz), m.ptr(mean), yv.ctypes.data, lp.ctypes.data, dth, dnoise.ctypes.data, dy.ctypes.data)
-        if wrt_x:
-            dxb = _dx_buffer(px, dt)
-            check(ctx.lib.gp_logpdf_grad_sum_x(*head, m.ptr(dxb)))
+        dxb = _dx_buffer(px, dt) if wrt_x else None
+        if wrt_x or call != "gp_logpdf_grad":
+            check(getattr(ctx.lib, call + ("_sum_x" if call == "gp_logpdf_grad" else "_sum"))(*head, m.ptr(dxb)))
         else:
             check(ctx.lib.gp_logpdf_grad_sum(*head))
         gth = np.array(dth[:len(nf.theta())])
@@ -1242,7 +1248,7 @@ def logpdf_and_grad(fx: FiniteGP, y, wrt_x: bool = False) -> tuple:
     dnoise = np.empty(_dnoise_shape(nz, px.n), dtype=dt)
     dy = np.empty(px.n, dtype=dt)
     dxb = _dx_buffer(px, dt) if wrt_x else None
-    check(ctx.lib.gp_logpdf_grad(ctx.handle, C.byref(kk), C.byref(px), C.byref(nz), m.ptr(mean), yv.ctypes.data,
+    check(getattr(ctx.lib, call)(ctx.handle, C.byref(kk), C.byref(px), C.byref(nz), m.ptr(mean), yv.ctypes.data,
                                  lp.ctypes.data, C.byref(dvar), dscale, dnoise.ctypes.data, dy.ctypes.data, m.ptr(dxb)))
     sc = None
     if kk.nscale == 1:
@@ -1253,6 +1259,53 @@ def logpdf_and_grad(fx: FiniteGP, y, wrt_x: bool = False) -> tuple:
     if wrt_x:
         g["x"] = _dx_shaped(dxb, px, fx.x)
     return lp[0], g
+
+
+# --------------------------------------------------------------------------------------------
+# leave-one-out cross-validation: gp_loo / gp_loo_grad and their *_sum forms
+# --------------------------------------------------------------------------------------------
+def _loo(fx: FiniteGP, y, who: str):
+    """(L, ℓ, μ, v) of gp_loo / gp_loo_sum for a GP prior and a vector of observations."""
+    y = _check_y(fx, y)
+    if y.ndim != 1:
+        raise TypeError(f"{who} expects a vector of observations")
+    f = fx.f
+    if not isinstance(f, GP):
+        raise TypeError(f"{who}: only GP priors are accelerated here (condition on the data with one fit instead of a PosteriorGP prior)")
+    ctx = f.context()
+    dt = np.result_type(_input_dtype(fx.x), np.float32 if y.dtype == np.float32 else np.float64).type
+    m = _Marshal(dt)
+    px = m.points(fx.x)
+    sfx, kk = m.any_kernel(f.kernel, px.d)
+    nz = m.noise(fx.sigma2, px.n)
+    mean = _mean_vector(f.mean_fn, fx.x, dt)
+    mean = None if mean is None else m.arr(mean)
+    yv = m.arr(y)
+    val = np.empty(1, dtype=dt)
+    lp, mu, var = (np.empty(px.n, dtype=dt) for _ in range(3))
+    check(getattr(ctx.lib, "gp_loo" + sfx)(ctx.handle, C.byref(kk), C.byref(px), C.byref(nz), m.ptr(mean), yv.ctypes.data, val.ctypes.data,
+                                           lp.ctypes.data, mu.ctypes.data, var.ctypes.data))
+    return val[0], lp, mu, var
+
+
+def loo_mean_and_var(fx: FiniteGP, y) -> tuple:
+    """Leave-one-out predictions (Rasmussen & Williams §5.4.2): (μ, v) with μ_i, v_i the predictive mean and variance of y_i — its own observation noise
+    included — given every other observation, from ONE fit (gp_loo): μ_i = y_i − α_i / [C⁻¹]_ii, v_i = 1 / [C⁻¹]_ii."""
+    _, _, mu, var = _loo(fx, y, "loo_mean_and_var")
+    return mu, var
+
+
+def loo_logpdf(fx: FiniteGP, y, pointwise: bool = False):
+    """The leave-one-out log predictive density L = Σ_i log p(y_i | y_−i) of fx at y (gp_loo); with pointwise, the n terms log p(y_i | y_−i) instead."""
+    val, lp, _, _ = _loo(fx, y, "loo_logpdf")
+    return lp if pointwise else val
+
+
+def loo_logpdf_and_grad(fx: FiniteGP, y, wrt_x: bool = False) -> tuple:
+    """Value and gradient of loo_logpdf(fx, y) as a training objective (gp_loo_grad / gp_loo_grad_sum): (L, grads) with the keys of logpdf_and_grad —
+    "variance" / "scale" (or "kernel" / "theta" for a composite kernel), "noise" (scalar, vector, or for a dense Σy the symmetric (n, n) matrix G with
+    dL = ⟨G, dΣy⟩), "y", "mean" and, with wrt_x, "x"."""
+    return _objective_and_grad(fx, y, wrt_x, "loo_logpdf_and_grad", "gp_loo_grad")
 
 
 # --------------------------------------------------------------------------------------------

@@ -1785,13 +1785,109 @@ static int32_t predict_grad_impl(gp_post* post, const gp_points* xs, const void*
     return 0;
 }
 
+// W = L⁻ᵀ (upper, row-major, np rows + 128 zeroed slack rows the GEMMs over-read) from the factor a fit left in post.A: what gp_logpdf_grad and the
+// leave-one-out calls both start from.  W is written in full by identity_kernel (until round 5 the block was zeroed first: 34 GB of writes at C4).
+template <typename T>
+static int32_t factor_inv_t(gp_ctx* c, hipStream_t s, DevBufs& bufs, const gp_post& post, T* W) {
+    const long np = post.np, ld = post.ld;
+    HIPCHK(hipMemsetAsync(W + np * ld, 0, sizeof(T) * (size_t)128 * ld, s));
+    hipLaunchKernelGGL(identity_kernel<T>, dim3((unsigned)((np + 255) / 256), (unsigned)np), dim3(256), 0, s, W, ld, np);
+    HIPCHK(hipGetLastError());
+    if (c->dib_nb >= 128 && np >= 2 * c->dib_nb) {
+        // L⁻ᵀ with the inverse diagonal blocks: dib_build (batched: one launch sequence for all blocks) writes L_bb⁻ᵀ onto W's diagonal and −L_bb⁻¹
+        // into Wn; a leaf of the recursion is then ONE triangular-k GEMM over the rows above its block.  (With the blocks built one after the
+        // other this did not pay — C2 93.0 -> 95.6 ms, C4 4.71 -> 4.72 s: the serial chains cost what the leaves they replaced cost.)
+        const long nbi = round_up(c->dib_nb, 128), ldw = nbi + c->ldpad;
+        const size_t wb = sizeof(T) * (size_t)(np + 128) * ldw;
+        void *Wn_v = 0, *Iw_v = 0, *S_v = 0;
+        RC(bufs.get(wb, &Wn_v));
+        RC(bufs.get(wb, &Iw_v));
+        RC(bufs.get(wb, &S_v));
+        RC(dib_build<T>(c, s, (const T*)post.A, ld, np, nbi, (T*)Wn_v, ldw, (T*)Iw_v, W, ld));
+        DibArgs<T> dib;
+        dib.W = (const T*)Wn_v; dib.ldw = ldw; dib.nbi = nbi; dib.S = (T*)S_v; dib.lds = ldw;
+        return trsm_upper_rec<T>(c, s, W, ld, (const T*)post.A, ld, 0, np, dib);
+    }
+    return trsm_upper_rec<T>(c, s, W, ld, (const T*)post.A, ld, 0, np);                  // W = I L⁻ᵀ = L⁻ᵀ (upper, row-major)
+}
+
+// The leave-one-out outputs of gp_loo / gp_loo_grad (host arrays of n entries in the kernel's dtype; any may be NULL)
+struct LooOut {
+    void *lp = nullptr, *mean = nullptr, *var = nullptr;
+};
+// Device side of the leave-one-out terms: c_i = [C⁻¹]_ii from W = L⁻ᵀ, then μ, v, ℓ into terms ([3][np]) and Σ ℓ_i into sum; with b / dsc also the
+// vectors b_i = α_i/c_i and d_i = √(1/c_i + α_i²/c_i²) the gradient's weights are built from (kernels.hpp).  y_h: the n observations on the host.
+template <typename T>
+static int32_t loo_terms(gp_ctx* c, hipStream_t s, DevBufs& bufs, const gp_post& post, const T* W, const T* y_h, T** terms, T* b, T* dsc, double** sum) {
+    const long n = post.n, np = post.np;
+    void *cd_v = 0, *y_v = 0, *t_v = 0, *sum_v = 0;
+    RC(bufs.get(sizeof(double) * (size_t)np, &cd_v));
+    RC(bufs.get(sizeof(T) * (size_t)np, &y_v));
+    RC(bufs.get(sizeof(T) * (size_t)3 * np, &t_v));
+    RC(bufs.get(sizeof(double), &sum_v));
+    HIPCHK(hipMemcpyAsync(y_v, y_h, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(loo_diag_kernel<T>, dim3((unsigned)np), dim3(256), 0, s, W, post.ld, np, (double*)cd_v);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(loo_terms_kernel<T>, dim3(1), dim3(256), 0, s, (const double*)cd_v, (const T*)post.alpha, (const T*)y_v, n, np, (T*)t_v, b, dsc,
+                       (double*)sum_v);
+    HIPCHK(hipGetLastError());
+    *terms = (T*)t_v;
+    *sum = (double*)sum_v;
+    return 0;
+}
+// (after the stream has been synchronised) the downloaded terms to the caller's arrays
+template <typename T>
+static void loo_put(const LooOut& o, const std::vector<T>& terms_h, long n, long np) {
+    if (o.mean) memcpy(o.mean, terms_h.data(), sizeof(T) * (size_t)n);
+    if (o.var) memcpy(o.var, terms_h.data() + np, sizeof(T) * (size_t)n);
+    if (o.lp) memcpy(o.lp, terms_h.data() + 2 * np, sizeof(T) * (size_t)n);
+}
+
+// gp_loo / gp_loo_sum: the value path — one fit, W = L⁻ᵀ, two bandwidth-bound kernels; no product with C⁻¹
+template <typename T>
+static int32_t loo_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, void* value_out,
+                        const LooOut& out, const KSum* ks) {
+    const long n = x->n;
+    gp_post post{};
+    post.ctx = c;
+    FitOut fo;
+    RC(fit_impl<T>(c, k, x, noise, mean, y, n, 1, fo, &post, nullptr, ks));
+    SkScope sk(c);
+    const long np = post.np, ld = post.ld;
+    hipStream_t s = c->sm;
+    DevBufs bufs(c);
+    bufs.v.push_back(post.A);  // the temporary posterior's blocks go back to the cache with everything else
+    bufs.v.push_back(post.xs);
+    bufs.v.push_back(post.alpha);
+    std::vector<T> terms_h((size_t)3 * np);
+    double sum_h = 0;
+    const int32_t rc = run_drained(c, [&]() -> int32_t {
+        void* W_v = 0;
+        RC(bufs.get(sizeof(T) * (size_t)(np + 128) * ld, &W_v));
+        RC(factor_inv_t<T>(c, s, bufs, post, (T*)W_v));
+        T* terms = nullptr;
+        double* sum = nullptr;
+        RC(loo_terms<T>(c, s, bufs, post, (const T*)W_v, (const T*)y, &terms, (T*)nullptr, (T*)nullptr, &sum));
+        HIPCHK(hipMemcpyAsync(terms_h.data(), terms, sizeof(T) * (size_t)3 * np, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&sum_h, sum, sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    });
+    if (rc != 0) return rc;
+    *(T*)value_out = (T)sum_h;
+    loo_put<T>(out, terms_h, n, np);
+    return 0;
+}
+
 // logpdf value + gradient (see include/gpmi355.h gp_logpdf_grad; ks != NULL: gp_logpdf_grad_sum / gp_logpdf_grad_sum_x, ∂/∂θ into dtheta)
 template <typename T>
 static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean,
                          const void* y, void* logpdf_out, double* dvar, double* dscale, void* dnoise, void* dy, void* dx,
-                         const KSum* ks = nullptr, double* dtheta = nullptr, long ldy = 0, int ncols = 1) {
+                         const KSum* ks = nullptr, double* dtheta = nullptr, long ldy = 0, int ncols = 1, bool loo = false) {
     // ncols > 1 (gp_logpdf_grad_cols): y is n×ncols with leading dimension ldy, the gradients are those of Σ_s logpdf(fx, y[:, s]); logpdf_out: ncols
     // entries, dy: n×ncols.  cols_weight_kernel folds Σ_s α_s α_sᵀ into Ci and the gradient kernels below run with a zeroed α vector (kernels.hpp).
+    // loo (gp_loo_grad, ncols == 1): value and gradients of the leave-one-out objective L = Σ_i log p(y_i | y_−i) instead — Ci is replaced by
+    // 2G = −Z Zᵀ + β αᵀ + α βᵀ (kernels.hpp, loo_*), the same gradient kernels run with a zeroed α, and dy = −β.
     const long n = x->n;
     const int d = x->d;
     gp_post post{};
@@ -1817,6 +1913,8 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
     std::vector<double> g_hv((size_t)(2 + ng), 0.0);  // [0] ∂/∂variance, [1] Σ_i ∂/∂Σy_ii, [2 + p] ∂/∂scale_p (∂/∂θ_p)
     double* g_h = g_hv.data();
     std::vector<T> dn_h((size_t)n);
+    std::vector<T> beta_h(loo ? (size_t)n : 0);  // leave-one-out: β = −∂L/∂y and the value Σ ℓ_i
+    double loo_sum_h = 0;
     std::vector<double> sc_h((size_t)nsc, 1.0);
     for (int p = 0; p < k->nscale; ++p) sc_h[p] = k->scale[p];
     const int32_t rc = run_drained(c, [&]() -> int32_t {
@@ -1830,29 +1928,10 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
         T* Ci = (T*)Ci_v;
         HIPCHK(hipMemsetAsync(g_v, 0, g_b, s));
         HIPCHK(hipMemcpyAsync(sc_v, sc_h.data(), sc_b, hipMemcpyHostToDevice, s));
-        // W is written in full by identity_kernel and Ci by the product below (beta0: C is overwritten, not read): only the 128 slack rows the
-        // GEMM over-reads need defined values (until round 5 both N×N blocks were zeroed first: 2 × 34 GB of writes at C4)
-        HIPCHK(hipMemsetAsync(W + np * ld, 0, sizeof(T) * (size_t)128 * ld, s));
+        // Ci is written in full by the product below (beta0: C is overwritten, not read), as W is by factor_inv_t: only the 128 slack rows the GEMM
+        // over-reads need defined values
         HIPCHK(hipMemsetAsync(Ci + np * ld, 0, sizeof(T) * (size_t)128 * ld, s));
-        hipLaunchKernelGGL(identity_kernel<T>, dim3((unsigned)((np + 255) / 256), (unsigned)np), dim3(256), 0, s, W, ld, np);
-        HIPCHK(hipGetLastError());
-        if (c->dib_nb >= 128 && np >= 2 * c->dib_nb) {
-            // L⁻ᵀ with the inverse diagonal blocks: dib_build (batched: one launch sequence for all blocks) writes L_bb⁻ᵀ onto W's diagonal and −L_bb⁻¹
-            // into Wn; a leaf of the recursion is then ONE triangular-k GEMM over the rows above its block.  (With the blocks built one after the
-            // other this did not pay — C2 93.0 -> 95.6 ms, C4 4.71 -> 4.72 s: the serial chains cost what the leaves they replaced cost.)
-            const long nbi = round_up(c->dib_nb, 128), ldw = nbi + c->ldpad;
-            const size_t wb = sizeof(T) * (size_t)(np + 128) * ldw;
-            void *Wn_v = 0, *Iw_v = 0, *S_v = 0;
-            RC(bufs.get(wb, &Wn_v));
-            RC(bufs.get(wb, &Iw_v));
-            RC(bufs.get(wb, &S_v));
-            RC(dib_build<T>(c, s, (const T*)post.A, ld, np, nbi, (T*)Wn_v, ldw, (T*)Iw_v, W, ld));
-            DibArgs<T> dib;
-            dib.W = (const T*)Wn_v; dib.ldw = ldw; dib.nbi = nbi; dib.S = (T*)S_v; dib.lds = ldw;
-            RC(trsm_upper_rec<T>(c, s, W, ld, (const T*)post.A, ld, 0, np, dib));
-        } else {
-            RC(trsm_upper_rec<T>(c, s, W, ld, (const T*)post.A, ld, 0, np));             // W = I L⁻ᵀ = L⁻ᵀ (upper, row-major)
-        }
+        RC(factor_inv_t<T>(c, s, bufs, post, W));
         {
             GridMap gw = plain_map(1, 0, 0);
             gw.ktri = 2;                                                                   // W upper: k starts at the row tile
@@ -1863,6 +1942,29 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
         dim3 grid((unsigned)(np / 128), (unsigned)(np / 128));
         if (ncols > 1) {
             hipLaunchKernelGGL(cols_weight_kernel<T>, grid, dim3(256), 0, s, Ci, ld, (const T*)post.alpha, np, ncols);
+            HIPCHK(hipGetLastError());
+            RC(bufs.get(dn_b, &a0_v));
+            HIPCHK(hipMemsetAsync(a0_v, 0, dn_b, s));
+            alpha_g = (const T*)a0_v;
+        }
+        if (loo) {
+            void *b_v = 0, *d_v = 0;
+            RC(bufs.get(dn_b, &b_v));
+            RC(bufs.get(dn_b, &d_v));
+            T* terms = nullptr;
+            double* sum = nullptr;
+            RC(loo_terms<T>(c, s, bufs, post, (const T*)W, (const T*)y, &terms, (T*)b_v, (T*)d_v, &sum));   // c_i from W, before Z takes its place
+            HIPCHK(hipMemcpyAsync(&loo_sum_h, sum, sizeof(double), hipMemcpyDeviceToHost, s));
+            RC(trsv<T>(c, s, (const T*)post.A, ld, np, (T*)b_v, np, 1, true));                               // β = C⁻¹ b = L⁻ᵀ (L⁻¹ b), in place
+            RC(trsv<T>(c, s, (const T*)post.A, ld, np, (T*)b_v, np, 1, false));
+            HIPCHK(hipMemcpyAsync(beta_h.data(), b_v, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, s));
+            hipLaunchKernelGGL(loo_mirror_scale_kernel<T>, dim3((unsigned)(np / 64), (unsigned)(np / 64)), dim3(256), 0, s, (const T*)Ci, ld, (const T*)d_v,
+                               W, ld);                                                                       // Z = Ci diag(d), full, into W's block
+            HIPCHK(hipGetLastError());
+            GridMap gz = plain_map(1, 0, 0);
+            gz.beta0 = 1;
+            RC(launch_gemm<T>(c, s, Ci, ld, W, ld, W, ld, np, np, np, gz));                                  // Ci = −Z Zᵀ (lower)
+            hipLaunchKernelGGL(loo_fold_kernel<T>, grid, dim3(256), 0, s, Ci, ld, (const T*)post.alpha, (const T*)b_v);  // += β αᵀ + α βᵀ: Ci = 2G
             HIPCHK(hipGetLastError());
             RC(bufs.get(dn_b, &a0_v));
             HIPCHK(hipMemsetAsync(a0_v, 0, dn_b, s));
@@ -1915,6 +2017,10 @@ static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, cons
     });
     if (rc != 0) return rc;
     for (int col = 0; col < ncols; ++col) ((T*)logpdf_out)[col] = (T)fo.logpdf[col];
+    if (loo) {
+        *(T*)logpdf_out = (T)loo_sum_h;
+        for (long i = 0; i < n; ++i) alpha_h[i] = beta_h[i];  // dy = −β below
+    }
     if (dvar) *dvar = g_h[0];
     if (dscale)
         for (int p = 0; p < k->nscale; ++p) dscale[p] = g_h[2 + p];
@@ -2723,17 +2829,33 @@ static int32_t logpdf_grad_cols_any(gp_ctx* c, const K* k, const gp_points* x, c
 // single kind: dvar / dscale / dx, dtheta NULL; composite: dtheta (one entry per θ entry) and dx, dvar / dscale NULL
 template <class K>
 static int32_t logpdf_grad_any(gp_ctx* c, const K* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, void* logpdf_out,
-                               double* dvar, double* dscale, void* dnoise, void* dy, void* dx, double* dtheta) {
+                               double* dvar, double* dscale, void* dnoise, void* dy, void* dx, double* dtheta, bool loo = false) {
     Guard gd(c);
     if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     ResolvedKernel rk;
     RC(check_fit_args(k, x, noise, rk));
     if (!y) return set_arg_err(6, "y is NULL");
-    if (!logpdf_out) return set_arg_err(7, "logpdf_out is NULL");
+    if (!logpdf_out) return set_arg_err(7, loo ? "value_out is NULL" : "logpdf_out is NULL");
     HIPCHK(hipSetDevice(c->device));
     return by_dtype(rk.k.dtype, [&](auto t) {
-        return grad_impl<decltype(t)>(c, &rk.k, x, noise, mean, y, logpdf_out, dvar, dscale, dnoise, dy, dx, rk.sum(), dtheta);
+        return grad_impl<decltype(t)>(c, &rk.k, x, noise, mean, y, logpdf_out, dvar, dscale, dnoise, dy, dx, rk.sum(), dtheta, 0, 1, loo);
     });
+}
+
+// gp_loo / gp_loo_sum: the leave-one-out predictions and Σ_i log p(y_i | y_−i) (argument checks as logpdf_grad_any)
+template <class K>
+static int32_t loo_any(gp_ctx* c, const K* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, void* value_out, void* lp_out,
+                       void* mean_out, void* var_out) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    ResolvedKernel rk;
+    RC(check_fit_args(k, x, noise, rk));
+    if (!y) return set_arg_err(6, "y is NULL");
+    if (!value_out) return set_arg_err(7, "value_out is NULL");
+    HIPCHK(hipSetDevice(c->device));
+    LooOut out;
+    out.lp = lp_out; out.mean = mean_out; out.var = var_out;
+    return by_dtype(rk.k.dtype, [&](auto t) { return loo_impl<decltype(t)>(c, &rk.k, x, noise, mean, y, value_out, out, rk.sum()); });
 }
 
 // logdet(cov(fx)) and sqmahal(fx, Y) — the two terms logpdf adds up (src/finite_gp_projection.jl:306-311): `logdetcov` is not in
@@ -2823,6 +2945,23 @@ int32_t gp_logpdf_grad_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, cons
 int32_t gp_logpdf_grad_sum_x(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y,
                              void* logpdf_out, double* dtheta, void* dnoise, void* dy, void* dx) {
     return logpdf_grad_any(c, k, x, noise, mean, y, logpdf_out, nullptr, nullptr, dnoise, dy, dx, dtheta);
+}
+
+int32_t gp_loo(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, void* value_out, void* lp_out,
+               void* mean_out, void* var_out) {
+    return loo_any(c, k, x, noise, mean, y, value_out, lp_out, mean_out, var_out);
+}
+int32_t gp_loo_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, void* value_out, void* lp_out,
+                   void* mean_out, void* var_out) {
+    return loo_any(c, k, x, noise, mean, y, value_out, lp_out, mean_out, var_out);
+}
+int32_t gp_loo_grad(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, void* value_out,
+                    double* dvar, double* dscale, void* dnoise, void* dy, void* dx) {
+    return logpdf_grad_any(c, k, x, noise, mean, y, value_out, dvar, dscale, dnoise, dy, dx, nullptr, true);
+}
+int32_t gp_loo_grad_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, void* value_out,
+                        double* dtheta, void* dnoise, void* dy, void* dx) {
+    return logpdf_grad_any(c, k, x, noise, mean, y, value_out, nullptr, nullptr, dnoise, dy, dx, dtheta, true);
 }
 
 int32_t gp_logpdf_terms(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean,

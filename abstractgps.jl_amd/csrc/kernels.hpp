@@ -2838,6 +2838,115 @@ __global__ __launch_bounds__(256) void cols_weight_kernel(T* __restrict__ Ci, lo
 }
 
 // ------------------------------------------------------------------------------------------------
+// Leave-one-out cross-validation (gp_loo / gp_loo_grad; Rasmussen & Williams §5.4.2).  With α = C⁻¹δ and c_i = [C⁻¹]_ii:
+//   μ_i = y_i − α_i/c_i,  v_i = 1/c_i,  ℓ_i = −½ log 2π + ½ log c_i − ½ α_i²/c_i,  L = Σ ℓ_i.
+// dL = ⟨G, dC⟩ with 2G = −Z Zᵀ + β αᵀ + α βᵀ, Z = C⁻¹ diag(d), d_i = √(1/c_i + α_i²/c_i²), β = C⁻¹ b, b_i = α_i/c_i: the weight matrix the gradient
+// kernels take in the place of −C⁻¹ (with a zeroed α vector, as after cols_weight_kernel).
+// ------------------------------------------------------------------------------------------------
+// cdiag[i] = Σ_{k ≥ i} W_ik² for W = L⁻ᵀ (upper, row-major): one block per row, the upper triangle only, fp64 sums in a fixed order
+template <typename T>
+__global__ __launch_bounds__(256) void loo_diag_kernel(const T* __restrict__ W, long ldw, long np, double* __restrict__ cdiag) {
+    __shared__ double red[4];
+    const long i = blockIdx.x;
+    const T* w = W + i * ldw;
+    double acc = 0;
+    for (long k = (i & ~255L) + threadIdx.x; k < np; k += 256) {
+        if (k >= i) {
+            const double v = (double)w[k];
+            acc = fma(v, v, acc);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) cdiag[i] = red[0] + red[1] + red[2] + red[3];
+}
+// The per-point terms from cdiag, α and y (ONE workgroup: Σ ℓ_i in a fixed order).  terms: [3][np] = μ, v, ℓ (entries i < n);  b, dsc (both or neither):
+// b_i = α_i/c_i and d_i, zero for the padded i in [n, np).
+template <typename T>
+__global__ __launch_bounds__(256) void loo_terms_kernel(const double* __restrict__ cdiag, const T* __restrict__ alpha, const T* __restrict__ y, long n, long np,
+                                                         T* __restrict__ terms, T* __restrict__ b, T* __restrict__ dsc, double* __restrict__ sum) {
+    __shared__ double red[4];
+    double acc = 0;
+    for (long i = threadIdx.x; i < np; i += 256) {
+        double r = 0, dd = 0;
+        if (i < n) {
+            const double ci = cdiag[i], a = (double)alpha[i];
+            r = a / ci;
+            const double l = -0.5 * 1.8378770664093454835606594728112 + 0.5 * log(ci) - 0.5 * a * r;
+            terms[i] = (T)((double)y[i] - r);
+            terms[np + i] = (T)(1.0 / ci);
+            terms[2 * np + i] = (T)l;
+            acc += l;
+            dd = sqrt(1.0 / ci + r * r);
+        }
+        if (b) {
+            b[i] = (T)r;
+            dsc[i] = (T)dd;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) sum[0] = red[0] + red[1] + red[2] + red[3];
+}
+// Z = Ci·diag(dsc), the FULL np×np matrix row-major, from the lower-stored symmetric Ci (entries i ≥ j are read, nothing else).  One 64×64 tile (I ≥ J)
+// per workgroup, read once in 64-element row segments: it goes out as it is to (I, J), scaled by dsc of its columns, and transposed to (J, I), scaled by
+// dsc of its rows, through an LDS image with rows padded to 65 elements so that the column reads fall on distinct banks and both stores write whole row
+// segments.  A diagonal tile takes its upper half from the mirrored entry and is stored once.
+template <typename T>
+__global__ __launch_bounds__(256) void loo_mirror_scale_kernel(const T* __restrict__ Ci, long ld, const T* __restrict__ dsc, T* __restrict__ Z, long ldz) {
+    if (blockIdx.x > blockIdx.y) return;
+    __shared__ T tile[64][65];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long r0 = (long)blockIdx.y * 64, c0 = (long)blockIdx.x * 64;
+    const bool diag = blockIdx.x == blockIdx.y;
+    const T dc = dsc[c0 + lane];
+#pragma unroll
+    for (int rr = 0; rr < 16; ++rr) {
+        const int row = w + 4 * rr;
+        const long i = r0 + row, j = c0 + lane;
+        const T v = (diag && lane > row) ? Ci[j * ld + i] : Ci[i * ld + j];
+        Z[i * ldz + j] = v * dc;
+        tile[row][lane] = v * dsc[i];
+    }
+    if (diag) return;
+    __syncthreads();
+#pragma unroll
+    for (int rr = 0; rr < 16; ++rr) {
+        const int row = w + 4 * rr;
+        Z[(c0 + row) * ldz + r0 + lane] = tile[lane][row];
+    }
+}
+// P_ij += β_i α_j + α_i β_j on the lower 128×128 tiles of P = −Z Zᵀ (whole tiles, the diagonal ones included, as cols_weight_kernel)
+template <typename T>
+__global__ __launch_bounds__(256) void loo_fold_kernel(T* __restrict__ P, long ld, const T* __restrict__ alpha, const T* __restrict__ beta) {
+    using pair_t = typename Tr<T>::pair_t;
+    if (blockIdx.x > blockIdx.y) return;
+    __shared__ double ai[128], bi[128];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const long r0 = (long)blockIdx.y * 128, c0 = (long)blockIdx.x * 128;
+    if (tid < 128) {
+        ai[tid] = (double)alpha[r0 + tid];
+        bi[tid] = (double)beta[r0 + tid];
+    }
+    const double aj0 = (double)alpha[c0 + 2 * lane], aj1 = (double)alpha[c0 + 2 * lane + 1];
+    const double bj0 = (double)beta[c0 + 2 * lane], bj1 = (double)beta[c0 + 2 * lane + 1];
+    __syncthreads();
+#pragma unroll 8
+    for (int rr = 0; rr < 32; ++rr) {
+        const int row = w + 4 * rr;
+        pair_t* p = reinterpret_cast<pair_t*>(P + (r0 + row) * ld + c0 + 2 * lane);
+        pair_t v = *p;
+        v.x = (T)((double)v.x + fma(bi[row], aj0, ai[row] * bj0));
+        v.y = (T)((double)v.y + fma(bi[row], aj1, ai[row] * bj1));
+        *p = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Gradients of the predictive mean and variance w.r.t. the test inputs (gp_posterior_predict_grad / gp_vfe_predict_grad, include/gpmi355.h):
 //     gm[p][j] =      Σ_i α_i  ∂k(x*_j, x_i)/∂x*_jp          (α read only when gm != nullptr)
 //     gv[p][j] = −2 · Σ_i w_ji ∂k(x*_j, x_i)/∂x*_jp          (row j of W = the weights C⁻¹k_j; read only when gv != nullptr)

@@ -28,7 +28,7 @@ using KernelFunctions: SqExponentialKernel, Matern12Kernel, ExponentialKernel, M
 using LinearAlgebra, FillArrays, Statistics, StatsBase, Distributions, Random
 using ChainRulesCore
 
-export HipGP, HipPosteriorGP, HipColumnsPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, posterior_columns, logpdf_and_grad_columns, elbo_and_grad, logpdf_batch, mean_and_var_batch, mean_and_var_grad_batch, joint_batch, mean_and_cov_batch, logpdf_heldout_batch, rand_batch, logpdf_and_grad_batch, BatchPosDefException
+export HipGP, HipPosteriorGP, HipColumnsPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, loo_mean_and_var, loo_logpdf, loo_logpdf_and_grad, posterior_columns, logpdf_and_grad_columns, elbo_and_grad, logpdf_batch, mean_and_var_batch, mean_and_var_grad_batch, joint_batch, mean_and_cov_batch, logpdf_heldout_batch, rand_batch, logpdf_and_grad_batch, BatchPosDefException
 
 const libgpmi355 = get(ENV, "GPMI355_LIB", joinpath(@__DIR__, "..", "csrc", "libgpmi355.so"))
 
@@ -970,6 +970,68 @@ function logpdf_and_grad_sum(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}, a
         end
     end
     return lp[], (theta=dθ, kernel=sum_chain(a.P, a.terms, dθ), noise=a.cn.kind == 0 ? dnoise[1] : dnoise, y=dy, mean=-dy, x=wrt_x ? dx : nothing)
+end
+
+# ---- leave-one-out cross-validation (Rasmussen & Williams §5.4.2): gp_loo / gp_loo_grad and their *_sum forms ----------------------------
+# loo_terms: (L, ℓ, μ, v) from ONE fit — μ_i, v_i the predictive mean and variance of y_i (its own noise included) given every other
+# observation, ℓ_i = log p(y_i | y_−i), L = Σ ℓ_i.
+function loo_terms(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real})
+    a = marshal(fx, eltype(y))
+    a === nothing && throw(ArgumentError("kernel / noise form is not accelerated"))
+    T = a.T
+    yv = Vector{T}(y)
+    n = length(yv)
+    val = Ref{T}(zero(T))
+    lp = Vector{T}(undef, n); mu = Vector{T}(undef, n); v = Vector{T}(undef, n)
+    mptr = a.m === nothing ? C_NULL : pointer(a.m)
+    GC.@preserve a yv lp mu v begin
+        if haskey(a, :ks)
+            check(ccall((:gp_loo_sum, libgpmi355), Int32,
+                (Ptr{Cvoid}, Ref{CKSum}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{T}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                fx.f.ctx.handle, a.ks, a.cx, a.cn, mptr, yv, val, lp, mu, v))
+        else
+            check(ccall((:gp_loo, libgpmi355), Int32,
+                (Ptr{Cvoid}, Ref{CKernel}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{T}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                fx.f.ctx.handle, a.ck, a.cx, a.cn, mptr, yv, val, lp, mu, v))
+        end
+    end
+    return val[], lp, mu, v
+end
+loo_mean_and_var(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}) = loo_terms(fx, y)[3:4]
+function loo_logpdf(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}; pointwise::Bool=false)
+    r = loo_terms(fx, y)
+    return pointwise ? r[2] : r[1]
+end
+# value and gradient of loo_logpdf as a training objective: the named tuple of logpdf_and_grad (of logpdf_and_grad_sum for a composite kernel)
+function loo_logpdf_and_grad(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}; wrt_x::Bool=false)
+    a = marshal(fx, eltype(y))
+    a === nothing && throw(ArgumentError("kernel / noise form is not accelerated"))
+    T = a.T
+    yv = Vector{T}(y)
+    val = Ref{T}(zero(T))
+    dnoise = dnoise_buffer(a.cn, T, length(yv))
+    dy = Vector{T}(undef, length(yv))
+    dx = wrt_x ? similar(a.xbuf) : T[]
+    mptr = a.m === nothing ? C_NULL : pointer(a.m)
+    if haskey(a, :ks)
+        dθ = zeros(Float64, length(sum_theta(a.P, a.terms)))
+        GC.@preserve a yv dθ dnoise dy dx begin
+            check(ccall((:gp_loo_grad_sum, libgpmi355), Int32,
+                (Ptr{Cvoid}, Ref{CKSum}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{T}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                fx.f.ctx.handle, a.ks, a.cx, a.cn, mptr, yv, val, dθ, dnoise, dy, wrt_x ? pointer(dx) : C_NULL))
+        end
+        return val[], (theta=dθ, kernel=sum_chain(a.P, a.terms, dθ), noise=a.cn.kind == 0 ? dnoise[1] : dnoise, y=dy, mean=-dy, x=wrt_x ? dx : nothing)
+    end
+    dvar = Ref{Float64}(0.0)
+    dscale = zeros(Float64, max(length(a.scales), 1))
+    GC.@preserve a yv dscale dnoise dy dx begin
+        check(ccall((:gp_loo_grad, libgpmi355), Int32,
+            (Ptr{Cvoid}, Ref{CKernel}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{T}, Ref{Float64}, Ptr{Float64},
+                Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+            fx.f.ctx.handle, a.ck, a.cx, a.cn, mptr, yv, val, dvar, dscale, dnoise, dy, wrt_x ? pointer(dx) : C_NULL))
+    end
+    return val[], (variance=dvar[], scale=dscale[1:length(a.scales)], noise=a.cn.kind == 0 ? dnoise[1] : dnoise, y=dy, mean=-dy,
+        x=wrt_x ? dx : nothing)
 end
 
 # ---- reverse-mode rule: Zygote / any ChainRules-based AD differentiates THROUGH the ccall -----------------------------------

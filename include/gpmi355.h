@@ -485,6 +485,36 @@ int32_t gp_logpdf_grad_cols_sum(gp_ctx* ctx, const gp_ksum* k, const gp_points* 
                                 int64_t ldy, int32_t ncols, void* logpdf_out, double* dtheta_out_or_null, void* dnoise_out_or_null, void* dY_out_or_null,
                                 void* dx_out_or_null);
 
+/* ---- leave-one-out cross-validation ---------------------------------------------------------------------------------------------- */
+/* How well f(x, Σy) predicts each observation from all the others (Rasmussen & Williams, GPML §5.4.2) without n refits.  With C = K + Σy,
+ * α = C⁻¹(y − m) and c_i = [C⁻¹]_ii:
+ *   mean_out[i] = μ_i = y_i − α_i / c_i          the predictive mean of y_i given y_−i
+ *   var_out[i]  = v_i = 1 / c_i                  its predictive variance, the noise of observation i included
+ *   lp_out[i]   = ℓ_i = −½ log 2π + ½ log c_i − ½ α_i² / c_i = log p(y_i | y_−i)
+ *   value_out[0] = L = Σ_i ℓ_i                   the LOO log predictive density (a diagnostic, and a training objective: gp_loo_grad)
+ * for any noise kind, a dense Σy included; n = 1 gives the prior prediction.  All outputs in the kernel's dtype, n entries each, any of the three
+ * arrays may be NULL.
+ * gp_loo / gp_loo_sum: one factorisation, W = L⁻ᵀ (the triangular inversion gp_logpdf_grad starts with), c_i = Σ_{k ≥ i} W_ik² and the terms by two
+ *   bandwidth-bound kernels (fp64 sums in a fixed order, no floating-point atomics: "deterministic" = 1 covers the call).  No product with C⁻¹:
+ *   2n³/3 flops, twice gp_logpdf's.
+ * gp_loo_grad / gp_loo_grad_sum: value_out = L and its gradient, outputs as gp_logpdf_grad / gp_logpdf_grad_sum_x (all optional except value_out).
+ *   dL = ⟨G, dC⟩ with a_i = ½(1/c_i + α_i²/c_i²), b_i = α_i/c_i, β = C⁻¹b and
+ *     G = −C⁻¹ diag(a) C⁻¹ + ½(β αᵀ + α βᵀ):
+ *   ∂/∂θ = Σ_ij G_ij ∂K_ij/∂θ;  dnoise_out: kind 0 tr G, kind 1 G_ii, kind 2 / 3 the full symmetric G (n×n, the convention of gp_logpdf_grad);
+ *   dy_out = −β (∂/∂m = +β);  dx_out through ∂K/∂x with the same weights.  On the device 2G = −Z Zᵀ + β αᵀ + α βᵀ with Z = C⁻¹ diag(√(2a)) takes the
+ *   place of −C⁻¹ in gp_logpdf_grad's buffers (one more n³ product on the MFMA GEMM and two bandwidth-bound passes: loo_mirror_scale_kernel,
+ *   loo_fold_kernel), then gp_logpdf_grad's gradient kernels run as they are: 2n³ flops, twice gp_logpdf_grad's, and no more device memory.
+ * Argument numbers and status codes as gp_logpdf_grad (a failed factorisation returns the LAPACK info and writes nothing).  On a multi-device ctx
+ * the calls run on the single-device engine of the ctx's first device, as gp_logpdf_grad does. */
+int32_t gp_loo(gp_ctx* ctx, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null, const void* y, void* value_out,
+               void* lp_out_or_null, void* mean_out_or_null, void* var_out_or_null);
+int32_t gp_loo_sum(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null, const void* y, void* value_out,
+                   void* lp_out_or_null, void* mean_out_or_null, void* var_out_or_null);
+int32_t gp_loo_grad(gp_ctx* ctx, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null, const void* y,
+                    void* value_out, double* dvariance_out, double* dscale_out, void* dnoise_out, void* dy_out, void* dx_out);
+int32_t gp_loo_grad_sum(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null, const void* y,
+                        void* value_out, double* dtheta_out_or_null, void* dnoise_out_or_null, void* dy_out_or_null, void* dx_out_or_null);
+
 /* ---- many small exact GPs in one call ------------------------------------------------------------------------------------------ */
 /* nb independent problems (k_b, x_b, Σy_b, m_b, y_b), each with its own size n_b: logpdf_out[b] = logpdf(f_b(x_b, Σy_b), y_b)
  * (src/finite_gp_projection.jl:306-311, once per problem — what a sampler over hyper-parameters, a multi-start optimiser, a grid search or a
