@@ -1452,17 +1452,6 @@ long pgrad_s(const PredictArgs& a, int b) {
     const long np = batch_np(a.xb(b).n);
     return (a.want_dvar() && a.xsb(b).n > 0) ? np * batch_ld(np) : 0;
 }
-// a gradient of the result buffer, dimension-major [d][ns], into the container layout of xs
-void unpack_grad(const gp_points& xs, const double* g, double* out) {
-    const long ns = xs.n;
-    if (xs.layout != 1) {
-        std::memcpy(out, g, sizeof(double) * (size_t)(ns * xs.d));
-        return;
-    }
-    for (int dd = 0; dd < xs.d; ++dd)
-        for (long i = 0; i < ns; ++i) out[(long)dd + i * xs.d] = g[(long)dd * ns + i];
-}
-
 // one wave: the fit launch of the problems idx[0..nw), then the predict launches against the slices it leaves — for a gradient call (a.grad) S = L⁻ᵀ of the
 // problems that need it in front of them, and batch_pgrad_kernel directly behind each predict launch, over the same tiles.  Caller holds the ctx lock.
 int32_t run_predict_wave(gp_ctx* c, const PredictArgs& a, const std::vector<KSum>& packed, const int* idx, int nw) {
@@ -1560,8 +1549,9 @@ int32_t run_predict_wave(gp_ctx* c, const PredictArgs& a, const std::vector<KSum
             for (long j = 0; j < ns; ++j) mo[j] = pm ? pm[j] + hout[mean_off[t] + j] : hout[mean_off[t] + j];
         }
         if (void* vo = a.out_b(a.var_out, 2, b)) std::memcpy(vo, hout + var_off[t], sizeof(double) * (size_t)ns);
-        if (dmean_off[t] >= 0) unpack_grad(a.xsb(b), hout + dmean_off[t], (double*)a.dmean_out[b]);
-        if (dvar_off[t] >= 0) unpack_grad(a.xsb(b), hout + dvar_off[t], (double*)a.dvar_out[b]);
+        const gp_points& q = a.xsb(b);  // the gradients lie dimension-major [d][ns] in the result buffer: into the container layout of xs
+        if (dmean_off[t] >= 0) grad_to_layout<double>(q.layout, ns, q.d, hout + dmean_off[t], ns, a.dmean_out[b]);
+        if (dvar_off[t] >= 0) grad_to_layout<double>(q.layout, ns, q.d, hout + dvar_off[t], ns, a.dvar_out[b]);
     }
     return 0;
 }
@@ -2077,7 +2067,7 @@ int32_t run_grad_wave(gp_ctx* c, const GradArgs& a, const std::vector<KSum>& pac
             const double* al = hout + L.pr[t].alpha_off;
             for (long j = 0; j < n; ++j) dy[j] = -al[j];
         }
-        if (void* dx = a.dxb(b)) unpack_grad(a.xb(b), hout + gx[L.pos[t]].dx_off, (double*)dx);
+        if (void* dx = a.dxb(b)) grad_to_layout<double>(a.xb(b).layout, n, a.xb(b).d, hout + gx[L.pos[t]].dx_off, n, dx);  // [d][n] -> the container layout of x
     }
     return 0;
 }

@@ -86,6 +86,18 @@ static inline void put(void* out, int dtype, size_t i, double v) {
     if (dtype == 0) ((double*)out)[i] = v;
     else ((float*)out)[i] = (float)v;
 }
+// A gradient against n points, g (double [d][ldg], dimension-major), into the container layout the points came in (gp_points.layout: 0 a vector, 1 point-
+// contiguous, 2 dimension-contiguous), as T: the one conversion every ∂/∂x, ∂/∂x* and ∂/∂z output of the single-problem and the batch calls goes through
+template <typename T> static inline void grad_to_layout(int layout, long n, int d, const double* g, long ldg, void* out) {
+    T* o = (T*)out;
+    for (int dd = 0; dd < d; ++dd) {
+        const double* gd = g + (size_t)dd * ldg;
+        if (layout == 1)
+            for (long i = 0; i < n; ++i) o[(long)dd + i * d] = (T)gd[i];
+        else  // a vector (d == 1), or dimension-contiguous
+            for (long i = 0; i < n; ++i) o[i + (long)dd * n] = (T)gd[i];
+    }
+}
 
 // ------------------------------------------------------------------------------------------------
 // handles

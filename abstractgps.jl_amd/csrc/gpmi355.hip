@@ -1237,6 +1237,39 @@ static void scale_points_into(const gp_kernel* k, const gp_points* x, long ldx, 
         }
     }
 }
+// The points of one call on the device: scale_points' copy [d][ldx] in a block of the caller's DevBufs, its upload queued on the main stream.  The object
+// owns the host copy, so it has to outlive that upload (declare it where the call's synchronise is in scope).  TD = double with T = float is the sparse
+// path's form: inputs arrive in T and are scaled in T, as the fit did, then widened.
+template <typename T, typename TD = T> struct StagedPoints {
+    std::vector<TD> h;
+    void* dev = nullptr;
+    const TD* ptr() const { return (const TD*)dev; }
+    int32_t stage(gp_ctx* c, DevBufs& bufs, const gp_kernel* k, const gp_points* x, long ldx) {
+        if constexpr (std::is_same<T, TD>::value) {
+            scale_points<T>(k, x, ldx, h);
+        } else {
+            std::vector<T> hT;
+            scale_points<T>(k, x, ldx, hT);
+            h.assign(hT.begin(), hT.end());
+        }
+        RC(bufs.get(sizeof(TD) * h.size(), &dev));
+        HIPCHK(hipMemcpyAsync(dev, h.data(), sizeof(TD) * h.size(), hipMemcpyHostToDevice, c->sm));
+        return 0;
+    }
+};
+// The input scales of a single kind as the gradient kernels read them: max(nscale, 1) doubles on the device, 1.0 where the kind has no scale (same lifetime rule)
+struct DevScales {
+    std::vector<double> h;
+    void* dev = nullptr;
+    const double* ptr() const { return (const double*)dev; }
+    int32_t stage(DevBufs& bufs, int nscale, const double* scale, hipStream_t s) {
+        h.assign((size_t)std::max(nscale, 1), 1.0);
+        for (int p = 0; p < nscale; ++p) h[p] = scale[p];
+        RC(bufs.get(sizeof(double) * h.size(), &dev));
+        HIPCHK(hipMemcpyAsync(dev, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, s));
+        return 0;
+    }
+};
 
 // ------------------------------------------------------------------------------------------------
 // posterior handle
@@ -1429,8 +1462,8 @@ struct FitOut {
     int32_t info = 0;
 };
 
-// gp_timings of a finished fit (the stream has been synchronised): the phases between the four ev_phase records and the event-bracketed GEMM launches
-static int32_t fit_timings(gp_ctx* c) {
+// gp_timings of a finished call (the stream has been synchronised): the phases between the four ev_phase records ...
+static int32_t phase_timings(gp_ctx* c) {
     float ms;
     HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[0], c->ev_phase[1]));
     c->tm.assemble_ms = ms;
@@ -1440,6 +1473,12 @@ static int32_t fit_timings(gp_ctx* c) {
     c->tm.solve_ms = ms;
     HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[0], c->ev_phase[3]));
     c->tm.total_ms = ms;
+    return 0;
+}
+// ... and, for a fit (exact or sparse), the event-bracketed GEMM launches
+static int32_t fit_timings(gp_ctx* c) {
+    float ms;
+    RC(phase_timings(c));
     c->tm.gemm_ms = 0;
     c->tm.gemm_flops = 0;
     c->tm.gemm_bytes = 0;
@@ -1564,34 +1603,64 @@ static int32_t fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const
     return 0;
 }
 
+// ---- what the predictive calls on a resident exact posterior share (test points xs_dev: StagedPoints, [d][nsp]; work queued on s, no synchronise unless said) ----
+// K_*x α into m_dev (nsp entries) and its download into m_h
+template <typename T>
+static int32_t post_mean(gp_post* post, hipStream_t s, const T* xs_dev, long ns, long nsp, T* m_dev, std::vector<T>& m_h) {
+    kvec<T>(post->kern.desc(), ns, s, xs_dev, nsp, (const T*)post->xs, post->np, post->d, post->n, (const T*)post->alpha, m_dev);
+    HIPCHK(hipGetLastError());
+    m_h.resize((size_t)ns);
+    HIPCHK(hipMemcpyAsync(m_h.data(), m_dev, sizeof(T) * (size_t)ns, hipMemcpyDeviceToHost, s));
+    return 0;
+}
+// (after the synchronise) out = m(x*) + K_*x α, the sum taken in TO
+template <typename T, typename TO> static void add_prior_mean(const T* prior_mean, const std::vector<T>& m_h, TO* out) {
+    for (size_t i = 0; i < m_h.size(); ++i) out[i] = (TO)(prior_mean ? prior_mean[i] : T(0)) + (TO)m_h[i];
+}
+// X (rows × np, leading dimension ldx) = K(x*[r0 .. r0 + rows), x) L⁻ᵀ: the Gram block of one chunk of test points, then the forward solve with the resident factor
+template <typename T>
+static int32_t cross_solve(gp_post* post, hipStream_t s, DevBufs& bufs, const T* xs_dev, long ns, long nsp, long r0, long rows, T* X, long ldx) {
+    GridMap g = plain_map(0, r0, 0);
+    dim3 grid((unsigned)(post->np / 128), (unsigned)(rows / 128));
+    gram<T>(post->kern.desc(), grid, s, X, ldx, xs_dev, nsp, (const T*)post->xs, post->np, post->d, (const T*)nullptr, ns, post->n, 0, g);
+    HIPCHK(hipGetLastError());
+    return trsm_post<T>(post, s, X, ldx, rows, bufs);
+}
+// vo[i] = k(x, x) − ‖X_i‖² for the first `valid` of the rows of a solved chunk: rowsumsq, its download, ONE synchronise (ss: host scratch of at least `rows`)
+template <typename T>
+static int32_t chunk_variance(gp_post* post, hipStream_t s, const T* X, long ldx, long rows, long valid, std::vector<double>& ss, T* vo) {
+    gp_ctx* c = post->ctx;
+    hipLaunchKernelGGL(rowsumsq_kernel<T>, dim3((unsigned)rows), dim3(256), 0, s, X, ldx, post->np, c->scal_dev + 8);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ss.data(), c->scal_dev + 8, sizeof(double) * rows, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (long i = 0; i < valid; ++i) vo[i] = (T)(post->kern.variance - ss[i]);  // k(x, x) = σ² (composite: Σ_t σ_t², every κ_f(x, x) = 1)
+    return 0;
+}
+
 // cols: gp_posterior_predict_cols — the mean of every column of the handle (mean_out: ns×ncols column-major) by ONE kmul launch instead of kvec
 template <typename T>
 static int32_t predict_impl(gp_post* post, const gp_points* xs, const void* pm, int what, void* mean_out,
-                            void* var_out, void* cov_out, bool cols = false) {
+                            void* var_out, void* cov_out, bool cols) {
     gp_ctx* c = post->ctx;
     SkScope sk(c);
-    const long n = post->n, np = post->np, ld = post->ld;
+    const long n = post->n, np = post->np;
     const long ns = xs->n, nsp = round_up(ns, 128);
     const int d = post->d;
     const gp_kernel k = post->kern.view(post->dtype);
-    std::vector<T> xs_h;
-    scale_points<T>(&k, xs, nsp, xs_h);
-    void* xs_v = nullptr;
-    const size_t xs_bytes = sizeof(T) * (size_t)d * nsp;
+    StagedPoints<T> sx;
     DevBufs bufs(c);
-    RC(bufs.get(xs_bytes, &xs_v));
     void *m_v = nullptr, *X_v = nullptr, *C_v = nullptr;
-    size_t m_bytes = sizeof(T) * (size_t)nsp, X_bytes = 0, C_bytes = 0;
+    const size_t m_bytes = sizeof(T) * (size_t)nsp;
     const T* prior_mean = (const T*)pm;
-    const T* A = (const T*)post->A;
     c->ev_used = 0;
     c->gemm_recs.clear();
     return run_drained(c, [&]() -> int32_t {
-        HIPCHK(hipMemcpyAsync(xs_v, xs_h.data(), xs_bytes, hipMemcpyHostToDevice, c->sm));
+        RC(sx.stage(c, bufs, &k, xs, nsp));
         if ((what & 1) && cols) {
             const int S = post->ncols;
             RC(bufs.get(m_bytes * (size_t)S, &m_v));
-            RC(kmul<T>(c, bufs, post->kern.desc(), ns, c->sm, (const T*)xs_v, nsp, (const T*)post->xs, np, d, n, (const T*)post->alpha, np, S, (T*)m_v, nsp));
+            RC(kmul<T>(c, bufs, post->kern.desc(), ns, c->sm, sx.ptr(), nsp, (const T*)post->xs, np, d, n, (const T*)post->alpha, np, S, (T*)m_v, nsp));
             T* mo = (T*)mean_out;
             HIPCHK(hipMemcpy2DAsync(mo, sizeof(T) * ns, m_v, sizeof(T) * nsp, sizeof(T) * ns, S, hipMemcpyDeviceToHost, c->sm));
             HIPCHK(hipStreamSynchronize(c->sm));
@@ -1600,13 +1669,10 @@ static int32_t predict_impl(gp_post* post, const gp_points* xs, const void* pm, 
                     for (long i = 0; i < ns; ++i) mo[(size_t)col * ns + i] += prior_mean[i];
         } else if (what & 1) {
             RC(bufs.get(m_bytes, &m_v));
-            kvec<T>(post->kern.desc(), ns, c->sm, (const T*)xs_v, nsp, (const T*)post->xs, np, d, n, (const T*)post->alpha, (T*)m_v);
-            HIPCHK(hipGetLastError());
-            std::vector<T> m_h(ns);
-            HIPCHK(hipMemcpyAsync(m_h.data(), m_v, sizeof(T) * ns, hipMemcpyDeviceToHost, c->sm));
+            std::vector<T> m_h;
+            RC(post_mean<T>(post, c->sm, sx.ptr(), ns, nsp, (T*)m_v, m_h));
             HIPCHK(hipStreamSynchronize(c->sm));
-            T* mo = (T*)mean_out;
-            for (long i = 0; i < ns; ++i) mo[i] = (prior_mean ? prior_mean[i] : T(0)) + m_h[i];
+            add_prior_mean<T, T>(prior_mean, m_h, (T*)mean_out);
         }
         if (what & 6) {
             const bool want_cov = (what & 4) != 0;
@@ -1614,38 +1680,22 @@ static int32_t predict_impl(gp_post* post, const gp_points* xs, const void* pm, 
             // the full covariance needs all of X at once.
             const long chunk = want_cov ? nsp : std::min<long>(nsp, 4096);
             const long ldx = np + c->ldpad;
-            X_bytes = sizeof(T) * (size_t)(chunk + 128) * ldx;
-            RC(bufs.get(X_bytes, &X_v));
+            RC(bufs.get(sizeof(T) * (size_t)(chunk + 128) * ldx, &X_v));
             RC(ctx_scal(c, 8 + chunk));
             T* X = (T*)X_v;
             std::vector<double> ss(chunk);
-            T* vo = (T*)var_out;
             for (long r0 = 0; r0 < nsp; r0 += chunk) {
                 const long rows = std::min(chunk, nsp - r0);
-                GridMap g = plain_map(0, r0, 0);
-                dim3 grid((unsigned)(np / 128), (unsigned)(rows / 128));
-                gram<T>(post->kern.desc(), grid, c->sm, X, ldx, (const T*)xs_v, nsp, (const T*)post->xs, np, d, (const T*)nullptr, ns, n, 0, g);
-                HIPCHK(hipGetLastError());
-                RC(trsm_post<T>(post, c->sm, X, ldx, rows, bufs));
-                if (what & 2) {
-                    hipLaunchKernelGGL(rowsumsq_kernel<T>, dim3((unsigned)rows), dim3(256), 0, c->sm, X, ldx, np,
-                                       c->scal_dev + 8);
-                    HIPCHK(hipGetLastError());
-                    HIPCHK(hipMemcpyAsync(ss.data(), c->scal_dev + 8, sizeof(double) * rows, hipMemcpyDeviceToHost,
-                                          c->sm));
-                    HIPCHK(hipStreamSynchronize(c->sm));
-                    for (long i = 0; i < rows && r0 + i < ns; ++i)
-                        vo[r0 + i] = (T)(post->kern.variance - ss[i]);  // k(x, x) = σ² (composite: Σ_t σ_t², every κ_f(x, x) = 1)
-                }
+                RC(cross_solve<T>(post, c->sm, bufs, sx.ptr(), ns, nsp, r0, rows, X, ldx));
+                if (what & 2) RC(chunk_variance<T>(post, c->sm, X, ldx, rows, std::min(rows, ns - r0), ss, (T*)var_out + r0));
             }
             if (want_cov) {
                 const long ldc = nsp + c->ldpad;
-                C_bytes = sizeof(T) * (size_t)(nsp + 128) * ldc;
-                RC(bufs.get(C_bytes, &C_v));
+                RC(bufs.get(sizeof(T) * (size_t)(nsp + 128) * ldc, &C_v));
                 T* Cm = (T*)C_v;
                 GridMap g = plain_map(0, 0, 0);
                 dim3 grid((unsigned)(nsp / 128), (unsigned)(nsp / 128));
-                gram<T>(post->kern.desc(), grid, c->sm, Cm, ldc, (const T*)xs_v, nsp, (const T*)xs_v, nsp, d, (const T*)nullptr, ns, ns, 0, g);
+                gram<T>(post->kern.desc(), grid, c->sm, Cm, ldc, sx.ptr(), nsp, sx.ptr(), nsp, d, (const T*)nullptr, ns, ns, 0, g);
                 HIPCHK(hipGetLastError());
                 RC(launch_gemm<T>(c, c->sm, Cm, ldc, X, ldx, X, ldx, nsp, nsp, np, plain_map(0, 0, 0)));
                 // symmetric: row-major == column-major
@@ -1676,20 +1726,6 @@ static int32_t launch_kpgrad(const KDesc& k, int nscale, const double* sc, long 
     }
     return 0;
 }
-// g (double [d][ldg], dimension-major) -> out in the container layout of xs, in T
-template <typename T>
-static void grad_to_layout(const gp_points* xs, const double* g, long ldg, void* out) {
-    T* o = (T*)out;
-    const long ns = xs->n;
-    const int d = xs->d;
-    for (int dd = 0; dd < d; ++dd)
-        for (long i = 0; i < ns; ++i) {
-            const T v = (T)g[(size_t)dd * ldg + i];
-            if (xs->layout == 0) o[i] = v;
-            else if (xs->layout == 1) o[(long)dd + i * d] = v;
-            else o[i + (long)dd * ns] = v;
-        }
-}
 
 // Predictive mean / variance AND their gradients w.r.t. the test inputs (include/gpmi355.h gp_posterior_predict_grad), next to predict_impl and in its
 // chunks.  Mean side: the α-weighted kernels only (no Gram matrix, no solve).  Variance side, per chunk of 4 096 test points: Gram → forward solve
@@ -1707,39 +1743,30 @@ static int32_t predict_grad_impl(gp_post* post, const gp_points* xs, const void*
     const int d = post->d;
     const gp_kernel k = post->kern.view(post->dtype);
     const KDesc kd = post->kern.desc();
-    std::vector<T> xs_h;
-    scale_points<T>(&k, xs, nsp, xs_h);
     const bool want_gm = (what & 1) && dmean_out, want_gv = (what & 2) && dvar_out, side_v = (what & 2) != 0;
-    const int nsc = std::max(k.nscale, 1);
-    std::vector<double> sc_h((size_t)nsc, 1.0);
-    for (int p = 0; p < k.nscale; ++p) sc_h[p] = k.scale[p];
-    void *xs_v = nullptr, *m_v = nullptr, *X_v = nullptr, *g_v = nullptr, *sc_v = nullptr;
-    const size_t xs_bytes = sizeof(T) * (size_t)d * nsp, g_bytes = sizeof(double) * (size_t)2 * d * nsp, sc_bytes = sizeof(double) * (size_t)nsc;
+    StagedPoints<T> sx;
+    DevScales sc;
+    void *m_v = nullptr, *X_v = nullptr, *g_v = nullptr;
+    const size_t g_bytes = sizeof(double) * (size_t)2 * d * nsp;
     DevBufs bufs(c);
-    RC(bufs.get(xs_bytes, &xs_v));
-    RC(bufs.get(g_bytes, &g_v));
-    RC(bufs.get(sc_bytes, &sc_v));
     std::vector<double> g_h((want_gm || want_gv) ? (size_t)2 * d * nsp : 0);
-    const T* prior_mean = (const T*)pm;
     c->ev_used = 0;
     c->gemm_recs.clear();
     const int32_t rc = run_drained(c, [&]() -> int32_t {
+        RC(sx.stage(c, bufs, &k, xs, nsp));
+        RC(bufs.get(g_bytes, &g_v));
+        RC(sc.stage(bufs, k.nscale, k.scale, c->sm));
         double* gm = want_gm ? (double*)g_v : nullptr;
         double* gv = want_gv ? (double*)g_v + (size_t)d * nsp : nullptr;
-        HIPCHK(hipMemcpyAsync(xs_v, xs_h.data(), xs_bytes, hipMemcpyHostToDevice, c->sm));
-        HIPCHK(hipMemcpyAsync(sc_v, sc_h.data(), sc_bytes, hipMemcpyHostToDevice, c->sm));
         if ((what & 1) && mean_out) {
             RC(bufs.get(sizeof(T) * (size_t)nsp, &m_v));
-            kvec<T>(kd, ns, c->sm, (const T*)xs_v, nsp, (const T*)post->xs, np, d, n, (const T*)post->alpha, (T*)m_v);
-            HIPCHK(hipGetLastError());
-            std::vector<T> m_h(ns);
-            HIPCHK(hipMemcpyAsync(m_h.data(), m_v, sizeof(T) * ns, hipMemcpyDeviceToHost, c->sm));
+            std::vector<T> m_h;
+            RC(post_mean<T>(post, c->sm, sx.ptr(), ns, nsp, (T*)m_v, m_h));
             HIPCHK(hipStreamSynchronize(c->sm));
-            T* mo = (T*)mean_out;
-            for (long i = 0; i < ns; ++i) mo[i] = (prior_mean ? prior_mean[i] : T(0)) + m_h[i];
+            add_prior_mean<T, T>((const T*)pm, m_h, (T*)mean_out);
         }
         if (want_gm && !want_gv)  // the mean side alone: one launch over every test point
-            RC(launch_kpgrad<T>(kd, k.nscale, (const double*)sc_v, ns, c->sm, (const T*)xs_v, nsp, (const T*)post->xs, np, d, n, (const T*)post->alpha,
+            RC(launch_kpgrad<T>(kd, k.nscale, sc.ptr(), ns, c->sm, sx.ptr(), nsp, (const T*)post->xs, np, d, n, (const T*)post->alpha,
                                 (const T*)nullptr, 0, gm, (double*)nullptr, nsp, 0));
         if (side_v) {
             const long chunk = std::min<long>(nsp, 4096);
@@ -1754,21 +1781,11 @@ static int32_t predict_grad_impl(gp_post* post, const gp_points* xs, const void*
             BackWs ws;
             for (long r0 = 0; r0 < nsp; r0 += chunk) {
                 const long rows = std::min(chunk, nsp - r0), valid = std::min(rows, ns - r0);
-                GridMap g = plain_map(0, r0, 0);
-                dim3 grid((unsigned)(np / 128), (unsigned)(rows / 128));
-                gram<T>(kd, grid, c->sm, X, ldx, (const T*)xs_v, nsp, (const T*)post->xs, np, d, (const T*)nullptr, ns, n, 0, g);
-                HIPCHK(hipGetLastError());
-                RC(trsm_post<T>(post, c->sm, X, ldx, rows, bufs));
-                if (vo) {
-                    hipLaunchKernelGGL(rowsumsq_kernel<T>, dim3((unsigned)rows), dim3(256), 0, c->sm, X, ldx, np, c->scal_dev + 8);
-                    HIPCHK(hipGetLastError());
-                    HIPCHK(hipMemcpyAsync(ss.data(), c->scal_dev + 8, sizeof(double) * rows, hipMemcpyDeviceToHost, c->sm));
-                    HIPCHK(hipStreamSynchronize(c->sm));
-                    for (long i = 0; i < valid; ++i) vo[r0 + i] = (T)(post->kern.variance - ss[i]);  // k(x, x) = σ² (composite: Σ_t σ_t²)
-                }
+                RC(cross_solve<T>(post, c->sm, bufs, sx.ptr(), ns, nsp, r0, rows, X, ldx));
+                if (vo) RC(chunk_variance<T>(post, c->sm, X, ldx, rows, valid, ss, vo + r0));
                 if (want_gv) {
                     RC(trsm_back_cached<T>(c, c->sm, X, ldx, rows, valid, (const T*)post->A, post->ld, np, post->dibc, bufs, ws));
-                    RC(launch_kpgrad<T>(kd, k.nscale, (const double*)sc_v, valid, c->sm, (const T*)xs_v, nsp, (const T*)post->xs, np, d, n,
+                    RC(launch_kpgrad<T>(kd, k.nscale, sc.ptr(), valid, c->sm, sx.ptr(), nsp, (const T*)post->xs, np, d, n,
                                         (const T*)post->alpha, (const T*)X, ldx, gm, gv, nsp, r0));
                 }
             }
@@ -1780,9 +1797,30 @@ static int32_t predict_grad_impl(gp_post* post, const gp_points* xs, const void*
         return 0;
     });
     if (rc != 0) return rc;
-    if (want_gm) grad_to_layout<T>(xs, g_h.data(), nsp, dmean_out);
-    if (want_gv) grad_to_layout<T>(xs, g_h.data() + (size_t)d * nsp, nsp, dvar_out);
+    if (want_gm) grad_to_layout<T>(xs->layout, ns, d, g_h.data(), nsp, dmean_out);
+    if (want_gv) grad_to_layout<T>(xs->layout, ns, d, g_h.data() + (size_t)d * nsp, nsp, dvar_out);
     return 0;
+}
+
+// W (np rows, leading dimension ld, written in full; the slack rows below are the caller's) = L⁻ᵀ (upper, row-major) of the lower factor L: I · L⁻ᵀ by
+// the restricted-row recursion.  nbi > 0: with the inverse diagonal blocks of that width — dib_build (batched: one launch sequence for all blocks)
+// writes L_bb⁻ᵀ onto W's diagonal and −L_bb⁻¹ into Wn; a leaf of the recursion is then ONE triangular-k GEMM over the rows above its block.  (With the
+// blocks built one after the other this did not pay — C2 93.0 -> 95.6 ms, C4 4.71 -> 4.72 s: the serial chains cost what the leaves they replaced cost.)
+template <typename T>
+static int32_t upper_inverse(gp_ctx* c, hipStream_t s, DevBufs& bufs, const T* L, long ld, long np, long nbi, T* W) {
+    hipLaunchKernelGGL(identity_kernel<T>, dim3((unsigned)((np + 255) / 256), (unsigned)np), dim3(256), 0, s, W, ld, np);
+    HIPCHK(hipGetLastError());
+    if (nbi <= 0) return trsm_upper_rec<T>(c, s, W, ld, L, ld, 0, np);  // W = I L⁻ᵀ down to the 64-wide leaves
+    const long ldw = nbi + c->ldpad;
+    const size_t wb = sizeof(T) * (size_t)(np + 128) * ldw;
+    void *Wn_v = 0, *Iw_v = 0, *S_v = 0;
+    RC(bufs.get(wb, &Wn_v));
+    RC(bufs.get(wb, &Iw_v));
+    RC(bufs.get(wb, &S_v));
+    RC(dib_build<T>(c, s, L, ld, np, nbi, (T*)Wn_v, ldw, (T*)Iw_v, W, ld));
+    DibArgs<T> dib;
+    dib.W = (const T*)Wn_v; dib.ldw = ldw; dib.nbi = nbi; dib.S = (T*)S_v; dib.lds = ldw;
+    return trsm_upper_rec<T>(c, s, W, ld, L, ld, 0, np, dib);
 }
 
 // W = L⁻ᵀ (upper, row-major, np rows + 128 zeroed slack rows the GEMMs over-read) from the factor a fit left in post.A: what gp_logpdf_grad and the
@@ -1791,24 +1829,7 @@ template <typename T>
 static int32_t factor_inv_t(gp_ctx* c, hipStream_t s, DevBufs& bufs, const gp_post& post, T* W) {
     const long np = post.np, ld = post.ld;
     HIPCHK(hipMemsetAsync(W + np * ld, 0, sizeof(T) * (size_t)128 * ld, s));
-    hipLaunchKernelGGL(identity_kernel<T>, dim3((unsigned)((np + 255) / 256), (unsigned)np), dim3(256), 0, s, W, ld, np);
-    HIPCHK(hipGetLastError());
-    if (c->dib_nb >= 128 && np >= 2 * c->dib_nb) {
-        // L⁻ᵀ with the inverse diagonal blocks: dib_build (batched: one launch sequence for all blocks) writes L_bb⁻ᵀ onto W's diagonal and −L_bb⁻¹
-        // into Wn; a leaf of the recursion is then ONE triangular-k GEMM over the rows above its block.  (With the blocks built one after the
-        // other this did not pay — C2 93.0 -> 95.6 ms, C4 4.71 -> 4.72 s: the serial chains cost what the leaves they replaced cost.)
-        const long nbi = round_up(c->dib_nb, 128), ldw = nbi + c->ldpad;
-        const size_t wb = sizeof(T) * (size_t)(np + 128) * ldw;
-        void *Wn_v = 0, *Iw_v = 0, *S_v = 0;
-        RC(bufs.get(wb, &Wn_v));
-        RC(bufs.get(wb, &Iw_v));
-        RC(bufs.get(wb, &S_v));
-        RC(dib_build<T>(c, s, (const T*)post.A, ld, np, nbi, (T*)Wn_v, ldw, (T*)Iw_v, W, ld));
-        DibArgs<T> dib;
-        dib.W = (const T*)Wn_v; dib.ldw = ldw; dib.nbi = nbi; dib.S = (T*)S_v; dib.lds = ldw;
-        return trsm_upper_rec<T>(c, s, W, ld, (const T*)post.A, ld, 0, np, dib);
-    }
-    return trsm_upper_rec<T>(c, s, W, ld, (const T*)post.A, ld, 0, np);                  // W = I L⁻ᵀ = L⁻ᵀ (upper, row-major)
+    return upper_inverse<T>(c, s, bufs, (const T*)post.A, ld, np, (c->dib_nb >= 128 && np >= 2 * c->dib_nb) ? round_up(c->dib_nb, 128) : 0, W);
 }
 
 // The leave-one-out outputs of gp_loo / gp_loo_grad (host arrays of n entries in the kernel's dtype; any may be NULL)
@@ -1843,22 +1864,40 @@ static void loo_put(const LooOut& o, const std::vector<T>& terms_h, long n, long
     if (o.lp) memcpy(o.lp, terms_h.data() + 2 * np, sizeof(T) * (size_t)n);
 }
 
+// A posterior that lives for one call (gp_loo, gp_logpdf_grad and their kin: fit, use, forget): fit_impl into a stack gp_post whose blocks go back to the
+// cache with the object, after the synchronise or drain every path ends in.  Declare it BEHIND the call's DevBufs: its blocks then return first, the order
+// the cache has always seen them in (which block a later call gets, and with it every address, depends on that order).  After a failed fit the destructor
+// releases nothing: fit_impl assigns post->A / xs / alpha on success alone and ctx_release ignores NULL.  (dibc.w is set only by a forward solve against the
+// handle, which no caller does today; it is released for completeness.)
+template <typename T> struct TempPost {
+    gp_post post{};
+    FitOut fo;
+    explicit TempPost(gp_ctx* c) { post.ctx = c; }
+    TempPost(const TempPost&) = delete;
+    int32_t fit(const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y, long ldy, int ncols, void* alpha_out,
+                const KSum* ks) {
+        return fit_impl<T>(post.ctx, k, x, noise, mean, Y, ldy, ncols, fo, &post, alpha_out, ks);
+    }
+    ~TempPost() {
+        ctx_release(post.ctx, post.A, post.A_bytes);
+        ctx_release(post.ctx, post.xs, post.xs_bytes);
+        ctx_release(post.ctx, post.alpha, post.alpha_bytes);
+        if (post.dibc.w) ctx_release(post.ctx, post.dibc.w, post.dibc.bytes);
+    }
+};
+
 // gp_loo / gp_loo_sum: the value path — one fit, W = L⁻ᵀ, two bandwidth-bound kernels; no product with C⁻¹
 template <typename T>
 static int32_t loo_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, void* value_out,
                         const LooOut& out, const KSum* ks) {
     const long n = x->n;
-    gp_post post{};
-    post.ctx = c;
-    FitOut fo;
-    RC(fit_impl<T>(c, k, x, noise, mean, y, n, 1, fo, &post, nullptr, ks));
+    DevBufs bufs(c);
+    TempPost<T> tp(c);
+    RC(tp.fit(k, x, noise, mean, y, n, 1, nullptr, ks));
+    const gp_post& post = tp.post;
     SkScope sk(c);
     const long np = post.np, ld = post.ld;
     hipStream_t s = c->sm;
-    DevBufs bufs(c);
-    bufs.v.push_back(post.A);  // the temporary posterior's blocks go back to the cache with everything else
-    bufs.v.push_back(post.xs);
-    bufs.v.push_back(post.alpha);
     std::vector<T> terms_h((size_t)3 * np);
     double sum_h = 0;
     const int32_t rc = run_drained(c, [&]() -> int32_t {
@@ -1879,169 +1918,218 @@ static int32_t loo_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const
     return 0;
 }
 
-// logpdf value + gradient (see include/gpmi355.h gp_logpdf_grad; ks != NULL: gp_logpdf_grad_sum / gp_logpdf_grad_sum_x, ∂/∂θ into dtheta)
+// ------------------------------------------------------------------------------------------------
+// Value + gradient of an objective of one exact fit (include/gpmi355.h gp_logpdf_grad, gp_logpdf_grad_cols, gp_loo_grad and their *_sum forms): every
+// gradient is a contraction Σ_ij (a_i a_j + Ci_ij) ∂K_ij of a weight matrix Ci (lower, row-major) and a vector a with the kernel's derivatives.  The
+// drivers at the end put the stages together: (a) W = L⁻ᵀ and Ci = −C⁻¹; (b) / (c) an objective that is not logpdf of one column folds its weights into
+// Ci and (d) contracts with a = 0; (e) the contraction; (f) the results to the caller's arrays.  Everything is queued on s; (e) ends in the synchronise.
+// ------------------------------------------------------------------------------------------------
+template <typename T> struct GradOut {  // what (e) produces: on the device, then on the host
+    void *g_v = nullptr, *dn_v = nullptr, *gx_v = nullptr;
+    DevScales sc;
+    std::vector<double> g_h;   // [0] ∂/∂variance, [1] Σ_i ∂/∂Σy_ii, [2 + p] ∂/∂scale_p (∂/∂θ_p of a composite kernel)
+    std::vector<T> dn_h;       // ∂/∂Σy_ii
+    std::vector<double> gx_h;  // ∂/∂x as [d][np]; empty: not wanted
+};
+// The blocks of a call — W and Ci ((np + 128) × ld each) and those of the results — with the sums zeroed and the kind's scales uploaded
 template <typename T>
-static int32_t grad_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean,
-                         const void* y, void* logpdf_out, double* dvar, double* dscale, void* dnoise, void* dy, void* dx,
-                         const KSum* ks = nullptr, double* dtheta = nullptr, long ldy = 0, int ncols = 1, bool loo = false) {
-    // ncols > 1 (gp_logpdf_grad_cols): y is n×ncols with leading dimension ldy, the gradients are those of Σ_s logpdf(fx, y[:, s]); logpdf_out: ncols
-    // entries, dy: n×ncols.  cols_weight_kernel folds Σ_s α_s α_sᵀ into Ci and the gradient kernels below run with a zeroed α vector (kernels.hpp).
-    // loo (gp_loo_grad, ncols == 1): value and gradients of the leave-one-out objective L = Σ_i log p(y_i | y_−i) instead — Ci is replaced by
-    // 2G = −Z Zᵀ + β αᵀ + α βᵀ (kernels.hpp, loo_*), the same gradient kernels run with a zeroed α, and dy = −β.
-    const long n = x->n;
-    const int d = x->d;
-    gp_post post{};
-    post.ctx = c;
-    FitOut fo;
-    std::vector<T> alpha_h((size_t)n * ncols);
-    RC(fit_impl<T>(c, k, x, noise, mean, y, ncols > 1 ? ldy : n, ncols, fo, &post, alpha_h.data(), ks));
-    SkScope sk(c);
+static int32_t grad_open(hipStream_t s, DevBufs& bufs, const gp_post& post, bool want_dx, T** W, T** Ci, GradOut<T>& go) {
+    const long np = post.np;
+    const KSum* ks = post.kern.desc().ks;
+    go.g_h.assign((size_t)(2 + (ks ? ks->nth : std::max(post.kern.nscale(), 1))), 0.0);
+    go.dn_h.resize((size_t)post.n);
+    go.gx_h.resize(want_dx ? (size_t)post.d * np : 0);
+    const size_t M_b = sizeof(T) * (size_t)(np + 128) * post.ld;
+    void *W_v = nullptr, *Ci_v = nullptr;
+    RC(bufs.get(M_b, &W_v));
+    RC(bufs.get(M_b, &Ci_v));
+    RC(bufs.get(sizeof(double) * go.g_h.size(), &go.g_v));
+    RC(bufs.get(sizeof(T) * (size_t)np, &go.dn_v));
+    HIPCHK(hipMemsetAsync(go.g_v, 0, sizeof(double) * go.g_h.size(), s));
+    RC(go.sc.stage(bufs, post.kern.nscale(), post.kern.scale.data(), s));  // (the scales' block in front of gx's: the order the cache has always seen)
+    if (want_dx) RC(bufs.get(sizeof(double) * go.gx_h.size(), &go.gx_v));
+    *W = (T*)W_v;
+    *Ci = (T*)Ci_v;
+    return 0;
+}
+// (a) W = L⁻ᵀ, Ci = −W Wᵀ = −C⁻¹ (lower; no sign fold: the kernels of (e) add what the product left — kernels.hpp).  Ci is written in full by the product
+// (beta0: C is overwritten, not read), as W is by factor_inv_t: only the 128 slack rows the GEMM over-reads need defined values
+template <typename T>
+static int32_t grad_inverse(gp_ctx* c, hipStream_t s, DevBufs& bufs, const gp_post& post, T* W, T* Ci) {
     const long np = post.np, ld = post.ld;
-    hipStream_t s = c->sm;
-    void *W_v = 0, *Ci_v = 0, *g_v = 0, *dn_v = 0, *sc_v = 0, *gx_v = 0, *a0_v = 0;
-    const T* alpha_g = (const T*)post.alpha;  // the α vector of the gradient kernels' weights α_i α_j + Ci_ij
-    const size_t gx_b = sizeof(double) * (size_t)d * np;
-    std::vector<double> gx_h(dx ? (size_t)d * np : 0);
-    const int nsc = std::max(k->nscale, 1);
-    const int ng = ks ? ks->nth : nsc;  // g[2 + p]: ∂/∂scale_p, or ∂/∂θ_p of a composite kernel
-    const size_t M_b = sizeof(T) * (size_t)(np + 128) * ld, g_b = sizeof(double) * (size_t)(2 + ng), dn_b = sizeof(T) * (size_t)np;
-    const size_t sc_b = sizeof(double) * (size_t)nsc;
-    DevBufs bufs(c);
-    bufs.v.push_back(post.A);  // the temporary posterior's blocks go back to the cache with everything else
-    bufs.v.push_back(post.xs);
-    bufs.v.push_back(post.alpha);
-    std::vector<double> g_hv((size_t)(2 + ng), 0.0);  // [0] ∂/∂variance, [1] Σ_i ∂/∂Σy_ii, [2 + p] ∂/∂scale_p (∂/∂θ_p)
-    double* g_h = g_hv.data();
-    std::vector<T> dn_h((size_t)n);
-    std::vector<T> beta_h(loo ? (size_t)n : 0);  // leave-one-out: β = −∂L/∂y and the value Σ ℓ_i
-    double loo_sum_h = 0;
-    std::vector<double> sc_h((size_t)nsc, 1.0);
-    for (int p = 0; p < k->nscale; ++p) sc_h[p] = k->scale[p];
-    const int32_t rc = run_drained(c, [&]() -> int32_t {
-        RC(bufs.get(M_b, &W_v));
-        RC(bufs.get(M_b, &Ci_v));
-        RC(bufs.get(g_b, &g_v));
-        RC(bufs.get(dn_b, &dn_v));
-        RC(bufs.get(sc_b, &sc_v));
-        if (dx) RC(bufs.get(gx_b, &gx_v));
-        T* W = (T*)W_v;
-        T* Ci = (T*)Ci_v;
-        HIPCHK(hipMemsetAsync(g_v, 0, g_b, s));
-        HIPCHK(hipMemcpyAsync(sc_v, sc_h.data(), sc_b, hipMemcpyHostToDevice, s));
-        // Ci is written in full by the product below (beta0: C is overwritten, not read), as W is by factor_inv_t: only the 128 slack rows the GEMM
-        // over-reads need defined values
-        HIPCHK(hipMemsetAsync(Ci + np * ld, 0, sizeof(T) * (size_t)128 * ld, s));
-        RC(factor_inv_t<T>(c, s, bufs, post, W));
-        {
-            GridMap gw = plain_map(1, 0, 0);
-            gw.ktri = 2;                                                                   // W upper: k starts at the row tile
-            gw.beta0 = 1;                                                                  // Ci is overwritten (its upper tiles are never read)
-            RC(launch_gemm<T>(c, s, Ci, ld, W, ld, W, ld, np, np, np, gw));                // Ci = −W Wᵀ = −C⁻¹ (lower), read as it is
-        }
-        // (no sign fold: the kernels below add the −C⁻¹ the product left — kernels.hpp)
-        dim3 grid((unsigned)(np / 128), (unsigned)(np / 128));
-        if (ncols > 1) {
-            hipLaunchKernelGGL(cols_weight_kernel<T>, grid, dim3(256), 0, s, Ci, ld, (const T*)post.alpha, np, ncols);
+    HIPCHK(hipMemsetAsync(Ci + np * ld, 0, sizeof(T) * (size_t)128 * ld, s));
+    RC(factor_inv_t<T>(c, s, bufs, post, W));
+    GridMap gw = plain_map(1, 0, 0);
+    gw.ktri = 2;   // W upper: k starts at the row tile
+    gw.beta0 = 1;  // Ci is overwritten (its upper tiles are never read)
+    return launch_gemm<T>(c, s, Ci, ld, W, ld, W, ld, np, np, np, gw);
+}
+// (d) the vector a of a folded objective: np zeros
+template <typename T>
+static int32_t zeroed_alpha(hipStream_t s, DevBufs& bufs, long np, const T** a0) {
+    void* a0_v = nullptr;
+    RC(bufs.get(sizeof(T) * (size_t)np, &a0_v));
+    HIPCHK(hipMemsetAsync(a0_v, 0, sizeof(T) * (size_t)np, s));
+    *a0 = (const T*)a0_v;
+    return 0;
+}
+// (b) Σ_s logpdf(fx, y[:, s]) over the post.ncols columns of the fit: Ci ← ncols·Ci + Σ_s α_s α_sᵀ (kernels.hpp cols_weight_kernel)
+template <typename T>
+static int32_t fold_cols(hipStream_t s, DevBufs& bufs, const gp_post& post, T* Ci, const T** a0) {
+    const long np = post.np;
+    hipLaunchKernelGGL(cols_weight_kernel<T>, dim3((unsigned)(np / 128), (unsigned)(np / 128)), dim3(256), 0, s, Ci, post.ld, (const T*)post.alpha, np, post.ncols);
+    HIPCHK(hipGetLastError());
+    return zeroed_alpha<T>(s, bufs, np, a0);
+}
+// (c) the leave-one-out objective L = Σ_i log p(y_i | y_−i): Ci ← 2G = −Z Zᵀ + β αᵀ + α βᵀ (kernels.hpp, loo_*).  W is used up (Z takes its block).
+// The value and β = −∂L/∂y are on their way to `out` when it returns.
+template <typename T> struct LooFold {
+    std::vector<T> beta_h;
+    double sum_h = 0;
+};
+template <typename T>
+static int32_t fold_loo(gp_ctx* c, hipStream_t s, DevBufs& bufs, const gp_post& post, const T* y_h, T* W, T* Ci, LooFold<T>& out, const T** a0) {
+    const long n = post.n, np = post.np, ld = post.ld;
+    const T* L = (const T*)post.A;
+    out.beta_h.resize((size_t)n);
+    void *b_v = 0, *d_v = 0;
+    RC(bufs.get(sizeof(T) * (size_t)np, &b_v));
+    RC(bufs.get(sizeof(T) * (size_t)np, &d_v));
+    T* terms = nullptr;
+    double* sum = nullptr;
+    RC(loo_terms<T>(c, s, bufs, post, (const T*)W, y_h, &terms, (T*)b_v, (T*)d_v, &sum));                        // c_i from W, before Z takes its place
+    HIPCHK(hipMemcpyAsync(&out.sum_h, sum, sizeof(double), hipMemcpyDeviceToHost, s));
+    RC(trsv<T>(c, s, L, ld, np, (T*)b_v, np, 1, true));                                                          // β = C⁻¹ b = L⁻ᵀ (L⁻¹ b), in place
+    RC(trsv<T>(c, s, L, ld, np, (T*)b_v, np, 1, false));
+    HIPCHK(hipMemcpyAsync(out.beta_h.data(), b_v, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, s));
+    hipLaunchKernelGGL(loo_mirror_scale_kernel<T>, dim3((unsigned)(np / 64), (unsigned)(np / 64)), dim3(256), 0, s, (const T*)Ci, ld, (const T*)d_v, W, ld);  // Z = Ci diag(d), full
+    HIPCHK(hipGetLastError());
+    GridMap gz = plain_map(1, 0, 0);
+    gz.beta0 = 1;
+    RC(launch_gemm<T>(c, s, Ci, ld, W, ld, W, ld, np, np, np, gz));                                              // Ci = −Z Zᵀ (lower)
+    hipLaunchKernelGGL(loo_fold_kernel<T>, dim3((unsigned)(np / 128), (unsigned)(np / 128)), dim3(256), 0, s, Ci, ld, (const T*)post.alpha, (const T*)b_v);  // += β αᵀ + α βᵀ
+    HIPCHK(hipGetLastError());
+    return zeroed_alpha<T>(s, bufs, np, a0);
+}
+// (e) the contraction: ∂/∂variance and ∂/∂scale (∂/∂θ), ∂/∂Σy (a dense one straight to the caller's n×n array dnoise_dense), ∂/∂x when go has room for
+// it; then the downloads and the synchronise
+template <typename T, int ND>
+static void launch_kgrad_fast(dim3 grid, hipStream_t s, const gp_post& post, const T* Ci, const double* sc, const T* a, double* g) {
+    hipLaunchKernelGGL((kgrad_fast_kernel<T, ND>), grid, dim3(256), 0, s, Ci, post.ld, (const T*)post.xs, post.np, post.d, post.kern.kind, (T)post.kern.variance,
+                       post.kern.nscale(), sc, a, post.n, g);
+}
+template <typename T>
+static int32_t grad_contract(gp_ctx* c, hipStream_t s, DevBufs& bufs, const gp_post& post, const T* Ci, const T* a, T* dnoise_dense, GradOut<T>& go) {
+    const long n = post.n, np = post.np, ld = post.ld;
+    const int d = post.d, nscale = post.kern.nscale();
+    const KSum* ks = post.kern.desc().ks;
+    const T* xs = (const T*)post.xs;
+    const T variance = (T)post.kern.variance;
+    double* g = (double*)go.g_v;
+    const dim3 grid((unsigned)(np / 128), (unsigned)(np / 128));
+    if (ks) {  // composite kernel: one launch per chunk of 16 θ entries
+        for (int p0 = 0; p0 < ks->nth; p0 += 16) {
+            launch_kgrad_sum<T>(grid, s, Ci, ld, xs, np, d, *ks, a, n, g, p0);
             HIPCHK(hipGetLastError());
-            RC(bufs.get(dn_b, &a0_v));
-            HIPCHK(hipMemsetAsync(a0_v, 0, dn_b, s));
-            alpha_g = (const T*)a0_v;
         }
-        if (loo) {
-            void *b_v = 0, *d_v = 0;
-            RC(bufs.get(dn_b, &b_v));
-            RC(bufs.get(dn_b, &d_v));
-            T* terms = nullptr;
-            double* sum = nullptr;
-            RC(loo_terms<T>(c, s, bufs, post, (const T*)W, (const T*)y, &terms, (T*)b_v, (T*)d_v, &sum));   // c_i from W, before Z takes its place
-            HIPCHK(hipMemcpyAsync(&loo_sum_h, sum, sizeof(double), hipMemcpyDeviceToHost, s));
-            RC(trsv<T>(c, s, (const T*)post.A, ld, np, (T*)b_v, np, 1, true));                               // β = C⁻¹ b = L⁻ᵀ (L⁻¹ b), in place
-            RC(trsv<T>(c, s, (const T*)post.A, ld, np, (T*)b_v, np, 1, false));
-            HIPCHK(hipMemcpyAsync(beta_h.data(), b_v, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, s));
-            hipLaunchKernelGGL(loo_mirror_scale_kernel<T>, dim3((unsigned)(np / 64), (unsigned)(np / 64)), dim3(256), 0, s, (const T*)Ci, ld, (const T*)d_v,
-                               W, ld);                                                                       // Z = Ci diag(d), full, into W's block
+    } else if (d <= 16 && (ld * (long)sizeof(T)) % 16 == 0) {  // the scratch-free form (16-byte loads of the weights): a single launch whatever the scales are
+        if (d <= 4) launch_kgrad_fast<T, 4>(grid, s, post, Ci, go.sc.ptr(), a, g);
+        else if (d <= 8) launch_kgrad_fast<T, 8>(grid, s, post, Ci, go.sc.ptr(), a, g);
+        else launch_kgrad_fast<T, 16>(grid, s, post, Ci, go.sc.ptr(), a, g);
+        HIPCHK(hipGetLastError());
+    } else {  // one launch per chunk of 16 ARD scales
+        for (int p0 = 0; p0 < std::max(nscale, 1); p0 += 16) {
+            hipLaunchKernelGGL(kgrad_kernel<T>, grid, dim3(256), 0, s, Ci, ld, xs, np, d, post.kern.kind, variance, nscale, go.sc.ptr(), a, n, g, p0);
             HIPCHK(hipGetLastError());
-            GridMap gz = plain_map(1, 0, 0);
-            gz.beta0 = 1;
-            RC(launch_gemm<T>(c, s, Ci, ld, W, ld, W, ld, np, np, np, gz));                                  // Ci = −Z Zᵀ (lower)
-            hipLaunchKernelGGL(loo_fold_kernel<T>, grid, dim3(256), 0, s, Ci, ld, (const T*)post.alpha, (const T*)b_v);  // += β αᵀ + α βᵀ: Ci = 2G
-            HIPCHK(hipGetLastError());
-            RC(bufs.get(dn_b, &a0_v));
-            HIPCHK(hipMemsetAsync(a0_v, 0, dn_b, s));
-            alpha_g = (const T*)a0_v;
         }
-        // one launch per chunk of 16 ARD scales (a single launch for scalar / no transform, whatever D is)
-#define GPMI_KGRAD_FAST(ND_)                                                                                                                  \
-    hipLaunchKernelGGL((kgrad_fast_kernel<T, ND_>), grid, dim3(256), 0, s, (const T*)Ci, ld, (const T*)post.xs, np, d, post.kern.kind, (T)post.kern.variance, \
-                       post.kern.nscale(), (const double*)sc_v, alpha_g, n, (double*)g_v)
-        if (ks) {  // composite kernel: one launch per chunk of 16 θ entries
-            for (int p0 = 0; p0 < ks->nth; p0 += 16) {
-                launch_kgrad_sum<T>(grid, s, (const T*)Ci, ld, (const T*)post.xs, np, d, *ks, alpha_g, n, (double*)g_v, p0);
-                HIPCHK(hipGetLastError());
-            }
-        } else if (d <= 16 && (ld * (long)sizeof(T)) % 16 == 0) {  // the scratch-free form (16-byte loads of the weights)
-            if (d <= 4) GPMI_KGRAD_FAST(4);
-            else if (d <= 8) GPMI_KGRAD_FAST(8);
-            else GPMI_KGRAD_FAST(16);
+    }
+    hipLaunchKernelGGL(noise_grad_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, Ci, ld, a, n, (T*)go.dn_v, g + 1);
+    HIPCHK(hipGetLastError());
+    if (dnoise_dense) RC(dense_grad_out<T>(c, s, bufs, Ci, ld, a, n, dnoise_dense));  // G = ½(a aᵀ + Ci), n×n
+    if (go.gx_v) {  // ∂/∂x: full-square pass (the mirrored Ci entry serves the tiles above the diagonal), 16 dimensions per launch
+        double* gx = (double*)go.gx_v;
+        HIPCHK(hipMemsetAsync(gx, 0, sizeof(double) * go.gx_h.size(), s));
+        if (ks) {  // composite kernel: post.xs holds the raw inputs, D <= 16 (pack_ksum), one launch
+            launch_kgradx_sum<T>(grid, s, Ci, ld, xs, np, d, *ks, a, n, gx, np);
             HIPCHK(hipGetLastError());
         } else {
-            for (int p0 = 0; p0 < (post.kern.nscale() > 1 ? post.kern.nscale() : 1); p0 += 16) {
-                hipLaunchKernelGGL(kgrad_kernel<T>, grid, dim3(256), 0, s, (const T*)Ci, ld, (const T*)post.xs, np, d, post.kern.kind,
-                                   (T)post.kern.variance, post.kern.nscale(), (const double*)sc_v, alpha_g, n, (double*)g_v, p0);
+            for (int p0 = 0; p0 < d; p0 += 16) {
+                hipLaunchKernelGGL(kgradx_kernel<T>, grid, dim3(256), 0, s, Ci, ld, xs, np, d, post.kern.kind, variance, nscale, go.sc.ptr(), a, n, gx, np, p0);
                 HIPCHK(hipGetLastError());
             }
         }
-#undef GPMI_KGRAD_FAST
-        hipLaunchKernelGGL(noise_grad_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const T*)Ci, ld,
-                           alpha_g, n, (T*)dn_v, (double*)g_v + 1);
-        HIPCHK(hipGetLastError());
-        if (dnoise && noise_dense(noise)) RC(dense_grad_out<T>(c, s, bufs, (const T*)Ci, ld, alpha_g, n, (T*)dnoise));  // G = ½(ααᵀ − C⁻¹), n×n
-        if (dx) {  // ∂/∂x: full-square pass (the mirrored C⁻¹ entry serves the tiles above the diagonal), 16 dimensions per launch
-            HIPCHK(hipMemsetAsync(gx_v, 0, gx_b, s));
-            if (ks) {  // composite kernel: post.xs holds the raw inputs, D <= 16 (pack_ksum), one launch
-                launch_kgradx_sum<T>(grid, s, (const T*)Ci, ld, (const T*)post.xs, np, d, *ks, alpha_g, n, (double*)gx_v, np);
-                HIPCHK(hipGetLastError());
-            } else {
-                for (int p0 = 0; p0 < d; p0 += 16) {
-                    hipLaunchKernelGGL(kgradx_kernel<T>, grid, dim3(256), 0, s, (const T*)Ci, ld, (const T*)post.xs, np, d, post.kern.kind,
-                                       (T)post.kern.variance, post.kern.nscale(), (const double*)sc_v, alpha_g, n, (double*)gx_v, np, p0);
-                    HIPCHK(hipGetLastError());
-                }
-            }
-            HIPCHK(hipMemcpyAsync(gx_h.data(), gx_v, gx_b, hipMemcpyDeviceToHost, s));
-        }
-        HIPCHK(hipMemcpyAsync(g_h, g_v, g_b, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(dn_h.data(), dn_v, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return 0;
-    });
-    if (rc != 0) return rc;
-    for (int col = 0; col < ncols; ++col) ((T*)logpdf_out)[col] = (T)fo.logpdf[col];
-    if (loo) {
-        *(T*)logpdf_out = (T)loo_sum_h;
-        for (long i = 0; i < n; ++i) alpha_h[i] = beta_h[i];  // dy = −β below
+        HIPCHK(hipMemcpyAsync(go.gx_h.data(), gx, sizeof(double) * go.gx_h.size(), hipMemcpyDeviceToHost, s));
     }
-    if (dvar) *dvar = g_h[0];
+    HIPCHK(hipMemcpyAsync(go.g_h.data(), g, sizeof(double) * go.g_h.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(go.dn_h.data(), go.dn_v, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+// (f) the results to the caller's arrays (any may be NULL).  dy_neg: what ∂/∂y is the negative of — α (n × ncols) or β; dnoise by the noise's kind
+// (a dense one was written by (e)); dx in the container layout of x (src/finite_gp_projection.jl:32-37)
+template <typename T>
+static void grad_scatter(const gp_post& post, const gp_points* x, const gp_noise* noise, const GradOut<T>& go, const std::vector<T>& dy_neg, double* dvar,
+                         double* dscale, double* dtheta, void* dnoise, void* dy, void* dx) {
+    const double* g = go.g_h.data();
+    const KSum* ks = post.kern.desc().ks;
+    if (dvar) *dvar = g[0];
     if (dscale)
-        for (int p = 0; p < k->nscale; ++p) dscale[p] = g_h[2 + p];
+        for (int p = 0; p < post.kern.nscale(); ++p) dscale[p] = g[2 + p];
     if (dtheta && ks)
-        for (int p = 0; p < ks->nth; ++p) dtheta[p] = g_h[2 + p];
-    if (dnoise) {
-        if (noise->kind == 0) *(T*)dnoise = (T)g_h[1];
-        else if (noise->kind == 1) memcpy(dnoise, dn_h.data(), sizeof(T) * (size_t)n);  // (dense: written above)
-    }
+        for (int p = 0; p < ks->nth; ++p) dtheta[p] = g[2 + p];
+    if (dnoise && noise->kind == 0) *(T*)dnoise = (T)g[1];
+    else if (dnoise && noise->kind == 1) memcpy(dnoise, go.dn_h.data(), sizeof(T) * (size_t)post.n);
     if (dy)
-        for (size_t i = 0; i < alpha_h.size(); ++i) ((T*)dy)[i] = -alpha_h[i];
-    if (dx) {  // same container layout as the inputs (src/finite_gp_projection.jl:32-37)
-        T* o = (T*)dx;
-        for (int dd = 0; dd < d; ++dd)
-            for (long i = 0; i < n; ++i) {
-                const T v = (T)gx_h[(size_t)dd * np + i];
-                if (x->layout == 0) o[i] = v;
-                else if (x->layout == 1) o[(long)dd + i * d] = v;
-                else o[i + (long)dd * n] = v;
-            }
-    }
+        for (size_t i = 0; i < dy_neg.size(); ++i) ((T*)dy)[i] = -dy_neg[i];
+    if (dx) grad_to_layout<T>(x->layout, post.n, post.d, go.gx_h.data(), post.np, dx);
+}
+
+// gp_logpdf_grad (ncols = 1, ldy = n) and gp_logpdf_grad_cols (ks != NULL: their _sum forms, ∂/∂θ into dtheta): Y is n×ncols with leading dimension ldy, the gradients are those of
+// Σ_s logpdf(fx, Y[:, s]); logpdf_out: ncols entries, dY: n×ncols.  One column has nothing to fold: the contraction runs on −C⁻¹ with α itself.  (ldy goes to fit_impl as given, also for ncols = 1 where the driver before this one passed n: a single column is never stepped over, the reads are the same.)
+template <typename T>
+static int32_t grad_logpdf_cols(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* Y, long ldy, int ncols,
+                                void* logpdf_out, double* dvar, double* dscale, void* dnoise, void* dY, void* dx, const KSum* ks, double* dtheta) {
+    DevBufs bufs(c);
+    TempPost<T> tp(c);
+    std::vector<T> alpha_h((size_t)x->n * ncols);
+    RC(tp.fit(k, x, noise, mean, Y, ldy, ncols, alpha_h.data(), ks));
+    const gp_post& post = tp.post;
+    SkScope sk(c);
+    GradOut<T> go;
+    RC(run_drained(c, [&]() -> int32_t {
+        T *W = nullptr, *Ci = nullptr;
+        const T* a = (const T*)post.alpha;
+        RC(grad_open<T>(c->sm, bufs, post, dx != nullptr, &W, &Ci, go));
+        RC(grad_inverse<T>(c, c->sm, bufs, post, W, Ci));
+        if (ncols > 1) RC(fold_cols<T>(c->sm, bufs, post, Ci, &a));
+        return grad_contract<T>(c, c->sm, bufs, post, Ci, a, noise_dense(noise) ? (T*)dnoise : nullptr, go);
+    }));
+    for (int col = 0; col < ncols; ++col) ((T*)logpdf_out)[col] = (T)tp.fo.logpdf[col];
+    grad_scatter<T>(post, x, noise, go, alpha_h, dvar, dscale, dtheta, dnoise, dY, dx);
+    return 0;
+}
+// gp_loo_grad: value_out = L = Σ_i log p(y_i | y_−i), dy = −β
+template <typename T>
+static int32_t grad_loo(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, void* value_out,
+                        double* dvar, double* dscale, void* dnoise, void* dy, void* dx, const KSum* ks, double* dtheta) {
+    DevBufs bufs(c);
+    TempPost<T> tp(c);
+    std::vector<T> alpha_h((size_t)x->n);  // (the fit hands α back as it does for gp_logpdf_grad; nothing here reads it)
+    RC(tp.fit(k, x, noise, mean, y, x->n, 1, alpha_h.data(), ks));
+    const gp_post& post = tp.post;
+    SkScope sk(c);
+    GradOut<T> go;
+    LooFold<T> lf;
+    RC(run_drained(c, [&]() -> int32_t {
+        T *W = nullptr, *Ci = nullptr;
+        const T* a = nullptr;
+        RC(grad_open<T>(c->sm, bufs, post, dx != nullptr, &W, &Ci, go));
+        RC(grad_inverse<T>(c, c->sm, bufs, post, W, Ci));
+        RC(fold_loo<T>(c, c->sm, bufs, post, (const T*)y, W, Ci, lf, &a));
+        return grad_contract<T>(c, c->sm, bufs, post, Ci, a, noise_dense(noise) ? (T*)dnoise : nullptr, go);
+    }));
+    *(T*)value_out = (T)lf.sum_h;
+    grad_scatter<T>(post, x, noise, go, lf.beta_h, dvar, dscale, dtheta, dnoise, dy, dx);
     return 0;
 }
 
@@ -2063,26 +2151,23 @@ static int32_t update_impl(gp_post* old, const gp_points* x2, const gp_noise* no
     if (!c->info_dev) HIPCHK(hipMalloc((void**)&c->info_dev, sizeof(int)));
     RC(ctx_scal(c, 16));
 
-    std::vector<T> x2s_h;
-    scale_points<T>(&k, x2, n2p, x2s_h);  // [d][n2p]
+    StagedPoints<T> sx2;  // [d][n2p]
     std::vector<T> noise_h((size_t)n2p, T(0));
     for (long i = 0; i < n2; ++i) noise_h[i] = noise_entry<T, T>(noise2, i);
     std::vector<T> delta_h((size_t)np, T(0));
     memcpy(delta_h.data(), delta_all, sizeof(T) * (size_t)n);
 
-    void *A_v = 0, *xs_v = 0, *alpha_v = 0, *X_v = 0, *S_v = 0, *x2_v = 0, *nz_v = 0;
+    void *A_v = 0, *xs_v = 0, *alpha_v = 0, *X_v = 0, *S_v = 0, *nz_v = 0;
     const long ldx = np1 + c->ldpad, lds = n2p + c->ldpad;
     const size_t A_b = sizeof(T) * (size_t)(mtot + 128) * ld, xs_b = sizeof(T) * (size_t)d * np, v_b = sizeof(T) * (size_t)np;
     const size_t X_b = sizeof(T) * (size_t)(n2p + 128) * ldx, S_b = sizeof(T) * (size_t)(n2p + 128) * lds;
-    const size_t x2_b = sizeof(T) * (size_t)d * n2p, nz_b = sizeof(T) * (size_t)n2p;
+    const size_t nz_b = sizeof(T) * (size_t)n2p;
     DevBufs bufs(c);
     RC(bufs.get(A_b, &A_v));
     RC(bufs.get(xs_b, &xs_v));
     RC(bufs.get(v_b, &alpha_v));
     RC(bufs.get(X_b, &X_v));
     RC(bufs.get(S_b, &S_v));
-    RC(bufs.get(x2_b, &x2_v));
-    RC(bufs.get(nz_b, &nz_v));
     T* A = (T*)A_v;
     T* X = (T*)X_v;
     T* S = (T*)S_v;
@@ -2090,27 +2175,22 @@ static int32_t update_impl(gp_post* old, const gp_points* x2, const gp_noise* no
     int info_h = 0;
     double scal_h[16] = {0};
     int32_t rc = run_drained(c, [&]() -> int32_t {
-        HIPCHK(hipMemcpyAsync(x2_v, x2s_h.data(), x2_b, hipMemcpyHostToDevice, s));
+        RC(sx2.stage(c, bufs, &k, x2, n2p));
+        RC(bufs.get(nz_b, &nz_v));
         HIPCHK(hipMemcpyAsync(nz_v, noise_h.data(), nz_b, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemsetAsync(c->info_dev, 0, sizeof(int), s));
         HIPCHK(hipMemsetAsync(c->scal_dev, 0, sizeof(double) * 16, s));
         // combined scaled inputs [d][np]: old block, then the new points
         HIPCHK(hipMemsetAsync(xs_v, 0, xs_b, s));
         HIPCHK(hipMemcpy2DAsync(xs_v, sizeof(T) * np, old->xs, sizeof(T) * np1, sizeof(T) * n1, d, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpy2DAsync((T*)xs_v + n1, sizeof(T) * np, x2_v, sizeof(T) * n2p, sizeof(T) * n2, d, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpy2DAsync((T*)xs_v + n1, sizeof(T) * np, sx2.ptr(), sizeof(T) * n2p, sizeof(T) * n2, d, hipMemcpyDeviceToDevice, s));
         // X = K(x2, x1) (n2p × np1; padding rows / columns zero), then X ← X L11⁻ᵀ = U12ᵀ                  :39
-        {
-            GridMap g = plain_map(0, 0, 0);
-            dim3 grid((unsigned)(np1 / 128), (unsigned)(n2p / 128));
-            gram<T>(old->kern.desc(), grid, s, X, ldx, (const T*)x2_v, n2p, (const T*)old->xs, np1, d, (const T*)nullptr, n2, n1, 0, g);
-            HIPCHK(hipGetLastError());
-        }
-        RC(trsm_post<T>(old, s, X, ldx, n2p, bufs));
+        RC(cross_solve<T>(old, s, bufs, sx2.ptr(), n2, n2p, 0, n2p, X, ldx));
         // S = C22 − U12ᵀ U12 (lower), chol(S) = U22ᵀ                                                       :40
         {
             GridMap g = plain_map(1, 0, 0);
             dim3 grid((unsigned)(n2p / 128), (unsigned)(n2p / 128));
-            gram<T>(old->kern.desc(), grid, s, S, lds, (const T*)x2_v, n2p, (const T*)x2_v, n2p, d, (const T*)nz_v, n2, n2, 1, g);
+            gram<T>(old->kern.desc(), grid, s, S, lds, sx2.ptr(), n2p, sx2.ptr(), n2p, d, (const T*)nz_v, n2, n2, 1, g);
             HIPCHK(hipGetLastError());
         }
         RC(launch_gemm<T>(c, s, S, lds, X, ldx, X, ldx, n2p, n2p, np1, plain_map(1, 0, 0)));
@@ -2219,16 +2299,16 @@ static int32_t post_joint(gp_post* post, const gp_points* xs, const void* pm, co
                           Joint<T>& J) {
     gp_ctx* c = post->ctx;
     SkScope sk(c);
-    const long n = post->n, np = post->np, ld = post->ld;
+    const long np = post->np;
     const long ns = xs->n, nsp = round_up(ns, 128);
     const int d = post->d;
     const gp_kernel k = post->kern.view(post->dtype);
-    std::vector<T> xs_h, nz_h;
-    scale_points<T>(&k, xs, nsp, xs_h);
+    StagedPoints<T> sx;
+    std::vector<T> nz_h, m_h;
     noise_to<T, T>(noise, ns, nsp, nz_h);
     const long ldx = np + c->ldpad, ldc = nsp + c->ldpad;
-    void *xs_v = 0, *m_v = 0, *X_v = 0, *nz_v = 0;
-    RC(bufs.get(sizeof(T) * (size_t)d * nsp, &xs_v));
+    void *m_v = 0, *X_v = 0, *nz_v = 0;
+    RC(sx.stage(c, bufs, &k, xs, nsp));
     RC(bufs.get(sizeof(T) * (size_t)nsp, &m_v));
     RC(bufs.get(sizeof(T) * (size_t)nsp, &nz_v));
     RC(bufs.get(sizeof(T) * (size_t)(nsp + 128) * ldx, &X_v));
@@ -2239,32 +2319,21 @@ static int32_t post_joint(gp_post* post, const gp_points* xs, const void* pm, co
     hipStream_t s = c->sm;
     c->ev_used = 0;
     c->gemm_recs.clear();
-    std::vector<T> m_h((size_t)ns);
-    HIPCHK(hipMemcpyAsync(xs_v, xs_h.data(), sizeof(T) * (size_t)d * nsp, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(nz_v, nz_h.data(), sizeof(T) * (size_t)nsp, hipMemcpyHostToDevice, s));
-    kvec<T>(post->kern.desc(), ns, s, (const T*)xs_v, nsp, (const T*)post->xs, np, d, n, (const T*)post->alpha, (T*)m_v);  // K_*x α
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(m_h.data(), m_v, sizeof(T) * (size_t)ns, hipMemcpyDeviceToHost, s));
-    {
-        GridMap g = plain_map(0, 0, 0);
-        dim3 grid((unsigned)(np / 128), (unsigned)(nsp / 128));
-        gram<T>(post->kern.desc(), grid, s, X, ldx, (const T*)xs_v, nsp, (const T*)post->xs, np, d, (const T*)nullptr, ns, n, 0, g);
-        HIPCHK(hipGetLastError());
-    }
-    RC(trsm_post<T>(post, s, X, ldx, nsp, bufs));                                                              // V ᵀ = K_*x L⁻ᵀ
+    RC(post_mean<T>(post, s, sx.ptr(), ns, nsp, (T*)m_v, m_h));                                                // K_*x α
+    RC(cross_solve<T>(post, s, bufs, sx.ptr(), ns, nsp, 0, nsp, X, ldx));                                      // V ᵀ = K_*x L⁻ᵀ
     {
         GridMap g = plain_map(1, 0, 0);
         dim3 grid((unsigned)(nsp / 128), (unsigned)(nsp / 128));
-        gram<T>(post->kern.desc(), grid, s, Cm, ldc, (const T*)xs_v, nsp, (const T*)xs_v, nsp, d, (const T*)nz_v, ns, ns, 1, g);
+        gram<T>(post->kern.desc(), grid, s, Cm, ldc, sx.ptr(), nsp, sx.ptr(), nsp, d, (const T*)nz_v, ns, ns, 1, g);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipMemsetAsync(Cm + nsp * ldc, 0, sizeof(T) * (size_t)(R + 128) * ldc, s));
     RC(launch_gemm<T>(c, s, Cm, ldc, X, ldx, X, ldx, nsp, nsp, np, plain_map(1, 0, 0)));                       // K** + Σy* − VᵀV
     if (noise_dense(noise)) RC((dense_add<T, T>(c, bufs, Cm, ldc, noise, ns)));                                // a dense Σy*
     HIPCHK(hipStreamSynchronize(s));
-    const T* prior_mean = (const T*)pm;
     J.mean.resize((size_t)ns);
-    for (long i = 0; i < ns; ++i) J.mean[i] = (double)(prior_mean ? prior_mean[i] : T(0)) + (double)m_h[i];
+    add_prior_mean<T, double>((const T*)pm, m_h, J.mean.data());
     return 0;
 }
 
@@ -2277,7 +2346,7 @@ static int32_t post_joint_dist(gp_post* post, const gp_points* xs, const void* p
     const int d = post->d;
     const gp_kernel k = post->kern.view(0);
     std::vector<double> m_h((size_t)ns), xs_n, xs_p, nz_h;
-    RC(predict_impl<double>(post, xs, pm, 1, m_h.data(), nullptr, nullptr));   // m(x*) + K_*x α (no factor involved)
+    RC(predict_impl<double>(post, xs, pm, 1, m_h.data(), nullptr, nullptr, false));   // m(x*) + K_*x α (no factor involved)
     scale_points<double>(&k, xs, ns, xs_n);
     scale_points<double>(&k, xs, nsp, xs_p);
     noise_to<double, double>(noise, ns, nsp, nz_h);
@@ -2721,21 +2790,16 @@ template <class K> static int32_t kernelmatrix_any(gp_ctx* c, const K* k, const 
         const gp_points* rp = y ? y : x;
         const long n = x->n, m = rp->n, np = round_up(n, 128), mp = round_up(m, 128);
         const long ld = np + c->ldpad;
-        std::vector<T> xc_h, xr_h;
-        scale_points<T>(&rk.k, x, np, xc_h);
-        if (y) scale_points<T>(&rk.k, y, mp, xr_h);
-        void *xc_v = nullptr, *xr_v = nullptr, *K_v = nullptr;
-        const size_t xcb = sizeof(T) * xc_h.size(), xrb = sizeof(T) * xr_h.size(), Kb = sizeof(T) * (size_t)mp * ld;
+        StagedPoints<T> xc, xr;
+        void* K_v = nullptr;
         DevBufs bufs(c);
-        RC(bufs.get(xcb, &xc_v));
-        if (y) RC(bufs.get(xrb, &xr_v));
-        RC(bufs.get(Kb, &K_v));
         return run_drained(c, [&]() -> int32_t {
-            HIPCHK(hipMemcpyAsync(xc_v, xc_h.data(), xcb, hipMemcpyHostToDevice, c->sm));
-            if (y) HIPCHK(hipMemcpyAsync(xr_v, xr_h.data(), xrb, hipMemcpyHostToDevice, c->sm));
+            RC(xc.stage(c, bufs, &rk.k, x, np));
+            if (y) RC(xr.stage(c, bufs, &rk.k, y, mp));
+            RC(bufs.get(sizeof(T) * (size_t)mp * ld, &K_v));
             GridMap g = plain_map(0, 0, 0);
             dim3 grid((unsigned)(np / 128), (unsigned)(mp / 128));
-            gram<T>(KDesc{rk.k.kind, rk.k.variance, rk.sum()}, grid, c->sm, (T*)K_v, ld, (const T*)(y ? xr_v : xc_v), y ? mp : np, (const T*)xc_v, np,
+            gram<T>(KDesc{rk.k.kind, rk.k.variance, rk.sum()}, grid, c->sm, (T*)K_v, ld, y ? xr.ptr() : xc.ptr(), y ? mp : np, xc.ptr(), np,
                     x->d, (const T*)nullptr, m, n, 0, g);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpy2DAsync(out, sizeof(T) * n, K_v, sizeof(T) * ld, sizeof(T) * n, m, hipMemcpyDeviceToHost,
@@ -2822,14 +2886,14 @@ static int32_t logpdf_grad_cols_any(gp_ctx* c, const K* k, const gp_points* x, c
     if (!logpdf_out) return set_arg_err(9, "logpdf_out is NULL");
     HIPCHK(hipSetDevice(c->device));
     return by_dtype(rk.k.dtype, [&](auto t) {
-        return grad_impl<decltype(t)>(c, &rk.k, x, noise, mean, Y, logpdf_out, dvar, dscale, dnoise, dY, dx, rk.sum(), dtheta, (long)ldy, ncols);
+        return grad_logpdf_cols<decltype(t)>(c, &rk.k, x, noise, mean, Y, (long)ldy, ncols, logpdf_out, dvar, dscale, dnoise, dY, dx, rk.sum(), dtheta);
     });
 }
 
 // single kind: dvar / dscale / dx, dtheta NULL; composite: dtheta (one entry per θ entry) and dx, dvar / dscale NULL
 template <class K>
 static int32_t logpdf_grad_any(gp_ctx* c, const K* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, void* logpdf_out,
-                               double* dvar, double* dscale, void* dnoise, void* dy, void* dx, double* dtheta, bool loo = false) {
+                               double* dvar, double* dscale, void* dnoise, void* dy, void* dx, double* dtheta, bool loo) {
     Guard gd(c);
     if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     ResolvedKernel rk;
@@ -2838,7 +2902,9 @@ static int32_t logpdf_grad_any(gp_ctx* c, const K* k, const gp_points* x, const 
     if (!logpdf_out) return set_arg_err(7, loo ? "value_out is NULL" : "logpdf_out is NULL");
     HIPCHK(hipSetDevice(c->device));
     return by_dtype(rk.k.dtype, [&](auto t) {
-        return grad_impl<decltype(t)>(c, &rk.k, x, noise, mean, y, logpdf_out, dvar, dscale, dnoise, dy, dx, rk.sum(), dtheta, 0, 1, loo);
+        using T = decltype(t);
+        if (loo) return grad_loo<T>(c, &rk.k, x, noise, mean, y, logpdf_out, dvar, dscale, dnoise, dy, dx, rk.sum(), dtheta);
+        return grad_logpdf_cols<T>(c, &rk.k, x, noise, mean, y, x->n, 1, logpdf_out, dvar, dscale, dnoise, dy, dx, rk.sum(), dtheta);  // one column
     });
 }
 
@@ -2935,16 +3001,16 @@ int32_t gp_logpdf_grad_cols_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x,
 
 int32_t gp_logpdf_grad(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y,
                        void* logpdf_out, double* dvar, double* dscale, void* dnoise, void* dy, void* dx) {
-    return logpdf_grad_any(c, k, x, noise, mean, y, logpdf_out, dvar, dscale, dnoise, dy, dx, nullptr);
+    return logpdf_grad_any(c, k, x, noise, mean, y, logpdf_out, dvar, dscale, dnoise, dy, dx, nullptr, false);
 }
 int32_t gp_logpdf_grad_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y,
                            void* logpdf_out, double* dtheta, void* dnoise, void* dy) {
-    return logpdf_grad_any(c, k, x, noise, mean, y, logpdf_out, nullptr, nullptr, dnoise, dy, nullptr, dtheta);
+    return logpdf_grad_any(c, k, x, noise, mean, y, logpdf_out, nullptr, nullptr, dnoise, dy, nullptr, dtheta, false);
 }
 
 int32_t gp_logpdf_grad_sum_x(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y,
                              void* logpdf_out, double* dtheta, void* dnoise, void* dy, void* dx) {
-    return logpdf_grad_any(c, k, x, noise, mean, y, logpdf_out, nullptr, nullptr, dnoise, dy, dx, dtheta);
+    return logpdf_grad_any(c, k, x, noise, mean, y, logpdf_out, nullptr, nullptr, dnoise, dy, dx, dtheta, false);
 }
 
 int32_t gp_loo(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, void* value_out, void* lp_out,
@@ -3031,7 +3097,7 @@ int32_t gp_posterior_predict(gp_post* post, const gp_points* xs, const void* pm,
     if ((what & 6) && multi_can_solve(post) && (!(what & 4) || xs->n <= 4096)) {
         // multi-device fit whose factor still lives as block-cyclic pieces: variances and (up to 4 096 test points) the full
         // covariance come from a forward solve ON the pieces (multi.hip: multi_predict_var) — no gather; the mean needs α only
-        if (what & 1) RC(predict_impl<double>(post, xs, pm, 1, mean_out, nullptr, nullptr));
+        if (what & 1) RC(predict_impl<double>(post, xs, pm, 1, mean_out, nullptr, nullptr, false));
         const gp_kernel k = post->kern.view(0);
         const long ns = xs->n;
         std::vector<double> xs_h;
@@ -3059,7 +3125,7 @@ int32_t gp_posterior_predict(gp_post* post, const gp_points* xs, const void* pm,
         return 0;
     }
     if (what & 6) RC(multi_gather(post));  // multi-device fit: the factor is assembled on this device on first need
-    return by_dtype(post->dtype, [&](auto t) { return predict_impl<decltype(t)>(post, xs, pm, what, mean_out, var_out, cov_out); });
+    return by_dtype(post->dtype, [&](auto t) { return predict_impl<decltype(t)>(post, xs, pm, what, mean_out, var_out, cov_out, false); });
 }
 
 int32_t gp_posterior_ncols(gp_post* post, int32_t* out) {
@@ -3223,7 +3289,7 @@ int32_t gp_vfe_fit(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_p
     std::unique_ptr<gp_vfe> p(out ? new gp_vfe() : nullptr);  // out == NULL: the objective only, no handle
     if (p) p->ctx = c;
     double obj = 0;
-    RC(by_dtype(k->dtype, [&](auto t) { return vfe_fit_impl<decltype(t)>(c, k, x, z, noise, jitter, mean, y, approx, p.get(), &obj); }));
+    RC(by_dtype(k->dtype, [&](auto t) { return vfe_fit_impl<decltype(t)>(c, k, x, z, noise, jitter, mean, y, approx, p.get(), &obj, nullptr, VFE_FIT); }));
     if (objective_out) put(objective_out, k->dtype, 0, obj);
     if (p) publish(c, p, out);
     return 0;

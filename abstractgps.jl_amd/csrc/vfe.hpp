@@ -75,29 +75,12 @@ static void vfe_release(gp_vfe* p) {  // under the ctx lock
     p->segs.clear();
 }
 
-// Iw ((mp + 256) × ld doubles, L_b bytes) ← L⁻ᵀ (upper, row-major) of the lower factor L: I · L⁻ᵀ by the restricted-row recursion.  "vfe_inv_nb" >= 128: the inverse
-// diagonal blocks of L all at once (dib_build: every launch of the restricted-row recursion carries the batch; L_bb⁻ᵀ lands on Iw's diagonal), then the levels
-// above them with ONE triangular-k GEMM per block — the mechanism of the gradient's L⁻ᵀ (grad_impl).  Used by the fit's prelude (inv(L_z)) and by vfe_grad_impl.
+// Iw ((mp + 256) × ld doubles, L_b bytes, zeroed first) ← L⁻ᵀ (upper, row-major) of the lower factor L (gpmi355.hip upper_inverse, the mechanism of the exact
+// gradient's L⁻ᵀ), with inverse diagonal blocks of "vfe_inv_nb" columns when that is >= 128.  Used by the fit's prelude (inv(L_z)) and by vfe_grad_impl.
 static int32_t vfe_upper_inverse(gp_ctx* c, hipStream_t s, const double* L, long ld, long mp, double* Iw, size_t L_b, DevBufs& bufs) {
     HIPCHK(hipMemsetAsync(Iw, 0, L_b, s));
-    hipLaunchKernelGGL(identity_kernel<double>, dim3((unsigned)((mp + 255) / 256), (unsigned)mp), dim3(256), 0, s, Iw, ld, mp);
-    HIPCHK(hipGetLastError());
     const long inb = c->vfe_inv_nb;
-    if (inb >= 128 && mp >= 2 * inb) {
-        const long ldw = inb + c->ldpad;
-        const size_t wb = sizeof(double) * (size_t)(mp + 128) * ldw;
-        void *Wn_v = 0, *Iw2_v = 0, *Sw_v = 0;
-        RC(bufs.get(wb, &Wn_v));
-        RC(bufs.get(wb, &Iw2_v));
-        RC(bufs.get(wb, &Sw_v));
-        RC(dib_build<double>(c, s, L, ld, mp, inb, (double*)Wn_v, ldw, (double*)Iw2_v, Iw, ld));
-        DibArgs<double> dib;
-        dib.W = (const double*)Wn_v; dib.ldw = ldw; dib.nbi = inb; dib.S = (double*)Sw_v; dib.lds = ldw;
-        RC(trsm_upper_rec<double>(c, s, Iw, ld, L, ld, 0, mp, dib));
-    } else {
-        RC(trsm_upper_rec<double>(c, s, Iw, ld, L, ld, 0, mp));
-    }
-    return 0;
+    return upper_inverse<double>(c, s, bufs, L, ld, mp, (inb >= 128 && mp >= 2 * inb) ? inb : 0, Iw);
 }
 
 enum { VFE_FIT = 0, VFE_UPDATE = 1, VFE_APPEND = 2 };
@@ -108,7 +91,7 @@ enum { VFE_FIT = 0, VFE_UPDATE = 1, VFE_APPEND = 2 };
 template <typename T>
 static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_points* z, const gp_noise* noise,
                             double jitter, const void* mean_or_null, const void* yv, int approx, gp_vfe* out,
-                            double* objective, const gp_vfe* prev = nullptr, int mode = VFE_FIT) {
+                            double* objective, const gp_vfe* prev, int mode) {
     const long m_old = prev ? prev->m : 0;
     const long m2 = (mode == VFE_APPEND) ? z->n : 0;
     const long m = mode == VFE_FIT ? z->n : m_old + m2;
@@ -532,26 +515,9 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
         HIPCHK(hipMemcpyAsync(scal_h, c->scal_dev, sizeof(double) * 16, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(rss_h.data(), rss_v, vT_b, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        float ms;
-        HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[0], c->ev_phase[1]));
-        c->tm.assemble_ms = ms;  // the M×M prelude: K_zz, its Cholesky, inv(L_z)
-        HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[1], c->ev_phase[2]));
-        c->tm.potrf_ms = ms;     // the streamed pass over the data points
-        HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[2], c->ev_phase[3]));
-        c->tm.solve_ms = ms;     // the M×M side after it: Λ_ε = chol(I + B Bᵀ), the vector solves
-        HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[0], c->ev_phase[3]));
-        c->tm.total_ms = ms;
-        c->tm.gemm_ms = 0;
-        c->tm.gemm_flops = 0;
-        c->tm.gemm_bytes = 0;
-        c->tm.gemm_launches = (int64_t)c->gemm_recs.size();
-        for (auto& r : c->gemm_recs) {
-            HIPCHK(hipEventElapsedTime(&ms, r.a, r.b));
-            c->tm.gemm_ms += ms;
-            c->tm.gemm_flops += r.flops;
-            c->tm.gemm_bytes += r.bytes;
-        }
-        return 0;
+        // gp_timings: assemble_ms = the M×M prelude (K_zz, its Cholesky, inv(L_z)), potrf_ms = the streamed pass over the data points, solve_ms = the M×M side
+        // after it (Λ_ε = chol(I + B Bᵀ), the vector solves)
+        return fit_timings(c);
     });
     if (rc != 0) return rc;
     // a failing factorisation: K_zz (+ the bordered block of an append) or Λ_ε — reported like the reference's cholesky calls
@@ -589,6 +555,17 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
     return 0;
 }
 
+// X (nsp × mp, leading dimension p->ld) = K(x*, z) L_z⁻ᵀ, the rows Aᵀ every predictive formula starts from (:187-195); xs_dev: the staged test points, [d][nsp]
+static int32_t vfe_cross_solve(gp_vfe* p, hipStream_t s, DevBufs& bufs, const double* xs_dev, long ns, long nsp, double* X) {
+    const long mp = p->mp, ld = p->ld;
+    GridMap g = plain_map(0, 0, 0);
+    dim3 grid((unsigned)(mp / 128), (unsigned)(nsp / 128));
+    launch_kmat<double>(grid, s, X, ld, xs_dev, nsp, (const double*)p->zs, mp, p->d, p->kern.kind, p->kern.variance, (const double*)nullptr, ns, p->m, 0, g,
+                        (const double*)nullptr, (const double*)nullptr);
+    HIPCHK(hipGetLastError());
+    return trsm_cached<double>(p->ctx, s, X, ld, nsp, (const double*)p->Lz, ld, mp, p->m, p->dib_z, bufs);
+}
+
 // Joint predictive distribution of the approximate posterior at x* on the device (always fp64 on the M side):
 //   A = U⁻ᵀ K_z*  ->  rows X1 = K_*z L_z⁻ᵀ,  X2 = X1 L_D⁻ᵀ;   cov = K** − X1 X1ᵀ + X2 X2ᵀ (+ Σy*)        :187-190, :205-210
 template <typename T>
@@ -600,15 +577,14 @@ static int32_t vfe_joint(gp_vfe* p, const gp_points* xs, const void* pm, const g
     const long ns = xs->n, nsp = round_up(ns, 128);
     const int d = p->d;
     const gp_kernel k = p->kern.view(0);
-    std::vector<T> xsT;
-    scale_points<T>(&k, xs, nsp, xsT);  // inputs arrive in T; scale in T (as the fit did), then widen
-    std::vector<double> xs_h(xsT.begin(), xsT.end()), nz_h;
+    StagedPoints<T, double> sx;  // inputs arrive in T; scaled in T (as the fit did), then widened
+    std::vector<double> nz_h;
     noise_to<double, T>(noise, ns, nsp, nz_h);
     const double* vec = (const double*)p->vec;
     const long ldc = nsp + c->ldpad;
     const size_t X_b = sizeof(double) * (size_t)(nsp + 128) * ld;
-    void *xs_v = 0, *nz_v = 0, *m_v = 0, *X1_v = 0, *X2_v = 0, *X2n_v = 0;
-    RC(bufs.get(sizeof(double) * xs_h.size(), &xs_v));
+    void *nz_v = 0, *m_v = 0, *X1_v = 0, *X2_v = 0, *X2n_v = 0;
+    RC(sx.stage(c, bufs, &k, xs, nsp));
     RC(bufs.get(sizeof(double) * (size_t)nsp, &nz_v));
     RC(bufs.get(sizeof(double) * (size_t)nsp, &m_v));
     RC(bufs.get(X_b, &X1_v));
@@ -623,20 +599,12 @@ static int32_t vfe_joint(gp_vfe* p, const gp_points* xs, const void* pm, const g
     c->ev_used = 0;
     c->gemm_recs.clear();
     std::vector<double> m_h((size_t)ns);
-    HIPCHK(hipMemcpyAsync(xs_v, xs_h.data(), sizeof(double) * xs_h.size(), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(nz_v, nz_h.data(), sizeof(double) * (size_t)nsp, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(kvec_kernel<double>, dim3((unsigned)ns), dim3(256), 0, s, (const double*)xs_v, nsp, (const double*)p->zs, mp, d,
+    hipLaunchKernelGGL(kvec_kernel<double>, dim3((unsigned)ns), dim3(256), 0, s, sx.ptr(), nsp, (const double*)p->zs, mp, d,
                        p->kern.kind, p->kern.variance, m, vec + 2 * mp, (double*)m_v);                                     // K_*z α
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(m_h.data(), m_v, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, s));
-    {
-        GridMap g = plain_map(0, 0, 0);
-        dim3 grid((unsigned)(mp / 128), (unsigned)(nsp / 128));
-        launch_kmat<double>(grid, s, X1, ld, (const double*)xs_v, nsp, (const double*)p->zs, mp, d,
-                           p->kern.kind, p->kern.variance, (const double*)nullptr, ns, m, 0, g, (const double*)nullptr, (const double*)nullptr);
-        HIPCHK(hipGetLastError());
-    }
-    RC(trsm_cached<double>(c, s, X1, ld, nsp, (const double*)p->Lz, ld, mp, p->m, p->dib_z, bufs));
+    RC(vfe_cross_solve(p, s, bufs, sx.ptr(), ns, nsp, X1));
     HIPCHK(hipMemcpyAsync(X2_v, X1_v, X_b, hipMemcpyDeviceToDevice, s));
     RC(trsm_cached<double>(c, s, X2, ld, nsp, (const double*)p->Ld, ld, mp, p->m, p->dib_d, bufs));
     {
@@ -648,7 +616,7 @@ static int32_t vfe_joint(gp_vfe* p, const gp_points* xs, const void* pm, const g
     {
         GridMap g = plain_map(1, 0, 0);
         dim3 grid((unsigned)(nsp / 128), (unsigned)(nsp / 128));
-        launch_kmat<double>(grid, s, Cm, ldc, (const double*)xs_v, nsp, (const double*)xs_v, nsp, d,
+        launch_kmat<double>(grid, s, Cm, ldc, sx.ptr(), nsp, sx.ptr(), nsp, d,
                            p->kern.kind, p->kern.variance, (const double*)nz_v, ns, ns, 1, g, (const double*)nullptr, (const double*)nullptr);
         HIPCHK(hipGetLastError());
     }
@@ -693,39 +661,28 @@ static int32_t vfe_predict_impl(gp_vfe* p, const gp_points* xs, const void* pm, 
     const long ns = xs->n, nsp = round_up(ns, 128);
     const int d = p->d;
     const gp_kernel k = p->kern.view(0);
-    // inputs arrive in T; scale in T (as the fit did), then widen
-    std::vector<T> xsT;
-    scale_points<T>(&k, xs, nsp, xsT);
-    std::vector<double> xs_h(xsT.begin(), xsT.end());
+    StagedPoints<T, double> sx;  // inputs arrive in T; scaled in T (as the fit did), then widened
     const double* vec = (const double*)p->vec;
-    const size_t xs_b = sizeof(double) * xs_h.size(), X_b = sizeof(double) * (size_t)(nsp + 128) * ld,
-                 o_b = sizeof(double) * (size_t)nsp * 3;
-    void *xs_v = 0, *X_v = 0, *o_v = 0;
+    const size_t X_b = sizeof(double) * (size_t)(nsp + 128) * ld, o_b = sizeof(double) * (size_t)nsp * 3;
+    void *X_v = 0, *o_v = 0;
     DevBufs bufs(c);
-    RC(bufs.get(xs_b, &xs_v));
-    RC(bufs.get(X_b, &X_v));
-    RC(bufs.get(o_b, &o_v));
-    double* X = (double*)X_v;
-    double* o = (double*)o_v;
     hipStream_t s = c->sm;
     c->ev_used = 0;
     c->gemm_recs.clear();
     std::vector<double> oh((size_t)nsp * 3, 0.0);
     const int32_t rc = run_drained(c, [&]() -> int32_t {
-        HIPCHK(hipMemcpyAsync(xs_v, xs_h.data(), xs_b, hipMemcpyHostToDevice, s));
+        RC(sx.stage(c, bufs, &k, xs, nsp));
+        RC(bufs.get(X_b, &X_v));
+        RC(bufs.get(o_b, &o_v));
+        double* X = (double*)X_v;
+        double* o = (double*)o_v;
         if (what & 1) {  // mean = m(x*) + K_*z α                                                  :183-185
-            hipLaunchKernelGGL(kvec_kernel<double>, dim3((unsigned)ns), dim3(256), 0, s, (const double*)xs_v, nsp,
+            hipLaunchKernelGGL(kvec_kernel<double>, dim3((unsigned)ns), dim3(256), 0, s, sx.ptr(), nsp,
                                (const double*)p->zs, mp, d, p->kern.kind, p->kern.variance, m, vec + 2 * mp, o);
             HIPCHK(hipGetLastError());
         }
         if (what & 2) {  // var = k** − ‖A‖²_col + ‖Λ_ε.U⁻ᵀ A‖²_col, Aᵀ = K_*z L_z⁻ᵀ                 :192-195
-            GridMap g = plain_map(0, 0, 0);
-            dim3 grid((unsigned)(mp / 128), (unsigned)(nsp / 128));
-            launch_kmat<double>(grid, s, X, ld, (const double*)xs_v, nsp,
-                               (const double*)p->zs, mp, d, p->kern.kind, p->kern.variance, (const double*)nullptr, ns, m, 0, g,
-                               (const double*)nullptr, (const double*)nullptr);
-            HIPCHK(hipGetLastError());
-            RC(trsm_cached<double>(c, s, X, ld, nsp, (const double*)p->Lz, ld, mp, p->m, p->dib_z, bufs));
+            RC(vfe_cross_solve(p, s, bufs, sx.ptr(), ns, nsp, X));
             hipLaunchKernelGGL(rowsumsq_kernel<double>, dim3((unsigned)nsp), dim3(256), 0, s, X, ld, mp, o + nsp);
             HIPCHK(hipGetLastError());
             RC(trsm_cached<double>(c, s, X, ld, nsp, (const double*)p->Ld, ld, mp, p->m, p->dib_d, bufs));
@@ -759,55 +716,43 @@ static int32_t vfe_predict_grad_impl(gp_vfe* p, const gp_points* xs, const void*
     const int d = p->d;
     const gp_kernel k = p->kern.view(0);
     const KDesc kd = p->kern.desc();
-    std::vector<T> xsT;
-    scale_points<T>(&k, xs, nsp, xsT);
-    std::vector<double> xs_h(xsT.begin(), xsT.end());
+    StagedPoints<T, double> sx;
+    DevScales sc;
     const double* vec = (const double*)p->vec;
     const bool want_gm = (what & 1) && dmean_out, want_gv = (what & 2) && dvar_out, side_v = (what & 2) != 0;
-    const int nsc = std::max(k.nscale, 1);
-    std::vector<double> sc_h((size_t)nsc, 1.0);
-    for (int q = 0; q < k.nscale; ++q) sc_h[q] = k.scale[q];
-    const size_t xs_b = sizeof(double) * xs_h.size(), X_b = sizeof(double) * (size_t)(nsp + 128) * ld, o_b = sizeof(double) * (size_t)nsp * 3,
-                 g_b = sizeof(double) * (size_t)2 * d * nsp, sc_b = sizeof(double) * (size_t)nsc;
-    void *xs_v = 0, *X1_v = 0, *X2_v = 0, *o_v = 0, *g_v = 0, *sc_v = 0;
+    const size_t X_b = sizeof(double) * (size_t)(nsp + 128) * ld, o_b = sizeof(double) * (size_t)nsp * 3, g_b = sizeof(double) * (size_t)2 * d * nsp;
+    void *X1_v = 0, *X2_v = 0, *o_v = 0, *g_v = 0;
     DevBufs bufs(c);
-    RC(bufs.get(xs_b, &xs_v));
-    RC(bufs.get(o_b, &o_v));
-    RC(bufs.get(g_b, &g_v));
-    RC(bufs.get(sc_b, &sc_v));
-    if (side_v) RC(bufs.get(X_b, &X1_v));
-    if (want_gv) RC(bufs.get(X_b, &X2_v));
-    double* X1 = (double*)X1_v;
-    double* X2 = want_gv ? (double*)X2_v : X1;
-    double* o = (double*)o_v;
     hipStream_t s = c->sm;
     c->ev_used = 0;
     c->gemm_recs.clear();
     std::vector<double> oh((size_t)nsp * 3, 0.0), g_h((want_gm || want_gv) ? (size_t)2 * d * nsp : 0);
     const int32_t rc = run_drained(c, [&]() -> int32_t {
+        RC(sx.stage(c, bufs, &k, xs, nsp));
+        RC(bufs.get(o_b, &o_v));
+        RC(bufs.get(g_b, &g_v));
+        RC(sc.stage(bufs, k.nscale, k.scale, s));
+        if (side_v) RC(bufs.get(X_b, &X1_v));
+        if (want_gv) RC(bufs.get(X_b, &X2_v));
+        double* X1 = (double*)X1_v;
+        double* X2 = want_gv ? (double*)X2_v : X1;
+        double* o = (double*)o_v;
         double* gm = want_gm ? (double*)g_v : nullptr;
         double* gv = want_gv ? (double*)g_v + (size_t)d * nsp : nullptr;
-        HIPCHK(hipMemcpyAsync(xs_v, xs_h.data(), xs_b, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(sc_v, sc_h.data(), sc_b, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemsetAsync(o, 0, o_b, s));
         // the 128 slack rows below the test points are operand over-read of the solves' GEMMs: finite, whatever the recycled block held
         if (side_v) HIPCHK(hipMemsetAsync(X1 + (size_t)nsp * ld, 0, sizeof(double) * (size_t)128 * ld, s));
         if (want_gv) HIPCHK(hipMemsetAsync(X2 + (size_t)nsp * ld, 0, sizeof(double) * (size_t)128 * ld, s));
         if ((what & 1) && mean_out) {
-            hipLaunchKernelGGL(kvec_kernel<double>, dim3((unsigned)ns), dim3(256), 0, s, (const double*)xs_v, nsp, (const double*)p->zs, mp, d, p->kern.kind,
+            hipLaunchKernelGGL(kvec_kernel<double>, dim3((unsigned)ns), dim3(256), 0, s, sx.ptr(), nsp, (const double*)p->zs, mp, d, p->kern.kind,
                                p->kern.variance, m, vec + 2 * mp, o);
             HIPCHK(hipGetLastError());
         }
         if (want_gm && !want_gv)
-            RC(launch_kpgrad<double>(kd, k.nscale, (const double*)sc_v, ns, s, (const double*)xs_v, nsp, (const double*)p->zs, mp, d, m, vec + 2 * mp,
+            RC(launch_kpgrad<double>(kd, k.nscale, sc.ptr(), ns, s, sx.ptr(), nsp, (const double*)p->zs, mp, d, m, vec + 2 * mp,
                                      (const double*)nullptr, 0, gm, (double*)nullptr, nsp, 0));
         if (side_v) {
-            GridMap g = plain_map(0, 0, 0);
-            dim3 grid((unsigned)(mp / 128), (unsigned)(nsp / 128));
-            launch_kmat<double>(grid, s, X1, ld, (const double*)xs_v, nsp, (const double*)p->zs, mp, d, p->kern.kind, p->kern.variance, (const double*)nullptr, ns,
-                                m, 0, g, (const double*)nullptr, (const double*)nullptr);
-            HIPCHK(hipGetLastError());
-            RC(trsm_cached<double>(c, s, X1, ld, nsp, (const double*)p->Lz, ld, mp, p->m, p->dib_z, bufs));
+            RC(vfe_cross_solve(p, s, bufs, sx.ptr(), ns, nsp, X1));
             hipLaunchKernelGGL(rowsumsq_kernel<double>, dim3((unsigned)nsp), dim3(256), 0, s, X1, ld, mp, o + nsp);
             HIPCHK(hipGetLastError());
             if (want_gv) HIPCHK(hipMemcpyAsync(X2, X1, sizeof(double) * (size_t)nsp * ld, hipMemcpyDeviceToDevice, s));
@@ -820,7 +765,7 @@ static int32_t vfe_predict_grad_impl(gp_vfe* p, const gp_points* xs, const void*
                 hipLaunchKernelGGL(rsub_kernel, dim3((unsigned)ns), dim3(256), 0, s, (const double*)X1, X2, ld, mp);
                 HIPCHK(hipGetLastError());
                 RC(trsm_back_cached<double>(c, s, X2, ld, nsp, ns, (const double*)p->Lz, ld, mp, p->dib_z, bufs, wb));
-                RC(launch_kpgrad<double>(kd, k.nscale, (const double*)sc_v, ns, s, (const double*)xs_v, nsp, (const double*)p->zs, mp, d, m, vec + 2 * mp,
+                RC(launch_kpgrad<double>(kd, k.nscale, sc.ptr(), ns, s, sx.ptr(), nsp, (const double*)p->zs, mp, d, m, vec + 2 * mp,
                                          (const double*)X2, ld, gm, gv, nsp, 0));
             }
         }
@@ -835,8 +780,8 @@ static int32_t vfe_predict_grad_impl(gp_vfe* p, const gp_points* xs, const void*
         for (long i = 0; i < ns; ++i) ((T*)mean_out)[i] = (T)((prior ? (double)prior[i] : 0.0) + oh[i]);
     if (side_v && var_out)
         for (long i = 0; i < ns; ++i) ((T*)var_out)[i] = (T)(p->kern.variance - oh[nsp + i] + oh[2 * nsp + i]);
-    if (want_gm) grad_to_layout<T>(xs, g_h.data(), nsp, dmean_out);
-    if (want_gv) grad_to_layout<T>(xs, g_h.data() + (size_t)d * nsp, nsp, dvar_out);
+    if (want_gm) grad_to_layout<T>(xs->layout, ns, d, g_h.data(), nsp, dmean_out);
+    if (want_gv) grad_to_layout<T>(xs->layout, ns, d, g_h.data() + (size_t)d * nsp, nsp, dvar_out);
     return 0;
 }
 
@@ -897,7 +842,7 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
     const int nsc = std::max(p->kern.nscale(), 1);
     const size_t L_b = sizeof(double) * (size_t)(mp + 128 + 128) * ld;
     const size_t X_b = sizeof(double) * (size_t)(CH + 128) * ld, g_b = sizeof(double) * (size_t)(2 + nsc + 2), gz_b = sizeof(double) * (size_t)d * mp;
-    void *W_v = 0, *V_v = 0, *H_v = 0, *R_v = 0, *E_v = 0, *Gp_v = 0, *Gz_v = 0, *X_v = 0, *X2_v = 0, *C2_v = 0, *xc_v = 0, *rc_v = 0, *bc_v = 0, *C_v = 0, *g_v = 0, *gz_v = 0, *sc_v = 0;
+    void *W_v = 0, *V_v = 0, *H_v = 0, *R_v = 0, *E_v = 0, *Gp_v = 0, *Gz_v = 0, *X_v = 0, *X2_v = 0, *C2_v = 0, *xc_v = 0, *rc_v = 0, *bc_v = 0, *C_v = 0, *g_v = 0, *gz_v = 0;
     DevBufs bufs(c);
     RC(bufs.get(L_b, &W_v));
     RC(bufs.get(L_b, &V_v));
@@ -917,13 +862,11 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
     RC(bufs.get(X_b, &C2_v));
     RC(bufs.get(g_b, &g_v));
     RC(bufs.get(gz_b, &gz_v));
-    RC(bufs.get(sizeof(double) * (size_t)nsc, &sc_v));
+    DevScales sc;
     double *W = (double*)W_v, *V = (double*)V_v, *H = (double*)H_v, *R = (double*)R_v, *E = (double*)E_v, *Gp = (double*)Gp_v, *Gz = (double*)Gz_v;
     const double* Lz = (const double*)p->Lz;
     const double* Ld = (const double*)p->Ld;
     const double* alpha = (const double*)p->vec + 2 * mp;
-    std::vector<double> sc_h((size_t)nsc, 1.0);
-    for (int q = 0; q < p->kern.nscale(); ++q) sc_h[q] = p->kern.scale[q];
     std::vector<double> g_h((size_t)(2 + nsc + 2), 0.0), gz_h((size_t)d * mp, 0.0);   // [0] ∂/∂variance, [2 + p] ∂/∂scale_p, [2 + nsc] Σ ∂/∂σ_i², [3 + nsc] Σ σ_i⁻²
     // per observation (concatenated over the segments, arrival order): what the host needs to finish ∂/∂σ_i², ∂/∂y_i, ∂/∂x_i
     long n_all = 0;
@@ -944,7 +887,7 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
     };
     const int32_t rc = run_drained(c, [&]() -> int32_t {
         HIPCHK(hipEventRecord(c->ev_phase[0], s));
-        HIPCHK(hipMemcpyAsync(sc_v, sc_h.data(), sizeof(double) * (size_t)nsc, hipMemcpyHostToDevice, s));
+        RC(sc.stage(bufs, p->kern.nscale(), p->kern.scale.data(), s));
         HIPCHK(hipMemsetAsync(g_v, 0, g_b, s));
         HIPCHK(hipMemsetAsync(gz_v, 0, gz_b, s));
         for (void* q : {H_v, R_v, E_v, Gp_v, Gz_v}) HIPCHK(hipMemsetAsync(q, 0, L_b, s));   // the GEMMs over-read whole operand tiles: defined slack rows
@@ -1071,11 +1014,11 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
             dim3 grid((unsigned)(mp / 128), (unsigned)((I.nr + 127) / 128));
             if (dx)
                 RC((launch_vgrad<double, true>(sa, grid, (const double*)Cb[bb], ld, 0, I.xr, I.ldxr, (const double*)p->zs, mp, d, p->kern.kind, p->kern.variance, p->kern.nscale(),
-                                               (const double*)sc_v, I.rs, I.b, alpha, I.nr, m, (double*)g_v, (double*)gz_v, mp, 1.0, cks[ci].rq, cks[ci].rp,
+                                               sc.ptr(), I.rs, I.b, alpha, I.nr, m, (double*)g_v, (double*)gz_v, mp, 1.0, cks[ci].rq, cks[ci].rp,
                                                cks[ci].gx, cks[ci].sg->npad)));
             else
                 RC((launch_vgrad<double, false>(sa, grid, (const double*)Cb[bb], ld, 0, I.xr, I.ldxr, (const double*)p->zs, mp, d, p->kern.kind, p->kern.variance, p->kern.nscale(),
-                                                (const double*)sc_v, I.rs, I.b, alpha, I.nr, m, (double*)g_v, (double*)gz_v, mp, 1.0, cks[ci].rq, cks[ci].rp,
+                                                sc.ptr(), I.rs, I.b, alpha, I.nr, m, (double*)g_v, (double*)gz_v, mp, 1.0, cks[ci].rq, cks[ci].rp,
                                                 (double*)nullptr, 0L)));
             if (ovl) {
                 RC(ctx_event(c, &evV[bb], false));
@@ -1110,44 +1053,22 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
         {
             dim3 grid((unsigned)(mp / 128), (unsigned)((m + 127) / 128));
             RC((launch_vgrad<double, false>(s, grid, (const double*)Gz, ld, 1, (const double*)p->zs, mp, (const double*)p->zs, mp, d, p->kern.kind, p->kern.variance, p->kern.nscale(),
-                                            (const double*)sc_v, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, m, m, (double*)g_v,
+                                            sc.ptr(), (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, m, m, (double*)g_v,
                                             (double*)gz_v, mp, 2.0, (double*)nullptr, (double*)nullptr, (double*)nullptr, 0L)));
         }
         HIPCHK(hipMemcpyAsync(g_h.data(), g_v, g_b, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(gz_h.data(), gz_v, gz_b, hipMemcpyDeviceToHost, s));
         HIPCHK(hipEventRecord(c->ev_phase[3], s));
         HIPCHK(hipStreamSynchronize(s));
-        float ms;
-        HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[0], c->ev_phase[1]));
-        c->tm.assemble_ms = ms;  // the M×M side
-        HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[1], c->ev_phase[2]));
-        c->tm.potrf_ms = ms;     // the streamed pass
-        HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[2], c->ev_phase[3]));
-        c->tm.solve_ms = ms;     // the K_zz term
-        HIPCHK(hipEventElapsedTime(&ms, c->ev_phase[0], c->ev_phase[3]));
-        c->tm.total_ms = ms;
-        return 0;
+        return phase_timings(c);  // gp_timings: assemble_ms = the M×M side, potrf_ms = the streamed pass, solve_ms = the K_zz term
     });
     if (rc != 0) return rc;
     if (dvar) *dvar = g_h[0] - (vfe ? 0.5 * g_h[3 + nsc] : 0.0);   // − ½ Σ_i ∂k_ii/∂σ_k² / σ_i²: the trace term
     if (dscale)
         for (int q = 0; q < p->kern.nscale(); ++q) dscale[q] = g_h[2 + q];
     if (dnoise_sum) *dnoise_sum = g_h[2 + nsc];
-    if (dz)  // the container layout of the pseudo-inputs (src/finite_gp_projection.jl:32-37): 0 vector, 1 ColVecs (D×M column-major), 2 RowVecs (M×D column-major)
-        for (int q = 0; q < d; ++q)
-            for (long j = 0; j < m; ++j) {
-                const double v = gz_h[(size_t)q * mp + j];
-                if (z_layout == 0) dz[j] = v;
-                else if (z_layout == 1) dz[(long)q + j * d] = v;
-                else dz[j + (long)q * m] = v;
-            }
-    if (dx)
-        for (int q = 0; q < d; ++q)
-            for (long i = 0; i < n_all; ++i) {
-                const T v = (T)gx_all[(size_t)q * n_all + i];
-                if (x_layout == 0) ((T*)dx)[i] = v;
-                else if (x_layout == 1) ((T*)dx)[(long)q + i * d] = v;
-                else ((T*)dx)[i + (long)q * n_all] = v;
-            }
+    // the container layouts of the pseudo-inputs and the inputs (src/finite_gp_projection.jl:32-37): 0 vector, 1 ColVecs (D×M column-major), 2 RowVecs (M×D column-major)
+    if (dz) grad_to_layout<double>(z_layout, m, d, gz_h.data(), mp, dz);
+    if (dx) grad_to_layout<T>(x_layout, n_all, d, gx_all.data(), n_all, dx);
     return 0;
 }

@@ -6,8 +6,10 @@ The set is the smallest that reaches every branch of the kernels' shared tile co
 three blocks with more than eight trailing wave tiles, inverse tiles from rows 0 / 128 / 256, a second trip of the tid + NT loops), D in {1, 3, 16}, the
 four radial kinds with no scale, one scale and ARD, scalar and diagonal noise, with and without a mean, α wanted and not, one problem that fails (a
 negative noise entry), two composite kernels (a sum with a product and a Periodic factor; one whose θ is longer than one pass of 16 entries), test
-points ns in {0, 1, 33, 128, 129, 300} with what in {1, 2, 3}, and one call with x, y and xs shared by every problem.  GPMI_BATCH_MAX_N and
-GPMI_BATCH_GRAD_MAX_N are set to the kernels' own limit, and "batch_grad_kernel_problems" must count every gradient problem.
+points ns in {0, 1, 33, 128, 129, 300} with what in {1, 2, 3}, and one call with x, y and xs shared by every problem.  The same problems go through
+gp_predict_grad_batch and gp_logpdf_grad_batch_x (and their _sum forms) with the containers of xs / x cycling over the layouts, since those gradients
+come back in the container's layout.  The GPMI_BATCH_*_MAX_N limits are set to the kernels' own, and the served-problem counter of every gradient
+family ("batch_grad_kernel_problems", "batch_pgrad_kernel_problems", "batch_gradx_kernel_problems") must count every problem of its calls.
 
     GPMI355_LIB=<library> python tools/batch_bits.py --out bits.json      # one process per library; compare the files"""
 import argparse
@@ -85,6 +87,8 @@ def main():
     a = ap.parse_args()
     os.environ["GPMI_BATCH_MAX_N"] = "2048"
     os.environ["GPMI_BATCH_GRAD_MAX_N"] = "2048"
+    os.environ["GPMI_BATCH_PGRAD_MAX_N"] = "2048"
+    os.environ["GPMI_BATCH_GRADX_MAX_N"] = "2048"
     import abstractgps_jl_amd as agp
 
     api = agp.api
@@ -139,6 +143,46 @@ def main():
             put(tag, b, "dnoise", call.dnoise[b])
             put(tag, b, "dy", call.dy[b])
 
+    def relayout(x, b):
+        """the points of x in the b-th of the container layouts the ABI knows: point-contiguous, dimension-contiguous, and for D = 1 a vector"""
+        X = np.asarray(x.X)
+        if X.shape[1] == 1 and b % 3 == 2:
+            return np.ascontiguousarray(X[:, 0])
+        return agp.RowVecs(np.ascontiguousarray(X) if b % 2 == 0 or X.shape[0] < 2 else np.asfortranarray(X))
+
+    def counted(call, counter):
+        before = ctx.get_param(counter)
+        run(call)
+        assert ctx.get_param(counter) - before == call.nb, f"{counter}: the kernels did not serve every problem"
+
+    def predict_grad(tag, fxs, ys, xss):
+        """gp_predict_grad_batch / _sum: the gradients come back in the container layout of each xs_b, so the layouts cycle"""
+        xss = xss if not isinstance(xss, list) else [relayout(xs, b) for b, xs in enumerate(xss)]
+        for what in (1, 2, 3):
+            (g,) = api._predict_groups(fxs, ys, xss)
+            call = api._predict_grad_marshal(g, what)
+            counted(call, "batch_pgrad_kernel_problems")
+            for b in range(call.nb):
+                t = f"{tag}/what{what}"
+                put(t, b, "logpdf", call.out[b])
+                put(t, b, "info", call.info[b])
+                for name, arrs in (("mean", call.means), ("var", call.vars), ("dmean", call.dmeans), ("dvar", call.dvars)):
+                    put(t, b, name, arrs[b] if arrs is not None else None)
+
+    def gradx(tag, fxs, ys):
+        """gp_logpdf_grad_batch_x / _sum_x: dx in the container layout of each x_b (the layouts cycle unless the problems share one x)"""
+        if len({id(fx.x) for fx in fxs}) == len(fxs):
+            fxs = [agp.FiniteGP(fx.f, relayout(fx.x, b), fx.sigma2) for b, fx in enumerate(fxs)]
+        (g,) = api._batch_groups(fxs, ys)
+        call = api._grad_batch_marshal(g, wrt_x=True)
+        counted(call, "batch_gradx_kernel_problems")
+        for b in range(call.nb):
+            put(tag, b, "logpdf", call.out[b])
+            put(tag, b, "info", call.info[b])
+            put(tag, b, "dnoise", call.dnoise[b])
+            put(tag, b, "dy", call.dy[b])
+            put(tag, b, "dx", call.dx[b])
+
     def points(fxs, seed, first):
         """ns cycles over POINTS from POINTS[first] on, shifted so that every size of the set meets several of them"""
         rng = np.random.default_rng(seed)
@@ -148,12 +192,17 @@ def main():
         fxs, ys = [p[0] for p in probs], [p[1] for p in probs]
         info = fit(f"fit/{name}", fxs, ys)
         assert np.count_nonzero(info) == (1 if name == "single" else 0), info
-        predict(f"predict/{name}", fxs, ys, points(fxs, 500, 0 if name == "single" else 4))
+        xss = points(fxs, 500, 0 if name == "single" else 4)
+        predict(f"predict/{name}", fxs, ys, xss)
         grad(f"grad/{name}", fxs, ys)
+        predict_grad(f"predict_grad/{name}", fxs, ys, xss)
+        gradx(f"gradx/{name}", fxs, ys)
     fxs, y, xs = shared_problems(agp)
     fit("fit/shared", fxs, y)
     predict("predict/shared", fxs, y, xs)
     grad("grad/shared", fxs, y)
+    predict_grad("predict_grad/shared", fxs, y, xs)
+    gradx("gradx/shared", fxs, y)
 
     Path(a.out).parent.mkdir(parents=True, exist_ok=True)
     Path(a.out).write_text(json.dumps(digests, indent=0, sort_keys=True) + "\n")
