@@ -137,6 +137,14 @@ PROTOTYPES = {
     "gp_vfe_n": (i64, [vp]),
     "gp_vfe_get_by": (i32, [vp, vp]),
     "gp_vfe_grad": (i32, [vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), vp, vp, vp, i32, vp, i32]),
+    "gp_vfe_fit_cols": (i32, [vp, PK, PP, PP, PN, dbl, vp, vp, i64, i32, i32, C.POINTER(vp), vp]),
+    "gp_vfe_update_cols": (i32, [vp, PP, PN, vp, vp, i64, C.POINTER(vp), vp]),
+    "gp_vfe_append_cols": (i32, [vp, PP, C.POINTER(vp), vp]),
+    "gp_vfe_ncols": (i32, [vp, C.POINTER(i32)]),
+    "gp_vfe_predict_cols": (i32, [vp, PP, vp, i32, vp, vp, vp]),
+    "gp_vfe_get_cols": (i32, [vp, vp, vp]),
+    "gp_vfe_get_by_cols": (i32, [vp, vp]),
+    "gp_vfe_grad_cols": (i32, [vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), vp, vp, vp, i32, vp, i32]),
     "gp_vfe_free": (i32, [vp]),
     "gpd_assemble": (i32, [vp, PK, vp, i64, i64, i32, vp, PG, vp, i64, i64, i64]),
     "gpd_potrf": (i32, [vp, vp, i64, i64, i64, vp, i32, i64, vp]),

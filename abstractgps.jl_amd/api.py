@@ -1703,9 +1703,15 @@ class ColumnsPosteriorGP(AbstractGP):
         raise TypeError("a FiniteGP over a column posterior (held-out logpdf, samples, sequential conditioning) is not offered: use posterior(fx, Y[:, s])")
 
 
-def posterior_columns(fx: FiniteGP, Y) -> ColumnsPosteriorGP:
-    """posterior(fx, Y[:, s]) for every column s of the (n, S) matrix Y from ONE Gram assembly and ONE factorisation (gp_posterior_fit_cols; S <= 128).
-    .data.alpha is (n, S), .logpdf_values (S,) = logpdf(fx, Y)."""
+def posterior_columns(fx, Y, *rest):
+    """posterior_columns(fx, Y): posterior(fx, Y[:, s]) for every column s of the (n, S) matrix Y from ONE Gram assembly and ONE factorisation
+    (gp_posterior_fit_cols; S <= 128).  .data.alpha is (n, S), .logpdf_values (S,) = logpdf(fx, Y).
+    posterior_columns(VFE(fz)|DTC(fz), fx, Y): the sparse posteriors of every column from ONE streamed pass (gp_vfe_fit_cols) — an
+    ApproxColumnsPosteriorGP."""
+    if len(rest) == 1:  # (approx, fx, Y): the positional names of the two-argument form shift by one
+        return _vfe_posterior_columns(fx, Y, rest[0])
+    if rest:
+        raise TypeError("posterior_columns(fx, Y) or posterior_columns(approx, fx, Y)")
     a = _cols_marshal(fx, Y, "posterior_columns")
     f = fx.f
     ctx = f.context()
@@ -2122,6 +2128,8 @@ def update_posterior(f_post_approx: ApproxPosteriorGP, fx: FiniteGP, y=None):
     B Bᵀ / B b_y only (gp_vfe_append)."""
     if f_post_approx.prior is not fx.f:
         raise AssertionError("f_post_approx.prior === fx.f")
+    if isinstance(f_post_approx, ApproxColumnsPosteriorGP):
+        return _vfe_cols_update(f_post_approx, fx, y)
     st = f_post_approx._state
     dt = f_post_approx._dtype
     mm = _Marshal(dt)
@@ -2174,3 +2182,234 @@ def elbo(a, fx: FiniteGP, y):
     if not isinstance(a, VFE):
         raise TypeError("elbo is defined for VFE")
     return approx_log_evidence(a, fx, y)
+
+
+# --------------------------------------------------------------------------------------------
+# VFE / DTC for a matrix of observations: gp_vfe_fit_cols / _update_cols / _append_cols / _predict_cols / _get_cols / _get_by_cols / _grad_cols
+# --------------------------------------------------------------------------------------------
+@dataclass(eq=False)
+class _VfeColsCall:
+    """The arguments of a gp_vfe_fit_cols call, built without a context (tests/test_vfe_cols_cpu.py reads them)."""
+    dt: type
+    m: _Marshal
+    px: gp_points
+    pz: gp_points
+    kk: gp_kernel
+    nz: gp_noise
+    jitter: float
+    mean: Optional[np.ndarray]  # the ONE prior-mean vector every column shares
+    Y: np.ndarray               # (n, S), column-major
+    ldy: int
+    ncols: int
+    approx: int
+
+
+def _cols_matrix(fx: FiniteGP, Y, name: str, ncols: Optional[int] = None) -> np.ndarray:
+    Y = np.asarray(Y)
+    if Y.ndim != 2:
+        raise TypeError(f"{name} expects an (n, S) matrix of observations, one sparse GP per column; a vector goes to its single-column counterpart")
+    if Y.shape[0] != len(fx):
+        raise ValueError(f"DimensionMismatch: length(fx) = {len(fx)} but Y has {Y.shape[0]} rows")
+    if not 1 <= Y.shape[1] <= _lib.cols_max():
+        raise ValueError(f"{name}: {Y.shape[1]} columns, 1..{_lib.cols_max()} (GPMI355_COLS_MAX) fit one call: split them into groups")
+    if ncols is not None and Y.shape[1] != ncols:
+        raise ValueError(f"{name}: Y has {Y.shape[1]} columns but the posterior holds {ncols}")
+    return Y
+
+
+def _vfe_cols_marshal(approx, fx: FiniteGP, Y, name: str) -> _VfeColsCall:
+    if not isinstance(approx, (VFE, DTC)):
+        raise TypeError(f"{name}: VFE or DTC")
+    Y = _cols_matrix(fx, Y, name)
+    f = fx.f
+    if approx.fz.f is not f:
+        raise AssertionError("vfe.fz.f === fx.f")
+    if not isinstance(f, GP):
+        raise TypeError("VFE/DTC: unsupported prior type")
+    if _is_composite(f.kernel):
+        raise NotImplementedError("VFE / DTC with a composite kernel are not accelerated (the exact path takes composite kernels)")
+    _refuse_dense_vfe(fx)
+    jit = np.asarray(approx.fz.sigma2)
+    if jit.ndim != 0:
+        raise NotImplementedError("inducing-point noise must be a scalar jitter")
+    dt = np.result_type(_input_dtype(fx.x), np.float32 if Y.dtype == np.float32 else np.float64).type
+    m = _Marshal(dt)
+    px, pz = m.points(fx.x), m.points(approx.fz.x)
+    kk = m.kernel(f.kernel, px.d)
+    nz = m.noise(fx.sigma2, px.n)
+    mean = _mean_vector(f.mean_fn, fx.x, dt)
+    mean = None if mean is None else m.arr(mean)
+    Yf = m.arr(Y, order="F")
+    return _VfeColsCall(dt, m, px, pz, kk, nz, float(jit), mean, Yf, max(Yf.shape[0], 1), Yf.shape[1], 0 if isinstance(approx, VFE) else 1)
+
+
+def _vfe_cols_call(approx, fx: FiniteGP, Y, want_post: bool, name: str):
+    a = _vfe_cols_marshal(approx, fx, Y, name)
+    ctx = fx.f.context()
+    obj = np.empty(a.ncols, dtype=a.dt)
+    h = C.c_void_p()
+    check(ctx.lib.gp_vfe_fit_cols(ctx.handle, C.byref(a.kk), C.byref(a.px), C.byref(a.pz), C.byref(a.nz), a.jitter, a.m.ptr(a.mean), a.Y.ctypes.data, a.ldy,
+                                  a.ncols, a.approx, C.byref(h) if want_post else None, obj.ctypes.data))
+    return (h if want_post else None), obj, ctx, a
+
+
+class _VfeColsData(_VfeData):
+    """_VfeData of a column posterior: `alpha`, `m_eps` are (M, S), `b_y` is (n, S); `U`, `Lam_U` do not depend on y."""
+
+    def __getitem__(self, k):
+        p = self._post
+        st, dt, m, S = p._state, p._dtype, p._m, p.ncols
+        lib = st.ctx.lib
+        if k in ("alpha", "m_eps"):
+            a = np.empty((m, S), dtype=dt, order="F")
+            check(lib.gp_vfe_get_cols(st.handle, a.ctypes.data if k == "alpha" else None, a.ctypes.data if k == "m_eps" else None))
+            return a
+        if k == "b_y":
+            n = int(lib.gp_vfe_n(st.handle))
+            out = np.empty((max(n, 0), S), dtype=dt, order="F")
+            check(lib.gp_vfe_get_by_cols(st.handle, out.ctypes.data))
+            return out
+        return super().__getitem__(k)
+
+
+class ApproxColumnsPosteriorGP(AbstractGP):
+    """S sparse posteriors that share x, z, kernel, jitter, Σy and the prior mean and differ in y (the columns of Y): ONE streamed pass, ONE pair of M×M
+    factors, α for every column.  `objective` is (S,); mean(x) is (ns, S); var / cov do not depend on y and are those of every column."""
+
+    def __init__(self, approx, prior: GP, state: _VfeState, dtype, m: int, ncols: int, objective):
+        self.approx, self.prior, self._state, self._dtype, self._m, self._ncols = approx, prior, state, dtype, m, ncols
+        self.objective = objective
+
+    @property
+    def ncols(self) -> int:
+        return self._ncols
+
+    @property
+    def data(self):
+        return _VfeColsData(self)
+
+    def _predict(self, x, what):
+        st, dt = self._state, self._dtype
+        mm = _Marshal(dt)
+        px = mm.points(x)
+        pm = _mean_vector(self.prior.mean_fn, x, dt)
+        pm = None if pm is None else mm.arr(pm)
+        mean = np.empty((px.n, self._ncols), dtype=dt, order="F") if what & 1 else None
+        var = np.empty(px.n, dtype=dt) if what & 2 else None
+        cov = np.empty((px.n, px.n), dtype=dt, order="F") if what & 4 else None
+        check(st.ctx.lib.gp_vfe_predict_cols(st.handle, C.byref(px), mm.ptr(pm), what, mm.ptr(mean), mm.ptr(var), mm.ptr(cov)))
+        return mean, var, cov
+
+    def mean(self, x=None):
+        if x is None:
+            return super().mean()
+        return self._predict(x, 1)[0]
+
+    def var(self, x):
+        return self._predict(x, 2)[1]
+
+    def cov(self, x, z=None):
+        if z is not None:
+            raise TypeError("cov(f, x, z) is not offered for a column posterior: take the block of cov(f, [x; z])")
+        return self._predict(x, 4)[2]
+
+    def mean_and_var(self, x):
+        return self._predict(x, 3)[:2]
+
+    def mean_and_cov(self, x):
+        m, _, c = self._predict(x, 5)
+        return m, c
+
+    def _one_column_only(self, *a, **k):
+        raise TypeError("a column posterior holds one mean per column: this method needs a single-column posterior (posterior(approx, fx, Y[:, s]))")
+
+    mean_and_var_grad = mean_grad = _one_column_only
+
+    def var_grad(self, x):
+        """(var, ∂var/∂x): the variance side uses no α."""
+        st = self._state
+        r = _predict_grad(st.ctx.lib.gp_vfe_predict_grad, st.handle, self._dtype, self.prior.mean_fn, x, 2)
+        return r[1], r[3]
+
+    def __call__(self, x, sigma2=default_sigma2):
+        raise TypeError("a FiniteGP over a column posterior (held-out logpdf, samples) is not offered: use posterior(approx, fx, Y[:, s])")
+
+    def objective_grad(self, wrt_x: bool = False) -> dict:
+        """Gradient of the SUM over the columns of the objective this posterior was fitted with, at its own parameters (gp_vfe_grad_cols).  Keys as
+        ApproxPosteriorGP.objective_grad; "y" and "mean" (= −"y") are (n, S) — sum "mean" over the columns for the shared mean vector."""
+        st, dt, S = self._state, self._dtype, self._ncols
+        n = int(st.ctx.lib.gp_vfe_n(st.handle))
+        zin = _as_input(self.approx.fz.x)
+        mm = _Marshal(dt)
+        pz = mm.points(self.approx.fz.x)
+        nscale = mm.kernel(self.prior.kernel, pz.d).nscale
+        dvar, dns = C.c_double(), C.c_double()
+        dscale = (C.c_double * max(nscale, 1))()
+        dnoise = np.empty(n, dtype=dt)
+        dY = np.empty((n, S), dtype=dt, order="F")
+        dz = None
+        if np.dtype(dt) == np.float64:
+            dz = np.empty((pz.n,) if pz.layout == 0 else ((pz.n, pz.d) if pz.layout == 1 else (pz.d, pz.n)), dtype=np.float64)
+        dxb = np.empty((n, pz.d), dtype=dt) if wrt_x else None          # layout 1: point-contiguous (N, D)
+        check(st.ctx.lib.gp_vfe_grad_cols(st.handle, C.byref(dvar), dscale, C.byref(dns), dnoise.ctypes.data, dY.ctypes.data, None if dz is None else dz.ctypes.data,
+                                          pz.layout, None if dxb is None else dxb.ctypes.data, 1))
+        sc = None if nscale == 0 else (float(dscale[0]) if nscale == 1 else np.array([dscale[i] for i in range(nscale)]))
+        g = {"variance": dvar.value, "scale": sc, "noise": dns.value, "noise_diag": dnoise, "y": dY, "mean": -dY}
+        if dz is not None:
+            if pz.layout == 0:
+                g["z"] = dz
+            else:
+                nd = dz if pz.layout == 1 else dz.T
+                g["z"] = np.ascontiguousarray(nd.T if isinstance(zin, ColVecs) else nd)
+        if wrt_x:
+            g["x"] = dxb[:, 0] if pz.d == 1 and pz.layout == 0 else dxb
+        return g
+
+
+def _vfe_posterior_columns(approx, fx: FiniteGP, Y) -> ApproxColumnsPosteriorGP:
+    h, obj, ctx, a = _vfe_cols_call(approx, fx, Y, True, "posterior_columns")
+    return ApproxColumnsPosteriorGP(approx, fx.f, _VfeState(ctx, h), a.dt, a.pz.n, a.ncols, obj)
+
+
+def _vfe_cols_update(post: ApproxColumnsPosteriorGP, fx: FiniteGP, Y2=None) -> ApproxColumnsPosteriorGP:
+    st, dt, S = post._state, post._dtype, post._ncols
+    mm = _Marshal(dt)
+    obj = np.empty(S, dtype=dt)
+    h = C.c_void_p()
+    if Y2 is None:  # new pseudo-points: fx is fz
+        pz = mm.points(fx.x)
+        check(st.ctx.lib.gp_vfe_append_cols(st.handle, C.byref(pz), C.byref(h), obj.ctypes.data))
+        z_all, _ = _stack_inputs(post.approx.fz.x, fx.x)
+        approx = type(post.approx)(post.prior(z_all, post.approx.fz.sigma2))
+        return ApproxColumnsPosteriorGP(approx, post.prior, _VfeState(st.ctx, h), dt, post._m + pz.n, S, obj)
+    Y2 = _cols_matrix(fx, Y2, "update_posterior", S)
+    _refuse_dense_vfe(fx)
+    px = mm.points(fx.x)
+    nz = mm.noise(fx.sigma2, px.n)
+    mean = _mean_vector(post.prior.mean_fn, fx.x, dt)
+    mean = None if mean is None else mm.arr(mean)
+    Yf = mm.arr(Y2, order="F")
+    check(st.ctx.lib.gp_vfe_update_cols(st.handle, C.byref(px), C.byref(nz), mm.ptr(mean), Yf.ctypes.data, max(Yf.shape[0], 1), C.byref(h), obj.ctypes.data))
+    return ApproxColumnsPosteriorGP(post.approx, post.prior, _VfeState(st.ctx, h), dt, post._m, S, obj)
+
+
+def approx_log_evidence_columns(a, fx: FiniteGP, Y) -> np.ndarray:
+    """approx_log_evidence(a, fx, Y[:, s]) for every column s, shape (S,), from one streamed pass (gp_vfe_fit_cols without a handle)."""
+    return _vfe_cols_call(a, fx, Y, False, "approx_log_evidence_columns")[1]
+
+
+def elbo_columns(a, fx: FiniteGP, Y) -> np.ndarray:
+    """elbo(vfe, fx, Y[:, s]) for every column s, shape (S,)."""
+    if not isinstance(a, VFE):
+        raise TypeError("elbo is defined for VFE")
+    return approx_log_evidence_columns(a, fx, Y)
+
+
+def elbo_and_grad_columns(a, fx: FiniteGP, Y, wrt_x: bool = False) -> tuple:
+    """(objectives (S,), gradient of their SUM): one column fit + one backward pass (gp_vfe_fit_cols + gp_vfe_grad_cols).  "x" comes back in the shape
+    of fx.x's array."""
+    post = _vfe_posterior_columns(a, fx, Y)
+    g = post.objective_grad(wrt_x)
+    if wrt_x and "x" in g and np.ndim(g["x"]) == 2 and isinstance(_as_input(fx.x), ColVecs):
+        g["x"] = np.ascontiguousarray(g["x"].T)
+    return post.objective, g

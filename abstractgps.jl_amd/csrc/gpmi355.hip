@@ -2610,7 +2610,7 @@ int32_t gp_ctx_get_param(gp_ctx* c, const char* name, int64_t* out) {
         *out = c->batch_gradx_problems;
         return 0;
     }
-    if (!strcmp(name, "cols_kernel_calls")) {  // kmul launches served by gp_posterior_predict_cols since the ctx was created
+    if (!strcmp(name, "cols_kernel_calls")) {  // kmul launches served by gp_posterior_predict_cols / gp_vfe_predict_cols since the ctx was created
         *out = c->cols_kernel_calls;
         return 0;
     }
@@ -3273,6 +3273,11 @@ int32_t gp_posterior_free(gp_post* post) {
 }
 
 // ---- VFE / DTC ---------------------------------------------------------------------------------------
+// What a handle of gp_vfe_fit_cols with more than one column cannot answer (one α, one y): argument error on the handle, nothing written.
+static int32_t vfe_cols_refused(const char* what) {
+    return set_arg_err(1, (std::string(what) + ": the handle holds more than one column of observations (gp_vfe_fit_cols); use the gp_vfe_*_cols calls").c_str());
+}
+
 int32_t gp_vfe_fit(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_points* z, const gp_noise* noise,
                    double jitter, const void* mean, const void* y, int32_t approx, gp_vfe** out, void* objective_out) {
     Guard gd(c);
@@ -3299,6 +3304,7 @@ int32_t gp_vfe_update(gp_vfe* old, const gp_points* x2, const gp_noise* noise2, 
                       void* objective_out) {
     Guard gd(old);
     if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
+    if (old->ncols > 1) return vfe_cols_refused("gp_vfe_update");
     RC(check_points(x2, 2));
     if (x2->d != old->d) return set_arg_err(2, "x2 has a different D than the training inputs");
     RC(check_noise(noise2, 3, false));
@@ -3322,6 +3328,7 @@ int32_t gp_vfe_update(gp_vfe* old, const gp_points* x2, const gp_noise* noise2, 
 int32_t gp_vfe_append(gp_vfe* old, const gp_points* z2, gp_vfe** out, void* objective_out) {
     Guard gd(old);
     if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
+    if (old->ncols > 1) return vfe_cols_refused("gp_vfe_append");
     RC(check_points(z2, 2));
     if (z2->d != old->d) return set_arg_err(2, "z2 has a different D than the pseudo-points");
     if (!out) return set_arg_err(3, "out is NULL");
@@ -3341,11 +3348,142 @@ int32_t gp_vfe_append(gp_vfe* old, const gp_points* z2, gp_vfe** out, void* obje
     return 0;
 }
 
+// ---- VFE / DTC for a matrix of observations (gp_vfe_fit_cols and its handle) -------------------------------
+static void put_objectives(void* objective_out, int dtype, const std::vector<double>& obj) {
+    if (objective_out)
+        for (size_t i = 0; i < obj.size(); ++i) put(objective_out, dtype, i, obj[i]);
+}
+
+int32_t gp_vfe_fit_cols(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_points* z, const gp_noise* noise, double jitter, const void* mean,
+                        const void* Y, int64_t ldy, int32_t ncols, int32_t approx, gp_vfe** out, void* objective_out) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    ResolvedKernel rk;
+    RC(check_fit_args(k, x, noise, rk, false));
+    RC(check_points(z, 4));
+    if (z->d != x->d) return set_arg_err(4, "z has a different D than x");
+    if (!(jitter >= 0)) return set_arg_err(6, "jitter must be >= 0");
+    if (!Y) return set_arg_err(8, "Y is NULL");
+    if (ldy < x->n) return set_arg_err(9, "ldy < n");
+    if (ncols < 1 || ncols > GPMI355_COLS_MAX) return set_arg_err(10, "ncols must be 1..GPMI355_COLS_MAX");
+    if (approx != 0 && approx != 1) return set_arg_err(11, "approx must be 0 (VFE) or 1 (DTC)");
+    if (out) *out = nullptr;
+    HIPCHK(hipSetDevice(c->device));
+    std::unique_ptr<gp_vfe> p(out ? new gp_vfe() : nullptr);  // out == NULL: the objectives only, no handle
+    if (p) p->ctx = c;
+    std::vector<double> obj((size_t)ncols, 0.0);
+    RC(by_dtype(k->dtype, [&](auto t) {
+        return vfe_fit_impl<decltype(t)>(c, k, x, z, noise, jitter, mean, Y, approx, p.get(), obj.data(), nullptr, VFE_FIT, (long)ldy, ncols);
+    }));
+    put_objectives(objective_out, k->dtype, obj);
+    if (p) publish(c, p, out);
+    return 0;
+}
+
+int32_t gp_vfe_update_cols(gp_vfe* old, const gp_points* x2, const gp_noise* noise2, const void* mean2, const void* Y2, int64_t ldy2, gp_vfe** out,
+                           void* objective_out) {
+    Guard gd(old);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
+    RC(check_points(x2, 2));
+    if (x2->d != old->d) return set_arg_err(2, "x2 has a different D than the training inputs");
+    RC(check_noise(noise2, 3, false));
+    if (!Y2) return set_arg_err(5, "Y2 is NULL");
+    if (ldy2 < x2->n) return set_arg_err(6, "ldy2 < n2");
+    if (!out) return set_arg_err(7, "out is NULL");
+    *out = nullptr;
+    gp_ctx* c = gd.c;
+    HIPCHK(hipSetDevice(c->device));
+    const gp_kernel k = old->kern.view(old->dtype);
+    auto p = std::make_unique<gp_vfe>();
+    p->ctx = c;
+    std::vector<double> obj((size_t)old->ncols, 0.0);
+    RC(by_dtype(old->dtype, [&](auto t) {
+        return vfe_fit_impl<decltype(t)>(c, &k, x2, nullptr, noise2, 0.0, mean2, Y2, old->approx, p.get(), obj.data(), old, VFE_UPDATE, (long)ldy2);
+    }));
+    put_objectives(objective_out, old->dtype, obj);
+    publish(c, p, out);
+    return 0;
+}
+
+int32_t gp_vfe_append_cols(gp_vfe* old, const gp_points* z2, gp_vfe** out, void* objective_out) {
+    Guard gd(old);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
+    RC(check_points(z2, 2));
+    if (z2->d != old->d) return set_arg_err(2, "z2 has a different D than the pseudo-points");
+    if (!out) return set_arg_err(3, "out is NULL");
+    *out = nullptr;
+    if (old->segs.empty()) return set_arg_err(1, "gp_vfe holds no observations");
+    gp_ctx* c = gd.c;
+    HIPCHK(hipSetDevice(c->device));
+    const gp_kernel k = old->kern.view(old->dtype);
+    auto p = std::make_unique<gp_vfe>();
+    p->ctx = c;
+    std::vector<double> obj((size_t)old->ncols, 0.0);
+    RC(by_dtype(old->dtype, [&](auto t) {
+        return vfe_fit_impl<decltype(t)>(c, &k, nullptr, z2, nullptr, 0.0, nullptr, nullptr, old->approx, p.get(), obj.data(), old, VFE_APPEND);
+    }));
+    put_objectives(objective_out, old->dtype, obj);
+    publish(c, p, out);
+    return 0;
+}
+
+int32_t gp_vfe_ncols(gp_vfe* p, int32_t* out) {
+    Guard gd(p);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
+    if (!out) return set_arg_err(2, "out is NULL");
+    *out = p->ncols;
+    return 0;
+}
+
+int32_t gp_vfe_predict_cols(gp_vfe* p, const gp_points* xs, const void* pm, int32_t what, void* mean_out, void* var_out, void* cov_out) {
+    Guard gd(p);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
+    RC(check_test_points(xs, p->d));
+    RC(check_predict_out(what, mean_out, var_out, cov_out, 4));
+    gp_ctx* c = gd.c;
+    HIPCHK(hipSetDevice(c->device));
+    return by_dtype(p->dtype, [&](auto t) { return vfe_predict_cols_impl<decltype(t)>(p, xs, pm, what, mean_out, var_out, cov_out); });
+}
+
+int32_t gp_vfe_get_cols(gp_vfe* p, void* alpha_out, void* meps_out) {
+    Guard gd(p);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
+    gp_ctx* c = gd.c;
+    HIPCHK(hipSetDevice(c->device));
+    const long vst = (long)p->vrows * p->mp;
+    std::vector<double> h((size_t)vst * 3);
+    HIPCHK(hipMemcpy(h.data(), p->vec, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+    for (int col = 0; col < p->ncols; ++col)
+        for (long i = 0; i < p->m; ++i) {
+            if (alpha_out) put(alpha_out, p->dtype, (size_t)col * p->m + i, h[2 * vst + (long)col * p->mp + i]);
+            if (meps_out) put(meps_out, p->dtype, (size_t)col * p->m + i, h[vst + (long)col * p->mp + i]);
+        }
+    return 0;
+}
+
+int32_t gp_vfe_get_by_cols(gp_vfe* p, void* B_out) {
+    Guard gd(p);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
+    if (!B_out) return set_arg_err(2, "B_out is NULL");
+    gp_ctx* c = gd.c;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t es = p->dtype == 0 ? 8 : 4;
+    const size_t n_all = (size_t)p->n_obs;
+    size_t off = 0;
+    for (const auto& sg : p->segs) {  // one segment per fit / update, in arrival order; row s of a segment's b = column s
+        if (sg->n > 0)
+            HIPCHK(hipMemcpy2D((char*)B_out + off, es * n_all, sg->b, es * (size_t)sg->npad, es * (size_t)sg->n, (size_t)p->ncols, hipMemcpyDeviceToHost));
+        off += es * (size_t)sg->n;
+    }
+    return 0;
+}
+
 int32_t gp_vfe_predict(gp_vfe* p, const gp_points* xs, const void* pm, int32_t what, void* mean_out, void* var_out, void* cov_out) {
     Guard gd(p);
     if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
     RC(check_test_points(xs, p->d));
     RC(check_predict_out(what, mean_out, var_out, cov_out, 4));
+    if ((what & 1) && p->ncols > 1) return vfe_cols_refused("gp_vfe_predict (mean)");
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
     return by_dtype(p->dtype, [&](auto t) { return vfe_predict_impl<decltype(t)>(p, xs, pm, what, mean_out, var_out, cov_out); });
@@ -3354,6 +3492,7 @@ int32_t gp_vfe_predict(gp_vfe* p, const gp_points* xs, const void* pm, int32_t w
 int32_t gp_vfe_predict_grad(gp_vfe* p, const gp_points* xs, const void* pm, int32_t what, void* mean_out, void* var_out, void* dmean_out, void* dvar_out) {
     Guard gd(p);
     if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
+    if ((what & 1) && p->ncols > 1) return vfe_cols_refused("gp_vfe_predict_grad (mean side)");
     RC(check_test_points(xs, p->d));
     RC(check_predict_grad_out(what, mean_out, var_out, dmean_out, dvar_out, 4));
     gp_ctx* c = gd.c;
@@ -3365,6 +3504,7 @@ int32_t gp_vfe_logpdf(gp_vfe* p, const gp_points* xs, const void* pm, const gp_n
                       int32_t ncols, void* out) {
     Guard gd(p);
     if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
+    if (p->ncols > 1) return vfe_cols_refused("gp_vfe_logpdf");
     RC(check_joint_args(xs, p->d, noise));
     RC(check_heldout(Y, ldy, ncols, out, xs->n, 5));
     gp_ctx* c = gd.c;
@@ -3383,6 +3523,7 @@ int32_t gp_vfe_logpdf(gp_vfe* p, const gp_points* xs, const void* pm, const gp_n
 int32_t gp_vfe_rand(gp_vfe* p, const gp_points* xs, const void* pm, const gp_noise* noise, const void* xi, int32_t ncols, void* out) {
     Guard gd(p);
     if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
+    if (p->ncols > 1) return vfe_cols_refused("gp_vfe_rand");
     RC(check_joint_args(xs, p->d, noise));
     RC(check_draws(xi, ncols, out, 5));
     gp_ctx* c = gd.c;
@@ -3400,6 +3541,7 @@ int32_t gp_vfe_rand(gp_vfe* p, const gp_points* xs, const void* pm, const gp_noi
 int32_t gp_vfe_get(gp_vfe* p, void* alpha_out, void* meps_out) {
     Guard gd(p);
     if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
+    if (p->ncols > 1) return vfe_cols_refused("gp_vfe_get");
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
     std::vector<double> h((size_t)p->mp * 3);
@@ -3443,6 +3585,7 @@ int64_t gp_vfe_n(gp_vfe* p) {
 int32_t gp_vfe_get_by(gp_vfe* p, void* by_out) {
     Guard gd(p);
     if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
+    if (p->ncols > 1) return vfe_cols_refused("gp_vfe_get_by");
     if (!by_out) return set_arg_err(2, "b_y_out is NULL");
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
@@ -3459,6 +3602,7 @@ int32_t gp_vfe_grad(gp_vfe* p, double* dvariance, double* dscale, double* dnoise
                     void* dx, int32_t x_layout) {
     Guard gd(p);
     if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
+    if (p->ncols > 1) return vfe_cols_refused("gp_vfe_grad");
     if (dz && p->dtype != 0)
         return set_arg_err(7, "pseudo-input gradients need an fp64 handle: the fp32-streamed B Bᵀ of an fp32 fit does not carry the cancellation between the K_zz and K_fz terms");
     if (dz && (z_layout < 0 || z_layout > 2 || (z_layout == 0 && p->d != 1))) return set_arg_err(8, "z_layout must be 0 (vector, D = 1), 1 (ColVecs) or 2 (RowVecs)");
@@ -3466,6 +3610,19 @@ int32_t gp_vfe_grad(gp_vfe* p, double* dvariance, double* dscale, double* dnoise
     gp_ctx* c = gd.c;
     HIPCHK(hipSetDevice(c->device));
     return by_dtype(p->dtype, [&](auto t) { return vfe_grad_impl<decltype(t)>(p, dvariance, dscale, dnoise_sum, dnoise_diag, dy, dz, z_layout, dx, x_layout); });
+}
+
+int32_t gp_vfe_grad_cols(gp_vfe* p, double* dvariance, double* dscale, double* dnoise_sum, void* dnoise_diag, void* dY, double* dz, int32_t z_layout,
+                         void* dx, int32_t x_layout) {
+    Guard gd(p);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_vfe");
+    if (dz && p->dtype != 0)
+        return set_arg_err(7, "pseudo-input gradients need an fp64 handle: the fp32-streamed B Bᵀ of an fp32 fit does not carry the cancellation between the K_zz and K_fz terms");
+    if (dz && (z_layout < 0 || z_layout > 2 || (z_layout == 0 && p->d != 1))) return set_arg_err(8, "z_layout must be 0 (vector, D = 1), 1 (ColVecs) or 2 (RowVecs)");
+    if (dx && (x_layout < 0 || x_layout > 2 || (x_layout == 0 && p->d != 1))) return set_arg_err(10, "x_layout must be 0 (vector, D = 1), 1 (ColVecs) or 2 (RowVecs)");
+    gp_ctx* c = gd.c;
+    HIPCHK(hipSetDevice(c->device));
+    return by_dtype(p->dtype, [&](auto t) { return vfe_grad_impl<decltype(t)>(p, dvariance, dscale, dnoise_sum, dnoise_diag, dY, dz, z_layout, dx, x_layout); });
 }
 
 int64_t gp_vfe_m(gp_vfe* p) {

@@ -1482,6 +1482,62 @@ __global__ __launch_bounds__(256) void vgrad_finish_kernel(const T* __restrict__
     }
 }
 
+// The column forms (gp_vfe_grad_cols: S columns of observations, the gradient of the SUM of their objectives).
+// dst[i][s] = scale · src[s][i] for i < n, s < S and 0 for S <= s < 128 (src: [S][lds_] in T, dst: [n][ldd] doubles; 32×32 tiles through LDS): the chunk's
+// b_y columns as the K-contiguous A operand of the rank-S weight term.  grid (4, ceil(n/32)).
+template <typename T>
+__global__ __launch_bounds__(256) void bt_cols_kernel(const T* __restrict__ src, long lds_, int S, long n, double scale, double* __restrict__ dst, long ldd) {
+    __shared__ double tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const long i0 = (long)blockIdx.y * 32;
+    const int s0 = blockIdx.x * 32;
+#pragma unroll
+    for (int r = ty; r < 32; r += 8) tile[r][tx] = (s0 + r < S && i0 + tx < n) ? scale * (double)src[(long)(s0 + r) * lds_ + i0 + tx] : 0.0;
+    __syncthreads();
+#pragma unroll
+    for (int r = ty; r < 32; r += 8)
+        if (i0 + r < n) dst[(i0 + r) * ldd + s0 + tx] = tile[tx][r];
+}
+// vgrad_finish_kernel for S columns, per chunk.  With r_i = σ_i⁻¹, b_is = r_i δ_is, rq_i the row sum of the chunk's vgrad launch over the combined weights
+// (= Σ_j σ²κ_ij T̃_ij + ½ Σ_s b_is rp_is, rp_is = Σ_j σ²κ_ij α_js) and Pt[s][i] = −r_i rp_is from the chunk's skinny GEMM:
+//   ∂L/∂σ_i² = S(−½ r² [+ ½ σ_k² r⁴ VFE]) + ½ r² Σ_s b_is² − rq r³ + ½ r² Σ_s b_is Pt_si        ∂L/∂Y_is = −r (b_is + Pt_si)
+// dn [n] and dY [S][lddy] in the handle's dtype (either may be NULL); sums as vgrad_finish_kernel.
+template <typename T>
+__global__ __launch_bounds__(256) void vgrad_finish_cols_kernel(const T* __restrict__ rs, const T* __restrict__ b, long ldb, int S, const double* __restrict__ rq,
+                                                                 const double* __restrict__ Pt, long ldp, long n, double variance, int vfe, T* __restrict__ dn,
+                                                                 T* __restrict__ dY, long lddy, double* __restrict__ sums) {
+    __shared__ double red[2][4];
+    double s0 = 0.0, s1 = 0.0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const double r = (double)rs[i], r2 = r * r;
+        double bb = 0.0, bp = 0.0;
+        for (int s = 0; s < S; ++s) {
+            const double bs = (double)b[(long)s * ldb + i], ps = Pt[(long)s * ldp + i];
+            bb = fma(bs, bs, bb);
+            bp = fma(bs, ps, bp);
+            if (dY) dY[(long)s * lddy + i] = (T)(-r * (bs + ps));
+        }
+        const double v = (double)S * (-0.5 * r2 + (vfe ? 0.5 * variance * r2 * r2 : 0.0)) + 0.5 * r2 * bb - rq[i] * r2 * r + 0.5 * r2 * bp;
+        if (dn) dn[i] = (T)v;
+        s0 += v;
+        s1 += r2;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s0 += __shfl_xor(s0, o, 64);
+        s1 += __shfl_xor(s1, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = s0;
+        red[1][threadIdx.x >> 6] = s1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicAdd(sums, red[0][0] + red[0][1] + red[0][2] + red[0][3]);
+        atomicAdd(sums + 1, red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+    }
+}
+
 // out[i][j] = sa·a[hi][lo] + sb·b[hi][lo] + dg·[i == j] + so·v_i v_j   (hi = max(i, j), lo = min(i, j); a, b lower-stored; b, v may be NULL): the symmetric
 // M×M combinations of the sparse gradient (I − A⁻¹ − B Bᵀ from two lower triangles; ½ E − ½ ααᵀ).  grid (ceil(n/256), n)
 __global__ __launch_bounds__(256) void sym_combine_kernel(double* __restrict__ out, long ldo, long n, const double* __restrict__ a, long lda, double sa,
@@ -3302,6 +3358,95 @@ __global__ __launch_bounds__(256) void ystats_kernel(const T* __restrict__ Y, lo
     if (threadIdx.x == 0) {
         rowss[row] += red[0][0] + red[0][1] + red[0][2] + red[0][3];
         cacc[row] -= red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    }
+}
+// The column form of ystats_kernel: S sparse GPs that share x, z, kernel and Σy and differ in y (gp_vfe_fit_cols).  ONE pass over the rows
+// [row_lo + 16·RT·blockIdx.x, + 16·RT) of Y = −B_c (M × ncols, data points contiguous):
+//   rowss[row] += Σ_c Y[row][c]²                                  (fp64, y-free)
+//   Cacc[s][row] −= Σ_c Y[row][c] · By[s][c]   for s < 16·SB      (Cacc: [16·SB][ldc] doubles; By: [16·SB][ldb] in T, zero rows beyond S, zeros beyond the
+//                                                                  segment's valid points)
+// on the fp64 16×16×4 MFMA whatever T is (fp32 operands are widened: their products are exact in fp64, the sums over the data points are fp64 as every
+// N-long reduction of the sparse path).  A = a 16-row tile of Y, B = a 16-column tile of Byᵀ; lane (i = l & 15, q = l >> 4) loads 16 bytes of row i of
+// either operand at data points k0 + VEC·q … (+ VEC), so MFMA step v pairs element v of both — any bijection of the data points onto the MFMA's k works, as
+// long as A and B share it.  Y goes through the streaming loads of ystats_kernel (read once); the By piece is re-read by every workgroup and stays cached.
+// A workgroup owns its rows for all data points and all columns: wave w takes the blocks w, w + 4, … of 4·VEC data points — a split that reads neither S
+// nor the data — and the four partial sums are added through LDS in wave order.  No atomics: bitwise repeatable, and a column's bits do not depend on
+// what the other columns hold.  ncols: a multiple of 16·VEC (the chunk is a multiple of 128).
+template <typename T, int RT>
+__global__ __launch_bounds__(256) void ystats_cols_kernel(const T* __restrict__ Y, long ldy, long ncols, const T* __restrict__ By, long ldb, int SB,
+                                                           long row_lo, double* __restrict__ Cacc, long ldc, double* __restrict__ rowss) {
+    constexpr int VEC = Tr<T>::VEC;
+    typedef typename Tr<T>::chunk_t vec_t;
+    __shared__ double red[4][RT][4][64];
+    __shared__ double redss[4][RT][16];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, q = lane >> 4, i16 = lane & 15;
+    const long row0 = row_lo + (long)blockIdx.x * (16 * RT);
+    d4_t acc[RT][8];
+    double ss[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        ss[rt] = 0;
+#pragma unroll
+        for (int cb = 0; cb < 8; ++cb) acc[rt][cb] = (d4_t)(0.0);
+    }
+    const T* yrow[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) yrow[rt] = Y + (row0 + rt * 16 + i16) * ldy + VEC * q;
+    const T* brow = By + (long)i16 * ldb + VEC * q;
+    for (long k0 = (long)w * (4 * VEC); k0 < ncols; k0 += 16 * VEC) {
+        vec_t a[RT], b[8];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) a[rt] = __builtin_nontemporal_load(reinterpret_cast<const vec_t*>(yrow[rt] + k0));
+#pragma unroll
+        for (int cb = 0; cb < 8; ++cb)
+            if (cb < SB) b[cb] = *reinterpret_cast<const vec_t*>(brow + (long)cb * 16 * ldb + k0);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+                const double av = (double)a[rt][v];
+                ss[rt] = fma(av, av, ss[rt]);
+#pragma unroll
+                for (int cb = 0; cb < 8; ++cb)
+                    if (cb < SB) acc[rt][cb] = Tr<double>::mfma(av, (double)b[cb][v], acc[rt][cb]);
+            }
+        }
+    }
+    // ‖B‖² rows: the four q-lanes of a row, then the waves in order
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+        ss[rt] += __shfl_xor(ss[rt], 16, 64);
+        ss[rt] += __shfl_xor(ss[rt], 32, 64);
+        if (q == 0) redss[w][rt][i16] = ss[rt];
+    }
+    for (int cb = 0; cb < SB; ++cb) {  // (SB is uniform over the workgroup)
+        __syncthreads();               // the previous column block's sums have been read
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                double v = 0;
+#pragma unroll
+                for (int c8 = 0; c8 < 8; ++c8)  // (static register index)
+                    if (c8 == cb) v = acc[rt][c8][r];
+                red[w][rt][r][lane] = v;
+            }
+        __syncthreads();
+        {
+            const int r = w, l = lane;  // thread (r, l) adds element r of lane l of every wave, wave 0 first
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+                const double sum = ((red[0][rt][r][l] + red[1][rt][r][l]) + red[2][rt][r][l]) + red[3][rt][r][l];
+                const long row = row0 + rt * 16 + Tr<double>::crow(l, r);
+                const int col = cb * 16 + (l & 15);
+                Cacc[(long)col * ldc + row] -= sum;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < 16 * RT) {
+        const int rt = tid >> 4, i = tid & 15;
+        rowss[row0 + rt * 16 + i] += ((redss[0][rt][i] + redss[1][rt][i]) + redss[2][rt][i]) + redss[3][rt][i];
     }
 }
 // dst[r][c] = src[r][c] for r < rows, c < cols (cols multiple of 2; 16-B accesses; grid-stride over rows): the 2-D block copy of

@@ -26,10 +26,13 @@
 //                         the retained observations computing ONLY the new block rows of B Bᵀ, B b_y and ‖B‖²
 #pragma once
 
-struct ObsSeg {  // one batch of observations, device resident: T xs[d][npad] (scaled), T rs[npad] = σ⁻¹, T b[npad] = σ⁻¹δ
+struct ObsSeg {  // one batch of observations, device resident: T xs[d][npad] (scaled), T rs[npad] = σ⁻¹, T b[brows][npad] = σ⁻¹δ per column of
+                 // observations (brows = 1 for a one-column handle, else the columns rounded up to 16: the MFMA blocks of ystats_cols_kernel; rows beyond
+                 // the columns and entries beyond n are zero)
     gp_ctx* ctx = nullptr;
     void *xs = nullptr, *rs = nullptr, *b = nullptr;
     long n = 0, npad = 0;
+    int brows = 1;
     ~ObsSeg() {  // runs under the ctx lock (gp_vfe_free / error paths of a locked call)
         ctx_release(ctx, xs, 0);
         ctx_release(ctx, rs, 0);
@@ -46,8 +49,11 @@ struct gp_vfe {
     double jitter = 0;
     void *Lz = nullptr, *Ld = nullptr;  // (mp + 256) × ld doubles: chol(K_zz + jitter I), Λ_ε factor
     void* zs = nullptr;                 // scaled inducing inputs, double [d][mp]
-    void* vec = nullptr;                // double [4][mp]: rows c, m_ε, α, spare
+    void* vec = nullptr;                // double [4][vrows·mp]: rows c, m_ε, α, spare — each [vrows][mp], one mp-long vector per column of observations
     int approx = 0;
+    int ncols = 1;                      // columns of observations (gp_vfe_fit_cols); 1 for every handle of the single-column calls
+    int vrows = 1;                      // rows of b / cacc / the vec blocks: 1 for ncols = 1, else ncols rounded up to 16
+    std::vector<double> ddc;            // ncols > 1: ‖b_s‖² per column (dd is column 0's)
     long n_obs = 0;
     long chunk = 16384;  // data points per streamed chunk of THIS handle (chosen by its first fit; its updates / appends / gradient keep it: the retained segments are padded to it)
     // streaming state before the M×M finalisation: −B Bᵀ (lower), B b_y, per-row ‖B‖², inv(L_z) and scaled z in T
@@ -88,10 +94,16 @@ enum { VFE_FIT = 0, VFE_UPDATE = 1, VFE_APPEND = 2 };
 // mode VFE_FIT:    x, y, noise, z, jitter given; prev == NULL
 // mode VFE_UPDATE: x, y, noise = the NEW observations; z == NULL; kernel / jitter / z from prev
 // mode VFE_APPEND: z = the NEW pseudo-points; x == NULL; everything else from prev
+// ncols columns of observations (gp_vfe_fit_cols; an update / append keeps prev's): yv is n×ncols column-major with leading dimension yld, objective has
+// ncols entries.  Everything but the observations is shared: ONE streamed pass, ystats_cols_kernel in place of ystats_kernel, the M×M vector solves as
+// blocked solves over the columns' rows.  ncols = 1 issues exactly the single-column launches.
 template <typename T>
 static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_points* z, const gp_noise* noise,
                             double jitter, const void* mean_or_null, const void* yv, int approx, gp_vfe* out,
-                            double* objective, const gp_vfe* prev, int mode) {
+                            double* objective, const gp_vfe* prev, int mode, long yld = 0, int ncols_in = 1) {
+    const int S = prev ? prev->ncols : ncols_in;
+    const bool cols = S > 1;
+    const int VR = cols ? (int)round_up(S, 16) : 1;  // rows of b / c_acc / the vec blocks
     const long m_old = prev ? prev->m : 0;
     const long m2 = (mode == VFE_APPEND) ? z->n : 0;
     const long m = mode == VFE_FIT ? z->n : m_old + m2;
@@ -135,11 +147,12 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
     T *xs_h = nullptr, *rs_h = nullptr, *b_h = nullptr;   // the N-long host vectors: page-locked staging of the ctx when it is to be had (three 16 MB uploads from
                                                           // pageable memory cost ≈ 10 ms at N = 2·10⁶; C5's are 1–3 MB and ride behind the prelude either way)
     double logdet_sy = prev ? prev->logdet_sy : 0, dd = prev ? prev->dd : 0, tr_kff = prev ? prev->tr_kff : 0;
+    std::vector<double> ddc = (prev && cols) ? prev->ddc : std::vector<double>(cols ? (size_t)S : 0, 0.0);  // ‖b_s‖² per column
     // the N-long host marshalling (scaled inputs, Σy^-1/2, b_y, the scalar sums: ≈ 1 ms at N = 262 144) runs AFTER the M×M prelude has been queued — the
     // device factors K_zz and inverts L_z meanwhile
     auto marshal_x = [&]() -> int32_t {
         if (!x) return 0;
-        const size_t cnt = (size_t)(d + 2) * (size_t)npad;
+        const size_t cnt = (size_t)(d + 1 + S) * (size_t)npad;   // (the rows of b beyond the S columns are zeroed on the device, not staged)
         xs_h = (T*)ctx_pinned(c, sizeof(T) * cnt);
         if (!xs_h) {
             host_pageable.resize(cnt);
@@ -150,6 +163,54 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
         scale_points_into<T>(k, x, npad, xs_h);
         std::fill(rs_h + n, rs_h + npad, T(0));
         std::fill(b_h + n, b_h + npad, T(0));
+        if (cols) {  // b_y of every column (rows of b_h; the entries beyond n stay zero), Σy shared
+            const bool iso = noise->kind == 0;
+            if (iso && !(noise->s > 0)) return n > 0 ? 1 : 0;
+            const double si_iso = iso ? 1.0 / std::sqrt(noise->s) : 0.0;
+            std::vector<double> si_d(iso ? 0 : (size_t)n);   // σ_i⁻¹ in double, formed once for all columns
+            for (long i = 0; i < n; ++i) {
+                const double s2 = iso ? noise->s : (double)((const T*)noise->diag)[i];
+                if (!(s2 > 0)) return 1 + (int32_t)i;
+                const double si = 1.0 / std::sqrt(s2);
+                rs_h[i] = (T)si;
+                if (!iso) {
+                    si_d[i] = si;
+                    logdet_sy += std::log(s2);
+                    tr_kff += k->variance / s2;
+                }
+            }
+            if (iso) {
+                logdet_sy += (double)n * std::log(noise->s);
+                tr_kff += (double)n * (k->variance / noise->s);
+            }
+            // the N × S values: the columns dealt to up to 8 host threads (a column's b_y and ‖b_s‖² are formed by one thread, in the order of the
+            // single-column loop: the same bits whatever the thread count)
+            auto do_cols = [&](int c0, int c1) {
+                for (int col = c0; col < c1; ++col) {
+                    const T* yc = y + (size_t)col * (size_t)yld;
+                    T* bc = b_h + (size_t)col * npad;
+                    double acc = 0;
+                    for (long i = 0; i < n; ++i) {
+                        const double si = iso ? si_iso : si_d[i];
+                        const T bi = (T)((double)(T)(yc[i] - (mean ? mean[i] : T(0))) * si);
+                        bc[i] = bi;
+                        acc += (double)bi * (double)bi;
+                    }
+                    std::fill(bc + n, bc + npad, T(0));
+                    ddc[col] += acc;
+                }
+            };
+            const int nth = (long)S * n >= (1L << 20) ? std::min(S, 8) : 1;
+            if (nth == 1) {
+                do_cols(0, S);
+            } else {
+                std::vector<std::thread> th;
+                for (int t = 0; t < nth; ++t) th.emplace_back(do_cols, (int)((long)S * t / nth), (int)((long)S * (t + 1) / nth));
+                for (auto& t : th) t.join();
+            }
+            dd = ddc[0];
+            return 0;
+        }
         if (noise->kind == 0) {  // Σy = σ² I: one square root, one logarithm (the general loop below spends ≈ 15 ns per observation on them: 30 ms at N = 2·10⁶)
             const double s2 = noise->s;
             if (!(s2 > 0)) return n > 0 ? 1 : 0;  // chol(Σy) fails at the first observation (reference :61 / :296)
@@ -199,7 +260,9 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
     const long ldy = CH + c->ldpad;             // Y = −B_c (M × CH)
     const size_t X_b = sizeof(T) * (size_t)(CH + 128) * ld, L_b = sizeof(double) * (size_t)(mp + 128 + 128) * ld;
     const size_t Y_b = sizeof(T) * (size_t)(mp + 128) * ldy, Li_b = sizeof(T) * (size_t)(mp + 128) * ld;
-    const size_t vT_b = sizeof(double) * (size_t)mp, vD_b = sizeof(double) * (size_t)mp * 4, jit_b = sizeof(double) * (size_t)mp;
+    const long vst = (long)VR * mp;  // one block of vec / c_acc: a vector of mp entries per column
+    const size_t vT_b = sizeof(double) * (size_t)mp, cT_b = sizeof(double) * (size_t)vst, vD_b = sizeof(double) * (size_t)vst * 4, jit_b = sizeof(double) * (size_t)mp;
+    const size_t R_b = sizeof(double) * (size_t)256 * ld;  // cols: the columns' vectors as 128 right-hand-side rows (+ 128 slack rows) of the blocked solves
     void *zsT_v = 0, *zsD_v = 0, *D_v = 0, *X_v = 0, *Lz_v = 0, *Ld_v = 0, *cT_v = 0, *rss_v = 0, *vec_v = 0, *jit_v = 0, *Y_v = 0,
          *Li_v = 0, *I_v = 0, *S_v = 0, *zn_v = 0, *znD_v = 0, *X2_v = 0, *Y2_v = 0, *S2_v = 0;
     DevBufs bufs(c);
@@ -211,7 +274,23 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
         seg->npad = npad;
         RC(ctx_alloc(c, sizeof(T) * (size_t)d * (size_t)npad, &seg->xs));
         RC(ctx_alloc(c, sizeof(T) * (size_t)npad, &seg->rs));
-        RC(ctx_alloc(c, sizeof(T) * (size_t)npad, &seg->b));
+        RC(ctx_alloc(c, sizeof(T) * (size_t)VR * (size_t)npad, &seg->b));
+        seg->brows = VR;
+    }
+    void *R_v = nullptr, *R2_v = nullptr, *q_v = nullptr;
+    std::vector<double> quad_h(128, 0.0);  // cols: ‖L_D⁻¹ c_s‖² per column
+    struct Dibs {  // cols: the inverse diagonal blocks the blocked solves build — the handle's once it is made, released otherwise
+        gp_ctx* c;
+        DibCache z, d;
+        ~Dibs() {
+            if (z.w) ctx_release(c, z.w, z.bytes);
+            if (d.w) ctx_release(c, d.w, d.bytes);
+        }
+    } dibs{c, DibCache(), DibCache()};
+    if (cols) {
+        RC(bufs.get(R_b, &R_v));
+        RC(bufs.get(R_b, &R2_v));
+        RC(bufs.get(sizeof(double) * 128, &q_v));
     }
     RC(bufs.get(zsT_b, &zsT_v));
     RC(bufs.get(zsD_b, &zsD_v));
@@ -228,7 +307,7 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
         RC(bufs.get(Y_b, &Y2_v));
         if (!is_f64) RC(bufs.get((size_t)NBAT * Li_b, &S2_v));
     }
-    RC(bufs.get(vT_b, &cT_v));
+    RC(bufs.get(cT_b, &cT_v));
     RC(bufs.get(vT_b, &rss_v));
     RC(bufs.get(vD_b, &vec_v));
     RC(bufs.get(jit_b, &jit_v));
@@ -307,8 +386,18 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
                 HIPCHK(hipStreamWaitEvent(sa, e, 0));
                 if (dual) HIPCHK(hipStreamWaitEvent(s, e, 0));
             }
-            hipLaunchKernelGGL(ystats_kernel<T>, dim3((unsigned)(mp - row_lo)), dim3(256), 0, sa, (const T*)Yb[bb], ldy, CH,
-                               (const T*)sg.b + c0, row_lo, (double*)cT_v, (double*)rss_v);   // c += B_c b_c ; ‖B‖² rows (fp64)
+            if (cols) {  // every column's c_s += B_c b_cs and the ‖B‖² rows in one pass over Y: 32 rows per workgroup (mp and row_lo are multiples of 128)
+                // experiment switch GPMI_YSTATS_COLS_ROWS=16: 16 rows per workgroup (twice the workgroups, twice the re-reads of the b chunk) — timed at C5, DESIGN.md
+                static const bool rows16 = [] { const char* e = getenv("GPMI_YSTATS_COLS_ROWS"); return e && !strcmp(e, "16"); }();
+                if (rows16)
+                    hipLaunchKernelGGL((ystats_cols_kernel<T, 1>), dim3((unsigned)((mp - row_lo) / 16)), dim3(256), 0, sa, (const T*)Yb[bb], ldy, CH,
+                                       (const T*)sg.b + c0, sg.npad, VR / 16, row_lo, (double*)cT_v, mp, (double*)rss_v);
+                else
+                    hipLaunchKernelGGL((ystats_cols_kernel<T, 2>), dim3((unsigned)((mp - row_lo) / 32)), dim3(256), 0, sa, (const T*)Yb[bb], ldy, CH,
+                                       (const T*)sg.b + c0, sg.npad, VR / 16, row_lo, (double*)cT_v, mp, (double*)rss_v);
+            } else
+                hipLaunchKernelGGL(ystats_kernel<T>, dim3((unsigned)(mp - row_lo)), dim3(256), 0, sa, (const T*)Yb[bb], ldy, CH,
+                                   (const T*)sg.b + c0, row_lo, (double*)cT_v, (double*)rss_v);   // c += B_c b_c ; ‖B‖² rows (fp64)
             HIPCHK(hipGetLastError());
             if (ovl) {
                 RC(ctx_event(c, &evYs[bb], false));
@@ -375,7 +464,8 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
         HIPCHK(hipMemsetAsync(c->info_dev, 0, sizeof(int), s));
         HIPCHK(hipMemsetAsync(c->scal_dev, 0, sizeof(double) * 16, s));
         HIPCHK(hipMemsetAsync(D_v, 0, D_b, s));
-        HIPCHK(hipMemsetAsync(cT_v, 0, vT_b, s));
+        HIPCHK(hipMemsetAsync(cT_v, 0, cT_b, s));
+        if (cols) HIPCHK(hipMemsetAsync(R_v, 0, R_b, s));
         HIPCHK(hipMemsetAsync(rss_v, 0, vT_b, s));
         HIPCHK(hipMemsetAsync(vec_v, 0, vD_b, s));
         if (mode == VFE_UPDATE) {  // resume: factor of K_zz, its inverse, the scaled inducing inputs and the running sums come from prev
@@ -384,7 +474,7 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
             HIPCHK(hipMemcpyAsync(zsT_v, prev->zsT, zsT_b, hipMemcpyDeviceToDevice, s));
             HIPCHK(hipMemcpyAsync(zsD_v, prev->zs, zsD_b, hipMemcpyDeviceToDevice, s));
             HIPCHK(hipMemcpyAsync(D_v, prev->Dacc, D_b, hipMemcpyDeviceToDevice, s));
-            HIPCHK(hipMemcpyAsync(cT_v, prev->cacc, vT_b, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(cT_v, prev->cacc, cT_b, hipMemcpyDeviceToDevice, s));
             HIPCHK(hipMemcpyAsync(rss_v, prev->rowss, vT_b, hipMemcpyDeviceToDevice, s));
         } else {
             if (mode == VFE_FIT) {
@@ -448,7 +538,8 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
                 // the finished block rows of the accumulators carry over (rows < row_lo; D_acc is lower, so columns < row_lo too)
                 if (row_lo > 0) {
                     HIPCHK(hipMemcpy2DAsync(D_v, sizeof(double) * ld, prev->Dacc, sizeof(double) * ldo, sizeof(double) * row_lo, row_lo, hipMemcpyDeviceToDevice, s));
-                    HIPCHK(hipMemcpyAsync(cT_v, prev->cacc, sizeof(double) * row_lo, hipMemcpyDeviceToDevice, s));
+                    if (cols) HIPCHK(hipMemcpy2DAsync(cT_v, sizeof(double) * mp, prev->cacc, sizeof(double) * mpo, sizeof(double) * row_lo, VR, hipMemcpyDeviceToDevice, s));
+                    else HIPCHK(hipMemcpyAsync(cT_v, prev->cacc, sizeof(double) * row_lo, hipMemcpyDeviceToDevice, s));
                     HIPCHK(hipMemcpyAsync(rss_v, prev->rowss, sizeof(double) * row_lo, hipMemcpyDeviceToDevice, s));
                 }
             }
@@ -468,7 +559,8 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
         if (x) {
             HIPCHK(hipMemcpyAsync(seg->xs, xs_h, sizeof(T) * (size_t)d * (size_t)npad, hipMemcpyHostToDevice, sa));
             HIPCHK(hipMemcpyAsync(seg->rs, rs_h, sizeof(T) * (size_t)npad, hipMemcpyHostToDevice, sa));
-            HIPCHK(hipMemcpyAsync(seg->b, b_h, sizeof(T) * (size_t)npad, hipMemcpyHostToDevice, sa));
+            if (VR > S) HIPCHK(hipMemsetAsync((T*)seg->b + (size_t)S * npad, 0, sizeof(T) * (size_t)(VR - S) * (size_t)npad, sa));  // the MFMA block's rows beyond the columns
+            HIPCHK(hipMemcpyAsync(seg->b, b_h, sizeof(T) * (size_t)S * (size_t)npad, hipMemcpyHostToDevice, sa));
         }
         if (ev_z && x && mode == VFE_FIT && n > 0) {  // chunk 0's kmat beside the prelude (0.34 ms at C5); everything else of the helper stream waits for the prelude below
             HIPCHK(hipStreamWaitEvent(sa, ev_z, 0));
@@ -492,9 +584,11 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
         }
         RC(stream_join());
         HIPCHK(hipEventRecord(c->ev_phase[2], s));
-        hipLaunchKernelGGL((convert_kernel<double, double>), convert_grid(mp), dim3(256), 0, s,
-                           (const double*)cT_v, vec, mp, 1.0);                                                              // c = B b_y
-        HIPCHK(hipGetLastError());
+        if (!cols) {
+            hipLaunchKernelGGL((convert_kernel<double, double>), convert_grid(mp), dim3(256), 0, s,
+                               (const double*)cT_v, vec, mp, 1.0);                                                          // c = B b_y
+            HIPCHK(hipGetLastError());
+        }
         // ---- D = I + B Bᵀ (fp64, symmetric), Λ_ε = chol(D)                                       :68-69
         hipLaunchKernelGGL(neg_sym_to_f64_kernel<double>, dim3((unsigned)((mp + 255) / 256), (unsigned)mp), dim3(256), 0, s,
                            (const double*)D_v, ld, Ld, ld, mp);
@@ -503,6 +597,27 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
         HIPCHK(hipGetLastError());
         RC(potrf_full<double>(c, Ld, ld, mp, mp, c->info_dev + 0, mp, c->scal_dev + 1));
         // ---- vectors
+        if (cols) {
+            // every column at once: the c_s are the rows of R (128 right-hand-side rows, zero beyond S) of the blocked solves the predictions use —
+            // forward against Λ_ε's factor (quad_s = ‖w_s‖²), backward against it (m_ε), backward against L_z (α); the inverse diagonal blocks they build
+            // stay with the handle
+            double* R = (double*)R_v;
+            const size_t rowb = sizeof(double) * (size_t)mp;
+            HIPCHK(hipMemcpy2DAsync(vec, rowb, cT_v, rowb, rowb, VR, hipMemcpyDeviceToDevice, s));                                 // c_s = B b_ys
+            HIPCHK(hipMemcpy2DAsync(R, sizeof(double) * ld, cT_v, rowb, rowb, VR, hipMemcpyDeviceToDevice, s));
+            RC(trsm_cached<double>(c, s, R, ld, 128, Ld, ld, mp, mp, dibs.d, bufs));                                               // w_s = L_D⁻¹ c_s
+            hipLaunchKernelGGL(rowsumsq_kernel<double>, dim3(128), dim3(256), 0, s, (const double*)R, ld, mp, (double*)q_v);
+            HIPCHK(hipGetLastError());
+            BackWs wb;
+            RC(trsm_back_cached<double>(c, s, R, ld, 128, S, Ld, ld, mp, dibs.d, bufs, wb));                                       // m_εs = L_D⁻ᵀ w_s
+            HIPCHK(hipMemcpy2DAsync(vec + vst, rowb, R, sizeof(double) * ld, rowb, VR, hipMemcpyDeviceToDevice, s));
+            // the backward solve uses the inverse diagonal blocks a forward solve leaves: one over zero rows builds L_z's (the first prediction would anyway)
+            HIPCHK(hipMemsetAsync(R2_v, 0, R_b, s));
+            RC(trsm_cached<double>(c, s, (double*)R2_v, ld, 128, Lz, ld, mp, m, dibs.z, bufs));
+            RC(trsm_back_cached<double>(c, s, R, ld, 128, S, Lz, ld, mp, dibs.z, bufs, wb));                                     // α_s = L_z⁻ᵀ m_εs
+            HIPCHK(hipMemcpy2DAsync(vec + 2 * vst, rowb, R, sizeof(double) * ld, rowb, VR, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(quad_h.data(), q_v, sizeof(double) * 128, hipMemcpyDeviceToHost, s));
+        } else {
         HIPCHK(hipMemcpyAsync(vec + mp, vec, sizeof(double) * mp, hipMemcpyDeviceToDevice, s));
         RC(trsv<double>(c, s, Ld, ld, mp, vec + mp, mp, 1, true));                // w = L_D⁻¹ c
         hipLaunchKernelGGL(rowsumsq_kernel<double>, dim3(1), dim3(256), 0, s, vec + mp, mp, mp, c->scal_dev + 3);
@@ -510,6 +625,7 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
         RC(trsv<double>(c, s, Ld, ld, mp, vec + mp, mp, 1, false));               // m_ε = L_D⁻ᵀ w      :71
         HIPCHK(hipMemcpyAsync(vec + 2 * mp, vec + mp, sizeof(double) * mp, hipMemcpyDeviceToDevice, s));
         RC(trsv<double>(c, s, Lz, ld, mp, vec + 2 * mp, mp, 1, false));           // α = L_z⁻ᵀ m_ε      :73
+        }
         HIPCHK(hipEventRecord(c->ev_phase[3], s));
         HIPCHK(hipMemcpyAsync(&info_h, c->info_dev, sizeof(int), hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(scal_h, c->scal_dev, sizeof(double) * 16, hipMemcpyDeviceToHost, s));
@@ -530,7 +646,22 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
     double obj = -0.5 * ((double)n_all * LOG2PI + logdet_sy + logdet_lam + dd - quad);
     if (approx == 0) obj -= 0.5 * (tr_kff - trZ);
     if (objective) *objective = obj;
+    if (cols && objective)  // a column's objective differs in ‖b_s‖² and ‖L_D⁻¹ B b_s‖² only
+        for (int col = 0; col < S; ++col) {
+            double o = -0.5 * ((double)n_all * LOG2PI + logdet_sy + logdet_lam + ddc[col] - quad_h[col]);
+            if (approx == 0) o -= 0.5 * (tr_kff - trZ);
+            objective[col] = o;
+        }
     if (out) {
+        out->ncols = S;
+        out->vrows = VR;
+        out->ddc = ddc;
+        if (cols) {
+            out->dib_z = dibs.z;
+            out->dib_d = dibs.d;
+            dibs.z = DibCache();
+            dibs.d = DibCache();
+        }
         out->ctx = c;
         out->dtype = k->dtype;
         out->m = m; out->mp = mp; out->ld = ld; out->d = d; out->jitter = jitter;
@@ -702,6 +833,42 @@ static int32_t vfe_predict_impl(gp_vfe* p, const gp_points* xs, const void* pm, 
     return 0;
 }
 
+// gp_vfe_predict_cols: the means of every column, mean_out (ns × ncols column-major) = m(x*) + K(x*, z) A with A = the M × ncols matrix of the α_s, by ONE
+// kmul launch over the pseudo-points (gpmi355.hip kmul: K_*z evaluated once for all columns, fixed-order partial sums); variance and covariance do not
+// depend on y and come from vfe_predict_impl.  fp64 on the device whatever the handle's dtype, as every prediction of the sparse path.
+template <typename T>
+static int32_t vfe_predict_cols_impl(gp_vfe* p, const gp_points* xs, const void* pm, int what, void* mean_out, void* var_out, void* cov_out) {
+    gp_ctx* c = p->ctx;
+    if (p->ncols == 1) return vfe_predict_impl<T>(p, xs, pm, what, mean_out, var_out, cov_out);  // one column: the call IS gp_vfe_predict
+    if (what & 1) {
+        const long mp = p->mp, ns = xs->n, nsp = round_up(ns, 128);
+        const int S = p->ncols;
+        const gp_kernel k = p->kern.view(0);
+        StagedPoints<T, double> sx;
+        DevBufs bufs(c);
+        void* m_v = nullptr;
+        hipStream_t s = c->sm;
+        c->ev_used = 0;
+        c->gemm_recs.clear();
+        std::vector<double> mh((size_t)ns * S);
+        const double* alpha = (const double*)p->vec + 2 * (long)p->vrows * mp;
+        const int32_t rc = run_drained(c, [&]() -> int32_t {
+            RC(sx.stage(c, bufs, &k, xs, nsp));
+            RC(bufs.get(sizeof(double) * (size_t)nsp * S, &m_v));
+            RC(kmul<double>(c, bufs, p->kern.desc(), ns, s, sx.ptr(), nsp, (const double*)p->zs, mp, p->d, p->m, alpha, mp, S, (double*)m_v, nsp));
+            HIPCHK(hipMemcpy2DAsync(mh.data(), sizeof(double) * ns, m_v, sizeof(double) * nsp, sizeof(double) * ns, S, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            return 0;
+        });
+        if (rc != 0) return rc;
+        const T* prior = (const T*)pm;
+        for (int col = 0; col < S; ++col)
+            for (long i = 0; i < ns; ++i) ((T*)mean_out)[(size_t)col * ns + i] = (T)((prior ? (double)prior[i] : 0.0) + mh[(size_t)col * ns + i]);
+    }
+    if (what & 6) return vfe_predict_impl<T>(p, xs, pm, what & 6, nullptr, var_out, cov_out);
+    return 0;
+}
+
 // Predictive mean / variance of a sparse posterior AND their gradients w.r.t. the test inputs (include/gpmi355.h gp_vfe_predict_grad), next to
 // vfe_predict_impl and with its buffers (fp64 whatever the handle's dtype; results rounded to T).  With A_j = L_z⁻¹ K(z, x*_j) a row of X1 = K_*z L_z⁻ᵀ:
 //   ∂mean_j = Σ_m α_m ∂k(x*_j, z_m),   ∂var_j = −2 Σ_m u_jm ∂k(x*_j, z_m),   u_j = L_z⁻ᵀ (A_j − Λ_ε⁻¹ A_j)
@@ -862,11 +1029,29 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
     RC(bufs.get(X_b, &C2_v));
     RC(bufs.get(g_b, &g_v));
     RC(bufs.get(gz_b, &gz_v));
+    // Columns (gp_vfe_grad_cols: the gradient of Σ_s objective_s; dy is then dY, n × S column-major).  The M×M algebra with the column sums folded in:
+    //   G = ½[S·W H Wᵀ − A Aᵀ] (A = the M × S matrix of the α_s): one rank-S MFMA GEMM E −= (A/√S)(A/√S)ᵀ before the combination, weight S/2.
+    // Per chunk two skinny MFMA GEMMs beside T̃ = (S K_c) G_ψ: the rank-S term of the weights, C −= (½√S b_c)(A/√S)ᵀ — so the chunk's −C is T̃ + ½ b_c Aᵀ and
+    // vgrad runs unchanged with ν = 0 — and Pt = −Aᵀ(S K_c)ᵀ (128 × CH), the per-column row sums; vgrad_finish_cols_kernel finishes ∂/∂σ_i², ∂/∂Y per chunk.
+    const int S = p->ncols;
+    const bool cols = S > 1;
+    const long ldt = 128 + c->ldpad, ldpt = CH + c->ldpad;
+    const size_t At_b = sizeof(double) * (size_t)256 * ld, A2_b = sizeof(double) * (size_t)(mp + 128) * ldt, Bt_b = sizeof(double) * (size_t)(CH + 128) * ldt,
+                 Pt_b = sizeof(double) * (size_t)256 * ldpt;
+    void *At_v = 0, *Ats_v = 0, *A2_v = 0, *Bt_v = 0, *Pt_v = 0, *nu0_v = 0;
+    if (cols) {
+        RC(bufs.get(At_b, &At_v));    // rows α_s
+        RC(bufs.get(At_b, &Ats_v));   // rows α_s/√S
+        RC(bufs.get(A2_b, &A2_v));    // its transpose: mp × 128
+        RC(bufs.get(Bt_b, &Bt_v));    // the chunk's ½√S b_y columns, CH × 128
+        RC(bufs.get(Pt_b, &Pt_v));
+        RC(bufs.get(sizeof(double) * (size_t)mp, &nu0_v));
+    }
     DevScales sc;
     double *W = (double*)W_v, *V = (double*)V_v, *H = (double*)H_v, *R = (double*)R_v, *E = (double*)E_v, *Gp = (double*)Gp_v, *Gz = (double*)Gz_v;
     const double* Lz = (const double*)p->Lz;
     const double* Ld = (const double*)p->Ld;
-    const double* alpha = (const double*)p->vec + 2 * mp;
+    const double* alpha = (const double*)p->vec + 2 * (long)p->vrows * mp;   // (columns: the rows α_s, mp apart)
     std::vector<double> g_h((size_t)(2 + nsc + 2), 0.0), gz_h((size_t)d * mp, 0.0);   // [0] ∂/∂variance, [2 + p] ∂/∂scale_p, [2 + nsc] Σ ∂/∂σ_i², [3 + nsc] Σ σ_i⁻²
     // per observation (concatenated over the segments, arrival order): what the host needs to finish ∂/∂σ_i², ∂/∂y_i, ∂/∂x_i
     long n_all = 0;
@@ -881,7 +1066,13 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
         GridMap ge = plain_map(1, 0, 0);
         ge.beta0 = 1;
         RC(launch_gemm<double>(c, s, E, ld, R, ld, W, ld, mp, mp, mp, ge));                    // E = −R Wᵀ = W Hm Wᵀ (lower)
-        hipLaunchKernelGGL(sym_combine_kernel, sq, dim3(256), 0, s, G, ld, mp, (const double*)E, ld, 0.5, (const double*)nullptr, 0L, 0.0, 0.0, alpha, -0.5);
+        if (cols) {  // G = (S/2) [W Hm Wᵀ − (A/√S)(A/√S)ᵀ]
+            RC(launch_gemm<double>(c, s, E, ld, (const double*)A2_v, ldt, (const double*)A2_v, ldt, mp, mp, 128, plain_map(1, 0, 0)));
+            hipLaunchKernelGGL(sym_combine_kernel, sq, dim3(256), 0, s, G, ld, mp, (const double*)E, ld, 0.5 * S, (const double*)nullptr, 0L, 0.0, 0.0,
+                               (const double*)nullptr, 0.0);
+        } else {
+            hipLaunchKernelGGL(sym_combine_kernel, sq, dim3(256), 0, s, G, ld, mp, (const double*)E, ld, 0.5, (const double*)nullptr, 0L, 0.0, 0.0, alpha, -0.5);
+        }
         HIPCHK(hipGetLastError());
         return 0;
     };
@@ -895,6 +1086,20 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
         if (C2_v) HIPCHK(hipMemsetAsync(C2_v, 0, X_b, s));
         HIPCHK(hipMemsetAsync(X_v, 0, X_b, s));
         if (X2_v) HIPCHK(hipMemsetAsync(X2_v, 0, X_b, s));
+        if (cols) {
+            for (void* q : {At_v, Ats_v}) HIPCHK(hipMemsetAsync(q, 0, At_b, s));
+            HIPCHK(hipMemsetAsync(A2_v, 0, A2_b, s));
+            HIPCHK(hipMemsetAsync(Bt_v, 0, Bt_b, s));
+            HIPCHK(hipMemsetAsync(Pt_v, 0, Pt_b, s));
+            HIPCHK(hipMemsetAsync(nu0_v, 0, sizeof(double) * (size_t)mp, s));
+            HIPCHK(hipMemcpy2DAsync(At_v, sizeof(double) * ld, alpha, sizeof(double) * mp, sizeof(double) * mp, S, hipMemcpyDeviceToDevice, s));
+            hipLaunchKernelGGL((convert_kernel<double, double>), convert_grid(256 * ld), dim3(256), 0, s, (const double*)At_v, (double*)Ats_v, 256 * ld,
+                               1.0 / std::sqrt((double)S));
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(transpose_rect_kernel<double>, dim3((unsigned)((mp + 31) / 32), 4), dim3(256), 0, s, (const double*)Ats_v, ld, (double*)A2_v, ldt,
+                               128L, mp, 0);
+            HIPCHK(hipGetLastError());
+        }
         // ---- M×M side, fp64
         RC(vfe_upper_inverse(c, s, Lz, ld, mp, W, L_b, bufs));                                  // W = L_z⁻ᵀ
         RC(vfe_upper_inverse(c, s, Ld, ld, mp, V, L_b, bufs));                                  // V = Λ_ε.L⁻ᵀ
@@ -922,9 +1127,11 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
             const ObsSeg* sg;
             long c0;
             double *rq, *rp, *gx;
+            size_t si;  // its segment
         };
         std::vector<Ck> cks;
         std::vector<std::array<void*, 3>> segb;
+        std::vector<std::array<void*, 2>> segc;  // columns: per segment ∂/∂σ_i² [npad] and ∂/∂Y [S][npad] in T
         for (auto& sgp : p->segs) {
             const ObsSeg& sg = *sgp;
             void *rq_v = 0, *rp_v = 0, *gx_v = 0;
@@ -936,14 +1143,21 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
             HIPCHK(hipMemsetAsync(rp_v, 0, r_b, s));
             if (dx) HIPCHK(hipMemsetAsync(gx_v, 0, r_b * d, s));
             segb.push_back({rq_v, rp_v, gx_v});
-            for (long c0 = 0; c0 < sg.npad && c0 < sg.n; c0 += CH) cks.push_back({&sg, c0, (double*)rq_v + c0, (double*)rp_v + c0, dx ? (double*)gx_v + c0 : nullptr});
+            void *dn_v = 0, *dY_v = 0;
+            if (cols && sg.n > 0) {  // ∂/∂σ_i² and ∂/∂Y of the segment, written chunk by chunk
+                RC(bufs.get(sizeof(T) * (size_t)sg.npad, &dn_v));
+                if (dy) RC(bufs.get(sizeof(T) * (size_t)S * (size_t)sg.npad, &dY_v));
+            }
+            segc.push_back({dn_v, dY_v});
+            for (long c0 = 0; c0 < sg.npad && c0 < sg.n; c0 += CH)
+                cks.push_back({&sg, c0, (double*)rq_v + c0, (double*)rp_v + c0, dx ? (double*)gx_v + c0 : nullptr, segc.size() - 1});
         }
         // One stream.  The two-stream forms were measured at C5 (fp64 handle, tools/c5_grad_probe.py): helpers on the ctx's high-priority stream beside the GEMMs
         // 146.8 ms against 142.5 serial; GEMMs on the high-priority stream, helpers on the main one 142.6 / 143.3; and after the helper kernel lost its scratch
         // traffic (vgrad_fast_kernel: 1.1 -> 0.25 ms per chunk) 132.4 with two streams against 129.1 with one — what is left beside the GEMM (kmat + vgrad ≈ 0.4 ms
         // of 8.1 per chunk) costs more as a co-runner than in line.  The double buffers and events below stay for the experiment switch GPMI_VGRAD_STREAMS=2.
         static const bool two_streams = [] { const char* e = getenv("GPMI_VGRAD_STREAMS"); return e && e[0] == '2'; }();
-        const bool ovl = two_streams && c->vfe_overlap != 0;
+        const bool ovl = two_streams && c->vfe_overlap != 0 && !cols;  // (the column form has one chunk-weight operand buffer: one stream)
         hipStream_t sa = s, sg = ovl ? c->sp : s;
         void* Xb[2] = {X_v, X2_v};
         void* Cb[2] = {C_v, C2_v};
@@ -1009,17 +1223,37 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
                 HIPCHK(hipEventRecord(evG[bb], sg));
             }
             const In I = in[bb];
+            const double* nuv = cols ? (const double*)nu0_v : alpha;
+            if (cols) {
+                const ObsSeg& sgc = *cks[ci].sg;
+                hipLaunchKernelGGL(bt_cols_kernel<T>, dim3(4, (unsigned)(CH / 32)), dim3(256), 0, sg, (const T*)sgc.b + cks[ci].c0, sgc.npad, S, CH,
+                                   0.5 * std::sqrt((double)S), (double*)Bt_v, ldt);
+                HIPCHK(hipGetLastError());
+                RC(launch_gemm<double>(c, sg, (double*)Cb[bb], ld, (const double*)Bt_v, ldt, (const double*)A2_v, ldt, CH, mp, 128, plain_map(0, 0, 0)));  // C −= ½ b_c Aᵀ
+                GridMap gp = plain_map(0, 0, 0);
+                gp.beta0 = 1;
+                RC(launch_gemm<double>(c, sg, (double*)Pt_v, ldpt, (const double*)At_v, ld, (const double*)Xb[bb], ld, 128, CH, mp, gp));                  // Pt = −Aᵀ (S K_c)ᵀ
+            }
             if (ci + 1 < cks.size()) RC(prep(ci + 1));  // beside this chunk's GEMM
             if (ovl) HIPCHK(hipStreamWaitEvent(sa, evG[bb], 0));
             dim3 grid((unsigned)(mp / 128), (unsigned)((I.nr + 127) / 128));
             if (dx)
                 RC((launch_vgrad<double, true>(sa, grid, (const double*)Cb[bb], ld, 0, I.xr, I.ldxr, (const double*)p->zs, mp, d, p->kern.kind, p->kern.variance, p->kern.nscale(),
-                                               sc.ptr(), I.rs, I.b, alpha, I.nr, m, (double*)g_v, (double*)gz_v, mp, 1.0, cks[ci].rq, cks[ci].rp,
+                                               sc.ptr(), I.rs, I.b, nuv, I.nr, m, (double*)g_v, (double*)gz_v, mp, 1.0, cks[ci].rq, cks[ci].rp,
                                                cks[ci].gx, cks[ci].sg->npad)));
             else
                 RC((launch_vgrad<double, false>(sa, grid, (const double*)Cb[bb], ld, 0, I.xr, I.ldxr, (const double*)p->zs, mp, d, p->kern.kind, p->kern.variance, p->kern.nscale(),
-                                                sc.ptr(), I.rs, I.b, alpha, I.nr, m, (double*)g_v, (double*)gz_v, mp, 1.0, cks[ci].rq, cks[ci].rp,
+                                                sc.ptr(), I.rs, I.b, nuv, I.nr, m, (double*)g_v, (double*)gz_v, mp, 1.0, cks[ci].rq, cks[ci].rp,
                                                 (double*)nullptr, 0L)));
+            if (cols) {  // the chunk's rows of rq are complete: ∂/∂σ_i², ∂/∂Y of its observations
+                const ObsSeg& sgc = *cks[ci].sg;
+                const long c0 = cks[ci].c0;
+                T* dYs = (T*)segc[cks[ci].si][1];
+                hipLaunchKernelGGL(vgrad_finish_cols_kernel<T>, dim3((unsigned)std::min<long>((I.nr + 255) / 256, 2048)), dim3(256), 0, sa, (const T*)sgc.rs + c0,
+                                   (const T*)sgc.b + c0, sgc.npad, S, (const double*)cks[ci].rq, (const double*)Pt_v, ldpt, I.nr, p->kern.variance, vfe ? 1 : 0,
+                                   (T*)segc[cks[ci].si][0] + c0, dYs ? dYs + c0 : (T*)nullptr, sgc.npad, (double*)g_v + 2 + nsc);
+                HIPCHK(hipGetLastError());
+            }
             if (ovl) {
                 RC(ctx_event(c, &evV[bb], false));
                 HIPCHK(hipEventRecord(evV[bb], sa));
@@ -1031,6 +1265,12 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
         for (size_t si = 0; si < p->segs.size(); ++si) {
             const ObsSeg& sg = *p->segs[si];
             if (sg.n == 0) continue;
+            if (cols) {  // finished chunk by chunk above; dY: n_all × S column-major on the host
+                if (dnoise) HIPCHK(hipMemcpyAsync((T*)dnoise + off, segc[si][0], sizeof(T) * (size_t)sg.n, hipMemcpyDeviceToHost, s));
+                if (dy)
+                    HIPCHK(hipMemcpy2DAsync((T*)dy + off, sizeof(T) * (size_t)n_all, segc[si][1], sizeof(T) * (size_t)sg.npad, sizeof(T) * (size_t)sg.n, (size_t)S,
+                                            hipMemcpyDeviceToHost, s));
+            } else {
             void *dn_v = 0, *dy_v = 0;
             RC(bufs.get(sizeof(T) * (size_t)sg.n, &dn_v));
             RC(bufs.get(sizeof(T) * (size_t)sg.n, &dy_v));
@@ -1039,6 +1279,7 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
             HIPCHK(hipGetLastError());
             if (dnoise) HIPCHK(hipMemcpyAsync((T*)dnoise + off, dn_v, sizeof(T) * (size_t)sg.n, hipMemcpyDeviceToHost, s));
             if (dy) HIPCHK(hipMemcpyAsync((T*)dy + off, dy_v, sizeof(T) * (size_t)sg.n, hipMemcpyDeviceToHost, s));
+            }
             if (dx) {
                 std::vector<double> gx_h((size_t)sg.npad * d);
                 HIPCHK(hipMemcpyAsync(gx_h.data(), segb[si][2], sizeof(double) * (size_t)sg.npad * d, hipMemcpyDeviceToHost, s));
@@ -1063,7 +1304,7 @@ static int32_t vfe_grad_impl(gp_vfe* p, double* dvar, double* dscale, double* dn
         return phase_timings(c);  // gp_timings: assemble_ms = the M×M side, potrf_ms = the streamed pass, solve_ms = the K_zz term
     });
     if (rc != 0) return rc;
-    if (dvar) *dvar = g_h[0] - (vfe ? 0.5 * g_h[3 + nsc] : 0.0);   // − ½ Σ_i ∂k_ii/∂σ_k² / σ_i²: the trace term
+    if (dvar) *dvar = g_h[0] - (vfe ? 0.5 * (double)S * g_h[3 + nsc] : 0.0);   // − ½ Σ_i ∂k_ii/∂σ_k² / σ_i²: the trace term (once per column)
     if (dscale)
         for (int q = 0; q < p->kern.nscale(); ++q) dscale[q] = g_h[2 + q];
     if (dnoise_sum) *dnoise_sum = g_h[2 + nsc];

@@ -28,7 +28,7 @@ using KernelFunctions: SqExponentialKernel, Matern12Kernel, ExponentialKernel, M
 using LinearAlgebra, FillArrays, Statistics, StatsBase, Distributions, Random
 using ChainRulesCore
 
-export HipGP, HipPosteriorGP, HipColumnsPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, loo_mean_and_var, loo_logpdf, loo_logpdf_and_grad, posterior_columns, logpdf_and_grad_columns, elbo_and_grad, logpdf_batch, mean_and_var_batch, mean_and_var_grad_batch, joint_batch, mean_and_cov_batch, logpdf_heldout_batch, rand_batch, logpdf_and_grad_batch, BatchPosDefException
+export HipGP, HipPosteriorGP, HipColumnsPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, loo_mean_and_var, loo_logpdf, loo_logpdf_and_grad, posterior_columns, logpdf_and_grad_columns, elbo_and_grad, HipApproxColumnsPosteriorGP, elbo_columns, approx_log_evidence_columns, elbo_and_grad_columns, objective_grad, columns_data, logpdf_batch, mean_and_var_batch, mean_and_var_grad_batch, joint_batch, mean_and_cov_batch, logpdf_heldout_batch, rand_batch, logpdf_and_grad_batch, BatchPosDefException
 
 const libgpmi355 = get(ENV, "GPMI355_LIB", joinpath(@__DIR__, "..", "csrc", "libgpmi355.so"))
 
@@ -1705,6 +1705,165 @@ function AbstractGPs.update_posterior(f::HipApproxPosteriorGP, fz::FiniteGP{<:Hi
     end
     fz_new = f.approx.fz.f(vcat(f.approx.fz.x, fz.x), f.approx.fz.Σy)                         # :160-162
     return approx_posterior(typeof(f.approx)(fz_new), f.prior, h, T, obj[], getfield(f, :x), getfield(f, :Σy))
+end
+
+# ---- VFE / DTC for a matrix of observations (include/gpmi355.h "VFE / DTC for a matrix of observations") ------------------
+# S = size(Y, 2) <= 128 sparse GPs that share x, z, kernel, jitter, Σy and the prior mean and differ in y: posterior_columns(approx, fx, Y) fits them from ONE
+# streamed pass (gp_vfe_fit_cols), mean(f, x) is length(x)×S from ONE kernel launch over the pseudo-points (gp_vfe_predict_cols), var / cov do not depend
+# on y; update_posterior continues all columns (gp_vfe_update_cols / gp_vfe_append_cols); elbo_and_grad_columns returns the objectives (length S) and the
+# gradient of their SUM (gp_vfe_grad_cols).  Single-kind kernels with a scalar / diagonal Σy, as the single-column sparse calls.
+struct HipApproxColumnsPosteriorGP{Tapprox,Tprior<:HipGP} <: AbstractGP
+    approx::Tapprox
+    prior::Tprior
+    handle::Base.RefValue{Ptr{Cvoid}}
+    T::DataType
+    ncols::Int
+    objective::Vector{Float64}         # ELBO / DTC evidence of every column from the same streamed pass
+end
+function approx_columns_posterior(approx, prior, h::Base.RefValue{Ptr{Cvoid}}, ::Type{T}, S, obj) where {T}
+    finalizer(hh -> ccall((:gp_vfe_free, libgpmi355), Int32, (Ptr{Cvoid},), hh[]), h)
+    return HipApproxColumnsPosteriorGP(approx, prior, h, T, Int(S), Vector{Float64}(obj))
+end
+
+function vfe_cols_call(approx::Union{VFE,DTC}, fx::FiniteGP{<:HipGP}, Y::AbstractMatrix{<:Real}, want_post::Bool)
+    @assert approx.fz.f === fx.f
+    a, Yv = columns_args(fx, Y)
+    (haskey(a, :ks) || is_dense(a.cn)) && throw(ArgumentError("VFE / DTC columns: composite kernels and a dense Σy are not accelerated"))
+    T = a.T
+    pz = points(approx.fz.x, T)
+    pz === nothing && throw(ArgumentError("unsupported container for the pseudo-points"))
+    jit = approx.fz.Σy
+    jit isa Diagonal{<:Any,<:Fill} || throw(ArgumentError("inducing-point noise must be a scalar jitter"))
+    jitter = Float64(FillArrays.getindex_value(jit.diag))
+    zbuf, cz = pz
+    n, S = size(Yv)
+    obj = Vector{T}(undef, S)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    mptr = a.m === nothing ? C_NULL : pointer(a.m)
+    GC.@preserve a zbuf Yv obj h begin
+        check(ccall((:gp_vfe_fit_cols, libgpmi355), Int32,
+            (Ptr{Cvoid}, Ref{CKernel}, Ref{CPoints}, Ref{CPoints}, Ref{CNoise}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32,
+                Ptr{Ptr{Cvoid}}, Ptr{Cvoid}),
+            fx.f.ctx.handle, a.ck, a.cx, cz, a.cn, jitter, mptr, Yv, max(n, 1), S, approx isa VFE ? 0 : 1,
+            want_post ? h : Ptr{Ptr{Cvoid}}(C_NULL), obj))
+    end
+    return (h, Vector{Float64}(obj), T, S)
+end
+
+function posterior_columns(approx::Union{VFE,DTC}, fx::FiniteGP{<:HipGP}, Y::AbstractMatrix{<:Real})
+    h, obj, T, S = vfe_cols_call(approx, fx, Y, true)
+    return approx_columns_posterior(approx, fx.f, h, T, S, obj)
+end
+approx_log_evidence_columns(approx::Union{VFE,DTC}, fx::FiniteGP{<:HipGP}, Y::AbstractMatrix{<:Real}) = vfe_cols_call(approx, fx, Y, false)[2]
+elbo_columns(vfe::VFE, fx::FiniteGP{<:HipGP}, Y::AbstractMatrix{<:Real}) = approx_log_evidence_columns(vfe, fx, Y)
+
+function ncolumns(f::HipApproxColumnsPosteriorGP)
+    out = Ref{Int32}(0)
+    check(ccall((:gp_vfe_ncols, libgpmi355), Int32, (Ptr{Cvoid}, Ref{Int32}), getfield(f, :handle)[], out))
+    return Int(out[])
+end
+
+# (α, m_ε) of every column, both M×S, and b_y, n×S: the y-dependent cache fields (src/sparse_approximations.jl:73) column by column
+function columns_data(f::HipApproxColumnsPosteriorGP)
+    T = getfield(f, :T)
+    h = getfield(f, :handle)
+    S = getfield(f, :ncols)
+    m = Int(ccall((:gp_vfe_m, libgpmi355), Int64, (Ptr{Cvoid},), h[]))
+    n = Int(ccall((:gp_vfe_n, libgpmi355), Int64, (Ptr{Cvoid},), h[]))
+    α = Matrix{T}(undef, m, S); m_ε = Matrix{T}(undef, m, S); b_y = Matrix{T}(undef, n, S)
+    GC.@preserve f α m_ε b_y begin
+        check(ccall((:gp_vfe_get_cols, libgpmi355), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), h[], α, m_ε))
+        check(ccall((:gp_vfe_get_by_cols, libgpmi355), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), h[], b_y))
+    end
+    return (α=α, m_ε=m_ε, b_y=b_y)
+end
+
+function predict(f::HipApproxColumnsPosteriorGP, x::AbstractVector, what::Integer)
+    T = getfield(f, :T)
+    px = points(x, T)
+    px === nothing && throw(ArgumentError("unsupported input container for the accelerated posterior (use a Vector, ColVecs or RowVecs)"))
+    xbuf, cx = px
+    ns = length(x)
+    pm = prior_mean(f.prior.gp, x, T)
+    m = (what & 1) != 0 ? Matrix{T}(undef, ns, getfield(f, :ncols)) : Matrix{T}(undef, 0, 0)
+    v = (what & 2) != 0 ? Vector{T}(undef, ns) : T[]
+    c = (what & 4) != 0 ? Matrix{T}(undef, ns, ns) : Matrix{T}(undef, 0, 0)
+    GC.@preserve f xbuf pm m v c begin
+        check(ccall((:gp_vfe_predict_cols, libgpmi355), Int32,
+            (Ptr{Cvoid}, Ref{CPoints}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+            getfield(f, :handle)[], cx, pm === nothing ? C_NULL : pointer(pm), what, m, v, c))
+    end
+    return m, v, c
+end
+Statistics.mean(f::HipApproxColumnsPosteriorGP, x::AbstractVector) = predict(f, x, 1)[1]            # length(x)×S
+Statistics.var(f::HipApproxColumnsPosteriorGP, x::AbstractVector) = predict(f, x, 2)[2]
+Statistics.cov(f::HipApproxColumnsPosteriorGP, x::AbstractVector) = predict(f, x, 4)[3]
+StatsBase.mean_and_var(f::HipApproxColumnsPosteriorGP, x::AbstractVector) = predict(f, x, 3)[1:2]
+function StatsBase.mean_and_cov(f::HipApproxColumnsPosteriorGP, x::AbstractVector)
+    m, _, c = predict(f, x, 5)
+    return m, c
+end
+(f::HipApproxColumnsPosteriorGP)(x...) = throw(ArgumentError("a FiniteGP over a column posterior is not offered: use posterior(approx, fx, Y[:, s])"))
+
+function AbstractGPs.update_posterior(f::HipApproxColumnsPosteriorGP, fx::FiniteGP{<:HipGP}, Y::AbstractMatrix{<:Real})
+    @assert f.prior === fx.f
+    T = getfield(f, :T)
+    S = getfield(f, :ncols)
+    size(Y, 1) == length(fx) || throw(DimensionMismatch("length(fx) = $(length(fx)) but Y has $(size(Y, 1)) rows"))
+    size(Y, 2) == S || throw(DimensionMismatch("Y has $(size(Y, 2)) columns but the posterior holds $S"))
+    xbuf, cx, nbuf, cn, m2 = joint_args(fx, f.prior.gp, T)
+    is_dense(cn) && throw(ArgumentError("update_posterior of a VFE / DTC posterior with a dense Σy is not accelerated (the reference factors Σy there)"))
+    Yv = Matrix{T}(Y)
+    obj = Vector{T}(undef, S)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve f xbuf nbuf m2 Yv obj begin
+        check(ccall((:gp_vfe_update_cols, libgpmi355), Int32,
+            (Ptr{Cvoid}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ref{Ptr{Cvoid}}, Ptr{Cvoid}),
+            getfield(f, :handle)[], cx, cn, m2 === nothing ? C_NULL : pointer(m2), Yv, max(size(Yv, 1), 1), h, obj))
+    end
+    return approx_columns_posterior(f.approx, f.prior, h, T, S, obj)
+end
+
+function AbstractGPs.update_posterior(f::HipApproxColumnsPosteriorGP, fz::FiniteGP{<:HipGP})
+    @assert f.prior === fz.f
+    T = getfield(f, :T)
+    S = getfield(f, :ncols)
+    pz = points(fz.x, T)
+    pz === nothing && throw(ArgumentError("unsupported container for the new pseudo-points"))
+    zbuf, cz = pz
+    obj = Vector{T}(undef, S)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve f zbuf obj begin
+        check(ccall((:gp_vfe_append_cols, libgpmi355), Int32, (Ptr{Cvoid}, Ref{CPoints}, Ref{Ptr{Cvoid}}, Ptr{Cvoid}), getfield(f, :handle)[], cz, h, obj))
+    end
+    fz_new = f.approx.fz.f(vcat(f.approx.fz.x, fz.x), f.approx.fz.Σy)
+    return approx_columns_posterior(typeof(f.approx)(fz_new), f.prior, h, T, S, obj)
+end
+
+# the objectives of every column and the gradient of their SUM at the posterior's own parameters; y / mean are n×S
+function objective_grad(f::HipApproxColumnsPosteriorGP, fx::FiniteGP{<:HipGP}; wrt_x::Bool=false)
+    T = getfield(f, :T)
+    S = getfield(f, :ncols)
+    h = getfield(f, :handle)
+    a = marshal(fx, T)
+    zbuf, cz = points(f.approx.fz.x, T)
+    n = Int(ccall((:gp_vfe_n, libgpmi355), Int64, (Ptr{Cvoid},), h[]))
+    (!wrt_x || length(fx) == n) || throw(ArgumentError("wrt_x: fx must hold every observation of the posterior ($n)"))
+    dvar = Ref{Float64}(0.0); dns = Ref{Float64}(0.0)
+    dscale = zeros(Float64, max(length(a.scales), 1))
+    dnoise = Vector{T}(undef, n); dY = Matrix{T}(undef, n, S)
+    dz = T === Float64 ? similar(zbuf, Float64) : Float64[]
+    dx = wrt_x ? similar(a.xbuf) : T[]
+    GC.@preserve f dscale dnoise dY dz dx check(ccall((:gp_vfe_grad_cols, libgpmi355), Int32,
+        (Ptr{Cvoid}, Ref{Float64}, Ptr{Float64}, Ref{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Cvoid}, Int32),
+        h[], dvar, dscale, dns, dnoise, dY, T === Float64 ? pointer(dz) : Ptr{Float64}(C_NULL), cz.layout,
+        wrt_x ? pointer(dx) : C_NULL, a.cx.layout))
+    return (variance=dvar[], scale=dscale[1:length(a.scales)], noise=a.cn.kind == 0 ? dns[] : dnoise, y=dY, mean=-dY,
+        z=T === Float64 ? dz : nothing, x=wrt_x ? dx : nothing)
+end
+function elbo_and_grad_columns(approx::Union{VFE,DTC}, fx::FiniteGP{<:HipGP}, Y::AbstractMatrix{<:Real}; wrt_x::Bool=false)
+    post = posterior_columns(approx, fx, Y)
+    return post.objective, objective_grad(post, fx; wrt_x=wrt_x)
 end
 
 end # module

@@ -839,6 +839,48 @@ int32_t gp_vfe_get_by(gp_vfe* post, void* b_y_out);
  * gp_get_timings afterwards: assemble = the M×M side, potrf = the streamed pass, solve = the K_zz term. */
 int32_t gp_vfe_grad(gp_vfe* post, double* dvariance_or_null, double* dscale_or_null, double* dnoise_sum_or_null, void* dnoise_diag_or_null, void* dy_or_null,
                     double* dz_or_null, int32_t z_layout, void* dx_or_null, int32_t x_layout);
+
+/* ---- VFE / DTC for a matrix of observations ("columns") --------------------------------------------------------------------------- */
+/* S = ncols <= GPMI355_COLS_MAX sparse GPs that share x, z, kernel, jitter, Σy (scalar or diagonal) and the prior-mean vector and differ in y — the columns
+ * of Y (n×ncols column-major, leading dimension ldy) — fitted, updated, predicted and differentiated from ONE streamed pass over the data: K(x_c, z), the
+ * triangular product and the SYRK of a chunk do not depend on y, only the product c_s = B b_ys does.  Single-kind kernels; composite kernels and a dense
+ * Σy are refused as on the rest of the sparse path.  fp64 and fp32 handles.
+ * gp_vfe_fit_cols: gp_vfe_fit for every column.  objective_out_or_null: ncols entries (elbo for approx 0, approx_log_evidence for 1).  ncols outside
+ *   1..GPMI355_COLS_MAX is an argument error (argument 10), ldy < n argument 9.  A failed factorisation returns the LAPACK info and no handle.  Per chunk
+ *   ystats_cols_kernel (csrc/kernels.hpp) reads Y = −B_c once and forms ‖B‖² per row and B_c b_cs for every column on the fp64 16×16×4 MFMA (fp32
+ *   operands widened: the sums over the data points are fp64 for either dtype); a workgroup owns 32 rows for all data points and all columns, its four
+ *   waves split the data points by a rule that reads neither ncols nor the data, and their partial sums are added in wave order: no floating-point
+ *   atomics, bitwise repeatable, a column's bits independent of what the other columns hold.  After the pass the M×M side solves all columns at once
+ *   (the blocked solves of the predictions over the columns' rows).  The handle retains b_y of every column: round_up(ncols, 16) × npad values of the
+ *   handle's dtype on the device (npad = n rounded up to the chunk; N = 2·10⁶, ncols = 128, fp32: about 1 GB).
+ *   With ncols = 1 the call IS gp_vfe_fit (the same launches, the same bits), and so is every *_cols call below its single-column counterpart.
+ * gp_vfe_update_cols / gp_vfe_append_cols: gp_vfe_update / gp_vfe_append on such a handle; Y2 (n2×ncols column-major, leading dimension ldy2) must have
+ *   the handle's ncols; objective_out_or_null: ncols entries.
+ * gp_vfe_ncols: the columns of a handle — 1 for every handle made by the single-column calls.
+ * gp_vfe_predict_cols: `what` bits as gp_vfe_predict.  mean_out: ns×ncols column-major, column s = m(x*) + K(x*, z) α_s, from ONE kmul_kernel launch over
+ *   the pseudo-points (K_*z evaluated once for all columns; counted in "cols_kernel_calls"; D > 16: one kvec launch per column); var_out (ns) and cov_out
+ *   (ns×ns) do not depend on y and are what gp_vfe_predict returns.
+ * gp_vfe_get_cols: α and m_ε of every column, both M×ncols column-major.   gp_vfe_get_by_cols: b_y of every column, n×ncols column-major, n = gp_vfe_n.
+ * gp_vfe_grad_cols: the gradient of Σ_s objective_s at the handle's parameters; outputs as gp_vfe_grad with dy replaced by dY (n×ncols column-major,
+ *   column s = ∂/∂Y[:, s]).  The M×M algebra of gp_vfe_grad with the column sums folded in — G_ψ = ½[S·W H_ψ Wᵀ − A Aᵀ], G_zz likewise, A = the M×ncols
+ *   matrix of the α_s — and per chunk two skinny MFMA GEMMs beside T̃ = (S K_c) G_ψ: the rank-S term ½ b_c Aᵀ into the chunk's weights and the per-column
+ *   row sums (S K_c) A.  fp64 pass for fp32 handles; dz on an fp32 handle stays refused (−7).
+ * A handle with ncols > 1 serves unchanged everything that does not use α: gp_vfe_predict with what ⊆ {var, cov}, the variance side of gp_vfe_predict_grad,
+ *   gp_vfe_get_factors, gp_vfe_m, gp_vfe_n, gp_vfe_free.  The mean bit of gp_vfe_predict, the mean side of gp_vfe_predict_grad, gp_vfe_get, gp_vfe_get_by,
+ *   gp_vfe_logpdf, gp_vfe_rand, gp_vfe_update, gp_vfe_append and gp_vfe_grad return −1 (the handle argument) with the reason in gp_last_error() and write
+ *   nothing. */
+int32_t gp_vfe_fit_cols(gp_ctx* ctx, const gp_kernel* k, const gp_points* x, const gp_points* z, const gp_noise* noise, double jitter,
+                        const void* mean_or_null, const void* Y, int64_t ldy, int32_t ncols, int32_t approx, gp_vfe** out, void* objective_out_or_null);
+int32_t gp_vfe_update_cols(gp_vfe* old, const gp_points* x2, const gp_noise* noise2, const void* mean2_or_null, const void* Y2, int64_t ldy2, gp_vfe** out,
+                           void* objective_out_or_null);
+int32_t gp_vfe_append_cols(gp_vfe* old, const gp_points* z2, gp_vfe** out, void* objective_out_or_null);
+int32_t gp_vfe_ncols(gp_vfe* post, int32_t* out);
+int32_t gp_vfe_predict_cols(gp_vfe* post, const gp_points* xs, const void* prior_mean_xs_or_null, int32_t what, void* mean_out, void* var_out,
+                            void* cov_out);
+int32_t gp_vfe_get_cols(gp_vfe* post, void* alpha_out_or_null, void* m_eps_out_or_null);
+int32_t gp_vfe_get_by_cols(gp_vfe* post, void* B_out);
+int32_t gp_vfe_grad_cols(gp_vfe* post, double* dvariance_or_null, double* dscale_or_null, double* dnoise_sum_or_null, void* dnoise_diag_or_null,
+                         void* dY_or_null, double* dz_or_null, int32_t z_layout, void* dx_or_null, int32_t x_layout);
 int32_t gp_vfe_free(gp_vfe* post);
 
 /* ---- device-level building blocks ------------------------------------------------------------ */
