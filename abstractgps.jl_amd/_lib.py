@@ -162,6 +162,11 @@ PROTOTYPES = {
     "gpd_trsv_f32": (i32, [vp, vp, i64, i64, vp, i64, i32, i32]),
     "gpd_gemv_t_f32": (i32, [vp, vp, i64, i64, i64, vp, vp]),
     "gpd_rowsumsq_f32": (i32, [vp, vp, i64, i64, i64, vp]),
+    **{f"gpd_grad_contract{s}": (i32, [vp, PK, vp, i64, vp, vp, i64, i64, i32, vp, vp, vp]) for s in ("", "_f32")},
+    **{f"gpd_grad_contract_sum{s}": (i32, [vp, PS, vp, i64, vp, vp, i64, i64, i32, vp, vp, vp]) for s in ("", "_f32")},
+    **{f"gpd_vgrad{s}": (i32, [vp, vp, i64, i32, vp, i64, vp, i64, i32, PK, vp, vp, vp, i64, i64, vp, vp, i64, dbl, vp, vp, vp, i64]) for s in ("", "_f32")},
+    **{f"gpd_ystats{s}": (i32, [vp, vp, i64, i64, vp, i64, i64, vp, vp]) for s in ("", "_f32")},
+    **{f"gpd_ystats_cols{s}": (i32, [vp, vp, i64, i64, vp, i64, i32, i64, i64, vp, i64, vp]) for s in ("", "_f32")},
     "gpd_sync": (i32, [vp]),
     "gpd_gemm_time": (i32, [vp, C.POINTER(dbl), C.POINTER(i64)]),
     "gp_rccl_selftest": (i32, [i32, i64, C.POINTER(dbl)]),

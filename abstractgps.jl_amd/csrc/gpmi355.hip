@@ -2011,53 +2011,81 @@ static int32_t fold_loo(gp_ctx* c, hipStream_t s, DevBufs& bufs, const gp_post& 
     HIPCHK(hipGetLastError());
     return zeroed_alpha<T>(s, bufs, np, a0);
 }
-// (e) the contraction: ∂/∂variance and ∂/∂scale (∂/∂θ), ∂/∂Σy (a dense one straight to the caller's n×n array dnoise_dense), ∂/∂x when go has room for
-// it; then the downloads and the synchronise
-template <typename T, int ND>
-static void launch_kgrad_fast(dim3 grid, hipStream_t s, const gp_post& post, const T* Ci, const double* sc, const T* a, double* g) {
-    hipLaunchKernelGGL((kgrad_fast_kernel<T, ND>), grid, dim3(256), 0, s, Ci, post.ld, (const T*)post.xs, post.np, post.d, post.kern.kind, (T)post.kern.variance,
-                       post.kern.nscale(), sc, a, post.n, g);
+// What the contraction's kernels take: the weights Ci (−C⁻¹, row-major lower) and a, the pre-scaled dimension-major inputs xs ([d][np]), the kernel (a single
+// kind with its scales on the device, or a composite one: ks).  launch_kgrad / launch_kgradx pick the instances — grad_contract and the device-level entry
+// point gpd_grad_contract (include/gpmi355.h) both go through them.
+template <typename T> struct ContractArgs {
+    const T* Ci;
+    long ld;
+    const T* xs;
+    long n, np;
+    int d, kind;
+    double variance;
+    int nscale;
+    const double* sc;
+    const KSum* ks;
+    const T* a;
+    dim3 grid() const { return dim3((unsigned)(np / 128), (unsigned)(np / 128)); }
+};
+template <typename T> static ContractArgs<T> contract_args(const gp_post& post, const T* Ci, const T* a, const double* sc) {
+    return ContractArgs<T>{Ci, post.ld, (const T*)post.xs, post.n, post.np, post.d, post.kern.kind, post.kern.variance, post.kern.nscale(), sc, post.kern.desc().ks, a};
 }
+template <typename T, int ND>
+static void launch_kgrad_fast(hipStream_t s, const ContractArgs<T>& A, double* g) {
+    hipLaunchKernelGGL((kgrad_fast_kernel<T, ND>), A.grid(), dim3(256), 0, s, A.Ci, A.ld, A.xs, A.np, A.d, A.kind, (T)A.variance, A.nscale, A.sc, A.a, A.n, g);
+}
+// g[0] += ∂/∂variance, g[2 + p] += ∂/∂scale_p (∂/∂θ_p), then dn[i] = ∂/∂Σy_ii and g[1] += Σ_i dn[i]
 template <typename T>
-static int32_t grad_contract(gp_ctx* c, hipStream_t s, DevBufs& bufs, const gp_post& post, const T* Ci, const T* a, T* dnoise_dense, GradOut<T>& go) {
-    const long n = post.n, np = post.np, ld = post.ld;
-    const int d = post.d, nscale = post.kern.nscale();
-    const KSum* ks = post.kern.desc().ks;
-    const T* xs = (const T*)post.xs;
-    const T variance = (T)post.kern.variance;
-    double* g = (double*)go.g_v;
-    const dim3 grid((unsigned)(np / 128), (unsigned)(np / 128));
-    if (ks) {  // composite kernel: one launch per chunk of 16 θ entries
-        for (int p0 = 0; p0 < ks->nth; p0 += 16) {
-            launch_kgrad_sum<T>(grid, s, Ci, ld, xs, np, d, *ks, a, n, g, p0);
+static int32_t launch_kgrad(hipStream_t s, const ContractArgs<T>& A, double* g, T* dn) {
+    const long n = A.n, ld = A.ld;
+    const int d = A.d, nscale = A.nscale;
+    if (A.ks) {  // composite kernel: one launch per chunk of 16 θ entries
+        for (int p0 = 0; p0 < A.ks->nth; p0 += 16) {
+            launch_kgrad_sum<T>(A.grid(), s, A.Ci, ld, A.xs, A.np, d, *A.ks, A.a, n, g, p0);
             HIPCHK(hipGetLastError());
         }
     } else if (d <= 16 && (ld * (long)sizeof(T)) % 16 == 0) {  // the scratch-free form (16-byte loads of the weights): a single launch whatever the scales are
-        if (d <= 4) launch_kgrad_fast<T, 4>(grid, s, post, Ci, go.sc.ptr(), a, g);
-        else if (d <= 8) launch_kgrad_fast<T, 8>(grid, s, post, Ci, go.sc.ptr(), a, g);
-        else launch_kgrad_fast<T, 16>(grid, s, post, Ci, go.sc.ptr(), a, g);
+        if (d <= 4) launch_kgrad_fast<T, 4>(s, A, g);
+        else if (d <= 8) launch_kgrad_fast<T, 8>(s, A, g);
+        else launch_kgrad_fast<T, 16>(s, A, g);
         HIPCHK(hipGetLastError());
     } else {  // one launch per chunk of 16 ARD scales
         for (int p0 = 0; p0 < std::max(nscale, 1); p0 += 16) {
-            hipLaunchKernelGGL(kgrad_kernel<T>, grid, dim3(256), 0, s, Ci, ld, xs, np, d, post.kern.kind, variance, nscale, go.sc.ptr(), a, n, g, p0);
+            hipLaunchKernelGGL(kgrad_kernel<T>, A.grid(), dim3(256), 0, s, A.Ci, ld, A.xs, A.np, d, A.kind, (T)A.variance, nscale, A.sc, A.a, n, g, p0);
             HIPCHK(hipGetLastError());
         }
     }
-    hipLaunchKernelGGL(noise_grad_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, Ci, ld, a, n, (T*)go.dn_v, g + 1);
+    hipLaunchKernelGGL(noise_grad_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, A.Ci, ld, A.a, n, dn, g + 1);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+// gx[p][i] += ∂/∂x_ip: full-square pass (the mirrored Ci entry serves the tiles above the diagonal), 16 dimensions per launch
+template <typename T>
+static int32_t launch_kgradx(hipStream_t s, const ContractArgs<T>& A, double* gx, long ldg) {
+    if (A.ks) {  // composite kernel: xs holds the raw inputs, D <= 16 (pack_ksum), one launch
+        launch_kgradx_sum<T>(A.grid(), s, A.Ci, A.ld, A.xs, A.np, A.d, *A.ks, A.a, A.n, gx, ldg);
+        HIPCHK(hipGetLastError());
+    } else {
+        for (int p0 = 0; p0 < A.d; p0 += 16) {
+            hipLaunchKernelGGL(kgradx_kernel<T>, A.grid(), dim3(256), 0, s, A.Ci, A.ld, A.xs, A.np, A.d, A.kind, (T)A.variance, A.nscale, A.sc, A.a, A.n, gx, ldg, p0);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    return 0;
+}
+// (e) the contraction: ∂/∂variance and ∂/∂scale (∂/∂θ), ∂/∂Σy (a dense one straight to the caller's n×n array dnoise_dense), ∂/∂x when go has room for
+// it; then the downloads and the synchronise
+template <typename T>
+static int32_t grad_contract(gp_ctx* c, hipStream_t s, DevBufs& bufs, const gp_post& post, const T* Ci, const T* a, T* dnoise_dense, GradOut<T>& go) {
+    const long n = post.n, np = post.np, ld = post.ld;
+    const ContractArgs<T> A = contract_args<T>(post, Ci, a, go.sc.ptr());
+    double* g = (double*)go.g_v;
+    RC(launch_kgrad<T>(s, A, g, (T*)go.dn_v));
     if (dnoise_dense) RC(dense_grad_out<T>(c, s, bufs, Ci, ld, a, n, dnoise_dense));  // G = ½(a aᵀ + Ci), n×n
-    if (go.gx_v) {  // ∂/∂x: full-square pass (the mirrored Ci entry serves the tiles above the diagonal), 16 dimensions per launch
+    if (go.gx_v) {
         double* gx = (double*)go.gx_v;
         HIPCHK(hipMemsetAsync(gx, 0, sizeof(double) * go.gx_h.size(), s));
-        if (ks) {  // composite kernel: post.xs holds the raw inputs, D <= 16 (pack_ksum), one launch
-            launch_kgradx_sum<T>(grid, s, Ci, ld, xs, np, d, *ks, a, n, gx, np);
-            HIPCHK(hipGetLastError());
-        } else {
-            for (int p0 = 0; p0 < d; p0 += 16) {
-                hipLaunchKernelGGL(kgradx_kernel<T>, grid, dim3(256), 0, s, Ci, ld, xs, np, d, post.kern.kind, variance, nscale, go.sc.ptr(), a, n, gx, np, p0);
-                HIPCHK(hipGetLastError());
-            }
-        }
+        RC(launch_kgradx<T>(s, A, gx, np));
         HIPCHK(hipMemcpyAsync(go.gx_h.data(), gx, sizeof(double) * go.gx_h.size(), hipMemcpyDeviceToHost, s));
     }
     HIPCHK(hipMemcpyAsync(go.g_h.data(), g, sizeof(double) * go.g_h.size(), hipMemcpyDeviceToHost, s));
@@ -3934,6 +3962,121 @@ static int32_t dev_rowsumsq(gp_ctx* c, const T* x, int64_t ldx, int64_t nrows, i
     HIPCHK(hipGetLastError());
     return 0;
 }
+
+// ---- the gradient contractions and the sparse path's N-long reductions on caller-supplied weights (include/gpmi355.h states each contract).  They launch through
+// the functions production launches through — launch_kgrad / launch_kgradx (grad_contract), launch_vgrad (vfe_grad_impl), launch_ystats / launch_ystats_cols
+// (vfe_fit_impl) — so the instance a shape gets here is the one it gets there.
+template <typename T> static inline bool aligned16(const T* p) { return ((uintptr_t)p & 15) == 0; }
+// The staged scales (a host vector and a cache block, both local to the call) must outlive their upload and every launch that reads them: the stream is drained on
+// EVERY way out of the call, an early error return included (declared after them, so it runs first)
+struct DrainOnExit {
+    hipStream_t s;
+    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
+};
+
+// k (a single kind) or ksum (a composite kernel): exactly one is non-NULL.  The kind's scales are staged from k->scale; the stream is drained before the staging
+// block goes back to the cache.
+template <typename T>
+static int32_t dev_grad_contract(gp_ctx* c, const gp_kernel* k, const gp_ksum* ksum, const T* ci, int64_t ld, const T* alpha, const T* x, int64_t n, int64_t np,
+                                 int32_t d, double* g, T* dn, double* gx) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    if (d < 1) return set_arg_err(9, "d must be >= 1");
+    KSum ks;
+    gp_kernel kid{};
+    if (ksum) RC(pack_ksum(ksum, d, 2, ks, kid));
+    else RC(check_kernel(k, d, 2));
+    const gp_kernel& kk = ksum ? kid : *k;
+    if (kk.dtype != (sizeof(T) == 4 ? 1 : 0)) return set_arg_err(2, "kernel dtype does not match the entry point's element type");
+    if (!ci || !aligned16(ci)) return set_arg_err(3, "ci must be non-NULL and 16-byte aligned");
+    if (np < 128 || np % 128) return set_arg_err(8, "np must be a positive multiple of 128");
+    if (n < 1 || n > np) return set_arg_err(7, "n must be in 1..np");
+    if (ld < np) return set_arg_err(4, "ld must be >= np");
+    if (!alpha) return set_arg_err(5, "alpha is NULL");
+    if (!x) return set_arg_err(6, "x is NULL");
+    if (!g) return set_arg_err(10, "g is NULL");
+    if (!dn) return set_arg_err(11, "dn is NULL");
+    HIPCHK(hipSetDevice(c->device));
+    DevBufs bufs(c);
+    DevScales sc;
+    DrainOnExit drain{c->sm};
+    RC(sc.stage(bufs, kk.nscale, kk.scale, c->sm));
+    const ContractArgs<T> A{ci, ld, x, n, np, d, kk.kind, kk.variance, kk.nscale, sc.ptr(), ksum ? &ks : nullptr, alpha};
+    RC(launch_kgrad<T>(c->sm, A, g, dn));
+    if (gx) RC(launch_kgradx<T>(c->sm, A, gx, np));
+    HIPCHK(hipStreamSynchronize(c->sm));  // the scales' block goes back to the cache when this returns
+    return 0;
+}
+
+template <typename T>
+static int32_t dev_vgrad(gp_ctx* c, const T* cm, int64_t ldc, int32_t explicit_w, const T* xr, int64_t ldxr, const T* xc, int64_t ldxc, int32_t d, const gp_kernel* k,
+                         const T* rs, const T* bv, const double* nu, int64_t nr, int64_t nc, double* g, double* gz, int64_t ldgz, double zfac, double* rowq,
+                         double* rowp, double* gx, int64_t ldgx) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    if (d < 1) return set_arg_err(9, "d must be >= 1");
+    RC(check_kernel(k, d, 10));
+    if (k->dtype != (sizeof(T) == 4 ? 1 : 0)) return set_arg_err(10, "kernel dtype does not match the entry point's element type");
+    if (nr < 1 || nc < 1) return set_arg_err(14, "nr, nc must be >= 1");
+    const long ncp = round_up(nc, 128), nrp = round_up(nr, 128);
+    if (!cm || ((uintptr_t)cm & (2 * sizeof(T) - 1)) != 0) return set_arg_err(2, "cm must be non-NULL and aligned to two elements");
+    if (ldc < ncp) return set_arg_err(3, "ldc must be >= nc rounded up to 128");
+    if (explicit_w != 0 && explicit_w != 1) return set_arg_err(4, "explicit_w must be 0 or 1");
+    if (!xr || ldxr < nrp) return set_arg_err(6, "xr is NULL or ldxr < nr rounded up to 128");
+    if (!xc || ldxc < ncp) return set_arg_err(8, "xc is NULL or ldxc < nc rounded up to 128");
+    if (!explicit_w && (!rs || !bv || !nu)) return set_arg_err(11, "rs, bv and nu are needed with explicit_w = 0");
+    if (!g) return set_arg_err(16, "g is NULL");
+    if (!gz || ldgz < nc) return set_arg_err(17, "gz is NULL or ldgz < nc");
+    if ((rowq == nullptr) != (rowp == nullptr)) return set_arg_err(20, "rowq and rowp come together");
+    if (gx && ldgx < nr) return set_arg_err(23, "ldgx < nr");
+    HIPCHK(hipSetDevice(c->device));
+    DevBufs bufs(c);
+    DevScales sc;
+    DrainOnExit drain{c->sm};
+    RC(sc.stage(bufs, k->nscale, k->scale, c->sm));
+    const dim3 grid((unsigned)(ncp / 128), (unsigned)(nrp / 128));
+    if (gx)
+        RC((launch_vgrad<T, true>(c->sm, grid, cm, ldc, explicit_w, xr, ldxr, xc, ldxc, d, k->kind, k->variance, k->nscale, sc.ptr(), rs, bv, nu, nr, nc, g, gz, ldgz,
+                                  zfac, rowq, rowp, gx, ldgx)));
+    else
+        RC((launch_vgrad<T, false>(c->sm, grid, cm, ldc, explicit_w, xr, ldxr, xc, ldxc, d, k->kind, k->variance, k->nscale, sc.ptr(), rs, bv, nu, nr, nc, g, gz, ldgz,
+                                   zfac, rowq, rowp, (double*)nullptr, 0L)));
+    HIPCHK(hipStreamSynchronize(c->sm));  // the scales' block goes back to the cache when this returns
+    return 0;
+}
+
+template <typename T>
+static int32_t dev_ystats(gp_ctx* c, const T* y, int64_t ldy, int64_t ncols, const T* b, int64_t row_lo, int64_t nrows, double* cacc, double* rowss) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    constexpr int E = 16 / (int)sizeof(T);
+    if (!y || !aligned16(y) || ldy % E != 0 || ldy < ncols) return set_arg_err(2, "y must be 16-byte aligned, ldy >= ncols with 16-byte rows");
+    if (ncols < 1) return set_arg_err(4, "ncols must be >= 1");
+    if (!b || !aligned16(b)) return set_arg_err(5, "b must be non-NULL and 16-byte aligned");
+    if (row_lo < 0 || nrows < 0) return set_arg_err(6, "row_lo, nrows must be >= 0");
+    if (!cacc || !rowss) return set_arg_err(8, "cacc / rowss is NULL");
+    if (nrows == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    return launch_ystats<T>(c->sm, y, ldy, ncols, b, row_lo, nrows, cacc, rowss);
+}
+
+template <typename T>
+static int32_t dev_ystats_cols(gp_ctx* c, const T* y, int64_t ldy, int64_t ncols, const T* by, int64_t ldb, int32_t sb, int64_t row_lo, int64_t nrows, double* cacc,
+                               int64_t ldc, double* rowss) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    constexpr int E = 16 / (int)sizeof(T);  // = Tr<T>::VEC: elements per 16-byte load
+    if (!y || !aligned16(y) || ldy % E != 0 || ldy < ncols) return set_arg_err(2, "y must be 16-byte aligned, ldy >= ncols with 16-byte rows");
+    if (ncols < 16 * E || ncols % (16 * E)) return set_arg_err(4, "ncols must be a positive multiple of 16 x (16 bytes / element size)");
+    if (!by || !aligned16(by) || ldb % E != 0 || ldb < ncols) return set_arg_err(5, "by must be 16-byte aligned, ldb >= ncols with 16-byte rows");
+    if (sb < 1 || sb > 8) return set_arg_err(7, "sb must be 1..8");
+    if (row_lo < 0 || nrows < 0 || nrows % 16) return set_arg_err(9, "row_lo >= 0 and nrows a multiple of 16 required");
+    if (!cacc || ldc < row_lo + nrows) return set_arg_err(10, "cacc is NULL or ldc < row_lo + nrows");
+    if (!rowss) return set_arg_err(12, "rowss is NULL");
+    if (nrows == 0) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    return launch_ystats_cols<T>(c->sm, y, ldy, ncols, by, ldb, sb, row_lo, nrows, cacc, ldc, rowss);
+}
 }  // extern "C++"
 
 int32_t gpd_assemble(gp_ctx* c, const gp_kernel* k, const double* x_dev, int64_t n_valid, int64_t n_pad, int32_t d,
@@ -4007,6 +4150,49 @@ int32_t gpd_rowsumsq(gp_ctx* c, const double* x, int64_t ldx, int64_t nrows, int
 }
 int32_t gpd_rowsumsq_f32(gp_ctx* c, const float* x, int64_t ldx, int64_t nrows, int64_t ncols, double* out_dev) {
     return dev_rowsumsq<float>(c, x, ldx, nrows, ncols, out_dev);
+}
+
+int32_t gpd_grad_contract(gp_ctx* c, const gp_kernel* k, const double* ci, int64_t ld, const double* alpha, const double* x, int64_t n, int64_t np, int32_t d,
+                          double* g, double* dn, double* gx) {
+    return dev_grad_contract<double>(c, k, nullptr, ci, ld, alpha, x, n, np, d, g, dn, gx);
+}
+int32_t gpd_grad_contract_f32(gp_ctx* c, const gp_kernel* k, const float* ci, int64_t ld, const float* alpha, const float* x, int64_t n, int64_t np, int32_t d,
+                              double* g, float* dn, double* gx) {
+    return dev_grad_contract<float>(c, k, nullptr, ci, ld, alpha, x, n, np, d, g, dn, gx);
+}
+int32_t gpd_grad_contract_sum(gp_ctx* c, const gp_ksum* k, const double* ci, int64_t ld, const double* alpha, const double* x, int64_t n, int64_t np, int32_t d,
+                              double* g, double* dn, double* gx) {
+    return dev_grad_contract<double>(c, nullptr, k, ci, ld, alpha, x, n, np, d, g, dn, gx);
+}
+int32_t gpd_grad_contract_sum_f32(gp_ctx* c, const gp_ksum* k, const float* ci, int64_t ld, const float* alpha, const float* x, int64_t n, int64_t np, int32_t d,
+                                  double* g, float* dn, double* gx) {
+    return dev_grad_contract<float>(c, nullptr, k, ci, ld, alpha, x, n, np, d, g, dn, gx);
+}
+
+int32_t gpd_vgrad(gp_ctx* c, const double* cm, int64_t ldc, int32_t explicit_w, const double* xr, int64_t ldxr, const double* xc, int64_t ldxc, int32_t d,
+                  const gp_kernel* k, const double* rs, const double* bv, const double* nu, int64_t nr, int64_t nc, double* g, double* gz, int64_t ldgz, double zfac,
+                  double* rowq, double* rowp, double* gx, int64_t ldgx) {
+    return dev_vgrad<double>(c, cm, ldc, explicit_w, xr, ldxr, xc, ldxc, d, k, rs, bv, nu, nr, nc, g, gz, ldgz, zfac, rowq, rowp, gx, ldgx);
+}
+int32_t gpd_vgrad_f32(gp_ctx* c, const float* cm, int64_t ldc, int32_t explicit_w, const float* xr, int64_t ldxr, const float* xc, int64_t ldxc, int32_t d,
+                      const gp_kernel* k, const float* rs, const float* bv, const double* nu, int64_t nr, int64_t nc, double* g, double* gz, int64_t ldgz, double zfac,
+                      double* rowq, double* rowp, double* gx, int64_t ldgx) {
+    return dev_vgrad<float>(c, cm, ldc, explicit_w, xr, ldxr, xc, ldxc, d, k, rs, bv, nu, nr, nc, g, gz, ldgz, zfac, rowq, rowp, gx, ldgx);
+}
+
+int32_t gpd_ystats(gp_ctx* c, const double* y, int64_t ldy, int64_t ncols, const double* b, int64_t row_lo, int64_t nrows, double* cacc, double* rowss) {
+    return dev_ystats<double>(c, y, ldy, ncols, b, row_lo, nrows, cacc, rowss);
+}
+int32_t gpd_ystats_f32(gp_ctx* c, const float* y, int64_t ldy, int64_t ncols, const float* b, int64_t row_lo, int64_t nrows, double* cacc, double* rowss) {
+    return dev_ystats<float>(c, y, ldy, ncols, b, row_lo, nrows, cacc, rowss);
+}
+int32_t gpd_ystats_cols(gp_ctx* c, const double* y, int64_t ldy, int64_t ncols, const double* by, int64_t ldb, int32_t sb, int64_t row_lo, int64_t nrows, double* cacc,
+                        int64_t ldc, double* rowss) {
+    return dev_ystats_cols<double>(c, y, ldy, ncols, by, ldb, sb, row_lo, nrows, cacc, ldc, rowss);
+}
+int32_t gpd_ystats_cols_f32(gp_ctx* c, const float* y, int64_t ldy, int64_t ncols, const float* by, int64_t ldb, int32_t sb, int64_t row_lo, int64_t nrows,
+                            double* cacc, int64_t ldc, double* rowss) {
+    return dev_ystats_cols<float>(c, y, ldy, ncols, by, ldb, sb, row_lo, nrows, cacc, ldc, rowss);
 }
 
 int32_t gpd_gemm_time(gp_ctx* c, double* ms_out, int64_t* launches_out) {

@@ -97,6 +97,30 @@ enum { VFE_FIT = 0, VFE_UPDATE = 1, VFE_APPEND = 2 };
 // ncols columns of observations (gp_vfe_fit_cols; an update / append keeps prev's): yv is n×ncols column-major with leading dimension yld, objective has
 // ncols entries.  Everything but the observations is shared: ONE streamed pass, ystats_cols_kernel in place of ystats_kernel, the M×M vector solves as
 // blocked solves over the columns' rows.  ncols = 1 issues exactly the single-column launches.
+// The two N-long reductions of the streamed pass over rows [row_lo, row_lo + nrows) of Y = −B_c (kernels.hpp ystats_kernel / ystats_cols_kernel): the fit below and
+// the device-level entry points gpd_ystats / gpd_ystats_cols (include/gpmi355.h) launch them through these.
+//   one column : cacc[row] −= Σ_c Y[row][c] b[c],  rowss[row] += Σ_c Y[row][c]²                 one workgroup per row
+//   S columns  : Cacc[s][row] −= Σ_c Y[row][c] By[s][c] for s < 16·SB,  rowss as above           32 rows per workgroup (RT = 2); 16 (RT = 1) where nrows is no
+//                multiple of 32 — the fit's nrows always is one (mp and row_lo are multiples of 128) — or with the experiment switch GPMI_YSTATS_COLS_ROWS=16
+//                (twice the workgroups, twice the re-reads of the b chunk — timed at C5)
+template <typename T>
+static int32_t launch_ystats(hipStream_t s, const T* Y, long ldy, long ncols, const T* b, long row_lo, long nrows, double* cacc, double* rowss) {
+    hipLaunchKernelGGL(ystats_kernel<T>, dim3((unsigned)nrows), dim3(256), 0, s, Y, ldy, ncols, b, row_lo, cacc, rowss);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+template <typename T>
+static int32_t launch_ystats_cols(hipStream_t s, const T* Y, long ldy, long ncols, const T* By, long ldb, int SB, long row_lo, long nrows, double* Cacc, long ldc,
+                                  double* rowss) {
+    static const bool rows16 = [] { const char* e = getenv("GPMI_YSTATS_COLS_ROWS"); return e && !strcmp(e, "16"); }();
+    if (rows16 || nrows % 32)
+        hipLaunchKernelGGL((ystats_cols_kernel<T, 1>), dim3((unsigned)(nrows / 16)), dim3(256), 0, s, Y, ldy, ncols, By, ldb, SB, row_lo, Cacc, ldc, rowss);
+    else
+        hipLaunchKernelGGL((ystats_cols_kernel<T, 2>), dim3((unsigned)(nrows / 32)), dim3(256), 0, s, Y, ldy, ncols, By, ldb, SB, row_lo, Cacc, ldc, rowss);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 template <typename T>
 static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_points* z, const gp_noise* noise,
                             double jitter, const void* mean_or_null, const void* yv, int approx, gp_vfe* out,
@@ -386,19 +410,10 @@ static int32_t vfe_fit_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, c
                 HIPCHK(hipStreamWaitEvent(sa, e, 0));
                 if (dual) HIPCHK(hipStreamWaitEvent(s, e, 0));
             }
-            if (cols) {  // every column's c_s += B_c b_cs and the ‖B‖² rows in one pass over Y: 32 rows per workgroup (mp and row_lo are multiples of 128)
-                // experiment switch GPMI_YSTATS_COLS_ROWS=16: 16 rows per workgroup (twice the workgroups, twice the re-reads of the b chunk) — timed at C5, DESIGN.md
-                static const bool rows16 = [] { const char* e = getenv("GPMI_YSTATS_COLS_ROWS"); return e && !strcmp(e, "16"); }();
-                if (rows16)
-                    hipLaunchKernelGGL((ystats_cols_kernel<T, 1>), dim3((unsigned)((mp - row_lo) / 16)), dim3(256), 0, sa, (const T*)Yb[bb], ldy, CH,
-                                       (const T*)sg.b + c0, sg.npad, VR / 16, row_lo, (double*)cT_v, mp, (double*)rss_v);
-                else
-                    hipLaunchKernelGGL((ystats_cols_kernel<T, 2>), dim3((unsigned)((mp - row_lo) / 32)), dim3(256), 0, sa, (const T*)Yb[bb], ldy, CH,
-                                       (const T*)sg.b + c0, sg.npad, VR / 16, row_lo, (double*)cT_v, mp, (double*)rss_v);
-            } else
-                hipLaunchKernelGGL(ystats_kernel<T>, dim3((unsigned)(mp - row_lo)), dim3(256), 0, sa, (const T*)Yb[bb], ldy, CH,
-                                   (const T*)sg.b + c0, row_lo, (double*)cT_v, (double*)rss_v);   // c += B_c b_c ; ‖B‖² rows (fp64)
-            HIPCHK(hipGetLastError());
+            if (cols)  // every column's c_s += B_c b_cs and the ‖B‖² rows in one pass over Y (launch_ystats_cols above)
+                RC(launch_ystats_cols<T>(sa, (const T*)Yb[bb], ldy, CH, (const T*)sg.b + c0, sg.npad, VR / 16, row_lo, mp - row_lo, (double*)cT_v, mp, (double*)rss_v));
+            else
+                RC(launch_ystats<T>(sa, (const T*)Yb[bb], ldy, CH, (const T*)sg.b + c0, row_lo, mp - row_lo, (double*)cT_v, (double*)rss_v));   // c += B_c b_c ; ‖B‖² rows (fp64)
             if (ovl) {
                 RC(ctx_event(c, &evYs[bb], false));
                 HIPCHK(hipEventRecord(evYs[bb], sa));

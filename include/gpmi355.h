@@ -962,6 +962,79 @@ int32_t gpd_trsv_f32(gp_ctx* ctx, const float* l, int64_t ldl, int64_t np, float
 int32_t gpd_gemv_t_f32(gp_ctx* ctx, const float* l, int64_t ldl, int64_t nrows, int64_t ncols, const float* a,
                        float* r);
 int32_t gpd_rowsumsq_f32(gp_ctx* ctx, const float* x, int64_t ldx, int64_t nrows, int64_t ncols, double* out_dev);
+
+/* ---- the gradient contractions and the sparse path's N-long reductions, on caller-supplied weights (tests/test_gpu_units_grad.py, test_gpu_units_sparse.py) ----
+ * The kernels that turn a factorisation into gradients, reachable without a factorisation: the weights are the caller's, so an error of the contraction is not hidden
+ * behind the conditioning of C.  Each entry launches through the function production launches through (csrc/gpmi355.hip launch_kgrad / launch_kgradx, csrc/vfe.hpp
+ * launch_vgrad / launch_ystats / launch_ystats_cols): a shape gets the kernel instance here that it gets in gp_logpdf_grad / gp_vfe_grad / gp_vfe_fit.  T = double, or
+ * float in the _f32 twins; every sum is fp64 whatever T is.  gpd_grad_contract* and gpd_vgrad* stage the kernel's scales and DRAIN the ctx stream before they
+ * return; gpd_ystats* only queue (gpd_sync).  "Read, never used" below means: the location must be addressable, its value — a NaN included — cannot reach an output.
+ *
+ * gpd_grad_contract: the contraction of gp_logpdf_grad,  Σ_{j<=i<n} w_ij ∂C_ij/∂θ  with  w_ij = (alpha_i alpha_j + ci_ij) · (i == j ? ½ : 1)   (ci = −C⁻¹).
+ *   ci    n rows of a row-major LOWER matrix, leading dimension ld >= np, 16-byte aligned.  Used: ci[i][j], j <= i < n.  Read, never used: ci[i][j] for i < n,
+ *         i < j < np (the D <= 16 form loads the 2-wide pair (2l, 2l+1) of every 128-tile on or below the diagonal and discards what lies above the diagonal or
+ *         beyond n).  Rows >= n are not read.  D <= 16 and ld·sizeof(T) a multiple of 16: kgrad_fast_kernel<T, 4|8|16>; otherwise kgrad_kernel<T>, once per 16 ARD
+ *         scales (the only form for D > 16; for D <= 16 the form production never takes, its ld being padded to 16 bytes).  Both must give the same sums.
+ *   alpha n entries; entries >= n are not read.
+ *   x     the inputs ALREADY multiplied by the scales (u = s∘x), dimension-major [d][np] with leading dimension np, np a multiple of 128.  Columns [n, np) are read,
+ *         never used.
+ *   k     kind 0..3, variance, nscale ∈ {0, 1, d} with `scale` on the HOST (it divides the scale sums and multiplies gx; x is not scaled again); dtype must be T's.
+ *   g     doubles, 2 + max(nscale, 1):  g[0] += Σ w κ (∂/∂variance),  g[1] += Σ_i dn[i],  g[2 + p] += Σ w σ² dκ/dr² ∂r²/∂s_p  (∂r²/∂s = 2r²/s for one scale,
+ *         2(u_ip − u_jp)²/s_p for ARD).  With nscale = 0, g[2] is not touched.  Atomic "+=": zero it for the value alone.
+ *   dn    T, n entries: dn[i] = ½ (alpha_i² + ci_ii), OVERWRITTEN; entries >= n untouched.
+ *   gx    NULL, or doubles [d][np]:  gx[p][i] += 2 s_p σ² Σ_{j≠i, j<n} (alpha_i alpha_j + ci_max(i,j),min(i,j)) dκ/dr² (u_ip − u_jp)  for i < n (kgradx_kernel, once per
+ *         16 dimensions); columns >= n untouched.  Atomic "+=".
+ *   Matern12 at r = 0 takes dκ/dr² = 0: a coincident pair adds exactly 0 to the scale sums and to gx.
+ * gpd_grad_contract_sum: the same for a composite kernel (kgrad_sum_kernel once per 16 θ entries, kgradx_sum_kernel): x holds the RAW inputs, D <= 16,
+ *   g[2 + p] += ∂/∂θ_p in the order of gp_logpdf_grad_sum's dtheta (2 + nθ doubles; g[0] is not touched), gx[p][j] += ∂/∂x_jp.
+ * Refused: kernel (−2), ci NULL / misaligned (−3), ld < np (−4), alpha / x NULL (−5 / −6), n outside 1..np (−7), np no multiple of 128 (−8), d < 1 (−9), g / dn NULL
+ * (−10 / −11). */
+int32_t gpd_grad_contract(gp_ctx* ctx, const gp_kernel* k, const double* ci, int64_t ld, const double* alpha, const double* x, int64_t n, int64_t np, int32_t d,
+                          double* g, double* dn, double* gx_or_null);
+int32_t gpd_grad_contract_f32(gp_ctx* ctx, const gp_kernel* k, const float* ci, int64_t ld, const float* alpha, const float* x, int64_t n, int64_t np, int32_t d,
+                              double* g, float* dn, double* gx_or_null);
+int32_t gpd_grad_contract_sum(gp_ctx* ctx, const gp_ksum* k, const double* ci, int64_t ld, const double* alpha, const double* x, int64_t n, int64_t np, int32_t d,
+                              double* g, double* dn, double* gx_or_null);
+int32_t gpd_grad_contract_sum_f32(gp_ctx* ctx, const gp_ksum* k, const float* ci, int64_t ld, const float* alpha, const float* x, int64_t n, int64_t np, int32_t d,
+                                  double* g, float* dn, double* gx_or_null);
+/* gpd_vgrad: the reverse pass of the sparse objective over one rectangular kernel block K(rows, cols), nr × nc (gp_vfe_grad runs it in fp64 only; the _f32 twin
+ * instantiates the same templates for float).  With W_ij = ∂L/∂K_ij, κ and dκ/dr² recomputed from the inputs:
+ *     g[0] += Σ W κ,   g[2 + p] += Σ W σ² dκ/dr² ∂r²/∂s_p  (as above; g: 2 + max(nscale, 1) doubles; g[1], and with nscale = 0 g[2], not touched),
+ *     gz[p][j] += zfac · Σ_i W_ij σ² dκ/dr² (−2 s_p)(u_ip − w_jp)   for j < nc       (doubles [d][ldgz], ldgz >= nc; required)
+ *     gx[p][i] +=        Σ_j W_ij σ² dκ/dr² (+2 s_p)(u_ip − w_jp)   for i < nr       (NULL, or doubles [d][ldgx], ldgx >= nr)
+ *   explicit_w = 1: W = cm.  rs, bv, nu, rowq, rowp are not read.
+ *   explicit_w = 0: cm = −T̃ and W_ij = rs_i (2 T̃_ij + bv_i nu_j), formed in fp64;  rowq[i] += Σ_j σ² κ_ij T̃_ij,  rowp[i] += Σ_j σ² κ_ij nu_j  for i < nr when rowq is
+ *                   non-NULL (rowq and rowp come together).  rs, bv: T, nr entries; nu: doubles, nc entries.
+ *   cm    nr rows, leading dimension ldc >= nc rounded up to 128, aligned to two elements.  Used: cm[i][j], i < nr, j < nc.  Read, never used: columns [nc, round_up(nc, 128))
+ *         of those rows (the 2-wide loads of the D <= 16 form).  D <= 16 and ldc even: vgrad_fast_kernel<T, 4|8|16, XG>; otherwise vgrad_kernel<T, 16, true, XG> once per
+ *         16 dimensions (for D <= 16: the form production never takes).  XG = (gx != NULL).
+ *   xr, xc  pre-scaled inputs, dimension-major [d][ldxr] / [d][ldxc], ldxr >= nr and ldxc >= nc rounded up to 128.  Columns beyond nr / nc up to that multiple: read by
+ *           vgrad_kernel (D > 16, and D <= 16 with an odd ldc), never used.
+ *   Everything is an atomic "+=" (rows / columns beyond nr / nc untouched).
+ * Refused: cm (−2), ldc (−3), explicit_w (−4), xr / ldxr (−6), xc / ldxc (−8), d (−9), kernel (−10), rs / bv / nu missing (−11), nr / nc < 1 (−14), g NULL (−16),
+ * gz / ldgz (−17), one of rowq / rowp (−20), ldgx (−23). */
+int32_t gpd_vgrad(gp_ctx* ctx, const double* cm, int64_t ldc, int32_t explicit_w, const double* xr, int64_t ldxr, const double* xc, int64_t ldxc, int32_t d,
+                  const gp_kernel* k, const double* rs, const double* bv, const double* nu, int64_t nr, int64_t nc, double* g, double* gz, int64_t ldgz, double zfac,
+                  double* rowq_or_null, double* rowp_or_null, double* gx_or_null, int64_t ldgx);
+int32_t gpd_vgrad_f32(gp_ctx* ctx, const float* cm, int64_t ldc, int32_t explicit_w, const float* xr, int64_t ldxr, const float* xc, int64_t ldxc, int32_t d,
+                      const gp_kernel* k, const float* rs, const float* bv, const double* nu, int64_t nr, int64_t nc, double* g, double* gz, int64_t ldgz, double zfac,
+                      double* rowq_or_null, double* rowp_or_null, double* gx_or_null, int64_t ldgx);
+/* gpd_ystats: for every row r in [row_lo, row_lo + nrows) of y (row-major, ldy):   rowss[r] += Σ_{c<ncols} y[r][c]²,   cacc[r] −= Σ_{c<ncols} y[r][c] · b[c]
+ *   (ystats_kernel, one workgroup per row; fp64 fused multiply-adds, a fixed order: bitwise repeatable).  Plain read-modify-write: other rows of cacc / rowss are not
+ *   touched, columns >= ncols of y and b are not read.  y, b 16-byte aligned and every row of y 16-byte aligned (ldy a multiple of 2 doubles / 4 floats): the body
+ *   moves 4 columns per thread as 16-byte loads, the last ncols % 4 columns one by one.
+ * gpd_ystats_cols: the same for 16·sb columns of observations at once (ystats_cols_kernel<T, RT> on the fp64 MFMA):
+ *     rowss[r] += Σ_c y[r][c]²,   cacc[s][r] −= Σ_c y[r][c] · by[s][c]   for s < 16·sb      (cacc: doubles [16·sb][ldc], ldc >= row_lo + nrows; by: T [16·sb][ldb])
+ *   by rows of unused columns must be ZERO (they are multiplied like the others; their cacc rows then keep their values).  ncols a multiple of 16·(16 / sizeof(T)):
+ *   32 doubles / 64 floats.  nrows a multiple of 16: 32 rows per workgroup (RT = 2, what the fit launches) when nrows is a multiple of 32, else 16 (RT = 1).  sb in 1..8.
+ *   y and by 16-byte aligned with 16-byte rows.  No atomics: bitwise repeatable, and a column's bits do not depend on what the other columns of by hold.
+ * Refused: y / ldy (−2), ncols (−4), b / by / ldb (−5), row_lo / nrows (−6; cols: −9), sb (−7), cacc / ldc (−8; cols: −10), rowss (−8; cols: −12). */
+int32_t gpd_ystats(gp_ctx* ctx, const double* y, int64_t ldy, int64_t ncols, const double* b, int64_t row_lo, int64_t nrows, double* cacc, double* rowss);
+int32_t gpd_ystats_f32(gp_ctx* ctx, const float* y, int64_t ldy, int64_t ncols, const float* b, int64_t row_lo, int64_t nrows, double* cacc, double* rowss);
+int32_t gpd_ystats_cols(gp_ctx* ctx, const double* y, int64_t ldy, int64_t ncols, const double* by, int64_t ldb, int32_t sb, int64_t row_lo, int64_t nrows,
+                        double* cacc, int64_t ldc, double* rowss);
+int32_t gpd_ystats_cols_f32(gp_ctx* ctx, const float* y, int64_t ldy, int64_t ncols, const float* by, int64_t ldb, int32_t sb, int64_t row_lo, int64_t nrows,
+                            double* cacc, int64_t ldc, double* rowss);
 /* With parameter "time_kernels" = 1 every gpd_gemm_nt launch is bracketed by HIP events on the ctx
  * stream.  This synchronises the stream, returns the summed launch durations (ms) and the launch count since the
  * previous call, and clears the records (the caller knows the algorithmic flops of its own launches). */

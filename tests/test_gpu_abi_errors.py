@@ -65,7 +65,8 @@ def env(agp):
     A64, A32 = torch.zeros(256 + 128, 288, dtype=torch.float64, device="cuda"), torch.zeros(256 + 128, 288, dtype=torch.float32, device="cuda")
     keep += [A64, A32]
     e.update(A64=C.c_void_p(A64.data_ptr()), A32=C.c_void_p(A32.data_ptr()), k32=L.gp_kernel(0, 1, 1.5, 0, None), k64=L.gp_kernel(0, 0, 1.5, 0, None),
-             k64_kind4=L.gp_kernel(4, 0, 1.5, 0, None), grid=L.gp_grid(1, 0, 1, 0, 1, 0))
+             k64_kind4=L.gp_kernel(4, 0, 1.5, 0, None), grid=L.gp_grid(1, 0, 1, 0, 1, 0), ks32=L.gp_ksum(1, 2, terms),
+             A64_off8=C.c_void_p(A64.data_ptr() + 8), A32_off8=C.c_void_p(A32.data_ptr() + 8))
     yield e
     assert lib.gp_posterior_free(post) == 0 and lib.gp_vfe_free(vfe) == 0
     del keep
@@ -78,6 +79,11 @@ GPD = lambda A, k: {  # noqa: E731  (fp64 / fp32 twins share their argument list
     "assemble": ["h", k, A, 200, 256, 3, A, "@grid", A, 288, 256, 256], "potrf": ["h", A, 288, 256, 256, None, 0, 256, None],
     "trsm": ["h", A, 288, 128, A, 288, 128], "gemm_nt": ["h", A, 288, A, 288, A, 288, 128, 128, 32, None, 0, 0], "trsv": ["h", A, 288, 256, A, 256, 1, 1],
     "gemv_t": ["h", A, 288, 128, 128, A, A], "rowsumsq": ["h", A, 288, 128, 128, A]}
+GPD_GRAD = lambda A, k: {  # noqa: E731  (the gradient contractions and the sparse reductions: n = 200 of np = 256 points, D = 3; a 200 × 100 rectangle; 4 rows of 100
+    # columns; 16 rows of 128 columns.  A dict of their own, and their rows at the END of TABLE: the ids of the earlier rows carry their position)
+    "grad_contract": ["h", k, A, 288, A, A, 200, 256, 3, A, A, None],
+    "vgrad": ["h", A, 288, 1, A, 256, A, 256, 3, k, None, None, None, 200, 100, A, A, 256, 1.0, None, None, None, 0],
+    "ystats": ["h", A, 288, 100, A, 0, 4, A, A], "ystats_cols": ["h", A, 288, 128, A, 288, 1, 0, 16, A, 288, A]}
 BASE = {
     "gp_ctx_create": ["@new", 0, None], "gp_ctx_set_param": ["h", "name", -1], "gp_ctx_get_param": ["h", "name", "@i64"], "gp_ctx_trim": ["h"],
     "gp_get_timings": ["h", "@tm"],
@@ -101,6 +107,8 @@ BASE = {
     "gpd_inv_lower": ["h", "A64", 288, 64, "A64", 288, "A64", None], "gpd_trsm_inv": ["h", "A64", 288, 128, "A64", 288, 64, "A64", 288],
     "gpd_gemm_time": ["h", "dbl", "@i64"], "gpd_sync": ["h"],
     **{f"gpd_{n}": a for n, a in GPD("A64", "@k64").items()}, **{f"gpd_{n}_f32": a for n, a in GPD("A32", "@k32").items()},
+    **{f"gpd_{n}": a for n, a in GPD_GRAD("A64", "@k64").items()}, **{f"gpd_{n}_f32": a for n, a in GPD_GRAD("A32", "@k32").items()},
+    "gpd_grad_contract_sum": GPD_GRAD("A64", "@ks")["grad_contract"], "gpd_grad_contract_sum_f32": GPD_GRAD("A32", "@ks32")["grad_contract"],
 }
 
 CTX, POST, VFE = "not a live gp_ctx", "not a live gp_post", "not a live gp_vfe"
@@ -202,6 +210,22 @@ TABLE = [
     ("gpd_inv_lower", 4, 32, -4, "nb must be a multiple of 64"), ("gpd_inv_lower", 4, 96, -4, "nb must be a multiple of 64"),
     *[("gpd_inv_lower", i, None, -2, "l / w / scratch1 is NULL") for i in (2, 5, 7)],
     ("gpd_trsm_inv", 4, 96, -3, "m, nb must be multiples of 64"), ("gpd_trsm_inv", 7, 32, -3, "m, nb must be multiples of 64"),
+    # the gradient contractions and the sparse reductions (include/gpmi355.h lists each entry's refusals): a NULL / never-issued ctx, then the arguments
+    *[(fn, 1, bad, -1, CTX) for fn in [*[f"gpd_{n}{s}" for n in GPD_GRAD(0, 0) for s in ("", "_f32")], "gpd_grad_contract_sum", "gpd_grad_contract_sum_f32"]
+      for bad in (None, 0xDEADBEEF)],
+    *[(f"gpd_grad_contract{s}", 8, 200, -8, "np must be a positive multiple of 128") for s in ("", "_f32", "_sum", "_sum_f32")],
+    ("gpd_grad_contract", 3, "A64_off8", -3, "ci must be non-NULL and 16-byte aligned"), ("gpd_grad_contract_f32", 3, "A32_off8", -3, "16-byte aligned"),
+    ("gpd_grad_contract", 7, 257, -7, "n must be in 1..np"), ("gpd_grad_contract_f32", 4, 255, -4, "ld must be >= np"),
+    ("gpd_grad_contract", 2, "@kk", -2, "nscale must be 0, 1 or D"), ("gpd_grad_contract", 2, "@k32", -2, "kernel dtype does not match"),
+    ("gpd_grad_contract_sum", 9, 17, -2, "composite kernel: D must be <= 16"), ("gpd_grad_contract_sum_f32", 2, "@ks", -2, "kernel dtype does not match"),
+    ("gpd_grad_contract_sum", 2, None, -2, "kernel is NULL"), ("gpd_grad_contract", 10, None, -10, "g is NULL"),
+    *[(f"gpd_vgrad{s}", 9, 0, -9, "d must be >= 1") for s in ("", "_f32")], ("gpd_vgrad_f32", 3, 100, -3, "ldc must be >= nc rounded up to 128"),
+    ("gpd_vgrad", 10, "@kk", -10, "nscale must be 0, 1 or D"), ("gpd_vgrad", 4, 0, -11, "rs, bv and nu are needed with explicit_w = 0"),
+    ("gpd_vgrad", 2, "A64_off8", -2, "aligned to two elements"), ("gpd_vgrad", 17, None, -17, "gz is NULL or ldgz < nc"), ("gpd_vgrad_f32", 20, "A32", -20, "come together"),
+    ("gpd_ystats", 3, 287, -2, "16-byte rows"), ("gpd_ystats_f32", 5, None, -5, "b must be non-NULL and 16-byte aligned"), ("gpd_ystats_f32", 3, 286, -2, "16-byte rows"),
+    ("gpd_ystats_cols", 7, 9, -7, "sb must be 1..8"), ("gpd_ystats_cols_f32", 7, 0, -7, "sb must be 1..8"), ("gpd_ystats_cols", 9, 8, -9, "nrows a multiple of 16"),
+    ("gpd_ystats_cols_f32", 4, 32, -4, "ncols must be a positive multiple"), ("gpd_ystats_cols", 4, 48, -4, "ncols must be a positive multiple"),
+    ("gpd_ystats_cols", 11, 8, -10, "cacc is NULL or ldc < row_lo + nrows"),
 ]
 
 
