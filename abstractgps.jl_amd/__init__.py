@@ -10,6 +10,6 @@ The directory name contains a dot, so import it through the root-level shim:
 from .api import *  # noqa: F401,F403
 from .api import (GP, ARDTransform, ColVecs, Context, FiniteGP, Kernel, Matern12Kernel, Matern32Kernel,
                   Matern52Kernel, PosteriorGP, RowVecs, ScaleTransform, SqExponentialKernel, cov, default_context,
-                  kernelmatrix, loglikelihood, VFE, DTC, ExactInference, ApproxPosteriorGP, approx_log_evidence, elbo, inducing_points, logpdf, logpdf_and_grad, logpdf_and_grad_columns, loo_mean_and_var, loo_logpdf, loo_logpdf_and_grad, posterior_columns, ColumnsPosteriorGP, ApproxColumnsPosteriorGP, elbo_columns, approx_log_evidence_columns, elbo_and_grad_columns, logpdf_batch, logpdf_and_grad_batch, mean_and_var_batch, mean_and_var_grad_batch, joint_batch, mean_and_cov_batch, logpdf_heldout_batch, rand_batch, sqmahal, logdetcov, gradlogpdf, marginals, mean, mean_and_cov, mean_and_var, posterior, rand, rand_, update_posterior, var,
+                  kernelmatrix, loglikelihood, VFE, DTC, ExactInference, ApproxPosteriorGP, approx_log_evidence, elbo, inducing_points, logpdf, logpdf_and_grad, logpdf_and_grad_columns, loo_mean_and_var, loo_logpdf, loo_logpdf_and_grad, loo_logpdf_batch, loo_mean_and_var_batch, loo_logpdf_and_grad_batch, posterior_columns, ColumnsPosteriorGP, ApproxColumnsPosteriorGP, elbo_columns, approx_log_evidence_columns, elbo_and_grad_columns, logpdf_batch, logpdf_and_grad_batch, mean_and_var_batch, mean_and_var_grad_batch, joint_batch, mean_and_cov_batch, logpdf_heldout_batch, rand_batch, sqmahal, logdetcov, gradlogpdf, marginals, mean, mean_and_cov, mean_and_var, posterior, rand, rand_, update_posterior, var,
                   with_lengthscale)
 from ._lib import GpmiError, PosDefException  # noqa: F401

@@ -116,6 +116,12 @@ PROTOTYPES = {
                                      C.POINTER(vp), C.POINTER(vp)]),
     "gp_logpdf_grad_batch_sum_x": (i32, [vp, i32, PS, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp), C.POINTER(vp),
                                          C.POINTER(vp), C.POINTER(vp)]),
+    "gp_loo_batch": (i32, [vp, i32, PK, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "gp_loo_batch_sum": (i32, [vp, i32, PS, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "gp_loo_grad_batch": (i32, [vp, i32, PK, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(dbl), C.POINTER(vp), C.POINTER(vp),
+                                C.POINTER(vp), C.POINTER(vp)]),
+    "gp_loo_grad_batch_sum": (i32, [vp, i32, PS, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp), C.POINTER(vp),
+                                    C.POINTER(vp), C.POINTER(vp)]),
     "gp_posterior_update": (i32, [vp, PP, PN, vp, C.POINTER(vp), vp, vp]),
     "gp_posterior_factor_mul": (i32, [vp, vp, i32, vp]),
     "gp_posterior_solve": (i32, [vp, vp, i32, vp]),
@@ -202,6 +208,16 @@ def batch_grad_max_n() -> int:
 def batch_gradx_max_n() -> int:
     """GPMI355_BATCH_GRADX_MAX_N of include/gpmi355.h: the largest problem gp_logpdf_grad_batch_x hands to its kernels when dx is asked for."""
     return int(re.search(r"#define GPMI355_BATCH_GRADX_MAX_N (\d+)", HEADER.read_text()).group(1))
+
+
+def batch_loo_max_n() -> int:
+    """GPMI355_BATCH_LOO_MAX_N of include/gpmi355.h: the largest problem gp_loo_batch hands to its kernels."""
+    return int(re.search(r"#define GPMI355_BATCH_LOO_MAX_N (\d+)", HEADER.read_text()).group(1))
+
+
+def batch_loo_grad_max_n() -> int:
+    """GPMI355_BATCH_LOO_GRAD_MAX_N of include/gpmi355.h: the largest problem gp_loo_grad_batch hands to its kernels (no problem of a call with dx)."""
+    return int(re.search(r"#define GPMI355_BATCH_LOO_GRAD_MAX_N (\d+)", HEADER.read_text()).group(1))
 
 
 def batch_pgrad_max_n() -> int:

@@ -1386,6 +1386,12 @@ def logpdf_and_grad_batch(fxs, ys, *, wrt_x: bool = False, on_error: str = "rais
     logpdf_and_grad(wrt_x=True) returns it — what a deep-kernel model behind many small GPs back-propagates into its feature map; problems that share one x
     object each get their own gradient w.r.t. it.  on_error = "raise": the PosDefException of the first failing problem (.info, .index); "nan": NaN in its
     logpdf and in every entry of its gradient."""
+    return _objective_and_grad_batch(fxs, ys, wrt_x, on_error, _grad_batch_marshal)
+
+
+def _objective_and_grad_batch(fxs, ys, wrt_x, on_error: str, marshal):
+    """The body logpdf_and_grad_batch (marshal = _grad_batch_marshal) and loo_logpdf_and_grad_batch (_loo_grad_batch_marshal) share: the two families
+    take the same arguments and return the same outputs."""
     if on_error not in ("raise", "nan"):
         raise ValueError('on_error must be "raise" or "nan"')
     if not isinstance(wrt_x, (bool, np.bool_)):
@@ -1396,7 +1402,7 @@ def logpdf_and_grad_batch(fxs, ys, *, wrt_x: bool = False, on_error: str = "rais
     grads = [None] * len(fxs)
     parts = []
     for g in _batch_groups(fxs, ys):
-        call = _grad_batch_marshal(g, bool(wrt_x))
+        call = marshal(g, bool(wrt_x))
         ctx = g.ctx or default_context()
         check(getattr(ctx.lib, call.entry)(ctx.handle, *call.args))
         parts.append((g.index, call.out, call.info, None))
@@ -1411,6 +1417,102 @@ def logpdf_and_grad_batch(fxs, ys, *, wrt_x: bool = False, on_error: str = "rais
             if wrt_x:
                 grads[i]["x"] = _dx_shaped(call.dx[j], call.pts[0 if g.nx == 1 else j], g.fxs[j].x)
     return _batch_merge(len(fxs), parts, False, on_error), grads
+
+
+# --------------------------------------------------------------------------------------------
+# leave-one-out cross-validation of many small problems in one call: gp_loo_batch / gp_loo_grad_batch and their *_sum forms
+# --------------------------------------------------------------------------------------------
+@dataclass(eq=False)
+class _LooBatchCall:
+    """The marshalled arguments of one gp_loo_batch[_sum] call (everything after the ctx) and the buffers behind them."""
+
+    entry: str
+    nb: int
+    nx: int
+    ny: int
+    args: tuple
+    out: np.ndarray           # L of every problem
+    info: np.ndarray
+    lp: Optional[list]        # per problem n entries, or None where the call does not ask for them
+    mean: Optional[list]
+    var: Optional[list]
+    keep: object
+
+
+def _loo_batch_marshal(g: _BatchGroup, want_lp: bool = True, want_pred: bool = True) -> _LooBatchCall:
+    """ctypes arguments of one group — needs no context.  The leading arguments are those of _batch_marshal; behind value_out and info_out the arrays of
+    ℓ (want_lp), μ and v (want_pred) pointers, NULL for what is not asked for."""
+    fit = _batch_marshal(g, False)
+    m, nb = fit.keep, fit.nb
+    ns = [len(fx) for fx in g.fxs]
+
+    def outs(want):
+        if not want:
+            return None, None
+        bufs = [np.empty(n, dtype=g.dtype) for n in ns]
+        arr = (C.c_void_p * nb)(*[a.ctypes.data for a in bufs])
+        m.keep.append(arr)
+        return bufs, arr
+
+    (lp, lparr), (mu, muarr), (var, vararr) = outs(want_lp), outs(want_pred), outs(want_pred)
+    return _LooBatchCall("gp_loo_batch" + ("_sum" if g.composite else ""), nb, g.nx, g.ny, fit.args[:-1] + (lparr, muarr, vararr), fit.out, fit.info,
+                         lp, mu, var, m)
+
+
+def _loo_grad_batch_marshal(g: _BatchGroup, wrt_x: bool = False) -> _GradBatchCall:
+    """ctypes arguments of one group — needs no context: those of _grad_batch_marshal for gp_loo_grad_batch[_sum], whose dx array is always part of the
+    prototype (NULL without wrt_x)."""
+    call = _grad_batch_marshal(g, wrt_x)
+    call.entry = "gp_loo_grad_batch" + ("_sum" if g.composite else "")
+    if not wrt_x:
+        call.args = call.args + (None,)
+    return call
+
+
+def _loo_batch(fxs, ys, on_error: str, want_lp: bool, want_pred: bool):
+    """(L in the caller's order, per-problem ℓ, μ, v lists) of one gp_loo_batch[_sum] call per group"""
+    if on_error not in ("raise", "nan"):
+        raise ValueError('on_error must be "raise" or "nan"')
+    fxs = list(fxs)
+    n = len(fxs)
+    lp, mu, var = [None] * n, [None] * n, [None] * n
+    if not fxs:
+        return np.empty(0), lp, mu, var
+    parts = []
+    for g in _batch_groups(fxs, ys):
+        call = _loo_batch_marshal(g, want_lp, want_pred)
+        ctx = g.ctx or default_context()
+        check(getattr(ctx.lib, call.entry)(ctx.handle, *call.args))
+        parts.append((g.index, call.out, call.info, None))
+        for j, i in enumerate(g.index):
+            if want_lp:
+                lp[i] = call.lp[j]
+            if want_pred:
+                mu[i], var[i] = call.mean[j], call.var[j]
+    return _batch_merge(n, parts, False, on_error), lp, mu, var
+
+
+def loo_logpdf_batch(fxs, ys, *, pointwise: bool = False, on_error: str = "raise"):
+    """loo_logpdf(fx_b, y_b) of many independent exact GPs in one library call per (ctx, dtype, single-kind / composite) group (gp_loo_batch) — what a grid
+    of hyper-parameters scored by its leave-one-out log predictive density evaluates again and again.  fxs, ys as in logpdf_batch (the same x / y object
+    in every entry is sent once).  Returns the array of L_b; with pointwise, (that array, the list of the vectors log p(y_i | y_−i) in the caller's
+    order).  on_error = "raise": the PosDefException of the first failing problem (.info, .index); "nan": NaN in every output of that problem."""
+    L, lp, _, _ = _loo_batch(fxs, ys, on_error, bool(pointwise), False)
+    return (L, lp) if pointwise else L
+
+
+def loo_mean_and_var_batch(fxs, ys, *, on_error: str = "raise"):
+    """loo_mean_and_var(fx_b, y_b) of many independent exact GPs in one library call per group (gp_loo_batch): (list of μ vectors, list of v vectors) in
+    the caller's order.  fxs, ys and on_error as in loo_logpdf_batch."""
+    _, _, mu, var = _loo_batch(fxs, ys, on_error, False, True)
+    return mu, var
+
+
+def loo_logpdf_and_grad_batch(fxs, ys, *, wrt_x: bool = False, on_error: str = "raise"):
+    """Value and gradient of loo_logpdf(fx_b, y_b) of many independent exact GPs in one library call per group (gp_loo_grad_batch) — restarts or folds
+    trained on the leave-one-out objective.  Arguments and result as logpdf_and_grad_batch: (array of L_b, list of the dicts of loo_logpdf_and_grad in the
+    caller's order).  With wrt_x every problem of the call runs on the single path inside the library (the batch kernels have no ∂/∂x yet)."""
+    return _objective_and_grad_batch(fxs, ys, wrt_x, on_error, _loo_grad_batch_marshal)
 
 
 def loglikelihood(fx: FiniteGP, Y):  # src/finite_gp_projection.jl:304

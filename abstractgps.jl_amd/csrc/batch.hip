@@ -515,6 +515,15 @@ __global__ __launch_bounds__(NT) void batch_inv_kernel(const double* __restrict_
     (void)strip_solve(V, A, ld, r0, nt, rows, sh, tid, lane, w);
 }
 
+// What the leave-one-out kernels know of a problem beyond its BatchProb and GradProb; same position in its table as the descriptor.  Offsets count doubles:
+// lpart_off (one partial Σ ℓ_i per 128-row tile), z_off (the Z strip, np rows of ld), d_off and e_off (d_i = √(2 a_i) and e_i = b_i / d_i, np entries each,
+// zero from n on) into the workspace; lp_off / mean_off / var_off (n entries each) and beta_off (β, np entries) into the result buffer.  −1: not wanted
+// (z_off, d_off, e_off and beta_off are all wanted, or none is: the value calls need none of them).
+struct LooProb {
+    long lpart_off, z_off, d_off, e_off, lp_off, mean_off, var_off, beta_off;
+};
+static_assert(sizeof(LooProb) % 8 == 0, "the tables are packed behind double data");
+
 // The 64×64 tile (ti >= tj) of the lower triangle of one problem:
 //   1. C⁻¹_tile = Σ_{k ≥ 64 ti} S[i, k] S[j, k] by mfma_tile_k64 straight from the strip, one 32×32 wave tile per wave; the weights
 //      W_ij = (α_i α_j − C⁻¹_ij)·(i = j ? ½ : 1) of the pairs j ≤ i < n into LDS;
@@ -523,9 +532,12 @@ __global__ __launch_bounds__(NT) void batch_inv_kernel(const double* __restrict_
 //      ksum_grad, GRAD_NP θ entries per pass in per-thread LDS slots.  The diagonal adds W_ii to the noise sum; a diagonal Σy's entries are stored directly.
 //   3. the per-thread sums by a butterfly per wave, the four waves added in order, stored as this tile's ng sums (batch_gsum_kernel adds the tiles).
 // A failed problem's tiles return at once (batch_gsum_kernel writes its NaN): neither slice nor strip is read.
-template <bool SUM>
+// LOO: the gradient of the leave-one-out objective (gp_loo_grad_batch) from the same steps 2 and 3.  Step 1 reads the Z strip batch_loo_z_kernel left and the β
+// of batch_loo_beta_kernel: the tile is Σ over ALL k of Z[i, k] Z[j, k] (Z is a full matrix), W_ij = (β_i α_j + α_i β_j − (Z Zᵀ)_ij)·(i = j ? ½ : 1) = 2 G_ij
+// resp. G_ii: Σ W ∂C/∂θ over the lower triangle is ⟨G, ∂C/∂θ⟩, the noise sum tr G, a diagonal Σy's entries G_ii.
+template <bool SUM, bool LOO>
 __global__ __launch_bounds__(GNT) void batch_grad_kernel(const double* __restrict__ in, double* __restrict__ ws, double* __restrict__ res, int nw,
-                                                        const GradProb* __restrict__ gps, const GradTile* __restrict__ tiles) {
+                                                        const GradProb* __restrict__ gps, const GradTile* __restrict__ tiles, const LooProb* __restrict__ lps) {
     __shared__ double Wt[BT][BT];
     __shared__ double acc[SUM ? GRAD_NP : 1][GNT];
     __shared__ double kf[SUM ? KSum::MAXFT : 1][GNT];
@@ -538,8 +550,9 @@ __global__ __launch_bounds__(GNT) void batch_grad_kernel(const double* __restric
     const int n = P.n, np = P.np, d = P.d;
     const long ld = P.ld;
     const int it0 = T.ti * BT, jt0 = T.tj * BT;
-    const double* __restrict__ S = ws + G.s_off;
+    const double* __restrict__ S = ws + (LOO ? lps[T.prob].z_off : G.s_off);  // LOO: the Z strip
     const double* __restrict__ alpha = res + P.alpha_off;
+    const double* __restrict__ beta = LOO ? res + lps[T.prob].beta_off : nullptr;
     const double* __restrict__ x = in + P.x_off;
     double* __restrict__ part = ws + G.part_off + (long)T.idx * G.ng;
 
@@ -551,18 +564,22 @@ __global__ __launch_bounds__(GNT) void batch_grad_kernel(const double* __restric
             const int i0 = it0 + 32 * wi, c0 = jt0 + 32 * wj;
             d4_t c4[2][2];
             acc_zero(c4);
-            for (int k0 = it0; k0 < np; k0 += BT) mfma_tile_k64<false>(c4, S, i0, S, c0, k0, ld, lane);
+            for (int k0 = LOO ? 0 : it0; k0 < np; k0 += BT) mfma_tile_k64<false>(c4, S, i0, S, c0, k0, ld, lane);
 #pragma unroll
             for (int hi = 0; hi < 2; ++hi)
 #pragma unroll
                 for (int hj = 0; hj < 2; ++hj) {
                     const int gj = c0 + 16 * hj + r;
                     const double aj = gj < n ? alpha[gj] : 0.0;
+                    const double bj = (LOO && gj < n) ? beta[gj] : 0.0;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const int gi = i0 + 16 * hi + Tr<double>::crow(lane, q);
                         double wv = 0.0;
-                        if (gi < n && gj <= gi) wv = (alpha[gi] * aj - c4[hi][hj][q]) * (gi == gj ? 0.5 : 1.0);
+                        if (gi < n && gj <= gi) {
+                            if (LOO) wv = (fma(beta[gi], aj, alpha[gi] * bj) - c4[hi][hj][q]) * (gi == gj ? 0.5 : 1.0);
+                            else wv = (alpha[gi] * aj - c4[hi][hj][q]) * (gi == gj ? 0.5 : 1.0);
+                        }
                         Wt[gi - it0][gj - jt0] = wv;
                     }
                 }
@@ -682,6 +699,150 @@ __global__ __launch_bounds__(128) void batch_gsum_kernel(const double* __restric
     double s = 0.0;
     for (int t = 0; t < G.ntiles; ++t) s += part[(long)t * G.ng + tid];
     res[G.g_off + tid] = s;
+}
+
+// ---- leave-one-out cross-validation: batch_loo_kernel, batch_loo_sum_kernel; for its gradient batch_loo_z_kernel, batch_loo_beta_kernel ---------------------
+// Launched behind batch_logpdf_kernel and batch_inv_kernel on the same stream, on the α and the S strips they left.  With C⁻¹ = S Sᵀ, c_i = [C⁻¹]_ii = Σ_{k ≥ i} S_ik²:
+//   μ_i = y_i − α_i / c_i,  v_i = 1 / c_i,  ℓ_i = −½ log 2π + ½ log c_i − ½ α_i² / c_i,  L = Σ ℓ_i;   a_i = ½(1/c_i + α_i²/c_i²),  b_i = α_i / c_i,  β = C⁻¹ b,
+//   dL = ⟨G, dC⟩ with 2G = β αᵀ + α βᵀ − Z Zᵀ,  Z = C⁻¹ diag(d),  d_i = √(2 a_i)   (batch_grad_kernel<SUM, true> contracts it).
+// Padding (n ≤ k < np): d_k = e_k = β_k = 0, so column k of Z is zero; the rows of S and C⁻¹ beyond n are those of the identity: nothing leaks either way.
+// As everywhere in this unit: launch boundaries are the only synchronisation, one writer per entry, every sum in an order the problem's size alone fixes.
+
+// 128 rows of one problem (the tile table of batch_inv_kernel): one wave per row at a time (rows w, w + 8, … of the tile), the lanes stride the row of S from
+// the first column of the row's 64-block on (left of it the strip is not written), 64 partial sums of squares joined by a butterfly.  Lane 0 writes the row's
+// terms; thread 0 adds the ℓ_i of the tile in row order into the tile's partial sum.  A failed problem's tiles return at once.
+__global__ __launch_bounds__(NT) void batch_loo_kernel(const double* __restrict__ in, double* __restrict__ ws, double* __restrict__ res, int nw,
+                                                       const GradProb* __restrict__ gps, const LooProb* __restrict__ lps, const GradTile* __restrict__ tiles) {
+    __shared__ double ls[TP];
+    const GradTile& T = tiles[blockIdx.x];
+    const BatchProb& P = reinterpret_cast<const BatchProb*>(in)[T.prob];
+    const LooProb& Q = lps[T.prob];
+    if (res[nw + P.slot] != 0.0) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = P.n, np = P.np, r0 = T.ti * TP;
+    const long ld = P.ld;
+    const int rows = np - r0 < TP ? np - r0 : TP;  // 64 or 128
+    const double* __restrict__ S = ws + gps[T.prob].s_off;
+    const double* __restrict__ alpha = res + P.alpha_off;
+    const double* __restrict__ y = in + P.y_off;
+    for (int li = w; li < rows; li += 8) {
+        const int i = r0 + li;  // wave-uniform
+        double s = 0.0;
+        if (i < n)
+            for (int k = (i & ~(BT - 1)) + lane; k < np; k += 64) {
+                const double t = S[(long)i * ld + k];
+                s = fma(t, t, s);
+            }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == 0) {
+            double lp = 0.0, dv = 0.0, ev = 0.0;
+            if (i < n) {
+                const double c = s, al = alpha[i], v = 1.0 / c, bi = al * v;
+                lp = -0.91893853320467274178032973640562 + 0.5 * log(c) - 0.5 * al * bi;
+                if (Q.lp_off >= 0) res[Q.lp_off + i] = lp;
+                if (Q.mean_off >= 0) res[Q.mean_off + i] = y[i] - bi;
+                if (Q.var_off >= 0) res[Q.var_off + i] = v;
+                dv = sqrt(fma(bi, bi, v));  // √(2 a_i), a_i = ½(v + b_i²)
+                ev = bi / dv;
+            }
+            ls[li] = lp;
+            if (Q.d_off >= 0) {
+                ws[Q.d_off + i] = dv;
+                ws[Q.e_off + i] = ev;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double s = 0.0;
+        for (int li = 0; li < rows; ++li) s += ls[li];
+        ws[Q.lpart_off + T.ti] = s;
+    }
+}
+
+// L of every problem of a wave: one workgroup per problem, thread 0 adds the tiles' partial sums in tile order and stores L in place of the logpdf.  A failed
+// problem gets NaN in L, in the three per-point outputs and in β; nothing of its workspace is read.
+__global__ __launch_bounds__(128) void batch_loo_sum_kernel(const double* __restrict__ in, const double* __restrict__ ws, double* __restrict__ res, int nw,
+                                                           const LooProb* __restrict__ lps) {
+    const BatchProb& P = reinterpret_cast<const BatchProb*>(in)[blockIdx.x];
+    const LooProb& Q = lps[blockIdx.x];
+    const int tid = threadIdx.x;
+    if (res[nw + P.slot] != 0.0) {
+        const double nan = __builtin_nan("");
+        if (tid == 0) res[P.slot] = nan;
+        for (int i = tid; i < P.n; i += 128) {
+            if (Q.lp_off >= 0) res[Q.lp_off + i] = nan;
+            if (Q.mean_off >= 0) res[Q.mean_off + i] = nan;
+            if (Q.var_off >= 0) res[Q.var_off + i] = nan;
+            if (Q.beta_off >= 0) res[Q.beta_off + i] = nan;
+        }
+        return;
+    }
+    if (tid != 0) return;
+    double s = 0.0;
+    for (int t = 0; t < (P.np + TP - 1) / TP; ++t) s += ws[Q.lpart_off + t];
+    res[P.slot] = s;
+}
+
+// The 64×64 tile (ti, tk) of the FULL square of Z = C⁻¹ diag(d) of one problem: C⁻¹_tile = Σ_{m ≥ 64·max(ti, tk)} S[i, m] S[k, m] by mfma_tile_k64 straight from
+// the S strip, one 32×32 wave tile per wave (step 1 of batch_gradx_kernel), times d_k, into the Z strip: every entry of the np × np square is written, by one
+// thread.  A failed problem's tiles return at once.
+__global__ __launch_bounds__(GNT) void batch_loo_z_kernel(const double* __restrict__ in, double* __restrict__ ws, const double* __restrict__ res, int nw,
+                                                         const GradProb* __restrict__ gps, const LooProb* __restrict__ lps, const GradTile* __restrict__ tiles) {
+    const GradTile& T = tiles[blockIdx.x];
+    const BatchProb& P = reinterpret_cast<const BatchProb*>(in)[T.prob];
+    const LooProb& Q = lps[T.prob];
+    if (res[nw + P.slot] != 0.0) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int np = P.np;
+    const long ld = P.ld;
+    const int it0 = T.ti * BT, kt0 = T.tj * BT;
+    const double* __restrict__ S = ws + gps[T.prob].s_off;
+    const double* __restrict__ dv = ws + Q.d_off;
+    double* __restrict__ Z = ws + Q.z_off;
+    const int r = lane & 15;
+    const int i0 = it0 + 32 * (w >> 1), c0 = kt0 + 32 * (w & 1);
+    d4_t c4[2][2];
+    acc_zero(c4);
+    for (int k0 = T.ti > T.tj ? it0 : kt0; k0 < np; k0 += BT) mfma_tile_k64<false>(c4, S, i0, S, c0, k0, ld, lane);
+#pragma unroll
+    for (int hi = 0; hi < 2; ++hi)
+#pragma unroll
+        for (int hj = 0; hj < 2; ++hj) {
+            const int gk = c0 + 16 * hj + r;
+            const double dk = dv[gk];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int gi = i0 + 16 * hi + Tr<double>::crow(lane, q);
+                Z[(long)gi * ld + gk] = c4[hi][hj][q] * dk;
+            }
+        }
+}
+
+// β = C⁻¹ b of 128 rows of one problem (the tile table of batch_inv_kernel) from the Z strip: β_i = Σ_k Z_ik e_k with e_k = b_k / d_k (d_k > 0 below n, e_k = 0
+// from n on), one wave per row at a time, the lanes stride the row, a butterfly joins them.  The rows from n on get 0.  A failed problem's tiles return at once.
+__global__ __launch_bounds__(NT) void batch_loo_beta_kernel(const double* __restrict__ in, const double* __restrict__ ws, double* __restrict__ res, int nw,
+                                                            const LooProb* __restrict__ lps, const GradTile* __restrict__ tiles) {
+    const GradTile& T = tiles[blockIdx.x];
+    const BatchProb& P = reinterpret_cast<const BatchProb*>(in)[T.prob];
+    const LooProb& Q = lps[T.prob];
+    if (res[nw + P.slot] != 0.0) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = P.n, np = P.np, r0 = T.ti * TP;
+    const long ld = P.ld;
+    const int rows = np - r0 < TP ? np - r0 : TP;
+    const double* __restrict__ Z = ws + Q.z_off;
+    const double* __restrict__ ev = ws + Q.e_off;
+    for (int li = w; li < rows; li += 8) {
+        const int i = r0 + li;  // wave-uniform
+        double s = 0.0;
+        if (i < n)
+            for (int k = lane; k < np; k += 64) s = fma(Z[(long)i * ld + k], ev[k], s);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == 0) res[Q.beta_off + i] = s;
+    }
 }
 
 // ---- the gradient of logpdf w.r.t. the inputs: batch_gradx_kernel, batch_gxsum_kernel ---------------------------------------------------------------------
@@ -1292,8 +1453,10 @@ int32_t launch_pgrad(const WaveMem& m, bool ks, int nw, const BatchTile* tiles, 
     HIPCHK(hipGetLastError());
     return 0;
 }
-int32_t launch_grad(const WaveMem& m, bool ks, int nw, const GradProb* gps, const GradTile* tiles, size_t ntiles) {
-    hipLaunchKernelGGL(ks ? batch_grad_kernel<true> : batch_grad_kernel<false>, dim3((unsigned)ntiles), dim3(GNT), 0, m.c->sm, m.in, m.ws, m.res, nw, gps, tiles);
+// lps: the LooProb table of a gp_loo_grad_batch wave (the weights of the leave-one-out objective), or NULL (those of logpdf)
+int32_t launch_grad(const WaveMem& m, bool ks, int nw, const GradProb* gps, const GradTile* tiles, size_t ntiles, const LooProb* lps = nullptr) {
+    auto kern = lps ? (ks ? batch_grad_kernel<true, true> : batch_grad_kernel<false, true>) : (ks ? batch_grad_kernel<true, false> : batch_grad_kernel<false, false>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(GNT), 0, m.c->sm, m.in, m.ws, m.res, nw, gps, tiles, lps);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2127,6 +2290,223 @@ int32_t gradx_batch_impl(gp_ctx* c, GradArgs& a) {
     return grad_batch_impl(c, a);
 }
 
+// ---- gp_loo_batch / gp_loo_batch_sum, gp_loo_grad_batch / gp_loo_grad_batch_sum ------------------------------------------------------------------------
+struct LooArgs : GradArgs {  // logpdf_out is value_out; the value calls leave every gradient array NULL, the gradient calls the three per-point arrays
+    bool grad;
+    void* const* lp = nullptr;
+    void* const* mean = nullptr;
+    void* const* var = nullptr;
+    void* lpb(int b) const { return lp ? lp[b] : nullptr; }
+    void* meanb(int b) const { return mean ? mean[b] : nullptr; }
+    void* varb(int b) const { return var ? var[b] : nullptr; }
+};
+
+long loo_tiles(long n) { return (batch_np(n) + TP - 1) / TP; }  // the 128-row tiles of a strip
+// workspace of a problem in a leave-one-out wave: its slice, the S strip and the partial sums of L; for the gradient the Z strip, d and e and the per-tile sums
+long loo_ws(const LooArgs& a, const std::vector<KSum>& packed, int b) {
+    const long n = a.xb(b).n, np = batch_np(n);
+    const long value = batch_slice(n) + np * batch_ld(np) + ((loo_tiles(n) + 1) & ~1L);
+    return a.grad ? value + np * batch_ld(np) + 2 * np + ((grad_ntiles(n) * (1 + grad_nkp(a, packed, b)) + 1) & ~1L) : value;
+}
+
+// NaN in every output of problem b beyond its value
+void loo_fill_nan(const LooArgs& a, int b, int nkp) {
+    const long n = a.xb(b).n;
+    fill_nan(a.lpb(b), a.dtype, n);
+    fill_nan(a.meanb(b), a.dtype, n);
+    fill_nan(a.varb(b), a.dtype, n);
+    if (a.grad) grad_fill_nan(a, b, nkp);
+}
+
+// one wave: the fit launch of the problems idx[0..nw) with α for every one of them, S = L⁻ᵀ, the leave-one-out terms and their sum; for the gradient Z, β, the
+// tile sums with the leave-one-out weights and their totals.  Caller holds the ctx lock.
+int32_t run_loo_wave(gp_ctx* c, const LooArgs& a, const std::vector<KSum>& packed, const int* idx, int nw) {
+    WaveLayout L;
+    wave_layout(a, idx, nw, [](int) { return true; }, L);
+    // behind the fit's input: the GradProb and LooProb tables (in the order of the descriptors), the 128-row tiles of the strips, the tiles of the triangle and
+    // of the full square, the widest problems first
+    std::vector<GradProb> gp((size_t)nw);
+    std::vector<LooProb> lq((size_t)nw);
+    std::vector<GradTile> itiles, gtiles, ztiles;
+    for (int s = 0; s < nw; ++s) {
+        const int t = L.order[s], b = idx[t];
+        const BatchProb& p = L.pr[t];
+        GradProb& g = gp[s];
+        LooProb& q = lq[s];
+        const int nt = p.np / BT;
+        g = GradProb{-1, -1, -1, -1, 0, 0};
+        q = LooProb{-1, -1, -1, -1, -1, -1, -1, -1};
+        g.s_off = take(L.ws, (long)p.np * p.ld);
+        q.lpart_off = take(L.ws, (loo_tiles(p.n) + 1) & ~1L);  // the next strip stays 16-byte aligned
+        if (a.lpb(b)) q.lp_off = take(L.roff, p.n);
+        if (a.meanb(b)) q.mean_off = take(L.roff, p.n);
+        if (a.varb(b)) q.var_off = take(L.roff, p.n);
+        for (int r0 = 0; r0 < p.np; r0 += TP) itiles.push_back(GradTile{s, r0 / TP, 0, 0});
+        if (!a.grad) continue;
+        g.ng = 1 + grad_nkp(a, packed, b);
+        g.ntiles = nt * (nt + 1) / 2;
+        q.z_off = take(L.ws, (long)p.np * p.ld);
+        q.d_off = take(L.ws, p.np);
+        q.e_off = take(L.ws, p.np);
+        g.part_off = take(L.ws, ((long)g.ntiles * g.ng + 1) & ~1L);
+        g.g_off = take(L.roff, g.ng);
+        g.dn_off = a.noise[b].kind == 1 ? take(L.roff, p.n) : -1;
+        q.beta_off = take(L.roff, p.np);
+        for (int ti = 0; ti < nt; ++ti) {
+            for (int tj = 0; tj <= ti; ++tj) gtiles.push_back(GradTile{s, ti, tj, ti * (ti + 1) / 2 + tj});
+            for (int tj = 0; tj < nt; ++tj) ztiles.push_back(GradTile{s, ti, tj, ti * nt + tj});
+        }
+    }
+    const long gp_off = take(L.off, (long)(gp.size() * sizeof(GradProb) / 8));
+    const long lq_off = take(L.off, (long)(lq.size() * sizeof(LooProb) / 8));
+    const long it_off = take(L.off, (long)(itiles.size() * sizeof(GradTile) / 8));
+    const long gt_off = take(L.off, (long)(gtiles.size() * sizeof(GradTile) / 8));
+    const long zt_off = take(L.off, (long)(ztiles.size() * sizeof(GradTile) / 8));
+
+    WaveMem m(c);
+    RC(m.alloc(L.off, L.ws, L.roff));
+    wave_fill(a, packed, idx, nw, L, m.hin);
+    std::memcpy(m.hin + gp_off, gp.data(), gp.size() * sizeof(GradProb));
+    std::memcpy(m.hin + lq_off, lq.data(), lq.size() * sizeof(LooProb));
+    std::memcpy(m.hin + it_off, itiles.data(), itiles.size() * sizeof(GradTile));
+    if (a.grad) {
+        std::memcpy(m.hin + gt_off, gtiles.data(), gtiles.size() * sizeof(GradTile));
+        std::memcpy(m.hin + zt_off, ztiles.data(), ztiles.size() * sizeof(GradTile));
+    }
+    RC(run_drained(c, [&]() -> int32_t {
+        const GradProb* gps = reinterpret_cast<const GradProb*>(m.in + gp_off);
+        const LooProb* lps = reinterpret_cast<const LooProb*>(m.in + lq_off);
+        const GradTile* its = reinterpret_cast<const GradTile*>(m.in + it_off);
+        const unsigned nit = (unsigned)itiles.size();
+        RC(m.upload());
+        RC(launch_fit(m, a.ks != nullptr, nw));
+        hipLaunchKernelGGL(batch_inv_kernel, dim3(nit), dim3(NT), 0, c->sm, m.in, m.ws, (const double*)m.res, nw, gps, its);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(batch_loo_kernel, dim3(nit), dim3(NT), 0, c->sm, m.in, m.ws, m.res, nw, gps, lps, its);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(batch_loo_sum_kernel, dim3((unsigned)nw), dim3(128), 0, c->sm, m.in, (const double*)m.ws, m.res, nw, lps);
+        HIPCHK(hipGetLastError());
+        if (a.grad) {
+            hipLaunchKernelGGL(batch_loo_z_kernel, dim3((unsigned)ztiles.size()), dim3(GNT), 0, c->sm, m.in, m.ws, (const double*)m.res, nw, gps, lps,
+                               reinterpret_cast<const GradTile*>(m.in + zt_off));
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL(batch_loo_beta_kernel, dim3(nit), dim3(NT), 0, c->sm, m.in, (const double*)m.ws, m.res, nw, lps, its);
+            HIPCHK(hipGetLastError());
+            RC(launch_grad(m, a.ks != nullptr, nw, gps, reinterpret_cast<const GradTile*>(m.in + gt_off), gtiles.size(), lps));
+            hipLaunchKernelGGL(batch_gsum_kernel, dim3((unsigned)nw), dim3(128), 0, c->sm, m.in, (const double*)m.ws, m.res, nw, gps);
+            HIPCHK(hipGetLastError());
+        }
+        return m.download_and_sync();
+    }));
+    const double* hout = m.hout;
+    (a.grad ? c->batch_loo_grad_problems : c->batch_loo_problems) += nw;
+    for (int t = 0; t < nw; ++t) {
+        const int b = idx[t];
+        const GradProb& g = gp[L.pos[t]];
+        const LooProb& q = lq[L.pos[t]];
+        const size_t bytes = sizeof(double) * (size_t)L.pr[t].n;
+        put_result(a, b, hout[t], (int32_t)hout[nw + t]);
+        if (q.lp_off >= 0) std::memcpy(a.lpb(b), hout + q.lp_off, bytes);
+        if (q.mean_off >= 0) std::memcpy(a.meanb(b), hout + q.mean_off, bytes);
+        if (q.var_off >= 0) std::memcpy(a.varb(b), hout + q.var_off, bytes);
+        if (!a.grad) continue;
+        const double* G = hout + g.g_off;  // [0] noise, then the kernel's parameters
+        if (a.dvar) a.dvar[b] = G[1];
+        if (a.dscale && a.dscale[b]) std::memcpy(a.dscale[b], G + 2, sizeof(double) * (size_t)(g.ng - 2));
+        if (a.dtheta) std::memcpy(a.dtheta[b], G + 1, sizeof(double) * (size_t)(g.ng - 1));
+        if (double* dn = (double*)a.dnb(b)) {
+            if (g.dn_off >= 0) std::memcpy(dn, hout + g.dn_off, bytes);
+            else dn[0] = G[0];
+        }
+        if (double* dy = (double*)a.dyb(b)) {
+            const double* be = hout + q.beta_off;
+            for (long j = 0; j < L.pr[t].n; ++j) dy[j] = -be[j];
+        }
+    }
+    return 0;
+}
+
+// the checks both bodies share, behind the ctx check: counts, arrays, problems; value_out and info_out are arguments 10 and 11
+int32_t loo_check_head(LooArgs& a, std::vector<KSum>& packed) {
+    RC(check_batch_head(a));
+    if (!a.logpdf_out) return set_arg_err(10, "value_out is NULL");
+    if (!a.info_out) return set_arg_err(11, "info_out is NULL");
+    return check_batch_problems(a, packed);
+}
+
+// gp_loo_batch / gp_loo_batch_sum
+int32_t loo_batch_impl(gp_ctx* c, LooArgs& a) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    if (a.nb < 0) return set_arg_err(2, "nb must be >= 0");
+    if (a.nb == 0) return 0;
+    std::vector<KSum> packed;
+    RC(loo_check_head(a, packed));
+    for (int b = 0; b < a.nb; ++b) {  // an output array that is given holds a pointer for every problem
+        if (a.lp && !a.lp[b]) return set_arg_err(12, "an lp_out pointer is NULL");
+        if (a.mean && !a.mean[b]) return set_arg_err(13, "a mean_out pointer is NULL");
+        if (a.var && !a.var[b]) return set_arg_err(14, "a var_out pointer is NULL");
+    }
+    std::vector<int> mine, routed;
+    split_by_path(a, env_capped(getenv("GPMI_BATCH_LOO_MAX_N"), GPMI355_BATCH_LOO_MAX_N), mine, routed);
+    RC(for_each_wave(c, mine, [&](int b) { return WaveCost{sizeof(double) * (size_t)loo_ws(a, packed, b), 0}; },  // slices, strips and partial sums count
+                     [&](const int* idx, int nw) { return run_loo_wave(c, a, packed, idx, nw); }));
+    // everything else: gp_loo / gp_loo_sum, one problem at a time, after the lock is released (as batch_impl does)
+    gd.lk.unlock();
+    for (int b : routed) {
+        const gp_points& x = a.xb(b);
+        void* val = logpdf_slot(a, b);
+        const int32_t rc = a.ks ? gp_loo_sum(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), val, a.lpb(b), a.meanb(b), a.varb(b))
+                                : gp_loo(c, &a.k[b], &x, &a.noise[b], a.mb(b), a.yb(b), val, a.lpb(b), a.meanb(b), a.varb(b));
+        if (rc < 0) return rc;
+        a.info_out[b] = rc;
+        if (rc > 0) {
+            put_result(a, b, std::numeric_limits<double>::quiet_NaN(), rc);
+            loo_fill_nan(a, b, 0);
+        }
+    }
+    return 0;
+}
+
+// gp_loo_grad_batch / gp_loo_grad_batch_sum.  A call that asks for dx runs on the single path, every problem of it: the kernels have no ∂/∂x yet.
+int32_t loo_grad_batch_impl(gp_ctx* c, LooArgs& a) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    if (a.nb < 0) return set_arg_err(2, "nb must be >= 0");
+    if (a.nb == 0) return 0;
+    std::vector<KSum> packed;
+    RC(loo_check_head(a, packed));
+    const int a_dn = a.ks ? a.arg0 + 1 : a.arg0 + 2, a_dy = a_dn + 1;
+    for (int b = 0; b < a.nb; ++b) {  // a gradient array that is given holds a pointer for every problem (dscale: wherever the problem has scales)
+        if (a.dscale && a.k[b].nscale > 0 && !a.dscale[b]) return set_arg_err(a.arg0 + 1, "a dscale_out pointer is NULL where the kernel has scales");
+        if (a.dtheta && !a.dtheta[b]) return set_arg_err(a.arg0, "a dtheta_out pointer is NULL");
+        if (a.dnoise && !a.dnoise[b]) return set_arg_err(a_dn, "a dnoise_out pointer is NULL");
+        if (a.dy && !a.dy[b]) return set_arg_err(a_dy, "a dy_out pointer is NULL");
+        if (a.dx && !a.dx[b]) return set_arg_err(a_dy + 1, "a dx_out pointer is NULL");
+    }
+    // which path serves a problem depends on that problem alone and on whether the call asks for dx
+    std::vector<int> mine, routed;
+    split_by_path(a, a.dx ? -1 : env_capped(getenv("GPMI_BATCH_LOO_GRAD_MAX_N"), GPMI355_BATCH_LOO_GRAD_MAX_N), mine, routed);
+    RC(for_each_wave(c, mine, [&](int b) { return WaveCost{sizeof(double) * (size_t)loo_ws(a, packed, b), 0}; },  // slices, both strips and tile sums count
+                     [&](const int* idx, int nw) { return run_loo_wave(c, a, packed, idx, nw); }));
+    // everything else: gp_loo_grad / gp_loo_grad_sum, one problem at a time, after the lock is released (as batch_impl does)
+    gd.lk.unlock();
+    for (int b : routed) {
+        const gp_points& x = a.xb(b);
+        void* val = logpdf_slot(a, b);
+        const int32_t rc = a.ks ? gp_loo_grad_sum(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), val, a.dtheta ? a.dtheta[b] : nullptr, a.dnb(b), a.dyb(b), a.dxb(b))
+                                : gp_loo_grad(c, &a.k[b], &x, &a.noise[b], a.mb(b), a.yb(b), val, a.dvar ? &a.dvar[b] : nullptr,
+                                              a.dscale ? a.dscale[b] : nullptr, a.dnb(b), a.dyb(b), a.dxb(b));
+        if (rc < 0) return rc;
+        a.info_out[b] = rc;
+        if (rc > 0) {
+            put_result(a, b, std::numeric_limits<double>::quiet_NaN(), rc);
+            loo_fill_nan(a, b, grad_nkp(a, packed, b));
+        }
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2243,5 +2623,43 @@ int32_t gp_logpdf_grad_batch_sum_x(gp_ctx* ctx, int32_t nb, const gp_ksum* k, in
     GradArgs a{{nb, nullptr, k, nx, x, noise, mean_or_null, ny, y, logpdf_out, info_out, nullptr, 0}, nullptr, nullptr, dtheta_out_or_null, dnoise_out_or_null, dy_out_or_null, 12, dx_out_or_null};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return gradx_batch_impl(ctx, a);
+}
+
+int32_t gp_loo_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                     const void* const* mean_or_null, int32_t ny, const void* const* y, void* value_out, int32_t* info_out,
+                     void* const* lp_out_or_null, void* const* mean_out_or_null, void* const* var_out_or_null) {
+    LooArgs a{{{nb, k, nullptr, nx, x, noise, mean_or_null, ny, y, value_out, info_out, nullptr, 0}, nullptr, nullptr, nullptr, nullptr, nullptr, 12}, false,
+              lp_out_or_null, mean_out_or_null, var_out_or_null};
+    if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
+    return loo_batch_impl(ctx, a);
+}
+
+int32_t gp_loo_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                         const void* const* mean_or_null, int32_t ny, const void* const* y, void* value_out, int32_t* info_out,
+                         void* const* lp_out_or_null, void* const* mean_out_or_null, void* const* var_out_or_null) {
+    LooArgs a{{{nb, nullptr, k, nx, x, noise, mean_or_null, ny, y, value_out, info_out, nullptr, 0}, nullptr, nullptr, nullptr, nullptr, nullptr, 12}, false,
+              lp_out_or_null, mean_out_or_null, var_out_or_null};
+    if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
+    return loo_batch_impl(ctx, a);
+}
+
+int32_t gp_loo_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                          const void* const* mean_or_null, int32_t ny, const void* const* y, void* value_out, int32_t* info_out,
+                          double* dvariance_out_or_null, double* const* dscale_out_or_null, void* const* dnoise_out_or_null,
+                          void* const* dy_out_or_null, void* const* dx_out_or_null) {
+    LooArgs a{{{nb, k, nullptr, nx, x, noise, mean_or_null, ny, y, value_out, info_out, nullptr, 0}, dvariance_out_or_null, dscale_out_or_null, nullptr,
+               dnoise_out_or_null, dy_out_or_null, 12, dx_out_or_null}, true};
+    if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
+    return loo_grad_batch_impl(ctx, a);
+}
+
+int32_t gp_loo_grad_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                              const void* const* mean_or_null, int32_t ny, const void* const* y, void* value_out, int32_t* info_out,
+                              double* const* dtheta_out_or_null, void* const* dnoise_out_or_null, void* const* dy_out_or_null,
+                              void* const* dx_out_or_null) {
+    LooArgs a{{{nb, nullptr, k, nx, x, noise, mean_or_null, ny, y, value_out, info_out, nullptr, 0}, nullptr, nullptr, dtheta_out_or_null, dnoise_out_or_null,
+               dy_out_or_null, 12, dx_out_or_null}, true};
+    if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
+    return loo_grad_batch_impl(ctx, a);
 }
 }

@@ -191,7 +191,9 @@ struct gp_ctx {
     int64_t batch_grad_problems = 0;           // problems served by the gradient kernels of gp_logpdf_grad_batch / _sum (batch.hip): read-only "batch_grad_kernel_problems"
     int64_t batch_pgrad_problems = 0;          // problems served by batch_pgrad_kernel of gp_predict_grad_batch / _sum (batch.hip): read-only "batch_pgrad_kernel_problems"
     int64_t batch_gradx_problems = 0;          // problems served by batch_gradx_kernel of gp_logpdf_grad_batch_x / _sum_x (batch.hip): read-only "batch_gradx_kernel_problems"
-    int64_t batch_joint_problems = 0;          // problems served by the kernels of gp_joint_batch / _sum (batch.hip): read-only "batch_joint_kernel_problems"
+    int64_t batch_loo_problems = 0;            // problems served by batch_loo_kernel of gp_loo_batch / _sum (batch.hip): read-only "batch_loo_kernel_problems"
+    int64_t batch_loo_grad_problems = 0;       // problems served by the kernels of gp_loo_grad_batch / _sum (batch.hip): read-only "batch_loo_grad_kernel_problems"
+    int64_t batch_joint_problems = 0;         // problems served by the kernels of gp_joint_batch / _sum (batch.hip): read-only "batch_joint_kernel_problems"
     int64_t cols_kernel_calls = 0;             // kmul launches served (gp_posterior_predict_cols; the kvec loop of single-kind D > 16 does not count): read-only "cols_kernel_calls"
     int64_t cols_kernel_splits = 0;            // workgroups along the training range of the last kmul launch (1 = no partial sums): read-only "cols_kernel_splits"
     long vfe_chunk = 0;                        // data points per streamed VFE chunk (multiple of vfe_ks); 0: automatic — 16 384 (measured best at C5) × a power of two for fewer pseudo-points (vfe.hpp)

@@ -2638,6 +2638,14 @@ int32_t gp_ctx_get_param(gp_ctx* c, const char* name, int64_t* out) {
         *out = c->batch_gradx_problems;
         return 0;
     }
+    if (!strcmp(name, "batch_loo_kernel_problems")) {  // the same for batch_loo_kernel (gp_loo_batch / _sum)
+        *out = c->batch_loo_problems;
+        return 0;
+    }
+    if (!strcmp(name, "batch_loo_grad_kernel_problems")) {  // the same for the kernels of gp_loo_grad_batch / _sum
+        *out = c->batch_loo_grad_problems;
+        return 0;
+    }
     if (!strcmp(name, "cols_kernel_calls")) {  // kmul launches served by gp_posterior_predict_cols / gp_vfe_predict_cols since the ctx was created
         *out = c->cols_kernel_calls;
         return 0;

@@ -28,7 +28,7 @@ using KernelFunctions: SqExponentialKernel, Matern12Kernel, ExponentialKernel, M
 using LinearAlgebra, FillArrays, Statistics, StatsBase, Distributions, Random
 using ChainRulesCore
 
-export HipGP, HipPosteriorGP, HipColumnsPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, loo_mean_and_var, loo_logpdf, loo_logpdf_and_grad, posterior_columns, logpdf_and_grad_columns, elbo_and_grad, HipApproxColumnsPosteriorGP, elbo_columns, approx_log_evidence_columns, elbo_and_grad_columns, objective_grad, columns_data, logpdf_batch, mean_and_var_batch, mean_and_var_grad_batch, joint_batch, mean_and_cov_batch, logpdf_heldout_batch, rand_batch, logpdf_and_grad_batch, BatchPosDefException
+export HipGP, HipPosteriorGP, HipColumnsPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, loo_mean_and_var, loo_logpdf, loo_logpdf_and_grad, loo_logpdf_batch, loo_mean_and_var_batch, loo_logpdf_and_grad_batch, posterior_columns, logpdf_and_grad_columns, elbo_and_grad, HipApproxColumnsPosteriorGP, elbo_columns, approx_log_evidence_columns, elbo_and_grad_columns, objective_grad, columns_data, logpdf_batch, mean_and_var_batch, mean_and_var_grad_batch, joint_batch, mean_and_cov_batch, logpdf_heldout_batch, rand_batch, logpdf_and_grad_batch, BatchPosDefException
 
 const libgpmi355 = get(ENV, "GPMI355_LIB", joinpath(@__DIR__, "..", "csrc", "libgpmi355.so"))
 
@@ -1032,6 +1032,148 @@ function loo_logpdf_and_grad(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}; w
     end
     return val[], (variance=dvar[], scale=dscale[1:length(a.scales)], noise=a.cn.kind == 0 ? dnoise[1] : dnoise, y=dy, mean=-dy,
         x=wrt_x ? dx : nothing)
+end
+
+# ---- leave-one-out cross-validation of many small problems in one call: gp_loo_batch / gp_loo_grad_batch and their *_sum forms -------
+# loo_terms_batch: (L, ℓ, μ, v) of loo_terms for every problem, in ONE library call per (context, eltype, single-kind / composite) group — a grid of
+# hyper-parameters scored by its leave-one-out log predictive density.  fxs, ys and on_error as in logpdf_batch; :nan leaves NaN in every output of a
+# failing problem.  Every problem must be one the ABI has a layout for.
+function loo_terms_batch(fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys; on_error::Symbol=:raise)
+    on_error in (:raise, :nan) || throw(ArgumentError("on_error must be :raise or :nan"))
+    nb = length(fxs)
+    yv = (ys isa AbstractVector{<:Real}) ? fill(ys, nb) : collect(ys)
+    length(yv) == nb || throw(DimensionMismatch("$(nb) problems but $(length(yv)) observation vectors"))
+    args = [marshal(fxs[b], eltype(yv[b])) for b in 1:nb]
+    any(a -> a === nothing, args) && throw(ArgumentError("kernel / noise form is not accelerated"))
+    T = (nb > 0 && all(a -> a.T === Float32, args)) ? Float32 : Float64
+    L = Vector{T}(undef, nb)
+    info = zeros(Int32, nb)
+    lps = Vector{Any}(nothing, nb); mus = Vector{Any}(nothing, nb); vs = Vector{Any}(nothing, nb)
+    groups = Dict{Any,Vector{Int}}()
+    for b in 1:nb
+        length(yv[b]) == length(fxs[b]) || throw(DimensionMismatch("problem $(b): length(fx) = $(length(fxs[b])) but y has $(length(yv[b])) entries"))
+        push!(get!(groups, (fxs[b].f.ctx, args[b].T, haskey(args[b], :ks)), Int[]), b)
+    end
+    for ((ctx, Tg, composite), idx) in groups
+        g = length(idx)
+        nx = all(b -> fxs[b].x === fxs[idx[1]].x, idx) ? 1 : g
+        ny = all(b -> yv[b] === yv[idx[1]], idx) ? 1 : g
+        cxs = [args[b].cx for b in idx[1:nx]]
+        cns = [args[b].cn for b in idx]
+        ybufs = [Vector{Tg}(yv[b]) for b in idx[1:ny]]
+        yptrs = Ptr{Cvoid}[pointer(v) for v in ybufs]
+        mptrs = Ptr{Cvoid}[args[b].m === nothing ? C_NULL : pointer(args[b].m) for b in idx]
+        out = Vector{Tg}(undef, g)
+        inf = zeros(Int32, g)
+        lpbufs = [Vector{Tg}(undef, length(fxs[b])) for b in idx]
+        mubufs = [Vector{Tg}(undef, length(fxs[b])) for b in idx]
+        vbufs = [Vector{Tg}(undef, length(fxs[b])) for b in idx]
+        lpptrs = Ptr{Cvoid}[pointer(v) for v in lpbufs]
+        muptrs = Ptr{Cvoid}[pointer(v) for v in mubufs]
+        vptrs = Ptr{Cvoid}[pointer(v) for v in vbufs]
+        GC.@preserve args ybufs cxs cns yptrs mptrs out inf lpbufs mubufs vbufs lpptrs muptrs vptrs begin
+            if composite
+                ks = [args[b].ks for b in idx]
+                GC.@preserve ks check(ccall((:gp_loo_batch_sum, libgpmi355), Int32,
+                    (Ptr{Cvoid}, Int32, Ptr{CKSum}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32},
+                     Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}),
+                    ctx.handle, g, ks, nx, cxs, cns, mptrs, ny, yptrs, out, inf, lpptrs, muptrs, vptrs))
+            else
+                cks = [args[b].ck for b in idx]
+                GC.@preserve cks check(ccall((:gp_loo_batch, libgpmi355), Int32,
+                    (Ptr{Cvoid}, Int32, Ptr{CKernel}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32},
+                     Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}),
+                    ctx.handle, g, cks, nx, cxs, cns, mptrs, ny, yptrs, out, inf, lpptrs, muptrs, vptrs))
+            end
+        end
+        for (j, b) in enumerate(idx)
+            L[b] = out[j]
+            info[b] = inf[j]
+            lps[b] = lpbufs[j]; mus[b] = mubufs[j]; vs[b] = vbufs[j]
+        end
+    end
+    bad = findfirst(!=(0), info)
+    (on_error === :raise && bad !== nothing) && throw(BatchPosDefException(Int(info[bad]), bad))
+    return L, lps, mus, vs
+end
+loo_mean_and_var_batch(fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys; on_error::Symbol=:raise) = loo_terms_batch(fxs, ys; on_error=on_error)[3:4]
+function loo_logpdf_batch(fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys; pointwise::Bool=false, on_error::Symbol=:raise)
+    r = loo_terms_batch(fxs, ys; on_error=on_error)
+    return pointwise ? (r[1], r[2]) : r[1]
+end
+
+# loo_logpdf_and_grad_batch(fxs, ys): value and gradient of loo_logpdf(fxs[b], ys[b]) in ONE library call per group; arguments and result as
+# logpdf_and_grad_batch, the gradients those of loo_logpdf_and_grad.  With wrt_x = true every problem of the call runs on the single path inside the
+# library (the batch kernels have no ∂/∂x yet).
+function loo_logpdf_and_grad_batch(fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys; wrt_x::Bool=false, on_error::Symbol=:raise)
+    on_error in (:raise, :nan) || throw(ArgumentError("on_error must be :raise or :nan"))
+    nb = length(fxs)
+    yv = (ys isa AbstractVector{<:Real}) ? fill(ys, nb) : collect(ys)
+    length(yv) == nb || throw(DimensionMismatch("$(nb) problems but $(length(yv)) observation vectors"))
+    args = [marshal(fxs[b], eltype(yv[b])) for b in 1:nb]
+    any(a -> a === nothing, args) && throw(ArgumentError("kernel / noise form is not accelerated"))
+    T = (nb > 0 && all(a -> a.T === Float32, args)) ? Float32 : Float64
+    L = Vector{T}(undef, nb)
+    info = zeros(Int32, nb)
+    grads = Vector{Any}(nothing, nb)
+    groups = Dict{Any,Vector{Int}}()
+    for b in 1:nb
+        length(yv[b]) == length(fxs[b]) || throw(DimensionMismatch("problem $(b): length(fx) = $(length(fxs[b])) but y has $(length(yv[b])) entries"))
+        push!(get!(groups, (fxs[b].f.ctx, args[b].T, haskey(args[b], :ks)), Int[]), b)
+    end
+    for ((ctx, Tg, composite), idx) in groups
+        g = length(idx)
+        nx = all(b -> fxs[b].x === fxs[idx[1]].x, idx) ? 1 : g
+        ny = all(b -> yv[b] === yv[idx[1]], idx) ? 1 : g
+        cxs = [args[b].cx for b in idx[1:nx]]
+        cns = [args[b].cn for b in idx]
+        ybufs = [Vector{Tg}(yv[b]) for b in idx[1:ny]]
+        yptrs = Ptr{Cvoid}[pointer(v) for v in ybufs]
+        mptrs = Ptr{Cvoid}[args[b].m === nothing ? C_NULL : pointer(args[b].m) for b in idx]
+        out = Vector{Tg}(undef, g)
+        inf = zeros(Int32, g)
+        dnbufs = [dnoise_buffer(args[b].cn, Tg, length(fxs[b])) for b in idx]
+        dybufs = [Vector{Tg}(undef, length(fxs[b])) for b in idx]
+        dnptrs = Ptr{Cvoid}[pointer(v) for v in dnbufs]
+        dyptrs = Ptr{Cvoid}[pointer(v) for v in dybufs]
+        dxbufs = wrt_x ? [similar(args[b].xbuf) for b in idx] : []   # same container layout as the inputs (Vector / D×N / N×D), one per problem
+        dxptrs = Ptr{Cvoid}[pointer(v) for v in dxbufs]
+        GC.@preserve args ybufs cxs cns yptrs mptrs out inf dnbufs dybufs dnptrs dyptrs dxbufs dxptrs begin
+            if composite
+                ks = [args[b].ks for b in idx]
+                dθs = [zeros(Float64, length(sum_theta(args[b].P, args[b].terms))) for b in idx]
+                dθptrs = Ptr{Float64}[pointer(v) for v in dθs]
+                GC.@preserve ks dθs dθptrs check(ccall((:gp_loo_grad_batch_sum, libgpmi355), Int32,
+                    (Ptr{Cvoid}, Int32, Ptr{CKSum}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32},
+                     Ptr{Ptr{Float64}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}),
+                    ctx.handle, g, ks, nx, cxs, cns, mptrs, ny, yptrs, out, inf, dθptrs, dnptrs, dyptrs, wrt_x ? pointer(dxptrs) : C_NULL))
+                for (j, b) in enumerate(idx)
+                    grads[b] = (theta=dθs[j], kernel=sum_chain(args[b].P, args[b].terms, dθs[j]), noise=cns[j].kind == 0 ? dnbufs[j][1] : dnbufs[j],
+                        y=dybufs[j], mean=-dybufs[j], x=wrt_x ? dxbufs[j] : nothing)
+                end
+            else
+                cks = [args[b].ck for b in idx]
+                dvars = zeros(Float64, g)
+                dss = [zeros(Float64, length(args[b].scales)) for b in idx]
+                dsptrs = Ptr{Float64}[isempty(v) ? Ptr{Float64}(C_NULL) : pointer(v) for v in dss]  # NULL where the kernel has no transform
+                GC.@preserve cks dvars dss dsptrs check(ccall((:gp_loo_grad_batch, libgpmi355), Int32,
+                    (Ptr{Cvoid}, Int32, Ptr{CKernel}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32},
+                     Ptr{Float64}, Ptr{Ptr{Float64}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}),
+                    ctx.handle, g, cks, nx, cxs, cns, mptrs, ny, yptrs, out, inf, dvars, dsptrs, dnptrs, dyptrs, wrt_x ? pointer(dxptrs) : C_NULL))
+                for (j, b) in enumerate(idx)
+                    grads[b] = (variance=dvars[j], scale=dss[j], noise=cns[j].kind == 0 ? dnbufs[j][1] : dnbufs[j], y=dybufs[j], mean=-dybufs[j],
+                        x=wrt_x ? dxbufs[j] : nothing)
+                end
+            end
+        end
+        for (j, b) in enumerate(idx)
+            L[b] = out[j]
+            info[b] = inf[j]
+        end
+    end
+    bad = findfirst(!=(0), info)
+    (on_error === :raise && bad !== nothing) && throw(BatchPosDefException(Int(info[bad]), bad))
+    return L, grads
 end
 
 # ---- reverse-mode rule: Zygote / any ChainRules-based AD differentiates THROUGH the ccall -----------------------------------

@@ -308,6 +308,7 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
  *                    since it was created (the problems routed to the single path do not count): which path ran, for tests and measurements
  *   "batch_gradx_kernel_problems"     read-only: the same for the input-gradient kernels of gp_logpdf_grad_batch_x / _sum_x (problems whose dx they computed)
  *   "batch_joint_kernel_problems"     read-only: the same for the kernels of gp_joint_batch / _sum
+ *   "batch_loo_kernel_problems", "batch_loo_grad_kernel_problems"   read-only: the same for the kernels of gp_loo_batch / _sum and of gp_loo_grad_batch / _sum
  *   "cols_kernel_calls", "cols_kernel_splits"   read-only: kmul launches gp_posterior_predict_cols has served on this ctx since it was created, and the workgroups
  *                    along the training range of the last of them (1 = unsplit, 0 = none yet): which path ran, for tests and measurements */
 /* The defaults above, machine-readable (single-device parameters; gp_ctx_get_param reads the same names): the test-suite asserts before
@@ -754,6 +755,61 @@ int32_t gp_logpdf_grad_batch_sum_x(gp_ctx* ctx, int32_t nb, const gp_ksum* k, in
                                    const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
                                    double* const* dtheta_out_or_null, void* const* dnoise_out_or_null, void* const* dy_out_or_null,
                                    void* const* dx_out_or_null);
+
+/* Leave-one-out cross-validation of nb independent problems in one call — the model-selection quantity a grid of hyper-parameters, a multi-start optimiser
+ * or a set of independent outputs over one x evaluates again and again; one gp_loo / gp_loo_grad call per problem otherwise.  The arguments up to y, the
+ * sharing through nx, ny ∈ {1, nb} and their checks are those of gp_logpdf_batch; per problem the semantics are those of gp_loo / gp_loo_sum and of
+ * gp_loo_grad / gp_loo_grad_sum:
+ *     value_out[b] = L_b (call dtype);  lp_out / mean_out / var_out: NULL, or nb pointers to n_b entries each (ℓ_i, μ_i, v_i; call dtype)
+ *     dvariance_out / dscale_out / dtheta_out: as in gp_logpdf_grad_batch (double; dscale_out[b] may be NULL where nscale_b = 0)
+ *     dnoise_out: nb pointers, call dtype: tr G (noise kind 0), n_b entries G_ii (kind 1), the full n_b × n_b G (kind 2 / 3);  dy_out: n_b entries −β
+ *     dx_out: nb pointers to n_b × d_b entries in the container layout of x_b, as dx_out of gp_loo_grad
+ *   Every output array is optional; an array that is given holds one non-NULL pointer per problem.  Failure is data: info_out[b] is the order of the
+ *   first leading minor that is not positive, that problem's value and every one of its outputs are NaN, the other problems are not affected.  The return
+ *   value reports argument errors only (−i, reason in gp_last_error(); nb = 0 returns 0 and touches nothing).
+ * fp64 problems with noise kind 0 / 1, D <= 16 and n_b <= GPMI355_BATCH_LOO_MAX_N (values) resp. GPMI355_BATCH_LOO_GRAD_MAX_N (gradients) run on the batch
+ * kernels (csrc/batch.hip), per wave: batch_logpdf_kernel (the fit, α always) and batch_inv_kernel (S = L⁻ᵀ in a strip beside the slice) as in
+ * gp_logpdf_grad_batch; batch_loo_kernel — one workgroup per 128 rows of the strip, one wave per row: c_i = Σ_{k ≥ i} S_ik² by lane-strided sums and a
+ * butterfly, then μ_i, v_i, ℓ_i and the tile's Σ ℓ_i — and batch_loo_sum_kernel, which adds a problem's tiles in order.  The gradient calls go on with
+ * batch_loo_z_kernel — one workgroup per 64×64 tile of the full square: Z = C⁻¹ diag(√(2a)) with C⁻¹_tile = S_i S_kᵀ by fp64 MFMA, into a second strip —
+ * batch_loo_beta_kernel — β_i = Σ_k Z_ik b_k / d_k, one wave per row — and the tile and sum kernels of gp_logpdf_grad_batch with the weights
+ * (β_i α_j + α_i β_j − (Z Zᵀ)_ij)·(i = j ? ½ : 1) in place of logpdf's (a template parameter of batch_grad_kernel; the contraction with ∂C/∂θ and the ordered
+ * sums are the same code).  No floating-point atomics, no waits between workgroups, every sum in an order the problem's size alone fixes: a problem's
+ * outputs are the same bits alone, at any position of any batch, and on repetition.  Both strips, the vectors and the per-tile sums count towards the
+ * workspace budget of a wave.  Every other problem — fp32, a dense Σy, a larger n_b or D, and EVERY problem of a call that asks for dx (the kernels have no
+ * ∂/∂x yet) — is answered inside the same call by gp_loo[_sum] / gp_loo_grad[_sum]; which path serves a problem depends on that problem alone and on
+ * whether dx is asked for.  The read-only ctx parameters "batch_loo_kernel_problems" and "batch_loo_grad_kernel_problems" count the problems the kernels
+ * served.
+ * GPMI355_BATCH_LOO_MAX_N / GPMI355_BATCH_LOO_GRAD_MAX_N: chosen by the rule that fixed the other four — each the largest multiple of 128 of the measured sweep
+ * (tools/batch_loo_profile.py, profiles/r32/batch_loo_profile.json: n = 64 … 2 048 × nb = 1, 8, 64, 512, SE, D = 3, scalar noise, all outputs except dx) at which
+ * ONE batch call beat the loop of gp_loo resp. gp_loo_grad calls in every cell with nb >= 8, a cell counting only where every sample of the batch call lies
+ * below every sample of the loop.  The nb = 8 cells decide both.  Values: 1 024 points 7.96 ms (7.96 – 7.96) against 8.47 ms (8.47 – 8.48); 1 152 points
+ * 10.49 ms (10.46 – 10.51) against 10.99 ms (10.47 – 11.20): the medians still favour the batch call, the ranges overlap, so the cell decides nothing and the
+ * limit stays at 1 024; 1 280 points 13.52 against 11.67 ms.  Gradients: 1 280 points 14.79 ms (14.77 – 14.80) against 16.95 ms (16.80 – 17.26), 1 536 points
+ * 23.42 against 19.35 ms (no size between the two was measured).  The gradient limit lies above the value limit because the opponent pays more for the
+ * gradient than the batch call does: at 1 024 points and nb = 8 the loop goes from 8.47 to 12.57 ms, the batch call from 7.96 to 8.80 ms.  At nb = 64 and
+ * 512 the batch call wins every size of the sweep (2 048 points: values 112.4 against 130.6 ms and 610 against 1 046 ms, gradients 153.1 against 187.3 ms
+ * and 1 095 against 1 527 ms; 64 points × 512: 0.39 against 124.8 ms and 0.44 against 223.8 ms).  A single problem loses to the one single call from 128
+ * points on for values (0.29 against 0.25 ms; 2 048 points: 41.6 against 2.0 ms) and from 256 points on for gradients (0.75 against 0.62 ms; 2 048 points:
+ * 42.6 against 2.9 ms), as in the other batch calls: one workgroup factors the whole problem.
+ * (The environment variables GPMI_BATCH_LOO_MAX_N and GPMI_BATCH_LOO_GRAD_MAX_N, 0 … 2 048 = what the kernels admit, read per call, override them for
+ * measurements.) */
+#define GPMI355_BATCH_LOO_MAX_N 1024
+#define GPMI355_BATCH_LOO_GRAD_MAX_N 1280
+int32_t gp_loo_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                     const void* const* mean_or_null, int32_t ny, const void* const* y, void* value_out, int32_t* info_out,
+                     void* const* lp_out_or_null, void* const* mean_out_or_null, void* const* var_out_or_null);
+int32_t gp_loo_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                         const void* const* mean_or_null, int32_t ny, const void* const* y, void* value_out, int32_t* info_out,
+                         void* const* lp_out_or_null, void* const* mean_out_or_null, void* const* var_out_or_null);
+int32_t gp_loo_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                          const void* const* mean_or_null, int32_t ny, const void* const* y, void* value_out, int32_t* info_out,
+                          double* dvariance_out_or_null, double* const* dscale_out_or_null, void* const* dnoise_out_or_null,
+                          void* const* dy_out_or_null, void* const* dx_out_or_null);
+int32_t gp_loo_grad_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx, const gp_points* x, const gp_noise* noise,
+                              const void* const* mean_or_null, int32_t ny, const void* const* y, void* value_out, int32_t* info_out,
+                              double* const* dtheta_out_or_null, void* const* dnoise_out_or_null, void* const* dy_out_or_null,
+                              void* const* dx_out_or_null);
 
 /* Sequential conditioning, posterior(fx::FiniteGP{<:PosteriorGP}, y) (src/exact_gpr_posterior.jl:46-56): the resident
  * factor of `old` is extended by the bordered-Cholesky step update_chol (src/util/common_covmat_ops.jl:38-42):
