@@ -173,6 +173,9 @@ PROTOTYPES = {
     **{f"gpd_vgrad{s}": (i32, [vp, vp, i64, i32, vp, i64, vp, i64, i32, PK, vp, vp, vp, i64, i64, vp, vp, i64, dbl, vp, vp, vp, i64]) for s in ("", "_f32")},
     **{f"gpd_ystats{s}": (i32, [vp, vp, i64, i64, vp, i64, i64, vp, vp]) for s in ("", "_f32")},
     **{f"gpd_ystats_cols{s}": (i32, [vp, vp, i64, i64, vp, i64, i32, i64, i64, vp, i64, vp]) for s in ("", "_f32")},
+    **{f"gpd_kvec{m}{s}": (i32, [vp, P, vp, i64, i64, vp, i64, i64, i32, vp, vp]) for m, P in (("", PK), ("_sum", PS)) for s in ("", "_f32")},
+    **{f"gpd_kmul{m}{s}": (i32, [vp, P, vp, i64, i64, vp, i64, i64, i32, vp, i64, i32, vp, i64]) for m, P in (("", PK), ("_sum", PS)) for s in ("", "_f32")},
+    **{f"gpd_kpgrad{m}{s}": (i32, [vp, P, vp, i64, vp, i64, i64, i32, vp, vp, i64, vp, vp, i64, i64, i64]) for m, P in (("", PK), ("_sum", PS)) for s in ("", "_f32")},
     "gpd_sync": (i32, [vp]),
     "gpd_gemm_time": (i32, [vp, C.POINTER(dbl), C.POINTER(i64)]),
     "gp_rccl_selftest": (i32, [i32, i64, C.POINTER(dbl)]),

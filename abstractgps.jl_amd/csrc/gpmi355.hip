@@ -4085,6 +4085,88 @@ static int32_t dev_ystats_cols(gp_ctx* c, const T* y, int64_t ldy, int64_t ncols
     HIPCHK(hipSetDevice(c->device));
     return launch_ystats_cols<T>(c->sm, y, ldy, ncols, by, ldb, sb, row_lo, nrows, cacc, ldc, rowss);
 }
+
+// ---- the prediction kernels on caller-supplied weights (include/gpmi355.h states each contract): K(x*, x) applied to a vector (kvec), to S columns (kmul), and
+// its derivative w.r.t. the test inputs (launch_kpgrad) — through the functions post_mean / predict_cols / predict_grad_impl and their sparse twins launch through.
+// k (a single kind) or ksum (a composite kernel): exactly one is non-NULL; on success kk is the kind's view (the identity kind for a composite kernel).
+static int32_t unit_kernel(const gp_kernel* k, const gp_ksum* ksum, int32_t d, int d_argi, bool f32, KSum& ks, gp_kernel& kk) {
+    if (d < 1) return set_arg_err(d_argi, "d must be >= 1");
+    if (ksum) {
+        RC(pack_ksum(ksum, d, 2, ks, kk));
+    } else {
+        RC(check_kernel(k, d, 2));
+        kk = *k;
+    }
+    if (kk.dtype != (f32 ? 1 : 0)) return set_arg_err(2, "kernel dtype does not match the entry point's element type");
+    return 0;
+}
+constexpr int64_t UNIT_MAX_POINTS = 1 << 30;  // one workgroup per test point (or per 64): far below the grid limit, and every index stays below 2^63
+
+template <typename T>
+static int32_t dev_kvec(gp_ctx* c, const gp_kernel* k, const gp_ksum* ksum, const T* xs, int64_t ldxs, int64_t ns, const T* x, int64_t ldx, int64_t n, int32_t d,
+                        const T* alpha, T* out) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    KSum ks;
+    gp_kernel kk{};
+    RC(unit_kernel(k, ksum, d, 9, sizeof(T) == 4, ks, kk));
+    if (ns < 1 || ns > UNIT_MAX_POINTS) return set_arg_err(5, "ns must be in 1..2^30");
+    if (!xs || ldxs < ns) return set_arg_err(3, "xs is NULL or ldxs < ns");
+    if (n < 1 || n > UNIT_MAX_POINTS) return set_arg_err(8, "n must be in 1..2^30");
+    if (!x || ldx < n) return set_arg_err(6, "x is NULL or ldx < n");
+    if (!alpha) return set_arg_err(10, "alpha is NULL");
+    if (!out) return set_arg_err(11, "out is NULL");
+    HIPCHK(hipSetDevice(c->device));
+    kvec<T>(KDesc{kk.kind, kk.variance, ksum ? &ks : nullptr}, ns, c->sm, xs, ldxs, x, ldx, d, n, alpha, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+template <typename T>
+static int32_t dev_kmul(gp_ctx* c, const gp_kernel* k, const gp_ksum* ksum, const T* xs, int64_t ldxs, int64_t ns, const T* x, int64_t ldx, int64_t n, int32_t d,
+                        const T* alpha, int64_t lda, int32_t S, T* out, int64_t ldo) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    KSum ks;
+    gp_kernel kk{};
+    RC(unit_kernel(k, ksum, d, 9, sizeof(T) == 4, ks, kk));
+    if (ns < 1 || ns > UNIT_MAX_POINTS) return set_arg_err(5, "ns must be in 1..2^30");
+    if (!xs || ldxs < round_up(ns, 128)) return set_arg_err(3, "xs is NULL or ldxs < ns rounded up to 128");
+    if (n < 1 || n > UNIT_MAX_POINTS) return set_arg_err(8, "n must be in 1..2^30");
+    if (!x || ldx < n) return set_arg_err(6, "x is NULL or ldx < n");
+    if (!alpha || lda < n) return set_arg_err(10, "alpha is NULL or lda < n");
+    if (S < 1 || S > 128) return set_arg_err(12, "S must be in 1..128");
+    if (!out || ldo < ns) return set_arg_err(13, "out is NULL or ldo < ns");
+    HIPCHK(hipSetDevice(c->device));
+    DevBufs bufs(c);
+    DrainOnExit drain{c->sm};  // the partial slices' block goes back to the cache when this returns
+    return kmul<T>(c, bufs, KDesc{kk.kind, kk.variance, ksum ? &ks : nullptr}, ns, c->sm, xs, ldxs, x, ldx, d, n, alpha, lda, S, out, ldo);
+}
+
+template <typename T>
+static int32_t dev_kpgrad(gp_ctx* c, const gp_kernel* k, const gp_ksum* ksum, const T* xs, int64_t ldxs, const T* x, int64_t ldx, int64_t n, int32_t d,
+                          const T* alpha, const T* W, int64_t ldw, double* gm, double* gv, int64_t ldg, int64_t j0, int64_t cnt) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    KSum ks;
+    gp_kernel kk{};
+    RC(unit_kernel(k, ksum, d, 8, sizeof(T) == 4, ks, kk));
+    if (j0 < 0 || j0 > UNIT_MAX_POINTS) return set_arg_err(15, "j0 must be in 0..2^30");
+    if (cnt < 1 || cnt > UNIT_MAX_POINTS) return set_arg_err(16, "cnt must be in 1..2^30");
+    if (!xs || ldxs < j0 + cnt) return set_arg_err(3, "xs is NULL or ldxs < j0 + cnt");
+    if (n < 1 || n > UNIT_MAX_POINTS) return set_arg_err(7, "n must be in 1..2^30");
+    if (!x || ldx < n) return set_arg_err(5, "x is NULL or ldx < n");
+    if (!gm && !gv) return set_arg_err(12, "gm and gv are both NULL");
+    if (gm && !alpha) return set_arg_err(9, "alpha is needed with gm");
+    if (gv && (!W || ldw < n)) return set_arg_err(10, "W is needed with gv, ldw >= n");
+    if (ldg < j0 + cnt) return set_arg_err(14, "ldg < j0 + cnt");
+    HIPCHK(hipSetDevice(c->device));
+    DevBufs bufs(c);
+    DevScales sc;
+    DrainOnExit drain{c->sm};  // the scales' block goes back to the cache when this returns
+    RC(sc.stage(bufs, kk.nscale, kk.scale, c->sm));
+    return launch_kpgrad<T>(KDesc{kk.kind, kk.variance, ksum ? &ks : nullptr}, kk.nscale, sc.ptr(), cnt, c->sm, xs, ldxs, x, ldx, d, n, alpha, W, ldw, gm, gv, ldg, j0);
+}
 }  // extern "C++"
 
 int32_t gpd_assemble(gp_ctx* c, const gp_kernel* k, const double* x_dev, int64_t n_valid, int64_t n_pad, int32_t d,
@@ -4201,6 +4283,57 @@ int32_t gpd_ystats_cols(gp_ctx* c, const double* y, int64_t ldy, int64_t ncols, 
 int32_t gpd_ystats_cols_f32(gp_ctx* c, const float* y, int64_t ldy, int64_t ncols, const float* by, int64_t ldb, int32_t sb, int64_t row_lo, int64_t nrows,
                             double* cacc, int64_t ldc, double* rowss) {
     return dev_ystats_cols<float>(c, y, ldy, ncols, by, ldb, sb, row_lo, nrows, cacc, ldc, rowss);
+}
+
+int32_t gpd_kvec(gp_ctx* c, const gp_kernel* k, const double* xs, int64_t ldxs, int64_t ns, const double* x, int64_t ldx, int64_t n, int32_t d, const double* alpha,
+                 double* out) {
+    return dev_kvec<double>(c, k, nullptr, xs, ldxs, ns, x, ldx, n, d, alpha, out);
+}
+int32_t gpd_kvec_f32(gp_ctx* c, const gp_kernel* k, const float* xs, int64_t ldxs, int64_t ns, const float* x, int64_t ldx, int64_t n, int32_t d, const float* alpha,
+                     float* out) {
+    return dev_kvec<float>(c, k, nullptr, xs, ldxs, ns, x, ldx, n, d, alpha, out);
+}
+int32_t gpd_kvec_sum(gp_ctx* c, const gp_ksum* k, const double* xs, int64_t ldxs, int64_t ns, const double* x, int64_t ldx, int64_t n, int32_t d, const double* alpha,
+                     double* out) {
+    return dev_kvec<double>(c, nullptr, k, xs, ldxs, ns, x, ldx, n, d, alpha, out);
+}
+int32_t gpd_kvec_sum_f32(gp_ctx* c, const gp_ksum* k, const float* xs, int64_t ldxs, int64_t ns, const float* x, int64_t ldx, int64_t n, int32_t d, const float* alpha,
+                         float* out) {
+    return dev_kvec<float>(c, nullptr, k, xs, ldxs, ns, x, ldx, n, d, alpha, out);
+}
+
+int32_t gpd_kmul(gp_ctx* c, const gp_kernel* k, const double* xs, int64_t ldxs, int64_t ns, const double* x, int64_t ldx, int64_t n, int32_t d, const double* alpha,
+                 int64_t lda, int32_t S, double* out, int64_t ldo) {
+    return dev_kmul<double>(c, k, nullptr, xs, ldxs, ns, x, ldx, n, d, alpha, lda, S, out, ldo);
+}
+int32_t gpd_kmul_f32(gp_ctx* c, const gp_kernel* k, const float* xs, int64_t ldxs, int64_t ns, const float* x, int64_t ldx, int64_t n, int32_t d, const float* alpha,
+                     int64_t lda, int32_t S, float* out, int64_t ldo) {
+    return dev_kmul<float>(c, k, nullptr, xs, ldxs, ns, x, ldx, n, d, alpha, lda, S, out, ldo);
+}
+int32_t gpd_kmul_sum(gp_ctx* c, const gp_ksum* k, const double* xs, int64_t ldxs, int64_t ns, const double* x, int64_t ldx, int64_t n, int32_t d, const double* alpha,
+                     int64_t lda, int32_t S, double* out, int64_t ldo) {
+    return dev_kmul<double>(c, nullptr, k, xs, ldxs, ns, x, ldx, n, d, alpha, lda, S, out, ldo);
+}
+int32_t gpd_kmul_sum_f32(gp_ctx* c, const gp_ksum* k, const float* xs, int64_t ldxs, int64_t ns, const float* x, int64_t ldx, int64_t n, int32_t d, const float* alpha,
+                         int64_t lda, int32_t S, float* out, int64_t ldo) {
+    return dev_kmul<float>(c, nullptr, k, xs, ldxs, ns, x, ldx, n, d, alpha, lda, S, out, ldo);
+}
+
+int32_t gpd_kpgrad(gp_ctx* c, const gp_kernel* k, const double* xs, int64_t ldxs, const double* x, int64_t ldx, int64_t n, int32_t d, const double* alpha,
+                   const double* w, int64_t ldw, double* gm, double* gv, int64_t ldg, int64_t j0, int64_t cnt) {
+    return dev_kpgrad<double>(c, k, nullptr, xs, ldxs, x, ldx, n, d, alpha, w, ldw, gm, gv, ldg, j0, cnt);
+}
+int32_t gpd_kpgrad_f32(gp_ctx* c, const gp_kernel* k, const float* xs, int64_t ldxs, const float* x, int64_t ldx, int64_t n, int32_t d, const float* alpha,
+                       const float* w, int64_t ldw, double* gm, double* gv, int64_t ldg, int64_t j0, int64_t cnt) {
+    return dev_kpgrad<float>(c, k, nullptr, xs, ldxs, x, ldx, n, d, alpha, w, ldw, gm, gv, ldg, j0, cnt);
+}
+int32_t gpd_kpgrad_sum(gp_ctx* c, const gp_ksum* k, const double* xs, int64_t ldxs, const double* x, int64_t ldx, int64_t n, int32_t d, const double* alpha,
+                       const double* w, int64_t ldw, double* gm, double* gv, int64_t ldg, int64_t j0, int64_t cnt) {
+    return dev_kpgrad<double>(c, nullptr, k, xs, ldxs, x, ldx, n, d, alpha, w, ldw, gm, gv, ldg, j0, cnt);
+}
+int32_t gpd_kpgrad_sum_f32(gp_ctx* c, const gp_ksum* k, const float* xs, int64_t ldxs, const float* x, int64_t ldx, int64_t n, int32_t d, const float* alpha,
+                           const float* w, int64_t ldw, double* gm, double* gv, int64_t ldg, int64_t j0, int64_t cnt) {
+    return dev_kpgrad<float>(c, nullptr, k, xs, ldxs, x, ldx, n, d, alpha, w, ldw, gm, gv, ldg, j0, cnt);
 }
 
 int32_t gpd_gemm_time(gp_ctx* c, double* ms_out, int64_t* launches_out) {

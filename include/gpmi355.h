@@ -1091,6 +1091,71 @@ int32_t gpd_ystats_cols(gp_ctx* ctx, const double* y, int64_t ldy, int64_t ncols
                         double* cacc, int64_t ldc, double* rowss);
 int32_t gpd_ystats_cols_f32(gp_ctx* ctx, const float* y, int64_t ldy, int64_t ncols, const float* by, int64_t ldb, int32_t sb, int64_t row_lo, int64_t nrows,
                             double* cacc, int64_t ldc, double* rowss);
+
+/* ---- the prediction kernels, on caller-supplied weights (tests/test_gpu_units_predict.py; reference and bounds: tests/predict_units_ref.py) ----
+ * Every number read from a posterior passes through one of three kernel families that apply the cross-kernel K(x*, x) to weights without storing K.  In a
+ * prediction the weights are alpha = C^-1 (y - m) or rows of C^-1 k_j and carry the conditioning of C; here they are the caller's.  Each entry launches through the
+ * function production launches through (csrc/gpmi355.hip kvec / kmul / launch_kpgrad): a shape gets the kernel instance here that it gets in gp_posterior_predict*,
+ * gp_posterior_predict_cols, gp_posterior_predict_grad and their gp_vfe_* twins.  T = double, or float in the _f32 twins.  All inputs are dimension-major
+ * ([d][ld]: dimension p of point i at [p * ld + i]).  A single kind (gpd_kvec, gpd_kmul, gpd_kpgrad; kind 0..3, nscale in {0, 1, d}, dtype = T's) takes inputs
+ * ALREADY multiplied by the scales (u = s * x; k->scale is read by gpd_kpgrad alone, on the HOST); a composite kernel (the _sum forms) takes the RAW inputs, D <= 16.
+ * No atomics anywhere: two calls return the same bits.  "Not read" below: the location need not even hold a value — a NaN there cannot reach an output.
+ *
+ * gpd_kvec:  out[j] = sum_{i<n} k(xs_j, x_i) alpha[i]  for j < ns   (kvec_kernel<T>; composite: kvec_sum_kernel<T, 1|4|16> for D <= 1 / 4 / 16).  One workgroup per
+ *   test point; the product variance * kappa * alpha[i] is formed in T, the sum is fp64 (a chain of ceil(n / 256) terms per thread, wave shuffles, four LDS
+ *   partials) and rounded to T once.  Any D for a single kind.
+ *   xs  [d][ldxs], ldxs >= ns: columns < ns used, columns >= ns not read.      x  [d][ldx], ldx >= n: columns < n used, columns >= n not read.
+ *   alpha  n entries used, entries >= n not read.      out  ns entries OVERWRITTEN, entries >= ns untouched.      Only queues (gpd_sync).
+ *   Refused: kernel (-2), xs / ldxs (-3), ns (-5), x / ldx (-6), n (-8), d < 1 (-9), alpha NULL (-10), out NULL (-11).
+ * gpd_kmul:  out[c][j] = sum_{i<n} k(xs_j, x_i) alpha[c][i]  for c < S <= 128, j < ns   (kmul_kernel<T, 4|16> for D <= 4 / 16, composite kmul_sum_kernel<T, 1|4|16>):
+ *   64 test points per workgroup, the training points in strips of 32, kappa from the VALU straight into the 16x16x4 MFMA, accumulation in T.  With few test points
+ *   the strips are dealt out to several workgroups (the rule reads n and ns only; smallest n that splits: 225), whose partial slices — in a block from the ctx's
+ *   cache — kmul_reduce_kernel adds in the order 0, 1, 2, ...: a column's bits depend on (n, ns, xs, x, its own alpha) and on nothing else, S and the other columns
+ *   included.  A single kind with D > 16 takes S gpd_kvec launches instead.  The ctx counters "cols_kernel_calls" / "cols_kernel_splits" move as in production.
+ *   xs  [d][ldxs], ldxs >= ns rounded up to 128 (what production stages): columns < ns used; columns [ns, ns rounded up to 64) are READ, NEVER USED (a workgroup
+ *       loads the inputs of all its 64 test rows; rows >= ns feed MFMA output rows that are not written).  With D > 16 they are not read.
+ *   x   [d][ldx], ldx >= n: columns < n used, columns >= n not read (both kappa and alpha are replaced by 0 for training indices >= n).
+ *   alpha  [S][lda], lda >= n: alpha[c][i], i < n used, the rest not read.      out  [S][ldo], ldo >= ns: out[c][j], c < S, j < ns OVERWRITTEN; rows >= S and
+ *   columns >= ns untouched.      DRAINS the ctx stream before it returns (the partial slices' block goes back to the cache).
+ *   Refused: kernel (-2), xs / ldxs (-3), ns (-5), x / ldx (-6), n (-8), d < 1 (-9), alpha / lda (-10), S outside 1..128 (-12), out / ldo (-13).
+ * gpd_kpgrad:  for the cnt test points j = j0 .. j0 + cnt - 1, every dimension p < d:
+ *       gm[p][j] =      sum_{i<n} alpha[i]    dk(xs_j, x_i)/dxs_jp         (NULL: not computed, alpha not read)
+ *       gv[p][j] = -2 * sum_{i<n} w[j - j0][i] dk(xs_j, x_i)/dxs_jp         (NULL: not computed, w not read)
+ *   with dk/dxs_p = 2 s_p variance kappa'(d^2) (u*_p - u_p) for a single kind (kpgrad_kernel<T>, once per 16 dimensions; s_p = 1, scale[0] or scale[p]; Matern12 at
+ *   d = 0 takes kappa' = 0: a test point on a training point gets exactly no contribution from it) and ksum_gradx for a composite kernel (kpgrad_sum_kernel<T,
+ *   1|4|16>).  d^2, kappa' and the difference u*_p - u_p are formed in T; the products and sums are fp64 whatever T is, one thread writes each entry.
+ *   xs  [d][ldxs], ldxs >= j0 + cnt: columns [j0, j0 + cnt) used, the others not read.      x  [d][ldx], ldx >= n: columns >= n not read.
+ *   alpha  n entries.      w  cnt rows of leading dimension ldw >= n, row b for test point j0 + b; columns >= n not read.
+ *   gm, gv  doubles [d][ldg], ldg >= j0 + cnt: columns [j0, j0 + cnt) OVERWRITTEN, all others untouched.  At least one of them.
+ *   Stages k->scale and DRAINS the ctx stream before it returns.
+ *   Refused: kernel (-2), xs / ldxs (-3), x / ldx (-5), n (-7), d < 1 (-8), alpha NULL with gm (-9), w NULL or ldw < n with gv (-10), gm and gv both NULL (-12),
+ *   ldg (-14), j0 (-15), cnt (-16).
+ * n, ns, cnt <= 2^30. */
+int32_t gpd_kvec(gp_ctx* ctx, const gp_kernel* k, const double* xs, int64_t ldxs, int64_t ns, const double* x, int64_t ldx, int64_t n, int32_t d, const double* alpha,
+                 double* out);
+int32_t gpd_kvec_f32(gp_ctx* ctx, const gp_kernel* k, const float* xs, int64_t ldxs, int64_t ns, const float* x, int64_t ldx, int64_t n, int32_t d, const float* alpha,
+                     float* out);
+int32_t gpd_kvec_sum(gp_ctx* ctx, const gp_ksum* k, const double* xs, int64_t ldxs, int64_t ns, const double* x, int64_t ldx, int64_t n, int32_t d,
+                     const double* alpha, double* out);
+int32_t gpd_kvec_sum_f32(gp_ctx* ctx, const gp_ksum* k, const float* xs, int64_t ldxs, int64_t ns, const float* x, int64_t ldx, int64_t n, int32_t d,
+                         const float* alpha, float* out);
+int32_t gpd_kmul(gp_ctx* ctx, const gp_kernel* k, const double* xs, int64_t ldxs, int64_t ns, const double* x, int64_t ldx, int64_t n, int32_t d, const double* alpha,
+                 int64_t lda, int32_t S, double* out, int64_t ldo);
+int32_t gpd_kmul_f32(gp_ctx* ctx, const gp_kernel* k, const float* xs, int64_t ldxs, int64_t ns, const float* x, int64_t ldx, int64_t n, int32_t d, const float* alpha,
+                     int64_t lda, int32_t S, float* out, int64_t ldo);
+int32_t gpd_kmul_sum(gp_ctx* ctx, const gp_ksum* k, const double* xs, int64_t ldxs, int64_t ns, const double* x, int64_t ldx, int64_t n, int32_t d,
+                     const double* alpha, int64_t lda, int32_t S, double* out, int64_t ldo);
+int32_t gpd_kmul_sum_f32(gp_ctx* ctx, const gp_ksum* k, const float* xs, int64_t ldxs, int64_t ns, const float* x, int64_t ldx, int64_t n, int32_t d,
+                         const float* alpha, int64_t lda, int32_t S, float* out, int64_t ldo);
+int32_t gpd_kpgrad(gp_ctx* ctx, const gp_kernel* k, const double* xs, int64_t ldxs, const double* x, int64_t ldx, int64_t n, int32_t d, const double* alpha_or_null,
+                   const double* w_or_null, int64_t ldw, double* gm_or_null, double* gv_or_null, int64_t ldg, int64_t j0, int64_t cnt);
+int32_t gpd_kpgrad_f32(gp_ctx* ctx, const gp_kernel* k, const float* xs, int64_t ldxs, const float* x, int64_t ldx, int64_t n, int32_t d, const float* alpha_or_null,
+                       const float* w_or_null, int64_t ldw, double* gm_or_null, double* gv_or_null, int64_t ldg, int64_t j0, int64_t cnt);
+int32_t gpd_kpgrad_sum(gp_ctx* ctx, const gp_ksum* k, const double* xs, int64_t ldxs, const double* x, int64_t ldx, int64_t n, int32_t d,
+                       const double* alpha_or_null, const double* w_or_null, int64_t ldw, double* gm_or_null, double* gv_or_null, int64_t ldg, int64_t j0, int64_t cnt);
+int32_t gpd_kpgrad_sum_f32(gp_ctx* ctx, const gp_ksum* k, const float* xs, int64_t ldxs, const float* x, int64_t ldx, int64_t n, int32_t d,
+                           const float* alpha_or_null, const float* w_or_null, int64_t ldw, double* gm_or_null, double* gv_or_null, int64_t ldg, int64_t j0,
+                           int64_t cnt);
 /* With parameter "time_kernels" = 1 every gpd_gemm_nt launch is bracketed by HIP events on the ctx
  * stream.  This synchronises the stream, returns the summed launch durations (ms) and the launch count since the
  * previous call, and clears the records (the caller knows the algorithmic flops of its own launches). */

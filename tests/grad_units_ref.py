@@ -227,6 +227,43 @@ def rect_reference(kind, variance, nscale, scale, xr, xc, cm, explicit_w, rs, bv
 PI = LD("3.14159265358979323846264338327950288")
 
 
+def composite_parts(rr, s, a, t, u):
+    """The factors of k = σ₁²·Periodic(r)·RQ(α)∘Scale(s) (+ σ₂²·White) at the differences t (a list of D longdouble arrays of one shape) and their relative errors
+    when evaluated in a type of unit roundoff u — what composite_reference's docstring derives; shared with tests/predict_units_ref.py.  rr, s, a: longdouble."""
+    D = len(t)
+    eps_d = gamma(D + 2, u)
+    eps_d2 = eps_d + 2 * u
+    sn = [np.sin(PI * tp) for tp in t]
+    dsn = [PI * np.abs(tp) * u + 4 * u * np.abs(sp) for tp, sp in zip(t, sn)]
+    v = [sp / rp for sp, rp in zip(sn, rr)]
+    dv = [dp / rp + u * np.abs(vp) for dp, rp, vp in zip(dsn, rr, v)]
+    acc = sum(vp * vp for vp in v)
+    dacc = sum(2 * np.abs(vp) * dvp for vp, dvp in zip(v, dv)) + eps_d * acc
+    kP = np.exp(-acc / 2)
+    dP = dacc / 2 + 6 * u
+    r2 = sum(tp * tp for tp in t)
+    eq = r2 == 0
+    q = s * s * r2 / (2 * a)
+    L = np.log1p(q)
+    kR = np.exp(-a * L)
+    dR = a * q * (eps_d2 + u) / (1 + q) + 5 * u * a * L + 6 * u
+    dPR = dP + dR
+    dk = -kR / (2 * (1 + q))
+    h = q / (1 + q) - L
+    return dict(eps_d=eps_d, eps_d2=eps_d2, sn=sn, dsn=dsn, kP=kP, kR=kR, dPR=dPR, r2=r2, eq=eq, q=q, L=L, dk=dk, h=h)
+
+
+def composite_dt(c_, s1, rr, s, t, p, u):
+    """∂k/∂t_p = A + B of that kernel (A: through the Periodic factor, B: through RQ) with the per-element errors EA, EB (composite_reference's docstring)"""
+    kP, kR, dPR, q, eps_d2, dk = (c_[k] for k in ("kP", "kR", "dPR", "q", "eps_d2", "dk"))
+    s2p = np.sin(2 * PI * t[p])
+    A = -s1 * kR * kP * (PI / 2) * s2p / rr[p] ** 2
+    B = s1 * kP * 2 * dk * s * s * t[p]
+    EA = np.abs(A) * dPR + s1 * kR * kP * (PI / 2) / rr[p] ** 2 * (2 * PI * np.abs(t[p]) * u + 4 * u * np.abs(s2p))
+    EB = np.abs(B) * (dPR + q * eps_d2 / (1 + q) + u)
+    return A, B, EA, EB
+
+
 def composite_reference(s1, r, s, a, s2, x, ci, alpha, n, np_pad):
     """gpd_grad_contract_sum for k = σ₁²·Periodic(r)·RQ(α)∘Scale(s) + σ₂²·White on RAW inputs x ([d][>= n], T-valued; every θ value must be exactly representable in T: the
     device casts θ to T where it evaluates a factor).  θ order as pack_ksum lays it out: [σ₁², r_0 … r_{D−1}, s, α, σ₂²].  dict of Out: theta ([D + 4]), gx ([d][n]), dn, g1.
@@ -261,26 +298,9 @@ def composite_reference(s1, r, s, a, s2, x, ci, alpha, n, np_pad):
     s1, s, a, s2 = LD(s1), LD(s), LD(a), LD(s2)
     rr = [LD(v) for v in r]
     T = np_pad // 128
-    eps_d = gamma(D + 2, u)
-    eps_d2 = eps_d + 2 * u
     t = [xw[p][:, None] - xw[p][None, :] for p in range(D)]
-    sn = [np.sin(PI * tp) for tp in t]
-    dsn = [PI * np.abs(tp) * u + 4 * u * np.abs(sp) for tp, sp in zip(t, sn)]
-    v = [sp / rp for sp, rp in zip(sn, rr)]
-    dv = [dp / rp + u * np.abs(vp) for dp, rp, vp in zip(dsn, rr, v)]
-    acc = sum(vp * vp for vp in v)
-    dacc = sum(2 * np.abs(vp) * dvp for vp, dvp in zip(v, dv)) + eps_d * acc
-    kP = np.exp(-acc / 2)
-    dP = dacc / 2 + 6 * u
-    r2 = sum(tp * tp for tp in t)
-    eq = r2 == 0
-    q = s * s * r2 / (2 * a)
-    L = np.log1p(q)
-    kR = np.exp(-a * L)
-    dR = a * q * (eps_d2 + u) / (1 + q) + 5 * u * a * L + 6 * u
-    dPR = dP + dR
-    dk = -kR / (2 * (1 + q))
-    h = q / (1 + q) - L
+    c_ = composite_parts(rr, s, a, t, u)
+    eps_d, eps_d2, sn, dsn, kP, kR, dPR, r2, eq, q, L, dk, h = (c_[k] for k in ("eps_d", "eps_d2", "sn", "dsn", "kP", "kR", "dPR", "r2", "eq", "q", "L", "dk", "h"))
     m_h, m_x = 64 + 6 + 3 + T * (T + 1) // 2 + 16, 128 + 1 + T + 16
 
     def out(F, E, Wv, Wa, m, natom, axis=None):
@@ -300,11 +320,7 @@ def composite_reference(s1, r, s, a, s2, x, ci, alpha, n, np_pad):
     res = {"theta": Out(np.stack([o.val for o in th]), np.stack([o.abs for o in th]), np.stack([o.bound for o in th]), nt)}
     gx = []
     for p in range(D):  # row j of gx sums over i: with t = x_j − x_i here (rows = j), the sign flips twice — ∂k/∂t is odd — so gx[p][j] = Σ_i W_ji ∂k/∂t_p(x_j − x_i)
-        s2p = np.sin(2 * PI * t[p])
-        A = -s1 * kR * kP * (PI / 2) * s2p / rr[p] ** 2
-        B = s1 * kP * 2 * dk * s * s * t[p]
-        EA = np.abs(A) * dPR + s1 * kR * kP * (PI / 2) / rr[p] ** 2 * (2 * PI * np.abs(t[p]) * u + 4 * u * np.abs(s2p))
-        EB = np.abs(B) * (dPR + q * eps_d2 / (1 + q) + u)
+        A, B, EA, EB = composite_dt(c_, s1, rr, s, t, p, u)
         ab = (Wfa * (np.abs(A) + np.abs(B))).sum(1)
         gx.append(Out((Wf * (A + B)).sum(1), ab, (Wfa * (EA + EB)).sum(1) + (2 * U64 + gamma(m_x, U64)) * ab, T))
     res["gx"] = Out(np.stack([o.val for o in gx]), np.stack([o.abs for o in gx]), np.stack([o.bound for o in gx]), T)

@@ -84,6 +84,9 @@ GPD_GRAD = lambda A, k: {  # noqa: E731  (the gradient contractions and the spar
     "grad_contract": ["h", k, A, 288, A, A, 200, 256, 3, A, A, None],
     "vgrad": ["h", A, 288, 1, A, 256, A, 256, 3, k, None, None, None, 200, 100, A, A, 256, 1.0, None, None, None, 0],
     "ystats": ["h", A, 288, 100, A, 0, 4, A, A], "ystats_cols": ["h", A, 288, 128, A, 288, 1, 0, 16, A, 288, A]}
+GPD_PRED = lambda A, k: {  # noqa: E731  (the prediction kernels on caller-supplied weights: 200 test points (ldxs = 256), 100 training points (ldx = 256), D = 3; 4 columns)
+    "kvec": ["h", k, A, 256, 200, A, 256, 100, 3, A, A], "kmul": ["h", k, A, 256, 200, A, 256, 100, 3, A, 128, 4, A, 256],
+    "kpgrad": ["h", k, A, 256, A, 256, 100, 3, A, A, 128, A, A, 256, 0, 200]}
 BASE = {
     "gp_ctx_create": ["@new", 0, None], "gp_ctx_set_param": ["h", "name", -1], "gp_ctx_get_param": ["h", "name", "@i64"], "gp_ctx_trim": ["h"],
     "gp_get_timings": ["h", "@tm"],
@@ -109,6 +112,8 @@ BASE = {
     **{f"gpd_{n}": a for n, a in GPD("A64", "@k64").items()}, **{f"gpd_{n}_f32": a for n, a in GPD("A32", "@k32").items()},
     **{f"gpd_{n}": a for n, a in GPD_GRAD("A64", "@k64").items()}, **{f"gpd_{n}_f32": a for n, a in GPD_GRAD("A32", "@k32").items()},
     "gpd_grad_contract_sum": GPD_GRAD("A64", "@ks")["grad_contract"], "gpd_grad_contract_sum_f32": GPD_GRAD("A32", "@ks32")["grad_contract"],
+    **{f"gpd_{n}": a for n, a in GPD_PRED("A64", "@k64").items()}, **{f"gpd_{n}_f32": a for n, a in GPD_PRED("A32", "@k32").items()},
+    **{f"gpd_{n}_sum": a for n, a in GPD_PRED("A64", "@ks").items()}, **{f"gpd_{n}_sum_f32": a for n, a in GPD_PRED("A32", "@ks32").items()},
 }
 
 CTX, POST, VFE = "not a live gp_ctx", "not a live gp_post", "not a live gp_vfe"
@@ -226,6 +231,21 @@ TABLE = [
     ("gpd_ystats_cols", 7, 9, -7, "sb must be 1..8"), ("gpd_ystats_cols_f32", 7, 0, -7, "sb must be 1..8"), ("gpd_ystats_cols", 9, 8, -9, "nrows a multiple of 16"),
     ("gpd_ystats_cols_f32", 4, 32, -4, "ncols must be a positive multiple"), ("gpd_ystats_cols", 4, 48, -4, "ncols must be a positive multiple"),
     ("gpd_ystats_cols", 11, 8, -10, "cacc is NULL or ldc < row_lo + nrows"),
+    # the prediction kernels on caller-supplied weights: a NULL / never-issued ctx for all twelve, then the arguments
+    *[(f"gpd_{n}{m}{s}", 1, bad, -1, CTX) for n in GPD_PRED(0, 0) for m in ("", "_sum") for s in ("", "_f32") for bad in (None, 0xDEADBEEF)],
+    *[(f"gpd_{n}{s}", 9 if n != "kpgrad" else 8, 0, -9 if n != "kpgrad" else -8, "d must be >= 1") for n in GPD_PRED(0, 0) for s in ("", "_f32", "_sum", "_sum_f32")],
+    ("gpd_kvec", 2, "@kk", -2, "nscale must be 0, 1 or D"), ("gpd_kvec", 2, "@k32", -2, "kernel dtype does not match"), ("gpd_kvec_sum_f32", 2, "@ks", -2, "kernel dtype does not match"),
+    ("gpd_kvec", 4, 199, -3, "xs is NULL or ldxs < ns"), ("gpd_kvec_f32", 3, None, -3, "xs is NULL or ldxs < ns"), ("gpd_kvec", 5, 0, -5, "ns must be in 1..2^30"),
+    ("gpd_kvec_sum", 7, 99, -6, "x is NULL or ldx < n"), ("gpd_kvec_f32", 8, 0, -8, "n must be in 1..2^30"), ("gpd_kvec", 10, None, -10, "alpha is NULL"),
+    ("gpd_kvec_f32", 11, None, -11, "out is NULL"), ("gpd_kvec_sum", 9, 17, -2, "composite kernel: D must be <= 16"),
+    ("gpd_kmul", 4, 200, -3, "ldxs < ns rounded up to 128"), ("gpd_kmul_f32", 4, 255, -3, "ldxs < ns rounded up to 128"), ("gpd_kmul", 6, None, -6, "x is NULL or ldx < n"),
+    ("gpd_kmul", 11, 99, -10, "alpha is NULL or lda < n"), ("gpd_kmul_sum", 10, None, -10, "alpha is NULL or lda < n"), ("gpd_kmul", 12, 0, -12, "S must be in 1..128"),
+    ("gpd_kmul_f32", 12, 129, -12, "S must be in 1..128"), ("gpd_kmul_sum_f32", 14, 199, -13, "out is NULL or ldo < ns"), ("gpd_kmul", 13, None, -13, "out is NULL or ldo < ns"),
+    ("gpd_kmul_sum", 9, 17, -2, "composite kernel: D must be <= 16"), ("gpd_kmul", 2, "@k64_kind4", -2, "kernel kind must be 0..3"),
+    ("gpd_kpgrad", 4, 199, -3, "xs is NULL or ldxs < j0 + cnt"), ("gpd_kpgrad_f32", 6, 99, -5, "x is NULL or ldx < n"), ("gpd_kpgrad", 7, 0, -7, "n must be in 1..2^30"),
+    ("gpd_kpgrad", 9, None, -9, "alpha is needed with gm"), ("gpd_kpgrad_sum", 10, None, -10, "W is needed with gv"), ("gpd_kpgrad_f32", 11, 99, -10, "W is needed with gv"),
+    ("gpd_kpgrad", 14, 199, -14, "ldg < j0 + cnt"), ("gpd_kpgrad_sum_f32", 15, -1, -15, "j0 must be in 0..2^30"), ("gpd_kpgrad", 16, 0, -16, "cnt must be in 1..2^30"),
+    ("gpd_kpgrad", 15, 57, -3, "xs is NULL or ldxs < j0 + cnt"), ("gpd_kpgrad", 2, "@kk_scale_null", -2, "nscale must be 0, 1 or D"),
 ]
 
 
