@@ -1291,6 +1291,18 @@ struct BatchArgs {
     void* ab(int b) const { return alpha_out ? alpha_out[b] : nullptr; }
 };
 
+// The leading arguments of every entry point.  The kernel array goes to the field of its type, so the two entry points of a pair build their arguments with
+// the same text and differ in the type of `k` alone.
+void set_kernels(BatchArgs& a, const gp_kernel* k) { a.k = k; }
+void set_kernels(BatchArgs& a, const gp_ksum* ks) { a.ks = ks; }
+template <class K>
+BatchArgs base_args(int32_t nb, const K* k, int32_t nx, const gp_points* x, const gp_noise* noise, const void* const* mean, int32_t ny, const void* const* y,
+                    void* logpdf_out, int32_t* info_out, void* const* alpha_out = nullptr) {
+    BatchArgs a{nb, nullptr, nullptr, nx, x, noise, mean, ny, y, logpdf_out, info_out, alpha_out, 0};
+    set_kernels(a, k);
+    return a;
+}
+
 // a size limit of the header; the environment variable read at the call site overrides it for measurements (0 … what the kernels admit)
 long env_capped(const char* env, long deflt) { return std::max(0L, std::min<long>(env ? atol(env) : deflt, BATCH_KERNEL_MAX_N)); }
 void fill_nan(void* out, int dtype, long n) {
@@ -1437,33 +1449,34 @@ struct WaveMem {
     }
 };
 
-// The launches of a wave on the ctx's main stream, the <SUM> dispatch of each kernel in one place (ks: the call brought composite kernels).
-int32_t launch_fit(const WaveMem& m, bool ks, int nw) {
-    hipLaunchKernelGGL(ks ? batch_logpdf_kernel<true> : batch_logpdf_kernel<false>, dim3((unsigned)nw), dim3(NT), 0, m.c->sm, m.in, m.ws, m.res, nw);
+// A table the kernels of a wave read from its packed input: the host vector, its place behind whatever L.off has reached (the order of the place() calls is
+// the order of the tables in the buffer), its copy into the staging buffer and its address on the device, from entry `first` on.
+template <class T> struct Table {
+    static_assert(sizeof(T) % 8 == 0, "the tables are packed behind double data");
+    std::vector<T> v;
+    long off = -1;
+    void place(WaveLayout& L) { off = take(L.off, (long)(v.size() * sizeof(T) / 8)); }
+    void fill(const WaveMem& m) const {
+        if (!v.empty()) std::memcpy(m.hin + off, v.data(), v.size() * sizeof(T));
+    }
+    const T* dev(const WaveMem& m, size_t first = 0) const { return reinterpret_cast<const T*>(m.in + off) + first; }
+};
+
+// One launch of a wave on the ctx's main stream.  Every kernel takes (in, ws, res, nw) in front; W and R are double or const double as the kernel declares
+// them, and the trailing arguments are converted to the kernel's own parameter types (hipLaunchKernelGGL deduces them twice and wants them equal).
+template <class W, class R, class... P, class... A>
+int32_t launch(const WaveMem& m, void (*kern)(const double*, W*, R*, int, P...), size_t grid, unsigned block, int nw, A... rest) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(block), 0, m.c->sm, m.in, static_cast<W*>(m.ws), static_cast<R*>(m.res), nw, static_cast<P>(rest)...);
     HIPCHK(hipGetLastError());
     return 0;
 }
-int32_t launch_predict(const WaveMem& m, bool ks, int nw, const BatchTile* tiles, size_t ntiles) {
-    hipLaunchKernelGGL(ks ? batch_predict_kernel<true> : batch_predict_kernel<false>, dim3((unsigned)ntiles), dim3(NT), 0, m.c->sm, m.in, m.ws, m.res, nw, tiles);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int32_t launch_pgrad(const WaveMem& m, bool ks, int nw, const BatchTile* tiles, const PGradTile* ptiles, size_t ntiles) {
-    hipLaunchKernelGGL(ks ? batch_pgrad_kernel<true> : batch_pgrad_kernel<false>, dim3((unsigned)ntiles), dim3(ks ? PGNT_SUM : NT), 0, m.c->sm, m.in, m.ws, m.res, nw, tiles, ptiles);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
+// The <SUM> dispatch of each kernel stands in one place (ks: the call brought composite kernels): here for the two kernels that several waves launch, at the
+// one launch site of every other.
+int32_t launch_fit(const WaveMem& m, bool ks, int nw) { return launch(m, ks ? batch_logpdf_kernel<true> : batch_logpdf_kernel<false>, nw, NT, nw); }
 // lps: the LooProb table of a gp_loo_grad_batch wave (the weights of the leave-one-out objective), or NULL (those of logpdf)
-int32_t launch_grad(const WaveMem& m, bool ks, int nw, const GradProb* gps, const GradTile* tiles, size_t ntiles, const LooProb* lps = nullptr) {
+int32_t launch_grad(const WaveMem& m, bool ks, int nw, const GradProb* gps, const Table<GradTile>& tiles, const LooProb* lps = nullptr) {
     auto kern = lps ? (ks ? batch_grad_kernel<true, true> : batch_grad_kernel<false, true>) : (ks ? batch_grad_kernel<true, false> : batch_grad_kernel<false, false>);
-    hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(GNT), 0, m.c->sm, m.in, m.ws, m.res, nw, gps, tiles, lps);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-int32_t launch_gradx(const WaveMem& m, bool ks, int nw, const GradProb* gps, const GradXProb* gxs, const GradTile* tiles, size_t ntiles) {
-    hipLaunchKernelGGL(ks ? batch_gradx_kernel<true> : batch_gradx_kernel<false>, dim3((unsigned)ntiles), dim3(GNT), 0, m.c->sm, m.in, m.ws, (const double*)m.res, nw, gps, gxs, tiles);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch(m, kern, tiles.v.size(), GNT, nw, gps, tiles.dev(m), lps);
 }
 
 // one launch: the problems idx[0..nw) of the call, all taken by the kernel.  Caller holds the ctx lock.
@@ -1549,6 +1562,24 @@ template <class Cost, class Run> int32_t for_each_wave(gp_ctx* c, const std::vec
     return 0;
 }
 
+// The single path's fit of problem b, by the kind of the call's descriptors (the routed loops: their calls take the ctx lock themselves).
+int32_t routed_fit(gp_ctx* c, const BatchArgs& a, int b, gp_post** post, void* alpha, void* lp) {
+    return a.ks ? gp_posterior_fit_sum(c, &a.ks[b], &a.xb(b), &a.noise[b], a.mb(b), a.yb(b), post, alpha, lp)
+                : gp_posterior_fit(c, &a.k[b], &a.xb(b), &a.noise[b], a.mb(b), a.yb(b), post, alpha, lp);
+}
+
+// What every routed loop does with the status of problem b's single-path calls: an error ends the batch call; a failed factorisation is the problem's info,
+// NaN in its logpdf and, by nan_fill(), in the family's other outputs.
+template <class Fill> int32_t routed_done(const BatchArgs& a, int b, int32_t rc, Fill&& nan_fill) {
+    if (rc < 0) return rc;
+    a.info_out[b] = rc;
+    if (rc > 0) {
+        put_result(a, b, std::numeric_limits<double>::quiet_NaN(), rc);
+        nan_fill();
+    }
+    return 0;
+}
+
 int32_t batch_impl(gp_ctx* c, BatchArgs& a) {
     Guard gd(c);
     if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
@@ -1572,19 +1603,13 @@ int32_t batch_impl(gp_ctx* c, BatchArgs& a) {
         void* lp = logpdf_slot(a, b);
         if (a.ab(b)) {
             gp_post* post = nullptr;
-            rc = a.ks ? gp_posterior_fit_sum(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), &post, a.ab(b), lp)
-                      : gp_posterior_fit(c, &a.k[b], &x, &a.noise[b], a.mb(b), a.yb(b), &post, a.ab(b), lp);
+            rc = routed_fit(c, a, b, &post, a.ab(b), lp);
             if (post) (void)gp_posterior_free(post);
         } else {
             rc = a.ks ? gp_logpdf_sum(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), x.n, 1, lp)
                       : gp_logpdf(c, &a.k[b], &x, &a.noise[b], a.mb(b), a.yb(b), x.n, 1, lp);
         }
-        if (rc < 0) return rc;
-        a.info_out[b] = rc;
-        if (rc > 0) {
-            put_result(a, b, std::numeric_limits<double>::quiet_NaN(), rc);
-            fill_nan(a.ab(b), a.dtype, x.n);
-        }
+        RC(routed_done(a, b, rc, [&] { fill_nan(a.ab(b), a.dtype, x.n); }));
     }
     return 0;
 }
@@ -1608,6 +1633,127 @@ struct PredictArgs : BatchArgs {
     bool want_dvar() const { return grad && (what & 2) && dvar_out; }
 };
 
+// nxs and xs of a call over test points (arguments 10 and 11 in every family)
+int32_t check_test_head(const PredictArgs& a) {
+    if (a.nxs != 1 && a.nxs != a.nb) return set_arg_err(10, "nxs must be 1 (one xs shared by every problem) or nb");
+    if (!a.xs) return set_arg_err(11, "test points array is NULL");
+    return 0;
+}
+// An array of per-problem pointers of such a call: a problem with test points needs its entry where the call asks for the array (wanted) and brought it.
+struct PointerArray {
+    const void* const* arr;
+    bool wanted;
+    int arg;
+    const char* msg;
+};
+// every problem's test points, Σy* (gp_joint_batch: argument 13, else NULL) and entries of `arrays`, in that order
+int32_t check_test_points(const PredictArgs& a, const gp_noise* noise_xs, std::initializer_list<PointerArray> arrays) {
+    for (int b = 0; b < a.nb; ++b) {
+        const gp_points& xs = a.xsb(b);
+        if (xs.n < 0) return set_arg_err(11, "xs: n must be >= 0");
+        if (xs.n == 0) continue;  // no test points: nothing of this problem's xs or outputs is touched
+        RC(check_points(&xs, 11));
+        if (xs.d != a.xb(b).d) return set_arg_err(11, "xs has a different D than the training inputs");
+        if (noise_xs) RC(check_noise(&noise_xs[b], 13, true));
+        for (const PointerArray& p : arrays)
+            if (p.wanted && p.arr && !p.arr[b]) return set_arg_err(p.arg, p.msg);
+    }
+    return 0;
+}
+
+// The test points of a wave and the predict launches over them, for gp_predict_batch, gp_predict_grad_batch and gp_joint_batch: behind the fit's input the
+// points (dimension-major, a shared set once) and the table of tiles of TP points; behind its results mean and variance of every problem.
+struct TestPoints {
+    std::vector<long> xs_off, mean_off, var_off;
+    Table<BatchTile> tiles;
+    std::vector<size_t> launch_end;  // a predict launch closes at BATCH_PRED_TILES tiles
+    SharedOnce xso, xsf;             // layout, filling
+    bool want_var;                   // the variance, and with it a strip of TP rows per tile
+    TestPoints(const PredictArgs& a, int nw, bool want_var_)
+        : xs_off((size_t)nw, -1), mean_off((size_t)nw, -1), var_off((size_t)nw, -1), xso{a.nxs == 1}, xsf{a.nxs == 1}, want_var(want_var_) {}
+
+    // offsets of the problems with test points, in the order of idx; rest(t) lays out what else problem t brings or returns
+    template <class Rest> void place(const PredictArgs& a, const int* idx, int nw, bool want_mean, WaveLayout& L, Rest&& rest) {
+        for (int t = 0; t < nw; ++t) {
+            const gp_points& xs = a.xsb(idx[t]);
+            if (xs.n == 0) continue;
+            xs_off[t] = xso.place(L.off, (long)xs.d * xs.n);
+            if (want_mean) mean_off[t] = take(L.roff, xs.n);
+            if (want_var) var_off[t] = take(L.roff, xs.n);
+            rest(t);
+        }
+    }
+
+    // The tiles, the widest problems first, their strips behind L.ws, and the table's place.  share: the launches of a wave run one after the other on one
+    // stream, so every launch group starts over at the same strips, and a group also closes when its strips would pass the workspace budget
+    // (gp_predict_batch, gp_predict_grad_batch).  Otherwise every tile keeps a strip of its own and after(t, first) — first: the strip of the problem's first
+    // tile — may take what follows the problem's strips (gp_joint_batch, whose later kernels read them).
+    template <class After> void tile(const PredictArgs& a, const int* idx, int nw, bool share, WaveLayout& L, After&& after) {
+        const long base = L.ws;
+        long top = base;
+        size_t launch_begin = 0;
+        for (int s = 0; s < nw; ++s) {
+            const int t = L.order[s];
+            const long ns = a.xsb(idx[t]).n, strip = want_var ? (long)TP * L.pr[t].ld : 0, first = L.ws;
+            if (ns == 0) continue;
+            for (long row0 = 0; row0 < ns; row0 += TP) {
+                const size_t open = tiles.v.size() - launch_begin;
+                if (open > 0 && (open == BATCH_PRED_TILES || (share && sizeof(double) * (size_t)(L.ws + strip) > BATCH_WS_BYTES))) {
+                    launch_end.push_back(tiles.v.size());
+                    launch_begin = tiles.v.size();
+                    if (share) L.ws = base;
+                }
+                tiles.v.push_back(BatchTile{xs_off[t], take(L.ws, strip), mean_off[t], var_off[t], L.pos[t], (int)ns, (int)row0, (int)std::min<long>(TP, ns - row0)});
+                top = std::max(top, L.ws);
+            }
+            if (!share) after(t, first);
+            top = std::max(top, L.ws);
+        }
+        if (tiles.v.size() > launch_begin) launch_end.push_back(tiles.v.size());
+        L.ws = top;
+        tiles.place(L);
+    }
+
+    void fill(const PredictArgs& a, const int* idx, int nw, const WaveMem& m) {
+        for (int t = 0; t < nw; ++t) {
+            const gp_points& xs = a.xsb(idx[t]);
+            if (xs.n > 0 && xsf.claim()) pack_points(xs, m.hin + xs_off[t]);
+        }
+        tiles.fill(m);
+    }
+
+    // The predict launches.  ptiles (gp_predict_grad_batch, else NULL): batch_pgrad_kernel directly behind each of them, over the same tiles — the strips are
+    // shared by the launch groups, so the gradients of a group follow its own predict launch and precede the next one.
+    int32_t launch_groups(const WaveMem& m, bool ks, int nw, const Table<PGradTile>* ptiles) const {
+        size_t t0 = 0;
+        for (size_t t1 : launch_end) {
+            RC(launch(m, ks ? batch_predict_kernel<true> : batch_predict_kernel<false>, t1 - t0, NT, nw, tiles.dev(m, t0)));
+            if (ptiles) RC(launch(m, ks ? batch_pgrad_kernel<true> : batch_pgrad_kernel<false>, t1 - t0, ks ? PGNT_SUM : NT, nw, tiles.dev(m, t0), ptiles->dev(m, t0)));
+            t0 = t1;
+        }
+        return 0;
+    }
+
+    // the mean of problem b (the t-th of the wave) to the caller, the prior mean at the test points added
+    void put_mean(const PredictArgs& a, int b, int t, const double* hout) const {
+        double* mo = (double*)a.out_b(a.mean_out, 1, b);
+        if (!mo) return;
+        const double* pm = (const double*)a.pmb(b);
+        for (long j = 0; j < a.xsb(b).n; ++j) mo[j] = pm ? pm[j] + hout[mean_off[t] + j] : hout[mean_off[t] + j];
+    }
+};
+
+// The S = L⁻ᵀ strip of the s-th descriptor of a wave, beside the slices, and the tiles of 128 rows batch_inv_kernel fills it by; the launch over the tiles of
+// every problem of the wave that has one.
+void place_s_strip(WaveLayout& L, int s, GradProb& g, Table<GradTile>& itiles) {
+    const BatchProb& p = L.pr[L.order[s]];
+    g.s_off = take(L.ws, (long)p.np * p.ld);
+    for (int r0 = 0; r0 < p.np; r0 += TP) itiles.v.push_back(GradTile{s, r0 / TP, 0, 0});
+}
+int32_t launch_inv(const WaveMem& m, int nw, const Table<GradProb>& gp, const Table<GradTile>& itiles) {
+    return itiles.v.empty() ? 0 : launch(m, batch_inv_kernel, itiles.v.size(), NT, nw, gp.dev(m), itiles.dev(m));
+}
+
 long predict_strip(const PredictArgs& a, long n) { return (a.what & 2) ? (long)TP * batch_ld(batch_np(n)) : 0; }  // the mean alone needs no strip
 
 // the S strip of a problem that has a variance-side gradient and test points (beside its slice, as in a gradient wave)
@@ -1620,84 +1766,39 @@ long pgrad_s(const PredictArgs& a, int b) {
 int32_t run_predict_wave(gp_ctx* c, const PredictArgs& a, const std::vector<KSum>& packed, const int* idx, int nw) {
     WaveLayout L;
     wave_layout(a, idx, nw, [&](int b) { return (a.what & 1) && a.xsb(b).n > 0; }, L);
-    // behind the fit's input: the test points (dimension-major, a shared set once), then the tile table; behind its results: mean and var of every problem
-    std::vector<long> xs_off((size_t)nw, -1), mean_off((size_t)nw, -1), var_off((size_t)nw, -1), dmean_off((size_t)nw, -1), dvar_off((size_t)nw, -1);
-    SharedOnce xso{a.nxs == 1}, xsf{a.nxs == 1};  // layout, filling
-    for (int t = 0; t < nw; ++t) {
+    TestPoints tp(a, nw, (a.what & 2) != 0);
+    std::vector<long> dmean_off((size_t)nw, -1), dvar_off((size_t)nw, -1);
+    tp.place(a, idx, nw, (a.what & 1) != 0, L, [&](int t) {
         const gp_points& xs = a.xsb(idx[t]);
-        if (xs.n == 0) continue;
-        xs_off[t] = xso.place(L.off, (long)xs.d * xs.n);
-        if (a.what & 1) mean_off[t] = take(L.roff, xs.n);
-        if (a.what & 2) var_off[t] = take(L.roff, xs.n);
         if (a.want_dmean()) dmean_off[t] = take(L.roff, (long)xs.d * xs.n);
         if (a.want_dvar()) dvar_off[t] = take(L.roff, (long)xs.d * xs.n);
-    }
-    // a gradient call: the S strips beside the slices, their tiles of 128 rows and the table batch_inv_kernel reads (built as run_grad_wave builds them)
-    std::vector<GradProb> gp(a.grad ? (size_t)nw : 0, GradProb{-1, -1, -1, -1, 0, 0});
-    std::vector<GradTile> itiles;
-    for (int s = 0; s < nw && a.grad; ++s) {
-        const int t = L.order[s];
-        const BatchProb& p = L.pr[t];
-        if (pgrad_s(a, idx[t]) == 0) continue;
-        gp[s].s_off = take(L.ws, (long)p.np * p.ld);
-        for (int r0 = 0; r0 < p.np; r0 += TP) itiles.push_back(GradTile{s, r0 / TP, 0, 0});
-    }
-    // tiles of TP test points, the widest problems first; a launch closes at BATCH_PRED_TILES tiles or when its strips would pass the workspace budget
-    std::vector<BatchTile> tiles;
-    std::vector<PGradTile> ptiles;
-    std::vector<size_t> launch_end;
-    long cur = L.ws, ws_top = L.ws;
-    size_t launch_begin = 0;
-    for (int s = 0; s < nw; ++s) {
-        const int t = L.order[s];
-        const long ns = a.xsb(idx[t]).n, strip = predict_strip(a, L.pr[t].n);
-        for (long row0 = 0; row0 < ns; row0 += TP) {
-            if (tiles.size() > launch_begin &&
-                (tiles.size() - launch_begin == BATCH_PRED_TILES || sizeof(double) * (size_t)(cur + strip) > BATCH_WS_BYTES)) {
-                launch_end.push_back(tiles.size());
-                launch_begin = tiles.size();
-                cur = L.ws;  // the launches of a wave run one after the other on one stream: they share the strips
-            }
-            BatchTile tl{xs_off[t], cur, mean_off[t], var_off[t], L.pos[t], (int)ns, (int)row0, (int)std::min<long>(TP, ns - row0)};
-            tiles.push_back(tl);
-            if (a.grad) ptiles.push_back(PGradTile{gp[s].s_off, dmean_off[t], dvar_off[t]});
-            cur += strip;
-            ws_top = std::max(ws_top, cur);
-        }
-    }
-    if (tiles.size() > launch_begin) launch_end.push_back(tiles.size());
-    const long tile_off = take(L.off, (long)(tiles.size() * sizeof(BatchTile) / 8));
-    const long pt_off = take(L.off, (long)(ptiles.size() * sizeof(PGradTile) / 8));
-    const long gp_off = take(L.off, (long)(gp.size() * sizeof(GradProb) / 8));
-    const long it_off = take(L.off, (long)(itiles.size() * sizeof(GradTile) / 8));
+    });
+    // a gradient call: the table batch_inv_kernel reads, with an S strip for the problems that need one, and a PGradTile beside every tile
+    Table<GradProb> gp;
+    Table<GradTile> itiles;
+    Table<PGradTile> ptiles;
+    gp.v.assign(a.grad ? (size_t)nw : 0, GradProb{-1, -1, -1, -1, 0, 0});
+    for (int s = 0; s < nw && a.grad; ++s)
+        if (pgrad_s(a, idx[L.order[s]]) != 0) place_s_strip(L, s, gp.v[s], itiles);
+    tp.tile(a, idx, nw, true, L, [](int, long) {});
+    if (a.grad)
+        for (const BatchTile& tl : tp.tiles.v) ptiles.v.push_back(PGradTile{gp.v[tl.prob].s_off, dmean_off[L.order[tl.prob]], dvar_off[L.order[tl.prob]]});
+    ptiles.place(L);
+    gp.place(L);
+    itiles.place(L);
 
     WaveMem m(c);
-    RC(m.alloc(L.off, ws_top, L.roff));
+    RC(m.alloc(L.off, L.ws, L.roff));
     wave_fill(a, packed, idx, nw, L, m.hin);
-    for (int t = 0; t < nw; ++t) {
-        const gp_points& xs = a.xsb(idx[t]);
-        if (xs.n > 0 && xsf.claim()) pack_points(xs, m.hin + xs_off[t]);
-    }
-    if (!tiles.empty()) std::memcpy(m.hin + tile_off, tiles.data(), tiles.size() * sizeof(BatchTile));
-    if (!ptiles.empty()) std::memcpy(m.hin + pt_off, ptiles.data(), ptiles.size() * sizeof(PGradTile));
-    if (!gp.empty()) std::memcpy(m.hin + gp_off, gp.data(), gp.size() * sizeof(GradProb));
-    if (!itiles.empty()) std::memcpy(m.hin + it_off, itiles.data(), itiles.size() * sizeof(GradTile));
+    tp.fill(a, idx, nw, m);
+    ptiles.fill(m);
+    gp.fill(m);
+    itiles.fill(m);
     RC(run_drained(c, [&]() -> int32_t {
         RC(m.upload());
         RC(launch_fit(m, a.ks != nullptr, nw));
-        if (!itiles.empty()) {
-            hipLaunchKernelGGL(batch_inv_kernel, dim3((unsigned)itiles.size()), dim3(NT), 0, c->sm, m.in, m.ws, (const double*)m.res, nw,
-                               reinterpret_cast<const GradProb*>(m.in + gp_off), reinterpret_cast<const GradTile*>(m.in + it_off));
-            HIPCHK(hipGetLastError());
-        }
-        size_t t0 = 0;
-        for (size_t t1 : launch_end) {
-            const BatchTile* tl = reinterpret_cast<const BatchTile*>(m.in + tile_off) + t0;
-            RC(launch_predict(m, a.ks != nullptr, nw, tl, t1 - t0));
-            // the strips are shared by the launch groups: the gradients of a group follow its own predict launch and precede the next one
-            if (a.want_dmean() || a.want_dvar()) RC(launch_pgrad(m, a.ks != nullptr, nw, tl, reinterpret_cast<const PGradTile*>(m.in + pt_off) + t0, t1 - t0));
-            t0 = t1;
-        }
+        RC(launch_inv(m, nw, gp, itiles));
+        RC(tp.launch_groups(m, a.ks != nullptr, nw, a.want_dmean() || a.want_dvar() ? &ptiles : nullptr));
         return m.download_and_sync();
     }));
     const double* hout = m.hout;
@@ -1707,11 +1808,8 @@ int32_t run_predict_wave(gp_ctx* c, const PredictArgs& a, const std::vector<KSum
         put_result(a, b, hout[t], (int32_t)hout[nw + t]);
         const long ns = a.xsb(b).n;
         if (ns == 0) continue;
-        if (double* mo = (double*)a.out_b(a.mean_out, 1, b)) {
-            const double* pm = (const double*)a.pmb(b);
-            for (long j = 0; j < ns; ++j) mo[j] = pm ? pm[j] + hout[mean_off[t] + j] : hout[mean_off[t] + j];
-        }
-        if (void* vo = a.out_b(a.var_out, 2, b)) std::memcpy(vo, hout + var_off[t], sizeof(double) * (size_t)ns);
+        tp.put_mean(a, b, t, hout);
+        if (void* vo = a.out_b(a.var_out, 2, b)) std::memcpy(vo, hout + tp.var_off[t], sizeof(double) * (size_t)ns);
         const gp_points& q = a.xsb(b);  // the gradients lie dimension-major [d][ns] in the result buffer: into the container layout of xs
         if (dmean_off[t] >= 0) grad_to_layout<double>(q.layout, ns, q.d, hout + dmean_off[t], ns, a.dmean_out[b]);
         if (dvar_off[t] >= 0) grad_to_layout<double>(q.layout, ns, q.d, hout + dvar_off[t], ns, a.dvar_out[b]);
@@ -1725,23 +1823,14 @@ int32_t predict_batch_impl(gp_ctx* c, PredictArgs& a) {
     if (a.nb < 0) return set_arg_err(2, "nb must be >= 0");
     if (a.nb == 0) return 0;
     RC(check_batch_head(a));
-    if (a.nxs != 1 && a.nxs != a.nb) return set_arg_err(10, "nxs must be 1 (one xs shared by every problem) or nb");
-    if (!a.xs) return set_arg_err(11, "test points array is NULL");
+    RC(check_test_head(a));
     if (a.what <= 0 || a.what > 3) return set_arg_err(13, "what must be a combination of 1|2");
     if ((a.what & 1) && !a.mean_out) return set_arg_err(14, "mean_out is NULL");
     if ((a.what & 2) && !a.var_out) return set_arg_err(15, "var_out is NULL");
     if (!a.info_out) return set_arg_err(17, "info_out is NULL");
     std::vector<KSum> packed;
     RC(check_batch_problems(a, packed));
-    for (int b = 0; b < a.nb; ++b) {
-        const gp_points& xs = a.xsb(b);
-        if (xs.n < 0) return set_arg_err(11, "xs: n must be >= 0");
-        if (xs.n == 0) continue;  // no test points: nothing of this problem's xs or outputs is touched
-        RC(check_points(&xs, 11));
-        if (xs.d != a.xb(b).d) return set_arg_err(11, "xs has a different D than the training inputs");
-        if ((a.what & 1) && !a.mean_out[b]) return set_arg_err(14, "a mean_out pointer is NULL");
-        if ((a.what & 2) && !a.var_out[b]) return set_arg_err(15, "a var_out pointer is NULL");
-    }
+    RC(check_test_points(a, nullptr, {{a.mean_out, (a.what & 1) != 0, 14, "a mean_out pointer is NULL"}, {a.var_out, (a.what & 2) != 0, 15, "a var_out pointer is NULL"}}));
     std::vector<int> mine, routed;
     split_by_path(a, env_capped(getenv("GPMI_BATCH_MAX_N"), GPMI355_BATCH_MAX_N), mine, routed);
     // the slices of a wave and its widest strip fit in the budget: the predict launches of a wave run one after the other and share the strips
@@ -1753,24 +1842,17 @@ int32_t predict_batch_impl(gp_ctx* c, PredictArgs& a) {
     // everything else: fit, predict and free on the single path, one problem at a time, after the lock is released (as batch_impl does)
     gd.lk.unlock();
     for (int b : routed) {
-        const gp_points& x = a.xb(b);
         const gp_points& xs = a.xsb(b);
         gp_post* post = nullptr;
-        void* lp = logpdf_slot(a, b);
-        int32_t rc = a.ks ? gp_posterior_fit_sum(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), &post, nullptr, lp)
-                          : gp_posterior_fit(c, &a.k[b], &x, &a.noise[b], a.mb(b), a.yb(b), &post, nullptr, lp);
+        int32_t rc = routed_fit(c, a, b, &post, nullptr, logpdf_slot(a, b));
         if (rc == 0 && xs.n > 0)
             rc = gp_posterior_predict(post, &xs, a.pmb(b), a.what, (a.what & 1) ? a.mean_out[b] : nullptr, (a.what & 2) ? a.var_out[b] : nullptr, nullptr);
         if (post) (void)gp_posterior_free(post);
-        if (rc < 0) return rc;
-        a.info_out[b] = rc;
-        if (rc > 0) {
-            put_result(a, b, std::numeric_limits<double>::quiet_NaN(), rc);
-            if (xs.n > 0) {
-                if (a.what & 1) fill_nan(a.mean_out[b], a.dtype, xs.n);
-                if (a.what & 2) fill_nan(a.var_out[b], a.dtype, xs.n);
-            }
-        }
+        RC(routed_done(a, b, rc, [&] {
+            if (xs.n <= 0) return;
+            if (a.what & 1) fill_nan(a.mean_out[b], a.dtype, xs.n);
+            if (a.what & 2) fill_nan(a.var_out[b], a.dtype, xs.n);
+        }));
     }
     return 0;
 }
@@ -1793,25 +1875,16 @@ int32_t predict_grad_batch_impl(gp_ctx* c, PredictArgs& a) {
     if (a.nb < 0) return set_arg_err(2, "nb must be >= 0");
     if (a.nb == 0) return 0;
     RC(check_batch_head(a));
-    if (a.nxs != 1 && a.nxs != a.nb) return set_arg_err(10, "nxs must be 1 (one xs shared by every problem) or nb");
-    if (!a.xs) return set_arg_err(11, "test points array is NULL");
+    RC(check_test_head(a));
     if (a.what <= 0 || a.what > 3) return set_arg_err(13, "what must be a combination of 1|2");
     if ((a.what & 1) && !a.mean_out && !a.dmean_out) return set_arg_err(14, "mean_out and dmean_out are both NULL");
     if ((a.what & 2) && !a.var_out && !a.dvar_out) return set_arg_err(15, "var_out and dvar_out are both NULL");
     if (!a.info_out) return set_arg_err(19, "info_out is NULL");
     std::vector<KSum> packed;
     RC(check_batch_problems(a, packed));
-    for (int b = 0; b < a.nb; ++b) {
-        const gp_points& xs = a.xsb(b);
-        if (xs.n < 0) return set_arg_err(11, "xs: n must be >= 0");
-        if (xs.n == 0) continue;  // no test points: nothing of this problem's xs or outputs is touched
-        RC(check_points(&xs, 11));
-        if (xs.d != a.xb(b).d) return set_arg_err(11, "xs has a different D than the training inputs");
-        if ((a.what & 1) && a.mean_out && !a.mean_out[b]) return set_arg_err(14, "a mean_out pointer is NULL");
-        if ((a.what & 2) && a.var_out && !a.var_out[b]) return set_arg_err(15, "a var_out pointer is NULL");
-        if ((a.what & 1) && a.dmean_out && !a.dmean_out[b]) return set_arg_err(16, "a dmean_out pointer is NULL");
-        if ((a.what & 2) && a.dvar_out && !a.dvar_out[b]) return set_arg_err(17, "a dvar_out pointer is NULL");
-    }
+    const bool m1 = (a.what & 1) != 0, m2 = (a.what & 2) != 0;
+    RC(check_test_points(a, nullptr, {{a.mean_out, m1, 14, "a mean_out pointer is NULL"}, {a.var_out, m2, 15, "a var_out pointer is NULL"},
+                                      {a.dmean_out, m1, 16, "a dmean_out pointer is NULL"}, {a.dvar_out, m2, 17, "a dvar_out pointer is NULL"}}));
     std::vector<int> mine, routed;
     split_by_path(a, env_capped(getenv("GPMI_BATCH_PGRAD_MAX_N"), GPMI355_BATCH_PGRAD_MAX_N), mine, routed);
     // The slices and S strips of a wave fit in the budget beside PGRAD_GROUP_TILES predict strips of its widest problem (W overwrites V in the strip: no second
@@ -1826,22 +1899,14 @@ int32_t predict_grad_batch_impl(gp_ctx* c, PredictArgs& a) {
     // everything else: fit, predict_grad and free on the single path, one problem at a time, after the lock is released (as batch_impl does)
     gd.lk.unlock();
     for (int b : routed) {
-        const gp_points& x = a.xb(b);
         const gp_points& xs = a.xsb(b);
         gp_post* post = nullptr;
-        void* lp = logpdf_slot(a, b);
-        int32_t rc = a.ks ? gp_posterior_fit_sum(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), &post, nullptr, lp)
-                          : gp_posterior_fit(c, &a.k[b], &x, &a.noise[b], a.mb(b), a.yb(b), &post, nullptr, lp);
+        int32_t rc = routed_fit(c, a, b, &post, nullptr, logpdf_slot(a, b));
         if (rc == 0 && xs.n > 0)
             rc = gp_posterior_predict_grad(post, &xs, a.pmb(b), a.what, a.out_b(a.mean_out, 1, b), a.out_b(a.var_out, 2, b), a.out_b(a.dmean_out, 1, b),
                                            a.out_b(a.dvar_out, 2, b));
         if (post) (void)gp_posterior_free(post);
-        if (rc < 0) return rc;
-        a.info_out[b] = rc;
-        if (rc > 0) {
-            put_result(a, b, std::numeric_limits<double>::quiet_NaN(), rc);
-            pgrad_fill_nan(a, b);
-        }
+        RC(routed_done(a, b, rc, [&] { pgrad_fill_nan(a, b); }));
     }
     return 0;
 }
@@ -1859,14 +1924,13 @@ struct JointArgs : PredictArgs {  // what: 1 mean | 4 latent covariance | 8 held
     bool want_fact() const { return (what & 24) != 0; }
     bool want_mean() const { return (what & 25) != 0; }  // the held-out logpdf and the samples are built on it
     long draws(int b) const { return (what & 16) ? xsb(b).n * (long)nsamp : 0; }
-    void* out_ptr(void* const* arr, int bit, int b) const { return (arr && (what & bit)) ? arr[b] : nullptr; }
     size_t esize() const { return dtype == 0 ? 8 : 4; }
 };
 
 // NaN in the held-out logpdf and the samples of problem b (a joint covariance that is not positive definite, or a failed fit)
 void joint_fill_nan(const JointArgs& a, int b) {
     if (a.what & 8) put(a.hlogpdf_out, a.dtype, b, std::numeric_limits<double>::quiet_NaN());
-    fill_nan(a.out_ptr(a.samples_out, 16, b), a.dtype, a.draws(b));
+    fill_nan(a.out_b(a.samples_out, 16, b), a.dtype, a.draws(b));
 }
 
 // workspace doubles of problem b beyond its slice: every predict strip (they stay alive for batch_jcov_kernel) and the joint slice
@@ -1882,23 +1946,18 @@ int32_t run_joint_wave(gp_ctx* c, const JointArgs& a, const std::vector<KSum>& p
     const bool need_v = a.what != 1;
     WaveLayout L;
     wave_layout(a, idx, nw, [&](int b) { return a.want_mean() && a.xsb(b).n > 0; }, L);
-    std::vector<long> xs_off((size_t)nw, -1), mean_off((size_t)nw, -1), var_off((size_t)nw, -1);
+    TestPoints tp(a, nw, need_v);  // the variance the predict kernel computes on its way to V: scratch
     std::vector<int> jp_of((size_t)nw, -1);
-    std::vector<JointProb> jp;
-    SharedOnce xso{a.nxs == 1}, xsf{a.nxs == 1};  // layout, filling
-    for (int t = 0; t < nw; ++t) {
+    Table<JointProb> jp;
+    Table<GradTile> jtiles;
+    tp.place(a, idx, nw, a.want_mean(), L, [&](int t) {
+        if (!need_v) return;
         const int b = idx[t];
-        const gp_points& xs = a.xsb(b);
-        const long ns = xs.n;
-        if (ns == 0) continue;
-        xs_off[t] = xso.place(L.off, (long)xs.d * ns);
-        if (a.want_mean()) mean_off[t] = take(L.roff, ns);
-        if (!need_v) continue;
-        var_off[t] = take(L.roff, ns);  // the variance the predict kernel computes on its way to V: scratch
+        const long ns = a.xsb(b).n;
         JointProb j{};
         j.prob = L.pos[t], j.ns = (int)ns, j.nsp = (int)batch_np(ns), j.nsamp = a.nsamp;
         j.v_off = j.js_off = -1;
-        j.xs_off = xs_off[t], j.mean_off = mean_off[t];
+        j.xs_off = tp.xs_off[t], j.mean_off = tp.mean_off[t];
         j.cov_off = (a.what & 4) ? take(L.roff, ns * ns) : -1;
         j.jr_off = a.want_fact() ? take(L.roff, 2) : -1;
         j.samp_off = (a.what & 16) ? take(L.roff, a.draws(b)) : -1;
@@ -1907,72 +1966,47 @@ int32_t run_joint_wave(gp_ctx* c, const JointArgs& a, const std::vector<KSum>& p
         const gp_noise* nz = a.noise_xs ? &a.noise_xs[b] : nullptr;
         j.noise_s = nz ? nz->s : 0.0;
         j.nzs_off = (nz && nz->kind == 1) ? take(L.off, ns) : -1;
-        jp_of[t] = (int)jp.size();
-        jp.push_back(j);
-    }
-    // a problem's tiles of TP test points lie one after the other, and so do their strips; a predict launch closes at BATCH_PRED_TILES tiles
-    std::vector<BatchTile> tiles;
-    std::vector<GradTile> jtiles;
-    std::vector<size_t> launch_end;
-    for (int s = 0; s < nw; ++s) {
-        const int t = L.order[s];
-        const long ns = a.xsb(idx[t]).n, strip = need_v ? (long)TP * L.pr[t].ld : 0;
-        if (ns == 0) continue;
-        if (jp_of[t] >= 0) jp[(size_t)jp_of[t]].v_off = L.ws;
-        for (long row0 = 0; row0 < ns; row0 += TP) {
-            if (!tiles.empty() && (tiles.size() - (launch_end.empty() ? 0 : launch_end.back())) == BATCH_PRED_TILES) launch_end.push_back(tiles.size());
-            tiles.push_back(BatchTile{xs_off[t], take(L.ws, strip), mean_off[t], var_off[t], L.pos[t], (int)ns, (int)row0, (int)std::min<long>(TP, ns - row0)});
-        }
-        if (jp_of[t] < 0) continue;
-        JointProb& j = jp[(size_t)jp_of[t]];
-        if (a.want_fact()) j.js_off = take(L.ws, batch_slice(ns));
+        jp_of[t] = (int)jp.v.size();
+        jp.v.push_back(j);
+    });
+    // a problem's tiles of TP test points lie one after the other, and so do their strips: V; behind them the joint slice
+    tp.tile(a, idx, nw, false, L, [&](int t, long first) {
+        if (jp_of[t] < 0) return;
+        JointProb& j = jp.v[(size_t)jp_of[t]];
+        j.v_off = first;
+        if (a.want_fact()) j.js_off = take(L.ws, batch_slice(j.ns));
         for (int ti = 0; ti < j.nsp / BT; ++ti)
-            for (int tj = 0; tj <= ti; ++tj) jtiles.push_back(GradTile{jp_of[t], ti, tj, 0});
-    }
-    if (!tiles.empty()) launch_end.push_back(tiles.size());
-    const long tile_off = take(L.off, (long)(tiles.size() * sizeof(BatchTile) / 8));
-    const long jp_off = take(L.off, (long)(jp.size() * sizeof(JointProb) / 8));
-    const long jt_off = take(L.off, (long)(jtiles.size() * sizeof(GradTile) / 8));
+            for (int tj = 0; tj <= ti; ++tj) jtiles.v.push_back(GradTile{jp_of[t], ti, tj, 0});
+    });
+    jp.place(L);
+    jtiles.place(L);
 
     WaveMem m(c);
     RC(m.alloc(L.off, L.ws, L.roff));
-    wave_fill(a, packed, idx, nw, L, m.hin);
+    double* const hin = m.hin;
+    wave_fill(a, packed, idx, nw, L, hin);
+    tp.fill(a, idx, nw, m);
     for (int t = 0; t < nw; ++t) {
-        const int b = idx[t];
-        const gp_points& xs = a.xsb(b);
-        if (xs.n == 0) continue;
-        if (xsf.claim()) pack_points(xs, m.hin + xs_off[t]);
         if (jp_of[t] < 0) continue;
-        const JointProb& j = jp[(size_t)jp_of[t]];
+        const int b = idx[t];
+        const long ns = a.xsb(b).n;
+        const JointProb& j = jp.v[(size_t)jp_of[t]];
         if (j.ysd_off >= 0) {
             const double *ys = (const double*)a.ys[b], *pm = (const double*)a.pmb(b);
-            for (long i = 0; i < xs.n; ++i) m.hin[j.ysd_off + i] = pm ? ys[i] - pm[i] : ys[i];
+            for (long i = 0; i < ns; ++i) hin[j.ysd_off + i] = pm ? ys[i] - pm[i] : ys[i];
         }
-        if (j.xi_off >= 0 && a.draws(b) > 0) std::memcpy(m.hin + j.xi_off, a.xi[b], sizeof(double) * (size_t)a.draws(b));
-        if (j.nzs_off >= 0) std::memcpy(m.hin + j.nzs_off, a.noise_xs[b].diag, sizeof(double) * (size_t)xs.n);
+        if (j.xi_off >= 0 && a.draws(b) > 0) std::memcpy(hin + j.xi_off, a.xi[b], sizeof(double) * (size_t)a.draws(b));
+        if (j.nzs_off >= 0) std::memcpy(hin + j.nzs_off, a.noise_xs[b].diag, sizeof(double) * (size_t)ns);
     }
-    if (!tiles.empty()) std::memcpy(m.hin + tile_off, tiles.data(), tiles.size() * sizeof(BatchTile));
-    if (!jp.empty()) std::memcpy(m.hin + jp_off, jp.data(), jp.size() * sizeof(JointProb));
-    if (!jtiles.empty()) std::memcpy(m.hin + jt_off, jtiles.data(), jtiles.size() * sizeof(GradTile));
+    jp.fill(m);
+    jtiles.fill(m);
     const bool ks = a.ks != nullptr;
     RC(run_drained(c, [&]() -> int32_t {
         RC(m.upload());
         RC(launch_fit(m, ks, nw));
-        size_t t0 = 0;
-        for (size_t t1 : launch_end) {
-            RC(launch_predict(m, ks, nw, reinterpret_cast<const BatchTile*>(m.in + tile_off) + t0, t1 - t0));
-            t0 = t1;
-        }
-        const JointProb* djp = reinterpret_cast<const JointProb*>(m.in + jp_off);
-        if (!jtiles.empty()) {
-            hipLaunchKernelGGL(ks ? batch_jcov_kernel<true> : batch_jcov_kernel<false>, dim3((unsigned)jtiles.size()), dim3(GNT), 0, c->sm, m.in, m.ws, m.res, nw, djp,
-                               reinterpret_cast<const GradTile*>(m.in + jt_off));
-            HIPCHK(hipGetLastError());
-        }
-        if (a.want_fact() && !jp.empty()) {
-            hipLaunchKernelGGL(batch_jfact_kernel, dim3((unsigned)jp.size()), dim3(NT), 0, c->sm, m.in, m.ws, m.res, nw, djp);
-            HIPCHK(hipGetLastError());
-        }
+        RC(tp.launch_groups(m, ks, nw, nullptr));
+        if (!jtiles.v.empty()) RC(launch(m, ks ? batch_jcov_kernel<true> : batch_jcov_kernel<false>, jtiles.v.size(), GNT, nw, jp.dev(m), jtiles.dev(m)));
+        if (a.want_fact() && !jp.v.empty()) RC(launch(m, batch_jfact_kernel, jp.v.size(), NT, nw, jp.dev(m)));
         return m.download_and_sync();
     }));
     const double* hout = m.hout;
@@ -1983,17 +2017,16 @@ int32_t run_joint_wave(gp_ctx* c, const JointArgs& a, const std::vector<KSum>& p
         if (a.info_joint) a.info_joint[b] = 0;
         const long ns = a.xsb(b).n;
         if (ns == 0) continue;
-        const double* pm = (const double*)a.pmb(b);
-        if (double* mo = (double*)a.out_ptr(a.mean_out, 1, b))
-            for (long j = 0; j < ns; ++j) mo[j] = pm ? pm[j] + hout[mean_off[t] + j] : hout[mean_off[t] + j];
+        tp.put_mean(a, b, t, hout);
         if (jp_of[t] < 0) continue;
-        const JointProb& j = jp[(size_t)jp_of[t]];
-        if (void* co = a.out_ptr(a.cov_out, 4, b)) std::memcpy(co, hout + j.cov_off, sizeof(double) * (size_t)(ns * ns));
+        const JointProb& j = jp.v[(size_t)jp_of[t]];
+        const double* pm = (const double*)a.pmb(b);
+        if (void* co = a.out_b(a.cov_out, 4, b)) std::memcpy(co, hout + j.cov_off, sizeof(double) * (size_t)(ns * ns));
         if (j.jr_off >= 0) {
             if (a.what & 8) ((double*)a.hlogpdf_out)[b] = hout[j.jr_off];
             if (a.info_joint) a.info_joint[b] = (int32_t)hout[j.jr_off + 1];
         }
-        if (double* so = (double*)a.out_ptr(a.samples_out, 16, b))
+        if (double* so = (double*)a.out_b(a.samples_out, 16, b))
             for (long e = 0; e < a.draws(b); ++e) so[e] = pm ? pm[e % ns] + hout[j.samp_off + e] : hout[j.samp_off + e];
     }
     return 0;
@@ -2005,32 +2038,22 @@ int32_t joint_batch_impl(gp_ctx* c, JointArgs& a) {
     if (a.nb < 0) return set_arg_err(2, "nb must be >= 0");
     if (a.nb == 0) return 0;
     RC(check_batch_head(a));
-    if (a.nxs != 1 && a.nxs != a.nb) return set_arg_err(10, "nxs must be 1 (one xs shared by every problem) or nb");
-    if (!a.xs) return set_arg_err(11, "test points array is NULL");
+    RC(check_test_head(a));
     if (a.what <= 0 || (a.what & ~29)) return set_arg_err(14, "what must be a combination of 1|4|8|16 (marginal variances: gp_predict_batch)");
     if ((a.what & 1) && !a.mean_out) return set_arg_err(15, "mean_out is NULL");
     if ((a.what & 4) && !a.cov_out) return set_arg_err(16, "cov_out is NULL");
     if ((a.what & 8) && !a.ys) return set_arg_err(17, "ys array is NULL");
     if ((a.what & 8) && !a.hlogpdf_out) return set_arg_err(18, "hlogpdf_out is NULL");
     if (a.nsamp < 0) return set_arg_err(19, "nsamp must be >= 0");
-    if ((a.what & 16) && a.nsamp > 0 && !a.xi) return set_arg_err(20, "xi array is NULL");
-    if ((a.what & 16) && a.nsamp > 0 && !a.samples_out) return set_arg_err(21, "samples_out is NULL");
+    const bool sampling = (a.what & 16) && a.nsamp > 0;
+    if (sampling && !a.xi) return set_arg_err(20, "xi array is NULL");
+    if (sampling && !a.samples_out) return set_arg_err(21, "samples_out is NULL");
     if (!a.info_out) return set_arg_err(23, "info_out is NULL");
     std::vector<KSum> packed;
     RC(check_batch_problems(a, packed));
-    for (int b = 0; b < a.nb; ++b) {
-        const gp_points& xs = a.xsb(b);
-        if (xs.n < 0) return set_arg_err(11, "xs: n must be >= 0");
-        if (xs.n == 0) continue;  // no test points: nothing of this problem's xs or outputs is touched
-        RC(check_points(&xs, 11));
-        if (xs.d != a.xb(b).d) return set_arg_err(11, "xs has a different D than the training inputs");
-        if (a.noise_xs) RC(check_noise(&a.noise_xs[b], 13, true));
-        if ((a.what & 1) && !a.mean_out[b]) return set_arg_err(15, "a mean_out pointer is NULL");
-        if ((a.what & 4) && !a.cov_out[b]) return set_arg_err(16, "a cov_out pointer is NULL");
-        if ((a.what & 8) && !a.ys[b]) return set_arg_err(17, "a ys pointer is NULL");
-        if ((a.what & 16) && a.nsamp > 0 && !a.xi[b]) return set_arg_err(20, "a xi pointer is NULL");
-        if ((a.what & 16) && a.nsamp > 0 && !a.samples_out[b]) return set_arg_err(21, "a samples_out pointer is NULL");
-    }
+    RC(check_test_points(a, a.noise_xs, {{a.mean_out, (a.what & 1) != 0, 15, "a mean_out pointer is NULL"}, {a.cov_out, (a.what & 4) != 0, 16, "a cov_out pointer is NULL"},
+                                         {a.ys, (a.what & 8) != 0, 17, "a ys pointer is NULL"}, {a.xi, sampling, 20, "a xi pointer is NULL"},
+                                         {a.samples_out, sampling, 21, "a samples_out pointer is NULL"}}));
     // which path serves a problem depends on that problem alone: gp_logpdf_batch's routing under the joint limits, and a Σy* the kernels take
     const long max_n = env_capped(getenv("GPMI_BATCH_JOINT_MAX_N"), GPMI355_BATCH_JOINT_MAX_N);
     const long max_ns = env_capped(getenv("GPMI_BATCH_JOINT_MAX_NS"), GPMI355_BATCH_JOINT_MAX_NS);
@@ -2056,16 +2079,13 @@ int32_t joint_batch_impl(gp_ctx* c, JointArgs& a) {
     gd.lk.unlock();
     const gp_noise zero_noise{0, 0.0, nullptr};
     for (int b : routed) {
-        const gp_points& x = a.xb(b);
         const gp_points& xs = a.xsb(b);
         const gp_noise* nz = a.noise_xs ? &a.noise_xs[b] : &zero_noise;
         gp_post* post = nullptr;
-        void* lp = logpdf_slot(a, b);
         int32_t rj = 0;
-        int32_t rc = a.ks ? gp_posterior_fit_sum(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), &post, nullptr, lp)
-                          : gp_posterior_fit(c, &a.k[b], &x, &a.noise[b], a.mb(b), a.yb(b), &post, nullptr, lp);
+        int32_t rc = routed_fit(c, a, b, &post, nullptr, logpdf_slot(a, b));
         if (rc == 0 && xs.n > 0 && (a.what & 5))
-            rc = gp_posterior_predict(post, &xs, a.pmb(b), a.what & 5, a.out_ptr(a.mean_out, 1, b), nullptr, a.out_ptr(a.cov_out, 4, b));
+            rc = gp_posterior_predict(post, &xs, a.pmb(b), a.what & 5, a.out_b(a.mean_out, 1, b), nullptr, a.out_b(a.cov_out, 4, b));
         if (rc == 0 && xs.n > 0 && (a.what & 8)) {
             rj = gp_posterior_logpdf(post, &xs, a.pmb(b), nz, a.ys[b], xs.n, 1, (char*)a.hlogpdf_out + a.esize() * (size_t)b);
             if (rj < 0) rc = rj;
@@ -2075,16 +2095,12 @@ int32_t joint_batch_impl(gp_ctx* c, JointArgs& a) {
             if (rj < 0) rc = rj;
         }
         if (post) (void)gp_posterior_free(post);
-        if (rc < 0) return rc;
-        a.info_out[b] = rc;
+        RC(routed_done(a, b, rc, [&] {
+            if (xs.n <= 0) return;
+            fill_nan(a.out_b(a.mean_out, 1, b), a.dtype, xs.n);
+            fill_nan(a.out_b(a.cov_out, 4, b), a.dtype, xs.n * xs.n);
+        }));
         if (a.info_joint) a.info_joint[b] = rc == 0 ? rj : 0;
-        if (rc > 0) {
-            put_result(a, b, std::numeric_limits<double>::quiet_NaN(), rc);
-            if (xs.n > 0) {
-                fill_nan(a.out_ptr(a.mean_out, 1, b), a.dtype, xs.n);
-                fill_nan(a.out_ptr(a.cov_out, 4, b), a.dtype, xs.n * xs.n);
-            }
-        }
         if ((rc > 0 || rj > 0) && xs.n > 0) joint_fill_nan(a, b);
     }
     return 0;
@@ -2103,6 +2119,19 @@ struct GradArgs : BatchArgs {
     void* dyb(int b) const { return dy ? dy[b] : nullptr; }
     void* dxb(int b) const { return dx ? dx[b] : nullptr; }
 };
+
+// a gradient array that is given holds a pointer for every problem (dscale: wherever the problem has scales)
+int32_t check_grad_pointers(const GradArgs& a) {
+    const int a_dn = a.ks ? a.arg0 + 1 : a.arg0 + 2, a_dy = a_dn + 1;
+    for (int b = 0; b < a.nb; ++b) {
+        if (a.dscale && a.k[b].nscale > 0 && !a.dscale[b]) return set_arg_err(a.arg0 + 1, "a dscale_out pointer is NULL where the kernel has scales");
+        if (a.dtheta && !a.dtheta[b]) return set_arg_err(a.arg0, "a dtheta_out pointer is NULL");
+        if (a.dnoise && !a.dnoise[b]) return set_arg_err(a_dn, "a dnoise_out pointer is NULL");
+        if (a.dy && !a.dy[b]) return set_arg_err(a_dy, "a dy_out pointer is NULL");
+        if (a.dx && !a.dx[b]) return set_arg_err(a_dy + 1, "a dx_out pointer is NULL");
+    }
+    return 0;
+}
 
 // the kernel parameters of problem b: variance + scales, or the θ entries of its composite kernel
 int grad_nkp(const GradArgs& a, const std::vector<KSum>& packed, int b) { return a.ks ? packed[b].nth : 1 + a.k[b].nscale; }
@@ -2131,82 +2160,89 @@ void grad_fill_nan(const GradArgs& a, int b, int nkp) {
     fill_nan(a.dxb(b), a.dtype, n * a.xb(b).d);
 }
 
+// The 64×64 tiles of the s-th descriptor's matrix of nt × nt tiles: its lower triangle, numbered ti (ti + 1) / 2 + tj, or the full square, numbered ti · nt + tj.
+void push_tiles(std::vector<GradTile>& tiles, int s, int nt, bool square) {
+    for (int ti = 0; ti < nt; ++ti)
+        for (int tj = 0; tj < (square ? nt : ti + 1); ++tj) tiles.push_back(GradTile{s, ti, tj, square ? ti * nt + tj : ti * (ti + 1) / 2 + tj});
+}
+// The gradient half of the s-th descriptor's GradProb (nkp kernel parameters; diag: the noise is a vector): the per-tile sums in the workspace, the totals and
+// the gradient of a diagonal noise in the results.
+void place_grad(WaveLayout& L, int s, int nkp, bool diag, GradProb& g) {
+    const BatchProb& p = L.pr[L.order[s]];
+    const int nt = p.np / BT;
+    g.ng = 1 + nkp;
+    g.ntiles = nt * (nt + 1) / 2;
+    g.part_off = take(L.ws, ((long)g.ntiles * g.ng + 1) & ~1L);  // the next strip stays 16-byte aligned
+    g.g_off = take(L.roff, g.ng);
+    g.dn_off = diag ? take(L.roff, p.n) : -1;
+}
+// the totals of problem b (n points) to the caller: G[0] noise, then the kernel's parameters
+void put_grads(const GradArgs& a, int b, const GradProb& g, long n, const double* hout) {
+    const double* G = hout + g.g_off;
+    if (a.dvar) a.dvar[b] = G[1];
+    if (a.dscale && a.dscale[b]) std::memcpy(a.dscale[b], G + 2, sizeof(double) * (size_t)(g.ng - 2));
+    if (a.dtheta) std::memcpy(a.dtheta[b], G + 1, sizeof(double) * (size_t)(g.ng - 1));
+    if (double* dn = (double*)a.dnb(b)) {
+        if (g.dn_off >= 0) std::memcpy(dn, hout + g.dn_off, sizeof(double) * (size_t)n);
+        else dn[0] = G[0];
+    }
+}
+
 // one wave: the fit launch of the problems idx[0..nw) with α for every one of them, then S = L⁻ᵀ, the tile sums and their totals.  Caller holds the ctx lock.
 int32_t run_grad_wave(gp_ctx* c, const GradArgs& a, const std::vector<KSum>& packed, const int* idx, int nw) {
     WaveLayout L;
     wave_layout(a, idx, nw, [](int) { return true; }, L);
     // behind the fit's input: the GradProb table (in the order of the descriptors), the tiles of S and the tiles of the triangle, the widest problems first
-    std::vector<GradProb> gp((size_t)nw);
-    std::vector<GradTile> itiles, gtiles;
+    Table<GradProb> gp;
+    Table<GradTile> itiles, gtiles;
+    gp.v.assign((size_t)nw, GradProb{-1, -1, -1, -1, 0, 0});
     for (int s = 0; s < nw; ++s) {
-        const int t = L.order[s], b = idx[t];
-        const BatchProb& p = L.pr[t];
-        GradProb& g = gp[s];
-        const int nt = p.np / BT;
-        g.ng = 1 + grad_nkp(a, packed, b);
-        g.ntiles = nt * (nt + 1) / 2;
-        g.s_off = take(L.ws, (long)p.np * p.ld);
-        g.part_off = take(L.ws, ((long)g.ntiles * g.ng + 1) & ~1L);  // the next strip stays 16-byte aligned
-        g.g_off = take(L.roff, g.ng);
-        g.dn_off = a.noise[b].kind == 1 ? take(L.roff, p.n) : -1;
-        for (int r0 = 0; r0 < p.np; r0 += TP) itiles.push_back(GradTile{s, r0 / TP, 0, 0});
-        for (int ti = 0; ti < nt; ++ti)
-            for (int tj = 0; tj <= ti; ++tj) gtiles.push_back(GradTile{s, ti, tj, ti * (ti + 1) / 2 + tj});
+        const int b = idx[L.order[s]];
+        place_s_strip(L, s, gp.v[s], itiles);
+        place_grad(L, s, grad_nkp(a, packed, b), a.noise[b].kind == 1, gp.v[s]);
+        push_tiles(gtiles.v, s, L.pr[L.order[s]].np / BT, false);
     }
     // the problems whose dx is wanted: their tables of row sums behind everything else in the workspace, the gradient [d][n] behind the other results, the
     // tiles of the full square and the 64-row blocks batch_gxsum_kernel adds them up in.  Without any, the wave is laid out and launched as it always was.
-    std::vector<GradXProb> gx;
-    std::vector<GradTile> xtiles, xrows;
+    Table<GradXProb> gx;
+    Table<GradTile> xtiles, xrows;
     int nwx = 0;
     for (int s = 0; s < nw; ++s) {
         const int t = L.order[s], b = idx[t];
         if (!a.dxb(b)) continue;
-        if (gx.empty()) gx.assign((size_t)nw, GradXProb{-1, -1});
+        if (gx.v.empty()) gx.v.assign((size_t)nw, GradXProb{-1, -1});
         const BatchProb& p = L.pr[t];
-        const int nt = p.np / BT;
-        gx[s].xpart_off = take(L.ws, gradx_part(a, b));
-        gx[s].dx_off = take(L.roff, (long)p.n * p.d);
-        for (int ti = 0; ti < nt; ++ti) {
-            for (int tj = 0; tj < nt; ++tj) xtiles.push_back(GradTile{s, ti, tj, ti * nt + tj});
-            xrows.push_back(GradTile{s, ti, 0, 0});
-        }
+        gx.v[s].xpart_off = take(L.ws, gradx_part(a, b));
+        gx.v[s].dx_off = take(L.roff, (long)p.n * p.d);
+        push_tiles(xtiles.v, s, p.np / BT, true);
+        for (int ti = 0; ti < p.np / BT; ++ti) xrows.v.push_back(GradTile{s, ti, 0, 0});
         ++nwx;
     }
-    const long gp_off = take(L.off, (long)(gp.size() * sizeof(GradProb) / 8));
-    const long it_off = take(L.off, (long)(itiles.size() * sizeof(GradTile) / 8));
-    const long gt_off = take(L.off, (long)(gtiles.size() * sizeof(GradTile) / 8));
-    const long gx_off = take(L.off, (long)(gx.size() * sizeof(GradXProb) / 8));
-    const long xt_off = take(L.off, (long)(xtiles.size() * sizeof(GradTile) / 8));
-    const long xr_off = take(L.off, (long)(xrows.size() * sizeof(GradTile) / 8));
+    gp.place(L);
+    itiles.place(L);
+    gtiles.place(L);
+    gx.place(L);
+    xtiles.place(L);
+    xrows.place(L);
 
     WaveMem m(c);
     RC(m.alloc(L.off, L.ws, L.roff));
     wave_fill(a, packed, idx, nw, L, m.hin);
-    std::memcpy(m.hin + gp_off, gp.data(), gp.size() * sizeof(GradProb));
-    std::memcpy(m.hin + it_off, itiles.data(), itiles.size() * sizeof(GradTile));
-    std::memcpy(m.hin + gt_off, gtiles.data(), gtiles.size() * sizeof(GradTile));
-    if (nwx) {
-        std::memcpy(m.hin + gx_off, gx.data(), gx.size() * sizeof(GradXProb));
-        std::memcpy(m.hin + xt_off, xtiles.data(), xtiles.size() * sizeof(GradTile));
-        std::memcpy(m.hin + xr_off, xrows.data(), xrows.size() * sizeof(GradTile));
-    }
+    gp.fill(m);
+    itiles.fill(m);
+    gtiles.fill(m);
+    gx.fill(m);
+    xtiles.fill(m);
+    xrows.fill(m);
     RC(run_drained(c, [&]() -> int32_t {
-        const GradProb* gps = reinterpret_cast<const GradProb*>(m.in + gp_off);
-        const GradTile* its = reinterpret_cast<const GradTile*>(m.in + it_off);
-        const GradTile* gts = reinterpret_cast<const GradTile*>(m.in + gt_off);
         RC(m.upload());
         RC(launch_fit(m, a.ks != nullptr, nw));
-        hipLaunchKernelGGL(batch_inv_kernel, dim3((unsigned)itiles.size()), dim3(NT), 0, c->sm, m.in, m.ws, (const double*)m.res, nw, gps, its);
-        HIPCHK(hipGetLastError());
-        RC(launch_grad(m, a.ks != nullptr, nw, gps, gts, gtiles.size()));
-        hipLaunchKernelGGL(batch_gsum_kernel, dim3((unsigned)nw), dim3(128), 0, c->sm, m.in, (const double*)m.ws, m.res, nw, gps);
-        HIPCHK(hipGetLastError());
+        RC(launch_inv(m, nw, gp, itiles));
+        RC(launch_grad(m, a.ks != nullptr, nw, gp.dev(m), gtiles));
+        RC(launch(m, batch_gsum_kernel, nw, 128, nw, gp.dev(m)));
         if (nwx) {
-            const GradXProb* gxs = reinterpret_cast<const GradXProb*>(m.in + gx_off);
-            RC(launch_gradx(m, a.ks != nullptr, nw, gps, gxs, reinterpret_cast<const GradTile*>(m.in + xt_off), xtiles.size()));
-            hipLaunchKernelGGL(batch_gxsum_kernel, dim3((unsigned)xrows.size()), dim3(BT), 0, c->sm, m.in, (const double*)m.ws, m.res, nw, gxs,
-                               reinterpret_cast<const GradTile*>(m.in + xr_off));
-            HIPCHK(hipGetLastError());
+            RC(launch(m, a.ks ? batch_gradx_kernel<true> : batch_gradx_kernel<false>, xtiles.v.size(), GNT, nw, gp.dev(m), gx.dev(m), xtiles.dev(m)));
+            RC(launch(m, batch_gxsum_kernel, xrows.v.size(), BT, nw, gx.dev(m), xrows.dev(m)));
         }
         return m.download_and_sync();
     }));
@@ -2215,22 +2251,14 @@ int32_t run_grad_wave(gp_ctx* c, const GradArgs& a, const std::vector<KSum>& pac
     c->batch_gradx_problems += nwx;
     for (int t = 0; t < nw; ++t) {
         const int b = idx[t];
-        const GradProb& g = gp[L.pos[t]];
         const long n = L.pr[t].n;
         put_result(a, b, hout[t], (int32_t)hout[nw + t]);
-        const double* G = hout + g.g_off;  // [0] noise, then the kernel's parameters
-        if (a.dvar) a.dvar[b] = G[1];
-        if (a.dscale && a.dscale[b]) std::memcpy(a.dscale[b], G + 2, sizeof(double) * (size_t)(g.ng - 2));
-        if (a.dtheta) std::memcpy(a.dtheta[b], G + 1, sizeof(double) * (size_t)(g.ng - 1));
-        if (double* dn = (double*)a.dnb(b)) {
-            if (g.dn_off >= 0) std::memcpy(dn, hout + g.dn_off, sizeof(double) * (size_t)n);
-            else dn[0] = G[0];
-        }
+        put_grads(a, b, gp.v[L.pos[t]], n, hout);
         if (double* dy = (double*)a.dyb(b)) {
             const double* al = hout + L.pr[t].alpha_off;
             for (long j = 0; j < n; ++j) dy[j] = -al[j];
         }
-        if (void* dx = a.dxb(b)) grad_to_layout<double>(a.xb(b).layout, n, a.xb(b).d, hout + gx[L.pos[t]].dx_off, n, dx);  // [d][n] -> the container layout of x
+        if (void* dx = a.dxb(b)) grad_to_layout<double>(a.xb(b).layout, n, a.xb(b).d, hout + gx.v[L.pos[t]].dx_off, n, dx);  // [d][n] -> the container layout of x
     }
     return 0;
 }
@@ -2245,15 +2273,7 @@ int32_t grad_batch_impl(gp_ctx* c, GradArgs& a) {
     if (!a.info_out) return set_arg_err(11, "info_out is NULL");
     std::vector<KSum> packed;
     RC(check_batch_problems(a, packed));
-    // a gradient array that is given holds a pointer for every problem (dscale: wherever the problem has scales)
-    const int a_dn = a.ks ? a.arg0 + 1 : a.arg0 + 2, a_dy = a_dn + 1;
-    for (int b = 0; b < a.nb; ++b) {
-        if (a.dscale && a.k[b].nscale > 0 && !a.dscale[b]) return set_arg_err(a.arg0 + 1, "a dscale_out pointer is NULL where the kernel has scales");
-        if (a.dtheta && !a.dtheta[b]) return set_arg_err(a.arg0, "a dtheta_out pointer is NULL");
-        if (a.dnoise && !a.dnoise[b]) return set_arg_err(a_dn, "a dnoise_out pointer is NULL");
-        if (a.dy && !a.dy[b]) return set_arg_err(a_dy, "a dy_out pointer is NULL");
-        if (a.dx && !a.dx[b]) return set_arg_err(a_dy + 1, "a dx_out pointer is NULL");
-    }
+    RC(check_grad_pointers(a));
     // which path serves a problem depends on that problem alone and on whether the call asks for dx: the input-gradient kernels have a limit of their own
     std::vector<int> mine, routed;
     split_by_path(a, a.dx ? env_capped(getenv("GPMI_BATCH_GRADX_MAX_N"), GPMI355_BATCH_GRADX_MAX_N)
@@ -2271,12 +2291,7 @@ int32_t grad_batch_impl(gp_ctx* c, GradArgs& a) {
                                                         a.dscale ? a.dscale[b] : nullptr, a.dnb(b), a.dyb(b), a.dxb(b))
                            : a.dxb(b) ? gp_logpdf_grad_sum_x(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), lp, dth, a.dnb(b), a.dyb(b), a.dxb(b))
                                       : gp_logpdf_grad_sum(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), lp, dth, a.dnb(b), a.dyb(b));
-        if (rc < 0) return rc;
-        a.info_out[b] = rc;
-        if (rc > 0) {
-            put_result(a, b, std::numeric_limits<double>::quiet_NaN(), rc);
-            grad_fill_nan(a, b, grad_nkp(a, packed, b));
-        }
+        RC(routed_done(a, b, rc, [&] { grad_fill_nan(a, b, grad_nkp(a, packed, b)); }));
     }
     return 0;
 }
@@ -2325,76 +2340,55 @@ int32_t run_loo_wave(gp_ctx* c, const LooArgs& a, const std::vector<KSum>& packe
     wave_layout(a, idx, nw, [](int) { return true; }, L);
     // behind the fit's input: the GradProb and LooProb tables (in the order of the descriptors), the 128-row tiles of the strips, the tiles of the triangle and
     // of the full square, the widest problems first
-    std::vector<GradProb> gp((size_t)nw);
-    std::vector<LooProb> lq((size_t)nw);
-    std::vector<GradTile> itiles, gtiles, ztiles;
+    Table<GradProb> gp;
+    Table<LooProb> lq;
+    Table<GradTile> itiles, gtiles, ztiles;
+    gp.v.assign((size_t)nw, GradProb{-1, -1, -1, -1, 0, 0});
+    lq.v.assign((size_t)nw, LooProb{-1, -1, -1, -1, -1, -1, -1, -1});
     for (int s = 0; s < nw; ++s) {
         const int t = L.order[s], b = idx[t];
         const BatchProb& p = L.pr[t];
-        GradProb& g = gp[s];
-        LooProb& q = lq[s];
-        const int nt = p.np / BT;
-        g = GradProb{-1, -1, -1, -1, 0, 0};
-        q = LooProb{-1, -1, -1, -1, -1, -1, -1, -1};
-        g.s_off = take(L.ws, (long)p.np * p.ld);
+        LooProb& q = lq.v[s];
+        place_s_strip(L, s, gp.v[s], itiles);
         q.lpart_off = take(L.ws, (loo_tiles(p.n) + 1) & ~1L);  // the next strip stays 16-byte aligned
         if (a.lpb(b)) q.lp_off = take(L.roff, p.n);
         if (a.meanb(b)) q.mean_off = take(L.roff, p.n);
         if (a.varb(b)) q.var_off = take(L.roff, p.n);
-        for (int r0 = 0; r0 < p.np; r0 += TP) itiles.push_back(GradTile{s, r0 / TP, 0, 0});
         if (!a.grad) continue;
-        g.ng = 1 + grad_nkp(a, packed, b);
-        g.ntiles = nt * (nt + 1) / 2;
         q.z_off = take(L.ws, (long)p.np * p.ld);
         q.d_off = take(L.ws, p.np);
         q.e_off = take(L.ws, p.np);
-        g.part_off = take(L.ws, ((long)g.ntiles * g.ng + 1) & ~1L);
-        g.g_off = take(L.roff, g.ng);
-        g.dn_off = a.noise[b].kind == 1 ? take(L.roff, p.n) : -1;
+        place_grad(L, s, grad_nkp(a, packed, b), a.noise[b].kind == 1, gp.v[s]);
         q.beta_off = take(L.roff, p.np);
-        for (int ti = 0; ti < nt; ++ti) {
-            for (int tj = 0; tj <= ti; ++tj) gtiles.push_back(GradTile{s, ti, tj, ti * (ti + 1) / 2 + tj});
-            for (int tj = 0; tj < nt; ++tj) ztiles.push_back(GradTile{s, ti, tj, ti * nt + tj});
-        }
+        push_tiles(gtiles.v, s, p.np / BT, false);
+        push_tiles(ztiles.v, s, p.np / BT, true);
     }
-    const long gp_off = take(L.off, (long)(gp.size() * sizeof(GradProb) / 8));
-    const long lq_off = take(L.off, (long)(lq.size() * sizeof(LooProb) / 8));
-    const long it_off = take(L.off, (long)(itiles.size() * sizeof(GradTile) / 8));
-    const long gt_off = take(L.off, (long)(gtiles.size() * sizeof(GradTile) / 8));
-    const long zt_off = take(L.off, (long)(ztiles.size() * sizeof(GradTile) / 8));
+    gp.place(L);
+    lq.place(L);
+    itiles.place(L);
+    gtiles.place(L);
+    ztiles.place(L);
 
     WaveMem m(c);
     RC(m.alloc(L.off, L.ws, L.roff));
     wave_fill(a, packed, idx, nw, L, m.hin);
-    std::memcpy(m.hin + gp_off, gp.data(), gp.size() * sizeof(GradProb));
-    std::memcpy(m.hin + lq_off, lq.data(), lq.size() * sizeof(LooProb));
-    std::memcpy(m.hin + it_off, itiles.data(), itiles.size() * sizeof(GradTile));
-    if (a.grad) {
-        std::memcpy(m.hin + gt_off, gtiles.data(), gtiles.size() * sizeof(GradTile));
-        std::memcpy(m.hin + zt_off, ztiles.data(), ztiles.size() * sizeof(GradTile));
-    }
+    gp.fill(m);
+    lq.fill(m);
+    itiles.fill(m);
+    gtiles.fill(m);
+    ztiles.fill(m);
     RC(run_drained(c, [&]() -> int32_t {
-        const GradProb* gps = reinterpret_cast<const GradProb*>(m.in + gp_off);
-        const LooProb* lps = reinterpret_cast<const LooProb*>(m.in + lq_off);
-        const GradTile* its = reinterpret_cast<const GradTile*>(m.in + it_off);
-        const unsigned nit = (unsigned)itiles.size();
+        const size_t nit = itiles.v.size();
         RC(m.upload());
         RC(launch_fit(m, a.ks != nullptr, nw));
-        hipLaunchKernelGGL(batch_inv_kernel, dim3(nit), dim3(NT), 0, c->sm, m.in, m.ws, (const double*)m.res, nw, gps, its);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(batch_loo_kernel, dim3(nit), dim3(NT), 0, c->sm, m.in, m.ws, m.res, nw, gps, lps, its);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(batch_loo_sum_kernel, dim3((unsigned)nw), dim3(128), 0, c->sm, m.in, (const double*)m.ws, m.res, nw, lps);
-        HIPCHK(hipGetLastError());
+        RC(launch_inv(m, nw, gp, itiles));
+        RC(launch(m, batch_loo_kernel, nit, NT, nw, gp.dev(m), lq.dev(m), itiles.dev(m)));
+        RC(launch(m, batch_loo_sum_kernel, nw, 128, nw, lq.dev(m)));
         if (a.grad) {
-            hipLaunchKernelGGL(batch_loo_z_kernel, dim3((unsigned)ztiles.size()), dim3(GNT), 0, c->sm, m.in, m.ws, (const double*)m.res, nw, gps, lps,
-                               reinterpret_cast<const GradTile*>(m.in + zt_off));
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(batch_loo_beta_kernel, dim3(nit), dim3(NT), 0, c->sm, m.in, (const double*)m.ws, m.res, nw, lps, its);
-            HIPCHK(hipGetLastError());
-            RC(launch_grad(m, a.ks != nullptr, nw, gps, reinterpret_cast<const GradTile*>(m.in + gt_off), gtiles.size(), lps));
-            hipLaunchKernelGGL(batch_gsum_kernel, dim3((unsigned)nw), dim3(128), 0, c->sm, m.in, (const double*)m.ws, m.res, nw, gps);
-            HIPCHK(hipGetLastError());
+            RC(launch(m, batch_loo_z_kernel, ztiles.v.size(), GNT, nw, gp.dev(m), lq.dev(m), ztiles.dev(m)));
+            RC(launch(m, batch_loo_beta_kernel, nit, NT, nw, lq.dev(m), itiles.dev(m)));
+            RC(launch_grad(m, a.ks != nullptr, nw, gp.dev(m), gtiles, lq.dev(m)));
+            RC(launch(m, batch_gsum_kernel, nw, 128, nw, gp.dev(m)));
         }
         return m.download_and_sync();
     }));
@@ -2402,25 +2396,18 @@ int32_t run_loo_wave(gp_ctx* c, const LooArgs& a, const std::vector<KSum>& packe
     (a.grad ? c->batch_loo_grad_problems : c->batch_loo_problems) += nw;
     for (int t = 0; t < nw; ++t) {
         const int b = idx[t];
-        const GradProb& g = gp[L.pos[t]];
-        const LooProb& q = lq[L.pos[t]];
-        const size_t bytes = sizeof(double) * (size_t)L.pr[t].n;
+        const LooProb& q = lq.v[L.pos[t]];
+        const long n = L.pr[t].n;
+        const size_t bytes = sizeof(double) * (size_t)n;
         put_result(a, b, hout[t], (int32_t)hout[nw + t]);
         if (q.lp_off >= 0) std::memcpy(a.lpb(b), hout + q.lp_off, bytes);
         if (q.mean_off >= 0) std::memcpy(a.meanb(b), hout + q.mean_off, bytes);
         if (q.var_off >= 0) std::memcpy(a.varb(b), hout + q.var_off, bytes);
         if (!a.grad) continue;
-        const double* G = hout + g.g_off;  // [0] noise, then the kernel's parameters
-        if (a.dvar) a.dvar[b] = G[1];
-        if (a.dscale && a.dscale[b]) std::memcpy(a.dscale[b], G + 2, sizeof(double) * (size_t)(g.ng - 2));
-        if (a.dtheta) std::memcpy(a.dtheta[b], G + 1, sizeof(double) * (size_t)(g.ng - 1));
-        if (double* dn = (double*)a.dnb(b)) {
-            if (g.dn_off >= 0) std::memcpy(dn, hout + g.dn_off, bytes);
-            else dn[0] = G[0];
-        }
+        put_grads(a, b, gp.v[L.pos[t]], n, hout);
         if (double* dy = (double*)a.dyb(b)) {
             const double* be = hout + q.beta_off;
-            for (long j = 0; j < L.pr[t].n; ++j) dy[j] = -be[j];
+            for (long j = 0; j < n; ++j) dy[j] = -be[j];
         }
     }
     return 0;
@@ -2458,12 +2445,7 @@ int32_t loo_batch_impl(gp_ctx* c, LooArgs& a) {
         void* val = logpdf_slot(a, b);
         const int32_t rc = a.ks ? gp_loo_sum(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), val, a.lpb(b), a.meanb(b), a.varb(b))
                                 : gp_loo(c, &a.k[b], &x, &a.noise[b], a.mb(b), a.yb(b), val, a.lpb(b), a.meanb(b), a.varb(b));
-        if (rc < 0) return rc;
-        a.info_out[b] = rc;
-        if (rc > 0) {
-            put_result(a, b, std::numeric_limits<double>::quiet_NaN(), rc);
-            loo_fill_nan(a, b, 0);
-        }
+        RC(routed_done(a, b, rc, [&] { loo_fill_nan(a, b, 0); }));
     }
     return 0;
 }
@@ -2476,14 +2458,7 @@ int32_t loo_grad_batch_impl(gp_ctx* c, LooArgs& a) {
     if (a.nb == 0) return 0;
     std::vector<KSum> packed;
     RC(loo_check_head(a, packed));
-    const int a_dn = a.ks ? a.arg0 + 1 : a.arg0 + 2, a_dy = a_dn + 1;
-    for (int b = 0; b < a.nb; ++b) {  // a gradient array that is given holds a pointer for every problem (dscale: wherever the problem has scales)
-        if (a.dscale && a.k[b].nscale > 0 && !a.dscale[b]) return set_arg_err(a.arg0 + 1, "a dscale_out pointer is NULL where the kernel has scales");
-        if (a.dtheta && !a.dtheta[b]) return set_arg_err(a.arg0, "a dtheta_out pointer is NULL");
-        if (a.dnoise && !a.dnoise[b]) return set_arg_err(a_dn, "a dnoise_out pointer is NULL");
-        if (a.dy && !a.dy[b]) return set_arg_err(a_dy, "a dy_out pointer is NULL");
-        if (a.dx && !a.dx[b]) return set_arg_err(a_dy + 1, "a dx_out pointer is NULL");
-    }
+    RC(check_grad_pointers(a));
     // which path serves a problem depends on that problem alone and on whether the call asks for dx
     std::vector<int> mine, routed;
     split_by_path(a, a.dx ? -1 : env_capped(getenv("GPMI_BATCH_LOO_GRAD_MAX_N"), GPMI355_BATCH_LOO_GRAD_MAX_N), mine, routed);
@@ -2497,24 +2472,21 @@ int32_t loo_grad_batch_impl(gp_ctx* c, LooArgs& a) {
         const int32_t rc = a.ks ? gp_loo_grad_sum(c, &a.ks[b], &x, &a.noise[b], a.mb(b), a.yb(b), val, a.dtheta ? a.dtheta[b] : nullptr, a.dnb(b), a.dyb(b), a.dxb(b))
                                 : gp_loo_grad(c, &a.k[b], &x, &a.noise[b], a.mb(b), a.yb(b), val, a.dvar ? &a.dvar[b] : nullptr,
                                               a.dscale ? a.dscale[b] : nullptr, a.dnb(b), a.dyb(b), a.dxb(b));
-        if (rc < 0) return rc;
-        a.info_out[b] = rc;
-        if (rc > 0) {
-            put_result(a, b, std::numeric_limits<double>::quiet_NaN(), rc);
-            loo_fill_nan(a, b, grad_nkp(a, packed, b));
-        }
+        RC(routed_done(a, b, rc, [&] { loo_fill_nan(a, b, grad_nkp(a, packed, b)); }));
     }
     return 0;
 }
 
 }  // namespace
 
+// The two entry points of a pair (gp_kernel / gp_ksum descriptors) have the same body: base_args() files `k` by its type.  The check of `k` stands in front of
+// the body: it reports argument 3 before the handle is looked at.
 extern "C" {
 
 int32_t gp_logpdf_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, const gp_noise* noise,
                         const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
                         void* const* alpha_out_or_null) {
-    BatchArgs a{nb, k, nullptr, nx, x, noise, mean_or_null, ny, y, logpdf_out, info_out, alpha_out_or_null, 0};
+    BatchArgs a = base_args(nb, k, nx, x, noise, mean_or_null, ny, y, logpdf_out, info_out, alpha_out_or_null);
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return batch_impl(ctx, a);
 }
@@ -2522,7 +2494,7 @@ int32_t gp_logpdf_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx,
 int32_t gp_logpdf_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx, const gp_points* x, const gp_noise* noise,
                             const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
                             void* const* alpha_out_or_null) {
-    BatchArgs a{nb, nullptr, k, nx, x, noise, mean_or_null, ny, y, logpdf_out, info_out, alpha_out_or_null, 0};
+    BatchArgs a = base_args(nb, k, nx, x, noise, mean_or_null, ny, y, logpdf_out, info_out, alpha_out_or_null);
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return batch_impl(ctx, a);
 }
@@ -2531,7 +2503,7 @@ int32_t gp_predict_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx
                          const void* const* mean_or_null, int32_t ny, const void* const* y, int32_t nxs, const gp_points* xs,
                          const void* const* prior_mean_xs_or_null, int32_t what, void* const* mean_out, void* const* var_out,
                          void* logpdf_out_or_null, int32_t* info_out) {
-    PredictArgs a{{nb, k, nullptr, nx, x, noise, mean_or_null, ny, y, logpdf_out_or_null, info_out, nullptr, 0}, nxs, xs, prior_mean_xs_or_null, what, mean_out, var_out};
+    PredictArgs a{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, logpdf_out_or_null, info_out), nxs, xs, prior_mean_xs_or_null, what, mean_out, var_out};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return predict_batch_impl(ctx, a);
 }
@@ -2540,7 +2512,7 @@ int32_t gp_predict_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t 
                              const void* const* mean_or_null, int32_t ny, const void* const* y, int32_t nxs, const gp_points* xs,
                              const void* const* prior_mean_xs_or_null, int32_t what, void* const* mean_out, void* const* var_out,
                              void* logpdf_out_or_null, int32_t* info_out) {
-    PredictArgs a{{nb, nullptr, k, nx, x, noise, mean_or_null, ny, y, logpdf_out_or_null, info_out, nullptr, 0}, nxs, xs, prior_mean_xs_or_null, what, mean_out, var_out};
+    PredictArgs a{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, logpdf_out_or_null, info_out), nxs, xs, prior_mean_xs_or_null, what, mean_out, var_out};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return predict_batch_impl(ctx, a);
 }
@@ -2549,7 +2521,7 @@ int32_t gp_predict_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32
                               const void* const* mean_or_null, int32_t ny, const void* const* y, int32_t nxs, const gp_points* xs,
                               const void* const* prior_mean_xs_or_null, int32_t what, void* const* mean_out_or_null, void* const* var_out_or_null,
                               void* const* dmean_out_or_null, void* const* dvar_out_or_null, void* logpdf_out_or_null, int32_t* info_out) {
-    PredictArgs a{{nb, k, nullptr, nx, x, noise, mean_or_null, ny, y, logpdf_out_or_null, info_out, nullptr, 0}, nxs, xs, prior_mean_xs_or_null, what,
+    PredictArgs a{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, logpdf_out_or_null, info_out), nxs, xs, prior_mean_xs_or_null, what,
                   mean_out_or_null, var_out_or_null, true, dmean_out_or_null, dvar_out_or_null};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return predict_grad_batch_impl(ctx, a);
@@ -2559,7 +2531,7 @@ int32_t gp_predict_grad_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int
                                   const void* const* mean_or_null, int32_t ny, const void* const* y, int32_t nxs, const gp_points* xs,
                                   const void* const* prior_mean_xs_or_null, int32_t what, void* const* mean_out_or_null, void* const* var_out_or_null,
                                   void* const* dmean_out_or_null, void* const* dvar_out_or_null, void* logpdf_out_or_null, int32_t* info_out) {
-    PredictArgs a{{nb, nullptr, k, nx, x, noise, mean_or_null, ny, y, logpdf_out_or_null, info_out, nullptr, 0}, nxs, xs, prior_mean_xs_or_null, what,
+    PredictArgs a{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, logpdf_out_or_null, info_out), nxs, xs, prior_mean_xs_or_null, what,
                   mean_out_or_null, var_out_or_null, true, dmean_out_or_null, dvar_out_or_null};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return predict_grad_batch_impl(ctx, a);
@@ -2570,8 +2542,7 @@ int32_t gp_joint_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, 
                        const void* const* prior_mean_xs_or_null, const gp_noise* noise_xs_or_null, int32_t what, void* const* mean_out_or_null,
                        void* const* cov_out_or_null, const void* const* ys_or_null, void* hlogpdf_out_or_null, int32_t nsamp, const void* const* xi_or_null,
                        void* const* samples_out_or_null, void* logpdf_out_or_null, int32_t* info_out, int32_t* info_joint_out_or_null) {
-    JointArgs a{{{nb, k, nullptr, nx, x, noise, mean_or_null, ny, y, logpdf_out_or_null, info_out, nullptr, 0}, nxs, xs, prior_mean_xs_or_null, what,
-                 mean_out_or_null, nullptr},
+    JointArgs a{{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, logpdf_out_or_null, info_out), nxs, xs, prior_mean_xs_or_null, what, mean_out_or_null, nullptr},
                 noise_xs_or_null, cov_out_or_null, ys_or_null, hlogpdf_out_or_null, nsamp, xi_or_null, samples_out_or_null, info_joint_out_or_null};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return joint_batch_impl(ctx, a);
@@ -2583,8 +2554,7 @@ int32_t gp_joint_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx
                            void* const* cov_out_or_null, const void* const* ys_or_null, void* hlogpdf_out_or_null, int32_t nsamp,
                            const void* const* xi_or_null, void* const* samples_out_or_null, void* logpdf_out_or_null, int32_t* info_out,
                            int32_t* info_joint_out_or_null) {
-    JointArgs a{{{nb, nullptr, k, nx, x, noise, mean_or_null, ny, y, logpdf_out_or_null, info_out, nullptr, 0}, nxs, xs, prior_mean_xs_or_null, what,
-                 mean_out_or_null, nullptr},
+    JointArgs a{{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, logpdf_out_or_null, info_out), nxs, xs, prior_mean_xs_or_null, what, mean_out_or_null, nullptr},
                 noise_xs_or_null, cov_out_or_null, ys_or_null, hlogpdf_out_or_null, nsamp, xi_or_null, samples_out_or_null, info_joint_out_or_null};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return joint_batch_impl(ctx, a);
@@ -2594,7 +2564,7 @@ int32_t gp_logpdf_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_
                              const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
                              double* dvariance_out_or_null, double* const* dscale_out_or_null, void* const* dnoise_out_or_null,
                              void* const* dy_out_or_null) {
-    GradArgs a{{nb, k, nullptr, nx, x, noise, mean_or_null, ny, y, logpdf_out, info_out, nullptr, 0}, dvariance_out_or_null, dscale_out_or_null, nullptr, dnoise_out_or_null, dy_out_or_null, 12};
+    GradArgs a{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, logpdf_out, info_out), dvariance_out_or_null, dscale_out_or_null, nullptr, dnoise_out_or_null, dy_out_or_null, 12};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return grad_batch_impl(ctx, a);
 }
@@ -2602,7 +2572,7 @@ int32_t gp_logpdf_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_
 int32_t gp_logpdf_grad_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx, const gp_points* x, const gp_noise* noise,
                                  const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
                                  double* const* dtheta_out_or_null, void* const* dnoise_out_or_null, void* const* dy_out_or_null) {
-    GradArgs a{{nb, nullptr, k, nx, x, noise, mean_or_null, ny, y, logpdf_out, info_out, nullptr, 0}, nullptr, nullptr, dtheta_out_or_null, dnoise_out_or_null, dy_out_or_null, 12};
+    GradArgs a{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, logpdf_out, info_out), nullptr, nullptr, dtheta_out_or_null, dnoise_out_or_null, dy_out_or_null, 12};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return grad_batch_impl(ctx, a);
 }
@@ -2611,7 +2581,7 @@ int32_t gp_logpdf_grad_batch_x(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int3
                                const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
                                double* dvariance_out_or_null, double* const* dscale_out_or_null, void* const* dnoise_out_or_null,
                                void* const* dy_out_or_null, void* const* dx_out_or_null) {
-    GradArgs a{{nb, k, nullptr, nx, x, noise, mean_or_null, ny, y, logpdf_out, info_out, nullptr, 0}, dvariance_out_or_null, dscale_out_or_null, nullptr, dnoise_out_or_null, dy_out_or_null, 12, dx_out_or_null};
+    GradArgs a{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, logpdf_out, info_out), dvariance_out_or_null, dscale_out_or_null, nullptr, dnoise_out_or_null, dy_out_or_null, 12, dx_out_or_null};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return gradx_batch_impl(ctx, a);
 }
@@ -2620,7 +2590,7 @@ int32_t gp_logpdf_grad_batch_sum_x(gp_ctx* ctx, int32_t nb, const gp_ksum* k, in
                                    const void* const* mean_or_null, int32_t ny, const void* const* y, void* logpdf_out, int32_t* info_out,
                                    double* const* dtheta_out_or_null, void* const* dnoise_out_or_null, void* const* dy_out_or_null,
                                    void* const* dx_out_or_null) {
-    GradArgs a{{nb, nullptr, k, nx, x, noise, mean_or_null, ny, y, logpdf_out, info_out, nullptr, 0}, nullptr, nullptr, dtheta_out_or_null, dnoise_out_or_null, dy_out_or_null, 12, dx_out_or_null};
+    GradArgs a{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, logpdf_out, info_out), nullptr, nullptr, dtheta_out_or_null, dnoise_out_or_null, dy_out_or_null, 12, dx_out_or_null};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return gradx_batch_impl(ctx, a);
 }
@@ -2628,7 +2598,7 @@ int32_t gp_logpdf_grad_batch_sum_x(gp_ctx* ctx, int32_t nb, const gp_ksum* k, in
 int32_t gp_loo_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, const gp_noise* noise,
                      const void* const* mean_or_null, int32_t ny, const void* const* y, void* value_out, int32_t* info_out,
                      void* const* lp_out_or_null, void* const* mean_out_or_null, void* const* var_out_or_null) {
-    LooArgs a{{{nb, k, nullptr, nx, x, noise, mean_or_null, ny, y, value_out, info_out, nullptr, 0}, nullptr, nullptr, nullptr, nullptr, nullptr, 12}, false,
+    LooArgs a{{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, value_out, info_out), nullptr, nullptr, nullptr, nullptr, nullptr, 12}, false,
               lp_out_or_null, mean_out_or_null, var_out_or_null};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return loo_batch_impl(ctx, a);
@@ -2637,7 +2607,7 @@ int32_t gp_loo_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, co
 int32_t gp_loo_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t nx, const gp_points* x, const gp_noise* noise,
                          const void* const* mean_or_null, int32_t ny, const void* const* y, void* value_out, int32_t* info_out,
                          void* const* lp_out_or_null, void* const* mean_out_or_null, void* const* var_out_or_null) {
-    LooArgs a{{{nb, nullptr, k, nx, x, noise, mean_or_null, ny, y, value_out, info_out, nullptr, 0}, nullptr, nullptr, nullptr, nullptr, nullptr, 12}, false,
+    LooArgs a{{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, value_out, info_out), nullptr, nullptr, nullptr, nullptr, nullptr, 12}, false,
               lp_out_or_null, mean_out_or_null, var_out_or_null};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return loo_batch_impl(ctx, a);
@@ -2647,7 +2617,7 @@ int32_t gp_loo_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t n
                           const void* const* mean_or_null, int32_t ny, const void* const* y, void* value_out, int32_t* info_out,
                           double* dvariance_out_or_null, double* const* dscale_out_or_null, void* const* dnoise_out_or_null,
                           void* const* dy_out_or_null, void* const* dx_out_or_null) {
-    LooArgs a{{{nb, k, nullptr, nx, x, noise, mean_or_null, ny, y, value_out, info_out, nullptr, 0}, dvariance_out_or_null, dscale_out_or_null, nullptr,
+    LooArgs a{{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, value_out, info_out), dvariance_out_or_null, dscale_out_or_null, nullptr,
                dnoise_out_or_null, dy_out_or_null, 12, dx_out_or_null}, true};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return loo_grad_batch_impl(ctx, a);
@@ -2657,7 +2627,7 @@ int32_t gp_loo_grad_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t
                               const void* const* mean_or_null, int32_t ny, const void* const* y, void* value_out, int32_t* info_out,
                               double* const* dtheta_out_or_null, void* const* dnoise_out_or_null, void* const* dy_out_or_null,
                               void* const* dx_out_or_null) {
-    LooArgs a{{{nb, nullptr, k, nx, x, noise, mean_or_null, ny, y, value_out, info_out, nullptr, 0}, nullptr, nullptr, dtheta_out_or_null, dnoise_out_or_null,
+    LooArgs a{{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, value_out, info_out), nullptr, nullptr, dtheta_out_or_null, dnoise_out_or_null,
                dy_out_or_null, 12, dx_out_or_null}, true};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return loo_grad_batch_impl(ctx, a);

@@ -123,3 +123,26 @@ def test_the_oracle_is_far_inside_the_gpu_tolerances_on_the_ragged_cases():
     assert cats == {"kind": {0, 1, 2, 3}, "tr": set(bc.TRANSFORMS), "d": {1, 3, 8}, "container": set(bc.CONTAINERS), "noise": set(bc.NOISES),
                     "mean": set(bc.MEANS)}
     assert set(bc.FIXED_SIZES) <= {c["n"] for c in bc.ragged_cases()} and len(bc.ragged_cases()) >= 32
+
+
+def test_each_repeated_block_of_the_batch_drivers_has_one_definition():
+    """DESIGN.md §"The batch unit's host drivers": the copies that seven features left behind do not grow back.  In the host half of batch.hip one helper
+    launches, one table helper lays a device table out, fills it and addresses it, and the routed loops take their posterior fit from one selector."""
+    from tests import test_abi_guard_static as gs
+
+    src = gs.strip_comments((gs.CSRC / "batch.hip").read_text())
+    host = src[src.index("using namespace gpmi;"):]
+
+    def block(marker):
+        i = host.index(marker)
+        return host[i:gs._close(host, host.index("{", i), "{", "}") + 1]
+
+    table, launch, wave_fill, selector = block("struct Table {"), block("int32_t launch("), block("void wave_fill("), block("int32_t routed_fit(")
+    assert src.count("hipLaunchKernelGGL") == 1 == launch.count("hipLaunchKernelGGL") and "HIPCHK(hipGetLastError())" in launch
+    assert host.count("hipGetLastError") == 1
+    assert host.count("reinterpret_cast<const") == table.count("reinterpret_cast<const") == 1
+    assert host.count("std::memcpy(m.hin +") == table.count("std::memcpy(m.hin +") + wave_fill.count("std::memcpy(m.hin +") == 1
+    assert host.count("gp_posterior_fit_sum(") == 1 == selector.count("gp_posterior_fit_sum(")
+    defs = gs.definitions(src)
+    for body in ("batch_impl", "predict_batch_impl", "predict_grad_batch_impl", "joint_batch_impl"):
+        assert defs[body][1].count("routed_fit(") == 1, body

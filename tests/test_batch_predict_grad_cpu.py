@@ -68,7 +68,7 @@ def test_the_new_entry_points_are_guarded_by_a_body_of_their_own():
     body = defs["predict_grad_batch_impl"][1]
     assert "Guard gd(c);" in body and "run_drained" not in body and "run_predict_wave(" in body
     # the lock is released before the routed problems re-enter the single path
-    assert body.index("gd.lk.unlock();") < body.index("gp_posterior_fit(") and body.index("gd.lk.unlock();") < body.index("gp_posterior_predict_grad(")
+    assert body.index("gd.lk.unlock();") < body.index("routed_fit(") and body.index("gd.lk.unlock();") < body.index("gp_posterior_predict_grad(")
     assert body.index("for_each_wave(") < body.index("gd.lk.unlock();")
     assert "run_drained(" in defs["run_predict_wave"][1]  # the device work of a wave
     # without the guard of the new body exactly the two new names are reported
