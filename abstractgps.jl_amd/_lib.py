@@ -152,6 +152,8 @@ PROTOTYPES = {
     "gp_vfe_get_by_cols": (i32, [vp, vp]),
     "gp_vfe_grad_cols": (i32, [vp, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), vp, vp, vp, i32, vp, i32]),
     "gp_vfe_free": (i32, [vp]),
+    "gp_vfe_batch": (i32, [vp, i32, PK, i32, PP, i32, PP, PN, C.POINTER(dbl), C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(i32), vp, C.POINTER(i32),
+                           C.POINTER(vp), C.POINTER(vp)]),
     "gpd_assemble": (i32, [vp, PK, vp, i64, i64, i32, vp, PG, vp, i64, i64, i64]),
     "gpd_potrf": (i32, [vp, vp, i64, i64, i64, vp, i32, i64, vp]),
     "gpd_trsm": (i32, [vp, vp, i64, i64, vp, i64, i64]),
@@ -221,6 +223,12 @@ def batch_loo_max_n() -> int:
 def batch_loo_grad_max_n() -> int:
     """GPMI355_BATCH_LOO_GRAD_MAX_N of include/gpmi355.h: the largest problem gp_loo_grad_batch hands to its kernels (no problem of a call with dx)."""
     return int(re.search(r"#define GPMI355_BATCH_LOO_GRAD_MAX_N (\d+)", HEADER.read_text()).group(1))
+
+
+def vfe_batch_limits() -> dict:
+    """GPMI355_VFE_BATCH_MAX_M / _SEG / _MAX_N of include/gpmi355.h: what gp_vfe_batch hands to its kernels, and the observations per stream workgroup."""
+    txt = HEADER.read_text()
+    return {k: int(re.search(rf"#define GPMI355_VFE_BATCH_{k} (\d+)", txt).group(1)) for k in ("MAX_M", "SEG", "MAX_N")}
 
 
 def batch_pgrad_max_n() -> int:

@@ -2287,6 +2287,113 @@ def elbo(a, fx: FiniteGP, y):
 
 
 # --------------------------------------------------------------------------------------------
+# many small sparse GPs in one call: gp_vfe_batch
+# --------------------------------------------------------------------------------------------
+@dataclass(eq=False)
+class _VfeBatchCall:
+    """The marshalled arguments of one gp_vfe_batch call (everything after the ctx) and the buffers behind them."""
+
+    nb: int
+    nx: int
+    nz: int
+    ny: int
+    args: tuple
+    out: np.ndarray
+    info: np.ndarray
+    alphas: Optional[list]
+    m_eps: Optional[list]
+    keep: object
+
+
+def _vfe_batch_groups(approxs, fxs, ys) -> list:
+    """Checks and grouping of an elbo_batch call — needs no context and no device.  The groups are those of _batch_groups (ctx, dtype); each carries its
+    approximations in .xss and nz in .nxs."""
+    approxs, fxs = list(approxs), list(fxs)
+    nb = len(approxs)
+    if len(fxs) == 1 and nb > 1:
+        fxs = fxs * nb  # one FiniteGP for every problem: the same object (and x) in every entry
+    if len(fxs) != nb:
+        raise ValueError(f"DimensionMismatch: {nb} approximations but {len(fxs)} FiniteGPs")
+    if not (isinstance(ys, np.ndarray) and ys.ndim == 1) and len(ys) == 1 and nb > 1:
+        ys = [ys[0]] * nb
+    for a, fx in zip(approxs, fxs):
+        if not isinstance(a, (VFE, DTC)):
+            raise TypeError("elbo_batch: every approximation must be a VFE or a DTC")
+        if a.fz.f is not fx.f:  # @assert vfe.fz.f === fx.f  (:59, :249, :283)
+            raise AssertionError("vfe.fz.f === fx.f")
+        if isinstance(fx.f, GP) and _is_composite(fx.f.kernel):
+            raise NotImplementedError("VFE / DTC with a composite kernel are not accelerated (the exact path takes composite kernels)")
+        _refuse_dense_vfe(fx)
+        if np.ndim(a.fz.sigma2) != 0:
+            raise NotImplementedError("inducing-point noise must be a scalar jitter")
+    groups = _batch_groups(fxs, ys)
+    for g in groups:
+        g.xss = [approxs[i] for i in g.index]
+        g.nxs = 1 if all(a.fz.x is g.xss[0].fz.x for a in g.xss) else len(g.index)
+    return groups
+
+
+def _vfe_batch_marshal(g: _BatchGroup, return_alpha: bool, return_m_eps: bool) -> _VfeBatchCall:
+    """ctypes arguments of one group — needs no context."""
+    m = _Marshal(g.dtype)
+    nb = len(g.index)
+    pts = (gp_points * g.nx)(*[m.points(fx.x) for fx in g.fxs[:g.nx]])
+    zs = (gp_points * g.nxs)(*[m.points(a.fz.x) for a in g.xss[:g.nxs]])
+    dims = [pts[0 if g.nx == 1 else b].d for b in range(nb)]
+    karr = (gp_kernel * nb)(*[m.kernel(fx.f.kernel, d) for fx, d in zip(g.fxs, dims)])
+    narr = (gp_noise * nb)(*[m.noise(fx.sigma2, len(fx)) for fx in g.fxs])
+    jit = (C.c_double * nb)(*[float(a.fz.sigma2) for a in g.xss])
+    kinds = (C.c_int32 * nb)(*[0 if isinstance(a, VFE) else 1 for a in g.xss])
+    means = [_mean_vector(fx.f.mean_fn, fx.x, g.dtype) for fx in g.fxs]
+    means = [None if v is None else m.arr(v) for v in means]
+    marr = None if all(v is None for v in means) else (C.c_void_p * nb)(*[None if v is None else v.ctypes.data for v in means])
+    yarr = (C.c_void_p * g.ny)(*[m.arr(y).ctypes.data for y in g.ys[:g.ny]])
+    out = np.empty(nb, dtype=g.dtype)
+    info = np.zeros(nb, dtype=np.int32)
+
+    def outs(want):
+        if not want:
+            return None, None
+        bufs = [np.empty(len(a.fz), dtype=g.dtype) for a in g.xss]
+        return bufs, (C.c_void_p * nb)(*[v.ctypes.data for v in bufs])
+
+    alphas, aarr = outs(return_alpha)
+    m_eps, earr = outs(return_m_eps)
+    m.keep += [pts, zs, karr, narr, jit, kinds, marr, yarr, aarr, earr]
+    args = (nb, karr, g.nx, pts, g.nxs, zs, narr, jit, marr, g.ny, yarr, kinds, out.ctypes.data, info.ctypes.data_as(C.POINTER(C.c_int32)), aarr, earr)
+    return _VfeBatchCall(nb, g.nx, g.nxs, g.ny, args, out, info, alphas, m_eps, m)
+
+
+def approx_log_evidence_batch(approxs, fxs, ys, *, return_alpha: bool = False, return_m_eps: bool = False, on_error: str = "raise"):
+    """approx_log_evidence(approxs[b], fxs[b], ys[b]) of many independent sparse GPs in one library call per (ctx, dtype) group (gp_vfe_batch;
+    src/sparse_approximations.jl:248-313 once per problem): the ELBO for a VFE entry, the DTC evidence for a DTC entry; with return_alpha / return_m_eps also
+    the lists of α_b = U \\ m_ε and m_ε (:71-73).  fxs and ys may have length 1 (shared by every problem) or len(approxs); the same x / y / z object in
+    every entry is sent once.  on_error as in logpdf_batch.  Returns the array of objectives, followed by the lists that were asked for."""
+    if on_error not in ("raise", "nan"):
+        raise ValueError('on_error must be "raise" or "nan"')
+    approxs = list(approxs)
+    want = [return_alpha, return_m_eps]
+    if not approxs:
+        return (np.empty(0), *([] for w in want if w)) if any(want) else np.empty(0)
+    parts, lists = [], [[None] * len(approxs), [None] * len(approxs)]
+    for g in _vfe_batch_groups(approxs, fxs, ys):
+        call = _vfe_batch_marshal(g, return_alpha, return_m_eps)
+        ctx = g.ctx or default_context()
+        check(ctx.lib.gp_vfe_batch(ctx.handle, *call.args))
+        parts.append((g.index, call.out, call.info, None))
+        for dst, src in zip(lists, (call.alphas, call.m_eps)):
+            for i, v in zip(g.index, src or []):
+                dst[i] = v
+    obj = _batch_merge(len(approxs), parts, False, on_error)
+    return (obj, *(l for l, w in zip(lists, want) if w)) if any(want) else obj
+
+
+def elbo_batch(approxs, fxs, ys, **kw):
+    """The same call under the name the optimisers use: VFE entries give the ELBO (:254), DTC entries the DTC evidence, per problem."""
+    return approx_log_evidence_batch(approxs, fxs, ys, **kw)
+
+
+# --------------------------------------------------------------------------------------------
 # VFE / DTC for a matrix of observations: gp_vfe_fit_cols / _update_cols / _append_cols / _predict_cols / _get_cols / _get_by_cols / _grad_cols
 # --------------------------------------------------------------------------------------------
 @dataclass(eq=False)

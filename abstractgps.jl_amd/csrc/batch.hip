@@ -3,7 +3,8 @@
 // below), the predictions at each problem's test points from the slices it leaves (batch_predict_kernel, further down), the gradient of logpdf from the same
 // slices (batch_inv_kernel, batch_grad_kernel, batch_gsum_kernel, behind it; with the input gradient of gp_logpdf_grad_batch_x / gp_logpdf_grad_batch_sum_x:
 // batch_gradx_kernel, batch_gxsum_kernel) and the gradients of the predictions w.r.t. the test inputs from the strips the predict kernel leaves and the S of
-// batch_inv_kernel (batch_pgrad_kernel), last the joint predictive distribution from the same strips (batch_jcov_kernel, batch_jfact_kernel).
+// batch_inv_kernel (batch_pgrad_kernel), the joint predictive distribution from the same strips (batch_jcov_kernel, batch_jfact_kernel); last many small
+// sparse GPs in one call (gp_vfe_batch: vfe_prelude_kernel, vfe_stream_kernel, vfe_final_kernel, described in front of them).
 //
 // ONE workgroup owns ONE problem from its inputs to its scalar: it assembles the lower triangle of K + Σy into the problem's slice of a
 // workspace (δ = y − m riding along as row np, as in the single path), factors it by a blocked right-looking Cholesky (64-column blocks:
@@ -41,6 +42,8 @@ enum {
     BATCH_PRED_TILES = 1024      // predict workgroups per launch at most: a wave with more tiles of test points runs several predict launches
 };
 static const size_t BATCH_WS_BYTES = (size_t)4 << 30;  // workspace per launch at most: a larger batch runs in waves
+static const size_t BATCH_IN_BYTES = (size_t)3 << 28;  // packed input per wave at most, where a family counts it (WaveCost::in): with what every problem shares and the results it stays
+                                                        // inside the page-locked staging of a ctx, so a wave's copies never take the pageable path
 static const size_t JOINT_PIN_BYTES = (size_t)1 << 30;  // what the page-locked staging of a ctx takes (ctx_pinned): a wave of gp_joint_batch stays below it
 
 // One problem of a wave, first thing in the packed input.  Offsets count doubles: *_off into the packed input (−1: absent), a_off into the
@@ -267,6 +270,33 @@ __device__ __forceinline__ int batch_chol(double* __restrict__ A, long ld, int n
     return failcol;
 }
 
+// zs ← L⁻ᵀ zs for the factor in the lower triangle of a slice (nt blocks of 64 columns), the vector in LDS: block after block from the last one, the diagonal
+// block in LDS and solved by wave 0 (one lane per entry), then the entries left of it updated, one per thread.
+__device__ __forceinline__ void back_sweep(const double* __restrict__ A, long ld, int nt, double* zs, double (*Ls)[BTS], int tid, int lane, int w) {
+    for (int kb = nt - 1; kb >= 0; --kb) {
+        const int j0 = kb * BT;
+        for (int e = tid; e < BT * BT; e += NT) Ls[e >> 6][e & 63] = A[(long)(j0 + (e >> 6)) * ld + j0 + (e & 63)];
+        __syncthreads();
+        if (w == 0) {
+            double v = zs[j0 + lane], out = 0.0;
+#pragma unroll
+            for (int j = BT - 1; j >= 0; --j) {
+                const double aj = lane_bcast<double>(v, j) / Ls[j][j];
+                if (lane == j) out = aj;
+                if (lane < j) v = fma(-Ls[j][lane], aj, v);
+            }
+            zs[j0 + lane] = out;
+        }
+        __syncthreads();
+        for (int cc = tid; cc < j0; cc += NT) {
+            double s = zs[cc];
+            for (int i = 0; i < BT; ++i) s = fma(-A[(long)(j0 + i) * ld + cc], zs[j0 + i], s);
+            zs[cc] = s;
+        }
+        __syncthreads();
+    }
+}
+
 template <bool SUM>
 __global__ __launch_bounds__(NT) void batch_logpdf_kernel(const double* __restrict__ in, double* __restrict__ ws, double* __restrict__ res, int nw) {
     __shared__ double Ls[BT][BTS];
@@ -347,28 +377,7 @@ __global__ __launch_bounds__(NT) void batch_logpdf_kernel(const double* __restri
     if (!alpha) return;
 
     // ---- 4. α = L⁻ᵀ z: backward sweep, the solved row in LDS
-    for (int kb = nt - 1; kb >= 0; --kb) {
-        const int j0 = kb * BT;
-        for (int e = tid; e < BT * BT; e += NT) Ls[e >> 6][e & 63] = A[(long)(j0 + (e >> 6)) * ld + j0 + (e & 63)];
-        __syncthreads();
-        if (w == 0) {
-            double v = zs[j0 + lane], out = 0.0;
-#pragma unroll
-            for (int j = BT - 1; j >= 0; --j) {
-                const double aj = lane_bcast<double>(v, j) / Ls[j][j];
-                if (lane == j) out = aj;
-                if (lane < j) v = fma(-Ls[j][lane], aj, v);
-            }
-            zs[j0 + lane] = out;
-        }
-        __syncthreads();
-        for (int cc = tid; cc < j0; cc += NT) {
-            double s = zs[cc];
-            for (int i = 0; i < BT; ++i) s = fma(-A[(long)(j0 + i) * ld + cc], zs[j0 + i], s);
-            zs[cc] = s;
-        }
-        __syncthreads();
-    }
+    back_sweep(A, ld, nt, zs, Ls, tid, lane, w);
     for (int j = tid; j < n; j += NT) alpha[j] = zs[j];
 }
 
@@ -1265,6 +1274,372 @@ __global__ __launch_bounds__(NT) void batch_jfact_kernel(const double* __restric
     }
 }
 
+// ---- many small sparse GPs (VFE / DTC, gp_vfe_batch): vfe_prelude_kernel, vfe_stream_kernel, vfe_final_kernel ----------------------------------------------
+// The formulation of vfe.hpp (S = Σy^-1/2, L_z L_zᵀ = K_zz + jitter·I):  B = L_z⁻¹ K_zx S,  G = B Bᵀ,  Λ_ε = I + G,  c = B b_y,  m_ε = Λ_ε \ c,  α = L_z⁻ᵀ m_ε,
+//   dtc = −½ (n log 2π + log|Σy| + log|Λ_ε| + ‖b_y‖² − ‖L_D⁻¹ c‖²),   elbo = dtc − ½ (tr(K_ff Σy⁻¹) − tr G).
+// Three launches on one stream, launch boundaries the only synchronisation: the M×M prelude per problem, the N-long pass per (problem, segment of VFE_SEG
+// observations) and the M×M finalisation per problem, which adds the segments' partial sums in segment order.  No flags, no tickets, no floating-point atomics;
+// every loop is bounded by the problem's sizes and every sum runs in an order they alone fix.
+enum {
+    VFE_SEG = GPMI355_VFE_BATCH_SEG,    // consecutive observations per workgroup of the stream kernel: 32 tiles — the 74 KB of W a workgroup loads and the 132 KB
+                                        // of partial sums it stores cost about one tile's work each, and an n of 16 384 already spreads over eight workgroups
+    VFE_MAXM = GPMI355_VFE_BATCH_MAX_M,
+    VT = 64,                            // observations per tile: one per lane in the Gram evaluation
+    KBS = 65,                           // LDS row stride of the tile K̃ / B (odd: the row-wise operand reads of B Bᵀ are conflict-free, like BTS)
+    VFE_KERNEL_MAX_N = 1 << 24          // what the measurement override admits at most (the segment table of a problem stays small)
+};
+static_assert(VFE_SEG % VT == 0 && VFE_MAXM % BT == 0 && VFE_MAXM <= 128, "the stream kernel's wave mapping is laid out for M <= 128");
+
+// One problem of a wave, in a table behind the packed data.  Offsets count doubles: z_off (the pseudo-inputs, scaled on the host as the sparse path scales
+// them, [d][m]), x_off (raw, [d][n]: shared between problems with different transforms, so the kernel applies the scale at the load — the same product the
+// host forms for the single path), y_off, m_off, nz_off (−1: absent) into the packed input; lz_off (the slice of L_z), w_off (the strip L_z⁻ᵀ, np rows of ld),
+// d_off (the slice of Λ_ε) and part_off (nseg slots of vfe_part(np)) into the workspace; alpha_off / meps_off into the result buffer (−1: not wanted).
+struct VfeProb {
+    long z_off, x_off, y_off, m_off, nz_off, lz_off, w_off, d_off, part_off, alpha_off, meps_off;
+    int n, m, np, ld, d, kind, nscale, slot, approx, nseg;
+    double variance, noise_s, jitter;
+    double scale[BATCH_MAXD];
+};
+static_assert(sizeof(VfeProb) % 8 == 0, "the tables are packed behind double data");
+struct VfeSeg {
+    int prob, seg;
+};
+static_assert(sizeof(VfeSeg) % 8 == 0, "the tables are packed behind double data");
+// a segment's slot of partial sums: G (np × np, the 32×32 tiles of the lower triangle written), c (np), Σ b², Σ log σ², Σ variance / σ² (+ padding)
+__host__ __device__ static inline long vfe_part(long np) { return np * np + np + 8; }
+
+// variance · κ of the squared length of t (inputs scaled beforehand)
+__device__ __forceinline__ double vfe_kval(const VfeProb& P, const double (&t)[BATCH_MAXD]) {
+    double d2 = 0.0;
+#pragma unroll
+    for (int p = 0; p < BATCH_MAXD; ++p) d2 = fma(t[p], t[p], d2);
+    return P.variance * kappa<double>(P.kind, d2);
+}
+
+// One workgroup per problem: the lower triangle of K_zz + jitter·I into the problem's slice (identity padding; the carried row and the 31 rows behind it zero),
+// batch_chol, then W = L_z⁻¹ as the strip V = L_z⁻ᵀ = Wᵀ by the substitution of batch_inv_kernel (strip_solve on the identity rows).  A failed factor marks
+// the problem (NaN and the minor's order in the result buffer): the later launches never read its slice.
+__global__ __launch_bounds__(NT) void vfe_prelude_kernel(const double* __restrict__ in, double* __restrict__ ws, double* __restrict__ res, int nw,
+                                                         const VfeProb* __restrict__ vps) {
+    __shared__ double sh[BT * BTS + BT];  // L_bb [BT][BTS] and 1 / L_jj behind it
+    __shared__ double red[BT];
+    const VfeProb& P = vps[blockIdx.x];
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int m = P.m, np = P.np, d = P.d;
+    const long ld = P.ld;
+    const int nt = np / BT;
+    double* __restrict__ Lz = ws + P.lz_off;
+    const double* __restrict__ z = in + P.z_off;
+    for (int ti = 0; ti < nt; ++ti)
+        for (int tj = 0; tj <= ti; ++tj) {
+            const int j = tj * BT + lane;
+            double zj[BATCH_MAXD];
+            batch_load_point(z, m, d, j, zj);
+            for (int rr = 0; rr < BT / 8; ++rr) {
+                const int i = ti * BT + w + 8 * rr;  // wave-uniform
+                double v;
+                if (i >= m || j >= m) {
+                    v = (i == j) ? 1.0 : 0.0;
+                } else {
+                    double t[BATCH_MAXD];
+                    batch_diff(z, m, d, i, zj, t);
+                    v = vfe_kval(P, t);
+                    if (i == j) v += P.jitter;
+                }
+                Lz[(long)i * ld + j] = v;
+            }
+        }
+    for (int j = tid; j < np; j += NT)
+        for (int r = 0; r < 32; ++r) Lz[(long)(np + r) * ld + j] = 0.0;
+    __syncthreads();
+    double logdet_half = 0.0;
+    const int failcol = batch_chol(Lz, ld, m, np, tid, lane, w, reinterpret_cast<double (*)[BTS]>(sh), sh + BT * BTS, red, logdet_half);
+    if (tid == 0) {
+        res[P.slot] = failcol ? __builtin_nan("") : 0.0;
+        res[nw + P.slot] = (double)failcol;
+    }
+    if (failcol) return;
+    double* __restrict__ V = ws + P.w_off;
+    for (int e = tid; e < np * np; e += NT) {
+        const int i = e / np, cc = e - i * np;
+        V[(long)i * ld + cc] = i == cc ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    (void)strip_solve(V, Lz, ld, 0, nt, np, sh, tid, lane, w);
+}
+
+// (ti, tj) of the t-th 32×32 tile of a lower triangle counted row by row
+__device__ __forceinline__ void lower_tile(int t, int& ti, int& tj) {
+    ti = 0;
+    while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
+    tj = t - ti * (ti + 1) / 2;
+}
+// g4 += B[i0 … i0 + 31, :] B[c0 … c0 + 31, :]ᵀ over the 64 observations of the tile in LDS: step s multiplies the observations {4 s + g}, a fixed order
+__device__ __forceinline__ void vfe_syrk_tile(d4_t (&g4)[2][2], const double* KB, int i0, int c0, int lane) {
+    const int r = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int s = 0; s < VT / 4; ++s) {
+        const int k = 4 * s + g;
+        const double a0 = KB[(i0 + r) * KBS + k], a1 = KB[(i0 + 16 + r) * KBS + k];
+        const double b0 = KB[(c0 + r) * KBS + k], b1 = KB[(c0 + 16 + r) * KBS + k];
+        g4[0][0] = Tr<double>::mfma(a0, b0, g4[0][0]);
+        g4[0][1] = Tr<double>::mfma(a0, b1, g4[0][1]);
+        g4[1][0] = Tr<double>::mfma(a1, b0, g4[1][0]);
+        g4[1][1] = Tr<double>::mfma(a1, b1, g4[1][1]);
+    }
+}
+
+// One workgroup per (problem, segment): the observations [seg·VFE_SEG, min(n, (seg + 1)·VFE_SEG)) in tiles of 64.  LDS (140.8 KB of the CU's 160: one workgroup,
+// eight waves, per CU): W = L_z⁻¹ as the 16×16 blocks of its lower triangle, each stored k-major (Wt[blk][k][row]: what the strip V = Wᵀ holds row by row, and
+// the MFMA's A operand reads 16 consecutive doubles of it: conflict-free) — 36 blocks, 73.7 KB at M = 128, resident for the whole segment; the tile buffer KB
+// (np rows × 64 observations, stride 65, 66.6 KB), which holds K̃ and then B; the 64 entries of b_y.  Per tile:
+//   1. K̃[i][j] = variance κ(z_i, x_j) σ_j⁻¹: lane = observation (its inputs scaled at the load, σ_j⁻¹ and b_j formed here; zeros beyond n), the eight waves
+//      interleave the pseudo-points (wave-uniform: their inputs by scalar loads); rows from m on are zero.  Wave 0 keeps the three scalar sums per lane.
+//   2. B = W K̃: wave w owns the column block w & 3 (16 observations) and the row blocks (w >> 2), (w >> 2) + 2, … — up to four 16×16 accumulators; the k loop
+//      of row block bi runs over the blocks 0 … bi alone (W is lower triangular).  All waves finish reading K̃ before any writes B over it.
+//   3. G += B Bᵀ on the 32×32 tiles of the lower triangle, accumulators in registers across the whole segment: ten tiles at np = 128 — wave w holds tile w, the
+//      waves 6 and 7 also the tiles 8 and 9 (three at np = 64: the waves 0 … 2).  Eight waves and not ten: step 2 splits evenly over eight (4 column blocks × 2 row
+//      parities), and the two double-loaded waves sit on different SIMDs (6 and 7 mod 4), so each SIMD's MFMA pipe serves at most three tiles of the ten.
+//   4. c += B b_y: thread i < np owns c_i (the waves 0 and 1, which hold one tile each), the 64 products in observation order.
+// The segment's G tiles, c and scalar sums go to its own slot.  A problem whose prelude failed returns at once.
+__global__ __launch_bounds__(NT) void vfe_stream_kernel(const double* __restrict__ in, double* __restrict__ ws, const double* __restrict__ res, int nw,
+                                                        const VfeProb* __restrict__ vps, const VfeSeg* __restrict__ segs) {
+    __shared__ double Wt[(VFE_MAXM / 16) * (VFE_MAXM / 16 + 1) / 2 * 256];
+    __shared__ double KB[VFE_MAXM * KBS];
+    __shared__ double bs[VT];
+    const VfeSeg S = segs[blockIdx.x];
+    const VfeProb& P = vps[S.prob];
+    if (res[nw + P.slot] != 0.0) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 15, g = lane >> 4;
+    const int n = P.n, m = P.m, np = P.np, d = P.d, nscale = P.nscale;
+    const long ld = P.ld;
+    const int nb16 = np / 16, ntl = (np / 32) * (np / 32 + 1) / 2;
+    const double* __restrict__ z = in + P.z_off;
+    const double* __restrict__ x = in + P.x_off;
+    const double* __restrict__ y = in + P.y_off;
+    {
+        const double* __restrict__ V = ws + P.w_off;
+        int cnt = 0;
+        for (int bi = 0; bi < nb16; ++bi)
+            for (int bk = 0; bk <= bi; ++bk, ++cnt) {
+                if ((cnt & 7) != w) continue;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int e = lane + 64 * q;  // e = 16 k + row
+                    Wt[cnt * 256 + e] = V[(long)(16 * bk + (e >> 4)) * ld + 16 * bi + (e & 15)];
+                }
+            }
+    }
+    // the wave's tiles of G
+    int i0a = 0, c0a = 0, i0b = 0, c0b = 0;
+    const bool has_a = w < ntl, has_b = w >= 6 && w + 2 < ntl;
+    if (has_a) {
+        int ti, tj;
+        lower_tile(w, ti, tj);
+        i0a = 32 * ti, c0a = 32 * tj;
+    }
+    if (has_b) {
+        int ti, tj;
+        lower_tile(w + 2, ti, tj);
+        i0b = 32 * ti, c0b = 32 * tj;
+    }
+    d4_t ga[2][2], gb[2][2];
+    acc_zero(ga);
+    acc_zero(gb);
+    double cacc = 0.0, sb2 = 0.0, slog = 0.0, sinv = 0.0;
+    const long o0 = (long)S.seg * VFE_SEG;
+    const int cnt = n - o0 < VFE_SEG ? (int)(n - o0) : (int)VFE_SEG;
+    __syncthreads();
+    for (int t0 = 0; t0 < cnt; t0 += VT) {
+        // ---- 1. K̃ into LDS
+        {
+            const bool valid = t0 + lane < cnt;
+            const long j = o0 + t0 + lane;
+            double xj[BATCH_MAXD];
+#pragma unroll
+            for (int p = 0; p < BATCH_MAXD; ++p)
+                xj[p] = (p < d && valid) ? (nscale == 0 ? 1.0 : P.scale[nscale == 1 ? 0 : p]) * x[(long)p * n + j] : 0.0;
+            double rs = 0.0;
+            if (valid) {
+                const double s2 = P.nz_off >= 0 ? in[P.nz_off + j] : P.noise_s;
+                rs = 1.0 / sqrt(s2);
+                if (w == 0) {
+                    const double bj = (y[j] - (P.m_off >= 0 ? in[P.m_off + j] : 0.0)) * rs;
+                    bs[lane] = bj;
+                    sb2 = fma(bj, bj, sb2);
+                    if (P.nz_off >= 0) {
+                        slog += log(s2);
+                        sinv += P.variance / s2;
+                    }
+                }
+            } else if (w == 0) {
+                bs[lane] = 0.0;
+            }
+            for (int rr = 0; rr < np / 8; ++rr) {
+                const int i = w + 8 * rr;  // wave-uniform
+                double v = 0.0;
+                if (i < m && valid) {
+                    double t[BATCH_MAXD];
+                    batch_diff(z, m, d, i, xj, t);
+                    v = vfe_kval(P, t) * rs;
+                }
+                KB[i * KBS + lane] = v;
+            }
+        }
+        __syncthreads();
+        // ---- 2. B = W K̃ over the non-zero k blocks, into registers; then over K̃
+        {
+            const int cb = w & 3;
+            d4_t acc[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                acc[q] = 0.0;
+                const int bi = (w >> 2) + 2 * q;
+                if (bi < nb16) {
+                    const double* wb = Wt + bi * (bi + 1) / 2 * 256;
+                    for (int bk = 0; bk <= bi; ++bk, wb += 256)
+#pragma unroll
+                        for (int s = 0; s < 4; ++s)
+                            acc[q] = Tr<double>::mfma(wb[(4 * s + g) * 16 + r], KB[(16 * bk + 4 * s + g) * KBS + 16 * cb + r], acc[q]);
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int bi = (w >> 2) + 2 * q;
+                if (bi < nb16)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) KB[(16 * bi + Tr<double>::crow(lane, e)) * KBS + 16 * cb + r] = acc[q][e];
+            }
+        }
+        __syncthreads();
+        // ---- 3. G += B Bᵀ;  4. c += B b_y
+        if (has_a) vfe_syrk_tile(ga, KB, i0a, c0a, lane);
+        if (has_b) vfe_syrk_tile(gb, KB, i0b, c0b, lane);
+        if (tid < np)
+            for (int j = 0; j < VT; ++j) cacc = fma(KB[tid * KBS + j], bs[j], cacc);
+        __syncthreads();
+    }
+    double* __restrict__ part = ws + P.part_off + (long)S.seg * vfe_part(np);
+    if (has_a) acc_store(ga, part, i0a, c0a, np, lane);
+    if (has_b) acc_store(gb, part, i0b, c0b, np, lane);
+    if (tid < np) part[(long)np * np + tid] = cacc;
+    if (w == 0) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            sb2 += __shfl_xor(sb2, o, 64);
+            slog += __shfl_xor(slog, o, 64);
+            sinv += __shfl_xor(sinv, o, 64);
+        }
+        if (lane == 0) {
+            double* sc = part + (long)np * np + np;
+            sc[0] = sb2;
+            sc[1] = slog;
+            sc[2] = sinv;
+        }
+    }
+}
+
+// One workgroup per problem: the segments' partial sums in segment order into the slice of Λ_ε = I + G (c as the carried row np, the layout batch_logpdf_kernel
+// uses for δ), batch_chol, the objective from Σ log L_D,ii, ‖L_D⁻¹ c‖² (the carried row) and the scalar sums (a scalar σ²: n log σ² and n variance / σ², as the
+// single path forms them), then m_ε = L_D⁻ᵀ (L_D⁻¹ c) and α = L_z⁻ᵀ m_ε by back_sweep where they are wanted.  A problem whose prelude failed gets NaN weights
+// here (objective and info are the prelude's); a Λ_ε that is not positive definite is data in the same way.
+__global__ __launch_bounds__(NT) void vfe_final_kernel(const double* __restrict__ in, double* __restrict__ ws, double* __restrict__ res, int nw,
+                                                       const VfeProb* __restrict__ vps) {
+    __shared__ double Ls[BT][BTS];
+    __shared__ double dinv[BT];
+    __shared__ double red[NT];
+    __shared__ double zs[VFE_MAXM];
+    const VfeProb& P = vps[blockIdx.x];
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = P.n, m = P.m, np = P.np, nseg = P.nseg;
+    const long ld = P.ld, psz = vfe_part(np);
+    const int nt = np / BT;
+    double* alpha = P.alpha_off >= 0 ? res + P.alpha_off : nullptr;
+    double* meps = P.meps_off >= 0 ? res + P.meps_off : nullptr;
+    auto nan_weights = [&] {
+        if (tid < m) {
+            if (alpha) alpha[tid] = __builtin_nan("");
+            if (meps) meps[tid] = __builtin_nan("");
+        }
+    };
+    if (res[nw + P.slot] != 0.0) {
+        nan_weights();
+        return;
+    }
+    double* __restrict__ D = ws + P.d_off;
+    const double* __restrict__ part = ws + P.part_off;
+    for (int e = tid; e < np * np; e += NT) {
+        const int i = e / np, j = e - i * np;
+        double s = 0.0;
+        if ((j >> 5) <= (i >> 5))
+            for (int sg = 0; sg < nseg; ++sg) s += part[sg * psz + e];
+        if (i == j) {
+            zs[i] = i < m ? s : 0.0;  // the diagonal of G, for its trace
+            s += 1.0;
+        }
+        D[(long)i * ld + j] = s;
+    }
+    for (int j = tid; j < np; j += NT) {
+        double s = 0.0;
+        for (int sg = 0; sg < nseg; ++sg) s += part[sg * psz + (long)np * np + j];
+        D[(long)np * ld + j] = s;
+        for (int r = 1; r < 32; ++r) D[(long)(np + r) * ld + j] = 0.0;
+    }
+    double dd = 0.0, logdet_sy = 0.0, tr_kff = 0.0, tr_g = 0.0;  // thread 0
+    __syncthreads();
+    if (tid == 0) {
+        for (int sg = 0; sg < nseg; ++sg) {
+            const double* sc = part + sg * psz + (long)np * np + np;
+            dd += sc[0];
+            logdet_sy += sc[1];
+            tr_kff += sc[2];
+        }
+        if (P.nz_off < 0) {
+            logdet_sy = (double)n * log(P.noise_s);
+            tr_kff = (double)n * (P.variance / P.noise_s);
+        }
+        for (int i = 0; i < m; ++i) tr_g += zs[i];
+    }
+    __syncthreads();
+    double logdet_half = 0.0;
+    const int failcol = batch_chol(D, ld, m, np, tid, lane, w, Ls, dinv, red, logdet_half);
+    if (failcol) {
+        if (tid == 0) {
+            res[P.slot] = __builtin_nan("");
+            res[nw + P.slot] = (double)failcol;
+        }
+        nan_weights();
+        return;
+    }
+    {  // ‖L_D⁻¹ c‖² from the carried row, as batch_logpdf_kernel reads ‖L⁻¹δ‖²
+        double s = 0.0;
+        for (int j = tid; j < np; j += NT) {
+            const double v = D[(long)np * ld + j];
+            zs[j] = v;
+            s = fma(v, v, s);
+        }
+        red[tid] = s;
+        __syncthreads();
+        for (int h = NT / 2; h > 0; h >>= 1) {
+            if (tid < h) red[tid] += red[tid + h];
+            __syncthreads();
+        }
+        if (tid == 0) {
+            double obj = -0.5 * ((double)n * 1.8378770664093454835606594728112 + logdet_sy + 2.0 * logdet_half + dd - red[0]);
+            if (P.approx == 0) obj -= 0.5 * (tr_kff - tr_g);
+            res[P.slot] = obj;
+        }
+    }
+    if (!alpha && !meps) return;
+    back_sweep(D, ld, nt, zs, Ls, tid, lane, w);
+    if (meps && tid < m) meps[tid] = zs[tid];
+    if (!alpha) return;
+    back_sweep(ws + P.lz_off, ld, nt, zs, Ls, tid, lane, w);
+    if (tid < m) alpha[tid] = zs[tid];
+}
+
 }  // namespace gpmi
 
 using namespace gpmi;
@@ -1304,7 +1679,7 @@ BatchArgs base_args(int32_t nb, const K* k, int32_t nx, const gp_points* x, cons
 }
 
 // a size limit of the header; the environment variable read at the call site overrides it for measurements (0 … what the kernels admit)
-long env_capped(const char* env, long deflt) { return std::max(0L, std::min<long>(env ? atol(env) : deflt, BATCH_KERNEL_MAX_N)); }
+long env_capped(const char* env, long deflt, long cap = BATCH_KERNEL_MAX_N) { return std::max(0L, std::min<long>(env ? atol(env) : deflt, cap)); }
 void fill_nan(void* out, int dtype, long n) {
     if (!out) return;
     if (dtype == 0) std::fill_n((double*)out, n, std::numeric_limits<double>::quiet_NaN());
@@ -1543,18 +1918,20 @@ void split_by_path(const BatchArgs& a, long max_n, std::vector<int>& mine, std::
     for (int b = 0; b < a.nb; ++b) (batch_takes(a, b, max_n) ? mine : routed).push_back(b);
 }
 
-// workspace bytes of one problem: `own` adds up over a wave, `shared` is needed once per wave, as wide as the widest problem asks for
-struct WaveCost { size_t own, shared; };
+// workspace bytes of one problem: `own` adds up over a wave, `shared` is needed once per wave, as wide as the widest problem asks for; `in`: the bytes the problem
+// alone adds to the wave's packed input, where they are not small beside its workspace (gp_vfe_batch: n reaches 262 144) — they add up against the staging limit
+struct WaveCost { size_t own, shared, in = 0; };
 // The kernel's problems in waves bounded by the launch size and by the workspace budget (a wave holds at least one problem); run(idx, nw) serves one wave.
 template <class Cost, class Run> int32_t for_each_wave(gp_ctx* c, const std::vector<int>& mine, Cost&& cost, Run&& run) {
     if (mine.empty()) return 0;
     HIPCHK(hipSetDevice(c->device));
     for (size_t i = 0, j; i < mine.size(); i = j) {
-        size_t own = 0, shared = 0;
+        size_t own = 0, shared = 0, in = 0;
         for (j = i; j < mine.size() && j - i < BATCH_WAVE_PROBLEMS; ++j) {
             const WaveCost w = cost(mine[j]);
-            if (j > i && own + w.own + std::max(shared, w.shared) > BATCH_WS_BYTES) break;
+            if (j > i && (own + w.own + std::max(shared, w.shared) > BATCH_WS_BYTES || in + w.in > BATCH_IN_BYTES)) break;
             own += w.own;
+            in += w.in;
             shared = std::max(shared, w.shared);
         }
         RC(run(mine.data() + i, (int)(j - i)));
@@ -2477,6 +2854,177 @@ int32_t loo_grad_batch_impl(gp_ctx* c, LooArgs& a) {
     return 0;
 }
 
+// ---- gp_vfe_batch ------------------------------------------------------------------------------------------------------------------------------------------
+struct VfeArgs : BatchArgs {  // logpdf_out is objective_out
+    int32_t nz;
+    const gp_points* z;
+    const double* jitter;
+    const int32_t* approx;
+    void* const* meps_out;
+    const gp_points& zb(int b) const { return z[nz == 1 ? 0 : b]; }
+    void* eb(int b) const { return meps_out ? meps_out[b] : nullptr; }
+};
+
+// the pseudo-inputs of one problem, dimension-major [d][m], scaled as the sparse path scales its inputs on the host (one product per entry)
+void pack_scaled_points(const gp_kernel& k, const gp_points& z, double* out) {
+    pack_points(z, out);
+    for (int dd = 0; dd < z.d && k.nscale > 0; ++dd) {
+        const double s = k.scale[k.nscale == 1 ? 0 : dd];
+        for (long i = 0; i < z.n; ++i) out[(size_t)dd * z.n + i] *= s;
+    }
+}
+
+int32_t check_vfe_args(VfeArgs& a) {
+    if (!a.k) return set_arg_err(3, "kernel array is NULL");
+    if (a.nx != 1 && a.nx != a.nb) return set_arg_err(4, "nx must be 1 (one x shared by every problem) or nb");
+    if (!a.x) return set_arg_err(5, "points array is NULL");
+    if (a.nz != 1 && a.nz != a.nb) return set_arg_err(6, "nz must be 1 (one z shared by every problem) or nb");
+    if (!a.z) return set_arg_err(7, "pseudo-points array is NULL");
+    if (!a.noise) return set_arg_err(8, "noise array is NULL");
+    if (!a.jitter) return set_arg_err(9, "jitter array is NULL");
+    if (a.ny != 1 && a.ny != a.nb) return set_arg_err(11, "ny must be 1 (one y shared by every problem) or nb");
+    if (!a.y) return set_arg_err(12, "y array is NULL");
+    for (int b = 0; b < a.ny; ++b)
+        if (!a.y[b]) return set_arg_err(12, "a y pointer is NULL");
+    if (!a.approx) return set_arg_err(13, "approx array is NULL");
+    if (!a.logpdf_out) return set_arg_err(14, "objective_out is NULL");
+    if (!a.info_out) return set_arg_err(15, "info_out is NULL");
+    a.dtype = a.k[0].dtype;
+    for (int b = 0; b < a.nb; ++b) {
+        const gp_points &x = a.xb(b), &z = a.zb(b);
+        RC(check_points(&x, 5));
+        RC(check_points(&z, 7));
+        if (z.d != x.d) return set_arg_err(7, "z has a different D than x");
+        RC(check_kernel(&a.k[b], x.d, 3));
+        if (a.k[b].dtype != a.dtype) return set_arg_err(3, "every descriptor of one batch call carries the same dtype");
+        RC(check_noise(&a.noise[b], 8, true));
+        if (!(a.jitter[b] >= 0)) return set_arg_err(9, "jitter must be >= 0");
+        if (a.ny == 1 && x.n != a.xb(0).n) return set_arg_err(11, "a shared y needs problems of one size");
+        if (a.approx[b] != 0 && a.approx[b] != 1) return set_arg_err(13, "approx must be 0 (VFE) or 1 (DTC)");
+    }
+    return 0;
+}
+
+// which path serves a problem depends on that problem alone (a noise variance that is not positive is the single path's to report)
+bool vfe_batch_takes(const VfeArgs& a, int b, long max_n) {
+    const gp_points& x = a.xb(b);
+    const gp_noise& nz = a.noise[b];
+    if (a.dtype != 0 || nz.kind > 1 || x.d > BATCH_MAXD || a.zb(b).n > VFE_MAXM || x.n > max_n) return false;
+    if (nz.kind == 0) return nz.s > 0;
+    const double* dg = (const double*)nz.diag;
+    return std::all_of(dg, dg + x.n, [](double v) { return v > 0; });
+}
+
+long vfe_nseg(long n) { return (n + VFE_SEG - 1) / VFE_SEG; }
+// workspace doubles of one problem: the slices of L_z and Λ_ε, the strip L_z⁻ᵀ and a slot of partial sums per segment
+long vfe_ws(const VfeArgs& a, int b) {
+    const long m = a.zb(b).n, np = batch_np(m);
+    return 2 * batch_slice(m) + np * batch_ld(np) + vfe_nseg(a.xb(b).n) * vfe_part(np);
+}
+
+// doubles problem b alone adds to the packed input of its wave: its z, mean and noise vector, and its x and y where the problems do not share them
+long vfe_in(const VfeArgs& a, int b) {
+    const gp_points &x = a.xb(b), &z = a.zb(b);
+    return (long)z.d * z.n + (a.nx == 1 ? 0 : (long)x.d * x.n) + (a.ny == 1 ? 0 : x.n) + (a.mb(b) ? x.n : 0) + (a.noise[b].kind == 1 ? x.n : 0);
+}
+
+// fills the data of a laid-out wave behind its tables: every problem's scaled z, then x and y (a shared one once), mean and noise vector
+void vfe_wave_fill(const VfeArgs& a, const int* idx, int nw, const std::vector<VfeProb>& pr, double* hin) {
+    SharedOnce xo{a.nx == 1}, yo{a.ny == 1};
+    for (int t = 0; t < nw; ++t) {
+        const int b = idx[t];
+        const gp_points& x = a.xb(b);
+        const VfeProb& p = pr[t];
+        pack_scaled_points(a.k[b], a.zb(b), hin + p.z_off);
+        if (xo.claim()) pack_points(x, hin + p.x_off);
+        if (yo.claim()) std::memcpy(hin + p.y_off, a.yb(b), sizeof(double) * x.n);
+        if (p.m_off >= 0) std::memcpy(hin + p.m_off, a.mb(b), sizeof(double) * x.n);
+        if (p.nz_off >= 0) std::memcpy(hin + p.nz_off, a.noise[b].diag, sizeof(double) * x.n);
+    }
+}
+
+// three launches: the problems idx[0..nw) of the call, all taken by the kernels.  Caller holds the ctx lock.
+int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw) {
+    WaveLayout L;
+    L.roff = 2L * nw;
+    Table<VfeProb> vp;
+    Table<VfeSeg> sg;
+    vp.v.assign((size_t)nw, VfeProb{});
+    vp.place(L);
+    SharedOnce xo{a.nx == 1}, yo{a.ny == 1};
+    for (int t = 0; t < nw; ++t) {
+        const int b = idx[t];
+        const gp_points &x = a.xb(b), &z = a.zb(b);
+        const gp_kernel& k = a.k[b];
+        VfeProb& p = vp.v[t];
+        p.n = (int)x.n, p.m = (int)z.n, p.np = (int)batch_np(z.n), p.ld = (int)batch_ld(p.np), p.d = x.d;
+        p.kind = k.kind, p.nscale = k.nscale, p.slot = t, p.approx = a.approx[b], p.nseg = (int)vfe_nseg(x.n);
+        p.variance = k.variance, p.noise_s = a.noise[b].s, p.jitter = a.jitter[b];
+        for (int q = 0; q < k.nscale; ++q) p.scale[q] = k.scale[q];
+        p.z_off = take(L.off, (long)z.d * z.n);
+        p.x_off = xo.place(L.off, (long)x.d * x.n);
+        p.y_off = yo.place(L.off, x.n);
+        p.m_off = a.mb(b) ? take(L.off, x.n) : -1;
+        p.nz_off = a.noise[b].kind == 1 ? take(L.off, x.n) : -1;
+        p.lz_off = take(L.ws, batch_slice(z.n));
+        p.w_off = take(L.ws, (long)p.np * p.ld);
+        p.d_off = take(L.ws, batch_slice(z.n));
+        p.part_off = take(L.ws, p.nseg * vfe_part(p.np));
+        p.alpha_off = a.ab(b) ? take(L.roff, z.n) : -1;
+        p.meps_off = a.eb(b) ? take(L.roff, z.n) : -1;
+        for (int s = 0; s < p.nseg; ++s) sg.v.push_back(VfeSeg{t, s});
+    }
+    sg.place(L);
+    WaveMem m(c);
+    RC(m.alloc(L.off, L.ws, L.roff));
+    vp.fill(m);
+    sg.fill(m);
+    vfe_wave_fill(a, idx, nw, vp.v, m.hin);
+    RC(run_drained(c, [&]() -> int32_t {
+        RC(m.upload());
+        RC(launch(m, vfe_prelude_kernel, nw, NT, nw, vp.dev(m)));
+        RC(launch(m, vfe_stream_kernel, sg.v.size(), NT, nw, vp.dev(m), sg.dev(m)));
+        RC(launch(m, vfe_final_kernel, nw, NT, nw, vp.dev(m)));
+        return m.download_and_sync();
+    }));
+    c->vfe_batch_problems += nw;
+    for (int t = 0; t < nw; ++t) {
+        const int b = idx[t];
+        const VfeProb& p = vp.v[t];
+        put_result(a, b, m.hout[t], (int32_t)m.hout[nw + t]);
+        if (p.alpha_off >= 0) std::memcpy(a.ab(b), m.hout + p.alpha_off, sizeof(double) * p.m);
+        if (p.meps_off >= 0) std::memcpy(a.eb(b), m.hout + p.meps_off, sizeof(double) * p.m);
+    }
+    return 0;
+}
+
+int32_t vfe_batch_impl(gp_ctx* c, VfeArgs& a) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    if (a.nb < 0) return set_arg_err(2, "nb must be >= 0");
+    if (a.nb == 0) return 0;
+    RC(check_vfe_args(a));
+    const long max_n = env_capped(getenv("GPMI_VFE_BATCH_MAX_N"), GPMI355_VFE_BATCH_MAX_N, VFE_KERNEL_MAX_N);
+    std::vector<int> mine, routed;
+    for (int b = 0; b < a.nb; ++b) (vfe_batch_takes(a, b, max_n) ? mine : routed).push_back(b);
+    RC(for_each_wave(c, mine, [&](int b) { return WaveCost{sizeof(double) * (size_t)vfe_ws(a, b), 0, sizeof(double) * (size_t)vfe_in(a, b)}; },
+                     [&](const int* idx, int nw) { return run_vfe_wave(c, a, idx, nw); }));
+    // everything else: gp_vfe_fit + gp_vfe_get + gp_vfe_free, one problem at a time, after the lock is released (as batch_impl does)
+    gd.lk.unlock();
+    for (int b : routed) {
+        const bool weights = a.ab(b) || a.eb(b);
+        gp_vfe* h = nullptr;
+        int32_t rc = gp_vfe_fit(c, &a.k[b], &a.xb(b), &a.zb(b), &a.noise[b], a.jitter[b], a.mb(b), a.yb(b), a.approx[b], weights ? &h : nullptr, logpdf_slot(a, b));
+        if (rc == 0 && h) rc = gp_vfe_get(h, a.ab(b), a.eb(b));
+        if (h) (void)gp_vfe_free(h);
+        RC(routed_done(a, b, rc, [&] {
+            fill_nan(a.ab(b), a.dtype, a.zb(b).n);
+            fill_nan(a.eb(b), a.dtype, a.zb(b).n);
+        }));
+    }
+    return 0;
+}
+
 }  // namespace
 
 // The two entry points of a pair (gp_kernel / gp_ksum descriptors) have the same body: base_args() files `k` by its type.  The check of `k` stands in front of
@@ -2631,5 +3179,12 @@ int32_t gp_loo_grad_batch_sum(gp_ctx* ctx, int32_t nb, const gp_ksum* k, int32_t
                dy_out_or_null, 12, dx_out_or_null}, true};
     if (nb > 0 && !k) return set_arg_err(3, "kernel array is NULL");
     return loo_grad_batch_impl(ctx, a);
+}
+
+int32_t gp_vfe_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, int32_t nz, const gp_points* z,
+                     const gp_noise* noise, const double* jitter, const void* const* mean_or_null, int32_t ny, const void* const* y,
+                     const int32_t* approx, void* objective_out, int32_t* info_out, void* const* alpha_out_or_null, void* const* m_eps_out_or_null) {
+    VfeArgs a{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, objective_out, info_out, alpha_out_or_null), nz, z, jitter, approx, m_eps_out_or_null};
+    return vfe_batch_impl(ctx, a);
 }
 }

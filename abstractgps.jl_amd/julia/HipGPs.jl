@@ -1655,6 +1655,85 @@ function AbstractGPs.approx_log_evidence(approx::Union{VFE,DTC}, fx::FiniteGP{<:
 end
 AbstractGPs.elbo(vfe::VFE, fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}) = approx_log_evidence(vfe, fx, y)  # :254
 
+# ---- many small sparse GPs in one call: gp_vfe_batch -------------------------------------------------------------------------------------
+# approx_log_evidence_batch(approxs, fxs, ys): approx_log_evidence(approxs[b], fxs[b], ys[b]) of independent VFE / DTC problems — the starts of a multi-start
+# optimiser over (θ, z), a grid, cross-validation folds — in ONE library call per (context, eltype) group; `fxs` and `ys` may hold one entry shared by all.
+# The same `x` / `y` / `z` object in every entry is sent once.  return_alpha / return_m_eps also return the lists of α_b and m_ε (:71-73).  on_error as in
+# logpdf_batch.  A problem the ABI has no layout for (composite kernel, dense Σy, non-scalar jitter) takes the stock path.
+function approx_log_evidence_batch(approxs::AbstractVector, fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys;
+                                   return_alpha::Bool=false, return_m_eps::Bool=false, on_error::Symbol=:raise)
+    on_error in (:raise, :nan) || throw(ArgumentError("on_error must be :raise or :nan"))
+    nb = length(approxs)
+    fv = length(fxs) == 1 ? fill(fxs[1], nb) : fxs
+    yv = (ys isa AbstractVector{<:Real}) ? fill(ys, nb) : (length(ys) == 1 ? fill(ys[1], nb) : collect(ys))
+    (length(fv) == nb && length(yv) == nb) || throw(DimensionMismatch("$(nb) approximations, $(length(fv)) FiniteGPs, $(length(yv)) observation vectors"))
+    obj = fill(NaN, nb)
+    info = zeros(Int32, nb)
+    alphas = Vector{Any}(nothing, nb)
+    mepss = Vector{Any}(nothing, nb)
+    args = Vector{Any}(nothing, nb)
+    groups = Dict{Any,Vector{Int}}()
+    for b in 1:nb
+        ap, fx, y = approxs[b], fv[b], yv[b]
+        @assert ap.fz.f === fx.f                                                       # :59, :249, :283
+        length(fx) == length(y) || throw(DimensionMismatch("problem $(b): length(fx) != length(y)"))
+        a = marshal(fx, eltype(y))
+        pz = (a === nothing || haskey(a, :ks) || is_dense(a.cn)) ? nothing : points(ap.fz.x, a.T)
+        if pz === nothing || !(ap.fz.Σy isa Diagonal{<:Any,<:Fill})  # stock path, one problem at a time
+            try
+                obj[b] = approx_log_evidence(typeof(ap)(FiniteGP(fx.f.gp, ap.fz.x, ap.fz.Σy)), stock(fx), y)
+            catch e
+                e isa PosDefException || rethrow()
+                info[b] = e.info
+            end
+        else
+            args[b] = (a=a, zbuf=pz[1], cz=pz[2], jitter=Float64(FillArrays.getindex_value(ap.fz.Σy.diag)))
+            push!(get!(groups, (fx.f.ctx, a.T), Int[]), b)
+        end
+    end
+    for ((ctx, Tg), idx) in groups
+        g = length(idx)
+        nx = all(b -> fv[b].x === fv[idx[1]].x, idx) ? 1 : g
+        nz = all(b -> approxs[b].fz.x === approxs[idx[1]].fz.x, idx) ? 1 : g
+        ny = all(b -> yv[b] === yv[idx[1]], idx) ? 1 : g
+        cks = [args[b].a.ck for b in idx]
+        cxs = [args[b].a.cx for b in idx[1:nx]]
+        czs = [args[b].cz for b in idx[1:nz]]
+        cns = [args[b].a.cn for b in idx]
+        jit = Float64[args[b].jitter for b in idx]
+        kinds = Int32[approxs[b] isa VFE ? 0 : 1 for b in idx]
+        ybufs = [Vector{Tg}(yv[b]) for b in idx[1:ny]]
+        yptrs = Ptr{Cvoid}[pointer(v) for v in ybufs]
+        mptrs = Ptr{Cvoid}[args[b].a.m === nothing ? C_NULL : pointer(args[b].a.m) for b in idx]
+        out = Vector{Tg}(undef, g)
+        inf = zeros(Int32, g)
+        abufs = return_alpha ? [Vector{Tg}(undef, length(approxs[b].fz)) for b in idx] : Vector{Tg}[]
+        ebufs = return_m_eps ? [Vector{Tg}(undef, length(approxs[b].fz)) for b in idx] : Vector{Tg}[]
+        aptrs = Ptr{Cvoid}[pointer(v) for v in abufs]
+        eptrs = Ptr{Cvoid}[pointer(v) for v in ebufs]
+        GC.@preserve args cks cxs czs cns jit kinds ybufs yptrs mptrs out inf abufs ebufs aptrs eptrs begin
+            check(ccall((:gp_vfe_batch, libgpmi355), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{CKernel}, Int32, Ptr{CPoints}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Float64}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}},
+                    Ptr{Int32}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}),
+                ctx.handle, g, cks, nx, cxs, nz, czs, cns, jit, mptrs, ny, yptrs, kinds, out, inf,
+                return_alpha ? pointer(aptrs) : C_NULL, return_m_eps ? pointer(eptrs) : C_NULL))
+        end
+        for (j, b) in enumerate(idx)
+            obj[b] = out[j]
+            info[b] = inf[j]
+            return_alpha && (alphas[b] = abufs[j])
+            return_m_eps && (mepss[b] = ebufs[j])
+        end
+    end
+    bad = findfirst(!iszero, info)
+    on_error === :raise && bad !== nothing && throw(BatchPosDefException(Int(info[bad]), bad))
+    res = Any[obj]
+    return_alpha && push!(res, alphas)
+    return_m_eps && push!(res, mepss)
+    return length(res) == 1 ? obj : Tuple(res)
+end
+elbo_batch(approxs, fxs, ys; kw...) = approx_log_evidence_batch(approxs, fxs, ys; kw...)
+
 # ---- value + gradient of the sparse objective: one fit + one backward pass over the retained observations (gp_vfe_grad) ------------------
 # The reference's users maximise `elbo(VFE(f(z, jitter)), f(x, Σy), y)` over kernel parameters and pseudo-points by AD / finite differences
 # (examples/0-intro-1d/script.jl:385-394); the ccall is opaque to AD, so the accelerated objective carries its own pullback.

@@ -309,6 +309,7 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
  *   "batch_gradx_kernel_problems"     read-only: the same for the input-gradient kernels of gp_logpdf_grad_batch_x / _sum_x (problems whose dx they computed)
  *   "batch_joint_kernel_problems"     read-only: the same for the kernels of gp_joint_batch / _sum
  *   "batch_loo_kernel_problems", "batch_loo_grad_kernel_problems"   read-only: the same for the kernels of gp_loo_batch / _sum and of gp_loo_grad_batch / _sum
+ *   "vfe_batch_kernel_problems"       read-only: the same for the kernels of gp_vfe_batch
  *   "cols_kernel_calls", "cols_kernel_splits"   read-only: kmul launches gp_posterior_predict_cols has served on this ctx since it was created, and the workgroups
  *                    along the training range of the last of them (1 = unsplit, 0 = none yet): which path ran, for tests and measurements */
 /* The defaults above, machine-readable (single-device parameters; gp_ctx_get_param reads the same names): the test-suite asserts before
@@ -938,6 +939,49 @@ int32_t gp_vfe_get_by_cols(gp_vfe* post, void* B_out);
 int32_t gp_vfe_grad_cols(gp_vfe* post, double* dvariance_or_null, double* dscale_or_null, double* dnoise_sum_or_null, void* dnoise_diag_or_null,
                          void* dY_or_null, double* dz_or_null, int32_t z_layout, void* dx_or_null, int32_t x_layout);
 int32_t gp_vfe_free(gp_vfe* post);
+
+/* ---- many small sparse GPs in one call ------------------------------------------------------------------------------------------------- */
+/* gp_vfe_batch: nb independent VFE / DTC problems — what a multi-start optimiser over (θ, z), a grid over lengthscale × noise × M, a sampler over
+ * hyper-parameters, cross-validation folds or one local sparse GP per region evaluate again and again (a loop of gp_vfe_fit calls otherwise).  Per problem
+ * the semantics are those of gp_vfe_fit followed by gp_vfe_get (src/sparse_approximations.jl:58-75, 248-313): objective_out[b] = elbo for approx[b] = 0,
+ * approx_log_evidence (DTC) for approx[b] = 1 and, where alpha_out_or_null[b] / m_eps_out_or_null[b] is not NULL, α_b = U \ m_ε and m_ε (M_b = z_b.n
+ * entries each).  Value and weights only: no handle, no gradient, no predictions.
+ *   k, noise, jitter, approx, objective_out, info_out: arrays of nb;  x: nx entries, z: nz entries, y: ny pointers (n_b entries each), nx, nz, ny ∈ {1, nb}
+ *   — 1 = every problem shares that array (a shared y needs problems of one size; a shared x and y are uploaded once);  mean_or_null, alpha_out_or_null,
+ *   m_eps_out_or_null: NULL, or nb pointers each of which may be NULL.  One dtype per call (that of k[0]).
+ * Failure is data, as in gp_logpdf_batch: info_out[b] is what gp_vfe_fit returns for the problem — 1 + the index of the first observation whose noise
+ * variance is not positive, or the order of the first leading minor that is not positive of K_zz + jitter·I or, where that factors, of Λ_ε (gp_vfe_fit's
+ * status does not tell the two matrices apart, and neither does this) — with NaN in that problem's objective, α and m_ε; the other problems are not
+ * affected.  The return value reports argument errors only (−i, reason in gp_last_error(); nb = 0 returns 0 and touches nothing).
+ * fp64 problems with noise kind 0 / 1 (every variance positive), D <= 16, 1 <= M_b <= GPMI355_VFE_BATCH_MAX_M and n_b <= GPMI355_VFE_BATCH_MAX_N run on
+ * three kernels per wave of problems (csrc/batch.hip), one packed copy in, one copy back; workspace (4 GiB) and packed input (768 MiB, inside the ctx's
+ * page-locked staging) of a wave are bounded, a larger batch runs in waves:
+ *   vfe_prelude_kernel  one workgroup per problem: K_zz + jitter·I, its Cholesky and W = L_z⁻¹;
+ *   vfe_stream_kernel   one workgroup per (problem, segment of GPMI355_VFE_BATCH_SEG consecutive observations): W stays in LDS; per tile of 64 observations
+ *                       K̃ = K(z, x_tile) Σy^-1/2 is evaluated into LDS (K_xz never reaches HBM), B = W K̃ by v_mfma_f64_16x16x4_f64 over the non-zero k blocks,
+ *                       G += B Bᵀ in register-resident 32×32 wave tiles, c += B b_y and the scalar sums; the segment's partial sums go to its own slot;
+ *   vfe_final_kernel    one workgroup per problem: the segments' partial sums in segment order, Λ_ε = chol(I + G) with c as the carried row, the objective,
+ *                       m_ε and α by backward sweeps.
+ * No floating-point atomics, no waits between workgroups, every sum in an order the problem's own sizes fix: objective and weights of a problem are the same
+ * bits alone, anywhere in any batch, and on repetition.  Every other problem (fp32, a larger M or n, D > 16, a dense Σy — refused as gp_vfe_fit refuses it)
+ * is answered inside the same call by gp_vfe_fit + gp_vfe_get + gp_vfe_free; which path serves a problem depends on that problem alone.  On a multi-device
+ * ctx the kernels run on the first device.  The read-only ctx parameter "vfe_batch_kernel_problems" counts the problems the kernels served.
+ * GPMI355_VFE_BATCH_MAX_N: by the rule that fixed the other batch thresholds — the largest n of the measured sweep (tools/vfe_batch_profile.py,
+ * profiles/r35/vfe_batch_profile.json: one process, SE, D = 3, M = 16, 64, 128 × n = 1 024 … 262 144 × nb = 1, 8, 64, 512, each with shared and with per-problem
+ * (x, y): 120 cells, none skipped, objective only) at which one batch call beat the loop of gp_vfe_fit calls in every cell with nb >= 8.  It beat it in all 90 of
+ * them, so the macro is the largest n swept.  The closest cells are those with per-problem data at n = 262 144 and M = 128, where packing and uploading the
+ * inputs (a wave's packed input is bounded, so nb = 512 runs in 6 waves) is most of the call: nb = 8 9.30 against 13.67 ms, nb = 64 62.7 against
+ * 110.9 ms, nb = 512 482 against 859 ms; shared, nb = 512 takes 180 against 771 ms.  A single problem (nb = 1) loses at M = 128 from n = 1 024 on (0.72 against
+ * 0.48 ms; 2.66 against 1.57 ms at n = 262 144) and wins or is within 25 % of the loop at M = 16 and 64: the rule does not count it, as for the other
+ * thresholds.  The weights variant (α and m_ε against fit + gp_vfe_get + free) was measured in 8 cells only (M = 128, n = 1 024 and 65 536, nb = 8 and 64:
+ * vfe_batch_profile_weights.json, 2.2 … 39 times faster); its cost beyond the objective is two M-long sweeps per problem.  (The environment variable
+ * GPMI_VFE_BATCH_MAX_N, read per call, overrides the macro for measurements.) */
+#define GPMI355_VFE_BATCH_MAX_M 128
+#define GPMI355_VFE_BATCH_SEG 2048
+#define GPMI355_VFE_BATCH_MAX_N 262144
+int32_t gp_vfe_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, int32_t nz, const gp_points* z,
+                     const gp_noise* noise, const double* jitter, const void* const* mean_or_null, int32_t ny, const void* const* y,
+                     const int32_t* approx, void* objective_out, int32_t* info_out, void* const* alpha_out_or_null, void* const* m_eps_out_or_null);
 
 /* ---- device-level building blocks ------------------------------------------------------------ */
 /* The operations the in-library multi-device driver composes (csrc/multi.hip calls the same engine functions), exposed on DEVICE
