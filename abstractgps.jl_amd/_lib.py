@@ -154,6 +154,8 @@ PROTOTYPES = {
     "gp_vfe_free": (i32, [vp]),
     "gp_vfe_batch": (i32, [vp, i32, PK, i32, PP, i32, PP, PN, C.POINTER(dbl), C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(i32), vp, C.POINTER(i32),
                            C.POINTER(vp), C.POINTER(vp)]),
+    "gp_vfe_grad_batch": (i32, [vp, i32, PK, i32, PP, i32, PP, PN, C.POINTER(dbl), C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(i32), vp, C.POINTER(i32),
+                                C.POINTER(dbl), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
     "gpd_assemble": (i32, [vp, PK, vp, i64, i64, i32, vp, PG, vp, i64, i64, i64]),
     "gpd_potrf": (i32, [vp, vp, i64, i64, i64, vp, i32, i64, vp]),
     "gpd_trsm": (i32, [vp, vp, i64, i64, vp, i64, i64]),

@@ -2393,6 +2393,57 @@ def elbo_batch(approxs, fxs, ys, **kw):
     return approx_log_evidence_batch(approxs, fxs, ys, **kw)
 
 
+def _grad_container(arr: np.ndarray, pts, inp):
+    """A gradient the library wrote in the container layout of `pts` (gp_points of the input `inp`), in the shape of inp's array."""
+    if pts.layout == 0:
+        return arr
+    nd = arr.reshape(pts.n, pts.d) if pts.layout == 1 else arr.reshape(pts.d, pts.n).T   # (n, d)
+    return np.ascontiguousarray(nd.T if isinstance(inp, ColVecs) else nd)
+
+
+def elbo_and_grad_batch(approxs, fxs, ys, *, wrt_x: bool = False, on_error: str = "raise") -> tuple:
+    """elbo_and_grad(approxs[b], fxs[b], ys[b], wrt_x) of many independent sparse GPs in one library call per (ctx, dtype) group (gp_vfe_grad_batch): the
+    array of objectives (ELBO for a VFE entry, DTC evidence for a DTC entry) and, in the caller's order, the list of gradient dicts — "variance", "scale",
+    "noise" (plus "noise_diag" for a diagonal noise), "y", "mean", "z" (fp64 problems) and with wrt_x "x".  fxs and ys may have length 1; the same x / z / y
+    object in every entry is sent once.  on_error as in elbo_batch; with "nan" a failed problem's dict holds NaN in every entry."""
+    if on_error not in ("raise", "nan"):
+        raise ValueError('on_error must be "raise" or "nan"')
+    if not isinstance(wrt_x, (bool, np.bool_)):
+        raise TypeError("wrt_x must be a bool")
+    approxs = list(approxs)
+    if not approxs:
+        return np.empty(0), []
+    parts, grads = [], [None] * len(approxs)
+    for g in _vfe_batch_groups(approxs, fxs, ys):
+        call = _vfe_batch_marshal(g, False, False)
+        nb, f64 = call.nb, np.dtype(g.dtype) == np.float64
+        pts, zs, karr, narr = call.args[3], call.args[5], call.args[1], call.args[6]
+        px = [pts[0 if g.nx == 1 else b] for b in range(nb)]
+        pz = [zs[0 if g.nxs == 1 else b] for b in range(nb)]
+        dvar = np.empty(nb)
+        dscale = [np.empty(max(karr[b].nscale, 1)) for b in range(nb)]
+        dnoise = [np.empty(px[b].n if narr[b].kind == 1 else 1, dtype=g.dtype) for b in range(nb)]
+        dy = [np.empty(px[b].n, dtype=g.dtype) for b in range(nb)]
+        dz = [np.empty(pz[b].n * pz[b].d) for b in range(nb)] if f64 else None   # an fp32 fit does not carry d/dz (gp_vfe_grad refuses it)
+        dx = [np.empty(px[b].n * px[b].d, dtype=g.dtype) for b in range(nb)] if wrt_x else None
+        ptrs = [None if v is None else (C.c_void_p * nb)(*[w.ctypes.data for w in v]) for v in (dscale, dnoise, dy, dz, dx)]
+        ctx = g.ctx or default_context()
+        check(ctx.lib.gp_vfe_grad_batch(ctx.handle, *call.args[:14], dvar.ctypes.data_as(C.POINTER(C.c_double)), *ptrs))
+        parts.append((g.index, call.out, call.info, None))
+        for b, i in enumerate(g.index):
+            ns = karr[b].nscale
+            d = {"variance": float(dvar[b]), "scale": None if ns == 0 else (float(dscale[b][0]) if ns == 1 else dscale[b]),
+                 "noise": float(dnoise[b].sum() if narr[b].kind == 1 else dnoise[b][0]), "y": dy[b], "mean": -dy[b]}
+            if narr[b].kind == 1:
+                d["noise_diag"] = dnoise[b]
+            if f64:
+                d["z"] = _grad_container(dz[b], pz[b], _as_input(g.xss[b].fz.x))
+            if wrt_x:
+                d["x"] = _grad_container(dx[b], px[b], _as_input(g.fxs[b].x))
+            grads[i] = d
+    return _batch_merge(len(approxs), parts, False, on_error), grads
+
+
 # --------------------------------------------------------------------------------------------
 # VFE / DTC for a matrix of observations: gp_vfe_fit_cols / _update_cols / _append_cols / _predict_cols / _get_cols / _get_by_cols / _grad_cols
 # --------------------------------------------------------------------------------------------

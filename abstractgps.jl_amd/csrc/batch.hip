@@ -4,7 +4,8 @@
 // slices (batch_inv_kernel, batch_grad_kernel, batch_gsum_kernel, behind it; with the input gradient of gp_logpdf_grad_batch_x / gp_logpdf_grad_batch_sum_x:
 // batch_gradx_kernel, batch_gxsum_kernel) and the gradients of the predictions w.r.t. the test inputs from the strips the predict kernel leaves and the S of
 // batch_inv_kernel (batch_pgrad_kernel), the joint predictive distribution from the same strips (batch_jcov_kernel, batch_jfact_kernel); last many small
-// sparse GPs in one call (gp_vfe_batch: vfe_prelude_kernel, vfe_stream_kernel, vfe_final_kernel, described in front of them).
+// sparse GPs in one call (gp_vfe_batch: vfe_prelude_kernel, vfe_stream_kernel, vfe_final_kernel; gp_vfe_grad_batch: vfe_gmm_kernel, vfe_gstream_kernel,
+// vfe_gfinish_kernel behind them; each described in front of its kernels).
 //
 // ONE workgroup owns ONE problem from its inputs to its scalar: it assembles the lower triangle of K + Σy into the problem's slice of a
 // workspace (δ = y − m riding along as row np, as in the single path), factors it by a blocked right-looking Cholesky (64-column blocks:
@@ -1640,6 +1641,420 @@ __global__ __launch_bounds__(NT) void vfe_final_kernel(const double* __restrict_
     if (tid < m) alpha[tid] = zs[tid];
 }
 
+// ---- value AND gradient of many small sparse GPs (gp_vfe_grad_batch): vfe_gmm_kernel, vfe_gstream_kernel, vfe_gfinish_kernel behind the three launches above ----
+// The formulation of vfe.hpp's gradient (V = L_z⁻ᵀ, the strip the prelude left; A = Λ_ε, its factor left by vfe_final_kernel; G = B Bᵀ):
+//   G_ψ = ½[V H_ψ Vᵀ − ααᵀ], H_ψ = I − A⁻¹ (VFE) | −A⁻¹ (DTC);   G_zz = ½[V H_zz Vᵀ − ααᵀ], H_zz = H_ψ − G (VFE) | H_ψ + I (DTC);
+//   per (pseudo-point i, observation j), T = G_ψ K̃:  W_ij = σ_j⁻¹(2 T_ij + b_j α_i), ∂/∂variance += W κ, w_ij = 2 W variance κ′ weighs ∂r²_ij;
+//   q_j = Σ_i variance κ_ij T_ij, p_j = Σ_i K̃_ij α_i  →  ∂/∂σ_j² and ∂/∂y_j as vgrad_finish_kernel forms them.
+// What the problem's gradient lays out, in its wave's tables beside VfeProb: u_off (the strip Λ_ε.L⁻ᵀ), h_off (H_ψ, then H_zz), rt_off (V H), gpsi_off,
+// gzz_off (np rows of ld each; gzz_off holds G until G_zz is written over it) and gpart_off (nseg slots of vfe_gpart(np, d)) into the workspace; gh_off
+// (∂/∂variance, 16 × ∂/∂scale, Σ ∂/∂σ²), dz_off ([d][m]), dn_off ([n], −1 for a scalar σ²), dy_off ([n]) and dx_off ([d][n], −1: not wanted) into the results.
+struct VfeGrad {
+    long u_off, h_off, rt_off, gpsi_off, gzz_off, gpart_off, gh_off, dz_off, dn_off, dy_off, dx_off;
+};
+static_assert(sizeof(VfeGrad) % 8 == 0, "the tables are packed behind double data");
+enum {
+    VFE_GH = 20,   // the hyper-parameter block of a problem's results: [0] ∂/∂variance, [1 + p] ∂/∂scale_p, [17] Σ_j ∂/∂σ_j²
+    GTS = 16 * 17  // a 16×16 block of G_ψ in LDS, k-major with row stride 17: read as stored and transposed (the upper blocks, through symmetry) without conflicts
+};
+// a segment's slot of gradient sums: Σ_j w_ij (z_i − x_j)_p and Σ_j w_ij (z_i − x_j)_p², both [d][np]; then Σ W κ, Σ_j ∂/∂σ_j², Σ_j σ_j⁻² (+ padding)
+__host__ __device__ static inline long vfe_gpart(long np, long d) { return 2 * np * d + 8; }
+
+// C = X Yᵀ on the 32×32 tiles (ti, tj) a workgroup's eight waves take round-robin, operands row-major with stride ld, from global memory through
+// mfma_tile_k64; the k loop of a tile starts at the 64-block klo(i0, j0) (what lies left of it is zero in an upper-triangular operand).  lower_only: the
+// tiles tj <= ti alone.  epi(i, j, v) gets every entry of the tile.
+template <class KLo, class Epi>
+__device__ __forceinline__ void vfe_mm_xyt(const double* X, const double* Y, long ld, int np, bool lower_only, int w, int lane, KLo&& klo, Epi&& epi) {
+    const int n32 = np / 32;
+    int cnt = 0;
+    for (int ti = 0; ti < n32; ++ti)
+        for (int tj = 0; tj < (lower_only ? ti + 1 : n32); ++tj) {
+            if ((cnt++ & 7) != w) continue;
+            const int i0 = 32 * ti, j0 = 32 * tj;
+            d4_t acc[2][2];
+            acc_zero(acc);
+            for (int k0 = klo(i0, j0) / BT * BT; k0 < np; k0 += BT) mfma_tile_k64<false>(acc, X, i0, Y, j0, k0, ld, lane);
+#pragma unroll
+            for (int h = 0; h < 4; ++h)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) epi(i0 + 16 * (h >> 1) + Tr<double>::crow(lane, q), j0 + 16 * (h & 1) + (lane & 15), acc[h >> 1][h & 1][q]);
+        }
+}
+
+// One workgroup per problem, the M×M side: U = Λ_ε.L⁻ᵀ by strip_solve on identity rows (as the prelude forms V), G = B Bᵀ summed again from the segments'
+// slots in segment order (vfe_final_kernel factored over its sum), then five products X Yᵀ on the fp64 MFMA in 32×32 wave tiles, zero 64-blocks of the
+// triangular operands skipped:  A⁻¹ = U Uᵀ → H_ψ;  R = V H_ψ;  V Rᵀ → G_ψ;  H_zz in place;  R = V H_zz;  V Rᵀ → G_zz.  The two conjugations compute the
+// lower tiles and write both halves: G_ψ and G_zz are symmetric to the bit.  Rows and columns from m on are written as zeros (V and A are the identity
+// there, so nothing of the padding reaches the m × m block; the −1 the DTC H_ψ would keep on the padded diagonal is dropped with them).
+__global__ __launch_bounds__(NT) void vfe_gmm_kernel(const double* __restrict__ in, double* __restrict__ ws, const double* __restrict__ res, int nw,
+                                                     const VfeProb* __restrict__ vps, const VfeGrad* __restrict__ gps) {
+    __shared__ double sh[BT * BTS + BT];
+    __shared__ double al[VFE_MAXM];
+    const VfeProb& P = vps[blockIdx.x];
+    const VfeGrad& Q = gps[blockIdx.x];
+    if (res[nw + P.slot] != 0.0) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int m = P.m, np = P.np, nseg = P.nseg;
+    const long ld = P.ld, psz = vfe_part(np);
+    const double vfe = P.approx == 0 ? 1.0 : 0.0;
+    double* __restrict__ U = ws + Q.u_off;
+    double* __restrict__ H = ws + Q.h_off;
+    double* __restrict__ R = ws + Q.rt_off;
+    double* __restrict__ Gp = ws + Q.gpsi_off;
+    double* __restrict__ Gz = ws + Q.gzz_off;
+    const double* __restrict__ V = ws + P.w_off;
+    const double* __restrict__ part = ws + P.part_off;
+    for (int e = tid; e < np * np; e += NT) {
+        const int i = e / np, j = e - i * np;
+        U[(long)i * ld + j] = i == j ? 1.0 : 0.0;
+        const int src = (j >> 5) <= (i >> 5) ? e : j * np + i;  // the stream kernel wrote the 32×32 tiles of the lower triangle
+        double s = 0.0;
+        for (int sg = 0; sg < nseg; ++sg) s += part[sg * psz + src];
+        Gz[(long)i * ld + j] = s;
+    }
+    if (tid < np) al[tid] = tid < m ? res[P.alpha_off + tid] : 0.0;
+    __syncthreads();
+    (void)strip_solve(U, ws + P.d_off, ld, 0, np / BT, np, sh, tid, lane, w);
+    auto from_row = [](int i0, int) { return i0; };
+    auto from_both = [](int i0, int j0) { return i0 > j0 ? i0 : j0; };
+    auto to_R = [&](int i, int j, double v) { R[(long)i * ld + j] = v; };
+    vfe_mm_xyt(U, U, ld, np, false, w, lane, from_both, [&](int i, int j, double v) { H[(long)i * ld + j] = (i < m && j < m) ? (i == j ? vfe : 0.0) - v : 0.0; });
+    __syncthreads();
+    auto conj_into = [&](double* G) {  // G = ½[V H Vᵀ − ααᵀ], both halves from the lower tiles
+        vfe_mm_xyt(V, H, ld, np, false, w, lane, from_row, to_R);  // R = V H (H symmetric)
+        __syncthreads();
+        vfe_mm_xyt(V, R, ld, np, true, w, lane, from_row, [&](int i, int j, double v) {
+            if (j > i) return;
+            const double gv = (i < m && j < m) ? 0.5 * (v - al[i] * al[j]) : 0.0;
+            G[(long)i * ld + j] = gv;
+            G[(long)j * ld + i] = gv;
+        });
+        __syncthreads();
+    };
+    conj_into(Gp);
+    for (int e = tid; e < m * m; e += NT) {
+        const int i = e / m, j = e - i * m;
+        H[(long)i * ld + j] += (i == j ? 1.0 - vfe : 0.0) - vfe * Gz[(long)i * ld + j];
+    }
+    __syncthreads();
+    conj_into(Gz);
+}
+
+// One workgroup per (problem, segment), the table of the fit's stream kernel; tiles of 64 observations.  LDS, 159.7 KB of the CU's 160 — one workgroup per CU,
+// as in the fit:  G_ψ as the 36 16×16 blocks of its lower triangle (GTS apart, 78.3 KB at M = 128; a full 128×128 copy, 131 KB, does not fit beside the tile
+// buffer, so the upper blocks are read transposed out of the lower ones — the stride of 17 keeps both reads conflict-free), resident for the whole segment;
+// the tile buffer KB (np × 64, stride 65, 66.6 KB), which holds K̃, then T, then w; the tile's scaled inputs xs [d][64]; α; per observation b_j and p_j;
+// one [8][64] table for the two sums the eight waves add up per observation.  Per tile:
+//   1. K̃ as in the fit (lane = observation, the waves interleave the pseudo-points) and, on the way, the wave's share of p_j = Σ_i K̃_ij α_i;
+//   2. T = G_ψ K̃ by MFMA over all k blocks, wave mapping of the fit's B = W K̃; T overwrites K̃ once every wave has read it;
+//   3. the elementwise pass, mapping of step 1: κ and κ′ again from (z_i − x_j) (kappa_and_dr2), W_ij, the thread's Σ W κ, the wave's share of q_j, and
+//      w_ij over T_ij.  Wave 0 then finishes ∂/∂σ_j² and ∂/∂y_j of the tile's observations and writes them straight to the results;
+//   4. the reductions over w: thread (i, p) — up to four pairs a thread, fixed for the segment, z_ip in a register — adds Σ_j w_ij t and Σ_j w_ij t² with
+//      t = z_ip − x_jp formed from the difference itself, in observation order, into its accumulators; where ∂/∂x is wanted thread (j, p) adds
+//      Σ_i w_ij (x_jp − z_ip) in pseudo-point order and writes it to the results.  K̃, T and w never reach HBM.
+// The segment's sums go to its own slot; every order above is fixed by (m, d, the segment's range) alone.
+__global__ __launch_bounds__(NT) void vfe_gstream_kernel(const double* __restrict__ in, double* __restrict__ ws, double* __restrict__ res, int nw,
+                                                         const VfeProb* __restrict__ vps, const VfeGrad* __restrict__ gps, const VfeSeg* __restrict__ segs) {
+    __shared__ double Gt[(VFE_MAXM / 16) * (VFE_MAXM / 16 + 1) / 2 * GTS];
+    __shared__ double KB[VFE_MAXM * KBS];
+    __shared__ double xs[BATCH_MAXD * VT];
+    __shared__ double red[8 * VT];
+    __shared__ double al[VFE_MAXM];
+    __shared__ double bs[VT], pj[VT];
+    const VfeSeg S = segs[blockIdx.x];
+    const VfeProb& P = vps[S.prob];
+    const VfeGrad& Q = gps[S.prob];
+    if (res[nw + P.slot] != 0.0) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 15, g = lane >> 4;
+    const int n = P.n, m = P.m, np = P.np, d = P.d, nscale = P.nscale;
+    const long ld = P.ld;
+    const int nb16 = np / 16;
+    const double var = P.variance;
+    const double* __restrict__ z = in + P.z_off;
+    const double* __restrict__ x = in + P.x_off;
+    const double* __restrict__ y = in + P.y_off;
+    {
+        const double* __restrict__ Gp = ws + Q.gpsi_off;
+        int cnt = 0;
+        for (int bi = 0; bi < nb16; ++bi)
+            for (int bk = 0; bk <= bi; ++bk, ++cnt) {
+                if ((cnt & 7) != w) continue;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int e = lane + 64 * q;  // e = 16 row + k
+                    Gt[cnt * GTS + (e & 15) * 17 + (e >> 4)] = Gp[(long)(16 * bi + (e >> 4)) * ld + 16 * bk + (e & 15)];
+                }
+            }
+        if (tid < np) al[tid] = tid < m ? res[P.alpha_off + tid] : 0.0;
+    }
+    // the thread's (i, p) pairs: e = p np + i
+    double zi[4], accz[4], accs[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int e = tid + NT * q, p = e / np, i = e - p * np;
+        zi[q] = (p < d && i < m) ? z[(long)p * m + i] : 0.0;
+        accz[q] = accs[q] = 0.0;
+    }
+    double vacc = 0.0, dnsum = 0.0, r2sum = 0.0;
+    const long o0 = (long)S.seg * VFE_SEG;
+    const int cnt = n - o0 < VFE_SEG ? (int)(n - o0) : (int)VFE_SEG;
+    __syncthreads();
+    for (int t0 = 0; t0 < cnt; t0 += VT) {
+        const bool valid = t0 + lane < cnt;
+        const long j = o0 + t0 + lane;
+        double xj[BATCH_MAXD];
+#pragma unroll
+        for (int p = 0; p < BATCH_MAXD; ++p)
+            xj[p] = (p < d && valid) ? (nscale == 0 ? 1.0 : P.scale[nscale == 1 ? 0 : p]) * x[(long)p * n + j] : 0.0;
+        double rs = 0.0;
+        // ---- 1. K̃ into LDS, the wave's share of p_j
+        {
+            if (valid) rs = 1.0 / sqrt(P.nz_off >= 0 ? in[P.nz_off + j] : P.noise_s);
+            if (w == 0) bs[lane] = valid ? (y[j] - (P.m_off >= 0 ? in[P.m_off + j] : 0.0)) * rs : 0.0;
+#pragma unroll
+            for (int p = 0; p < BATCH_MAXD; ++p)
+                if ((p & 7) == w) xs[p * VT + lane] = xj[p];
+            double pp = 0.0;
+            for (int rr = 0; rr < np / 8; ++rr) {
+                const int i = w + 8 * rr;  // wave-uniform
+                double v = 0.0;
+                if (i < m && valid) {
+                    double t[BATCH_MAXD];
+                    batch_diff(z, m, d, i, xj, t);
+                    v = vfe_kval(P, t) * rs;
+                    pp = fma(v, al[i], pp);
+                }
+                KB[i * KBS + lane] = v;
+            }
+            red[w * VT + lane] = pp;
+        }
+        __syncthreads();
+        if (w == 1) {
+            double s = 0.0;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) s += red[q * VT + lane];
+            pj[lane] = s;
+        }
+        // ---- 2. T = G_ψ K̃ into registers; then over K̃
+        {
+            const int cb = w & 3;
+            d4_t acc[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                acc[q] = 0.0;
+                const int bi = (w >> 2) + 2 * q;
+                if (bi < nb16)
+                    for (int bk = 0; bk < nb16; ++bk) {
+                        const bool low = bk <= bi;
+                        const double* gb = Gt + (low ? bi * (bi + 1) / 2 + bk : bk * (bk + 1) / 2 + bi) * GTS;
+#pragma unroll
+                        for (int s = 0; s < 4; ++s)
+                            acc[q] = Tr<double>::mfma(low ? gb[(4 * s + g) * 17 + r] : gb[r * 17 + 4 * s + g], KB[(16 * bk + 4 * s + g) * KBS + 16 * cb + r], acc[q]);
+                    }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int bi = (w >> 2) + 2 * q;
+                if (bi < nb16)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) KB[(16 * bi + Tr<double>::crow(lane, e)) * KBS + 16 * cb + r] = acc[q][e];
+            }
+        }
+        __syncthreads();
+        // ---- 3. the elementwise pass: w over T, the wave's share of q_j
+        {
+            const double bj = bs[lane];
+            double qq = 0.0;
+            for (int rr = 0; rr < np / 8; ++rr) {
+                const int i = w + 8 * rr;  // wave-uniform
+                if (i >= m) break;
+                double t[BATCH_MAXD];
+                batch_diff(z, m, d, i, xj, t);
+                double d2 = 0.0;
+#pragma unroll
+                for (int p = 0; p < BATCH_MAXD; ++p) d2 = fma(t[p], t[p], d2);
+                double kap, dk;
+                kappa_and_dr2<double>(P.kind, d2, kap, dk);
+                const double T = KB[i * KBS + lane];
+                const double W = rs * (2.0 * T + bj * al[i]);
+                vacc = fma(W, kap, vacc);
+                qq = fma(var * kap, T, qq);
+                KB[i * KBS + lane] = valid ? 2.0 * W * var * dk : 0.0;
+            }
+            red[w * VT + lane] = qq;
+        }
+        __syncthreads();
+        if (w == 0 && valid) {
+            double rq = 0.0;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) rq += red[q * VT + lane];
+            const double b = bs[lane], r2 = rs * rs, pr = pj[lane];  // pr = σ_j⁻¹ Σ_i variance κ_ij α_i
+            const double dn = -0.5 * r2 + 0.5 * b * b * r2 - rq * r2 * rs - pr * b * r2 + (P.approx == 0 ? 0.5 * var * r2 * r2 : 0.0);
+            res[Q.dy_off + j] = -(b * rs - pr * rs);
+            if (Q.dn_off >= 0) res[Q.dn_off + j] = dn;
+            dnsum += dn;
+            r2sum += r2;
+        }
+        // ---- 4. the reductions over w
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int e = tid + NT * q, p = e / np, i = e - p * np;
+            if (p < d && i < m) {
+                const double* wr = KB + i * KBS;
+                const double* xp = xs + p * VT;
+                double az = accz[q], as = accs[q];
+                for (int jj = 0; jj < VT; ++jj) {
+                    const double t = zi[q] - xp[jj], wt = wr[jj] * t;
+                    az += wt;
+                    as = fma(wt, t, as);
+                }
+                accz[q] = az, accs[q] = as;
+            }
+        }
+        if (Q.dx_off >= 0)
+            for (int p = w; p < d; p += 8) {  // wave-uniform
+                const double sp = nscale == 0 ? 1.0 : P.scale[nscale == 1 ? 0 : p];
+                const double xv = xs[p * VT + lane];
+                double s = 0.0;
+                for (int i = 0; i < m; ++i) s = fma(KB[i * KBS + lane], xv - z[(long)p * m + i], s);
+                if (valid) res[Q.dx_off + (long)p * n + j] = sp * s;
+            }
+        __syncthreads();
+    }
+    double* __restrict__ part = ws + Q.gpart_off + (long)S.seg * vfe_gpart(np, d);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int e = tid + NT * q;
+        if (e < np * d) {
+            part[e] = accz[q];
+            part[(long)np * d + e] = accs[q];
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        vacc += __shfl_xor(vacc, o, 64);
+        dnsum += __shfl_xor(dnsum, o, 64);
+        r2sum += __shfl_xor(r2sum, o, 64);
+    }
+    if (lane == 0) red[w] = vacc;
+    __syncthreads();
+    if (tid == 0) {
+        double* sc = part + 2L * np * d;
+        double v = 0.0;
+        for (int q = 0; q < 8; ++q) v += red[q];
+        sc[0] = v;
+        sc[1] = dnsum;
+        sc[2] = r2sum;
+    }
+}
+
+// One workgroup per problem: the segments' sums in segment order, then the K_zz term — w_ij = 2 G_zz,ij variance κ′(z_i, z_j) over the full m × m square
+// into LDS (lane = column, the waves interleave the rows, as in the stream kernel; Σ G_zz κ on the way), reduced by the same (i, p) threads with factor 2 on
+// ∂/∂z (z_i enters K_zz through both arguments) — the trace term of the VFE objective on ∂/∂variance, and the problem's results: ∂/∂z as [d][m] times the
+// scales, ∂/∂scale (ARD: per dimension, the rows in order; one Scale: all dimensions), ∂/∂variance and Σ_j ∂/∂σ_j².
+__global__ __launch_bounds__(NT) void vfe_gfinish_kernel(const double* __restrict__ in, const double* __restrict__ ws, double* __restrict__ res, int nw,
+                                                         const VfeProb* __restrict__ vps, const VfeGrad* __restrict__ gps) {
+    __shared__ double WK[VFE_MAXM * (VFE_MAXM + 1)];
+    __shared__ double zl[BATCH_MAXD * VFE_MAXM];
+    __shared__ double red[8];
+    const VfeProb& P = vps[blockIdx.x];
+    const VfeGrad& Q = gps[blockIdx.x];
+    if (res[nw + P.slot] != 0.0) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int m = P.m, np = P.np, d = P.d, nseg = P.nseg, nscale = P.nscale;
+    const long ld = P.ld, gsz = vfe_gpart(np, d);
+    const int wks = np + 1;
+    const double var = P.variance;
+    const double* __restrict__ z = in + P.z_off;
+    const double* __restrict__ Gz = ws + Q.gzz_off;
+    const double* __restrict__ part = ws + Q.gpart_off;
+    for (int e = tid; e < d * np; e += NT) {
+        const int p = e / np, i = e - p * np;
+        zl[e] = i < m ? z[(long)p * m + i] : 0.0;
+    }
+    double accz[4], accs[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int e = tid + NT * q;
+        accz[q] = accs[q] = 0.0;
+        if (e < np * d)
+            for (int sg = 0; sg < nseg; ++sg) {
+                accz[q] += part[sg * gsz + e];
+                accs[q] += part[sg * gsz + (long)np * d + e];
+            }
+    }
+    double vacc = 0.0;
+    for (int j0 = 0; j0 < np; j0 += 64) {
+        const int j = j0 + lane;
+        double zj[BATCH_MAXD];
+        batch_load_point(z, m, d, j, zj);
+        for (int rr = 0; rr < np / 8; ++rr) {
+            const int i = w + 8 * rr;  // wave-uniform
+            double v = 0.0;
+            if (i < m && j < m) {
+                double t[BATCH_MAXD];
+                batch_diff(z, m, d, i, zj, t);
+                double d2 = 0.0;
+#pragma unroll
+                for (int p = 0; p < BATCH_MAXD; ++p) d2 = fma(t[p], t[p], d2);
+                double kap, dk;
+                kappa_and_dr2<double>(P.kind, d2, kap, dk);
+                const double W = Gz[(long)i * ld + j];
+                vacc = fma(W, kap, vacc);
+                v = 2.0 * W * var * dk;
+            }
+            WK[i * wks + j] = v;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int e = tid + NT * q, p = e / np, i = e - p * np;
+        if (p < d && i < m) {
+            const double zv = zl[e];
+            double az = 0.0, as = 0.0;
+            for (int j = 0; j < m; ++j) {
+                const double t = zv - zl[p * np + j], wt = WK[i * wks + j] * t;
+                az += wt;
+                as = fma(wt, t, as);
+            }
+            accz[q] += 2.0 * az;
+            accs[q] += as;
+            res[Q.dz_off + (long)p * m + i] = (nscale == 0 ? 1.0 : P.scale[nscale == 1 ? 0 : p]) * accz[q];
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) vacc += __shfl_xor(vacc, o, 64);
+    __syncthreads();
+    if (lane == 0) red[w] = vacc;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int e = tid + NT * q;
+        if (e < np * d) WK[e] = accs[q];  // [d][np]; rows from m on hold zeros
+    }
+    __syncthreads();
+    double* gh = res + Q.gh_off;
+    if (tid == 0) {
+        double v = 0.0, dns = 0.0, r2 = 0.0;
+        for (int sg = 0; sg < nseg; ++sg) {
+            const double* sc = part + sg * gsz + 2L * np * d;
+            v += sc[0];
+            dns += sc[1];
+            r2 += sc[2];
+        }
+        for (int q = 0; q < 8; ++q) v += red[q];
+        gh[0] = v - (P.approx == 0 ? 0.5 * r2 : 0.0);
+        gh[17] = dns;
+    }
+    if (tid < (nscale == 1 ? 1 : nscale)) {
+        double s = 0.0;
+        for (int e = (nscale == 1 ? 0 : tid * np); e < (nscale == 1 ? d * np : (tid + 1) * np); ++e) s += WK[e];
+        gh[1 + tid] = s / P.scale[tid];
+    }
+}
+
 }  // namespace gpmi
 
 using namespace gpmi;
@@ -1919,7 +2334,7 @@ void split_by_path(const BatchArgs& a, long max_n, std::vector<int>& mine, std::
 }
 
 // workspace bytes of one problem: `own` adds up over a wave, `shared` is needed once per wave, as wide as the widest problem asks for; `in`: the bytes the problem
-// alone adds to the wave's packed input, where they are not small beside its workspace (gp_vfe_batch: n reaches 262 144) — they add up against the staging limit
+// alone adds to the wave's packed input, where they are not small beside its workspace (gp_vfe_batch: n reaches 262 144; gp_vfe_grad_batch adds the n-long results it stages back) — they add up against the staging limit
 struct WaveCost { size_t own, shared, in = 0; };
 // The kernel's problems in waves bounded by the launch size and by the workspace budget (a wave holds at least one problem); run(idx, nw) serves one wave.
 template <class Cost, class Run> int32_t for_each_wave(gp_ctx* c, const std::vector<int>& mine, Cost&& cost, Run&& run) {
@@ -2864,6 +3279,15 @@ struct VfeArgs : BatchArgs {  // logpdf_out is objective_out
     const gp_points& zb(int b) const { return z[nz == 1 ? 0 : b]; }
     void* eb(int b) const { return meps_out ? meps_out[b] : nullptr; }
 };
+// the gradient outputs of gp_vfe_grad_batch (arrays of nb; dscale, dz and dx may be NULL)
+struct VfeGradOut {
+    double* dvar;
+    double* const* dscale;
+    void* const* dnoise;
+    void* const* dy;
+    double* const* dz;
+    void* const* dx;
+};
 
 // the pseudo-inputs of one problem, dimension-major [d][m], scaled as the sparse path scales its inputs on the host (one product per entry)
 void pack_scaled_points(const gp_kernel& k, const gp_points& z, double* out) {
@@ -2921,11 +3345,23 @@ long vfe_ws(const VfeArgs& a, int b) {
     const long m = a.zb(b).n, np = batch_np(m);
     return 2 * batch_slice(m) + np * batch_ld(np) + vfe_nseg(a.xb(b).n) * vfe_part(np);
 }
+// what the gradient adds: Λ_ε.L⁻ᵀ, H, V H, G_ψ and G_zz (np rows of ld each) and a slot of gradient sums per segment
+long vfe_grad_ws(const VfeArgs& a, int b) {
+    const long np = batch_np(a.zb(b).n);
+    return 5 * np * batch_ld(np) + vfe_nseg(a.xb(b).n) * vfe_gpart(np, a.xb(b).d);
+}
 
 // doubles problem b alone adds to the packed input of its wave: its z, mean and noise vector, and its x and y where the problems do not share them
 long vfe_in(const VfeArgs& a, int b) {
     const gp_points &x = a.xb(b), &z = a.zb(b);
     return (long)z.d * z.n + (a.nx == 1 ? 0 : (long)x.d * x.n) + (a.ny == 1 ? 0 : x.n) + (a.mb(b) ? x.n : 0) + (a.noise[b].kind == 1 ? x.n : 0);
+}
+
+// doubles problem b alone adds to the result buffer of a gradient wave (run_vfe_wave's layout): α, the sums, dz, dy and, where they exist, the dnoise vector and
+// dx.  They are page-locked staging like the packed input and as long (dx: n·d per problem even where x is shared), so the wave bound counts them with it.
+long vfe_grad_out(const VfeArgs& a, const VfeGradOut& go, int b) {
+    const gp_points &x = a.xb(b), &z = a.zb(b);
+    return 2 + z.n + VFE_GH + (long)z.d * z.n + x.n + (a.noise[b].kind == 1 ? x.n : 0) + (go.dx ? (long)x.d * x.n : 0);
 }
 
 // fills the data of a laid-out wave behind its tables: every problem's scaled z, then x and y (a shared one once), mean and noise vector
@@ -2943,14 +3379,31 @@ void vfe_wave_fill(const VfeArgs& a, const int* idx, int nw, const std::vector<V
     }
 }
 
-// three launches: the problems idx[0..nw) of the call, all taken by the kernels.  Caller holds the ctx lock.
-int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw) {
+// NaN in every gradient entry of problem b (the call's dtype: a routed fp32 problem has float arrays)
+void vfe_grad_fill_nan(const VfeArgs& a, const VfeGradOut& go, int b) {
+    const gp_points &x = a.xb(b), &z = a.zb(b);
+    go.dvar[b] = std::numeric_limits<double>::quiet_NaN();
+    if (go.dscale) fill_nan(go.dscale[b], 0, a.k[b].nscale);
+    fill_nan(go.dnoise[b], a.dtype, a.noise[b].kind == 1 ? x.n : 1);
+    fill_nan(go.dy[b], a.dtype, x.n);
+    if (go.dz) fill_nan(go.dz[b], 0, (long)z.n * z.d);
+    if (go.dx) fill_nan(go.dx[b], a.dtype, (long)x.n * x.d);
+}
+
+// three launches: the problems idx[0..nw) of the call, all taken by the kernels.  Caller holds the ctx lock.  With go (gp_vfe_grad_batch) three more behind them:
+// α of every problem goes to the result buffer, whether the caller asked for it or not, and the gradient's tables and results are laid out beside the fit's.
+int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw, const VfeGradOut* go = nullptr) {
     WaveLayout L;
     L.roff = 2L * nw;
     Table<VfeProb> vp;
     Table<VfeSeg> sg;
+    Table<VfeGrad> vg;
     vp.v.assign((size_t)nw, VfeProb{});
     vp.place(L);
+    if (go) {
+        vg.v.assign((size_t)nw, VfeGrad{});
+        vg.place(L);
+    }
     SharedOnce xo{a.nx == 1}, yo{a.ny == 1};
     for (int t = 0; t < nw; ++t) {
         const int b = idx[t];
@@ -2970,30 +3423,61 @@ int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw) {
         p.w_off = take(L.ws, (long)p.np * p.ld);
         p.d_off = take(L.ws, batch_slice(z.n));
         p.part_off = take(L.ws, p.nseg * vfe_part(p.np));
-        p.alpha_off = a.ab(b) ? take(L.roff, z.n) : -1;
+        p.alpha_off = (a.ab(b) || go) ? take(L.roff, z.n) : -1;
         p.meps_off = a.eb(b) ? take(L.roff, z.n) : -1;
         for (int s = 0; s < p.nseg; ++s) sg.v.push_back(VfeSeg{t, s});
+        if (go) {
+            VfeGrad& q = vg.v[t];
+            const long sq = (long)p.np * p.ld;
+            q.u_off = take(L.ws, sq), q.h_off = take(L.ws, sq), q.rt_off = take(L.ws, sq), q.gpsi_off = take(L.ws, sq), q.gzz_off = take(L.ws, sq);
+            q.gpart_off = take(L.ws, p.nseg * vfe_gpart(p.np, p.d));
+            q.gh_off = take(L.roff, VFE_GH);
+            q.dz_off = take(L.roff, (long)z.d * z.n);
+            q.dn_off = a.noise[b].kind == 1 ? take(L.roff, x.n) : -1;
+            q.dy_off = take(L.roff, x.n);
+            q.dx_off = go->dx ? take(L.roff, (long)x.d * x.n) : -1;
+        }
     }
     sg.place(L);
     WaveMem m(c);
     RC(m.alloc(L.off, L.ws, L.roff));
     vp.fill(m);
     sg.fill(m);
+    vg.fill(m);
     vfe_wave_fill(a, idx, nw, vp.v, m.hin);
     RC(run_drained(c, [&]() -> int32_t {
         RC(m.upload());
         RC(launch(m, vfe_prelude_kernel, nw, NT, nw, vp.dev(m)));
         RC(launch(m, vfe_stream_kernel, sg.v.size(), NT, nw, vp.dev(m), sg.dev(m)));
         RC(launch(m, vfe_final_kernel, nw, NT, nw, vp.dev(m)));
+        if (go) {
+            RC(launch(m, vfe_gmm_kernel, nw, NT, nw, vp.dev(m), vg.dev(m)));
+            RC(launch(m, vfe_gstream_kernel, sg.v.size(), NT, nw, vp.dev(m), vg.dev(m), sg.dev(m)));
+            RC(launch(m, vfe_gfinish_kernel, nw, NT, nw, vp.dev(m), vg.dev(m)));
+        }
         return m.download_and_sync();
     }));
-    c->vfe_batch_problems += nw;
+    (go ? c->vfe_grad_batch_problems : c->vfe_batch_problems) += nw;
     for (int t = 0; t < nw; ++t) {
         const int b = idx[t];
         const VfeProb& p = vp.v[t];
         put_result(a, b, m.hout[t], (int32_t)m.hout[nw + t]);
-        if (p.alpha_off >= 0) std::memcpy(a.ab(b), m.hout + p.alpha_off, sizeof(double) * p.m);
+        if (p.alpha_off >= 0 && a.ab(b)) std::memcpy(a.ab(b), m.hout + p.alpha_off, sizeof(double) * p.m);
         if (p.meps_off >= 0) std::memcpy(a.eb(b), m.hout + p.meps_off, sizeof(double) * p.m);
+        if (!go) continue;
+        if (m.hout[nw + t] != 0.0) {  // failure is data: the gradient kernels skipped the problem
+            vfe_grad_fill_nan(a, *go, b);
+            continue;
+        }
+        const VfeGrad& q = vg.v[t];
+        const double* gh = m.hout + q.gh_off;
+        go->dvar[b] = gh[0];
+        if (go->dscale && p.nscale > 0) std::memcpy(go->dscale[b], gh + 1, sizeof(double) * p.nscale);
+        if (q.dn_off >= 0) std::memcpy(go->dnoise[b], m.hout + q.dn_off, sizeof(double) * p.n);
+        else *(double*)go->dnoise[b] = gh[17];
+        std::memcpy(go->dy[b], m.hout + q.dy_off, sizeof(double) * p.n);
+        if (go->dz) grad_to_layout<double>(a.zb(b).layout, p.m, p.d, m.hout + q.dz_off, p.m, go->dz[b]);  // [d][m] -> the container layout of z
+        if (go->dx) grad_to_layout<double>(a.xb(b).layout, p.n, p.d, m.hout + q.dx_off, p.n, go->dx[b]);
     }
     return 0;
 }
@@ -3021,6 +3505,49 @@ int32_t vfe_batch_impl(gp_ctx* c, VfeArgs& a) {
             fill_nan(a.ab(b), a.dtype, a.zb(b).n);
             fill_nan(a.eb(b), a.dtype, a.zb(b).n);
         }));
+    }
+    return 0;
+}
+
+// gp_vfe_grad_batch: the body of vfe_batch_impl with the gradient behind the fit — three more launches per wave, gp_vfe_grad behind gp_vfe_fit for the rest
+int32_t vfe_grad_batch_impl(gp_ctx* c, VfeArgs& a, const VfeGradOut& go) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    if (a.nb < 0) return set_arg_err(2, "nb must be >= 0");
+    if (a.nb == 0) return 0;
+    RC(check_vfe_args(a));
+    if (!go.dvar) return set_arg_err(16, "dvariance_out is NULL");
+    if (!go.dnoise) return set_arg_err(18, "dnoise_out is NULL");
+    if (!go.dy) return set_arg_err(19, "dy_out is NULL");
+    for (int b = 0; b < a.nb; ++b) {
+        if (go.dscale && a.k[b].nscale > 0 && !go.dscale[b]) return set_arg_err(17, "a dscale_out pointer is NULL where the kernel has scales");
+        if (!go.dnoise[b]) return set_arg_err(18, "a dnoise_out pointer is NULL");
+        if (!go.dy[b]) return set_arg_err(19, "a dy_out pointer is NULL");
+        if (go.dz && !go.dz[b]) return set_arg_err(20, "a dz_out pointer is NULL");
+        if (go.dx && !go.dx[b]) return set_arg_err(21, "a dx_out pointer is NULL");
+    }
+    const long max_n = env_capped(getenv("GPMI_VFE_GRAD_BATCH_MAX_N"), GPMI355_VFE_GRAD_BATCH_MAX_N, VFE_KERNEL_MAX_N);
+    std::vector<int> mine, routed;
+    for (int b = 0; b < a.nb; ++b) (vfe_batch_takes(a, b, max_n) ? mine : routed).push_back(b);
+    RC(for_each_wave(c, mine,
+                     [&](int b) {  // the staging bound covers what goes in and what comes back
+                         return WaveCost{sizeof(double) * (size_t)(vfe_ws(a, b) + vfe_grad_ws(a, b)), 0, sizeof(double) * (size_t)(vfe_in(a, b) + vfe_grad_out(a, go, b))};
+                     },
+                     [&](const int* idx, int nw) { return run_vfe_wave(c, a, idx, nw, &go); }));
+    // everything else: gp_vfe_fit + gp_vfe_grad + gp_vfe_free, one problem at a time, after the lock is released; the single path's rules hold (dz on an
+    // fp32 handle is refused there)
+    gd.lk.unlock();
+    for (int b : routed) {
+        const bool diag = a.noise[b].kind == 1;
+        gp_vfe* h = nullptr;
+        double dns = 0.0;
+        int32_t rc = gp_vfe_fit(c, &a.k[b], &a.xb(b), &a.zb(b), &a.noise[b], a.jitter[b], a.mb(b), a.yb(b), a.approx[b], &h, logpdf_slot(a, b));
+        if (rc == 0 && h)
+            rc = gp_vfe_grad(h, &go.dvar[b], go.dscale ? go.dscale[b] : nullptr, diag ? nullptr : &dns, diag ? go.dnoise[b] : nullptr, go.dy[b],
+                             go.dz ? go.dz[b] : nullptr, a.zb(b).layout, go.dx ? go.dx[b] : nullptr, a.xb(b).layout);
+        if (h) (void)gp_vfe_free(h);
+        if (rc == 0 && !diag) put(go.dnoise[b], a.dtype, 0, dns);
+        RC(routed_done(a, b, rc, [&] { vfe_grad_fill_nan(a, go, b); }));
     }
     return 0;
 }
@@ -3186,5 +3713,13 @@ int32_t gp_vfe_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, co
                      const int32_t* approx, void* objective_out, int32_t* info_out, void* const* alpha_out_or_null, void* const* m_eps_out_or_null) {
     VfeArgs a{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, objective_out, info_out, alpha_out_or_null), nz, z, jitter, approx, m_eps_out_or_null};
     return vfe_batch_impl(ctx, a);
+}
+
+int32_t gp_vfe_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, int32_t nz, const gp_points* z,
+                          const gp_noise* noise, const double* jitter, const void* const* mean_or_null, int32_t ny, const void* const* y,
+                          const int32_t* approx, void* objective_out, int32_t* info_out, double* dvariance_out, double* const* dscale_out_or_null,
+                          void* const* dnoise_out, void* const* dy_out, double* const* dz_out_or_null, void* const* dx_out_or_null) {
+    VfeArgs a{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, objective_out, info_out), nz, z, jitter, approx, nullptr};
+    return vfe_grad_batch_impl(ctx, a, VfeGradOut{dvariance_out, dscale_out_or_null, dnoise_out, dy_out, dz_out_or_null, dx_out_or_null});
 }
 }

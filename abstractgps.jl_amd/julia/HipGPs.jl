@@ -1734,6 +1734,78 @@ function approx_log_evidence_batch(approxs::AbstractVector, fxs::AbstractVector{
 end
 elbo_batch(approxs, fxs, ys; kw...) = approx_log_evidence_batch(approxs, fxs, ys; kw...)
 
+# ---- value + gradient of many small sparse GPs in one call: gp_vfe_grad_batch ---------------------------------------------------------------
+# elbo_and_grad_batch(approxs, fxs, ys; wrt_x): elbo_and_grad of every problem — (objectives, vector of the named tuples elbo_and_grad returns) — in ONE
+# library call per (context, eltype) group; sharing rules and on_error as approx_log_evidence_batch.  Accelerated forms only (single-kind kernel, scalar or
+# diagonal Σy, scalar jitter): there is no stock-path pullback to fall back on.
+function elbo_and_grad_batch(approxs::AbstractVector, fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys; wrt_x::Bool=false, on_error::Symbol=:raise)
+    on_error in (:raise, :nan) || throw(ArgumentError("on_error must be :raise or :nan"))
+    nb = length(approxs)
+    fv = length(fxs) == 1 ? fill(fxs[1], nb) : fxs
+    yv = (ys isa AbstractVector{<:Real}) ? fill(ys, nb) : (length(ys) == 1 ? fill(ys[1], nb) : collect(ys))
+    (length(fv) == nb && length(yv) == nb) || throw(DimensionMismatch("$(nb) approximations, $(length(fv)) FiniteGPs, $(length(yv)) observation vectors"))
+    obj = fill(NaN, nb)
+    info = zeros(Int32, nb)
+    grads = Vector{Any}(nothing, nb)
+    args = Vector{Any}(nothing, nb)
+    groups = Dict{Any,Vector{Int}}()
+    for b in 1:nb
+        ap, fx, y = approxs[b], fv[b], yv[b]
+        @assert ap.fz.f === fx.f
+        length(fx) == length(y) || throw(DimensionMismatch("problem $(b): length(fx) != length(y)"))
+        a = marshal(fx, eltype(y))
+        (a === nothing || haskey(a, :ks) || is_dense(a.cn) || !(ap.fz.Σy isa Diagonal{<:Any,<:Fill})) &&
+            throw(ArgumentError("problem $(b): kernel / noise / pseudo-input form is not accelerated"))
+        pz = points(ap.fz.x, a.T)
+        args[b] = (a=a, zbuf=pz[1], cz=pz[2], jitter=Float64(FillArrays.getindex_value(ap.fz.Σy.diag)))
+        push!(get!(groups, (fx.f.ctx, a.T), Int[]), b)
+    end
+    for ((ctx, Tg), idx) in groups
+        g = length(idx)
+        nx = all(b -> fv[b].x === fv[idx[1]].x, idx) ? 1 : g
+        nz = all(b -> approxs[b].fz.x === approxs[idx[1]].fz.x, idx) ? 1 : g
+        ny = all(b -> yv[b] === yv[idx[1]], idx) ? 1 : g
+        cks = [args[b].a.ck for b in idx]
+        cxs = [args[b].a.cx for b in idx[1:nx]]
+        czs = [args[b].cz for b in idx[1:nz]]
+        cns = [args[b].a.cn for b in idx]
+        jit = Float64[args[b].jitter for b in idx]
+        kinds = Int32[approxs[b] isa VFE ? 0 : 1 for b in idx]
+        ybufs = [Vector{Tg}(yv[b]) for b in idx[1:ny]]
+        yptrs = Ptr{Cvoid}[pointer(v) for v in ybufs]
+        mptrs = Ptr{Cvoid}[args[b].a.m === nothing ? C_NULL : pointer(args[b].a.m) for b in idx]
+        out = Vector{Tg}(undef, g)
+        inf = zeros(Int32, g)
+        dvar = zeros(Float64, g)
+        dscs = [zeros(Float64, max(length(args[b].a.scales), 1)) for b in idx]
+        dnos = [Vector{Tg}(undef, args[b].a.cn.kind == 0 ? 1 : length(yv[b])) for b in idx]
+        dys = [Vector{Tg}(undef, length(yv[b])) for b in idx]
+        dzs = Tg === Float64 ? [similar(args[b].zbuf, Float64) for b in idx] : Vector{Float64}[]
+        dxs = wrt_x ? [similar(args[b].a.xbuf) for b in idx] : Vector{Tg}[]
+        sptrs = Ptr{Float64}[pointer(v) for v in dscs]
+        nptrs = Ptr{Cvoid}[pointer(v) for v in dnos]
+        dyptrs = Ptr{Cvoid}[pointer(v) for v in dys]
+        zptrs = Ptr{Float64}[pointer(v) for v in dzs]
+        xptrs = Ptr{Cvoid}[pointer(v) for v in dxs]
+        GC.@preserve args cks cxs czs cns jit kinds ybufs yptrs mptrs out inf dvar dscs dnos dys dzs dxs sptrs nptrs dyptrs zptrs xptrs begin
+            check(ccall((:gp_vfe_grad_batch, libgpmi355), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{CKernel}, Int32, Ptr{CPoints}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Float64}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}},
+                    Ptr{Int32}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Float64}, Ptr{Ptr{Float64}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Float64}}, Ptr{Ptr{Cvoid}}),
+                ctx.handle, g, cks, nx, cxs, nz, czs, cns, jit, mptrs, ny, yptrs, kinds, out, inf, dvar, sptrs, nptrs, dyptrs,
+                Tg === Float64 ? pointer(zptrs) : C_NULL, wrt_x ? pointer(xptrs) : C_NULL))
+        end
+        for (j, b) in enumerate(idx)
+            obj[b] = out[j]
+            info[b] = inf[j]
+            grads[b] = (variance=dvar[j], scale=dscs[j][1:length(args[b].a.scales)], noise=args[b].a.cn.kind == 0 ? dnos[j][1] : dnos[j], y=dys[j], mean=-dys[j],
+                z=Tg === Float64 ? dzs[j] : nothing, x=wrt_x ? dxs[j] : nothing)
+        end
+    end
+    bad = findfirst(!iszero, info)
+    on_error === :raise && bad !== nothing && throw(BatchPosDefException(Int(info[bad]), bad))
+    return obj, grads
+end
+
 # ---- value + gradient of the sparse objective: one fit + one backward pass over the retained observations (gp_vfe_grad) ------------------
 # The reference's users maximise `elbo(VFE(f(z, jitter)), f(x, Σy), y)` over kernel parameters and pseudo-points by AD / finite differences
 # (examples/0-intro-1d/script.jl:385-394); the ccall is opaque to AD, so the accelerated objective carries its own pullback.

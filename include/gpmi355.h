@@ -310,6 +310,7 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
  *   "batch_joint_kernel_problems"     read-only: the same for the kernels of gp_joint_batch / _sum
  *   "batch_loo_kernel_problems", "batch_loo_grad_kernel_problems"   read-only: the same for the kernels of gp_loo_batch / _sum and of gp_loo_grad_batch / _sum
  *   "vfe_batch_kernel_problems"       read-only: the same for the kernels of gp_vfe_batch
+ *   "vfe_grad_batch_kernel_problems"  read-only: the same for the kernels of gp_vfe_grad_batch
  *   "cols_kernel_calls", "cols_kernel_splits"   read-only: kmul launches gp_posterior_predict_cols has served on this ctx since it was created, and the workgroups
  *                    along the training range of the last of them (1 = unsplit, 0 = none yet): which path ran, for tests and measurements */
 /* The defaults above, machine-readable (single-device parameters; gp_ctx_get_param reads the same names): the test-suite asserts before
@@ -982,6 +983,43 @@ int32_t gp_vfe_free(gp_vfe* post);
 int32_t gp_vfe_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, int32_t nz, const gp_points* z,
                      const gp_noise* noise, const double* jitter, const void* const* mean_or_null, int32_t ny, const void* const* y,
                      const int32_t* approx, void* objective_out, int32_t* info_out, void* const* alpha_out_or_null, void* const* m_eps_out_or_null);
+
+/* gp_vfe_grad_batch: value AND gradient of nb independent VFE / DTC problems in one call — what every gradient-based caller of gp_vfe_batch needs per step (a
+ * loop of gp_vfe_fit + gp_vfe_grad + gp_vfe_free otherwise).  Inputs, sharing rules (nx, nz, ny ∈ {1, nb}) and objective_out / info_out exactly as
+ * gp_vfe_batch; per problem the semantics are those of gp_vfe_fit followed by gp_vfe_grad.  Outputs, arrays of nb:
+ *   dvariance_out [nb]        ∂/∂σ_k²                          dscale_out_or_null[b] [nscale_b]   ∂/∂s or ∂/∂v_p (a pointer wherever the kernel has scales)
+ *   dnoise_out[b]             ONE entry, Σ_i ∂/∂Σy_ii, for a scalar σ²; n_b entries for a diagonal noise (as gp_logpdf_grad_batch lays it out)
+ *   dy_out[b] [n_b]           ∂/∂y_i (= −∂/∂m_i)               dz_out_or_null[b] [m_b·d]  ∂/∂z in the layout of that problem's z, fp64
+ *   dx_out_or_null[b] [n_b·d] ∂/∂x in the layout of that problem's x; problems sharing one x object each get their own array
+ * objective, dnoise, dy and dx in the call's dtype.  Failure is data: a failed problem reports info_out[b] and gets NaN in its objective and in every
+ * gradient entry; the others are not affected.  The return value reports argument errors only.
+ * Eligibility as gp_vfe_batch with n_b <= GPMI355_VFE_GRAD_BATCH_MAX_N; the fit's three launches run unchanged (the objective is bit-equal to gp_vfe_batch's,
+ * α always goes to the result buffer), three more follow per wave (csrc/batch.hip):
+ *   vfe_gmm_kernel      one workgroup per problem: Λ_ε.L⁻ᵀ by substitution on the resident factor, B Bᵀ summed again from the segments' slots, then
+ *                       A⁻¹ = U Uᵀ and the two conjugations G_ψ = ½[V H_ψ Vᵀ − ααᵀ], G_zz = ½[V H_zz Vᵀ − ααᵀ] on v_mfma_f64_16x16x4_f64 in 32×32 wave tiles,
+ *                       zero blocks of the triangular operands skipped, both halves written from the lower tiles;
+ *   vfe_gstream_kernel  one workgroup per (problem, segment of GPMI355_VFE_BATCH_SEG observations): G_ψ stays in LDS as the 36 16×16 blocks of its lower
+ *                       triangle (a full copy does not fit beside the tile buffer; the upper blocks are read transposed); per tile of 64 observations
+ *                       K̃ into LDS, T = G_ψ K̃ by MFMA over K̃, then κ and κ′ again from (z_i − x_j) for the weights, ∂/∂σ_j², ∂/∂y_j and ∂/∂x_j straight
+ *                       to the results and the segment's sums of ∂/∂variance, ∂/∂scale, ∂/∂z into its own slot; K_xz, T and the weights never reach HBM;
+ *   vfe_gfinish_kernel  one workgroup per problem: the slots in segment order, the K_zz term with G_zz over the full M×M square, the VFE trace term.
+ * No floating-point atomics, no waits between workgroups, every sum in an order the problem's own sizes fix: the same bits alone, anywhere in any batch and
+ * on repetition.  Every other problem is answered inside the call by gp_vfe_fit + gp_vfe_grad + gp_vfe_free under the single path's rules (dz on an fp32
+ * handle is refused: −7).  The read-only ctx parameter "vfe_grad_batch_kernel_problems" counts the problems the kernels served.
+ * GPMI355_VFE_GRAD_BATCH_MAX_N: by the rule of the other batch thresholds — the largest n of the measured sweep (tools/vfe_grad_batch_profile.py,
+ * profiles/r36/vfe_grad_batch_profile.json and, for nb = 512, vfe_grad_batch_profile_nb512.json: one process each, SE, D = 3, all outputs except dx,
+ * M = 16, 64, 128 × n = 1 024 … 262 144 × nb = 1, 8, 64, 512, shared and per-problem (x, y): 120 cells, none skipped) at which one batch call beat the loop of
+ * gp_vfe_fit + gp_vfe_grad + gp_vfe_free in every cell with nb >= 8.  It beat it in all 90 of them, so the macro is the largest n swept.  The closest cells:
+ * M = 128, n = 262 144, per-problem data, nb = 8 15.9 against 23.4 ms, nb = 64 103 against 187 ms and nb = 512 824 against 1 438 ms (shared: 10.9 against
+ * 21.9, 64.6 against 176 and 489 against 1 373 ms); at n = 1 024 the call is 5 (M = 128, nb = 8) to 350 (M = 16, nb = 512) times faster.  A single problem (nb = 1) loses at M = 64 from n = 4 096 on (1.11 against 0.94 ms) and at M = 128 everywhere (1.45 against
+ * 0.94 ms at n = 1 024, 5.2 against 2.75 ms at n = 262 144: one workgroup runs the M×M side from global memory); the rule does not count it.  dx was measured
+ * in 8 cells only (M = 128, n = 1 024 and 65 536, nb = 8 and 64: vfe_grad_batch_profile_dx.json, 2.3 … 37 times faster).  (The environment variable
+ * GPMI_VFE_GRAD_BATCH_MAX_N, read per call, overrides the macro for measurements.) */
+#define GPMI355_VFE_GRAD_BATCH_MAX_N 262144
+int32_t gp_vfe_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, int32_t nz, const gp_points* z,
+                          const gp_noise* noise, const double* jitter, const void* const* mean_or_null, int32_t ny, const void* const* y,
+                          const int32_t* approx, void* objective_out, int32_t* info_out, double* dvariance_out, double* const* dscale_out_or_null,
+                          void* const* dnoise_out, void* const* dy_out, double* const* dz_out_or_null, void* const* dx_out_or_null);
 
 /* ---- device-level building blocks ------------------------------------------------------------ */
 /* The operations the in-library multi-device driver composes (csrc/multi.hip calls the same engine functions), exposed on DEVICE
