@@ -2444,6 +2444,48 @@ def elbo_and_grad_batch(approxs, fxs, ys, *, wrt_x: bool = False, on_error: str 
     return _batch_merge(len(approxs), parts, False, on_error), grads
 
 
+def approx_mean_and_var_batch(approxs, fxs, ys, xs, *, what: int = 3, return_objective: bool = False, on_error: str = "raise"):
+    """mean_and_var(posterior(approxs[b], fxs[b], ys[b]), xs[b]) of many independent sparse GPs in one library call per (ctx, dtype) group
+    (gp_vfe_predict_batch; src/sparse_approximations.jl:183-217 once per problem).  approxs, fxs, ys as in elbo_batch; xs: ONE container shared by every
+    problem, or a sequence of length 1 or len(approxs) (each entry with its own number of test points, 0 included); the same xs object in every entry is
+    sent once.  what: 1 the mean, 2 the variance, 3 both.  Returns (means, vars): lists of arrays in the caller's order, None for a side not asked for;
+    with return_objective the array of objectives follows.  on_error as in elbo_batch; with "nan" a failed problem has NaN in its outputs."""
+    if on_error not in ("raise", "nan"):
+        raise ValueError('on_error must be "raise" or "nan"')
+    if what not in (1, 2, 3):
+        raise ValueError("what must be 1 (mean), 2 (var) or 3 (both)")
+    approxs = list(approxs)
+    n = len(approxs)
+    xs = [xs] if isinstance(xs, (np.ndarray, ColVecs, RowVecs)) else list(xs)
+    if len(xs) == 1 and n > 1:
+        xs = xs * n
+    if len(xs) != n:
+        raise ValueError(f"DimensionMismatch: {n} problems but {len(xs)} sets of test points")
+    means, vars_ = ([None] * n if what & 1 else None), ([None] * n if what & 2 else None)
+    if not approxs:
+        return (means, vars_, np.empty(0)) if return_objective else (means, vars_)
+    parts = []
+    for g in _vfe_batch_groups(approxs, fxs, ys):
+        call = _vfe_batch_marshal(g, False, False)
+        m, nb = call.keep, call.nb
+        tss = [xs[i] for i in g.index]
+        nts = 1 if all(v is tss[0] for v in tss) else nb
+        xpts = (gp_points * nts)(*[m.points(v) for v in tss[:nts]])
+        pms = [_mean_vector(fx.f.mean_fn, v, g.dtype) for fx, v in zip(g.fxs, tss)]  # m(x*) on the host; None = ZeroMean
+        pms = [None if v is None else m.arr(v) for v in pms]
+        pmarr = None if all(v is None for v in pms) else (C.c_void_p * nb)(*[None if v is None else v.ctypes.data for v in pms])
+        outs = [[np.empty(int(xpts[0 if nts == 1 else b].n), dtype=g.dtype) for b in range(nb)] if what & side else None for side in (1, 2)]
+        oarrs = [None if o is None else (C.c_void_p * nb)(*[a.ctypes.data for a in o]) for o in outs]
+        ctx = g.ctx or default_context()
+        check(ctx.lib.gp_vfe_predict_batch(ctx.handle, *call.args[:12], nts, xpts, pmarr, what, *oarrs, *call.args[12:14]))
+        parts.append((g.index, call.out, call.info, None))
+        for dst, src in zip((means, vars_), outs):
+            for i, v in zip(g.index, src or []):
+                dst[i] = v
+    obj = _batch_merge(n, parts, False, on_error)
+    return (means, vars_, obj) if return_objective else (means, vars_)
+
+
 # --------------------------------------------------------------------------------------------
 # VFE / DTC for a matrix of observations: gp_vfe_fit_cols / _update_cols / _append_cols / _predict_cols / _get_cols / _get_by_cols / _grad_cols
 # --------------------------------------------------------------------------------------------

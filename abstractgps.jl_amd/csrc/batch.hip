@@ -204,6 +204,17 @@ __device__ __forceinline__ double strip_solve(double* V, const double* A, long l
     return ss;
 }
 
+// S = L⁻ᵀ of the factor in the lower triangle of a slice (np rows and columns, identity padding), as a strip of np rows: strip_solve on the rows of the
+// identity.  What the sparse kernels invert their two M×M factors by (L_z in vfe_prelude_kernel, the factor of Λ_ε in vfe_gmm_kernel and vfe_pprep_kernel).
+__device__ __forceinline__ void strip_inverse_t(double* S, const double* A, long ld, int np, double* sh, int tid, int lane, int w) {
+    for (int e = tid; e < np * np; e += NT) {
+        const int i = e / np, cc = e - i * np;
+        S[(long)i * ld + cc] = i == cc ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    (void)strip_solve(S, A, ld, 0, np / BT, np, sh, tid, lane, w);
+}
+
 // The blocked right-looking Cholesky of a slice in the batch_slice layout, by one workgroup of NT threads: 64-column blocks, the diagonal block in LDS, the rows
 // below it (the carried row np included) by rows_solve_b64, the trailing update on 32×32 wave tiles dealt round-robin to the eight waves.  Ls, dinv and red
 // are the workgroup's LDS ([BT][BTS], [BT], at least BT entries); logdet_half gains Σ log L_ii of the rows below n (thread 0 holds the sum).  Returns 0, or the
@@ -1360,13 +1371,7 @@ __global__ __launch_bounds__(NT) void vfe_prelude_kernel(const double* __restric
         res[nw + P.slot] = (double)failcol;
     }
     if (failcol) return;
-    double* __restrict__ V = ws + P.w_off;
-    for (int e = tid; e < np * np; e += NT) {
-        const int i = e / np, cc = e - i * np;
-        V[(long)i * ld + cc] = i == cc ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    (void)strip_solve(V, Lz, ld, 0, nt, np, sh, tid, lane, w);
+    strip_inverse_t(ws + P.w_off, Lz, ld, np, sh, tid, lane, w);
 }
 
 // (ti, tj) of the t-th 32×32 tile of a lower triangle counted row by row
@@ -1387,6 +1392,51 @@ __device__ __forceinline__ void vfe_syrk_tile(d4_t (&g4)[2][2], const double* KB
         g4[0][1] = Tr<double>::mfma(a0, b1, g4[0][1]);
         g4[1][0] = Tr<double>::mfma(a1, b0, g4[1][0]);
         g4[1][1] = Tr<double>::mfma(a1, b1, g4[1][1]);
+    }
+}
+
+// W = L_z⁻¹ out of the strip V = Wᵀ into LDS as the 16×16 blocks of its lower triangle, counted row by row, each k-major (Wt[blk][k][row]); the eight waves
+// take the blocks round-robin, and the caller's barrier closes the load
+__device__ __forceinline__ void vfe_load_wt(double* Wt, const double* __restrict__ V, long ld, int nb16, int w, int lane) {
+    int cnt = 0;
+    for (int bi = 0; bi < nb16; ++bi)
+        for (int bk = 0; bk <= bi; ++bk, ++cnt) {
+            if ((cnt & 7) != w) continue;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int e = lane + 64 * q;  // e = 16 k + row
+                Wt[cnt * 256 + e] = V[(long)(16 * bk + (e >> 4)) * ld + 16 * bi + (e & 15)];
+            }
+        }
+}
+// acc[q] = (T X)[row block (w >> 2) + 2 q, column block w & 3] for a lower-triangular T and the tile X in LDS (np rows, stride KBS): the k loop of row block bi
+// runs over the blocks 0 … bi alone.  frag(bi, bk, k) is T[16 bi + r][16 bk + k], this lane's entry of the A operand.  Returns Σ of the squares of the lane's
+// sixteen entries (q, then e: an order the lane's position in the tile does not enter).
+template <class Frag>
+__device__ __forceinline__ double vfe_tri_mm(d4_t (&acc)[4], const double* X, int nb16, int w, int lane, Frag&& frag) {
+    const int r = lane & 15, g = lane >> 4, cb = w & 3;
+    double sq = 0.0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        acc[q] = 0.0;
+        const int bi = (w >> 2) + 2 * q;
+        if (bi < nb16)
+            for (int bk = 0; bk <= bi; ++bk)
+#pragma unroll
+                for (int s = 0; s < 4; ++s) acc[q] = Tr<double>::mfma(frag(bi, bk, 4 * s + g), X[(16 * bk + 4 * s + g) * KBS + 16 * cb + r], acc[q]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sq = fma(acc[q][e], acc[q][e], sq);
+    }
+    return sq;
+}
+// the accumulators of vfe_tri_mm back over the tile
+__device__ __forceinline__ void vfe_tri_store(const d4_t (&acc)[4], double* X, int nb16, int w, int lane) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int bi = (w >> 2) + 2 * q;
+        if (bi < nb16)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) X[(16 * bi + Tr<double>::crow(lane, e)) * KBS + 16 * (w & 3) + (lane & 15)] = acc[q][e];
     }
 }
 
@@ -1419,19 +1469,7 @@ __global__ __launch_bounds__(NT) void vfe_stream_kernel(const double* __restrict
     const double* __restrict__ z = in + P.z_off;
     const double* __restrict__ x = in + P.x_off;
     const double* __restrict__ y = in + P.y_off;
-    {
-        const double* __restrict__ V = ws + P.w_off;
-        int cnt = 0;
-        for (int bi = 0; bi < nb16; ++bi)
-            for (int bk = 0; bk <= bi; ++bk, ++cnt) {
-                if ((cnt & 7) != w) continue;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int e = lane + 64 * q;  // e = 16 k + row
-                    Wt[cnt * 256 + e] = V[(long)(16 * bk + (e >> 4)) * ld + 16 * bi + (e & 15)];
-                }
-            }
-    }
+    vfe_load_wt(Wt, ws + P.w_off, ld, nb16, w, lane);
     // the wave's tiles of G
     int i0a = 0, c0a = 0, i0b = 0, c0b = 0;
     const bool has_a = w < ntl, has_b = w >= 6 && w + 2 < ntl;
@@ -1491,28 +1529,10 @@ __global__ __launch_bounds__(NT) void vfe_stream_kernel(const double* __restrict
         __syncthreads();
         // ---- 2. B = W K̃ over the non-zero k blocks, into registers; then over K̃
         {
-            const int cb = w & 3;
             d4_t acc[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                acc[q] = 0.0;
-                const int bi = (w >> 2) + 2 * q;
-                if (bi < nb16) {
-                    const double* wb = Wt + bi * (bi + 1) / 2 * 256;
-                    for (int bk = 0; bk <= bi; ++bk, wb += 256)
-#pragma unroll
-                        for (int s = 0; s < 4; ++s)
-                            acc[q] = Tr<double>::mfma(wb[(4 * s + g) * 16 + r], KB[(16 * bk + 4 * s + g) * KBS + 16 * cb + r], acc[q]);
-                }
-            }
+            (void)vfe_tri_mm(acc, KB, nb16, w, lane, [&](int bi, int bk, int k) { return Wt[(bi * (bi + 1) / 2 + bk) * 256 + k * 16 + r]; });
             __syncthreads();
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int bi = (w >> 2) + 2 * q;
-                if (bi < nb16)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) KB[(16 * bi + Tr<double>::crow(lane, e)) * KBS + 16 * cb + r] = acc[q][e];
-            }
+            vfe_tri_store(acc, KB, nb16, w, lane);
         }
         __syncthreads();
         // ---- 3. G += B Bᵀ;  4. c += B b_y
@@ -1706,15 +1726,13 @@ __global__ __launch_bounds__(NT) void vfe_gmm_kernel(const double* __restrict__ 
     const double* __restrict__ part = ws + P.part_off;
     for (int e = tid; e < np * np; e += NT) {
         const int i = e / np, j = e - i * np;
-        U[(long)i * ld + j] = i == j ? 1.0 : 0.0;
         const int src = (j >> 5) <= (i >> 5) ? e : j * np + i;  // the stream kernel wrote the 32×32 tiles of the lower triangle
         double s = 0.0;
         for (int sg = 0; sg < nseg; ++sg) s += part[sg * psz + src];
         Gz[(long)i * ld + j] = s;
     }
     if (tid < np) al[tid] = tid < m ? res[P.alpha_off + tid] : 0.0;
-    __syncthreads();
-    (void)strip_solve(U, ws + P.d_off, ld, 0, np / BT, np, sh, tid, lane, w);
+    strip_inverse_t(U, ws + P.d_off, ld, np, sh, tid, lane, w);  // its barrier also orders the sums above
     auto from_row = [](int i0, int) { return i0; };
     auto from_both = [](int i0, int j0) { return i0 > j0 ? i0 : j0; };
     auto to_R = [&](int i, int j, double v) { R[(long)i * ld + j] = v; };
@@ -2052,6 +2070,122 @@ __global__ __launch_bounds__(NT) void vfe_gfinish_kernel(const double* __restric
         double s = 0.0;
         for (int e = (nscale == 1 ? 0 : tid * np); e < (nscale == 1 ? d * np : (tid + 1) * np); ++e) s += WK[e];
         gh[1 + tid] = s / P.scale[tid];
+    }
+}
+
+// ---- predictions of many small sparse GPs (gp_vfe_predict_batch): vfe_pprep_kernel, vfe_predict_kernel behind the fit's three launches ---------------------
+// With k*_j = K(z, x*_j), W = L_z⁻¹ (the strip the prelude left), E = L_D⁻¹ (L_D the factor of Λ_ε vfe_final_kernel left) and α out of the result buffer:
+//   mean_j = m(x*_j) + k*_jᵀ α,   var_j = k(x*_j, x*_j) − ‖W k*_j‖² + ‖E W k*_j‖²   (not clamped; the single path's formula, the same for VFE and DTC).
+// The two norms and not one resident Q = Wᵀ(I − Λ_ε⁻¹)W: the explicit Q loses two to three digits of the variance where it is smallest (include/gpmi355.h).
+enum {
+    VFE_PSEG = GPMI355_VFE_PREDICT_BATCH_SEG,  // consecutive test points per workgroup of the predict kernel
+    VFE_PRED_LAUNCH_SEGS = 1 << 16             // segments per predict launch at most
+};
+static_assert(VFE_PSEG % VT == 0, "a segment is whole tiles");
+// What a problem's predictions lay out beside VfeProb: u_off, the strip E ᵀ = L_D⁻ᵀ (np rows of ld) in the workspace; −1 where no variance is asked for or the
+// problem has no test points.
+struct VfePred {
+    long u_off;
+};
+// One segment of test points: xs_off ([d][ns], raw) and pm_off (m(x*), −1: none) into the packed input, mean_off / var_off (arrays of ns; −1: not wanted) into
+// the result buffer; the points [row0, row0 + cnt) of the ns of problem `prob`.
+struct VfePSeg {
+    long xs_off, pm_off, mean_off, var_off;
+    int prob, ns, row0, cnt;
+};
+static_assert(sizeof(VfePred) % 8 == 0 && sizeof(VfePSeg) % 8 == 0, "the tables are packed behind double data");
+
+// One workgroup per problem: E = L_D⁻¹ as the strip U = L_D⁻ᵀ, the first step of vfe_gmm_kernel.  A problem whose fit failed, or that needs no strip, is skipped.
+__global__ __launch_bounds__(NT) void vfe_pprep_kernel(const double* __restrict__ in, double* __restrict__ ws, const double* __restrict__ res, int nw,
+                                                       const VfeProb* __restrict__ vps, const VfePred* __restrict__ pps) {
+    __shared__ double sh[BT * BTS + BT];
+    const VfeProb& P = vps[blockIdx.x];
+    const long u_off = pps[blockIdx.x].u_off;
+    if (u_off < 0 || res[nw + P.slot] != 0.0) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    strip_inverse_t(ws + u_off, ws + P.d_off, P.ld, P.np, sh, tid, lane, w);
+}
+
+// One workgroup per (problem, segment of VFE_PSEG test points), tiles of 64.  LDS, 140 KB (one workgroup, eight waves, per CU): W in the blocked layout of
+// vfe_stream_kernel, resident for the whole segment; the tile buffer KB (np × 64, stride 65), which holds K*, then B*; α; the partial column norms of the two
+// row parities.  E does not fit beside them: its operand fragments come from global memory — the strip U = Eᵀ holds the sixteen rows of a fragment
+// consecutively, at most 128 KB per problem and read by every workgroup of the problem, so it stays in L2.  Per tile:
+//   1. K*[i][j] = variance κ(z_i, x*_j): lane = test point (its inputs scaled at the load; zeros beyond cnt), the eight waves interleave the pseudo-points;
+//      rows from m on are zero.  Wave 0 then takes mean_j = m_j + Σ_i K*_ij α_i off the tile, in pseudo-point order.
+//   2. B* = W K* (vfe_tri_mm, the stream kernel's product), written over K* once every wave has read it; ‖B*_j‖² out of the accumulators.
+//   3. C* = E B* the same way, never stored: ‖C*_j‖² alone.
+//   4. var_j = (variance − ‖B*_j‖²) + ‖C*_j‖², wave 0.
+// The norm of a column is the sum of its lane's sixteen squares, then of the four lane groups by two exchanges, then of the two row parities: no step sees
+// another column or the column's place in the tile, so a test point's results are the same bits in any company.  Padding rows of B* and C* are zero, padding
+// test points are never written.  A problem whose fit failed returns at once (the host fills its NaN).
+__global__ __launch_bounds__(NT) void vfe_predict_kernel(const double* __restrict__ in, const double* __restrict__ ws, double* __restrict__ res, int nw,
+                                                         const VfeProb* __restrict__ vps, const VfePred* __restrict__ pps, const VfePSeg* __restrict__ segs) {
+    __shared__ double Wt[(VFE_MAXM / 16) * (VFE_MAXM / 16 + 1) / 2 * 256];
+    __shared__ double KB[VFE_MAXM * KBS];
+    __shared__ double al[VFE_MAXM];
+    __shared__ double nrm[2][2][VT];  // [B*, C*][row parity][test point]
+    const VfePSeg S = segs[blockIdx.x];
+    const VfeProb& P = vps[S.prob];
+    if (res[nw + P.slot] != 0.0) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 15, g = lane >> 4;
+    const int m = P.m, np = P.np, d = P.d, nscale = P.nscale, ns = S.ns;
+    const long ld = P.ld;
+    const int nb16 = np / 16;
+    const bool want_mean = S.mean_off >= 0, want_var = S.var_off >= 0;
+    const double* __restrict__ z = in + P.z_off;
+    const double* __restrict__ xs = in + S.xs_off;
+    const double* __restrict__ U = ws + (want_var ? pps[S.prob].u_off : 0);
+    if (want_var) vfe_load_wt(Wt, ws + P.w_off, ld, nb16, w, lane);
+    if (want_mean && tid < np) al[tid] = tid < m ? res[P.alpha_off + tid] : 0.0;
+    __syncthreads();
+    for (int t0 = 0; t0 < S.cnt; t0 += VT) {
+        const bool valid = t0 + lane < S.cnt;
+        const long j = (long)S.row0 + t0 + lane;
+        // ---- 1. K* into LDS, the mean off it
+        {
+            double xj[BATCH_MAXD];
+#pragma unroll
+            for (int p = 0; p < BATCH_MAXD; ++p)
+                xj[p] = (p < d && valid) ? (nscale == 0 ? 1.0 : P.scale[nscale == 1 ? 0 : p]) * xs[(long)p * ns + j] : 0.0;
+            for (int rr = 0; rr < np / 8; ++rr) {
+                const int i = w + 8 * rr;  // wave-uniform
+                double v = 0.0;
+                if (i < m && valid) {
+                    double t[BATCH_MAXD];
+                    batch_diff(z, m, d, i, xj, t);
+                    v = vfe_kval(P, t);
+                }
+                KB[i * KBS + lane] = v;
+            }
+        }
+        __syncthreads();
+        if (want_mean && w == 0 && valid) {
+            double s = 0.0;
+            for (int i = 0; i < m; ++i) s = fma(KB[i * KBS + lane], al[i], s);
+            res[S.mean_off + j] = S.pm_off >= 0 ? in[S.pm_off + j] + s : s;
+        }
+        if (!want_var) {
+            __syncthreads();  // the next tile's K* waits for the mean's reads
+            continue;
+        }
+        // ---- 2. B* = W K* over K*, its column norms
+        d4_t acc[4];
+        double sq = vfe_tri_mm(acc, KB, nb16, w, lane, [&](int bi, int bk, int k) { return Wt[(bi * (bi + 1) / 2 + bk) * 256 + k * 16 + r]; });
+        sq += __shfl_xor(sq, 16, 64);
+        sq += __shfl_xor(sq, 32, 64);
+        __syncthreads();
+        vfe_tri_store(acc, KB, nb16, w, lane);
+        if (g == 0) nrm[0][w >> 2][16 * (w & 3) + r] = sq;
+        __syncthreads();
+        // ---- 3. C* = E B*: the column norms alone
+        sq = vfe_tri_mm(acc, KB, nb16, w, lane, [&](int bi, int bk, int k) { return U[(long)(16 * bk + k) * ld + 16 * bi + r]; });
+        sq += __shfl_xor(sq, 16, 64);
+        sq += __shfl_xor(sq, 32, 64);
+        if (g == 0) nrm[1][w >> 2][16 * (w & 3) + r] = sq;
+        __syncthreads();
+        // ---- 4. the variance
+        if (w == 0 && valid) res[S.var_off + j] = (P.variance - (nrm[0][0][lane] + nrm[0][1][lane])) + (nrm[1][0][lane] + nrm[1][1][lane]);
     }
 }
 
@@ -2425,10 +2559,10 @@ struct PredictArgs : BatchArgs {
     bool want_dvar() const { return grad && (what & 2) && dvar_out; }
 };
 
-// nxs and xs of a call over test points (arguments 10 and 11 in every family)
-int32_t check_test_head(const PredictArgs& a) {
-    if (a.nxs != 1 && a.nxs != a.nb) return set_arg_err(10, "nxs must be 1 (one xs shared by every problem) or nb");
-    if (!a.xs) return set_arg_err(11, "test points array is NULL");
+// nxs and xs of a call over test points (arguments 10 and 11 in every exact family, `arg` and arg + 1 in gp_vfe_predict_batch)
+template <class A> int32_t check_test_head(const A& a, int arg = 10) {
+    if (a.nxs != 1 && a.nxs != a.nb) return set_arg_err(arg, "nxs must be 1 (one xs shared by every problem) or nb");
+    if (!a.xs) return set_arg_err(arg + 1, "test points array is NULL");
     return 0;
 }
 // An array of per-problem pointers of such a call: a problem with test points needs its entry where the call asks for the array (wanted) and brought it.
@@ -2439,13 +2573,13 @@ struct PointerArray {
     const char* msg;
 };
 // every problem's test points, Σy* (gp_joint_batch: argument 13, else NULL) and entries of `arrays`, in that order
-int32_t check_test_points(const PredictArgs& a, const gp_noise* noise_xs, std::initializer_list<PointerArray> arrays) {
+template <class A> int32_t check_test_points(const A& a, const gp_noise* noise_xs, std::initializer_list<PointerArray> arrays, int arg = 11) {
     for (int b = 0; b < a.nb; ++b) {
         const gp_points& xs = a.xsb(b);
-        if (xs.n < 0) return set_arg_err(11, "xs: n must be >= 0");
+        if (xs.n < 0) return set_arg_err(arg, "xs: n must be >= 0");
         if (xs.n == 0) continue;  // no test points: nothing of this problem's xs or outputs is touched
-        RC(check_points(&xs, 11));
-        if (xs.d != a.xb(b).d) return set_arg_err(11, "xs has a different D than the training inputs");
+        RC(check_points(&xs, arg));
+        if (xs.d != a.xb(b).d) return set_arg_err(arg, "xs has a different D than the training inputs");
         if (noise_xs) RC(check_noise(&noise_xs[b], 13, true));
         for (const PointerArray& p : arrays)
             if (p.wanted && p.arr && !p.arr[b]) return set_arg_err(p.arg, p.msg);
@@ -3288,6 +3422,18 @@ struct VfeGradOut {
     double* const* dz;
     void* const* dx;
 };
+// gp_vfe_predict_batch: the test side as PredictArgs carries it for gp_predict_batch (what: 1 mean | 2 var); objective_out may be NULL
+struct VfePredictArgs : VfeArgs {
+    int32_t nxs;
+    const gp_points* xs;
+    const void* const* pm;
+    int32_t what;
+    void* const* mean_out;
+    void* const* var_out;
+    const gp_points& xsb(int b) const { return xs[nxs == 1 ? 0 : b]; }
+    const void* pmb(int b) const { return pm ? pm[b] : nullptr; }
+    void* out_b(void* const* arr, int side, int b) const { return (what & side) ? arr[b] : nullptr; }
+};
 
 // the pseudo-inputs of one problem, dimension-major [d][m], scaled as the sparse path scales its inputs on the host (one product per entry)
 void pack_scaled_points(const gp_kernel& k, const gp_points& z, double* out) {
@@ -3298,7 +3444,8 @@ void pack_scaled_points(const gp_kernel& k, const gp_points& z, double* out) {
     }
 }
 
-int32_t check_vfe_args(VfeArgs& a) {
+// obj_arg / info_arg: where the call has objective_out and info_out (obj_arg 0: the objective may be left out)
+int32_t check_vfe_args(VfeArgs& a, int obj_arg = 14, int info_arg = 15) {
     if (!a.k) return set_arg_err(3, "kernel array is NULL");
     if (a.nx != 1 && a.nx != a.nb) return set_arg_err(4, "nx must be 1 (one x shared by every problem) or nb");
     if (!a.x) return set_arg_err(5, "points array is NULL");
@@ -3311,8 +3458,8 @@ int32_t check_vfe_args(VfeArgs& a) {
     for (int b = 0; b < a.ny; ++b)
         if (!a.y[b]) return set_arg_err(12, "a y pointer is NULL");
     if (!a.approx) return set_arg_err(13, "approx array is NULL");
-    if (!a.logpdf_out) return set_arg_err(14, "objective_out is NULL");
-    if (!a.info_out) return set_arg_err(15, "info_out is NULL");
+    if (obj_arg && !a.logpdf_out) return set_arg_err(obj_arg, "objective_out is NULL");
+    if (!a.info_out) return set_arg_err(info_arg, "info_out is NULL");
     a.dtype = a.k[0].dtype;
     for (int b = 0; b < a.nb; ++b) {
         const gp_points &x = a.xb(b), &z = a.zb(b);
@@ -3379,6 +3526,17 @@ void vfe_wave_fill(const VfeArgs& a, const int* idx, int nw, const std::vector<V
     }
 }
 
+// the test side of a prediction wave behind that: the test points (a shared set once) and prior mean of every problem that has a first segment, at its offsets
+void vfe_test_fill(const VfePredictArgs& a, const int* idx, int nw, const std::vector<VfePSeg>& ps, const std::vector<long>& first_seg, double* hin) {
+    SharedOnce xso{a.nxs == 1};
+    for (int t = 0; t < nw; ++t) {
+        if (first_seg[t] < 0) continue;
+        const VfePSeg& s = ps[(size_t)first_seg[t]];
+        if (xso.claim()) pack_points(a.xsb(idx[t]), hin + s.xs_off);
+        if (s.pm_off >= 0) std::memcpy(hin + s.pm_off, a.pmb(idx[t]), sizeof(double) * s.ns);
+    }
+}
+
 // NaN in every gradient entry of problem b (the call's dtype: a routed fp32 problem has float arrays)
 void vfe_grad_fill_nan(const VfeArgs& a, const VfeGradOut& go, int b) {
     const gp_points &x = a.xb(b), &z = a.zb(b);
@@ -3390,21 +3548,35 @@ void vfe_grad_fill_nan(const VfeArgs& a, const VfeGradOut& go, int b) {
     if (go.dx) fill_nan(go.dx[b], a.dtype, (long)x.n * x.d);
 }
 
+// test points per workgroup of the predict kernel (the segments are the host's: the kernel takes their bounds from the table); the environment variable
+// GPMI_VFE_PREDICT_BATCH_SEG, read per call, overrides the header's value for measurements (whole tiles)
+long vfe_pseg() { return std::max<long>(VT, env_capped(getenv("GPMI_VFE_PREDICT_BATCH_SEG"), VFE_PSEG, 1 << 20) / VT * VT); }
+
 // three launches: the problems idx[0..nw) of the call, all taken by the kernels.  Caller holds the ctx lock.  With go (gp_vfe_grad_batch) three more behind them:
 // α of every problem goes to the result buffer, whether the caller asked for it or not, and the gradient's tables and results are laid out beside the fit's.
-int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw, const VfeGradOut* go = nullptr) {
+// With pa (gp_vfe_predict_batch: a itself) the two prediction launches instead: α likewise, the test points and prior means behind the fit's input (a shared
+// set once), the strip L_D⁻ᵀ of every problem whose variance is asked for behind its slices, mean and variance behind the fit's results.
+int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw, const VfeGradOut* go = nullptr, const VfePredictArgs* pa = nullptr) {
     WaveLayout L;
     L.roff = 2L * nw;
     Table<VfeProb> vp;
     Table<VfeSeg> sg;
     Table<VfeGrad> vg;
+    Table<VfePred> vq;
+    Table<VfePSeg> ps;
+    std::vector<long> first_seg((size_t)nw, -1);  // a problem's first entry of ps: its offsets
+    const long pseg = vfe_pseg();
     vp.v.assign((size_t)nw, VfeProb{});
     vp.place(L);
+    if (pa) {
+        vq.v.assign((size_t)nw, VfePred{-1});
+        vq.place(L);
+    }
     if (go) {
         vg.v.assign((size_t)nw, VfeGrad{});
         vg.place(L);
     }
-    SharedOnce xo{a.nx == 1}, yo{a.ny == 1};
+    SharedOnce xo{a.nx == 1}, yo{a.ny == 1}, xso{pa && pa->nxs == 1};
     for (int t = 0; t < nw; ++t) {
         const int b = idx[t];
         const gp_points &x = a.xb(b), &z = a.zb(b);
@@ -3423,7 +3595,7 @@ int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw, const 
         p.w_off = take(L.ws, (long)p.np * p.ld);
         p.d_off = take(L.ws, batch_slice(z.n));
         p.part_off = take(L.ws, p.nseg * vfe_part(p.np));
-        p.alpha_off = (a.ab(b) || go) ? take(L.roff, z.n) : -1;
+        p.alpha_off = (a.ab(b) || go || pa) ? take(L.roff, z.n) : -1;
         p.meps_off = a.eb(b) ? take(L.roff, z.n) : -1;
         for (int s = 0; s < p.nseg; ++s) sg.v.push_back(VfeSeg{t, s});
         if (go) {
@@ -3437,14 +3609,28 @@ int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw, const 
             q.dy_off = take(L.roff, x.n);
             q.dx_off = go->dx ? take(L.roff, (long)x.d * x.n) : -1;
         }
+        if (pa && pa->xsb(b).n > 0) {
+            const gp_points& xs = pa->xsb(b);
+            const long ns = xs.n;
+            if (pa->what & 2) vq.v[t].u_off = take(L.ws, (long)p.np * p.ld);
+            const long xs_off = xso.place(L.off, (long)xs.d * ns), pm_off = pa->pmb(b) ? take(L.off, ns) : -1;
+            const long mean_off = (pa->what & 1) ? take(L.roff, ns) : -1, var_off = (pa->what & 2) ? take(L.roff, ns) : -1;
+            first_seg[t] = (long)ps.v.size();
+            for (long r0 = 0; r0 < ns; r0 += pseg)
+                ps.v.push_back(VfePSeg{xs_off, pm_off, mean_off, var_off, t, (int)ns, (int)r0, (int)std::min<long>(pseg, ns - r0)});
+        }
     }
     sg.place(L);
+    ps.place(L);
     WaveMem m(c);
     RC(m.alloc(L.off, L.ws, L.roff));
     vp.fill(m);
     sg.fill(m);
     vg.fill(m);
+    vq.fill(m);
+    ps.fill(m);
     vfe_wave_fill(a, idx, nw, vp.v, m.hin);
+    if (pa) vfe_test_fill(*pa, idx, nw, ps.v, first_seg, m.hin);
     RC(run_drained(c, [&]() -> int32_t {
         RC(m.upload());
         RC(launch(m, vfe_prelude_kernel, nw, NT, nw, vp.dev(m)));
@@ -3455,15 +3641,30 @@ int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw, const 
             RC(launch(m, vfe_gstream_kernel, sg.v.size(), NT, nw, vp.dev(m), vg.dev(m), sg.dev(m)));
             RC(launch(m, vfe_gfinish_kernel, nw, NT, nw, vp.dev(m), vg.dev(m)));
         }
+        if (pa && !ps.v.empty()) {
+            if (pa->what & 2) RC(launch(m, vfe_pprep_kernel, nw, NT, nw, vp.dev(m), vq.dev(m)));
+            for (size_t s0 = 0; s0 < ps.v.size(); s0 += VFE_PRED_LAUNCH_SEGS)
+                RC(launch(m, vfe_predict_kernel, std::min<size_t>(VFE_PRED_LAUNCH_SEGS, ps.v.size() - s0), NT, nw, vp.dev(m), vq.dev(m), ps.dev(m, s0)));
+        }
         return m.download_and_sync();
     }));
-    (go ? c->vfe_grad_batch_problems : c->vfe_batch_problems) += nw;
+    (go ? c->vfe_grad_batch_problems : pa ? c->vfe_predict_batch_problems : c->vfe_batch_problems) += nw;
     for (int t = 0; t < nw; ++t) {
         const int b = idx[t];
         const VfeProb& p = vp.v[t];
         put_result(a, b, m.hout[t], (int32_t)m.hout[nw + t]);
         if (p.alpha_off >= 0 && a.ab(b)) std::memcpy(a.ab(b), m.hout + p.alpha_off, sizeof(double) * p.m);
         if (p.meps_off >= 0) std::memcpy(a.eb(b), m.hout + p.meps_off, sizeof(double) * p.m);
+        if (first_seg[t] >= 0) {  // failure is data: the prediction kernels skipped the problem
+            const VfePSeg& s = ps.v[first_seg[t]];
+            const bool failed = m.hout[nw + t] != 0.0;
+            for (int side = 1; side <= 2; ++side) {
+                void* out = pa->out_b(side == 1 ? pa->mean_out : pa->var_out, side, b);
+                if (!out) continue;
+                if (failed) fill_nan(out, 0, s.ns);
+                else std::memcpy(out, m.hout + (side == 1 ? s.mean_off : s.var_off), sizeof(double) * s.ns);
+            }
+        }
         if (!go) continue;
         if (m.hout[nw + t] != 0.0) {  // failure is data: the gradient kernels skipped the problem
             vfe_grad_fill_nan(a, *go, b);
@@ -3548,6 +3749,60 @@ int32_t vfe_grad_batch_impl(gp_ctx* c, VfeArgs& a, const VfeGradOut& go) {
         if (h) (void)gp_vfe_free(h);
         if (rc == 0 && !diag) put(go.dnoise[b], a.dtype, 0, dns);
         RC(routed_done(a, b, rc, [&] { vfe_grad_fill_nan(a, go, b); }));
+    }
+    return 0;
+}
+
+// doubles problem b alone adds to the workspace (the strip L_D⁻ᵀ) and to the page-locked staging of a prediction wave (its test points where they are not
+// shared, prior mean, segment table, α, mean and variance)
+long vfe_predict_ws(const VfePredictArgs& a, int b) {
+    const long np = batch_np(a.zb(b).n);
+    return ((a.what & 2) && a.xsb(b).n > 0) ? np * batch_ld(np) : 0;
+}
+long vfe_predict_io(const VfePredictArgs& a, int b) {
+    const gp_points& xs = a.xsb(b);
+    const long nseg = (xs.n + vfe_pseg() - 1) / vfe_pseg();
+    return a.zb(b).n + (a.nxs == 1 ? 0 : (long)xs.d * xs.n) + (a.pmb(b) ? xs.n : 0) + nseg * (long)(sizeof(VfePSeg) / 8) + ((a.what & 1) + (a.what >> 1)) * xs.n;
+}
+
+// the test side of gp_vfe_predict_batch that needs neither the handle nor a device (arguments 14 … 19)
+int32_t check_vfe_test_head(const VfePredictArgs& a) {
+    RC(check_test_head(a, 14));
+    if (a.what <= 0 || a.what > 3) return set_arg_err(17, "what must be a combination of 1|2");
+    if ((a.what & 1) && !a.mean_out) return set_arg_err(18, "mean_out is NULL");
+    if ((a.what & 2) && !a.var_out) return set_arg_err(19, "var_out is NULL");
+    return 0;
+}
+
+// gp_vfe_predict_batch: the body of vfe_batch_impl with the predictions behind the fit — two more launches per wave, gp_vfe_predict behind gp_vfe_fit for the rest
+int32_t vfe_predict_batch_impl(gp_ctx* c, VfePredictArgs& a) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    if (a.nb < 0) return set_arg_err(2, "nb must be >= 0");
+    if (a.nb == 0) return 0;
+    RC(check_vfe_args(a, 0, 21));
+    RC(check_test_points(a, nullptr, {{a.mean_out, (a.what & 1) != 0, 18, "a mean_out pointer is NULL"}, {a.var_out, (a.what & 2) != 0, 19, "a var_out pointer is NULL"}}, 15));
+    const long max_n = env_capped(getenv("GPMI_VFE_PREDICT_BATCH_MAX_N"), GPMI355_VFE_PREDICT_BATCH_MAX_N, VFE_KERNEL_MAX_N);
+    std::vector<int> mine, routed;
+    for (int b = 0; b < a.nb; ++b) (vfe_batch_takes(a, b, max_n) ? mine : routed).push_back(b);
+    RC(for_each_wave(c, mine,
+                     [&](int b) {  // the staging bound covers what goes in and what comes back
+                         return WaveCost{sizeof(double) * (size_t)(vfe_ws(a, b) + vfe_predict_ws(a, b)), 0, sizeof(double) * (size_t)(vfe_in(a, b) + vfe_predict_io(a, b))};
+                     },
+                     [&](const int* idx, int nw) { return run_vfe_wave(c, a, idx, nw, nullptr, &a); }));
+    // everything else: gp_vfe_fit + gp_vfe_predict + gp_vfe_free, one problem at a time, after the lock is released (as batch_impl does)
+    gd.lk.unlock();
+    for (int b : routed) {
+        const gp_points& xs = a.xsb(b);
+        gp_vfe* h = nullptr;
+        int32_t rc = gp_vfe_fit(c, &a.k[b], &a.xb(b), &a.zb(b), &a.noise[b], a.jitter[b], a.mb(b), a.yb(b), a.approx[b], xs.n > 0 ? &h : nullptr, logpdf_slot(a, b));
+        if (rc == 0 && h) rc = gp_vfe_predict(h, &xs, a.pmb(b), a.what, a.out_b(a.mean_out, 1, b), a.out_b(a.var_out, 2, b), nullptr);
+        if (h) (void)gp_vfe_free(h);
+        RC(routed_done(a, b, rc, [&] {
+            if (xs.n <= 0) return;
+            fill_nan(a.out_b(a.mean_out, 1, b), a.dtype, xs.n);
+            fill_nan(a.out_b(a.var_out, 2, b), a.dtype, xs.n);
+        }));
     }
     return 0;
 }
@@ -3721,5 +3976,16 @@ int32_t gp_vfe_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t n
                           void* const* dnoise_out, void* const* dy_out, double* const* dz_out_or_null, void* const* dx_out_or_null) {
     VfeArgs a{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, objective_out, info_out), nz, z, jitter, approx, nullptr};
     return vfe_grad_batch_impl(ctx, a, VfeGradOut{dvariance_out, dscale_out_or_null, dnoise_out, dy_out, dz_out_or_null, dx_out_or_null});
+}
+
+// The checks of the test side stand in front of the body: they report their arguments before the handle is looked at.
+int32_t gp_vfe_predict_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, int32_t nz, const gp_points* z,
+                             const gp_noise* noise, const double* jitter, const void* const* mean_or_null, int32_t ny, const void* const* y,
+                             const int32_t* approx, int32_t nxs, const gp_points* xs, const void* const* prior_mean_xs_or_null, int32_t what,
+                             void* const* mean_out, void* const* var_out, void* objective_out_or_null, int32_t* info_out) {
+    VfePredictArgs a{{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, objective_out_or_null, info_out), nz, z, jitter, approx, nullptr},
+                     nxs, xs, prior_mean_xs_or_null, what, mean_out, var_out};
+    if (nb > 0) RC(check_vfe_test_head(a));
+    return vfe_predict_batch_impl(ctx, a);
 }
 }

@@ -311,6 +311,7 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
  *   "batch_loo_kernel_problems", "batch_loo_grad_kernel_problems"   read-only: the same for the kernels of gp_loo_batch / _sum and of gp_loo_grad_batch / _sum
  *   "vfe_batch_kernel_problems"       read-only: the same for the kernels of gp_vfe_batch
  *   "vfe_grad_batch_kernel_problems"  read-only: the same for the kernels of gp_vfe_grad_batch
+ *   "vfe_predict_batch_kernel_problems"  read-only: the same for the kernels of gp_vfe_predict_batch
  *   "cols_kernel_calls", "cols_kernel_splits"   read-only: kmul launches gp_posterior_predict_cols has served on this ctx since it was created, and the workgroups
  *                    along the training range of the last of them (1 = unsplit, 0 = none yet): which path ran, for tests and measurements */
 /* The defaults above, machine-readable (single-device parameters; gp_ctx_get_param reads the same names): the test-suite asserts before
@@ -1020,6 +1021,56 @@ int32_t gp_vfe_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t n
                           const gp_noise* noise, const double* jitter, const void* const* mean_or_null, int32_t ny, const void* const* y,
                           const int32_t* approx, void* objective_out, int32_t* info_out, double* dvariance_out, double* const* dscale_out_or_null,
                           void* const* dnoise_out, void* const* dy_out, double* const* dz_out_or_null, void* const* dx_out_or_null);
+
+/* gp_vfe_predict_batch: the predictions of nb independent VFE / DTC problems in one call — what the callers of gp_vfe_batch want of every problem next (a loop
+ * of gp_vfe_fit + gp_vfe_predict + gp_vfe_free otherwise).  Inputs and sharing rules (nx, nz, ny ∈ {1, nb}) up to `approx` exactly as gp_vfe_batch; the test
+ * side as gp_predict_batch has it: xs: nxs ∈ {1, nb} entries (1 = one set of test points shared by every problem, uploaded once; ns_b = 0 is legal and
+ * touches nothing of that problem), prior_mean_xs_or_null: NULL, or nb pointers each of which may be NULL, what ⊆ {bit 0 mean, bit 1 var} (0 or any other
+ * bit is an argument error), mean_out / var_out: nb pointers of ns_b entries — the array of a side asked for must not be NULL, the other is not read.  Per
+ * problem the semantics are those of gp_vfe_fit followed by gp_vfe_predict (src/sparse_approximations.jl:183-217):
+ *   mean_j = m(x*_j) + Σ_i k(x*_j, z_i) α_i,   var_j = k(x*_j, x*_j) − ‖L_z⁻¹ k_z*j‖² + ‖L_D⁻¹ L_z⁻¹ k_z*j‖²   (not clamped; the same for VFE and DTC).
+ * objective_out_or_null [nb] and info_out [nb] as gp_vfe_batch.  Failure is data: a failed problem reports info_out[b] and gets NaN in its objective, mean
+ * and var; the others are not affected.  The return value reports argument errors only (nb = 0 returns 0); those of the test side (nxs, xs, what, a NULL
+ * array of a side asked for) are reported before the handle is looked at.
+ * Eligibility as gp_vfe_batch with n_b <= GPMI355_VFE_PREDICT_BATCH_MAX_N; the fit's three launches run unchanged (the objective is bit-equal to
+ * gp_vfe_batch's, α always goes to the result buffer), two more follow per wave (csrc/batch.hip):
+ *   vfe_pprep_kernel    one workgroup per problem: E = L_D⁻¹ as the strip L_D⁻ᵀ by substitution on the resident factor (the first step of vfe_gmm_kernel);
+ *   vfe_predict_kernel  one workgroup per (problem, segment of GPMI355_VFE_PREDICT_BATCH_SEG consecutive test points): W = L_z⁻¹ stays in LDS in the stream
+ *                       kernel's blocked layout; per tile of 64 test points K* = K(z, x*_tile) is evaluated into LDS (K_z* never reaches HBM), the mean is
+ *                       taken off the tile, B* = W K* by v_mfma_f64_16x16x4_f64 over the non-zero k blocks goes back over the tile, C* = E B* by the same
+ *                       MFMA with E's operand fragments from global memory (at most 128 KB per problem, shared by its workgroups: L2) is never stored;
+ *                       ‖B*_j‖² and ‖C*_j‖² are column sums of squares out of the accumulators.
+ * The two norms and not one symmetric Q = Wᵀ(I − Λ_ε⁻¹)W resident in LDS with var = k** − k*ᵀQk*: W and E together do not fit beside a tile, which makes Q
+ * tempting, but in NumPy fp64 against the oracle (SE / Matern, M = 65 and 128, n = 2 048 and 4 133, jitter 1e-4 … 1e-8) the explicit Q loses two to three
+ * digits of the variance (up to 1.8e-10 absolute against 3.2e-13), and the two norms are what gp_vfe_predict and the oracle compute.
+ * No floating-point atomics, no waits between workgroups, and the arithmetic of a test point touches no other column: its mean and variance are the same
+ * bits alone, among any other test points, in any batch and on repetition.  Every other problem is answered inside the call by gp_vfe_fit + gp_vfe_predict +
+ * gp_vfe_free; which path serves a problem depends on that problem alone.  The read-only ctx parameter "vfe_predict_batch_kernel_problems" counts the
+ * problems the kernels served.
+ * Against the oracle's vfe_posterior(...).mean / .var over the table of tests/test_gpu_vfe_predict_batch.py (M = 1 … 128, ns = 0 … 2·SEG + 37, all four kernel
+ * kinds, test points on training and pseudo-inputs included) the largest deviations are 1.9e-14 (mean) and 5.4e-15 (var).  The compiler's report for gfx950:
+ * vfe_pprep_kernel 202 VGPRs, 0 AGPRs, 33 792 B of LDS, no scratch; vfe_predict_kernel 150 VGPRs, 0 AGPRs, 143 360 B of LDS, no scratch.
+ * GPMI355_VFE_PREDICT_BATCH_SEG: the segments are the host's (the kernel takes their bounds from a table), so 128 / 512 / 2 048 were compared in one process
+ * with the settings alternating (tools/vfe_predict_batch_profile.py --segs, profiles/r37/vfe_predict_batch_seg.json: M = 128, n = 4 096, per-problem test
+ * points).  With 64 test points a problem is one segment under all three (equal to 0.1 %).  With 4 096: nb = 8 1.39 / 1.56 / 2.27 ms, nb = 64 3.04 / 2.87 /
+ * 3.28 ms, nb = 512 21.2 / 20.1 / 19.8 ms — few problems want short segments (more workgroups), many want long ones (W loaded less often); 512 is best at
+ * nb = 64 and within 13 % and 2 % of the best at the ends.  (GPMI_VFE_PREDICT_BATCH_SEG, read per call, overrides it for measurements.)
+ * GPMI355_VFE_PREDICT_BATCH_MAX_N: by the rule of the other batch thresholds — the largest n of the measured sweep (tools/vfe_predict_batch_profile.py
+ * --min-s 0.1, profiles/r37/vfe_predict_batch_profile.json: one process, SE, D = 3, what = 3, M = 16, 64, 128 × n = 1 024 … 262 144 × nb = 1, 8, 64, 512 × 64 and
+ * 1 024 test points per problem, shared and per-problem (x, y, xs): 240 cells, none skipped, each checked against the loop's values) at which one batch call
+ * beat the loop of gp_vfe_fit + gp_vfe_predict + gp_vfe_free in every cell with nb >= 8.  It beat it in all 180 of them, so the macro is the largest n swept.
+ * The closest cells are those with per-problem data at M = 128, n = 262 144, where packing and uploading the inputs is most of the call (1 024 test points):
+ * nb = 8 9.49 against 14.7 ms, nb = 64 62.1 against 117 ms, nb = 512 487 against 950 ms (shared: 5.13 against 13.4, 24.7 against 108 and 183 against 995 ms);
+ * at n = 1 024 the call is up to 379 times faster (M = 16, nb = 512, shared, 64 test points: 0.83 against 316 ms).  A single problem (nb = 1) loses at M = 128
+ * everywhere (0.86 against 0.62 ms at n = 1 024, 3.0 against 1.7 ms at n = 262 144: one workgroup runs the M×M side) and at M = 64 between n = 4 096 and
+ * 65 536 by at most 14 %; the rule does not count it.  (The environment variable GPMI_VFE_PREDICT_BATCH_MAX_N, read per call, overrides the macro for
+ * measurements.) */
+#define GPMI355_VFE_PREDICT_BATCH_SEG 512
+#define GPMI355_VFE_PREDICT_BATCH_MAX_N 262144
+int32_t gp_vfe_predict_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, int32_t nz, const gp_points* z,
+                             const gp_noise* noise, const double* jitter, const void* const* mean_or_null, int32_t ny, const void* const* y,
+                             const int32_t* approx, int32_t nxs, const gp_points* xs, const void* const* prior_mean_xs_or_null, int32_t what,
+                             void* const* mean_out, void* const* var_out, void* objective_out_or_null, int32_t* info_out);
 
 /* ---- device-level building blocks ------------------------------------------------------------ */
 /* The operations the in-library multi-device driver composes (csrc/multi.hip calls the same engine functions), exposed on DEVICE
