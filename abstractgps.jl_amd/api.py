@@ -2486,6 +2486,60 @@ def approx_mean_and_var_batch(approxs, fxs, ys, xs, *, what: int = 3, return_obj
     return (means, vars_, obj) if return_objective else (means, vars_)
 
 
+def approx_mean_and_var_grad_batch(approxs, fxs, ys, xs, *, what: int = 3, mean_grads=None, return_objective: bool = False, on_error: str = "raise"):
+    """mean_and_var_grad(posterior(approxs[b], fxs[b], ys[b]), xs[b]) of many independent sparse GPs in one library call per (ctx, dtype) group
+    (gp_vfe_predict_grad_batch): the predictions of approx_mean_and_var_batch AND their gradients w.r.t. the test inputs — what a gradient-based acquisition
+    step over many sparse surrogates evaluates.  approxs, fxs, ys, xs, what, on_error as in approx_mean_and_var_batch.  Returns the list of
+    (mean, var, dmean, dvar) in the caller's order, None for whatever was not asked for; the gradients have the shape of each xs_b's array, as
+    ApproxPosteriorGP.mean_and_var_grad shapes them (with return_objective: that list and the array of objectives).  mean_grads as in mean_and_var_grad_batch."""
+    if on_error not in ("raise", "nan"):
+        raise ValueError('on_error must be "raise" or "nan"')
+    if what not in (1, 2, 3):
+        raise ValueError("what must be 1 (mean), 2 (var) or 3 (both)")
+    approxs = list(approxs)
+    n = len(approxs)
+    xs = [xs] if isinstance(xs, (np.ndarray, ColVecs, RowVecs)) else list(xs)
+    if len(xs) == 1 and n > 1:
+        xs = xs * n
+    if len(xs) != n:
+        raise ValueError(f"DimensionMismatch: {n} problems but {len(xs)} sets of test points")
+    if not approxs:
+        return ([], np.empty(0)) if return_objective else []
+    mean_grads = [None] * n if mean_grads is None else list(mean_grads)
+    if len(mean_grads) != n:
+        raise ValueError(f"DimensionMismatch: {n} problems but {len(mean_grads)} entries of mean_grads")
+    quads, parts = [None] * n, []
+    for g in _vfe_batch_groups(approxs, fxs, ys):
+        for i, fx in zip(g.index, g.fxs):
+            if callable(fx.f.mean_fn) and (what & 1) and mean_grads[i] is None:
+                raise TypeError(f"problem {i}: the prior mean is a CustomMean: pass mean_grads[{i}] = callable returning its (ns × d) derivative at xs")
+        call = _vfe_batch_marshal(g, False, False)
+        m, nb = call.keep, call.nb
+        tss = [xs[i] for i in g.index]
+        nts = 1 if all(v is tss[0] for v in tss) else nb
+        xpts = (gp_points * nts)(*[m.points(v) for v in tss[:nts]])
+        pxs = [xpts[0 if nts == 1 else b] for b in range(nb)]
+        pms = [_mean_vector(fx.f.mean_fn, v, g.dtype) for fx, v in zip(g.fxs, tss)]  # m(x*) on the host; None = ZeroMean
+        pms = [None if v is None else m.arr(v) for v in pms]
+        pmarr = None if all(v is None for v in pms) else (C.c_void_p * nb)(*[None if v is None else v.ctypes.data for v in pms])
+        outs = [[np.empty(int(px.n), dtype=g.dtype) for px in pxs] if what & side else None for side in (1, 2)]
+        outs += [[_dx_buffer(px, g.dtype) for px in pxs] if what & side else None for side in (1, 2)]
+        oarrs = [None if o is None else (C.c_void_p * nb)(*[a.ctypes.data for a in o]) for o in outs]
+        ctx = g.ctx or default_context()
+        check(ctx.lib.gp_vfe_predict_grad_batch(ctx.handle, *call.args[:12], nts, xpts, pmarr, what, *oarrs, *call.args[12:14]))
+        parts.append((g.index, call.out, call.info, None))
+        for j, i in enumerate(g.index):
+            mean, var, dmean, dvar = [None if o is None else o[j] for o in outs]
+            dmean = None if dmean is None else _dx_shaped(dmean, pxs[j], tss[j])
+            dvar = None if dvar is None else _dx_shaped(dvar, pxs[j], tss[j])
+            if dmean is not None and callable(g.fxs[j].f.mean_fn):
+                gm = np.asarray(mean_grads[i](tss[j]), dtype=g.dtype).reshape(pxs[j].n, pxs[j].d)  # (ns × d)
+                dmean = dmean + (gm[:, 0] if pxs[j].layout == 0 else (gm.T if isinstance(_as_input(tss[j]), ColVecs) else gm))
+            quads[i] = (mean, var, dmean, dvar)
+    obj = _batch_merge(n, parts, False, on_error)
+    return (quads, obj) if return_objective else quads
+
+
 # --------------------------------------------------------------------------------------------
 # VFE / DTC for a matrix of observations: gp_vfe_fit_cols / _update_cols / _append_cols / _predict_cols / _get_cols / _get_by_cols / _grad_cols
 # --------------------------------------------------------------------------------------------

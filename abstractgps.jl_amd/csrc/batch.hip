@@ -1396,7 +1396,9 @@ __device__ __forceinline__ void vfe_syrk_tile(d4_t (&g4)[2][2], const double* KB
 }
 
 // W = L_z⁻¹ out of the strip V = Wᵀ into LDS as the 16×16 blocks of its lower triangle, counted row by row, each k-major (Wt[blk][k][row]); the eight waves
-// take the blocks round-robin, and the caller's barrier closes the load
+// take the blocks round-robin, and the caller's barrier closes the load.  KS: doubles between the k rows of a block — 16, or 17 where the upper blocks are also
+// read transposed out of the lower ones (vfe_predict_kernel<true>; the odd stride is meant to spread the transposed read over the banks, as GTS does in vfe_gstream_kernel — not measured)
+template <int KS = 16>
 __device__ __forceinline__ void vfe_load_wt(double* Wt, const double* __restrict__ V, long ld, int nb16, int w, int lane) {
     int cnt = 0;
     for (int bi = 0; bi < nb16; ++bi)
@@ -1405,7 +1407,7 @@ __device__ __forceinline__ void vfe_load_wt(double* Wt, const double* __restrict
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int e = lane + 64 * q;  // e = 16 k + row
-                Wt[cnt * 256 + e] = V[(long)(16 * bk + (e >> 4)) * ld + 16 * bi + (e & 15)];
+                Wt[cnt * (16 * KS) + (e >> 4) * KS + (e & 15)] = V[(long)(16 * bk + (e >> 4)) * ld + 16 * bi + (e & 15)];
             }
         }
 }
@@ -1428,6 +1430,20 @@ __device__ __forceinline__ double vfe_tri_mm(d4_t (&acc)[4], const double* X, in
         for (int e = 0; e < 4; ++e) sq = fma(acc[q][e], acc[q][e], sq);
     }
     return sq;
+}
+// The transposed counterpart: acc[q] = (T X)[row block (w >> 2) + 2 q, column block w & 3] for an UPPER-triangular T, so the k loop of row block bi runs over
+// the blocks bi … nb16 − 1.  frag(bi, bk, k) is T[16 bi + r][16 bk + k] as above; same wave mapping, same order within a block.
+template <class Frag>
+__device__ __forceinline__ void vfe_triu_mm(d4_t (&acc)[4], const double* X, int nb16, int w, int lane, Frag&& frag) {
+    const int r = lane & 15, g = lane >> 4, cb = w & 3;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        acc[q] = 0.0;
+        const int bi = (w >> 2) + 2 * q;
+        for (int bk = bi; bk < nb16; ++bk)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) acc[q] = Tr<double>::mfma(frag(bi, bk, 4 * s + g), X[(16 * bk + 4 * s + g) * KBS + 16 * cb + r], acc[q]);
+    }
 }
 // the accumulators of vfe_tri_mm back over the tile
 __device__ __forceinline__ void vfe_tri_store(const d4_t (&acc)[4], double* X, int nb16, int w, int lane) {
@@ -2087,10 +2103,11 @@ static_assert(VFE_PSEG % VT == 0, "a segment is whole tiles");
 struct VfePred {
     long u_off;
 };
-// One segment of test points: xs_off ([d][ns], raw) and pm_off (m(x*), −1: none) into the packed input, mean_off / var_off (arrays of ns; −1: not wanted) into
-// the result buffer; the points [row0, row0 + cnt) of the ns of problem `prob`.
+// One segment of test points: xs_off ([d][ns], raw) and pm_off (m(x*), −1: none) into the packed input, mean_off / var_off (arrays of ns; −1: not wanted) and
+// dmean_off / dvar_off (gp_vfe_predict_grad_batch: the gradients w.r.t. the test inputs, dimension-major [d][ns]; −1: not wanted) into the result buffer; the
+// points [row0, row0 + cnt) of the ns of problem `prob`.
 struct VfePSeg {
-    long xs_off, pm_off, mean_off, var_off;
+    long xs_off, pm_off, mean_off, var_off, dmean_off, dvar_off;
     int prob, ns, row0, cnt;
 };
 static_assert(sizeof(VfePred) % 8 == 0 && sizeof(VfePSeg) % 8 == 0, "the tables are packed behind double data");
@@ -2118,9 +2135,72 @@ __global__ __launch_bounds__(NT) void vfe_pprep_kernel(const double* __restrict_
 // The norm of a column is the sum of its lane's sixteen squares, then of the four lane groups by two exchanges, then of the two row parities: no step sees
 // another column or the column's place in the tile, so a test point's results are the same bits in any company.  Padding rows of B* and C* are zero, padding
 // test points are never written.  A problem whose fit failed returns at once (the host fills its NaN).
+//
+// GRAD (gp_vfe_predict_grad_batch) goes on per tile, with B* kept in the accumulators of step 2 and u_j = Wᵀ (B*_j − Eᵀ E B*_j):
+//   5. C* over B* in the tile buffer (every wave has read B* by then); D* = B* − Eᵀ C* (vfe_triu_mm: Eᵀ is upper triangular, the k loop of row block bi runs over
+//      bi … nb16 − 1; its fragments are the strip U read along its rows, sixteen rows a fragment, from L2), D* over C*.
+//   6. U* = Wᵀ D* the same way, Wᵀ's fragments read transposed out of the resident lower blocks of W (k rows 17 apart instead of 16, so that the sixteen rows of this read
+//      do not all fall on one bank as they would 16 apart — the intent, not measured; 78.3 KB instead of 73.7), U* over D*.
+//   7. the contraction, in the mapping of step 1: lane = test point, the eight waves interleave the pseudo-points; κ′ of (z_i − x*_j) once per (i, j) for both
+//      sides (kappa_and_dr2; Matern12 at distance 0 gives 0), Σ_i α_i κ′ t_p and Σ_i U*_ij κ′ t_p in 2 × 16 registers.  The eight waves' sums meet in the tile
+//      buffer, free by then — [wave][dimension][point], 64 KB at D = 16, one side after the other — and thread (p, j) adds them in wave order and writes
+//      dmean[j, p] = −2 σ² s_p Σ,  dvar[j, p] = 4 σ² s_p Σ  (t = z_i − s ∘ x*_j).  One writer per (j, p), no atomics; every order is fixed by m alone.
+// Mean side alone: no W, no strip, no MFMA — steps 1 and 7.  The values take the steps above unchanged: they are gp_vfe_predict_batch's bits.
+// Compiler report for gfx950 (VGPR / AGPR / LDS / scratch): <false> 150 / 0 / 143 360 B / 0; <true> 256 / 0 / 147 968 B / 0.
+static_assert(8 * BATCH_MAXD * VT <= VFE_MAXM * KBS, "the contraction's partial sums of one side fit in the tile buffer");
+static_assert((long)VFE_MAXM * (VFE_MAXM + 16) < (1L << 31), "the strip index of step 5 (below np · batch_ld(np)) is formed in 32 bits");
+// Step 7 of vfe_predict_kernel<true>.  On entry every wave may read KB (U* where dv); on exit KB is free again.
+__device__ __forceinline__ void vfe_pgrad_contract(const VfeProb& P, const VfePSeg& S, const double* __restrict__ z, const double* __restrict__ xs, double* KB,
+                                                   const double* al, double* __restrict__ res, int t0, bool dm, bool dv, int tid, int lane, int w) {
+    const int m = P.m, d = P.d, nscale = P.nscale, ns = S.ns;
+    const bool valid = t0 + lane < S.cnt;
+    const long j = (long)S.row0 + t0 + lane;
+    double xj[BATCH_MAXD], gm[BATCH_MAXD], gv[BATCH_MAXD];
+#pragma unroll
+    for (int p = 0; p < BATCH_MAXD; ++p) {
+        xj[p] = (p < d && valid) ? (nscale == 0 ? 1.0 : P.scale[nscale == 1 ? 0 : p]) * xs[(long)p * ns + j] : 0.0;
+        gm[p] = gv[p] = 0.0;
+    }
+#pragma unroll 1
+    for (int i = w; i < m; i += 8) {  // wave-uniform; one body at a time: two would not fit the registers beside the 2 × 16 sums
+        double t[BATCH_MAXD];
+        batch_diff(z, m, d, i, xj, t);
+        double d2 = 0.0;
+#pragma unroll
+        for (int p = 0; p < BATCH_MAXD; ++p) d2 = fma(t[p], t[p], d2);
+        double kap, dk;
+        kappa_and_dr2<double>(P.kind, d2, kap, dk);
+        const double cm = dm ? al[i] * dk : 0.0, cv = dv ? KB[i * KBS + lane] * dk : 0.0;
+#pragma unroll
+        for (int p = 0; p < BATCH_MAXD; ++p) {
+            gm[p] = fma(cm, t[p], gm[p]);
+            gv[p] = fma(cv, t[p], gv[p]);
+        }
+    }
+    __syncthreads();
+    auto reduce = [&](const double (&gs)[BATCH_MAXD], long off, double f) {
+#pragma unroll
+        for (int p = 0; p < BATCH_MAXD; ++p)
+            if (p < d) KB[(w * BATCH_MAXD + p) * VT + lane] = gs[p];
+        __syncthreads();
+        for (int e = tid; e < d * VT; e += NT) {
+            const int p = e >> 6, c = e & 63;
+            double s = 0.0;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) s += KB[(q * BATCH_MAXD + p) * VT + c];
+            if (t0 + c < S.cnt) res[off + (long)p * ns + S.row0 + t0 + c] = f * (nscale == 0 ? 1.0 : P.scale[nscale == 1 ? 0 : p]) * s;
+        }
+        __syncthreads();
+    };
+    if (dm) reduce(gm, S.dmean_off, -2.0 * P.variance);
+    if (dv) reduce(gv, S.dvar_off, 4.0 * P.variance);
+}
+
+template <bool GRAD>
 __global__ __launch_bounds__(NT) void vfe_predict_kernel(const double* __restrict__ in, const double* __restrict__ ws, double* __restrict__ res, int nw,
                                                          const VfeProb* __restrict__ vps, const VfePred* __restrict__ pps, const VfePSeg* __restrict__ segs) {
-    __shared__ double Wt[(VFE_MAXM / 16) * (VFE_MAXM / 16 + 1) / 2 * 256];
+    constexpr int WKS = GRAD ? 17 : 16, WBS = 16 * WKS;  // W's blocks: doubles between k rows, and per block
+    __shared__ double Wt[(VFE_MAXM / 16) * (VFE_MAXM / 16 + 1) / 2 * WBS];
     __shared__ double KB[VFE_MAXM * KBS];
     __shared__ double al[VFE_MAXM];
     __shared__ double nrm[2][2][VT];  // [B*, C*][row parity][test point]
@@ -2133,11 +2213,13 @@ __global__ __launch_bounds__(NT) void vfe_predict_kernel(const double* __restric
     const long ld = P.ld;
     const int nb16 = np / 16;
     const bool want_mean = S.mean_off >= 0, want_var = S.var_off >= 0;
+    const bool want_dmean = GRAD && S.dmean_off >= 0, want_dvar = GRAD && S.dvar_off >= 0;
+    const bool chain = want_var || want_dvar;  // the products of steps 2 and 3
     const double* __restrict__ z = in + P.z_off;
     const double* __restrict__ xs = in + S.xs_off;
-    const double* __restrict__ U = ws + (want_var ? pps[S.prob].u_off : 0);
-    if (want_var) vfe_load_wt(Wt, ws + P.w_off, ld, nb16, w, lane);
-    if (want_mean && tid < np) al[tid] = tid < m ? res[P.alpha_off + tid] : 0.0;
+    const double* __restrict__ U = ws + (chain ? pps[S.prob].u_off : 0);
+    if (chain) vfe_load_wt<WKS>(Wt, ws + P.w_off, ld, nb16, w, lane);
+    if ((want_mean || want_dmean) && tid < np) al[tid] = tid < m ? res[P.alpha_off + tid] : 0.0;
     __syncthreads();
     for (int t0 = 0; t0 < S.cnt; t0 += VT) {
         const bool valid = t0 + lane < S.cnt;
@@ -2148,7 +2230,7 @@ __global__ __launch_bounds__(NT) void vfe_predict_kernel(const double* __restric
 #pragma unroll
             for (int p = 0; p < BATCH_MAXD; ++p)
                 xj[p] = (p < d && valid) ? (nscale == 0 ? 1.0 : P.scale[nscale == 1 ? 0 : p]) * xs[(long)p * ns + j] : 0.0;
-            for (int rr = 0; rr < np / 8; ++rr) {
+            for (int rr = 0; rr < (!GRAD || want_mean || chain ? np / 8 : 0); ++rr) {  // the gradient of the mean alone needs no K*
                 const int i = w + 8 * rr;  // wave-uniform
                 double v = 0.0;
                 if (i < m && valid) {
@@ -2165,27 +2247,47 @@ __global__ __launch_bounds__(NT) void vfe_predict_kernel(const double* __restric
             for (int i = 0; i < m; ++i) s = fma(KB[i * KBS + lane], al[i], s);
             res[S.mean_off + j] = S.pm_off >= 0 ? in[S.pm_off + j] + s : s;
         }
-        if (!want_var) {
-            __syncthreads();  // the next tile's K* waits for the mean's reads
-            continue;
+        if (!chain) {
+            __syncthreads();  // the next tile's K*, or the contraction's sums, wait for the mean's reads
+        } else {
+            // ---- 2. B* = W K* over K*, its column norms
+            d4_t accb[4], acc[4];
+            double sq = vfe_tri_mm(accb, KB, nb16, w, lane, [&](int bi, int bk, int k) { return Wt[(bi * (bi + 1) / 2 + bk) * WBS + k * WKS + r]; });
+            sq += __shfl_xor(sq, 16, 64);
+            sq += __shfl_xor(sq, 32, 64);
+            __syncthreads();
+            vfe_tri_store(accb, KB, nb16, w, lane);
+            if (g == 0) nrm[0][w >> 2][16 * (w & 3) + r] = sq;
+            __syncthreads();
+            // ---- 3. C* = E B*: the column norms alone
+            sq = vfe_tri_mm(acc, KB, nb16, w, lane, [&](int bi, int bk, int k) { return U[(long)(16 * bk + k) * ld + 16 * bi + r]; });
+            sq += __shfl_xor(sq, 16, 64);
+            sq += __shfl_xor(sq, 32, 64);
+            if (g == 0) nrm[1][w >> 2][16 * (w & 3) + r] = sq;
+            __syncthreads();
+            // ---- 4. the variance
+            if (want_var && w == 0 && valid) res[S.var_off + j] = (P.variance - (nrm[0][0][lane] + nrm[0][1][lane])) + (nrm[1][0][lane] + nrm[1][1][lane]);
+            if (want_dvar) {
+                // ---- 5. C* over B*, D* = B* − Eᵀ C* over C*
+                vfe_tri_store(acc, KB, nb16, w, lane);
+                __syncthreads();
+                // The index is formed in 32 bits on purpose: with 64-bit row offsets the kernel, which sits at the 256 registers a lane of an eight-wave
+                // workgroup has, spilled two doubles to scratch.  It stays below np · ld <= 128 · batch_ld(128).
+                vfe_triu_mm(acc, KB, nb16, w, lane, [&](int bi, int bk, int k) { return U[(16 * bi + r) * (int)ld + 16 * bk + k]; });
+#pragma unroll
+                for (int q = 0; q < 4; ++q) accb[q] -= acc[q];
+                __syncthreads();
+                vfe_tri_store(accb, KB, nb16, w, lane);
+                __syncthreads();
+                // ---- 6. U* = Wᵀ D* over D*
+                vfe_triu_mm(acc, KB, nb16, w, lane, [&](int bi, int bk, int k) { return Wt[(bk * (bk + 1) / 2 + bi) * WBS + r * WKS + k]; });
+                __syncthreads();
+                vfe_tri_store(acc, KB, nb16, w, lane);
+                __syncthreads();
+            }
         }
-        // ---- 2. B* = W K* over K*, its column norms
-        d4_t acc[4];
-        double sq = vfe_tri_mm(acc, KB, nb16, w, lane, [&](int bi, int bk, int k) { return Wt[(bi * (bi + 1) / 2 + bk) * 256 + k * 16 + r]; });
-        sq += __shfl_xor(sq, 16, 64);
-        sq += __shfl_xor(sq, 32, 64);
-        __syncthreads();
-        vfe_tri_store(acc, KB, nb16, w, lane);
-        if (g == 0) nrm[0][w >> 2][16 * (w & 3) + r] = sq;
-        __syncthreads();
-        // ---- 3. C* = E B*: the column norms alone
-        sq = vfe_tri_mm(acc, KB, nb16, w, lane, [&](int bi, int bk, int k) { return U[(long)(16 * bk + k) * ld + 16 * bi + r]; });
-        sq += __shfl_xor(sq, 16, 64);
-        sq += __shfl_xor(sq, 32, 64);
-        if (g == 0) nrm[1][w >> 2][16 * (w & 3) + r] = sq;
-        __syncthreads();
-        // ---- 4. the variance
-        if (w == 0 && valid) res[S.var_off + j] = (P.variance - (nrm[0][0][lane] + nrm[0][1][lane])) + (nrm[1][0][lane] + nrm[1][1][lane]);
+        // ---- 7. the contraction with ∂k/∂x*
+        if (want_dmean || want_dvar) vfe_pgrad_contract(P, S, z, xs, KB, al, res, t0, want_dmean, want_dvar, tid, lane, w);
     }
 }
 
@@ -3430,9 +3532,13 @@ struct VfePredictArgs : VfeArgs {
     int32_t what;
     void* const* mean_out;
     void* const* var_out;
+    // gp_vfe_predict_grad_batch only (grad): the gradient arrays; there each of the four arrays may be NULL, not both of a side that is asked for
+    bool grad = false;
+    void* const* dmean_out = nullptr;
+    void* const* dvar_out = nullptr;
     const gp_points& xsb(int b) const { return xs[nxs == 1 ? 0 : b]; }
     const void* pmb(int b) const { return pm ? pm[b] : nullptr; }
-    void* out_b(void* const* arr, int side, int b) const { return (what & side) ? arr[b] : nullptr; }
+    void* out_b(void* const* arr, int side, int b) const { return (arr && (what & side)) ? arr[b] : nullptr; }
 };
 
 // the pseudo-inputs of one problem, dimension-major [d][m], scaled as the sparse path scales its inputs on the host (one product per entry)
@@ -3614,10 +3720,11 @@ int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw, const 
             const long ns = xs.n;
             if (pa->what & 2) vq.v[t].u_off = take(L.ws, (long)p.np * p.ld);
             const long xs_off = xso.place(L.off, (long)xs.d * ns), pm_off = pa->pmb(b) ? take(L.off, ns) : -1;
-            const long mean_off = (pa->what & 1) ? take(L.roff, ns) : -1, var_off = (pa->what & 2) ? take(L.roff, ns) : -1;
+            const long mean_off = pa->out_b(pa->mean_out, 1, b) ? take(L.roff, ns) : -1, var_off = pa->out_b(pa->var_out, 2, b) ? take(L.roff, ns) : -1;
+            const long dmean_off = pa->out_b(pa->dmean_out, 1, b) ? take(L.roff, ns * xs.d) : -1, dvar_off = pa->out_b(pa->dvar_out, 2, b) ? take(L.roff, ns * xs.d) : -1;
             first_seg[t] = (long)ps.v.size();
             for (long r0 = 0; r0 < ns; r0 += pseg)
-                ps.v.push_back(VfePSeg{xs_off, pm_off, mean_off, var_off, t, (int)ns, (int)r0, (int)std::min<long>(pseg, ns - r0)});
+                ps.v.push_back(VfePSeg{xs_off, pm_off, mean_off, var_off, dmean_off, dvar_off, t, (int)ns, (int)r0, (int)std::min<long>(pseg, ns - r0)});
         }
     }
     sg.place(L);
@@ -3644,11 +3751,12 @@ int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw, const 
         if (pa && !ps.v.empty()) {
             if (pa->what & 2) RC(launch(m, vfe_pprep_kernel, nw, NT, nw, vp.dev(m), vq.dev(m)));
             for (size_t s0 = 0; s0 < ps.v.size(); s0 += VFE_PRED_LAUNCH_SEGS)
-                RC(launch(m, vfe_predict_kernel, std::min<size_t>(VFE_PRED_LAUNCH_SEGS, ps.v.size() - s0), NT, nw, vp.dev(m), vq.dev(m), ps.dev(m, s0)));
+                RC(launch(m, pa->grad ? vfe_predict_kernel<true> : vfe_predict_kernel<false>, std::min<size_t>(VFE_PRED_LAUNCH_SEGS, ps.v.size() - s0), NT, nw,
+                          vp.dev(m), vq.dev(m), ps.dev(m, s0)));
         }
         return m.download_and_sync();
     }));
-    (go ? c->vfe_grad_batch_problems : pa ? c->vfe_predict_batch_problems : c->vfe_batch_problems) += nw;
+    (go ? c->vfe_grad_batch_problems : !pa ? c->vfe_batch_problems : pa->grad ? c->vfe_predict_grad_batch_problems : c->vfe_predict_batch_problems) += nw;
     for (int t = 0; t < nw; ++t) {
         const int b = idx[t];
         const VfeProb& p = vp.v[t];
@@ -3663,6 +3771,12 @@ int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw, const 
                 if (!out) continue;
                 if (failed) fill_nan(out, 0, s.ns);
                 else std::memcpy(out, m.hout + (side == 1 ? s.mean_off : s.var_off), sizeof(double) * s.ns);
+            }
+            for (int side = 1; side <= 2; ++side) {  // the gradients: [d][ns] -> the container layout of xs
+                void* out = pa->out_b(side == 1 ? pa->dmean_out : pa->dvar_out, side, b);
+                if (!out) continue;
+                if (failed) fill_nan(out, 0, (long)s.ns * p.d);
+                else grad_to_layout<double>(pa->xsb(b).layout, s.ns, p.d, m.hout + (side == 1 ? s.dmean_off : s.dvar_off), s.ns, out);
             }
         }
         if (!go) continue;
@@ -3754,7 +3868,7 @@ int32_t vfe_grad_batch_impl(gp_ctx* c, VfeArgs& a, const VfeGradOut& go) {
 }
 
 // doubles problem b alone adds to the workspace (the strip L_D⁻ᵀ) and to the page-locked staging of a prediction wave (its test points where they are not
-// shared, prior mean, segment table, α, mean and variance)
+// shared, prior mean, segment table, α, mean and variance and, with gradients, d entries per test point and side)
 long vfe_predict_ws(const VfePredictArgs& a, int b) {
     const long np = batch_np(a.zb(b).n);
     return ((a.what & 2) && a.xsb(b).n > 0) ? np * batch_ld(np) : 0;
@@ -3762,27 +3876,42 @@ long vfe_predict_ws(const VfePredictArgs& a, int b) {
 long vfe_predict_io(const VfePredictArgs& a, int b) {
     const gp_points& xs = a.xsb(b);
     const long nseg = (xs.n + vfe_pseg() - 1) / vfe_pseg();
-    return a.zb(b).n + (a.nxs == 1 ? 0 : (long)xs.d * xs.n) + (a.pmb(b) ? xs.n : 0) + nseg * (long)(sizeof(VfePSeg) / 8) + ((a.what & 1) + (a.what >> 1)) * xs.n;
+    return a.zb(b).n + (a.nxs == 1 ? 0 : (long)xs.d * xs.n) + (a.pmb(b) ? xs.n : 0) + nseg * (long)(sizeof(VfePSeg) / 8) +
+           ((a.what & 1) + (a.what >> 1)) * xs.n * (a.grad ? 1 + xs.d : 1);
 }
 
-// the test side of gp_vfe_predict_batch that needs neither the handle nor a device (arguments 14 … 19)
+// the test side of gp_vfe_predict_batch / gp_vfe_predict_grad_batch that needs neither the handle nor a device (arguments 14 … 19, … 21 with gradients)
 int32_t check_vfe_test_head(const VfePredictArgs& a) {
     RC(check_test_head(a, 14));
     if (a.what <= 0 || a.what > 3) return set_arg_err(17, "what must be a combination of 1|2");
-    if ((a.what & 1) && !a.mean_out) return set_arg_err(18, "mean_out is NULL");
-    if ((a.what & 2) && !a.var_out) return set_arg_err(19, "var_out is NULL");
+    if ((a.what & 1) && !a.mean_out && !a.dmean_out) return set_arg_err(18, a.grad ? "mean_out and dmean_out are both NULL" : "mean_out is NULL");
+    if ((a.what & 2) && !a.var_out && !a.dvar_out) return set_arg_err(19, a.grad ? "var_out and dvar_out are both NULL" : "var_out is NULL");
     return 0;
 }
 
-// gp_vfe_predict_batch: the body of vfe_batch_impl with the predictions behind the fit — two more launches per wave, gp_vfe_predict behind gp_vfe_fit for the rest
+// NaN in every output of problem b that the call was given (the call's dtype: a routed fp32 problem has float arrays)
+void vfe_predict_fill_nan(const VfePredictArgs& a, int b) {
+    const gp_points& xs = a.xsb(b);
+    if (xs.n <= 0) return;
+    fill_nan(a.out_b(a.mean_out, 1, b), a.dtype, xs.n);
+    fill_nan(a.out_b(a.var_out, 2, b), a.dtype, xs.n);
+    fill_nan(a.out_b(a.dmean_out, 1, b), a.dtype, xs.n * xs.d);
+    fill_nan(a.out_b(a.dvar_out, 2, b), a.dtype, xs.n * xs.d);
+}
+
+// gp_vfe_predict_batch: the body of vfe_batch_impl with the predictions behind the fit — two more launches per wave, gp_vfe_predict behind gp_vfe_fit for the rest.
+// gp_vfe_predict_grad_batch (a.grad): the same body with the gradient variant of the predict kernel and gp_vfe_predict_grad for the rest.
 int32_t vfe_predict_batch_impl(gp_ctx* c, VfePredictArgs& a) {
     Guard gd(c);
     if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
     if (a.nb < 0) return set_arg_err(2, "nb must be >= 0");
     if (a.nb == 0) return 0;
-    RC(check_vfe_args(a, 0, 21));
-    RC(check_test_points(a, nullptr, {{a.mean_out, (a.what & 1) != 0, 18, "a mean_out pointer is NULL"}, {a.var_out, (a.what & 2) != 0, 19, "a var_out pointer is NULL"}}, 15));
-    const long max_n = env_capped(getenv("GPMI_VFE_PREDICT_BATCH_MAX_N"), GPMI355_VFE_PREDICT_BATCH_MAX_N, VFE_KERNEL_MAX_N);
+    RC(check_vfe_args(a, 0, a.grad ? 23 : 21));
+    const bool m1 = (a.what & 1) != 0, m2 = (a.what & 2) != 0;
+    RC(check_test_points(a, nullptr, {{a.mean_out, m1, 18, "a mean_out pointer is NULL"}, {a.var_out, m2, 19, "a var_out pointer is NULL"},
+                                      {a.dmean_out, m1, 20, "a dmean_out pointer is NULL"}, {a.dvar_out, m2, 21, "a dvar_out pointer is NULL"}}, 15));
+    const long max_n = a.grad ? env_capped(getenv("GPMI_VFE_PREDICT_GRAD_BATCH_MAX_N"), GPMI355_VFE_PREDICT_GRAD_BATCH_MAX_N, VFE_KERNEL_MAX_N)
+                              : env_capped(getenv("GPMI_VFE_PREDICT_BATCH_MAX_N"), GPMI355_VFE_PREDICT_BATCH_MAX_N, VFE_KERNEL_MAX_N);
     std::vector<int> mine, routed;
     for (int b = 0; b < a.nb; ++b) (vfe_batch_takes(a, b, max_n) ? mine : routed).push_back(b);
     RC(for_each_wave(c, mine,
@@ -3790,19 +3919,18 @@ int32_t vfe_predict_batch_impl(gp_ctx* c, VfePredictArgs& a) {
                          return WaveCost{sizeof(double) * (size_t)(vfe_ws(a, b) + vfe_predict_ws(a, b)), 0, sizeof(double) * (size_t)(vfe_in(a, b) + vfe_predict_io(a, b))};
                      },
                      [&](const int* idx, int nw) { return run_vfe_wave(c, a, idx, nw, nullptr, &a); }));
-    // everything else: gp_vfe_fit + gp_vfe_predict + gp_vfe_free, one problem at a time, after the lock is released (as batch_impl does)
+    // everything else: gp_vfe_fit + gp_vfe_predict (gp_vfe_predict_grad) + gp_vfe_free, one problem at a time, after the lock is released (as batch_impl does)
     gd.lk.unlock();
     for (int b : routed) {
         const gp_points& xs = a.xsb(b);
         gp_vfe* h = nullptr;
         int32_t rc = gp_vfe_fit(c, &a.k[b], &a.xb(b), &a.zb(b), &a.noise[b], a.jitter[b], a.mb(b), a.yb(b), a.approx[b], xs.n > 0 ? &h : nullptr, logpdf_slot(a, b));
-        if (rc == 0 && h) rc = gp_vfe_predict(h, &xs, a.pmb(b), a.what, a.out_b(a.mean_out, 1, b), a.out_b(a.var_out, 2, b), nullptr);
+        if (rc == 0 && h)
+            rc = a.grad ? gp_vfe_predict_grad(h, &xs, a.pmb(b), a.what, a.out_b(a.mean_out, 1, b), a.out_b(a.var_out, 2, b), a.out_b(a.dmean_out, 1, b),
+                                              a.out_b(a.dvar_out, 2, b))
+                        : gp_vfe_predict(h, &xs, a.pmb(b), a.what, a.out_b(a.mean_out, 1, b), a.out_b(a.var_out, 2, b), nullptr);
         if (h) (void)gp_vfe_free(h);
-        RC(routed_done(a, b, rc, [&] {
-            if (xs.n <= 0) return;
-            fill_nan(a.out_b(a.mean_out, 1, b), a.dtype, xs.n);
-            fill_nan(a.out_b(a.var_out, 2, b), a.dtype, xs.n);
-        }));
+        RC(routed_done(a, b, rc, [&] { vfe_predict_fill_nan(a, b); }));
     }
     return 0;
 }
@@ -3985,6 +4113,17 @@ int32_t gp_vfe_predict_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_
                              void* const* mean_out, void* const* var_out, void* objective_out_or_null, int32_t* info_out) {
     VfePredictArgs a{{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, objective_out_or_null, info_out), nz, z, jitter, approx, nullptr},
                      nxs, xs, prior_mean_xs_or_null, what, mean_out, var_out};
+    if (nb > 0) RC(check_vfe_test_head(a));
+    return vfe_predict_batch_impl(ctx, a);
+}
+
+int32_t gp_vfe_predict_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, int32_t nz, const gp_points* z,
+                                  const gp_noise* noise, const double* jitter, const void* const* mean_or_null, int32_t ny, const void* const* y,
+                                  const int32_t* approx, int32_t nxs, const gp_points* xs, const void* const* prior_mean_xs_or_null, int32_t what,
+                                  void* const* mean_out_or_null, void* const* var_out_or_null, void* const* dmean_out_or_null, void* const* dvar_out_or_null,
+                                  void* objective_out_or_null, int32_t* info_out) {
+    VfePredictArgs a{{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, objective_out_or_null, info_out), nz, z, jitter, approx, nullptr},
+                     nxs, xs, prior_mean_xs_or_null, what, mean_out_or_null, var_out_or_null, true, dmean_out_or_null, dvar_out_or_null};
     if (nb > 0) RC(check_vfe_test_head(a));
     return vfe_predict_batch_impl(ctx, a);
 }

@@ -1882,6 +1882,90 @@ function approx_mean_and_var_batch(approxs::AbstractVector, fxs::AbstractVector{
     return return_objective ? (res..., obj) : res
 end
 
+# ---- … and their gradients w.r.t. the test inputs: gp_vfe_predict_grad_batch --------------------------------------------------------------------
+# approx_mean_and_var_grad_batch(approxs, fxs, ys, xs; what, mean_grads): the quadruples (mean, var, dmean, dvar) of every problem — `nothing` for whatever was
+# not asked for, the gradients in the container layout of xs[b] as mean_and_var_grad shapes them — in ONE library call per (context, eltype) group.  Arguments,
+# sharing rules and on_error as approx_mean_and_var_batch; mean_grads as mean_and_var_grad_batch (the device treats the prior mean as constant in x*).
+function approx_mean_and_var_grad_batch(approxs::AbstractVector, fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys, xs::AbstractVector; what::Integer=3,
+                                        mean_grads=nothing, return_objective::Bool=false, on_error::Symbol=:raise)
+    on_error in (:raise, :nan) || throw(ArgumentError("on_error must be :raise or :nan"))
+    what in (1, 2, 3) || throw(ArgumentError("what must be 1 (mean), 2 (var) or 3 (both)"))
+    nb = length(approxs)
+    fv = length(fxs) == 1 ? fill(fxs[1], nb) : fxs
+    yv = (ys isa AbstractVector{<:Real}) ? fill(ys, nb) : (length(ys) == 1 ? fill(ys[1], nb) : collect(ys))
+    xv = length(xs) == 1 ? fill(xs[1], nb) : xs
+    mg = mean_grads === nothing ? fill(nothing, nb) : collect(Any, mean_grads)
+    (length(fv) == nb && length(yv) == nb && length(xv) == nb && length(mg) == nb) ||
+        throw(DimensionMismatch("$(nb) approximations, $(length(fv)) FiniteGPs, $(length(yv)) observation vectors, $(length(xv)) sets of test points, $(length(mg)) entries of mean_grads"))
+    obj = fill(NaN, nb)
+    info = zeros(Int32, nb)
+    quads = Vector{Any}(nothing, nb)
+    args = Vector{Any}(nothing, nb)
+    groups = Dict{Any,Vector{Int}}()
+    for b in 1:nb
+        ap, fx, y = approxs[b], fv[b], yv[b]
+        @assert ap.fz.f === fx.f
+        length(fx) == length(y) || throw(DimensionMismatch("problem $(b): length(fx) != length(y)"))
+        a = marshal(fx, eltype(y))
+        (a === nothing || haskey(a, :ks) || is_dense(a.cn) || !(ap.fz.Σy isa Diagonal{<:Any,<:Fill})) &&
+            throw(ArgumentError("problem $(b): kernel / noise / pseudo-input form is not accelerated"))
+        ((what & 1) != 0 && fx.f.gp.mean isa CustomMean && mg[b] === nothing) &&
+            throw(ArgumentError("problem $(b): the prior mean is a CustomMean: pass mean_grads[$(b)] = function returning its ns × d derivative at xs"))
+        pz = points(ap.fz.x, a.T)
+        args[b] = (a=a, zbuf=pz[1], cz=pz[2], jitter=Float64(FillArrays.getindex_value(ap.fz.Σy.diag)))
+        push!(get!(groups, (fx.f.ctx, a.T), Int[]), b)
+    end
+    for ((ctx, Tg), idx) in groups
+        g = length(idx)
+        nx = all(b -> fv[b].x === fv[idx[1]].x, idx) ? 1 : g
+        nz = all(b -> approxs[b].fz.x === approxs[idx[1]].fz.x, idx) ? 1 : g
+        ny = all(b -> yv[b] === yv[idx[1]], idx) ? 1 : g
+        nxs = all(b -> xv[b] === xv[idx[1]], idx) ? 1 : g
+        cks = [args[b].a.ck for b in idx]
+        cxs = [args[b].a.cx for b in idx[1:nx]]
+        czs = [args[b].cz for b in idx[1:nz]]
+        cns = [args[b].a.cn for b in idx]
+        jit = Float64[args[b].jitter for b in idx]
+        kinds = Int32[approxs[b] isa VFE ? 0 : 1 for b in idx]
+        ybufs = [Vector{Tg}(yv[b]) for b in idx[1:ny]]
+        yptrs = Ptr{Cvoid}[pointer(v) for v in ybufs]
+        mptrs = Ptr{Cvoid}[args[b].a.m === nothing ? C_NULL : pointer(args[b].a.m) for b in idx]
+        xsp = [points(xv[b], Tg) for b in idx[1:nxs]]  # (buffer, CPoints)
+        cxss = [p[2] for p in xsp]
+        pms = [prior_mean(fv[b].f.gp, xv[b], Tg) for b in idx]  # m(x*) on the host; nothing = ZeroMean
+        pmptrs = Ptr{Cvoid}[m === nothing ? C_NULL : pointer(m) for m in pms]
+        mbufs = [Vector{Tg}(undef, (what & 1) != 0 ? length(xv[b]) : 0) for b in idx]
+        vbufs = [Vector{Tg}(undef, (what & 2) != 0 ? length(xv[b]) : 0) for b in idx]
+        dmbufs = [(what & 1) != 0 ? similar(xsp[nxs == 1 ? 1 : j][1]) : Tg[] for j in 1:g]  # in the container layout of xs
+        dvbufs = [(what & 2) != 0 ? similar(xsp[nxs == 1 ? 1 : j][1]) : Tg[] for j in 1:g]
+        moptrs = Ptr{Cvoid}[pointer(v) for v in mbufs]
+        voptrs = Ptr{Cvoid}[pointer(v) for v in vbufs]
+        dmptrs = Ptr{Cvoid}[pointer(v) for v in dmbufs]
+        dvptrs = Ptr{Cvoid}[pointer(v) for v in dvbufs]
+        out = Vector{Tg}(undef, g)
+        inf = zeros(Int32, g)
+        GC.@preserve args cks cxs czs cns jit kinds ybufs yptrs mptrs xsp cxss pms pmptrs mbufs vbufs dmbufs dvbufs moptrs voptrs dmptrs dvptrs out inf begin
+            check(ccall((:gp_vfe_predict_grad_batch, libgpmi355), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{CKernel}, Int32, Ptr{CPoints}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Float64}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}},
+                    Ptr{Int32}, Int32, Ptr{CPoints}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Cvoid},
+                    Ptr{Int32}),
+                ctx.handle, g, cks, nx, cxs, nz, czs, cns, jit, mptrs, ny, yptrs, kinds, nxs, cxss, pmptrs, what,
+                (what & 1) != 0 ? pointer(moptrs) : C_NULL, (what & 2) != 0 ? pointer(voptrs) : C_NULL,
+                (what & 1) != 0 ? pointer(dmptrs) : C_NULL, (what & 2) != 0 ? pointer(dvptrs) : C_NULL, out, inf))
+        end
+        for (j, b) in enumerate(idx)
+            obj[b] = out[j]
+            info[b] = inf[j]
+            dm = (what & 1) != 0 ? dmbufs[j] : nothing
+            (dm !== nothing && fv[b].f.gp.mean isa CustomMean) && (dm = grad_plus(xv[b], dm, Tg.(mg[b](xv[b]))))
+            quads[b] = ((what & 1) != 0 ? mbufs[j] : nothing, (what & 2) != 0 ? vbufs[j] : nothing, dm, (what & 2) != 0 ? dvbufs[j] : nothing)
+        end
+    end
+    bad = findfirst(!iszero, info)
+    on_error === :raise && bad !== nothing && throw(BatchPosDefException(Int(info[bad]), bad))
+    return return_objective ? (quads, obj) : quads
+end
+
 # ---- value + gradient of the sparse objective: one fit + one backward pass over the retained observations (gp_vfe_grad) ------------------
 # The reference's users maximise `elbo(VFE(f(z, jitter)), f(x, Σy), y)` over kernel parameters and pseudo-points by AD / finite differences
 # (examples/0-intro-1d/script.jl:385-394); the ccall is opaque to AD, so the accelerated objective carries its own pullback.

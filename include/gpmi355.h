@@ -312,6 +312,7 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
  *   "vfe_batch_kernel_problems"       read-only: the same for the kernels of gp_vfe_batch
  *   "vfe_grad_batch_kernel_problems"  read-only: the same for the kernels of gp_vfe_grad_batch
  *   "vfe_predict_batch_kernel_problems"  read-only: the same for the kernels of gp_vfe_predict_batch
+ *   "vfe_predict_grad_batch_kernel_problems"  read-only: the same for the kernels of gp_vfe_predict_grad_batch
  *   "cols_kernel_calls", "cols_kernel_splits"   read-only: kmul launches gp_posterior_predict_cols has served on this ctx since it was created, and the workgroups
  *                    along the training range of the last of them (1 = unsplit, 0 = none yet): which path ran, for tests and measurements */
 /* The defaults above, machine-readable (single-device parameters; gp_ctx_get_param reads the same names): the test-suite asserts before
@@ -1071,6 +1072,46 @@ int32_t gp_vfe_predict_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_
                              const gp_noise* noise, const double* jitter, const void* const* mean_or_null, int32_t ny, const void* const* y,
                              const int32_t* approx, int32_t nxs, const gp_points* xs, const void* const* prior_mean_xs_or_null, int32_t what,
                              void* const* mean_out, void* const* var_out, void* objective_out_or_null, int32_t* info_out);
+
+/* gp_vfe_predict_grad_batch: the predictions of gp_vfe_predict_batch AND their gradients w.r.t. the test inputs, of nb independent VFE / DTC problems in one
+ * call — what a gradient-based acquisition step over many sparse surrogates evaluates (a loop of gp_vfe_fit + gp_vfe_predict_grad + gp_vfe_free otherwise).
+ * Every argument up to `what` as gp_vfe_predict_batch; the four output arrays as gp_predict_grad_batch has them: each may be NULL, but not both arrays of a
+ * side that is asked for; a given array holds a non-NULL pointer wherever ns_b > 0; the gradients are ns_b·d entries in the container layout of xs_b, in the
+ * call's dtype.  Per problem the semantics are those of gp_vfe_fit followed by gp_vfe_predict_grad: with W = L_z⁻¹, E = L_D⁻¹ and k*_j = K(z, x*_j),
+ *   dmean[j,p] = Σ_m α_m ∂k(x*_j, z_m)/∂x*_jp,   dvar[j,p] = −2 Σ_m u_jm ∂k(x*_j, z_m)/∂x*_jp,   u_j = Wᵀ (B*_j − Eᵀ E B*_j),   B*_j = W k*_j
+ * (the prior mean and k(x*, x*) count as constant in x*; Matern12 at distance 0 contributes 0).  Failure is data: a failed problem reports info_out[b] and has
+ * NaN in every output, gradients included.  The return value reports argument errors only (nb = 0 returns 0); those of the test side are reported before the
+ * handle is looked at.
+ * Eligibility as gp_vfe_predict_batch with n_b <= GPMI355_VFE_PREDICT_GRAD_BATCH_MAX_N; every other problem is answered inside the call by gp_vfe_fit +
+ * gp_vfe_predict_grad + gp_vfe_free, and which path serves a problem depends on that problem alone.  The fit's three launches and vfe_pprep_kernel run
+ * unchanged; the predict kernel is the compile-time variant vfe_predict_kernel<true> (csrc/batch.hip), whose mean, variance and objective are the bits of
+ * gp_vfe_predict_batch.  Per tile of 64 test points it keeps B* in the accumulators of B* = W K*, stores C* = E B* over B* in LDS, forms D* = B* − Eᵀ C* and
+ * U* = Wᵀ D* by v_mfma_f64_16x16x4_f64 over the non-zero blocks of the two UPPER-triangular operands (k blocks bi … nb16 − 1), and contracts U* and α with
+ * ∂k/∂x* re-evaluated from the packed z and x*: lane = test point, the waves interleave the pseudo-points, κ′ once per (m, j) for both sides, sums in
+ * registers; the eight waves' sums meet in the tile buffer (free by then) and one thread per (j, p) adds them in wave order.  No atomics; every order is
+ * fixed by m alone, so a test point's four outputs are the same bits alone, in any batch, at any offset of its set and on repetition.
+ * Placement of E: Eᵀ's fragments are read from the strip U = Eᵀ that vfe_pprep_kernel leaves, along its rows (sixteen rows a fragment, 32 B each, from L2);
+ * an untransposed second copy of E was not built and not measured.  Wᵀ's fragments come transposed out of the resident lower blocks of W, whose k rows lie 17
+ * doubles apart in this variant (78.3 KB instead of 73.7) so that the sixteen rows of that read do not share one bank (the intent; not measured).  With what = 1 neither W, the strip nor the MFMA is used.
+ * Compiler report for gfx950: vfe_predict_kernel<true> 256 VGPRs, 0 AGPRs, 147 968 B of LDS, no scratch (<false> unchanged: 150 / 0 / 143 360 / 0).
+ * Against the oracle (vfe_posterior for the values, tests/predict_grad_ref.py::sparse_grads for the gradients) over the tables of
+ * tests/test_gpu_vfe_predict_grad_batch.py the largest deviations are 2.8e-14 (mean), 6.2e-15 (var), 1.8e-13 (dmean), 1.7e-14 (dvar).
+ * GPMI355_VFE_PREDICT_GRAD_BATCH_MAX_N: by the rule of the other batch thresholds — the largest n of the measured sweep at which one batch call beat the loop of
+ * gp_vfe_fit + gp_vfe_predict_grad + gp_vfe_free in every cell with nb >= 8 (tools/vfe_predict_grad_batch_profile.py --min-s 0.02 --loop-samples 2, SE, D = 3,
+ * what = 3 with all four outputs, M = 16, 64, 128 × n = 1 024 … 262 144 × nb = 1, 8, 64, 512 × 64 and 1 024 test points per problem, shared and per-problem
+ * (x, y, xs): 240 cells, none skipped, each checked against the loop's values; two processes, split by n: profiles/r38/vfe_predict_grad_batch_profile_n1024_65536.json
+ * and …_n262144.json).  It beat it in all 180 of them, so the macro is the largest n swept.  The closest cells are those with per-problem data and 64 test
+ * points at M = 128, n = 262 144, where packing and uploading the inputs is most of the call: nb = 8 9.38 against 18.5 ms, nb = 64 61.5 against 149 ms, nb = 512
+ * 489 against 1 171 ms (at n = 65 536, nb = 8: 2.68 against 9.90 ms).  A single problem (nb = 1) loses at M = 128 with 64 test points from n = 4 096 on (2.83
+ * against 2.18 ms at n = 262 144: one workgroup runs the M×M side); the rule does not count it.  The cost against gp_vfe_predict_batch (what = 3) on the
+ * same cells ("grad_over_values"): 0.88 … 2.67 — near 1 where the fit dominates (0.99 … 1.10 at n = 262 144), largest at n = 1 024 with 1 024 test points.
+ * (The environment variable GPMI_VFE_PREDICT_GRAD_BATCH_MAX_N, read per call, overrides the macro for measurements.) */
+#define GPMI355_VFE_PREDICT_GRAD_BATCH_MAX_N 262144
+int32_t gp_vfe_predict_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, int32_t nz, const gp_points* z,
+                                  const gp_noise* noise, const double* jitter, const void* const* mean_or_null, int32_t ny, const void* const* y,
+                                  const int32_t* approx, int32_t nxs, const gp_points* xs, const void* const* prior_mean_xs_or_null, int32_t what,
+                                  void* const* mean_out_or_null, void* const* var_out_or_null, void* const* dmean_out_or_null, void* const* dvar_out_or_null,
+                                  void* objective_out_or_null, int32_t* info_out);
 
 /* ---- device-level building blocks ------------------------------------------------------------ */
 /* The operations the in-library multi-device driver composes (csrc/multi.hip calls the same engine functions), exposed on DEVICE
