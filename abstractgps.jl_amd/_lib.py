@@ -160,6 +160,9 @@ PROTOTYPES = {
                                    C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp), vp, C.POINTER(i32)]),
     "gp_vfe_predict_grad_batch": (i32, [vp, i32, PK, i32, PP, i32, PP, PN, C.POINTER(dbl), C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(i32), i32, PP,
                                         C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, C.POINTER(i32)]),
+    "gp_vfe_joint_batch": (i32, [vp, i32, PK, i32, PP, i32, PP, PN, C.POINTER(dbl), C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(i32), i32, PP,
+                                 C.POINTER(vp), PN, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, i32, C.POINTER(vp), C.POINTER(vp), vp, C.POINTER(i32),
+                                 C.POINTER(i32)]),
     "gpd_assemble": (i32, [vp, PK, vp, i64, i64, i32, vp, PG, vp, i64, i64, i64]),
     "gpd_potrf": (i32, [vp, vp, i64, i64, i64, vp, i32, i64, vp]),
     "gpd_trsm": (i32, [vp, vp, i64, i64, vp, i64, i64]),
@@ -246,6 +249,12 @@ def vfe_predict_batch_limits() -> dict:
 def vfe_predict_grad_batch_max_n() -> int:
     """GPMI355_VFE_PREDICT_GRAD_BATCH_MAX_N of include/gpmi355.h: the largest n gp_vfe_predict_grad_batch hands to its kernels."""
     return int(re.search(r"#define GPMI355_VFE_PREDICT_GRAD_BATCH_MAX_N (\d+)", HEADER.read_text()).group(1))
+
+
+def vfe_joint_batch_limits() -> dict:
+    """GPMI355_VFE_JOINT_BATCH_MAX_N / _MAX_NS of include/gpmi355.h: the largest n and the most test points gp_vfe_joint_batch hands to its kernels."""
+    txt = HEADER.read_text()
+    return {k: int(re.search(rf"#define GPMI355_VFE_JOINT_BATCH_{k} (\d+)", txt).group(1)) for k in ("MAX_N", "MAX_NS")}
 
 
 def batch_pgrad_max_n() -> int:

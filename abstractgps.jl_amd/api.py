@@ -1008,6 +1008,16 @@ def _joint_marshal(g: _BatchGroup, what: int, noises, ys_heldout, xis) -> _Joint
     m, nb = pc.keep, pc.nb
     nbk, karr, nx, pts, narr, marr, ny, yarr, nxs, xpts, pmarr, _, moarr, _, out, info = pc.args
     ns = [int(xpts[0 if g.nxs == 1 else b].n) for b in range(nb)]
+    nzarr, coarr, ysarr, heldout_ptr, nsamp, xiarr, soarr, info_joint, covs, heldout, samples = _joint_side(m, g, ns, what, noises, ys_heldout, xis)
+    args = (nbk, karr, nx, pts, narr, marr, ny, yarr, nxs, xpts, pmarr, nzarr, what, moarr, coarr, ysarr, heldout_ptr, nsamp, xiarr, soarr, out, info,
+            info_joint.ctypes.data_as(C.POINTER(C.c_int32)))
+    return _JointCall("gp_joint_batch" + ("_sum" if g.composite else ""), nb, g.nx, g.ny, g.nxs, args, pc.out, pc.info, info_joint, pc.means, covs, heldout, samples, m)
+
+
+def _joint_side(m, g: _BatchGroup, ns: list, what: int, noises, ys_heldout, xis) -> tuple:
+    """The joint side of a gp_joint_batch / gp_vfe_joint_batch call for a group whose problems have ns[b] test points: the ctypes arguments noise_xs, cov_out, ys,
+    hlogpdf_out, nsamp, xi, samples_out, then info_joint and the buffers behind covariances, held-out logpdf and samples (None for what is not asked for)."""
+    nb = len(ns)
     nzarr = None
     if noises is not None and any(v is not None for v in noises):
         nzarr = (gp_noise * nb)(*[m.noise(0.0 if v is None else v, k) for v, k in zip(noises, ns)])
@@ -1038,9 +1048,7 @@ def _joint_marshal(g: _BatchGroup, what: int, noises, ys_heldout, xis) -> _Joint
         soarr = (C.c_void_p * nb)(*[a.ctypes.data for a in samples])
     info_joint = np.zeros(nb, dtype=np.int32)
     m.keep += [nzarr, coarr, ysarr, xiarr, soarr]
-    args = (nbk, karr, nx, pts, narr, marr, ny, yarr, nxs, xpts, pmarr, nzarr, what, moarr, coarr, ysarr, None if heldout is None else heldout.ctypes.data, nsamp,
-            xiarr, soarr, out, info, info_joint.ctypes.data_as(C.POINTER(C.c_int32)))
-    return _JointCall("gp_joint_batch" + ("_sum" if g.composite else ""), nb, g.nx, g.ny, g.nxs, args, pc.out, pc.info, info_joint, pc.means, covs, heldout, samples, m)
+    return nzarr, coarr, ysarr, None if heldout is None else heldout.ctypes.data, nsamp, xiarr, soarr, info_joint, covs, heldout, samples
 
 
 def _per_problem(v, n: int, name: str):
@@ -2538,6 +2546,85 @@ def approx_mean_and_var_grad_batch(approxs, fxs, ys, xs, *, what: int = 3, mean_
             quads[i] = (mean, var, dmean, dvar)
     obj = _batch_merge(n, parts, False, on_error)
     return (quads, obj) if return_objective else quads
+
+
+def approx_joint_batch(approxs, fxs, ys, xs, *, noise=None, ys_heldout=None, xi=None, what: Optional[int] = None, return_objective: bool = False,
+                       on_error: str = "raise"):
+    """The joint predictive distribution of many independent sparse GPs at their test points, in one library call per (ctx, dtype) group (gp_vfe_joint_batch) —
+    per problem what posterior(approxs[b], fxs[b], ys[b])(xs[b], noise[b]) answers (src/sparse_approximations.jl:183-217, src/finite_gp_projection.jl:133-136,
+    233-237, 306-311): mean and latent covariance, the held-out logpdf and joint samples mean + chol(cov + noise_b).L @ xi_b.  approxs, fxs, ys, xs as in
+    approx_mean_and_var_batch; noise, ys_heldout, xi, what and on_error as in joint_batch.  Returns the list of (mean, cov, heldout_logpdf, samples) in the
+    caller's order, None for what was not asked for (with return_objective: that list and the array of objectives)."""
+    if on_error not in ("raise", "nan"):
+        raise ValueError('on_error must be "raise" or "nan"')
+    if what is None:
+        what = JOINT_MEAN | JOINT_COV | (JOINT_LOGPDF if ys_heldout is not None else 0) | (JOINT_RAND if xi is not None else 0)
+    if what <= 0 or what & ~(JOINT_MEAN | JOINT_COV | JOINT_LOGPDF | JOINT_RAND):
+        raise ValueError("what must be a combination of 1 (mean), 4 (cov), 8 (held-out logpdf) and 16 (samples)")
+    if what & JOINT_LOGPDF and ys_heldout is None:
+        raise ValueError("the held-out logpdf needs ys_heldout")
+    if what & JOINT_RAND and xi is None:
+        raise ValueError("samples need xi, the standard normals of every problem")
+    approxs = list(approxs)
+    n = len(approxs)
+    xs = [xs] if isinstance(xs, (np.ndarray, ColVecs, RowVecs)) else list(xs)
+    if len(xs) == 1 and n > 1:
+        xs = xs * n
+    if len(xs) != n:
+        raise ValueError(f"DimensionMismatch: {n} problems but {len(xs)} sets of test points")
+    if not approxs:
+        return ([], np.empty(0)) if return_objective else []
+    noise, ys_heldout, xi = _per_problem(noise, n, "noise"), _per_problem(ys_heldout, n, "ys_heldout"), _per_problem(xi, n, "xi")
+    quads, parts, joint_bad = [None] * n, [], []
+    for g in _vfe_batch_groups(approxs, fxs, ys):
+        call = _vfe_batch_marshal(g, False, False)
+        m, nb = call.keep, call.nb
+        tss = [xs[i] for i in g.index]
+        nts = 1 if all(v is tss[0] for v in tss) else nb
+        xpts = (gp_points * nts)(*[m.points(v) for v in tss[:nts]])
+        ns = [int(xpts[0 if nts == 1 else b].n) for b in range(nb)]
+        pms = [_mean_vector(fx.f.mean_fn, v, g.dtype) for fx, v in zip(g.fxs, tss)]  # m(x*) on the host; None = ZeroMean
+        pms = [None if v is None else m.arr(v) for v in pms]
+        pmarr = None if all(v is None for v in pms) else (C.c_void_p * nb)(*[None if v is None else v.ctypes.data for v in pms])
+        means = [np.empty(k, dtype=g.dtype) for k in ns] if what & JOINT_MEAN else None
+        moarr = None if means is None else (C.c_void_p * nb)(*[a.ctypes.data for a in means])
+        pick = lambda v: None if v is None else [v[i] for i in g.index]
+        *side, info_joint, covs, heldout, samples = _joint_side(m, g, ns, what, pick(noise), pick(ys_heldout), pick(xi))
+        nzarr, coarr, ysarr, hptr, nsamp, xiarr, soarr = side
+        ctx = g.ctx or default_context()
+        check(ctx.lib.gp_vfe_joint_batch(ctx.handle, *call.args[:12], nts, xpts, pmarr, nzarr, what, moarr, coarr, ysarr, hptr, nsamp, xiarr, soarr, *call.args[12:14],
+                                         info_joint.ctypes.data_as(C.POINTER(C.c_int32))))
+        parts.append((g.index, call.out, call.info, None))
+        for j, i in enumerate(g.index):
+            quads[i] = tuple(None if o is None else o[j] for o in (means, covs, heldout, samples))
+            if info_joint[j]:
+                joint_bad.append((i, int(info_joint[j])))
+    obj = _batch_merge(n, parts, False, on_error)
+    if on_error == "raise" and joint_bad:
+        i, info = min(joint_bad)
+        raise PosDefException(info, index=i)
+    return (quads, obj) if return_objective else quads
+
+
+def approx_mean_and_cov_batch(approxs, fxs, ys, xs, **kw):
+    """mean_and_cov(posterior(approxs[b], fxs[b], ys[b]), xs[b]) of every problem: the (mean, cov) pairs of approx_joint_batch(what = 1 | 4)."""
+    res = approx_joint_batch(approxs, fxs, ys, xs, what=JOINT_MEAN | JOINT_COV, **kw)
+    pairs = [(q[0], q[1]) for q in (res[0] if kw.get("return_objective") else res)]
+    return (pairs, res[1]) if kw.get("return_objective") else pairs
+
+
+def approx_logpdf_heldout_batch(approxs, fxs, ys, xs, ys_heldout, *, noise=None, **kw):
+    """logpdf(posterior(approxs[b], fxs[b], ys[b])(xs[b], noise[b]), ys_heldout[b]) of every problem: approx_joint_batch(what = 8) as one array."""
+    res = approx_joint_batch(approxs, fxs, ys, xs, noise=noise, ys_heldout=ys_heldout, what=JOINT_LOGPDF, **kw)
+    hl = np.array([q[2] for q in (res[0] if kw.get("return_objective") else res)])
+    return (hl, res[1]) if kw.get("return_objective") else hl
+
+
+def approx_rand_batch(approxs, fxs, ys, xs, xi, *, noise=None, **kw):
+    """rand(posterior(approxs[b], fxs[b], ys[b])(xs[b], noise[b]), nsamp) of every problem with the caller's standard normals xi_b: approx_joint_batch(what = 16)."""
+    res = approx_joint_batch(approxs, fxs, ys, xs, noise=noise, xi=xi, what=JOINT_RAND, **kw)
+    draws = [q[3] for q in (res[0] if kw.get("return_objective") else res)]
+    return (draws, res[1]) if kw.get("return_objective") else draws
 
 
 # --------------------------------------------------------------------------------------------

@@ -5,7 +5,8 @@
 // batch_gradx_kernel, batch_gxsum_kernel) and the gradients of the predictions w.r.t. the test inputs from the strips the predict kernel leaves and the S of
 // batch_inv_kernel (batch_pgrad_kernel), the joint predictive distribution from the same strips (batch_jcov_kernel, batch_jfact_kernel); last many small
 // sparse GPs in one call (gp_vfe_batch: vfe_prelude_kernel, vfe_stream_kernel, vfe_final_kernel; gp_vfe_grad_batch: vfe_gmm_kernel, vfe_gstream_kernel,
-// vfe_gfinish_kernel behind them; each described in front of its kernels).
+// vfe_gfinish_kernel behind them; gp_vfe_predict_batch / gp_vfe_predict_grad_batch: vfe_pprep_kernel, vfe_predict_kernel; gp_vfe_joint_batch: the strip-writing
+// variant of vfe_predict_kernel, vfe_jcov_kernel and batch_jfact_kernel; each described in front of its kernels).
 //
 // ONE workgroup owns ONE problem from its inputs to its scalar: it assembles the lower triangle of K + Σy into the problem's slice of a
 // workspace (δ = y − m riding along as row np, as in the single path), factors it by a blocked right-looking Cholesky (64-column blocks:
@@ -1131,9 +1132,11 @@ __global__ __launch_bounds__(SUM ? PGNT_SUM : NT) void batch_pgrad_kernel(const 
 // joint slice in the batch_slice(ns) layout; −1: no factorisation wanted) into the workspace; cov_off (ns × ns, column-major; −1: not wanted), mean_off (the
 // mean batch_predict_kernel wrote, without the prior mean; −1 without a joint slice), samp_off (ns × nsamp; −1) and jr_off (held-out logpdf, then the failed minor
 // of the joint; −1) into the result buffer; xs_off, ysd_off (y* − m(x*); −1: zeros), nzs_off (a diagonal Σy*; −1: noise_s) and xi_off (ns × nsamp) into the input.
+// slot: where the fit left the problem's status (res[nw + slot]) — batch_jfact_kernel reads nothing else of the fit, so it serves the sparse family too
+// (gp_vfe_joint_batch: prob is the position of the problem's VfeProb, v_off the strip of B*, c_off that of C*, the mean includes the prior mean and ysd is y*).
 struct JointProb {
-    long v_off, js_off, cov_off, mean_off, samp_off, jr_off, xs_off, ysd_off, nzs_off, xi_off;
-    int prob, ns, nsp, nsamp;
+    long v_off, c_off, js_off, cov_off, mean_off, samp_off, jr_off, xs_off, ysd_off, nzs_off, xi_off;
+    int prob, ns, nsp, nsamp, slot, pad_;
     double noise_s;
 };
 static_assert(sizeof(JointProb) % 8 == 0, "the tables are packed behind double data");
@@ -1235,14 +1238,13 @@ __global__ __launch_bounds__(NT) void batch_jfact_kernel(const double* __restric
     __shared__ double dinv[BT];
     __shared__ double red[NT];
     const JointProb& J = jps[blockIdx.x];
-    const BatchProb& P = reinterpret_cast<const BatchProb*>(in)[J.prob];
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ns = J.ns, nsp = J.nsp, nsamp = J.nsamp;
     const long lds = batch_ld(nsp);
     double* __restrict__ A = ws + J.js_off;
     double* __restrict__ out = J.samp_off >= 0 ? res + J.samp_off : nullptr;
     double* __restrict__ jr = res + J.jr_off;
-    const bool fit_failed = res[nw + P.slot] != 0.0;  // the same value in every thread
+    const bool fit_failed = res[nw + J.slot] != 0.0;  // the same value in every thread
     double logdet_half = 0.0;
     const int failcol = fit_failed ? 0 : batch_chol(A, lds, ns, nsp, tid, lane, w, Ls, dinv, red, logdet_half);
     if (fit_failed || failcol) {
@@ -2099,9 +2101,10 @@ enum {
 };
 static_assert(VFE_PSEG % VT == 0, "a segment is whole tiles");
 // What a problem's predictions lay out beside VfeProb: u_off, the strip E ᵀ = L_D⁻ᵀ (np rows of ld) in the workspace; −1 where no variance is asked for or the
-// problem has no test points.
+// problem has no test points.  bs_off / cs_off (gp_vfe_joint_batch; −1 otherwise): the strips vfe_predict_kernel<false, true> stores B* and C* into, row = test
+// point — ns rounded up to 64 rows of ld doubles each, the columns [0, np) of every row written (zeros from m on and in the rows from ns on).
 struct VfePred {
-    long u_off;
+    long u_off, bs_off, cs_off;
 };
 // One segment of test points: xs_off ([d][ns], raw) and pm_off (m(x*), −1: none) into the packed input, mean_off / var_off (arrays of ns; −1: not wanted) and
 // dmean_off / dvar_off (gp_vfe_predict_grad_batch: the gradients w.r.t. the test inputs, dimension-major [d][ns]; −1: not wanted) into the result buffer; the
@@ -2146,7 +2149,24 @@ __global__ __launch_bounds__(NT) void vfe_pprep_kernel(const double* __restrict_
 //      buffer, free by then — [wave][dimension][point], 64 KB at D = 16, one side after the other — and thread (p, j) adds them in wave order and writes
 //      dmean[j, p] = −2 σ² s_p Σ,  dvar[j, p] = 4 σ² s_p Σ  (t = z_i − s ∘ x*_j).  One writer per (j, p), no atomics; every order is fixed by m alone.
 // Mean side alone: no W, no strip, no MFMA — steps 1 and 7.  The values take the steps above unchanged: they are gp_vfe_predict_batch's bits.
-// Compiler report for gfx950 (VGPR / AGPR / LDS / scratch): <false> 150 / 0 / 143 360 B / 0; <true> 256 / 0 / 147 968 B / 0.
+//
+// STRIP (gp_vfe_joint_batch, vfe_predict_kernel<false, true>) runs steps 1 – 3 as they are — the chain always, the variance never — and stores the tile of B* out of
+// the accumulators of step 2 and that of C* out of those of step 3 into the problem's two strips, TRANSPOSED: row = test point, so that vfe_jcov_kernel's tile
+// products read both operands along rows, as batch_jcov_kernel reads V.  A lane holds four consecutive pseudo-point rows of one test point: 32 contiguous bytes
+// of a strip row.  The stores go from registers to global memory and touch no LDS, so they stand behind the existing barriers of steps 2 and 3 and add none; a
+// padding test point (beyond cnt, up to the tile's 64) has a zero column of K*, so its strip rows are written as the zeros the products read.
+// Compiler report for gfx950 (VGPR / AGPR / LDS / scratch): <false> 150 / 0 / 143 360 B / 0; <true> 256 / 0 / 147 968 B / 0; <false, true> 155 / 0 / 143 360 B / 0.
+// the accumulators of vfe_tri_mm into a strip whose row 0 is the tile's first test point: strip[16 cb + r][16 bi + 4 g + e]
+__device__ __forceinline__ void vfe_strip_store(const d4_t (&acc)[4], double* __restrict__ strip, long ld, int nb16, int w, int lane) {
+    double* row = strip + (long)(16 * (w & 3) + (lane & 15)) * ld + 4 * (lane >> 4);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int bi = (w >> 2) + 2 * q;
+        if (bi < nb16)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) row[16 * bi + e] = acc[q][e];
+    }
+}
 static_assert(8 * BATCH_MAXD * VT <= VFE_MAXM * KBS, "the contraction's partial sums of one side fit in the tile buffer");
 static_assert((long)VFE_MAXM * (VFE_MAXM + 16) < (1L << 31), "the strip index of step 5 (below np · batch_ld(np)) is formed in 32 bits");
 // Step 7 of vfe_predict_kernel<true>.  On entry every wave may read KB (U* where dv); on exit KB is free again.
@@ -2196,7 +2216,7 @@ __device__ __forceinline__ void vfe_pgrad_contract(const VfeProb& P, const VfePS
     if (dv) reduce(gv, S.dvar_off, 4.0 * P.variance);
 }
 
-template <bool GRAD>
+template <bool GRAD, bool STRIP = false>
 __global__ __launch_bounds__(NT) void vfe_predict_kernel(const double* __restrict__ in, const double* __restrict__ ws, double* __restrict__ res, int nw,
                                                          const VfeProb* __restrict__ vps, const VfePred* __restrict__ pps, const VfePSeg* __restrict__ segs) {
     constexpr int WKS = GRAD ? 17 : 16, WBS = 16 * WKS;  // W's blocks: doubles between k rows, and per block
@@ -2214,7 +2234,10 @@ __global__ __launch_bounds__(NT) void vfe_predict_kernel(const double* __restric
     const int nb16 = np / 16;
     const bool want_mean = S.mean_off >= 0, want_var = S.var_off >= 0;
     const bool want_dmean = GRAD && S.dmean_off >= 0, want_dvar = GRAD && S.dvar_off >= 0;
-    const bool chain = want_var || want_dvar;  // the products of steps 2 and 3
+    const bool chain = STRIP || want_var || want_dvar;  // the products of steps 2 and 3
+    // the two strips of the problem from this segment's first row on (the memory is the workspace's: const only in this kernel's other variants)
+    double* __restrict__ Bs = STRIP ? const_cast<double*>(ws) + pps[S.prob].bs_off + (long)S.row0 * ld : nullptr;
+    double* __restrict__ Cs = STRIP ? const_cast<double*>(ws) + pps[S.prob].cs_off + (long)S.row0 * ld : nullptr;
     const double* __restrict__ z = in + P.z_off;
     const double* __restrict__ xs = in + S.xs_off;
     const double* __restrict__ U = ws + (chain ? pps[S.prob].u_off : 0);
@@ -2258,12 +2281,14 @@ __global__ __launch_bounds__(NT) void vfe_predict_kernel(const double* __restric
             __syncthreads();
             vfe_tri_store(accb, KB, nb16, w, lane);
             if (g == 0) nrm[0][w >> 2][16 * (w & 3) + r] = sq;
+            if (STRIP) vfe_strip_store(accb, Bs + (long)t0 * ld, ld, nb16, w, lane);
             __syncthreads();
             // ---- 3. C* = E B*: the column norms alone
             sq = vfe_tri_mm(acc, KB, nb16, w, lane, [&](int bi, int bk, int k) { return U[(long)(16 * bk + k) * ld + 16 * bi + r]; });
             sq += __shfl_xor(sq, 16, 64);
             sq += __shfl_xor(sq, 32, 64);
             if (g == 0) nrm[1][w >> 2][16 * (w & 3) + r] = sq;
+            if (STRIP) vfe_strip_store(acc, Cs + (long)t0 * ld, ld, nb16, w, lane);
             __syncthreads();
             // ---- 4. the variance
             if (want_var && w == 0 && valid) res[S.var_off + j] = (P.variance - (nrm[0][0][lane] + nrm[0][1][lane])) + (nrm[1][0][lane] + nrm[1][1][lane]);
@@ -2289,6 +2314,107 @@ __global__ __launch_bounds__(NT) void vfe_predict_kernel(const double* __restric
         // ---- 7. the contraction with ∂k/∂x*
         if (want_dmean || want_dvar) vfe_pgrad_contract(P, S, z, xs, KB, al, res, t0, want_dmean, want_dvar, tid, lane, w);
     }
+}
+
+// ---- the joint predictive distribution of many small sparse GPs (gp_vfe_joint_batch): vfe_jcov_kernel, then batch_jfact_kernel ----------------------------------
+// Launched behind vfe_predict_kernel<false, true>, whose two strips per problem hold B* = L_z⁻¹ K_z* and C* = L_D⁻¹ B* with row = test point.  The 64×64 tile
+// (ti >= tj) of the ns × ns matrix of one problem (GradTile: prob = its JointProb), four waves with one 32×32 wave tile each, in the contract of batch_jcov_kernel:
+//   acc = K(x*_I, x*_J) evaluated from the packed test points through LDS (the scale applied at the load, as the other sparse kernels do; identity where a point
+//   lies beyond ns), then acc −= B_I B_Jᵀ over the np / 64 blocks of the first strip and acc += C_I C_Jᵀ over those of the second, by mfma_tile_k64 in its two
+//   signs: (K** − B Bᵀ) + C Cᵀ, the order of gp_vfe_predict's bit 2 and of the oracle.
+// Stored twice: into the covariance output, the tile and its mirror image (the wave tile on the diagonal computes the pairs j <= i only: both triangles hold
+// the same bits by construction), and with Σy* on the diagonal into the joint slice (batch_slice(ns) layout) that batch_jfact_kernel factors; the workgroups of
+// the tiles (ti, 0) also write the carried row δ* = y* − mean (the mean vfe_predict_kernel wrote includes m(x*)) and the 31 zero rows behind it.
+// Placement of the operands: the two panels of a tile (2 × 64 × np doubles from each strip, np <= 128: at most 256 KB) are read as register fragments straight
+// from global memory — sixteen consecutive doubles of a strip row per lane and 64-wide k block, 128 B — and not staged in LDS: every panel is read by at most
+// ns / 64 <= 16 workgroups of the same problem, launched next to each other, so it stays in L2, and a wave reads each entry of its operands exactly once (nothing
+// to reuse inside the workgroup but the two waves that share a row or a column panel).  The LDS placement was not built and not measured.
+// Only what this call wrote is read: the strips have every row up to ns rounded up to 64 (zeros from ns on).  A failed fit: NaN in the covariance; the joint
+// slice is not written (batch_jfact_kernel does not read it then).  No atomics, no waits; every sum runs in an order np alone fixes.
+// Compiler report for gfx950 (VGPR / AGPR / LDS / scratch): 145 / 32 / 33 280 B / 0.
+__global__ __launch_bounds__(GNT) void vfe_jcov_kernel(const double* __restrict__ in, double* __restrict__ ws, double* __restrict__ res, int nw,
+                                                      const VfeProb* __restrict__ vps, const JointProb* __restrict__ jps, const GradTile* __restrict__ tiles) {
+    __shared__ double Kt[BT * BTS];
+    const GradTile& T = tiles[blockIdx.x];
+    const JointProb& J = jps[T.prob];
+    const VfeProb& P = vps[J.prob];
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ns = J.ns, nsp = J.nsp, d = P.d, nscale = P.nscale;
+    const long lds = batch_ld(nsp);
+    const bool diag = T.ti == T.tj;
+    double* __restrict__ cov = J.cov_off >= 0 ? res + J.cov_off : nullptr;
+    double* __restrict__ S = J.js_off >= 0 ? ws + J.js_off : nullptr;
+    if (res[nw + J.slot] != 0.0) {
+        for (int e = tid; e < BT * BT && cov; e += GNT) {
+            const int gi = T.ti * BT + (e >> 6), gj = T.tj * BT + (e & 63);
+            if (gi < ns && gj < ns) cov[gj + (long)gi * ns] = cov[gi + (long)gj * ns] = __builtin_nan("");
+        }
+        return;
+    }
+    if (S && T.tj == 0) {  // the carried row and the zero rows of the trailing update's 32-row tiles
+        const double* mean = res + J.mean_off;
+        for (int e = tid; e < BT * 32; e += GNT) {
+            const int r = e >> 6, j = T.ti * BT + (e & 63);
+            S[(long)(nsp + r) * lds + j] = (r == 0 && j < ns && J.ysd_off >= 0) ? in[J.ysd_off + j] - mean[j] : 0.0;
+        }
+    }
+    {  // K(x*_I, x*_J) into LDS: lane = column with its scaled inputs in registers, the four waves interleave the rows (wave-uniform: the row's inputs by scalar loads)
+        const double* __restrict__ xs = in + J.xs_off;
+        const int gj = T.tj * BT + lane;
+        double sc[BATCH_MAXD], xj[BATCH_MAXD];
+#pragma unroll
+        for (int p = 0; p < BATCH_MAXD; ++p) {
+            sc[p] = nscale == 0 ? 1.0 : P.scale[nscale == 1 ? 0 : p];
+            xj[p] = (p < d && gj < ns) ? sc[p] * xs[(long)p * ns + gj] : 0.0;
+        }
+        for (int rr = 0; rr < BT / 4; ++rr) {
+            const int li = w + 4 * rr, gi = T.ti * BT + li;
+            double v;
+            if (gi >= ns || gj >= ns) {
+                v = (gi == gj) ? 1.0 : 0.0;
+            } else {
+                double t[BATCH_MAXD];
+#pragma unroll
+                for (int p = 0; p < BATCH_MAXD; ++p) t[p] = p < d ? sc[p] * xs[(long)p * ns + gi] - xj[p] : 0.0;
+                v = vfe_kval(P, t);
+            }
+            Kt[li * BTS + lane] = v;
+        }
+    }
+    __syncthreads();
+    const int wi = w >> 1, wj = w & 1;
+    if (diag && wj > wi) return;  // the wave tile strictly above the diagonal: its mirror image computes it
+    const int i0 = T.ti * BT + 32 * wi, c0 = T.tj * BT + 32 * wj, r = lane & 15;  // c0 <= i0
+    d4_t acc[2][2];
+    acc_load(acc, Kt, 32 * wi, 32 * wj, BTS, lane);
+    if (i0 < ns) {  // beyond ns the rows of both strips are zero: the identity stays
+        const double* __restrict__ Bs = ws + J.v_off;
+        const double* __restrict__ Cs = ws + J.c_off;
+        for (int k0 = 0; k0 < P.np; k0 += BT) mfma_tile_k64<true>(acc, Bs, i0, Bs, c0, k0, P.ld, lane);
+        for (int k0 = 0; k0 < P.np; k0 += BT) mfma_tile_k64<false>(acc, Cs, i0, Cs, c0, k0, P.ld, lane);
+    }
+    const bool lower_only = diag && wi == wj;  // the wave tile on the diagonal: the pairs j <= i, mirrored
+#pragma unroll
+    for (int hi = 0; hi < 2; ++hi)
+#pragma unroll
+        for (int hj = 0; hj < 2; ++hj) {
+            const int gj = c0 + 16 * hj + r;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int gi = i0 + 16 * hi + Tr<double>::crow(lane, q);
+                if (lower_only && gj > gi) continue;
+                const double v = acc[hi][hj][q];
+                if (cov && gi < ns && gj < ns) {
+                    cov[gj + (long)gi * ns] = v;
+                    if (gi != gj) cov[gi + (long)gj * ns] = v;
+                }
+                if (S) {
+                    const double nz = (gi == gj && gi < ns) ? (J.nzs_off >= 0 ? in[J.nzs_off + gi] : J.noise_s) : 0.0;
+                    S[(long)gi * lds + gj] = v + nz;
+                    if (diag && gi != gj) S[(long)gj * lds + gi] = v;  // the whole diagonal block is loaded into LDS by the factorisation
+                }
+            }
+        }
 }
 
 }  // namespace gpmi
@@ -2674,15 +2800,15 @@ struct PointerArray {
     int arg;
     const char* msg;
 };
-// every problem's test points, Σy* (gp_joint_batch: argument 13, else NULL) and entries of `arrays`, in that order
-template <class A> int32_t check_test_points(const A& a, const gp_noise* noise_xs, std::initializer_list<PointerArray> arrays, int arg = 11) {
+// every problem's test points, Σy* (gp_joint_batch: argument 13, gp_vfe_joint_batch: 17, else NULL) and entries of `arrays`, in that order
+template <class A> int32_t check_test_points(const A& a, const gp_noise* noise_xs, std::initializer_list<PointerArray> arrays, int arg = 11, int nz_arg = 13) {
     for (int b = 0; b < a.nb; ++b) {
         const gp_points& xs = a.xsb(b);
         if (xs.n < 0) return set_arg_err(arg, "xs: n must be >= 0");
         if (xs.n == 0) continue;  // no test points: nothing of this problem's xs or outputs is touched
         RC(check_points(&xs, arg));
         if (xs.d != a.xb(b).d) return set_arg_err(arg, "xs has a different D than the training inputs");
-        if (noise_xs) RC(check_noise(&noise_xs[b], 13, true));
+        if (noise_xs) RC(check_noise(&noise_xs[b], nz_arg, true));
         for (const PointerArray& p : arrays)
             if (p.wanted && p.arr && !p.arr[b]) return set_arg_err(p.arg, p.msg);
     }
@@ -2956,7 +3082,7 @@ struct JointArgs : PredictArgs {  // what: 1 mean | 4 latent covariance | 8 held
 };
 
 // NaN in the held-out logpdf and the samples of problem b (a joint covariance that is not positive definite, or a failed fit)
-void joint_fill_nan(const JointArgs& a, int b) {
+template <class A> void joint_fill_nan(const A& a, int b) {  // JointArgs, or VfeJointArgs
     if (a.what & 8) put(a.hlogpdf_out, a.dtype, b, std::numeric_limits<double>::quiet_NaN());
     fill_nan(a.out_b(a.samples_out, 16, b), a.dtype, a.draws(b));
 }
@@ -2983,8 +3109,8 @@ int32_t run_joint_wave(gp_ctx* c, const JointArgs& a, const std::vector<KSum>& p
         const int b = idx[t];
         const long ns = a.xsb(b).n;
         JointProb j{};
-        j.prob = L.pos[t], j.ns = (int)ns, j.nsp = (int)batch_np(ns), j.nsamp = a.nsamp;
-        j.v_off = j.js_off = -1;
+        j.prob = L.pos[t], j.slot = L.pr[t].slot, j.ns = (int)ns, j.nsp = (int)batch_np(ns), j.nsamp = a.nsamp;
+        j.v_off = j.c_off = j.js_off = -1;
         j.xs_off = tp.xs_off[t], j.mean_off = tp.mean_off[t];
         j.cov_off = (a.what & 4) ? take(L.roff, ns * ns) : -1;
         j.jr_off = a.want_fact() ? take(L.roff, 2) : -1;
@@ -3540,6 +3666,22 @@ struct VfePredictArgs : VfeArgs {
     const void* pmb(int b) const { return pm ? pm[b] : nullptr; }
     void* out_b(void* const* arr, int side, int b) const { return (arr && (what & side)) ? arr[b] : nullptr; }
 };
+// gp_vfe_joint_batch: the joint side as JointArgs carries it for gp_joint_batch (what: 1 mean | 4 latent covariance | 8 held-out logpdf | 16 samples; var_out is not used)
+struct VfeJointArgs : VfePredictArgs {
+    const gp_noise* noise_xs;
+    void* const* cov_out;
+    const void* const* ys;
+    void* hlogpdf_out;
+    int32_t nsamp;
+    const void* const* xi;
+    void* const* samples_out;
+    int32_t* info_joint;
+    bool want_strips() const { return (what & 28) != 0; }  // B* and C*: everything but the mean alone
+    bool want_fact() const { return (what & 24) != 0; }
+    bool want_mean() const { return (what & 25) != 0; }  // the held-out logpdf and the samples are built on it
+    long draws(int b) const { return (what & 16) ? xsb(b).n * (long)nsamp : 0; }
+    size_t esize() const { return dtype == 0 ? 8 : 4; }
+};
 
 // the pseudo-inputs of one problem, dimension-major [d][m], scaled as the sparse path scales its inputs on the host (one product per entry)
 void pack_scaled_points(const gp_kernel& k, const gp_points& z, double* out) {
@@ -3643,6 +3785,18 @@ void vfe_test_fill(const VfePredictArgs& a, const int* idx, int nw, const std::v
     }
 }
 
+// the joint side of a gp_vfe_joint_batch wave behind that: y* (the mean on the device includes m(x*)), ξ and a diagonal Σy* of every problem that has a JointProb
+void vfe_joint_fill(const VfeJointArgs& a, const int* idx, int nw, const std::vector<JointProb>& jp, const std::vector<int>& jp_of, double* hin) {
+    for (int t = 0; t < nw; ++t) {
+        if (jp_of[t] < 0) continue;
+        const int b = idx[t];
+        const JointProb& j = jp[(size_t)jp_of[t]];
+        if (j.ysd_off >= 0) std::memcpy(hin + j.ysd_off, a.ys[b], sizeof(double) * (size_t)j.ns);
+        if (j.xi_off >= 0 && a.draws(b) > 0) std::memcpy(hin + j.xi_off, a.xi[b], sizeof(double) * (size_t)a.draws(b));
+        if (j.nzs_off >= 0) std::memcpy(hin + j.nzs_off, a.noise_xs[b].diag, sizeof(double) * (size_t)j.ns);
+    }
+}
+
 // NaN in every gradient entry of problem b (the call's dtype: a routed fp32 problem has float arrays)
 void vfe_grad_fill_nan(const VfeArgs& a, const VfeGradOut& go, int b) {
     const gp_points &x = a.xb(b), &z = a.zb(b);
@@ -3662,7 +3816,12 @@ long vfe_pseg() { return std::max<long>(VT, env_capped(getenv("GPMI_VFE_PREDICT_
 // α of every problem goes to the result buffer, whether the caller asked for it or not, and the gradient's tables and results are laid out beside the fit's.
 // With pa (gp_vfe_predict_batch: a itself) the two prediction launches instead: α likewise, the test points and prior means behind the fit's input (a shared
 // set once), the strip L_D⁻ᵀ of every problem whose variance is asked for behind its slices, mean and variance behind the fit's results.
-int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw, const VfeGradOut* go = nullptr, const VfePredictArgs* pa = nullptr) {
+// With ja (gp_vfe_joint_batch: a itself, pa the same object) the predict launches store the strips of B* and C* (vfe_predict_kernel<false, true>; the mean alone
+// takes the plain variant), and vfe_jcov_kernel over the 64×64 tiles of every problem's ns × ns matrix and batch_jfact_kernel on the joint slices follow: both
+// strips and the joint slice behind the problem's other workspace, covariance, held-out logpdf and samples behind its other results, y*, ξ and a diagonal Σy*
+// behind its other input, as run_joint_wave lays them out.
+int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw, const VfeGradOut* go = nullptr, const VfePredictArgs* pa = nullptr,
+                     const VfeJointArgs* ja = nullptr) {
     WaveLayout L;
     L.roff = 2L * nw;
     Table<VfeProb> vp;
@@ -3670,12 +3829,16 @@ int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw, const 
     Table<VfeGrad> vg;
     Table<VfePred> vq;
     Table<VfePSeg> ps;
+    Table<JointProb> jp;
+    Table<GradTile> jtiles;
     std::vector<long> first_seg((size_t)nw, -1);  // a problem's first entry of ps: its offsets
+    std::vector<int> jp_of((size_t)nw, -1);       // a problem's entry of jp
+    const bool strips = ja && ja->want_strips();
     const long pseg = vfe_pseg();
     vp.v.assign((size_t)nw, VfeProb{});
     vp.place(L);
     if (pa) {
-        vq.v.assign((size_t)nw, VfePred{-1});
+        vq.v.assign((size_t)nw, VfePred{-1, -1, -1});
         vq.place(L);
     }
     if (go) {
@@ -3718,17 +3881,40 @@ int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw, const 
         if (pa && pa->xsb(b).n > 0) {
             const gp_points& xs = pa->xsb(b);
             const long ns = xs.n;
-            if (pa->what & 2) vq.v[t].u_off = take(L.ws, (long)p.np * p.ld);
+            if ((pa->what & 2) || strips) vq.v[t].u_off = take(L.ws, (long)p.np * p.ld);
             const long xs_off = xso.place(L.off, (long)xs.d * ns), pm_off = pa->pmb(b) ? take(L.off, ns) : -1;
-            const long mean_off = pa->out_b(pa->mean_out, 1, b) ? take(L.roff, ns) : -1, var_off = pa->out_b(pa->var_out, 2, b) ? take(L.roff, ns) : -1;
+            const long mean_off = (pa->out_b(pa->mean_out, 1, b) || (ja && ja->want_mean())) ? take(L.roff, ns) : -1, var_off = pa->out_b(pa->var_out, 2, b) ? take(L.roff, ns) : -1;
             const long dmean_off = pa->out_b(pa->dmean_out, 1, b) ? take(L.roff, ns * xs.d) : -1, dvar_off = pa->out_b(pa->dvar_out, 2, b) ? take(L.roff, ns * xs.d) : -1;
             first_seg[t] = (long)ps.v.size();
             for (long r0 = 0; r0 < ns; r0 += pseg)
                 ps.v.push_back(VfePSeg{xs_off, pm_off, mean_off, var_off, dmean_off, dvar_off, t, (int)ns, (int)r0, (int)std::min<long>(pseg, ns - r0)});
+            if (strips) {
+                const long rows = (ns + VT - 1) / VT * VT;  // the predict kernel writes whole tiles of 64 test points
+                JointProb j{};
+                j.prob = j.slot = t, j.ns = (int)ns, j.nsp = (int)batch_np(ns), j.nsamp = ja->nsamp;
+                j.v_off = vq.v[t].bs_off = take(L.ws, rows * p.ld);
+                j.c_off = vq.v[t].cs_off = take(L.ws, rows * p.ld);
+                j.js_off = ja->want_fact() ? take(L.ws, batch_slice(ns)) : -1;
+                j.xs_off = xs_off, j.mean_off = mean_off;
+                j.cov_off = (ja->what & 4) ? take(L.roff, ns * ns) : -1;
+                j.jr_off = ja->want_fact() ? take(L.roff, 2) : -1;
+                j.samp_off = (ja->what & 16) ? take(L.roff, ja->draws(b)) : -1;
+                j.ysd_off = (ja->what & 8) ? take(L.off, ns) : -1;
+                j.xi_off = (ja->what & 16) ? take(L.off, ja->draws(b)) : -1;
+                const gp_noise* nz = ja->noise_xs ? &ja->noise_xs[b] : nullptr;
+                j.noise_s = nz ? nz->s : 0.0;
+                j.nzs_off = (nz && nz->kind == 1) ? take(L.off, ns) : -1;
+                jp_of[t] = (int)jp.v.size();
+                jp.v.push_back(j);
+                for (int ti = 0; ti < j.nsp / BT; ++ti)
+                    for (int tj = 0; tj <= ti; ++tj) jtiles.v.push_back(GradTile{jp_of[t], ti, tj, 0});
+            }
         }
     }
     sg.place(L);
     ps.place(L);
+    jp.place(L);
+    jtiles.place(L);
     WaveMem m(c);
     RC(m.alloc(L.off, L.ws, L.roff));
     vp.fill(m);
@@ -3736,8 +3922,11 @@ int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw, const 
     vg.fill(m);
     vq.fill(m);
     ps.fill(m);
+    jp.fill(m);
+    jtiles.fill(m);
     vfe_wave_fill(a, idx, nw, vp.v, m.hin);
     if (pa) vfe_test_fill(*pa, idx, nw, ps.v, first_seg, m.hin);
+    if (ja) vfe_joint_fill(*ja, idx, nw, jp.v, jp_of, m.hin);
     RC(run_drained(c, [&]() -> int32_t {
         RC(m.upload());
         RC(launch(m, vfe_prelude_kernel, nw, NT, nw, vp.dev(m)));
@@ -3749,14 +3938,16 @@ int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw, const 
             RC(launch(m, vfe_gfinish_kernel, nw, NT, nw, vp.dev(m), vg.dev(m)));
         }
         if (pa && !ps.v.empty()) {
-            if (pa->what & 2) RC(launch(m, vfe_pprep_kernel, nw, NT, nw, vp.dev(m), vq.dev(m)));
+            if ((pa->what & 2) || strips) RC(launch(m, vfe_pprep_kernel, nw, NT, nw, vp.dev(m), vq.dev(m)));
             for (size_t s0 = 0; s0 < ps.v.size(); s0 += VFE_PRED_LAUNCH_SEGS)
-                RC(launch(m, pa->grad ? vfe_predict_kernel<true> : vfe_predict_kernel<false>, std::min<size_t>(VFE_PRED_LAUNCH_SEGS, ps.v.size() - s0), NT, nw,
-                          vp.dev(m), vq.dev(m), ps.dev(m, s0)));
+                RC(launch(m, strips ? vfe_predict_kernel<false, true> : pa->grad ? vfe_predict_kernel<true> : vfe_predict_kernel<false>,
+                          std::min<size_t>(VFE_PRED_LAUNCH_SEGS, ps.v.size() - s0), NT, nw, vp.dev(m), vq.dev(m), ps.dev(m, s0)));
+            if (!jtiles.v.empty()) RC(launch(m, vfe_jcov_kernel, jtiles.v.size(), GNT, nw, vp.dev(m), jp.dev(m), jtiles.dev(m)));
+            if (ja && ja->want_fact() && !jp.v.empty()) RC(launch(m, batch_jfact_kernel, jp.v.size(), NT, nw, jp.dev(m)));
         }
         return m.download_and_sync();
     }));
-    (go ? c->vfe_grad_batch_problems : !pa ? c->vfe_batch_problems : pa->grad ? c->vfe_predict_grad_batch_problems : c->vfe_predict_batch_problems) += nw;
+    (go ? c->vfe_grad_batch_problems : !pa ? c->vfe_batch_problems : ja ? c->vfe_joint_batch_problems : pa->grad ? c->vfe_predict_grad_batch_problems : c->vfe_predict_batch_problems) += nw;
     for (int t = 0; t < nw; ++t) {
         const int b = idx[t];
         const VfeProb& p = vp.v[t];
@@ -3778,6 +3969,16 @@ int32_t run_vfe_wave(gp_ctx* c, const VfeArgs& a, const int* idx, int nw, const 
                 if (failed) fill_nan(out, 0, (long)s.ns * p.d);
                 else grad_to_layout<double>(pa->xsb(b).layout, s.ns, p.d, m.hout + (side == 1 ? s.dmean_off : s.dvar_off), s.ns, out);
             }
+        }
+        if (ja && ja->info_joint) ja->info_joint[b] = 0;
+        if (jp_of[t] >= 0) {  // the kernels wrote the NaN of a failed fit, and of a failed joint factorisation, themselves
+            const JointProb& j = jp.v[(size_t)jp_of[t]];
+            if (void* co = ja->out_b(ja->cov_out, 4, b)) std::memcpy(co, m.hout + j.cov_off, sizeof(double) * (size_t)j.ns * j.ns);
+            if (j.jr_off >= 0) {
+                if (ja->what & 8) ((double*)ja->hlogpdf_out)[b] = m.hout[j.jr_off];
+                if (ja->info_joint) ja->info_joint[b] = (int32_t)m.hout[j.jr_off + 1];
+            }
+            if (void* so = ja->out_b(ja->samples_out, 16, b)) std::memcpy(so, m.hout + j.samp_off, sizeof(double) * (size_t)ja->draws(b));
         }
         if (!go) continue;
         if (m.hout[nw + t] != 0.0) {  // failure is data: the gradient kernels skipped the problem
@@ -3931,6 +4132,90 @@ int32_t vfe_predict_batch_impl(gp_ctx* c, VfePredictArgs& a) {
                         : gp_vfe_predict(h, &xs, a.pmb(b), a.what, a.out_b(a.mean_out, 1, b), a.out_b(a.var_out, 2, b), nullptr);
         if (h) (void)gp_vfe_free(h);
         RC(routed_done(a, b, rc, [&] { vfe_predict_fill_nan(a, b); }));
+    }
+    return 0;
+}
+
+// ---- gp_vfe_joint_batch ------------------------------------------------------------------------------------------------------------------------------------
+// the test side of gp_vfe_joint_batch that needs neither the handle nor a device (arguments 14 … 25), in the order of joint_batch_impl's checks
+int32_t check_vfe_joint_head(const VfeJointArgs& a) {
+    RC(check_test_head(a, 14));
+    if (a.what <= 0 || (a.what & ~29)) return set_arg_err(18, "what must be a combination of 1|4|8|16 (marginal variances: gp_vfe_predict_batch)");
+    if ((a.what & 1) && !a.mean_out) return set_arg_err(19, "mean_out is NULL");
+    if ((a.what & 4) && !a.cov_out) return set_arg_err(20, "cov_out is NULL");
+    if ((a.what & 8) && !a.ys) return set_arg_err(21, "ys array is NULL");
+    if ((a.what & 8) && !a.hlogpdf_out) return set_arg_err(22, "hlogpdf_out is NULL");
+    if (a.nsamp < 0) return set_arg_err(23, "nsamp must be >= 0");
+    if ((a.what & 16) && a.nsamp > 0 && !a.xi) return set_arg_err(24, "xi array is NULL");
+    if ((a.what & 16) && a.nsamp > 0 && !a.samples_out) return set_arg_err(25, "samples_out is NULL");
+    return 0;
+}
+
+// doubles problem b alone adds to the workspace (the strip L_D⁻ᵀ, the strips of B* and C*, the joint slice) and to the page-locked staging of a joint wave
+// (what vfe_predict_io counts for the mean, then y*, ξ and a diagonal Σy* going in, covariance, status pair and draws coming back, and the tile table)
+long vfe_joint_ws(const VfeJointArgs& a, int b) {
+    const long ns = a.xsb(b).n, np = batch_np(a.zb(b).n);
+    if (ns == 0 || !a.want_strips()) return 0;
+    return np * batch_ld(np) + 2 * ((ns + VT - 1) / VT * VT) * batch_ld(np) + (a.want_fact() ? batch_slice(ns) : 0);
+}
+long vfe_joint_io(const VfeJointArgs& a, int b) {
+    const gp_points& xs = a.xsb(b);
+    const long ns = xs.n, nseg = (ns + vfe_pseg() - 1) / vfe_pseg(), nts = batch_np(ns) / BT;
+    return a.zb(b).n + (a.nxs == 1 ? 0 : (long)xs.d * ns) + (a.pmb(b) ? ns : 0) + nseg * (long)(sizeof(VfePSeg) / 8) + 3 * ns + ((a.what & 4) ? ns * ns : 0) + 2 * a.draws(b) + 2 +
+           (long)(sizeof(JointProb) / 8) + nts * (nts + 1) / 2 * (long)(sizeof(GradTile) / 8);
+}
+
+// gp_vfe_joint_batch: the body of vfe_predict_batch_impl with the joint side behind the predictions — the strip-writing predict kernel, vfe_jcov_kernel and
+// batch_jfact_kernel per wave; gp_vfe_fit + gp_vfe_predict (bits 0 and 2) + gp_vfe_logpdf + gp_vfe_rand + gp_vfe_free for the rest
+int32_t vfe_joint_batch_impl(gp_ctx* c, VfeJointArgs& a) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    if (a.nb < 0) return set_arg_err(2, "nb must be >= 0");
+    if (a.nb == 0) return 0;
+    RC(check_vfe_args(a, 0, 27));
+    const bool sampling = (a.what & 16) && a.nsamp > 0;
+    RC(check_test_points(a, a.noise_xs, {{a.mean_out, (a.what & 1) != 0, 19, "a mean_out pointer is NULL"}, {a.cov_out, (a.what & 4) != 0, 20, "a cov_out pointer is NULL"},
+                                         {a.ys, (a.what & 8) != 0, 21, "a ys pointer is NULL"}, {a.xi, sampling, 24, "a xi pointer is NULL"},
+                                         {a.samples_out, sampling, 25, "a samples_out pointer is NULL"}}, 15, 17));
+    // which path serves a problem depends on that problem alone: gp_vfe_batch's routing under the joint limits, and a Σy* the kernels take
+    const long max_n = env_capped(getenv("GPMI_VFE_JOINT_BATCH_MAX_N"), GPMI355_VFE_JOINT_BATCH_MAX_N, VFE_KERNEL_MAX_N);
+    const long max_ns = env_capped(getenv("GPMI_VFE_JOINT_BATCH_MAX_NS"), GPMI355_VFE_JOINT_BATCH_MAX_NS);
+    std::vector<int> mine, routed;
+    for (int b = 0; b < a.nb; ++b) {
+        const bool nz_ok = !a.noise_xs || a.xsb(b).n == 0 || a.noise_xs[b].kind <= 1;
+        (vfe_batch_takes(a, b, max_n) && a.xsb(b).n <= max_ns && nz_ok ? mine : routed).push_back(b);
+    }
+    RC(for_each_wave(c, mine,
+                     [&](int b) {  // the staging bound covers what goes in and what comes back
+                         return WaveCost{sizeof(double) * (size_t)(vfe_ws(a, b) + vfe_joint_ws(a, b)), 0, sizeof(double) * (size_t)(vfe_in(a, b) + vfe_joint_io(a, b))};
+                     },
+                     [&](const int* idx, int nw) { return run_vfe_wave(c, a, idx, nw, nullptr, &a, &a); }));
+    // everything else: the single-path sequence, one problem at a time, after the lock is released (as batch_impl does)
+    gd.lk.unlock();
+    const gp_noise zero_noise{0, 0.0, nullptr};
+    for (int b : routed) {
+        const gp_points& xs = a.xsb(b);
+        const gp_noise* nz = a.noise_xs ? &a.noise_xs[b] : &zero_noise;
+        gp_vfe* h = nullptr;
+        int32_t rj = 0;
+        int32_t rc = gp_vfe_fit(c, &a.k[b], &a.xb(b), &a.zb(b), &a.noise[b], a.jitter[b], a.mb(b), a.yb(b), a.approx[b], xs.n > 0 ? &h : nullptr, logpdf_slot(a, b));
+        if (rc == 0 && h && (a.what & 5)) rc = gp_vfe_predict(h, &xs, a.pmb(b), a.what & 5, a.out_b(a.mean_out, 1, b), nullptr, a.out_b(a.cov_out, 4, b));
+        if (rc == 0 && h && (a.what & 8)) {
+            rj = gp_vfe_logpdf(h, &xs, a.pmb(b), nz, a.ys[b], xs.n, 1, (char*)a.hlogpdf_out + a.esize() * (size_t)b);
+            if (rj < 0) rc = rj;
+        }
+        if (rc == 0 && rj == 0 && h && a.draws(b) > 0) {
+            rj = gp_vfe_rand(h, &xs, a.pmb(b), nz, a.xi[b], a.nsamp, a.samples_out[b]);
+            if (rj < 0) rc = rj;
+        }
+        if (h) (void)gp_vfe_free(h);
+        RC(routed_done(a, b, rc, [&] {
+            if (xs.n <= 0) return;
+            fill_nan(a.out_b(a.mean_out, 1, b), a.dtype, xs.n);
+            fill_nan(a.out_b(a.cov_out, 4, b), a.dtype, xs.n * xs.n);
+        }));
+        if (a.info_joint) a.info_joint[b] = rc == 0 ? rj : 0;
+        if ((rc > 0 || rj > 0) && xs.n > 0) joint_fill_nan(a, b);
     }
     return 0;
 }
@@ -4126,5 +4411,18 @@ int32_t gp_vfe_predict_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, i
                      nxs, xs, prior_mean_xs_or_null, what, mean_out_or_null, var_out_or_null, true, dmean_out_or_null, dvar_out_or_null};
     if (nb > 0) RC(check_vfe_test_head(a));
     return vfe_predict_batch_impl(ctx, a);
+}
+
+int32_t gp_vfe_joint_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, int32_t nz, const gp_points* z,
+                           const gp_noise* noise, const double* jitter, const void* const* mean_or_null, int32_t ny, const void* const* y,
+                           const int32_t* approx, int32_t nxs, const gp_points* xs, const void* const* prior_mean_xs_or_null,
+                           const gp_noise* noise_xs_or_null, int32_t what, void* const* mean_out_or_null, void* const* cov_out_or_null,
+                           const void* const* ys_or_null, void* hlogpdf_out_or_null, int32_t nsamp, const void* const* xi_or_null,
+                           void* const* samples_out_or_null, void* objective_out_or_null, int32_t* info_out, int32_t* info_joint_out_or_null) {
+    VfeJointArgs a{{{base_args(nb, k, nx, x, noise, mean_or_null, ny, y, objective_out_or_null, info_out), nz, z, jitter, approx, nullptr},
+                    nxs, xs, prior_mean_xs_or_null, what, mean_out_or_null, nullptr},
+                   noise_xs_or_null, cov_out_or_null, ys_or_null, hlogpdf_out_or_null, nsamp, xi_or_null, samples_out_or_null, info_joint_out_or_null};
+    if (nb > 0) RC(check_vfe_joint_head(a));
+    return vfe_joint_batch_impl(ctx, a);
 }
 }

@@ -193,6 +193,7 @@ struct gp_ctx {
     int64_t batch_gradx_problems = 0;          // problems served by batch_gradx_kernel of gp_logpdf_grad_batch_x / _sum_x (batch.hip): read-only "batch_gradx_kernel_problems"
     int64_t vfe_grad_batch_problems = 0;       // problems served by the kernels of gp_vfe_grad_batch (batch.hip): read-only "vfe_grad_batch_kernel_problems"
     int64_t vfe_predict_batch_problems = 0;    // problems served by the kernels of gp_vfe_predict_batch (batch.hip): read-only "vfe_predict_batch_kernel_problems"
+    int64_t vfe_joint_batch_problems = 0;      // problems served by the kernels of gp_vfe_joint_batch (batch.hip): read-only "vfe_joint_batch_kernel_problems"
     int64_t vfe_predict_grad_batch_problems = 0;  // problems served by the kernels of gp_vfe_predict_grad_batch (batch.hip): read-only "vfe_predict_grad_batch_kernel_problems"
     int64_t vfe_batch_problems = 0;           // problems served by the kernels of gp_vfe_batch (batch.hip): read-only "vfe_batch_kernel_problems"
     int64_t batch_loo_problems = 0;            // problems served by batch_loo_kernel of gp_loo_batch / _sum (batch.hip): read-only "batch_loo_kernel_problems"

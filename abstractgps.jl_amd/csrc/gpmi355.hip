@@ -2662,6 +2662,10 @@ int32_t gp_ctx_get_param(gp_ctx* c, const char* name, int64_t* out) {
         *out = c->vfe_predict_grad_batch_problems;
         return 0;
     }
+    if (!strcmp(name, "vfe_joint_batch_kernel_problems")) {  // the same for the kernels of gp_vfe_joint_batch
+        *out = c->vfe_joint_batch_problems;
+        return 0;
+    }
     if (!strcmp(name, "cols_kernel_calls")) {  // kmul launches served by gp_posterior_predict_cols / gp_vfe_predict_cols since the ctx was created
         *out = c->cols_kernel_calls;
         return 0;

@@ -1966,6 +1966,108 @@ function approx_mean_and_var_grad_batch(approxs::AbstractVector, fxs::AbstractVe
     return return_objective ? (quads, obj) : quads
 end
 
+# ---- the joint predictive distribution of many small sparse GPs in one call: gp_vfe_joint_batch ----------------------------------------------------
+# approx_joint_batch(approxs, fxs, ys, xs; noise, ys_heldout, xi, what): per problem what posterior(approxs[b], fxs[b], ys[b])(xs[b], noise[b]) answers
+# (:183-217; src/finite_gp_projection.jl:133-136, 233-237, 306-311) — the vector of (mean, cov, heldout_logpdf, samples) tuples in the caller's order, `nothing`
+# for what was not asked for, the objectives behind it with return_objective — in ONE library call per (context, eltype) group.  approxs, fxs, ys, xs, sharing
+# rules and accelerated forms as approx_mean_and_var_batch; noise, ys_heldout, xi, what and on_error as joint_batch.
+function approx_joint_batch(approxs::AbstractVector, fxs::AbstractVector{<:FiniteGP{<:HipGP}}, ys, xs::AbstractVector; noise=nothing, ys_heldout=nothing,
+                            xi=nothing, what::Integer=1 | 4 | (ys_heldout === nothing ? 0 : 8) | (xi === nothing ? 0 : 16), return_objective::Bool=false,
+                            on_error::Symbol=:raise)
+    on_error in (:raise, :nan) || throw(ArgumentError("on_error must be :raise or :nan"))
+    (what > 0 && (what & ~29) == 0) || throw(ArgumentError("what must be a combination of 1 (mean), 4 (cov), 8 (held-out logpdf) and 16 (samples)"))
+    ((what & 8) == 0 || ys_heldout !== nothing) || throw(ArgumentError("the held-out logpdf needs ys_heldout"))
+    ((what & 16) == 0 || xi !== nothing) || throw(ArgumentError("samples need xi, the standard normals of every problem"))
+    nb = length(approxs)
+    fv = length(fxs) == 1 ? fill(fxs[1], nb) : fxs
+    yv = (ys isa AbstractVector{<:Real}) ? fill(ys, nb) : (length(ys) == 1 ? fill(ys[1], nb) : collect(ys))
+    xv = length(xs) == 1 ? fill(xs[1], nb) : xs
+    nzv = (noise === nothing || noise isa Real) ? fill(noise, nb) : collect(noise)
+    (length(fv) == nb && length(yv) == nb && length(xv) == nb && length(nzv) == nb) ||
+        throw(DimensionMismatch("$(nb) approximations, $(length(fv)) FiniteGPs, $(length(yv)) observation vectors, $(length(xv)) sets of test points, $(length(nzv)) entries of noise"))
+    nsamp = (what & 16) != 0 && nb > 0 ? size(xi[1], 2) : 0
+    obj = fill(NaN, nb)
+    info = zeros(Int32, nb)
+    infoj = zeros(Int32, nb)
+    quads = Vector{Any}(nothing, nb)
+    args = Vector{Any}(nothing, nb)
+    groups = Dict{Any,Vector{Int}}()
+    for b in 1:nb
+        ap, fx, y = approxs[b], fv[b], yv[b]
+        @assert ap.fz.f === fx.f
+        length(fx) == length(y) || throw(DimensionMismatch("problem $(b): length(fx) != length(y)"))
+        a = marshal(fx, eltype(y))
+        (a === nothing || haskey(a, :ks) || is_dense(a.cn) || !(ap.fz.Σy isa Diagonal{<:Any,<:Fill}) || joint_noise(nzv[b], length(xv[b]), a.T) === nothing) &&
+            throw(ArgumentError("problem $(b): kernel / noise / pseudo-input form is not accelerated"))
+        ((what & 8) == 0 || length(ys_heldout[b]) == length(xv[b])) ||
+            throw(DimensionMismatch("problem $(b): $(length(xv[b])) test points but ys_heldout has $(length(ys_heldout[b])) entries"))
+        pz = points(ap.fz.x, a.T)
+        args[b] = (a=a, zbuf=pz[1], cz=pz[2], jitter=Float64(FillArrays.getindex_value(ap.fz.Σy.diag)))
+        push!(get!(groups, (fx.f.ctx, a.T), Int[]), b)
+    end
+    for ((ctx, Tg), idx) in groups
+        g = length(idx)
+        nx = all(b -> fv[b].x === fv[idx[1]].x, idx) ? 1 : g
+        nz = all(b -> approxs[b].fz.x === approxs[idx[1]].fz.x, idx) ? 1 : g
+        ny = all(b -> yv[b] === yv[idx[1]], idx) ? 1 : g
+        nxs = all(b -> xv[b] === xv[idx[1]], idx) ? 1 : g
+        cks = [args[b].a.ck for b in idx]
+        cxs = [args[b].a.cx for b in idx[1:nx]]
+        czs = [args[b].cz for b in idx[1:nz]]
+        cns = [args[b].a.cn for b in idx]
+        jit = Float64[args[b].jitter for b in idx]
+        kinds = Int32[approxs[b] isa VFE ? 0 : 1 for b in idx]
+        ybufs = [Vector{Tg}(yv[b]) for b in idx[1:ny]]
+        yptrs = Ptr{Cvoid}[pointer(v) for v in ybufs]
+        mptrs = Ptr{Cvoid}[args[b].a.m === nothing ? C_NULL : pointer(args[b].a.m) for b in idx]
+        xsp = [points(xv[b], Tg) for b in idx[1:nxs]]  # (buffer, CPoints)
+        cxss = [p[2] for p in xsp]
+        pms = [prior_mean(fv[b].f.gp, xv[b], Tg) for b in idx]  # m(x*) on the host; nothing = ZeroMean
+        pmptrs = Ptr{Cvoid}[m === nothing ? C_NULL : pointer(m) for m in pms]
+        nzs = [joint_noise(nzv[b], length(xv[b]), Tg) for b in idx]  # (buffer, CNoise)
+        cnzs = [p[2] for p in nzs]
+        mbufs = [Vector{Tg}(undef, (what & 1) != 0 ? length(xv[b]) : 0) for b in idx]
+        cbufs = [Matrix{Tg}(undef, ((what & 4) != 0 ? (length(xv[b]), length(xv[b])) : (0, 0))...) for b in idx]
+        ysbufs = [(what & 8) != 0 ? Vector{Tg}(ys_heldout[b]) : Tg[] for b in idx]
+        xibufs = [(what & 16) != 0 ? Matrix{Tg}(reshape(xi[b], length(xv[b]), nsamp)) : Matrix{Tg}(undef, 0, 0) for b in idx]
+        sbufs = [Matrix{Tg}(undef, ((what & 16) != 0 ? (length(xv[b]), nsamp) : (0, 0))...) for b in idx]
+        moptrs = Ptr{Cvoid}[pointer(v) for v in mbufs]
+        coptrs = Ptr{Cvoid}[pointer(v) for v in cbufs]
+        ysptrs = Ptr{Cvoid}[pointer(v) for v in ysbufs]
+        xiptrs = Ptr{Cvoid}[pointer(v) for v in xibufs]
+        soptrs = Ptr{Cvoid}[pointer(v) for v in sbufs]
+        hl = zeros(Tg, g)
+        out = Vector{Tg}(undef, g)
+        inf = zeros(Int32, g)
+        infj = zeros(Int32, g)
+        GC.@preserve args cks cxs czs cns jit kinds ybufs yptrs mptrs xsp cxss pms pmptrs nzs cnzs mbufs cbufs ysbufs xibufs sbufs moptrs coptrs ysptrs xiptrs soptrs hl out inf infj begin
+            check(ccall((:gp_vfe_joint_batch, libgpmi355), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{CKernel}, Int32, Ptr{CPoints}, Int32, Ptr{CPoints}, Ptr{CNoise}, Ptr{Float64}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Ptr{Cvoid}},
+                    Ptr{Int32}, Int32, Ptr{CPoints}, Ptr{Ptr{Cvoid}}, Ptr{CNoise}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Int32,
+                    Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}),
+                ctx.handle, g, cks, nx, cxs, nz, czs, cns, jit, mptrs, ny, yptrs, kinds, nxs, cxss, pmptrs, cnzs, what,
+                (what & 1) != 0 ? pointer(moptrs) : C_NULL, (what & 4) != 0 ? pointer(coptrs) : C_NULL, (what & 8) != 0 ? pointer(ysptrs) : C_NULL,
+                (what & 8) != 0 ? pointer(hl) : C_NULL, nsamp, (what & 16) != 0 ? pointer(xiptrs) : C_NULL, (what & 16) != 0 ? pointer(soptrs) : C_NULL,
+                out, inf, infj))
+        end
+        for (j, b) in enumerate(idx)
+            obj[b] = out[j]
+            info[b] = inf[j]
+            infoj[b] = infj[j]
+            quads[b] = ((what & 1) != 0 ? mbufs[j] : nothing, (what & 4) != 0 ? cbufs[j] : nothing, (what & 8) != 0 ? hl[j] : nothing,
+                        (what & 16) != 0 ? sbufs[j] : nothing)
+        end
+    end
+    bad = findfirst(!iszero, info)
+    on_error === :raise && bad !== nothing && throw(BatchPosDefException(Int(info[bad]), bad))
+    badj = findfirst(!iszero, infoj)
+    on_error === :raise && badj !== nothing && throw(BatchPosDefException(Int(infoj[badj]), badj))
+    return return_objective ? (quads, obj) : quads
+end
+approx_mean_and_cov_batch(approxs, fxs, ys, xs; kw...) = (r = approx_joint_batch(approxs, fxs, ys, xs; what=5, kw...); q = r isa Tuple ? r[1] : r; p = [(t[1], t[2]) for t in q]; r isa Tuple ? (p, r[2]) : p)
+approx_logpdf_heldout_batch(approxs, fxs, ys, xs, ys_heldout; kw...) = (r = approx_joint_batch(approxs, fxs, ys, xs; ys_heldout=ys_heldout, what=8, kw...); q = r isa Tuple ? r[1] : r; p = [t[3] for t in q]; r isa Tuple ? (p, r[2]) : p)
+approx_rand_batch(approxs, fxs, ys, xs, xi; kw...) = (r = approx_joint_batch(approxs, fxs, ys, xs; xi=xi, what=16, kw...); q = r isa Tuple ? r[1] : r; p = [t[4] for t in q]; r isa Tuple ? (p, r[2]) : p)
+
 # ---- value + gradient of the sparse objective: one fit + one backward pass over the retained observations (gp_vfe_grad) ------------------
 # The reference's users maximise `elbo(VFE(f(z, jitter)), f(x, Σy), y)` over kernel parameters and pseudo-points by AD / finite differences
 # (examples/0-intro-1d/script.jl:385-394); the ccall is opaque to AD, so the accelerated objective carries its own pullback.

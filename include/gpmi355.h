@@ -313,6 +313,7 @@ int32_t gp_ctx_destroy(gp_ctx* ctx);
  *   "vfe_grad_batch_kernel_problems"  read-only: the same for the kernels of gp_vfe_grad_batch
  *   "vfe_predict_batch_kernel_problems"  read-only: the same for the kernels of gp_vfe_predict_batch
  *   "vfe_predict_grad_batch_kernel_problems"  read-only: the same for the kernels of gp_vfe_predict_grad_batch
+ *   "vfe_joint_batch_kernel_problems"  read-only: the same for the kernels of gp_vfe_joint_batch
  *   "cols_kernel_calls", "cols_kernel_splits"   read-only: kmul launches gp_posterior_predict_cols has served on this ctx since it was created, and the workgroups
  *                    along the training range of the last of them (1 = unsplit, 0 = none yet): which path ran, for tests and measurements */
 /* The defaults above, machine-readable (single-device parameters; gp_ctx_get_param reads the same names): the test-suite asserts before
@@ -1112,6 +1113,66 @@ int32_t gp_vfe_predict_grad_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, i
                                   const int32_t* approx, int32_t nxs, const gp_points* xs, const void* const* prior_mean_xs_or_null, int32_t what,
                                   void* const* mean_out_or_null, void* const* var_out_or_null, void* const* dmean_out_or_null, void* const* dvar_out_or_null,
                                   void* objective_out_or_null, int32_t* info_out);
+
+/* gp_vfe_joint_batch: the JOINT predictive distribution of nb independent VFE / DTC problems at their test points in one call — the latent covariance, the
+ * held-out log density and joint samples, what gp_joint_batch returns for exact GPs (a loop of gp_vfe_fit + gp_vfe_predict(what = 5) + gp_vfe_logpdf +
+ * gp_vfe_rand + gp_vfe_free otherwise: four whole-chip launches per problem and an M × ns solve from global memory each time).  Per problem the semantics are
+ * those of that sequence (src/sparse_approximations.jl:183-217; src/finite_gp_projection.jl:133-136, 233-237, 306-311).
+ *   The arguments up to `approx` exactly as gp_vfe_predict_batch; the test side, the outputs and `what` exactly as gp_joint_batch: noise_xs_or_null: nb entries
+ *   Σy*_b, NULL = zero; what: bit 0 the mean, bit 2 the latent covariance K** − B*ᵀB* + C*ᵀC* (B* = L_z⁻¹ K_z*, C* = L_D⁻¹ B*; no Σy* added), bit 3 the held-out
+ *   logpdf, bit 4 samples — bit 1, every other bit and 0 are argument errors; cov_out: ns_b × ns_b entries, column-major, both triangles written and exactly
+ *   symmetric; samples: out[:, s] = mean + L* xi[:, s] with L* L*ᵀ = C* + Σy* (nsamp >= 0).  ns_b = 0 is legal and touches nothing of that problem but its
+ *   objective and info entries.  objective_out_or_null: the ELBO (VFE) or the DTC log evidence, as gp_vfe_batch; info_out: the fit; info_joint_out_or_null:
+ *   the order of the first leading minor of C*_b + Σy*_b that is not positive, or 0.
+ * Failure is data, exactly as in gp_joint_batch: a failed fit gives NaN in every output of that problem and sets info_out[b]; a failed joint factorisation
+ * gives NaN in that problem's held-out logpdf and samples only and reports its minor in info_joint_out[b]; other problems are never touched.  The return value
+ * reports argument errors only (nb = 0 returns 0); those of the test side (arguments 14 … 25) are reported before the handle is looked at.
+ * Eligibility as gp_vfe_batch (fp64, M <= 128, D <= 16, noise kind 0 / 1) with n_b <= GPMI355_VFE_JOINT_BATCH_MAX_N, ns_b <= GPMI355_VFE_JOINT_BATCH_MAX_NS
+ * and a Σy*_b that is absent or of kind 0 / 1.  The fit's three launches and vfe_pprep_kernel run unchanged (the objective is bit-equal to gp_vfe_batch's, the
+ * mean to gp_vfe_predict_batch's); behind them, per wave (csrc/batch.hip):
+ *   vfe_predict_kernel<false, true>  the compile-time variant of the predict kernel that also stores the tile of B* out of the accumulators of step 2 and
+ *                       that of C* out of those of step 3 into two strips per problem, row = test point (ns_b rounded up to 64 rows of M rounded up to 64,
+ *                       plus 16, doubles; zeros in the padding), a lane's four accumulator entries being 32 consecutive bytes of a strip row.  The stores
+ *                       go from registers to global memory behind the existing barriers: no barrier is added, and the other two variants keep their code;
+ *   vfe_jcov_kernel     one workgroup per 64×64 tile (ti >= tj) of a problem's ns_b × ns_b matrix, four waves with a 32×32 wave tile each: K(x*_I, x*_J)
+ *                       from the packed test points through LDS (scale applied at the load; identity beyond ns_b), then acc −= B_I B_Jᵀ and acc += C_I C_Jᵀ
+ *                       by v_mfma_f64_16x16x4_f64 over the k blocks of the two strips — (K** − B Bᵀ) + C Cᵀ, the single path's and the oracle's order;
+ *                       the diagonal wave tile computes the pairs j <= i and mirrors them; the tile goes to the covariance (with its mirror image) and,
+ *                       with Σy* on the diagonal, to the joint slice, the (ti, 0) workgroups writing the carried row δ* = y* − mean;
+ *   batch_jfact_kernel  gp_joint_batch's kernel, unchanged but for where it finds the fit's status (a slot in its own table, so that it needs no
+ *                       descriptor of the exact family): the blocked Cholesky of the joint slice, the logpdf off the carried row, the samples.
+ * The operand panels of a covariance tile (2 × 64 × np doubles from each strip) are read as register fragments from global memory: a problem's two strips are
+ * at most 2 MB, read by at most 16 × 17 / 2 workgroups launched side by side, and stay in L2; staging them in LDS once per workgroup was not built and not
+ * measured.  No floating-point atomics, no waits between workgroups; every sum runs in an order the problem's own sizes fix: a problem's outputs are the same
+ * bits alone, in any batch and on repetition.  Every other problem (fp32, M > 128, D > 16, ns_b or n_b above the thresholds, a dense Σy*) is answered inside the
+ * call by the single-path sequence above; which path serves a problem depends on that problem alone.  The read-only ctx parameter
+ * "vfe_joint_batch_kernel_problems" counts the problems the kernels served.
+ * Against the oracle's vfe_posterior(...).mean_and_cov, logpdf and rand_from over the tables of tests/test_gpu_vfe_joint_batch.py (M = 1 … 128, ns = 0 … 513,
+ * D = 1, 3, 16, all four kernel kinds, VFE and DTC, test points on pseudo-inputs and training inputs included) the largest deviations are 4.0e-14 (mean),
+ * 2.9e-14 (covariance), 1.4e-13 (held-out logpdf, relative) and 1.5e-13 (samples); the single path on the same tables: 4.3e-14, 3.0e-14, 1.3e-14, 3.7e-13.
+ * The compiler's report for gfx950 (VGPR / AGPR / LDS / scratch): vfe_predict_kernel<false, true> 155 / 0 / 143 360 B / 0 (<false> 150 / 0 / 143 360 / 0 and
+ * <true> 256 / 0 / 147 968 / 0, both as before); vfe_jcov_kernel 145 / 32 / 33 280 B / 0; batch_jfact_kernel 232 / 0 / 37 888 B / 0.
+ * GPMI355_VFE_JOINT_BATCH_MAX_N / _MAX_NS: by the rule of the other batch thresholds — the largest values of the measured sweep at which one call beat the loop
+ * of gp_vfe_fit + gp_vfe_predict(what = 5) + gp_vfe_logpdf + gp_vfe_rand + gp_vfe_free in every cell with nb >= 8 (tools/vfe_joint_batch_profile.py --samples 3
+ * --min-s 0.02, SE, D = 3, what = 29 with 4 samples, scalar Σy*, M = 16, 64, 128 × n = 1 024 … 262 144 × nb = 1, 8, 64, 512 × ns = 64, 256, 1 024, shared and
+ * per-problem (x, y, xs), each cell checked against the loop's values; four processes, profiles/r39/vfe_joint_batch_profile_*.json).  330 of the 360 cells
+ * were run.  NOT run: nb = 512 at n = 65 536 and 262 144 for M = 16 and 64 (both modes) and for M = 128 with per-problem data — the loop alone takes 6.5 s a
+ * repetition there; nb = 512 at those n was measured at M = 128 with shared data only.  The call won all 240 measured cells with nb >= 8, so the macros are the
+ * largest n and ns swept.  The closest cells are those with per-problem data at M = 128, n = 262 144, where packing and uploading the inputs is most of the call:
+ * ns = 64: nb = 8 10.04 ms (10.00 – 10.04) against 23.60 ms (23.59 – 23.62), nb = 64 61.3 against 185.6 ms; ns = 1 024: nb = 8 19.2 against 107.6 ms, nb = 64
+ * 106 against 861 ms; shared data, ns = 1 024, nb = 512: 470 against 6 981 ms.  Up to n = 16 384 the call is 8.4 (M = 128, n = 16 384, nb = 8, per-problem data, 64 test points:
+ * 1.62 against 13.6 ms) to 445 (M = 16, n = 1 024, nb = 512, shared, 64 test points: 1.94 against 864 ms) times faster: the loop pays four whole-chip launches
+ * and the M × ns solves from global memory per problem, 1.7 ms with 64 test points and 12.7 ms with 1 024.  A single problem (nb = 1) wins everywhere but at
+ * M = 128, n = 262 144 with 64 test points (2.98 against 2.80 ms, both modes: one workgroup runs the M×M side); the rule does not count it.  More than 1 024
+ * test points were not measured, and ONE workgroup factors a problem's joint slice, so ns_b is held to what was. / GPMI_VFE_JOINT_BATCH_MAX_NS, read per call, override the macros for measurements; MAX_NS up to 2 048.) */
+#define GPMI355_VFE_JOINT_BATCH_MAX_N 262144
+#define GPMI355_VFE_JOINT_BATCH_MAX_NS 1024
+int32_t gp_vfe_joint_batch(gp_ctx* ctx, int32_t nb, const gp_kernel* k, int32_t nx, const gp_points* x, int32_t nz, const gp_points* z,
+                           const gp_noise* noise, const double* jitter, const void* const* mean_or_null, int32_t ny, const void* const* y,
+                           const int32_t* approx, int32_t nxs, const gp_points* xs, const void* const* prior_mean_xs_or_null,
+                           const gp_noise* noise_xs_or_null, int32_t what, void* const* mean_out_or_null, void* const* cov_out_or_null,
+                           const void* const* ys_or_null, void* hlogpdf_out_or_null, int32_t nsamp, const void* const* xi_or_null,
+                           void* const* samples_out_or_null, void* objective_out_or_null, int32_t* info_out, int32_t* info_joint_out_or_null);
 
 /* ---- device-level building blocks ------------------------------------------------------------ */
 /* The operations the in-library multi-device driver composes (csrc/multi.hip calls the same engine functions), exposed on DEVICE
