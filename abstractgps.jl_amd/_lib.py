@@ -92,6 +92,8 @@ PROTOTYPES = {
     "gp_logpdf_grad_cols_sum": (i32, [vp, PS, PP, PN, vp, vp, i64, i32, vp, C.POINTER(dbl), vp, vp, vp]),
     "gp_loo": (i32, [vp, PK, PP, PN, vp, vp, vp, vp, vp, vp]),
     "gp_loo_sum": (i32, [vp, PS, PP, PN, vp, vp, vp, vp, vp, vp]),
+    "gp_kfold": (i32, [vp, PK, PP, PN, vp, vp, C.POINTER(i32), i32, vp, vp, vp, vp]),
+    "gp_kfold_sum": (i32, [vp, PS, PP, PN, vp, vp, C.POINTER(i32), i32, vp, vp, vp, vp]),
     "gp_loo_grad": (i32, [vp, PK, PP, PN, vp, vp, vp, C.POINTER(dbl), C.POINTER(dbl), vp, vp, vp]),
     "gp_loo_grad_sum": (i32, [vp, PS, PP, PN, vp, vp, vp, C.POINTER(dbl), vp, vp, vp]),
     "gp_logpdf_batch": (i32, [vp, i32, PK, i32, PP, PN, C.POINTER(vp), i32, C.POINTER(vp), vp, C.POINTER(i32), C.POINTER(vp)]),
@@ -222,6 +224,11 @@ def batch_grad_max_n() -> int:
 def batch_gradx_max_n() -> int:
     """GPMI355_BATCH_GRADX_MAX_N of include/gpmi355.h: the largest problem gp_logpdf_grad_batch_x hands to its kernels when dx is asked for."""
     return int(re.search(r"#define GPMI355_BATCH_GRADX_MAX_N (\d+)", HEADER.read_text()).group(1))
+
+
+def kfold_max_fold() -> int:
+    """GPMI355_KFOLD_MAX_FOLD of include/gpmi355.h: the largest fold gp_kfold factors."""
+    return int(re.search(r"#define GPMI355_KFOLD_MAX_FOLD (\d+)", HEADER.read_text()).group(1))
 
 
 def batch_loo_max_n() -> int:

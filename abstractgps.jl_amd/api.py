@@ -1272,8 +1272,8 @@ def _objective_and_grad(fx: FiniteGP, y, wrt_x: bool, who: str, call: str) -> tu
 # --------------------------------------------------------------------------------------------
 # leave-one-out cross-validation: gp_loo / gp_loo_grad and their *_sum forms
 # --------------------------------------------------------------------------------------------
-def _loo(fx: FiniteGP, y, who: str):
-    """(L, ℓ, μ, v) of gp_loo / gp_loo_sum for a GP prior and a vector of observations."""
+def _cv_marshal(fx: FiniteGP, y, who: str):
+    """What gp_loo and gp_kfold share: (ctx, dtype, marshal, "" / "_sum", the arguments from the kernel to y) for a GP prior and a vector of observations."""
     y = _check_y(fx, y)
     if y.ndim != 1:
         raise TypeError(f"{who} expects a vector of observations")
@@ -1289,10 +1289,15 @@ def _loo(fx: FiniteGP, y, who: str):
     mean = _mean_vector(f.mean_fn, fx.x, dt)
     mean = None if mean is None else m.arr(mean)
     yv = m.arr(y)
+    return ctx, dt, m, sfx, px.n, (C.byref(kk), C.byref(px), C.byref(nz), m.ptr(mean), yv.ctypes.data)
+
+
+def _loo(fx: FiniteGP, y, who: str):
+    """(L, ℓ, μ, v) of gp_loo / gp_loo_sum for a GP prior and a vector of observations."""
+    ctx, dt, m, sfx, n, args = _cv_marshal(fx, y, who)
     val = np.empty(1, dtype=dt)
-    lp, mu, var = (np.empty(px.n, dtype=dt) for _ in range(3))
-    check(getattr(ctx.lib, "gp_loo" + sfx)(ctx.handle, C.byref(kk), C.byref(px), C.byref(nz), m.ptr(mean), yv.ctypes.data, val.ctypes.data,
-                                           lp.ctypes.data, mu.ctypes.data, var.ctypes.data))
+    lp, mu, var = (np.empty(n, dtype=dt) for _ in range(3))
+    check(getattr(ctx.lib, "gp_loo" + sfx)(ctx.handle, *args, val.ctypes.data, lp.ctypes.data, mu.ctypes.data, var.ctypes.data))
     return val[0], lp, mu, var
 
 
@@ -1425,6 +1430,52 @@ def _objective_and_grad_batch(fxs, ys, wrt_x, on_error: str, marshal):
             if wrt_x:
                 grads[i]["x"] = _dx_shaped(call.dx[j], call.pts[0 if g.nx == 1 else j], g.fxs[j].x)
     return _batch_merge(len(fxs), parts, False, on_error), grads
+
+
+# --------------------------------------------------------------------------------------------
+# K-fold cross-validation from one factorisation: gp_kfold / gp_kfold_sum
+# --------------------------------------------------------------------------------------------
+def _fold_labels(folds, n: int, who: str) -> tuple:
+    """(int32 labels, K) of an integer array of n labels 0..K−1, every label in use and no fold above the library's limit."""
+    folds = np.asarray(folds)
+    if not np.issubdtype(folds.dtype, np.integer):
+        raise TypeError(f"{who}: folds must be an integer array, got {folds.dtype}")
+    if folds.shape != (n,):
+        raise ValueError(f"{who}: folds must hold one label per observation, shape ({n},), got {folds.shape}")
+    if folds.min() < 0:
+        raise ValueError(f"{who}: negative fold label")
+    sizes = np.bincount(folds)
+    if (sizes == 0).any():
+        raise ValueError(f"{who}: empty fold {int(np.flatnonzero(sizes == 0)[0])}: the labels must be 0..K-1, each in use")
+    if sizes.max() > _lib.kfold_max_fold():
+        raise ValueError(f"{who}: fold {int(sizes.argmax())} holds {int(sizes.max())} observations, the limit is {_lib.kfold_max_fold()}")
+    return np.ascontiguousarray(folds, dtype=np.int32), len(sizes)
+
+
+def _kfold(fx: FiniteGP, y, folds, who: str, want_lp: bool, want_pred: bool):
+    """(value, per-fold lp, μ, v) of gp_kfold / gp_kfold_sum; the arrays that are not wanted are None and not computed."""
+    lab, K = _fold_labels(folds, len(_check_y(fx, y)), who)  # refused before a context exists
+    ctx, dt, m, sfx, n, args = _cv_marshal(fx, y, who)
+    val = np.empty(1, dtype=dt)
+    lp = np.empty(K, dtype=dt) if want_lp else None
+    mu, var = (np.empty(n, dtype=dt) if want_pred else None for _ in range(2))
+    check(getattr(ctx.lib, "gp_kfold" + sfx)(ctx.handle, *args, lab.ctypes.data_as(C.POINTER(C.c_int32)), K, val.ctypes.data, m.ptr(lp), m.ptr(mu),
+                                             m.ptr(var)))
+    return val[0], lp, mu, var
+
+
+def kfold_logpdf(fx: FiniteGP, y, folds, pointwise: bool = False):
+    """The K-fold log predictive density Σ_F log p(y_F | y_−F) of fx at y from ONE fit (gp_kfold); with pointwise, the K per-fold terms instead.
+    folds: n integer labels 0..K−1, any subsets, each non-empty and of at most GPMI355_KFOLD_MAX_FOLD observations."""
+    val, lp, _, _ = _kfold(fx, y, folds, "kfold_logpdf", bool(pointwise), False)
+    return lp if pointwise else val
+
+
+def kfold_mean_and_var(fx: FiniteGP, y, folds) -> tuple:
+    """K-fold predictions from ONE fit (gp_kfold): (μ, v) with μ_i, v_i the predictive mean and marginal variance of y_i — its own observation noise
+    included — given the observations of every other fold.  folds as in kfold_logpdf."""
+    _, _, mu, var = _kfold(fx, y, folds, "kfold_mean_and_var", False, True)
+    return mu, var
 
 
 # --------------------------------------------------------------------------------------------

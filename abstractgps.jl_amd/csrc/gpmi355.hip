@@ -7,6 +7,7 @@
 // Mirrors, on the device, reference src/finite_gp_projection.jl:306-311 and
 // src/exact_gpr_posterior.jl:29-35, 60-90 (see include/gpmi355.h for the per-entry citations).
 #include "kernels.hpp"  // includes engine.hpp (shared structs, registry, error helpers)
+#include "kfold.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -1918,6 +1919,81 @@ static int32_t loo_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const
     return 0;
 }
 
+// gp_kfold / gp_kfold_sum: one fit, W = L⁻ᵀ, then every fold's P_FF = W_F W_Fᵀ in one launch and one workgroup per fold for the rest (kfold.hpp).
+// The host sorts each fold's indices (ascending by construction), lays the folds' fp64 blocks out one after the other — leading dimension |F| rounded up
+// to 64 plus a de-aliasing pad, 64 scratch rows behind each — and lists the lower 64×64 tiles of all folds.  Every entry of a block that a kernel reads
+// is written by a kernel first.  One upload of the tables, one download of [lp | mean | var | info].
+template <typename T>
+static int32_t kfold_impl(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, const int32_t* fold,
+                          int32_t nfolds, const std::vector<int32_t>& cnt, void* value_out, const LooOut& out, const KSum* ks) {
+    const long n = x->n;
+    std::vector<KfFold> fo((size_t)nfolds);
+    std::vector<KfTile> tiles;
+    size_t ptot = 0;
+    int32_t off = 0;
+    for (int32_t f = 0; f < nfolds; ++f) {
+        const int32_t npad = (int32_t)round_up(cnt[f], 64), ldp = npad + 8;
+        fo[f].poff = (int64_t)ptot; fo[f].off = off; fo[f].cnt = cnt[f]; fo[f].npad = npad; fo[f].ldp = ldp;
+        ptot += (size_t)(npad + 64) * ldp;
+        off += cnt[f];
+        for (int32_t I = 0; I < npad / 64; ++I)
+            for (int32_t J = 0; J <= I; ++J) tiles.push_back(KfTile{f, I, J, 0});
+    }
+    const size_t fo_b = sizeof(KfFold) * fo.size(), tl_b = sizeof(KfTile) * tiles.size(), ix_b = sizeof(int32_t) * (size_t)n;
+    std::vector<char> tab(fo_b + tl_b + ix_b);
+    memcpy(tab.data(), fo.data(), fo_b);
+    memcpy(tab.data() + fo_b, tiles.data(), tl_b);
+    {
+        int32_t* ix = (int32_t*)(tab.data() + fo_b + tl_b);
+        std::vector<int32_t> pos((size_t)nfolds);
+        for (int32_t f = 0; f < nfolds; ++f) pos[f] = fo[f].off;
+        for (long i = 0; i < n; ++i) ix[pos[fold[i]]++] = (int32_t)i;
+    }
+    DevBufs bufs(c);
+    TempPost<T> tp(c);
+    RC(tp.fit(k, x, noise, mean, y, n, 1, nullptr, ks));
+    const gp_post& post = tp.post;
+    SkScope sk(c);
+    const long np = post.np, ld = post.ld;
+    hipStream_t s = c->sm;
+    const size_t nres = (size_t)nfolds + 2 * (size_t)n;  // doubles: lp, mean, var; then one int32 per fold
+    std::vector<double> res_h(nres + ((size_t)nfolds + 1) / 2);
+    const int32_t rc = run_drained(c, [&]() -> int32_t {
+        void *W_v = 0, *tab_v = 0, *P_v = 0, *y_v = 0, *res_v = 0;
+        RC(bufs.get(sizeof(T) * (size_t)(np + 128) * ld, &W_v));
+        RC(factor_inv_t<T>(c, s, bufs, post, (T*)W_v));
+        RC(bufs.get(tab.size(), &tab_v));
+        RC(bufs.get(sizeof(double) * ptot, &P_v));
+        RC(bufs.get(sizeof(T) * (size_t)n, &y_v));
+        RC(bufs.get(sizeof(double) * res_h.size(), &res_v));
+        HIPCHK(hipMemcpyAsync(tab_v, tab.data(), tab.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(y_v, y, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, s));
+        const KfFold* fo_d = (const KfFold*)tab_v;
+        const KfTile* tl_d = (const KfTile*)((const char*)tab_v + fo_b);
+        const int32_t* ix_d = (const int32_t*)((const char*)tab_v + fo_b + tl_b);
+        double* res = (double*)res_v;
+        hipLaunchKernelGGL(kfold_gram_kernel<T>, dim3((unsigned)tiles.size()), dim3(256), 0, s, (const T*)W_v, ld, (int)np, tl_d, fo_d, ix_d, (double*)P_v);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(kfold_fact_kernel<T>, dim3((unsigned)nfolds), dim3(KF_NT), 0, s, fo_d, ix_d, (double*)P_v, (const T*)post.alpha, (const T*)y_v,
+                           out.mean ? 1 : 0, out.var ? 1 : 0, res, res + nfolds, res + nfolds + n, (int32_t*)(res + nres));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(res_h.data(), res_v, sizeof(double) * res_h.size(), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    });
+    if (rc != 0) return rc;
+    const int32_t* info = (const int32_t*)(res_h.data() + nres);
+    for (int32_t f = 0; f < nfolds; ++f)
+        if (info[f] != 0) return set_err_text((int32_t)n + 1 + f, "gp_kfold: the block of C⁻¹ of fold " + std::to_string(f) + " is not positive definite");
+    double sum = 0;
+    for (int32_t f = 0; f < nfolds; ++f) sum += res_h[f];  // in fold order
+    *(T*)value_out = (T)sum;
+    for (int32_t f = 0; f < nfolds && out.lp; ++f) ((T*)out.lp)[f] = (T)res_h[f];
+    for (long i = 0; i < n && out.mean; ++i) ((T*)out.mean)[i] = (T)res_h[(size_t)nfolds + i];
+    for (long i = 0; i < n && out.var; ++i) ((T*)out.var)[i] = (T)res_h[(size_t)nfolds + n + i];
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Value + gradient of an objective of one exact fit (include/gpmi355.h gp_logpdf_grad, gp_logpdf_grad_cols, gp_loo_grad and their *_sum forms): every
 // gradient is a contraction Σ_ij (a_i a_j + Ci_ij) ∂K_ij of a weight matrix Ci (lower, row-major) and a vector a with the kernel's derivatives.  The
@@ -2980,6 +3056,37 @@ static int32_t loo_any(gp_ctx* c, const K* k, const gp_points* x, const gp_noise
     return by_dtype(rk.k.dtype, [&](auto t) { return loo_impl<decltype(t)>(c, &rk.k, x, noise, mean, y, value_out, out, rk.sum()); });
 }
 
+// gp_kfold / gp_kfold_sum: argument numbers as loo_any, then fold (7) and nfolds (8) and the outputs behind them.  The fold table is checked here,
+// before any device work.
+template <class K>
+static int32_t kfold_any(gp_ctx* c, const K* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, const int32_t* fold,
+                         int32_t nfolds, void* value_out, void* lp_out, void* mean_out, void* var_out) {
+    Guard gd(c);
+    if (!gd.ok) return set_arg_err(1, "not a live gp_ctx");
+    ResolvedKernel rk;
+    RC(check_fit_args(k, x, noise, rk));
+    if (!y) return set_arg_err(6, "y is NULL");
+    if (!fold) return set_arg_err(7, "fold is NULL");
+    if (nfolds < 1) return set_arg_err(8, "nfolds must be >= 1");
+    if (nfolds > x->n) return set_arg_err(8, "nfolds > n: some fold is empty");
+    if (!value_out) return set_arg_err(9, "value_out is NULL");
+    std::vector<int32_t> cnt((size_t)nfolds, 0);
+    for (int64_t i = 0; i < x->n; ++i) {
+        if (fold[i] < 0 || fold[i] >= nfolds) return set_arg_err(7, "fold id out of range: every fold[i] must be in [0, nfolds)");
+        ++cnt[fold[i]];
+    }
+    for (int32_t f = 0; f < nfolds; ++f) {
+        if (cnt[f] == 0) return set_arg_err(7, "empty fold: every id in [0, nfolds) must occur");
+        if (cnt[f] > GPMI355_KFOLD_MAX_FOLD) return set_arg_err(7, "fold above GPMI355_KFOLD_MAX_FOLD (1024) observations");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    LooOut out;
+    out.lp = lp_out; out.mean = mean_out; out.var = var_out;
+    return by_dtype(rk.k.dtype, [&](auto t) {
+        return kfold_impl<decltype(t)>(c, &rk.k, x, noise, mean, y, fold, nfolds, cnt, value_out, out, rk.sum());
+    });
+}
+
 // logdet(cov(fx)) and sqmahal(fx, Y) — the two terms logpdf adds up (src/finite_gp_projection.jl:306-311): `logdetcov` is not in
 // the reference's API by that name but `sqmahal` is (src/finite_gp_projection.jl:313-326), and `gradlogpdf` (:328-337) is −α of
 // the posterior fit.  Y may be NULL (ncols ignored): logdet only.  Outputs in the kernel's dtype; either may be NULL.
@@ -3076,6 +3183,14 @@ int32_t gp_loo(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise
 int32_t gp_loo_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, void* value_out, void* lp_out,
                    void* mean_out, void* var_out) {
     return loo_any(c, k, x, noise, mean, y, value_out, lp_out, mean_out, var_out);
+}
+int32_t gp_kfold(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, const int32_t* fold,
+                 int32_t nfolds, void* value_out, void* lp_out, void* mean_out, void* var_out) {
+    return kfold_any(c, k, x, noise, mean, y, fold, nfolds, value_out, lp_out, mean_out, var_out);
+}
+int32_t gp_kfold_sum(gp_ctx* c, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, const int32_t* fold,
+                     int32_t nfolds, void* value_out, void* lp_out, void* mean_out, void* var_out) {
+    return kfold_any(c, k, x, noise, mean, y, fold, nfolds, value_out, lp_out, mean_out, var_out);
 }
 int32_t gp_loo_grad(gp_ctx* c, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean, const void* y, void* value_out,
                     double* dvar, double* dscale, void* dnoise, void* dy, void* dx) {

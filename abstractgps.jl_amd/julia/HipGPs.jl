@@ -28,7 +28,7 @@ using KernelFunctions: SqExponentialKernel, Matern12Kernel, ExponentialKernel, M
 using LinearAlgebra, FillArrays, Statistics, StatsBase, Distributions, Random
 using ChainRulesCore
 
-export HipGP, HipPosteriorGP, HipColumnsPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, loo_mean_and_var, loo_logpdf, loo_logpdf_and_grad, loo_logpdf_batch, loo_mean_and_var_batch, loo_logpdf_and_grad_batch, posterior_columns, logpdf_and_grad_columns, elbo_and_grad, HipApproxColumnsPosteriorGP, elbo_columns, approx_log_evidence_columns, elbo_and_grad_columns, objective_grad, columns_data, logpdf_batch, mean_and_var_batch, mean_and_var_grad_batch, joint_batch, mean_and_cov_batch, logpdf_heldout_batch, rand_batch, logpdf_and_grad_batch, BatchPosDefException
+export HipGP, HipPosteriorGP, HipColumnsPosteriorGP, HipApproxPosteriorGP, HipContext, logpdf_and_grad, loo_mean_and_var, loo_logpdf, loo_logpdf_and_grad, loo_logpdf_batch, loo_mean_and_var_batch, loo_logpdf_and_grad_batch, kfold_logpdf, kfold_mean_and_var, posterior_columns, logpdf_and_grad_columns, elbo_and_grad, HipApproxColumnsPosteriorGP, elbo_columns, approx_log_evidence_columns, elbo_and_grad_columns, objective_grad, columns_data, logpdf_batch, mean_and_var_batch, mean_and_var_grad_batch, joint_batch, mean_and_cov_batch, logpdf_heldout_batch, rand_batch, logpdf_and_grad_batch, BatchPosDefException
 
 const libgpmi355 = get(ENV, "GPMI355_LIB", joinpath(@__DIR__, "..", "csrc", "libgpmi355.so"))
 
@@ -1000,6 +1000,47 @@ end
 loo_mean_and_var(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}) = loo_terms(fx, y)[3:4]
 function loo_logpdf(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}; pointwise::Bool=false)
     r = loo_terms(fx, y)
+    return pointwise ? r[2] : r[1]
+end
+# ---- K-fold cross-validation from one factorisation: gp_kfold / gp_kfold_sum ----------------------------------------------------------
+# kfold_terms: (Σ_F lp_F, lp, μ, v) from ONE fit — lp_F = log p(y_F | y_−F); μ_i, v_i the predictive mean and marginal variance of y_i (its own
+# noise included) given the observations of every other fold.  folds: n labels 1..K (Julia's numbering; the library's are 0..K−1), any subsets,
+# each non-empty and of at most GPMI355_KFOLD_MAX_FOLD = 1024 observations.
+function kfold_terms(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}, folds::AbstractVector{<:Integer})
+    a = marshal(fx, eltype(y))
+    a === nothing && throw(ArgumentError("kernel / noise form is not accelerated"))
+    T = a.T
+    yv = Vector{T}(y)
+    n = length(yv)
+    length(folds) == n || throw(ArgumentError("folds must hold one label per observation"))
+    minimum(folds) >= 1 || throw(ArgumentError("fold labels are 1..K"))
+    K = Int(maximum(folds))
+    sizes = zeros(Int, K)
+    for f in folds
+        sizes[f] += 1
+    end
+    all(>(0), sizes) || throw(ArgumentError("empty fold $(findfirst(==(0), sizes)): the labels must be 1..K, each in use"))
+    maximum(sizes) <= 1024 || throw(ArgumentError("fold $(argmax(sizes)) holds $(maximum(sizes)) observations, the limit is 1024"))
+    lab = Vector{Int32}(folds .- 1)
+    val = Ref{T}(zero(T))
+    lp = Vector{T}(undef, K); mu = Vector{T}(undef, n); v = Vector{T}(undef, n)
+    mptr = a.m === nothing ? C_NULL : pointer(a.m)
+    GC.@preserve a yv lab lp mu v begin
+        if haskey(a, :ks)
+            check(ccall((:gp_kfold_sum, libgpmi355), Int32,
+                (Ptr{Cvoid}, Ref{CKSum}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Int32, Ref{T}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                fx.f.ctx.handle, a.ks, a.cx, a.cn, mptr, yv, lab, Int32(K), val, lp, mu, v))
+        else
+            check(ccall((:gp_kfold, libgpmi355), Int32,
+                (Ptr{Cvoid}, Ref{CKernel}, Ref{CPoints}, Ref{CNoise}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Int32, Ref{T}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                fx.f.ctx.handle, a.ck, a.cx, a.cn, mptr, yv, lab, Int32(K), val, lp, mu, v))
+        end
+    end
+    return val[], lp, mu, v
+end
+kfold_mean_and_var(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}, folds::AbstractVector{<:Integer}) = kfold_terms(fx, y, folds)[3:4]
+function kfold_logpdf(fx::FiniteGP{<:HipGP}, y::AbstractVector{<:Real}, folds::AbstractVector{<:Integer}; pointwise::Bool=false)
+    r = kfold_terms(fx, y, folds)
     return pointwise ? r[2] : r[1]
 end
 # value and gradient of loo_logpdf as a training objective: the named tuple of logpdf_and_grad (of logpdf_and_grad_sum for a composite kernel)

@@ -521,6 +521,33 @@ int32_t gp_loo_grad(gp_ctx* ctx, const gp_kernel* k, const gp_points* x, const g
 int32_t gp_loo_grad_sum(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null, const void* y,
                         void* value_out, double* dtheta_out_or_null, void* dnoise_out_or_null, void* dy_out_or_null, void* dx_out_or_null);
 
+/* ---- K-fold cross-validation from one factorisation ---------------------------------------------------------------------------------- */
+/* How well f(x, Σy) predicts each fold of observations from all the other folds, without K refits.  fold[i] ∈ [0, nfolds) is the fold of
+ * observation i: any subsets, not necessarily contiguous or equal in size; every fold non-empty and of at most GPMI355_KFOLD_MAX_FOLD observations.
+ * With P = C⁻¹, α = P(y − m) and a fold F:
+ *   y_F | y_−F ~ N(y_F − P_FF⁻¹ α_F, P_FF⁻¹)
+ *   lp_out[f]    = log p(y_F | y_−F) = −½ α_Fᵀ P_FF⁻¹ α_F + ½ logdet P_FF − ½|F| log 2π          (nfolds entries)
+ *   value_out[0] = Σ_f lp_out[f], added in fold order
+ *   mean_out[i], var_out[i]: the predictive mean and marginal variance of y_i given the other folds, the noise of observation i included
+ *                            (n entries each, in the caller's order)
+ * for any noise kind, a dense Σy included; outputs in the kernel's dtype; any of the three arrays may be NULL.  Two identities: singleton folds
+ * (fold[i] = i) are gp_loo; one fold of everything is the prior — lp_out[0] = logpdf(f(x, Σy), y), mean_out = m, var_out = diag C.
+ * One fit and W = L⁻ᵀ (as gp_loo), then [P_FF]_ij = Σ_{k ≥ max(i,j)} W_ik W_jk for all folds in one launch (kfold_gram_kernel: lower 64×64 tiles of gathered
+ * rows on the fp64 MFMA) and one workgroup per fold (kfold_fact_kernel: blocked Cholesky P_FF = R Rᵀ, u = R⁻¹α_F, r = R⁻ᵀu, lp = −½‖u‖² + Σ log R_ii − ½|F| log 2π,
+ * mean = y − r and, when var_out is given, R⁻¹ in place and var_i = Σ_{k ≥ i} (R⁻¹)_ki²): 2n³/3 flops for the fit and the inversion against the K·n³/3 of K refits, plus
+ * Σ_F (n|F|² + |F|³) for the folds.  fp64 arithmetic whatever the dtype, sums in a fixed order, no atomics: a fold's results depend on n and its index set alone.
+ * GPMI355_KFOLD_MAX_FOLD is the size one workgroup factors (as GPMI355_BATCH_JOINT_MAX_NS); larger folds through the engine's blocked Cholesky, the gradient
+ * of the objective and a batched form are not provided.
+ * Argument numbers as gp_loo up to y (6), then fold (7), nfolds (8), value_out (9); a fold id out of range, an empty fold, a fold above the limit
+ * and nfolds < 1 are refused with a reason before any device work.  A failed factorisation returns the LAPACK info (1..n) and writes nothing; a fold
+ * f whose P_FF does not factor — C⁻¹ has lost definiteness to rounding — returns n + 1 + f and writes nothing.  On a multi-device ctx the calls run
+ * on the single-device engine of the ctx's first device, as gp_loo does. */
+#define GPMI355_KFOLD_MAX_FOLD 1024
+int32_t gp_kfold(gp_ctx* ctx, const gp_kernel* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null, const void* y,
+                 const int32_t* fold, int32_t nfolds, void* value_out, void* lp_out_or_null, void* mean_out_or_null, void* var_out_or_null);
+int32_t gp_kfold_sum(gp_ctx* ctx, const gp_ksum* k, const gp_points* x, const gp_noise* noise, const void* mean_or_null, const void* y,
+                     const int32_t* fold, int32_t nfolds, void* value_out, void* lp_out_or_null, void* mean_out_or_null, void* var_out_or_null);
+
 /* ---- many small exact GPs in one call ------------------------------------------------------------------------------------------ */
 /* nb independent problems (k_b, x_b, Σy_b, m_b, y_b), each with its own size n_b: logpdf_out[b] = logpdf(f_b(x_b, Σy_b), y_b)
  * (src/finite_gp_projection.jl:306-311, once per problem — what a sampler over hyper-parameters, a multi-start optimiser, a grid search or a
